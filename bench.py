@@ -10,14 +10,20 @@ deep).  `value` is the throughput of the K timed steps; `single_stream` reports 
 latency) next to it, and the roofline object is measured on one batch running alone.  Multi-GPU: one process per GPU,
 batches sharded with no data-path collective (weak scaling), barrier + synchronize on both sides, max over ranks.
 
+A plain run does only what `value` needs: set-up, W warm-up steps, the K timed steps, the JSON line.  Everything else -- the parity spot checks
+against the oracle, the steady-state and single-call figures, the roofline, the secondary legs (product, verifyBatch, sign, aggregation, MSM,
+configs[3], one-process multi-GPU) and the CPU baselines -- runs only with --full.  --dump-outputs DIR writes the outputs of the last timed step
+(DIR/pairings.npy, see dump_outputs) so that two builds can be compared output for output on the same seeded inputs.
+
 Prints ONE JSON line (see DESIGN.md section 6 for the field definitions):
   value        pairings/s, whole job
-  roofline     dominant kernel (nbls_vm_kernel) against the gfx950 integer-multiplier issue rate:
+  ms_per_step  milliseconds per timed step (the K timed steps' wall time / K)
+  roofline     (--full) dominant kernel (nbls_vm_kernel) against the gfx950 integer-multiplier issue rate:
                achieved = algorithmic 32x32 multiply-adds per second (Fp multiplications of the
                reference algorithm x 300 MAD32) from HIP-event kernel durations measured in this run;
                peak = 256 CU x 64 lanes/clk (one 32x32->64 multiply-add per lane per 4 clocks per SIMD, measured with
                tools/ubench/int_rates.hip) x 2.4 GHz
-  cpu_baseline oracle/ (C restatement of the reference algorithm) on the host cores, bounded sample, rank 0, N=1 only
+  cpu_baseline (--full) oracle/ (C restatement of the reference algorithm) on the host cores, bounded sample, rank 0, N=1 only
 """
 import argparse
 import hashlib
@@ -80,6 +86,23 @@ def synth_stream(eng, oracle, n, seed=0x6e626c73, first=0, check=(0, 1, -1)):
     return G1, G2
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, name, d_out, n):
+    """--dump-outputs: the n pairings a step returned (576-byte Fp12 values, twelve 48-byte Fp coefficients each) as DIR/<name>.npy, float32 of shape (n, 576), one exact
+    float per output byte.  A batch larger than DUMP_MAX_BYTES allows is sampled: a fixed, seeded set of rows in index order, their indices in DIR/<name>_rows.npy (float64)."""
+    import numpy as np
+    a = d_out[:576 * n].cpu().numpy().reshape(n, 576)
+    rows = (DUMP_MAX_BYTES - 4096) // (576 * 4 + 8)      # room for the row indices and the two .npy headers
+    os.makedirs(dirname, exist_ok=True)
+    if n > rows:
+        idx = np.sort(np.random.default_rng(0x6e626c73).choice(n, rows, replace=False))
+        a = a[idx]
+        np.save(os.path.join(dirname, name + '_rows.npy'), idx.astype(np.float64))
+    np.save(os.path.join(dirname, name + '.npy'), a.astype(np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -100,6 +123,8 @@ def main():
     ap.add_argument('--mark-timed-region', action='store_true', help='bracket the timed steps with two tiny torch fill kernels, so that a rocprofv3 kernel trace of the run shows where the timed region starts and ends (tools/profile_round3.sh)')
     ap.add_argument('--config3-pairings', type=int, default=1 << 20, help='independent pairings of the BASELINE configs[3] leg, sharded over the ranks, ONE call per rank (1M over 8 GPUs = 131,072 per rank); 0 disables')
     ap.add_argument('--dry-launch', action='store_true', help='launch check without a GPU: the ranks of --gpus N rendezvous over gloo, all-reduce their ranks and rank 0 prints one JSON line (tests/test_bench_launch.py)')
+    ap.add_argument('--full', action='store_true', help='besides `value`: the oracle parity checks, steady-state and single-call figures, roofline, secondary legs and CPU baselines (the leg options above apply only here)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='after the timed steps, write the pairings of the last timed step to DIR/pairings.npy (float32, one value per output byte; DIR/pairings_rank<r>.npy with several ranks)')
     args = ap.parse_args()
 
     # `python bench.py --gpus N` with no launcher around it: start the N ranks ourselves (one process per GPU under torch.distributed.run, the
@@ -170,7 +195,7 @@ def main():
     pkg = importlib.import_module('noble-bls12-381_amd')
     import oracle_py
     ranks_seen = None
-    if multi:   # a real collective over the job's backend before anything is timed: how many distinct ranks answered (the SCALE record can check that RCCL saw N of them)
+    if multi and args.full:   # a real collective over the job's backend before anything is timed: how many distinct ranks answered (the SCALE record can check that RCCL saw N of them)
         dev_ = 'cpu' if args.dist_backend == 'gloo' else 'cuda'     # gloo gathers host tensors (ranks may share a GPU there)
         mine = torch.tensor([rank], dtype=torch.int32, device=dev_); everyone = torch.empty(world, dtype=torch.int32, device=dev_)
         dist.all_gather_into_tensor(everyone, mine)
@@ -184,7 +209,7 @@ def main():
     eng = pipe.engines[0]
 
     n = args.batch
-    G1, G2 = synth_stream(eng, oracle, n, seed=0x6e626c73, first=rank * n)      # item i of rank r is pair r * n + i of the stream
+    G1, G2 = synth_stream(eng, oracle, n, seed=0x6e626c73, first=rank * n, check=(0, 1, -1) if args.full else ())      # item i of rank r is pair r * n + i of the stream
     d_g1 = torch.frombuffer(bytearray(G1), dtype=torch.uint8).cuda()
     d_g2 = torch.frombuffer(bytearray(G2), dtype=torch.uint8).cuda()
     d_outs = [torch.empty(576 * n, dtype=torch.uint8, device='cuda') for _ in range(D)]
@@ -200,17 +225,20 @@ def main():
 
     # parity spot check inside the bench: first 8 results of every in-flight buffer against the oracle.  The oracle's reference is computed BEFORE the GPU runs (round 5): the
     # device then goes from these calls through the warm-up steps into the timed steps without tens of milliseconds of idling in between (a burst that starts on a chip that has just
-    # dropped to its idle clocks measures the clock ramp, not the engine: tools/ab_bench_depth.sh)
-    ref, _ = oracle.pairing_batch(G1[:96 * 8], G2[:192 * 8], True, False, threads=8)
+    # dropped to its idle clocks measures the clock ramp, not the engine: tools/ab_bench_depth.sh).  A plain run makes the same first call on every context (scratch and code
+    # objects are in place before the warm-up) and leaves the check to --full.
     ref_first = os.environ.get('NBLS_BENCH_REF_FIRST', '1') != '0'
+    if args.full and ref_first:
+        ref, _ = oracle.pairing_batch(G1[:96 * 8], G2[:192 * 8], True, False, threads=8)
     for i in range(D):
         step(i)
     torch.cuda.synchronize()
-    if not ref_first:
-        ref, _ = oracle.pairing_batch(G1[:96 * 8], G2[:192 * 8], True, False, threads=8)
-    heads = torch.stack([o[:576 * 8] for o in d_outs]).cpu().numpy()      # one copy for all in-flight buffers
-    for k in range(D):
-        assert bytes(heads[k].tobytes()) == ref, 'bench parity check failed'
+    if args.full:
+        if not ref_first:
+            ref, _ = oracle.pairing_batch(G1[:96 * 8], G2[:192 * 8], True, False, threads=8)
+        heads = torch.stack([o[:576 * 8] for o in d_outs]).cpu().numpy()      # one copy for all in-flight buffers
+        for k in range(D):
+            assert bytes(heads[k].tobytes()) == ref, 'bench parity check failed'
 
     local_times = []      # this rank's own time of every timed region (the line's `value` uses the maximum over the ranks; the per-rank figures go into `multi_gpu`)
 
@@ -247,6 +275,26 @@ def main():
     # ramp is noise and the second region is skipped.  NBLS_BENCH_PREWARM=0 switches the second region off.
     PREWARM = int(os.environ.get('NBLS_BENCH_PREWARM', str(8 * D)))
     dt = timed_region(args.mark_timed_region)
+    value = n * args.steps * world / dt
+    if args.dump_outputs:      # the pool is fed round-robin: the last timed step used the context before the next one
+        dump_outputs(args.dump_outputs, 'pairings' if world == 1 else 'pairings_rank%d' % rank, d_outs[(pipe.slot - 1) % D], n)
+    head = {
+        'metric': 'pairings/sec', 'value': round(value, 2), 'unit': 'pairings/s', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
+        'ms_per_step': round(dt / args.steps * 1e3, 4), 'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
+        'dtype': 'int64', 'dtype_detail': 'signed 64-bit column accumulators over 14 x 28-bit limbs (v_mad_i64_i32), 381-bit Fp in Montgomery form R = 2^392; results bit-exact', 'data': 'synthetic',
+        'config': {'workload': 'batch of %d independent BLS12-381 pairings per GPU (Miller loop + final exponentiation, inputs pre-validated, bit-exact vs reference), inputs/outputs resident in HBM' % n,
+                   'batch_per_gpu': n, 'sharding': 'independent batches per rank, no collective', 'batches_in_flight': D,
+                   'protocol': '`value` = exactly W warm-up + K timed steps with no other untimed steps in front of them (the round 1-4 protocol)' + ('; the figure after %d further untimed steps is `steady_state`' % PREWARM if args.full else '')},
+        'full': args.full,
+    }
+    if not args.full:
+        if multi:
+            dist.barrier()
+            dist.destroy_process_group()
+        if rank == 0:
+            sys.stdout.flush()
+            print(json.dumps(head), flush=True)
+        return
     dt_steady = None
     if PREWARM > 0 and args.steps <= 64:
         for i in range(PREWARM):
@@ -265,8 +313,6 @@ def main():
     torch.cuda.synchronize()
     dt_serial = (time.perf_counter() - s0) * args.steps / serial_steps     # scaled to args.steps (the figures below divide by it)
     step = step1
-    total = n * args.steps * world
-    value = total / dt
 
     # ---- secondary leg (all N): 2^18-term multi-pairing product with shared final exponentiation, terms sharded over the
     # ranks, ONE all-gather of 576-byte Fp12 partials over RCCL (BASELINE configs[4])
@@ -807,13 +853,8 @@ def main():
             mleg = {'metric': 'G1 multi-scalar multiplication points/sec (255-bit scalars, bucket method)', 'n': nm, 'value': round(nm / mdt, 2), 'ms': round(mdt * 1e3, 3),
                     'host_call_points_per_s': round(nm / hdt, 2), 'note': 'value: points and scalars resident in HBM; host_call: nbls_g1_msm from host buffers incl. PCIe and Python marshalling',
                     'cpu_baseline': {'value': round(1 / cmdt, 2), 'unit': 'points/s', 'cores': 1, 'kind': 'port', 'sample': '%d scalar multiplications + sum on one host thread (oracle/ double-and-add, no bucket method)' % nc}}
-        line = {
-            'metric': 'pairings/sec', 'value': round(value, 2), 'unit': 'pairings/s', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
-            'ms_per_step': round(dt / args.steps * 1e3, 4), 'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
-            'dtype': 'int64', 'dtype_detail': 'signed 64-bit column accumulators over 14 x 28-bit limbs (v_mad_i64_i32), 381-bit Fp in Montgomery form R = 2^392; results bit-exact', 'data': 'synthetic',
-            'config': {'workload': 'batch of %d independent BLS12-381 pairings per GPU (Miller loop + final exponentiation, inputs pre-validated, bit-exact vs reference), inputs/outputs resident in HBM' % n,
-                       'batch_per_gpu': n, 'sharding': 'independent batches per rank, no collective', 'batches_in_flight': D,
-                       'protocol': '`value` = exactly W warm-up + K timed steps with no other untimed steps in front of them (the round 1-4 protocol); the figure after %d further untimed steps is `steady_state`' % PREWARM},
+        line = dict(head)
+        line.update({
             # the scalars a reader of a truncated line needs, before the large nested objects (round-5 review item 4)
             'summary': {'value_pairings_per_s': round(value, 2), 'steady_state_pairings_per_s': round(n * args.steps * world / dt_steady, 2) if dt_steady else None, 'prewarm_steps_of_steady_state': PREWARM if dt_steady else 0,
                         'single_call_ms': round(dt_serial / args.steps * 1e3, 4), 'single_call_roofline_frac': roof['frac'] if roof else None,
@@ -834,7 +875,7 @@ def main():
             'roofline': roof, 'cpu_baseline': cpu, 'facade': facade, 'product': product, 'verify_batch': vbatch if vbatch is not None else vshard, 'verify_batch_sharded': vshard if vbatch is not None else None, 'sign': sleg, 'aggregate': aleg, 'msm': mleg,
             'config3': config3, 'multi_one_process': multi1, 'multi_gpu': multi_gpu,
             'pool': {'depth': D, 'entry_point': 'nbls_pool_pairing_batch_dev (include/nbls.h): `value` is measured through the C ABI pool; noble-bls12-381_amd/pipeline.py only forwards to it'},
-        }
+        })
         out_line = json.dumps(line)
     else:
         out_line = None

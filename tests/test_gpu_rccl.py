@@ -57,7 +57,7 @@ def test_bench_distributed_branches_one_rank():
     run with one rank through --force-dist: the driver's multi-GPU launch executes exactly these lines."""
     import json
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY='0', MASTER_PORT='29537')
-    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--force-dist', '--steps', '4', '--warmup', '1', '--batch', '256', '--inflight', '2', '--verify-batch', '64',
+    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--full', '--force-dist', '--steps', '4', '--warmup', '1', '--batch', '256', '--inflight', '2', '--verify-batch', '64',
            '--product-terms', '256', '--sign-batch', '0', '--msm-points', '0', '--large-batch', '0', '--no-cpu-baseline']
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stdout + out.stderr
@@ -76,7 +76,7 @@ def test_bench_two_ranks_self_launched():
     backend = 'nccl' if torch.cuda.device_count() >= 2 else 'gloo'
     env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
     env['HSA_ENABLE_IPC_MODE_LEGACY'] = '0'
-    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--dist-backend', backend, '--steps', '6', '--warmup', '2', '--batch', '512', '--inflight', '3',
+    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--full', '--gpus', '2', '--dist-backend', backend, '--steps', '6', '--warmup', '2', '--batch', '512', '--inflight', '3',
            '--verify-batch', '128', '--product-terms', '512', '--sign-batch', '0', '--msm-points', '0', '--large-batch', '0', '--no-cpu-baseline']
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]

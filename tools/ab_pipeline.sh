@@ -1,6 +1,6 @@
 # the headline leg (512 steps, twelve contexts) under hardware-queue limits and with / without the chained final exponentiation in the in-flight contexts; then verifyBatch alone
 # in a fresh process (default queue limit) and inside a bench run.  Usage (GPU box): bash tools/ab_pipeline.sh > gpurun_out/ab_pipeline.txt
-B="python bench.py --no-cpu-baseline --product-terms 0 --sign-batch 0 --msm-points 0 --large-batch 0"
+B="python bench.py --full --no-cpu-baseline --product-terms 0 --sign-batch 0 --msm-points 0 --large-batch 0"
 P='import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); v=d.get("verify_batch") or {}; print(d["value"], d["ms_per_step"], d["config"]["batches_in_flight"], "single", d["single_call"]["ms_per_batch"], "verify", v.get("ms"), v.get("single_verify_ms"))'
 for rep in 1 2; do
   for q in 16 22 32; do

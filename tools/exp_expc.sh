@@ -9,4 +9,4 @@ for m in 1000000000 0; do
   python tools/exp_time.py 65536 5 2>&1 | tail -1
 done 2>&1 | tee gpurun_out/r3e/expc_ab.txt
 unset NBLS_EXPC_MIN
-python bench.py --steps 256 --warmup 16 --verify-batch 0 --msm-points 0 --sign-batch 0 --product-terms 0 --no-cpu-baseline 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('inflight', d['value'], 'single', d['single_call']['ms_per_batch'], 'large', d['roofline']['large_batch']['ms_per_call'], d['roofline']['large_batch']['in_flight'])" | tee -a gpurun_out/r3e/expc_ab.txt
+python bench.py --full --steps 256 --warmup 16 --verify-batch 0 --msm-points 0 --sign-batch 0 --product-terms 0 --no-cpu-baseline 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('inflight', d['value'], 'single', d['single_call']['ms_per_batch'], 'large', d['roofline']['large_batch']['ms_per_call'], d['roofline']['large_batch']['in_flight'])"

@@ -3,7 +3,7 @@
 # and their mean latency (SQ_IFETCH_LEVEL / SQ_IFETCH), branches.   Output: gpurun_out/pmc_icache/summary_b*.csv
 export TMPDIR=/tmp NBLS_HALVES_MIN=0
 out=$PWD/gpurun_out/pmc_icache; rm -rf $out; mkdir -p $out
-common="--no-cpu-baseline --verify-batch 0 --product-terms 0 --sign-batch 0 --msm-points 0 --large-batch 0"
+common="--full --no-cpu-baseline --verify-batch 0 --product-terms 0 --sign-batch 0 --msm-points 0 --large-batch 0"
 for b in 4096 65536; do
   i=0
   for set in "SQC_ICACHE_REQ SQC_ICACHE_HITS SQC_ICACHE_MISSES SQC_ICACHE_MISSES_DUPLICATE SQ_WAVES SQ_INSTS_VALU SQ_WAVE_CYCLES" "SQ_IFETCH SQ_IFETCH_LEVEL SQ_INSTS_BRANCH SQ_INSTS_SALU SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES"; do

@@ -10,7 +10,7 @@
 export TMPDIR=/tmp
 export NBLS_HALVES_MIN=0      # kernel traces and counters of kernels running alone: a large call is not split into two overlapping halves here
 out=$PWD/gpurun_out/prof_r2; mkdir -p $out
-common="--no-cpu-baseline --verify-batch 0 --product-terms 0 --sign-batch 0 --msm-points 0 --large-batch 0"
+common="--full --no-cpu-baseline --verify-batch 0 --product-terms 0 --sign-batch 0 --msm-points 0 --large-batch 0"
 stats() {   # <name> <bench args>
   rocprofv3 --kernel-trace --stats --output-format csv -d $out/$1 -- python bench.py $2 $common > $out/$1.log 2>&1
   f=$(find $out/$1 -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp $f $out/kernel_stats_$1.csv
@@ -32,5 +32,5 @@ done
 unset NBLS_HALVES_MIN
 python tools/verify_breakdown.py > $out/verify_breakdown.txt 2>&1
 python tools/verify_breakdown.py 1 > $out/verify_breakdown_n1.txt 2>&1
-python bench.py > $out/bench_default.json 2> $out/bench_default.err
+python bench.py --full > $out/bench_default.json 2> $out/bench_default.err
 ls -la $out/*.csv $out/*.txt $out/*.json

@@ -10,7 +10,7 @@
 #   6. the JSON line of a default bench run and of the driver's arguments                                      -> bench_default.json, bench_driver_args.json
 export TMPDIR=/tmp
 out=$PWD/gpurun_out/prof_r3; rm -rf $out; mkdir -p $out
-common="--no-cpu-baseline --verify-batch 0 --product-terms 0 --sign-batch 0 --msm-points 0 --large-batch 0"
+common="--full --no-cpu-baseline --verify-batch 0 --product-terms 0 --sign-batch 0 --msm-points 0 --large-batch 0"
 stats() {   # <name> <bench args>
   rocprofv3 --kernel-trace --stats --output-format csv -d $out/$1 -- python bench.py $2 $common > $out/$1.log 2>&1
   f=$(find $out/$1 -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp $f $out/kernel_stats_$1.csv
@@ -54,7 +54,7 @@ unset NBLS_HALVES_MIN
 python tools/hbm_traffic.py $out/pmc_b4096.csv $out/pmc_b65536.csv > $out/hbm_traffic.json
 python tools/verify_breakdown.py > $out/verify_breakdown_n65536.txt 2>&1
 python tools/verify_breakdown.py 1 > $out/verify_breakdown_n1.txt 2>&1
-python bench.py > $out/bench_default.json 2> $out/bench_default.err
-python bench.py --gpus 1 --steps 20 --warmup 5 > $out/bench_driver_args.json 2> $out/bench_driver_args.err
+python bench.py --full > $out/bench_default.json 2> $out/bench_default.err
+python bench.py --full --gpus 1 --steps 20 --warmup 5 > $out/bench_driver_args.json 2> $out/bench_driver_args.err
 /opt/rocm/lib/llvm/bin/llvm-readelf --notes noble-bls12-381_amd/libnbls.so 2>/dev/null | grep -E "\.name:|\.vgpr_count|\.sgpr_count|spill_count|\.group_segment_fixed_size" > $out/kernel_resources.txt
 ls -la $out/*.csv $out/*.txt $out/*.json

@@ -8,7 +8,7 @@
 #   4. the JSON line of a default bench run and of the driver's arguments      -> bench_default.json, bench_driver_args.json
 export TMPDIR=/tmp
 out=$PWD/gpurun_out/prof_r4; rm -rf $out; mkdir -p $out
-common="--no-cpu-baseline --verify-batch 0 --product-terms 0 --sign-batch 0 --msm-points 0 --large-batch 0"
+common="--full --no-cpu-baseline --verify-batch 0 --product-terms 0 --sign-batch 0 --msm-points 0 --large-batch 0"
 stats() {   # <name> <bench args>
   rocprofv3 --kernel-trace --stats --output-format csv -d $out/$1 -- python bench.py $2 $common > $out/$1.log 2>&1
   f=$(find $out/$1 -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp $f $out/kernel_stats_$1.csv
@@ -60,7 +60,7 @@ python tools/verify_breakdown.py > $out/verify_breakdown_n65536.txt 2>&1
 python tools/verify_breakdown.py 1 > $out/verify_breakdown_n1.txt 2>&1
 bash tools/verify_timeline.sh 65536 r4_n65536 > /dev/null 2>&1; cp gpurun_out/verify_timeline_r4_n65536/timeline.txt $out/verify_timeline_n65536.txt
 bash tools/verify_timeline.sh 1 r4_n1 > /dev/null 2>&1; cp gpurun_out/verify_timeline_r4_n1/timeline.txt $out/verify_timeline_n1.txt
-python bench.py > $out/bench_default.json 2> $out/bench_default.err
-python bench.py --gpus 1 --steps 20 --warmup 5 > $out/bench_driver_args.json 2> $out/bench_driver_args.err
+python bench.py --full > $out/bench_default.json 2> $out/bench_default.err
+python bench.py --full --gpus 1 --steps 20 --warmup 5 > $out/bench_driver_args.json 2> $out/bench_driver_args.err
 rm -rf $out/b4096 $out/b65536 $out/b4096_inflight12 $out/pmc_b4096 $out/pmc_b65536     # the raw traces stay on the box; the summaries are merged back
 ls -la $out

@@ -9,7 +9,7 @@
 #   5. the JSON line of a default bench run and of the driver's arguments      -> bench_default.json, bench_driver_args.json
 export TMPDIR=/tmp
 out=$PWD/gpurun_out/prof_r5; rm -rf $out; mkdir -p $out
-common="--no-cpu-baseline --verify-batch 0 --product-terms 0 --sign-batch 0 --msm-points 0 --large-batch 0"
+common="--full --no-cpu-baseline --verify-batch 0 --product-terms 0 --sign-batch 0 --msm-points 0 --large-batch 0"
 stats() {   # <name> <bench args>
   rocprofv3 --kernel-trace --stats --output-format csv -d $out/$1 -- python bench.py $2 $common > $out/$1.log 2>&1
   f=$(find $out/$1 -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp $f $out/kernel_stats_$1.csv
@@ -67,7 +67,7 @@ NBLS_VERIFY_PIPE=0 bash tools/verify_timeline.sh 65536 r5_twophase > /dev/null 2
 ( for v in "NBLS_G1_FIXED=0 NBLS_G2_GLS=0" "NBLS_G1_FIXED=1 NBLS_G2_GLS=1"; do env $v python tools/mul_time.py 2>&1 | sed "s/^/$v: /"; done ) > $out/ab_mul.txt 2>&1
 bash tools/clocks_under_load.sh > $out/clocks_under_load.txt 2>&1
 python tools/stress_parity.py > $out/stress_parity.txt 2>&1
-python bench.py > $out/bench_default.json 2> $out/bench_default.err
-python bench.py --gpus 1 --steps 20 --warmup 5 > $out/bench_driver_args.json 2> $out/bench_driver_args.err
+python bench.py --full > $out/bench_default.json 2> $out/bench_default.err
+python bench.py --full --gpus 1 --steps 20 --warmup 5 > $out/bench_driver_args.json 2> $out/bench_driver_args.err
 rm -rf $out/b4096 $out/b65536 $out/b4096_inflight12 $out/pmc_b4096 $out/pmc_b65536     # the raw traces stay on the box; the summaries are merged back
 ls -la $out

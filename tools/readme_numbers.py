@@ -8,7 +8,7 @@ p = os.path.join(ROOT, 'README.md')
 s = open(p).read()
 a = s.index('**Numbers on one MI355X'); b = s.index('What round 6 changed:')
 lb = d['roofline']['large_batch']; vb = d['verify_batch']; sg = d['sign']; fc = d['facade']; cl = lb['in_flight']; ss = d['steady_state']
-new = """**Numbers on one MI355X, measured as the driver measures them** (`python bench.py --gpus 1 --steps 20 --warmup 5`, `profiles/round6_bench_driver_args.json`; that box ran
+new = """**Numbers on one MI355X, measured as the driver measures them** (`python bench.py --full --gpus 1 --steps 20 --warmup 5`, `profiles/round6_bench_driver_args.json`; that box ran
 saturated at %.2f GHz / %d W; the boxes of the pool sustain 2.13 - 2.26 GHz at the same ~1300 W, and saturated figures follow: 21.1 - 23.2 ms for one 65,536-pairing call (`profiles/round6_box_spread.txt`); round 5's driver record in brackets):
 
 | | round 6 | |
@@ -22,7 +22,7 @@ saturated at %.2f GHz / %d W; the boxes of the pool sustain 2.13 - 2.26 GHz at t
 | a single `verify` (C ABI) / `await bls.verify()` / `await bls.sign()` from JavaScript | **%.2f / %.2f / %.2f ms** | [3.68 / 3.59 / 2.90] |
 | `getPublicKey` / `sign`, 8192 keys from host buffers; `sign` with everything resident in HBM | %.2f M keys/s / **%.2f M sigs/s**; %.2f M sigs/s | [5.32 M / 1.74 M; 2.13 M] |
 
-With 512 steps (`python bench.py`, the steady state): %.2f M pairings/s (%d %%). The same box's host: the C restatement of the reference %.1f k pairings/s on %d threads; the
+With 512 steps (`python bench.py --full`, the steady state): %.2f M pairings/s (%d %%). The same box's host: the C restatement of the reference %.1f k pairings/s on %d threads; the
 reference's algorithm in JavaScript BigInt %d pairings/s on one core, %.1f k on all %d.
 
 """ % (sum(cl['sclk_mhz_under_load']) / 2 / 1000, round(sum(cl['package_power_w_under_load']) / 2), d['value'] / 1e6, round(100 * d['roofline']['frac_at_value']), ss['pairings_per_s'] / 1e6,
