@@ -250,16 +250,17 @@ def test_chained_and_separate_final_exponentiation(oracle, golden):
 
 @pytest.mark.gpu
 def test_default_dispatch_thresholds(oracle, golden):
-    """Batch sizes either side of the library's default dispatch thresholds (two halves from 8192 pairs, except the one-full-round window 10,753 .. 12,288),
-    untouched tuning: every pairing byte-equal to the oracle, last item included."""
+    """Batch sizes either side of the library's default dispatch thresholds, untouched tuning: one stream below 16,384 pairs, two halves on two streams from
+    16,384 (NBLS_HALVES_MIN; the one-full-round window 10,753 .. 12,288 lies below it and runs on one stream as well) -- every pairing byte-equal to the oracle,
+    last item included."""
     import os
     pkg = importlib.import_module('noble-bls12-381_amd')
     eng = pkg.Engine(0)
     pairs = golden['pairs']
-    for n in (8191, 8192, 10753, 12289):
+    for n in (8191, 8192, 10753, 12289, 16383, 16384, 16385):
         g1 = b''.join(hx(pairs[(3 * i + n) % len(pairs)]['g1']) for i in range(n)); g2 = b''.join(hx(pairs[(5 * i + 1) % len(pairs)]['g2']) for i in range(n))
         got, _ = eng.pairing_batch(g1, g2, True, False)
-        exp, _ = oracle.pairing_batch(g1, g2, True, False, threads=os.cpu_count() or 16)
+        exp, _ = oracle.pairing_batch(g1, g2, True, False, threads=min(16, os.cpu_count() or 16))
         assert got == exp, n
 
 
