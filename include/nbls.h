@@ -197,6 +197,22 @@ int nbls_verify_batch_msgs_dev(nbls_ctx* ctx, size_t n, const void* d_sig96, con
 int nbls_verify_batch_dev_inputs(nbls_ctx* ctx, size_t n, const void* d_sig96, const void* d_uniform256, const void* d_pk48, int* ok,
                                  int8_t* pk_status /* n, may be NULL */, void* stream);
 
+/* verify(signature_i, message_i, publicKey_i) (index.ts:756-767) for n independent sets, checked together by a random linear combination (no reference counterpart; the
+ * MSM's follow-on).  With secret weights r_i = BE64(SHA-256(seed32 || BE64(i))[0..8]) | 2^63 every set is accepted when
+ *   prod_i e([r_i]pk_i, H(m_i)) * e(-G1, sum_i [r_i]sig_i) = 1
+ * -- n + 1 Miller loops and ONE final exponentiation where n verify calls spend 2n and n.  If some set is invalid the check passes with probability at most 2^-63 over the
+ * weights.  A seed an attacker can predict voids that guarantee: pass NULL (32 bytes from getrandom(2) on every call; NBLS_ENOSUP when the OS gives none -- never a fixed seed)
+ * unless a reproducible test needs its own.  Messages, offsets and the DST as nbls_verify_batch (a DST over 255 bytes is hashed with H2C-OVERSIZE-DST-; NBLS_EINVAL when the
+ * offsets decrease, for n = 0, n > 2^22 or a missing pointer); sigs96 = n compressed signatures, pks48 = n compressed keys.
+ * status[i] (may be NULL) = what the reference's verify(sig_i, m_i, pk_i) does, in its order (key, message, signature, pairing): the key decoder's status if >= 2 (3 outside the
+ * subgroup, 4 no square root), else 10 + the signature decoder's status if >= 2, else 1 for a zero key and 11 for a zero signature (the reference throws "No pairings at point of
+ * Infinity"), else 0 when the set verifies and NBLS_ST_NOT_VERIFIED when it does not.  *all_ok = 1 exactly when every set has status 0.  Where the combined check does not accept
+ * (a set failed to decode, the product is not one, the weighted sum of the signatures is zero) a per-set pass judges every set on its own; with status == NULL the call stops
+ * after the combined check instead and answers *all_ok = 0 (fast reject).  Returns NBLS_OK whatever the sets hold. */
+#define NBLS_ST_NOT_VERIFIED 9
+int nbls_verify_multiple(nbls_ctx* ctx, size_t n, const uint8_t* sigs96, const uint8_t* msgs, const uint32_t* offsets, const uint8_t* pks48, const uint8_t* dst, size_t dst_len,
+                         const uint8_t* seed32 /* NULL: from the OS */, int* all_ok, int8_t* status /* n, may be NULL */);
+
 /* One rank's share of a verifyBatch spread over several GPUs (one process per GPU): the Miller product of this rank's n
  * (key, message) pairs, times millerLoop(-G, S) on the ONE rank that passes the signature (d_sig96 = NULL elsewhere), WITHOUT the
  * final exponentiation, as 576 wire bytes in device memory.  Ranks all-gather their partials and finish with
@@ -219,10 +235,11 @@ int nbls_miller_product_partial_into(nbls_ctx* ctx, size_t n, const uint8_t* g1_
 int nbls_verify_batch_partial_into(nbls_ctx* ctx, size_t n, const uint8_t* sig96 /* or NULL */, const uint8_t* msgs, const uint32_t* offsets, const uint8_t* pk48,
                                    const uint8_t* dst, size_t dst_len, void* d_dst576, int* zero_flag, int8_t* pk_status /* n, may be NULL */);
 const char* nbls_config_describe(void);   /* "NBLS_X=value(env|default) ...": every environment switch the library has read so far and the value in force -- print it next to an A/B result */
-/* 4 (round 6): nbls_hw_queues, NBLS_TUNE_WIDE_MAX, NBLS_TUNE_H2C_NORM_MIN, NBLS_TUNE_INV_WIDE_MAX, NBLS_TUNE_LS_MAX / _LS2_MAX (additions only); the library sets GPU_MAX_HW_QUEUES = 22 at load when the variable is unset (see nbls_pool_init below).
+/* 5: nbls_verify_multiple, NBLS_ST_NOT_VERIFIED, scratch slots 20 .. 43 (additions only).
+   4 (round 6): nbls_hw_queues, NBLS_TUNE_WIDE_MAX, NBLS_TUNE_H2C_NORM_MIN, NBLS_TUNE_INV_WIDE_MAX, NBLS_TUNE_LS_MAX / _LS2_MAX (additions only); the library sets GPU_MAX_HW_QUEUES = 22 at load when the variable is unset (see nbls_pool_init below).
    3 (round 5): nbls_program_kernel, nbls_pool_*, nbls_sign_batch_dev, NBLS_TUNE_VERIFY_* / _SAC_MAX / _PT_LS2_MAX (additions only); nbls_verify_batch_partial_dev writes d_out_fp12 even when it reports a zero point or a decode error
    (contents then meaningless); 2: *_partial take *d_partial as OUT only, *_partial_into added, nbls_tower_op_batch, nbls_verify_batch_msgs_dev.  The bindings check it at load. */
-#define NBLS_ABI_VERSION 4
+#define NBLS_ABI_VERSION 5
 int nbls_abi_version(void);
 int nbls_context_device(nbls_ctx* ctx);
 

@@ -29,6 +29,9 @@ extern "C" int nbls_g1_wide_combine_launch(const void* S, int nwin, int shift, v
 extern "C" int nbls_fp_inv_launch(unsigned n, const void* in, void* out, void* stream);
 extern "C" int nbls_flag_compact_launch(unsigned n, const void* flags, void* list, void* count, void* stream);
 extern "C" int nbls_xmd_launch(unsigned n, const void* msgs, const void* offsets, const void* dst, unsigned dst_len, void* out, unsigned len_in_bytes, void* bad_flag, void* stream);
+extern "C" int nbls_rlc_weights_launch(unsigned n, const void* seed32, void* out, void* stream);   // rlc_kernels.hip
+extern "C" int nbls_rlc_interleave_launch(unsigned n, const void* pk96, const void* neg_g1, const void* h192, const void* sig192, void* g1x, void* g2x, void* stream);
+extern "C" int nbls_rlc_is_one_launch(unsigned n, const void* f576, void* ok, void* stream);
 extern "C" int nbls_msm_keys_launch(unsigned n, unsigned nwin, const void* scalars, void* keys, void* vals, void* stream);
 extern "C" int nbls_msm_decompose_launch(unsigned n, unsigned dims, const void* scalars, void* out, void* stream);
 extern "C" int nbls_msm_sac_launch(unsigned n, const void* scalars, void* out, void* stream);
@@ -78,7 +81,7 @@ struct nbls_ctx {
   uint8_t *F = nullptr, *N = nullptr, *NI = nullptr, *io_g1 = nullptr, *io_g2 = nullptr, *io_f12 = nullptr, *one12 = nullptr;
   uint8_t* T[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // t1..t7 of the final exponentiation, raw Fp12
   // general scratch pool for the codec / hash / sum pipelines (grown on demand)
-  static const int NSB = 20;
+  static const int NSB = 44;   // 0 .. 19: see verify_stage; 20 .. 43: nbls_verify_multiple (pipelines_multi_verify.cpp)
   uint8_t* sb[NSB] = {nullptr}; size_t sb_cap[NSB] = {0};
   // staging buffers of the host-buffer entry points (HostIO): kept between calls -- a hipMalloc / hipFree pair per buffer and call cost more than the copies at small batches
   struct IoBlock { void* p; size_t cap; bool busy; }; std::vector<IoBlock> io_pool; size_t io_pool_bytes = 0;
@@ -278,7 +281,7 @@ int ensure_g1_fixed(nbls_ctx* ctx, hipStream_t s);
 int sign_points(nbls_ctx* ctx, size_t n, const void* d_uniform, void* h, const void* d_keys32, void* d_out192, void* d_status, hipStream_t s);
 bool scalar_is_zero_mod_r(const uint8_t* k32);
 int mul_host(nbls_ctx* ctx, bool g2, size_t n, const uint8_t* pts, const uint8_t* scalars32, uint8_t* out, int8_t* status);
-int dev_msm(nbls_ctx* ctx, bool g2, size_t n, const void* d_pts, const void* d_scalars, unsigned nbits, void* d_out, void* d_status, hipStream_t s);
+int dev_msm(nbls_ctx* ctx, bool g2, size_t n, const void* d_pts, const void* d_scalars, unsigned nbits, void* d_out, void* d_status, hipStream_t s, int slot0 = 0);
 unsigned scalars_bit_length(size_t n, const uint8_t* k32);
 int msm_host(nbls_ctx* ctx, bool g2, size_t n, const uint8_t* pts, const uint8_t* scalars32, uint8_t* out, int8_t* status);
 int dst_on_device(nbls_ctx* ctx, const uint8_t* dst, size_t* dst_len, hipStream_t s, uint8_t** dd);
@@ -291,5 +294,7 @@ bool verify_pipe_enabled();
 bool fp12_wire_is_one(const uint8_t* out);
 int verify_decide(const std::vector<int8_t>& st, size_t n, const uint8_t* out, int* ok, int8_t* pk_status);
 int verify_stage(nbls_ctx* ctx, size_t n, const void* d_sig96, const void* d_uniform, const void* d_pk48, std::vector<int8_t>& st, void* stream);
+int verify_multiple_pipeline(nbls_ctx* ctx, size_t n, const uint8_t* sigs96, const uint8_t* msgs, const uint32_t* offsets, const uint8_t* pks48, const uint8_t* dst, size_t dst_len,
+    const uint8_t* seed32, int* all_ok, int8_t* status);   // pipelines_multi_verify.cpp
 int verify_batch_partial_core(nbls_ctx* ctx, size_t n, const uint8_t* sig96 /* or NULL */, const uint8_t* msgs, const uint32_t* offsets, const uint8_t* pk48,
                                      const uint8_t* dst, size_t dst_len, void* d_dst, void** d_partial, int* zero_flag, int8_t* pk_status);

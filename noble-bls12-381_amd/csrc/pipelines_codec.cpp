@@ -412,9 +412,9 @@ EXPORT int nbls_g2_mul_batch(nbls_ctx* ctx, size_t n, const uint8_t* g2_aff, con
 //   3. sum_b b * B_b per window = sum_t 2^t * T_t with T_t = sum of the buckets whose index has bit t: 12 * 2^11 gathered
 //      points per window, a balanced tree of 11 rounds of pairwise additions (data independent).
 //   4. Horner over t inside every window (one item per window), then acc <- 2^12 * acc + S_w from the top window down.
-// Result: affine wire bytes + status (1 = the sum is the zero point).  nbits bounds the scalars (< 2^nbits), 0 = 256.
+// Result: affine wire bytes + status (1 = the sum is the zero point).  nbits bounds the scalars (< 2^nbits), 0 = 256.  Scratch slots slot0 + 0 .. 9, 11, 13.
 #define MSMCHK(call) do { int e_ = (call); if (e_) { ctx->last_hip = e_; return NBLS_EHIP; } } while (0)
-int dev_msm(nbls_ctx* ctx, bool g2, size_t n, const void* d_pts, const void* d_scalars, unsigned nbits, void* d_out, void* d_status, hipStream_t s) {
+int dev_msm(nbls_ctx* ctx, bool g2, size_t n, const void* d_pts, const void* d_scalars, unsigned nbits, void* d_out, void* d_status, hipStream_t s, int slot0) {
   const size_t a = g2 ? 192 : 96, p = g2 ? 6 * RAW : 3 * RAW;
   const unsigned C = MSM_WINDOW_BITS;
   uint8_t* ident = g2 ? ctx->ident_g2 : ctx->ident_g1;
@@ -430,14 +430,14 @@ int dev_msm(nbls_ctx* ctx, bool g2, size_t n, const void* d_pts, const void* d_s
   const unsigned nwin = (nbits + C - 1) / C;
   const size_t m = n * nwin, nb = (size_t)nwin << C, ng = ((size_t)nwin * C) << (C - 1);
   uint8_t *Pj, *P, *A, *K, *tmp, *Bk, *G, *Gh, *N, *NI, *acc, *cnt, *Ks = nullptr; int r;
-  if (split && (r = need(ctx, 13, (n + 1) * 32, &Ks))) return r;
+  if (split && (r = need(ctx, slot0 + 13, (n + 1) * 32, &Ks))) return r;
   size_t tmp_bytes = 0;
   size_t scan_bytes = 0;
   if (m) { MSMCHK(nbls_msm_sort_launch(nullptr, &tmp_bytes, nullptr, nullptr, nullptr, nullptr, m, 17, s)); MSMCHK(nbls_msm_rank_launch(nullptr, &scan_bytes, m, nullptr, nullptr, nullptr,
       s)); tmp_bytes = std::max(tmp_bytes, scan_bytes); }
-  if ((r = need(ctx, 0, (n + 1) * p, &Pj)) || (r = need(ctx, 1, (m + 1) * p, &P)) || (r = need(ctx, 2, ((size_t)nwin + 1) * p, &A)) || (r = need(ctx, 3, (m + 1) * 24, &K)) ||
-      (r = need(ctx, 4, RAW, &N)) || (r = need(ctx, 5, RAW, &NI)) || (r = need(ctx, 6, tmp_bytes + 16, &tmp)) || (r = need(ctx, 7, nb * p, &Bk)) || (r = need(ctx, 8, ng * p, &G)) ||
-      (r = need(ctx, 9, (ng / 2 + 2) * p, &Gh)) || (r = need(ctx, 11, 64 * 4, &cnt))) return r;
+  if ((r = need(ctx, slot0 + 0, (n + 1) * p, &Pj)) || (r = need(ctx, slot0 + 1, (m + 1) * p, &P)) || (r = need(ctx, slot0 + 2, ((size_t)nwin + 1) * p, &A)) || (r = need(ctx, slot0 + 3, (m + 1) * 24, &K)) ||
+      (r = need(ctx, slot0 + 4, RAW, &N)) || (r = need(ctx, slot0 + 5, RAW, &NI)) || (r = need(ctx, slot0 + 6, tmp_bytes + 16, &tmp)) || (r = need(ctx, slot0 + 7, nb * p, &Bk)) || (r = need(ctx, slot0 + 8, ng * p, &G)) ||
+      (r = need(ctx, slot0 + 9, (ng / 2 + 2) * p, &Gh)) || (r = need(ctx, slot0 + 11, 64 * 4, &cnt))) return r;
   acc = Gh + ng / 2 * p;     // (slot 10 belongs to verifyBatch, which drops the context lock between its stages)
   uint32_t *kin = (uint32_t*)K, *vin = kin + m, *kout = vin + m, *vout = kout + m, *pos = vout + m, *list = pos + m;
   uint32_t* counters = (uint32_t*)cnt;    // [0] longest run, [1 + round] pairs of that round

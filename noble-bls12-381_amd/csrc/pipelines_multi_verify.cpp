@@ -1,0 +1,135 @@
+// pipelines_multi_verify.cpp -- verify(sig_i, m_i, pk_i) (reference index.ts:756-767) for n INDEPENDENT sets, checked together by a random linear combination
+// (the MSM's follow-on).  With secret 64-bit weights r_i (rlc_weights.h) every set is valid when
+//   prod_i e([r_i]pk_i, H(m_i)) * e(-G1, sum_i [r_i]sig_i) = 1:
+// n + 1 Miller loops and ONE final exponentiation where n verify calls spend 2n and n.  An invalid set passes with probability at most 2^-63 over the weights; the weights
+// stop the cancellation that beats a plain sum (sig_a + D, sig_b - D).  Where the combined answer does not count -- some set failed to decode, the product is not one, or the
+// weighted sum of the signatures is the zero point -- and the caller asked for statuses, a per-set pass judges every set on its own: millerLoop(pk_i, H_i) x millerLoop(-G1, sig_i)
+// with the UNWEIGHTED key (P_MILLER_RAW2), n final exponentiations, one byte per set compared with one on the device.
+//
+// One chain as verify_pipeline builds it: the inputs travel as one copy from the page-locked block, nothing is decided on the host before the combined result is read back
+// (with the decoder statuses, in one copy), and the per-set pass is a second chain with a second read-back.
+//   s (the call's stream):  H2D copy -> weights -> fork | expand_message_xmd -> hash-to-G2 (H_i)            | join -> Miller loops of n + 1 pairs -> product -> final exp -> read-back
+//   side2:                  keys: decompress -> [r_i]pk_i (P_G1_MUL64) -> inversion -> affine
+//   side:                   signatures: decompress -> S = sum_i [r_i]sig_i (G2 MSM with 64-bit scalars; dev_msm synchronises its stream once, after the decoding)
+// Scratch slots: chains that run side by side never share one --
+//   s: 9 staged inputs, 8 expand_message_xmd output, 0 .. 6 / 11 / 13 / 18 / 19 hash-to-G2 (dev_hash_to_g2), 20 weights, 21 the decoded points, the pairs and what is read back;
+//   side2: 14 .. 16 / 17 key decompression, 23 / 24 / 25 the ladder's projective points (+ the affine program's unused statuses), norms and their inverses;
+//   side: 26 .. 28 / 29 signature decompression, 30 .. 39 / 41 / 43 the MSM (dev_msm slot0 = 30);
+//   per-set pass (s, after the read-back): 22 the interleaved pairs, the n final exponentiations and the verdict bytes.
+#include "nbls_internal.h"
+#include <cerrno>
+#include <sys/random.h>
+
+static int os_seed(uint8_t* seed) {
+  size_t got = 0;
+  while (got < 32) {
+    const ssize_t k = getrandom(seed + got, 32 - got, 0);
+    if (k < 0) { if (errno == EINTR) continue; return NBLS_ENOSUP; }   // never a fixed seed instead
+    got += (size_t)k;
+  }
+  return NBLS_OK;
+}
+
+int verify_multiple_pipeline(nbls_ctx* ctx, size_t n, const uint8_t* sigs96, const uint8_t* msgs, const uint32_t* offsets, const uint8_t* pks48, const uint8_t* dst, size_t dst_len,
+                             const uint8_t* seed32, int* all_ok, int8_t* status) {
+  uint8_t seed[32];
+  if (seed32) memcpy(seed, seed32, 32);
+  else { const int e = os_seed(seed); if (e) return e; }
+  for (size_t i = 0; i < n; i++) if (offsets[i + 1] < offsets[i]) return NBLS_EINVAL;
+  const size_t total = offsets[n] - offsets[0];
+  uint8_t dst_hash[32];
+  if (dst_len > 255) { Sha256 c; c.update((const uint8_t*)"H2C-OVERSIZE-DST-", 17); c.update(dst, dst_len); c.final(dst_hash); dst = dst_hash; dst_len = 32; }
+  // the staged block: messages | offsets (relative) | DST | keys | signatures | seed
+  const size_t o_off = (total + 15) & ~(size_t)15, o_dst = o_off + (((n + 1) * 4 + 15) & ~(size_t)15), o_pk = o_dst + 256, o_sig = o_pk + ((n * 48 + 15) & ~(size_t)15),
+               o_seed = o_sig + n * 96, in_bytes = o_seed + 32;
+  // slot 21: [r_i]pk_i and -G1 | H_i and S | pk_i | sig_i | result (576) | key statuses | signature statuses | MSM status | bad-offsets word
+  const size_t o_h = (n + 1) * 96, o_pkd = o_h + (n + 1) * 192, o_sgd = o_pkd + n * 96, o_res = o_sgd + n * 192, st_bytes = ((2 * n + 1 + 3) & ~(size_t)3) + 4,
+               back = 576 + st_bytes;
+  LOCKED(ctx);
+  StreamOrder order_(ctx, s);
+  uint8_t *c, *du, *W, *P, *Pj, *N, *NI; int r;
+  if ((r = need(ctx, 9, in_bytes, &c)) || (r = need(ctx, 8, n * 256, &du)) || (r = need(ctx, 20, n * 32, &W)) || (r = need(ctx, 21, o_res + back, &P)) ||
+      (r = need(ctx, 23, n * 3 * RAW + n, &Pj)) || (r = need(ctx, 24, n * RAW, &N)) || (r = need(ctx, 25, n * RAW, &NI)) || (r = ensure_pinned(ctx, in_bytes)) ||
+      (r = ensure_pinned_out(ctx, back)) || (r = ensure_scratch(ctx, n + 1)) || (r = ensure_side(ctx)) || (r = ensure_side2(ctx)))
+    return r;
+  if (!ctx->ev_fork && hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming) != hipSuccess) { ctx->last_hip = (int)hipGetLastError(); return NBLS_EHIP; }
+  uint8_t *RPK = P, *H = P + o_h, *PK = P + o_pkd, *SG = P + o_sgd, *O = P + o_res, *STK = O + 576, *STS = STK + n, *MS = STS + n;
+  uint32_t* d_bad = (uint32_t*)(O + 576 + st_bytes - 4);
+  uint8_t* pin = ctx->pinned;
+  if (total) memcpy(pin, msgs + offsets[0], total);
+  { uint32_t* rel = (uint32_t*)(pin + o_off); for (size_t i = 0; i <= n; i++) rel[i] = offsets[i] - offsets[0]; }
+  memcpy(pin + o_dst, dst, dst_len); memcpy(pin + o_pk, pks48, n * 48); memcpy(pin + o_sig, sigs96, n * 96); memcpy(pin + o_seed, seed, 32);
+  ForkGuard fork_guard;   // from the first asynchronous copy on: an error return waits for every stream of the call
+  HIPCHK(hipMemcpyAsync(c, pin, in_bytes, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemsetAsync(d_bad, 0, 4, s));
+  if (nbls_rlc_weights_launch((unsigned)n, c + o_seed, W, s)) { ctx->last_hip = (int)hipGetLastError(); return NBLS_EHIP; }
+  HIPCHK(hipEventRecord(ctx->ev_fork, s));
+  // signatures (side): PointG2.fromSignature, index.ts:500-530
+  HIPCHK(hipStreamWaitEvent(ctx->side, ctx->ev_fork, 0));
+  if ((r = dev_decompress(ctx, true, n, c + o_sig, SG, STS, ctx->side, 26, 29))) return r;
+  // keys (side2): PointG1.fromHex, index.ts:301-326, then [r_i]pk_i
+  HIPCHK(hipStreamWaitEvent(ctx->side2, ctx->ev_fork, 0));
+  if ((r = dev_decompress(ctx, false, n, c + o_pk, PK, STK, ctx->side2, 14, 17))) return r;
+  if ((r = run(ctx, P_G1_MUL64, n, {B(0, PK, 96), B(2, W, 32), B(3, Pj, 3 * RAW), B(4, N, RAW)}, ctx->side2))) return r;
+  if ((r = run_inv_buf(ctx, n, N, NI, ctx->side2))) return r;
+  if ((r = run(ctx, P_G1_TO_AFFINE, n, {B(3, Pj, 3 * RAW), B(4, NI, RAW), B(2, RPK, 96), B(7, Pj + n * 3 * RAW, 1)}, ctx->side2))) return r;
+  HIPCHK(hipEventRecord(ctx->ev_join2, ctx->side2));
+  // messages (s): expand_message_xmd, PointG2.hashToCurve (index.ts:481-490)
+  { const int e = nbls_xmd_launch((unsigned)n, c, c + o_off, c + o_dst, (unsigned)dst_len, du, 256, d_bad, s); if (e) { ctx->last_hip = e; return NBLS_EHIP; } }
+  if ((r = dev_hash_to_g2(ctx, n, du, H, s))) return r;
+  // S = sum_i [r_i]sig_i behind the signatures on the side stream (enqueued last: dev_msm waits on the host for its stream once, with the hash chain and the keys in flight)
+  if ((r = dev_msm(ctx, true, n, SG, W, 64, H + n * 192, MS, ctx->side, 30))) return r;
+  HIPCHK(hipEventRecord(ctx->ev_join, ctx->side));
+  HIPCHK(hipStreamWaitEvent(s, ctx->ev_join2, 0));
+  HIPCHK(hipStreamWaitEvent(s, ctx->ev_join, 0));
+  HIPCHK(hipMemcpyAsync(RPK + n * 96, ctx->neg_g1, 96, hipMemcpyDeviceToDevice, s));   // PointG1.BASE.negate()
+  size_t m = 0;
+  uint8_t* res = ctx->F;
+  if ((r = miller_values(ctx, n + 1, RPK, H, &m, s)) || (r = reduce_product(ctx, m, &res, s)) || (r = finish_single(ctx, res, 1, O, s))) return r;
+  HIPCHK(hipMemcpyAsync(ctx->pinned_out, O, back, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  fork_guard.armed = false;      // synchronised: both side streams were joined into s
+  std::vector<uint8_t> rb(ctx->pinned_out, ctx->pinned_out + back);
+  uint32_t bad = 0; memcpy(&bad, rb.data() + 576 + st_bytes - 4, 4);
+  if (bad) return NBLS_EINVAL;
+  const int8_t *stk = (const int8_t*)rb.data() + 576, *sts = stk + n;
+  bool decoded = sts[n] == 0;   // (the MSM's status: 1 = the weighted sum is the zero point)
+  for (size_t i = 0; i < n && decoded; i++) if (stk[i] || sts[i]) decoded = false;
+  if (decoded && fp12_wire_is_one(rb.data())) {
+    *all_ok = 1;
+    if (status) memset(status, 0, n);
+    return NBLS_OK;
+  }
+  *all_ok = 0;
+  if (!status) return NBLS_OK;     // fast reject: no per-set work
+  // the per-set pass, on the unweighted keys: millerLoop(pk_i, H_i) x millerLoop(-G1, sig_i), final exponentiation, compared with one on the device
+  uint8_t *X;
+  if ((r = need(ctx, 22, n * (192 + 384 + 576) + n, &X))) return r;
+  uint8_t *G1x = X, *G2x = G1x + n * 192, *E = G2x + n * 384, *V = E + n * 576;
+  if (nbls_rlc_interleave_launch((unsigned)n, PK, ctx->neg_g1, H, SG, G1x, G2x, s)) { ctx->last_hip = (int)hipGetLastError(); return NBLS_EHIP; }
+  if ((r = run(ctx, P_MILLER_RAW2, n, {B(0, G1x, 192), B(1, G2x, 384), B(3, ctx->F, F12)}, s)) || (r = run(ctx, P_NORM_RAW, n, {B(3, ctx->F, F12), B(4, ctx->N, RAW)}, s)) ||
+      (r = final_exp_pipeline(ctx, n, ctx->F, E, s)))
+    return r;
+  if (nbls_rlc_is_one_launch((unsigned)n, E, V, s)) { ctx->last_hip = (int)hipGetLastError(); return NBLS_EHIP; }
+  if ((r = ensure_pinned_out(ctx, n))) return r;
+  HIPCHK(hipMemcpyAsync(ctx->pinned_out, V, n, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  int all = 1;
+  for (size_t i = 0; i < n; i++) {
+    // the reference's order (oracle_verify): the key decodes, the message hashes, the signature decodes, the pairing throws on a zero point ("No pairings at point of Infinity")
+    const int8_t k = stk[i], g = sts[i];
+    const int8_t v = k >= 2 ? k : g >= 2 ? (int8_t)(10 + g) : k == 1 ? 1 : g == 1 ? 11 : ctx->pinned_out[i] ? 0 : NBLS_ST_NOT_VERIFIED;
+    status[i] = v;
+    if (v) all = 0;
+  }
+  *all_ok = all;
+  return NBLS_OK;
+}
+
+EXPORT int nbls_verify_multiple(nbls_ctx* ctx, size_t n, const uint8_t* sigs96, const uint8_t* msgs, const uint32_t* offsets, const uint8_t* pks48, const uint8_t* dst, size_t dst_len,
+                                const uint8_t* seed32, int* all_ok, int8_t* status) {
+  std::lock_guard<std::recursive_mutex> whole_call_(ctx ? ctx->mu : g_null_mu);   // scratch and I/O staging buffers belong to this call until it returns
+  if (!ctx || !all_ok || !n || !sigs96 || !offsets || !pks48 || !dst || (!msgs && offsets[n] != offsets[0])) return NBLS_EINVAL;
+  if (n > ((size_t)1 << 22)) return NBLS_EINVAL;   // dev_msm's bound
+  return verify_multiple_pipeline(ctx, n, sigs96, msgs, offsets, pks48, dst, dst_len, seed32, all_ok, status);
+}

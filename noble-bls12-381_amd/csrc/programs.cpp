@@ -595,6 +595,16 @@ static Program build(ProgId id) {
       B.sched_window = w3 ? 300 : env_int("NBLS_G1MUL_WINDOW", 200);   // scalar bits are extracted just in time instead of all 256 up front (they would pin 256 LDS slots)
       return B.compile(w3 ? "g1_mul_w3" : "g1_mul", G1MUL_W);
     }
+    case P_G1_MUL64: {
+      // the ladder above on 64 = 1 + 21 * 3 bits: 63 doublings and 21 additions where P_G1_MUL_W3 spends 255 and 85 (the weights have 24 leading zero bytes)
+      SFp x = input(0, 0), y = input(0, 48);
+      SFp k = input_raw(2, 24, 8);
+      Pt<SFp> r = pt_mul_ladder(pt_affine(x, y), k, 64, 3);
+      outputw(r.x, 3, 0); outputw(r.y, 3, 48); outputw(r.z, 3, 96);
+      outputw(r.z, 4, 0);
+      B.sched_window = 300;
+      return B.compile("g1_mul64", G1MUL_W);
+    }
     case P_G2_MUL_GLS: {
       SFp2 x = input_fp2(1, 0), y = input_fp2(1, 96);
       SFp a[4]; for (int i = 0; i < 4; i++) a[i] = input_raw(2, 32 * i, 32);

@@ -88,6 +88,7 @@ enum ProgId {
   P_H2C_NA,            // 256 uniform bytes (buf 0) -> t0, t1 (3), N(u conj(v)) of both maps (4: the first exponentiation's input), state (5: per map zt2, num, den, a = u conj(v), d = N(v): 9 raw elements of 16)
   P_H2C_NM,            // one map per item: t (3), state (4), n = N(a)^((p+1)/4) (5) -> num of the chosen x, a1 / 2, delta (6: 4 raw elements), delta d^3 (7: the second exponentiation's input)
   P_H2C_NB,            // one map per item: t (3), state (4), e = (delta d^3)^((p-3)/4) (5) -> projective point on E2' (6), what P_H2C_B1 produces
+  P_G1_MUL64,          // [r]P for the 64-bit weights of nbls_verify_multiple (rlc_weights.h; top bit set): affine P (buf 0), 32-byte scalar whose low 8 bytes are read (buf 2) -> projective (3), Z (4)
   P_COUNT
 };
 // |x| = 2^63 + 2^62 + 2^60 + 2^57 + 2^48 + 2^16: the compressed chain runs to 2^57 and its values at the set bits 16, 48, 57 are decompressed; the powers

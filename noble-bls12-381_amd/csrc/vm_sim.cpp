@@ -11,6 +11,7 @@
 #include "fp_inv.h"
 #include "pow_exec.h"
 #include "pow_wide.h"
+#include "rlc_weights.h"
 #include "wide_exec.h"
 #include "g1_wide.h"
 #include "fp_inv_wide.h"
@@ -443,6 +444,8 @@ __attribute__((visibility("default"))) int nbls_sim_layout_info(int prog, unsign
   return 0;
 }
 // the scalar side of the endomorphism splits as the device runs it (scalar_split.h): dims = 2 / 4: base-|z| digits; dims = 0: the sign-aligned recoding (4 x 32 bytes per scalar)
+// the weights of nbls_verify_multiple as rlc_kernels.hip derives them (rlc_weights.h): r_i for the set index i, 32 bytes big-endian
+__attribute__((visibility("default"))) void nbls_sim_rlc_weight(const uint8_t* seed32, uint64_t i, uint8_t* out32) { rlc_weight(seed32, i, out32); }
 __attribute__((visibility("default"))) void nbls_sim_scalar_split(unsigned n, unsigned dims, const uint8_t* scalars, uint8_t* out) {
   for (unsigned i = 0; i < n; i++) { if (dims) scalar_decompose(scalars + 32ull * i, dims, out + 32ull * dims * i); else scalar_sac_recode(scalars + 32ull * i, out + 128ull * i); }
 }

@@ -12,7 +12,7 @@ except ImportError:      # the binding itself needs only ctypes
     _np = None
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-ABI_VERSION = 4   # include/nbls.h NBLS_ABI_VERSION: checked at load (round 4's advisor: an ABI-1 caller of *_partial read stale bytes from an ABI-2 library with no error)
+ABI_VERSION = 5   # include/nbls.h NBLS_ABI_VERSION: checked at load (round 4's advisor: an ABI-1 caller of *_partial read stale bytes from an ABI-2 library with no error)
 PROGRAMS = []   # names of the step programs in the library's numbering (filled by load_library from nbls_program_name)
 DST_DEFAULT = b'BLS_SIG_BLS12381G2_XMD:SHA-256_SSWU_RO_NUL_'   # htfDefaults.DST, reference index.ts:64
 
@@ -65,6 +65,7 @@ def load_library():
     lib.nbls_sign_batch.argtypes = [vp, sz, vp, vp, vp, sz, vp, vp, vp]
     lib.nbls_sign_batch_dev.argtypes = [vp, sz, vp, vp, vp, sz, vp, vp, vp, vp]
     lib.nbls_verify_batch.argtypes = [vp, sz, vp, vp, vp, vp, vp, sz, C.POINTER(i32)]
+    lib.nbls_verify_multiple.argtypes = [vp, sz, vp, vp, vp, vp, vp, sz, vp, C.POINTER(i32), vp]
     lib.nbls_verify_batch_dev_inputs.argtypes = [vp, sz, vp, vp, vp, C.POINTER(i32), vp, vp]
     lib.nbls_verify_batch_msgs_dev.argtypes = [vp, sz, vp, vp, vp, vp, vp, sz, C.POINTER(i32), vp]
     lib.nbls_verify_batch_partial_dev.argtypes = [vp, sz, vp, vp, vp, vp, C.POINTER(i32), vp, vp]
@@ -358,6 +359,19 @@ class Engine:
         ok = C.c_int(0)
         self._chk(self.lib.nbls_verify_batch(self.h, len(msgs), sig96, blob, offs, b''.join(pks48), dst, len(dst), C.byref(ok)))
         return bool(ok.value)
+
+    def verify_multiple(self, sigs96, msgs, pks48, dst=DST_DEFAULT, seed=None, per_set=True):
+        """verify(sig_i, msg_i, pk_i) for n independent sets, checked together by a random linear combination (nbls_verify_multiple) -> (all_ok, statuses or None).
+        statuses: bytes, one per set (0 ok, 9 not verified, the key's decoder status, 10 + the signature's, 1 / 11 for a zero key / signature); seed: 32 bytes, None = from the OS;
+        per_set=False: the combined check alone (fast reject, statuses None)"""
+        n = len(msgs)
+        if len(sigs96) != n or len(pks48) != n or (seed is not None and len(seed) != 32):
+            raise NblsError('verify_multiple: %d messages, %d signatures, %d keys, seed of %s bytes' % (n, len(sigs96), len(pks48), None if seed is None else len(seed)))
+        blob, offs = self._pack(msgs)
+        ok = C.c_int(0)
+        st = C.create_string_buffer(max(n, 1)) if per_set else None
+        self._chk(self.lib.nbls_verify_multiple(self.h, n, b''.join(sigs96), blob, offs, b''.join(pks48), dst, len(dst), seed, C.byref(ok), st))
+        return bool(ok.value), (st.raw[:n] if per_set else None)
 
     def verify_batch_dev(self, n, d_sig, d_uniform, d_pk, stream=None):
         ok = C.c_int(0)

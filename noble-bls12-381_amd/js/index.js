@@ -435,6 +435,47 @@ async function verify(signature, message, publicKey) {
   if (r.code) { const st = r.status[0] || r.status[1]; throw new Error(st >= 10 ? G2_STATUS[st - 10] : G1_STATUS[st]); }
   return Fp12.fromBytes(r.out).equals(Fp12.ONE);
 }
+// verify(signature_i, message_i, publicKey_i) for n independent sets at once (no reference counterpart; blst's verify_multiple_aggregate_signatures): the wire-format sets
+// take ONE engine call on a worker thread (nbls_verify_multiple: a random linear combination with weights seeded from the OS, n + 1 Miller loops and one final
+// exponentiation, a per-set pass only when that check fails).  Sets with point objects, and every set the engine reports as one where verify throws (a point that does not
+// decode, a zero point), go through verify itself, in index order: the first set that throws there throws the reference's message.  The inputs are packed into buffers
+// allocated once (a spread of 100k+ arrays into one call throws RangeError).
+async function verifyMultipleSignatures(sets) {
+  if (!Array.isArray(sets) || !sets.length) throw new Error('Expected non-empty array');
+  ensureInit();
+  const n = sets.length, wire = new Array(n);
+  let w = 0, total = 0;
+  for (let i = 0; i < n; i++) {
+    const { signature, message, publicKey } = sets[i];
+    wire[i] = null;
+    if (signature instanceof PointG2 || message instanceof PointG2 || publicKey instanceof PointG1) continue;
+    let sig, msg, pk;
+    try { sig = ensureBytes(signature); msg = ensureBytes(message); pk = ensureBytes(publicKey); } catch (e) { continue; }
+    if (sig.length !== 96 || pk.length !== 48) continue;
+    wire[i] = [sig, msg, pk]; w++; total += msg.length;
+  }
+  let status = null;
+  if (w) {
+    const sigs = new Uint8Array(96 * w), pks = new Uint8Array(48 * w), msgs = new Uint8Array(total), offs = new Uint32Array(w + 1);
+    for (let i = 0, k = 0; i < n; i++) {
+      if (!wire[i]) continue;
+      const [sig, msg, pk] = wire[i];
+      sigs.set(sig, 96 * k); pks.set(pk, 48 * k); msgs.set(msg, offs[k]); offs[k + 1] = offs[k] + msg.length; k++;
+    }
+    status = (await native.verifyMultipleAsync(sigs, msgs, offs, pks, stringToBytes(htfDefaults.DST))).status;   // worker thread: the event loop keeps running
+  }
+  let all = true;
+  for (let i = 0, k = 0; i < n; i++) {
+    if (wire[i]) {
+      const st = status[k++];
+      if (st === 0) continue;
+      if (st === 9) { all = false; continue; }      // NBLS_ST_NOT_VERIFIED
+    }
+    const { signature, message, publicKey } = sets[i];
+    if (!(await verify(signature, message, publicKey))) all = false;
+  }
+  return all;
+}
 // reference index.ts:771-788
 function aggregatePublicKeys(publicKeys) {
   if (!publicKeys.length) throw new Error('Expected non-empty array');
@@ -531,5 +572,5 @@ const utils = {
   },
 };
 
-module.exports = { CURVE, Fp, Fr, Fp2, Fp6, Fp12, PointG1, PointG2, pairing, pairingBatch, millerProduct, getPublicKey, getPublicKeys, sign, signBatch, verify, verifyBatch,
+module.exports = { CURVE, Fp, Fr, Fp2, Fp6, Fp12, PointG1, PointG2, pairing, pairingBatch, millerProduct, getPublicKey, getPublicKeys, sign, signBatch, verify, verifyBatch, verifyMultipleSignatures,
   aggregatePublicKeys, aggregateSignatures, utils, init: (dev, contexts) => { if (contexts === undefined) native.init(dev || 0); else native.init(dev || 0, contexts); inited = true; } };
