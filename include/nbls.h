@@ -213,6 +213,28 @@ int nbls_verify_batch_dev_inputs(nbls_ctx* ctx, size_t n, const void* d_sig96, c
 int nbls_verify_multiple(nbls_ctx* ctx, size_t n, const uint8_t* sigs96, const uint8_t* msgs, const uint32_t* offsets, const uint8_t* pks48, const uint8_t* dst, size_t dst_len,
                          const uint8_t* seed32 /* NULL: from the OS */, int* all_ok, int8_t* status /* n, may be NULL */);
 
+/* verify(sig_j, m_j, aggregatePublicKeys(keys_j)) (index.ts:756-778) for n sets, checked together by one random linear combination over the SETS (weights r_j as in
+ * nbls_verify_multiple): prod_j e([r_j]apk_j, H(m_j)) * e(-G1, sum_j [r_j]sig_j) = 1 with apk_j the sum of set j's keys.  Set j: sigs96[j], message msgs[offsets[j] .. offsets[j+1]),
+ * keys pks48[key_offsets[j] .. key_offsets[j+1]) (48-byte compressed, in 48-byte units).  status[j], in the reference's order: the decoder status of the set's first key that does
+ * not decode (3 outside the subgroup, 4 no square root: aggregatePublicKeys throws there), else 10 + the signature decoder's status if >= 2, else 1 when the keys sum to the zero
+ * point ({pk, -pk}, only 0xc0... keys: "No pairings at point of Infinity"), else 11 for a zero signature, else 0 or NBLS_ST_NOT_VERIFIED.  A zero key inside a set is valid and adds
+ * nothing.  Seed, per-set pass, fast reject (status == NULL), *all_ok and return codes as nbls_verify_multiple; NBLS_EINVAL also for a set without keys (the reference throws
+ * "Expected non-empty array"), decreasing key offsets and more than 2^24 keys in one call. */
+int nbls_verify_aggregates(nbls_ctx* ctx, size_t n, const uint8_t* sigs96, const uint8_t* msgs, const uint32_t* offsets, const uint8_t* pks48, const uint32_t* key_offsets,
+                           const uint8_t* dst, size_t dst_len, const uint8_t* seed32 /* NULL: from the OS */, int* all_ok, int8_t* status /* n, may be NULL */);
+/* A table of keys decoded once (PointG1.fromHex, index.ts:298-327) and kept in device memory of ctx's device: nbls_verify_aggregates_indexed names keys by their index in it, so that
+ * no key is decoded or subgroup-checked again.  status[i] (may be NULL) = the decoder's status of key i (0, 1 for the zero key, 3, 4); a key that did not decode stays in the table and
+ * fails every set that names it with that status.  At most 2^24 keys.  The table belongs to no context: any context on the same device may use it, after its creator is destroyed
+ * too; nbls_keyset_destroy must not run while a call uses it. */
+typedef struct nbls_keyset nbls_keyset;
+int  nbls_keyset_create(nbls_ctx* ctx, size_t n, const uint8_t* pks48, int8_t* status /* n, may be NULL */, nbls_keyset** out);
+void nbls_keyset_destroy(nbls_keyset* ks);
+int  nbls_keyset_size(const nbls_keyset* ks, size_t* n);
+/* The same as nbls_verify_aggregates, with the keys of set j = table entries key_index[key_offsets[j] .. key_offsets[j+1]); NBLS_EINVAL also for an index >= the table's size and
+ * for a table created on another device than ctx's. */
+int nbls_verify_aggregates_indexed(nbls_ctx* ctx, const nbls_keyset* ks, size_t n, const uint8_t* sigs96, const uint8_t* msgs, const uint32_t* offsets, const uint32_t* key_index,
+                                   const uint32_t* key_offsets, const uint8_t* dst, size_t dst_len, const uint8_t* seed32, int* all_ok, int8_t* status);
+
 /* One rank's share of a verifyBatch spread over several GPUs (one process per GPU): the Miller product of this rank's n
  * (key, message) pairs, times millerLoop(-G, S) on the ONE rank that passes the signature (d_sig96 = NULL elsewhere), WITHOUT the
  * final exponentiation, as 576 wire bytes in device memory.  Ranks all-gather their partials and finish with
@@ -235,7 +257,8 @@ int nbls_miller_product_partial_into(nbls_ctx* ctx, size_t n, const uint8_t* g1_
 int nbls_verify_batch_partial_into(nbls_ctx* ctx, size_t n, const uint8_t* sig96 /* or NULL */, const uint8_t* msgs, const uint32_t* offsets, const uint8_t* pk48,
                                    const uint8_t* dst, size_t dst_len, void* d_dst576, int* zero_flag, int8_t* pk_status /* n, may be NULL */);
 const char* nbls_config_describe(void);   /* "NBLS_X=value(env|default) ...": every environment switch the library has read so far and the value in force -- print it next to an A/B result */
-/* 5: nbls_verify_multiple, NBLS_ST_NOT_VERIFIED, scratch slots 20 .. 43 (additions only).
+/* 5: nbls_verify_multiple, NBLS_ST_NOT_VERIFIED, scratch slots 20 .. 43 (additions only); then nbls_verify_aggregates, nbls_verify_aggregates_indexed, nbls_keyset_create /
+   _destroy / _size, scratch slots 44 .. 47 (additions only, same version).
    4 (round 6): nbls_hw_queues, NBLS_TUNE_WIDE_MAX, NBLS_TUNE_H2C_NORM_MIN, NBLS_TUNE_INV_WIDE_MAX, NBLS_TUNE_LS_MAX / _LS2_MAX (additions only); the library sets GPU_MAX_HW_QUEUES = 22 at load when the variable is unset (see nbls_pool_init below).
    3 (round 5): nbls_program_kernel, nbls_pool_*, nbls_sign_batch_dev, NBLS_TUNE_VERIFY_* / _SAC_MAX / _PT_LS2_MAX (additions only); nbls_verify_batch_partial_dev writes d_out_fp12 even when it reports a zero point or a decode error
    (contents then meaningless); 2: *_partial take *d_partial as OUT only, *_partial_into added, nbls_tower_op_batch, nbls_verify_batch_msgs_dev.  The bindings check it at load. */

@@ -66,6 +66,12 @@ def load_library():
     lib.nbls_sign_batch_dev.argtypes = [vp, sz, vp, vp, vp, sz, vp, vp, vp, vp]
     lib.nbls_verify_batch.argtypes = [vp, sz, vp, vp, vp, vp, vp, sz, C.POINTER(i32)]
     lib.nbls_verify_multiple.argtypes = [vp, sz, vp, vp, vp, vp, vp, sz, vp, C.POINTER(i32), vp]
+    lib.nbls_verify_aggregates.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, sz, vp, C.POINTER(i32), vp]
+    lib.nbls_verify_aggregates_indexed.argtypes = [vp, vp, sz, vp, vp, vp, vp, vp, vp, sz, vp, C.POINTER(i32), vp]
+    lib.nbls_keyset_create.argtypes = [vp, sz, vp, vp, C.POINTER(vp)]
+    lib.nbls_keyset_destroy.argtypes = [vp]
+    lib.nbls_keyset_destroy.restype = None
+    lib.nbls_keyset_size.argtypes = [vp, C.POINTER(sz)]
     lib.nbls_verify_batch_dev_inputs.argtypes = [vp, sz, vp, vp, vp, C.POINTER(i32), vp, vp]
     lib.nbls_verify_batch_msgs_dev.argtypes = [vp, sz, vp, vp, vp, vp, vp, sz, C.POINTER(i32), vp]
     lib.nbls_verify_batch_partial_dev.argtypes = [vp, sz, vp, vp, vp, vp, C.POINTER(i32), vp, vp]
@@ -110,6 +116,31 @@ def load_library():
     lib.nbls_timing_enable.argtypes = [vp, i32]
     lib.nbls_timing_read.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_uint32)]
     return lib
+
+
+class KeySet:
+    """A table of decoded keys in device memory (nbls_keyset_create; Engine.create_keyset).  Freed by close() or when the object goes away."""
+
+    def __init__(self, lib, handle):
+        self.lib = lib
+        self.h = handle
+
+    def __len__(self):
+        n = C.c_size_t(0)
+        if self.h is None or self.lib.nbls_keyset_size(self.h, C.byref(n)) != 0:
+            raise NblsError('KeySet: the table is closed')
+        return n.value
+
+    def close(self):
+        if getattr(self, 'h', None):
+            self.lib.nbls_keyset_destroy(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class Engine:
@@ -371,6 +402,63 @@ class Engine:
         ok = C.c_int(0)
         st = C.create_string_buffer(max(n, 1)) if per_set else None
         self._chk(self.lib.nbls_verify_multiple(self.h, n, b''.join(sigs96), blob, offs, b''.join(pks48), dst, len(dst), seed, C.byref(ok), st))
+        return bool(ok.value), (st.raw[:n] if per_set else None)
+
+    @staticmethod
+    def _u32(vals):
+        """a sequence of non-negative ints -> a ctypes uint32 array"""
+        n = len(vals)
+        if _np is not None and n >= 256:
+            return (C.c_uint32 * n).from_buffer(_np.ascontiguousarray(vals, dtype=_np.uint32))
+        return (C.c_uint32 * n)(*vals)
+
+    def _key_offsets(self, sets):
+        lens = [len(k) for k in sets]
+        if _np is not None and len(lens) >= 256:
+            offs = _np.zeros(len(lens) + 1, dtype=_np.uint32)
+            _np.cumsum(_np.fromiter(lens, dtype=_np.uint32, count=len(lens)), out=offs[1:])
+            return (C.c_uint32 * len(offs)).from_buffer(offs)
+        offs = [0]
+        for k in lens:
+            offs.append(offs[-1] + k)
+        return (C.c_uint32 * len(offs))(*offs)
+
+    def verify_aggregates(self, sigs96, msgs, key_sets, dst=DST_DEFAULT, seed=None, per_set=True):
+        """verify(sig_j, msg_j, aggregatePublicKeys(key_sets[j])) for n sets, checked together by a random linear combination (nbls_verify_aggregates) -> (all_ok, statuses or None).
+        key_sets: a list of lists of 48-byte compressed keys.  statuses: bytes, one per set (0 ok, 9 not verified, the first bad key's decoder status, 10 + the signature's,
+        1 when the keys sum to zero, 11 for a zero signature); seed and per_set as verify_multiple"""
+        n = len(msgs)
+        if len(sigs96) != n or len(key_sets) != n or (seed is not None and len(seed) != 32):
+            raise NblsError('verify_aggregates: %d messages, %d signatures, %d key sets, seed of %s bytes' % (n, len(sigs96), len(key_sets), None if seed is None else len(seed)))
+        blob, offs = self._pack(msgs)
+        koffs = self._key_offsets(key_sets)
+        pks = b''.join(b''.join(k) for k in key_sets)
+        ok = C.c_int(0)
+        st = C.create_string_buffer(max(n, 1)) if per_set else None
+        self._chk(self.lib.nbls_verify_aggregates(self.h, n, b''.join(sigs96), blob, offs, pks, koffs, dst, len(dst), seed, C.byref(ok), st))
+        return bool(ok.value), (st.raw[:n] if per_set else None)
+
+    def create_keyset(self, pks48):
+        """nbls_keyset_create: decode the keys once into a table in this device's memory -> (KeySet, status bytes: 0, 1 for the zero key, 3, 4 per key)"""
+        n = len(pks48)
+        h = C.c_void_p()
+        st = C.create_string_buffer(max(n, 1))
+        self._chk(self.lib.nbls_keyset_create(self.h, n, b''.join(pks48), st, C.byref(h)))
+        return KeySet(self.lib, h), st.raw[:n]
+
+    def verify_aggregates_indexed(self, keyset, sigs96, msgs, index_sets, dst=DST_DEFAULT, seed=None, per_set=True):
+        """verify_aggregates with the keys of set j named by their indices in `keyset` (a KeySet of create_keyset): index_sets is a list of lists of ints"""
+        n = len(msgs)
+        if len(sigs96) != n or len(index_sets) != n or (seed is not None and len(seed) != 32):
+            raise NblsError('verify_aggregates_indexed: %d messages, %d signatures, %d index sets, seed of %s bytes' % (n, len(sigs96), len(index_sets), None if seed is None else len(seed)))
+        if keyset.h is None:
+            raise NblsError('verify_aggregates_indexed: the key table is closed')
+        blob, offs = self._pack(msgs)
+        koffs = self._key_offsets(index_sets)
+        idx = self._u32([i for s in index_sets for i in s])
+        ok = C.c_int(0)
+        st = C.create_string_buffer(max(n, 1)) if per_set else None
+        self._chk(self.lib.nbls_verify_aggregates_indexed(self.h, keyset.h, n, b''.join(sigs96), blob, offs, idx, koffs, dst, len(dst), seed, C.byref(ok), st))
         return bool(ok.value), (st.raw[:n] if per_set else None)
 
     def verify_batch_dev(self, n, d_sig, d_uniform, d_pk, stream=None):

@@ -105,6 +105,8 @@ export declare function aggregateSignatures(signatures: PointG2[]): PointG2;
 export declare function verifyBatch(signature: Hex | PointG2, messages: (Hex | PointG2)[], publicKeys: (Hex | PointG1)[]): Promise<boolean>;
 /** verify(signature, message, publicKey) for every set, checked together by a random linear combination on the GPU; throws where verify throws for the first such set */
 export declare function verifyMultipleSignatures(sets: { publicKey: Hex | PointG1; message: Hex | PointG2; signature: Hex | PointG2 }[]): Promise<boolean>;
+/** verify(signature, message, aggregatePublicKeys(publicKeys)) for every set, checked together by a random linear combination on the GPU; throws where that throws for the first such set */
+export declare function verifyMultipleAggregateSignatures(sets: { publicKeys: (Hex | PointG1)[]; message: Hex | PointG2; signature: Hex | PointG2 }[]): Promise<boolean>;
 
 // additive batched entry points (one engine call each)
 export declare function pairingBatch(Ps: PointG1[] | Uint8Array /* n x 96 affine bytes */, Qs: PointG2[] | Uint8Array /* n x 192 */, withFinalExponent?: boolean, validate?: boolean): { out: Uint8Array /* n x 576 */; status: Uint8Array };

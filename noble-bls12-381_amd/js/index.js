@@ -476,6 +476,58 @@ async function verifyMultipleSignatures(sets) {
   }
   return all;
 }
+// verify(signature_j, message_j, aggregatePublicKeys(publicKeys_j)) for n sets at once (no reference counterpart; blst's aggregate-verify of many sets): the wire-format sets take
+// ONE engine call on a worker thread (nbls_verify_aggregates: the keys of every set summed on the device, then one random linear combination over the sets with weights seeded from
+// the OS).  Sets with point objects, and every set the engine reports with a status other than 0 or 9 (a key or signature that does not decode, a zero aggregate or signature), go
+// through verify(signature, message, aggregatePublicKeys(publicKeys)) itself, in index order: the first set that throws there throws the reference's message.  The inputs are packed
+// in one pass into buffers allocated once (a spread of 100k+ arrays into one call throws RangeError).
+async function verifyMultipleAggregateSignatures(sets) {
+  if (!Array.isArray(sets) || !sets.length) throw new Error('Expected non-empty array');
+  ensureInit();
+  const n = sets.length, wire = new Array(n);
+  let w = 0, total = 0, nkeys = 0;
+  for (let i = 0; i < n; i++) {
+    const { signature, message, publicKeys } = sets[i];
+    wire[i] = null;
+    if (!Array.isArray(publicKeys) || !publicKeys.length || signature instanceof PointG2 || message instanceof PointG2) continue;
+    let sig, msg, ok = true;
+    const keys = new Array(publicKeys.length);
+    try {
+      sig = ensureBytes(signature); msg = ensureBytes(message);
+      for (let k = 0; k < publicKeys.length && ok; k++) {
+        if (publicKeys[k] instanceof PointG1) { ok = false; break; }
+        keys[k] = ensureBytes(publicKeys[k]);
+        if (keys[k].length !== 48) ok = false;
+      }
+    } catch (e) { continue; }
+    if (!ok || sig.length !== 96) continue;
+    wire[i] = [sig, msg, keys]; w++; total += msg.length; nkeys += keys.length;
+  }
+  let status = null;
+  if (w) {
+    const sigs = new Uint8Array(96 * w), pks = new Uint8Array(48 * nkeys), msgs = new Uint8Array(total), offs = new Uint32Array(w + 1), koffs = new Uint32Array(w + 1);
+    for (let i = 0, j = 0; i < n; i++) {
+      if (!wire[i]) continue;
+      const [sig, msg, keys] = wire[i];
+      sigs.set(sig, 96 * j); msgs.set(msg, offs[j]); offs[j + 1] = offs[j] + msg.length;
+      let at = koffs[j];
+      for (let k = 0; k < keys.length; k++, at++) pks.set(keys[k], 48 * at);
+      koffs[j + 1] = at; j++;
+    }
+    status = (await native.verifyAggregatesAsync(sigs, msgs, offs, pks, koffs, stringToBytes(htfDefaults.DST))).status;   // worker thread: the event loop keeps running
+  }
+  let all = true;
+  for (let i = 0, j = 0; i < n; i++) {
+    if (wire[i]) {
+      const st = status[j++];
+      if (st === 0) continue;
+      if (st === 9) { all = false; continue; }      // NBLS_ST_NOT_VERIFIED
+    }
+    const { signature, message, publicKeys } = sets[i];
+    if (!(await verify(signature, message, aggregatePublicKeys(publicKeys)))) all = false;
+  }
+  return all;
+}
 // reference index.ts:771-788
 function aggregatePublicKeys(publicKeys) {
   if (!publicKeys.length) throw new Error('Expected non-empty array');
@@ -572,5 +624,5 @@ const utils = {
   },
 };
 
-module.exports = { CURVE, Fp, Fr, Fp2, Fp6, Fp12, PointG1, PointG2, pairing, pairingBatch, millerProduct, getPublicKey, getPublicKeys, sign, signBatch, verify, verifyBatch, verifyMultipleSignatures,
+module.exports = { CURVE, Fp, Fr, Fp2, Fp6, Fp12, PointG1, PointG2, pairing, pairingBatch, millerProduct, getPublicKey, getPublicKeys, sign, signBatch, verify, verifyBatch, verifyMultipleSignatures, verifyMultipleAggregateSignatures,
   aggregatePublicKeys, aggregateSignatures, utils, init: (dev, contexts) => { if (contexts === undefined) native.init(dev || 0); else native.init(dev || 0, contexts); inited = true; } };
