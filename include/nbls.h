@@ -235,6 +235,23 @@ int  nbls_keyset_size(const nbls_keyset* ks, size_t* n);
 int nbls_verify_aggregates_indexed(nbls_ctx* ctx, const nbls_keyset* ks, size_t n, const uint8_t* sigs96, const uint8_t* msgs, const uint32_t* offsets, const uint32_t* key_index,
                                    const uint32_t* key_offsets, const uint8_t* dst, size_t dst_len, const uint8_t* seed32, int* all_ok, int8_t* status);
 
+/* The three calls above for sets that SHARE messages: msgs / offsets hold n_msgs distinct messages (offsets has n_msgs + 1 entries) and set i signs message msg_index[i].  The
+ * factors of one message are multiplied together by bilinearity,
+ *   prod_{g < n_msgs} e(sum_{i : msg_index[i] = g} [r_i]pk_i, H(m_g)) * e(-G1, sum_i [r_i]sig_i) = 1,
+ * n_msgs hashes to G2 and n_msgs + 1 Miller loops instead of n and n + 1, exactly as sound: the weights r_i stay per SET (by set index i, as in nbls_verify_multiple), so two
+ * signers of one message whose signatures are exchanged are still caught.  status[i] and *all_ok are byte for byte what the twin without `_shared` returns for the expanded input
+ * (set i given the bytes of message msg_index[i]) and the same seed.  Messages may repeat inside msgs; msg_index may be any map onto 0 .. n_msgs - 1, the identity included, and the
+ * sets of one message need not be contiguous.  When the weighted keys of one message sum to the zero point the combined check cannot count (like a zero weighted sum of the
+ * signatures): the per-set pass judges the sets, and with status == NULL the call answers *all_ok = 0.  Seed, DST rule, fast reject and return codes as the twins; NBLS_EINVAL also
+ * for n_msgs = 0, n_msgs > n, a missing msg_index, an index >= n_msgs and a message that no set names -- refused before any device work. */
+int nbls_verify_multiple_shared(nbls_ctx* ctx, size_t n, const uint8_t* sigs96, size_t n_msgs, const uint8_t* msgs, const uint32_t* offsets, const uint32_t* msg_index /* n */,
+                                const uint8_t* pks48, const uint8_t* dst, size_t dst_len, const uint8_t* seed32 /* NULL: from the OS */, int* all_ok, int8_t* status /* n, may be NULL */);
+int nbls_verify_aggregates_shared(nbls_ctx* ctx, size_t n, const uint8_t* sigs96, size_t n_msgs, const uint8_t* msgs, const uint32_t* offsets, const uint32_t* msg_index /* n */,
+                                  const uint8_t* pks48, const uint32_t* key_offsets, const uint8_t* dst, size_t dst_len, const uint8_t* seed32, int* all_ok, int8_t* status);
+int nbls_verify_aggregates_indexed_shared(nbls_ctx* ctx, const nbls_keyset* ks, size_t n, const uint8_t* sigs96, size_t n_msgs, const uint8_t* msgs, const uint32_t* offsets,
+                                          const uint32_t* msg_index /* n */, const uint32_t* key_index, const uint32_t* key_offsets, const uint8_t* dst, size_t dst_len,
+                                          const uint8_t* seed32, int* all_ok, int8_t* status);
+
 /* One rank's share of a verifyBatch spread over several GPUs (one process per GPU): the Miller product of this rank's n
  * (key, message) pairs, times millerLoop(-G, S) on the ONE rank that passes the signature (d_sig96 = NULL elsewhere), WITHOUT the
  * final exponentiation, as 576 wire bytes in device memory.  Ranks all-gather their partials and finish with
@@ -258,7 +275,8 @@ int nbls_verify_batch_partial_into(nbls_ctx* ctx, size_t n, const uint8_t* sig96
                                    const uint8_t* dst, size_t dst_len, void* d_dst576, int* zero_flag, int8_t* pk_status /* n, may be NULL */);
 const char* nbls_config_describe(void);   /* "NBLS_X=value(env|default) ...": every environment switch the library has read so far and the value in force -- print it next to an A/B result */
 /* 5: nbls_verify_multiple, NBLS_ST_NOT_VERIFIED, scratch slots 20 .. 43 (additions only); then nbls_verify_aggregates, nbls_verify_aggregates_indexed, nbls_keyset_create /
-   _destroy / _size, scratch slots 44 .. 47 (additions only, same version).
+   _destroy / _size, scratch slots 44 .. 47 (additions only, same version); then nbls_verify_multiple_shared, nbls_verify_aggregates_shared,
+   nbls_verify_aggregates_indexed_shared, scratch slots 48 .. 50 (additions only, same version).
    4 (round 6): nbls_hw_queues, NBLS_TUNE_WIDE_MAX, NBLS_TUNE_H2C_NORM_MIN, NBLS_TUNE_INV_WIDE_MAX, NBLS_TUNE_LS_MAX / _LS2_MAX (additions only); the library sets GPU_MAX_HW_QUEUES = 22 at load when the variable is unset (see nbls_pool_init below).
    3 (round 5): nbls_program_kernel, nbls_pool_*, nbls_sign_batch_dev, NBLS_TUNE_VERIFY_* / _SAC_MAX / _PT_LS2_MAX (additions only); nbls_verify_batch_partial_dev writes d_out_fp12 even when it reports a zero point or a decode error
    (contents then meaningless); 2: *_partial take *d_partial as OUT only, *_partial_into added, nbls_tower_op_batch, nbls_verify_batch_msgs_dev.  The bindings check it at load. */

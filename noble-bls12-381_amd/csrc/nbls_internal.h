@@ -36,6 +36,9 @@ extern "C" int nbls_agg_keys_launch(unsigned nkeys, unsigned n, const void* koff
                                     void* stream);   // agg_kernels.hip
 extern "C" int nbls_agg_points_launch(size_t nkeys, unsigned elem_bytes, const void* index, const void* st, const void* ident, const void* src, void* dst, void* stream);
 extern "C" int nbls_agg_status_launch(unsigned n, const void* first_bad, const void* st, const void* zero, void* out, void* stream);
+extern "C" int nbls_grp_zero_launch(unsigned m, const void* zero, const void* fixed96, void* rpk96, void* flag_u32, void* stream);   // grp_kernels.hip
+extern "C" int nbls_grp_interleave_launch(unsigned n, const void* msg_index, const void* pk96, const void* neg_g1, const void* h192, const void* sig192, void* g1x, void* g2x,
+                                          void* stream);
 extern "C" int nbls_msm_keys_launch(unsigned n, unsigned nwin, const void* scalars, void* keys, void* vals, void* stream);
 extern "C" int nbls_msm_decompose_launch(unsigned n, unsigned dims, const void* scalars, void* out, void* stream);
 extern "C" int nbls_msm_sac_launch(unsigned n, const void* scalars, void* out, void* stream);
@@ -85,7 +88,7 @@ struct nbls_ctx {
   uint8_t *F = nullptr, *N = nullptr, *NI = nullptr, *io_g1 = nullptr, *io_g2 = nullptr, *io_f12 = nullptr, *one12 = nullptr;
   uint8_t* T[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // t1..t7 of the final exponentiation, raw Fp12
   // general scratch pool for the codec / hash / sum pipelines (grown on demand)
-  static const int NSB = 48;   // 0 .. 19: see verify_stage; 20 .. 43: nbls_verify_multiple, 44 .. 47: nbls_verify_aggregates (pipelines_multi_verify.cpp)
+  static const int NSB = 51;   // 0 .. 19: see verify_stage; 20 .. 43: nbls_verify_multiple, 44 .. 47: nbls_verify_aggregates, 48 .. 50: the shared-message forms (pipelines_multi_verify.cpp)
   uint8_t* sb[NSB] = {nullptr}; size_t sb_cap[NSB] = {0};
   // staging buffers of the host-buffer entry points (HostIO): kept between calls -- a hipMalloc / hipFree pair per buffer and call cost more than the copies at small batches
   struct IoBlock { void* p; size_t cap; bool busy; }; std::vector<IoBlock> io_pool; size_t io_pool_bytes = 0;
@@ -302,8 +305,11 @@ int verify_stage(nbls_ctx* ctx, size_t n, const void* d_sig96, const void* d_uni
 struct nbls_keyset { int device = 0; size_t n = 0; uint8_t* pts = nullptr; int8_t* st = nullptr; };
 // the keys of nbls_verify_aggregates(_indexed): set j owns entries key_offsets[j] .. key_offsets[j + 1] of pks48 (compressed) or of key_index (into ks)
 struct AggKeys { size_t nkeys = 0, maxset = 0; const uint32_t* key_offsets = nullptr; const uint8_t* pks48 = nullptr; const nbls_keyset* ks = nullptr; const uint32_t* key_index = nullptr; };
-// pipelines_multi_verify.cpp: agg == NULL: one key per set (nbls_verify_multiple, pks48); else the aggregate key of every set
+// the messages of the shared-message forms: msgs / offsets hold n_msgs messages, set i signs message msg_index[i]; maxgroup = the sets of the largest group (the pipeline's own
+// pass over the index fills it in: callers leave 0)
+struct MsgGroups { size_t n_msgs = 0; const uint32_t* msg_index = nullptr; size_t maxgroup = 0; };
+// pipelines_multi_verify.cpp: agg == NULL: one key per set (nbls_verify_multiple, pks48); else the aggregate key of every set.  mg == NULL: one message per set
 int verify_multiple_pipeline(nbls_ctx* ctx, size_t n, const uint8_t* sigs96, const uint8_t* msgs, const uint32_t* offsets, const uint8_t* pks48, const AggKeys* agg,
-    const uint8_t* dst, size_t dst_len, const uint8_t* seed32, int* all_ok, int8_t* status);
+    const MsgGroups* mg, const uint8_t* dst, size_t dst_len, const uint8_t* seed32, int* all_ok, int8_t* status);
 int verify_batch_partial_core(nbls_ctx* ctx, size_t n, const uint8_t* sig96 /* or NULL */, const uint8_t* msgs, const uint32_t* offsets, const uint8_t* pk48,
                                      const uint8_t* dst, size_t dst_len, void* d_dst, void** d_partial, int* zero_flag, int8_t* pk_status);

@@ -68,6 +68,9 @@ def load_library():
     lib.nbls_verify_multiple.argtypes = [vp, sz, vp, vp, vp, vp, vp, sz, vp, C.POINTER(i32), vp]
     lib.nbls_verify_aggregates.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, sz, vp, C.POINTER(i32), vp]
     lib.nbls_verify_aggregates_indexed.argtypes = [vp, vp, sz, vp, vp, vp, vp, vp, vp, sz, vp, C.POINTER(i32), vp]
+    lib.nbls_verify_multiple_shared.argtypes = [vp, sz, vp, sz, vp, vp, vp, vp, vp, sz, vp, C.POINTER(i32), vp]
+    lib.nbls_verify_aggregates_shared.argtypes = [vp, sz, vp, sz, vp, vp, vp, vp, vp, vp, sz, vp, C.POINTER(i32), vp]
+    lib.nbls_verify_aggregates_indexed_shared.argtypes = [vp, vp, sz, vp, sz, vp, vp, vp, vp, vp, vp, sz, vp, C.POINTER(i32), vp]
     lib.nbls_keyset_create.argtypes = [vp, sz, vp, vp, C.POINTER(vp)]
     lib.nbls_keyset_destroy.argtypes = [vp]
     lib.nbls_keyset_destroy.restype = None
@@ -116,6 +119,20 @@ def load_library():
     lib.nbls_timing_enable.argtypes = [vp, i32]
     lib.nbls_timing_read.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_uint32)]
     return lib
+
+
+def group_messages(msgs):
+    """a flat list of messages -> (distinct, index): the distinct messages by byte equality in the order of their first appearance, and index[i] = the position of msgs[i] among
+    them -- the (msgs, msg_index) arguments of Engine.verify_multiple_shared and its twins"""
+    seen, distinct, index = {}, [], []
+    for m in msgs:
+        m = bytes(m)
+        g = seen.get(m)
+        if g is None:
+            g = seen[m] = len(distinct)
+            distinct.append(m)
+        index.append(g)
+    return distinct, index
 
 
 class KeySet:
@@ -459,6 +476,53 @@ class Engine:
         ok = C.c_int(0)
         st = C.create_string_buffer(max(n, 1)) if per_set else None
         self._chk(self.lib.nbls_verify_aggregates_indexed(self.h, keyset.h, n, b''.join(sigs96), blob, offs, idx, koffs, dst, len(dst), seed, C.byref(ok), st))
+        return bool(ok.value), (st.raw[:n] if per_set else None)
+
+    def _shared_args(self, what, sigs96, msgs, msg_index, sets, seed):
+        """-> n, the packed messages, their offsets and the message index as a ctypes uint32 array.  A numpy uint32 array is taken as it is (no copy); a list of 65,536 ints
+        costs ~3 ms to check and convert, a tenth of the call"""
+        n = len(sigs96)
+        if len(msg_index) != n or len(sets) != n or (seed is not None and len(seed) != 32):
+            raise NblsError('%s: %d signatures, %d message indices, %d keys or key sets, seed of %s bytes' % (what, n, len(msg_index), len(sets), None if seed is None else len(seed)))
+        if _np is not None and isinstance(msg_index, _np.ndarray) and msg_index.dtype == _np.uint32 and msg_index.ndim == 1:
+            a = _np.ascontiguousarray(msg_index)
+            idx = (C.c_uint32 * n).from_buffer(a if a.flags.writeable else a.copy())
+        else:
+            if n and not 0 <= min(msg_index) <= max(msg_index) <= 0xffffffff:
+                raise NblsError('%s: a message index outside 0 .. 2^32 - 1' % what)
+            idx = self._u32(msg_index)
+        blob, offs = self._pack(msgs)
+        return n, blob, offs, idx
+
+    def verify_multiple_shared(self, sigs96, msgs, msg_index, pks48, dst=DST_DEFAULT, seed=None, per_set=True):
+        """verify_multiple for sets that share messages (nbls_verify_multiple_shared): msgs holds the distinct messages, set i signs msgs[msg_index[i]]; one hash and one Miller
+        loop per message.  Returns what verify_multiple returns for the expanded input and the same seed.  group_messages turns a flat list into (msgs, msg_index)"""
+        n, blob, offs, idx = self._shared_args('verify_multiple_shared', sigs96, msgs, msg_index, pks48, seed)
+        ok = C.c_int(0)
+        st = C.create_string_buffer(max(n, 1)) if per_set else None
+        self._chk(self.lib.nbls_verify_multiple_shared(self.h, n, b''.join(sigs96), len(msgs), blob, offs, idx, b''.join(pks48), dst, len(dst), seed, C.byref(ok), st))
+        return bool(ok.value), (st.raw[:n] if per_set else None)
+
+    def verify_aggregates_shared(self, sigs96, msgs, msg_index, key_sets, dst=DST_DEFAULT, seed=None, per_set=True):
+        """verify_aggregates for sets that share messages (nbls_verify_aggregates_shared): msgs and msg_index as verify_multiple_shared"""
+        n, blob, offs, idx = self._shared_args('verify_aggregates_shared', sigs96, msgs, msg_index, key_sets, seed)
+        koffs = self._key_offsets(key_sets)
+        pks = b''.join(b''.join(k) for k in key_sets)
+        ok = C.c_int(0)
+        st = C.create_string_buffer(max(n, 1)) if per_set else None
+        self._chk(self.lib.nbls_verify_aggregates_shared(self.h, n, b''.join(sigs96), len(msgs), blob, offs, idx, pks, koffs, dst, len(dst), seed, C.byref(ok), st))
+        return bool(ok.value), (st.raw[:n] if per_set else None)
+
+    def verify_aggregates_indexed_shared(self, keyset, sigs96, msgs, msg_index, index_sets, dst=DST_DEFAULT, seed=None, per_set=True):
+        """verify_aggregates_indexed for sets that share messages (nbls_verify_aggregates_indexed_shared): msgs and msg_index as verify_multiple_shared"""
+        n, blob, offs, idx = self._shared_args('verify_aggregates_indexed_shared', sigs96, msgs, msg_index, index_sets, seed)
+        if keyset.h is None:
+            raise NblsError('verify_aggregates_indexed_shared: the key table is closed')
+        koffs = self._key_offsets(index_sets)
+        kidx = self._u32([i for s in index_sets for i in s])
+        ok = C.c_int(0)
+        st = C.create_string_buffer(max(n, 1)) if per_set else None
+        self._chk(self.lib.nbls_verify_aggregates_indexed_shared(self.h, keyset.h, n, b''.join(sigs96), len(msgs), blob, offs, idx, kidx, koffs, dst, len(dst), seed, C.byref(ok), st))
         return bool(ok.value), (st.raw[:n] if per_set else None)
 
     def verify_batch_dev(self, n, d_sig, d_uniform, d_pk, stream=None):

@@ -107,6 +107,12 @@ export declare function verifyBatch(signature: Hex | PointG2, messages: (Hex | P
 export declare function verifyMultipleSignatures(sets: { publicKey: Hex | PointG1; message: Hex | PointG2; signature: Hex | PointG2 }[]): Promise<boolean>;
 /** verify(signature, message, aggregatePublicKeys(publicKeys)) for every set, checked together by a random linear combination on the GPU; throws where that throws for the first such set */
 export declare function verifyMultipleAggregateSignatures(sets: { publicKeys: (Hex | PointG1)[]; message: Hex | PointG2; signature: Hex | PointG2 }[]): Promise<boolean>;
+/** The two calls of the N-API addon (nbls_napi.node) that verifyMultipleSignatures / verifyMultipleAggregateSignatures take when at least two wire-format sets have equal messages:
+ * msgs / offsets hold the distinct messages, set i signs message msgIndex[i] (nbls_verify_multiple_shared / nbls_verify_aggregates_shared; a type only, the facade does not export the addon) */
+export interface NativeSharedCalls {
+  verifyMultipleSharedAsync(sigs96: Uint8Array, msgs: Uint8Array, offsets: Uint32Array, msgIndex: Uint32Array, pks48: Uint8Array, dst: Uint8Array): Promise<{ ok: boolean; status: Uint8Array }>;
+  verifyAggregatesSharedAsync(sigs96: Uint8Array, msgs: Uint8Array, offsets: Uint32Array, msgIndex: Uint32Array, pks48: Uint8Array, keyOffsets: Uint32Array, dst: Uint8Array): Promise<{ ok: boolean; status: Uint8Array }>;
+}
 
 // additive batched entry points (one engine call each)
 export declare function pairingBatch(Ps: PointG1[] | Uint8Array /* n x 96 affine bytes */, Qs: PointG2[] | Uint8Array /* n x 192 */, withFinalExponent?: boolean, validate?: boolean): { out: Uint8Array /* n x 576 */; status: Uint8Array };

@@ -435,11 +435,32 @@ async function verify(signature, message, publicKey) {
   if (r.code) { const st = r.status[0] || r.status[1]; throw new Error(st >= 10 ? G2_STATUS[st - 10] : G1_STATUS[st]); }
   return Fp12.fromBytes(r.out).equals(Fp12.ONE);
 }
+// Sets that sign the same bytes (the attestations of one slot share a handful of signing roots) need ONE hash-to-G2 and ONE Miller loop per message: wire[i] = [sig, msg, ...] or
+// null for the n sets of a call, w of them wire-format.  Returns null when no two wire sets have equal messages (the caller then makes the call it always made), else the distinct
+// messages packed (msgs, offs) and index[k] = the message of the k-th wire set.  A Map keyed by the message bytes read as a latin1 string, one pass, no spread over n arrays.
+// NBLS_JS_SHARED=0 in the environment: never group (tests compare the two routes).
+function groupWireMessages(wire, w) {
+  if (w < 2 || process.env.NBLS_JS_SHARED === '0') return null;
+  const seen = new Map(), distinct = [], index = new Uint32Array(w);
+  let total = 0;
+  for (let i = 0, k = 0; i < wire.length; i++) {
+    if (!wire[i]) continue;
+    const msg = wire[i][1], key = Buffer.from(msg.buffer, msg.byteOffset, msg.length).toString('latin1');
+    let g = seen.get(key);
+    if (g === undefined) { g = distinct.length; seen.set(key, g); distinct.push(msg); total += msg.length; }
+    index[k++] = g;
+  }
+  if (distinct.length === w) return null;
+  const msgs = new Uint8Array(total), offs = new Uint32Array(distinct.length + 1);
+  for (let g = 0; g < distinct.length; g++) { msgs.set(distinct[g], offs[g]); offs[g + 1] = offs[g] + distinct[g].length; }
+  return { msgs, offs, index };
+}
 // verify(signature_i, message_i, publicKey_i) for n independent sets at once (no reference counterpart; blst's verify_multiple_aggregate_signatures): the wire-format sets
 // take ONE engine call on a worker thread (nbls_verify_multiple: a random linear combination with weights seeded from the OS, n + 1 Miller loops and one final
 // exponentiation, a per-set pass only when that check fails).  Sets with point objects, and every set the engine reports as one where verify throws (a point that does not
 // decode, a zero point), go through verify itself, in index order: the first set that throws there throws the reference's message.  The inputs are packed into buffers
-// allocated once (a spread of 100k+ arrays into one call throws RangeError).
+// allocated once (a spread of 100k+ arrays into one call throws RangeError).  When at least two wire sets have equal messages the call is nbls_verify_multiple_shared on the
+// distinct messages (groupWireMessages): the same statuses, one hash and one Miller loop per message.
 async function verifyMultipleSignatures(sets) {
   if (!Array.isArray(sets) || !sets.length) throw new Error('Expected non-empty array');
   ensureInit();
@@ -462,7 +483,9 @@ async function verifyMultipleSignatures(sets) {
       const [sig, msg, pk] = wire[i];
       sigs.set(sig, 96 * k); pks.set(pk, 48 * k); msgs.set(msg, offs[k]); offs[k + 1] = offs[k] + msg.length; k++;
     }
-    status = (await native.verifyMultipleAsync(sigs, msgs, offs, pks, stringToBytes(htfDefaults.DST))).status;   // worker thread: the event loop keeps running
+    const grp = groupWireMessages(wire, w);
+    status = (grp ? await native.verifyMultipleSharedAsync(sigs, grp.msgs, grp.offs, grp.index, pks, stringToBytes(htfDefaults.DST))
+      : await native.verifyMultipleAsync(sigs, msgs, offs, pks, stringToBytes(htfDefaults.DST))).status;   // worker thread: the event loop keeps running
   }
   let all = true;
   for (let i = 0, k = 0; i < n; i++) {
@@ -480,7 +503,8 @@ async function verifyMultipleSignatures(sets) {
 // ONE engine call on a worker thread (nbls_verify_aggregates: the keys of every set summed on the device, then one random linear combination over the sets with weights seeded from
 // the OS).  Sets with point objects, and every set the engine reports with a status other than 0 or 9 (a key or signature that does not decode, a zero aggregate or signature), go
 // through verify(signature, message, aggregatePublicKeys(publicKeys)) itself, in index order: the first set that throws there throws the reference's message.  The inputs are packed
-// in one pass into buffers allocated once (a spread of 100k+ arrays into one call throws RangeError).
+// in one pass into buffers allocated once (a spread of 100k+ arrays into one call throws RangeError).  Equal messages among the wire sets: nbls_verify_aggregates_shared, as in
+// verifyMultipleSignatures.
 async function verifyMultipleAggregateSignatures(sets) {
   if (!Array.isArray(sets) || !sets.length) throw new Error('Expected non-empty array');
   ensureInit();
@@ -514,7 +538,9 @@ async function verifyMultipleAggregateSignatures(sets) {
       for (let k = 0; k < keys.length; k++, at++) pks.set(keys[k], 48 * at);
       koffs[j + 1] = at; j++;
     }
-    status = (await native.verifyAggregatesAsync(sigs, msgs, offs, pks, koffs, stringToBytes(htfDefaults.DST))).status;   // worker thread: the event loop keeps running
+    const grp = groupWireMessages(wire, w);
+    status = (grp ? await native.verifyAggregatesSharedAsync(sigs, grp.msgs, grp.offs, grp.index, pks, koffs, stringToBytes(htfDefaults.DST))
+      : await native.verifyAggregatesAsync(sigs, msgs, offs, pks, koffs, stringToBytes(htfDefaults.DST))).status;   // worker thread: the event loop keeps running
   }
   let all = true;
   for (let i = 0, j = 0; i < n; i++) {

@@ -2,7 +2,7 @@
  * nbls_napi.c -- thin N-API addon: exposes the C ABI of libnbls.so (include/nbls.h) to Node.  No arithmetic here.
  * libnbls.so is loaded with dlopen at module init so the addon builds with plain gcc (no HIP needed):
  *     gcc -shared -fPIC -I/usr/include/node -I../../include nbls_napi.c -o nbls_napi.node -ldl
- * Calls are synchronous (they block for the duration of the GPU work) except verifyBatchAsync (and signBatchAsync, verifyMultipleAsync, verifyAggregatesAsync), which runs on a libuv worker thread
+ * Calls are synchronous (they block for the duration of the GPU work) except verifyBatchAsync (and signBatchAsync, verifyMultipleAsync, verifyAggregatesAsync, verifyMultipleSharedAsync, verifyAggregatesSharedAsync), which runs on a libuv worker thread
  * (napi_create_async_work) and resolves a Promise: the facade's verifyBatch uses it for wire-format inputs (the calls that can take tens of milliseconds).  Typed arrays are passed by reference (napi_get_typedarray_info), no copies.
  */
 #include <node_api.h>
@@ -19,7 +19,7 @@ SYM(nbls_init) SYM(nbls_destroy) SYM(nbls_strerror) SYM(nbls_pairing_batch) SYM(
 SYM(nbls_g1_validate_batch) SYM(nbls_g2_validate_batch) SYM(nbls_g1_decompress_batch) SYM(nbls_g2_decompress_batch)
 SYM(nbls_hash_to_g2_batch) SYM(nbls_g1_sum) SYM(nbls_g2_sum) SYM(nbls_verify_batch) SYM(nbls_g1_mul_batch) SYM(nbls_g2_mul_batch) SYM(nbls_sign_batch) SYM(nbls_hash_to_g1_batch) SYM(nbls_encode_to_g1_batch) SYM(nbls_encode_to_g2_batch) SYM(nbls_g1_msm) SYM(nbls_g2_msm)
 SYM(nbls_init_multi) SYM(nbls_destroy_multi) SYM(nbls_multi_device_count) SYM(nbls_multi_context) SYM(nbls_multi_pairing_batch) SYM(nbls_multi_miller_product) SYM(nbls_multi_verify_batch)
-SYM(nbls_g2_prepare) SYM(nbls_pairing_prepared) SYM(nbls_verify_multiple) SYM(nbls_verify_aggregates)
+SYM(nbls_g2_prepare) SYM(nbls_pairing_prepared) SYM(nbls_verify_multiple) SYM(nbls_verify_aggregates) SYM(nbls_verify_multiple_shared) SYM(nbls_verify_aggregates_shared)
 SYM(nbls_g1_from_hex_batch) SYM(nbls_g2_from_hex_batch) SYM(nbls_g2_from_signature_batch) SYM(nbls_g1_clear_cofactor_batch) SYM(nbls_g2_clear_cofactor_batch)
 static nbls_ctx* ctx;
 static nbls_multi* multi;   /* several GPUs behind one handle (initMulti): ctx is then its first context; the batch calls shard over all of them */
@@ -325,6 +325,65 @@ static napi_value VerifyAggregatesAsync(napi_env env, napi_callback_info info) {
   return promise;
 }
 
+/* verifyMultipleSharedAsync(sigs96, msgs, offsets, msgIndex, pks48, dst) and verifyAggregatesSharedAsync(sigs96, msgs, offsets, msgIndex, pks48, keyOffsets, dst)
+ * -> Promise<{ok, status}>: nbls_verify_multiple_shared / nbls_verify_aggregates_shared (msgs / offsets hold the DISTINCT messages, set i signs message msgIndex[i]: one hash and one
+ * Miller loop per message) on a libuv worker thread with a context of the pool, like their twins.  n = the length of msgIndex (a Uint32Array); the library checks the index itself. */
+typedef struct {
+  napi_async_work work; napi_deferred deferred; napi_ref refs[8]; int nrefs;
+  const uint8_t *sigs, *msgs, *pks, *dst; const uint32_t *offs, *idx, *koffs /* NULL: one key per set */; size_t n, n_msgs, dst_len; int8_t* st;
+  nbls_ctx* c; int rc, ok;
+} shared_verify_job;
+static void shared_verify_execute(napi_env env, void* data) { shared_verify_job* j = (shared_verify_job*)data; (void)env;
+  j->rc = j->koffs ? p_nbls_verify_aggregates_shared(j->c, j->n, j->sigs, j->n_msgs, j->msgs, j->offs, j->idx, j->pks, j->koffs, j->dst, j->dst_len, NULL, &j->ok, j->st)
+                   : p_nbls_verify_multiple_shared(j->c, j->n, j->sigs, j->n_msgs, j->msgs, j->offs, j->idx, j->pks, j->dst, j->dst_len, NULL, &j->ok, j->st); }
+static void shared_verify_complete(napi_env env, napi_status status, void* data) {
+  shared_verify_job* j = (shared_verify_job*)data;
+  napi_value st = NULL; napi_get_reference_value(env, j->refs[j->nrefs - 1], &st);
+  for (int i = 0; i < j->nrefs; i++) napi_delete_reference(env, j->refs[i]);
+  if (status != napi_ok || j->rc) {
+    char m[128]; snprintf(m, sizeof m, "nbls: %s (code %d)", p_nbls_strerror ? p_nbls_strerror(j->rc) : "error", j->rc);
+    napi_value msg, err; napi_create_string_utf8(env, m, NAPI_AUTO_LENGTH, &msg); napi_create_error(env, NULL, msg, &err); napi_reject_deferred(env, j->deferred, err);
+  } else {
+    napi_value o, k; napi_create_object(env, &o); napi_get_boolean(env, j->ok != 0, &k);
+    napi_set_named_property(env, o, "ok", k); napi_set_named_property(env, o, "status", st); napi_resolve_deferred(env, j->deferred, o);
+  }
+  napi_delete_async_work(env, j->work); free(j);
+}
+static napi_value shared_verify_queue(napi_env env, shared_verify_job* j, napi_value* argv, int nargs, napi_value vst, const char* what) {
+  j->c = pool_take(); j->nrefs = nargs + 1;
+  for (int i = 0; i < nargs; i++) napi_create_reference(env, argv[i], 1, &j->refs[i]);
+  napi_create_reference(env, vst, 1, &j->refs[nargs]);
+  napi_value promise, name; napi_create_promise(env, &j->deferred, &promise); napi_create_string_utf8(env, what, NAPI_AUTO_LENGTH, &name);
+  if (napi_create_async_work(env, NULL, name, shared_verify_execute, shared_verify_complete, j, &j->work) != napi_ok || napi_queue_async_work(env, j->work) != napi_ok) {
+    for (int i = 0; i < j->nrefs; i++) napi_delete_reference(env, j->refs[i]); free(j); napi_throw_error(env, NULL, "napi_create_async_work failed"); return NULL; }
+  return promise;
+}
+static napi_value VerifyMultipleSharedAsync(napi_env env, napi_callback_info info) {
+  ARGS(6); NEED_CTX(); BYTES(0, sigs, ls); BYTES(1, msgs, lm); BYTES(2, offs, lo); BYTES(3, idx, li); BYTES(4, pks, lp); BYTES(5, dst, ld); (void)lm;
+  COUNT_FROM_OFFSETS(n_msgs, lo);
+  const size_t n = li / 4;
+  if (li % 4 || lp != n * 48 || ls != n * 96) { napi_throw_range_error(env, NULL, "bad message index, signature or public key array length"); return NULL; }
+  uint8_t* st; napi_value vst = new_u8(env, n ? n : 1, &st); ALLOCATED(vst);
+  shared_verify_job* j = (shared_verify_job*)calloc(1, sizeof *j); if (!j) { napi_throw_error(env, NULL, "out of memory"); return NULL; }
+  j->sigs = sigs; j->msgs = msgs; j->offs = (const uint32_t*)offs; j->idx = (const uint32_t*)idx; j->pks = pks; j->dst = dst; j->dst_len = ld; j->n = n; j->n_msgs = n_msgs; j->st = (int8_t*)st;
+  return shared_verify_queue(env, j, argv, 6, vst, "nbls_verify_multiple_shared");
+}
+static napi_value VerifyAggregatesSharedAsync(napi_env env, napi_callback_info info) {
+  ARGS(7); NEED_CTX(); BYTES(0, sigs, ls); BYTES(1, msgs, lm); BYTES(2, offs, lo); BYTES(3, idx, li); BYTES(4, pks, lp); BYTES(5, koffs, lk); BYTES(6, dst, ld); (void)lm;
+  COUNT_FROM_OFFSETS(n_msgs, lo);
+  const size_t n = li / 4;
+  if (li % 4 || ls != n * 96 || lk != (n + 1) * 4) { napi_throw_range_error(env, NULL, "bad message index, signature or key offset array length"); return NULL; }
+  {   /* the keys the offsets name must be in pks48 (the library checks the rest: order, empty sets, count) */
+    const uint32_t* ko = (const uint32_t*)koffs;
+    if (ko[n] < ko[0] || (size_t)ko[n] * 48 > lp) { napi_throw_range_error(env, NULL, "key offsets run past the public key array"); return NULL; }
+  }
+  uint8_t* st; napi_value vst = new_u8(env, n ? n : 1, &st); ALLOCATED(vst);
+  shared_verify_job* j = (shared_verify_job*)calloc(1, sizeof *j); if (!j) { napi_throw_error(env, NULL, "out of memory"); return NULL; }
+  j->sigs = sigs; j->msgs = msgs; j->offs = (const uint32_t*)offs; j->idx = (const uint32_t*)idx; j->pks = pks; j->koffs = (const uint32_t*)koffs; j->dst = dst; j->dst_len = ld; j->n = n;
+  j->n_msgs = n_msgs; j->st = (int8_t*)st;
+  return shared_verify_queue(env, j, argv, 7, vst, "nbls_verify_aggregates_shared");
+}
+
 /* signBatchAsync(msgs, offsets, dst, keys32) -> Promise<{out: n*192 affine signature points, status}>: nbls_sign_batch on a libuv worker thread (the reference's
  * sign is async, index.ts:744-752).  The output arrays are created here, on the main thread, and kept alive by references like the inputs. */
 typedef struct {
@@ -370,7 +429,7 @@ static napi_value ModuleInit(napi_env env, napi_value exports) {
   LOAD(nbls_init) LOAD(nbls_destroy) LOAD(nbls_strerror) LOAD(nbls_pairing_batch) LOAD(nbls_miller_product) LOAD(nbls_final_exp_batch)
   LOAD(nbls_g1_validate_batch) LOAD(nbls_g2_validate_batch) LOAD(nbls_g1_decompress_batch) LOAD(nbls_g2_decompress_batch)
   LOAD(nbls_hash_to_g2_batch) LOAD(nbls_g1_sum) LOAD(nbls_g2_sum) LOAD(nbls_verify_batch) LOAD(nbls_g1_mul_batch) LOAD(nbls_g2_mul_batch) LOAD(nbls_sign_batch) LOAD(nbls_hash_to_g1_batch) LOAD(nbls_encode_to_g1_batch) LOAD(nbls_encode_to_g2_batch) LOAD(nbls_g1_msm) LOAD(nbls_g2_msm)
-  LOAD(nbls_init_multi) LOAD(nbls_destroy_multi) LOAD(nbls_multi_device_count) LOAD(nbls_multi_context) LOAD(nbls_multi_pairing_batch) LOAD(nbls_multi_miller_product) LOAD(nbls_multi_verify_batch) LOAD(nbls_g2_prepare) LOAD(nbls_pairing_prepared) LOAD(nbls_verify_multiple) LOAD(nbls_verify_aggregates)
+  LOAD(nbls_init_multi) LOAD(nbls_destroy_multi) LOAD(nbls_multi_device_count) LOAD(nbls_multi_context) LOAD(nbls_multi_pairing_batch) LOAD(nbls_multi_miller_product) LOAD(nbls_multi_verify_batch) LOAD(nbls_g2_prepare) LOAD(nbls_pairing_prepared) LOAD(nbls_verify_multiple) LOAD(nbls_verify_aggregates) LOAD(nbls_verify_multiple_shared) LOAD(nbls_verify_aggregates_shared)
   LOAD(nbls_g1_from_hex_batch) LOAD(nbls_g2_from_hex_batch) LOAD(nbls_g2_from_signature_batch) LOAD(nbls_g1_clear_cofactor_batch) LOAD(nbls_g2_clear_cofactor_batch)
   {   /* the ABI the addon was written against (include/nbls.h NBLS_ABI_VERSION): an older or newer library is refused at load instead of misread at run time */
     int (*abi)(void) = (int (*)(void))dlsym(lib, "nbls_abi_version");
@@ -382,7 +441,8 @@ static napi_value ModuleInit(napi_env env, napi_value exports) {
     {"g1Validate", 0, G1Validate, 0, 0, 0, napi_enumerable, 0}, {"g2Validate", 0, G2Validate, 0, 0, 0, napi_enumerable, 0}, {"g1Sum", 0, G1Sum, 0, 0, 0, napi_enumerable, 0},
     {"g2Sum", 0, G2Sum, 0, 0, 0, napi_enumerable, 0}, {"hashToG2", 0, HashToG2, 0, 0, 0, napi_enumerable, 0}, {"verifyBatch", 0, VerifyBatch, 0, 0, 0, napi_enumerable, 0},
     {"g1Mul", 0, G1Mul, 0, 0, 0, napi_enumerable, 0}, {"g2Mul", 0, G2Mul, 0, 0, 0, napi_enumerable, 0}, {"signBatch", 0, SignBatch, 0, 0, 0, napi_enumerable, 0},
-    {"hashToCurve", 0, HashToCurve, 0, 0, 0, napi_enumerable, 0}, {"g1Msm", 0, G1Msm, 0, 0, 0, napi_enumerable, 0}, {"g2Msm", 0, G2Msm, 0, 0, 0, napi_enumerable, 0}, {"verifyBatchAsync", 0, VerifyBatchAsync, 0, 0, 0, napi_enumerable, 0}, {"verifyMultipleAsync", 0, VerifyMultipleAsync, 0, 0, 0, napi_enumerable, 0}, {"verifyAggregatesAsync", 0, VerifyAggregatesAsync, 0, 0, 0, napi_enumerable, 0}, {"signBatchAsync", 0, SignBatchAsync, 0, 0, 0, napi_enumerable, 0},
+    {"hashToCurve", 0, HashToCurve, 0, 0, 0, napi_enumerable, 0}, {"g1Msm", 0, G1Msm, 0, 0, 0, napi_enumerable, 0}, {"g2Msm", 0, G2Msm, 0, 0, 0, napi_enumerable, 0}, {"verifyBatchAsync", 0, VerifyBatchAsync, 0, 0, 0, napi_enumerable, 0}, {"verifyMultipleAsync", 0, VerifyMultipleAsync, 0, 0, 0, napi_enumerable, 0}, {"verifyAggregatesAsync", 0, VerifyAggregatesAsync, 0, 0, 0, napi_enumerable, 0},
+    {"verifyMultipleSharedAsync", 0, VerifyMultipleSharedAsync, 0, 0, 0, napi_enumerable, 0}, {"verifyAggregatesSharedAsync", 0, VerifyAggregatesSharedAsync, 0, 0, 0, napi_enumerable, 0}, {"signBatchAsync", 0, SignBatchAsync, 0, 0, 0, napi_enumerable, 0},
     {"initMulti", 0, InitMulti, 0, 0, 0, napi_enumerable, 0}, {"g2Prepare", 0, G2Prepare, 0, 0, 0, napi_enumerable, 0}, {"pairingPrepared", 0, PairingPrepared, 0, 0, 0, napi_enumerable, 0},
     {"decodePoints", 0, DecodePoints, 0, 0, 0, napi_enumerable, 0}, {"clearCofactor", 0, ClearCofactor, 0, 0, 0, napi_enumerable, 0}};
   napi_define_properties(env, exports, sizeof d / sizeof d[0], d);
