@@ -1,6 +1,7 @@
-// nbls_internal.h -- what the translation units of the runtime share (round 6: csrc/nbls_api.cpp, 2,000 lines with every pipeline in one unit, split into
-// runtime.cpp / tuning.cpp / pipelines_pairing.cpp / pipelines_codec.cpp / pipelines_verify.cpp; pool and multi-device handles: nbls_multi.cpp): the context, the
-// launch helpers and the device-side pipelines the exported entry points are built from.  Internal functions have hidden visibility (csrc/Makefile: -fvisibility=hidden).
+// nbls_internal.h -- what the translation units of the runtime share (runtime.cpp / tuning.cpp / pipelines_pairing.cpp / pipelines_codec.cpp / pipelines_verify.cpp /
+// pipelines_multi_verify.cpp; pool and multi-device handles: nbls_multi.cpp): the context, the map of its scratch slots (enum Slot: the one place that says which chain owns
+// which slot, checked at compile time), the launch helpers and the device-side pipelines the exported entry points are built from.  Internal functions have hidden visibility
+// (csrc/Makefile: -fvisibility=hidden).
 #pragma once
 #include <hip/hip_runtime.h>
 #include "config.h"
@@ -63,6 +64,69 @@ static const size_t LINE_BYTES = (size_t)LINE_ELEMS * RAW;   // one line table: 
 static const size_t SPLIT_MILLER_MIN = 4097;
 static const size_t LINES_CHUNK = 131072;   // pairs whose line tables are in HBM at a time (3.4 GB of the 288); larger batches run chunk by chunk on the same stream
 
+// ---- BEGIN scratch slots -----------------------------------------------------------------------------------------------------------------------------------
+// The scratch pool of a context (nbls_ctx::sb, handed out by need()) is indexed by these names.  need() frees and reallocates a slot that has to grow, so chains that run side
+// by side on different streams of one call must never share a slot, and no slot may be regrown under a kernel in flight.  This block is the whole map: who owns which slot, the
+// slots every chain touches (the masks) and the chains that run concurrently (the static_asserts).  A new chain takes new enumerators in front of NSB, gets a mask, and is
+// asserted against everything it runs beside.  The numbers are the indices into sb[]: they fix the order of allocation and are never reused for something else.
+enum Slot {
+  // the call's own stream, one pipeline at a time: hash-to-curve (field elements, exponentiation inputs, powers, points), the point sum's two halves, the ladder's points (its
+  // digits in SB_WORK_C / SB_WORK_B when the caller brings none), the decoders and the MSM when they run alone (DEC_MAIN, MSM_MAIN)
+  SB_WORK_A = 0, SB_WORK_B = 1, SB_WORK_C = 2, SB_WORK_D = 3,
+  SB_NORM = 4, SB_NORM_INV = 5,   // norms of projective points and their inverses
+  SB_POINT_ST = 6,                // statuses of the affine program that nobody reads (hash-to-curve)
+  SB_MSGS = 7,                    // dev_expand: the message bytes; sign_points: the recoded keys, made on side2 beside the hash chain and read by the ladder after it
+  SB_UNIFORM = 8,                 // expand_message_xmd output
+  SB_STAGED = 9,                  // the one staged input block of verifyBatch and of the multi-verify calls
+  SB_VB_PAIRS = 10,               // verifyBatch: pairs (g1 | g2), result, statuses; the two-stage route reads it between its stages, where the context lock is dropped
+  SB_POW_TABLE = 11,              // run_pow's table when the caller passes none; hash-to-G2's
+  SB_OFFS_DST = 12,               // dev_expand: offsets and domain-separation tag
+  SB_CLEAR_S = 13,                // PointG2.clearCofactor's third array (dev_clear_g2 S)
+  SB_KEYS_X = 14, SB_KEYS_R = 15, SB_KEYS_C = 16, SB_KEYS_POW = 17,   // DEC_KEYS: key decompression beside the hash chain (verifyBatch, the multi-verify calls)
+  SB_SWU_STATE = 18, SB_SWU_POINTS = 19,                              // hash-to-G2: SWU state per message, the two points of a message
+  // verify_multiple_pipeline (pipelines_multi_verify.cpp)
+  SB_RLC_WEIGHTS = 20,
+  SB_RLC_PAIRS = 21,              // the decoded points, the pairs and what is read back
+  SB_RLC_PER_SET = 22,            // per-set pass: the interleaved pairs, the n final exponentiations and the verdict bytes
+  SB_RLC_KEYS_PROJ = 23, SB_RLC_KEYS_NORM = 24, SB_RLC_KEYS_INV = 25,   // the ladder's projective points (+ the affine program's unused statuses), norms and their inverses
+  SB_SIGS_X = 26, SB_SIGS_R = 27, SB_SIGS_C = 28, SB_SIGS_POW = 29,     // DEC_SIGS: signature decompression
+  SB_RLC_MSM = 30,                // MSM_RLC: 30 .. 39, 41 and 43 (MsmSlots::Buf); 40 and 42 are unused
+  SB_AGG_DECODED = 44, SB_AGG_POINTS = 45, SB_AGG_LABELS = 46, SB_AGG_SUMS = 47,   // SEG_AGG: the per-set key sums of nbls_verify_aggregates (+ the decoded keys in front of them)
+  SB_GRP_POINTS = 48, SB_GRP_LABELS = 49, SB_GRP_SUMS = 50,                        // SEG_GRP: the per-message key sums of the shared-message forms
+  NSB
+};
+static_assert(NSB == 51, "sb[] indices do not shift");
+constexpr uint64_t slot_bit(int i) { return (uint64_t)1 << i; }
+template <typename... S> constexpr uint64_t slots(S... s) { return (slot_bit(s) | ...); }
+// one instance of dev_decompress: three arrays of field elements and the exponentiation table
+struct DecSlots { Slot x, r, c, pow; constexpr uint64_t mask() const { return slots(x, r, c, pow); } };
+constexpr DecSlots DEC_MAIN{SB_WORK_A, SB_WORK_B, SB_WORK_C, SB_POW_TABLE}, DEC_KEYS{SB_KEYS_X, SB_KEYS_R, SB_KEYS_C, SB_KEYS_POW}, DEC_SIGS{SB_SIGS_X, SB_SIGS_R, SB_SIGS_C, SB_SIGS_POW};
+// one instance of dev_msm: its buffers at fixed distances from a base slot (the gaps keep MSM_MAIN off SB_VB_PAIRS and SB_OFFS_DST)
+struct MsmSlots {
+  enum Buf { POINTS = 0, SORTED = 1, WINDOW_SUMS = 2, KEYS = 3, NORM = 4, NORM_INV = 5, TEMP = 6, BUCKETS = 7, SLICES = 8, SLICES_HALF = 9, COUNTERS = 11, SPLIT_SCALARS = 13 };
+  Slot base;
+  constexpr Slot operator[](Buf b) const { return (Slot)(base + b); }
+  constexpr uint64_t mask() const { return slots(POINTS, SORTED, WINDOW_SUMS, KEYS, NORM, NORM_INV, TEMP, BUCKETS, SLICES, SLICES_HALF, COUNTERS, SPLIT_SCALARS) << base; }
+};
+constexpr MsmSlots MSM_MAIN{SB_WORK_A}, MSM_RLC{SB_RLC_MSM};
+// one instance of segment_sums (pipelines_multi_verify.cpp): gathered points | ids, ranks, pair lists, counters, statuses | sums, norms, inverses.  zero_with_sums: the zero
+// flags of the sums lie behind the inverses (else behind the statuses): the two instances keep the layouts they were written with
+struct SegSlots { Slot points, labels, sums; bool zero_with_sums; constexpr uint64_t mask() const { return slots(points, labels, sums); } };
+constexpr SegSlots SEG_AGG{SB_AGG_POINTS, SB_AGG_LABELS, SB_AGG_SUMS, false}, SEG_GRP{SB_GRP_POINTS, SB_GRP_LABELS, SB_GRP_SUMS, true};
+// what every chain touches
+constexpr uint64_t M_HASH_G2 = slots(SB_WORK_A, SB_WORK_B, SB_WORK_C, SB_WORK_D, SB_NORM, SB_NORM_INV, SB_POINT_ST, SB_POW_TABLE, SB_CLEAR_S, SB_SWU_STATE, SB_SWU_POINTS);   // dev_hash_to_g2
+constexpr uint64_t M_LADDER = slots(SB_WORK_A, SB_WORK_B, SB_WORK_C, SB_NORM, SB_NORM_INV);                 // dev_point_mul
+constexpr uint64_t M_VB_MAIN = slots(SB_VB_PAIRS, SB_UNIFORM) | M_HASH_G2;                                 // verify_stage / verify_pipeline on the call's stream (and its sub-batch streams)
+constexpr uint64_t M_RLC_MAIN = slots(SB_STAGED, SB_UNIFORM, SB_RLC_WEIGHTS, SB_RLC_PAIRS, SB_RLC_PER_SET) | M_HASH_G2;   // verify_multiple_pipeline on the call's stream
+constexpr uint64_t M_RLC_SIDE2 = DEC_KEYS.mask() | slots(SB_AGG_DECODED, SB_RLC_KEYS_PROJ, SB_RLC_KEYS_NORM, SB_RLC_KEYS_INV) | SEG_AGG.mask() | SEG_GRP.mask();   // its key chain
+constexpr uint64_t M_RLC_SIDE = DEC_SIGS.mask() | MSM_RLC.mask();                                           // its signature chain
+// what runs side by side
+static_assert(!(M_VB_MAIN & DEC_KEYS.mask()), "verifyBatch decodes its keys (side2, or the sub-batch's own stream) beside the hash chain");
+static_assert(!(M_RLC_MAIN & M_RLC_SIDE2) && !(M_RLC_MAIN & M_RLC_SIDE) && !(M_RLC_SIDE & M_RLC_SIDE2), "verify_multiple_pipeline: the chains on s, side and side2 run side by side");
+static_assert(!(SEG_AGG.mask() & SEG_GRP.mask()), "the per-message sums follow the per-set sums on side2 with nothing regrown under a kernel in flight");
+static_assert(!(slot_bit(SB_MSGS) & (M_HASH_G2 | M_LADDER)), "sign_points: the keys are recoded on side2 beside the hash chain, and the digits outlive it until the ladder has read them");
+static_assert(!(slot_bit(SB_VB_PAIRS) & MSM_MAIN.mask()), "verifyBatch keeps its pairs across the calls of its two-stage route: dev_msm on the main slots must not regrow them");
+// ---- END scratch slots -------------------------------------------------------------------------------------------------------------------------------------
 #define EXPORT extern "C" __attribute__((visibility("default")))
 extern std::recursive_mutex g_null_mu;   // locked in place of a context's mutex when the caller passed no context (the call then fails with NBLS_EINVAL)
 
@@ -88,7 +152,6 @@ struct nbls_ctx {
   uint8_t *F = nullptr, *N = nullptr, *NI = nullptr, *io_g1 = nullptr, *io_g2 = nullptr, *io_f12 = nullptr, *one12 = nullptr;
   uint8_t* T[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // t1..t7 of the final exponentiation, raw Fp12
   // general scratch pool for the codec / hash / sum pipelines (grown on demand)
-  static const int NSB = 51;   // 0 .. 19: see verify_stage; 20 .. 43: nbls_verify_multiple, 44 .. 47: nbls_verify_aggregates, 48 .. 50: the shared-message forms (pipelines_multi_verify.cpp)
   uint8_t* sb[NSB] = {nullptr}; size_t sb_cap[NSB] = {0};
   // staging buffers of the host-buffer entry points (HostIO): kept between calls -- a hipMalloc / hipFree pair per buffer and call cost more than the copies at small batches
   struct IoBlock { void* p; size_t cap; bool busy; }; std::vector<IoBlock> io_pool; size_t io_pool_bytes = 0;
@@ -160,6 +223,9 @@ struct nbls_ctx {
 };
 
 #define HIPCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { ctx->last_hip = (int)e_; return NBLS_EHIP; } } while (0)
+// the same for the extern "C" *_launch wrappers of the .hip files, which return the launch's hipError_t as an int.  They read it with hipGetLastError(), which also CLEARS it: the
+// code has to be taken from the wrapper's return value, a second hipGetLastError() at the call site yields 0
+#define LAUNCHCHK(call) do { int e_ = (call); if (e_) { ctx->last_hip = e_; return NBLS_EHIP; } } while (0)
 
 // A chain: several programs executed back to back by ONE launch (aot.h): every wavefront runs them in order for its own items, the values between them pass
 // through the HBM scratch buffers the separate launches would use.  Falls back to one launch per program when some program is not on an ahead-of-time kernel,
@@ -248,7 +314,7 @@ int ensure_scratch(nbls_ctx* ctx, size_t n);
 int ensure_expc_scratch(nbls_ctx* ctx);
 int ensure_io(nbls_ctx* ctx, size_t n);
 int ensure_lines(nbls_ctx* ctx, size_t n);
-int need(nbls_ctx* ctx, int i, size_t bytes, uint8_t** out);
+int need(nbls_ctx* ctx, Slot i, size_t bytes, uint8_t** out);
 int ensure_side(nbls_ctx* ctx);
 int ensure_side2(nbls_ctx* ctx);
 int ensure_pinned(nbls_ctx* ctx, size_t bytes);
@@ -268,9 +334,11 @@ int acc_prepared(nbls_ctx* ctx, size_t n, const void* d_g1, const void* d_tables
 int partial_buffer(nbls_ctx* ctx, void* d_dst, uint8_t** dst);
 int miller_product_partial_core(nbls_ctx* ctx, size_t n, const uint8_t* g1, const uint8_t* g2, int validate, void* d_dst, void** d_partial, int8_t* status);
 int dev_validate(nbls_ctx* ctx, bool g2, size_t n, const void* d_pts, void* d_status, hipStream_t s);
-int dev_decompress(nbls_ctx* ctx, bool g2, size_t n, const void* d_in, void* d_out, void* d_status, hipStream_t s, int slot0 = 0, int pow_slot = 11, int mode = 0, size_t io = 0, size_t ntot = 0);
+int dev_decompress(nbls_ctx* ctx, bool g2, size_t n, const void* d_in, void* d_out, void* d_status, hipStream_t s, const DecSlots& sl = DEC_MAIN, int mode = 0, size_t io = 0,
+    size_t ntot = 0);
 int dev_clear_g2(nbls_ctx* ctx, size_t n, void* in, uint8_t* base, uint8_t* S, void* out, void* N, hipStream_t s);
 int dev_hash_to_g2(nbls_ctx* ctx, size_t n, const void* d_uniform, void* d_out, hipStream_t s, size_t io = 0, size_t ntot = 0, uint8_t** proj = nullptr);
+int to_affine(nbls_ctx* ctx, bool g2, size_t n, const void* Pj, void* N, void* NI, void* d_out, void* d_status, hipStream_t s, bool norm = true);
 int dev_point_sum(nbls_ctx* ctx, bool g2, size_t n, const void* d_pts, void* d_out, void* d_status, hipStream_t s);
 int decompress_host(nbls_ctx* ctx, bool g2, size_t n, const uint8_t* in, uint8_t* out, int8_t* status);
 int dev_expand(nbls_ctx* ctx, size_t n, const uint8_t* msgs, const uint32_t* offs, const uint8_t* dst, size_t dst_len, uint8_t** d_uniform, hipStream_t s, unsigned len_in_bytes = 256);
@@ -288,7 +356,8 @@ int ensure_g1_fixed(nbls_ctx* ctx, hipStream_t s);
 int sign_points(nbls_ctx* ctx, size_t n, const void* d_uniform, void* h, const void* d_keys32, void* d_out192, void* d_status, hipStream_t s);
 bool scalar_is_zero_mod_r(const uint8_t* k32);
 int mul_host(nbls_ctx* ctx, bool g2, size_t n, const uint8_t* pts, const uint8_t* scalars32, uint8_t* out, int8_t* status);
-int dev_msm(nbls_ctx* ctx, bool g2, size_t n, const void* d_pts, const void* d_scalars, unsigned nbits, void* d_out, void* d_status, hipStream_t s, int slot0 = 0);
+int dev_msm(nbls_ctx* ctx, bool g2, size_t n, const void* d_pts, const void* d_scalars, unsigned nbits, void* d_out, void* d_status, hipStream_t s, const MsmSlots& sl = MSM_MAIN);
+int segmented_sum(nbls_ctx* ctx, bool g2, size_t count, const uint32_t* keys, const uint32_t* rank, uint32_t* list, uint32_t* counters, uint8_t* P, size_t maxrun, hipStream_t s);
 unsigned scalars_bit_length(size_t n, const uint8_t* k32);
 int msm_host(nbls_ctx* ctx, bool g2, size_t n, const uint8_t* pts, const uint8_t* scalars32, uint8_t* out, int8_t* status);
 int dst_on_device(nbls_ctx* ctx, const uint8_t* dst, size_t* dst_len, hipStream_t s, uint8_t** dd);
@@ -303,13 +372,16 @@ int verify_decide(const std::vector<int8_t>& st, size_t n, const uint8_t* out, i
 int verify_stage(nbls_ctx* ctx, size_t n, const void* d_sig96, const void* d_uniform, const void* d_pk48, std::vector<int8_t>& st, void* stream);
 // a table of decoded keys (nbls_keyset_create): raw projective points, the identity stored for zero keys and keys that did not decode, and the decoder's status of every key
 struct nbls_keyset { int device = 0; size_t n = 0; uint8_t* pts = nullptr; int8_t* st = nullptr; };
-// the keys of nbls_verify_aggregates(_indexed): set j owns entries key_offsets[j] .. key_offsets[j + 1] of pks48 (compressed) or of key_index (into ks)
-struct AggKeys { size_t nkeys = 0, maxset = 0; const uint32_t* key_offsets = nullptr; const uint8_t* pks48 = nullptr; const nbls_keyset* ks = nullptr; const uint32_t* key_index = nullptr; };
-// the messages of the shared-message forms: msgs / offsets hold n_msgs messages, set i signs message msg_index[i]; maxgroup = the sets of the largest group (the pipeline's own
-// pass over the index fills it in: callers leave 0)
-struct MsgGroups { size_t n_msgs = 0; const uint32_t* msg_index = nullptr; size_t maxgroup = 0; };
-// pipelines_multi_verify.cpp: agg == NULL: one key per set (nbls_verify_multiple, pks48); else the aggregate key of every set.  mg == NULL: one message per set
-int verify_multiple_pipeline(nbls_ctx* ctx, size_t n, const uint8_t* sigs96, const uint8_t* msgs, const uint32_t* offsets, const uint8_t* pks48, const AggKeys* agg,
-    const MsgGroups* mg, const uint8_t* dst, size_t dst_len, const uint8_t* seed32, int* all_ok, int8_t* status);
+// the keys of nbls_verify_aggregates(_indexed): set j owns entries key_offsets[j] .. key_offsets[j + 1] of the call's compressed keys (MultiVerifyIn::pks48) or of key_index (into ks);
+// nkeys and maxset are filled in by the argument check
+struct AggKeys { const uint32_t* key_offsets = nullptr; const nbls_keyset* ks = nullptr; const uint32_t* key_index = nullptr; size_t nkeys = 0, maxset = 0; };
+// the messages of the shared-message forms: msgs / offsets hold n_msgs messages, set i signs message msg_index[i]
+struct MsgGroups { size_t n_msgs = 0; const uint32_t* msg_index = nullptr; };
+// pipelines_multi_verify.cpp: what the six multi-verify entry points hand to their one pipeline.  agg == NULL: one key per set (pks48 = n keys); else the aggregate key of every
+// set.  mg == NULL: one message per set
+struct MultiVerifyIn {
+  size_t n; const uint8_t *sigs96, *msgs; const uint32_t* offsets; const uint8_t* pks48; const AggKeys* agg; const MsgGroups* mg; const uint8_t* dst; size_t dst_len; const uint8_t* seed32;
+};
+int verify_multiple_pipeline(nbls_ctx* ctx, const MultiVerifyIn& in, int* all_ok, int8_t* status);
 int verify_batch_partial_core(nbls_ctx* ctx, size_t n, const uint8_t* sig96 /* or NULL */, const uint8_t* msgs, const uint32_t* offsets, const uint8_t* pk48,
                                      const uint8_t* dst, size_t dst_len, void* d_dst, void** d_partial, int* zero_flag, int8_t* pk_status);

@@ -9,20 +9,26 @@ int dev_validate(nbls_ctx* ctx, bool g2, size_t n, const void* d_pts, void* d_st
   return g2 ? run(ctx, P_G2_VALIDATE, n, {B(1, d_pts, 192), B(7, d_status, 1)}, s) : run(ctx, P_G1_VALIDATE, n, {B(0, d_pts, 96), B(7, d_status, 1)}, s);
 }
 // PointG1.fromHex (48 B) / PointG2.fromSignature (96 B): compressed -> affine wire bytes + status
-// slot0 / pow_slot: scratch-pool slots used (three from slot0, one for the exponentiation table), so that two chains can run on
-// different streams at the same time
+// sl: the scratch slots of this instance (three arrays and the exponentiation table), so that two chains can run on different streams at the same time
 // mode (G2 only): 0 fromSignature 96 B, 1 fromSignature 192 B, 2 fromHex 96 B (no subgroup check, flag rules)
 // io / ntot: the call works on items [io, io + n) of scratch arrays sized for ntot items (verify_pipeline: sub-batches of one call run side by side on slices of the same arrays)
-int dev_decompress(nbls_ctx* ctx, bool g2, size_t n, const void* d_in, void* d_out, void* d_status, hipStream_t s, int slot0, int pow_slot, int mode, size_t io, size_t ntot) {
+int dev_decompress(nbls_ctx* ctx, bool g2, size_t n, const void* d_in, void* d_out, void* d_status, hipStream_t s, const DecSlots& sl, int mode, size_t io, size_t ntot) {
   const size_t e = g2 ? (mode == 1 ? 192 : 96) : 48, q = g2 ? 2 * RAW : RAW, pq = POW_TAB * (g2 ? 2 : 1) * RAW;
   if (ntot < io + n) ntot = io + n;
   uint8_t *X, *R, *Cd, *pw; int r;
-  if ((r = need(ctx, slot0, ntot * q, &X)) || (r = need(ctx, slot0 + 1, ntot * q, &R)) || (r = need(ctx, slot0 + 2, ntot * q, &Cd)) || (r = need(ctx, pow_slot, ntot * pq, &pw))) return r;
+  if ((r = need(ctx, sl.x, ntot * q, &X)) || (r = need(ctx, sl.r, ntot * q, &R)) || (r = need(ctx, sl.c, ntot * q, &Cd)) || (r = need(ctx, sl.pow, ntot * pq, &pw))) return r;
   X += io * q; R += io * q; Cd += io * q; pw += io * pq;
   const ProgId pa = !g2 ? P_G1_DEC_A : mode == 1 ? P_G2_DEC_A192 : P_G2_DEC_A, pb = !g2 ? P_G1_DEC_B : mode == 1 ? P_G2_DEC_B192 : mode == 2 ? P_G2_DEC_B_HEX : P_G2_DEC_B;
   if ((r = run(ctx, pa, n, {B(0, d_in, e), B(3, X, q), B(4, R, q)}, s))) return r;
   if ((r = run_pow(ctx, g2 ? 1 : 0, n, R, Cd, s, pw))) return r;
   return run(ctx, pb, n, {B(0, d_in, e), B(3, X, q), B(4, R, q), B(5, Cd, q), B(6, d_out, g2 ? 192 : 96), B(7, d_status, 1)}, s);
+}
+// raw projective points -> affine wire bytes + status (1 = the zero point): [norm of Z ->] inversion -> affine program.  norm = false: an earlier program has left the norms in N
+int to_affine(nbls_ctx* ctx, bool g2, size_t n, const void* Pj, void* N, void* NI, void* d_out, void* d_status, hipStream_t s, bool norm) {
+  const size_t p = g2 ? 6 * RAW : 3 * RAW; int r;
+  if (norm && (r = run(ctx, g2 ? P_G2_NORM : P_G1_NORM, n, {B(3, Pj, p), B(4, N, RAW)}, s))) return r;
+  if ((r = run_inv_buf(ctx, n, N, NI, s))) return r;
+  return run(ctx, g2 ? P_G2_TO_AFFINE : P_G1_TO_AFFINE, n, {B(3, Pj, p), B(4, NI, RAW), B(2, d_out, g2 ? 192 : 96), B(7, d_status, 1)}, s);
 }
 // 256 uniform bytes per message (expand_message_xmd output) -> hash point, affine wire bytes (PointG2.hashToCurve, index.ts:481-490)
 // PointG2.clearCofactor (index.ts:659-672) on raw projective points: three programs: the t1-independent points, then one around each multiplication by x (programs.h P_H2C_C0 / C1 / C2).
@@ -33,15 +39,15 @@ int dev_clear_g2(nbls_ctx* ctx, size_t n, void* in, uint8_t* base, uint8_t* S, v
   // out may be in: every item reads its t1 before its result is stored
   return run(ctx, pt_ls2_variant(ctx, P_H2C_C2, n), n, {B(3, base, 6 * RAW), B(4, in, 6 * RAW), B(5, S, 6 * RAW), B(6, out, 6 * RAW), B(7, N, RAW)}, s);
 }
-// io / ntot: see dev_decompress; proj: stop at the raw projective points (scratch slot 1) -- the caller multiplies them (sign) and normalises once, at the end
+// io / ntot: see dev_decompress; proj: stop at the raw projective points (SB_WORK_B) -- the caller multiplies them (sign) and normalises once, at the end
 int dev_hash_to_g2(nbls_ctx* ctx, size_t n, const void* d_uniform, void* d_out, hipStream_t s, size_t io, size_t ntot, uint8_t** proj) {
   if (ntot < io + n) ntot = io + n;
   uint8_t *T, *E, *Pw, *Q, *N, *NI, *st, *St, *Pt2, *S, *tab; int r;
   const size_t ST = 32;   // raw elements of SWU state per message: 2 x 12 (P_H2C_A) or 2 x 16 (P_H2C_NA / NM)
-  if ((r = need(ctx, 0, ntot * 4 * RAW, &T)) || (r = need(ctx, 1, ntot * 6 * RAW, &E)) || (r = need(ctx, 2, ntot * 4 * RAW, &Pw)) || (r = need(ctx, 3, ntot * 6 * RAW, &Q)) ||
-      (r = need(ctx, 4, ntot * RAW, &N)) || (r = need(ctx, 5, ntot * RAW, &NI)) || (r = need(ctx, 6, ntot, &st)) || (r = need(ctx, 18, ntot * ST * RAW, &St)) || (r = need(ctx, 19,
-          ntot * 12 * RAW, &Pt2)) ||
-      (r = need(ctx, 13, ntot * 6 * RAW, &S)) || (r = need(ctx, 11, ntot * 4 * POW_TAB * RAW, &tab))) return r;
+  if ((r = need(ctx, SB_WORK_A, ntot * 4 * RAW, &T)) || (r = need(ctx, SB_WORK_B, ntot * 6 * RAW, &E)) || (r = need(ctx, SB_WORK_C, ntot * 4 * RAW, &Pw)) ||
+      (r = need(ctx, SB_WORK_D, ntot * 6 * RAW, &Q)) || (r = need(ctx, SB_NORM, ntot * RAW, &N)) || (r = need(ctx, SB_NORM_INV, ntot * RAW, &NI)) || (r = need(ctx, SB_POINT_ST, ntot, &st)) ||
+      (r = need(ctx, SB_SWU_STATE, ntot * ST * RAW, &St)) || (r = need(ctx, SB_SWU_POINTS, ntot * 12 * RAW, &Pt2)) || (r = need(ctx, SB_CLEAR_S, ntot * 6 * RAW, &S)) ||
+      (r = need(ctx, SB_POW_TABLE, ntot * 4 * POW_TAB * RAW, &tab))) return r;
   T += io * 4 * RAW; E += io * 6 * RAW; Pw += io * 4 * RAW; Q += io * 6 * RAW; N += io * RAW; NI += io * RAW; st += io; St += io * ST * RAW; Pt2 += io * 12 * RAW; S += io * 6 * RAW;
   tab += io * 4 * POW_TAB * RAW;
   if (ntot >= ctx->h2c_norm_min) {   // ntot: the messages of the whole call (verifyBatch hashes its sub-batches side by side)
@@ -63,14 +69,13 @@ int dev_hash_to_g2(nbls_ctx* ctx, size_t n, const void* d_uniform, void* d_out, 
   if ((r = run(ctx, P_H2C_B2, n, {B(3, Pt2, 12 * RAW), B(6, E, 6 * RAW)}, s))) return r;        // E is free again: reuse it for the E2 point
   if ((r = dev_clear_g2(ctx, n, E, Q, S, E, N, s))) return r;
   if (proj) { *proj = E; return NBLS_OK; }
-  if ((r = run_inv_buf(ctx, n, N, NI, s))) return r;
-  return run(ctx, P_G2_TO_AFFINE, n, {B(3, E, 6 * RAW), B(4, NI, RAW), B(2, d_out, 192), B(7, st, 1)}, s);
+  return to_affine(ctx, true, n, E, N, NI, d_out, st, s, false);
 }
 // sum of n affine points (left fold of add == tree of complete additions): affine wire bytes + status (1 = sum is the zero point)
 int dev_point_sum(nbls_ctx* ctx, bool g2, size_t n, const void* d_pts, void* d_out, void* d_status, hipStream_t s) {
   const size_t a = g2 ? 192 : 96, p = g2 ? 6 * RAW : 3 * RAW;
   uint8_t *A, *Bf, *N, *NI; int r;
-  if ((r = need(ctx, 0, (n + 2) * p, &A)) || (r = need(ctx, 1, (n / 2 + 2) * p, &Bf)) || (r = need(ctx, 4, RAW, &N)) || (r = need(ctx, 5, RAW, &NI))) return r;
+  if ((r = need(ctx, SB_WORK_A, (n + 2) * p, &A)) || (r = need(ctx, SB_WORK_B, (n / 2 + 2) * p, &Bf)) || (r = need(ctx, SB_NORM, RAW, &N)) || (r = need(ctx, SB_NORM_INV, RAW, &NI))) return r;
   uint8_t* ident = g2 ? ctx->ident_g2 : ctx->ident_g1;
   if (n == 0) { HIPCHK(hipMemcpyAsync(A, ident, p, hipMemcpyDeviceToDevice, s)); }
   else if ((r = run(ctx, g2 ? P_G2_TO_PROJ : P_G1_TO_PROJ, n, {B(g2 ? 1 : 0, d_pts, a), B(3, A, p)}, s))) return r;
@@ -80,9 +85,7 @@ int dev_point_sum(nbls_ctx* ctx, bool g2, size_t n, const void* d_pts, void* d_o
     if ((r = run(ctx, g2 ? P_G2_ADD2 : P_G1_ADD2, m / 2, {B(3, src, 2 * p), B(5, dst, p)}, s))) return r;
     std::swap(src, dst); m /= 2;
   }
-  if ((r = run(ctx, g2 ? P_G2_NORM : P_G1_NORM, 1, {B(3, src, p), B(4, N, RAW)}, s))) return r;
-  if ((r = run_inv_buf(ctx, 1, N, NI, s))) return r;
-  return run(ctx, g2 ? P_G2_TO_AFFINE : P_G1_TO_AFFINE, 1, {B(3, src, p), B(4, NI, RAW), B(2, d_out, a), B(7, d_status, 1)}, s);
+  return to_affine(ctx, g2, 1, src, N, NI, d_out, d_status, s);
 }
 
 EXPORT int nbls_g1_validate_batch(nbls_ctx* ctx, size_t n, const uint8_t* g1_aff, int8_t* status) {
@@ -122,15 +125,14 @@ int dev_expand(nbls_ctx* ctx, size_t n, const uint8_t* msgs, const uint32_t* off
   uint8_t dst_hash[32];
   if (dst_len > 255) { Sha256 c; c.update((const uint8_t*)"H2C-OVERSIZE-DST-", 17); c.update(dst, dst_len); c.final(dst_hash); dst = dst_hash; dst_len = 32; }
   uint8_t *dm, *dofs, *dd, *du; int r;
-  if ((r = need(ctx, 7, total + 4, &dm)) || (r = need(ctx, 12, (n + 1) * 4 + 256, &dofs)) || (r = need(ctx, 8, n * (size_t)len_in_bytes, &du))) return r;
+  if ((r = need(ctx, SB_MSGS, total + 4, &dm)) || (r = need(ctx, SB_OFFS_DST, (n + 1) * 4 + 256, &dofs)) || (r = need(ctx, SB_UNIFORM, n * (size_t)len_in_bytes, &du))) return r;
   dd = dofs + (n + 1) * 4;
   std::vector<uint32_t> rel(n + 1); for (size_t i = 0; i <= n; i++) rel[i] = offs[i] - offs[0];
   if (total) HIPCHK(hipMemcpyAsync(dm, msgs + offs[0], total, hipMemcpyHostToDevice, s));
   HIPCHK(hipMemcpyAsync(dofs, rel.data(), (n + 1) * 4, hipMemcpyHostToDevice, s));
   HIPCHK(hipMemcpyAsync(dd, dst, dst_len, hipMemcpyHostToDevice, s));
   HIPCHK(hipStreamSynchronize(s));     // `rel` and a hashed DST live on this stack frame
-  int e = nbls_xmd_launch((unsigned)n, dm, dofs, dd, (unsigned)dst_len, du, len_in_bytes, nullptr, s);
-  if (e) { ctx->last_hip = e; return NBLS_EHIP; }
+  LAUNCHCHK(nbls_xmd_launch((unsigned)n, dm, dofs, dd, (unsigned)dst_len, du, len_in_bytes, nullptr, s));
   *d_uniform = du;
   return NBLS_OK;
 }
@@ -157,29 +159,27 @@ EXPORT int nbls_g2_sum(nbls_ctx* ctx, size_t n, const uint8_t* pts192, uint8_t* 
 // PointG1.hashToCurve (count = 2) / PointG1.encodeToCurve (count = 1) on 64 * count uniform bytes per message (index.ts:331-350)
 int dev_hash_to_g1(nbls_ctx* ctx, int count, size_t n, const void* d_uniform, void* d_out, hipStream_t s) {
   uint8_t *U, *E, *Pw, *Q, *Q2, *N, *NI, *st; int r;
-  if ((r = need(ctx, 0, n * 2 * RAW, &U)) || (r = need(ctx, 1, n * 3 * RAW, &E)) || (r = need(ctx, 2, n * 2 * RAW, &Pw)) || (r = need(ctx, 3, n * 3 * RAW, &Q)) ||
-      (r = need(ctx, 4, n * RAW, &N)) || (r = need(ctx, 5, n * RAW, &NI)) || (r = need(ctx, 6, n, &st))) return r;
+  if ((r = need(ctx, SB_WORK_A, n * 2 * RAW, &U)) || (r = need(ctx, SB_WORK_B, n * 3 * RAW, &E)) || (r = need(ctx, SB_WORK_C, n * 2 * RAW, &Pw)) || (r = need(ctx, SB_WORK_D, n * 3 * RAW, &Q)) ||
+      (r = need(ctx, SB_NORM, n * RAW, &N)) || (r = need(ctx, SB_NORM_INV, n * RAW, &NI)) || (r = need(ctx, SB_POINT_ST, n, &st))) return r;
   Q2 = E;   // E (the exponentiation inputs) is free again after the pow kernel
   const size_t us = (size_t)count * RAW;
   if ((r = run(ctx, count == 2 ? P_H2C1_A : P_ENC1_A, n, {B(0, d_uniform, 64 * (size_t)count), B(3, U, us), B(4, E, us)}, s))) return r;
   if ((r = run_pow(ctx, 3, (size_t)count * n, E, Pw, s))) return r;
   if ((r = run(ctx, count == 2 ? P_H2C1_B : P_ENC1_B, n, {B(3, U, us), B(5, Pw, us), B(6, Q, 3 * RAW)}, s))) return r;
   if ((r = run(ctx, P_G1_CLEAR, n, {B(3, Q, 3 * RAW), B(6, Q2, 3 * RAW), B(7, N, RAW)}, s))) return r;
-  if ((r = run_inv_buf(ctx, n, N, NI, s))) return r;
-  return run(ctx, P_G1_TO_AFFINE, n, {B(3, Q2, 3 * RAW), B(4, NI, RAW), B(2, d_out, 96), B(7, st, 1)}, s);
+  return to_affine(ctx, false, n, Q2, N, NI, d_out, st, s, false);
 }
 // PointG2.encodeToCurve on 128 uniform bytes per message (index.ts:491-497)
 int dev_encode_to_g2(nbls_ctx* ctx, size_t n, const void* d_uniform, void* d_out, hipStream_t s) {
   uint8_t *T, *E, *Pw, *Q, *N, *NI, *st; int r;
-  if ((r = need(ctx, 0, n * 2 * RAW, &T)) || (r = need(ctx, 1, n * 6 * RAW, &E)) || (r = need(ctx, 2, n * 2 * RAW, &Pw)) || (r = need(ctx, 3, n * 6 * RAW, &Q)) ||
-      (r = need(ctx, 4, n * RAW, &N)) || (r = need(ctx, 5, n * RAW, &NI)) || (r = need(ctx, 6, n, &st))) return r;
+  if ((r = need(ctx, SB_WORK_A, n * 2 * RAW, &T)) || (r = need(ctx, SB_WORK_B, n * 6 * RAW, &E)) || (r = need(ctx, SB_WORK_C, n * 2 * RAW, &Pw)) || (r = need(ctx, SB_WORK_D, n * 6 * RAW, &Q)) ||
+      (r = need(ctx, SB_NORM, n * RAW, &N)) || (r = need(ctx, SB_NORM_INV, n * RAW, &NI)) || (r = need(ctx, SB_POINT_ST, n, &st))) return r;
   if ((r = run(ctx, P_ENC2_A, n, {B(0, d_uniform, 128), B(3, T, 2 * RAW), B(4, E, 2 * RAW)}, s))) return r;
   if ((r = run_pow(ctx, 2, n, E, Pw, s))) return r;
   if ((r = run(ctx, P_ENC2_B, n, {B(3, T, 2 * RAW), B(5, Pw, 2 * RAW), B(6, E, 6 * RAW)}, s))) return r;
-  uint8_t* S; if ((r = need(ctx, 13, n * 6 * RAW, &S))) return r;
+  uint8_t* S; if ((r = need(ctx, SB_CLEAR_S, n * 6 * RAW, &S))) return r;
   if ((r = dev_clear_g2(ctx, n, E, Q, S, E, N, s))) return r;
-  if ((r = run_inv_buf(ctx, n, N, NI, s))) return r;
-  return run(ctx, P_G2_TO_AFFINE, n, {B(3, E, 6 * RAW), B(4, NI, RAW), B(2, d_out, 192), B(7, st, 1)}, s);
+  return to_affine(ctx, true, n, E, N, NI, d_out, st, s, false);
 }
 // mode: 0 = PointG1.hashToCurve, 1 = PointG1.encodeToCurve, 2 = PointG2.encodeToCurve
 int hash_curve_host(nbls_ctx* ctx, int mode, size_t n, const uint8_t* msgs, const uint32_t* offsets, const uint8_t* dst, size_t dst_len, uint8_t* out) {
@@ -223,8 +223,8 @@ int decode_host(nbls_ctx* ctx, int kind /* 0 g1.fromHex, 1 g2.fromHex, 2 g2.from
   HIPCHK(hipMemcpyAsync(d, in, n * len, hipMemcpyHostToDevice, s));
   int r;
   if (kind == 0) r = len == 48 ? dev_decompress(ctx, false, n, d, o, st, s) : run(ctx, P_G1_FROM_RAW, n, {B(0, d, 96), B(6, o, 96), B(7, st, 1)}, s);
-  else if (kind == 1) r = len == 96 ? dev_decompress(ctx, true, n, d, o, st, s, 0, 11, 2) : run(ctx, P_G2_FROM_RAW, n, {B(0, d, 192), B(6, o, 192), B(7, st, 1)}, s);
-  else r = dev_decompress(ctx, true, n, d, o, st, s, 0, 11, len == 192 ? 1 : 0);
+  else if (kind == 1) r = len == 96 ? dev_decompress(ctx, true, n, d, o, st, s, DEC_MAIN, 2) : run(ctx, P_G2_FROM_RAW, n, {B(0, d, 192), B(6, o, 192), B(7, st, 1)}, s);
+  else r = dev_decompress(ctx, true, n, d, o, st, s, DEC_MAIN, len == 192 ? 1 : 0);
   if (r) return r;
   HIPCHK(hipMemcpyAsync(out, o, n * a, hipMemcpyDeviceToHost, s)); HIPCHK(hipMemcpyAsync(status, st, n, hipMemcpyDeviceToHost, s)); HIPCHK(hipStreamSynchronize(s));
   return NBLS_OK;
@@ -264,8 +264,7 @@ int clear_host(nbls_ctx* ctx, bool g2, size_t n, const uint8_t* aff, uint8_t* ou
   if ((r = run(ctx, g2 ? P_G2_TO_PROJ : P_G1_TO_PROJ, n, {B(g2 ? 1 : 0, d, a), B(3, P, p)}, s))) return r;
   if (g2) { void* S2 = io.alloc(n * p); if (!S2) return NBLS_EHIP; if ((r = dev_clear_g2(ctx, n, P, (uint8_t*)Q, (uint8_t*)S2, Q, N, s))) return r; }
   else if ((r = run(ctx, P_G1_CLEAR, n, {B(3, P, p), B(6, Q, p), B(7, N, RAW)}, s))) return r;
-  if ((r = run_inv_buf(ctx, n, N, NI, s))) return r;
-  if ((r = run(ctx, g2 ? P_G2_TO_AFFINE : P_G1_TO_AFFINE, n, {B(3, Q, p), B(4, NI, RAW), B(2, o, a), B(7, st, 1)}, s))) return r;
+  if ((r = to_affine(ctx, g2, n, Q, N, NI, o, st, s, false))) return r;
   HIPCHK(hipMemcpyAsync(out, o, n * a, hipMemcpyDeviceToHost, s)); HIPCHK(hipMemcpyAsync(status, st, n, hipMemcpyDeviceToHost, s)); HIPCHK(hipStreamSynchronize(s));
   return NBLS_OK;
 }
@@ -302,30 +301,30 @@ int ensure_g1_fixed(nbls_ctx* ctx, hipStream_t s) {
 }
 int dev_point_mul(nbls_ctx* ctx, bool g2, size_t n, const void* d_pts, size_t pt_stride, const void* d_scalars, void* d_out, void* d_status, hipStream_t s, bool allow_fixed, bool in_subgroup,
                   uint8_t* recoded) {   // recoded: the sign-aligned digits of the scalars, made by the caller (sign_points: beside the hash chain), or NULL
-  const size_t a = g2 ? 192 : 96, p = g2 ? 6 * RAW : 3 * RAW;
+  const size_t p = g2 ? 6 * RAW : 3 * RAW;
   uint8_t *Pj, *N, *NI; int r;
   // getPublicKey (the base point is G1.BASE for every item): no doublings, the multiples of the generator come from a table (round 5: 86 additions instead of 256 doublings + 128
   // additions; NBLS_G1_FIXED=0 keeps the ladder)
   static const bool fixed_on = env_long("NBLS_G1_FIXED", 1) != 0;
   const bool fixed = allow_fixed && fixed_on && !g2 && d_pts == ctx->gen_g1 && pt_stride == 0;
   if (fixed && (r = ensure_g1_fixed(ctx, s))) return r;
-  if ((r = need(ctx, 0, n * p, &Pj)) || (r = need(ctx, 4, n * RAW, &N)) || (r = need(ctx, 5, n * RAW, &NI))) return r;
+  if ((r = need(ctx, SB_WORK_A, n * p, &Pj)) || (r = need(ctx, SB_NORM, n * RAW, &N)) || (r = need(ctx, SB_NORM_INV, n * RAW, &NI))) return r;
   // sign (the base points are hash outputs: in G2 by construction): the scalar split along psi, four 65-bit digits on one accumulator (codec.h pt_mul_gls_g2: 66 doublings + 132 additions
   // instead of 256 + 128; NBLS_G2_GLS=0 keeps the plain ladder).  The digits are made on the device by the MSM's decomposition kernel (branch-free long division by |z|).
   static const bool gls_on = env_long("NBLS_G2_GLS", 1) != 0;
   if (g2 && in_subgroup && gls_on) {
     // up to sac_max keys d_pts are RAW PROJECTIVE points (six raw elements each, pt_stride = 6 * RAW: sign_points() below) -- the hash points as cofactor clearing leaves them in
-    // scratch slot 1, so the digits go to slot 2; above, affine wire points as everywhere else
+    // SB_WORK_B, so the digits go to SB_WORK_C; above, affine wire points as everywhere else
     uint8_t* dig = recoded;
-    if (!dig && (r = need(ctx, n <= ctx->sac_max ? 2 : 1, n * 128, &dig))) return r;
+    if (!dig && (r = need(ctx, n <= ctx->sac_max ? SB_WORK_C : SB_WORK_B, n * 128, &dig))) return r;
     // while every wavefront of the launch is resident at once the length of ONE wavefront's instruction stream is the time: the sign-aligned recoding with one addition per bit
     // (codec.h pt_mul_sac_g2: 65 doublings + 73 additions; its table of eight points takes 101 slots = three workgroups per CU = 768 wavefronts of 8 keys); above 6144 keys the
     // windowed form, whose table of four leaves room for six workgroups per CU (NBLS_G2_SAC_MAX / NBLS_TUNE_SAC_MAX; 0 = never)
     if (n <= ctx->sac_max) {
-      if (!recoded && nbls_msm_sac_launch((unsigned)n, d_scalars, dig, s)) { ctx->last_hip = (int)hipGetLastError(); return NBLS_EHIP; }
+      if (!recoded) LAUNCHCHK(nbls_msm_sac_launch((unsigned)n, d_scalars, dig, s));
       if ((r = run(ctx, pt_ls2_variant(ctx, P_G2_MUL_SAC, n), n, {B(1, d_pts, pt_stride), B(2, dig, 128), B(3, Pj, p), B(4, N, RAW)}, s))) return r;
     } else {
-    if (nbls_msm_decompose_launch((unsigned)n, 4, d_scalars, dig, s)) { ctx->last_hip = (int)hipGetLastError(); return NBLS_EHIP; }
+    LAUNCHCHK(nbls_msm_decompose_launch((unsigned)n, 4, d_scalars, dig, s));
     if ((r = run(ctx, P_G2_MUL_GLS, n, {B(1, d_pts, pt_stride), B(2, dig, 128), B(3, Pj, p), B(4, N, RAW)}, s))) return r;
     }
     HIPCHK(hipMemsetAsync(dig, 0, n * 128, s));      // the recoded digits ARE the private keys: not left in a scratch slot that later calls reuse
@@ -339,8 +338,7 @@ int dev_point_mul(nbls_ctx* ctx, bool g2, size_t n, const void* d_pts, size_t pt
   const bool w3 = (n + (g2 ? 7 : 15)) / (g2 ? 8 : 16) <= w3_waves;
   if ((r = run(ctx, g2 ? (w3 ? P_G2_MUL_W3 : P_G2_MUL) : (w3 ? P_G1_MUL_W3 : P_G1_MUL), n, {B(g2 ? 1 : 0, d_pts, pt_stride), B(2, d_scalars, 32), B(3, Pj, p), B(4, N, RAW)}, s))) return r;
   }
-  if ((r = run_inv_buf(ctx, n, N, NI, s))) return r;
-  return run(ctx, g2 ? P_G2_TO_AFFINE : P_G1_TO_AFFINE, n, {B(3, Pj, p), B(4, NI, RAW), B(2, d_out, a), B(7, d_status, 1)}, s);
+  return to_affine(ctx, g2, n, Pj, N, NI, d_out, d_status, s, false);
 }
 // sign's two halves: hash-to-G2, then the key ladder on the hash points.  Up to sac_max keys the points stay projective in between (no inversion, no affine program: the
 // sign-aligned ladder reads raw projective points); above, they are normalised first (the windowed ladder's affine input keeps it at six workgroups per CU).  `h`: n * 192 bytes of
@@ -351,10 +349,10 @@ int sign_points(nbls_ctx* ctx, size_t n, const void* d_uniform, void* h, const v
   if (gls_on && n <= ctx->sac_max) {
     // the recoding of the keys (0.045 ms for one key: a branch-free long division) does not need the hash points: it runs beside the hash chain on a side stream (round 6)
     uint8_t *pj, *dig;
-    if ((r = need(ctx, 7, n * 128, &dig)) || (r = ensure_side2(ctx))) return r;      // slot 7: used by neither the hash chain nor the ladder
+    if ((r = need(ctx, SB_MSGS, n * 128, &dig)) || (r = ensure_side2(ctx))) return r;
     HIPCHK(hipEventRecord(ctx->ev_fork, s)); HIPCHK(hipStreamWaitEvent(ctx->side2, ctx->ev_fork, 0));
     ForkGuard fork;
-    if (nbls_msm_sac_launch((unsigned)n, d_keys32, dig, ctx->side2)) { ctx->last_hip = (int)hipGetLastError(); return NBLS_EHIP; }
+    LAUNCHCHK(nbls_msm_sac_launch((unsigned)n, d_keys32, dig, ctx->side2));
     HIPCHK(hipEventRecord(ctx->ev_join2, ctx->side2));
     if ((r = dev_hash_to_g2(ctx, n, d_uniform, nullptr, s, 0, 0, &pj))) return r;
     HIPCHK(hipStreamWaitEvent(s, ctx->ev_join2, 0));
@@ -412,9 +410,23 @@ EXPORT int nbls_g2_mul_batch(nbls_ctx* ctx, size_t n, const uint8_t* g2_aff, con
 //   3. sum_b b * B_b per window = sum_t 2^t * T_t with T_t = sum of the buckets whose index has bit t: 12 * 2^11 gathered
 //      points per window, a balanced tree of 11 rounds of pairwise additions (data independent).
 //   4. Horner over t inside every window (one item per window), then acc <- 2^12 * acc + S_w from the top window down.
-// Result: affine wire bytes + status (1 = the sum is the zero point).  nbits bounds the scalars (< 2^nbits), 0 = 256.  Scratch slots slot0 + 0 .. 9, 11, 13.
-#define MSMCHK(call) do { int e_ = (call); if (e_) { ctx->last_hip = e_; return NBLS_EHIP; } } while (0)
-int dev_msm(nbls_ctx* ctx, bool g2, size_t n, const void* d_pts, const void* d_scalars, unsigned nbits, void* d_out, void* d_status, hipStream_t s, int slot0) {
+// Result: affine wire bytes + status (1 = the sum is the zero point).  nbits bounds the scalars (< 2^nbits), 0 = 256.  sl: the scratch slots of this instance.
+//
+// Step 2 on its own, for every caller that has segments to sum (dev_msm: runs of equal keys; segment_sums in pipelines_multi_verify.cpp: the keys of a set, the sets of a message):
+// `count` points P whose segment is keys[j] and whose place inside it is rank[j]; ceil(log2(maxrun)) rounds leave every segment's sum at its first point.  counters: one word per
+// round (the pairs of that round), list: count words.
+int segmented_sum(nbls_ctx* ctx, bool g2, size_t count, const uint32_t* keys, const uint32_t* rank, uint32_t* list, uint32_t* counters, uint8_t* P, size_t maxrun, hipStream_t s) {
+  const size_t p = g2 ? 6 * RAW : 3 * RAW; int r;
+  for (size_t d = 1; d < maxrun; d *= 2, counters++) {
+    const size_t bound = count / (d + 1) + 1;      // every pair owns d + 1 list positions of its own segment
+    LAUNCHCHK(nbls_msm_pairs_launch(count, (unsigned)d, keys, rank, list, counters, s));
+    // P[j] += P[j + d] for the listed j, in place: the step program addresses its buffers through the list (KernelArgs.item_index);
+    // a listed element is never the partner of another one (ranks are multiples of 2d), so no pair touches another pair's points
+    if ((r = run(ctx, g2 ? P_G2_ADD_AB : P_G1_ADD_AB, bound, {B(3, P, p), B(4, P + d * p, p), B(5, P, p)}, s, counters, list))) return r;
+  }
+  return NBLS_OK;
+}
+int dev_msm(nbls_ctx* ctx, bool g2, size_t n, const void* d_pts, const void* d_scalars, unsigned nbits, void* d_out, void* d_status, hipStream_t s, const MsmSlots& sl) {
   const size_t a = g2 ? 192 : 96, p = g2 ? 6 * RAW : 3 * RAW;
   const unsigned C = MSM_WINDOW_BITS;
   uint8_t* ident = g2 ? ctx->ident_g2 : ctx->ident_g1;
@@ -430,41 +442,34 @@ int dev_msm(nbls_ctx* ctx, bool g2, size_t n, const void* d_pts, const void* d_s
   const unsigned nwin = (nbits + C - 1) / C;
   const size_t m = n * nwin, nb = (size_t)nwin << C, ng = ((size_t)nwin * C) << (C - 1);
   uint8_t *Pj, *P, *A, *K, *tmp, *Bk, *G, *Gh, *N, *NI, *acc, *cnt, *Ks = nullptr; int r;
-  if (split && (r = need(ctx, slot0 + 13, (n + 1) * 32, &Ks))) return r;
+  if (split && (r = need(ctx, sl[MsmSlots::SPLIT_SCALARS], (n + 1) * 32, &Ks))) return r;
   size_t tmp_bytes = 0;
   size_t scan_bytes = 0;
-  if (m) { MSMCHK(nbls_msm_sort_launch(nullptr, &tmp_bytes, nullptr, nullptr, nullptr, nullptr, m, 17, s)); MSMCHK(nbls_msm_rank_launch(nullptr, &scan_bytes, m, nullptr, nullptr, nullptr,
+  if (m) { LAUNCHCHK(nbls_msm_sort_launch(nullptr, &tmp_bytes, nullptr, nullptr, nullptr, nullptr, m, 17, s)); LAUNCHCHK(nbls_msm_rank_launch(nullptr, &scan_bytes, m, nullptr, nullptr, nullptr,
       s)); tmp_bytes = std::max(tmp_bytes, scan_bytes); }
-  if ((r = need(ctx, slot0 + 0, (n + 1) * p, &Pj)) || (r = need(ctx, slot0 + 1, (m + 1) * p, &P)) || (r = need(ctx, slot0 + 2, ((size_t)nwin + 1) * p, &A)) || (r = need(ctx, slot0 + 3, (m + 1) * 24, &K)) ||
-      (r = need(ctx, slot0 + 4, RAW, &N)) || (r = need(ctx, slot0 + 5, RAW, &NI)) || (r = need(ctx, slot0 + 6, tmp_bytes + 16, &tmp)) || (r = need(ctx, slot0 + 7, nb * p, &Bk)) || (r = need(ctx, slot0 + 8, ng * p, &G)) ||
-      (r = need(ctx, slot0 + 9, (ng / 2 + 2) * p, &Gh)) || (r = need(ctx, slot0 + 11, 64 * 4, &cnt))) return r;
-  acc = Gh + ng / 2 * p;     // (slot 10 belongs to verifyBatch, which drops the context lock between its stages)
+  if ((r = need(ctx, sl[MsmSlots::POINTS], (n + 1) * p, &Pj)) || (r = need(ctx, sl[MsmSlots::SORTED], (m + 1) * p, &P)) || (r = need(ctx, sl[MsmSlots::WINDOW_SUMS], ((size_t)nwin + 1) * p, &A)) ||
+      (r = need(ctx, sl[MsmSlots::KEYS], (m + 1) * 24, &K)) || (r = need(ctx, sl[MsmSlots::NORM], RAW, &N)) || (r = need(ctx, sl[MsmSlots::NORM_INV], RAW, &NI)) ||
+      (r = need(ctx, sl[MsmSlots::TEMP], tmp_bytes + 16, &tmp)) || (r = need(ctx, sl[MsmSlots::BUCKETS], nb * p, &Bk)) || (r = need(ctx, sl[MsmSlots::SLICES], ng * p, &G)) ||
+      (r = need(ctx, sl[MsmSlots::SLICES_HALF], (ng / 2 + 2) * p, &Gh)) || (r = need(ctx, sl[MsmSlots::COUNTERS], 64 * 4, &cnt))) return r;
+  acc = Gh + ng / 2 * p;
   uint32_t *kin = (uint32_t*)K, *vin = kin + m, *kout = vin + m, *vout = kout + m, *pos = vout + m, *list = pos + m;
   uint32_t* counters = (uint32_t*)cnt;    // [0] longest run, [1 + round] pairs of that round
-  MSMCHK(nbls_msm_fill_launch(nb, (unsigned)p, ident, Bk, s));
+  LAUNCHCHK(nbls_msm_fill_launch(nb, (unsigned)p, ident, Bk, s));
   if (m) {
     if (split) {
       if ((r = run(ctx, g2 ? P_G2_MSM_PREP : P_G1_MSM_PREP, n_in, {B(g2 ? 1 : 0, d_pts, a), B(3, Pj, dims * p)}, s))) return r;
-      MSMCHK(nbls_msm_decompose_launch((unsigned)n_in, dims, d_scalars, Ks, s));
+      LAUNCHCHK(nbls_msm_decompose_launch((unsigned)n_in, dims, d_scalars, Ks, s));
     } else if ((r = run(ctx, g2 ? P_G2_TO_PROJ : P_G1_TO_PROJ, n, {B(g2 ? 1 : 0, d_pts, a), B(3, Pj, p)}, s))) return r;
-    MSMCHK(nbls_msm_keys_launch((unsigned)n, nwin, split ? Ks : (const uint8_t*)d_scalars, kin, vin, s));
-    MSMCHK(nbls_msm_sort_launch(tmp, &tmp_bytes, kin, kout, vin, vout, m, 17, s));
-    MSMCHK(nbls_msm_gather_launch(m, (unsigned)p, vout, Pj, P, s));
-    MSMCHK(nbls_msm_rank_launch(tmp, &scan_bytes, m, kout, pos, counters, s));
+    LAUNCHCHK(nbls_msm_keys_launch((unsigned)n, nwin, split ? Ks : (const uint8_t*)d_scalars, kin, vin, s));
+    LAUNCHCHK(nbls_msm_sort_launch(tmp, &tmp_bytes, kin, kout, vin, vout, m, 17, s));
+    LAUNCHCHK(nbls_msm_gather_launch(m, (unsigned)p, vout, Pj, P, s));
+    LAUNCHCHK(nbls_msm_rank_launch(tmp, &scan_bytes, m, kout, pos, counters, s));
     uint32_t maxrun = 0;
     HIPCHK(hipMemcpyAsync(&maxrun, counters, 4, hipMemcpyDeviceToHost, s)); HIPCHK(hipStreamSynchronize(s));
-    int round = 0;
-    for (size_t d = 1; d < maxrun; d *= 2, round++) {
-      const size_t bound = m / (d + 1) + 1;      // every pair owns d + 1 list positions of its own
-      uint32_t* c = counters + 1 + round;
-      MSMCHK(nbls_msm_pairs_launch(m, (unsigned)d, kout, pos, list, c, s));
-      // P[j] += P[j + d] for the listed j, in place: the step program addresses its buffers through the list (KernelArgs.item_index);
-      // a listed element is never the partner of another one (ranks are multiples of 2d), so no pair touches another pair's points
-      if ((r = run(ctx, g2 ? P_G2_ADD_AB : P_G1_ADD_AB, bound, {B(3, P, p), B(4, P + d * p, p), B(5, P, p)}, s, c, list))) return r;
-    }
-    MSMCHK(nbls_msm_heads_launch(m, (unsigned)p, kout, P, Bk, s));
+    if ((r = segmented_sum(ctx, g2, m, kout, pos, list, counters + 1, P, maxrun, s))) return r;
+    LAUNCHCHK(nbls_msm_heads_launch(m, (unsigned)p, kout, P, Bk, s));
   }
-  MSMCHK(nbls_msm_bitsel_launch(nwin, (unsigned)p, Bk, G, s));
+  LAUNCHCHK(nbls_msm_bitsel_launch(nwin, (unsigned)p, Bk, G, s));
   uint8_t *src = G, *dst = Gh;
   for (size_t cnt = ng; cnt > (size_t)nwin * C; cnt /= 2) {
     if ((r = run(ctx, g2 ? P_G2_ADD2 : P_G1_ADD2, cnt / 2, {B(3, src, 2 * p), B(5, dst, p)}, s))) return r;
@@ -474,18 +479,16 @@ int dev_msm(nbls_ctx* ctx, bool g2, size_t n, const void* d_pts, const void* d_s
   static const bool wide_combine = env_long("NBLS_MSM_WIDE", 1) != 0;
   // Horner over the bit-slices t of every window (sum_t 2^t T_t, one sum per window), then over the windows (below).  G1 (round 6): both with one limb per lane, a wavefront per
   // sum, the four products of a doubling level on its four rows (g1_wide.h: 0.74 -> 0.25 ms of a 65,536-point call); G2 and NBLS_MSM_WIDE=0: the step programs
-  if (!g2 && wide_combine) MSMCHK(nbls_g1_wide_combine_launch(src, (int)C, 1, S, nwin, s));
+  if (!g2 && wide_combine) LAUNCHCHK(nbls_g1_wide_combine_launch(src, (int)C, 1, S, nwin, s));
   else if ((r = run(ctx, g2 ? P_G2_HORNER : P_G1_HORNER, nwin, {B(3, src, C * p), B(5, S, p)}, s))) return r;
   // acc <- 2^12 acc + S_w from the top window down: (nwin - 1) x (12 doublings + 1 addition) on ONE point
-  if (!g2 && wide_combine) MSMCHK(nbls_g1_wide_combine_launch(S, (int)nwin, (int)C, acc, 1, s));
+  if (!g2 && wide_combine) LAUNCHCHK(nbls_g1_wide_combine_launch(S, (int)nwin, (int)C, acc, 1, s));
   else {
     HIPCHK(hipMemcpyAsync(acc, S + (size_t)(nwin - 1) * p, p, hipMemcpyDeviceToDevice, s));
     for (int w = (int)nwin - 2; w >= 0; w--)
       if ((r = run(ctx, g2 ? P_G2_SHIFTADD : P_G1_SHIFTADD, 1, {B(3, acc, p), B(4, S + (size_t)w * p, p), B(5, acc, p)}, s))) return r;
   }
-  if ((r = run(ctx, g2 ? P_G2_NORM : P_G1_NORM, 1, {B(3, acc, p), B(4, N, RAW)}, s))) return r;
-  if ((r = run_inv_buf(ctx, 1, N, NI, s))) return r;
-  return run(ctx, g2 ? P_G2_TO_AFFINE : P_G1_TO_AFFINE, 1, {B(3, acc, p), B(4, NI, RAW), B(2, d_out, a), B(7, d_status, 1)}, s);
+  return to_affine(ctx, g2, 1, acc, N, NI, d_out, d_status, s);
 }
 unsigned scalars_bit_length(size_t n, const uint8_t* k32) {   // max over the batch
   int lead = 32;   // leading zero bytes common to all scalars
@@ -536,14 +539,13 @@ EXPORT int nbls_sign_batch(nbls_ctx* ctx, size_t n, const uint8_t* msgs, const u
   io.secret(din + o_key, n * 32);
   int r;
   const size_t pin_out = (in_bytes + 63) & ~(size_t)63;      // the way back has its own part of the pinned block: nothing waits between the ladder and the copy out
-  if ((r = need(ctx, 8, n * 256, &du)) || (r = ensure_pinned(ctx, pin_out + out_bytes))) return r;
+  if ((r = need(ctx, SB_UNIFORM, n * 256, &du)) || (r = ensure_pinned(ctx, pin_out + out_bytes))) return r;
   uint8_t* pin = ctx->pinned;
   if (total) memcpy(pin, msgs + offsets[0], total);
   { uint32_t* rel = (uint32_t*)(pin + o_off); for (size_t i = 0; i <= n; i++) rel[i] = offsets[i] - offsets[0]; }
   memcpy(pin + o_dst, dst, dst_len); memcpy(pin + o_key, keys32, n * 32);
   HIPCHK(hipMemcpyAsync(din, pin, in_bytes, hipMemcpyHostToDevice, s));
-  const int e = nbls_xmd_launch((unsigned)n, din, din + o_off, din + o_dst, (unsigned)dst_len, du, 256, nullptr, s);
-  if (e) { ctx->last_hip = e; return NBLS_EHIP; }
+  LAUNCHCHK(nbls_xmd_launch((unsigned)n, din, din + o_off, din + o_dst, (unsigned)dst_len, du, 256, nullptr, s));
   if ((r = sign_points(ctx, n, du, h, din + o_key, dout, dout + n * 192, s))) return r;
   if ((r = io.wipe(s))) return r;
   HIPCHK(hipMemcpyAsync(pin + pin_out, dout, out_bytes, hipMemcpyDeviceToHost, s));
@@ -586,11 +588,10 @@ EXPORT int nbls_sign_batch_dev(nbls_ctx* ctx, size_t n, const void* d_msgs, cons
   StreamOrder order_(ctx, s);
   HostIO io{ctx}; io.s = s; void* h = io.alloc(n * 192); if (!h) return NBLS_EHIP;
   uint8_t* du;
-  if ((r = need(ctx, 8, n * 256 + 16, &du))) return r;
+  if ((r = need(ctx, SB_UNIFORM, n * 256 + 16, &du))) return r;
   uint32_t* d_bad = (uint32_t*)(du + n * 256);
   HIPCHK(hipMemsetAsync(d_bad, 0, 4, s));
-  const int e = nbls_xmd_launch((unsigned)n, (const uint8_t*)d_msgs, (const uint8_t*)d_offsets, dd, (unsigned)dst_len, du, 256, d_bad, s);
-  if (e) { ctx->last_hip = e; return NBLS_EHIP; }
+  LAUNCHCHK(nbls_xmd_launch((unsigned)n, (const uint8_t*)d_msgs, (const uint8_t*)d_offsets, dd, (unsigned)dst_len, du, 256, d_bad, s));
   if ((r = sign_points(ctx, n, du, h, d_keys32, d_out192, d_status, s))) return r;
   uint32_t bad = 0; HIPCHK(hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, s)); HIPCHK(hipStreamSynchronize(s));
   return bad ? NBLS_EINVAL : NBLS_OK;     // offsets[i + 1] < offsets[i] somewhere

@@ -36,7 +36,7 @@ int expx(nbls_ctx* ctx, size_t n, uint8_t* in, uint8_t* out, hipStream_t s) {
   if ((r = run(ctx, P_EXPC_DEC_B, n, {B(3, ctx->KS, KSB), B(4, ctx->NI, RAW), B(6, ctx->KD, KDB), B(5, out, F12), B(7, ctx->Kflag, 1)}, s))) return r;
   uint32_t* count = ctx->Kcount + (ctx->ioff ? 1 : 0);    // the two halves of a split call run concurrently
   uint32_t* list = ctx->Klist + ctx->ioff;
-  if (nbls_flag_compact_launch((unsigned)n, ctx->Kflag + ctx->ioff, list, count, s)) { ctx->last_hip = (int)hipGetLastError(); return NBLS_EHIP; }
+  LAUNCHCHK(nbls_flag_compact_launch((unsigned)n, ctx->Kflag + ctx->ioff, list, count, s));
   return run(ctx, P_EXPX, n, {B(3, in, F12), B(5, out, F12)}, s, count, list);   // workgroups beyond the listed items exit at once
 }
 // n raw Fp12 in `f_raw` (norms already in ctx->N) -> finalExponentiate -> wire bytes at d_out (math.ts:856-874)

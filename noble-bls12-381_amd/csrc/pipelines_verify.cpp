@@ -63,10 +63,10 @@ int verify_pipeline(nbls_ctx* ctx, size_t n, const VerifyIn& in, int final_exp, 
   StreamOrder order_(ctx, s);
   int r;
   uint8_t *G1, *G2, *ST, *O, *du = nullptr;
-  if ((r = need(ctx, 10, (n + 1) * (96 + 192) + (n + 1) + 576 + 64 + 16, &G1))) return r;
+  if ((r = need(ctx, SB_VB_PAIRS, (n + 1) * (96 + 192) + (n + 1) + 576 + 64 + 16, &G1))) return r;
   G2 = G1 + (n + 1) * 96; O = G2 + (n + 1) * 192; ST = O + 576;
   uint32_t* d_bad = (uint32_t*)(ST + ((np + 3) & ~(size_t)3));   // one word behind the statuses
-  if (!in.d_uniform && (r = need(ctx, 8, n * 256, &du))) return r;
+  if (!in.d_uniform && (r = need(ctx, SB_UNIFORM, n * 256, &du))) return r;
   const std::vector<size_t> plan = verify_plan(ctx, n);
   const size_t K = plan.size();
   if (!ctx->ev_fork && hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming) != hipSuccess) { ctx->last_hip = (int)hipGetLastError(); return NBLS_EHIP; }
@@ -89,15 +89,14 @@ int verify_pipeline(nbls_ctx* ctx, size_t n, const VerifyIn& in, int final_exp, 
     // one sub-batch: keys on a second stream beside the hash chain (both contain a per-lane exponentiation kernel that leaves issue slots free), then the Miller loops of all pairs
     if ((r = ensure_side2(ctx))) return r;
     HIPCHK(hipStreamWaitEvent(ctx->side2, ctx->ev_fork, 0));
-    if ((r = dev_decompress(ctx, false, n, in.d_pk48, G1, ST, ctx->side2, 14, 17))) return r;      // normP1: PointG1.fromHex; scratch slots 14..16 / 17
+    if ((r = dev_decompress(ctx, false, n, in.d_pk48, G1, ST, ctx->side2, DEC_KEYS))) return r;      // normP1: PointG1.fromHex
     HIPCHK(hipEventRecord(ctx->ev_join2, ctx->side2));
     const uint8_t* uni = (const uint8_t*)in.d_uniform;
     if (!uni) {
-      const int e = nbls_xmd_launch((unsigned)n, in.d_msgs, in.d_offsets, in.dst_dev, in.dst_len, du, 256, d_bad, s);
-      if (e) { ctx->last_hip = e; return NBLS_EHIP; }
+      LAUNCHCHK(nbls_xmd_launch((unsigned)n, in.d_msgs, in.d_offsets, in.dst_dev, in.dst_len, du, 256, d_bad, s));
       uni = du;
     }
-    if ((r = dev_hash_to_g2(ctx, n, uni, G2, s))) return r;                                       // normP2Hash: PointG2.hashToCurve; slots 0..6 / 11 / 13 / 18 / 19
+    if ((r = dev_hash_to_g2(ctx, n, uni, G2, s))) return r;                                       // normP2Hash: PointG2.hashToCurve
     HIPCHK(hipStreamWaitEvent(s, ctx->ev_join2, 0));
     if (in.d_sig96) {
       HIPCHK(hipMemcpyAsync(G1 + n * 96, ctx->neg_g1, 96, hipMemcpyDeviceToDevice, s));            // PointG1.BASE.negate()
@@ -115,12 +114,11 @@ int verify_pipeline(nbls_ctx* ctx, size_t n, const VerifyIn& in, int final_exp, 
       if (c && (r = pipe_stream(ctx, c - 1, &sc))) return r;
       if ((r = pipe_event(ctx, c, &evc))) return r;
       if (c) HIPCHK(hipStreamWaitEvent(sc, ctx->ev_fork, 0));
-      auto keys = [&]() { return dev_decompress(ctx, false, nc, (const uint8_t*)in.d_pk48 + o * 48, G1 + o * 96, ST + o, sc, 14, 17, 0, o, n); };   // normP1: PointG1.fromHex
+      auto keys = [&]() { return dev_decompress(ctx, false, nc, (const uint8_t*)in.d_pk48 + o * 48, G1 + o * 96, ST + o, sc, DEC_KEYS, 0, o, n); };   // normP1: PointG1.fromHex
       auto hash = [&]() -> int {                                                                                                                  // normP2Hash: PointG2.hashToCurve
         const uint8_t* uni = (const uint8_t*)in.d_uniform + o * 256;
         if (!in.d_uniform) {
-          const int e = nbls_xmd_launch((unsigned)nc, in.d_msgs, (const uint32_t*)in.d_offsets + o, in.dst_dev, in.dst_len, du + o * 256, 256, d_bad, sc);
-          if (e) { ctx->last_hip = e; return NBLS_EHIP; }
+          LAUNCHCHK(nbls_xmd_launch((unsigned)nc, in.d_msgs, (const uint32_t*)in.d_offsets + o, in.dst_dev, in.dst_len, du + o * 256, 256, d_bad, sc));
           uni = du + o * 256;
         }
         return dev_hash_to_g2(ctx, nc, uni, G2 + o * 192, sc, o, n);
@@ -223,14 +221,13 @@ EXPORT int nbls_verify_batch(nbls_ctx* ctx, size_t n, const uint8_t* sig96, cons
     const size_t o_off = (total + 15) & ~(size_t)15, o_dst = o_off + (((n + 1) * 4 + 15) & ~(size_t)15), o_pk = o_dst + 256, o_sig = o_pk + ((n * 48 + 15) & ~(size_t)15), in_bytes = o_sig + 96;
     LOCKED(ctx);
     uint8_t *c, *du; int r;
-    if ((r = need(ctx, 9, in_bytes, &c)) || (r = need(ctx, 8, n * 256, &du)) || (r = ensure_pinned(ctx, in_bytes))) return r;
+    if ((r = need(ctx, SB_STAGED, in_bytes, &c)) || (r = need(ctx, SB_UNIFORM, n * 256, &du)) || (r = ensure_pinned(ctx, in_bytes))) return r;
     uint8_t* pin = ctx->pinned;
     if (total) memcpy(pin, msgs + offsets[0], total);
     { uint32_t* rel = (uint32_t*)(pin + o_off); for (size_t i = 0; i <= n; i++) rel[i] = offsets[i] - offsets[0]; }
     memcpy(pin + o_dst, dst, dst_len); memcpy(pin + o_pk, pk48, n * 48); memcpy(pin + o_sig, sig96, 96);
     HIPCHK(hipMemcpyAsync(c, pin, in_bytes, hipMemcpyHostToDevice, s));
-    const int e = nbls_xmd_launch((unsigned)n, c, c + o_off, c + o_dst, (unsigned)dst_len, du, 256, nullptr, s);
-    if (e) { ctx->last_hip = e; return NBLS_EHIP; }
+    LAUNCHCHK(nbls_xmd_launch((unsigned)n, c, c + o_off, c + o_dst, (unsigned)dst_len, du, 256, nullptr, s));
     d_sig = c + o_sig; d_uni = du; d_pk = c + o_pk;
   }
   return nbls_verify_batch_dev_inputs(ctx, n, d_sig, d_uni, d_pk, ok, nullptr, nullptr);
@@ -256,11 +253,10 @@ EXPORT int nbls_verify_batch_msgs_dev(nbls_ctx* ctx, size_t n, const void* d_sig
     hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
     StreamOrder order_(ctx, s);
     int r;
-    if ((r = need(ctx, 8, n * 256 + 16, &du))) return r;
+    if ((r = need(ctx, SB_UNIFORM, n * 256 + 16, &du))) return r;
     uint32_t* d_bad = (uint32_t*)(du + n * 256);
     HIPCHK(hipMemsetAsync(d_bad, 0, 4, s));
-    const int e = nbls_xmd_launch((unsigned)n, (const uint8_t*)d_msgs, (const uint8_t*)d_offsets, dd, (unsigned)dst_len, du, 256, d_bad, s);
-    if (e) { ctx->last_hip = e; return NBLS_EHIP; }
+    LAUNCHCHK(nbls_xmd_launch((unsigned)n, (const uint8_t*)d_msgs, (const uint8_t*)d_offsets, dd, (unsigned)dst_len, du, 256, d_bad, s));
     uint32_t bad = 0; HIPCHK(hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, s)); HIPCHK(hipStreamSynchronize(s));
     if (bad) return NBLS_EINVAL;
   }
@@ -268,7 +264,7 @@ EXPORT int nbls_verify_batch_msgs_dev(nbls_ctx* ctx, size_t n, const void* d_sig
 }
 // Same with inputs resident in HBM: signature (96 B), expand_message_xmd outputs (256 B per message), public keys (48 B each).
 // decode + hash stage shared by verifyBatch and its multi-GPU shard: keys -> G1 points, messages -> G2 hash points, and (when a
-// signature is given) the pair (-G, S) appended; the pairs land in scratch slot 10 (g1 | g2), statuses in st (n or n + 1 entries)
+// signature is given) the pair (-G, S) appended; the pairs land in scratch slot SB_VB_PAIRS (g1 | g2), statuses in st (n or n + 1 entries)
 int verify_stage(nbls_ctx* ctx, size_t n, const void* d_sig96, const void* d_uniform, const void* d_pk48, std::vector<int8_t>& st, void* stream) {
   const size_t np = n + (d_sig96 ? 1 : 0);
   st.assign(np, 0);
@@ -276,7 +272,7 @@ int verify_stage(nbls_ctx* ctx, size_t n, const void* d_sig96, const void* d_uni
   hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
   StreamOrder order_(ctx, s);
   uint8_t *G1, *G2, *ST, *O; int r;
-  if ((r = need(ctx, 10, (n + 1) * (96 + 192) + (n + 1) + 576 + 64, &G1))) return r;
+  if ((r = need(ctx, SB_VB_PAIRS, (n + 1) * (96 + 192) + (n + 1) + 576 + 64, &G1))) return r;
   G2 = G1 + (n + 1) * 96; O = G2 + (n + 1) * 192; ST = O + 576;
   if (d_sig96) {
     // normP2: PointG2.fromSignature for the ONE signature, on the side stream with its own scratch (overlaps everything below).
@@ -292,13 +288,12 @@ int verify_stage(nbls_ctx* ctx, size_t n, const void* d_sig96, const void* d_uni
   }
   // normP1 (PointG1.fromHex of the keys) on a second stream beside normP2Hash (PointG2.hashToCurve of the messages): both chains
   // contain a per-lane exponentiation kernel that fills the chip only two wavefronts deep and issues at half rate, so running
-  // them side by side costs little more than the longer one.  Scratch slots 14..16 / 17 for the key chain (0..6 / 11 / 13 / 18 / 19 belong to the hash,
-  // 7..9 / 12 hold the staged messages, keys and expand_message_xmd output of the host-buffer entry point).
+  // them side by side costs little more than the longer one (the key chain has scratch slots of its own: DEC_KEYS).
   static const bool overlap = !env_set("NBLS_VERIFY_NO_OVERLAP");
   if (overlap) {
     if ((r = ensure_side2(ctx))) return r;
     HIPCHK(hipEventRecord(ctx->ev_fork, s)); HIPCHK(hipStreamWaitEvent(ctx->side2, ctx->ev_fork, 0));
-    if ((r = dev_decompress(ctx, false, n, d_pk48, G1, ST, ctx->side2, 14, 17))) return r;
+    if ((r = dev_decompress(ctx, false, n, d_pk48, G1, ST, ctx->side2, DEC_KEYS))) return r;
     HIPCHK(hipEventRecord(ctx->ev_join2, ctx->side2));
     if ((r = dev_hash_to_g2(ctx, n, d_uniform, G2, s))) return r;
     HIPCHK(hipStreamWaitEvent(s, ctx->ev_join2, 0));
@@ -329,7 +324,7 @@ EXPORT int nbls_verify_batch_dev_inputs(nbls_ctx* ctx, size_t n, const void* d_s
   for (size_t i = 0; i <= n; i++) if (st[i] > 1) return NBLS_EDECODE;       // the reference throws before its try block
   for (size_t i = 0; i <= n; i++) if (st[i] == 1) { *ok = 0; return NBLS_OK; }   // zero point -> pairing() throws -> false
   {
-    uint8_t* base = ctx->sb[10];
+    uint8_t* base = ctx->sb[SB_VB_PAIRS];
     r = nbls_miller_product_dev(ctx, n + 1, base, base + (n + 1) * 96, 1, base + (n + 1) * 288, stream);
     if (r) return r;
     std::lock_guard<std::recursive_mutex> g_(ctx->mu);
@@ -365,7 +360,7 @@ EXPORT int nbls_verify_batch_partial_dev(nbls_ctx* ctx, size_t n, const void* d_
   *zero_flag = 0;
   for (int8_t v : st) if (v == 1) { *zero_flag = 1; return NBLS_OK; }
   const size_t np = st.size();
-  uint8_t* base = ctx->sb[10];
+  uint8_t* base = ctx->sb[SB_VB_PAIRS];
   // the pairs sit at stride n + 1 inside the scratch block whether or not the signature pair is present
   return nbls_miller_product_dev(ctx, np, base, base + (n + 1) * 96, 0, d_out_fp12, stream);
 }
@@ -378,7 +373,7 @@ int verify_batch_partial_core(nbls_ctx* ctx, size_t n, const uint8_t* sig96 /* o
   uint8_t *b, *c, *part; int r;
   if ((r = partial_buffer(ctx, d_dst, &part))) return r;
   if ((r = dev_expand(ctx, n, msgs, offsets, dst, dst_len, &b, s))) return r;
-  if ((r = need(ctx, 9, n * 48 + 96, &c))) return r;
+  if ((r = need(ctx, SB_STAGED, n * 48 + 96, &c))) return r;
   HIPCHK(hipMemcpyAsync(c, pk48, n * 48, hipMemcpyHostToDevice, s));
   if (sig96) HIPCHK(hipMemcpyAsync(c + n * 48, sig96, 96, hipMemcpyHostToDevice, s));
   HIPCHK(hipStreamSynchronize(s));

@@ -243,7 +243,7 @@ int ensure_pinned_out(nbls_ctx* ctx, size_t bytes) {
   ctx->pinned_out_cap = cap;
   return NBLS_OK;
 }
-int need(nbls_ctx* ctx, int i, size_t bytes, uint8_t** out) {
+int need(nbls_ctx* ctx, Slot i, size_t bytes, uint8_t** out) {
   if (bytes > ctx->sb_cap[i]) {
     if (ctx->sb[i]) hipFree(ctx->sb[i]);
     ctx->sb[i] = nullptr; ctx->sb_cap[i] = 0;
@@ -261,18 +261,15 @@ size_t pow_wide_max() { static const size_t v = (size_t)env_long("NBLS_POW_WIDE_
 int run_pow(nbls_ctx* ctx, int which, size_t n, const void* in, void* out, hipStream_t s, uint8_t* scratch) {
   int is_fp2 = which == 1 || which == 2;
   if (n <= pow_wide_max()) {
-    const int e = nbls_pow_wide_launch((unsigned)n, in, out, ctx->nib[which], ctx->nnib[which], which == 1 ? 8 : which == 2 ? 7 : 0, s);
-    if (e) { ctx->last_hip = e; return NBLS_EHIP; }
+    LAUNCHCHK(nbls_pow_wide_launch((unsigned)n, in, out, ctx->nib[which], ctx->nnib[which], which == 1 ? 8 : which == 2 ? 7 : 0, s));
     return NBLS_OK;
   }
-  if (!scratch) { int r = need(ctx, 11, n * POW_TAB * (is_fp2 ? 2 : 1) * RAW, &scratch); if (r) return r; }
-  int e = nbls_fp_pow_launch((unsigned)n, in, out, ctx->nib[which], ctx->nnib[which], scratch, which == 1 ? 8 : which == 2 ? 7 : 0, s);   // Fp2: a^((p^2+7)/16) = b^K a^8, a^((p^2-9)/16) = b^K a^7
-  if (e) { ctx->last_hip = e; return NBLS_EHIP; }
+  if (!scratch) { int r = need(ctx, SB_POW_TABLE, n * POW_TAB * (is_fp2 ? 2 : 1) * RAW, &scratch); if (r) return r; }
+  LAUNCHCHK(nbls_fp_pow_launch((unsigned)n, in, out, ctx->nib[which], ctx->nnib[which], scratch, which == 1 ? 8 : which == 2 ? 7 : 0, s));   // Fp2: a^((p^2+7)/16) = b^K a^8, a^((p^2-9)/16) = b^K a^7
   return NBLS_OK;
 }
 int run_inv_buf(nbls_ctx* ctx, size_t n, const void* in, void* out, hipStream_t s) {
-  int e = n <= ctx->inv_wide_max ? nbls_fp_inv_wide_launch((unsigned)n, in, out, s) : nbls_fp_inv_launch((unsigned)n, in, out, s);
-  if (e) { ctx->last_hip = e; return NBLS_EHIP; }
+  LAUNCHCHK(n <= ctx->inv_wide_max ? nbls_fp_inv_wide_launch((unsigned)n, in, out, s) : nbls_fp_inv_launch((unsigned)n, in, out, s));
   return NBLS_OK;
 }
 
