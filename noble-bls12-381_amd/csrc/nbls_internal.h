@@ -292,6 +292,12 @@ struct HostIO {
   }
 };
 #define LOCKED(ctx) std::lock_guard<std::recursive_mutex> g_((ctx)->mu); HIPCHK(hipSetDevice((ctx)->device)); hipStream_t s = (ctx)->stream
+// the same for an entry point that works on device pointers and takes the caller's stream (NULL: the context's): `s` is that stream, ordered behind the context's previous call
+static inline hipStream_t call_stream(nbls_ctx* ctx, void* stream) { return stream ? (hipStream_t)stream : ctx->stream; }
+#define DEV_ENTER(ctx, stream) std::lock_guard<std::recursive_mutex> g_((ctx)->mu); HIPCHK(hipSetDevice((ctx)->device)); hipStream_t s = call_stream((ctx), (stream)); StreamOrder order_((ctx), s)
+// first statement of an entry point that makes several locked calls: scratch and I/O staging buffers belong to it until it returns.  Stands in front of the argument check, so it
+// has to survive a null context
+#define WHOLE_CALL(ctx) std::lock_guard<std::recursive_mutex> whole_call_((ctx) ? (ctx)->mu : g_null_mu)
 
 // ---- internal functions (hidden visibility; defined in runtime.cpp, tuning.cpp and the pipelines_*.cpp files)
 struct VerifyIn;
@@ -309,14 +315,16 @@ int run(nbls_ctx* ctx, ProgId id, size_t n, std::initializer_list<std::pair<int,
     const uint32_t* item_index = nullptr);
 int run_inv(nbls_ctx* ctx, size_t n, hipStream_t s);
 bool chains_enabled();
-int run_chain(nbls_ctx* ctx, size_t n, std::initializer_list<ChainLink> links, hipStream_t s);
+int run_chain(nbls_ctx* ctx, size_t n, const ChainLink* links, size_t count, hipStream_t s);   // links: a named array (the buffer lists of a copied ChainLink dangle)
 int ensure_scratch(nbls_ctx* ctx, size_t n);
 int ensure_expc_scratch(nbls_ctx* ctx);
 int ensure_io(nbls_ctx* ctx, size_t n);
 int ensure_lines(nbls_ctx* ctx, size_t n);
 int need(nbls_ctx* ctx, Slot i, size_t bytes, uint8_t** out);
+int ensure_fork_event(nbls_ctx* ctx);
 int ensure_side(nbls_ctx* ctx);
 int ensure_side2(nbls_ctx* ctx);
+int ensure_half_stream(nbls_ctx* ctx);
 int ensure_pinned(nbls_ctx* ctx, size_t bytes);
 int ensure_pinned_out(nbls_ctx* ctx, size_t bytes);
 size_t pow_wide_max();
@@ -329,6 +337,7 @@ int expx(nbls_ctx* ctx, size_t n, uint8_t* in, uint8_t* out, hipStream_t s);
 int final_exp_pipeline(nbls_ctx* ctx, size_t n, uint8_t* f_raw, void* d_out, hipStream_t s);
 int finish_single(nbls_ctx* ctx, uint8_t* f_raw, int final_exp, void* d_out, hipStream_t s);
 int pairing_core(nbls_ctx* ctx, size_t n, const void* d_g1, const void* d_g2, int with_final_exp, void* d_out, hipStream_t s, bool two_programs);
+int lines_acc(nbls_ctx* ctx, size_t c, const uint8_t* g1, const uint8_t* g2, uint8_t* L, size_t GR, uint8_t* acc_out, size_t h, hipStream_t s);
 int miller_values(nbls_ctx* ctx, size_t n, const void* d_g1, const void* d_g2, size_t* m_out, hipStream_t s);
 int acc_prepared(nbls_ctx* ctx, size_t n, const void* d_g1, const void* d_tables, size_t table_stride, hipStream_t s);
 int partial_buffer(nbls_ctx* ctx, void* d_dst, uint8_t** dst);
@@ -363,11 +372,11 @@ int msm_host(nbls_ctx* ctx, bool g2, size_t n, const uint8_t* pts, const uint8_t
 int dst_on_device(nbls_ctx* ctx, const uint8_t* dst, size_t* dst_len, hipStream_t s, uint8_t** dd);
 std::vector<size_t> verify_plan(nbls_ctx* ctx, size_t n);
 int pipe_event(nbls_ctx* ctx, size_t i, hipEvent_t* e);
-int ensure_half_stream(nbls_ctx* ctx);
 int pipe_stream(nbls_ctx* ctx, size_t i, hipStream_t* st);
 int verify_pipeline(nbls_ctx* ctx, size_t n, const VerifyIn& in, int final_exp, void* d_out, uint8_t* out, std::vector<int8_t>& st, int* bad_offsets, void* stream);
 bool verify_pipe_enabled();
 bool fp12_wire_is_one(const uint8_t* out);
+int verify_statuses(const std::vector<int8_t>& st, size_t n, int* zero_flag, int8_t* pk_status);
 int verify_decide(const std::vector<int8_t>& st, size_t n, const uint8_t* out, int* ok, int8_t* pk_status);
 int verify_stage(nbls_ctx* ctx, size_t n, const void* d_sig96, const void* d_uniform, const void* d_pk48, std::vector<int8_t>& st, void* stream);
 // a table of decoded keys (nbls_keyset_create): raw projective points, the identity stored for zero keys and keys that did not decode, and the decoder's status of every key

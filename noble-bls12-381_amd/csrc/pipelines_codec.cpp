@@ -514,16 +514,14 @@ EXPORT int nbls_g2_msm(nbls_ctx* ctx, size_t n, const uint8_t* pts192, const uin
 // in device memory; enqueued on `stream` (NULL = the context's stream) except for one 4-byte read-back in the middle
 EXPORT int nbls_msm_dev(nbls_ctx* ctx, int g2, size_t n, const void* d_pts, const void* d_scalars32, unsigned nbits, void* d_out, void* d_status, void* stream) {
   if (!ctx || !d_out || !d_status || (n && (!d_pts || !d_scalars32))) return NBLS_EINVAL;
-  std::lock_guard<std::recursive_mutex> g_(ctx->mu); HIPCHK(hipSetDevice(ctx->device));
-  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-  StreamOrder order_(ctx, s);
+  DEV_ENTER(ctx, stream);
   return dev_msm(ctx, g2 != 0, n, d_pts, d_scalars32, nbits, d_out, d_status, s);
 }
 
 // sign(message_i, key_i) (index.ts:744-752): hashToCurve -> multiply by the key -> affine signature point (the caller
 // compresses, PointG2.toSignature index.ts:586-602).  status: 0 ok, 5 key is 0 mod r.
 EXPORT int nbls_sign_batch(nbls_ctx* ctx, size_t n, const uint8_t* msgs, const uint32_t* offsets, const uint8_t* dst, size_t dst_len, const uint8_t* keys32, uint8_t* out192, int8_t* status) {
-  std::lock_guard<std::recursive_mutex> whole_call_(ctx ? ctx->mu : g_null_mu);   // scratch and I/O staging buffers belong to this call until it returns
+  WHOLE_CALL(ctx);   // scratch and I/O staging buffers belong to this call until it returns
   if (!ctx || (n && (!offsets || !out192 || !dst || !keys32))) return NBLS_EINVAL; if (!n) return NBLS_OK;
   // Round 6: ONE pinned staging block in, one out.  Round 5 made six copies from / to pageable memory (messages, offsets, tag, keys; signatures, statuses) with a
   // synchronisation in the middle: 0.5 ms of a 4.4 ms call at 8192 keys (the same call on resident inputs: 3.85 ms).  Inputs are packed into the context's pinned buffer --
@@ -578,14 +576,12 @@ int dst_on_device(nbls_ctx* ctx, const uint8_t* dst, size_t* dst_len, hipStream_
 // the constant-time ladder in one chain on `stream`.  Synchronises (the offsets are validated by the hashing kernel and the verdict is read back).  index.ts:744-752.
 EXPORT int nbls_sign_batch_dev(nbls_ctx* ctx, size_t n, const void* d_msgs, const void* d_offsets, const uint8_t* dst, size_t dst_len, const void* d_keys32, void* d_out192, void* d_status,
     void* stream) {
-  std::lock_guard<std::recursive_mutex> whole_call_(ctx ? ctx->mu : g_null_mu);
+  WHOLE_CALL(ctx);
   if (!ctx || (n && (!d_offsets || !d_keys32 || !d_out192 || !d_status || !dst))) return NBLS_EINVAL;
   if (!n) return NBLS_OK;
-  HIPCHK(hipSetDevice(ctx->device));
-  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+  DEV_ENTER(ctx, stream);
   uint8_t* dd; int r;
-  if ((r = dst_on_device(ctx, dst, &dst_len, s, &dd))) return r;
-  StreamOrder order_(ctx, s);
+  if ((r = dst_on_device(ctx, dst, &dst_len, s, &dd))) return r;   // (enqueues nothing on s; with a new tag it waits for s, which StreamOrder has put behind the previous call's stream)
   HostIO io{ctx}; io.s = s; void* h = io.alloc(n * 192); if (!h) return NBLS_EHIP;
   uint8_t* du;
   if ((r = need(ctx, SB_UNIFORM, n * 256 + 16, &du))) return r;

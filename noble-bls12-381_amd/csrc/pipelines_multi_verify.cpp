@@ -130,8 +130,7 @@ int verify_multiple_pipeline(nbls_ctx* ctx, const MultiVerifyIn& in, int* all_ok
   // bad-offsets word | (shared messages) zero-group word
   const size_t o_h = (nh + 1) * 96, o_pkd = o_h + (nh + 1) * 192, o_sgd = o_pkd + n * 96, o_res = o_sgd + n * 192, o_bad = 576 + ((2 * n + 1 + 3) & ~(size_t)3),
                st_bytes = o_bad - 576 + (mg ? 8 : 4), back = 576 + st_bytes;
-  LOCKED(ctx);
-  StreamOrder order_(ctx, s);
+  DEV_ENTER(ctx, nullptr);
   uint8_t *c, *du, *W, *P, *Pj, *N, *NI = nullptr; int r;
   if ((r = need(ctx, SB_STAGED, in_bytes, &c)) || (r = need(ctx, SB_UNIFORM, nh * 256, &du)) || (r = need(ctx, SB_RLC_WEIGHTS, n * 32, &W)) || (r = need(ctx, SB_RLC_PAIRS, o_res + back, &P)) ||
       (r = need(ctx, SB_RLC_KEYS_PROJ, n * 3 * RAW + n, &Pj)) || (r = need(ctx, SB_RLC_KEYS_NORM, n * RAW, &N)) || (!mg && (r = need(ctx, SB_RLC_KEYS_INV, n * RAW, &NI))) ||
@@ -232,7 +231,7 @@ static const size_t AGG_MAX_KEYS = (size_t)1 << 24;   // keys per call (u32 set 
 // indices; aggregates: key offsets that are increasing -- no empty set, the reference's aggregatePublicKeys throws "Expected non-empty array" -- over at most AGG_MAX_KEYS keys,
 // every index inside the table.  Fills in agg->nkeys / maxset.
 static int multi_verify(nbls_ctx* ctx, MultiVerifyIn in, AggKeys* agg, bool indexed, const MsgGroups* mg, int* all_ok, int8_t* status) {
-  std::lock_guard<std::recursive_mutex> whole_call_(ctx ? ctx->mu : g_null_mu);   // scratch and I/O staging buffers belong to this call until it returns
+  WHOLE_CALL(ctx);   // scratch and I/O staging buffers belong to this call until it returns
   const size_t n = in.n, nh = mg ? mg->n_msgs : n;
   if (!ctx || !all_ok || !n || n > ((size_t)1 << 22) || !in.sigs96 || !in.offsets || !in.dst || (mg && (!mg->msg_index || !nh || nh > n))) return NBLS_EINVAL;
   if (!in.msgs && in.offsets[nh] != in.offsets[0]) return NBLS_EINVAL;
@@ -288,7 +287,7 @@ EXPORT int nbls_verify_aggregates_indexed_shared(nbls_ctx* ctx, const nbls_keyse
 // decoder's status of every key (which nbls_verify_aggregates_indexed reports for a set that names the key).  Owns its device memory: usable from any context on the same device,
 // and after the creating context is destroyed.
 EXPORT int nbls_keyset_create(nbls_ctx* ctx, size_t n, const uint8_t* pks48, int8_t* status, nbls_keyset** out) {
-  std::lock_guard<std::recursive_mutex> whole_call_(ctx ? ctx->mu : g_null_mu);
+  WHOLE_CALL(ctx);
   if (!ctx || !n || !pks48 || !out || n > AGG_MAX_KEYS) return NBLS_EINVAL;
   *out = nullptr;
   LOCKED(ctx);

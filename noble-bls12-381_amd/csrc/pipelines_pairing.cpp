@@ -45,25 +45,20 @@ int final_exp_pipeline(nbls_ctx* ctx, size_t n, uint8_t* f_raw, void* d_out, hip
   uint8_t** T = ctx->T;
   if ((r = run_inv(ctx, n, s))) return r;
   if ((r = run(ctx, P_FE_EASY, n, {B(3, f_raw, F12), B(4, ctx->NI, RAW), B(5, T[0], F12)}, s))) return r;
+  // the seven launches between the easy part and the final product (math.ts:862-867): t2 = t1^x, t3 = conj(t1^2) t2, t4 = t3^x, t5 = t4^x, t6' = t5^x, t6 = t6' t2^2, t7 = t6^x
+  const ChainLink mid[7] = {{P_EXPX, {B(3, T[0], F12), B(5, T[1], F12)}},                          // t2
+                            {P_FE_MID1, {B(3, T[0], F12), B(5, T[1], F12), B(6, T[2], F12)}},      // t3
+                            {P_EXPX, {B(3, T[2], F12), B(5, T[3], F12)}},                          // t4
+                            {P_EXPX, {B(3, T[3], F12), B(5, T[4], F12)}},                          // t5
+                            {P_EXPX, {B(3, T[4], F12), B(5, T[6], F12)}},                          // t6' (parked in T7's buffer)
+                            {P_FE_MID2, {B(3, T[6], F12), B(5, T[1], F12), B(6, T[5], F12)}},      // t6
+                            {P_EXPX, {B(3, T[5], F12), B(5, T[6], F12)}}};                         // t7
   if (n < ctx->expc_min && n < ctx->chain_max && !ctx->in_halves && ls_variant(ctx, P_EXPX, n) == P_EXPX && !wide_applies(ctx, ctx->prog[P_EXPX], (int)P_EXPX, n)) {
-    // the seven launches between the easy part and the final product as one chain (math.ts:862-867): t2 = t1^x, t3 = conj(t1^2) t2, t4 = t3^x, t5 = t4^x,
-    // t6' = t5^x, t6 = t6' t2^2, t7 = t6^x
-    if ((r = run_chain(ctx, n, {{P_EXPX, {B(3, T[0], F12), B(5, T[1], F12)}},
-                                {P_FE_MID1, {B(3, T[0], F12), B(5, T[1], F12), B(6, T[2], F12)}},
-                                {P_EXPX, {B(3, T[2], F12), B(5, T[3], F12)}},
-                                {P_EXPX, {B(3, T[3], F12), B(5, T[4], F12)}},
-                                {P_EXPX, {B(3, T[4], F12), B(5, T[6], F12)}},
-                                {P_FE_MID2, {B(3, T[6], F12), B(5, T[1], F12), B(6, T[5], F12)}},
-                                {P_EXPX, {B(3, T[5], F12), B(5, T[6], F12)}}}, s))) return r;
-    return run(ctx, P_FE_FINAL, n, {B(0, T[0], F12), B(1, T[1], F12), B(2, T[2], F12), B(3, T[3], F12), B(4, T[4], F12), B(5, T[5], F12), B(6, T[6], F12), B(7, d_out, 576)}, s);
+    if ((r = run_chain(ctx, n, mid, 7, s))) return r;      // as one chain
+  } else for (const ChainLink& l : mid) {                  // launch by launch; the exponentiations through expx(), which has forms of its own (rows of P_EXPX are {in, out})
+    const BufArg* b = l.bufs.begin();
+    if ((r = l.id == P_EXPX ? expx(ctx, n, (uint8_t*)b[0].second.first, (uint8_t*)b[1].second.first, s) : run(ctx, l.id, n, l.bufs, s))) return r;
   }
-  if ((r = expx(ctx, n, T[0], T[1], s))) return r;   // t2
-  if ((r = run(ctx, P_FE_MID1, n, {B(3, T[0], F12), B(5, T[1], F12), B(6, T[2], F12)}, s))) return r;   // t3
-  if ((r = expx(ctx, n, T[2], T[3], s))) return r;   // t4
-  if ((r = expx(ctx, n, T[3], T[4], s))) return r;   // t5
-  if ((r = expx(ctx, n, T[4], T[6], s))) return r;   // t6' (parked in T7's buffer)
-  if ((r = run(ctx, P_FE_MID2, n, {B(3, T[6], F12), B(5, T[1], F12), B(6, T[5], F12)}, s))) return r;   // t6
-  if ((r = expx(ctx, n, T[5], T[6], s))) return r;   // t7
   return run(ctx, P_FE_FINAL, n, {B(0, T[0], F12), B(1, T[1], F12), B(2, T[2], F12), B(3, T[3], F12), B(4, T[4], F12), B(5, T[5], F12), B(6, T[6], F12), B(7, d_out, 576)}, s);
 }
 // one raw Fp12 -> final exponentiation (or plain encoding) -> wire bytes on device
@@ -73,26 +68,31 @@ int finish_single(nbls_ctx* ctx, uint8_t* f_raw, int final_exp, void* d_out, hip
   if ((r = run(ctx, P_NORM_RAW, 1, {B(3, f_raw, F12), B(4, ctx->N, RAW)}, s))) return r;
   return final_exp_pipeline(ctx, 1, f_raw, d_out, s);
 }
+// the product of the m raw Fp12 values in ctx->F (m = 0: ONE) -> finish_single
+static int finish_product(nbls_ctx* ctx, size_t m, int final_exp, void* d_out, hipStream_t s) {
+  int r;
+  uint8_t* res = ctx->F;
+  if (m == 0) HIPCHK(hipMemcpyAsync(ctx->F, ctx->one12, F12, hipMemcpyDeviceToDevice, s));
+  else if ((r = reduce_product(ctx, m, &res, s))) return r;
+  return finish_single(ctx, res, final_exp, d_out, s);
+}
 
 EXPORT int nbls_pairing_batch_dev(nbls_ctx* ctx, size_t n, const void* d_g1, const void* d_g2, int with_final_exp, void* d_out, void* stream) {
   if (!ctx || (n && (!d_g1 || !d_g2 || !d_out))) return NBLS_EINVAL;
   if (n == 0) return NBLS_OK;
-  std::lock_guard<std::recursive_mutex> g(ctx->mu);
-  HIPCHK(hipSetDevice(ctx->device));
-  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-  StreamOrder order_(ctx, s);
-  // A batch of 8192 pairs or more runs as two halves on two streams: every launch of a dependent chain ends in a partly filled round of wavefronts (EXPX at 65,536 pairs: 4.65
-  // rounds of 2,816 resident wavefronts), and the tail of one half is filled by the other (65,536 pairs: 27.4 -> 25.9 ms).  Both halves use the caller's scratch
-  // through an item offset (ctx->ioff, applied by run() to every per-item buffer) and the two-program Miller loop (what counts with work in flight is the instruction count).
-  // (measured from 8192 pairs up: 8192 5.08 -> 4.69 ms, 16,384 8.53 -> 7.73, 24,576 11.96 -> 10.33, 32,768 14.96 -> 13.64, 65,536 27.5 -> 26.0; the exception is a batch that
-  // fills the chip exactly three wavefronts deep in ONE round with the fused program, 12,288 pairs: 6.04 ms against 6.39)
-  const bool one_full_round = n > 10752 && n <= 12288;
-  if (n >= ctx->halves_min && !one_full_round && n <= LINES_CHUNK) {
+  DEV_ENTER(ctx, stream);
+  // A batch of ctx->halves_min pairs or more (16,384; 8192 until the end of round 6, nbls_internal.h) runs as two halves on two streams: every launch of a dependent chain ends in a
+  // partly filled round of wavefronts (EXPX at 65,536 pairs: 4.65 rounds of 2,816 resident wavefronts), and the tail of one half is filled by the other (65,536 pairs: 27.4 -> 25.9 ms).
+  // Both halves use the caller's scratch through an item offset (ctx->ioff, applied by run() to every per-item buffer) and the two-program Miller loop (what counts with work in flight
+  // is the instruction count).
+  // (measured in round 5, when the threshold was 8192: 8192 5.08 -> 4.69 ms, 16,384 8.53 -> 7.73, 24,576 11.96 -> 10.33, 32,768 14.96 -> 13.64, 65,536 27.5 -> 26.0.  The exception then
+  // was a batch that fills the chip exactly three wavefronts deep in ONE round with the fused program, 12,288 pairs: 6.04 ms against 6.39; that window, 10,753 .. 12,288 pairs, lies
+  // below today's threshold and has no case of its own any more)
+  if (n >= ctx->halves_min && n <= LINES_CHUNK) {
     int r;
     if ((r = ensure_lines(ctx, n))) return r;
     if (with_final_exp && (r = ensure_scratch(ctx, n))) return r;
-    if (!ctx->half_stream && (hipStreamCreateWithFlags(&ctx->half_stream, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&ctx->ev_half_fork, hipEventDisableTiming) != hipSuccess ||
-                              hipEventCreateWithFlags(&ctx->ev_half_join, hipEventDisableTiming) != hipSuccess)) { ctx->last_hip = (int)hipGetLastError(); return NBLS_EHIP; }
+    if ((r = ensure_half_stream(ctx))) return r;
     // size of the first half in per cent (clamped to 1 .. 99): slightly unequal halves do not run phase-locked (profiles/round5_ab_split.txt: 16,384 pairs 6.25 -> 6.14 ms, 65,536 within
     // noise)
     static const size_t split_pct = (size_t)std::min<long>(99, std::max<long>(1, env_long("NBLS_HALVES_SPLIT_PCT", 55)));
@@ -216,6 +216,29 @@ EXPORT int nbls_pairing_batch(nbls_ctx* ctx, size_t n, const uint8_t* g1, const 
   return NBLS_OK;
 }
 
+// The Miller stage of the product forms: c pairs -> their line tables at L (P_LINES_PQ) -> ceil(c / GR) raw accumulators from acc_out on, GR (1, 2, 4 or 8) tables sharing one
+// (P_ACC_RAW .. P_ACC8_RAW).  A last group of fewer than GR tables is filled up with the unit table, so L holds up to GR - 1 tables more than c.  h < c: the stage runs as two parts,
+// [0, h) on s and everything behind it on the half stream, joined into s at the end; h is a multiple of GR, so that no group spans the parts.  h >= c: one part.  The callers choose
+// GR and h: their thresholds were measured separately (miller_values, verify_pipeline).
+int lines_acc(nbls_ctx* ctx, size_t c, const uint8_t* g1, const uint8_t* g2, uint8_t* L, size_t GR, uint8_t* acc_out, size_t h, hipStream_t s) {
+  int r;
+  const ProgId acc = GR == 8 ? P_ACC8_RAW : GR == 4 ? P_ACC4_RAW : GR == 2 ? P_ACC2_RAW : P_ACC_RAW;
+  if (h == 0 || h > c) h = c;
+  if (h < c) {
+    if ((r = ensure_half_stream(ctx))) return r;
+    HIPCHK(hipEventRecord(ctx->ev_half_fork, s)); HIPCHK(hipStreamWaitEvent(ctx->half_stream, ctx->ev_half_fork, 0));
+  }
+  for (size_t lo = 0; lo < c; lo += h) {
+    const size_t cc = lo ? c - lo : h, gg = (cc + GR - 1) / GR;      // two parts: [0, h) and everything behind it
+    hipStream_t sh = lo ? ctx->half_stream : s;
+    if ((r = run(ctx, P_LINES_PQ, cc, {B(0, g1 + lo * 96, 96), B(1, g2 + lo * 192, 192), B(3, L + lo * LINE_BYTES, LINE_BYTES)}, sh))) return r;
+    for (size_t k = cc; k < GR * gg; k++) HIPCHK(hipMemcpyAsync(L + (lo + k) * LINE_BYTES, ctx->unit_lines, LINE_BYTES, hipMemcpyDeviceToDevice, sh));
+    if ((r = run(ctx, acc, gg, {B(3, L + lo * LINE_BYTES, GR * LINE_BYTES), B(5, acc_out + lo / GR * F12, F12)}, sh))) return r;
+    if (lo) break;
+  }
+  if (h < c) { HIPCHK(hipEventRecord(ctx->ev_half_join, ctx->half_stream)); HIPCHK(hipStreamWaitEvent(s, ctx->ev_half_join, 0)); }
+  return NBLS_OK;
+}
 // n >= 1 pairs -> *m_out raw Miller values (products of up to eight Miller loops each) in ctx->F[0 .. *m_out); the caller multiplies them (reduce_product)
 int miller_values(nbls_ctx* ctx, size_t n, const void* d_g1, const void* d_g2, size_t* m_out, hipStream_t s) {
   int r;
@@ -238,34 +261,20 @@ int miller_values(nbls_ctx* ctx, size_t n, const void* d_g1, const void* d_g2, s
       // multiplying by it changes nothing) instead of getting a launch -- and the latency of a whole Miller loop -- of its own.
       // round 4: EIGHT pairs per accumulator from acc8_min pairs per call (one squaring per eight line tables: 1,921 instead of 2,196 instructions per pair and bit) -- off since round 6
       // round 6: FEWER pairs per accumulator where a launch is too small to fill the device with four: the accumulation program's instruction stream grows with the pairs per
-      // item (four: 1.46 ms for one wavefront), and 4097 pairs in groups of four are 205 wavefronts on 1024 SIMDs.  By the pairs of ONE launch (a call of 8192 pairs and more
+      // item (four: 1.46 ms for one wavefront), and 4097 pairs in groups of four are 205 wavefronts on 1024 SIMDs.  By the pairs of ONE launch (a call of halves_min pairs and more
       // runs as two halves): one pair per item below acc2_min, two below acc4_min, four above; eight no longer pays at any size (profiles/round6_ab_acc_width.txt: 4098 pairs
       // 2.91 -> 2.13 ms, 8192 4.01 -> 2.77, 16,384 4.54 -> 3.79, 49,152 8.59 -> 7.85, 2^18 32.2 -> 30.9 ms)
       static const size_t acc2_min = (size_t)env_long("NBLS_ACC2_MIN", 6144), acc4_min = (size_t)env_long("NBLS_ACC4_MIN", 28672);
       const size_t chunk = n < LINES_CHUNK ? n : LINES_CHUNK, part = (chunk >= ctx->halves_min && ctx->ioff == 0) ? chunk / 2 : chunk;
       const size_t GR = n >= ctx->acc8_min ? 8 : part >= acc4_min ? 4 : part >= acc2_min ? 2 : 1;
-      const ProgId acc = GR == 8 ? P_ACC8_RAW : GR == 4 ? P_ACC4_RAW : GR == 2 ? P_ACC2_RAW : P_ACC_RAW;
       if ((r = ensure_lines(ctx, n + GR - 1))) return r;
       m = 0;
       for (size_t o = 0; o < n; o += LINES_CHUNK) {   // LINES_CHUNK is a multiple of eight: a chunk boundary never splits a group
-        const size_t c = n - o < LINES_CHUNK ? n - o : LINES_CHUNK, cg = (c + GR - 1) / GR;
+        const size_t c = n - o < LINES_CHUNK ? n - o : LINES_CHUNK;
         // a large chunk runs as two halves (whole groups) on two streams, like nbls_pairing_batch_dev: the tail of LINES / ACC of one half under the other
         const size_t h = (c >= ctx->halves_min && ctx->ioff == 0) ? ((c / 2 + GR - 1) & ~(GR - 1)) : c;
-        if (h < c && !ctx->half_stream && (hipStreamCreateWithFlags(&ctx->half_stream, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&ctx->ev_half_fork,
-            hipEventDisableTiming) != hipSuccess ||
-                                           hipEventCreateWithFlags(&ctx->ev_half_join, hipEventDisableTiming) != hipSuccess)) { ctx->last_hip = (int)hipGetLastError(); return NBLS_EHIP; }
-        if (h < c) { HIPCHK(hipEventRecord(ctx->ev_half_fork, s)); HIPCHK(hipStreamWaitEvent(ctx->half_stream, ctx->ev_half_fork, 0)); }
-        for (size_t lo = 0; lo < c; lo += h) {
-          const size_t cc = lo ? c - lo : h, gg = (cc + GR - 1) / GR;      // two parts: [0, h) and everything behind it
-          hipStream_t sh = lo ? ctx->half_stream : s;
-          if ((r = run(ctx, P_LINES_PQ, cc, {B(0, (const uint8_t*)d_g1 + (o + lo) * 96, 96), B(1, (const uint8_t*)d_g2 + (o + lo) * 192, 192), B(3, ctx->L + lo * LINE_BYTES, LINE_BYTES)},
-              sh))) return r;
-          for (size_t k = cc; k < GR * gg; k++) HIPCHK(hipMemcpyAsync(ctx->L + (lo + k) * LINE_BYTES, ctx->unit_lines, LINE_BYTES, hipMemcpyDeviceToDevice, sh));
-          if ((r = run(ctx, acc, gg, {B(3, ctx->L + lo * LINE_BYTES, GR * LINE_BYTES), B(5, ctx->F + (m + lo / GR) * F12, F12)}, sh))) return r;
-          if (lo) break;
-        }
-        if (h < c) { HIPCHK(hipEventRecord(ctx->ev_half_join, ctx->half_stream)); HIPCHK(hipStreamWaitEvent(s, ctx->ev_half_join, 0)); }
-        m += cg;
+        if ((r = lines_acc(ctx, c, (const uint8_t*)d_g1 + o * 96, (const uint8_t*)d_g2 + o * 192, ctx->L, GR, ctx->F + m * F12, h, s))) return r;
+        m += (c + GR - 1) / GR;
       }
     }
     *m_out = m;
@@ -274,20 +283,11 @@ int miller_values(nbls_ctx* ctx, size_t n, const void* d_g1, const void* d_g2, s
 }
 EXPORT int nbls_miller_product_dev(nbls_ctx* ctx, size_t n, const void* d_g1, const void* d_g2, int final_exp, void* d_out, void* stream) {
   if (!ctx || !d_out || (n && (!d_g1 || !d_g2))) return NBLS_EINVAL;
-  std::lock_guard<std::recursive_mutex> g(ctx->mu);
-  HIPCHK(hipSetDevice(ctx->device));
-  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-  StreamOrder order_(ctx, s);
+  DEV_ENTER(ctx, stream);
   int r;
-  if ((r = ensure_scratch(ctx, n ? n : 1))) return r;
-  uint8_t* res = ctx->F;
-  if (n == 0) { HIPCHK(hipMemcpyAsync(ctx->F, ctx->one12, F12, hipMemcpyDeviceToDevice, s)); }
-  else {
-    size_t m = 0;
-    if ((r = miller_values(ctx, n, d_g1, d_g2, &m, s))) return r;
-    if ((r = reduce_product(ctx, m, &res, s))) return r;
-  }
-  return finish_single(ctx, res, final_exp, d_out, s);
+  size_t m = 0;
+  if ((r = ensure_scratch(ctx, n ? n : 1)) || (n && (r = miller_values(ctx, n, d_g1, d_g2, &m, s)))) return r;
+  return finish_product(ctx, m, final_exp, d_out, s);
 }
 
 EXPORT int nbls_miller_product(nbls_ctx* ctx, size_t n, const uint8_t* g1, const uint8_t* g2, int final_exp, int validate, uint8_t* out, int8_t* status) {
@@ -316,10 +316,7 @@ EXPORT int nbls_miller_product(nbls_ctx* ctx, size_t n, const uint8_t* g1, const
 EXPORT int nbls_final_exp_batch_dev(nbls_ctx* ctx, size_t n, const void* d_in, void* d_out, void* stream) {
   if (!ctx || (n && (!d_in || !d_out))) return NBLS_EINVAL;
   if (n == 0) return NBLS_OK;
-  std::lock_guard<std::recursive_mutex> g(ctx->mu);
-  HIPCHK(hipSetDevice(ctx->device));
-  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-  StreamOrder order_(ctx, s);
+  DEV_ENTER(ctx, stream);
   int r;
   if ((r = ensure_scratch(ctx, n))) return r;
   if ((r = run(ctx, P_NORM_BYTES, n, {B(2, d_in, 576), B(3, ctx->F, F12), B(4, ctx->N, RAW)}, s))) return r;
@@ -327,34 +324,26 @@ EXPORT int nbls_final_exp_batch_dev(nbls_ctx* ctx, size_t n, const void* d_in, v
 }
 
 EXPORT int nbls_final_exp_batch(nbls_ctx* ctx, size_t n, const uint8_t* in, uint8_t* out) {
-  std::lock_guard<std::recursive_mutex> whole_call_(ctx ? ctx->mu : g_null_mu);   // scratch and I/O staging buffers belong to this call until it returns
   if (!ctx || (n && (!in || !out))) return NBLS_EINVAL;
   if (n == 0) return NBLS_OK;
+  LOCKED(ctx);   // scratch and I/O staging buffers belong to this call until it returns
   int r;
-  {
-    std::lock_guard<std::recursive_mutex> g(ctx->mu);
-    HIPCHK(hipSetDevice(ctx->device));
-    if ((r = ensure_io(ctx, 2 * n))) return r;
-    HIPCHK(hipMemcpyAsync(ctx->io_f12, in, n * 576, hipMemcpyHostToDevice, ctx->stream));
-  }
+  if ((r = ensure_io(ctx, 2 * n))) return r;
   uint8_t* d_out = ctx->io_f12 + n * 576;
-  if ((r = nbls_final_exp_batch_dev(ctx, n, ctx->io_f12, d_out, ctx->stream))) return r;
-  std::lock_guard<std::recursive_mutex> g(ctx->mu);
-  HIPCHK(hipMemcpyAsync(out, d_out, n * 576, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
+  HIPCHK(hipMemcpyAsync(ctx->io_f12, in, n * 576, hipMemcpyHostToDevice, s));
+  if ((r = nbls_final_exp_batch_dev(ctx, n, ctx->io_f12, d_out, s))) return r;
+  HIPCHK(hipMemcpyAsync(out, d_out, n * 576, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
   return NBLS_OK;
 }
 
 // One tower operation on n elements (include/nbls.h): wire bytes in and out, everything on the device.  Inversions are two programs around the inversion kernel.
 EXPORT int nbls_tower_op_batch(nbls_ctx* ctx, int field, int op, int param, size_t n, const uint8_t* a, const uint8_t* b, const uint8_t* c, const uint8_t* d, uint8_t* out) {
-  std::lock_guard<std::recursive_mutex> whole_call_(ctx ? ctx->mu : g_null_mu);
   if (!ctx || (n && (!a || !out))) return NBLS_EINVAL;
   const Program* p0 = get_tower_program(field, op, param, 0);
   if (!p0) return NBLS_EINVAL;
   if (n == 0) return NBLS_OK;
-  HIPCHK(hipSetDevice(ctx->device));
-  hipStream_t s = ctx->stream;
-  StreamOrder order_(ctx, s);
+  DEV_ENTER(ctx, nullptr);
   const size_t esz = 48 * (size_t)field;
   // operand sizes: b is a full element for the binary operations, an Fp2 for the sparse products; c, d are Fp2
   const bool sparse = op == 10 || op == 11 || op == 12;
@@ -362,15 +351,13 @@ EXPORT int nbls_tower_op_batch(nbls_ctx* ctx, int field, int op, int param, size
   if ((p0->buf_extent[1] && !b) || (p0->buf_extent[2] && !c) || (p0->buf_extent[3] && !d)) return NBLS_EINVAL;
   int r;
   if ((r = ensure_scratch(ctx, n))) return r;
-  const size_t need = n * (2 * esz + bsz + csz + dsz);
-  uint8_t* io = nullptr;
-  HIPCHK(hipMalloc(&io, need));
-  uint8_t *da = io, *db = da + n * esz, *dc = db + n * bsz, *dd = dc + n * csz, *dout = dd + n * dsz;
-  auto fail = [&](int code) { hipFree(io); return code; };
-  if (hipMemcpyAsync(da, a, n * esz, hipMemcpyHostToDevice, s) != hipSuccess) return fail(NBLS_EHIP);
-  if (b && hipMemcpyAsync(db, b, n * bsz, hipMemcpyHostToDevice, s) != hipSuccess) return fail(NBLS_EHIP);
-  if (c && hipMemcpyAsync(dc, c, n * csz, hipMemcpyHostToDevice, s) != hipSuccess) return fail(NBLS_EHIP);
-  if (d && hipMemcpyAsync(dd, d, n * dsz, hipMemcpyHostToDevice, s) != hipSuccess) return fail(NBLS_EHIP);
+  HostIO io{ctx};   // one staging block: a | b | c | d | out
+  uint8_t* da = (uint8_t*)io.alloc(n * (2 * esz + bsz + csz + dsz)); if (!da) return NBLS_EHIP;
+  uint8_t *db = da + n * esz, *dc = db + n * bsz, *dd = dc + n * csz, *dout = dd + n * dsz;
+  HIPCHK(hipMemcpyAsync(da, a, n * esz, hipMemcpyHostToDevice, s));
+  if (b) HIPCHK(hipMemcpyAsync(db, b, n * bsz, hipMemcpyHostToDevice, s));
+  if (c) HIPCHK(hipMemcpyAsync(dc, c, n * csz, hipMemcpyHostToDevice, s));
+  if (d) HIPCHK(hipMemcpyAsync(dd, d, n * dsz, hipMemcpyHostToDevice, s));
   auto launch = [&](int part) -> int {
     const Program* p = get_tower_program(field, op, param, part);
     if (!p) return NBLS_EINVAL;
@@ -378,33 +365,21 @@ EXPORT int nbls_tower_op_batch(nbls_ctx* ctx, int field, int op, int param, size
     if (!dp.p) { const int e = upload_program(ctx, dp, *p, -1); if (e) return e; }
     return run_dev(ctx, dp, -1, n, {B(0, da, esz), B(1, db, bsz), B(2, dc, csz), B(3, dd, dsz), B(4, ctx->N, RAW), B(5, ctx->NI, RAW), B(7, dout, esz)}, s, nullptr, nullptr);
   };
-  if ((r = launch(0))) return fail(r);
-  if (op == 5) {   // NBLS_TOP_INV
-    if ((r = run_inv(ctx, n, s))) return fail(r);
-    if ((r = launch(1))) return fail(r);
-  }
-  if (hipMemcpyAsync(out, dout, n * esz, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) return fail(NBLS_EHIP);
-  hipFree(io);
+  if ((r = launch(0))) return r;
+  if (op == 5 && ((r = run_inv(ctx, n, s)) || (r = launch(1)))) return r;   // NBLS_TOP_INV
+  HIPCHK(hipMemcpyAsync(out, dout, n * esz, hipMemcpyDeviceToHost, s)); HIPCHK(hipStreamSynchronize(s));
   return NBLS_OK;
 }
 
 // n Fp12 wire elements on the device -> their product, optionally final-exponentiated (multi-GPU: partials of all ranks)
 EXPORT int nbls_fp12_product_final_dev(nbls_ctx* ctx, size_t n, const void* d_in, int final_exp, void* d_out, void* stream) {
   if (!ctx || !d_out || (n && !d_in)) return NBLS_EINVAL;
-  std::lock_guard<std::recursive_mutex> g(ctx->mu);
-  HIPCHK(hipSetDevice(ctx->device));
-  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-  StreamOrder order_(ctx, s);
+  DEV_ENTER(ctx, stream);
   int r;
   if ((r = ensure_scratch(ctx, n ? n : 1))) return r;
-  uint8_t* res = ctx->F;
-  if (n == 0) { HIPCHK(hipMemcpyAsync(ctx->F, ctx->one12, F12, hipMemcpyDeviceToDevice, s)); }
-  else {
-    // wire bytes -> raw Montgomery (P_NORM_BYTES also writes N, which is ignored here)
-    if ((r = run(ctx, P_NORM_BYTES, n, {B(2, d_in, 576), B(3, ctx->F, F12), B(4, ctx->N, RAW)}, s))) return r;
-    if ((r = reduce_product(ctx, n, &res, s))) return r;
-  }
-  return finish_single(ctx, res, final_exp, d_out, s);
+  // wire bytes -> raw Montgomery (P_NORM_BYTES also writes N, which is ignored here)
+  if (n && (r = run(ctx, P_NORM_BYTES, n, {B(2, d_in, 576), B(3, ctx->F, F12), B(4, ctx->N, RAW)}, s))) return r;
+  return finish_product(ctx, n, final_exp, d_out, s);
 }
 
 // ---- prepared G2 points: PointG2.pairingPrecomputes() (index.ts:703-711) and PointG1.millerLoop (index.ts:452-454) -----------------
@@ -412,27 +387,20 @@ EXPORT int nbls_fp12_product_final_dev(nbls_ctx* ctx, size_t n, const void* d_in
 EXPORT int nbls_g2_prepare_dev(nbls_ctx* ctx, size_t n, const void* d_g2, void* d_tables, void* stream) {
   if (!ctx || (n && (!d_g2 || !d_tables))) return NBLS_EINVAL;
   if (n == 0) return NBLS_OK;
-  std::lock_guard<std::recursive_mutex> g(ctx->mu);
-  HIPCHK(hipSetDevice(ctx->device));
-  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-  StreamOrder order_(ctx, s);
+  DEV_ENTER(ctx, stream);
   return run(ctx, P_LINES_Q, n, {B(1, d_g2, 192), B(3, d_tables, LINE_BYTES)}, s);
 }
 // raw tables <-> the reference's value: 68 x [Fp2, Fp2, Fp2] as Fp2.toBytes (NBLS_LINE_WIRE_BYTES per point)
 EXPORT int nbls_lines_to_wire_dev(nbls_ctx* ctx, size_t n, const void* d_tables, void* d_wire, void* stream) {
   if (!ctx || (n && (!d_tables || !d_wire))) return NBLS_EINVAL;
   if (n == 0) return NBLS_OK;
-  std::lock_guard<std::recursive_mutex> g(ctx->mu);
-  HIPCHK(hipSetDevice(ctx->device));
-  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+  DEV_ENTER(ctx, stream);
   return run(ctx, P_LINES_BYTES, n * N_LINES, {B(3, d_tables, 6 * RAW), B(2, d_wire, 288)}, s);
 }
 EXPORT int nbls_lines_from_wire_dev(nbls_ctx* ctx, size_t n, const void* d_wire, void* d_tables, void* stream) {
   if (!ctx || (n && (!d_tables || !d_wire))) return NBLS_EINVAL;
   if (n == 0) return NBLS_OK;
-  std::lock_guard<std::recursive_mutex> g(ctx->mu);
-  HIPCHK(hipSetDevice(ctx->device));
-  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+  DEV_ENTER(ctx, stream);
   return run(ctx, P_LINES_FROM_BYTES, n * N_LINES, {B(2, d_wire, 288), B(3, d_tables, 6 * RAW)}, s);
 }
 // millerLoop(table_i, P_i) for n items (table_stride = NBLS_LINE_TABLE_BYTES) or millerLoop(table, P_i) with ONE table for every item
@@ -445,10 +413,7 @@ int acc_prepared(nbls_ctx* ctx, size_t n, const void* d_g1, const void* d_tables
 EXPORT int nbls_pairing_prepared_dev(nbls_ctx* ctx, size_t n, const void* d_g1, const void* d_tables, size_t table_stride, int with_final_exp, void* d_out, void* stream) {
   if (!ctx || (n && (!d_g1 || !d_tables || !d_out))) return NBLS_EINVAL;
   if (n == 0) return NBLS_OK;
-  std::lock_guard<std::recursive_mutex> g(ctx->mu);
-  HIPCHK(hipSetDevice(ctx->device));
-  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-  StreamOrder order_(ctx, s);
+  DEV_ENTER(ctx, stream);
   int r = acc_prepared(ctx, n, d_g1, d_tables, table_stride, s); if (r) return r;
   if (!with_final_exp) return run(ctx, P_RAW_TO_BYTES, n, {B(3, ctx->F, F12), B(2, d_out, 576)}, s);
   if ((r = run(ctx, P_NORM_RAW, n, {B(3, ctx->F, F12), B(4, ctx->N, RAW)}, s))) return r;
@@ -456,18 +421,9 @@ EXPORT int nbls_pairing_prepared_dev(nbls_ctx* ctx, size_t n, const void* d_g1, 
 }
 EXPORT int nbls_miller_product_prepared_dev(nbls_ctx* ctx, size_t n, const void* d_g1, const void* d_tables, size_t table_stride, int final_exp, void* d_out, void* stream) {
   if (!ctx || !d_out || (n && (!d_g1 || !d_tables))) return NBLS_EINVAL;
-  std::lock_guard<std::recursive_mutex> g(ctx->mu);
-  HIPCHK(hipSetDevice(ctx->device));
-  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-  StreamOrder order_(ctx, s);
-  int r;
-  uint8_t* res = ctx->F;
-  if (n == 0) { if ((r = ensure_scratch(ctx, 1))) return r; HIPCHK(hipMemcpyAsync(ctx->F, ctx->one12, F12, hipMemcpyDeviceToDevice, s)); }
-  else {
-    if ((r = acc_prepared(ctx, n, d_g1, d_tables, table_stride, s))) return r;
-    if ((r = reduce_product(ctx, n, &res, s))) return r;
-  }
-  return finish_single(ctx, res, final_exp, d_out, s);
+  DEV_ENTER(ctx, stream);
+  int r = n ? acc_prepared(ctx, n, d_g1, d_tables, table_stride, s) : ensure_scratch(ctx, 1); if (r) return r;
+  return finish_product(ctx, n, final_exp, d_out, s);
 }
 // host buffers: affine G2 points -> tables in wire form (what PointG2.pairingPrecomputes() returns)
 EXPORT int nbls_g2_prepare(nbls_ctx* ctx, size_t n, const uint8_t* g2_aff, uint8_t* out_wire) {
@@ -517,15 +473,15 @@ int partial_buffer(nbls_ctx* ctx, void* d_dst, uint8_t** dst) {
   return NBLS_OK;
 }
 int miller_product_partial_core(nbls_ctx* ctx, size_t n, const uint8_t* g1, const uint8_t* g2, int validate, void* d_dst, void** d_partial, int8_t* status) {
-  std::lock_guard<std::recursive_mutex> whole_call_(ctx ? ctx->mu : g_null_mu);
+  WHOLE_CALL(ctx);
   if (!ctx || (n && (!g1 || !g2))) return NBLS_EINVAL;
   int r;
   if (status) memset(status, 0, n);
   if (validate && n) {
-    std::vector<int8_t> st1(n), st2(n);
-    if ((r = nbls_g1_validate_batch(ctx, n, g1, st1.data())) || (r = nbls_g2_validate_batch(ctx, n, g2, st2.data()))) return r;
+    std::vector<int8_t> st12(2 * n);
+    if ((r = nbls_g1_validate_batch(ctx, n, g1, st12.data())) || (r = nbls_g2_validate_batch(ctx, n, g2, st12.data() + n))) return r;
     bool bad = false;
-    for (size_t i = 0; i < n; i++) { int8_t c = st1[i] ? st1[i] : (st2[i] ? (int8_t)(10 + st2[i]) : 0); if (status) status[i] = c; bad |= c != 0; }
+    for (size_t i = 0; i < n; i++) { const int8_t c = pair_code(st12.data(), n, i); if (status) status[i] = c; bad = bad || c; }
     if (bad) return NBLS_EDECODE;
   }
   LOCKED(ctx);

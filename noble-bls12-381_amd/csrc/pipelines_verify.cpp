@@ -36,13 +36,6 @@ int pipe_event(nbls_ctx* ctx, size_t i, hipEvent_t* e) {
   *e = ctx->pipe_ev[i];
   return NBLS_OK;
 }
-int ensure_half_stream(nbls_ctx* ctx) {
-  if (!ctx->half_stream && (hipStreamCreateWithFlags(&ctx->half_stream, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&ctx->ev_half_fork, hipEventDisableTiming) != hipSuccess ||
-                            hipEventCreateWithFlags(&ctx->ev_half_join, hipEventDisableTiming) != hipSuccess)) { ctx->last_hip = (int)hipGetLastError(); return NBLS_EHIP; }
-  return NBLS_OK;
-}
-// final_exp = 1: the product's final exponentiation as 576 wire bytes in `out` (host); 0: the product itself as wire bytes at d_out (device; a shard's partial).
-// st: n statuses of the keys (+ 1 of the signature) as the decoders wrote them; *bad_offsets: the message offsets were not monotonic.
 int pipe_stream(nbls_ctx* ctx, size_t i, hipStream_t* st) {
   // NBLS_VERIFY_PRIO=1: the streams of the later sub-batches get the lowest priority the device offers (experiment: does the first sub-batch then finish its hash chain early?)
   static const long prio_mode = env_long("NBLS_VERIFY_PRIO", 0);
@@ -55,12 +48,32 @@ int pipe_stream(nbls_ctx* ctx, size_t i, hipStream_t* st) {
   *st = ctx->pipe_streams[i];
   return NBLS_OK;
 }
+// normP2: PointG2.fromSignature for the ONE signature, on the side stream with its own scratch (its Fp2 exponentiation on two lanes is pure latency, and it overlaps everything the
+// caller enqueues before sig_join).  The caller has recorded ev_fork on its stream.  The side stream is created on first use: HIP spreads streams over a few hardware queues in
+// creation order, and contexts that only run pairing batches (noble-bls12-381_amd/pipeline.py keeps several in flight) should each get a queue of their own.
+static int sig_fork(nbls_ctx* ctx, const void* d_sig96, uint8_t* g2_out, uint8_t* st_out) {
+  int r;
+  if ((r = ensure_side(ctx))) return r;
+  uint8_t *X = ctx->side_scratch, *Rr = X + 2 * RAW, *Cd = Rr + 2 * RAW, *pw = Cd + 2 * RAW;
+  HIPCHK(hipStreamWaitEvent(ctx->side, ctx->ev_fork, 0));
+  if ((r = run(ctx, P_G2_DEC_A, 1, {B(0, d_sig96, 96), B(3, X, 2 * RAW), B(4, Rr, 2 * RAW)}, ctx->side))) return r;
+  if ((r = run_pow(ctx, 1, 1, Rr, Cd, ctx->side, pw))) return r;
+  if ((r = run(ctx, P_G2_DEC_B, 1, {B(0, d_sig96, 96), B(3, X, 2 * RAW), B(4, Rr, 2 * RAW), B(5, Cd, 2 * RAW), B(6, g2_out, 192), B(7, st_out, 1)}, ctx->side))) return r;
+  HIPCHK(hipEventRecord(ctx->ev_join, ctx->side));
+  return NBLS_OK;
+}
+// the signature's pair (-G, S) is complete on `s`: its G1 half at g1_out, and `s` waits for sig_fork's chain
+static int sig_join(nbls_ctx* ctx, uint8_t* g1_out, hipStream_t s) {
+  HIPCHK(hipMemcpyAsync(g1_out, ctx->neg_g1, 96, hipMemcpyDeviceToDevice, s));         // PointG1.BASE.negate()
+  HIPCHK(hipStreamWaitEvent(s, ctx->ev_join, 0));
+  return NBLS_OK;
+}
+// final_exp = 1: the product's final exponentiation as 576 wire bytes in `out` (host); 0: the product itself as wire bytes at d_out (device; a shard's partial).
+// st: n statuses of the keys (+ 1 of the signature) as the decoders wrote them; *bad_offsets: the message offsets were not monotonic.
 int verify_pipeline(nbls_ctx* ctx, size_t n, const VerifyIn& in, int final_exp, void* d_out, uint8_t* out, std::vector<int8_t>& st, int* bad_offsets, void* stream) {
   const size_t np = n + (in.d_sig96 ? 1 : 0);
   st.assign(np + 8, 0);
-  std::lock_guard<std::recursive_mutex> g_(ctx->mu); HIPCHK(hipSetDevice(ctx->device));
-  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-  StreamOrder order_(ctx, s);
+  DEV_ENTER(ctx, stream);
   int r;
   uint8_t *G1, *G2, *ST, *O, *du = nullptr;
   if ((r = need(ctx, SB_VB_PAIRS, (n + 1) * (96 + 192) + (n + 1) + 576 + 64 + 16, &G1))) return r;
@@ -69,20 +82,11 @@ int verify_pipeline(nbls_ctx* ctx, size_t n, const VerifyIn& in, int final_exp, 
   if (!in.d_uniform && (r = need(ctx, SB_UNIFORM, n * 256, &du))) return r;
   const std::vector<size_t> plan = verify_plan(ctx, n);
   const size_t K = plan.size();
-  if (!ctx->ev_fork && hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming) != hipSuccess) { ctx->last_hip = (int)hipGetLastError(); return NBLS_EHIP; }
+  if ((r = ensure_fork_event(ctx))) return r;
   HIPCHK(hipMemsetAsync(d_bad, 0, 4, s));
   HIPCHK(hipEventRecord(ctx->ev_fork, s));
   ForkGuard fork_guard;
-  if (in.d_sig96) {
-    // normP2: PointG2.fromSignature for the ONE signature, on the side stream with its own scratch (its Fp2 exponentiation on two lanes is pure latency)
-    if ((r = ensure_side(ctx))) return r;
-    uint8_t *X = ctx->side_scratch, *Rr = X + 2 * RAW, *Cd = Rr + 2 * RAW, *pw = Cd + 2 * RAW;
-    HIPCHK(hipStreamWaitEvent(ctx->side, ctx->ev_fork, 0));
-    if ((r = run(ctx, P_G2_DEC_A, 1, {B(0, in.d_sig96, 96), B(3, X, 2 * RAW), B(4, Rr, 2 * RAW)}, ctx->side))) return r;
-    if ((r = run_pow(ctx, 1, 1, Rr, Cd, ctx->side, pw))) return r;
-    if ((r = run(ctx, P_G2_DEC_B, 1, {B(0, in.d_sig96, 96), B(3, X, 2 * RAW), B(4, Rr, 2 * RAW), B(5, Cd, 2 * RAW), B(6, G2 + n * 192, 192), B(7, ST + n, 1)}, ctx->side))) return r;
-    HIPCHK(hipEventRecord(ctx->ev_join, ctx->side));
-  }
+  if (in.d_sig96 && (r = sig_fork(ctx, in.d_sig96, G2 + n * 192, ST + n))) return r;
   if ((r = ensure_scratch(ctx, np))) return r;
   size_t m_off = 0;
   if (K == 1) {
@@ -98,10 +102,7 @@ int verify_pipeline(nbls_ctx* ctx, size_t n, const VerifyIn& in, int final_exp, 
     }
     if ((r = dev_hash_to_g2(ctx, n, uni, G2, s))) return r;                                       // normP2Hash: PointG2.hashToCurve
     HIPCHK(hipStreamWaitEvent(s, ctx->ev_join2, 0));
-    if (in.d_sig96) {
-      HIPCHK(hipMemcpyAsync(G1 + n * 96, ctx->neg_g1, 96, hipMemcpyDeviceToDevice, s));            // PointG1.BASE.negate()
-      HIPCHK(hipStreamWaitEvent(s, ctx->ev_join, 0));
-    }
+    if (in.d_sig96 && (r = sig_join(ctx, G1 + n * 96, s))) return r;
     if ((r = miller_values(ctx, np, G1, G2, &m_off, s))) return r;
   } else {
     // scratch is sized once for the whole call (the sub-batches work on slices of it): grow it before anything is in flight
@@ -139,37 +140,19 @@ int verify_pipeline(nbls_ctx* ctx, size_t n, const VerifyIn& in, int final_exp, 
       } else if (c & 1) { if ((r = hash()) || (r = keys())) return r; }
       else { if ((r = keys()) || (r = hash())) return r; }
       size_t cc = nc;
-      if (last && in.d_sig96) {
-        HIPCHK(hipMemcpyAsync(G1 + n * 96, ctx->neg_g1, 96, hipMemcpyDeviceToDevice, sc));         // PointG1.BASE.negate()
-        HIPCHK(hipStreamWaitEvent(sc, ctx->ev_join, 0));
-        cc++;
-      }
+      if (last && in.d_sig96) { if ((r = sig_join(ctx, G1 + n * 96, sc))) return r; cc++; }
       // line tables per accumulator: four where a quarter of the sub-batch's pairs still are thousands of items, fewer where only the length of one wavefront's instruction stream counts
       // (round 6: four from 32,768 pairs instead of 8192 -- verifyBatch(32,768) 13.2 -> 12.0 ms, (65,536) unchanged; profiles/round6_ab_acc_width.txt)
       static const size_t v_acc4_min = (size_t)env_long("NBLS_VERIFY_ACC4_MIN", 32768), v_acc2_min = (size_t)env_long("NBLS_VERIFY_ACC2_MIN", 2048);
       const size_t GR = cc >= v_acc4_min ? 4 : cc >= v_acc2_min ? 2 : 1;
-      const ProgId acc = GR == 4 ? P_ACC4_RAW : GR == 2 ? P_ACC2_RAW : P_ACC_RAW;
-      const size_t gg = (cc + GR - 1) / GR;
       uint8_t* Lc = ctx->L + (o + 4 * c) * LINE_BYTES;      // its own line tables (+ up to three unit tables behind them)
       // experiment: the FIRST (large) sub-batch's Miller loops run alone once the small ones are done; as two halves on two streams, like nbls_pairing_batch_dev, so that the partly filled
       // last round of LINES / ACC of one half runs under the other -- measured NO better (profiles/round5_ab_verify2.txt: 12 % worse with the default split, even with a 75 / 25 split),
       // so the switch NBLS_VERIFY_HALVES=1 is off by default
       static const bool halves_on = env_long("NBLS_VERIFY_HALVES", 0) != 0;
       const size_t h = (c == 0 && halves_on && cc >= 2 * ctx->halves_min) ? (((cc / 2) + GR * 64 - 1) / (GR * 64)) * (GR * 64) : cc;   // whole groups, whole wavefronts
-      if (h < cc) {
-        if ((r = ensure_half_stream(ctx))) return r;
-        HIPCHK(hipEventRecord(ctx->ev_half_fork, sc)); HIPCHK(hipStreamWaitEvent(ctx->half_stream, ctx->ev_half_fork, 0));
-      }
-      for (size_t lo = 0; lo < cc; lo += h) {
-        const size_t part = lo ? cc - lo : h, pg = (part + GR - 1) / GR;
-        hipStream_t sh = lo ? ctx->half_stream : sc;
-        if ((r = run(ctx, P_LINES_PQ, part, {B(0, G1 + (o + lo) * 96, 96), B(1, G2 + (o + lo) * 192, 192), B(3, Lc + lo * LINE_BYTES, LINE_BYTES)}, sh))) return r;
-        for (size_t k = part; k < GR * pg; k++) HIPCHK(hipMemcpyAsync(Lc + (lo + k) * LINE_BYTES, ctx->unit_lines, LINE_BYTES, hipMemcpyDeviceToDevice, sh));
-        if ((r = run(ctx, acc, pg, {B(3, Lc + lo * LINE_BYTES, GR * LINE_BYTES), B(5, ctx->F + (m_off + lo / GR) * F12, F12)}, sh))) return r;
-        if (lo) break;
-      }
-      if (h < cc) { HIPCHK(hipEventRecord(ctx->ev_half_join, ctx->half_stream)); HIPCHK(hipStreamWaitEvent(sc, ctx->ev_half_join, 0)); }
-      m_off += gg;
+      if ((r = lines_acc(ctx, cc, G1 + o * 96, G2 + o * 192, Lc, GR, ctx->F + m_off * F12, h, sc))) return r;
+      m_off += (cc + GR - 1) / GR;
       if (c) { HIPCHK(hipEventRecord(evc, sc)); HIPCHK(hipStreamWaitEvent(s, evc, 0)); }      // (enqueued on s behind sub-batch 0's own work)
       o += nc;
     }
@@ -193,11 +176,16 @@ int verify_pipeline(nbls_ctx* ctx, size_t n, const VerifyIn& in, int final_exp, 
 bool verify_pipe_enabled() { static const bool on = env_long("NBLS_VERIFY_PIPE", 1) != 0; return on; }
 bool fp12_wire_is_one(const uint8_t* out) { bool one = out[47] == 1; for (int i = 0; i < 576 && one; i++) if (i != 47 && out[i]) one = false; return one; }   // exp.equals(Fp12.ONE)
 // the whole of verifyBatch behind the pipeline: decide from the statuses as the reference does (index.ts:792-821)
-int verify_decide(const std::vector<int8_t>& st, size_t n, const uint8_t* out, int* ok, int8_t* pk_status) {
+int verify_statuses(const std::vector<int8_t>& st, size_t n, int* zero_flag, int8_t* pk_status) {
   if (pk_status) memcpy(pk_status, st.data(), n);
   for (int8_t v : st) if (v > 1) return NBLS_EDECODE;                  // the reference throws before its try block
-  for (int8_t v : st) if (v == 1) { *ok = 0; return NBLS_OK; }          // zero point -> pairing() throws -> false
-  *ok = fp12_wire_is_one(out) ? 1 : 0;
+  *zero_flag = 0;
+  for (int8_t v : st) if (v == 1) *zero_flag = 1;                       // zero point -> pairing() throws -> false
+  return NBLS_OK;
+}
+int verify_decide(const std::vector<int8_t>& st, size_t n, const uint8_t* out, int* ok, int8_t* pk_status) {
+  int zero; const int r = verify_statuses(st, n, &zero, pk_status); if (r) return r;
+  *ok = !zero && fp12_wire_is_one(out) ? 1 : 0;
   return NBLS_OK;
 }
 // verifyBatch(signature, messages, publicKeys) on wire inputs (index.ts:792-821): every message hashes to its own point
@@ -207,39 +195,38 @@ int verify_decide(const std::vector<int8_t>& st, size_t n, const uint8_t* out, i
 //   inside the try block, index.ts:716, 818-820).
 EXPORT int nbls_verify_batch_dev_inputs(nbls_ctx* ctx, size_t n, const void* d_sig96, const void* d_uniform, const void* d_pk48, int* ok, int8_t* pk_status, void* stream);
 EXPORT int nbls_verify_batch(nbls_ctx* ctx, size_t n, const uint8_t* sig96, const uint8_t* msgs, const uint32_t* offsets, const uint8_t* pk48, const uint8_t* dst, size_t dst_len, int* ok) {
-  std::lock_guard<std::recursive_mutex> whole_call_(ctx ? ctx->mu : g_null_mu);   // scratch and I/O staging buffers belong to this call until it returns
+  WHOLE_CALL(ctx);
   if (!ctx || !ok || !n || !sig96 || !offsets || !pk48 || !dst) return NBLS_EINVAL;
-  void *d_sig, *d_uni, *d_pk;
-  {
-    // Round 6: messages, offsets, tag, keys and the signature travel as ONE copy from a page-locked block (five copies from pageable memory and two synchronisations before
-    // the chain even started: ~0.2 ms of a 2.8 ms verify); nothing waits on the host until the pipeline's single synchronisation at the end (the block belongs to the context,
-    // whose mutex this call holds).
-    for (size_t i = 0; i < n; i++) if (offsets[i + 1] < offsets[i]) return NBLS_EINVAL;
-    const size_t total = offsets[n] - offsets[0];
-    uint8_t dst_hash[32];
-    if (dst_len > 255) { Sha256 c; c.update((const uint8_t*)"H2C-OVERSIZE-DST-", 17); c.update(dst, dst_len); c.final(dst_hash); dst = dst_hash; dst_len = 32; }
-    const size_t o_off = (total + 15) & ~(size_t)15, o_dst = o_off + (((n + 1) * 4 + 15) & ~(size_t)15), o_pk = o_dst + 256, o_sig = o_pk + ((n * 48 + 15) & ~(size_t)15), in_bytes = o_sig + 96;
-    LOCKED(ctx);
-    uint8_t *c, *du; int r;
-    if ((r = need(ctx, SB_STAGED, in_bytes, &c)) || (r = need(ctx, SB_UNIFORM, n * 256, &du)) || (r = ensure_pinned(ctx, in_bytes))) return r;
-    uint8_t* pin = ctx->pinned;
-    if (total) memcpy(pin, msgs + offsets[0], total);
-    { uint32_t* rel = (uint32_t*)(pin + o_off); for (size_t i = 0; i <= n; i++) rel[i] = offsets[i] - offsets[0]; }
-    memcpy(pin + o_dst, dst, dst_len); memcpy(pin + o_pk, pk48, n * 48); memcpy(pin + o_sig, sig96, 96);
-    HIPCHK(hipMemcpyAsync(c, pin, in_bytes, hipMemcpyHostToDevice, s));
-    LAUNCHCHK(nbls_xmd_launch((unsigned)n, c, c + o_off, c + o_dst, (unsigned)dst_len, du, 256, nullptr, s));
-    d_sig = c + o_sig; d_uni = du; d_pk = c + o_pk;
-  }
-  return nbls_verify_batch_dev_inputs(ctx, n, d_sig, d_uni, d_pk, ok, nullptr, nullptr);
+  // Round 6: messages, offsets, tag, keys and the signature travel as ONE copy from a page-locked block (five copies from pageable memory and two synchronisations before
+  // the chain even started: ~0.2 ms of a 2.8 ms verify); nothing waits on the host until the pipeline's single synchronisation at the end (the block belongs to the context,
+  // whose mutex this call holds).
+  for (size_t i = 0; i < n; i++) if (offsets[i + 1] < offsets[i]) return NBLS_EINVAL;
+  const size_t total = offsets[n] - offsets[0];
+  uint8_t dst_hash[32];
+  if (dst_len > 255) { Sha256 c; c.update((const uint8_t*)"H2C-OVERSIZE-DST-", 17); c.update(dst, dst_len); c.final(dst_hash); dst = dst_hash; dst_len = 32; }
+  const size_t o_off = (total + 15) & ~(size_t)15, o_dst = o_off + (((n + 1) * 4 + 15) & ~(size_t)15), o_pk = o_dst + 256, o_sig = o_pk + ((n * 48 + 15) & ~(size_t)15), in_bytes = o_sig + 96;
+  LOCKED(ctx);
+  uint8_t *c, *du; int r;
+  if ((r = need(ctx, SB_STAGED, in_bytes, &c)) || (r = need(ctx, SB_UNIFORM, n * 256, &du)) || (r = ensure_pinned(ctx, in_bytes))) return r;
+  uint8_t* pin = ctx->pinned;
+  if (total) memcpy(pin, msgs + offsets[0], total);
+  { uint32_t* rel = (uint32_t*)(pin + o_off); for (size_t i = 0; i <= n; i++) rel[i] = offsets[i] - offsets[0]; }
+  memcpy(pin + o_dst, dst, dst_len); memcpy(pin + o_pk, pk48, n * 48); memcpy(pin + o_sig, sig96, 96);
+  HIPCHK(hipMemcpyAsync(c, pin, in_bytes, hipMemcpyHostToDevice, s));
+  ForkGuard in_flight;   // an error return below must not leave the copy out of ctx->pinned or the hashing kernel running: the next call repacks the block and may regrow the slots
+  LAUNCHCHK(nbls_xmd_launch((unsigned)n, c, c + o_off, c + o_dst, (unsigned)dst_len, du, 256, nullptr, s));
+  r = nbls_verify_batch_dev_inputs(ctx, n, c + o_sig, du, c + o_pk, ok, nullptr, nullptr);
+  if (r == NBLS_OK || r == NBLS_EDECODE) in_flight.armed = false;   // both verdicts are read behind the call's synchronisation
+  return r;
 }
 // verifyBatch with EVERYTHING resident in HBM (bench.py's verifyBatch value): signature, the message bytes with their n + 1 offsets (uint32, relative to d_msgs),
 // compressed keys.  SHA-256 expand_message_xmd (index.ts:207-231) runs first, on the same stream, then the call continues as nbls_verify_batch_dev_inputs.
 EXPORT int nbls_verify_batch_msgs_dev(nbls_ctx* ctx, size_t n, const void* d_sig96, const void* d_msgs, const void* d_offsets, const void* d_pk48, const uint8_t* dst, size_t dst_len,
     int* ok, void* stream) {
-  std::lock_guard<std::recursive_mutex> whole_call_(ctx ? ctx->mu : g_null_mu);
+  WHOLE_CALL(ctx);
   if (!ctx || !ok || !n || !d_sig96 || !d_offsets || !d_pk48 || !dst) return NBLS_EINVAL;
   uint8_t* dd;
-  { const int r = dst_on_device(ctx, dst, &dst_len, stream ? (hipStream_t)stream : ctx->stream, &dd); if (r) return r; }
+  { const int r = dst_on_device(ctx, dst, &dst_len, call_stream(ctx, stream), &dd); if (r) return r; }
   if (verify_pipe_enabled()) {
     VerifyIn in{d_sig96, nullptr, d_msgs, d_offsets, dd, (unsigned)dst_len, d_pk48};
     std::vector<int8_t> st; uint8_t out[576]; int bad = 0;
@@ -249,9 +236,7 @@ EXPORT int nbls_verify_batch_msgs_dev(nbls_ctx* ctx, size_t n, const void* d_sig
   }
   uint8_t* du;
   {
-    std::lock_guard<std::recursive_mutex> g_(ctx->mu);
-    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-    StreamOrder order_(ctx, s);
+    DEV_ENTER(ctx, stream);
     int r;
     if ((r = need(ctx, SB_UNIFORM, n * 256 + 16, &du))) return r;
     uint32_t* d_bad = (uint32_t*)(du + n * 256);
@@ -268,24 +253,12 @@ EXPORT int nbls_verify_batch_msgs_dev(nbls_ctx* ctx, size_t n, const void* d_sig
 int verify_stage(nbls_ctx* ctx, size_t n, const void* d_sig96, const void* d_uniform, const void* d_pk48, std::vector<int8_t>& st, void* stream) {
   const size_t np = n + (d_sig96 ? 1 : 0);
   st.assign(np, 0);
-  std::lock_guard<std::recursive_mutex> g_(ctx->mu); HIPCHK(hipSetDevice(ctx->device));
-  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-  StreamOrder order_(ctx, s);
+  DEV_ENTER(ctx, stream);
   uint8_t *G1, *G2, *ST, *O; int r;
   if ((r = need(ctx, SB_VB_PAIRS, (n + 1) * (96 + 192) + (n + 1) + 576 + 64, &G1))) return r;
   G2 = G1 + (n + 1) * 96; O = G2 + (n + 1) * 192; ST = O + 576;
-  if (d_sig96) {
-    // normP2: PointG2.fromSignature for the ONE signature, on the side stream with its own scratch (overlaps everything below).
-    // The side stream is created on first use: HIP spreads streams over a few hardware queues in creation order, and contexts
-    // that only run pairing batches (noble-bls12-381_amd/pipeline.py keeps several in flight) should each get a queue of their own.
-    if ((r = ensure_side(ctx))) return r;
-    uint8_t *X = ctx->side_scratch, *Rr = X + 2 * RAW, *Cd = Rr + 2 * RAW, *pw = Cd + 2 * RAW;
-    HIPCHK(hipEventRecord(ctx->ev_fork, s)); HIPCHK(hipStreamWaitEvent(ctx->side, ctx->ev_fork, 0));
-    if ((r = run(ctx, P_G2_DEC_A, 1, {B(0, d_sig96, 96), B(3, X, 2 * RAW), B(4, Rr, 2 * RAW)}, ctx->side))) return r;
-    if ((r = run_pow(ctx, 1, 1, Rr, Cd, ctx->side, pw))) return r;
-    if ((r = run(ctx, P_G2_DEC_B, 1, {B(0, d_sig96, 96), B(3, X, 2 * RAW), B(4, Rr, 2 * RAW), B(5, Cd, 2 * RAW), B(6, G2 + n * 192, 192), B(7, ST + n, 1)}, ctx->side))) return r;
-    HIPCHK(hipEventRecord(ctx->ev_join, ctx->side));
-  }
+  if ((r = ensure_fork_event(ctx))) return r;
+  if (d_sig96) { HIPCHK(hipEventRecord(ctx->ev_fork, s)); if ((r = sig_fork(ctx, d_sig96, G2 + n * 192, ST + n))) return r; }
   // normP1 (PointG1.fromHex of the keys) on a second stream beside normP2Hash (PointG2.hashToCurve of the messages): both chains
   // contain a per-lane exponentiation kernel that fills the chip only two wavefronts deep and issues at half rate, so running
   // them side by side costs little more than the longer one (the key chain has scratch slots of its own: DEC_KEYS).
@@ -301,16 +274,13 @@ int verify_stage(nbls_ctx* ctx, size_t n, const void* d_sig96, const void* d_uni
     if ((r = dev_decompress(ctx, false, n, d_pk48, G1, ST, s))) return r;                       // normP1: PointG1.fromHex
     if ((r = dev_hash_to_g2(ctx, n, d_uniform, G2, s))) return r;                               // normP2Hash: PointG2.hashToCurve
   }
-  if (d_sig96) {
-    HIPCHK(hipMemcpyAsync(G1 + n * 96, ctx->neg_g1, 96, hipMemcpyDeviceToDevice, s));         // PointG1.BASE.negate()
-    HIPCHK(hipStreamWaitEvent(s, ctx->ev_join, 0));
-  }
+  if (d_sig96 && (r = sig_join(ctx, G1 + n * 96, s))) return r;
   HIPCHK(hipMemcpyAsync(st.data(), ST, np, hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
   return NBLS_OK;
 }
 EXPORT int nbls_verify_batch_dev_inputs(nbls_ctx* ctx, size_t n, const void* d_sig96, const void* d_uniform, const void* d_pk48, int* ok, int8_t* pk_status, void* stream) {
-  std::lock_guard<std::recursive_mutex> whole_call_(ctx ? ctx->mu : g_null_mu);   // scratch and I/O staging buffers belong to this call until it returns
+  WHOLE_CALL(ctx);
   if (!ctx || !ok || !n || !d_sig96 || !d_uniform || !d_pk48) return NBLS_EINVAL;
   std::vector<int8_t> st;
   uint8_t out[576];
@@ -319,16 +289,14 @@ EXPORT int nbls_verify_batch_dev_inputs(nbls_ctx* ctx, size_t n, const void* d_s
     int r = verify_pipeline(ctx, n, in, 1, nullptr, out, st, nullptr, stream); if (r) return r;
     return verify_decide(st, n, out, ok, pk_status);
   }
-  int r = verify_stage(ctx, n, d_sig96, d_uniform, d_pk48, st, stream); if (r) return r;
-  if (pk_status) memcpy(pk_status, st.data(), n);
-  for (size_t i = 0; i <= n; i++) if (st[i] > 1) return NBLS_EDECODE;       // the reference throws before its try block
-  for (size_t i = 0; i <= n; i++) if (st[i] == 1) { *ok = 0; return NBLS_OK; }   // zero point -> pairing() throws -> false
+  int zero, r;
+  if ((r = verify_stage(ctx, n, d_sig96, d_uniform, d_pk48, st, stream)) || (r = verify_statuses(st, n, &zero, pk_status))) return r;
+  if (zero) { *ok = 0; return NBLS_OK; }
   {
     uint8_t* base = ctx->sb[SB_VB_PAIRS];
     r = nbls_miller_product_dev(ctx, n + 1, base, base + (n + 1) * 96, 1, base + (n + 1) * 288, stream);
     if (r) return r;
-    std::lock_guard<std::recursive_mutex> g_(ctx->mu);
-    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    hipStream_t s = call_stream(ctx, stream);   // (the whole-call lock is held)
     HIPCHK(hipMemcpyAsync(out, base + (n + 1) * 288, 576, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
   }
@@ -340,7 +308,7 @@ EXPORT int nbls_verify_batch_dev_inputs(nbls_ctx* ctx, size_t n, const void* d_s
 // as 576 wire bytes in device memory.  The ranks exchange their partials (one all-gather) and finish with
 // nbls_fp12_product_final_dev.  *zero_flag = 1 when a zero point was met (verifyBatch then answers false; d_out is not written).
 EXPORT int nbls_verify_batch_partial_dev(nbls_ctx* ctx, size_t n, const void* d_sig96, const void* d_uniform, const void* d_pk48, void* d_out_fp12, int* zero_flag, int8_t* pk_status, void* stream) {
-  std::lock_guard<std::recursive_mutex> whole_call_(ctx ? ctx->mu : g_null_mu);   // scratch and I/O staging buffers belong to this call until it returns
+  WHOLE_CALL(ctx);
   if (!ctx || !zero_flag || !n || !d_uniform || !d_pk48 || !d_out_fp12) return NBLS_EINVAL;
   std::vector<int8_t> st;
   if (verify_pipe_enabled()) {
@@ -348,17 +316,11 @@ EXPORT int nbls_verify_batch_partial_dev(nbls_ctx* ctx, size_t n, const void* d_
     // code and the flag first
     VerifyIn in{d_sig96, d_uniform, nullptr, nullptr, nullptr, 0, d_pk48};
     int r = verify_pipeline(ctx, n, in, 0, d_out_fp12, nullptr, st, nullptr, stream); if (r) return r;
-    if (pk_status) memcpy(pk_status, st.data(), n);
-    for (int8_t v : st) if (v > 1) return NBLS_EDECODE;
-    *zero_flag = 0;
-    for (int8_t v : st) if (v == 1) *zero_flag = 1;
-    return NBLS_OK;
+    return verify_statuses(st, n, zero_flag, pk_status);
   }
-  int r = verify_stage(ctx, n, d_sig96, d_uniform, d_pk48, st, stream); if (r) return r;
-  if (pk_status) memcpy(pk_status, st.data(), n);
-  for (int8_t v : st) if (v > 1) return NBLS_EDECODE;
-  *zero_flag = 0;
-  for (int8_t v : st) if (v == 1) { *zero_flag = 1; return NBLS_OK; }
+  int r;
+  if ((r = verify_stage(ctx, n, d_sig96, d_uniform, d_pk48, st, stream)) || (r = verify_statuses(st, n, zero_flag, pk_status))) return r;
+  if (*zero_flag) return NBLS_OK;
   const size_t np = st.size();
   uint8_t* base = ctx->sb[SB_VB_PAIRS];
   // the pairs sit at stride n + 1 inside the scratch block whether or not the signature pair is present
@@ -367,7 +329,7 @@ EXPORT int nbls_verify_batch_partial_dev(nbls_ctx* ctx, size_t n, const void* d_
 
 int verify_batch_partial_core(nbls_ctx* ctx, size_t n, const uint8_t* sig96 /* or NULL */, const uint8_t* msgs, const uint32_t* offsets, const uint8_t* pk48,
                                      const uint8_t* dst, size_t dst_len, void* d_dst, void** d_partial, int* zero_flag, int8_t* pk_status) {
-  std::lock_guard<std::recursive_mutex> whole_call_(ctx ? ctx->mu : g_null_mu);
+  WHOLE_CALL(ctx);
   if (!ctx || !zero_flag || !n || !offsets || !pk48 || !dst) return NBLS_EINVAL;
   LOCKED(ctx);
   uint8_t *b, *c, *part; int r;

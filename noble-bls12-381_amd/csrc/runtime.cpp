@@ -133,28 +133,28 @@ int run_inv(nbls_ctx* ctx, size_t n, hipStream_t s) {
 // burst are coarse (twenty 4096-pairing calls on twenty streams 2.82 against 2.85 M pairings/s, 512 calls twelve deep 3.05 against 3.08 M; tools/ab_chain20.sh).  The pool
 // (nbls_pool_init, nbls_multi.cpp) therefore sets it to 0 for its contexts.
 bool chains_enabled() { static const bool on = env_long("NBLS_CHAIN", 1) != 0; return on; }
-int run_chain(nbls_ctx* ctx, size_t n, std::initializer_list<ChainLink> links, hipStream_t s) {
+int run_chain(nbls_ctx* ctx, size_t n, const ChainLink* links, size_t count, hipStream_t s) {
   int r;
-  bool fuse = chains_enabled() && !checked_mode() && links.size() <= (size_t)AOT_MAX_SEGS;
+  bool fuse = chains_enabled() && !checked_mode() && count <= (size_t)AOT_MAX_SEGS;
   int k = -1; u32 W = 0, G = 0, lds = 0;
-  for (auto& l : links) {
-    if ((r = upload(ctx, l.id))) return r;
-    const DevProgram& d = ctx->prog[l.id];
+  for (const ChainLink* l = links; l < links + count; l++) {
+    if ((r = upload(ctx, l->id))) return r;
+    const DevProgram& d = ctx->prog[l->id];
     if (d.aot < 0 || (k >= 0 && (d.aot != k || d.p->W != W || d.p->G != G))) fuse = false;
     k = d.aot; W = d.p->W; G = d.p->G; lds = std::max(lds, d.aot_lds);
   }
-  if (!fuse) { for (auto& l : links) if ((r = run(ctx, l.id, n, l.bufs, s))) return r; return NBLS_OK; }
+  if (!fuse) { for (const ChainLink* l = links; l < links + count; l++) if ((r = run(ctx, l->id, n, l->bufs, s))) return r; return NBLS_OK; }
   AotArgs a; memset(&a, 0, sizeof a);
-  for (auto& l : links) {
+  for (const ChainLink* l = links; l < links + count; l++) {
     IOBuf bufs[MAX_BUFS]; memset(bufs, 0, sizeof bufs);
-    for (auto& b : l.bufs) { bufs[b.first].ptr = (uint8_t*)b.second.first + ctx->ioff * b.second.second; bufs[b.first].stride = b.second.second; }
-    aot_seg(a.seg[a.nseg++], ctx->prog[l.id], bufs);
+    for (auto& b : l->bufs) { bufs[b.first].ptr = (uint8_t*)b.second.first + ctx->ioff * b.second.second; bufs[b.first].stride = b.second.second; }
+    aot_seg(a.seg[a.nseg++], ctx->prog[l->id], bufs);
   }
   a.W = W; a.G = G; a.n_items = (u32)n; a.qp_table = ctx->qp_table;
   hipEvent_t e0 = nullptr, e1 = nullptr;
   if (ctx->timing) { e0 = timing_event(ctx); e1 = timing_event(ctx); hipEventRecord(e0, s); }
   const int e = nbls_aot_launch(k, &a, lds, s);
-  if (ctx->timing) { hipEventRecord(e1, s); ctx->tev.push_back({(int)links.begin()->id, {e0, e1}}); }   // the whole chain is booked on its first program
+  if (ctx->timing) { hipEventRecord(e1, s); ctx->tev.push_back({(int)links->id, {e0, e1}}); }   // the whole chain is booked on its first program
   if (e) { ctx->last_hip = e; return NBLS_EHIP; }
   return NBLS_OK;
 }
@@ -210,7 +210,7 @@ int ensure_lines(nbls_ctx* ctx, size_t n) {
 }
 // The side streams (verifyBatch's one-element chains and key decoding; the validity programs of a small validated pairing call) are created on first use: HIP spreads
 // streams over a few hardware queues in creation order, and contexts that only run pairing batches (pipeline.py keeps several in flight) should each get a queue of their own.
-static int ensure_fork_event(nbls_ctx* ctx) {
+int ensure_fork_event(nbls_ctx* ctx) {
   if (!ctx->ev_fork && hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming) != hipSuccess) { ctx->last_hip = (int)hipGetLastError(); return NBLS_EHIP; }
   return NBLS_OK;
 }
@@ -225,6 +225,11 @@ int ensure_side2(nbls_ctx* ctx) {    // ctx->side2, ev_fork, ev_join2
   int r = ensure_fork_event(ctx); if (r) return r;
   if (!ctx->side2 && hipStreamCreateWithFlags(&ctx->side2, hipStreamNonBlocking) != hipSuccess) { ctx->side2 = nullptr; ctx->last_hip = (int)hipGetLastError(); return NBLS_EHIP; }
   if (!ctx->ev_join2 && hipEventCreateWithFlags(&ctx->ev_join2, hipEventDisableTiming) != hipSuccess) { ctx->last_hip = (int)hipGetLastError(); return NBLS_EHIP; }
+  return NBLS_OK;
+}
+int ensure_half_stream(nbls_ctx* ctx) {   // ctx->half_stream, ev_half_fork, ev_half_join: the second half of a large pairing call or Miller stage (lines_acc)
+  if (!ctx->half_stream && (hipStreamCreateWithFlags(&ctx->half_stream, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&ctx->ev_half_fork, hipEventDisableTiming) != hipSuccess ||
+                            hipEventCreateWithFlags(&ctx->ev_half_join, hipEventDisableTiming) != hipSuccess)) { ctx->last_hip = (int)hipGetLastError(); return NBLS_EHIP; }
   return NBLS_OK;
 }
 int ensure_pinned(nbls_ctx* ctx, size_t bytes) {

@@ -251,8 +251,8 @@ def test_chained_and_separate_final_exponentiation(oracle, golden):
 @pytest.mark.gpu
 def test_default_dispatch_thresholds(oracle, golden):
     """Batch sizes either side of the library's default dispatch thresholds, untouched tuning: one stream below 16,384 pairs, two halves on two streams from
-    16,384 (NBLS_HALVES_MIN; the one-full-round window 10,753 .. 12,288 lies below it and runs on one stream as well) -- every pairing byte-equal to the oracle,
-    last item included."""
+    16,384 (NBLS_HALVES_MIN; 10,753 and 12,289 bracket the window 10,753 .. 12,288 that had a one-stream case of its own while the threshold was 8192: it lies below
+    today's threshold and is dispatched like its neighbours) -- every pairing byte-equal to the oracle, last item included."""
     import os
     pkg = importlib.import_module('noble-bls12-381_amd')
     eng = pkg.Engine(0)
