@@ -252,6 +252,39 @@ int nbls_verify_aggregates_indexed_shared(nbls_ctx* ctx, const nbls_keyset* ks, 
                                           const uint32_t* msg_index /* n */, const uint32_t* key_index, const uint32_t* key_offsets, const uint8_t* dst, size_t dst_len,
                                           const uint8_t* seed32, int* all_ok, int8_t* status);
 
+/* The scalar field Fr = Z / r (math.ts:295-386) on the device, n elements per call: add / subtract / negate / multiply / square / invert / div / pow (math.ts:317-349).
+ * Elements are 32 bytes big-endian, ANY 256-bit value (reduced mod r first, as `new Fr(v)` does, math.ts:301-303); outputs are canonical (< r).  b32: the second operand, or
+ * POW's exponent (read as a 256-bit integer, not reduced); NULL for the unary operations.  status (may be NULL): 5 where INV / DIV meets 0 mod r (the reference throws), the
+ * output element is then all-zero.  Control flow on the device does not depend on the operands (INV is the fixed chain x^(r - 2)), but the Fr calls are NOT an interface for
+ * secrets: nothing is wiped from staging or scratch memory.  Shamir-splitting of keys stays on the caller's side. */
+#define NBLS_FROP_ADD 0
+#define NBLS_FROP_SUB 1
+#define NBLS_FROP_NEG 2
+#define NBLS_FROP_MUL 3
+#define NBLS_FROP_SQR 4
+#define NBLS_FROP_INV 5
+#define NBLS_FROP_DIV 6
+#define NBLS_FROP_POW 7
+int nbls_fr_op_batch(nbls_ctx* ctx, int op, size_t n, const uint8_t* a32, const uint8_t* b32, uint8_t* out32, int8_t* status);
+
+/* Threshold signatures: Lagrange coefficients at zero and the recombination of t-of-n shares (no reference counterpart; the reference's README names the use).  The shares come
+ * in n_groups contiguous groups: group g = entries group_offsets[g] .. group_offsets[g + 1] of ids32 and of the share array (n_groups + 1 offsets, strictly increasing: no
+ * empty group; the first need not be 0, the entries in front of it are not read), ids32 = one 32-byte big-endian identifier x_k per share (any value, reduced mod r).
+ *   nbls_lagrange_at_zero   out32[k] = lambda_k = prod_{j != k} x_j / (x_j - x_k) over the share's group, canonical.  status[g] (may be NULL): 0, or NBLS_ST_BAD_IDS when an
+ *                           identifier of the group is 0 mod r or two of them are equal mod r (that group's coefficients are then all-zero).
+ *   nbls_g2_combine_shares  out96[g] = compress(sum_k [lambda_k] share_k) for shares that are 96-byte compressed G2 points decoded by PointG2.fromSignature's rules
+ *                           (index.ts:500-530): signature shares.  nbls_g1_combine_shares: 48-byte compressed G1 points, PointG1.fromHex's rules (index.ts:298-327): the shares
+ *                           of a group public key.  status[g] (may be NULL), in this order: NBLS_ST_BAD_IDS; else what nbls_g*_decompress_batch reports for the group's first
+ *                           share that does not decode (>= 2: 3 outside the subgroup, 4 no square root); else 1 when the combination is the zero point (output 0xc0 00..); else 0.
+ *                           A zero share (0xc0 00..) is valid and adds nothing.  A group with a status other than 0 / 1 gets all-zero output and never disturbs its neighbours.
+ * One chain on the context's stream: one copy in, the decoder, the coefficients, the ladders (the coefficients are public: the G2 ladder is the psi-split one), one sum per group,
+ * compression, one copy out.  Returns NBLS_OK whatever the groups hold; NBLS_EINVAL before any device work for a missing pointer, n_groups = 0, offsets that do not strictly
+ * increase, more than 2^24 shares in the call and a group of more than 2^16 shares.  Not an interface for secrets (see nbls_fr_op_batch). */
+#define NBLS_ST_BAD_IDS 20
+int nbls_lagrange_at_zero(nbls_ctx* ctx, size_t n_groups, const uint32_t* group_offsets, const uint8_t* ids32, uint8_t* out32, int8_t* status /* n_groups, may be NULL */);
+int nbls_g2_combine_shares(nbls_ctx* ctx, size_t n_groups, const uint32_t* group_offsets, const uint8_t* ids32, const uint8_t* shares96, uint8_t* out96, int8_t* status);
+int nbls_g1_combine_shares(nbls_ctx* ctx, size_t n_groups, const uint32_t* group_offsets, const uint8_t* ids32, const uint8_t* shares48, uint8_t* out48, int8_t* status);
+
 /* One rank's share of a verifyBatch spread over several GPUs (one process per GPU): the Miller product of this rank's n
  * (key, message) pairs, times millerLoop(-G, S) on the ONE rank that passes the signature (d_sig96 = NULL elsewhere), WITHOUT the
  * final exponentiation, as 576 wire bytes in device memory.  Ranks all-gather their partials and finish with
@@ -276,7 +309,8 @@ int nbls_verify_batch_partial_into(nbls_ctx* ctx, size_t n, const uint8_t* sig96
 const char* nbls_config_describe(void);   /* "NBLS_X=value(env|default) ...": every environment switch the library has read so far and the value in force -- print it next to an A/B result */
 /* 5: nbls_verify_multiple, NBLS_ST_NOT_VERIFIED, scratch slots 20 .. 43 (additions only); then nbls_verify_aggregates, nbls_verify_aggregates_indexed, nbls_keyset_create /
    _destroy / _size, scratch slots 44 .. 47 (additions only, same version); then nbls_verify_multiple_shared, nbls_verify_aggregates_shared,
-   nbls_verify_aggregates_indexed_shared, scratch slots 48 .. 50 (additions only, same version).
+   nbls_verify_aggregates_indexed_shared, scratch slots 48 .. 50 (additions only, same version); then nbls_fr_op_batch, nbls_lagrange_at_zero, nbls_g2_combine_shares,
+   nbls_g1_combine_shares, NBLS_FROP_*, NBLS_ST_BAD_IDS, scratch slots 51 .. 56 (additions only, same version).
    4 (round 6): nbls_hw_queues, NBLS_TUNE_WIDE_MAX, NBLS_TUNE_H2C_NORM_MIN, NBLS_TUNE_INV_WIDE_MAX, NBLS_TUNE_LS_MAX / _LS2_MAX (additions only); the library sets GPU_MAX_HW_QUEUES = 22 at load when the variable is unset (see nbls_pool_init below).
    3 (round 5): nbls_program_kernel, nbls_pool_*, nbls_sign_batch_dev, NBLS_TUNE_VERIFY_* / _SAC_MAX / _PT_LS2_MAX (additions only); nbls_verify_batch_partial_dev writes d_out_fp12 even when it reports a zero point or a decode error
    (contents then meaningless); 2: *_partial take *d_partial as OUT only, *_partial_into added, nbls_tower_op_batch, nbls_verify_batch_msgs_dev.  The bindings check it at load. */

@@ -1,5 +1,5 @@
 // nbls_internal.h -- what the translation units of the runtime share (runtime.cpp / tuning.cpp / pipelines_pairing.cpp / pipelines_codec.cpp / pipelines_verify.cpp /
-// pipelines_multi_verify.cpp; pool and multi-device handles: nbls_multi.cpp): the context, the map of its scratch slots (enum Slot: the one place that says which chain owns
+// pipelines_multi_verify.cpp / pipelines_threshold.cpp; pool and multi-device handles: nbls_multi.cpp): the context, the map of its scratch slots (enum Slot: the one place that says which chain owns
 // which slot, checked at compile time), the launch helpers and the device-side pipelines the exported entry points are built from.  Internal functions have hidden visibility
 // (csrc/Makefile: -fvisibility=hidden).
 #pragma once
@@ -40,6 +40,11 @@ extern "C" int nbls_agg_status_launch(unsigned n, const void* first_bad, const v
 extern "C" int nbls_grp_zero_launch(unsigned m, const void* zero, const void* fixed96, void* rpk96, void* flag_u32, void* stream);   // grp_kernels.hip
 extern "C" int nbls_grp_interleave_launch(unsigned n, const void* msg_index, const void* pk96, const void* neg_g1, const void* h192, const void* sig192, void* g1x, void* g2x,
                                           void* stream);
+extern "C" int nbls_fr_op_launch(unsigned n, int op, const void* a32, const void* b32, void* out32, void* status, void* stream);   // fr_kernels.hip
+extern "C" int nbls_fr_lagrange_launch(unsigned n, unsigned ngroups, const void* off, const void* ids32, void* X, void* L, void* group_of, void* bad_group, void* out32, void* stream);
+extern "C" int nbls_fr_combine_status_launch(unsigned ngroups, unsigned out_bytes, const void* bad_group, const void* first_bad, const void* st, const void* zero, void* out,
+                                             void* status, void* stream);
+extern "C" int nbls_fr_group_status_launch(unsigned ngroups, const void* bad_group, void* status, void* stream);
 extern "C" int nbls_msm_keys_launch(unsigned n, unsigned nwin, const void* scalars, void* keys, void* vals, void* stream);
 extern "C" int nbls_msm_decompose_launch(unsigned n, unsigned dims, const void* scalars, void* out, void* stream);
 extern "C" int nbls_msm_sac_launch(unsigned n, const void* scalars, void* out, void* stream);
@@ -93,9 +98,12 @@ enum Slot {
   SB_RLC_MSM = 30,                // MSM_RLC: 30 .. 39, 41 and 43 (MsmSlots::Buf); 40 and 42 are unused
   SB_AGG_DECODED = 44, SB_AGG_POINTS = 45, SB_AGG_LABELS = 46, SB_AGG_SUMS = 47,   // SEG_AGG: the per-set key sums of nbls_verify_aggregates (+ the decoded keys in front of them)
   SB_GRP_POINTS = 48, SB_GRP_LABELS = 49, SB_GRP_SUMS = 50,                        // SEG_GRP: the per-message key sums of the shared-message forms
+  // combine_pipeline (pipelines_threshold.cpp): the decoded shares and their statuses | identifiers and coefficients in Montgomery form, groups, flags, the canonical
+  // coefficients | the affine sums, what is read back | SEG_THR: one sum per group
+  SB_THR_SHARES = 51, SB_THR_SCALARS = 52, SB_THR_OUT = 53, SB_THR_POINTS = 54, SB_THR_LABELS = 55, SB_THR_SUMS = 56,
   NSB
 };
-static_assert(NSB == 51, "sb[] indices do not shift");
+static_assert(NSB == 57, "sb[] indices do not shift");
 constexpr uint64_t slot_bit(int i) { return (uint64_t)1 << i; }
 template <typename... S> constexpr uint64_t slots(S... s) { return (slot_bit(s) | ...); }
 // one instance of dev_decompress: three arrays of field elements and the exponentiation table
@@ -112,7 +120,7 @@ constexpr MsmSlots MSM_MAIN{SB_WORK_A}, MSM_RLC{SB_RLC_MSM};
 // one instance of segment_sums (pipelines_multi_verify.cpp): gathered points | ids, ranks, pair lists, counters, statuses | sums, norms, inverses.  zero_with_sums: the zero
 // flags of the sums lie behind the inverses (else behind the statuses): the two instances keep the layouts they were written with
 struct SegSlots { Slot points, labels, sums; bool zero_with_sums; constexpr uint64_t mask() const { return slots(points, labels, sums); } };
-constexpr SegSlots SEG_AGG{SB_AGG_POINTS, SB_AGG_LABELS, SB_AGG_SUMS, false}, SEG_GRP{SB_GRP_POINTS, SB_GRP_LABELS, SB_GRP_SUMS, true};
+constexpr SegSlots SEG_AGG{SB_AGG_POINTS, SB_AGG_LABELS, SB_AGG_SUMS, false}, SEG_GRP{SB_GRP_POINTS, SB_GRP_LABELS, SB_GRP_SUMS, true}, SEG_THR{SB_THR_POINTS, SB_THR_LABELS, SB_THR_SUMS, true};
 // what every chain touches
 constexpr uint64_t M_HASH_G2 = slots(SB_WORK_A, SB_WORK_B, SB_WORK_C, SB_WORK_D, SB_NORM, SB_NORM_INV, SB_POINT_ST, SB_POW_TABLE, SB_CLEAR_S, SB_SWU_STATE, SB_SWU_POINTS);   // dev_hash_to_g2
 constexpr uint64_t M_LADDER = slots(SB_WORK_A, SB_WORK_B, SB_WORK_C, SB_NORM, SB_NORM_INV);                 // dev_point_mul
@@ -120,12 +128,14 @@ constexpr uint64_t M_VB_MAIN = slots(SB_VB_PAIRS, SB_UNIFORM) | M_HASH_G2;      
 constexpr uint64_t M_RLC_MAIN = slots(SB_STAGED, SB_UNIFORM, SB_RLC_WEIGHTS, SB_RLC_PAIRS, SB_RLC_PER_SET) | M_HASH_G2;   // verify_multiple_pipeline on the call's stream
 constexpr uint64_t M_RLC_SIDE2 = DEC_KEYS.mask() | slots(SB_AGG_DECODED, SB_RLC_KEYS_PROJ, SB_RLC_KEYS_NORM, SB_RLC_KEYS_INV) | SEG_AGG.mask() | SEG_GRP.mask();   // its key chain
 constexpr uint64_t M_RLC_SIDE = DEC_SIGS.mask() | MSM_RLC.mask();                                           // its signature chain
+constexpr uint64_t M_THR_OWN = slots(SB_STAGED, SB_THR_SHARES, SB_THR_SCALARS, SB_THR_OUT) | SEG_THR.mask();   // combine_pipeline: what outlives the stages it calls
 // what runs side by side
 static_assert(!(M_VB_MAIN & DEC_KEYS.mask()), "verifyBatch decodes its keys (side2, or the sub-batch's own stream) beside the hash chain");
 static_assert(!(M_RLC_MAIN & M_RLC_SIDE2) && !(M_RLC_MAIN & M_RLC_SIDE) && !(M_RLC_SIDE & M_RLC_SIDE2), "verify_multiple_pipeline: the chains on s, side and side2 run side by side");
 static_assert(!(SEG_AGG.mask() & SEG_GRP.mask()), "the per-message sums follow the per-set sums on side2 with nothing regrown under a kernel in flight");
 static_assert(!(slot_bit(SB_MSGS) & (M_HASH_G2 | M_LADDER)), "sign_points: the keys are recoded on side2 beside the hash chain, and the digits outlive it until the ladder has read them");
 static_assert(!(slot_bit(SB_VB_PAIRS) & MSM_MAIN.mask()), "verifyBatch keeps its pairs across the calls of its two-stage route: dev_msm on the main slots must not regrow them");
+static_assert(!(M_THR_OWN & (DEC_MAIN.mask() | M_LADDER)), "combine_pipeline: the decoder and the ladder regrow their own slots between the stages that read the shares and the coefficients");
 // ---- END scratch slots -------------------------------------------------------------------------------------------------------------------------------------
 #define EXPORT extern "C" __attribute__((visibility("default")))
 extern std::recursive_mutex g_null_mu;   // locked in place of a context's mutex when the caller passed no context (the call then fails with NBLS_EINVAL)
@@ -360,13 +370,18 @@ int decode_host(nbls_ctx* ctx, int kind /* 0 g1.fromHex, 1 g2.fromHex, 2 g2.from
 int encode_host(nbls_ctx* ctx, bool g2, size_t n, const uint8_t* aff, const int8_t* zero, int compressed, uint8_t* out);
 int clear_host(nbls_ctx* ctx, bool g2, size_t n, const uint8_t* aff, uint8_t* out, int8_t* status);
 int dev_point_mul(nbls_ctx* ctx, bool g2, size_t n, const void* d_pts, size_t pt_stride, const void* d_scalars, void* d_out, void* d_status, hipStream_t s, bool allow_fixed = true,
-    bool in_subgroup = false, uint8_t* recoded = nullptr);
+    bool in_subgroup = false, uint8_t* recoded = nullptr, uint8_t** proj = nullptr);
+bool g2_ladder_takes_projective(const nbls_ctx* ctx, size_t n);   // an in-subgroup G2 dev_point_mul of n items reads raw projective points (stride 6 * RAW), not affine ones
 int ensure_g1_fixed(nbls_ctx* ctx, hipStream_t s);
 int sign_points(nbls_ctx* ctx, size_t n, const void* d_uniform, void* h, const void* d_keys32, void* d_out192, void* d_status, hipStream_t s);
 bool scalar_is_zero_mod_r(const uint8_t* k32);
 int mul_host(nbls_ctx* ctx, bool g2, size_t n, const uint8_t* pts, const uint8_t* scalars32, uint8_t* out, int8_t* status);
 int dev_msm(nbls_ctx* ctx, bool g2, size_t n, const void* d_pts, const void* d_scalars, unsigned nbits, void* d_out, void* d_status, hipStream_t s, const MsmSlots& sl = MSM_MAIN);
 int segmented_sum(nbls_ctx* ctx, bool g2, size_t count, const uint32_t* keys, const uint32_t* rank, uint32_t* list, uint32_t* counters, uint8_t* P, size_t maxrun, hipStream_t s);
+// pipelines_multi_verify.cpp: one sum per contiguous segment as affine wire bytes; what the caller's closing status kernel reads comes back in SegSums
+struct SegSums { const uint32_t* first; const int8_t* st; uint8_t* zero; };   // per segment: first position with a status >= 2; per position: status; per segment: the sum is the zero point
+int segment_sums(nbls_ctx* ctx, bool g2, const SegSlots& sl, size_t count, size_t nseg, const uint32_t* d_off, const uint32_t* d_index, const uint8_t* src, const int8_t* st_src,
+                 size_t maxseg, uint8_t* out, SegSums* o, hipStream_t s);
 unsigned scalars_bit_length(size_t n, const uint8_t* k32);
 int msm_host(nbls_ctx* ctx, bool g2, size_t n, const uint8_t* pts, const uint8_t* scalars32, uint8_t* out, int8_t* status);
 int dst_on_device(nbls_ctx* ctx, const uint8_t* dst, size_t* dst_len, hipStream_t s, uint8_t** dd);

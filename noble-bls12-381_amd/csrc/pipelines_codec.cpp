@@ -299,8 +299,14 @@ int ensure_g1_fixed(nbls_ctx* ctx, hipStream_t s) {
   ctx->g1_fixed = tab;
   return NBLS_OK;
 }
+// The psi-split G2 ladders (NBLS_G2_GLS=0 keeps the plain one) and which of the two forms n items take: up to sac_max the sign-aligned form, which reads RAW PROJECTIVE points
+// (six raw elements each, pt_stride = 6 * RAW); above, the windowed form on affine wire points.  dev_point_mul and every caller that prepares its points (sign_points,
+// combine_pipeline) ask here, so the ladder and its input cannot disagree
+static bool g2_gls_on() { static const bool on = env_long("NBLS_G2_GLS", 1) != 0; return on; }
+bool g2_ladder_takes_projective(const nbls_ctx* ctx, size_t n) { return g2_gls_on() && n <= ctx->sac_max; }
 int dev_point_mul(nbls_ctx* ctx, bool g2, size_t n, const void* d_pts, size_t pt_stride, const void* d_scalars, void* d_out, void* d_status, hipStream_t s, bool allow_fixed, bool in_subgroup,
-                  uint8_t* recoded) {   // recoded: the sign-aligned digits of the scalars, made by the caller (sign_points: beside the hash chain), or NULL
+                  uint8_t* recoded, uint8_t** proj) {   // recoded: the sign-aligned digits of the scalars, made by the caller (sign_points: beside the hash chain), or NULL
+  // proj: stop at the ladder's raw projective points (SB_WORK_A) -- the caller sums them and normalises only the sums (combine_pipeline)
   const size_t p = g2 ? 6 * RAW : 3 * RAW;
   uint8_t *Pj, *N, *NI; int r;
   // getPublicKey (the base point is G1.BASE for every item): no doublings, the multiples of the generator come from a table (round 5: 86 additions instead of 256 doublings + 128
@@ -311,16 +317,16 @@ int dev_point_mul(nbls_ctx* ctx, bool g2, size_t n, const void* d_pts, size_t pt
   if ((r = need(ctx, SB_WORK_A, n * p, &Pj)) || (r = need(ctx, SB_NORM, n * RAW, &N)) || (r = need(ctx, SB_NORM_INV, n * RAW, &NI))) return r;
   // sign (the base points are hash outputs: in G2 by construction): the scalar split along psi, four 65-bit digits on one accumulator (codec.h pt_mul_gls_g2: 66 doublings + 132 additions
   // instead of 256 + 128; NBLS_G2_GLS=0 keeps the plain ladder).  The digits are made on the device by the MSM's decomposition kernel (branch-free long division by |z|).
-  static const bool gls_on = env_long("NBLS_G2_GLS", 1) != 0;
-  if (g2 && in_subgroup && gls_on) {
+  if (g2 && in_subgroup && g2_gls_on()) {
+    const bool sac = g2_ladder_takes_projective(ctx, n);
     // up to sac_max keys d_pts are RAW PROJECTIVE points (six raw elements each, pt_stride = 6 * RAW: sign_points() below) -- the hash points as cofactor clearing leaves them in
     // SB_WORK_B, so the digits go to SB_WORK_C; above, affine wire points as everywhere else
     uint8_t* dig = recoded;
-    if (!dig && (r = need(ctx, n <= ctx->sac_max ? SB_WORK_C : SB_WORK_B, n * 128, &dig))) return r;
+    if (!dig && (r = need(ctx, sac ? SB_WORK_C : SB_WORK_B, n * 128, &dig))) return r;
     // while every wavefront of the launch is resident at once the length of ONE wavefront's instruction stream is the time: the sign-aligned recoding with one addition per bit
     // (codec.h pt_mul_sac_g2: 65 doublings + 73 additions; its table of eight points takes 101 slots = three workgroups per CU = 768 wavefronts of 8 keys); above 6144 keys the
     // windowed form, whose table of four leaves room for six workgroups per CU (NBLS_G2_SAC_MAX / NBLS_TUNE_SAC_MAX; 0 = never)
-    if (n <= ctx->sac_max) {
+    if (sac) {
       if (!recoded) LAUNCHCHK(nbls_msm_sac_launch((unsigned)n, d_scalars, dig, s));
       if ((r = run(ctx, pt_ls2_variant(ctx, P_G2_MUL_SAC, n), n, {B(1, d_pts, pt_stride), B(2, dig, 128), B(3, Pj, p), B(4, N, RAW)}, s))) return r;
     } else {
@@ -338,6 +344,7 @@ int dev_point_mul(nbls_ctx* ctx, bool g2, size_t n, const void* d_pts, size_t pt
   const bool w3 = (n + (g2 ? 7 : 15)) / (g2 ? 8 : 16) <= w3_waves;
   if ((r = run(ctx, g2 ? (w3 ? P_G2_MUL_W3 : P_G2_MUL) : (w3 ? P_G1_MUL_W3 : P_G1_MUL), n, {B(g2 ? 1 : 0, d_pts, pt_stride), B(2, d_scalars, 32), B(3, Pj, p), B(4, N, RAW)}, s))) return r;
   }
+  if (proj) { *proj = Pj; return NBLS_OK; }
   return to_affine(ctx, g2, n, Pj, N, NI, d_out, d_status, s, false);
 }
 // sign's two halves: hash-to-G2, then the key ladder on the hash points.  Up to sac_max keys the points stay projective in between (no inversion, no affine program: the
@@ -345,8 +352,7 @@ int dev_point_mul(nbls_ctx* ctx, bool g2, size_t n, const void* d_pts, size_t pt
 // device scratch for the affine points of the second form
 int sign_points(nbls_ctx* ctx, size_t n, const void* d_uniform, void* h, const void* d_keys32, void* d_out192, void* d_status, hipStream_t s) {
   int r;
-  static const bool gls_on = env_long("NBLS_G2_GLS", 1) != 0;
-  if (gls_on && n <= ctx->sac_max) {
+  if (g2_ladder_takes_projective(ctx, n)) {
     // the recoding of the keys (0.045 ms for one key: a branch-free long division) does not need the hash points: it runs beside the hash chain on a side stream (round 6)
     uint8_t *pj, *dig;
     if ((r = need(ctx, SB_MSGS, n * 128, &dig)) || (r = ensure_side2(ctx))) return r;

@@ -32,15 +32,15 @@ static int os_seed(uint8_t* seed) {
   return NBLS_OK;
 }
 
-// One sum per segment, as affine wire bytes: `count` positions in `nseg` contiguous segments (d_off: nseg + 1 offsets), position k holding the point src[index ? index[k] : k]
-// (raw projective) with status st_src[the same].  agg_keys_kernel gives every position its segment, its rank and its status, and every segment its first position whose status
-// is not 0; agg_points_kernel gathers the points with the identity in place of those whose status is not 0 (the sum stays defined); the segments are contiguous, so segment id and
-// rank stand in for the MSM's sorted (window, digit) keys, and ceil(log2(maxseg)) rounds of segmented_sum leave every sum at its segment's first position -- a launch count
-// independent of the sizes; then heads, norm / inversion / affine over the nseg sums -> out96.  What the caller's closing status kernel reads comes back in `o`.
-struct SegSums { const uint32_t* first; const int8_t* st; uint8_t* zero; };   // per segment: first position with a status; per position: status; per segment: the sum is the zero point
-static int segment_sums(nbls_ctx* ctx, const SegSlots& sl, size_t count, size_t nseg, const uint32_t* d_off, const uint32_t* d_index, const uint8_t* src, const int8_t* st_src, size_t maxseg,
-                        uint8_t* out96, SegSums* o, hipStream_t s) {
-  const size_t p = 3 * RAW;
+// One sum per segment, as affine wire bytes (G1: 96 B, G2: 192 B): `count` positions in `nseg` contiguous segments (d_off: nseg + 1 offsets), position k holding the point
+// src[index ? index[k] : k] (raw projective) with status st_src[the same].  agg_keys_kernel gives every position its segment, its rank and its status, and every segment its first
+// position whose status is >= 2; agg_points_kernel gathers the points with the identity in place of those whose status is not 0 (the sum stays defined); the segments are
+// contiguous, so segment id and rank stand in for the MSM's sorted (window, digit) keys, and ceil(log2(maxseg)) rounds of segmented_sum leave every sum at its segment's first
+// position -- a launch count independent of the sizes; then heads, norm / inversion / affine over the nseg sums -> out.  What the caller's closing status kernel reads comes back
+// in `o` (SegSums, nbls_internal.h).  Callers: the key sums of the multi-verify calls below (G1) and the recombination of threshold shares (pipelines_threshold.cpp, G1 and G2).
+int segment_sums(nbls_ctx* ctx, bool g2, const SegSlots& sl, size_t count, size_t nseg, const uint32_t* d_off, const uint32_t* d_index, const uint8_t* src, const int8_t* st_src,
+                 size_t maxseg, uint8_t* out, SegSums* o, hipStream_t s) {
+  const size_t p = (g2 ? 6 : 3) * RAW;
   uint8_t *GP, *U, *A; int r;
   if ((r = need(ctx, sl.points, (count + 1) * p, &GP)) || (r = need(ctx, sl.labels, count * 13 + nseg * 4 + 32 * 4 + (sl.zero_with_sums ? 0 : nseg), &U)) ||
       (r = need(ctx, sl.sums, nseg * (p + 2 * RAW) + (sl.zero_with_sums ? nseg : 0), &A)))
@@ -49,11 +49,11 @@ static int segment_sums(nbls_ctx* ctx, const SegSlots& sl, size_t count, size_t 
   int8_t* GST = (int8_t*)(counters + 32);
   uint8_t *N = A + nseg * p, *NI = N + nseg * RAW, *Z = sl.zero_with_sums ? NI + nseg * RAW : (uint8_t*)GST + count;
   LAUNCHCHK(nbls_agg_keys_launch((unsigned)count, (unsigned)nseg, d_off, d_index, st_src, id, rank, GST, first, s));
-  LAUNCHCHK(nbls_agg_points_launch(count, (unsigned)p, d_index, GST, ctx->ident_g1, src, GP, s));
-  if ((r = segmented_sum(ctx, false, count, id, rank, list, counters, GP, maxseg, s))) return r;
+  LAUNCHCHK(nbls_agg_points_launch(count, (unsigned)p, d_index, GST, g2 ? ctx->ident_g2 : ctx->ident_g1, src, GP, s));
+  if ((r = segmented_sum(ctx, g2, count, id, rank, list, counters, GP, maxseg, s))) return r;
   LAUNCHCHK(nbls_msm_heads_launch(count, (unsigned)p, id, GP, A, s));   // A[j] = the sum of segment j, left at its first position
   *o = {first, GST, Z};
-  return to_affine(ctx, false, nseg, A, N, NI, out96, Z, s);
+  return to_affine(ctx, g2, nseg, A, N, NI, out, Z, s);
 }
 
 // The aggregate key of every set (aggregatePublicKeys, index.ts:771-778) on `s` -> PK (affine wire bytes, n x 96) and one status byte per set (STK): the decoder's status of the
@@ -74,7 +74,7 @@ static int aggregate_keys(nbls_ctx* ctx, size_t n, const AggKeys& agg, const uin
     src = KP; st_src = KST;
   }
   SegSums o;
-  if ((r = segment_sums(ctx, SEG_AGG, K, n, d_koff, agg.ks ? (const uint32_t*)d_keys : nullptr, src, st_src, agg.maxset, PK, &o, s))) return r;
+  if ((r = segment_sums(ctx, false, SEG_AGG, K, n, d_koff, agg.ks ? (const uint32_t*)d_keys : nullptr, src, st_src, agg.maxset, PK, &o, s))) return r;
   LAUNCHCHK(nbls_agg_status_launch((unsigned)n, o.first, o.st, o.zero, STK, s));
   return NBLS_OK;
 }
@@ -86,7 +86,7 @@ static int aggregate_keys(nbls_ctx* ctx, size_t n, const AggKeys& agg, const uin
 static int group_keys(nbls_ctx* ctx, size_t n, size_t m, size_t maxgroup, const uint32_t* d_order, const uint32_t* d_goff, const int8_t* STK, const uint8_t* Pj, uint8_t* RPK,
                       uint32_t* d_gzero, hipStream_t s) {
   SegSums o;
-  const int r = segment_sums(ctx, SEG_GRP, n, m, d_goff, d_order, Pj, STK, maxgroup, RPK, &o, s); if (r) return r;
+  const int r = segment_sums(ctx, false, SEG_GRP, n, m, d_goff, d_order, Pj, STK, maxgroup, RPK, &o, s); if (r) return r;
   LAUNCHCHK(nbls_grp_zero_launch((unsigned)m, o.zero, ctx->neg_g1, RPK, d_gzero, s));
   return NBLS_OK;
 }

@@ -12,6 +12,7 @@
 #include "pow_exec.h"
 #include "pow_wide.h"
 #include "rlc_weights.h"
+#include "fr_exec.h"
 #include "wide_exec.h"
 #include "g1_wide.h"
 #include "fp_inv_wide.h"
@@ -448,6 +449,47 @@ __attribute__((visibility("default"))) int nbls_sim_layout_info(int prog, unsign
 __attribute__((visibility("default"))) void nbls_sim_rlc_weight(const uint8_t* seed32, uint64_t i, uint8_t* out32) { rlc_weight(seed32, i, out32); }
 __attribute__((visibility("default"))) void nbls_sim_scalar_split(unsigned n, unsigned dims, const uint8_t* scalars, uint8_t* out) {
   for (unsigned i = 0; i < n; i++) { if (dims) scalar_decompose(scalars + 32ull * i, dims, out + 32ull * dims * i); else scalar_sac_recode(scalars + 32ull * i, out + 128ull * i); }
+}
+// the scalar field as fr_kernels.hip runs it (fr_exec.h).  nbls_sim_fr_consts: r | -r^-1 mod 2^32 | R^2 mod r | R mod r | r - 2 as 8 + 1 + 8 + 8 + 8 words
+__attribute__((visibility("default"))) void nbls_sim_fr_consts(u32* out33) {
+  const Fr r2 = fr_r2(), one = fr_one();
+  for (int i = 0; i < FR_NL; i++) { out33[i] = fr_mod(i); out33[9 + i] = r2.l[i]; out33[17 + i] = one.l[i]; out33[25 + i] = fr_rm2(i); }
+  out33[8] = fr_n0();
+}
+// fr_op_kernel for every element: 32-byte big-endian operands (b = NULL for unary operations) -> out32 and status (5 where INV / DIV meets 0 mod r)
+__attribute__((visibility("default"))) void nbls_sim_fr_op(unsigned n, int op, const uint8_t* a32, const uint8_t* b32, uint8_t* out32, int8_t* status) {
+  for (unsigned i = 0; i < n; i++) status[i] = (int8_t)fr_op_bytes(op, a32 + 32ull * i, b32 ? b32 + 32ull * i : a32 + 32ull * i, out32 + 32ull * i);
+}
+// the conversions of fr_exec.h: wire bytes -> Montgomery limbs (to_mont != 0: fr_to_mont_kernel) or back (as fr_lagrange_out_kernel and fr_op_bytes do)
+__attribute__((visibility("default"))) void nbls_sim_fr_convert(unsigned n, int to_mont, const uint8_t* in, uint8_t* out) {
+  for (unsigned i = 0; i < n; i++) { if (to_mont) ((Fr*)out)[i] = fr_from_bytes(in + 32ull * i); else fr_to_bytes(((const Fr*)in)[i], out + 32ull * i); }
+}
+// nbls_fr_lagrange_launch: the conversion, fr_lagrange_kernel workgroup by workgroup (64 lanes, the wavefront's identifier range staged in tiles of 64, lanes past n running
+// along with the last share) and fr_lagrange_out_kernel.  off: ngroups + 1 relative offsets; status: one byte per group (20 = unusable identifiers)
+__attribute__((visibility("default"))) void nbls_sim_fr_lagrange(unsigned n, unsigned ngroups, const u32* off, const uint8_t* ids32, uint8_t* out32, int8_t* status) {
+  const u32 W = 64;
+  std::vector<Fr> x(n), lambda(n);
+  std::vector<u32> group_of(n), bad_group(ngroups, 0);
+  for (unsigned i = 0; i < n; i++) x[i] = fr_from_bytes(ids32 + 32ull * i);
+  for (u32 k0 = 0; k0 < n; k0 += W) {
+    u32 kk[W], g[W]; std::vector<FrLagrange> s;
+    for (u32 l = 0; l < W; l++) { kk[l] = k0 + l < n ? k0 + l : n - 1; g[l] = fr_group_of(off, ngroups, kk[l]); s.push_back(fr_lagrange_begin(x[kk[l]])); }
+    const u32 rb = off[g[0]], re = off[g[W - 1] + 1];
+    for (u32 t = rb; t < re; t += W) {
+      Fr tile[W];
+      for (u32 l = 0; l < W; l++) tile[l] = x[t + l < re ? t + l : re - 1];
+      const u32 cnt = re - t < W ? re - t : W;
+      for (u32 l = 0; l < W; l++) fr_lagrange_tile(s[l], tile, t, cnt, off[g[l]], off[g[l] + 1], kk[l]);
+    }
+    for (u32 l = 0; l < W && k0 + l < n; l++) {
+      u32 bad;
+      lambda[k0 + l] = fr_lagrange_finish(s[l], &bad);
+      group_of[k0 + l] = g[l];
+      if (bad) bad_group[g[l]] |= 1;
+    }
+  }
+  for (unsigned k = 0; k < n; k++) fr_store_be(fr_select((u32)0 - (u32)(bad_group[group_of[k]] != 0), fr_zero(), fr_from_mont(lambda[k])), out32 + 32ull * k);
+  for (unsigned j = 0; j < ngroups; j++) status[j] = bad_group[j] ? 20 : 0;
 }
 __attribute__((visibility("default"))) int nbls_sim_program_count() { return (int)P_COUNT; }
 __attribute__((visibility("default"))) void nbls_sim_stats() { for (int i = 0; i < P_COUNT; i++) print_stats(get_program((ProgId)i)); }

@@ -71,6 +71,10 @@ def load_library():
     lib.nbls_verify_multiple_shared.argtypes = [vp, sz, vp, sz, vp, vp, vp, vp, vp, sz, vp, C.POINTER(i32), vp]
     lib.nbls_verify_aggregates_shared.argtypes = [vp, sz, vp, sz, vp, vp, vp, vp, vp, vp, sz, vp, C.POINTER(i32), vp]
     lib.nbls_verify_aggregates_indexed_shared.argtypes = [vp, vp, sz, vp, sz, vp, vp, vp, vp, vp, vp, sz, vp, C.POINTER(i32), vp]
+    lib.nbls_fr_op_batch.argtypes = [vp, i32, sz, vp, vp, vp, vp]
+    lib.nbls_lagrange_at_zero.argtypes = [vp, sz, vp, vp, vp, vp]
+    lib.nbls_g2_combine_shares.argtypes = [vp, sz, vp, vp, vp, vp, vp]
+    lib.nbls_g1_combine_shares.argtypes = [vp, sz, vp, vp, vp, vp, vp]
     lib.nbls_keyset_create.argtypes = [vp, sz, vp, vp, C.POINTER(vp)]
     lib.nbls_keyset_destroy.argtypes = [vp]
     lib.nbls_keyset_destroy.restype = None
@@ -368,6 +372,64 @@ class Engine:
         out = C.create_string_buffer(max(n * sz // 2, 1))
         self._chk((self.lib.nbls_g2_compress_batch if g2 else self.lib.nbls_g1_compress_batch)(self.h, n, aff, out))
         return out.raw[:n * sz // 2]
+
+    # ---- the scalar field Fr and threshold recombination (include/nbls.h: nbls_fr_op_batch, nbls_lagrange_at_zero, nbls_g*_combine_shares); not an interface for secrets
+    FR_OPS = {'add': 0, 'sub': 1, 'neg': 2, 'mul': 3, 'sqr': 4, 'inv': 5, 'div': 6, 'pow': 7}
+
+    @staticmethod
+    def _fr32(v):
+        """an Fr element / identifier / exponent as the C ABI takes it: a Python int (0 <= v < 2^256) or 32 bytes big-endian"""
+        if isinstance(v, int):
+            return v.to_bytes(32, 'big')
+        v = bytes(v)
+        if len(v) != 32:
+            raise NblsError('expected 32 bytes, got %d' % len(v))
+        return v
+
+    def fr_op(self, op, a, b=None):
+        """Fr elementwise (math.ts:295-386): op = 'add' | 'sub' | 'neg' | 'mul' | 'sqr' | 'inv' | 'div' | 'pow' (or its NBLS_FROP_* number); a, b: lists of ints or 32-byte values,
+        b = the second operands or pow's exponents -> (list of 32-byte canonical results, status list: 5 where inv / div meets 0 mod r)"""
+        op = self.FR_OPS[op] if isinstance(op, str) else int(op)
+        n = len(a)
+        if b is not None and len(b) != n:
+            raise NblsError('fr_op: %d first and %d second operands' % (n, len(b)))
+        out = C.create_string_buffer(max(32 * n, 1)); st = C.create_string_buffer(max(n, 1))
+        self._chk(self.lib.nbls_fr_op_batch(self.h, op, n, b''.join(map(self._fr32, a)), None if b is None else b''.join(map(self._fr32, b)), out, st))
+        raw = out.raw   # one copy of the buffer, not one per element
+        return [raw[32 * i:32 * i + 32] for i in range(n)], list(st.raw[:n])
+
+    def _groups(self, sizes, ids):
+        offs = [0]
+        for t in sizes:
+            offs.append(offs[-1] + t)
+        return (C.c_uint32 * len(offs))(*offs), b''.join(self._fr32(x) for g in ids for x in g)
+
+    def lagrange_at_zero(self, groups):
+        """groups: a list of identifier lists -> (per group the list of 32-byte coefficients lambda_k = prod_{j != k} x_j / (x_j - x_k), status list: NBLS_ST_BAD_IDS = 20 for a
+        group with an identifier that is 0 mod r or two that are equal mod r -- its coefficients are all-zero)"""
+        sizes = [len(g) for g in groups]
+        offs, ids = self._groups(sizes, groups)
+        n = offs[len(sizes)]
+        out = C.create_string_buffer(max(32 * n, 1)); st = C.create_string_buffer(max(len(sizes), 1))
+        self._chk(self.lib.nbls_lagrange_at_zero(self.h, len(sizes), offs, ids, out, st))
+        raw = out.raw
+        return [[raw[32 * k:32 * k + 32] for k in range(offs[g], offs[g + 1])] for g in range(len(sizes))], list(st.raw[:len(sizes)])
+
+    def combine_shares(self, groups, g2=True):
+        """groups: a list of (ids, shares): t identifiers (ints or 32-byte values) and t compressed shares (96-byte signature shares, or with g2=False 48-byte public-key shares)
+        -> (list of compressed combinations sum_k [lambda_k]share_k, status list: 0, 1 = the zero point (0xc0 00..), 3 / 4 = a share that does not decode, 20 = bad identifiers;
+        a group with a status >= 2 yields all-zero bytes)"""
+        e = 96 if g2 else 48
+        for ids, shares in groups:
+            if len(ids) != len(shares) or any(len(x) != e for x in shares):
+                raise NblsError('combine_shares: every group needs one %d-byte share per identifier' % e)
+        offs, ids = self._groups([len(g[0]) for g in groups], [g[0] for g in groups])
+        m = len(groups)
+        out = C.create_string_buffer(max(e * m, 1)); st = C.create_string_buffer(max(m, 1))
+        f = self.lib.nbls_g2_combine_shares if g2 else self.lib.nbls_g1_combine_shares
+        self._chk(f(self.h, m, offs, ids, b''.join(bytes(x) for g in groups for x in g[1]), out, st))
+        raw = out.raw
+        return [raw[e * g:e * g + e] for g in range(m)], list(st.raw[:m])
 
     def get_public_keys(self, keys):
         """getPublicKey for a batch of private keys -> list of 48-byte compressed keys; raises like the reference on a zero key"""

@@ -71,6 +71,11 @@ export declare class PointG1 {
   /** additive: sum of points / multi-scalar multiplication on the GPU */
   static sum(points: PointG1[]): PointG1;
   static msm(points: PointG1[], scalars: (bigint | number)[]): PointG1;
+  /** threshold recombination on the GPU: sum_k [lambda_k]share_k with the Lagrange coefficients at zero of the identifiers (any value below 2^256, reduced mod CURVE.r).
+   *  Compressed shares (bytes or hex) give bytes, points give a point.  Throws Error on identifiers that are zero or repeated mod r and on a share that does not decode. */
+  static combineShares(shares: PointG1[], ids: ShareId[]): Promise<PointG1>;
+  static combineShares(shares: Hex[], ids: ShareId[]): Promise<Uint8Array>;
+  static combineSharesBatch(groups: ShareGroup<PointG1>[]): Promise<(PointG1 | Uint8Array)[]>;
   isZero(): boolean; equals(rhs: PointG1): boolean; negate(): PointG1; add(rhs: PointG1): PointG1; subtract(rhs: PointG1): PointG1; double(): PointG1;
   multiply(scalar: bigint | number): PointG1; multiplyUnsafe(scalar: bigint | number): PointG1; multiplyPrecomputed(scalar: bigint | number): PointG1;
   assertValidity(): this; toAffine(): [Fp, Fp]; toRawBytes(isCompressed?: boolean): Uint8Array; toHex(isCompressed?: boolean): string;
@@ -87,6 +92,11 @@ export declare class PointG2 {
   static encodeToCurve(msg: Hex, options?: { DST?: string }): Promise<PointG2>;
   static sum(points: PointG2[]): PointG2;
   static msm(points: PointG2[], scalars: (bigint | number)[]): PointG2;
+  /** threshold recombination on the GPU: sum_k [lambda_k]share_k with the Lagrange coefficients at zero of the identifiers (any value below 2^256, reduced mod CURVE.r).
+   *  Compressed shares (bytes or hex) give bytes, points give a point.  Throws Error on identifiers that are zero or repeated mod r and on a share that does not decode. */
+  static combineShares(shares: PointG2[], ids: ShareId[]): Promise<PointG2>;
+  static combineShares(shares: Hex[], ids: ShareId[]): Promise<Uint8Array>;
+  static combineSharesBatch(groups: ShareGroup<PointG2>[]): Promise<(PointG2 | Uint8Array)[]>;
   isZero(): boolean; equals(rhs: PointG2): boolean; negate(): PointG2; add(rhs: PointG2): PointG2; subtract(rhs: PointG2): PointG2; double(): PointG2;
   multiply(scalar: bigint | number): PointG2; multiplyUnsafe(scalar: bigint | number): PointG2; multiplyPrecomputed(scalar: bigint | number): PointG2;
   assertValidity(): this; toAffine(): [Fp2, Fp2]; toSignature(): Uint8Array; toRawBytes(isCompressed?: boolean): Uint8Array; toHex(isCompressed?: boolean): string;
@@ -107,6 +117,16 @@ export declare function verifyBatch(signature: Hex | PointG2, messages: (Hex | P
 export declare function verifyMultipleSignatures(sets: { publicKey: Hex | PointG1; message: Hex | PointG2; signature: Hex | PointG2 }[]): Promise<boolean>;
 /** verify(signature, message, aggregatePublicKeys(publicKeys)) for every set, checked together by a random linear combination on the GPU; throws where that throws for the first such set */
 export declare function verifyMultipleAggregateSignatures(sets: { publicKeys: (Hex | PointG1)[]; message: Hex | PointG2; signature: Hex | PointG2 }[]): Promise<boolean>;
+export type ShareId = bigint | number | string | Uint8Array;
+/** one group of combineSharesBatch: its shares are all points or all compressed bytes / hex */
+export type ShareGroup<P> = { shares: P[] | Hex[]; ids: ShareId[] } | [P[] | Hex[], ShareId[]];
+/** what the addon's Fr and threshold calls take (nbls_fr_op_batch, nbls_lagrange_at_zero, nbls_g2_combine_shares / nbls_g1_combine_shares; a type only, the facade does not export
+ * the addon): 32-byte big-endian elements, groupOffsets = groups + 1 entries; every call has a synchronous twin without the suffix */
+export interface NativeThresholdCalls {
+  frOpAsync(op: number, a32: Uint8Array, b32: Uint8Array | null): Promise<{ out: Uint8Array; status: Uint8Array }>;
+  lagrangeAtZeroAsync(groupOffsets: Uint32Array, ids32: Uint8Array): Promise<{ out: Uint8Array; status: Uint8Array }>;
+  combineSharesAsync(g2: number, groupOffsets: Uint32Array, ids32: Uint8Array, shares: Uint8Array): Promise<{ out: Uint8Array; status: Uint8Array }>;
+}
 /** The two calls of the N-API addon (nbls_napi.node) that verifyMultipleSignatures / verifyMultipleAggregateSignatures take when at least two wire-format sets have equal messages:
  * msgs / offsets hold the distinct messages, set i signs message msgIndex[i] (nbls_verify_multiple_shared / nbls_verify_aggregates_shared; a type only, the facade does not export the addon) */
 export interface NativeSharedCalls {

@@ -72,6 +72,48 @@ function validateScalar(n) {
 }
 const scalarBytes = (n) => hexToBytes(validateScalar(n).toString(16).padStart(64, '0'));
 
+// ---- threshold recombination (nbls_g2_combine_shares / nbls_g1_combine_shares; not in the reference, whose README names the use): sum_k [lambda_k]share_k with the Lagrange
+// coefficients at zero of the identifiers, one call for all groups, on a worker thread.  Identifiers: bigint | number | hex | 32 bytes, any value below 2^256 (reduced mod r).
+function shareIdBytes(x) {
+  if (x instanceof Uint8Array) { if (x.length !== 32) throw new Error('Invalid share identifier: expected 32 bytes'); return x; }
+  if (typeof x === 'number' && !Number.isSafeInteger(x)) throw new Error('Invalid share identifier: expected an integer');
+  const v = typeof x === 'string' ? BigInt('0x' + x.replace(/^0x/, '')) : BigInt(x);
+  if (v < 0n || v >> 256n) throw new Error('Invalid share identifier: expected 0 <= id < 2^256');
+  return hexToBytes(v.toString(16).padStart(64, '0'));
+}
+// groups: [{ shares, ids }] (or [shares, ids] pairs).  A group of points yields a point; of bytes or hex (compressed shares), bytes; a group that mixes the
+// two is refused.  Throws Error on identifiers that are zero or
+// repeated mod r and on a share that does not decode, as the decoders do
+async function combineSharesBatch(Point, groups) {
+  const g2 = Point === PointG2, e = g2 ? 96 : 48, STATUS = g2 ? G2_STATUS : G1_STATUS;
+  if (!groups.length) throw new Error('Expected non-empty array');
+  const offs = new Uint32Array(groups.length + 1), ids = [], shares = [], asPoint = [];
+  groups.forEach((grp, g) => {
+    const sh = Array.isArray(grp) ? grp[0] : grp.shares, id = Array.isArray(grp) ? grp[1] : grp.ids;
+    if (!sh || !id || !sh.length || sh.length !== id.length) throw new Error('Expected as many share identifiers as shares, at least one');
+    const points = sh.filter((p) => p instanceof Point).length;
+    if (points && points !== sh.length) throw new Error('Expected the shares of a group to be all points or all compressed bytes');
+    asPoint.push(points > 0);
+    for (const p of sh) {
+      const b = p instanceof Point ? (g2 ? p.toSignature() : p.toRawBytes(true)) : ensureBytes(p);
+      if (b.length !== e) throw new Error('Invalid share: expected ' + e + ' compressed bytes');
+      shares.push(b);
+    }
+    for (const x of id) ids.push(shareIdBytes(x));
+    offs[g + 1] = offs[g] + sh.length;
+  });
+  ensureInit();
+  const { out, status } = await native.combineSharesAsync(g2 ? 1 : 0, offs, concat(...ids), concat(...shares));
+  return groups.map((_, g) => {
+    const st = status[g];
+    if (st === 20) throw new Error('Invalid share identifiers: zero or repeated modulo CURVE.r');
+    if (st > 1) throw new Error(STATUS[st] || 'Invalid share (status ' + st + ')');
+    const bytes = out.slice(g * e, g * e + e);
+    if (!asPoint[g]) return bytes;
+    return st === 1 ? Point.ZERO : (g2 ? PointG2.fromSignature(bytes) : PointG1.fromHex(bytes));
+  });
+}
+
 // Points are held as affine wire bytes (what the engine consumes) or as the zero point.  The reference's constructor form
 // new PointG1(x: Fp, y: Fp, z?: Fp) (index.ts:291) is accepted too: the projective triple is made affine on the host.
 class PointG1 {
@@ -183,6 +225,9 @@ class PointG1 {
     const { out, status } = native.g1Msm(concat(...keep.map((i) => points[i].aff)), concat(...keep.map((i) => hexToBytes(BigInt(scalars[i]).toString(16).padStart(64, '0')))));
     return status[0] === 1 ? PointG1.ZERO : new PointG1(out);
   }
+  // t-of-n threshold shares -> the group's public key: sum_k [lambda_k]share_k (combineSharesBatch above)
+  static async combineShares(shares, ids) { return (await combineSharesBatch(PointG1, [{ shares, ids }]))[0]; }
+  static combineSharesBatch(groups) { return combineSharesBatch(PointG1, groups); }
   equals(rhs) { return this.zero === rhs.zero && (this.zero || bytesToHex(this.aff) === bytesToHex(rhs.aff)); }
   // reference index.ts:359-381
   toHex(isCompressed = false) {
@@ -326,6 +371,9 @@ class PointG2 {
     const { out, status } = native.g2Msm(concat(...keep.map((i) => points[i].aff)), concat(...keep.map((i) => hexToBytes(BigInt(scalars[i]).toString(16).padStart(64, '0')))));
     return status[0] === 1 ? PointG2.ZERO : new PointG2(out);
   }
+  // t-of-n threshold shares -> the group's signature: sum_k [lambda_k]share_k (combineSharesBatch above)
+  static async combineShares(shares, ids) { return (await combineSharesBatch(PointG2, [{ shares, ids }]))[0]; }
+  static combineSharesBatch(groups) { return combineSharesBatch(PointG2, groups); }
   equals(rhs) { return this.zero === rhs.zero && (this.zero || bytesToHex(this.aff) === bytesToHex(rhs.aff)); }
   // reference index.ts:586-598
   toSignature() {

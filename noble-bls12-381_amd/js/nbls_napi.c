@@ -2,7 +2,7 @@
  * nbls_napi.c -- thin N-API addon: exposes the C ABI of libnbls.so (include/nbls.h) to Node.  No arithmetic here.
  * libnbls.so is loaded with dlopen at module init so the addon builds with plain gcc (no HIP needed):
  *     gcc -shared -fPIC -I/usr/include/node -I../../include nbls_napi.c -o nbls_napi.node -ldl
- * Calls are synchronous (they block for the duration of the GPU work) except verifyBatchAsync (and signBatchAsync, verifyMultipleAsync, verifyAggregatesAsync, verifyMultipleSharedAsync, verifyAggregatesSharedAsync), which runs on a libuv worker thread
+ * Calls are synchronous (they block for the duration of the GPU work) except verifyBatchAsync (and signBatchAsync, verifyMultipleAsync, verifyAggregatesAsync, verifyMultipleSharedAsync, verifyAggregatesSharedAsync, frOpAsync, lagrangeAtZeroAsync, combineSharesAsync), which runs on a libuv worker thread
  * (napi_create_async_work) and resolves a Promise: the facade's verifyBatch uses it for wire-format inputs (the calls that can take tens of milliseconds).  Typed arrays are passed by reference (napi_get_typedarray_info), no copies.
  */
 #include <node_api.h>
@@ -21,6 +21,7 @@ SYM(nbls_hash_to_g2_batch) SYM(nbls_g1_sum) SYM(nbls_g2_sum) SYM(nbls_verify_bat
 SYM(nbls_init_multi) SYM(nbls_destroy_multi) SYM(nbls_multi_device_count) SYM(nbls_multi_context) SYM(nbls_multi_pairing_batch) SYM(nbls_multi_miller_product) SYM(nbls_multi_verify_batch)
 SYM(nbls_g2_prepare) SYM(nbls_pairing_prepared) SYM(nbls_verify_multiple) SYM(nbls_verify_aggregates) SYM(nbls_verify_multiple_shared) SYM(nbls_verify_aggregates_shared)
 SYM(nbls_g1_from_hex_batch) SYM(nbls_g2_from_hex_batch) SYM(nbls_g2_from_signature_batch) SYM(nbls_g1_clear_cofactor_batch) SYM(nbls_g2_clear_cofactor_batch)
+SYM(nbls_fr_op_batch) SYM(nbls_lagrange_at_zero) SYM(nbls_g2_combine_shares) SYM(nbls_g1_combine_shares)
 static nbls_ctx* ctx;
 static nbls_multi* multi;   /* several GPUs behind one handle (initMulti): ctx is then its first context; the batch calls shard over all of them */
 #define MULTI() (multi && p_nbls_multi_device_count(multi) > 1)
@@ -419,6 +420,89 @@ static napi_value SignBatchAsync(napi_env env, napi_callback_info info) {
   return promise;
 }
 
+/* The scalar field and threshold recombination (nbls_fr_op_batch, nbls_lagrange_at_zero, nbls_g2_combine_shares / nbls_g1_combine_shares), each as a synchronous native and an
+ * *Async twin on a libuv worker thread with a context of the pool -> {out, status}:
+ *   frOp(op, a32, b32 | null)                          n = a32.length / 32 elements; status[i] = 5 where inv / div meets 0 mod r
+ *   lagrangeAtZero(groupOffsets, ids32)                groupOffsets: Uint32Array of groups + 1 entries; out = one coefficient per identifier, status per group
+ *   combineShares(g2, groupOffsets, ids32, shares)     g2 != 0: 96-byte signature shares, else 48-byte public-key shares; out = one compressed point per group, status per group
+ * The offsets must name identifiers and shares that are in the arrays (checked here); the library checks the rest. */
+typedef struct {
+  napi_async_work work; napi_deferred deferred; napi_ref refs[6]; int nrefs;
+  int kind /* 0 frOp, 1 lagrangeAtZero, 2 combineShares */, op, g2; const uint8_t *a, *b, *shares; const uint32_t* offs; size_t n; uint8_t* out; int8_t* st;
+  nbls_ctx* c; int rc;
+} thr_job;
+static void thr_execute(napi_env env, void* data) { thr_job* j = (thr_job*)data; (void)env;
+  j->rc = j->kind == 0 ? p_nbls_fr_op_batch(j->c, j->op, j->n, j->a, j->b, j->out, j->st)
+        : j->kind == 1 ? p_nbls_lagrange_at_zero(j->c, j->n, j->offs, j->a, j->out, j->st)
+        : (j->g2 ? p_nbls_g2_combine_shares : p_nbls_g1_combine_shares)(j->c, j->n, j->offs, j->a, j->shares, j->out, j->st); }
+static void thr_complete(napi_env env, napi_status status, void* data) {
+  thr_job* j = (thr_job*)data;
+  if (status != napi_ok || j->rc) {
+    char m[128]; snprintf(m, sizeof m, "nbls: %s (code %d)", p_nbls_strerror ? p_nbls_strerror(j->rc) : "error", j->rc);
+    napi_value msg, err; napi_create_string_utf8(env, m, NAPI_AUTO_LENGTH, &msg); napi_create_error(env, NULL, msg, &err); napi_reject_deferred(env, j->deferred, err);
+  } else {
+    napi_value vo, vs; napi_get_reference_value(env, j->refs[j->nrefs - 2], &vo); napi_get_reference_value(env, j->refs[j->nrefs - 1], &vs);
+    napi_resolve_deferred(env, j->deferred, result2(env, vo, vs));
+  }
+  for (int i = 0; i < j->nrefs; i++) napi_delete_reference(env, j->refs[i]);
+  napi_delete_async_work(env, j->work); free(j);
+}
+/* runs the job here (async == 0) or queues it; vo / vs: the output arrays, made by the caller on the main thread */
+static napi_value thr_run(napi_env env, thr_job* job, int async, napi_value* argv, int nargs, napi_value vo, napi_value vs) {
+  if (!async) { job->c = ctx; thr_execute(env, job); return job->rc ? throw_code(env, job->rc) : result2(env, vo, vs); }
+  thr_job* j = (thr_job*)calloc(1, sizeof *j); if (!j) { napi_throw_error(env, NULL, "out of memory"); return NULL; }
+  *j = *job; j->c = pool_take(); j->nrefs = nargs + 2;
+  for (int i = 0; i < nargs; i++) napi_create_reference(env, argv[i], 1, &j->refs[i]);
+  napi_create_reference(env, vo, 1, &j->refs[nargs]); napi_create_reference(env, vs, 1, &j->refs[nargs + 1]);
+  napi_value promise, name; napi_create_promise(env, &j->deferred, &promise); napi_create_string_utf8(env, "nbls_threshold", NAPI_AUTO_LENGTH, &name);
+  if (napi_create_async_work(env, NULL, name, thr_execute, thr_complete, j, &j->work) != napi_ok || napi_queue_async_work(env, j->work) != napi_ok) {
+    for (int i = 0; i < j->nrefs; i++) napi_delete_reference(env, j->refs[i]); free(j); napi_throw_error(env, NULL, "napi_create_async_work failed"); return NULL; }
+  return promise;
+}
+static napi_value fr_op_call(napi_env env, napi_callback_info info, int async) {
+  ARGS(3); NEED_CTX(); BYTES(1, a, la);
+  int32_t op; if (napi_get_value_int32(env, argv[0], &op) != napi_ok) { napi_throw_type_error(env, NULL, "expected an operation number"); return NULL; }
+  uint8_t* b = NULL; size_t lb = 0;
+  napi_valuetype t; napi_typeof(env, argv[2], &t);
+  if (t != napi_null && t != napi_undefined && !get_bytes(env, argv[2], &b, &lb)) { napi_throw_type_error(env, NULL, "expected Uint8Array or null"); return NULL; }
+  if (la % 32 || (b && lb != la)) { napi_throw_range_error(env, NULL, "operands are 32 bytes each, as many second operands as first ones"); return NULL; }
+  thr_job job; memset(&job, 0, sizeof job);
+  job.kind = 0; job.op = op; job.a = a; job.b = b; job.n = la / 32;
+  napi_value vo = new_u8(env, la ? la : 1, &job.out), vs = new_u8(env, job.n ? job.n : 1, (uint8_t**)&job.st); ALLOCATED(vo); ALLOCATED(vs);
+  return thr_run(env, &job, async, argv + 1, b ? 2 : 1, vo, vs);   /* references to the arrays only */
+}
+static napi_value FrOp(napi_env env, napi_callback_info info) { return fr_op_call(env, info, 0); }
+static napi_value FrOpAsync(napi_env env, napi_callback_info info) { return fr_op_call(env, info, 1); }
+/* groups + 1 offsets whose last entry stays inside `have` items */
+static int thr_offsets_ok(const uint8_t* offs, size_t lo, size_t have, size_t* groups) {
+  if (lo < 8 || lo % 4) return 0;
+  *groups = lo / 4 - 1;
+  return (size_t)((const uint32_t*)offs)[*groups] <= have;
+}
+static napi_value lagrange_call(napi_env env, napi_callback_info info, int async) {
+  ARGS(2); NEED_CTX(); BYTES(0, offs, lo); BYTES(1, ids, li);
+  size_t m;
+  if (li % 32 || !thr_offsets_ok(offs, lo, li / 32, &m)) { napi_throw_range_error(env, NULL, "bad group offsets or identifier array length"); return NULL; }
+  thr_job job; memset(&job, 0, sizeof job);
+  job.kind = 1; job.offs = (const uint32_t*)offs; job.a = ids; job.n = m;
+  napi_value vo = new_u8(env, li ? li : 1, &job.out), vs = new_u8(env, m, (uint8_t**)&job.st); ALLOCATED(vo); ALLOCATED(vs);
+  return thr_run(env, &job, async, argv, 2, vo, vs);
+}
+static napi_value LagrangeAtZero(napi_env env, napi_callback_info info) { return lagrange_call(env, info, 0); }
+static napi_value LagrangeAtZeroAsync(napi_env env, napi_callback_info info) { return lagrange_call(env, info, 1); }
+static napi_value combine_call(napi_env env, napi_callback_info info, int async) {
+  ARGS(4); NEED_CTX(); BYTES(1, offs, lo); BYTES(2, ids, li); BYTES(3, shares, ls);
+  int32_t g2; if (napi_get_value_int32(env, argv[0], &g2) != napi_ok) { napi_throw_type_error(env, NULL, "expected 0 (G1) or 1 (G2)"); return NULL; }
+  const size_t e = g2 ? 96 : 48; size_t m;
+  if (li % 32 || ls != li / 32 * e || !thr_offsets_ok(offs, lo, li / 32, &m)) { napi_throw_range_error(env, NULL, "bad group offsets, identifier or share array length"); return NULL; }
+  thr_job job; memset(&job, 0, sizeof job);
+  job.kind = 2; job.g2 = g2 != 0; job.offs = (const uint32_t*)offs; job.a = ids; job.shares = shares; job.n = m;
+  napi_value vo = new_u8(env, m * e, &job.out), vs = new_u8(env, m, (uint8_t**)&job.st); ALLOCATED(vo); ALLOCATED(vs);
+  return thr_run(env, &job, async, argv + 1, 3, vo, vs);
+}
+static napi_value CombineShares(napi_env env, napi_callback_info info) { return combine_call(env, info, 0); }
+static napi_value CombineSharesAsync(napi_env env, napi_callback_info info) { return combine_call(env, info, 1); }
+
 static napi_value ModuleInit(napi_env env, napi_value exports) {
   const char* path = getenv("NBLS_LIB");
   char buf[4096];
@@ -431,6 +515,7 @@ static napi_value ModuleInit(napi_env env, napi_value exports) {
   LOAD(nbls_hash_to_g2_batch) LOAD(nbls_g1_sum) LOAD(nbls_g2_sum) LOAD(nbls_verify_batch) LOAD(nbls_g1_mul_batch) LOAD(nbls_g2_mul_batch) LOAD(nbls_sign_batch) LOAD(nbls_hash_to_g1_batch) LOAD(nbls_encode_to_g1_batch) LOAD(nbls_encode_to_g2_batch) LOAD(nbls_g1_msm) LOAD(nbls_g2_msm)
   LOAD(nbls_init_multi) LOAD(nbls_destroy_multi) LOAD(nbls_multi_device_count) LOAD(nbls_multi_context) LOAD(nbls_multi_pairing_batch) LOAD(nbls_multi_miller_product) LOAD(nbls_multi_verify_batch) LOAD(nbls_g2_prepare) LOAD(nbls_pairing_prepared) LOAD(nbls_verify_multiple) LOAD(nbls_verify_aggregates) LOAD(nbls_verify_multiple_shared) LOAD(nbls_verify_aggregates_shared)
   LOAD(nbls_g1_from_hex_batch) LOAD(nbls_g2_from_hex_batch) LOAD(nbls_g2_from_signature_batch) LOAD(nbls_g1_clear_cofactor_batch) LOAD(nbls_g2_clear_cofactor_batch)
+  LOAD(nbls_fr_op_batch) LOAD(nbls_lagrange_at_zero) LOAD(nbls_g2_combine_shares) LOAD(nbls_g1_combine_shares)
   {   /* the ABI the addon was written against (include/nbls.h NBLS_ABI_VERSION): an older or newer library is refused at load instead of misread at run time */
     int (*abi)(void) = (int (*)(void))dlsym(lib, "nbls_abi_version");
     if (!abi || abi() != NBLS_ABI_VERSION) { napi_throw_error(env, NULL, "libnbls.so: ABI version differs from the one this addon was built for (include/nbls.h NBLS_ABI_VERSION)"); return exports; }
@@ -444,7 +529,10 @@ static napi_value ModuleInit(napi_env env, napi_value exports) {
     {"hashToCurve", 0, HashToCurve, 0, 0, 0, napi_enumerable, 0}, {"g1Msm", 0, G1Msm, 0, 0, 0, napi_enumerable, 0}, {"g2Msm", 0, G2Msm, 0, 0, 0, napi_enumerable, 0}, {"verifyBatchAsync", 0, VerifyBatchAsync, 0, 0, 0, napi_enumerable, 0}, {"verifyMultipleAsync", 0, VerifyMultipleAsync, 0, 0, 0, napi_enumerable, 0}, {"verifyAggregatesAsync", 0, VerifyAggregatesAsync, 0, 0, 0, napi_enumerable, 0},
     {"verifyMultipleSharedAsync", 0, VerifyMultipleSharedAsync, 0, 0, 0, napi_enumerable, 0}, {"verifyAggregatesSharedAsync", 0, VerifyAggregatesSharedAsync, 0, 0, 0, napi_enumerable, 0}, {"signBatchAsync", 0, SignBatchAsync, 0, 0, 0, napi_enumerable, 0},
     {"initMulti", 0, InitMulti, 0, 0, 0, napi_enumerable, 0}, {"g2Prepare", 0, G2Prepare, 0, 0, 0, napi_enumerable, 0}, {"pairingPrepared", 0, PairingPrepared, 0, 0, 0, napi_enumerable, 0},
-    {"decodePoints", 0, DecodePoints, 0, 0, 0, napi_enumerable, 0}, {"clearCofactor", 0, ClearCofactor, 0, 0, 0, napi_enumerable, 0}};
+    {"decodePoints", 0, DecodePoints, 0, 0, 0, napi_enumerable, 0}, {"clearCofactor", 0, ClearCofactor, 0, 0, 0, napi_enumerable, 0},
+    {"frOp", 0, FrOp, 0, 0, 0, napi_enumerable, 0}, {"frOpAsync", 0, FrOpAsync, 0, 0, 0, napi_enumerable, 0}, {"lagrangeAtZero", 0, LagrangeAtZero, 0, 0, 0, napi_enumerable, 0},
+    {"lagrangeAtZeroAsync", 0, LagrangeAtZeroAsync, 0, 0, 0, napi_enumerable, 0}, {"combineShares", 0, CombineShares, 0, 0, 0, napi_enumerable, 0},
+    {"combineSharesAsync", 0, CombineSharesAsync, 0, 0, 0, napi_enumerable, 0}};
   napi_define_properties(env, exports, sizeof d / sizeof d[0], d);
   return exports;
 }
