@@ -301,8 +301,10 @@ struct HostIO {
     return p;
   }
 };
-#define LOCKED(ctx) std::lock_guard<std::recursive_mutex> g_((ctx)->mu); HIPCHK(hipSetDevice((ctx)->device)); hipStream_t s = (ctx)->stream
-// the same for an entry point that works on device pointers and takes the caller's stream (NULL: the context's): `s` is that stream, ordered behind the context's previous call
+// a host-buffer entry point: works on the context's stream, ordered behind the context's previous call like every other call (a device-resident call on a caller's stream returns
+// with its work still queued, and the pipelines the host-buffer calls run -- dev_msm, dev_point_mul, dev_expand, ... -- use the same scratch slots)
+#define LOCKED(ctx) std::lock_guard<std::recursive_mutex> g_((ctx)->mu); HIPCHK(hipSetDevice((ctx)->device)); hipStream_t s = (ctx)->stream; StreamOrder order_((ctx), s)
+// the same for an entry point that works on device pointers and takes the caller's stream (NULL: the context's): `s` is that stream
 static inline hipStream_t call_stream(nbls_ctx* ctx, void* stream) { return stream ? (hipStream_t)stream : ctx->stream; }
 #define DEV_ENTER(ctx, stream) std::lock_guard<std::recursive_mutex> g_((ctx)->mu); HIPCHK(hipSetDevice((ctx)->device)); hipStream_t s = call_stream((ctx), (stream)); StreamOrder order_((ctx), s)
 // first statement of an entry point that makes several locked calls: scratch and I/O staging buffers belong to it until it returns.  Stands in front of the argument check, so it

@@ -59,9 +59,11 @@ def test_wide_expx_agrees_with_the_interpreter_on_extreme_elements(sim):
 
 
 def test_g1_window_combination_with_one_limb_per_lane(sim):
-    """csrc/g1_wide.h (device: nbls_g1_wide_combine_kernel, one wavefront): sum_w 2^(12 w) S_w over eleven projective window sums -- the tail of the G1 multi-scalar
+    """csrc/g1_wide.h (device: nbls_g1_wide_combine_kernel, one wavefront): sum_w 2^(shift w) S_w over nwin projective window sums -- the tail of the G1 multi-scalar
     multiplication -- against plain affine arithmetic on y^2 = x^3 + 4 in Python, for ordinary points, a window sum that is the identity, equal and opposite neighbours (the
-    formulas are the complete ones), raw inputs at the top of the range scratch elements may have; outputs exact and below 8 p; no 32 / 64-bit assumption violated."""
+    formulas are the complete ones), raw inputs at the top of the range scratch elements may have; outputs exact and below 8 p; no 32 / 64-bit assumption violated.
+    Shapes: dev_msm launches the kernel first as 12 terms with shift 1 (the Horner sum over the bit slices of a window), then over the windows with shift 12 and nwin anywhere in
+    1 .. 16 (11: the endomorphism split, 6: 64-bit scalars).  The ordinary, all-identity and large-raw-input trials run at every shape, the others wherever nwin has room."""
     import random
     p = vmsim_py.P_MOD; R = 1 << 392; RAW = vmsim_py.RAW
     rnd = random.Random(1212)
@@ -110,24 +112,33 @@ def test_g1_window_combination_with_one_limb_per_lane(sim):
             out.append(v * pow(R, -1, p) % p)
         return out
 
-    nwin, shift = 11, 12
-    for trial in range(6):
-        W = [point() for _ in range(nwin)]
-        if trial == 1: W[3] = None; W[10] = None                 # identity window sums, also the top one
-        if trial == 2: W[5] = W[6]; W[7] = (W[8][0], (-W[8][1]) % p)
-        if trial == 3: W = [None] * nwin
-        if trial == 4:                                           # the running sum meets its own negative: 2^12 acc + S = 0 at window 4
-            acc = None
-            for w in range(nwin - 1, 4, -1): acc = add(mul(1 << shift, acc), W[w]) if acc is not None else W[w]
-            t = mul(1 << shift, acc); W[4] = (t[0], (-t[1]) % p)
-        S = vmsim_py.buf(b''.join(raw_proj(Q, big=(trial == 5)) for Q in W))
-        out = vmsim_py.buf(3 * RAW)
-        sim.nbls_sim_g1_wide_combine(S, nwin, shift, out)
-        X, Y, Z = unraw(out.raw)
-        exp = None
-        for w in range(nwin - 1, -1, -1): exp = add(mul(1 << shift, exp), W[w])
-        if exp is None:
-            assert X == 0 and Z == 0 and Y != 0, trial
-        else:
-            assert Z != 0 and X * pow(Z, -1, p) % p == exp[0] and Y * pow(Z, -1, p) % p == exp[1], trial
+    for nwin, shift in ((11, 12), (12, 1), (1, 12), (1, 1), (2, 12), (6, 12), (16, 12)):
+        for trial in range(6):
+            W = [point() for _ in range(nwin)]
+            if trial == 1:                                           # identity window sums, also the top one
+                if nwin < 2: continue
+                W[nwin - 1] = None
+                if nwin > 4: W[3] = None
+            if trial == 2:                                           # equal neighbours, opposite neighbours
+                if nwin < 2: continue
+                a = 5 if nwin > 8 else 0
+                W[a] = W[a + 1]
+                if nwin > a + 3: W[a + 2] = (W[a + 3][0], (-W[a + 3][1]) % p)
+            if trial == 3: W = [None] * nwin
+            if trial == 4:                                           # the running sum meets its own negative: 2^shift acc + S = 0 at window c (4 where nwin has six windows)
+                if nwin < 2: continue
+                c = min(4, nwin - 2)
+                acc = None
+                for w in range(nwin - 1, c, -1): acc = add(mul(1 << shift, acc), W[w]) if acc is not None else W[w]
+                t = mul(1 << shift, acc); W[c] = (t[0], (-t[1]) % p)
+            S = vmsim_py.buf(b''.join(raw_proj(Q, big=(trial == 5)) for Q in W))
+            out = vmsim_py.buf(3 * RAW)
+            sim.nbls_sim_g1_wide_combine(S, nwin, shift, out)
+            X, Y, Z = unraw(out.raw)
+            exp = None
+            for w in range(nwin - 1, -1, -1): exp = add(mul(1 << shift, exp), W[w])
+            if exp is None:
+                assert X == 0 and Z == 0 and Y != 0, (nwin, shift, trial)
+            else:
+                assert Z != 0 and X * pow(Z, -1, p) % p == exp[0] and Y * pow(Z, -1, p) % p == exp[1], (nwin, shift, trial)
     assert sim.nbls_sim_wide_violations() == 0
