@@ -310,7 +310,7 @@ const char* nbls_config_describe(void);   /* "NBLS_X=value(env|default) ...": ev
 /* 5: nbls_verify_multiple, NBLS_ST_NOT_VERIFIED, scratch slots 20 .. 43 (additions only); then nbls_verify_aggregates, nbls_verify_aggregates_indexed, nbls_keyset_create /
    _destroy / _size, scratch slots 44 .. 47 (additions only, same version); then nbls_verify_multiple_shared, nbls_verify_aggregates_shared,
    nbls_verify_aggregates_indexed_shared, scratch slots 48 .. 50 (additions only, same version); then nbls_fr_op_batch, nbls_lagrange_at_zero, nbls_g2_combine_shares,
-   nbls_g1_combine_shares, NBLS_FROP_*, NBLS_ST_BAD_IDS, scratch slots 51 .. 56 (additions only, same version).
+   nbls_g1_combine_shares, NBLS_FROP_*, NBLS_ST_BAD_IDS, scratch slots 51 .. 56 (additions only, same version); then nbls_field_kernel_raw (addition only, same version).
    4 (round 6): nbls_hw_queues, NBLS_TUNE_WIDE_MAX, NBLS_TUNE_H2C_NORM_MIN, NBLS_TUNE_INV_WIDE_MAX, NBLS_TUNE_LS_MAX / _LS2_MAX (additions only); the library sets GPU_MAX_HW_QUEUES = 22 at load when the variable is unset (see nbls_pool_init below).
    3 (round 5): nbls_program_kernel, nbls_pool_*, nbls_sign_batch_dev, NBLS_TUNE_VERIFY_* / _SAC_MAX / _PT_LS2_MAX (additions only); nbls_verify_batch_partial_dev writes d_out_fp12 even when it reports a zero point or a decode error
    (contents then meaningless); 2: *_partial take *d_partial as OUT only, *_partial_into added, nbls_tower_op_batch, nbls_verify_batch_msgs_dev.  The bindings check it at load. */
@@ -359,6 +359,12 @@ int nbls_program_stats(nbls_ctx* ctx, int prog, uint32_t* out8);   /* steps, mul
 int nbls_device_synchronize(nbls_ctx* ctx);
 /* Placement study (tools/placement.py): runs one step program on n scratch items; out_blocks[5b..5b+4] = HW_ID | XCC_ID << 32, start tick, end tick (s_memtime), start, end time (s_memrealtime, 100 MHz) of workgroup b. */
 int nbls_placement_probe(nbls_ctx* ctx, size_t n, uint64_t* out_blocks);
+/* The stand-alone field kernels on raw operands (tests/test_gpu_field_kernels.py): kind 0 .. 3 = the fixed exponents (p+1)/4, (p^2+7)/16, (p^2-9)/16, (p-3)/4 (Fp.sqrt,
+ * Fp2.sqrt, sqrt_div_fp2 and the SWU exponent: math.ts:251-264, 521-538, 1196-1198), kind 4 = the Montgomery inverse (Fp.invert, math.ts:134-156).  form 1: one element per lane
+ * (kinds 1, 2: one pair of lanes), form 2: one limb per lane, form 0: what the pipelines' own dispatch takes for this n under the context's tuning.  Elements are the engine's raw
+ * scratch elements, 64 bytes each: 14 little-endian 28-bit limbs in 32-bit words, then 8 zero bytes; any representative below 16 p (the inverse: below 2^392).  Kinds 1 and 2 read
+ * and write 2 n elements, c0 then c1.  NBLS_EINVAL for an unknown kind or form, missing buffers with n > 0 and n > 2^24; n = 0 is NBLS_OK. */
+int nbls_field_kernel_raw(nbls_ctx* ctx, int kind, int form, size_t n, const uint8_t* in_raw, uint8_t* out_raw);
 /* Per-kernel HIP-event timing (benchmark roofline leg): ms[i]/counts[i] for program i, last entry = inversion kernel. */
 #define NBLS_N_PROGRAMS 128
 /* Tuning knobs of a context (defaults are the measured optimum; tests use them to force a code path).

@@ -68,6 +68,32 @@ EXPORT int nbls_placement_probe(nbls_ctx* ctx, size_t n, uint64_t* out_blocks) {
   hipFree(dbg);
   return NBLS_OK;
 }
+// The stand-alone field kernels on raw operands: the four fixed exponents (numbered as run_pow's `which`) and the inversion, in the form the caller names (1: one element per
+// lane, 2: one limb per lane) or the one run_pow / run_inv_buf take for this n (0).  NBLS_POW_WIDE_MAX is read once per process, so the explicit forms are what lets a test run
+// both kernels of an exponent in one process at any n.
+EXPORT int nbls_field_kernel_raw(nbls_ctx* ctx, int kind, int form, size_t n, const uint8_t* in_raw, uint8_t* out_raw) {
+  if (!ctx || kind < 0 || kind > 4 || form < 0 || form > 2 || n > ((size_t)1 << 24) || (n && (!in_raw || !out_raw))) return NBLS_EINVAL;
+  if (!n) return NBLS_OK;
+  const bool is_fp2 = kind == 1 || kind == 2;
+  const size_t bytes = n * (is_fp2 ? 2 : 1) * RAW;
+  LOCKED(ctx); HostIO io{ctx}; void *d = io.alloc(bytes), *o = io.alloc(bytes); if (!d || !o) return NBLS_EHIP;
+  HIPCHK(hipMemcpyAsync(d, in_raw, bytes, hipMemcpyHostToDevice, s));
+  int r;
+  if (kind == 4) {
+    if (form == 0) { if ((r = run_inv_buf(ctx, n, d, o, s))) return r; }
+    else LAUNCHCHK(form == 2 ? nbls_fp_inv_wide_launch((unsigned)n, d, o, s) : nbls_fp_inv_launch((unsigned)n, d, o, s));
+  } else if (form == 0) { if ((r = run_pow(ctx, kind, n, d, o, s))) return r; }
+  else {
+    const int tail = kind == 1 ? 8 : kind == 2 ? 7 : 0;
+    if (form == 2) LAUNCHCHK(nbls_pow_wide_launch((unsigned)n, d, o, ctx->nib[kind], ctx->nnib[kind], tail, s));
+    else {
+      uint8_t* tab; if ((r = need(ctx, SB_POW_TABLE, n * POW_TAB * (is_fp2 ? 2 : 1) * RAW, &tab))) return r;
+      LAUNCHCHK(nbls_fp_pow_launch((unsigned)n, d, o, ctx->nib[kind], ctx->nnib[kind], tab, tail, s));
+    }
+  }
+  HIPCHK(hipMemcpyAsync(out_raw, o, bytes, hipMemcpyDeviceToHost, s)); HIPCHK(hipStreamSynchronize(s));
+  return NBLS_OK;
+}
 EXPORT int nbls_program_stats(nbls_ctx* ctx, int prog, uint32_t* o) {
   (void)ctx;
   if (prog < 0 || prog >= P_COUNT || !o) return NBLS_EINVAL;

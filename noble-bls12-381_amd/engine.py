@@ -90,6 +90,7 @@ def load_library():
     lib.nbls_miller_product_prepared_dev.argtypes = [vp, sz, vp, vp, sz, i32, vp, vp]
     lib.nbls_pairing_prepared.argtypes = [vp, sz, vp, vp, sz, i32, i32, vp]
     lib.nbls_set_tuning.argtypes = [vp, i32, C.c_longlong]
+    lib.nbls_field_kernel_raw.argtypes = [vp, i32, i32, sz, vp, vp]
     for nm in ('nbls_g1_from_hex_batch', 'nbls_g2_from_hex_batch', 'nbls_g2_from_signature_batch'):
         getattr(lib, nm).argtypes = [vp, sz, vp, sz, vp, vp]
     lib.nbls_g1_to_hex_batch.argtypes = [vp, sz, vp, vp, i32, vp]
@@ -699,6 +700,23 @@ class Engine:
         out = C.create_string_buffer(n * esz)
         args = [C.c_char_p(x) if x is not None else None for x in (a, b, c, d)]
         self._chk(self.lib.nbls_tower_op_batch(self.h, C.c_int(field), C.c_int(op), C.c_int(param), C.c_size_t(n), args[0], args[1], args[2], args[3], out))
+        return out.raw
+
+    FIELD_KINDS = {'sqrt': 0, 'fp2_sqrt': 1, 'fp2_sqrt_div': 2, 'swu': 3, 'inv': 4}
+
+    def field_kernel_raw(self, kind, form, n, raw, out=None):
+        """the stand-alone field kernels on raw scratch elements (include/nbls.h nbls_field_kernel_raw): kind = 0 .. 3 (the exponents (p+1)/4, (p^2+7)/16, (p^2-9)/16, (p-3)/4)
+        or 4 (the Montgomery inverse), or its name in FIELD_KINDS; form = 1 (one element per lane), 2 (one limb per lane) or 0 (what the pipelines would take for this n);
+        raw: n elements of 64 bytes (kinds 1, 2: 2 n, c0 then c1); out: a ctypes buffer to write into (it may be longer: the call writes the elements' bytes only) -> its bytes"""
+        kind = self.FIELD_KINDS[kind] if isinstance(kind, str) else int(kind)
+        size = 64 * n * (2 if kind in (1, 2) else 1)
+        if len(raw) < size:
+            raise NblsError('field_kernel_raw: %d bytes for %d elements' % (len(raw), n))
+        if out is None:
+            out = C.create_string_buffer(max(size, 1))
+        elif len(out) < size:
+            raise NblsError('field_kernel_raw: output buffer of %d bytes for %d elements' % (len(out), n))
+        self._chk(self.lib.nbls_field_kernel_raw(self.h, kind, int(form), n, raw, out))
         return out.raw
 
     def config_describe(self):

@@ -12,6 +12,7 @@ import importlib
 import random
 import pytest
 from goldenio import hx
+from field_cases import EXT      # the extremal field elements, shared with the tower and field-kernel tests
 
 pytestmark = pytest.mark.gpu
 P = 0x1a0111ea397fe69a4b1ba7b6434bacd764774b84f38512bf6730d2a0f6b0f6241eabfffeb153ffffb9feffffffffaaab
@@ -27,19 +28,6 @@ def eng():
 
 def fp(v):
     return (v % P).to_bytes(48, 'big')
-
-
-# extremal field elements: the ends of the range, the middle, single high bits, alternating 28-bit limb patterns (the engine's limb size)
-def _extremes():
-    lim = (1 << 28) - 1
-    alt_a = sum((lim if i % 2 == 0 else 0) << (28 * i) for i in range(14)) % P
-    alt_b = sum((lim if i % 2 == 1 else 0) << (28 * i) for i in range(14)) % P
-    all_ones_limbs = sum(lim << (28 * i) for i in range(13))           # 13 saturated limbs, below p
-    return [P - 1, 0, 1, (P - 1) // 2, (P + 1) // 2, (1 << 380) + 0x123456789abcdef, (1 << 380) - 1, P - 2, 2, alt_a, alt_b, all_ones_limbs,
-            (1 << 379) + (1 << 28) - 1, P - (1 << 28), 3 * (P // 4)]
-
-
-EXT = _extremes()
 
 
 def _fp12_cases():

@@ -1,6 +1,7 @@
 """GPU parity tests for the rows of SURVEY 8(a) around the pairing: validity checks, decoders, hash-to-G2, sums, verifyBatch."""
 import hashlib
 import importlib
+import random
 import pytest
 from ctypes import c_int as C_int
 from goldenio import hx
@@ -115,6 +116,57 @@ def test_point_sums(eng, oracle, golden):
             out, st = eng.point_sum(pts[:sz * n], g2)
             rst, ref = (oracle.g2_sum if g2 else oracle.g1_sum)(pts[:sz * n])
             assert (st, out) == (rst, ref)
+
+
+@pytest.fixture(scope='module')
+def known_points(oracle):
+    """per group: 64 points a_i G with known a_i (test_gpu_msm._points), so that a sum of any size is checked with ONE oracle multiplication besides the oracle's own sum"""
+    from test_gpu_msm import _points
+    return {g2: _points(oracle, 64, 2024 + g2, g2=bool(g2)) for g2 in (0, 1)}
+
+
+def _gen_mul(oracle, g2, t):
+    return (oracle.g2_mul(oracle.g2_generator(), t) if g2 else oracle.g1_mul(oracle.g1_generator(), t))[1]
+
+
+@pytest.mark.parametrize('g2,n', [(0, n) for n in (13, 31, 32, 33, 63, 64, 65, 127, 128, 129, 1000, 4097)] + [(1, n) for n in (13, 33, 64, 65, 129, 1025)])
+def test_point_sums_over_deep_trees(eng, oracle, known_points, g2, n):
+    """dev_point_sum's tree of complete additions beyond twelve points: sizes around the powers of two, and sizes that are odd at several levels (4097 -> 2049 -> 1025; every odd
+    level is padded with the identity), the leaves drawn from 64 known points -- so equal neighbours (a doubling at the leaves) occur as well"""
+    from test_gpu_msm import R_ORDER
+    a, pts = known_points[g2]
+    rnd = random.Random(4097 * g2 + n)
+    idx = [rnd.randrange(64) for _ in range(n)]
+    blob = b''.join(pts[i] for i in idx)
+    out, st = eng.point_sum(blob, bool(g2))
+    rst, ref = (oracle.g2_sum if g2 else oracle.g1_sum)(blob)
+    assert (st, out) == (rst, ref) and st == 0
+    assert out == _gen_mul(oracle, g2, sum(a[i] for i in idx) % R_ORDER)
+
+
+@pytest.mark.parametrize('g2', [0, 1], ids=['g1', 'g2'])
+def test_point_sums_exceptional_nodes(eng, oracle, known_points, g2):
+    """the nodes where an incomplete addition formula would fail: a doubling at the leaves and one level up, an identity node added to a point (on either side) and to another
+    identity node, a zero total over more than two points, and the empty sum"""
+    from test_gpu_msm import R_ORDER, _neg
+    a, pts = known_points[g2]
+    sz = 192 if g2 else 96
+    (Pa, Qa, Ra, Sa), (Pt, Qt, Rt, St) = a[:4], pts[:4]
+    for name, blob, t in (('[P, P, Q, R]', Pt + Pt + Qt + Rt, 2 * Pa + Qa + Ra), ('[P, Q, P, Q]', Pt + Qt + Pt + Qt, 2 * Pa + 2 * Qa),
+                          ('[P, -P, Q]', Pt + _neg(Pt) + Qt, Qa), ('[Q, P, -P]', Qt + Pt + _neg(Pt), Qa),
+                          ('[P, -P, Q, -Q, S]', Pt + _neg(Pt) + Qt + _neg(Qt) + St, Sa)):
+        out, st = eng.point_sum(blob, bool(g2))
+        rst, ref = (oracle.g2_sum if g2 else oracle.g1_sum)(blob)
+        assert (st, out) == (0, _gen_mul(oracle, g2, t % R_ORDER)), name
+        assert (rst, ref) == (st, out), name
+    # a zero total: status 1 and an all-zero output
+    negs = [_neg(p) for p in pts]
+    order = [(37 * i + 11) % 64 for i in range(64)]
+    assert sorted(order) == list(range(64))
+    for name, blob in (('[P, -P, Q, -Q]', Pt + _neg(Pt) + Qt + _neg(Qt)), ('64 points and their negatives', b''.join(pts) + b''.join(negs[i] for i in order))):
+        assert eng.point_sum(blob, bool(g2)) == (bytes(sz), 1), name
+        assert (oracle.g2_sum if g2 else oracle.g1_sum)(blob)[0] == 1, name
+    assert eng.point_sum(b'', bool(g2))[1] == 1
 
 
 def test_verify_batch(eng, oracle, golden, testdata):

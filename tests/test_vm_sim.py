@@ -1,6 +1,7 @@
 """Compiled step programs executed by the host VM simulator, checked bit-for-bit against oracle/ (CPU only)."""
 import ctypes as C
 import pytest
+import field_cases
 import vmsim_py
 from goldenio import hx
 
@@ -129,13 +130,9 @@ def test_point_sum_programs(sim, oracle, golden):
 def test_fp_inverse_edge_cases(sim):
     """the per-lane inversion routine (fp_inv.h) on structured inputs: any representative below 2^392, powers of two,
     all-ones, values next to p, tiny and zero; expected a^-1 in the same Montgomery form (Fp.invert, math.ts:134-156)"""
-    import random
     p = vmsim_py.P_MOD
-    rnd = random.Random(381)
-    xs = [rnd.randrange(1, p) for _ in range(500)] + [rnd.randrange(1, 1 << rnd.randrange(1, 392)) for _ in range(1500)]
-    xs += [1 << i for i in range(392)] + [(1 << i) - 1 for i in range(1, 392)] + [p - (1 << i) for i in range(380)]
-    xs += [1, 2, p - 1, 0, 5 * p + 3, (1 << 391) + 12345, p + 1, 2 * p - 1]
-    inp = b''.join(b''.join(((x >> (28 * i)) & 0xfffffff).to_bytes(4, 'little') for i in range(14)) + bytes(8) for x in xs)
+    xs = field_cases.inverse_inputs()      # shared with the device test (tests/test_gpu_field_kernels.py)
+    inp = field_cases.raw(xs)
     src = C.create_string_buffer(inp, len(inp)); dst = C.create_string_buffer(len(inp))
     sim.nbls_sim_fp_inv(C.c_uint(len(xs)), src, dst)
     R = 1 << 392
@@ -173,11 +170,9 @@ def test_pow_chains(sim):
     """the fixed-exponent chains of the per-lane kernels (pow_exec.h: sliding windows over odd powers, a dedicated Fp squaring, signed Fp2 operands, the
     split a^e = (conj(a) a^11)^K a^tail of the two Fp2 exponents) executed on the host, against Python's pow() and against the plain square-and-multiply
     stand-in: Fp.sqrt's a^((p+1)/4) (math.ts:251-264), the SWU exponent (p-3)/4, Fp2.sqrt's (p^2+7)/16 and sqrt_div_fp2's (p^2-9)/16 (math.ts:521-538, 1196-1198)"""
-    import random
     p = vmsim_py.P_MOD
     R = 1 << 392
-    rnd = random.Random(5381)
-    xs = [rnd.randrange(0, p) for _ in range(40)] + [0, 1, 2, p - 1, p - 2, (1 << 380), (1 << 381) - 1 - p, 3 * p + 5, 15 * p + 7, (p + 1) // 2]
+    xs = field_cases.pow_inputs()          # shared with the device test (tests/test_gpu_field_kernels.py): any representative below 16 p
     for which, e in ((0, (p + 1) // 4), (3, (p - 3) // 4)):
         src = C.create_string_buffer(_raw(xs), 64 * len(xs)); dst = C.create_string_buffer(64 * len(xs))
         sim.nbls_sim_fp_pow(C.c_uint(len(xs)), src, dst, which)
@@ -186,14 +181,8 @@ def test_pow_chains(sim):
             a = (x * pow(R, -1, p)) % p                      # the element a raw value stands for
             assert got < 4 * p and got % p == (pow(a, e, p) * R) % p, (which, hex(x))
     # Fp2: elements (c0, c1), both components any representative below 16 p
-    def f2mul(a, b): return ((a[0] * b[0] - a[1] * b[1]) % p, (a[0] * b[1] + a[1] * b[0]) % p)
-    def f2pow(a, e):
-        r = (1, 0)
-        for bit in bin(e)[2:]:
-            r = f2mul(r, r)
-            if bit == '1': r = f2mul(r, a)
-        return r
-    pairs = [(rnd.randrange(0, p), rnd.randrange(0, p)) for _ in range(12)] + [(0, 0), (1, 0), (0, 1), (p - 1, p - 1), (5, 0), (0, 7), (15 * p + 3, 14 * p + 9), (p - 1, 1)]
+    f2pow = field_cases.f2pow
+    pairs = field_cases.fp2_pow_inputs()
     flat = [c for pr in pairs for c in pr]
     for which, e in ((1, (p * p + 7) // 16), (2, (p * p - 9) // 16)):
         src = C.create_string_buffer(_raw(flat), 64 * len(flat)); dst = C.create_string_buffer(64 * len(flat)); ref = C.create_string_buffer(64 * len(flat))
