@@ -285,6 +285,27 @@ int nbls_lagrange_at_zero(nbls_ctx* ctx, size_t n_groups, const uint32_t* group_
 int nbls_g2_combine_shares(nbls_ctx* ctx, size_t n_groups, const uint32_t* group_offsets, const uint8_t* ids32, const uint8_t* shares96, uint8_t* out96, int8_t* status);
 int nbls_g1_combine_shares(nbls_ctx* ctx, size_t n_groups, const uint32_t* group_offsets, const uint8_t* ids32, const uint8_t* shares48, uint8_t* out48, int8_t* status);
 
+/* Share public keys: the commitment polynomial of a DKG / Feldman VSS evaluated in the exponent (no reference counterpart).  F(x) = sum_j [x^j] A_j with the committed
+ * coefficients A_j = [a_j]G, A_0 the group key; pk_k = F(x_k) is the public key of share k, and [s]G == F(x_me) is the check a participant runs on a share it receives.
+ * n_groups polynomials per call: group g owns the coefficients coef_offsets[g] .. coef_offsets[g + 1] of the coefficient array, LOWEST degree first, and the identifiers
+ * id_offsets[g] .. id_offsets[g + 1] of ids32 (n_groups + 1 offsets each, strictly increasing: no empty group; the first need not be 0, the entries in front of it are not read).
+ *   coefficients  compressed points decoded as nbls_g*_combine_shares decodes its shares: 48 bytes by PointG1.fromHex's rules, 96 bytes by PointG2.fromSignature's, subgroup
+ *                 check included.  A zero coefficient (0xc0 00..) is valid and adds nothing.
+ *   identifiers   32 bytes big-endian, ANY value, zero included: F(0) = A_0 is a legitimate question (refusing zero identifiers is nbls_lagrange_at_zero's job); x and x + r
+ *                 give the same bytes.
+ *   out[k]        compress(F_g(x_k)), one per identifier.  status[k] (may be NULL), in this order: what nbls_g*_decompress_batch reports for the group's FIRST coefficient that
+ *                 does not decode (>= 2: 3 outside the subgroup, 4 no square root), for every identifier of that group, with all-zero output; else 1 when F(x_k) is the zero
+ *                 point (output 0xc0 00..); else 0.  A bad group never disturbs its neighbours.
+ * One chain on the context's stream: one copy in, the decoder, Horner's rule in the exponent (acc <- [x]acc + A_j from the highest coefficient down: one step program per
+ * coefficient; a call whose identifiers are all below 2^16 as given runs the 16-bit form of the step), to-affine, compression, one copy out; the identifiers are worked through
+ * in slabs (NBLS_TUNE_POLY_SLAB) so that scratch stays bounded.  Returns NBLS_OK whatever the groups hold; NBLS_EINVAL before any device work for a missing pointer, n_groups = 0,
+ * offsets that do not strictly increase, more than 2^16 coefficients in one group, more than 2^24 coefficients or more than 2^22 identifiers in the call.  Coefficients and
+ * identifiers are public values: like the Fr calls this is NOT an interface for secrets (nothing is wiped, the short form's choice depends on the identifiers). */
+int nbls_g1_poly_eval(nbls_ctx* ctx, size_t n_groups, const uint32_t* coef_offsets /* n_groups + 1 */, const uint8_t* coefs48, const uint32_t* id_offsets /* n_groups + 1 */,
+                      const uint8_t* ids32, uint8_t* out48 /* one per identifier */, int8_t* status /* one per identifier, may be NULL */);
+int nbls_g2_poly_eval(nbls_ctx* ctx, size_t n_groups, const uint32_t* coef_offsets /* n_groups + 1 */, const uint8_t* coefs96, const uint32_t* id_offsets /* n_groups + 1 */,
+                      const uint8_t* ids32, uint8_t* out96 /* one per identifier */, int8_t* status /* one per identifier, may be NULL */);
+
 /* One rank's share of a verifyBatch spread over several GPUs (one process per GPU): the Miller product of this rank's n
  * (key, message) pairs, times millerLoop(-G, S) on the ONE rank that passes the signature (d_sig96 = NULL elsewhere), WITHOUT the
  * final exponentiation, as 576 wire bytes in device memory.  Ranks all-gather their partials and finish with
@@ -310,7 +331,8 @@ const char* nbls_config_describe(void);   /* "NBLS_X=value(env|default) ...": ev
 /* 5: nbls_verify_multiple, NBLS_ST_NOT_VERIFIED, scratch slots 20 .. 43 (additions only); then nbls_verify_aggregates, nbls_verify_aggregates_indexed, nbls_keyset_create /
    _destroy / _size, scratch slots 44 .. 47 (additions only, same version); then nbls_verify_multiple_shared, nbls_verify_aggregates_shared,
    nbls_verify_aggregates_indexed_shared, scratch slots 48 .. 50 (additions only, same version); then nbls_fr_op_batch, nbls_lagrange_at_zero, nbls_g2_combine_shares,
-   nbls_g1_combine_shares, NBLS_FROP_*, NBLS_ST_BAD_IDS, scratch slots 51 .. 56 (additions only, same version); then nbls_field_kernel_raw (addition only, same version).
+   nbls_g1_combine_shares, NBLS_FROP_*, NBLS_ST_BAD_IDS, scratch slots 51 .. 56 (additions only, same version); then nbls_field_kernel_raw (addition only, same version); then nbls_g1_poly_eval,
+   nbls_g2_poly_eval, nbls_extra_program_kernel, NBLS_TUNE_POLY_SLAB, scratch slots 57 .. 61 (additions only, same version).
    4 (round 6): nbls_hw_queues, NBLS_TUNE_WIDE_MAX, NBLS_TUNE_H2C_NORM_MIN, NBLS_TUNE_INV_WIDE_MAX, NBLS_TUNE_LS_MAX / _LS2_MAX (additions only); the library sets GPU_MAX_HW_QUEUES = 22 at load when the variable is unset (see nbls_pool_init below).
    3 (round 5): nbls_program_kernel, nbls_pool_*, nbls_sign_batch_dev, NBLS_TUNE_VERIFY_* / _SAC_MAX / _PT_LS2_MAX (additions only); nbls_verify_batch_partial_dev writes d_out_fp12 even when it reports a zero point or a decode error
    (contents then meaningless); 2: *_partial take *d_partial as OUT only, *_partial_into added, nbls_tower_op_batch, nbls_verify_batch_msgs_dev.  The bindings check it at load. */
@@ -386,12 +408,16 @@ int nbls_field_kernel_raw(nbls_ctx* ctx, int kind, int form, size_t n, const uin
 #define NBLS_TUNE_INV_WIDE_MAX 12     /* round 6: elements up to which an Fp inversion launch runs with one limb per lane, four elements per wavefront (shorter for ONE call, eight times the instructions per element: default 4096; nbls_pool_init sets 256 on its contexts; 0 = never) */
 #define NBLS_TUNE_LS_MAX 13           /* items up to which the pairing programs run in their four-lane forms (default 1024; nbls_pool_init sets 0 on its contexts: the forms shorten ONE call at up to four times the instructions per item) */
 #define NBLS_TUNE_LS2_MAX 14          /* ... in their two-lane forms, above LS_MAX (default 2048; pool contexts 0) */
+#define NBLS_TUNE_POLY_SLAB 15        /* identifiers that nbls_g*_poly_eval works through at a time: the per-step coefficient buffer and the accumulators never exceed one slab (default 2^18; 0 = the default) */
 int nbls_set_tuning(nbls_ctx* ctx, int key, long long value);
 int nbls_program_count(void);                 /* number of step programs; timing slot nbls_program_count() = the inversion kernel */
 const char* nbls_program_name(int prog);
 /* the kernel that executes program `prog` in this context: "nbls_aot_<name>" (ahead-of-time specialised, the product path) or "nbls_vm_kernel[_ls4]" (the interpreter:
    NBLS_AOT=0, or the build-time and run-time compilations of the program disagree); NULL on a bad index.  The string is static. */
 const char* nbls_program_kernel(nbls_ctx* ctx, int prog);
+/* the same for a step program outside the numbered ones, by name: "poly_g1_16", "poly_g1_256", "poly_g2_16", "poly_g2_256" (the Horner steps of nbls_g*_poly_eval, short and
+   full form); NULL for any other name */
+const char* nbls_extra_program_kernel(nbls_ctx* ctx, const char* name);
 int nbls_timing_enable(nbls_ctx* ctx, int on);
 int nbls_timing_read(nbls_ctx* ctx, float* ms /*[NBLS_N_PROGRAMS+1]*/, uint32_t* counts /*[NBLS_N_PROGRAMS+1]*/);
 

@@ -75,6 +75,12 @@
   X(5, miller_ls2, P_MILLER_FE_LS2, P_MILLER_RAW_LS2, P_MILLER_BYTES_LS2, P_COUNT)                    \
   X(6, g2pt_ls2, P_H2C_C1_LS2, P_H2C_C2_LS2, P_G2_MUL_SAC_LS2, P_COUNT)
 
+// Kernels of the programs outside ProgId (programs.h ExtraProg): X(part, kernel name, two ExtraProgs it serves; XP_COUNT = none).  The Horner steps of nbls_g*_poly_eval, each
+// kernel serving the short and the full form of its group.
+#define NBLS_AOT_EXTRA_KERNELS(X)                \
+  X(1, poly_g1, XP_POLY_G1_16, XP_POLY_G1_256)  \
+  X(7, poly_g2, XP_POLY_G2_16, XP_POLY_G2_256)
+
 namespace nbls {
 
 // K_DOT flags of a signature
@@ -130,6 +136,7 @@ std::string aot_translate_with(const Program& p, AotProgram& out, const AotLayou
 // kernel side (aot_kernel.hip)
 extern "C" const char* nbls_aot_name(int k);   // "nbls_aot_<name>" of kernel k
 extern "C" int nbls_aot_index(int prog_id);   // index of the ahead-of-time kernel that serves a ProgId, or -1
+extern "C" int nbls_aot_extra_index(int extra_prog);   // the same for an ExtraProg
 // remap the signature indices of a translated program to kernel k's table: 0, or -1 when a signature is not in the table
 extern "C" int nbls_aot_bind(int k, nbls::AotProgram* ap);
 extern "C" int nbls_aot_launch(int k, const nbls::AotArgs* a, unsigned lds_bytes, void* stream);

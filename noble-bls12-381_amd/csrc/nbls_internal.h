@@ -1,5 +1,5 @@
 // nbls_internal.h -- what the translation units of the runtime share (runtime.cpp / tuning.cpp / pipelines_pairing.cpp / pipelines_codec.cpp / pipelines_verify.cpp /
-// pipelines_multi_verify.cpp / pipelines_threshold.cpp; pool and multi-device handles: nbls_multi.cpp): the context, the map of its scratch slots (enum Slot: the one place that says which chain owns
+// pipelines_multi_verify.cpp / pipelines_threshold.cpp / pipelines_poly.cpp; pool and multi-device handles: nbls_multi.cpp): the context, the map of its scratch slots (enum Slot: the one place that says which chain owns
 // which slot, checked at compile time), the launch helpers and the device-side pipelines the exported entry points are built from.  Internal functions have hidden visibility
 // (csrc/Makefile: -fvisibility=hidden).
 #pragma once
@@ -45,6 +45,11 @@ extern "C" int nbls_fr_lagrange_launch(unsigned n, unsigned ngroups, const void*
 extern "C" int nbls_fr_combine_status_launch(unsigned ngroups, unsigned out_bytes, const void* bad_group, const void* first_bad, const void* st, const void* zero, void* out,
                                              void* status, void* stream);
 extern "C" int nbls_fr_group_status_launch(unsigned ngroups, const void* bad_group, void* status, void* stream);
+// poly_kernels.hip
+extern "C" int nbls_poly_group_launch(unsigned n, unsigned ngroups, const void* off, void* group_of, void* stream);
+extern "C" int nbls_poly_coef_launch(size_t items, unsigned elem_bytes, unsigned j, const void* group_of, const void* coff, const void* ident, const void* pts, void* dst, void* stream);
+extern "C" int nbls_poly_status_launch(unsigned n, unsigned out_bytes, const void* group_of, const void* first_bad, const void* st, const void* zero, void* out, void* status,
+                                       void* stream);
 extern "C" int nbls_msm_keys_launch(unsigned n, unsigned nwin, const void* scalars, void* keys, void* vals, void* stream);
 extern "C" int nbls_msm_decompose_launch(unsigned n, unsigned dims, const void* scalars, void* out, void* stream);
 extern "C" int nbls_msm_sac_launch(unsigned n, const void* scalars, void* out, void* stream);
@@ -101,9 +106,12 @@ enum Slot {
   // combine_pipeline (pipelines_threshold.cpp): the decoded shares and their statuses | identifiers and coefficients in Montgomery form, groups, flags, the canonical
   // coefficients | the affine sums, what is read back | SEG_THR: one sum per group
   SB_THR_SHARES = 51, SB_THR_SCALARS = 52, SB_THR_OUT = 53, SB_THR_POINTS = 54, SB_THR_LABELS = 55, SB_THR_SUMS = 56,
+  // poly_pipeline (pipelines_poly.cpp): the decoded coefficients, their statuses and raw projective forms | groups, ranks, first bad positions, the group of every identifier |
+  // one slab: accumulators, norms, inverses, affine points, zero flags | one slab: the step's coefficient of every item | the compressed results and statuses (what is read back)
+  SB_POLY_COEFS = 57, SB_POLY_LABELS = 58, SB_POLY_ACC = 59, SB_POLY_STEP = 60, SB_POLY_OUT = 61,
   NSB
 };
-static_assert(NSB == 57, "sb[] indices do not shift");
+static_assert(NSB == 62, "sb[] indices do not shift");
 constexpr uint64_t slot_bit(int i) { return (uint64_t)1 << i; }
 template <typename... S> constexpr uint64_t slots(S... s) { return (slot_bit(s) | ...); }
 // one instance of dev_decompress: three arrays of field elements and the exponentiation table
@@ -129,6 +137,7 @@ constexpr uint64_t M_RLC_MAIN = slots(SB_STAGED, SB_UNIFORM, SB_RLC_WEIGHTS, SB_
 constexpr uint64_t M_RLC_SIDE2 = DEC_KEYS.mask() | slots(SB_AGG_DECODED, SB_RLC_KEYS_PROJ, SB_RLC_KEYS_NORM, SB_RLC_KEYS_INV) | SEG_AGG.mask() | SEG_GRP.mask();   // its key chain
 constexpr uint64_t M_RLC_SIDE = DEC_SIGS.mask() | MSM_RLC.mask();                                           // its signature chain
 constexpr uint64_t M_THR_OWN = slots(SB_STAGED, SB_THR_SHARES, SB_THR_SCALARS, SB_THR_OUT) | SEG_THR.mask();   // combine_pipeline: what outlives the stages it calls
+constexpr uint64_t M_POLY_OWN = slots(SB_STAGED, SB_POLY_COEFS, SB_POLY_LABELS, SB_POLY_ACC, SB_POLY_STEP, SB_POLY_OUT);   // poly_pipeline: what outlives the decoder it calls
 // what runs side by side
 static_assert(!(M_VB_MAIN & DEC_KEYS.mask()), "verifyBatch decodes its keys (side2, or the sub-batch's own stream) beside the hash chain");
 static_assert(!(M_RLC_MAIN & M_RLC_SIDE2) && !(M_RLC_MAIN & M_RLC_SIDE) && !(M_RLC_SIDE & M_RLC_SIDE2), "verify_multiple_pipeline: the chains on s, side and side2 run side by side");
@@ -136,6 +145,9 @@ static_assert(!(SEG_AGG.mask() & SEG_GRP.mask()), "the per-message sums follow t
 static_assert(!(slot_bit(SB_MSGS) & (M_HASH_G2 | M_LADDER)), "sign_points: the keys are recoded on side2 beside the hash chain, and the digits outlive it until the ladder has read them");
 static_assert(!(slot_bit(SB_VB_PAIRS) & MSM_MAIN.mask()), "verifyBatch keeps its pairs across the calls of its two-stage route: dev_msm on the main slots must not regrow them");
 static_assert(!(M_THR_OWN & (DEC_MAIN.mask() | M_LADDER)), "combine_pipeline: the decoder and the ladder regrow their own slots between the stages that read the shares and the coefficients");
+static_assert(!(M_POLY_OWN & DEC_MAIN.mask()), "poly_pipeline: the decoder regrows its own slots while the staged coefficients and the decoded points are held");
+static_assert(!((M_POLY_OWN & ~slot_bit(SB_STAGED)) & (M_THR_OWN | M_RLC_MAIN | M_RLC_SIDE | M_RLC_SIDE2 | M_VB_MAIN | M_LADDER | MSM_MAIN.mask())),
+              "poly_pipeline keeps to slots of its own: no other chain's buffers are regrown or overwritten by it");
 // ---- END scratch slots -------------------------------------------------------------------------------------------------------------------------------------
 #define EXPORT extern "C" __attribute__((visibility("default")))
 extern std::recursive_mutex g_null_mu;   // locked in place of a context's mutex when the caller passed no context (the call then fails with NBLS_EINVAL)
@@ -158,6 +170,8 @@ struct nbls_ctx {
   DevProgram prog[P_COUNT];
   std::vector<uint8_t> dst_host; uint8_t* dst_dev = nullptr;   // hash-to-curve domain-separation tag last used by nbls_verify_batch_msgs_dev, and its device copy
   std::map<std::tuple<int, int, int, int>, DevProgram> tower;   // single tower operations (nbls_tower_op_batch), uploaded on first use
+  DevProgram extra[XP_COUNT];   // the programs outside ProgId (programs.h ExtraProg), uploaded on first use with their ahead-of-time kernels
+  size_t poly_slab = 0;         // nbls_set_tuning(NBLS_TUNE_POLY_SLAB): identifiers per slab of nbls_g*_poly_eval; 0 = the default (pipelines_poly.cpp)
   // scratch (device)
   uint8_t *F = nullptr, *N = nullptr, *NI = nullptr, *io_g1 = nullptr, *io_g2 = nullptr, *io_f12 = nullptr, *one12 = nullptr;
   uint8_t* T[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // t1..t7 of the final exponentiation, raw Fp12
@@ -317,6 +331,7 @@ bool checked_mode();
 bool aot_enabled();
 int upload_program(nbls_ctx* ctx, DevProgram& d, const Program& p, const int k);
 int upload(nbls_ctx* ctx, ProgId id);
+int upload_extra(nbls_ctx* ctx, ExtraProg id);
 void free_program(DevProgram& d);
 bool wide_applies(const nbls_ctx* ctx, const DevProgram& d, int id, size_t n);
 hipEvent_t timing_event(nbls_ctx* ctx);

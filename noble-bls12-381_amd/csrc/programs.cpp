@@ -886,6 +886,39 @@ const Program* get_tower_program(int field, int op, int param, int part) {
   return it->second.steps.empty() ? nullptr : &it->second;
 }
 
+// ---------------------------------------------------------------- programs outside ProgId (programs.h ExtraProg)
+// The Horner step: the ladders' windowed form (2-bit windows: the table of four keeps the LDS image small) on a PROJECTIVE base, then one complete addition.  Every case the
+// caller can produce is covered by the complete formulas: an identity accumulator (the table is identities, the result is A), an identity coefficient, [x]acc = -A (the
+// identity comes out) and [x]acc = A (the addition doubles).
+static Program build_extra(ExtraProg id) {
+  Builder B;
+  if (env_int("NBLS_AOT_SHARED_CONSTS", 1)) B.shared_consts = 1;
+  const bool g2 = id == XP_POLY_G2_16 || id == XP_POLY_G2_256, low16 = id == XP_POLY_G1_16 || id == XP_POLY_G2_16;
+  // the short form loads the identifier's last four bytes and tests bits 0 .. 15 of them: bytes 0 .. 29 never reach the result
+  const SFp k = low16 ? input_raw(2, 28, 4) : input_raw(2, 0, 32);
+  const int nbits = low16 ? 16 : 256;
+  if (!g2) {
+    auto ld = [&](int buf) { return Pt<SFp>{inputw(buf, 0), inputw(buf, 48), inputw(buf, 96)}; };
+    Pt<SFp> r = pt_add(pt_mul_ladder(ld(3), k, nbits, 2), ld(4));
+    outputw(r.x, 3, 0); outputw(r.y, 3, 48); outputw(r.z, 3, 96);
+    B.sched_window = env_int("NBLS_G1MUL_WINDOW", 200);   // as P_G1_MUL: the scalar bits (and here the coefficient) are fetched just in time
+    return B.compile(low16 ? "poly_g1_16" : "poly_g1_256", G1MUL_W);
+  }
+  auto ld = [&](int buf) { return Pt<SFp2>{{inputw(buf, 0), inputw(buf, 48)}, {inputw(buf, 96), inputw(buf, 144)}, {inputw(buf, 192), inputw(buf, 240)}}; };
+  Pt<SFp2> r = pt_add(pt_mul_ladder(ld(3), k, nbits, 2), ld(4));
+  outputw(r.x.c0, 3, 0); outputw(r.x.c1, 3, 48); outputw(r.y.c0, 3, 96); outputw(r.y.c1, 3, 144); outputw(r.z.c0, 3, 192); outputw(r.z.c1, 3, 240);
+  B.sched_window = env_int("NBLS_MUL_WINDOW", 300);
+  return B.compile(low16 ? "poly_g2_16" : "poly_g2_256", G2MUL_W);
+}
+const Program& get_extra_program(ExtraProg id) {
+  static Program cache[XP_COUNT];
+  static bool built[XP_COUNT];
+  static std::mutex mu;
+  std::lock_guard<std::mutex> g(mu);
+  if (!built[id]) { cache[id] = build_extra(id); built[id] = true; }
+  return cache[id];
+}
+
 const Program& get_program(ProgId id) {
   static Program cache[P_COUNT];
   static bool built[P_COUNT];

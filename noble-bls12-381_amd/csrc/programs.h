@@ -104,5 +104,11 @@ const Program& get_program(ProgId id);
 // Buffers: 0 a, 1 b, 2 c, 3 d (wire bytes, 48 * field each; b / c / d of a sparse product are Fp2), 7 out; inversions: 4 the Fp element to invert (raw), 5 its inverse (raw).
 // Returns nullptr for a combination the reference does not have.
 const Program* get_tower_program(int field, int op, int param, int part);
+// Product programs OUTSIDE ProgId (the enum's length is part of what the test-suite pins): built on first use, kept per context beside the tower programs, with ahead-of-time
+// kernels of their own (aot.h NBLS_AOT_EXTRA_KERNELS).  One Horner step of a commitment polynomial in the exponent (pipelines_poly.cpp): accumulator (buf 3: raw projective, in
+// place), identifier x (buf 2: 32 bytes big-endian, any value), the step's coefficient (buf 4: raw projective) -> acc = [x]acc + A.  The _16 forms read the low 16 bits of the
+// identifier (16 doublings instead of 256); the accumulator lies in the order-r subgroup, so the _256 forms take any 256-bit value as P_G1_MUL does.
+enum ExtraProg { XP_POLY_G1_16 = 0, XP_POLY_G1_256, XP_POLY_G2_16, XP_POLY_G2_256, XP_COUNT };
+const Program& get_extra_program(ExtraProg id);
 void print_stats(const Program& p);
 }  // namespace nbls

@@ -21,6 +21,11 @@ int upload(nbls_ctx* ctx, ProgId id) {
   if (d.p) return NBLS_OK;
   return upload_program(ctx, d, get_program(id), aot_enabled() ? nbls_aot_index((int)id) : -1);
 }
+int upload_extra(nbls_ctx* ctx, ExtraProg id) {
+  DevProgram& d = ctx->extra[id];
+  if (d.p) return NBLS_OK;
+  return upload_program(ctx, d, get_extra_program(id), aot_enabled() ? nbls_aot_extra_index((int)id) : -1);
+}
 // k: index of the ahead-of-time kernel that serves the program, or -1
 void free_program(DevProgram& d) {
   for (void* p : {(void*)d.steps, (void*)d.descs, (void*)d.consts, (void*)d.aot_steps, (void*)d.aot_descs}) if (p) hipFree(p);
@@ -340,6 +345,7 @@ EXPORT void nbls_destroy(nbls_ctx* ctx) {
   hipSetDevice(ctx->device);
   if (ctx->dst_dev) hipFree(ctx->dst_dev);
   for (auto& kv : ctx->tower) free_program(kv.second);
+  for (DevProgram& d : ctx->extra) free_program(d);
   for (auto& d : ctx->prog) free_program(d);
   for (uint8_t* p : {ctx->F, ctx->N, ctx->NI, ctx->io_g1, ctx->io_g2, ctx->io_f12, ctx->one12, ctx->gen_g1, ctx->g1_fixed, ctx->side_scratch, ctx->L, ctx->partial, ctx->unit_lines, ctx->KS,
       ctx->KD, ctx->Kflag, (uint8_t*)ctx->Klist, (uint8_t*)ctx->Kcount}) if (p) hipFree(p);

@@ -85,6 +85,8 @@ struct Pend { u32 dst; u32 v[NL]; };
   }
 #define SIM_ROW(ID, KIND, P0, FLAGS, T, SH0, SH1, CNT) {KIND, P0, FLAGS, T, SH0, SH1},
 NBLS_AOT_KERNELS(SIM_TABLE)
+#define SIM_TABLE_EXTRA(PART, NAME, E0, E1) SIM_TABLE(PART, NAME, E0, E1, E0, E1)
+NBLS_AOT_EXTRA_KERNELS(SIM_TABLE_EXTRA)   // the kernels of the programs outside ProgId (programs.h ExtraProg)
 // lane-split kernels (aot.h NBLS_AOT_LS_KERNELS): the same bodies with LS = 4.  The device sums the columns of the four sub-lanes of a lane-op with two DPP stages
 // (lane i <- v[i] + v[i+1] + v[i+2] + v[i+3] inside rows of 16 lanes); here the lanes of a step are visited from 63 down to 0, every lane leaves its columns in
 // g_ls_cols before it takes the sum, so the three partners of a sub-lane 0 are already there.
@@ -108,14 +110,17 @@ struct SimKernel { int prog_id[4]; SimStepFn fn; const AotSig* sigs; unsigned ns
 #define SIM_ENTRY(PART, NAME, Q0, Q1, Q2, Q3) {{(int)Q0, (int)Q1, (int)Q2, (int)Q3}, sim_step_##NAME, sim_sigs_##NAME, (unsigned)(sizeof(sim_sigs_##NAME) / sizeof(AotSig)), 0},
 #define SIM_ENTRY_LS(PART, NAME, Q0, Q1, Q2, Q3) {{(int)Q0, (int)Q1, (int)Q2, (int)Q3}, sim_step_##NAME, sim_sigs_##NAME, (unsigned)(sizeof(sim_sigs_##NAME) / sizeof(AotSig)), 4},
 #define SIM_ENTRY_LS2(PART, NAME, Q0, Q1, Q2, Q3) {{(int)Q0, (int)Q1, (int)Q2, (int)Q3}, sim_step_##NAME, sim_sigs_##NAME, (unsigned)(sizeof(sim_sigs_##NAME) / sizeof(AotSig)), 2},
-static const SimKernel g_sim_kernels[] = {NBLS_AOT_KERNELS(SIM_ENTRY) NBLS_AOT_LS_KERNELS(SIM_ENTRY_LS) NBLS_AOT_LS2_KERNELS(SIM_ENTRY_LS2)};
+// an ExtraProg is entered as P_COUNT + 1 + its number, as in aot_kernel.hip
+#define SIM_XP(E) ((int)E == (int)XP_COUNT ? (int)P_COUNT : (int)P_COUNT + 1 + (int)E)
+#define SIM_ENTRY_EXTRA(PART, NAME, E0, E1) {{SIM_XP(E0), SIM_XP(E1), (int)P_COUNT, (int)P_COUNT}, sim_step_##NAME, sim_sigs_##NAME, (unsigned)(sizeof(sim_sigs_##NAME) / sizeof(AotSig)), 0},
+static const SimKernel g_sim_kernels[] = {NBLS_AOT_KERNELS(SIM_ENTRY) NBLS_AOT_LS_KERNELS(SIM_ENTRY_LS) NBLS_AOT_LS2_KERNELS(SIM_ENTRY_LS2) NBLS_AOT_EXTRA_KERNELS(SIM_ENTRY_EXTRA)};
 static int g_sim_aot = 0;
 // 0: ran; -2: the program has no ahead-of-time kernel; -3: its signatures are not in the kernel's table
-static int sim_run_aot(int prog, unsigned n_items, const IOBuf* bufs) {
+// key: a ProgId, or P_COUNT + 1 + an ExtraProg
+static int sim_run_aot_program(int key, const Program& p, unsigned n_items, const IOBuf* bufs) {
   const SimKernel* K = nullptr;
-  if (prog >= 0 && prog < (int)P_COUNT) for (auto& k : g_sim_kernels) for (int j = 0; j < 4; j++) if (k.prog_id[j] == prog) K = &k;
+  if (key >= 0 && key != (int)P_COUNT) for (auto& k : g_sim_kernels) for (int j = 0; j < 4; j++) if (k.prog_id[j] == key) K = &k;
   if (!K) return -2;
-  const Program& p = get_program((ProgId)prog);
   AotProgram ap;
   if (!aot_translate(p, ap).empty()) return -3;
   std::vector<unsigned> map(ap.sigs.size());
@@ -141,6 +146,10 @@ static int sim_run_aot(int prog, unsigned n_items, const IOBuf* bufs) {
     }
   }
   return 0;
+}
+static int sim_run_aot(int prog, unsigned n_items, const IOBuf* bufs) {
+  if (prog < 0 || prog >= (int)P_COUNT) return -2;
+  return sim_run_aot_program(prog, get_program((ProgId)prog), n_items, bufs);
 }
 
 // The one-limb-per-lane form (pow_wide.h) on the host: a value of type U is the array of the 32 lanes of a wavefront's first two rows, every cross-lane move a loop.  The
@@ -297,6 +306,26 @@ __attribute__((visibility("default"))) int nbls_sim_run(int prog, unsigned n_ite
   if (g_sim_wide) { const int r = sim_run_wide(get_program((ProgId)prog), n_items, b); if (r != -4) return r; }
   if (g_sim_aot) { const int r = sim_run_aot(prog, n_items, b); if (r != -2) return r; }
   sim_run(get_program((ProgId)prog), n_items, b);
+  return 0;
+}
+// The programs outside ProgId (programs.h ExtraProg; nbls_sim_run refuses everything from P_COUNT on): count, name, the static verifier (0 = passed; the message goes to
+// stderr), and a run -- aot = 0: the interpreter's semantics; 1: the translated form on the step bodies of the program's ahead-of-time kernel (-2: it has none, -3: its
+// signatures are not in the kernel's table)
+__attribute__((visibility("default"))) int nbls_sim_extra_count(void) { return (int)XP_COUNT; }
+__attribute__((visibility("default"))) const char* nbls_sim_extra_name(int xp) { return xp >= 0 && xp < (int)XP_COUNT ? get_extra_program((ExtraProg)xp).name.c_str() : nullptr; }
+__attribute__((visibility("default"))) int nbls_sim_extra_verify(int xp) {
+  if (xp < 0 || xp >= (int)XP_COUNT) return -1;
+  const std::string e = verify_program(get_extra_program((ExtraProg)xp));
+  if (!e.empty()) fprintf(stderr, "nbls_sim_extra_verify: %s\n", e.c_str());
+  return e.empty() ? 0 : 1;
+}
+__attribute__((visibility("default"))) int nbls_sim_extra_run(int xp, int aot, unsigned n_items, uint8_t** ptrs, const uint64_t* strides) {
+  if (xp < 0 || xp >= (int)XP_COUNT) return -1;
+  IOBuf b[MAX_BUFS];
+  for (int i = 0; i < MAX_BUFS; i++) { b[i].ptr = ptrs[i]; b[i].stride = strides[i]; }
+  const Program& p = get_extra_program((ExtraProg)xp);
+  if (aot) return sim_run_aot_program((int)P_COUNT + 1 + xp, p, n_items, b);
+  sim_run(p, n_items, b);
   return 0;
 }
 // out = in^-1 on raw elements (16 words each): the same fp_mont_inverse routine the inversion kernel runs per lane

@@ -75,6 +75,8 @@ def load_library():
     lib.nbls_lagrange_at_zero.argtypes = [vp, sz, vp, vp, vp, vp]
     lib.nbls_g2_combine_shares.argtypes = [vp, sz, vp, vp, vp, vp, vp]
     lib.nbls_g1_combine_shares.argtypes = [vp, sz, vp, vp, vp, vp, vp]
+    lib.nbls_g1_poly_eval.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp]
+    lib.nbls_g2_poly_eval.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp]
     lib.nbls_keyset_create.argtypes = [vp, sz, vp, vp, C.POINTER(vp)]
     lib.nbls_keyset_destroy.argtypes = [vp]
     lib.nbls_keyset_destroy.restype = None
@@ -117,6 +119,8 @@ def load_library():
     lib.nbls_pool_synchronize.argtypes = [vp]
     lib.nbls_program_kernel.restype = C.c_char_p
     lib.nbls_program_kernel.argtypes = [vp, i32]
+    lib.nbls_extra_program_kernel.restype = C.c_char_p
+    lib.nbls_extra_program_kernel.argtypes = [vp, C.c_char_p]
     if lib.nbls_abi_version() != ABI_VERSION:
         raise NblsError('libnbls.so has ABI %d, this binding is written for ABI %d (rebuild: make -C noble-bls12-381_amd/csrc)' % (lib.nbls_abi_version(), ABI_VERSION))
     if not PROGRAMS:
@@ -432,6 +436,24 @@ class Engine:
         raw = out.raw
         return [raw[e * g:e * g + e] for g in range(m)], list(st.raw[:m])
 
+    def poly_eval(self, groups, g2=False):
+        """Share public keys from commitment polynomials (include/nbls.h nbls_g*_poly_eval).  groups: a list of (coefs, ids): the t compressed coefficients A_j = [a_j]G of one
+        polynomial, lowest degree first (48-byte G1 points, or with g2=True 96-byte G2 points), and the identifiers to evaluate it at (ints or 32-byte values, any value)
+        -> (per group the list of compressed F(x_k) = sum_j [x_k^j]A_j, per group the status list: 0, 1 = the zero point (0xc0 00..), 3 / 4 = the group's first coefficient that
+        does not decode, with all-zero bytes)"""
+        e = 96 if g2 else 48
+        for coefs, ids in groups:
+            if not len(coefs) or not len(ids) or any(len(x) != e for x in coefs):
+                raise NblsError('poly_eval: every group needs at least one %d-byte coefficient and one identifier' % e)
+        coffs, _ = self._groups([len(g[0]) for g in groups], [])
+        ioffs, ids = self._groups([len(g[1]) for g in groups], [g[1] for g in groups])
+        m, n = len(groups), ioffs[len(groups)]
+        out = C.create_string_buffer(max(e * n, 1)); st = C.create_string_buffer(max(n, 1))
+        f = self.lib.nbls_g2_poly_eval if g2 else self.lib.nbls_g1_poly_eval
+        self._chk(f(self.h, m, coffs, b''.join(bytes(x) for g in groups for x in g[0]), ioffs, ids, out, st))
+        raw, sraw = out.raw, st.raw
+        return ([[raw[e * k:e * k + e] for k in range(ioffs[g], ioffs[g + 1])] for g in range(m)], [list(sraw[ioffs[g]:ioffs[g + 1]]) for g in range(m)])
+
     def get_public_keys(self, keys):
         """getPublicKey for a batch of private keys -> list of 48-byte compressed keys; raises like the reference on a zero key"""
         aff, st = self.point_mul_batch(keys)
@@ -660,6 +682,10 @@ class Engine:
         """items up to which the G2 point chains of verify / sign run in their two-lane forms (NBLS_TUNE_PT_LS2_MAX; default 4096, 0: never)"""
         self._chk(self.lib.nbls_set_tuning(self.h, 9, n))
 
+    def set_poly_slab(self, n):
+        """identifiers that poly_eval works through at a time (NBLS_TUNE_POLY_SLAB = 15; default 2^18, 0: the default)"""
+        self._chk(self.lib.nbls_set_tuning(self.h, 15, int(n)))
+
     def set_verify_pipeline(self, chunks=None, last_pct=None, pipe_min=None):
         """verifyBatch as a software pipeline (NBLS_TUNE_VERIFY_CHUNKS / _LAST_PCT / _PIPE_MIN): number of chunks (0 / 1: one), size of the last chunk in
         per cent of the batch, signatures from which a call is chunked at all"""
@@ -681,6 +707,13 @@ class Engine:
         k = self.lib.nbls_program_kernel(self.h, PROGRAMS.index(name))
         if k is None:
             raise NblsError('nbls_program_kernel(%s) failed' % name)
+        return k.decode()
+
+    def extra_program_kernel(self, name):
+        """the same for a program outside PROGRAMS, by name: 'poly_g1_16', 'poly_g1_256', 'poly_g2_16', 'poly_g2_256' (the Horner steps of poly_eval)"""
+        k = self.lib.nbls_extra_program_kernel(self.h, name.encode())
+        if k is None:
+            raise NblsError('nbls_extra_program_kernel(%s) failed' % name)
         return k.decode()
 
     def kernel_bindings(self):

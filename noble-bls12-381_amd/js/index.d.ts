@@ -76,6 +76,11 @@ export declare class PointG1 {
   static combineShares(shares: PointG1[], ids: ShareId[]): Promise<PointG1>;
   static combineShares(shares: Hex[], ids: ShareId[]): Promise<Uint8Array>;
   static combineSharesBatch(groups: ShareGroup<PointG1>[]): Promise<(PointG1 | Uint8Array)[]>;
+  /** share public keys on the GPU: the commitment polynomial F(x) = sum_j [x^j]A_j of a DKG / Feldman VSS (coefficients lowest degree first, A_0 = the group key) at the
+   *  identifiers (any value below 2^256, zero included).  Compressed coefficients (bytes or hex) give bytes, points give points.  Throws Error on a coefficient that does not decode. */
+  static evalCommitment(coefs: PointG1[], ids: ShareId[]): Promise<PointG1[]>;
+  static evalCommitment(coefs: Hex[], ids: ShareId[]): Promise<Uint8Array[]>;
+  static evalCommitmentBatch(groups: CommitmentGroup<PointG1>[]): Promise<(PointG1[] | Uint8Array[])[]>;
   isZero(): boolean; equals(rhs: PointG1): boolean; negate(): PointG1; add(rhs: PointG1): PointG1; subtract(rhs: PointG1): PointG1; double(): PointG1;
   multiply(scalar: bigint | number): PointG1; multiplyUnsafe(scalar: bigint | number): PointG1; multiplyPrecomputed(scalar: bigint | number): PointG1;
   assertValidity(): this; toAffine(): [Fp, Fp]; toRawBytes(isCompressed?: boolean): Uint8Array; toHex(isCompressed?: boolean): string;
@@ -97,6 +102,11 @@ export declare class PointG2 {
   static combineShares(shares: PointG2[], ids: ShareId[]): Promise<PointG2>;
   static combineShares(shares: Hex[], ids: ShareId[]): Promise<Uint8Array>;
   static combineSharesBatch(groups: ShareGroup<PointG2>[]): Promise<(PointG2 | Uint8Array)[]>;
+  /** share public keys on the GPU: the commitment polynomial F(x) = sum_j [x^j]A_j of a DKG / Feldman VSS (coefficients lowest degree first, A_0 = the group key) at the
+   *  identifiers (any value below 2^256, zero included).  Compressed coefficients (bytes or hex) give bytes, points give points.  Throws Error on a coefficient that does not decode. */
+  static evalCommitment(coefs: PointG2[], ids: ShareId[]): Promise<PointG2[]>;
+  static evalCommitment(coefs: Hex[], ids: ShareId[]): Promise<Uint8Array[]>;
+  static evalCommitmentBatch(groups: CommitmentGroup<PointG2>[]): Promise<(PointG2[] | Uint8Array[])[]>;
   isZero(): boolean; equals(rhs: PointG2): boolean; negate(): PointG2; add(rhs: PointG2): PointG2; subtract(rhs: PointG2): PointG2; double(): PointG2;
   multiply(scalar: bigint | number): PointG2; multiplyUnsafe(scalar: bigint | number): PointG2; multiplyPrecomputed(scalar: bigint | number): PointG2;
   assertValidity(): this; toAffine(): [Fp2, Fp2]; toSignature(): Uint8Array; toRawBytes(isCompressed?: boolean): Uint8Array; toHex(isCompressed?: boolean): string;
@@ -120,12 +130,16 @@ export declare function verifyMultipleAggregateSignatures(sets: { publicKeys: (H
 export type ShareId = bigint | number | string | Uint8Array;
 /** one group of combineSharesBatch: its shares are all points or all compressed bytes / hex */
 export type ShareGroup<P> = { shares: P[] | Hex[]; ids: ShareId[] } | [P[] | Hex[], ShareId[]];
+/** one group of evalCommitmentBatch: its coefficients are all points or all compressed bytes / hex */
+export type CommitmentGroup<P> = { coefs: P[] | Hex[]; ids: ShareId[] } | [P[] | Hex[], ShareId[]];
 /** what the addon's Fr and threshold calls take (nbls_fr_op_batch, nbls_lagrange_at_zero, nbls_g2_combine_shares / nbls_g1_combine_shares; a type only, the facade does not export
  * the addon): 32-byte big-endian elements, groupOffsets = groups + 1 entries; every call has a synchronous twin without the suffix */
 export interface NativeThresholdCalls {
   frOpAsync(op: number, a32: Uint8Array, b32: Uint8Array | null): Promise<{ out: Uint8Array; status: Uint8Array }>;
   lagrangeAtZeroAsync(groupOffsets: Uint32Array, ids32: Uint8Array): Promise<{ out: Uint8Array; status: Uint8Array }>;
   combineSharesAsync(g2: number, groupOffsets: Uint32Array, ids32: Uint8Array, shares: Uint8Array): Promise<{ out: Uint8Array; status: Uint8Array }>;
+  /** nbls_g1_poly_eval / nbls_g2_poly_eval: one compressed point and one status per identifier */
+  polyEvalAsync(g2: number, coefOffsets: Uint32Array, coefs: Uint8Array, idOffsets: Uint32Array, ids32: Uint8Array): Promise<{ out: Uint8Array; status: Uint8Array }>;
 }
 /** The two calls of the N-API addon (nbls_napi.node) that verifyMultipleSignatures / verifyMultipleAggregateSignatures take when at least two wire-format sets have equal messages:
  * msgs / offsets hold the distinct messages, set i signs message msgIndex[i] (nbls_verify_multiple_shared / nbls_verify_aggregates_shared; a type only, the facade does not export the addon) */

@@ -114,6 +114,42 @@ async function combineSharesBatch(Point, groups) {
   });
 }
 
+// ---- share public keys (nbls_g1_poly_eval / nbls_g2_poly_eval; not in the reference): the commitment polynomial of a DKG / Feldman VSS, F(x) = sum_j [x^j]A_j with the committed
+// coefficients A_j lowest degree first (A_0 = the group key), evaluated at the share identifiers -- any value below 2^256, zero included: F(0) = A_0 --, one call for all groups,
+// on a worker thread.  groups: [{ coefs, ids }] (or [coefs, ids] pairs).  A group of points yields points; of bytes or hex (compressed coefficients), bytes; a group that mixes
+// the two is refused.  Throws Error on a coefficient that does not decode, as the decoders do
+async function evalCommitmentBatch(Point, groups) {
+  const g2 = Point === PointG2, e = g2 ? 96 : 48, STATUS = g2 ? G2_STATUS : G1_STATUS;
+  if (!groups.length) throw new Error('Expected non-empty array');
+  const coffs = new Uint32Array(groups.length + 1), offs = new Uint32Array(groups.length + 1), ids = [], coefs = [], asPoint = [];
+  groups.forEach((grp, g) => {
+    const cf = Array.isArray(grp) ? grp[0] : grp.coefs, id = Array.isArray(grp) ? grp[1] : grp.ids;
+    if (!cf || !id || !cf.length || !id.length) throw new Error('Expected at least one coefficient and one identifier');
+    const points = cf.filter((p) => p instanceof Point).length;
+    if (points && points !== cf.length) throw new Error('Expected the coefficients of a group to be all points or all compressed bytes');
+    asPoint.push(points > 0);
+    for (const p of cf) {
+      const b = p instanceof Point ? (g2 ? p.toSignature() : p.toRawBytes(true)) : ensureBytes(p);
+      if (b.length !== e) throw new Error('Invalid coefficient: expected ' + e + ' compressed bytes');
+      coefs.push(b);
+    }
+    for (const x of id) ids.push(shareIdBytes(x));
+    coffs[g + 1] = coffs[g] + cf.length; offs[g + 1] = offs[g] + id.length;
+  });
+  ensureInit();
+  const { out, status } = await native.polyEvalAsync(g2 ? 1 : 0, coffs, concat(...coefs), offs, concat(...ids));
+  return groups.map((_, g) => {
+    const res = [];
+    for (let k = offs[g]; k < offs[g + 1]; k++) {
+      const st = status[k];
+      if (st > 1) throw new Error(STATUS[st] || 'Invalid coefficient (status ' + st + ')');
+      const bytes = out.slice(k * e, k * e + e);
+      res.push(!asPoint[g] ? bytes : st === 1 ? Point.ZERO : (g2 ? PointG2.fromSignature(bytes) : PointG1.fromHex(bytes)));
+    }
+    return res;
+  });
+}
+
 // Points are held as affine wire bytes (what the engine consumes) or as the zero point.  The reference's constructor form
 // new PointG1(x: Fp, y: Fp, z?: Fp) (index.ts:291) is accepted too: the projective triple is made affine on the host.
 class PointG1 {
@@ -228,6 +264,9 @@ class PointG1 {
   // t-of-n threshold shares -> the group's public key: sum_k [lambda_k]share_k (combineSharesBatch above)
   static async combineShares(shares, ids) { return (await combineSharesBatch(PointG1, [{ shares, ids }]))[0]; }
   static combineSharesBatch(groups) { return combineSharesBatch(PointG1, groups); }
+  // commitment polynomial (coefficients lowest degree first) -> the public keys of the shares with these identifiers (evalCommitmentBatch above)
+  static async evalCommitment(coefs, ids) { return (await evalCommitmentBatch(PointG1, [{ coefs, ids }]))[0]; }
+  static evalCommitmentBatch(groups) { return evalCommitmentBatch(PointG1, groups); }
   equals(rhs) { return this.zero === rhs.zero && (this.zero || bytesToHex(this.aff) === bytesToHex(rhs.aff)); }
   // reference index.ts:359-381
   toHex(isCompressed = false) {
@@ -374,6 +413,9 @@ class PointG2 {
   // t-of-n threshold shares -> the group's signature: sum_k [lambda_k]share_k (combineSharesBatch above)
   static async combineShares(shares, ids) { return (await combineSharesBatch(PointG2, [{ shares, ids }]))[0]; }
   static combineSharesBatch(groups) { return combineSharesBatch(PointG2, groups); }
+  // the same for schemes whose keys live in G2 (evalCommitmentBatch above)
+  static async evalCommitment(coefs, ids) { return (await evalCommitmentBatch(PointG2, [{ coefs, ids }]))[0]; }
+  static evalCommitmentBatch(groups) { return evalCommitmentBatch(PointG2, groups); }
   equals(rhs) { return this.zero === rhs.zero && (this.zero || bytesToHex(this.aff) === bytesToHex(rhs.aff)); }
   // reference index.ts:586-598
   toSignature() {

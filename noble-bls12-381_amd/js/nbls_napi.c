@@ -2,7 +2,7 @@
  * nbls_napi.c -- thin N-API addon: exposes the C ABI of libnbls.so (include/nbls.h) to Node.  No arithmetic here.
  * libnbls.so is loaded with dlopen at module init so the addon builds with plain gcc (no HIP needed):
  *     gcc -shared -fPIC -I/usr/include/node -I../../include nbls_napi.c -o nbls_napi.node -ldl
- * Calls are synchronous (they block for the duration of the GPU work) except verifyBatchAsync (and signBatchAsync, verifyMultipleAsync, verifyAggregatesAsync, verifyMultipleSharedAsync, verifyAggregatesSharedAsync, frOpAsync, lagrangeAtZeroAsync, combineSharesAsync), which runs on a libuv worker thread
+ * Calls are synchronous (they block for the duration of the GPU work) except verifyBatchAsync (and signBatchAsync, verifyMultipleAsync, verifyAggregatesAsync, verifyMultipleSharedAsync, verifyAggregatesSharedAsync, frOpAsync, lagrangeAtZeroAsync, combineSharesAsync, polyEvalAsync), which runs on a libuv worker thread
  * (napi_create_async_work) and resolves a Promise: the facade's verifyBatch uses it for wire-format inputs (the calls that can take tens of milliseconds).  Typed arrays are passed by reference (napi_get_typedarray_info), no copies.
  */
 #include <node_api.h>
@@ -21,7 +21,7 @@ SYM(nbls_hash_to_g2_batch) SYM(nbls_g1_sum) SYM(nbls_g2_sum) SYM(nbls_verify_bat
 SYM(nbls_init_multi) SYM(nbls_destroy_multi) SYM(nbls_multi_device_count) SYM(nbls_multi_context) SYM(nbls_multi_pairing_batch) SYM(nbls_multi_miller_product) SYM(nbls_multi_verify_batch)
 SYM(nbls_g2_prepare) SYM(nbls_pairing_prepared) SYM(nbls_verify_multiple) SYM(nbls_verify_aggregates) SYM(nbls_verify_multiple_shared) SYM(nbls_verify_aggregates_shared)
 SYM(nbls_g1_from_hex_batch) SYM(nbls_g2_from_hex_batch) SYM(nbls_g2_from_signature_batch) SYM(nbls_g1_clear_cofactor_batch) SYM(nbls_g2_clear_cofactor_batch)
-SYM(nbls_fr_op_batch) SYM(nbls_lagrange_at_zero) SYM(nbls_g2_combine_shares) SYM(nbls_g1_combine_shares)
+SYM(nbls_fr_op_batch) SYM(nbls_lagrange_at_zero) SYM(nbls_g2_combine_shares) SYM(nbls_g1_combine_shares) SYM(nbls_g1_poly_eval) SYM(nbls_g2_poly_eval)
 static nbls_ctx* ctx;
 static nbls_multi* multi;   /* several GPUs behind one handle (initMulti): ctx is then its first context; the batch calls shard over all of them */
 #define MULTI() (multi && p_nbls_multi_device_count(multi) > 1)
@@ -425,15 +425,18 @@ static napi_value SignBatchAsync(napi_env env, napi_callback_info info) {
  *   frOp(op, a32, b32 | null)                          n = a32.length / 32 elements; status[i] = 5 where inv / div meets 0 mod r
  *   lagrangeAtZero(groupOffsets, ids32)                groupOffsets: Uint32Array of groups + 1 entries; out = one coefficient per identifier, status per group
  *   combineShares(g2, groupOffsets, ids32, shares)     g2 != 0: 96-byte signature shares, else 48-byte public-key shares; out = one compressed point per group, status per group
+ *   polyEval(g2, coefOffsets, coefs, idOffsets, ids32) nbls_g*_poly_eval: commitment polynomials (g2 != 0: 96-byte coefficients, else 48-byte ones, lowest degree first) at the
+ *                                                      identifiers of their groups; out = one compressed point per identifier, status per identifier
  * The offsets must name identifiers and shares that are in the arrays (checked here); the library checks the rest. */
 typedef struct {
   napi_async_work work; napi_deferred deferred; napi_ref refs[6]; int nrefs;
-  int kind /* 0 frOp, 1 lagrangeAtZero, 2 combineShares */, op, g2; const uint8_t *a, *b, *shares; const uint32_t* offs; size_t n; uint8_t* out; int8_t* st;
+  int kind /* 0 frOp, 1 lagrangeAtZero, 2 combineShares, 3 polyEval */, op, g2; const uint8_t *a, *b, *shares; const uint32_t *offs, *coffs; size_t n; uint8_t* out; int8_t* st;
   nbls_ctx* c; int rc;
 } thr_job;
 static void thr_execute(napi_env env, void* data) { thr_job* j = (thr_job*)data; (void)env;
   j->rc = j->kind == 0 ? p_nbls_fr_op_batch(j->c, j->op, j->n, j->a, j->b, j->out, j->st)
         : j->kind == 1 ? p_nbls_lagrange_at_zero(j->c, j->n, j->offs, j->a, j->out, j->st)
+        : j->kind == 3 ? (j->g2 ? p_nbls_g2_poly_eval : p_nbls_g1_poly_eval)(j->c, j->n, j->coffs, j->shares, j->offs, j->a, j->out, j->st)
         : (j->g2 ? p_nbls_g2_combine_shares : p_nbls_g1_combine_shares)(j->c, j->n, j->offs, j->a, j->shares, j->out, j->st); }
 static void thr_complete(napi_env env, napi_status status, void* data) {
   thr_job* j = (thr_job*)data;
@@ -502,6 +505,20 @@ static napi_value combine_call(napi_env env, napi_callback_info info, int async)
 }
 static napi_value CombineShares(napi_env env, napi_callback_info info) { return combine_call(env, info, 0); }
 static napi_value CombineSharesAsync(napi_env env, napi_callback_info info) { return combine_call(env, info, 1); }
+static napi_value poly_call(napi_env env, napi_callback_info info, int async) {
+  ARGS(5); NEED_CTX(); BYTES(1, coffs, lc); BYTES(2, coefs, lf); BYTES(3, offs, lo); BYTES(4, ids, li);
+  int32_t g2; if (napi_get_value_int32(env, argv[0], &g2) != napi_ok) { napi_throw_type_error(env, NULL, "expected 0 (G1) or 1 (G2)"); return NULL; }
+  const size_t e = g2 ? 96 : 48; size_t m, mc;
+  if (li % 32 || lf % e || !thr_offsets_ok(offs, lo, li / 32, &m) || !thr_offsets_ok(coffs, lc, lf / e, &mc) || mc != m) {
+    napi_throw_range_error(env, NULL, "bad coefficient or identifier offsets, coefficient or identifier array length"); return NULL; }
+  const size_t n = li / 32;
+  thr_job job; memset(&job, 0, sizeof job);
+  job.kind = 3; job.g2 = g2 != 0; job.coffs = (const uint32_t*)coffs; job.shares = coefs; job.offs = (const uint32_t*)offs; job.a = ids; job.n = m;
+  napi_value vo = new_u8(env, n ? n * e : 1, &job.out), vs = new_u8(env, n ? n : 1, (uint8_t**)&job.st); ALLOCATED(vo); ALLOCATED(vs);
+  return thr_run(env, &job, async, argv + 1, 4, vo, vs);
+}
+static napi_value PolyEval(napi_env env, napi_callback_info info) { return poly_call(env, info, 0); }
+static napi_value PolyEvalAsync(napi_env env, napi_callback_info info) { return poly_call(env, info, 1); }
 
 static napi_value ModuleInit(napi_env env, napi_value exports) {
   const char* path = getenv("NBLS_LIB");
@@ -515,7 +532,7 @@ static napi_value ModuleInit(napi_env env, napi_value exports) {
   LOAD(nbls_hash_to_g2_batch) LOAD(nbls_g1_sum) LOAD(nbls_g2_sum) LOAD(nbls_verify_batch) LOAD(nbls_g1_mul_batch) LOAD(nbls_g2_mul_batch) LOAD(nbls_sign_batch) LOAD(nbls_hash_to_g1_batch) LOAD(nbls_encode_to_g1_batch) LOAD(nbls_encode_to_g2_batch) LOAD(nbls_g1_msm) LOAD(nbls_g2_msm)
   LOAD(nbls_init_multi) LOAD(nbls_destroy_multi) LOAD(nbls_multi_device_count) LOAD(nbls_multi_context) LOAD(nbls_multi_pairing_batch) LOAD(nbls_multi_miller_product) LOAD(nbls_multi_verify_batch) LOAD(nbls_g2_prepare) LOAD(nbls_pairing_prepared) LOAD(nbls_verify_multiple) LOAD(nbls_verify_aggregates) LOAD(nbls_verify_multiple_shared) LOAD(nbls_verify_aggregates_shared)
   LOAD(nbls_g1_from_hex_batch) LOAD(nbls_g2_from_hex_batch) LOAD(nbls_g2_from_signature_batch) LOAD(nbls_g1_clear_cofactor_batch) LOAD(nbls_g2_clear_cofactor_batch)
-  LOAD(nbls_fr_op_batch) LOAD(nbls_lagrange_at_zero) LOAD(nbls_g2_combine_shares) LOAD(nbls_g1_combine_shares)
+  LOAD(nbls_fr_op_batch) LOAD(nbls_lagrange_at_zero) LOAD(nbls_g2_combine_shares) LOAD(nbls_g1_combine_shares) LOAD(nbls_g1_poly_eval) LOAD(nbls_g2_poly_eval)
   {   /* the ABI the addon was written against (include/nbls.h NBLS_ABI_VERSION): an older or newer library is refused at load instead of misread at run time */
     int (*abi)(void) = (int (*)(void))dlsym(lib, "nbls_abi_version");
     if (!abi || abi() != NBLS_ABI_VERSION) { napi_throw_error(env, NULL, "libnbls.so: ABI version differs from the one this addon was built for (include/nbls.h NBLS_ABI_VERSION)"); return exports; }
@@ -532,7 +549,8 @@ static napi_value ModuleInit(napi_env env, napi_value exports) {
     {"decodePoints", 0, DecodePoints, 0, 0, 0, napi_enumerable, 0}, {"clearCofactor", 0, ClearCofactor, 0, 0, 0, napi_enumerable, 0},
     {"frOp", 0, FrOp, 0, 0, 0, napi_enumerable, 0}, {"frOpAsync", 0, FrOpAsync, 0, 0, 0, napi_enumerable, 0}, {"lagrangeAtZero", 0, LagrangeAtZero, 0, 0, 0, napi_enumerable, 0},
     {"lagrangeAtZeroAsync", 0, LagrangeAtZeroAsync, 0, 0, 0, napi_enumerable, 0}, {"combineShares", 0, CombineShares, 0, 0, 0, napi_enumerable, 0},
-    {"combineSharesAsync", 0, CombineSharesAsync, 0, 0, 0, napi_enumerable, 0}};
+    {"combineSharesAsync", 0, CombineSharesAsync, 0, 0, 0, napi_enumerable, 0}, {"polyEval", 0, PolyEval, 0, 0, 0, napi_enumerable, 0},
+    {"polyEvalAsync", 0, PolyEvalAsync, 0, 0, 0, napi_enumerable, 0}};
   napi_define_properties(env, exports, sizeof d / sizeof d[0], d);
   return exports;
 }
