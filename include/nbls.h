@@ -167,11 +167,36 @@ int nbls_g2_mul_batch(nbls_ctx* ctx, size_t n, const uint8_t* g2_aff /* n*192 */
  * index.ts:771-788, whose unweighted sums are nbls_g1_sum / nbls_g2_sum; the building block of random-linear-combination batch
  * verification of distinct signatures).  Points: affine wire bytes in the prime-order subgroup (nbls_g*_validate_batch); scalars:
  * 32 bytes big-endian each, any value.  Bucket method (12-bit windows) on the device; NOT constant time in the scalars (public
- * coefficients), use nbls_g*_mul_batch for secret ones.  out: one affine point; status: 0 ok, 1 the sum is the zero point. */
+ * coefficients), use nbls_g*_mul_batch for secret ones.  out: one affine point; status: 0 ok, 1 the sum is the zero point (output
+ * then all-zero). */
 int nbls_g1_msm(nbls_ctx* ctx, size_t n, const uint8_t* pts96, const uint8_t* scalars32, uint8_t* out96, int8_t* status);
 int nbls_g2_msm(nbls_ctx* ctx, size_t n, const uint8_t* pts192, const uint8_t* scalars32, uint8_t* out192, int8_t* status);
 /* the same with points, scalars, result and status resident in device memory; all scalars < 2^nbits (0 = 256) */
 int nbls_msm_dev(nbls_ctx* ctx, int g2, size_t n, const void* d_pts, const void* d_scalars32, unsigned nbits, void* d_out, void* d_status, void* stream);
+/* Many independent sums in one call (no reference counterpart): weighted aggregates, Feldman / DKG batch checks, commitments of many polynomials to one basis.
+ *   _batch   out[g] = sum over i in [group_offsets[g], group_offsets[g + 1]) of [k_i]P_i: n_groups + 1 offsets into the point and the scalar array, NON-DECREASING -- an empty
+ *            group is a legitimate empty sum (status 1, as nbls_g*_msm with n = 0); the first offset need not be 0, the entries in front of it are not read.
+ *   _rows    n_rows scalar vectors against ONE set of n_pts points: out[r] = sum_j [k[r * n_pts + j]]P_j; the points are converted and split once, not n_rows times (unless n_pts is above
+ *            NBLS_TUNE_MSMB_BIG: every row is then a big group and runs through the pipeline of nbls_g*_msm, which converts the points again for each row).
+ * Points and scalars exactly as nbls_g*_msm takes them: affine wire bytes in the prime-order subgroup, NOT validated; 32 bytes big-endian, any value.  NOT constant time and not
+ * an interface for secrets (nothing is wiped; window width and scalar split depend on the scalars).  out[g]: affine wire bytes; status[g] (may be NULL): 0, or 1 when the sum is
+ * the zero point (output all-zero).  Every group's output and status are byte for byte what nbls_g*_msm returns for that group alone.
+ * One copy in, one chain on the context's stream, one copy out: conversion and GLV / GLS split of all points and scalars once, then the groups in slabs of whole groups
+ * (NBLS_TUNE_MSMB_SLAB bounds the scratch of a slab) through the bucket method with (group, window, digit) keys and a window width chosen per call from {4, 6, 8, 10, 12} by the
+ * mean group size (NBLS_TUNE_MSMB_WINDOW forces it); one doubling-and-add chain over the bit positions combines all groups of a slab at once.  A slab whose largest group has
+ * more than 8 points after the split reads its longest run back (4 bytes), as nbls_g*_msm does; a group of more than NBLS_TUNE_MSMB_BIG points, and a call of one group, run
+ * through the pipeline of nbls_g*_msm on the same stream.
+ * Returns NBLS_OK whatever the groups hold; NBLS_EINVAL before any device work for a missing pointer (points and scalars may be NULL only when the call holds none),
+ * n_groups = 0 or n_rows = 0, n_pts = 0 (an empty point set is refused: use _batch with empty groups), decreasing offsets, more than 2^22 points or scalars in the call, more
+ * than 2^20 groups or rows. */
+int nbls_g1_msm_batch(nbls_ctx* ctx, size_t n_groups, const uint32_t* group_offsets /* n_groups + 1 */, const uint8_t* pts96, const uint8_t* scalars32, uint8_t* out96 /* n_groups */,
+                      int8_t* status /* n_groups, may be NULL */);
+int nbls_g2_msm_batch(nbls_ctx* ctx, size_t n_groups, const uint32_t* group_offsets /* n_groups + 1 */, const uint8_t* pts192, const uint8_t* scalars32, uint8_t* out192 /* n_groups */,
+                      int8_t* status /* n_groups, may be NULL */);
+int nbls_g1_msm_rows(nbls_ctx* ctx, size_t n_pts, const uint8_t* pts96, size_t n_rows, const uint8_t* scalars32 /* n_rows * n_pts */, uint8_t* out96 /* n_rows */,
+                     int8_t* status /* n_rows, may be NULL */);
+int nbls_g2_msm_rows(nbls_ctx* ctx, size_t n_pts, const uint8_t* pts192, size_t n_rows, const uint8_t* scalars32 /* n_rows * n_pts */, uint8_t* out192 /* n_rows */,
+                     int8_t* status /* n_rows, may be NULL */);
 
 /* sign(message_i, privateKey_i) -- reference index.ts:744-752: PointG2.hashToCurve(message) multiplied by the key; output is
  * the affine signature point (192 B), which PointG2.toSignature (index.ts:586-602) compresses on the caller's side.
@@ -332,7 +357,10 @@ const char* nbls_config_describe(void);   /* "NBLS_X=value(env|default) ...": ev
    _destroy / _size, scratch slots 44 .. 47 (additions only, same version); then nbls_verify_multiple_shared, nbls_verify_aggregates_shared,
    nbls_verify_aggregates_indexed_shared, scratch slots 48 .. 50 (additions only, same version); then nbls_fr_op_batch, nbls_lagrange_at_zero, nbls_g2_combine_shares,
    nbls_g1_combine_shares, NBLS_FROP_*, NBLS_ST_BAD_IDS, scratch slots 51 .. 56 (additions only, same version); then nbls_field_kernel_raw (addition only, same version); then nbls_g1_poly_eval,
-   nbls_g2_poly_eval, nbls_extra_program_kernel, NBLS_TUNE_POLY_SLAB, scratch slots 57 .. 61 (additions only, same version).
+   nbls_g2_poly_eval, nbls_extra_program_kernel, NBLS_TUNE_POLY_SLAB, scratch slots 57 .. 61 (additions only, same version); then nbls_g1_msm_batch, nbls_g2_msm_batch,
+   nbls_g1_msm_rows, nbls_g2_msm_rows, NBLS_TUNE_MSMB_WINDOW / _BIG / _SLAB, the names "dbladd_g1" / "dbladd_g2" of nbls_extra_program_kernel, scratch slots 62 .. 63 (additions only, same version); with them ONE CHANGE TO EXISTING CALLS, same version: nbls_g1_msm / nbls_g2_msm write all-zero output bytes when the status is 1 (the sum is the
+   zero point).  The bytes were unspecified there before (what the affine conversion made of a Z that is 0 mod p: in G1 a zero x and an arbitrary y); the status, and every output with status 0, are unchanged.
+   nbls_msm_dev, which leaves its result on the device, is not changed.
    4 (round 6): nbls_hw_queues, NBLS_TUNE_WIDE_MAX, NBLS_TUNE_H2C_NORM_MIN, NBLS_TUNE_INV_WIDE_MAX, NBLS_TUNE_LS_MAX / _LS2_MAX (additions only); the library sets GPU_MAX_HW_QUEUES = 22 at load when the variable is unset (see nbls_pool_init below).
    3 (round 5): nbls_program_kernel, nbls_pool_*, nbls_sign_batch_dev, NBLS_TUNE_VERIFY_* / _SAC_MAX / _PT_LS2_MAX (additions only); nbls_verify_batch_partial_dev writes d_out_fp12 even when it reports a zero point or a decode error
    (contents then meaningless); 2: *_partial take *d_partial as OUT only, *_partial_into added, nbls_tower_op_batch, nbls_verify_batch_msgs_dev.  The bindings check it at load. */
@@ -409,6 +437,9 @@ int nbls_field_kernel_raw(nbls_ctx* ctx, int kind, int form, size_t n, const uin
 #define NBLS_TUNE_LS_MAX 13           /* items up to which the pairing programs run in their four-lane forms (default 1024; nbls_pool_init sets 0 on its contexts: the forms shorten ONE call at up to four times the instructions per item) */
 #define NBLS_TUNE_LS2_MAX 14          /* ... in their two-lane forms, above LS_MAX (default 2048; pool contexts 0) */
 #define NBLS_TUNE_POLY_SLAB 15        /* identifiers that nbls_g*_poly_eval works through at a time: the per-step coefficient buffer and the accumulators never exceed one slab (default 2^18; 0 = the default) */
+#define NBLS_TUNE_MSMB_WINDOW 16      /* window width of nbls_g*_msm_batch / _rows: 4, 6, 8, 10 or 12 bits; 0 (default) = chosen per call: the width that minimises points * windows + windows * c * 2^(c - 1) for the mean group */
+#define NBLS_TUNE_MSMB_BIG 17         /* points (as given) above which a group of nbls_g*_msm_batch / _rows runs through the pipeline of nbls_g*_msm on the same stream (default 16384; 0 = the default) */
+#define NBLS_TUNE_MSMB_SLAB 18        /* budget of one slab of groups: sum over its groups of (points after the split) * windows + windows * c * 2^(c - 1), the sorted entries and gathered bucket points that are in scratch at a time; a group that exceeds it alone is a slab of its own (default 2^23; 0 = the default) */
 int nbls_set_tuning(nbls_ctx* ctx, int key, long long value);
 int nbls_program_count(void);                 /* number of step programs; timing slot nbls_program_count() = the inversion kernel */
 const char* nbls_program_name(int prog);
@@ -416,7 +447,7 @@ const char* nbls_program_name(int prog);
    NBLS_AOT=0, or the build-time and run-time compilations of the program disagree); NULL on a bad index.  The string is static. */
 const char* nbls_program_kernel(nbls_ctx* ctx, int prog);
 /* the same for a step program outside the numbered ones, by name: "poly_g1_16", "poly_g1_256", "poly_g2_16", "poly_g2_256" (the Horner steps of nbls_g*_poly_eval, short and
-   full form); NULL for any other name */
+   full form), "dbladd_g1", "dbladd_g2" (the doubling-and-add steps that combine the bit-slices of nbls_g*_msm_batch / _rows); NULL for any other name */
 const char* nbls_extra_program_kernel(nbls_ctx* ctx, const char* name);
 int nbls_timing_enable(nbls_ctx* ctx, int on);
 int nbls_timing_read(nbls_ctx* ctx, float* ms /*[NBLS_N_PROGRAMS+1]*/, uint32_t* counts /*[NBLS_N_PROGRAMS+1]*/);

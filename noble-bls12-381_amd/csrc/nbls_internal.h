@@ -1,5 +1,5 @@
 // nbls_internal.h -- what the translation units of the runtime share (runtime.cpp / tuning.cpp / pipelines_pairing.cpp / pipelines_codec.cpp / pipelines_verify.cpp /
-// pipelines_multi_verify.cpp / pipelines_threshold.cpp / pipelines_poly.cpp; pool and multi-device handles: nbls_multi.cpp): the context, the map of its scratch slots (enum Slot: the one place that says which chain owns
+// pipelines_multi_verify.cpp / pipelines_threshold.cpp / pipelines_poly.cpp / pipelines_msm_batch.cpp; pool and multi-device handles: nbls_multi.cpp): the context, the map of its scratch slots (enum Slot: the one place that says which chain owns
 // which slot, checked at compile time), the launch helpers and the device-side pipelines the exported entry points are built from.  Internal functions have hidden visibility
 // (csrc/Makefile: -fvisibility=hidden).
 #pragma once
@@ -60,6 +60,10 @@ extern "C" int nbls_msm_pairs_launch(size_t m, unsigned d, const void* keys, con
 extern "C" int nbls_msm_fill_launch(size_t count, unsigned elem_bytes, const void* ident, void* dst, void* stream);
 extern "C" int nbls_msm_heads_launch(size_t m, unsigned elem_bytes, const void* keys, const void* P, void* buckets, void* stream);
 extern "C" int nbls_msm_bitsel_launch(unsigned nwin, unsigned elem_bytes, const void* buckets, void* G, void* stream);
+// msmb_kernels.hip
+extern "C" int nbls_msmb_keys_launch(unsigned m, unsigned dims, unsigned nwin, unsigned c, unsigned i0, unsigned g0, unsigned ngroups, unsigned n_pts, const void* off,
+                                     const void* scalars, void* keys, void* vals, void* stream);
+extern "C" int nbls_msmb_bitsel_launch(size_t nbw, unsigned c, unsigned elem_bytes, const void* buckets, void* G, void* stream);
 extern "C" int nbls_fp_pow_launch(unsigned n, const void* in, void* out, const void* ops, int nops, void* scratch, int is_fp2, void* stream);
 extern "C" int nbls_pow_wide_launch(unsigned n, const void* in, void* out, const void* ops, int nops, int is_fp2, void* stream);
 
@@ -109,9 +113,13 @@ enum Slot {
   // poly_pipeline (pipelines_poly.cpp): the decoded coefficients, their statuses and raw projective forms | groups, ranks, first bad positions, the group of every identifier |
   // one slab: accumulators, norms, inverses, affine points, zero flags | one slab: the step's coefficient of every item | the compressed results and statuses (what is read back)
   SB_POLY_COEFS = 57, SB_POLY_LABELS = 58, SB_POLY_ACC = 59, SB_POLY_STEP = 60, SB_POLY_OUT = 61,
+  // msm_batch_pipeline (pipelines_msm_batch.cpp), both sized once per call before its first launch: the staged input, the converted points, the split scalars and what is read
+  // back | one slab: keys, sorted points, buckets, bit-slices, accumulators.  (Two slots, carved by the pipeline: the masks below are 64 bits wide.)
+  SB_MSMB_CALL = 62, SB_MSMB_SLAB = 63,
   NSB
 };
-static_assert(NSB == 62, "sb[] indices do not shift");
+// all 64 bits of the slot masks are taken: the next chain that needs a slot of its own widens slot_bit / slots / the masks beyond uint64_t first
+static_assert(NSB == 64, "sb[] indices do not shift");
 constexpr uint64_t slot_bit(int i) { return (uint64_t)1 << i; }
 template <typename... S> constexpr uint64_t slots(S... s) { return (slot_bit(s) | ...); }
 // one instance of dev_decompress: three arrays of field elements and the exponentiation table
@@ -138,6 +146,7 @@ constexpr uint64_t M_RLC_SIDE2 = DEC_KEYS.mask() | slots(SB_AGG_DECODED, SB_RLC_
 constexpr uint64_t M_RLC_SIDE = DEC_SIGS.mask() | MSM_RLC.mask();                                           // its signature chain
 constexpr uint64_t M_THR_OWN = slots(SB_STAGED, SB_THR_SHARES, SB_THR_SCALARS, SB_THR_OUT) | SEG_THR.mask();   // combine_pipeline: what outlives the stages it calls
 constexpr uint64_t M_POLY_OWN = slots(SB_STAGED, SB_POLY_COEFS, SB_POLY_LABELS, SB_POLY_ACC, SB_POLY_STEP, SB_POLY_OUT);   // poly_pipeline: what outlives the decoder it calls
+constexpr uint64_t M_MSMB_OWN = slots(SB_MSMB_CALL, SB_MSMB_SLAB);   // msm_batch_pipeline: what outlives the dev_msm calls of its big groups
 // what runs side by side
 static_assert(!(M_VB_MAIN & DEC_KEYS.mask()), "verifyBatch decodes its keys (side2, or the sub-batch's own stream) beside the hash chain");
 static_assert(!(M_RLC_MAIN & M_RLC_SIDE2) && !(M_RLC_MAIN & M_RLC_SIDE) && !(M_RLC_SIDE & M_RLC_SIDE2), "verify_multiple_pipeline: the chains on s, side and side2 run side by side");
@@ -148,6 +157,8 @@ static_assert(!(M_THR_OWN & (DEC_MAIN.mask() | M_LADDER)), "combine_pipeline: th
 static_assert(!(M_POLY_OWN & DEC_MAIN.mask()), "poly_pipeline: the decoder regrows its own slots while the staged coefficients and the decoded points are held");
 static_assert(!((M_POLY_OWN & ~slot_bit(SB_STAGED)) & (M_THR_OWN | M_RLC_MAIN | M_RLC_SIDE | M_RLC_SIDE2 | M_VB_MAIN | M_LADDER | MSM_MAIN.mask())),
               "poly_pipeline keeps to slots of its own: no other chain's buffers are regrown or overwritten by it");
+static_assert(!(M_MSMB_OWN & (MSM_MAIN.mask() | M_POLY_OWN | M_THR_OWN | M_RLC_MAIN | M_RLC_SIDE | M_RLC_SIDE2 | M_VB_MAIN | M_LADDER)),
+              "msm_batch_pipeline: its big groups run through dev_msm on the main slots between its slabs, which must regrow nothing the call still holds");
 // ---- END scratch slots -------------------------------------------------------------------------------------------------------------------------------------
 #define EXPORT extern "C" __attribute__((visibility("default")))
 extern std::recursive_mutex g_null_mu;   // locked in place of a context's mutex when the caller passed no context (the call then fails with NBLS_EINVAL)
@@ -172,6 +183,9 @@ struct nbls_ctx {
   std::map<std::tuple<int, int, int, int>, DevProgram> tower;   // single tower operations (nbls_tower_op_batch), uploaded on first use
   DevProgram extra[XP_COUNT];   // the programs outside ProgId (programs.h ExtraProg), uploaded on first use with their ahead-of-time kernels
   size_t poly_slab = 0;         // nbls_set_tuning(NBLS_TUNE_POLY_SLAB): identifiers per slab of nbls_g*_poly_eval; 0 = the default (pipelines_poly.cpp)
+  // nbls_set_tuning(NBLS_TUNE_MSMB_WINDOW / _BIG / _SLAB): the batched MSM's window width, the points from which a group runs through dev_msm, the entries of a slab; 0 = automatic /
+  // the defaults (pipelines_msm_batch.cpp)
+  size_t msmb_window = 0, msmb_big = 0, msmb_slab = 0;
   // scratch (device)
   uint8_t *F = nullptr, *N = nullptr, *NI = nullptr, *io_g1 = nullptr, *io_g2 = nullptr, *io_f12 = nullptr, *one12 = nullptr;
   uint8_t* T[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // t1..t7 of the final exponentiation, raw Fp12

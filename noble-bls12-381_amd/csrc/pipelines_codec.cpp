@@ -511,6 +511,9 @@ int msm_host(nbls_ctx* ctx, bool g2, size_t n, const uint8_t* pts, const uint8_t
   if (n) { HIPCHK(hipMemcpyAsync(dp, pts, n * a, hipMemcpyHostToDevice, s)); HIPCHK(hipMemcpyAsync(dk, scalars32, n * 32, hipMemcpyHostToDevice, s)); }
   int r = dev_msm(ctx, g2, n, dp, dk, n ? scalars_bit_length(n, scalars32) : 1, o, st, s); if (r) return r;
   int8_t z = 0; HIPCHK(hipMemcpyAsync(out, o, a, hipMemcpyDeviceToHost, s)); HIPCHK(hipMemcpyAsync(&z, st, 1, hipMemcpyDeviceToHost, s)); HIPCHK(hipStreamSynchronize(s));
+  // the zero point has no affine form: what P_G*_TO_AFFINE leaves there depends on the representative of 0 in Z (the one-limb-per-lane combine leaves p, and the binary GCD of
+  // the inversion does not map that to 0).  All-zero bytes, as every other call reports the zero point
+  if (z == 1) memset(out, 0, a);
   if (status) *status = z;
   return NBLS_OK;
 }

@@ -887,12 +887,25 @@ const Program* get_tower_program(int field, int op, int param, int part) {
 }
 
 // ---------------------------------------------------------------- programs outside ProgId (programs.h ExtraProg)
+// (the doubling-and-add steps of the batched MSM, dbladd_g1 / dbladd_g2, are P_G*_SHIFTADD with one doubling, in place: first in build_extra)
 // The Horner step: the ladders' windowed form (2-bit windows: the table of four keeps the LDS image small) on a PROJECTIVE base, then one complete addition.  Every case the
 // caller can produce is covered by the complete formulas: an identity accumulator (the table is identities, the result is A), an identity coefficient, [x]acc = -A (the
 // identity comes out) and [x]acc = A (the addition doubles).
 static Program build_extra(ExtraProg id) {
   Builder B;
   if (env_int("NBLS_AOT_SHARED_CONSTS", 1)) B.shared_consts = 1;
+  if (id == XP_DBLADD_G1) {
+    auto ld = [&](int buf) { return Pt<SFp>{inputw(buf, 0), inputw(buf, 48), inputw(buf, 96)}; };
+    Pt<SFp> r = pt_add(pt_dbl(ld(3)), ld(4));
+    outputw(r.x, 3, 0); outputw(r.y, 3, 48); outputw(r.z, 3, 96);
+    return B.compile("dbladd_g1", 4);
+  }
+  if (id == XP_DBLADD_G2) {
+    auto ld = [&](int buf) { return Pt<SFp2>{{inputw(buf, 0), inputw(buf, 48)}, {inputw(buf, 96), inputw(buf, 144)}, {inputw(buf, 192), inputw(buf, 240)}}; };
+    Pt<SFp2> r = pt_add(pt_dbl(ld(3)), ld(4));
+    outputw(r.x.c0, 3, 0); outputw(r.x.c1, 3, 48); outputw(r.y.c0, 3, 96); outputw(r.y.c1, 3, 144); outputw(r.z.c0, 3, 192); outputw(r.z.c1, 3, 240);
+    return B.compile("dbladd_g2", 8);
+  }
   const bool g2 = id == XP_POLY_G2_16 || id == XP_POLY_G2_256, low16 = id == XP_POLY_G1_16 || id == XP_POLY_G2_16;
   // the short form loads the identifier's last four bytes and tests bits 0 .. 15 of them: bytes 0 .. 29 never reach the result
   const SFp k = low16 ? input_raw(2, 28, 4) : input_raw(2, 0, 32);

@@ -108,7 +108,12 @@ const Program* get_tower_program(int field, int op, int param, int part);
 // kernels of their own (aot.h NBLS_AOT_EXTRA_KERNELS).  One Horner step of a commitment polynomial in the exponent (pipelines_poly.cpp): accumulator (buf 3: raw projective, in
 // place), identifier x (buf 2: 32 bytes big-endian, any value), the step's coefficient (buf 4: raw projective) -> acc = [x]acc + A.  The _16 forms read the low 16 bits of the
 // identifier (16 doublings instead of 256); the accumulator lies in the order-r subgroup, so the _256 forms take any 256-bit value as P_G1_MUL does.
-enum ExtraProg { XP_POLY_G1_16 = 0, XP_POLY_G1_256, XP_POLY_G2_16, XP_POLY_G2_256, XP_COUNT };
+// The doubling-and-add steps of the batched MSM's combination (pipelines_msm_batch.cpp): accumulator (buf 3: raw projective, in place), bit-slice sum T (buf 4: raw projective)
+// -> acc = 2 acc + T, complete formulas throughout (identity accumulators, identity slices, T = -2 acc and T = 2 acc are ordinary inputs).
+enum ExtraProg { XP_POLY_G1_16 = 0, XP_POLY_G1_256, XP_POLY_G2_16, XP_POLY_G2_256, XP_DBLADD_G1, XP_DBLADD_G2, XP_COUNT };
+// The simulator's index-taking entry points (nbls_sim_extra_count / _name / _verify / _run) stop in front of this one: the suite pins their count at the four Horner steps.
+// Every later program is reached by name (nbls_sim_extra_verify_named / _run_named), as nbls_extra_program_kernel reaches it in the engine.
+static const int XP_NUMBERED = XP_DBLADD_G1;
 const Program& get_extra_program(ExtraProg id);
 void print_stats(const Program& p);
 }  // namespace nbls

@@ -144,6 +144,9 @@ EXPORT int nbls_set_tuning(nbls_ctx* ctx, int key, long long value) {
     case NBLS_TUNE_VERIFY_LAST_PCT: if (value < 1 || value > 100) return NBLS_EINVAL; ctx->verify_last_pct = (long)value; return NBLS_OK;
     case NBLS_TUNE_VERIFY_PIPE_MIN: if (value < 0) return NBLS_EINVAL; ctx->verify_pipe_min = (long)value; return NBLS_OK;
     case NBLS_TUNE_POLY_SLAB: if (value < 0) return NBLS_EINVAL; ctx->poly_slab = (size_t)value; return NBLS_OK;
+    case NBLS_TUNE_MSMB_WINDOW: if (value != 0 && value != 4 && value != 6 && value != 8 && value != 10 && value != 12) return NBLS_EINVAL; ctx->msmb_window = (size_t)value; return NBLS_OK;
+    case NBLS_TUNE_MSMB_BIG: if (value < 0) return NBLS_EINVAL; ctx->msmb_big = (size_t)value; return NBLS_OK;
+    case NBLS_TUNE_MSMB_SLAB: if (value < 0) return NBLS_EINVAL; ctx->msmb_slab = (size_t)value; return NBLS_OK;
     default: return NBLS_EINVAL;
   }
 }
@@ -157,8 +160,8 @@ EXPORT const char* nbls_program_kernel(nbls_ctx* ctx, int prog) {
   const DevProgram& d = ctx->prog[prog];
   return d.aot >= 0 ? nbls_aot_name(d.aot) : d.p->lsplit == 4 ? "nbls_vm_kernel_ls4" : d.p->lsplit == 1 ? "nbls_vm_kernel" : "none (two-lane programs have no interpreter form)";
 }
-// The same for a program outside the numbered registry, by its name ("poly_g1_16", "poly_g1_256", "poly_g2_16", "poly_g2_256": the Horner steps of nbls_g*_poly_eval); NULL for a
-// name that is not one.  The query uploads the program.
+// The same for a program outside the numbered registry, by its name ("poly_g1_16", "poly_g1_256", "poly_g2_16", "poly_g2_256": the Horner steps of nbls_g*_poly_eval;
+// "dbladd_g1", "dbladd_g2": the combination steps of nbls_g*_msm_batch / _rows); NULL for a name that is not one.  The query uploads the program.
 EXPORT const char* nbls_extra_program_kernel(nbls_ctx* ctx, const char* name) {
   if (!ctx || !name) return nullptr;
   std::lock_guard<std::recursive_mutex> g(ctx->mu);

@@ -311,22 +311,34 @@ __attribute__((visibility("default"))) int nbls_sim_run(int prog, unsigned n_ite
 // The programs outside ProgId (programs.h ExtraProg; nbls_sim_run refuses everything from P_COUNT on): count, name, the static verifier (0 = passed; the message goes to
 // stderr), and a run -- aot = 0: the interpreter's semantics; 1: the translated form on the step bodies of the program's ahead-of-time kernel (-2: it has none, -3: its
 // signatures are not in the kernel's table)
-__attribute__((visibility("default"))) int nbls_sim_extra_count(void) { return (int)XP_COUNT; }
-__attribute__((visibility("default"))) const char* nbls_sim_extra_name(int xp) { return xp >= 0 && xp < (int)XP_COUNT ? get_extra_program((ExtraProg)xp).name.c_str() : nullptr; }
-__attribute__((visibility("default"))) int nbls_sim_extra_verify(int xp) {
-  if (xp < 0 || xp >= (int)XP_COUNT) return -1;
+__attribute__((visibility("default"))) int nbls_sim_extra_count(void) { return XP_NUMBERED; }
+__attribute__((visibility("default"))) const char* nbls_sim_extra_name(int xp) { return xp >= 0 && xp < XP_NUMBERED ? get_extra_program((ExtraProg)xp).name.c_str() : nullptr; }
+static int sim_extra_verify(int xp) {
   const std::string e = verify_program(get_extra_program((ExtraProg)xp));
   if (!e.empty()) fprintf(stderr, "nbls_sim_extra_verify: %s\n", e.c_str());
   return e.empty() ? 0 : 1;
 }
-__attribute__((visibility("default"))) int nbls_sim_extra_run(int xp, int aot, unsigned n_items, uint8_t** ptrs, const uint64_t* strides) {
-  if (xp < 0 || xp >= (int)XP_COUNT) return -1;
+static int sim_extra_run(int xp, int aot, unsigned n_items, uint8_t** ptrs, const uint64_t* strides) {
   IOBuf b[MAX_BUFS];
   for (int i = 0; i < MAX_BUFS; i++) { b[i].ptr = ptrs[i]; b[i].stride = strides[i]; }
   const Program& p = get_extra_program((ExtraProg)xp);
   if (aot) return sim_run_aot_program((int)P_COUNT + 1 + xp, p, n_items, b);
   sim_run(p, n_items, b);
   return 0;
+}
+__attribute__((visibility("default"))) int nbls_sim_extra_verify(int xp) { return xp < 0 || xp >= XP_NUMBERED ? -1 : sim_extra_verify(xp); }
+__attribute__((visibility("default"))) int nbls_sim_extra_run(int xp, int aot, unsigned n_items, uint8_t** ptrs, const uint64_t* strides) {
+  return xp < 0 || xp >= XP_NUMBERED ? -1 : sim_extra_run(xp, aot, n_items, ptrs, strides);
+}
+// The same by name, for every program of ExtraProg -- the numbered entry points above stop at XP_NUMBERED (programs.h); -1 for a name that is none
+static int sim_extra_by_name(const char* name) {
+  if (name) for (int i = 0; i < (int)XP_COUNT; i++) if (get_extra_program((ExtraProg)i).name == name) return i;
+  return -1;
+}
+__attribute__((visibility("default"))) int nbls_sim_extra_verify_named(const char* name) { const int xp = sim_extra_by_name(name); return xp < 0 ? -1 : sim_extra_verify(xp); }
+__attribute__((visibility("default"))) int nbls_sim_extra_run_named(const char* name, int aot, unsigned n_items, uint8_t** ptrs, const uint64_t* strides) {
+  const int xp = sim_extra_by_name(name);
+  return xp < 0 ? -1 : sim_extra_run(xp, aot, n_items, ptrs, strides);
 }
 // out = in^-1 on raw elements (16 words each): the same fp_mont_inverse routine the inversion kernel runs per lane
 // the same inverse with one limb per lane (fp_inv_wide.h), one element after the other

@@ -62,6 +62,10 @@ def load_library():
     lib.nbls_g1_msm.argtypes = [vp, sz, vp, vp, vp, vp]
     lib.nbls_g2_msm.argtypes = [vp, sz, vp, vp, vp, vp]
     lib.nbls_msm_dev.argtypes = [vp, i32, sz, vp, vp, C.c_uint32, vp, vp, vp]
+    lib.nbls_g1_msm_batch.argtypes = [vp, sz, vp, vp, vp, vp, vp]
+    lib.nbls_g2_msm_batch.argtypes = [vp, sz, vp, vp, vp, vp, vp]
+    lib.nbls_g1_msm_rows.argtypes = [vp, sz, vp, sz, vp, vp, vp]
+    lib.nbls_g2_msm_rows.argtypes = [vp, sz, vp, sz, vp, vp, vp]
     lib.nbls_sign_batch.argtypes = [vp, sz, vp, vp, vp, sz, vp, vp, vp]
     lib.nbls_sign_batch_dev.argtypes = [vp, sz, vp, vp, vp, sz, vp, vp, vp, vp]
     lib.nbls_verify_batch.argtypes = [vp, sz, vp, vp, vp, vp, vp, sz, C.POINTER(i32)]
@@ -352,6 +356,36 @@ class Engine:
         f = self.lib.nbls_g2_msm if g2 else self.lib.nbls_g1_msm
         self._chk(f(self.h, n, pts, b''.join(scalars), out, C.byref(st)))
         return out.raw, st.value
+
+    def msm_batch(self, groups_pts, groups_scalars, g2=False):
+        """many independent sums in one call (include/nbls.h nbls_g*_msm_batch).  groups_pts: per group its concatenated affine wire points; groups_scalars: per group the list
+        of its 32-byte big-endian scalars, or those already concatenated (an empty group is an empty sum) -> (per group the affine wire bytes, per group the status: 1 = the zero point, all-zero bytes); every
+        group's result is byte for byte what msm gives for it alone"""
+        sz = 192 if g2 else 96
+        m = len(groups_scalars)
+        ks = [k if isinstance(k, (bytes, bytearray)) else b''.join(k) for k in groups_scalars]
+        assert len(groups_pts) == m and all(len(p) * 32 == sz * len(k) for p, k in zip(groups_pts, ks))
+        offs = [0]
+        for k in ks:
+            offs.append(offs[-1] + len(k) // 32)
+        out = C.create_string_buffer(max(sz * m, 1)); st = C.create_string_buffer(max(m, 1))
+        f = self.lib.nbls_g2_msm_batch if g2 else self.lib.nbls_g1_msm_batch
+        self._chk(f(self.h, m, (C.c_uint32 * len(offs))(*offs), b''.join(groups_pts), b''.join(ks), out, st))
+        raw = out.raw
+        return [raw[sz * g:sz * g + sz] for g in range(m)], list(st.raw[:m])
+
+    def msm_rows(self, pts, rows, g2=False):
+        """many scalar vectors against one set of points (nbls_g*_msm_rows).  pts: the concatenated affine wire points; rows: per row the list of one 32-byte scalar per
+        point, or the row's scalars already concatenated -> (per row the affine wire bytes, per row the status) as msm_batch"""
+        sz = 192 if g2 else 96
+        n, m = len(pts) // sz, len(rows)
+        ks = b''.join(r if isinstance(r, (bytes, bytearray)) else b''.join(r) for r in rows)
+        assert len(pts) == sz * n and len(ks) == 32 * n * m
+        out = C.create_string_buffer(max(sz * m, 1)); st = C.create_string_buffer(max(m, 1))
+        f = self.lib.nbls_g2_msm_rows if g2 else self.lib.nbls_g1_msm_rows
+        self._chk(f(self.h, n, pts, m, ks, out, st))
+        raw = out.raw
+        return [raw[sz * g:sz * g + sz] for g in range(m)], list(st.raw[:m])
 
     def msm_dev(self, g2, n, d_pts, d_scalars, nbits, d_out, d_status, stream=0):
         self._chk(self.lib.nbls_msm_dev(self.h, int(bool(g2)), n, d_pts, d_scalars, nbits, d_out, d_status, stream))
@@ -686,6 +720,13 @@ class Engine:
         """identifiers that poly_eval works through at a time (NBLS_TUNE_POLY_SLAB = 15; default 2^18, 0: the default)"""
         self._chk(self.lib.nbls_set_tuning(self.h, 15, int(n)))
 
+    def set_msm_batch(self, window=None, big=None, slab=None):
+        """msm_batch / msm_rows (NBLS_TUNE_MSMB_WINDOW = 16 / _BIG = 17 / _SLAB = 18): the window width (4, 6, 8, 10, 12; 0: chosen per call), the points above which a group
+        runs alone through the pipeline of msm, the budget of a slab of groups; 0: the defaults"""
+        for key, v in ((16, window), (17, big), (18, slab)):
+            if v is not None:
+                self._chk(self.lib.nbls_set_tuning(self.h, key, int(v)))
+
     def set_verify_pipeline(self, chunks=None, last_pct=None, pipe_min=None):
         """verifyBatch as a software pipeline (NBLS_TUNE_VERIFY_CHUNKS / _LAST_PCT / _PIPE_MIN): number of chunks (0 / 1: one), size of the last chunk in
         per cent of the batch, signatures from which a call is chunked at all"""
@@ -710,7 +751,8 @@ class Engine:
         return k.decode()
 
     def extra_program_kernel(self, name):
-        """the same for a program outside PROGRAMS, by name: 'poly_g1_16', 'poly_g1_256', 'poly_g2_16', 'poly_g2_256' (the Horner steps of poly_eval)"""
+        """the same for a program outside PROGRAMS, by name: 'poly_g1_16', 'poly_g1_256', 'poly_g2_16', 'poly_g2_256' (the Horner steps of poly_eval), 'dbladd_g1', 'dbladd_g2'
+        (the combination steps of msm_batch / msm_rows)"""
         k = self.lib.nbls_extra_program_kernel(self.h, name.encode())
         if k is None:
             raise NblsError('nbls_extra_program_kernel(%s) failed' % name)
