@@ -145,6 +145,14 @@ int nbls_hash_to_g1_batch(nbls_ctx* ctx, size_t n, const uint8_t* msgs, const ui
 int nbls_encode_to_g1_batch(nbls_ctx* ctx, size_t n, const uint8_t* msgs, const uint32_t* offsets, const uint8_t* dst, size_t dst_len, uint8_t* out96);
 int nbls_encode_to_g2_batch(nbls_ctx* ctx, size_t n, const uint8_t* msgs, const uint32_t* offsets, const uint8_t* dst, size_t dst_len, uint8_t* out192);
 
+/* The same four maps BEHIND expand_message_xmd, on n items of caller-chosen uniform bytes (for tests: the inputs where the 64-byte -> Fp reduction and the SWU maps branch are not
+ * SHA-256 outputs).  kind 0 = PointG2.hashToCurve (256 bytes in, 192 out), 1 = PointG2.encodeToCurve (128 -> 192), 2 = PointG1.hashToCurve (128 -> 96), 3 = PointG1.encodeToCurve
+ * (64 -> 96); each field element is 64 big-endian bytes, any value (reduced mod p).  The launches are those of the message calls for the same n.  status (may be NULL): 0 ok,
+ * 1 the result is the zero point (output then all-zero).  NBLS_EINVAL before any device work for a NULL context, an unknown kind, or missing buffers with n > 0; n = 0 is NBLS_OK.
+ * Items of kinds 0 and 2 whose two field elements satisfy u0 = +-u1 mod p are outside the contract (the reference doubles the SWU point with a formula that is not the
+ * isogenous curve's, or maps its zero point's (0, 0) on): the device reports them as the zero point, status 1 with all-zero bytes, and every other item of the call is unaffected. */
+int nbls_map_uniform_batch(nbls_ctx* ctx, int kind, size_t n, const uint8_t* uniform, uint8_t* out, int8_t* status);
+
 /* Sum of n affine points: the reduce step of aggregatePublicKeys / aggregateSignatures (index.ts:771-788). *status = 1 when
  * the sum is the zero point (output then all-zero). */
 int nbls_g1_sum(nbls_ctx* ctx, size_t n, const uint8_t* pts96, uint8_t* out96, int8_t* status);
@@ -219,6 +227,8 @@ int nbls_verify_batch(nbls_ctx* ctx, size_t n, const uint8_t* sig96, const uint8
  * (the whole of verifyBatch index.ts:792-821 for wire-format inputs with nothing done on the host).  dst_len <= 255. */
 int nbls_verify_batch_msgs_dev(nbls_ctx* ctx, size_t n, const void* d_sig96, const void* d_msgs, const void* d_offsets, const void* d_pk48, const uint8_t* dst, size_t dst_len,
                                int* ok, void* stream);
+/* d_uniform256: an item whose two field elements satisfy u0 = +-u1 mod p is outside the contract (see nbls_map_uniform_batch): the hash stage yields the zero point for it, handed to
+ * the Miller loop as all-zero affine bytes WITHOUT a status of its own, so the call's verdict is unspecified; the hash points of the other items are unaffected. */
 int nbls_verify_batch_dev_inputs(nbls_ctx* ctx, size_t n, const void* d_sig96, const void* d_uniform256, const void* d_pk48, int* ok,
                                  int8_t* pk_status /* n, may be NULL */, void* stream);
 
@@ -337,6 +347,8 @@ int nbls_g2_poly_eval(nbls_ctx* ctx, size_t n_groups, const uint32_t* coef_offse
  * nbls_fp12_product_final_dev (product + shared finalExponentiate, index.ts:811-817), then compare with Fp12.ONE.
  * *zero_flag = 1: a zero point was met (verifyBatch answers false).  NBLS_EDECODE as nbls_verify_batch.  ABI 3: the call decides nothing on the host before its end, so d_out_fp12 IS
  * written in both cases -- with a meaningless product; look at the return code and the flag first. */
+/* d_uniform256: an item whose two field elements satisfy u0 = +-u1 mod p is outside the contract (see nbls_map_uniform_batch): the hash stage yields the zero point for it, handed to
+ * the Miller loop as all-zero affine bytes and NOT reported through *zero_flag, so the partial product is unspecified; the hash points of the other items are unaffected. */
 int nbls_verify_batch_partial_dev(nbls_ctx* ctx, size_t n, const void* d_sig96 /* or NULL */, const void* d_uniform256, const void* d_pk48,
                                   void* d_out_fp12, int* zero_flag, int8_t* pk_status /* n, may be NULL */, void* stream);
 
@@ -358,7 +370,7 @@ const char* nbls_config_describe(void);   /* "NBLS_X=value(env|default) ...": ev
    nbls_verify_aggregates_indexed_shared, scratch slots 48 .. 50 (additions only, same version); then nbls_fr_op_batch, nbls_lagrange_at_zero, nbls_g2_combine_shares,
    nbls_g1_combine_shares, NBLS_FROP_*, NBLS_ST_BAD_IDS, scratch slots 51 .. 56 (additions only, same version); then nbls_field_kernel_raw (addition only, same version); then nbls_g1_poly_eval,
    nbls_g2_poly_eval, nbls_extra_program_kernel, NBLS_TUNE_POLY_SLAB, scratch slots 57 .. 61 (additions only, same version); then nbls_g1_msm_batch, nbls_g2_msm_batch,
-   nbls_g1_msm_rows, nbls_g2_msm_rows, NBLS_TUNE_MSMB_WINDOW / _BIG / _SLAB, the names "dbladd_g1" / "dbladd_g2" of nbls_extra_program_kernel, scratch slots 62 .. 63 (additions only, same version); with them ONE CHANGE TO EXISTING CALLS, same version: nbls_g1_msm / nbls_g2_msm write all-zero output bytes when the status is 1 (the sum is the
+   nbls_g1_msm_rows, nbls_g2_msm_rows, NBLS_TUNE_MSMB_WINDOW / _BIG / _SLAB, the names "dbladd_g1" / "dbladd_g2" of nbls_extra_program_kernel, scratch slots 62 .. 63 (additions only, same version); then nbls_map_uniform_batch (addition only, same version); with the MSM calls ONE CHANGE TO EXISTING CALLS, same version: nbls_g1_msm / nbls_g2_msm write all-zero output bytes when the status is 1 (the sum is the
    zero point).  The bytes were unspecified there before (what the affine conversion made of a Z that is 0 mod p: in G1 a zero x and an arbitrary y); the status, and every output with status 0, are unchanged.
    nbls_msm_dev, which leaves its result on the device, is not changed.
    4 (round 6): nbls_hw_queues, NBLS_TUNE_WIDE_MAX, NBLS_TUNE_H2C_NORM_MIN, NBLS_TUNE_INV_WIDE_MAX, NBLS_TUNE_LS_MAX / _LS2_MAX (additions only); the library sets GPU_MAX_HW_QUEUES = 22 at load when the variable is unset (see nbls_pool_init below).

@@ -197,6 +197,23 @@ EXPORT int nbls_encode_to_g1_batch(nbls_ctx* ctx, size_t n, const uint8_t* msgs,
 EXPORT int nbls_encode_to_g2_batch(nbls_ctx* ctx, size_t n, const uint8_t* msgs, const uint32_t* offsets, const uint8_t* dst, size_t dst_len, uint8_t* out192) { return hash_curve_host(ctx,
     2, n, msgs, offsets, dst, dst_len, out192); }
 
+// hash-to-curve BEHIND expand_message_xmd on caller-chosen uniform bytes (tests/test_gpu_h2c_map.py): the bodies of nbls_hash_to_g2_batch / hash_curve_host without dev_expand, so the
+// launches are the pipelines' own -- h2c_norm_min against n, the point chains' form by n, run_pow's wide form up to pow_wide_max() elements.
+// kind: 0 G2 hash (256 bytes in, 192 out), 1 G2 encode (128 -> 192), 2 G1 hash (128 -> 96), 3 G1 encode (64 -> 96); status 1 = the zero point (P_G*_TO_AFFINE found Z = 0)
+EXPORT int nbls_map_uniform_batch(nbls_ctx* ctx, int kind, size_t n, const uint8_t* uniform, uint8_t* out, int8_t* status) {
+  if (!ctx || kind < 0 || kind > 3 || (n && (!uniform || !out))) return NBLS_EINVAL; if (!n) return NBLS_OK;
+  const size_t in = kind == 0 ? 256 : kind == 3 ? 64 : 128, a = kind < 2 ? 192 : 96;
+  LOCKED(ctx); HostIO io{ctx}; void *d = io.alloc(n * in), *o = io.alloc(n * a); if (!d || !o) return NBLS_EHIP;
+  HIPCHK(hipMemcpyAsync(d, uniform, n * in, hipMemcpyHostToDevice, s));
+  int r = kind == 0 ? dev_hash_to_g2(ctx, n, d, o, s) : kind == 1 ? dev_encode_to_g2(ctx, n, d, o, s) : dev_hash_to_g1(ctx, kind == 2 ? 2 : 1, n, d, o, s); if (r) return r;
+  uint8_t* st; if ((r = need(ctx, SB_POINT_ST, n, &st))) return r;       // where all three pipelines leave to_affine's status bytes
+  std::vector<int8_t> zero(n);
+  HIPCHK(hipMemcpyAsync(out, o, n * a, hipMemcpyDeviceToHost, s)); HIPCHK(hipMemcpyAsync(zero.data(), st, n, hipMemcpyDeviceToHost, s)); HIPCHK(hipStreamSynchronize(s));
+  for (size_t i = 0; i < n; i++) if (zero[i]) memset(out + i * a, 0, a);
+  if (status) memcpy(status, zero.data(), n);
+  return NBLS_OK;
+}
+
 // PointG1.toHex(true) / PointG2.toSignature for non-zero affine points (index.ts:359-371, 586-602): bulk serialisation
 int compress_host(nbls_ctx* ctx, bool g2, size_t n, const uint8_t* aff, uint8_t* out) {
   if (!ctx || (n && (!aff || !out))) return NBLS_EINVAL; if (!n) return NBLS_OK;

@@ -97,6 +97,7 @@ def load_library():
     lib.nbls_pairing_prepared.argtypes = [vp, sz, vp, vp, sz, i32, i32, vp]
     lib.nbls_set_tuning.argtypes = [vp, i32, C.c_longlong]
     lib.nbls_field_kernel_raw.argtypes = [vp, i32, i32, sz, vp, vp]
+    lib.nbls_map_uniform_batch.argtypes = [vp, i32, sz, vp, vp, vp]
     for nm in ('nbls_g1_from_hex_batch', 'nbls_g2_from_hex_batch', 'nbls_g2_from_signature_batch'):
         getattr(lib, nm).argtypes = [vp, sz, vp, sz, vp, vp]
     lib.nbls_g1_to_hex_batch.argtypes = [vp, sz, vp, vp, i32, vp]
@@ -326,6 +327,22 @@ class Engine:
         f = self.lib.nbls_encode_to_g2_batch if g2 else (self.lib.nbls_encode_to_g1_batch if encode else self.lib.nbls_hash_to_g1_batch)
         self._chk(f(self.h, len(msgs), blob, offs, dst, len(dst), out))
         return out.raw[:sz * len(msgs)]
+
+    MAP_UNIFORM_BYTES = {0: (256, 192), 1: (128, 192), 2: (128, 96), 3: (64, 96)}
+
+    def map_uniform_batch(self, kind, uniform):
+        """hash-to-curve behind expand_message_xmd on chosen uniform bytes (include/nbls.h nbls_map_uniform_batch): kind 0 G2 hash (256 bytes per item), 1 G2 encode (128),
+        2 G1 hash (128), 3 G1 encode (64) -> (affine wire bytes, status bytes: 1 = the zero point, its bytes all-zero)"""
+        if kind not in self.MAP_UNIFORM_BYTES:
+            raise NblsError('map_uniform_batch: unknown kind %r' % (kind,))
+        isz, osz = self.MAP_UNIFORM_BYTES[kind]
+        n = len(uniform) // isz
+        if len(uniform) != isz * n:
+            raise NblsError('map_uniform_batch: %d bytes are not a multiple of %d' % (len(uniform), isz))
+        out = C.create_string_buffer(max(osz * n, 1))
+        st = C.create_string_buffer(max(n, 1))
+        self._chk(self.lib.nbls_map_uniform_batch(self.h, kind, n, uniform, out, st))
+        return out.raw[:osz * n], st.raw[:n]
 
     def point_sum(self, pts, g2=False):
         sz = 192 if g2 else 96

@@ -104,6 +104,12 @@ class Oracle:
     def hash_to_field(self, msg, dst=DST_DEFAULT):
         return self.call('hash_to_field', 192, msg, C.c_size_t(len(msg)), dst, C.c_size_t(len(dst)))
 
+    def map_uniform(self, kind, uniform):
+        """hash-to-curve behind expand_message_xmd: kind 0 G2 hash (256 bytes), 1 G2 encode (128), 2 G1 hash (128), 3 G1 encode (64) -> (status, affine bytes); status 0 ok,
+        1 the zero point, -2 / -3 where the reference throws (SWU failure, zero isogeny denominator); zero bytes unless 0"""
+        assert len(uniform) == (256, 128, 128, 64)[kind]
+        return self.call('map_uniform', 192 if kind < 2 else 96, C.c_int(kind), uniform)
+
     def expand_message_xmd(self, msg, dst, n):
         out = self._out(n)
         self.lib.oracle_expand_message_xmd(msg, C.c_size_t(len(msg)), dst, C.c_size_t(len(dst)), out, C.c_size_t(n))

@@ -77,6 +77,18 @@ def test_decode_and_hash_programs_translated(sim, oracle, golden, testdata):
     T.test_norm_method_square_root_corner_cases(sim)
 
 
+@pytest.mark.parametrize('form', ['plain', 'ls2', 'norm'])
+def test_hash_maps_on_chosen_field_elements_translated(sim, form):
+    """the chosen uniform bytes of tests/h2c_cases.py (the edges of the 64-byte reduction, exceptional denominators, the a1 = 0 family of the norm method, degenerate items)
+    through the translated programs: every select and flag step of the SWU programs on the inputs where it takes its other side"""
+    for name in ('ENC2_A', 'ENC2_B', 'H2C1_A', 'H2C1_B', 'ENC1_A', 'ENC1_B', 'G1_CLEAR', 'G1_TO_AFFINE'):
+        assert sim.nbls_sim_has_aot(vmsim_py.P[name]) == 1, name
+    T.test_hash_to_g2_on_chosen_field_elements(sim, form)
+    if form == 'plain':
+        T.test_encode_to_g2_and_g1_maps_on_chosen_field_elements(sim)
+        T.test_degenerate_hash_items_give_the_zero_point(sim)
+
+
 def test_slot_placement_table_is_current_and_pays(sim):
     """round 5 (csrc/aot_layout.h): the generated slot placements of the pairing path's programs belong to the programs as they compile NOW (a row whose hash no longer
     matches is ignored at run time -- correct, but the kernels then run with round 4's bank conflicts: regenerate with `make -C noble-bls12-381_amd/csrc layout`), and under the

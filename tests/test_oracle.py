@@ -250,3 +250,67 @@ def test_hash_and_encode_to_curve_kats(oracle, golden, testdata):
         assert oracle.hash_to_g1(m, dst)[1] == hx(v['g1_hash'])
         assert oracle.encode_to_g1(m, dst)[1] == hx(v['g1_encode'])
         assert oracle.encode_to_g2(m, dst)[1] == hx(v['g2_encode'])
+
+
+# ---- hash-to-curve behind expand_message_xmd on chosen uniform bytes (tests/h2c_cases.py, tests/golden/ref_h2c_map.json.gz) --------------------------------------------
+@pytest.fixture(scope='module')
+def h2c_map():
+    import goldenio
+    return goldenio.load('ref_h2c_map.json.gz')['cases']
+
+
+def test_h2c_map_fixture_holds_the_case_lists(h2c_map):
+    """the fixture was generated from the lists of tests/h2c_cases.py as they are now, in their order, and the reference's u = os2ip(64 bytes) mod p is the integer reduction: the
+    64-byte -> Fp stage is pinned by Python integers, independently of the reference, the oracle and the programs"""
+    import h2c_cases as H
+    want = [c for k in range(4) for c in H.cases(k)]
+    assert [(v['name'], v['kind'], hx(v['uniform']), v['degenerate']) for v in h2c_map] == [tuple(c) for c in want]
+    for v in h2c_map:
+        b = hx(v['uniform'])
+        assert [int(u, 16) for u in v['u']] == [int.from_bytes(b[k:k + 64], 'big') % H.P for k in range(0, len(b), 64)], v['name']
+    # the reference completes every case: equal SWU points are doubled by its addition, opposite ones give its zero point, which toAffine turns into (0, 0) (math.ts:949-958)
+    assert all(v['result'] == 'ok' and len(hx(v['aff'])) == H.OUT_BYTES[v['kind']] for v in h2c_map)
+    assert sum(v['degenerate'] for v in h2c_map) == 6
+
+
+def test_h2c_map_oracle_equals_the_reference(oracle, h2c_map):
+    """oracle_map_uniform (the message paths' own code behind the expansion) on every case, the degenerate items included: the reference's bytes, and ok where it does not throw"""
+    for v in h2c_map:
+        st, out = oracle.map_uniform(v['kind'], hx(v['uniform']))
+        assert (st == 0) == (v['result'] == 'ok'), (v['name'], st, v['result'])
+        if st == 0:
+            assert out == hx(v['aff']), (v['kind'], v['name'])
+    assert oracle.call('map_uniform', 192, C.c_int(4), bytes(256))[0] == -4 and oracle.call('map_uniform', 192, C.c_int(-1), bytes(256))[0] == -4
+
+
+def test_h2c_case_lists_cover_the_classes_they_claim(h2c_map):
+    """The branches the case lists are there for, counted on Python integers (h2c_cases.swu2_classes / swu1_classes restate the two square-root methods): a class that a change
+    of the lists loses fails here instead of passing unnoticed.  The integer model itself is held to the reference: its SWU output equals the fixture's on every G2 element."""
+    import h2c_cases as H
+    g2 = [v for v in h2c_map if v['kind'] == 1]
+    cls = []
+    for v, c in zip(g2, H.cases(1)):
+        k = H.swu2_classes(H.elements_of(c)[0])
+        assert '%096x%096x%096x%096x' % (k['x'] + k['y']) == v['swu'][0], v['name']
+        cls.append(k)
+    seeded = [k for v, k in zip(g2, cls) if v['name'].startswith('seeded')]
+    assert len(seeded) == 64
+    # the Fp2 method: each of the four roots of unity res / gamma and each of the four eta candidates ec / x1c, among the seeded ordinary elements alone
+    assert {k['root'] for k in seeded if k['success']} == {0, 1, 2, 3}
+    assert {k['eta'] for k in seeded if not k['success']} == {0, 1, 2, 3}
+    # the norm method: delta = 0 with pos, delta != 0 with either pos; on both legs; roots with a zero coordinate (sgn0's z0 branch, `other` = 0); exceptional denominators
+    for leg in (True, False):
+        fam = [k for k in cls if k['a1_zero'] and k['success'] == leg]
+        assert any(k['delta_zero'] and k['pos'] for k in fam), leg
+        assert {k['pos'] for k in fam if not k['delta_zero']} == {True, False}, leg
+        assert sum(k['delta_zero'] for k in fam) >= 2 and sum(not k['delta_zero'] for k in fam) >= 2
+    assert any(k['zero_coord'] and k['y'][0] == 0 for k in cls) and any(k['zero_coord'] and k['y'][1] == 0 for k in cls)
+    assert sum(k['exceptional'] for k in cls) == 1                      # t = 0 (Z t^2 = -1 has no solution: -1 / Z is not a square of Fp2)
+    # G1: both outcomes of y1^2 gxd == gx1 among the seeded elements, and the three u with an exceptional denominator
+    g1 = [(c, H.swu1_classes(H.elements_of(c)[0])) for c in H.cases(3)]
+    assert {k['first'] for c, k in g1 if c.name.startswith('seeded')} == {True, False}
+    assert sorted(H.elements_of(c)[0] for c, k in g1 if k['exceptional'] and c.name in ('u=0', 'u=+sqrt(-1/11)', 'u=-sqrt(-1/11)')) == sorted([0, H.SQRT_M1_11, H.P - H.SQRT_M1_11])
+    # the hash kinds carry every element in either slot
+    for kind, single in ((0, 1), (2, 3)):
+        names = {c.name for c in H.cases(kind)}
+        assert all('u0: ' + c.name in names and 'u1: ' + c.name in names for c in H.cases(single) if not c.name.startswith('seeded'))

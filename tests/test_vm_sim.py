@@ -1,5 +1,6 @@
 """Compiled step programs executed by the host VM simulator, checked bit-for-bit against oracle/ (CPU only)."""
 import ctypes as C
+import functools
 import pytest
 import field_cases
 import vmsim_py
@@ -682,3 +683,55 @@ def test_norm_method_square_root_corner_cases(sim):
         if k < 12:
             real += y[1] == 0; imag += y[0] == 0
     assert real and imag and real + imag == 12
+
+
+# ---- hash-to-curve behind expand_message_xmd on chosen uniform bytes (tests/h2c_cases.py; expected bytes: the reference's, tests/golden/ref_h2c_map.json.gz) -------------
+@functools.lru_cache(maxsize=None)
+def _h2c_map():
+    import goldenio
+    vs = goldenio.load('ref_h2c_map.json.gz')['cases']
+    return {k: [v for v in vs if v['kind'] == k] for k in range(4)}
+
+
+def _check_h2c_map(kind, fn, what):
+    """every non-degenerate case of one kind in ONE launch sequence (so structured items share their programs' passes with ordinary ones): the reference's bytes, status 0"""
+    vs = [v for v in _h2c_map()[kind] if not v['degenerate']]
+    a = 192 if kind < 2 else 96
+    out, st = fn(b''.join(hx(v['uniform']) for v in vs))
+    bad = [v['name'] for i, v in enumerate(vs) if out[a * i:a * i + a] != hx(v['aff']) or (st is not None and st[i] != 0)]
+    assert not bad, (what, bad)
+
+
+@pytest.mark.parametrize('form', ['plain', 'ls2', 'norm'])
+def test_hash_to_g2_on_chosen_field_elements(sim, form):
+    """P_H2C_A / B1 (the Fp2 square root with its four root-of-unity and four eta candidates) or P_H2C_NA / NM / NB (the norm method: a1 = 0, delta = 0, roots with a zero
+    coordinate), P_H2C_B2 and the cofactor programs in their plain and two-lane forms, on the edges of the 64-byte reduction and the branch points of the SWU map"""
+    _check_h2c_map(0, lambda u: vmsim_py.hash_to_g2(sim, u, form == 'ls2', form == 'norm', status=True), form)
+
+
+def test_encode_to_g2_and_g1_maps_on_chosen_field_elements(sim):
+    """P_ENC2_A / B, P_H2C1_A / B and P_ENC1_A / B with P_G1_CLEAR: the exceptional denominators u = 0 and u = +-sqrt(-1/11), both outcomes of y1^2 gxd == gx1"""
+    _check_h2c_map(1, lambda u: (vmsim_py.encode_to_g2(sim, u), None), 'encode_to_g2')
+    _check_h2c_map(2, lambda u: vmsim_py.hash_to_g1(sim, u, 2, status=True), 'hash_to_g1 count 2')
+    _check_h2c_map(3, lambda u: vmsim_py.hash_to_g1(sim, u, 1, status=True), 'hash_to_g1 count 1')
+
+
+def test_degenerate_hash_items_give_the_zero_point(sim):
+    """u0 = +-u1 mod p is outside the contract (the two SWU points are equal or opposite: the reference's addition doubles with a formula that is not the isogenous curve's, or
+    returns its zero point and maps (0, 0) on).  pt_add_generic (curve.h) has neither branch: for equal points U = V = 0 and the sum is (0 : 0 : 0); for opposite points V = 0
+    and it is (0 : -U^3 W : 0); the homogenised isogeny sends either to (0 : 0 : 0), the complete formulas of the cofactor programs keep it there, and P_G*_TO_AFFINE reports
+    Z = 0 as status 1 with zero bytes -- in every form, and without touching the ordinary items beside them."""
+    for kind in (0, 2):
+        vs = _h2c_map()[kind]
+        deg, ordn = [v for v in vs if v['degenerate']], [v for v in vs if not v['degenerate']][-5:]
+        assert len(deg) == 3
+        mix = [deg[0], ordn[0], ordn[1], deg[1], ordn[2], deg[2], ordn[3], ordn[4]]
+        uni = b''.join(hx(v['uniform']) for v in mix)
+        a = 192 if kind == 0 else 96
+        runs = [vmsim_py.hash_to_g2(sim, uni, ls2, norm, status=True) for ls2, norm in ((False, False), (True, False), (False, True))] if kind == 0 else [vmsim_py.hash_to_g1(sim, uni, 2, status=True)]
+        for out, st in runs:
+            for i, v in enumerate(mix):
+                if v['degenerate']:
+                    assert st[i] == 1 and out[a * i:a * i + a] == bytes(a), (kind, v['name'])
+                else:
+                    assert st[i] == 0 and out[a * i:a * i + a] == hx(v['aff']), (kind, v['name'])

@@ -108,9 +108,9 @@ def g2_decompress(lib, comp, mode='sig'):
     return out.raw, list(st.raw)
 
 
-def hash_to_g2(lib, uniform, ls2=False, norm=False):
+def hash_to_g2(lib, uniform, ls2=False, norm=False, status=False):
     """uniform: n * 256 bytes of expand_message_xmd output; ls2: the two ladders of clearCofactor in their two-lane forms (launches of at most 4096 messages);
-    norm: the SWU square root by the norm method (two Fp exponentiations; launches of NBLS_H2C_NORM_MIN messages and more)"""
+    norm: the SWU square root by the norm method (two Fp exponentiations; launches of NBLS_H2C_NORM_MIN messages and more); status: return (bytes, G2_TO_AFFINE's status bytes)"""
     n = len(uniform) // 256
     T, E, Pw, Q, N, NI, out, st = buf(4 * RAW * n), buf(4 * RAW * n), buf(4 * RAW * n), buf(6 * RAW * n), buf(RAW * n), buf(RAW * n), buf(192 * n), buf(n)
     St, Pt2 = buf(32 * RAW * n), buf(12 * RAW * n)
@@ -136,7 +136,7 @@ def hash_to_g2(lib, uniform, ls2=False, norm=False):
     run(lib, 'H2C_C2_LS2' if ls2 else 'H2C_C2', n, {3: (Q, 6 * RAW), 4: (E2, 6 * RAW), 5: (S, 6 * RAW), 6: (E2, 6 * RAW), 7: (N, RAW)})
     lib.nbls_sim_fp_inv(C.c_uint(n), N, NI)
     run(lib, 'G2_TO_AFFINE', n, {3: (E2, 6 * RAW), 4: (NI, RAW), 2: (out, 192), 7: (st, 1)})
-    return out.raw
+    return (out.raw, st.raw[:n]) if status else out.raw
 
 
 def point_sum(lib, pts, g2=False):
@@ -370,7 +370,7 @@ def compress(lib, aff, g2=False):
     return out.raw
 
 
-def hash_to_g1(lib, uniform, count):
+def hash_to_g1(lib, uniform, count, status=False):
     """dev_hash_to_g1() of csrc/pipelines_codec.cpp on the simulator; uniform: n * 64 * count bytes of expand_message_xmd output"""
     n = len(uniform) // (64 * count)
     us = count * RAW
@@ -381,7 +381,7 @@ def hash_to_g1(lib, uniform, count):
     run(lib, 'G1_CLEAR', n, {3: (Q, 3 * RAW), 6: (Q2, 3 * RAW), 7: (N, RAW)})
     lib.nbls_sim_fp_inv(C.c_uint(n), N, NI)
     run(lib, 'G1_TO_AFFINE', n, {3: (Q2, 3 * RAW), 4: (NI, RAW), 2: (out, 96), 7: (st, 1)})
-    return out.raw
+    return (out.raw, st.raw[:n]) if status else out.raw
 
 
 def encode_to_g2(lib, uniform):
