@@ -1,7 +1,7 @@
 // nbls_internal.h -- what the translation units of the runtime share (runtime.cpp / tuning.cpp / pipelines_pairing.cpp / pipelines_codec.cpp / pipelines_verify.cpp /
 // pipelines_multi_verify.cpp / pipelines_threshold.cpp / pipelines_poly.cpp / pipelines_msm_batch.cpp; pool and multi-device handles: nbls_multi.cpp): the context, the map of its scratch slots (enum Slot: the one place that says which chain owns
-// which slot, checked at compile time), the launch helpers and the device-side pipelines the exported entry points are built from.  Internal functions have hidden visibility
-// (csrc/Makefile: -fvisibility=hidden).
+// which slot, checked at compile time), the launch helpers, the staged block of the host-buffer pipelines (staging.h, included at the end) and the device-side pipelines the
+// exported entry points are built from.  Internal functions have hidden visibility (csrc/Makefile: -fvisibility=hidden).
 #pragma once
 #include <hip/hip_runtime.h>
 #include "config.h"
@@ -284,19 +284,22 @@ struct StreamOrder {
 // A call that has forked work onto other streams of the context (the side streams of verifyBatch, the second half of a large pairing call) and then fails must not return while
 // those streams still run: StreamOrder records the call's end on `s` only, and the next call would free, regrow or overwrite scratch the orphaned kernels use.
 // Armed right after the fork; every error return in between synchronises the device, the success path disarms it.
+// keys: device scratch that holds key material (the recoded digits of sign's ladder), zeroed behind that wait.  The pipelines that stage a block carry the rule in Staged (staging.h).
 struct ForkGuard {
-  bool armed = true;
-  ~ForkGuard() { if (armed) (void)hipDeviceSynchronize(); }
+  bool armed = true; void* keys = nullptr; size_t key_bytes = 0;
+  ~ForkGuard() { if (armed) { (void)hipDeviceSynchronize(); if (keys) (void)hipMemset(keys, 0, key_bytes); } }
 };
 typedef std::pair<int, std::pair<const void*, size_t>> BufArg;
 static inline BufArg B(int idx, const void* p, size_t stride) { return {idx, {p, stride}}; }
 // ---- host-buffer wrappers ------------------------------------------------------------------------------------
-// Staging buffers on the device for one host-buffer call.  Round 5: taken from a pool the context keeps (best fit among the free blocks of at most four times the size; a miss
+// The pipelines that pack all their inputs into ONE page-locked block, send it as one copy and read one block back do so through Staged (staging.h).  The per-array wrappers
+// use HostIO: staging buffers on the device for one host-buffer call.  Round 5: taken from a pool the context keeps (best fit among the free blocks of at most four times the size; a miss
 // allocates) and handed back when the call returns -- every such call ends with a stream synchronisation and holds the context's mutex throughout, so a block is never reused while
 // the device still works on it.  The pool is capped (NBLS_IO_POOL_MB, default 1024): free blocks are released oldest first when it would grow past the cap.
 // Round 6: a call that fails half way may leave copies or kernels in flight on its stream, so the destructor synchronises the stream before the blocks
-// become free (on the success path the call has just synchronised: a query of an idle stream); buffers registered with secret() -- device copies of private keys -- are
-// zeroed on the call's stream before its last synchronisation (wipe()), or here when the call did not get that far: the pool hands blocks to later, unrelated calls.
+// become free (on the success path the call has just synchronised: a query of an idle stream; nbls_sign_batch declares its Staged AFTER its HostIO, so an error
+// return has waited for the whole device before this runs); buffers registered with secret() -- device copies of private keys -- are zeroed on the call's stream before its
+// last synchronisation (wipe()), or here when the call did not get that far: the pool hands blocks to later, unrelated calls.  The host copy of such keys is Staged::secret's.
 struct HostIO {
   nbls_ctx* ctx; std::vector<size_t> mine; hipStream_t s = nullptr; std::vector<std::pair<void*, size_t>> secrets; bool wiped = false;
   ~HostIO() {
@@ -440,3 +443,5 @@ struct MultiVerifyIn {
 int verify_multiple_pipeline(nbls_ctx* ctx, const MultiVerifyIn& in, int* all_ok, int8_t* status);
 int verify_batch_partial_core(nbls_ctx* ctx, size_t n, const uint8_t* sig96 /* or NULL */, const uint8_t* msgs, const uint32_t* offsets, const uint8_t* pk48,
                                      const uint8_t* dst, size_t dst_len, void* d_dst, void** d_partial, int* zero_flag, int8_t* pk_status);
+#define NBLS_STAGING_CALL   // Staged / read_back use the context and the declarations above
+#include "staging.h"

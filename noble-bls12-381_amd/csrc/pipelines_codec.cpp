@@ -123,11 +123,11 @@ int dev_expand(nbls_ctx* ctx, size_t n, const uint8_t* msgs, const uint32_t* off
   for (size_t i = 0; i < n; i++) if (offs[i + 1] < offs[i]) return NBLS_EINVAL;
   const size_t total = offs[n] - offs[0];
   uint8_t dst_hash[32];
-  if (dst_len > 255) { Sha256 c; c.update((const uint8_t*)"H2C-OVERSIZE-DST-", 17); c.update(dst, dst_len); c.final(dst_hash); dst = dst_hash; dst_len = 32; }
+  dst = effective_dst(dst, &dst_len, dst_hash);
   uint8_t *dm, *dofs, *dd, *du; int r;
   if ((r = need(ctx, SB_MSGS, total + 4, &dm)) || (r = need(ctx, SB_OFFS_DST, (n + 1) * 4 + 256, &dofs)) || (r = need(ctx, SB_UNIFORM, n * (size_t)len_in_bytes, &du))) return r;
   dd = dofs + (n + 1) * 4;
-  std::vector<uint32_t> rel(n + 1); for (size_t i = 0; i <= n; i++) rel[i] = offs[i] - offs[0];
+  std::vector<uint32_t> rel(n + 1); pack_rel(rel.data(), offs, n);   // (three copies from pageable memory straight into the slots: this path does not stage through the block)
   if (total) HIPCHK(hipMemcpyAsync(dm, msgs + offs[0], total, hipMemcpyHostToDevice, s));
   HIPCHK(hipMemcpyAsync(dofs, rel.data(), (n + 1) * 4, hipMemcpyHostToDevice, s));
   HIPCHK(hipMemcpyAsync(dd, dst, dst_len, hipMemcpyHostToDevice, s));
@@ -340,6 +340,7 @@ int dev_point_mul(nbls_ctx* ctx, bool g2, size_t n, const void* d_pts, size_t pt
     // SB_WORK_B, so the digits go to SB_WORK_C; above, affine wire points as everywhere else
     uint8_t* dig = recoded;
     if (!dig && (r = need(ctx, sac ? SB_WORK_C : SB_WORK_B, n * 128, &dig))) return r;
+    ForkGuard digits{true, dig, n * 128};   // an error return before the memset behind the ladder is enqueued zeroes the digits
     // while every wavefront of the launch is resident at once the length of ONE wavefront's instruction stream is the time: the sign-aligned recoding with one addition per bit
     // (codec.h pt_mul_sac_g2: 65 doublings + 73 additions; its table of eight points takes 101 slots = three workgroups per CU = 768 wavefronts of 8 keys); above 6144 keys the
     // windowed form, whose table of four leaves room for six workgroups per CU (NBLS_G2_SAC_MAX / NBLS_TUNE_SAC_MAX; 0 = never)
@@ -351,6 +352,7 @@ int dev_point_mul(nbls_ctx* ctx, bool g2, size_t n, const void* d_pts, size_t pt
     if ((r = run(ctx, P_G2_MUL_GLS, n, {B(1, d_pts, pt_stride), B(2, dig, 128), B(3, Pj, p), B(4, N, RAW)}, s))) return r;
     }
     HIPCHK(hipMemsetAsync(dig, 0, n * 128, s));      // the recoded digits ARE the private keys: not left in a scratch slot that later calls reuse
+    digits.armed = false;
   } else
   if (fixed) {
     if ((r = run(ctx, P_G1_MUL_FIXED, n, {B(2, d_scalars, 32), B(5, ctx->g1_fixed, 0), B(3, Pj, p), B(4, N, RAW)}, s))) return r;
@@ -374,13 +376,13 @@ int sign_points(nbls_ctx* ctx, size_t n, const void* d_uniform, void* h, const v
     uint8_t *pj, *dig;
     if ((r = need(ctx, SB_MSGS, n * 128, &dig)) || (r = ensure_side2(ctx))) return r;
     HIPCHK(hipEventRecord(ctx->ev_fork, s)); HIPCHK(hipStreamWaitEvent(ctx->side2, ctx->ev_fork, 0));
-    ForkGuard fork;
+    ForkGuard fork{true, dig, n * 128};   // the digits are the keys: an error return before the ladder has read them (dev_point_mul zeroes them behind it) zeroes them too
     LAUNCHCHK(nbls_msm_sac_launch((unsigned)n, d_keys32, dig, ctx->side2));
     HIPCHK(hipEventRecord(ctx->ev_join2, ctx->side2));
     if ((r = dev_hash_to_g2(ctx, n, d_uniform, nullptr, s, 0, 0, &pj))) return r;
     HIPCHK(hipStreamWaitEvent(s, ctx->ev_join2, 0));
-    fork.armed = false;
-    return dev_point_mul(ctx, true, n, pj, 6 * RAW, d_keys32, d_out192, d_status, s, true, true, dig);
+    if (!(r = dev_point_mul(ctx, true, n, pj, 6 * RAW, d_keys32, d_out192, d_status, s, true, true, dig))) fork.armed = false;
+    return r;
   }
   if ((r = dev_hash_to_g2(ctx, n, d_uniform, h, s))) return r;
   return dev_point_mul(ctx, true, n, h, 192, d_keys32, d_out192, d_status, s, true, true);      // H(m) is in G2: the ladder may split the key along psi
@@ -549,36 +551,27 @@ EXPORT int nbls_msm_dev(nbls_ctx* ctx, int g2, size_t n, const void* d_pts, cons
 EXPORT int nbls_sign_batch(nbls_ctx* ctx, size_t n, const uint8_t* msgs, const uint32_t* offsets, const uint8_t* dst, size_t dst_len, const uint8_t* keys32, uint8_t* out192, int8_t* status) {
   WHOLE_CALL(ctx);   // scratch and I/O staging buffers belong to this call until it returns
   if (!ctx || (n && (!offsets || !out192 || !dst || !keys32))) return NBLS_EINVAL; if (!n) return NBLS_OK;
-  // Round 6: ONE pinned staging block in, one out.  Round 5 made six copies from / to pageable memory (messages, offsets, tag, keys; signatures, statuses) with a
+  // Round 6: ONE pinned staging block in, one out (Staged, staging.h).  Round 5 made six copies from / to pageable memory (messages, offsets, tag, keys; signatures, statuses) with a
   // synchronisation in the middle: 0.5 ms of a 4.4 ms call at 8192 keys (the same call on resident inputs: 3.85 ms).  Inputs are packed into the context's pinned buffer --
   // [message bytes | n + 1 relative offsets | tag (256 B) | keys] -- and travel as one asynchronous copy; signatures and statuses come back the same way.
   for (size_t i = 0; i < n; i++) if (offsets[i + 1] < offsets[i]) return NBLS_EINVAL;
   const size_t total = offsets[n] - offsets[0];
-  uint8_t dst_hash[32];
-  if (dst_len > 255) { Sha256 c; c.update((const uint8_t*)"H2C-OVERSIZE-DST-", 17); c.update(dst, dst_len); c.final(dst_hash); dst = dst_hash; dst_len = 32; }
-  const size_t o_off = (total + 15) & ~(size_t)15, o_dst = o_off + (((n + 1) * 4 + 15) & ~(size_t)15), o_key = o_dst + 256, in_bytes = o_key + n * 32, out_bytes = n * 192 + n;
   LOCKED(ctx); HostIO io{ctx};
-  uint8_t *h = (uint8_t*)io.alloc(n * 192), *din = (uint8_t*)io.alloc(in_bytes), *dout = (uint8_t*)io.alloc(out_bytes), *du;
+  Staged st(ctx, s);   // (behind the HostIO: an error return waits for the device and zeroes the host copy of the keys before the device blocks go back to the pool)
+  const size_t o_msg = st.bytes(total ? msgs + offsets[0] : nullptr, total), o_off = st.rel(offsets, n), o_dst = st.dst(dst, dst_len), o_key = st.secret(keys32, n * 32), out_bytes = n * 192 + n;
+  uint8_t *h = (uint8_t*)io.alloc(n * 192), *din = (uint8_t*)io.alloc(st.in_bytes), *dout = (uint8_t*)io.alloc(out_bytes), *du; const uint8_t* res;
   if (!h || !din || !dout) return NBLS_EHIP;
   io.secret(din + o_key, n * 32);
   int r;
-  const size_t pin_out = (in_bytes + 63) & ~(size_t)63;      // the way back has its own part of the pinned block: nothing waits between the ladder and the copy out
-  if ((r = need(ctx, SB_UNIFORM, n * 256, &du)) || (r = ensure_pinned(ctx, pin_out + out_bytes))) return r;
-  uint8_t* pin = ctx->pinned;
-  if (total) memcpy(pin, msgs + offsets[0], total);
-  { uint32_t* rel = (uint32_t*)(pin + o_off); for (size_t i = 0; i <= n; i++) rel[i] = offsets[i] - offsets[0]; }
-  memcpy(pin + o_dst, dst, dst_len); memcpy(pin + o_key, keys32, n * 32);
-  HIPCHK(hipMemcpyAsync(din, pin, in_bytes, hipMemcpyHostToDevice, s));
-  LAUNCHCHK(nbls_xmd_launch((unsigned)n, din, din + o_off, din + o_dst, (unsigned)dst_len, du, 256, nullptr, s));
+  if ((r = need(ctx, SB_UNIFORM, n * 256, &du)) || (r = st.send(din, out_bytes))) return r;
+  LAUNCHCHK(nbls_xmd_launch((unsigned)n, din + o_msg, din + o_off, din + o_dst, (unsigned)st.dst_len, du, 256, nullptr, s));
   if ((r = sign_points(ctx, n, du, h, din + o_key, dout, dout + n * 192, s))) return r;
   if ((r = io.wipe(s))) return r;
-  HIPCHK(hipMemcpyAsync(pin + pin_out, dout, out_bytes, hipMemcpyDeviceToHost, s));
   std::vector<int8_t> tmp(n, 0);
   for (size_t i = 0; i < n; i++) if (scalar_is_zero_mod_r(keys32 + 32 * i)) tmp[i] = 5;      // (host work under the device's: normalizePrivKey's rejection, index.ts:269-279)
-  HIPCHK(hipStreamSynchronize(s));
-  memset(pin + o_key, 0, n * 32);        // the host copy of the keys does not outlive the call either
-  memcpy(out192, pin + pin_out, n * 192);
-  for (size_t i = 0; i < n; i++) if (tmp[i] != 5) tmp[i] = (int8_t)pin[pin_out + n * 192 + i];
+  if ((r = st.fetch(dout, out_bytes, &res))) return r;
+  memcpy(out192, res, n * 192);
+  for (size_t i = 0; i < n; i++) if (tmp[i] != 5) tmp[i] = (int8_t)res[n * 192 + i];
   if (status) memcpy(status, tmp.data(), n);
   return NBLS_OK;
 }
@@ -587,7 +580,7 @@ EXPORT int nbls_sign_batch(nbls_ctx* ctx, size_t n, const uint8_t* msgs, const u
 // state.  A DST longer than 255 bytes is replaced by its SHA-256 digest (RFC 9380 5.3.3), as in dev_expand and the reference's expand_message_xmd (index.ts:207-231).
 int dst_on_device(nbls_ctx* ctx, const uint8_t* dst, size_t* dst_len, hipStream_t s, uint8_t** dd) {
   uint8_t dst_hash[32];
-  if (*dst_len > 255) { Sha256 c; c.update((const uint8_t*)"H2C-OVERSIZE-DST-", 17); c.update(dst, *dst_len); c.final(dst_hash); dst = dst_hash; *dst_len = 32; }
+  dst = effective_dst(dst, dst_len, dst_hash);
   std::lock_guard<std::recursive_mutex> g_(ctx->mu); HIPCHK(hipSetDevice(ctx->device));
   if (!ctx->dst_dev) HIPCHK(hipMalloc(&ctx->dst_dev, 256));
   if (ctx->dst_host.size() != *dst_len || memcmp(ctx->dst_host.data(), dst, *dst_len)) {

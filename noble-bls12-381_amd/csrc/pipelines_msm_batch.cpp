@@ -73,24 +73,19 @@ static int msm_batch_pipeline(nbls_ctx* ctx, bool g2, size_t n_groups, const std
   const size_t max_nbw = max_ngs * nwin, max_nb = max_nbw << c, max_ng = (max_nbw * c) << (c - 1);
   const size_t tmp_bytes = std::max(sort_bytes, scan_bytes) + 16;
   // the call's block: points | scalars | offsets (what is staged) | converted points | split scalars | affine sums | statuses (what is read back)
-  const size_t o_k = al(npoints * a), o_off = o_k + al(N * 32), in_bytes = o_off + al((n_groups + 1) * 4), o_pj = in_bytes, o_ks = o_pj + al((npoints * dims + 1) * p),
+  hipStream_t s = ctx->stream;
+  Staged io(ctx, s);
+  const size_t o_pts = io.bytes(pts, npoints * a), o_k = io.bytes(scalars, N * 32), o_off = io.rel(off.data(), n_groups), o_pj = al(io.in_bytes), o_ks = o_pj + al((npoints * dims + 1) * p),
                o_out = o_ks + al(split ? (N + 1) * 32 * dims : 0), back = n_groups * a + n_groups, call_bytes = o_out + al(back);
   // a slab's block: keys, values, both sorted, ranks, pair list | counters | sort / scan scratch | sorted points | buckets | bit-slices | their halves | accumulators | norms | inverses
   const size_t s_cnt = al((maxM + 1) * 24), s_tmp = s_cnt + al(64 * 4), s_P = s_tmp + al(tmp_bytes), s_bk = s_P + al((maxM + 1) * p), s_G = s_bk + al((max_nb + 1) * p),
                s_Gh = s_G + al((max_ng + 1) * p), s_acc = s_Gh + al((max_ng / 2 + 1) * p), s_N = s_acc + al((max_ngs + 1) * p), s_NI = s_N + al((max_ngs + 1) * RAW),
                slab_bytes = s_NI + al((max_ngs + 1) * RAW);
   const ExtraProg xp = g2 ? XP_DBLADD_G2 : XP_DBLADD_G1;
-  uint8_t *CB, *SL; int r;
-  if ((r = need(ctx, SB_MSMB_CALL, call_bytes, &CB)) || (r = need(ctx, SB_MSMB_SLAB, slab_bytes, &SL)) || (r = ensure_pinned(ctx, in_bytes)) || (r = ensure_pinned_out(ctx, back)) ||
-      (r = upload_extra(ctx, xp)))
-    return r;
-  hipStream_t s = ctx->stream;
-  uint8_t* pin = ctx->pinned;
-  if (npoints) memcpy(pin, pts, npoints * a);
-  if (N) memcpy(pin + o_k, scalars, N * 32);
-  memcpy(pin + o_off, off.data(), (n_groups + 1) * 4);
-  HIPCHK(hipMemcpyAsync(CB, pin, in_bytes, hipMemcpyHostToDevice, s));
-  const uint8_t *d_pts = CB, *d_k = CB + o_k; const uint32_t* d_off = (const uint32_t*)(CB + o_off);
+  uint8_t *CB, *SL; const uint8_t* res; int r;
+  // (from the copy on a failed call returns, and a later call touches the scratch, only after the device has drained)
+  if ((r = need(ctx, SB_MSMB_CALL, call_bytes, &CB)) || (r = need(ctx, SB_MSMB_SLAB, slab_bytes, &SL)) || (r = upload_extra(ctx, xp)) || (r = io.send(CB, back))) return r;
+  const uint8_t *d_pts = CB + o_pts, *d_k = CB + o_k; const uint32_t* d_off = (const uint32_t*)(CB + o_off);
   uint8_t *Pj = CB + o_pj, *Ks = CB + o_ks, *O = CB + o_out, *OST = O + n_groups * a;
   const uint8_t* ident = g2 ? ctx->ident_g2 : ctx->ident_g1;
   const bool any_slab = maxM != 0;
@@ -137,19 +132,15 @@ static int msm_batch_pipeline(nbls_ctx* ctx, bool g2, size_t n_groups, const std
     }
     if ((r = to_affine(ctx, g2, ngs, acc, Nm, NI, O + g0 * a, OST + g0, s))) return r;
   }
-  HIPCHK(hipMemcpyAsync(ctx->pinned_out, O, back, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  memcpy(out, ctx->pinned_out, n_groups * a);
+  if ((r = io.fetch(O, back, &res))) return r;
+  memcpy(out, res, n_groups * a);
   // the zero point has no affine form: P_G*_TO_AFFINE multiplies by the inverse of a Z that is 0 mod p, and which representative of 0 the chain before it left there (dev_msm's
   // one-limb-per-lane combine leaves p) decides what the binary GCD returns for it.  The contract is all-zero bytes
-  const uint8_t* zero = ctx->pinned_out + n_groups * a;
+  const uint8_t* zero = res + n_groups * a;
   for (size_t g = 0; g < n_groups; g++) if (zero[g]) memset(out + g * a, 0, a);
   if (status) memcpy(status, zero, n_groups);
   return NBLS_OK;
 }
-
-// A failed call may leave copies or kernels queued on the context's stream: nothing returns to the caller, and no later call touches the scratch, before they have drained
-struct MsmbDrain { hipStream_t s; ~MsmbDrain() { (void)hipStreamSynchronize(s); } };
 
 static int msm_batch_host(nbls_ctx* ctx, bool g2, size_t n_groups, const uint32_t* group_offsets, size_t n_pts, const uint8_t* pts, const uint8_t* scalars, uint8_t* out, int8_t* status) {
   WHOLE_CALL(ctx);
@@ -161,7 +152,7 @@ static int msm_batch_host(nbls_ctx* ctx, bool g2, size_t n_groups, const uint32_
     for (size_t g = 0; g < n_groups; g++) if (group_offsets[g + 1] < group_offsets[g]) return NBLS_EINVAL;
     first = group_offsets[0];
     if ((size_t)group_offsets[n_groups] - first > MSMB_MAX_ITEMS) return NBLS_EINVAL;
-    for (size_t g = 0; g <= n_groups; g++) off[g] = group_offsets[g] - group_offsets[0];
+    pack_rel(off.data(), group_offsets, n_groups);
     npoints = off[n_groups];
   } else {
     if (!n_pts || n_pts > MSMB_MAX_ITEMS || n_groups * n_pts > MSMB_MAX_ITEMS) return NBLS_EINVAL;
@@ -172,7 +163,6 @@ static int msm_batch_host(nbls_ctx* ctx, bool g2, size_t n_groups, const uint32_
   // one group IS nbls_g*_msm: the same call, without the staging copy of this pipeline (0.1 ms of a 65,536-point call)
   if (n_groups == 1) return msm_host(ctx, g2, off[1], pts ? pts + first * a : nullptr, scalars ? scalars + first * 32 : nullptr, out, status);
   LOCKED(ctx);
-  MsmbDrain drain{s};
   return msm_batch_pipeline(ctx, g2, n_groups, off, group_offsets ? 0 : n_pts, npoints, pts ? pts + first * a : nullptr, scalars ? scalars + first * 32 : nullptr, out, status);
 }
 EXPORT int nbls_g1_msm_batch(nbls_ctx* ctx, size_t n_groups, const uint32_t* group_offsets, const uint8_t* pts96, const uint8_t* scalars32, uint8_t* out96, int8_t* status) {

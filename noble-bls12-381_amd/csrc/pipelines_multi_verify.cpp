@@ -96,7 +96,6 @@ static int group_keys(nbls_ctx* ctx, size_t n, size_t m, size_t maxgroup, const 
 // number of messages hashed, and of Miller loops beside the signatures')
 int verify_multiple_pipeline(nbls_ctx* ctx, const MultiVerifyIn& in, int* all_ok, int8_t* status) {
   const size_t n = in.n; const uint32_t* offsets = in.offsets; const AggKeys* agg = in.agg; const MsgGroups* mg = in.mg;
-  const uint8_t* dst = in.dst; size_t dst_len = in.dst_len;   // (a tag of more than 255 bytes is replaced by its digest below)
   uint8_t seed[32];
   if (in.seed32) memcpy(seed, in.seed32, 32);
   else { const int e = os_seed(seed); if (e) return e; }
@@ -118,42 +117,28 @@ int verify_multiple_pipeline(nbls_ctx* ctx, const MultiVerifyIn& in, int* all_ok
     for (size_t i = 0; i < n; i++) order[at[mg->msg_index[i]]++] = (uint32_t)i;
   }
   const size_t total = offsets[nh] - offsets[0];
-  uint8_t dst_hash[32];
-  if (dst_len > 255) { Sha256 c; c.update((const uint8_t*)"H2C-OVERSIZE-DST-", 17); c.update(dst, dst_len); c.final(dst_hash); dst = dst_hash; dst_len = 32; }
-  // the staged block: messages | offsets (relative) | DST | keys | signatures | seed.  Keys: n compressed keys, or (aggregates) the call's compressed keys / table indices followed by
-  // the n + 1 key offsets (relative) at o_pk + o_koff
-  const size_t o_koff = agg ? ((agg->nkeys * (agg->ks ? 4 : 48) + 15) & ~(size_t)15) : 0, key_bytes = agg ? o_koff + (n + 1) * 4 : n * 48;
-  // shared messages: the message index, then the group offsets and the sorted sets, behind the seed
-  const size_t o_off = (total + 15) & ~(size_t)15, o_dst = o_off + (((nh + 1) * 4 + 15) & ~(size_t)15), o_pk = o_dst + 256, o_sig = o_pk + ((key_bytes + 15) & ~(size_t)15),
-               o_seed = o_sig + n * 96, o_idx = o_seed + 32, o_grp = o_idx + n * 4, in_bytes = mg ? o_grp + (nh + 1 + n) * 4 : o_idx;
+  // the staged block: messages | offsets (relative) | DST | keys | key offsets | signatures | seed | message index | groups.  Keys: n compressed keys, or (aggregates) the call's
+  // compressed keys / table indices and the n + 1 key offsets (relative); shared messages: the message index, then the group offsets and the sorted sets
   // SB_RLC_PAIRS: [r_i]pk_i (shared messages: the weighted key of every group) and -G1 | H_i and S | pk_i | sig_i | result (576) | key statuses | signature statuses | MSM status |
   // bad-offsets word | (shared messages) zero-group word
   const size_t o_h = (nh + 1) * 96, o_pkd = o_h + (nh + 1) * 192, o_sgd = o_pkd + n * 96, o_res = o_sgd + n * 192, o_bad = 576 + ((2 * n + 1 + 3) & ~(size_t)3),
                st_bytes = o_bad - 576 + (mg ? 8 : 4), back = 576 + st_bytes;
   DEV_ENTER(ctx, nullptr);
-  uint8_t *c, *du, *W, *P, *Pj, *N, *NI = nullptr; int r;
-  if ((r = need(ctx, SB_STAGED, in_bytes, &c)) || (r = need(ctx, SB_UNIFORM, nh * 256, &du)) || (r = need(ctx, SB_RLC_WEIGHTS, n * 32, &W)) || (r = need(ctx, SB_RLC_PAIRS, o_res + back, &P)) ||
+  Staged io(ctx, s);
+  const uint32_t k0 = agg ? agg->key_offsets[0] : 0;
+  const size_t o_msg = io.bytes(total ? in.msgs + offsets[0] : nullptr, total), o_off = io.rel(offsets, nh), o_dst = io.dst(in.dst, in.dst_len),
+               o_pk = !agg ? io.bytes(in.pks48, n * 48) : agg->ks ? io.bytes(agg->key_index + k0, agg->nkeys * 4) : io.bytes(in.pks48 + (size_t)k0 * 48, agg->nkeys * 48),
+               o_koff = agg ? io.rel(agg->key_offsets, n) : 0, o_sig = io.bytes(in.sigs96, n * 96), o_seed = io.bytes(seed, 32),
+               o_idx = io.bytes(mg ? mg->msg_index : nullptr, mg ? n * 4 : 0), o_grp = io.bytes(groups.data(), groups.size() * 4);
+  uint8_t *c, *du, *W, *P, *Pj, *N, *NI = nullptr; const uint8_t* got; int r;
+  if ((r = need(ctx, SB_STAGED, io.in_bytes, &c)) || (r = need(ctx, SB_UNIFORM, nh * 256, &du)) || (r = need(ctx, SB_RLC_WEIGHTS, n * 32, &W)) || (r = need(ctx, SB_RLC_PAIRS, o_res + back, &P)) ||
       (r = need(ctx, SB_RLC_KEYS_PROJ, n * 3 * RAW + n, &Pj)) || (r = need(ctx, SB_RLC_KEYS_NORM, n * RAW, &N)) || (!mg && (r = need(ctx, SB_RLC_KEYS_INV, n * RAW, &NI))) ||
-      (r = ensure_pinned(ctx, in_bytes)) || (r = ensure_pinned_out(ctx, back)) || (r = ensure_scratch(ctx, n + 1)) || (r = ensure_side(ctx)) || (r = ensure_side2(ctx)))
+      (r = ensure_scratch(ctx, n + 1)) || (r = ensure_side(ctx)) || (r = ensure_side2(ctx)))
     return r;
   if (!ctx->ev_fork && hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming) != hipSuccess) { ctx->last_hip = (int)hipGetLastError(); return NBLS_EHIP; }
   uint8_t *RPK = P, *H = P + o_h, *PK = P + o_pkd, *SG = P + o_sgd, *O = P + o_res, *STK = O + 576, *STS = STK + n, *MS = STS + n;
   uint32_t* d_bad = (uint32_t*)(O + o_bad);
-  uint8_t* pin = ctx->pinned;
-  if (total) memcpy(pin, in.msgs + offsets[0], total);
-  { uint32_t* rel = (uint32_t*)(pin + o_off); for (size_t i = 0; i <= nh; i++) rel[i] = offsets[i] - offsets[0]; }
-  if (mg) { memcpy(pin + o_idx, mg->msg_index, n * 4); memcpy(pin + o_grp, groups.data(), groups.size() * 4); }
-  memcpy(pin + o_dst, dst, dst_len); memcpy(pin + o_sig, in.sigs96, n * 96); memcpy(pin + o_seed, seed, 32);
-  if (!agg) memcpy(pin + o_pk, in.pks48, n * 48);
-  else {
-    const uint32_t k0 = agg->key_offsets[0];
-    if (agg->ks) memcpy(pin + o_pk, agg->key_index + k0, agg->nkeys * 4);
-    else memcpy(pin + o_pk, in.pks48 + (size_t)k0 * 48, agg->nkeys * 48);
-    uint32_t* rel = (uint32_t*)(pin + o_pk + o_koff);
-    for (size_t j = 0; j <= n; j++) rel[j] = agg->key_offsets[j] - k0;
-  }
-  ForkGuard fork_guard;   // from the first asynchronous copy on: an error return waits for every stream of the call
-  HIPCHK(hipMemcpyAsync(c, pin, in_bytes, hipMemcpyHostToDevice, s));
+  if ((r = io.send(c, back))) return r;   // from here on an error return waits for every stream of the call
   HIPCHK(hipMemsetAsync(d_bad, 0, mg ? 8 : 4, s));
   LAUNCHCHK(nbls_rlc_weights_launch((unsigned)n, c + o_seed, W, s));
   HIPCHK(hipEventRecord(ctx->ev_fork, s));
@@ -163,7 +148,7 @@ int verify_multiple_pipeline(nbls_ctx* ctx, const MultiVerifyIn& in, int* all_ok
   // keys (side2): PointG1.fromHex, index.ts:301-326 (aggregates: of every key, then one sum per set), then [r_i]pk_i
   HIPCHK(hipStreamWaitEvent(ctx->side2, ctx->ev_fork, 0));
   if (!agg) { if ((r = dev_decompress(ctx, false, n, c + o_pk, PK, STK, ctx->side2, DEC_KEYS))) return r; }
-  else if ((r = aggregate_keys(ctx, n, *agg, c + o_pk, (const uint32_t*)(c + o_pk + o_koff), PK, (int8_t*)STK, ctx->side2))) return r;
+  else if ((r = aggregate_keys(ctx, n, *agg, c + o_pk, (const uint32_t*)(c + o_koff), PK, (int8_t*)STK, ctx->side2))) return r;
   if ((r = run(ctx, P_G1_MUL64, n, {B(0, PK, 96), B(2, W, 32), B(3, Pj, 3 * RAW), B(4, N, RAW)}, ctx->side2))) return r;
   if (mg) {
     const uint32_t* d_goff = (const uint32_t*)(c + o_grp);
@@ -171,7 +156,7 @@ int verify_multiple_pipeline(nbls_ctx* ctx, const MultiVerifyIn& in, int* all_ok
   } else if ((r = to_affine(ctx, false, n, Pj, N, NI, RPK, Pj + n * 3 * RAW, ctx->side2, false))) return r;
   HIPCHK(hipEventRecord(ctx->ev_join2, ctx->side2));
   // messages (s): expand_message_xmd, PointG2.hashToCurve (index.ts:481-490)
-  LAUNCHCHK(nbls_xmd_launch((unsigned)nh, c, c + o_off, c + o_dst, (unsigned)dst_len, du, 256, d_bad, s));
+  LAUNCHCHK(nbls_xmd_launch((unsigned)nh, c + o_msg, c + o_off, c + o_dst, (unsigned)io.dst_len, du, 256, d_bad, s));
   if ((r = dev_hash_to_g2(ctx, nh, du, H, s))) return r;
   // S = sum_i [r_i]sig_i behind the signatures on the side stream (enqueued last: dev_msm waits on the host for its stream once, with the hash chain and the keys in flight)
   if ((r = dev_msm(ctx, true, n, SG, W, 64, H + nh * 192, MS, ctx->side, MSM_RLC))) return r;
@@ -182,10 +167,8 @@ int verify_multiple_pipeline(nbls_ctx* ctx, const MultiVerifyIn& in, int* all_ok
   size_t m = 0;
   uint8_t* res = ctx->F;
   if ((r = miller_values(ctx, nh + 1, RPK, H, &m, s)) || (r = reduce_product(ctx, m, &res, s)) || (r = finish_single(ctx, res, 1, O, s))) return r;
-  HIPCHK(hipMemcpyAsync(ctx->pinned_out, O, back, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  fork_guard.armed = false;      // synchronised: both side streams were joined into s
-  std::vector<uint8_t> rb(ctx->pinned_out, ctx->pinned_out + back);
+  if ((r = io.fetch(O, back, &got))) return r;   // synchronised: both side streams were joined into s
+  std::vector<uint8_t> rb(got, got + back);      // (the per-set pass reads back through the same block)
   uint32_t bad = 0, gzero = 0; memcpy(&bad, rb.data() + o_bad, 4);
   if (bad) return NBLS_EINVAL;
   if (mg) memcpy(&gzero, rb.data() + o_bad + 4, 4);
@@ -208,14 +191,12 @@ int verify_multiple_pipeline(nbls_ctx* ctx, const MultiVerifyIn& in, int* all_ok
       (r = final_exp_pipeline(ctx, n, ctx->F, E, s)))
     return r;
   LAUNCHCHK(nbls_rlc_is_one_launch((unsigned)n, E, V, s));
-  if ((r = ensure_pinned_out(ctx, n))) return r;
-  HIPCHK(hipMemcpyAsync(ctx->pinned_out, V, n, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
+  if ((r = read_back(ctx, s, V, n, &got))) return r;
   int all = 1;
   for (size_t i = 0; i < n; i++) {
     // the reference's order (oracle_verify): the key decodes, the message hashes, the signature decodes, the pairing throws on a zero point ("No pairings at point of Infinity")
     const int8_t k = stk[i], g = sts[i];
-    const int8_t v = k >= 2 ? k : g >= 2 ? (int8_t)(10 + g) : k == 1 ? 1 : g == 1 ? 11 : ctx->pinned_out[i] ? 0 : NBLS_ST_NOT_VERIFIED;
+    const int8_t v = k >= 2 ? k : g >= 2 ? (int8_t)(10 + g) : k == 1 ? 1 : g == 1 ? 11 : got[i] ? 0 : NBLS_ST_NOT_VERIFIED;
     status[i] = v;
     if (v) all = 0;
   }
@@ -239,12 +220,7 @@ static int multi_verify(nbls_ctx* ctx, MultiVerifyIn in, AggKeys* agg, bool inde
   if (agg) {
     const uint32_t* ko = agg->key_offsets;
     if (!ko) return NBLS_EINVAL;
-    for (size_t j = 0; j < n; j++) {
-      if (ko[j + 1] <= ko[j]) return NBLS_EINVAL;
-      agg->maxset = std::max(agg->maxset, (size_t)(ko[j + 1] - ko[j]));
-    }
-    agg->nkeys = ko[n] - ko[0];
-    if (agg->nkeys > AGG_MAX_KEYS) return NBLS_EINVAL;
+    if (!strict_groups(n, ko, &agg->nkeys, &agg->maxset) || agg->nkeys > AGG_MAX_KEYS) return NBLS_EINVAL;
     if (indexed) for (size_t k = ko[0]; k < ko[n]; k++) if (agg->key_index[k] >= agg->ks->n) return NBLS_EINVAL;
   }
   in.agg = agg; in.mg = mg;

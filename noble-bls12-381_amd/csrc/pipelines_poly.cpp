@@ -15,17 +15,6 @@
 static const size_t POLY_MAX_COEFS = (size_t)1 << 24, POLY_MAX_GROUP = (size_t)1 << 16, POLY_MAX_IDS = (size_t)1 << 22;
 static const size_t POLY_SLAB_DEFAULT = (size_t)1 << 18;   // identifiers per slab: 2^18 x (accumulator, norm, inverse, affine point, step coefficient) = 160 MB in G1, 285 MB in G2
 
-// strictly increasing offsets -> the number of entries and the largest group
-static int check_offsets(size_t n_groups, const uint32_t* off, size_t* n, size_t* maxgroup) {
-  size_t mx = 0;
-  for (size_t g = 0; g < n_groups; g++) {
-    if (off[g + 1] <= off[g]) return NBLS_EINVAL;
-    mx = std::max(mx, (size_t)(off[g + 1] - off[g]));
-  }
-  *n = off[n_groups] - off[0]; *maxgroup = mx;
-  return NBLS_OK;
-}
-
 static int poly_pipeline(nbls_ctx* ctx, bool g2, size_t n_groups, const uint32_t* coff, size_t C, size_t T, const uint8_t* coefs, const uint32_t* ioff, size_t M, const uint8_t* ids32,
                          uint8_t* out, int8_t* status) {
   const size_t e = g2 ? 96 : 48, a = 2 * e, p = (g2 ? 6 : 3) * RAW;
@@ -34,27 +23,21 @@ static int poly_pipeline(nbls_ctx* ctx, bool g2, size_t n_groups, const uint32_t
   const ExtraProg xp = g2 ? (low16 ? XP_POLY_G2_16 : XP_POLY_G2_256) : (low16 ? XP_POLY_G1_16 : XP_POLY_G1_256);
   const size_t slab = std::min(M, ctx->poly_slab ? ctx->poly_slab : POLY_SLAB_DEFAULT);
   // the staged block: coefficients | identifiers | coefficient offsets | identifier offsets (both relative); what is read back: compressed points | statuses
-  const size_t o_ids = C * e, o_coff = o_ids + M * 32, o_ioff = o_coff + (n_groups + 1) * 4, in_bytes = o_ioff + (n_groups + 1) * 4, back = M * e + M;
   DEV_ENTER(ctx, nullptr);
+  Staged io(ctx, s);
+  const size_t o_cf = io.bytes(coefs + (size_t)coff[0] * e, C * e), o_ids = io.bytes(ids, M * 32), o_coff = io.rel(coff, n_groups), o_ioff = io.rel(ioff, n_groups), back = M * e + M;
   uint8_t *c, *CF, *LB, *AC, *SP, *O; int r;
-  if ((r = need(ctx, SB_STAGED, in_bytes, &c)) || (r = need(ctx, SB_POLY_COEFS, C * (a + p) + C, &CF)) || (r = need(ctx, SB_POLY_LABELS, (2 * C + n_groups + M) * 4 + C, &LB)) ||
+  if ((r = need(ctx, SB_STAGED, io.in_bytes, &c)) || (r = need(ctx, SB_POLY_COEFS, C * (a + p) + C, &CF)) || (r = need(ctx, SB_POLY_LABELS, (2 * C + n_groups + M) * 4 + C, &LB)) ||
       (r = need(ctx, SB_POLY_ACC, slab * (p + 2 * RAW + a), &AC)) || (r = need(ctx, SB_POLY_STEP, slab * p, &SP)) || (r = need(ctx, SB_POLY_OUT, ((back + 15) & ~(size_t)15) + M, &O)) ||
-      (r = ensure_pinned(ctx, in_bytes)) || (r = ensure_pinned_out(ctx, back)) || (r = upload_extra(ctx, xp)))
+      (r = upload_extra(ctx, xp)) || (r = io.send(c, back)))
     return r;
   uint8_t *AFF = CF, *PR = AFF + C * a; int8_t* ST = (int8_t*)(PR + C * p);
   uint32_t *set_id = (uint32_t*)LB, *rank = set_id + C, *first = rank + C, *group_of = first + n_groups; int8_t* GST = (int8_t*)(group_of + M);
   uint8_t *ACC = AC, *N = ACC + slab * p, *NI = N + slab * RAW, *AFF2 = NI + slab * RAW;
   uint8_t *OST = O + M * e, *Z = O + ((back + 15) & ~(size_t)15);
-  uint8_t* pin = ctx->pinned;
-  memcpy(pin, coefs + (size_t)coff[0] * e, C * e);
-  memcpy(pin + o_ids, ids, M * 32);
-  { uint32_t* rel = (uint32_t*)(pin + o_coff); for (size_t g = 0; g <= n_groups; g++) rel[g] = coff[g] - coff[0]; }
-  { uint32_t* rel = (uint32_t*)(pin + o_ioff); for (size_t g = 0; g <= n_groups; g++) rel[g] = ioff[g] - ioff[0]; }
-  ForkGuard guard;   // from the first asynchronous copy on: an error return waits for the device
-  HIPCHK(hipMemcpyAsync(c, pin, in_bytes, hipMemcpyHostToDevice, s));
   const uint8_t* d_ids = c + o_ids;
   const uint32_t *d_coff = (const uint32_t*)(c + o_coff), *d_ioff = (const uint32_t*)(c + o_ioff);
-  if ((r = dev_decompress(ctx, g2, C, c, AFF, ST, s))) return r;
+  if ((r = dev_decompress(ctx, g2, C, c + o_cf, AFF, ST, s))) return r;
   if ((r = run(ctx, g2 ? P_G2_TO_PROJ : P_G1_TO_PROJ, C, {B(g2 ? 1 : 0, AFF, a), B(3, PR, p)}, s))) return r;
   // every coefficient's group and status, every group's first position with a status >= 2; then the identity where the status is not 0 (in place)
   LAUNCHCHK(nbls_agg_keys_launch((unsigned)C, (unsigned)n_groups, d_coff, nullptr, ST, set_id, rank, GST, first, s));
@@ -74,18 +57,13 @@ static int poly_pipeline(nbls_ctx* ctx, bool g2, size_t n_groups, const uint32_t
     if ((r = run(ctx, g2 ? P_G2_COMPRESS : P_G1_COMPRESS, ms, {B(0, AFF2, a), B(2, O + k0 * e, e)}, s))) return r;
   }
   LAUNCHCHK(nbls_poly_status_launch((unsigned)M, (unsigned)e, group_of, first, GST, Z, O, OST, s));
-  HIPCHK(hipMemcpyAsync(ctx->pinned_out, O, back, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  guard.armed = false;
-  memcpy(out, ctx->pinned_out, M * e);
-  if (status) memcpy(status, ctx->pinned_out + M * e, M);
-  return NBLS_OK;
+  return io.fetch_to(O, out, M * e, status, M);
 }
 
 static int poly_eval(nbls_ctx* ctx, bool g2, size_t n_groups, const uint32_t* coff, const uint8_t* coefs, const uint32_t* ioff, const uint8_t* ids32, uint8_t* out, int8_t* status) {
   WHOLE_CALL(ctx);
   size_t C = 0, T = 0, M = 0, maxids = 0;
-  if (!ctx || !coff || !coefs || !ioff || !ids32 || !out || !n_groups || n_groups > POLY_MAX_IDS || check_offsets(n_groups, coff, &C, &T) || check_offsets(n_groups, ioff, &M, &maxids) ||
+  if (!ctx || !coff || !coefs || !ioff || !ids32 || !out || !n_groups || n_groups > POLY_MAX_IDS || !strict_groups(n_groups, coff, &C, &T) || !strict_groups(n_groups, ioff, &M, &maxids) ||
       T > POLY_MAX_GROUP || C > POLY_MAX_COEFS || M > POLY_MAX_IDS)
     return NBLS_EINVAL;
   return poly_pipeline(ctx, g2, n_groups, coff, C, T, coefs, ioff, M, ids32, out, status);

@@ -15,14 +15,8 @@ static const size_t THR_MAX_SHARES = (size_t)1 << 24, THR_MAX_GROUP = (size_t)1 
 
 // what the three group calls refuse before any device work; fills in the number of shares and the largest group
 static int check_groups(size_t n_groups, const uint32_t* off, size_t* n, size_t* maxgroup) {
-  if (!n_groups || !off || n_groups > THR_MAX_SHARES) return NBLS_EINVAL;
-  size_t mx = 0;
-  for (size_t g = 0; g < n_groups; g++) {
-    if (off[g + 1] <= off[g]) return NBLS_EINVAL;
-    mx = std::max(mx, (size_t)(off[g + 1] - off[g]));
-  }
-  *n = off[n_groups] - off[0]; *maxgroup = mx;
-  return *n > THR_MAX_SHARES || mx > THR_MAX_GROUP ? NBLS_EINVAL : NBLS_OK;
+  if (!n_groups || !off || n_groups > THR_MAX_SHARES || !strict_groups(n_groups, off, n, maxgroup)) return NBLS_EINVAL;
+  return *n > THR_MAX_SHARES || *maxgroup > THR_MAX_GROUP ? NBLS_EINVAL : NBLS_OK;
 }
 
 // the coefficients of n identifiers (wire bytes, device) in n_groups groups (d_off: relative offsets, device) on `s` -> *L32: n canonical scalars (at dst when the caller has a
@@ -41,24 +35,19 @@ static int combine_pipeline(nbls_ctx* ctx, bool g2, size_t n_groups, const uint3
                             int8_t* status) {
   const size_t e = g2 ? 96 : 48, a = 2 * e, p = (g2 ? 6 : 3) * RAW;
   // the staged block: identifiers | shares | offsets (relative); what is read back: compressed sums | statuses
-  const size_t o_sh = n * 32, o_off = o_sh + n * e, in_bytes = o_off + (n_groups + 1) * 4, back = n_groups * e + n_groups;
   DEV_ENTER(ctx, nullptr);
+  Staged io(ctx, s);
+  const size_t o_ids = io.bytes(ids32 + (size_t)off[0] * 32, n * 32), o_sh = io.bytes(shares + (size_t)off[0] * e, n * e), o_off = io.rel(off, n_groups), back = n_groups * e + n_groups;
   uint8_t *c, *SH, *O; int r;
-  if ((r = need(ctx, SB_STAGED, in_bytes, &c)) || (r = need(ctx, SB_THR_SHARES, n * a + n, &SH)) || (r = need(ctx, SB_THR_OUT, n_groups * a + ((back + 15) & ~(size_t)15), &O)) ||
-      (r = ensure_pinned(ctx, in_bytes)) || (r = ensure_pinned_out(ctx, back)))
+  if ((r = need(ctx, SB_STAGED, io.in_bytes, &c)) || (r = need(ctx, SB_THR_SHARES, n * a + n, &SH)) || (r = need(ctx, SB_THR_OUT, n_groups * a + ((back + 15) & ~(size_t)15), &O)) ||
+      (r = io.send(c, back)))
     return r;
   int8_t* ST = (int8_t*)(SH + n * a);
   uint8_t *AFF = O + ((back + 15) & ~(size_t)15), *OST = O + n_groups * e;
-  uint8_t* pin = ctx->pinned;
-  memcpy(pin, ids32 + (size_t)off[0] * 32, n * 32);
-  memcpy(pin + o_sh, shares + (size_t)off[0] * e, n * e);
-  { uint32_t* rel = (uint32_t*)(pin + o_off); for (size_t g = 0; g <= n_groups; g++) rel[g] = off[g] - off[0]; }
-  ForkGuard guard;   // from the first asynchronous copy on: an error return waits for the device
-  HIPCHK(hipMemcpyAsync(c, pin, in_bytes, hipMemcpyHostToDevice, s));
   const uint32_t* d_off = (const uint32_t*)(c + o_off);
   if ((r = dev_decompress(ctx, g2, n, c + o_sh, SH, ST, s))) return r;
   uint8_t *L32, *Pj; uint32_t* bad;
-  if ((r = dev_lagrange(ctx, n, n_groups, d_off, c, nullptr, &L32, &bad, s))) return r;
+  if ((r = dev_lagrange(ctx, n, n_groups, d_off, c + o_ids, nullptr, &L32, &bad, s))) return r;
   // the ladders.  G2: the psi-split forms of sign -- up to sac_max items the sign-aligned one, which reads raw projective points (made here, in the slot sign's hash chain leaves
   // them in); a share that did not decode yields some point or other, which segment_sums replaces by the identity
   const void* pts = SH; size_t stride = a;
@@ -72,12 +61,7 @@ static int combine_pipeline(nbls_ctx* ctx, bool g2, size_t n_groups, const uint3
   if ((r = segment_sums(ctx, g2, SEG_THR, n, n_groups, d_off, nullptr, Pj, ST, maxgroup, AFF, &o, s))) return r;
   if ((r = run(ctx, g2 ? P_G2_COMPRESS : P_G1_COMPRESS, n_groups, {B(0, AFF, a), B(2, O, e)}, s))) return r;
   LAUNCHCHK(nbls_fr_combine_status_launch((unsigned)n_groups, (unsigned)e, bad, o.first, o.st, o.zero, O, OST, s));
-  HIPCHK(hipMemcpyAsync(ctx->pinned_out, O, back, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  guard.armed = false;
-  memcpy(out, ctx->pinned_out, n_groups * e);
-  if (status) memcpy(status, ctx->pinned_out + n_groups * e, n_groups);
-  return NBLS_OK;
+  return io.fetch_to(O, out, n_groups * e, status, n_groups);
 }
 
 static int combine_shares(nbls_ctx* ctx, bool g2, size_t n_groups, const uint32_t* off, const uint8_t* ids32, const uint8_t* shares, uint8_t* out, int8_t* status) {
@@ -97,23 +81,15 @@ EXPORT int nbls_lagrange_at_zero(nbls_ctx* ctx, size_t n_groups, const uint32_t*
   WHOLE_CALL(ctx);
   size_t n = 0, maxgroup = 0;
   if (!ctx || !ids32 || !out32 || check_groups(n_groups, group_offsets, &n, &maxgroup)) return NBLS_EINVAL;
-  const size_t o_off = n * 32, in_bytes = o_off + (n_groups + 1) * 4, back = n * 32 + n_groups;   // what is read back: coefficients | statuses
+  // the staged block: identifiers | offsets (relative); what is read back: coefficients | statuses
   DEV_ENTER(ctx, nullptr);
+  Staged io(ctx, s);
+  const size_t o_ids = io.bytes(ids32 + (size_t)group_offsets[0] * 32, n * 32), o_off = io.rel(group_offsets, n_groups), back = n * 32 + n_groups;
   uint8_t *c, *O, *L32; uint32_t* bad; int r;
-  if ((r = need(ctx, SB_STAGED, in_bytes, &c)) || (r = need(ctx, SB_THR_OUT, back, &O)) || (r = ensure_pinned(ctx, in_bytes)) || (r = ensure_pinned_out(ctx, back))) return r;
-  uint8_t* pin = ctx->pinned;
-  memcpy(pin, ids32 + (size_t)group_offsets[0] * 32, n * 32);
-  { uint32_t* rel = (uint32_t*)(pin + o_off); for (size_t g = 0; g <= n_groups; g++) rel[g] = group_offsets[g] - group_offsets[0]; }
-  ForkGuard guard;
-  HIPCHK(hipMemcpyAsync(c, pin, in_bytes, hipMemcpyHostToDevice, s));
-  if ((r = dev_lagrange(ctx, n, n_groups, (const uint32_t*)(c + o_off), c, O, &L32, &bad, s))) return r;
+  if ((r = need(ctx, SB_STAGED, io.in_bytes, &c)) || (r = need(ctx, SB_THR_OUT, back, &O)) || (r = io.send(c, back))) return r;
+  if ((r = dev_lagrange(ctx, n, n_groups, (const uint32_t*)(c + o_off), c + o_ids, O, &L32, &bad, s))) return r;
   LAUNCHCHK(nbls_fr_group_status_launch((unsigned)n_groups, bad, O + n * 32, s));
-  HIPCHK(hipMemcpyAsync(ctx->pinned_out, O, back, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  guard.armed = false;
-  memcpy(out32, ctx->pinned_out, n * 32);
-  if (status) memcpy(status, ctx->pinned_out + n * 32, n_groups);
-  return NBLS_OK;
+  return io.fetch_to(O, out32, n * 32, status, n_groups);
 }
 
 EXPORT int nbls_fr_op_batch(nbls_ctx* ctx, int op, size_t n, const uint8_t* a32, const uint8_t* b32, uint8_t* out32, int8_t* status) {
@@ -121,19 +97,11 @@ EXPORT int nbls_fr_op_batch(nbls_ctx* ctx, int op, size_t n, const uint8_t* a32,
   if (!ctx || op < NBLS_FROP_ADD || op > NBLS_FROP_POW || n > THR_MAX_SHARES || (n && (!a32 || !out32 || (!unary && !b32)))) return NBLS_EINVAL;
   if (!n) return NBLS_OK;
   // the staged block: first operands | second operands (binary operations); what is read back: results | statuses
-  const size_t in_bytes = n * (unary ? 32 : 64), back = n * 32 + n;
   DEV_ENTER(ctx, nullptr);
+  Staged io(ctx, s);
+  const size_t o_a = io.bytes(a32, n * 32), o_b = io.bytes(b32, unary ? 0 : n * 32), back = n * 32 + n;
   uint8_t *c, *O; int r;
-  if ((r = need(ctx, SB_STAGED, in_bytes, &c)) || (r = need(ctx, SB_THR_OUT, back, &O)) || (r = ensure_pinned(ctx, in_bytes)) || (r = ensure_pinned_out(ctx, back))) return r;
-  memcpy(ctx->pinned, a32, n * 32);
-  if (!unary) memcpy(ctx->pinned + n * 32, b32, n * 32);
-  ForkGuard guard;
-  HIPCHK(hipMemcpyAsync(c, ctx->pinned, in_bytes, hipMemcpyHostToDevice, s));
-  LAUNCHCHK(nbls_fr_op_launch((unsigned)n, op, c, unary ? nullptr : c + n * 32, O, O + n * 32, s));
-  HIPCHK(hipMemcpyAsync(ctx->pinned_out, O, back, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  guard.armed = false;
-  memcpy(out32, ctx->pinned_out, n * 32);
-  if (status) memcpy(status, ctx->pinned_out + n * 32, n);
-  return NBLS_OK;
+  if ((r = need(ctx, SB_STAGED, io.in_bytes, &c)) || (r = need(ctx, SB_THR_OUT, back, &O)) || (r = io.send(c, back))) return r;
+  LAUNCHCHK(nbls_fr_op_launch((unsigned)n, op, c + o_a, unary ? nullptr : c + o_b, O, O + n * 32, s));
+  return io.fetch_to(O, out32, n * 32, status, n);
 }

@@ -162,12 +162,11 @@ int verify_pipeline(nbls_ctx* ctx, size_t n, const VerifyIn& in, int final_exp, 
   if ((r = finish_single(ctx, res, final_exp, final_exp ? (void*)O : d_out, s))) return r;
   // the result and the statuses lie behind one another (O | ST | bad-offsets word): ONE copy into page-locked memory (round 6: two copies into pageable memory before)
   const size_t st_bytes = ((np + 3) & ~(size_t)3) + 4, back = 576 + st_bytes;
-  if ((r = ensure_pinned_out(ctx, back))) return r;
-  HIPCHK(hipMemcpyAsync(ctx->pinned_out, O, back, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
+  const uint8_t* got;
+  if ((r = read_back(ctx, s, O, back, &got))) return r;
   fork_guard.armed = false;      // synchronised: every forked stream was joined into s
-  if (final_exp) memcpy(out, ctx->pinned_out, 576);
-  memcpy(st.data(), ctx->pinned_out + 576, st_bytes);
+  if (final_exp) memcpy(out, got, 576);
+  memcpy(st.data(), got + 576, st_bytes);
   uint32_t bad = 0; memcpy(&bad, st.data() + ((np + 3) & ~(size_t)3), 4);
   if (bad_offsets) *bad_offsets = bad != 0;
   st.resize(np);
@@ -202,21 +201,15 @@ EXPORT int nbls_verify_batch(nbls_ctx* ctx, size_t n, const uint8_t* sig96, cons
   // whose mutex this call holds).
   for (size_t i = 0; i < n; i++) if (offsets[i + 1] < offsets[i]) return NBLS_EINVAL;
   const size_t total = offsets[n] - offsets[0];
-  uint8_t dst_hash[32];
-  if (dst_len > 255) { Sha256 c; c.update((const uint8_t*)"H2C-OVERSIZE-DST-", 17); c.update(dst, dst_len); c.final(dst_hash); dst = dst_hash; dst_len = 32; }
-  const size_t o_off = (total + 15) & ~(size_t)15, o_dst = o_off + (((n + 1) * 4 + 15) & ~(size_t)15), o_pk = o_dst + 256, o_sig = o_pk + ((n * 48 + 15) & ~(size_t)15), in_bytes = o_sig + 96;
   LOCKED(ctx);
+  Staged io(ctx, s);   // messages | offsets (relative) | DST | keys | signature
+  const size_t o_msg = io.bytes(total ? msgs + offsets[0] : nullptr, total), o_off = io.rel(offsets, n), o_dst = io.dst(dst, dst_len), o_pk = io.bytes(pk48, n * 48), o_sig = io.bytes(sig96, 96);
   uint8_t *c, *du; int r;
-  if ((r = need(ctx, SB_STAGED, in_bytes, &c)) || (r = need(ctx, SB_UNIFORM, n * 256, &du)) || (r = ensure_pinned(ctx, in_bytes))) return r;
-  uint8_t* pin = ctx->pinned;
-  if (total) memcpy(pin, msgs + offsets[0], total);
-  { uint32_t* rel = (uint32_t*)(pin + o_off); for (size_t i = 0; i <= n; i++) rel[i] = offsets[i] - offsets[0]; }
-  memcpy(pin + o_dst, dst, dst_len); memcpy(pin + o_pk, pk48, n * 48); memcpy(pin + o_sig, sig96, 96);
-  HIPCHK(hipMemcpyAsync(c, pin, in_bytes, hipMemcpyHostToDevice, s));
-  ForkGuard in_flight;   // an error return below must not leave the copy out of ctx->pinned or the hashing kernel running: the next call repacks the block and may regrow the slots
-  LAUNCHCHK(nbls_xmd_launch((unsigned)n, c, c + o_off, c + o_dst, (unsigned)dst_len, du, 256, nullptr, s));
-  r = nbls_verify_batch_dev_inputs(ctx, n, c + o_sig, du, c + o_pk, ok, nullptr, nullptr);
-  if (r == NBLS_OK || r == NBLS_EDECODE) in_flight.armed = false;   // both verdicts are read behind the call's synchronisation
+  // an error return behind the copy must not leave it or the hashing kernel running: the next call repacks the block and may regrow the slots
+  if ((r = need(ctx, SB_STAGED, io.in_bytes, &c)) || (r = need(ctx, SB_UNIFORM, n * 256, &du)) || (r = io.send(c, 0))) return r;
+  LAUNCHCHK(nbls_xmd_launch((unsigned)n, c + o_msg, c + o_off, c + o_dst, (unsigned)io.dst_len, du, 256, nullptr, s));
+  r = nbls_verify_batch_dev_inputs(ctx, n, c + o_sig, du, c + o_pk, ok, nullptr, nullptr);   // (the read-back and the call's synchronisation are verify_pipeline's)
+  if (r == NBLS_OK || r == NBLS_EDECODE) io.done();   // both verdicts are read behind that synchronisation
   return r;
 }
 // verifyBatch with EVERYTHING resident in HBM (bench.py's verifyBatch value): signature, the message bytes with their n + 1 offsets (uint32, relative to d_msgs),

@@ -49,10 +49,17 @@ struct Sha256 {
     for (int i = 0; i < 8; i++) { out[4 * i] = h[i] >> 24; out[4 * i + 1] = h[i] >> 16; out[4 * i + 2] = h[i] >> 8; out[4 * i + 3] = h[i]; }
   }
 };
+// RFC 9380 5.3.3, the one statement of the rule: a tag of more than 255 bytes is replaced by its digest.  Returns the tag to hash with (dst, or scratch32) and sets *len to its length
+static inline const uint8_t* effective_dst(const uint8_t* dst, size_t* len, uint8_t* scratch32) {
+  if (*len <= 255) return dst;
+  Sha256 c; c.update((const uint8_t*)"H2C-OVERSIZE-DST-", 17); c.update(dst, *len); c.final(scratch32);
+  *len = 32;
+  return scratch32;
+}
 // out[len_in_bytes]; returns false when ell > 255 (the reference throws 'Invalid xmd length')
 static inline bool expand_message_xmd(const uint8_t* msg, size_t msg_len, const uint8_t* dst, size_t dst_len, uint8_t* out, size_t len_in_bytes) {
   uint8_t dst_hash[32];
-  if (dst_len > 255) { Sha256 c; c.update((const uint8_t*)"H2C-OVERSIZE-DST-", 17); c.update(dst, dst_len); c.final(dst_hash); dst = dst_hash; dst_len = 32; }
+  dst = effective_dst(dst, &dst_len, dst_hash);
   size_t ell = (len_in_bytes + 31) / 32; if (ell > 255) return false;
   uint8_t dlen = (uint8_t)dst_len, zpad[64] = {0}, lib[2] = {(uint8_t)(len_in_bytes >> 8), (uint8_t)len_in_bytes}, zero = 0, b0[32], bi[32];
   { Sha256 c; c.update(zpad, 64); c.update(msg, msg_len); c.update(lib, 2); c.update(&zero, 1); c.update(dst, dst_len); c.update(&dlen, 1); c.final(b0); }

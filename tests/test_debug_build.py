@@ -57,6 +57,34 @@ def test_sanitizer_selftest():
     assert 'ERROR: AddressSanitizer' not in out.stderr and 'runtime error' not in out.stderr, out.stderr
 
 
+@pytest.mark.skipif(subprocess.call(['sh', '-c', 'echo "int main(){}" | g++ -x c++ -fsanitize=address,undefined -o /dev/null - 2>/dev/null']) != 0, reason='no sanitizer runtime')
+def test_sanitizer_staging():
+    """the pure part of csrc/staging.h (tests/c/staging_test.cpp): part offsets, relative offsets and the oversize-tag rule, packed into heap blocks of exactly the layout's size"""
+    import hashlib
+    subprocess.check_call(['make', '-s', '-C', CSRC, '../staging_test'])
+    env = dict(os.environ, ASAN_OPTIONS='detect_leaks=0')
+    out = subprocess.run([os.path.join(ROOT, 'noble-bls12-381_amd', 'staging_test')], capture_output=True, text=True, timeout=60, env=env)
+    assert out.returncode == 0, out.stdout + out.stderr
+    assert 'failures 0' in out.stdout, out.stdout
+    assert 'ERROR: AddressSanitizer' not in out.stderr and 'runtime error' not in out.stderr, out.stderr
+    lines = out.stdout.splitlines()
+    lay = [ln for ln in lines if ln.startswith('layout')][0].split()
+    parts = [tuple(int(x) for x in p.split(':')) for p in lay[1:-2]]      # (bytes, offset)
+    assert [b for b, _ in parts] == [0, 1, 15, 16, 17, 0]
+    end = 0
+    for size, off in parts:
+        assert off % 16 == 0 and off >= end      # aligned, increasing, disjoint: no part starts inside the one before
+        end = off + size
+    assert int(lay[-1]) == end                   # in_bytes is the end of the last part
+    assert [ln.split()[1:] for ln in lines if ln.startswith('rel')] == [['0', '0', '4', '35'], ['0', '5']]
+    tags = {int(ln.split()[1]): (int(ln.split()[3]), bytes.fromhex(ln.split()[5]) if len(ln.split()) > 5 else b'') for ln in lines if ln.startswith('dst')}
+    assert sorted(tags) == [0, 1, 255, 256, 300]
+    for n, (eff, got) in tags.items():
+        dst = bytes((7 * i + 3) & 0xff for i in range(n))
+        want = dst if n <= 255 else hashlib.sha256(b'H2C-OVERSIZE-DST-' + dst).digest()
+        assert (eff, got) == (len(want), want), n
+
+
 @pytest.mark.gpu
 def test_checked_engine_library(golden):
     """the golden pairings, a Miller product and a verifyBatch through the checked library in a fresh process (NBLS_LIBRARY selects it)"""
