@@ -459,8 +459,13 @@ const char* nbls_program_name(int prog);
    NBLS_AOT=0, or the build-time and run-time compilations of the program disagree); NULL on a bad index.  The string is static. */
 const char* nbls_program_kernel(nbls_ctx* ctx, int prog);
 /* the same for a step program outside the numbered ones, by name: "poly_g1_16", "poly_g1_256", "poly_g2_16", "poly_g2_256" (the Horner steps of nbls_g*_poly_eval, short and
-   full form), "dbladd_g1", "dbladd_g2" (the doubling-and-add steps that combine the bit-slices of nbls_g*_msm_batch / _rows); NULL for any other name */
+   full form), "dbladd_g1", "dbladd_g2" (the doubling-and-add steps that combine the bit-slices of nbls_g*_msm_batch / _rows), "lines_fe" (the line program of the pairings that end in a
+   final exponentiation; NBLS_LINES_FE=0 keeps "lines_pq" for them); NULL for any other name */
 const char* nbls_extra_program_kernel(nbls_ctx* ctx, const char* name);
+/* launches of such a program in this context so far, -1 for a name that is none (its launches are booked in the timing slot of the numbered program whose stage they serve) */
+long long nbls_extra_program_launches(nbls_ctx* ctx, const char* name);
+/* private (scratch) memory per lane of ahead-of-time kernel k = 0, 1, ... as loaded, -1 past the last one: 0 for every kernel of this build */
+int nbls_aot_kernel_private_bytes(int k);
 int nbls_timing_enable(nbls_ctx* ctx, int on);
 int nbls_timing_read(nbls_ctx* ctx, float* ms /*[NBLS_N_PROGRAMS+1]*/, uint32_t* counts /*[NBLS_N_PROGRAMS+1]*/);
 

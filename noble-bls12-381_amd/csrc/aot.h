@@ -76,12 +76,14 @@
   X(6, g2pt_ls2, P_H2C_C1_LS2, P_H2C_C2_LS2, P_G2_MUL_SAC_LS2, P_COUNT)
 
 // Kernels of the programs outside ProgId (programs.h ExtraProg): X(part, kernel name, two ExtraProgs it serves; XP_COUNT = none).  The Horner steps of nbls_g*_poly_eval, each
-// kernel serving the short and the full form of its group; the doubling-and-add steps of the batched MSM (pipelines_msm_batch.cpp), one kernel per group.
+// kernel serving the short and the full form of its group; the doubling-and-add steps of the batched MSM (pipelines_msm_batch.cpp), one kernel per group; the line program of
+// the pairings that end in a final exponentiation (pipelines_pairing.cpp pairing_core).
 #define NBLS_AOT_EXTRA_KERNELS(X)                \
   X(1, poly_g1, XP_POLY_G1_16, XP_POLY_G1_256)  \
   X(7, poly_g2, XP_POLY_G2_16, XP_POLY_G2_256)  \
   X(2, dbladd_g1, XP_DBLADD_G1, XP_COUNT)       \
-  X(3, dbladd_g2, XP_DBLADD_G2, XP_COUNT)
+  X(3, dbladd_g2, XP_DBLADD_G2, XP_COUNT)       \
+  X(5, lines_fe, XP_LINES_FE, XP_COUNT)
 
 namespace nbls {
 
@@ -136,6 +138,7 @@ std::string aot_translate_with(const Program& p, AotProgram& out, const AotLayou
 }  // namespace nbls
 
 // kernel side (aot_kernel.hip)
+extern "C" int nbls_aot_private_bytes(int k);   // private-segment bytes per lane of kernel k (hipFuncGetAttributes), -1 for a k that is none
 extern "C" const char* nbls_aot_name(int k);   // "nbls_aot_<name>" of kernel k
 extern "C" int nbls_aot_index(int prog_id);   // index of the ahead-of-time kernel that serves a ProgId, or -1
 extern "C" int nbls_aot_extra_index(int extra_prog);   // the same for an ExtraProg

@@ -17,6 +17,14 @@ struct DevDesc {
   __device__ __forceinline__ V4 quad(const u32 i) const { return i == 0 ? q0 : i == 1 ? q1 : i == 2 ? q2 : blk[64 * i]; }
 };
 
+// The lane of the wavefront (one wavefront per workgroup), read afresh wherever a segment starts: an opaque read is not kept in registers across the step loop, whose bodies
+// use the whole budget -- the lane, lane + 64 and its descriptor offset, held from the kernel's entry, were what the register allocator spilled to scratch memory (four
+// scratch instructions in every kernel that has an eight-round body; none now, and no private segment to set up for the launch)
+__device__ __forceinline__ u32 aot_lane() {
+  u32 l;
+  asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
+  return l;
+}
 template <class Dispatch>
 __device__ __forceinline__ void aot_body(const AotArgs& ka, Dispatch&& dispatch) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -40,12 +48,13 @@ __device__ __forceinline__ void aot_body(const AotArgs& ka, Dispatch&& dispatch)
     if (g) __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
     // constants: replicated at the start of every instance region, or one shared copy at the start of the LDS image
     const u32 per_inst = sg.nconst * NL, copies = sg.shared_consts ? 1u : ka.G;
-    for (u32 i = lane; i < copies * per_inst; i += 64) {
+    const u32 sl = aot_lane();
+    for (u32 i = sl; i < copies * per_inst; i += 64) {
       const u32 c0 = i / per_inst, r = i - c0 * per_inst, c = r / NL, l = r - c * NL;
       *(u32*)(lds + c0 * sg.inst_bytes + c * sg.slot_bytes + 4 * l) = sg.consts[c * RAW_WORDS + l];
     }
     __syncthreads();   // single wave: orders the constant fill before first use
-    const V4* descs4 = (const V4*)sg.descs + lane;
+    const V4* descs4 = (const V4*)sg.descs + sl;
     const uint2* as = (const uint2*)sg.steps;
     const u32 nsteps = sg.nsteps;
     uint2 h = as[0], nh = as[nsteps > 1 ? 1 : 0];
@@ -126,6 +135,12 @@ extern "C" int nbls_aot_extra_index(int extra_prog) {
   if (extra_prog < 0 || extra_prog >= (int)nbls::XP_COUNT) return -1;
   for (int k = 0; k < nbls::g_nkernels; k++) for (int j = 0; j < 4; j++) if (nbls::g_kernels[k].prog_id[j] == (int)nbls::P_COUNT + 1 + extra_prog) return k;
   return -1;
+}
+extern "C" int nbls_aot_private_bytes(int k) {
+  if (k < 0 || k >= nbls::g_nkernels) return -1;
+  hipFuncAttributes a;
+  if (hipFuncGetAttributes(&a, nbls::g_kernels[k].fn) != hipSuccess) { (void)hipGetLastError(); return -2; }
+  return (int)a.localSizeBytes;
 }
 extern "C" const char* nbls_aot_name(int k) { return k >= 0 && k < nbls::g_nkernels ? nbls::g_kernels[k].name : nullptr; }
 extern "C" int nbls_aot_bind(int k, nbls::AotProgram* ap) {

@@ -170,6 +170,7 @@ struct DevProgram {
   bool wide_ok = false;   // every step is one the one-limb-per-lane interpreter implements (wide_exec.h): launches of at most ctx->wide_max items run on nbls_vm_kernel_wide
   // ahead-of-time kernel of this program (aot.h) and the translated program, when every step's signature is in the kernel's table
   int aot = -1; AotStep* aot_steps = nullptr; u32* aot_descs = nullptr; u32 aot_lds = 0;
+  mutable unsigned long long launches = 0;   // launches of this program in this context (run_dev): nbls_extra_program_launches tells a test WHICH line program a call took
 };
 
 size_t ls_max();      // defaults of the lane-split thresholds (NBLS_LS_MAX / NBLS_LS2_MAX), tuning.cpp

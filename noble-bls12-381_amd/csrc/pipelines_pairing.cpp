@@ -129,10 +129,17 @@ int pairing_core(nbls_ctx* ctx, size_t n, const void* d_g1, const void* d_g2, in
   // calcPairingPrecomputes + millerLoop (math.ts:1331-1388) as two programs: line tables through HBM (LINE_BYTES per pair)
   if ((r = ensure_lines(ctx, n))) return r;
   if (with_final_exp && (r = ensure_scratch(ctx, n))) return r;
+  // A call that ends in the final exponentiation takes its lines from XP_LINES_FE (programs.h): the reference's lines times Fp2 factors, which the easy part removes, without the
+  // halvings and multipliers LINES_PQ pays for the reference's own representatives; same table layout, so ACC_FE reads either.  pairing(P, Q, false) keeps LINES_PQ: its bytes ARE
+  // the representatives.  NBLS_LINES_FE=0 forces LINES_PQ everywhere (A/B runs; programs.h lines_fe_enabled).  The launch is booked in LINES_PQ's timing slot: the same stage of the call.
+  const bool lines_fe = with_final_exp && lines_fe_enabled();
+  if (lines_fe && (r = upload_extra(ctx, XP_LINES_FE))) return r;
   for (size_t o = 0; o < n; o += LINES_CHUNK) {
     const size_t c = n - o < LINES_CHUNK ? n - o : LINES_CHUNK;
     const uint8_t *g1 = (const uint8_t*)d_g1 + o * 96, *g2 = (const uint8_t*)d_g2 + o * 192;
-    if ((r = run(ctx, P_LINES_PQ, c, {B(0, g1, 96), B(1, g2, 192), B(3, ctx->L, LINE_BYTES)}, s))) return r;
+    if (lines_fe) r = run_dev(ctx, ctx->extra[XP_LINES_FE], (int)P_LINES_PQ, c, {B(0, g1, 96), B(1, g2, 192), B(3, ctx->L, LINE_BYTES)}, s, nullptr, nullptr);
+    else r = run(ctx, P_LINES_PQ, c, {B(0, g1, 96), B(1, g2, 192), B(3, ctx->L, LINE_BYTES)}, s);
+    if (r) return r;
     if (!with_final_exp) r = run(ctx, P_ACC_BYTES, c, {B(3, ctx->L, LINE_BYTES), B(2, (uint8_t*)d_out + o * 576, 576)}, s);
     else r = run(ctx, P_ACC_FE, c, {B(3, ctx->L, LINE_BYTES), B(5, ctx->F + o * F12, F12), B(4, ctx->N + o * RAW, RAW)}, s);
     if (r) return r;

@@ -146,6 +146,50 @@ static void trace_lines(const SFp2& Qx, const SFp2& Qy, const LineSink& out) {
     }
   }
 }
+// LINES for the calls that end in the final exponentiation (programs.h XP_LINES_FE).  There a line may carry any non-zero Fp2 factor (the easy part sends it to ONE) and R may be
+// any representative of the reference's point, which removes what LINES_PQ pays to reproduce the reference's own: the halving of every doubling and the multiplier 3 on its first
+// product level (either one forces a second carry pass on every lane of its step, aot_exec.h aot_dot_finish).  State (T = 3 X, Y, E = 6 Z); per doubling
+//   level 1: t0 = Y^2, u = xi E^2 (= 9 b' Z^2 = 3 t2 of the reference), w2 = 2 Y E (= 6 t4), q = T^2 (= 9 X^2), ty2 = 2 T Y     -- factors 2 ride on doubled operands
+//   sums:    c0 = u - 3 t0, a3 = 3 (t0 - u), 3 t0, t0.c0 + t0.c1, 3 (t0.c0 - t0.c1)                                            -- the factor 3 lives here, as repeated terms
+//   level 2: T' = a3 ty2, Y' = 12 t0^2 - c0^2, E' = (2 * 3 t0)(2 w2), and the line 3 * (t2 - t0, 3 X^2 Px, -t4 Py) = (c0, q Px, -w2 * Py / 2)
+// which is the reference's doubling of (X : Y : Z) scaled by 12: 12 ((t0 + t3) / 2)^2 - 36 t2^2 = 3 (t0 + u)^2 - 4 u^2 = 12 t0^2 - (3 t0 - u)^2, again a difference of two Fp2
+// squares (two limb products per coefficient, as in LINES_PQ), and the subtracted square is the line coefficient the sums level forms anyway.  3 itself cannot be absorbed into
+// a coordinate's scale for good (it is a non-residue; EXPERIMENTS.md), but as repeated terms of a sum it costs nothing: the sums level has the step signature it had, without the
+// halving.  Py / 2 is formed once per item and takes Py's slot (an addition step reads Py as Py / 2 + Py / 2, a pre-addition): the program keeps LINES_PQ's LDS footprint and
+// with it the 80-byte slot stride.  The five addition steps run the reference's formulas on the representative (6 X, 6 Y, E) = (2 T, 6 Y, E).
+static void trace_lines_fe(const SFp& Px, const SFp& Py, const SFp2& Qx, const SFp2& Qy, int buf) {
+  Builder* B = Builder::cur();
+  const SFp Pyh = mat(mul(Py, SFp(B->frac_const(1, 2))));
+  int j = 0;
+  auto emit = [&](const SFp2& c0, const SFp2& e1, const SFp2& e2) {
+    const int off = 48 * 6 * j++;
+    outputw(c0.c0, buf, off); outputw(c0.c1, buf, off + 48);
+    outputw(e1.c0, buf, off + 96); outputw(e1.c1, buf, off + 144);
+    outputw(e2.c0, buf, off + 192); outputw(e2.c1, buf, off + 240);
+  };
+  SFp2 T = mat(scale(Qx, 3)), Y = Qy, E = {SFp(B->small_const(6)), SFp()};
+  for (int i = 62; i >= 0; i--) {
+    SFp2 t0 = mat(sqr(Y)), u = mat(mulnr(sqr(E))), w2 = mat(scale(mul(Y, E), 2)), q = mat(sqr(T)), ty2 = mat(scale(mul(T, Y), 2));
+    SFp2 c0 = mat(u - scale(t0, 3)), a3 = mat(scale(t0 - u, 3)), t03 = mat(scale(t0, 3));
+    SFp tp = mat(t0.c0 + t0.c1), tm3 = mat(scale(t0.c0 - t0.c1, 3));
+    emit(c0, mul_fp(q, Px), -mul_fp(w2, Pyh));
+    SFp2 nT = mat(mul(a3, ty2));
+    SFp2 nY = mat(SFp2{mul(scale(tp, 2), scale(tm3, 2)) - mul(c0.c0 + c0.c1, c0.c0 - c0.c1), mul(scale(t03.c0, 2), t03.c1 + t0.c1) - mul(scale(c0.c0, 2), c0.c1)});
+    SFp2 nE = mat(mul(scale(t03, 2), scale(w2, 2)));
+    T = nT; Y = nY; E = nE;
+    if ((NBLS_X >> i) & 1) {
+      // addition step, math.ts:1353-1367, on (Rx, Ry, Rz) = (2 T, 6 Y, E); the new state is (3 Rx', Ry', 6 Rz')
+      const SFp2 Rx = scale(T, 2);
+      SFp2 Ry = mat(scale(Y, 6));
+      SFp2 a0 = mat(scale(Y, 6) - mul(Qy, E)), a1 = mat(Rx - mul(Qx, E));
+      emit(mat(mul(a0, Qx) - mul(a1, Qy)), -mul_fp(a0, Px), mul_fp(a1, scale(Pyh, 2)));
+      SFp2 a2 = mat(sqr(a1)), a3 = mat(mul(a2, a1)), a4 = mat(mul(a2, Rx));
+      SFp2 a5 = mat(a3 - scale(a4, 2) + mul(sqr(a0), E));
+      nT = mat(scale(mul(a1, a5), 3)); nY = mat(mul(a4 - a5, a0) - mul(a3, Ry)); nE = mat(scale(mul(E, a3), 6));
+      T = nT; Y = nY; E = nE;
+    }
+  }
+}
 static SFp2 load_line_coef(int buf, int off) { return {inputw(buf, off), inputw(buf, off + 48)}; }
 // ACC: millerLoop (math.ts:1373-1388) over m line tables per item with ONE accumulator: f <- (f * prod_t line_t)^2 per bit.  m = 1 is the
 // reference's loop; for m > 1 the product of the m Miller values is the same field element ((prod a_t)^2 = prod a_t^2), so Miller products
@@ -211,6 +255,21 @@ static SFp12 trace_fe_final(const SFp12& t1, const SFp12& t2, const SFp12& t3, c
   SFp12 c = mat(frob(mul(t6, conj(t1)), 1));
   SFp12 d = mat(mul(mat(mul(t7, conj(t3))), t1));
   return mul(mat(mul(mat(mul(a, b)), c)), d);
+}
+// The same product as ONE chain of nine factors (round 3 measured it on the interpreter; here on the ahead-of-time kernel): the Frobenius map is a ring homomorphism, so
+//   (t2 t5)^(p^2) (t4 t1)^(p^3) (t6 conj(t1))^p D = ((((t4 t1)^p t2 t5)^p t6 conj(t1))^p D,   D = t7 conj(t3) t1
+// -- eight multiplications and three maps one after the other, every one an Fp12 operation of twelve lane-ops: at 12 lanes per item no lane idles and five items share a
+// wavefront, where the tree above runs its four independent products side by side on 32 lanes for two items.  The output is canonical wire bytes: the same bytes.
+// t(i) loads t_i where it is used (t1 three times): no factor waits in LDS for its turn.
+template <class Load>
+static SFp12 trace_fe_final_chain(Load t) {
+  SFp12 m = mat(frob(mat(mul(t(4), t(1))), 1));
+  m = mat(mul(m, t(2))); m = mat(mul(m, t(5)));
+  m = mat(frob(m, 1));
+  m = mat(mul(m, t(6))); m = mat(mul(m, conj(t(1))));
+  m = mat(frob(m, 1));
+  m = mat(mul(m, t(7))); m = mat(mul(m, conj(t(3))));
+  return mul(m, t(1));
 }
 
 static void load_points(SFp& Px, SFp& Py, SFp2& Qx, SFp2& Qy) {
@@ -393,6 +452,11 @@ static Program build(ProgId id) {
       return B.compile("fe_mid2", env_int("NBLS_FE_MID_W", 12));
     }
     case P_FE_FINAL: {
+      if (env_int("NBLS_FE_FINAL_CHAIN", 1)) {   // 0: the product tree on 32 lanes (until round 6)
+        B.sched_window = env_int("NBLS_FE_FINAL_WINDOW", 150);   // as EXPX: a factor is loaded about one multiplication ahead of its use
+        output_fp12(trace_fe_final_chain([&](int i) { return inputw_fp12(i - 1, 0); }), 7, 0);
+        return B.compile("fe_final", env_int("NBLS_FE_FINAL_W", 12));
+      }
       SFp12 t[7]; for (int i = 0; i < 7; i++) t[i] = inputw_fp12(i, 0);
       output_fp12(trace_fe_final(t[0], t[1], t[2], t[3], t[4], t[5], t[6]), 7, 0);
       return B.compile("fe_final", env_int("NBLS_FE_FINAL_W", 32));
@@ -894,6 +958,12 @@ const Program* get_tower_program(int field, int op, int param, int part) {
 static Program build_extra(ExtraProg id) {
   Builder B;
   if (env_int("NBLS_AOT_SHARED_CONSTS", 1)) B.shared_consts = 1;
+  if (id == XP_LINES_FE) {
+    SFp Px, Py; SFp2 Qx, Qy; load_points(Px, Py, Qx, Qy);
+    B.light_max = MAX_DOT_PRODUCTS; B.neg_cap = 7.0; B.store_batch = 6;   // as P_LINES_PQ: the ten lane-ops of a level in ONE step, 3 t0 and 3 u subtracted as they are
+    trace_lines_fe(Px, Py, Qx, Qy, 3);
+    return B.compile("lines_fe", LINES_W);
+  }
   if (id == XP_DBLADD_G1) {
     auto ld = [&](int buf) { return Pt<SFp>{inputw(buf, 0), inputw(buf, 48), inputw(buf, 96)}; };
     Pt<SFp> r = pt_add(pt_dbl(ld(3)), ld(4));
@@ -923,6 +993,7 @@ static Program build_extra(ExtraProg id) {
   B.sched_window = env_int("NBLS_MUL_WINDOW", 300);
   return B.compile(low16 ? "poly_g2_16" : "poly_g2_256", G2MUL_W);
 }
+bool lines_fe_enabled() { static const bool on = env_long("NBLS_LINES_FE", 1) != 0; return on; }
 const Program& get_extra_program(ExtraProg id) {
   static Program cache[XP_COUNT];
   static bool built[XP_COUNT];

@@ -110,10 +110,16 @@ const Program* get_tower_program(int field, int op, int param, int part);
 // identifier (16 doublings instead of 256); the accumulator lies in the order-r subgroup, so the _256 forms take any 256-bit value as P_G1_MUL does.
 // The doubling-and-add steps of the batched MSM's combination (pipelines_msm_batch.cpp): accumulator (buf 3: raw projective, in place), bit-slice sum T (buf 4: raw projective)
 // -> acc = 2 acc + T, complete formulas throughout (identity accumulators, identity slices, T = -2 acc and T = 2 acc are ordinary inputs).
-enum ExtraProg { XP_POLY_G1_16 = 0, XP_POLY_G1_256, XP_POLY_G2_16, XP_POLY_G2_256, XP_DBLADD_G1, XP_DBLADD_G2, XP_COUNT };
+// The line program of the calls that END IN THE FINAL EXPONENTIATION (pipelines_pairing.cpp pairing_core, two-program form): G1 (buf 0), G2 (buf 1) -> lines (buf 3) in the
+// layout of P_LINES_PQ, every line the reference's times a non-zero Fp2 factor and R any projective representative (programs.cpp trace_lines_fe).  A factor in a proper subfield
+// of Fp12 is sent to ONE by the easy part of the final exponentiation, so pairing(P, Q) is the reference's element; pairing(P, Q, false), prepared lines and the Miller products
+// keep P_LINES_PQ, whose bytes are pinned.
+enum ExtraProg { XP_POLY_G1_16 = 0, XP_POLY_G1_256, XP_POLY_G2_16, XP_POLY_G2_256, XP_DBLADD_G1, XP_DBLADD_G2, XP_LINES_FE, XP_COUNT };
 // The simulator's index-taking entry points (nbls_sim_extra_count / _name / _verify / _run) stop in front of this one: the suite pins their count at the four Horner steps.
 // Every later program is reached by name (nbls_sim_extra_verify_named / _run_named), as nbls_extra_program_kernel reaches it in the engine.
 static const int XP_NUMBERED = XP_DBLADD_G1;
 const Program& get_extra_program(ExtraProg id);
+// Does a call that ends in the final exponentiation take its lines from XP_LINES_FE?  NBLS_LINES_FE=0: never (LINES_PQ everywhere, for A/B runs); read once per process.
+bool lines_fe_enabled();
 void print_stats(const Program& p);
 }  // namespace nbls

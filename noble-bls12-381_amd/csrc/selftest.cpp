@@ -11,6 +11,8 @@
 #include "vm_exec.h"
 
 extern "C" int nbls_sim_run(int prog, unsigned n_items, uint8_t** ptrs, const uint64_t* strides);
+extern "C" int nbls_sim_extra_run_named(const char* name, int aot, unsigned n_items, uint8_t** ptrs, const uint64_t* strides);
+extern "C" void nbls_sim_set_aot(int on);
 using namespace nbls;
 
 static void be48(uint8_t* o, const u32* limbs) { u32 w[12]; limbs_to_words(w, limbs); for (int i = 0; i < 12; i++) { u32 v = w[11 - i]; o[4 * i] = v >> 24; o[4 * i + 1] = v >> 16; o[4 * i + 2] = v >> 8; o[4 * i + 3] = v; } }
@@ -22,7 +24,11 @@ int main() {
     const std::string e = verify_program(p);
     if (!e.empty()) { printf("VERIFY FAILED %s\n", e.c_str()); bad++; }
   }
-  printf("programs %d verified, failures %d\n", (int)P_COUNT, bad);
+  for (int i = 0; i < XP_COUNT; i++) {
+    const std::string e = verify_program(get_extra_program((ExtraProg)i));
+    if (!e.empty()) { printf("VERIFY FAILED %s\n", e.c_str()); bad++; }
+  }
+  printf("programs %d verified, failures %d\n", (int)P_COUNT + (int)XP_COUNT, bad);
   // pairing(G1, G2, false): generators in wire form
   uint8_t g1[96], g2[192], out1[576], out2[576];
   be48(g1, NBLS_G1X_RAW); be48(g1 + 48, NBLS_G1Y_RAW);
@@ -39,6 +45,19 @@ int main() {
     std::vector<uint8_t> lines((size_t)LINE_ELEMS * RAW_FP_BYTES);
     uint8_t* ptrs[8] = {g1, g2, out2, lines.data(), nullptr, nullptr, nullptr, nullptr}; uint64_t strides[8] = {96, 192, 576, lines.size(), 0, 0, 0, 0};
     if (nbls_sim_run(P_LINES_PQ, 1, ptrs, strides) || nbls_sim_run(P_ACC_BYTES, 1, ptrs, strides)) return 2;
+  }
+  {
+    // the line program of the calls that end in a final exponentiation, interpreted and translated, into a table of exactly LINE_ELEMS elements, then the accumulation and FE_FINAL
+    // in its translated form (the chain of nine factors) on that value seven times over: memory safety of the new programs' loads and stores; what they compute is the tests' matter
+    std::vector<uint8_t> lines((size_t)LINE_ELEMS * RAW_FP_BYTES), F(12 * RAW_FP_BYTES), N(RAW_FP_BYTES), W(576);
+    for (int aot = 0; aot < 2; aot++) {
+      uint8_t* ptrs[8] = {g1, g2, nullptr, lines.data(), N.data(), F.data(), nullptr, nullptr}; uint64_t strides[8] = {96, 192, 0, lines.size(), N.size(), F.size(), 0, 0};
+      nbls_sim_set_aot(aot);
+      if (nbls_sim_extra_run_named("lines_fe", aot, 1, ptrs, strides) || nbls_sim_run(P_ACC_FE, 1, ptrs, strides)) return 2;
+      uint8_t* tp[8] = {F.data(), F.data(), F.data(), F.data(), F.data(), F.data(), F.data(), W.data()}; uint64_t ts[8] = {F.size(), F.size(), F.size(), F.size(), F.size(), F.size(), F.size(), 576};
+      if (nbls_sim_run(P_FE_FINAL, 1, tp, ts)) return 2;
+    }
+    nbls_sim_set_aot(0);
   }
   if (memcmp(out1, out2, 576)) { printf("MISMATCH between the fused and the split Miller loop\n"); bad++; }
   printf("miller c0.c0.c0 ");

@@ -161,7 +161,7 @@ EXPORT const char* nbls_program_kernel(nbls_ctx* ctx, int prog) {
   return d.aot >= 0 ? nbls_aot_name(d.aot) : d.p->lsplit == 4 ? "nbls_vm_kernel_ls4" : d.p->lsplit == 1 ? "nbls_vm_kernel" : "none (two-lane programs have no interpreter form)";
 }
 // The same for a program outside the numbered registry, by its name ("poly_g1_16", "poly_g1_256", "poly_g2_16", "poly_g2_256": the Horner steps of nbls_g*_poly_eval;
-// "dbladd_g1", "dbladd_g2": the combination steps of nbls_g*_msm_batch / _rows); NULL for a name that is not one.  The query uploads the program.
+// "dbladd_g1", "dbladd_g2": the combination steps of nbls_g*_msm_batch / _rows; "lines_fe": the line program of the pairings that end in a final exponentiation); NULL for a name that is not one.  The query uploads the program.
 EXPORT const char* nbls_extra_program_kernel(nbls_ctx* ctx, const char* name) {
   if (!ctx || !name) return nullptr;
   std::lock_guard<std::recursive_mutex> g(ctx->mu);
@@ -173,6 +173,17 @@ EXPORT const char* nbls_extra_program_kernel(nbls_ctx* ctx, const char* name) {
   }
   return nullptr;
 }
+// launches of a program outside the numbered registry in this context so far (its launches are booked in the timing slot of the stage they serve, so the timing does not tell
+// them from the numbered program of that stage: "lines_fe" from "lines_pq"); -1 for a name that is none.  The query does not upload anything.
+EXPORT long long nbls_extra_program_launches(nbls_ctx* ctx, const char* name) {
+  if (!ctx || !name) return -1;
+  std::lock_guard<std::recursive_mutex> g(ctx->mu);
+  for (int i = 0; i < (int)XP_COUNT; i++) if (get_extra_program((ExtraProg)i).name == name) return (long long)ctx->extra[i].launches;
+  return -1;
+}
+// private (scratch) memory per lane of ahead-of-time kernel k as the loaded code object declares it, -1 past the last kernel: every kernel of aot_kernel.hip is built to need none
+// (a spill in a step body costs every step; tests/test_gpu_lines_fe.py asserts 0 on the device for every kernel)
+EXPORT int nbls_aot_kernel_private_bytes(int k) { return nbls_aot_private_bytes(k); }
 EXPORT int nbls_program_count(void) { return (int)P_COUNT; }
 EXPORT const char* nbls_program_name(int prog) { return prog >= 0 && prog < P_COUNT ? get_program((ProgId)prog).name.c_str() : nullptr; }
 

@@ -340,6 +340,22 @@ __attribute__((visibility("default"))) int nbls_sim_extra_run_named(const char* 
   const int xp = sim_extra_by_name(name);
   return xp < 0 ? -1 : sim_extra_run(xp, aot, n_items, ptrs, strides);
 }
+// the line nbls_sim_stats prints per numbered program, for one of these; -1 for a name that is none
+__attribute__((visibility("default"))) int nbls_sim_extra_stats_named(const char* name) { const int xp = sim_extra_by_name(name); if (xp < 0) return -1; print_stats(get_extra_program((ExtraProg)xp)); return 0; }
+// lanes per item of a numbered program as it compiled in this process (which form of a program an environment switch selected)
+__attribute__((visibility("default"))) int nbls_sim_program_lanes(int prog) { return prog < 0 || prog >= P_COUNT ? -1 : (int)get_program((ProgId)prog).W; }
+// what pairing_core (pipelines_pairing.cpp) asks before it picks the line program of a call with final exponentiation
+__attribute__((visibility("default"))) int nbls_sim_lines_fe_enabled(void) { return lines_fe_enabled() ? 1 : 0; }
+// nbls_sim_layout_info for one of these
+__attribute__((visibility("default"))) int nbls_sim_extra_layout_info_named(const char* name, unsigned long* out4) {
+  const int xp = sim_extra_by_name(name); if (xp < 0) return -1;
+  const Program& p = get_extra_program((ExtraProg)xp);
+  const AotLayout* l = aot_layout_for(p);
+  const AotLdsCost c0 = aot_layout_cost(p, AotLayout());
+  const AotLdsCost c1 = l ? aot_layout_cost(p, *l) : c0;
+  out4[0] = l ? 1 : 0; out4[1] = c0.cycles; out4[2] = c1.cycles; out4[3] = c0.floor;
+  return 0;
+}
 // out = in^-1 on raw elements (16 words each): the same fp_mont_inverse routine the inversion kernel runs per lane
 // the same inverse with one limb per lane (fp_inv_wide.h), one element after the other
 __attribute__((visibility("default"))) void nbls_sim_fp_inv_wide(unsigned n, const u32* in, u32* out) {

@@ -769,11 +769,17 @@ class Engine:
 
     def extra_program_kernel(self, name):
         """the same for a program outside PROGRAMS, by name: 'poly_g1_16', 'poly_g1_256', 'poly_g2_16', 'poly_g2_256' (the Horner steps of poly_eval), 'dbladd_g1', 'dbladd_g2'
-        (the combination steps of msm_batch / msm_rows)"""
+        (the combination steps of msm_batch / msm_rows), 'lines_fe' (the line program of the pairings that end in a final exponentiation)"""
         k = self.lib.nbls_extra_program_kernel(self.h, name.encode())
         if k is None:
             raise NblsError('nbls_extra_program_kernel(%s) failed' % name)
         return k.decode()
+
+    def extra_program_launches(self, name):
+        """launches of a program outside PROGRAMS in this context so far (they are booked in the timing slot of the stage they serve: 'lines_fe' in 'lines_pq')"""
+        self.lib.nbls_extra_program_launches.restype = C.c_longlong
+        self.lib.nbls_extra_program_launches.argtypes = [C.c_void_p, C.c_char_p]
+        return self.lib.nbls_extra_program_launches(self.h, name.encode())
 
     def kernel_bindings(self):
         """{program: kernel} over every step program"""
