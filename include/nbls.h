@@ -341,6 +341,43 @@ int nbls_g1_poly_eval(nbls_ctx* ctx, size_t n_groups, const uint32_t* coef_offse
 int nbls_g2_poly_eval(nbls_ctx* ctx, size_t n_groups, const uint32_t* coef_offsets /* n_groups + 1 */, const uint8_t* coefs96, const uint32_t* id_offsets /* n_groups + 1 */,
                       const uint8_t* ids32, uint8_t* out96 /* one per identifier */, int8_t* status /* one per identifier, may be NULL */);
 
+/* KZG on BLS12-381 (EIP-4844; no reference counterpart): the verifier's side of blob commitments.  The prover's side, blob_to_kzg_commitment, is nbls_g1_msm_rows over the
+ * Lagrange basis of the setup.  Field elements are 32 bytes big-endian and must be CANONICAL (bytes_to_bls_field: a value >= r is refused, status NBLS_ST_NON_CANONICAL) --
+ * unlike nbls_fr_op_batch, which reduces.  The formulas are EIP-4844's as the project's issue states them; the specification's own test vectors have not been run.
+ *
+ * nbls_fr_eval_roots: evaluate_polynomial_in_evaluation_form for n polynomials, each at its own point.  With N = 2^log2_n, polynomial i is given by its N values
+ * evals32[i N .. i N + N) on the roots of unity in bit-reversed order, w_j = omega^rev(j), omega = 7^((r - 1) / N), rev = the reversal of the log2_n bits of j:
+ *   out32[i] = p_i(z_i) = (z^N - 1) / N * sum_j f_j w_j / (z - w_j),   and f_j itself where z = w_j.
+ * status[i] (may be NULL): 0, or NBLS_ST_NON_CANONICAL when an element of the polynomial or z_i is >= r (out32[i] is then all-zero; the neighbours are not disturbed).
+ * One copy in, one kernel (a workgroup per polynomial, one field inversion per lane), one copy out; the table of roots is built on the device on the first use of a log2_n and
+ * kept with the context.  NBLS_EINVAL before any device work for log2_n outside 1 .. 12, a NULL context, missing buffers with n > 0, more than 2^24 elements in the call; n = 0 is
+ * NBLS_OK.  Not an interface for secrets (see nbls_fr_op_batch). */
+#define NBLS_ST_NON_CANONICAL 21   /* a 32-byte field element is >= r */
+int nbls_fr_eval_roots(nbls_ctx* ctx, unsigned log2_n /* 1 .. 12 */, size_t n, const uint8_t* evals32 /* n << log2_n elements */, const uint8_t* z32 /* n */,
+                       uint8_t* out32 /* n */, int8_t* status /* n, may be NULL */);
+/* verify_kzg_proof_batch: n tuples (commitment C_i, point z_i, value y_i, proof pi_i) against the setup's [tau]G2 (96 bytes compressed, PointG2.fromSignature's rules), checked
+ * together by a random linear combination with the weights r_i of nbls_verify_multiple (same seed rule: NULL = 32 bytes from getrandom(2) on every call):
+ *   e(-sum_i [r_i]pi_i, [tau]G2) * e(sum_i [r_i]C_i + sum_i [r_i z_i]pi_i - [sum_i r_i y_i]G1, G2) = 1
+ * -- MSMs of n points each, two Miller loops against prepared tables and ONE final exponentiation.  Commitments and proofs are 48 bytes compressed, decoded by PointG1.fromHex's rules, subgroup
+ * check included.  ZERO POINTS ARE VALID: 0xc0 00.. is the commitment of the zero polynomial and the proof of a constant one; a zero point takes part as the identity and status 1
+ * is never reported; either or both combined points may be the zero point (every polynomial of the call constant), which counts as a factor of one.
+ * status[i] (may be NULL), in this order: the commitment decoder's status if >= 2 (3 outside the subgroup, 4 no square root); else 10 + the proof decoder's status if >= 2; else
+ * NBLS_ST_NON_CANONICAL when z_i or y_i is >= r; else 0, or NBLS_ST_NOT_VERIFIED.  *all_ok = 1 exactly when every status is 0.  Items with one of the first three statuses take
+ * part in the combined sums with weight zero, and the combined check never accepts while there is one.  Where it does not accept, a per-item pass judges every tuple,
+ *   e(-pi_i, [tau]G2) * e(C_i + [z_i]pi_i - [y_i]G1, G2) = 1,
+ * with the two prepared tables shared by all items and one batched final exponentiation; with status == NULL the call stops after the combined check instead and answers
+ * *all_ok = 0 (fast reject).  Returns NBLS_OK whatever the tuples hold; NBLS_EDECODE when tau_g2_96 does not decode or is the zero point; NBLS_EINVAL for n = 0, n > 2^22 or a
+ * missing pointer.  *all_ok and status are NOT written when the call returns an error, NBLS_EDECODE included (the chain has then run on the undecoded [tau]G2 and is discarded). */
+int nbls_kzg_verify_proofs(nbls_ctx* ctx, size_t n, const uint8_t* commitments48, const uint8_t* z32, const uint8_t* y32, const uint8_t* proofs48, const uint8_t* tau_g2_96,
+                           const uint8_t* seed32 /* NULL: from the OS */, int* all_ok, int8_t* status /* n, may be NULL */);
+/* verify_blob_kzg_proof_batch: blob i = the 2^log2_n values of polynomial i (log2_n = 12: the mainnet blob of 131,072 bytes; smaller sizes exist for tests),
+ *   z_i = BE(SHA-256("FSBLOBVERIFY_V1_" || BE128(N) || blob_i || commitment_i)) mod r   (on host threads, behind the copy of the blobs: 2 N + 2 dependent SHA-256 blocks per blob are no work for a GPU lane),
+ *   y_i = p_i(z_i)   (on the device, as nbls_fr_eval_roots; the blobs cross the bus once),
+ * then the chain, statuses and return codes of nbls_kzg_verify_proofs; a blob with an element >= r gets NBLS_ST_NON_CANONICAL.  NBLS_EINVAL also for log2_n outside 1 .. 12 and
+ * more than 2^24 blob elements in the call. */
+int nbls_kzg_verify_blobs(nbls_ctx* ctx, unsigned log2_n, size_t n, const uint8_t* blobs /* n * (32 << log2_n) */, const uint8_t* commitments48, const uint8_t* proofs48,
+                          const uint8_t* tau_g2_96, const uint8_t* seed32, int* all_ok, int8_t* status);
+
 /* One rank's share of a verifyBatch spread over several GPUs (one process per GPU): the Miller product of this rank's n
  * (key, message) pairs, times millerLoop(-G, S) on the ONE rank that passes the signature (d_sig96 = NULL elsewhere), WITHOUT the
  * final exponentiation, as 576 wire bytes in device memory.  Ranks all-gather their partials and finish with
@@ -370,7 +407,7 @@ const char* nbls_config_describe(void);   /* "NBLS_X=value(env|default) ...": ev
    nbls_verify_aggregates_indexed_shared, scratch slots 48 .. 50 (additions only, same version); then nbls_fr_op_batch, nbls_lagrange_at_zero, nbls_g2_combine_shares,
    nbls_g1_combine_shares, NBLS_FROP_*, NBLS_ST_BAD_IDS, scratch slots 51 .. 56 (additions only, same version); then nbls_field_kernel_raw (addition only, same version); then nbls_g1_poly_eval,
    nbls_g2_poly_eval, nbls_extra_program_kernel, NBLS_TUNE_POLY_SLAB, scratch slots 57 .. 61 (additions only, same version); then nbls_g1_msm_batch, nbls_g2_msm_batch,
-   nbls_g1_msm_rows, nbls_g2_msm_rows, NBLS_TUNE_MSMB_WINDOW / _BIG / _SLAB, the names "dbladd_g1" / "dbladd_g2" of nbls_extra_program_kernel, scratch slots 62 .. 63 (additions only, same version); then nbls_map_uniform_batch (addition only, same version); with the MSM calls ONE CHANGE TO EXISTING CALLS, same version: nbls_g1_msm / nbls_g2_msm write all-zero output bytes when the status is 1 (the sum is the
+   nbls_g1_msm_rows, nbls_g2_msm_rows, NBLS_TUNE_MSMB_WINDOW / _BIG / _SLAB, the names "dbladd_g1" / "dbladd_g2" of nbls_extra_program_kernel, scratch slots 62 .. 63 (additions only, same version); then nbls_map_uniform_batch (addition only, same version); then nbls_fr_eval_roots, nbls_kzg_verify_proofs, nbls_kzg_verify_blobs, NBLS_ST_NON_CANONICAL, scratch slots 64 .. 68 (additions only, same version); with the MSM calls ONE CHANGE TO EXISTING CALLS, same version: nbls_g1_msm / nbls_g2_msm write all-zero output bytes when the status is 1 (the sum is the
    zero point).  The bytes were unspecified there before (what the affine conversion made of a Z that is 0 mod p: in G1 a zero x and an arbitrary y); the status, and every output with status 0, are unchanged.
    nbls_msm_dev, which leaves its result on the device, is not changed.
    4 (round 6): nbls_hw_queues, NBLS_TUNE_WIDE_MAX, NBLS_TUNE_H2C_NORM_MIN, NBLS_TUNE_INV_WIDE_MAX, NBLS_TUNE_LS_MAX / _LS2_MAX (additions only); the library sets GPU_MAX_HW_QUEUES = 22 at load when the variable is unset (see nbls_pool_init below).

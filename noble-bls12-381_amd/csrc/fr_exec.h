@@ -198,4 +198,90 @@ NBLS_FR_HD Fr fr_lagrange_finish(const FrLagrange& s, uint32_t* bad) {
   return fr_mul(s.num, fr_inv(s.den));
 }
 
+// ---- Polynomials in evaluation form over the N = 2^k roots of unity, k = 1 .. 12 (evaluate_polynomial_in_evaluation_form of EIP-4844; kzg_kernels.hip and nbls_sim_fr_eval_roots):
+//   p(z) = (z^N - 1) / N * sum_j f_j w_j / (z - w_j),   w_j = omega^rev(j),  omega = 7^((r - 1) / N),  rev = the k-bit reversal;   p(w_j) = f_j.
+// A workgroup of `lanes` lanes owns one polynomial; lane t owns the terms j = t, t + lanes, .. (ceil(N / lanes) of them).  fr_eval_lane inverts the lane's denominators
+// with ONE fr_inv (Montgomery's trick: the running products wait in the workgroup's shared memory); a vanishing
+// denominator is replaced by one under a mask and its index remembered; terms past N (N < lanes) are masked the same way.  The lane sums meet in a tree of fr_add -- exact, so
+// the order of the additions cannot change a bit -- and fr_eval_finish closes: the factor (z^N - 1) / N, the element f_j itself where z = w_j, zero where an input was >= r.
+// Values: the table and z are in Montgomery form; the elements f_j stay plain (a product plain x Montgomery is plain), so sums and results need no conversion.
+NBLS_FR_HD uint32_t fr_ge_r_mask(const Fr& a) {   // all ones when the plain 256-bit value a is >= r: bytes_to_bls_field refuses it
+  uint64_t bw = 0;
+#pragma unroll
+  for (int i = 0; i < FR_NL; i++) bw = (((uint64_t)a.l[i] - fr_mod(i) - bw) >> 32) & 1;
+  return (uint32_t)bw - 1;
+}
+NBLS_FR_HD Fr fr_rm1_shr(unsigned k) {   // (r - 1) >> k as plain limbs, 0 <= k < 32 (2^32 divides r - 1)
+  Fr e;
+#pragma unroll
+  for (int i = 0; i < FR_NL; i++) {
+    const uint32_t lo = i == 0 ? 0u : fr_mod(i), hi = i + 1 < FR_NL ? fr_mod(i + 1) : 0u;
+    e.l[i] = k ? (lo >> k) | (hi << (32 - k)) : lo;
+  }
+  return e;
+}
+NBLS_FR_HD uint32_t fr_bitrev(uint32_t j, unsigned bits) {
+  uint32_t o = 0;
+  for (unsigned b = 0; b < bits; b++) o |= ((j >> b) & 1) << (bits - 1 - b);
+  return o;
+}
+NBLS_FR_HD Fr fr_omega(unsigned log2_n) { Fr seven = fr_zero(); seven.l[0] = 7; return fr_pow(fr_mul(seven, fr_r2()), fr_rm1_shr(log2_n)); }
+// entry j of the table of 2^log2_n roots in bit-reversed order, Montgomery form (the exponent has at most 12 bits; all of them are walked)
+NBLS_FR_HD Fr fr_root_entry(const Fr& omega, unsigned log2_n, uint32_t j) {
+  const uint32_t e = fr_bitrev(j, log2_n);
+  Fr acc = fr_one();
+  for (int b = 11; b >= 0; b--) {
+    acc = fr_sqr(acc);
+    acc = fr_select((uint32_t)0 - ((e >> b) & 1), fr_mul(acc, omega), acc);
+  }
+  return acc;
+}
+NBLS_FR_HD Fr fr_inv_pow2(unsigned log2_n) {   // 1 / 2^log2_n = r - (r - 1) / 2^log2_n, Montgomery form
+  return fr_mul(fr_sub(fr_zero(), fr_rm1_shr(log2_n)), fr_r2());
+}
+struct FrEvalPart { Fr sum; uint32_t hit, bad; };   // the lane's plain partial sum | the index j with z = w_j, else 0xffffffff | all ones when an element the lane read is >= r
+// pre: the products in front of each of the lane's denominators, terms x 8 x lanes words laid out [term][limb][lane] (LDS on the device: consecutive lanes on consecutive banks);
+// held in registers, sixteen terms of unrolled code let the compiler hoist every load of the walk and spill (measured on gfx950: 256 VGPRs and 1252 bytes of private memory)
+NBLS_FR_HD FrEvalPart fr_eval_lane(const uint8_t* f32, const Fr* roots, const Fr& z, uint32_t N, uint32_t lane, uint32_t lanes, uint32_t* pre) {
+  const uint32_t terms = (N + lanes - 1) / lanes;   // the workgroup's bound, the same for every lane
+  const Fr one = fr_one();
+  Fr acc = one;
+  FrEvalPart o{fr_zero(), 0xffffffffu, 0};
+  for (uint32_t k = 0; k < terms; k++) {
+    const uint32_t j = lane + k * lanes, live = (uint32_t)0 - (uint32_t)(j < N), jj = j < N ? j : N - 1;
+    const Fr d = fr_sub(z, roots[jj]);
+    const uint32_t zm = fr_is_zero_mask(d) & live;
+    o.hit = (o.hit & ~zm) | (j & zm);
+#pragma unroll
+    for (int i = 0; i < FR_NL; i++) pre[(k * FR_NL + i) * lanes + lane] = acc.l[i];
+    acc = fr_mul(acc, fr_select(zm | ~live, one, d));
+  }
+  Fr inv = fr_inv(acc);
+  for (uint32_t k = terms; k-- > 0;) {
+    const uint32_t j = lane + k * lanes, live = (uint32_t)0 - (uint32_t)(j < N), jj = j < N ? j : N - 1;
+    const Fr w = roots[jj], d0 = fr_sub(z, w);
+    const Fr d = fr_select((fr_is_zero_mask(d0) & live) | ~live, one, d0);
+    const Fr f = fr_load_be(f32 + 32ull * jj);
+    o.bad |= fr_ge_r_mask(f) & live;
+    Fr p;
+#pragma unroll
+    for (int i = 0; i < FR_NL; i++) p.l[i] = pre[(k * FR_NL + i) * lanes + lane];
+    const Fr t = fr_mul(fr_mul(f, w), fr_mul(inv, p));   // f_j w_j / (z - w_j), plain
+    inv = fr_mul(inv, d);
+    o.sum = fr_add(o.sum, fr_select(live, t, fr_zero()));
+  }
+  return o;
+}
+// sum: the workgroup's plain sum; hit / bad: the lanes' combined (bad also where z itself was >= r) -> 32 bytes big-endian; returns the status (21 = NBLS_ST_NON_CANONICAL, else 0)
+NBLS_FR_HD int fr_eval_finish(const Fr& sum, uint32_t hit, uint32_t bad, const Fr& z, unsigned log2_n, const uint8_t* f32, uint8_t* out32) {
+  Fr zn = z;
+  for (unsigned i = 0; i < log2_n; i++) zn = fr_sqr(zn);
+  const Fr fac = fr_mul(fr_sub(zn, fr_one()), fr_inv_pow2(log2_n));
+  const uint32_t hm = (uint32_t)0 - (uint32_t)(hit != 0xffffffffu);
+  Fr v = fr_select(hm, fr_load_be(f32 + 32ull * (hit & hm)), fr_mul(sum, fac));
+  fr_store_be(fr_select(bad, fr_zero(), v), out32);
+  return (int)(bad & 21);
+}
+enum { FR_EVAL_LANES = 256 };   // lanes per polynomial: 16 terms each at N = 4096
+
 }  // namespace nbls

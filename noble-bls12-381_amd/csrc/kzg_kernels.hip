@@ -1,0 +1,177 @@
+// kzg_kernels.hip -- the scalar-field side of KZG verification (pipelines_kzg.cpp): polynomials in evaluation form evaluated at a point (nbls_fr_eval_roots, and y_i = p_i(z_i) of
+// nbls_kzg_verify_blobs), the table of roots of unity, and the small Fr kernels around the two MSMs of the combined check and the ladders of the per-item pass.  The arithmetic is
+// fr_exec.h's, written once and shared with the simulator (nbls_sim_fr_eval_roots); the curve arithmetic runs as step programs (decoder, MSM, ladders, Miller loops).
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <atomic>
+#include <mutex>
+#include "fr_exec.h"
+#include "nbls.h"   // NBLS_ST_NON_CANONICAL, NBLS_ST_NOT_VERIFIED
+
+namespace {
+typedef uint32_t u32;
+typedef uint64_t u64;
+using namespace nbls;
+
+constexpr int EV = FR_EVAL_LANES;   // 256 lanes = four wavefronts per polynomial
+
+// table[j] = omega^rev(j) in Montgomery form, one entry per lane: built once per context and log2_n (two short exponentiations per entry; 4096 entries at most)
+__global__ void kzg_roots_kernel(u32 log2_n, Fr* __restrict__ table) {
+  const u32 j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j < (1u << log2_n)) table[j] = fr_root_entry(fr_omega(log2_n), log2_n, j);
+}
+
+// One workgroup per polynomial, lane t on the terms t, t + 256, .. (ceil(N / 256) of them: the loop bounds are the workgroup's), ONE fixed-chain inversion per lane.  N < 256
+// leaves lanes idle under fr_eval_lane's mask.  Dynamic LDS: the running products of the batch inversion, 8 KB per term of a lane (128 KB at N = 4096), [term][limb][lane] so that
+// a wavefront's 64 words fall on 64 banks.  The 256 partial sums meet in an LDS tree (8 KB) of modular additions; at most one lane of the workgroup meets a vanishing denominator
+// (the roots are distinct) and leaves its index in LDS.
+__global__ void __launch_bounds__(EV) kzg_eval_kernel(u32 log2_n, const uint8_t* __restrict__ evals, const uint8_t* __restrict__ z32, const Fr* __restrict__ roots,
+                                                      uint8_t* __restrict__ out32, int8_t* __restrict__ status) {
+  extern __shared__ u32 pre[];
+  __shared__ Fr part[EV];
+  __shared__ u32 sh_hit, sh_bad;
+  const u32 N = 1u << log2_n, t = threadIdx.x;
+  const u64 p = blockIdx.x;
+  const uint8_t* f32 = evals + ((p * 32) << log2_n);
+  const Fr zraw = fr_load_be(z32 + 32 * p), z = fr_mul(zraw, fr_r2());
+  if (t == 0) { sh_hit = 0xffffffffu; sh_bad = fr_ge_r_mask(zraw); }
+  __syncthreads();
+  const FrEvalPart me = fr_eval_lane(f32, roots, z, N, t, EV, pre);
+  part[t] = me.sum;
+  if (me.hit != 0xffffffffu) sh_hit = me.hit;
+  if (me.bad) atomicOr(&sh_bad, 0xffffffffu);
+  __syncthreads();
+  for (u32 s = EV / 2; s > 0; s >>= 1) {
+    if (t < s) part[t] = fr_add(part[t], part[t + s]);
+    __syncthreads();
+  }
+  if (t == 0) status[p] = (int8_t)fr_eval_finish(part[0], sh_hit, sh_bad, z, log2_n, f32, out32 + 32 * p);
+}
+
+__device__ inline void copy96(uint8_t* dst, const uint8_t* src) {
+  const uint4* s = (const uint4*)src; uint4* d = (uint4*)dst;
+#pragma unroll
+  for (int q = 0; q < 6; q++) d[q] = s[q];
+}
+
+// The scalars of the combined check, one item per lane.  dst: the decoder statuses of the n commitments, then of the n proofs; w32: the weights r_i; z32 / y32: 32 bytes
+// big-endian; yst (may be NULL): the status of the device evaluation that produced y_i.  pre[i] = the item's status before any pairing (commitment, proof, canonical scalars: in
+// that order).  An item with pre != 0 gets zero scalars everywhere; a zero point (decoder status 1) takes part as the identity: zero scalars for that point alone.  Every point that
+// a zero scalar stands for is replaced by the generator, so that the MSM reads points of the curve only; aff[2 n] = the generator, the point of sum_i r_i y_i.
+//   s1[i] = r_i (the 64-bit MSM over the proofs);  s2[i] = r_i, s2[n + i] = r_i z_i mod r (the 256-bit MSM);  t[i] = r_i y_i mod r, plain limbs, summed by kzg_sum_kernel
+__global__ void kzg_items_kernel(u32 n, const int8_t* __restrict__ dst, const uint8_t* __restrict__ w32, const uint8_t* __restrict__ z32, const uint8_t* __restrict__ y32,
+                                 const int8_t* __restrict__ yst, const uint8_t* __restrict__ gen96, uint8_t* __restrict__ aff, uint8_t* __restrict__ s1, uint8_t* __restrict__ s2,
+                                 Fr* __restrict__ t, int8_t* __restrict__ pre) {
+  const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  if (i == 0) copy96(aff + 192ull * n, gen96);
+  const int sc = dst[i], sp = dst[n + i];
+  const Fr zr = fr_load_be(z32 + 32ull * i), yr = fr_load_be(y32 + 32ull * i);
+  const bool nc = (fr_ge_r_mask(zr) | fr_ge_r_mask(yr)) != 0 || (yst && yst[i] != 0);
+  const int st = sc >= 2 ? sc : sp >= 2 ? 10 + sp : nc ? NBLS_ST_NON_CANONICAL : 0;
+  pre[i] = (int8_t)st;
+  const u32 live = (u32)0 - (u32)(st == 0), use_c = live & ((u32)0 - (u32)(sc == 0)), use_p = live & ((u32)0 - (u32)(sp == 0));
+  const Fr zero = fr_zero(), r = fr_load_be(w32 + 32ull * i), rm = fr_mul(r, fr_r2());
+  fr_store_be(fr_select(use_p, r, zero), s1 + 32ull * i);
+  fr_store_be(fr_select(use_c, r, zero), s2 + 32ull * i);
+  fr_store_be(fr_select(use_p, fr_mul(rm, fr_select(live, zr, zero)), zero), s2 + 32ull * (n + i));
+  t[i] = fr_select(live, fr_mul(rm, fr_select(live, yr, zero)), zero);
+  if (!use_c) copy96(aff + 96ull * i, gen96);
+  if (!use_p) copy96(aff + 96ull * (n + i), gen96);
+}
+// out32 = -(sum_i t[i]) mod r as 32 bytes big-endian: one workgroup, the lanes striding over the items, an LDS tree of modular additions
+__global__ void __launch_bounds__(256) kzg_sum_kernel(u32 n, const Fr* __restrict__ t, uint8_t* __restrict__ out32) {
+  __shared__ Fr part[256];
+  Fr acc = fr_zero();
+  for (u32 i = threadIdx.x; i < n; i += 256) acc = fr_add(acc, t[i]);
+  part[threadIdx.x] = acc;
+  __syncthreads();
+  for (u32 s = 128; s > 0; s >>= 1) {
+    if (threadIdx.x < s) part[threadIdx.x] = fr_add(part[threadIdx.x], part[threadIdx.x + s]);
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) fr_store_be(fr_neg(part[0]), out32);
+}
+// pts[i] = the generator where zero[i] == 1: a zero point cannot go into a Miller loop; the verdict is taken from the flag, not from that factor
+__global__ void kzg_fix_zero_kernel(u32 n, const int8_t* __restrict__ zero, const uint8_t* __restrict__ gen96, uint8_t* __restrict__ pts) {
+  const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n && zero[i] == 1) copy96(pts + 96ull * i, gen96);
+}
+// the per-item pass: zs[i] = z_i (zero where the item is out or its proof is the zero point), ny[i] = -y_i mod r (zero where the item is out)
+__global__ void kzg_item_scalars_kernel(u32 n, const int8_t* __restrict__ pre, const int8_t* __restrict__ dst, const uint8_t* __restrict__ z32, const uint8_t* __restrict__ y32,
+                                        uint8_t* __restrict__ zs, uint8_t* __restrict__ ny) {
+  const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const u32 live = (u32)0 - (u32)(pre[i] == 0), use_p = live & ((u32)0 - (u32)(dst[n + i] == 0));
+  const Fr zero = fr_zero();
+  fr_store_be(fr_select(use_p, fr_load_be(z32 + 32ull * i), zero), zs + 32ull * i);
+  fr_store_be(fr_neg(fr_select(live, fr_load_be(y32 + 32ull * i), zero)), ny + 32ull * i);
+}
+// status[i] of the per-item pass.  x = C_i + [z_i]pi_i - [y_i]G1: with a zero proof the tuple holds exactly when x is the zero point; with a non-zero proof a zero x fails
+// (e(pi, [tau]G2) is not one) and otherwise the pairing product decides (one[i]: the final exponentiation is Fp12.ONE)
+__global__ void kzg_item_status_kernel(u32 n, const int8_t* __restrict__ pre, const int8_t* __restrict__ dst, const int8_t* __restrict__ xzero, const uint8_t* __restrict__ one,
+                                       int8_t* __restrict__ status) {
+  const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const bool pz = dst[n + i] == 1, xz = xzero[i] == 1;
+  const bool ok = pz ? xz : (!xz && one[i] != 0);
+  status[i] = pre[i] ? pre[i] : ok ? 0 : NBLS_ST_NOT_VERIFIED;
+}
+
+inline unsigned blocks_for(u64 threads, unsigned per = 256) { return (unsigned)((threads + per - 1) / per); }
+}  // namespace
+
+extern "C" {
+int nbls_kzg_roots_launch(unsigned log2_n, void* table, void* stream) {
+  hipLaunchKernelGGL(kzg_roots_kernel, dim3(blocks_for((u64)1 << log2_n, 64)), dim3(64), 0, (hipStream_t)stream, log2_n, (Fr*)table);
+  return (int)hipGetLastError();
+}
+// n polynomials of 2^log2_n elements each (1 <= log2_n <= 12) at their points z -> out32 (n x 32 bytes) and status (n bytes, not NULL)
+int nbls_kzg_eval_launch(unsigned log2_n, unsigned n, const void* evals32, const void* z32, const void* roots, void* out32, void* status, void* stream) {
+  if (!n) return 0;
+  if (log2_n < 1 || log2_n > 12) return (int)hipErrorInvalidValue;
+  const unsigned terms = ((1u << log2_n) + EV - 1) / EV, lds = terms * FR_NL * EV * 4;
+  // more than the 64 KB a launch may ask for by default.  The limit is a per-device function attribute: set once on every device a launch is made on (as nbls_vm_launch does);
+  // the common case, already set, takes no lock
+  static std::atomic<bool> attr_set[64];
+  static std::mutex attr_mu;
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
+  if (!attr_set[dev].load(std::memory_order_acquire)) {
+    std::lock_guard<std::mutex> g(attr_mu);
+    if (!attr_set[dev].load(std::memory_order_relaxed)) {
+      const hipError_t e = hipFuncSetAttribute((const void*)kzg_eval_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 16 * FR_NL * EV * 4);
+      if (e != hipSuccess) return (int)e;
+      attr_set[dev].store(true, std::memory_order_release);
+    }
+  }
+  hipLaunchKernelGGL(kzg_eval_kernel, dim3(n), dim3(EV), lds, (hipStream_t)stream, log2_n, (const uint8_t*)evals32, (const uint8_t*)z32, (const Fr*)roots, (uint8_t*)out32, (int8_t*)status);
+  return (int)hipGetLastError();
+}
+int nbls_kzg_items_launch(unsigned n, const void* dst, const void* w32, const void* z32, const void* y32, const void* yst, const void* gen96, void* aff, void* s1, void* s2, void* t,
+                          void* pre, void* stream) {
+  if (!n) return 0;
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(kzg_items_kernel, dim3(blocks_for(n, 64)), dim3(64), 0, s, n, (const int8_t*)dst, (const uint8_t*)w32, (const uint8_t*)z32, (const uint8_t*)y32, (const int8_t*)yst,
+                     (const uint8_t*)gen96, (uint8_t*)aff, (uint8_t*)s1, (uint8_t*)s2, (Fr*)t, (int8_t*)pre);
+  hipLaunchKernelGGL(kzg_sum_kernel, dim3(1), dim3(256), 0, s, n, (const Fr*)t, (uint8_t*)s2 + 64ull * n);
+  return (int)hipGetLastError();
+}
+int nbls_kzg_fix_zero_launch(unsigned n, const void* zero, const void* gen96, void* pts, void* stream) {
+  if (!n) return 0;
+  hipLaunchKernelGGL(kzg_fix_zero_kernel, dim3(blocks_for(n)), dim3(256), 0, (hipStream_t)stream, n, (const int8_t*)zero, (const uint8_t*)gen96, (uint8_t*)pts);
+  return (int)hipGetLastError();
+}
+int nbls_kzg_item_scalars_launch(unsigned n, const void* pre, const void* dst, const void* z32, const void* y32, void* zs, void* ny, void* stream) {
+  if (!n) return 0;
+  hipLaunchKernelGGL(kzg_item_scalars_kernel, dim3(blocks_for(n, 64)), dim3(64), 0, (hipStream_t)stream, n, (const int8_t*)pre, (const int8_t*)dst, (const uint8_t*)z32,
+                     (const uint8_t*)y32, (uint8_t*)zs, (uint8_t*)ny);
+  return (int)hipGetLastError();
+}
+int nbls_kzg_item_status_launch(unsigned n, const void* pre, const void* dst, const void* xzero, const void* one, void* status, void* stream) {
+  if (!n) return 0;
+  hipLaunchKernelGGL(kzg_item_status_kernel, dim3(blocks_for(n)), dim3(256), 0, (hipStream_t)stream, n, (const int8_t*)pre, (const int8_t*)dst, (const int8_t*)xzero, (const uint8_t*)one,
+                     (int8_t*)status);
+  return (int)hipGetLastError();
+}
+}

@@ -1,5 +1,5 @@
 // nbls_internal.h -- what the translation units of the runtime share (runtime.cpp / tuning.cpp / pipelines_pairing.cpp / pipelines_codec.cpp / pipelines_verify.cpp /
-// pipelines_multi_verify.cpp / pipelines_threshold.cpp / pipelines_poly.cpp / pipelines_msm_batch.cpp; pool and multi-device handles: nbls_multi.cpp): the context, the map of its scratch slots (enum Slot: the one place that says which chain owns
+// pipelines_multi_verify.cpp / pipelines_threshold.cpp / pipelines_poly.cpp / pipelines_msm_batch.cpp / pipelines_kzg.cpp; pool and multi-device handles: nbls_multi.cpp): the context, the map of its scratch slots (enum Slot: the one place that says which chain owns
 // which slot, checked at compile time), the launch helpers, the staged block of the host-buffer pipelines (staging.h, included at the end) and the device-side pipelines the
 // exported entry points are built from.  Internal functions have hidden visibility (csrc/Makefile: -fvisibility=hidden).
 #pragma once
@@ -60,6 +60,14 @@ extern "C" int nbls_msm_pairs_launch(size_t m, unsigned d, const void* keys, con
 extern "C" int nbls_msm_fill_launch(size_t count, unsigned elem_bytes, const void* ident, void* dst, void* stream);
 extern "C" int nbls_msm_heads_launch(size_t m, unsigned elem_bytes, const void* keys, const void* P, void* buckets, void* stream);
 extern "C" int nbls_msm_bitsel_launch(unsigned nwin, unsigned elem_bytes, const void* buckets, void* G, void* stream);
+// kzg_kernels.hip
+extern "C" int nbls_kzg_roots_launch(unsigned log2_n, void* table, void* stream);
+extern "C" int nbls_kzg_eval_launch(unsigned log2_n, unsigned n, const void* evals32, const void* z32, const void* roots, void* out32, void* status, void* stream);
+extern "C" int nbls_kzg_items_launch(unsigned n, const void* dst, const void* w32, const void* z32, const void* y32, const void* yst, const void* gen96, void* aff, void* s1, void* s2,
+                                     void* t, void* pre, void* stream);
+extern "C" int nbls_kzg_fix_zero_launch(unsigned n, const void* zero, const void* gen96, void* pts, void* stream);
+extern "C" int nbls_kzg_item_scalars_launch(unsigned n, const void* pre, const void* dst, const void* z32, const void* y32, void* zs, void* ny, void* stream);
+extern "C" int nbls_kzg_item_status_launch(unsigned n, const void* pre, const void* dst, const void* xzero, const void* one, void* status, void* stream);
 // msmb_kernels.hip
 extern "C" int nbls_msmb_keys_launch(unsigned m, unsigned dims, unsigned nwin, unsigned c, unsigned i0, unsigned g0, unsigned ngroups, unsigned n_pts, const void* off,
                                      const void* scalars, void* keys, void* vals, void* stream);
@@ -83,6 +91,7 @@ static const size_t LINES_CHUNK = 131072;   // pairs whose line tables are in HB
 // by side on different streams of one call must never share a slot, and no slot may be regrown under a kernel in flight.  This block is the whole map: who owns which slot, the
 // slots every chain touches (the masks) and the chains that run concurrently (the static_asserts).  A new chain takes new enumerators in front of NSB, gets a mask, and is
 // asserted against everything it runs beside.  The numbers are the indices into sb[]: they fix the order of allocation and are never reused for something else.
+typedef unsigned __int128 SlotMask;   // one bit per slot
 enum Slot {
   // the call's own stream, one pipeline at a time: hash-to-curve (field elements, exponentiation inputs, powers, points), the point sum's two halves, the ladder's points (its
   // digits in SB_WORK_C / SB_WORK_B when the caller brings none), the decoders and the MSM when they run alone (DEC_MAIN, MSM_MAIN)
@@ -114,39 +123,42 @@ enum Slot {
   // one slab: accumulators, norms, inverses, affine points, zero flags | one slab: the step's coefficient of every item | the compressed results and statuses (what is read back)
   SB_POLY_COEFS = 57, SB_POLY_LABELS = 58, SB_POLY_ACC = 59, SB_POLY_STEP = 60, SB_POLY_OUT = 61,
   // msm_batch_pipeline (pipelines_msm_batch.cpp), both sized once per call before its first launch: the staged input, the converted points, the split scalars and what is read
-  // back | one slab: keys, sorted points, buckets, bit-slices, accumulators.  (Two slots, carved by the pipeline: the masks below are 64 bits wide.)
+  // back | one slab: keys, sorted points, buckets, bit-slices, accumulators.  (Two slots, carved by the pipeline.)
   SB_MSMB_CALL = 62, SB_MSMB_SLAB = 63,
+  // kzg_pipeline (pipelines_kzg.cpp): the decoded commitments and proofs (+ the generator), their statuses | weights, the scalars of the MSMs, the products r_i y_i, the
+  // values y_i and statuses of the blob evaluation, the challenges | [tau]G2 and -G2, their two line tables, the two combined points, the three parts of B | what is read back | everything of the per-item pass
+  SB_KZG_POINTS = 64, SB_KZG_SCALARS = 65, SB_KZG_PAIRS = 66, SB_KZG_OUT = 67, SB_KZG_ITEMS = 68,
   NSB
 };
-// all 64 bits of the slot masks are taken: the next chain that needs a slot of its own widens slot_bit / slots / the masks beyond uint64_t first
-static_assert(NSB == 64, "sb[] indices do not shift");
-constexpr uint64_t slot_bit(int i) { return (uint64_t)1 << i; }
-template <typename... S> constexpr uint64_t slots(S... s) { return (slot_bit(s) | ...); }
+static_assert(NSB == 69, "sb[] indices do not shift");
+constexpr SlotMask slot_bit(int i) { return (SlotMask)1 << i; }
+template <typename... S> constexpr SlotMask slots(S... s) { return (slot_bit(s) | ...); }
 // one instance of dev_decompress: three arrays of field elements and the exponentiation table
-struct DecSlots { Slot x, r, c, pow; constexpr uint64_t mask() const { return slots(x, r, c, pow); } };
+struct DecSlots { Slot x, r, c, pow; constexpr SlotMask mask() const { return slots(x, r, c, pow); } };
 constexpr DecSlots DEC_MAIN{SB_WORK_A, SB_WORK_B, SB_WORK_C, SB_POW_TABLE}, DEC_KEYS{SB_KEYS_X, SB_KEYS_R, SB_KEYS_C, SB_KEYS_POW}, DEC_SIGS{SB_SIGS_X, SB_SIGS_R, SB_SIGS_C, SB_SIGS_POW};
 // one instance of dev_msm: its buffers at fixed distances from a base slot (the gaps keep MSM_MAIN off SB_VB_PAIRS and SB_OFFS_DST)
 struct MsmSlots {
   enum Buf { POINTS = 0, SORTED = 1, WINDOW_SUMS = 2, KEYS = 3, NORM = 4, NORM_INV = 5, TEMP = 6, BUCKETS = 7, SLICES = 8, SLICES_HALF = 9, COUNTERS = 11, SPLIT_SCALARS = 13 };
   Slot base;
   constexpr Slot operator[](Buf b) const { return (Slot)(base + b); }
-  constexpr uint64_t mask() const { return slots(POINTS, SORTED, WINDOW_SUMS, KEYS, NORM, NORM_INV, TEMP, BUCKETS, SLICES, SLICES_HALF, COUNTERS, SPLIT_SCALARS) << base; }
+  constexpr SlotMask mask() const { return slots(POINTS, SORTED, WINDOW_SUMS, KEYS, NORM, NORM_INV, TEMP, BUCKETS, SLICES, SLICES_HALF, COUNTERS, SPLIT_SCALARS) << base; }
 };
 constexpr MsmSlots MSM_MAIN{SB_WORK_A}, MSM_RLC{SB_RLC_MSM};
 // one instance of segment_sums (pipelines_multi_verify.cpp): gathered points | ids, ranks, pair lists, counters, statuses | sums, norms, inverses.  zero_with_sums: the zero
 // flags of the sums lie behind the inverses (else behind the statuses): the two instances keep the layouts they were written with
-struct SegSlots { Slot points, labels, sums; bool zero_with_sums; constexpr uint64_t mask() const { return slots(points, labels, sums); } };
+struct SegSlots { Slot points, labels, sums; bool zero_with_sums; constexpr SlotMask mask() const { return slots(points, labels, sums); } };
 constexpr SegSlots SEG_AGG{SB_AGG_POINTS, SB_AGG_LABELS, SB_AGG_SUMS, false}, SEG_GRP{SB_GRP_POINTS, SB_GRP_LABELS, SB_GRP_SUMS, true}, SEG_THR{SB_THR_POINTS, SB_THR_LABELS, SB_THR_SUMS, true};
 // what every chain touches
-constexpr uint64_t M_HASH_G2 = slots(SB_WORK_A, SB_WORK_B, SB_WORK_C, SB_WORK_D, SB_NORM, SB_NORM_INV, SB_POINT_ST, SB_POW_TABLE, SB_CLEAR_S, SB_SWU_STATE, SB_SWU_POINTS);   // dev_hash_to_g2
-constexpr uint64_t M_LADDER = slots(SB_WORK_A, SB_WORK_B, SB_WORK_C, SB_NORM, SB_NORM_INV);                 // dev_point_mul
-constexpr uint64_t M_VB_MAIN = slots(SB_VB_PAIRS, SB_UNIFORM) | M_HASH_G2;                                 // verify_stage / verify_pipeline on the call's stream (and its sub-batch streams)
-constexpr uint64_t M_RLC_MAIN = slots(SB_STAGED, SB_UNIFORM, SB_RLC_WEIGHTS, SB_RLC_PAIRS, SB_RLC_PER_SET) | M_HASH_G2;   // verify_multiple_pipeline on the call's stream
-constexpr uint64_t M_RLC_SIDE2 = DEC_KEYS.mask() | slots(SB_AGG_DECODED, SB_RLC_KEYS_PROJ, SB_RLC_KEYS_NORM, SB_RLC_KEYS_INV) | SEG_AGG.mask() | SEG_GRP.mask();   // its key chain
-constexpr uint64_t M_RLC_SIDE = DEC_SIGS.mask() | MSM_RLC.mask();                                           // its signature chain
-constexpr uint64_t M_THR_OWN = slots(SB_STAGED, SB_THR_SHARES, SB_THR_SCALARS, SB_THR_OUT) | SEG_THR.mask();   // combine_pipeline: what outlives the stages it calls
-constexpr uint64_t M_POLY_OWN = slots(SB_STAGED, SB_POLY_COEFS, SB_POLY_LABELS, SB_POLY_ACC, SB_POLY_STEP, SB_POLY_OUT);   // poly_pipeline: what outlives the decoder it calls
-constexpr uint64_t M_MSMB_OWN = slots(SB_MSMB_CALL, SB_MSMB_SLAB);   // msm_batch_pipeline: what outlives the dev_msm calls of its big groups
+constexpr SlotMask M_HASH_G2 = slots(SB_WORK_A, SB_WORK_B, SB_WORK_C, SB_WORK_D, SB_NORM, SB_NORM_INV, SB_POINT_ST, SB_POW_TABLE, SB_CLEAR_S, SB_SWU_STATE, SB_SWU_POINTS);   // dev_hash_to_g2
+constexpr SlotMask M_LADDER = slots(SB_WORK_A, SB_WORK_B, SB_WORK_C, SB_NORM, SB_NORM_INV);                 // dev_point_mul
+constexpr SlotMask M_VB_MAIN = slots(SB_VB_PAIRS, SB_UNIFORM) | M_HASH_G2;                                 // verify_stage / verify_pipeline on the call's stream (and its sub-batch streams)
+constexpr SlotMask M_RLC_MAIN = slots(SB_STAGED, SB_UNIFORM, SB_RLC_WEIGHTS, SB_RLC_PAIRS, SB_RLC_PER_SET) | M_HASH_G2;   // verify_multiple_pipeline on the call's stream
+constexpr SlotMask M_RLC_SIDE2 = DEC_KEYS.mask() | slots(SB_AGG_DECODED, SB_RLC_KEYS_PROJ, SB_RLC_KEYS_NORM, SB_RLC_KEYS_INV) | SEG_AGG.mask() | SEG_GRP.mask();   // its key chain
+constexpr SlotMask M_RLC_SIDE = DEC_SIGS.mask() | MSM_RLC.mask();                                           // its signature chain
+constexpr SlotMask M_THR_OWN = slots(SB_STAGED, SB_THR_SHARES, SB_THR_SCALARS, SB_THR_OUT) | SEG_THR.mask();   // combine_pipeline: what outlives the stages it calls
+constexpr SlotMask M_POLY_OWN = slots(SB_STAGED, SB_POLY_COEFS, SB_POLY_LABELS, SB_POLY_ACC, SB_POLY_STEP, SB_POLY_OUT);   // poly_pipeline: what outlives the decoder it calls
+constexpr SlotMask M_KZG_OWN = slots(SB_STAGED, SB_KZG_POINTS, SB_KZG_SCALARS, SB_KZG_PAIRS, SB_KZG_OUT, SB_KZG_ITEMS);   // kzg_pipeline: what outlives the decoder, the MSMs and the ladders it calls
+constexpr SlotMask M_MSMB_OWN = slots(SB_MSMB_CALL, SB_MSMB_SLAB);   // msm_batch_pipeline: what outlives the dev_msm calls of its big groups
 // what runs side by side
 static_assert(!(M_VB_MAIN & DEC_KEYS.mask()), "verifyBatch decodes its keys (side2, or the sub-batch's own stream) beside the hash chain");
 static_assert(!(M_RLC_MAIN & M_RLC_SIDE2) && !(M_RLC_MAIN & M_RLC_SIDE) && !(M_RLC_SIDE & M_RLC_SIDE2), "verify_multiple_pipeline: the chains on s, side and side2 run side by side");
@@ -159,6 +171,8 @@ static_assert(!((M_POLY_OWN & ~slot_bit(SB_STAGED)) & (M_THR_OWN | M_RLC_MAIN | 
               "poly_pipeline keeps to slots of its own: no other chain's buffers are regrown or overwritten by it");
 static_assert(!(M_MSMB_OWN & (MSM_MAIN.mask() | M_POLY_OWN | M_THR_OWN | M_RLC_MAIN | M_RLC_SIDE | M_RLC_SIDE2 | M_VB_MAIN | M_LADDER)),
               "msm_batch_pipeline: its big groups run through dev_msm on the main slots between its slabs, which must regrow nothing the call still holds");
+static_assert(!(M_KZG_OWN & (DEC_MAIN.mask() | MSM_RLC.mask() | M_LADDER)), "kzg_pipeline: the decoder, the MSMs (on the slots of MSM_RLC: MSM_MAIN holds SB_STAGED) and the ladders of the per-item pass regrow their slots while the call holds its own");
+static_assert(!((M_KZG_OWN & ~slot_bit(SB_STAGED)) & (M_MSMB_OWN | M_POLY_OWN | M_THR_OWN | M_RLC_MAIN | M_RLC_SIDE | M_RLC_SIDE2 | M_VB_MAIN | MSM_MAIN.mask())), "kzg_pipeline keeps to slots of its own");
 // ---- END scratch slots -------------------------------------------------------------------------------------------------------------------------------------
 #define EXPORT extern "C" __attribute__((visibility("default")))
 extern std::recursive_mutex g_null_mu;   // locked in place of a context's mutex when the caller passed no context (the call then fails with NBLS_EINVAL)
@@ -247,6 +261,7 @@ struct nbls_ctx {
   size_t ls_max = ::ls_max(), ls2_max = ::ls2_max();
   size_t chain_max = (size_t)env_long("NBLS_CHAIN_MAX", 8192);                  // nbls_set_tuning(NBLS_TUNE_CHAIN_MAX); see run_chain
   u32* qp_table = nullptr;      // multiples of p for the weak reduction (vm_exec.h weak_reduce), device copy
+  uint8_t* kzg_roots[13] = {nullptr};   // kzg_kernels.hip: the 2^k roots of unity in bit-reversed order, Montgomery form (32 bytes each), built on first use of log2_n = k, freed with the context
   uint8_t* unit_lines = nullptr;   // a line table whose 68 lines are all 1 (c0 = 1, c1 = c2 = 0): the neutral partner of an odd last pair
   uint8_t* partial = nullptr;   // 576 bytes: the Fp12 partial of the *_partial entry points (multi-GPU reductions)
   uint8_t* L = nullptr; size_t cap_L = 0;   // line tables of the Miller loop (LINE_BYTES each), at most LINES_CHUNK of them
@@ -442,6 +457,7 @@ struct MultiVerifyIn {
   size_t n; const uint8_t *sigs96, *msgs; const uint32_t* offsets; const uint8_t* pks48; const AggKeys* agg; const MsgGroups* mg; const uint8_t* dst; size_t dst_len; const uint8_t* seed32;
 };
 int verify_multiple_pipeline(nbls_ctx* ctx, const MultiVerifyIn& in, int* all_ok, int8_t* status);
+int os_seed(uint8_t* seed32);
 int verify_batch_partial_core(nbls_ctx* ctx, size_t n, const uint8_t* sig96 /* or NULL */, const uint8_t* msgs, const uint32_t* offsets, const uint8_t* pk48,
                                      const uint8_t* dst, size_t dst_len, void* d_dst, void** d_partial, int* zero_flag, int8_t* pk_status);
 #define NBLS_STAGING_CALL   // Staged / read_back use the context and the declarations above

@@ -22,7 +22,7 @@
 #include <new>
 #include <sys/random.h>
 
-static int os_seed(uint8_t* seed) {
+int os_seed(uint8_t* seed) {   // 32 bytes from getrandom(2): the seed of the secret weights when the caller passes none (also pipelines_kzg.cpp)
   size_t got = 0;
   while (got < 32) {
     const ssize_t k = getrandom(seed + got, 32 - got, 0);

@@ -548,6 +548,32 @@ __attribute__((visibility("default"))) void nbls_sim_fr_lagrange(unsigned n, uns
   for (unsigned k = 0; k < n; k++) fr_store_be(fr_select((u32)0 - (u32)(bad_group[group_of[k]] != 0), fr_zero(), fr_from_mont(lambda[k])), out32 + 32ull * k);
   for (unsigned j = 0; j < ngroups; j++) status[j] = bad_group[j] ? 20 : 0;
 }
+// nbls_fr_eval_roots as kzg_kernels.hip runs it: the table of roots (kzg_roots_kernel), then per polynomial the FR_EVAL_LANES lanes of kzg_eval_kernel with the same terms per
+// lane, the tree of additions in the workgroup's order, and the closing step.  Returns -1 (NBLS_EINVAL) under the rules of the device call that need no context
+static void sim_eval_poly(unsigned log2_n, const uint8_t* f32, const uint8_t* z32, const Fr* roots, uint8_t* out32, int8_t* status) {
+  const u32 N = 1u << log2_n, W = FR_EVAL_LANES;
+  const Fr zraw = fr_load_be(z32), z = fr_mul(zraw, fr_r2());
+  std::vector<Fr> part(W);
+  std::vector<u32> pre((size_t)((N + W - 1) / W) * FR_NL * W);
+  u32 hit = 0xffffffffu, bad = fr_ge_r_mask(zraw);
+  for (u32 l = 0; l < W; l++) {
+    const FrEvalPart p = fr_eval_lane(f32, roots, z, N, l, W, pre.data());
+    part[l] = p.sum; bad |= p.bad;
+    if (p.hit != 0xffffffffu) hit = p.hit;
+  }
+  for (u32 s = W / 2; s > 0; s >>= 1) for (u32 l = 0; l < s; l++) part[l] = fr_add(part[l], part[l + s]);
+  const int st = fr_eval_finish(part[0], hit, bad, z, log2_n, f32, out32);
+  if (status) *status = (int8_t)st;
+}
+__attribute__((visibility("default"))) int nbls_sim_fr_eval_roots(unsigned log2_n, size_t n, const uint8_t* evals32, const uint8_t* z32, uint8_t* out32, int8_t* status) {
+  if (log2_n < 1 || log2_n > 12 || (n && (!evals32 || !z32 || !out32)) || (n << log2_n) > ((size_t)1 << 24)) return -1;
+  const u32 N = 1u << log2_n;
+  std::vector<Fr> roots(N);
+  const Fr omega = fr_omega(log2_n);
+  for (u32 j = 0; j < N; j++) roots[j] = fr_root_entry(omega, log2_n, j);
+  for (size_t p = 0; p < n; p++) sim_eval_poly(log2_n, evals32 + 32ull * N * p, z32 + 32ull * p, roots.data(), out32 + 32ull * p, status ? status + p : nullptr);
+  return 0;
+}
 __attribute__((visibility("default"))) int nbls_sim_program_count() { return (int)P_COUNT; }
 __attribute__((visibility("default"))) void nbls_sim_stats() { for (int i = 0; i < P_COUNT; i++) print_stats(get_program((ProgId)i)); }
 }

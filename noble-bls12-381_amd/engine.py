@@ -81,6 +81,9 @@ def load_library():
     lib.nbls_g1_combine_shares.argtypes = [vp, sz, vp, vp, vp, vp, vp]
     lib.nbls_g1_poly_eval.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp]
     lib.nbls_g2_poly_eval.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp]
+    lib.nbls_fr_eval_roots.argtypes = [vp, C.c_uint, sz, vp, vp, vp, vp]
+    lib.nbls_kzg_verify_proofs.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, C.POINTER(i32), vp]
+    lib.nbls_kzg_verify_blobs.argtypes = [vp, C.c_uint, sz, vp, vp, vp, vp, vp, C.POINTER(i32), vp]
     lib.nbls_keyset_create.argtypes = [vp, sz, vp, vp, C.POINTER(vp)]
     lib.nbls_keyset_destroy.argtypes = [vp]
     lib.nbls_keyset_destroy.restype = None
@@ -504,6 +507,50 @@ class Engine:
         self._chk(f(self.h, m, coffs, b''.join(bytes(x) for g in groups for x in g[0]), ioffs, ids, out, st))
         raw, sraw = out.raw, st.raw
         return ([[raw[e * k:e * k + e] for k in range(ioffs[g], ioffs[g + 1])] for g in range(m)], [list(sraw[ioffs[g]:ioffs[g + 1]]) for g in range(m)])
+
+    # ---- KZG (include/nbls.h: nbls_fr_eval_roots, nbls_kzg_verify_proofs, nbls_kzg_verify_blobs); field elements must be canonical here (status 21 otherwise)
+    def fr_eval_roots(self, log2_n, polys, zs):
+        """polys: n polynomials, each the list of its 2^log2_n values on the roots of unity in bit-reversed order (ints or 32-byte values), or their concatenated bytes; zs: n points
+        -> (list of 32-byte values p_i(z_i), status list: 21 = an element or the point is >= r, the value is then all-zero)"""
+        n = len(zs)
+        ev = bytes(polys) if isinstance(polys, (bytes, bytearray, memoryview)) else b''.join(self._fr32(v) for f in polys for v in f)
+        if len(ev) != (32 * n) << log2_n:
+            raise NblsError('fr_eval_roots: %d points need %d bytes of values, got %d' % (n, (32 * n) << log2_n, len(ev)))
+        out = C.create_string_buffer(max(32 * n, 1)); st = C.create_string_buffer(max(n, 1))
+        self._chk(self.lib.nbls_fr_eval_roots(self.h, log2_n, n, ev, b''.join(map(self._fr32, zs)), out, st))
+        raw = out.raw
+        return [raw[32 * i:32 * i + 32] for i in range(n)], list(st.raw[:n])
+
+    @staticmethod
+    def _kzg_args(name, n, commitments48, proofs48, tau_g2_96, seed):
+        if len(commitments48) != n or len(proofs48) != n or any(len(x) != 48 for x in commitments48) or any(len(x) != 48 for x in proofs48) or len(tau_g2_96) != 96 or \
+           (seed is not None and len(seed) != 32):
+            raise NblsError('%s: %d items need %d 48-byte commitments and proofs, 96 bytes of [tau]G2 and a seed of 32 bytes or None' % (name, n, n))
+
+    def kzg_verify_proofs(self, commitments48, zs, ys, proofs48, tau_g2_96, seed=None, per_item=True):
+        """verify_kzg_proof_batch: n tuples (commitment, z, y, proof) against the setup's compressed [tau]G2 -> (all_ok, status bytes or None).  statuses: 0 ok, 9 not verified,
+        3 / 4 the commitment does not decode, 13 / 14 the proof, 21 z or y is >= r; seed: 32 bytes, None = from the OS; per_item=False: the combined check alone (fast reject)"""
+        n = len(zs)
+        if len(ys) != n:
+            raise NblsError('kzg_verify_proofs: %d points and %d values' % (n, len(ys)))
+        self._kzg_args('kzg_verify_proofs', n, commitments48, proofs48, tau_g2_96, seed)
+        ok = C.c_int(0)
+        st = C.create_string_buffer(max(n, 1)) if per_item else None
+        self._chk(self.lib.nbls_kzg_verify_proofs(self.h, n, b''.join(commitments48), b''.join(map(self._fr32, zs)), b''.join(map(self._fr32, ys)), b''.join(proofs48), bytes(tau_g2_96),
+                                                  seed, C.byref(ok), st))
+        return bool(ok.value), (st.raw[:n] if per_item else None)
+
+    def kzg_verify_blobs(self, log2_n, blobs, commitments48, proofs48, tau_g2_96, seed=None, per_item=True):
+        """verify_blob_kzg_proof_batch: blobs = n byte strings of 32 << log2_n bytes each (log2_n = 12: the mainnet blob); the challenge is hashed on host threads, the polynomial
+        evaluated on the device -> (all_ok, status bytes or None) as kzg_verify_proofs; 21 also for a blob with an element >= r"""
+        n = len(blobs)
+        if any(len(b) != 32 << log2_n for b in blobs):
+            raise NblsError('kzg_verify_blobs: every blob has %d bytes' % (32 << log2_n))
+        self._kzg_args('kzg_verify_blobs', n, commitments48, proofs48, tau_g2_96, seed)
+        ok = C.c_int(0)
+        st = C.create_string_buffer(max(n, 1)) if per_item else None
+        self._chk(self.lib.nbls_kzg_verify_blobs(self.h, log2_n, n, b''.join(blobs), b''.join(commitments48), b''.join(proofs48), bytes(tau_g2_96), seed, C.byref(ok), st))
+        return bool(ok.value), (st.raw[:n] if per_item else None)
 
     def get_public_keys(self, keys):
         """getPublicKey for a batch of private keys -> list of 48-byte compressed keys; raises like the reference on a zero key"""

@@ -81,6 +81,12 @@ export declare class PointG1 {
   static evalCommitment(coefs: PointG1[], ids: ShareId[]): Promise<PointG1[]>;
   static evalCommitment(coefs: Hex[], ids: ShareId[]): Promise<Uint8Array[]>;
   static evalCommitmentBatch(groups: CommitmentGroup<PointG1>[]): Promise<(PointG1[] | Uint8Array[])[]>;
+  /** EIP-4844 verify_kzg_proof_batch against the setup's [tau]G2; status: 0 ok, 9 not verified, 3 / 4 commitment, 13 / 14 proof, 21 non-canonical field element */
+  static verifyKzgProofBatch(commitments: (PointG1 | Hex)[], zs: ShareId[], ys: ShareId[], proofs: (PointG1 | Hex)[], tauG2: PointG2 | Hex, opts?: KzgOptions): KzgResult;
+  static verifyKzgProofBatchAsync(commitments: (PointG1 | Hex)[], zs: ShareId[], ys: ShareId[], proofs: (PointG1 | Hex)[], tauG2: PointG2 | Hex, opts?: KzgOptions): Promise<KzgResult>;
+  /** EIP-4844 verify_blob_kzg_proof_batch: blobs of 32 * 2^k bytes (k = 12 on mainnet); the challenge is hashed on the host, the polynomial evaluated on the device */
+  static verifyBlobKzgProofBatch(blobs: Hex[], commitments: (PointG1 | Hex)[], proofs: (PointG1 | Hex)[], tauG2: PointG2 | Hex, opts?: KzgOptions): KzgResult;
+  static verifyBlobKzgProofBatchAsync(blobs: Hex[], commitments: (PointG1 | Hex)[], proofs: (PointG1 | Hex)[], tauG2: PointG2 | Hex, opts?: KzgOptions): Promise<KzgResult>;
   isZero(): boolean; equals(rhs: PointG1): boolean; negate(): PointG1; add(rhs: PointG1): PointG1; subtract(rhs: PointG1): PointG1; double(): PointG1;
   multiply(scalar: bigint | number): PointG1; multiplyUnsafe(scalar: bigint | number): PointG1; multiplyPrecomputed(scalar: bigint | number): PointG1;
   assertValidity(): this; toAffine(): [Fp, Fp]; toRawBytes(isCompressed?: boolean): Uint8Array; toHex(isCompressed?: boolean): string;
@@ -128,6 +134,9 @@ export declare function verifyMultipleSignatures(sets: { publicKey: Hex | PointG
 /** verify(signature, message, aggregatePublicKeys(publicKeys)) for every set, checked together by a random linear combination on the GPU; throws where that throws for the first such set */
 export declare function verifyMultipleAggregateSignatures(sets: { publicKeys: (Hex | PointG1)[]; message: Hex | PointG2; signature: Hex | PointG2 }[]): Promise<boolean>;
 export type ShareId = bigint | number | string | Uint8Array;
+/** KZG: seed = 32 bytes for reproducible weights (default: from the OS); perItem === false stops after the combined check (status null) */
+export interface KzgOptions { seed?: Hex; perItem?: boolean }
+export interface KzgResult { ok: boolean; status: Uint8Array | null }
 /** one group of combineSharesBatch: its shares are all points or all compressed bytes / hex */
 export type ShareGroup<P> = { shares: P[] | Hex[]; ids: ShareId[] } | [P[] | Hex[], ShareId[]];
 /** one group of evalCommitmentBatch: its coefficients are all points or all compressed bytes / hex */
@@ -140,6 +149,11 @@ export interface NativeThresholdCalls {
   combineSharesAsync(g2: number, groupOffsets: Uint32Array, ids32: Uint8Array, shares: Uint8Array): Promise<{ out: Uint8Array; status: Uint8Array }>;
   /** nbls_g1_poly_eval / nbls_g2_poly_eval: one compressed point and one status per identifier */
   polyEvalAsync(g2: number, coefOffsets: Uint32Array, coefs: Uint8Array, idOffsets: Uint32Array, ids32: Uint8Array): Promise<{ out: Uint8Array; status: Uint8Array }>;
+  /** nbls_kzg_verify_proofs / nbls_kzg_verify_blobs: out = the verdict as a native int (4 bytes), status = one byte per item */
+  kzgVerifyProofs(commitments48: Uint8Array, z32: Uint8Array, y32: Uint8Array, proofs48: Uint8Array, tauG2: Uint8Array, seed32: Uint8Array | null, perItem: number): { out: Uint8Array; status: Uint8Array };
+  kzgVerifyProofsAsync(commitments48: Uint8Array, z32: Uint8Array, y32: Uint8Array, proofs48: Uint8Array, tauG2: Uint8Array, seed32: Uint8Array | null, perItem: number): Promise<{ out: Uint8Array; status: Uint8Array }>;
+  kzgVerifyBlobs(log2n: number, blobs: Uint8Array, commitments48: Uint8Array, proofs48: Uint8Array, tauG2: Uint8Array, seed32: Uint8Array | null, perItem: number): { out: Uint8Array; status: Uint8Array };
+  kzgVerifyBlobsAsync(log2n: number, blobs: Uint8Array, commitments48: Uint8Array, proofs48: Uint8Array, tauG2: Uint8Array, seed32: Uint8Array | null, perItem: number): Promise<{ out: Uint8Array; status: Uint8Array }>;
 }
 /** The two calls of the N-API addon (nbls_napi.node) that verifyMultipleSignatures / verifyMultipleAggregateSignatures take when at least two wire-format sets have equal messages:
  * msgs / offsets hold the distinct messages, set i signs message msgIndex[i] (nbls_verify_multiple_shared / nbls_verify_aggregates_shared; a type only, the facade does not export the addon) */

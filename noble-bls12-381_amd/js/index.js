@@ -150,6 +150,73 @@ async function evalCommitmentBatch(Point, groups) {
   });
 }
 
+// ---- KZG (nbls_kzg_verify_proofs / nbls_kzg_verify_blobs; EIP-4844, not in the reference): verify_kzg_proof_batch and verify_blob_kzg_proof_batch against the setup's [tau]G2
+// (96 compressed bytes, hex, or a PointG2).  Commitments and proofs: 48 compressed bytes, hex, or PointG1 (the zero point is valid for both); z, y: bigint | number | hex | 32
+// bytes, canonical (a value >= CURVE.r is refused with status 21).  -> { ok, status }: ok = every item verified; status = one byte per item (0 ok, 9 not verified, 3 / 4 the
+// commitment does not decode, 13 / 14 the proof, 21 a non-canonical field element), or null with opts.perItem === false (the combined check alone).  opts.seed: 32 bytes for a
+// reproducible test; by default the weights come from the OS.  The arrays are filled by loops: a mainnet call carries blobs of 131,072 bytes each
+function kzgPack(items, width, what, toBytes) {
+  const out = new Uint8Array(items.length * width);
+  for (let i = 0; i < items.length; i++) {
+    const b = toBytes(items[i]);
+    if (b.length !== width) throw new Error('Invalid ' + what + ': expected ' + width + ' bytes');
+    out.set(b, i * width);
+  }
+  return out;
+}
+const kzgG1 = (p) => (p instanceof PointG1 ? p.toRawBytes(true) : ensureBytes(p));
+const kzgTau = (t) => { const b = t instanceof PointG2 ? t.toSignature() : ensureBytes(t); if (b.length !== 96) throw new Error('Invalid [tau]G2: expected 96 compressed bytes'); return b; };
+function kzgSeed(opts) {
+  const seed = opts && opts.seed ? ensureBytes(opts.seed) : null;
+  if (seed && seed.length !== 32) throw new Error('Invalid seed: expected 32 bytes');
+  return seed;
+}
+function kzgResult(res, perItem) {
+  const ok = (res.out[0] | res.out[1] | res.out[2] | res.out[3]) !== 0;
+  return { ok, status: perItem ? res.status : null };
+}
+function kzgProofArgs(commitments, zs, ys, proofs, tauG2, opts) {
+  const n = commitments.length;
+  if (!n) throw new Error('Expected non-empty array');
+  if (zs.length !== n || ys.length !== n || proofs.length !== n) throw new Error('Expected as many points, values and proofs as commitments');
+  const perItem = !(opts && opts.perItem === false);
+  return [kzgPack(commitments, 48, 'commitment', kzgG1), kzgPack(zs, 32, 'field element', shareIdBytes), kzgPack(ys, 32, 'field element', shareIdBytes), kzgPack(proofs, 48, 'proof', kzgG1),
+    kzgTau(tauG2), kzgSeed(opts), perItem ? 1 : 0];
+}
+function kzgBlobArgs(blobs, commitments, proofs, tauG2, opts) {
+  const n = blobs.length;
+  if (!n) throw new Error('Expected non-empty array');
+  if (commitments.length !== n || proofs.length !== n) throw new Error('Expected as many commitments and proofs as blobs');
+  const first = ensureBytes(blobs[0]), log2n = Math.round(Math.log2(first.length / 32));
+  if (log2n < 1 || log2n > 12 || first.length !== 32 << log2n) throw new Error('Invalid blob: expected 32 * 2^k bytes, 1 <= k <= 12');
+  const perItem = !(opts && opts.perItem === false);
+  return [log2n, kzgPack(blobs, first.length, 'blob', ensureBytes), kzgPack(commitments, 48, 'commitment', kzgG1), kzgPack(proofs, 48, 'proof', kzgG1), kzgTau(tauG2), kzgSeed(opts), perItem ? 1 : 0];
+}
+function kzgFail(e) {
+  if (e && e.nblsCode === -5) throw new Error('Invalid [tau]G2: does not decode or is the zero point');
+  throw e;
+}
+function verifyKzgProofBatch(commitments, zs, ys, proofs, tauG2, opts) {
+  const a = kzgProofArgs(commitments, zs, ys, proofs, tauG2, opts);
+  ensureInit();
+  try { return kzgResult(native.kzgVerifyProofs(a[0], a[1], a[2], a[3], a[4], a[5], a[6]), a[6]); } catch (e) { return kzgFail(e); }
+}
+async function verifyKzgProofBatchAsync(commitments, zs, ys, proofs, tauG2, opts) {
+  const a = kzgProofArgs(commitments, zs, ys, proofs, tauG2, opts);
+  ensureInit();
+  try { return kzgResult(await native.kzgVerifyProofsAsync(a[0], a[1], a[2], a[3], a[4], a[5], a[6]), a[6]); } catch (e) { return kzgFail(e); }
+}
+function verifyBlobKzgProofBatch(blobs, commitments, proofs, tauG2, opts) {
+  const a = kzgBlobArgs(blobs, commitments, proofs, tauG2, opts);
+  ensureInit();
+  try { return kzgResult(native.kzgVerifyBlobs(a[0], a[1], a[2], a[3], a[4], a[5], a[6]), a[6]); } catch (e) { return kzgFail(e); }
+}
+async function verifyBlobKzgProofBatchAsync(blobs, commitments, proofs, tauG2, opts) {
+  const a = kzgBlobArgs(blobs, commitments, proofs, tauG2, opts);
+  ensureInit();
+  try { return kzgResult(await native.kzgVerifyBlobsAsync(a[0], a[1], a[2], a[3], a[4], a[5], a[6]), a[6]); } catch (e) { return kzgFail(e); }
+}
+
 // Points are held as affine wire bytes (what the engine consumes) or as the zero point.  The reference's constructor form
 // new PointG1(x: Fp, y: Fp, z?: Fp) (index.ts:291) is accepted too: the projective triple is made affine on the host.
 class PointG1 {
@@ -267,6 +334,11 @@ class PointG1 {
   // commitment polynomial (coefficients lowest degree first) -> the public keys of the shares with these identifiers (evalCommitmentBatch above)
   static async evalCommitment(coefs, ids) { return (await evalCommitmentBatch(PointG1, [{ coefs, ids }]))[0]; }
   static evalCommitmentBatch(groups) { return evalCommitmentBatch(PointG1, groups); }
+  // KZG commitments and proofs are G1 points: verify_kzg_proof_batch / verify_blob_kzg_proof_batch of EIP-4844 (above), synchronous and on a worker thread
+  static verifyKzgProofBatch(commitments, zs, ys, proofs, tauG2, opts) { return verifyKzgProofBatch(commitments, zs, ys, proofs, tauG2, opts); }
+  static verifyKzgProofBatchAsync(commitments, zs, ys, proofs, tauG2, opts) { return verifyKzgProofBatchAsync(commitments, zs, ys, proofs, tauG2, opts); }
+  static verifyBlobKzgProofBatch(blobs, commitments, proofs, tauG2, opts) { return verifyBlobKzgProofBatch(blobs, commitments, proofs, tauG2, opts); }
+  static verifyBlobKzgProofBatchAsync(blobs, commitments, proofs, tauG2, opts) { return verifyBlobKzgProofBatchAsync(blobs, commitments, proofs, tauG2, opts); }
   equals(rhs) { return this.zero === rhs.zero && (this.zero || bytesToHex(this.aff) === bytesToHex(rhs.aff)); }
   // reference index.ts:359-381
   toHex(isCompressed = false) {

@@ -2,7 +2,7 @@
  * nbls_napi.c -- thin N-API addon: exposes the C ABI of libnbls.so (include/nbls.h) to Node.  No arithmetic here.
  * libnbls.so is loaded with dlopen at module init so the addon builds with plain gcc (no HIP needed):
  *     gcc -shared -fPIC -I/usr/include/node -I../../include nbls_napi.c -o nbls_napi.node -ldl
- * Calls are synchronous (they block for the duration of the GPU work) except verifyBatchAsync (and signBatchAsync, verifyMultipleAsync, verifyAggregatesAsync, verifyMultipleSharedAsync, verifyAggregatesSharedAsync, frOpAsync, lagrangeAtZeroAsync, combineSharesAsync, polyEvalAsync), which runs on a libuv worker thread
+ * Calls are synchronous (they block for the duration of the GPU work) except verifyBatchAsync (and signBatchAsync, verifyMultipleAsync, verifyAggregatesAsync, verifyMultipleSharedAsync, verifyAggregatesSharedAsync, frOpAsync, lagrangeAtZeroAsync, combineSharesAsync, polyEvalAsync, kzgVerifyProofsAsync, kzgVerifyBlobsAsync), which runs on a libuv worker thread
  * (napi_create_async_work) and resolves a Promise: the facade's verifyBatch uses it for wire-format inputs (the calls that can take tens of milliseconds).  Typed arrays are passed by reference (napi_get_typedarray_info), no copies.
  */
 #include <node_api.h>
@@ -22,6 +22,7 @@ SYM(nbls_init_multi) SYM(nbls_destroy_multi) SYM(nbls_multi_device_count) SYM(nb
 SYM(nbls_g2_prepare) SYM(nbls_pairing_prepared) SYM(nbls_verify_multiple) SYM(nbls_verify_aggregates) SYM(nbls_verify_multiple_shared) SYM(nbls_verify_aggregates_shared)
 SYM(nbls_g1_from_hex_batch) SYM(nbls_g2_from_hex_batch) SYM(nbls_g2_from_signature_batch) SYM(nbls_g1_clear_cofactor_batch) SYM(nbls_g2_clear_cofactor_batch)
 SYM(nbls_fr_op_batch) SYM(nbls_lagrange_at_zero) SYM(nbls_g2_combine_shares) SYM(nbls_g1_combine_shares) SYM(nbls_g1_poly_eval) SYM(nbls_g2_poly_eval)
+SYM(nbls_kzg_verify_proofs) SYM(nbls_kzg_verify_blobs)
 static nbls_ctx* ctx;
 static nbls_multi* multi;   /* several GPUs behind one handle (initMulti): ctx is then its first context; the batch calls shard over all of them */
 #define MULTI() (multi && p_nbls_multi_device_count(multi) > 1)
@@ -429,20 +430,30 @@ static napi_value SignBatchAsync(napi_env env, napi_callback_info info) {
  *                                                      identifiers of their groups; out = one compressed point per identifier, status per identifier
  * The offsets must name identifiers and shares that are in the arrays (checked here); the library checks the rest. */
 typedef struct {
-  napi_async_work work; napi_deferred deferred; napi_ref refs[6]; int nrefs;
-  int kind /* 0 frOp, 1 lagrangeAtZero, 2 combineShares, 3 polyEval */, op, g2; const uint8_t *a, *b, *shares; const uint32_t *offs, *coffs; size_t n; uint8_t* out; int8_t* st;
+  napi_async_work work; napi_deferred deferred; napi_ref refs[9]; int nrefs;
+  int kind /* 0 frOp, 1 lagrangeAtZero, 2 combineShares, 3 polyEval, 4 kzgVerifyProofs, 5 kzgVerifyBlobs */, op, g2; const uint8_t *a, *b, *shares; const uint32_t *offs, *coffs; size_t n;
+  uint8_t* out; int8_t* st;
+  const uint8_t *proofs, *tau, *seed; int per_item;   /* KZG: a = commitments, b = z (proofs) or the blobs, shares = y, op = log2_n; out = the verdict as one int */
   nbls_ctx* c; int rc;
 } thr_job;
 static void thr_execute(napi_env env, void* data) { thr_job* j = (thr_job*)data; (void)env;
   j->rc = j->kind == 0 ? p_nbls_fr_op_batch(j->c, j->op, j->n, j->a, j->b, j->out, j->st)
         : j->kind == 1 ? p_nbls_lagrange_at_zero(j->c, j->n, j->offs, j->a, j->out, j->st)
+        : j->kind == 4 ? p_nbls_kzg_verify_proofs(j->c, j->n, j->a, j->b, j->shares, j->proofs, j->tau, j->seed, (int*)j->out, j->per_item ? j->st : NULL)
+        : j->kind == 5 ? p_nbls_kzg_verify_blobs(j->c, (unsigned)j->op, j->n, j->b, j->a, j->proofs, j->tau, j->seed, (int*)j->out, j->per_item ? j->st : NULL)
         : j->kind == 3 ? (j->g2 ? p_nbls_g2_poly_eval : p_nbls_g1_poly_eval)(j->c, j->n, j->coffs, j->shares, j->offs, j->a, j->out, j->st)
         : (j->g2 ? p_nbls_g2_combine_shares : p_nbls_g1_combine_shares)(j->c, j->n, j->offs, j->a, j->shares, j->out, j->st); }
+/* the Error of a failed call of this family: the message of throw_code, and the library's return code as the number `nblsCode` (what the facade reads: never the text) */
+static napi_value thr_error(napi_env env, int rc) {
+  char m[128]; snprintf(m, sizeof m, "nbls: %s (code %d)", p_nbls_strerror ? p_nbls_strerror(rc) : "error", rc);
+  napi_value msg, err, code; napi_create_string_utf8(env, m, NAPI_AUTO_LENGTH, &msg); napi_create_error(env, NULL, msg, &err);
+  napi_create_int32(env, rc, &code); napi_set_named_property(env, err, "nblsCode", code);
+  return err;
+}
 static void thr_complete(napi_env env, napi_status status, void* data) {
   thr_job* j = (thr_job*)data;
   if (status != napi_ok || j->rc) {
-    char m[128]; snprintf(m, sizeof m, "nbls: %s (code %d)", p_nbls_strerror ? p_nbls_strerror(j->rc) : "error", j->rc);
-    napi_value msg, err; napi_create_string_utf8(env, m, NAPI_AUTO_LENGTH, &msg); napi_create_error(env, NULL, msg, &err); napi_reject_deferred(env, j->deferred, err);
+    napi_reject_deferred(env, j->deferred, thr_error(env, j->rc));
   } else {
     napi_value vo, vs; napi_get_reference_value(env, j->refs[j->nrefs - 2], &vo); napi_get_reference_value(env, j->refs[j->nrefs - 1], &vs);
     napi_resolve_deferred(env, j->deferred, result2(env, vo, vs));
@@ -452,7 +463,7 @@ static void thr_complete(napi_env env, napi_status status, void* data) {
 }
 /* runs the job here (async == 0) or queues it; vo / vs: the output arrays, made by the caller on the main thread */
 static napi_value thr_run(napi_env env, thr_job* job, int async, napi_value* argv, int nargs, napi_value vo, napi_value vs) {
-  if (!async) { job->c = ctx; thr_execute(env, job); return job->rc ? throw_code(env, job->rc) : result2(env, vo, vs); }
+  if (!async) { job->c = ctx; thr_execute(env, job); if (job->rc) { napi_throw(env, thr_error(env, job->rc)); return NULL; } return result2(env, vo, vs); }
   thr_job* j = (thr_job*)calloc(1, sizeof *j); if (!j) { napi_throw_error(env, NULL, "out of memory"); return NULL; }
   *j = *job; j->c = pool_take(); j->nrefs = nargs + 2;
   for (int i = 0; i < nargs; i++) napi_create_reference(env, argv[i], 1, &j->refs[i]);
@@ -520,6 +531,49 @@ static napi_value poly_call(napi_env env, napi_callback_info info, int async) {
 static napi_value PolyEval(napi_env env, napi_callback_info info) { return poly_call(env, info, 0); }
 static napi_value PolyEvalAsync(napi_env env, napi_callback_info info) { return poly_call(env, info, 1); }
 
+/* KZG (nbls_kzg_verify_proofs / nbls_kzg_verify_blobs), synchronous and *Async -> {out, status}: out = the verdict (4 bytes, a native int: non-zero = every item verified),
+ * status = one byte per item (all-zero when perItem is 0 and the call stopped after the combined check)
+ *   kzgVerifyProofs(commitments48, z32, y32, proofs48, tauG2, seed32 | null, perItem)
+ *   kzgVerifyBlobs(log2n, blobs, commitments48, proofs48, tauG2, seed32 | null, perItem) */
+static int kzg_seed(napi_env env, napi_value v, const uint8_t** seed) {
+  napi_valuetype t; napi_typeof(env, v, &t);
+  *seed = NULL;
+  if (t == napi_null || t == napi_undefined) return 1;
+  uint8_t* p; size_t l;
+  if (!get_bytes(env, v, &p, &l) || l != 32) { napi_throw_type_error(env, NULL, "expected a 32-byte seed or null"); return 0; }
+  *seed = p; return 1;
+}
+static napi_value kzg_proofs_call(napi_env env, napi_callback_info info, int async) {
+  ARGS(7); NEED_CTX(); BYTES(0, cs, lc); BYTES(1, z, lz); BYTES(2, y, ly); BYTES(3, ps, lp); BYTES(4, tau, lt);
+  const uint8_t* seed; if (!kzg_seed(env, argv[5], &seed)) return NULL;
+  int32_t per; if (napi_get_value_int32(env, argv[6], &per) != napi_ok) { napi_throw_type_error(env, NULL, "expected 0 or 1"); return NULL; }
+  const size_t n = lc / 48;
+  if (!n || lc != n * 48 || lp != lc || lz != n * 32 || ly != lz || lt != 96) { napi_throw_range_error(env, NULL, "n commitments and proofs of 48 bytes, n points and values of 32 bytes, 96 bytes of [tau]G2"); return NULL; }
+  thr_job job; memset(&job, 0, sizeof job);
+  job.kind = 4; job.a = cs; job.b = z; job.shares = y; job.proofs = ps; job.tau = tau; job.seed = seed; job.per_item = per != 0; job.n = n;
+  napi_value vo = new_u8(env, 4, &job.out), vs = new_u8(env, n, (uint8_t**)&job.st); ALLOCATED(vo); ALLOCATED(vs);
+  memset(job.out, 0, 4); memset(job.st, 0, n);
+  return thr_run(env, &job, async, argv, seed ? 6 : 5, vo, vs);
+}
+static napi_value KzgVerifyProofs(napi_env env, napi_callback_info info) { return kzg_proofs_call(env, info, 0); }
+static napi_value KzgVerifyProofsAsync(napi_env env, napi_callback_info info) { return kzg_proofs_call(env, info, 1); }
+static napi_value kzg_blobs_call(napi_env env, napi_callback_info info, int async) {
+  ARGS(7); NEED_CTX(); BYTES(1, blobs, lb); BYTES(2, cs, lc); BYTES(3, ps, lp); BYTES(4, tau, lt);
+  int32_t log2n, per;
+  if (napi_get_value_int32(env, argv[0], &log2n) != napi_ok || napi_get_value_int32(env, argv[6], &per) != napi_ok) { napi_throw_type_error(env, NULL, "expected numbers for log2n and perItem"); return NULL; }
+  const uint8_t* seed; if (!kzg_seed(env, argv[5], &seed)) return NULL;
+  const size_t n = lc / 48;
+  if (log2n < 1 || log2n > 12 || !n || lc != n * 48 || lp != lc || lb != (n * 32) << log2n || lt != 96) {
+    napi_throw_range_error(env, NULL, "log2n in 1 .. 12, n blobs of 32 << log2n bytes, n commitments and proofs of 48 bytes, 96 bytes of [tau]G2"); return NULL; }
+  thr_job job; memset(&job, 0, sizeof job);
+  job.kind = 5; job.op = log2n; job.b = blobs; job.a = cs; job.proofs = ps; job.tau = tau; job.seed = seed; job.per_item = per != 0; job.n = n;
+  napi_value vo = new_u8(env, 4, &job.out), vs = new_u8(env, n, (uint8_t**)&job.st); ALLOCATED(vo); ALLOCATED(vs);
+  memset(job.out, 0, 4); memset(job.st, 0, n);
+  return thr_run(env, &job, async, argv + 1, seed ? 5 : 4, vo, vs);
+}
+static napi_value KzgVerifyBlobs(napi_env env, napi_callback_info info) { return kzg_blobs_call(env, info, 0); }
+static napi_value KzgVerifyBlobsAsync(napi_env env, napi_callback_info info) { return kzg_blobs_call(env, info, 1); }
+
 static napi_value ModuleInit(napi_env env, napi_value exports) {
   const char* path = getenv("NBLS_LIB");
   char buf[4096];
@@ -532,7 +586,7 @@ static napi_value ModuleInit(napi_env env, napi_value exports) {
   LOAD(nbls_hash_to_g2_batch) LOAD(nbls_g1_sum) LOAD(nbls_g2_sum) LOAD(nbls_verify_batch) LOAD(nbls_g1_mul_batch) LOAD(nbls_g2_mul_batch) LOAD(nbls_sign_batch) LOAD(nbls_hash_to_g1_batch) LOAD(nbls_encode_to_g1_batch) LOAD(nbls_encode_to_g2_batch) LOAD(nbls_g1_msm) LOAD(nbls_g2_msm)
   LOAD(nbls_init_multi) LOAD(nbls_destroy_multi) LOAD(nbls_multi_device_count) LOAD(nbls_multi_context) LOAD(nbls_multi_pairing_batch) LOAD(nbls_multi_miller_product) LOAD(nbls_multi_verify_batch) LOAD(nbls_g2_prepare) LOAD(nbls_pairing_prepared) LOAD(nbls_verify_multiple) LOAD(nbls_verify_aggregates) LOAD(nbls_verify_multiple_shared) LOAD(nbls_verify_aggregates_shared)
   LOAD(nbls_g1_from_hex_batch) LOAD(nbls_g2_from_hex_batch) LOAD(nbls_g2_from_signature_batch) LOAD(nbls_g1_clear_cofactor_batch) LOAD(nbls_g2_clear_cofactor_batch)
-  LOAD(nbls_fr_op_batch) LOAD(nbls_lagrange_at_zero) LOAD(nbls_g2_combine_shares) LOAD(nbls_g1_combine_shares) LOAD(nbls_g1_poly_eval) LOAD(nbls_g2_poly_eval)
+  LOAD(nbls_fr_op_batch) LOAD(nbls_lagrange_at_zero) LOAD(nbls_g2_combine_shares) LOAD(nbls_g1_combine_shares) LOAD(nbls_g1_poly_eval) LOAD(nbls_g2_poly_eval) LOAD(nbls_kzg_verify_proofs) LOAD(nbls_kzg_verify_blobs)
   {   /* the ABI the addon was written against (include/nbls.h NBLS_ABI_VERSION): an older or newer library is refused at load instead of misread at run time */
     int (*abi)(void) = (int (*)(void))dlsym(lib, "nbls_abi_version");
     if (!abi || abi() != NBLS_ABI_VERSION) { napi_throw_error(env, NULL, "libnbls.so: ABI version differs from the one this addon was built for (include/nbls.h NBLS_ABI_VERSION)"); return exports; }
@@ -550,7 +604,9 @@ static napi_value ModuleInit(napi_env env, napi_value exports) {
     {"frOp", 0, FrOp, 0, 0, 0, napi_enumerable, 0}, {"frOpAsync", 0, FrOpAsync, 0, 0, 0, napi_enumerable, 0}, {"lagrangeAtZero", 0, LagrangeAtZero, 0, 0, 0, napi_enumerable, 0},
     {"lagrangeAtZeroAsync", 0, LagrangeAtZeroAsync, 0, 0, 0, napi_enumerable, 0}, {"combineShares", 0, CombineShares, 0, 0, 0, napi_enumerable, 0},
     {"combineSharesAsync", 0, CombineSharesAsync, 0, 0, 0, napi_enumerable, 0}, {"polyEval", 0, PolyEval, 0, 0, 0, napi_enumerable, 0},
-    {"polyEvalAsync", 0, PolyEvalAsync, 0, 0, 0, napi_enumerable, 0}};
+    {"polyEvalAsync", 0, PolyEvalAsync, 0, 0, 0, napi_enumerable, 0}, {"kzgVerifyProofs", 0, KzgVerifyProofs, 0, 0, 0, napi_enumerable, 0},
+    {"kzgVerifyProofsAsync", 0, KzgVerifyProofsAsync, 0, 0, 0, napi_enumerable, 0}, {"kzgVerifyBlobs", 0, KzgVerifyBlobs, 0, 0, 0, napi_enumerable, 0},
+    {"kzgVerifyBlobsAsync", 0, KzgVerifyBlobsAsync, 0, 0, 0, napi_enumerable, 0}};
   napi_define_properties(env, exports, sizeof d / sizeof d[0], d);
   return exports;
 }
