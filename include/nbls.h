@@ -341,8 +341,8 @@ int nbls_g1_poly_eval(nbls_ctx* ctx, size_t n_groups, const uint32_t* coef_offse
 int nbls_g2_poly_eval(nbls_ctx* ctx, size_t n_groups, const uint32_t* coef_offsets /* n_groups + 1 */, const uint8_t* coefs96, const uint32_t* id_offsets /* n_groups + 1 */,
                       const uint8_t* ids32, uint8_t* out96 /* one per identifier */, int8_t* status /* one per identifier, may be NULL */);
 
-/* KZG on BLS12-381 (EIP-4844; no reference counterpart): the verifier's side of blob commitments.  The prover's side, blob_to_kzg_commitment, is nbls_g1_msm_rows over the
- * Lagrange basis of the setup.  Field elements are 32 bytes big-endian and must be CANONICAL (bytes_to_bls_field: a value >= r is refused, status NBLS_ST_NON_CANONICAL) --
+/* KZG on BLS12-381 (EIP-4844; no reference counterpart): the verifier's side of blob commitments here, the prover's side (commitments, proofs, the
+ * quotient) below under "KZG, the prover's side".  Field elements are 32 bytes big-endian and must be CANONICAL (bytes_to_bls_field: a value >= r is refused, status NBLS_ST_NON_CANONICAL) --
  * unlike nbls_fr_op_batch, which reduces.  The formulas are EIP-4844's as the project's issue states them; the specification's own test vectors have not been run.
  *
  * nbls_fr_eval_roots: evaluate_polynomial_in_evaluation_form for n polynomials, each at its own point.  With N = 2^log2_n, polynomial i is given by its N values
@@ -378,6 +378,49 @@ int nbls_kzg_verify_proofs(nbls_ctx* ctx, size_t n, const uint8_t* commitments48
 int nbls_kzg_verify_blobs(nbls_ctx* ctx, unsigned log2_n, size_t n, const uint8_t* blobs /* n * (32 << log2_n) */, const uint8_t* commitments48, const uint8_t* proofs48,
                           const uint8_t* tau_g2_96, const uint8_t* seed32, int* all_ok, int8_t* status);
 
+/* KZG, the prover's side (EIP-4844: blob_to_kzg_commitment, compute_kzg_proof, compute_blob_kzg_proof).  Blobs are public and the MSM is not constant time: NOT an interface
+ * for secrets.
+ *
+ * nbls_kzg_setup: the setup's g1_lagrange in device memory, decoded ONCE.  lagrange48 holds 2^log2_n compressed G1 points in BIT-REVERSED ORDER: entry j is [L_j(tau)]G1 for the
+ * root w_j = omega^rev(j) -- the order of nbls_fr_eval_roots and of the blob elements.  Entries are decoded by PointG1.fromHex's rules, subgroup check included; status[j] (may be
+ * NULL) is the decoder's status.  An entry with a status >= 2, or a zero point (status 1: no real setup contains one), makes the call return NBLS_EDECODE with *out = NULL; the
+ * statuses are written in both cases.  The points are kept as the batched MSM reads them after its conversion (each point and its endomorphism image, raw projective: about
+ * 1.5 MB at 4096 points), so decoding, subgroup check and split are never repeated per call.  The object belongs to no context: any context on the same device may use it, also
+ * after the creating context is destroyed; nbls_kzg_setup_destroy must not run while a call uses it.  NBLS_EINVAL for log2_n outside 1 .. 12 or a missing pointer.  Parsing
+ * the ceremony's file formats stays with the caller. */
+typedef struct nbls_kzg_setup nbls_kzg_setup;
+int  nbls_kzg_setup_create(nbls_ctx* ctx, unsigned log2_n, const uint8_t* lagrange48 /* 2^log2_n compressed G1 points */, int8_t* status /* 2^log2_n, may be NULL */,
+                           nbls_kzg_setup** out);
+void nbls_kzg_setup_destroy(nbls_kzg_setup* s);
+int  nbls_kzg_setup_log2n(const nbls_kzg_setup* s, unsigned* log2_n);
+/* The quotient of an opening in evaluation form, for n polynomials each at its own point (layout, order of the roots and limits as nbls_fr_eval_roots):
+ *   out_y32[i] = y = p_i(z_i), exactly what nbls_fr_eval_roots returns;   out_q32[i N + j] = q_j = (f_j - y) / (w_j - z)  for every j with w_j != z;
+ *   where z = w_m: q_m = sum_{j != m} (f_j - y) w_j / (z (z - w_j))   (compute_quotient_eval_within_domain; computed as -1 / z * sum_{j != m} q_j w_j).
+ * Elements must be canonical: an element of the polynomial >= r, or z_i >= r, gives status[i] = NBLS_ST_NON_CANONICAL, y and the whole quotient row are then all-zero and the
+ * neighbouring polynomials are not disturbed.  One copy in, one kernel (a workgroup per polynomial: the batch inversion of the evaluation keeps its inverses), one copy out.
+ * NBLS_EINVAL before any device work for log2_n outside 1 .. 12, a NULL context, missing buffers with n > 0, more than 2^24 elements in the call; n = 0 is NBLS_OK. */
+int nbls_fr_quotient_roots(nbls_ctx* ctx, unsigned log2_n /* 1 .. 12 */, size_t n, const uint8_t* evals32 /* n << log2_n */, const uint8_t* z32 /* n */, uint8_t* out_y32 /* n */,
+                           uint8_t* out_q32 /* n << log2_n */, int8_t* status /* n, may be NULL */);
+/* The three prover calls.  Blob i = the 2^log2_n values of polynomial i as in nbls_kzg_verify_blobs; the size comes from the setup.
+ *   nbls_kzg_commit_blobs        blob_to_kzg_commitment:  C_i = sum_j [f_ij] L_j, 48 bytes compressed
+ *   nbls_kzg_compute_proofs      compute_kzg_proof:       y_i = p_i(z_i), pi_i = sum_j [q_ij] L_j with the quotient of nbls_fr_quotient_roots
+ *   nbls_kzg_compute_blob_proofs compute_blob_kzg_proof:  z_i = the FSBLOBVERIFY_V1_ challenge of (blob_i, commitment_i), hashed on up to eight host threads behind the copy of the
+ *                                blobs, then as compute_proofs (y_i is not returned).  GIVEN COMMITMENTS ARE ONLY HASHED, NOT DECODED: bytes that are no commitment of the blob
+ *                                yield a proof that will not verify.  With commitments48 == NULL the call commits first, on the blobs already on the device, and reads the 48 n
+ *                                bytes back (the one synchronisation the challenge needs); they are returned in out_commitments48, which is then required (else it may be NULL).
+ * Each call is one chain on the context's stream: one copy in, the canonical check of the blob elements (inside the quotient kernel; a small kernel of its own for commitments),
+ * the quotient rows written as 32-byte big-endian scalars straight into the MSM's scalar array, the batched MSM in its rows form (as nbls_g1_msm_rows, split along the
+ * endomorphism, window width by its cost model, slabs by NBLS_TUNE_MSMB_SLAB) against the setup's converted points, to-affine, compression, one copy out.
+ * status[i] (may be NULL): 0, or NBLS_ST_NON_CANONICAL for a blob element or z_i >= r; that item's outputs are then ALL-ZERO bytes (48 zero bytes are deliberately no valid
+ * encoding; a zero y).  ZERO POINTS ARE VALID as in the verifier: the zero polynomial commits to 0xc0 00.., a constant polynomial's proof is 0xc0 00.., both with status 0.
+ * Returns NBLS_OK whatever the blobs hold; NBLS_EINVAL before any device work for a missing pointer, n = 0, a setup created on another device, or n << log2_n above 2^22 (the
+ * batched MSM's bound on scalars per call: 1024 mainnet blobs fit exactly) or n above 2^20 (its bound on rows: reached only at log2_n = 1). */
+int nbls_kzg_commit_blobs(nbls_ctx* ctx, const nbls_kzg_setup* setup, size_t n, const uint8_t* blobs, uint8_t* out_commitments48, int8_t* status /* n, may be NULL */);
+int nbls_kzg_compute_proofs(nbls_ctx* ctx, const nbls_kzg_setup* setup, size_t n, const uint8_t* blobs, const uint8_t* z32, uint8_t* out_proofs48, uint8_t* out_y32,
+                            int8_t* status /* n, may be NULL */);
+int nbls_kzg_compute_blob_proofs(nbls_ctx* ctx, const nbls_kzg_setup* setup, size_t n, const uint8_t* blobs, const uint8_t* commitments48 /* or NULL */,
+                                 uint8_t* out_commitments48 /* required when commitments48 == NULL */, uint8_t* out_proofs48, int8_t* status /* n, may be NULL */);
+
 /* One rank's share of a verifyBatch spread over several GPUs (one process per GPU): the Miller product of this rank's n
  * (key, message) pairs, times millerLoop(-G, S) on the ONE rank that passes the signature (d_sig96 = NULL elsewhere), WITHOUT the
  * final exponentiation, as 576 wire bytes in device memory.  Ranks all-gather their partials and finish with
@@ -407,7 +450,7 @@ const char* nbls_config_describe(void);   /* "NBLS_X=value(env|default) ...": ev
    nbls_verify_aggregates_indexed_shared, scratch slots 48 .. 50 (additions only, same version); then nbls_fr_op_batch, nbls_lagrange_at_zero, nbls_g2_combine_shares,
    nbls_g1_combine_shares, NBLS_FROP_*, NBLS_ST_BAD_IDS, scratch slots 51 .. 56 (additions only, same version); then nbls_field_kernel_raw (addition only, same version); then nbls_g1_poly_eval,
    nbls_g2_poly_eval, nbls_extra_program_kernel, NBLS_TUNE_POLY_SLAB, scratch slots 57 .. 61 (additions only, same version); then nbls_g1_msm_batch, nbls_g2_msm_batch,
-   nbls_g1_msm_rows, nbls_g2_msm_rows, NBLS_TUNE_MSMB_WINDOW / _BIG / _SLAB, the names "dbladd_g1" / "dbladd_g2" of nbls_extra_program_kernel, scratch slots 62 .. 63 (additions only, same version); then nbls_map_uniform_batch (addition only, same version); then nbls_fr_eval_roots, nbls_kzg_verify_proofs, nbls_kzg_verify_blobs, NBLS_ST_NON_CANONICAL, scratch slots 64 .. 68 (additions only, same version); with the MSM calls ONE CHANGE TO EXISTING CALLS, same version: nbls_g1_msm / nbls_g2_msm write all-zero output bytes when the status is 1 (the sum is the
+   nbls_g1_msm_rows, nbls_g2_msm_rows, NBLS_TUNE_MSMB_WINDOW / _BIG / _SLAB, the names "dbladd_g1" / "dbladd_g2" of nbls_extra_program_kernel, scratch slots 62 .. 63 (additions only, same version); then nbls_map_uniform_batch (addition only, same version); then nbls_fr_eval_roots, nbls_kzg_verify_proofs, nbls_kzg_verify_blobs, NBLS_ST_NON_CANONICAL, scratch slots 64 .. 68 (additions only, same version); then nbls_kzg_setup_create / _destroy / _log2n, nbls_fr_quotient_roots, nbls_kzg_commit_blobs, nbls_kzg_compute_proofs, nbls_kzg_compute_blob_proofs, scratch slots 69 .. 70 (additions only, same version); with the MSM calls ONE CHANGE TO EXISTING CALLS, same version: nbls_g1_msm / nbls_g2_msm write all-zero output bytes when the status is 1 (the sum is the
    zero point).  The bytes were unspecified there before (what the affine conversion made of a Z that is 0 mod p: in G1 a zero x and an arbitrary y); the status, and every output with status 0, are unchanged.
    nbls_msm_dev, which leaves its result on the device, is not changed.
    4 (round 6): nbls_hw_queues, NBLS_TUNE_WIDE_MAX, NBLS_TUNE_H2C_NORM_MIN, NBLS_TUNE_INV_WIDE_MAX, NBLS_TUNE_LS_MAX / _LS2_MAX (additions only); the library sets GPU_MAX_HW_QUEUES = 22 at load when the variable is unset (see nbls_pool_init below).

@@ -242,7 +242,10 @@ NBLS_FR_HD Fr fr_inv_pow2(unsigned log2_n) {   // 1 / 2^log2_n = r - (r - 1) / 2
 struct FrEvalPart { Fr sum; uint32_t hit, bad; };   // the lane's plain partial sum | the index j with z = w_j, else 0xffffffff | all ones when an element the lane read is >= r
 // pre: the products in front of each of the lane's denominators, terms x 8 x lanes words laid out [term][limb][lane] (LDS on the device: consecutive lanes on consecutive banks);
 // held in registers, sixteen terms of unrolled code let the compiler hoist every load of the walk and spill (measured on gfx950: 256 VGPRs and 1252 bytes of private memory)
-NBLS_FR_HD FrEvalPart fr_eval_lane(const uint8_t* f32, const Fr* roots, const Fr& z, uint32_t N, uint32_t lane, uint32_t lanes, uint32_t* pre) {
+// KEEP (the quotient, below): the backward walk leaves 1 / (z - w_j), Montgomery form, in the slot the product in front of term j came from -- the same lane's own slot, read
+// just before it is written.  The slot of a masked term (z = w_j, or j >= N) then holds a value nobody may use
+template <bool KEEP>
+NBLS_FR_HD FrEvalPart fr_eval_lane_t(const uint8_t* f32, const Fr* roots, const Fr& z, uint32_t N, uint32_t lane, uint32_t lanes, uint32_t* pre) {
   const uint32_t terms = (N + lanes - 1) / lanes;   // the workgroup's bound, the same for every lane
   const Fr one = fr_one();
   Fr acc = one;
@@ -266,22 +269,69 @@ NBLS_FR_HD FrEvalPart fr_eval_lane(const uint8_t* f32, const Fr* roots, const Fr
     Fr p;
 #pragma unroll
     for (int i = 0; i < FR_NL; i++) p.l[i] = pre[(k * FR_NL + i) * lanes + lane];
-    const Fr t = fr_mul(fr_mul(f, w), fr_mul(inv, p));   // f_j w_j / (z - w_j), plain
+    Fr t;                                                // f_j w_j / (z - w_j), plain
+    if (KEEP) {
+      const Fr id = fr_mul(inv, p);                      // 1 / (z - w_j), Montgomery form
+#pragma unroll
+      for (int i = 0; i < FR_NL; i++) pre[(k * FR_NL + i) * lanes + lane] = id.l[i];
+      t = fr_mul(fr_mul(f, w), id);
+    } else t = fr_mul(fr_mul(f, w), fr_mul(inv, p));
     inv = fr_mul(inv, d);
     o.sum = fr_add(o.sum, fr_select(live, t, fr_zero()));
   }
   return o;
 }
-// sum: the workgroup's plain sum; hit / bad: the lanes' combined (bad also where z itself was >= r) -> 32 bytes big-endian; returns the status (21 = NBLS_ST_NON_CANONICAL, else 0)
-NBLS_FR_HD int fr_eval_finish(const Fr& sum, uint32_t hit, uint32_t bad, const Fr& z, unsigned log2_n, const uint8_t* f32, uint8_t* out32) {
+NBLS_FR_HD FrEvalPart fr_eval_lane(const uint8_t* f32, const Fr* roots, const Fr& z, uint32_t N, uint32_t lane, uint32_t lanes, uint32_t* pre) {
+  return fr_eval_lane_t<false>(f32, roots, z, N, lane, lanes, pre);
+}
+// the value alone: the factor (z^N - 1) / N on the workgroup's plain sum, or the element f_hit itself
+NBLS_FR_HD Fr fr_eval_value(const Fr& sum, uint32_t hit, const Fr& z, unsigned log2_n, const uint8_t* f32) {
   Fr zn = z;
   for (unsigned i = 0; i < log2_n; i++) zn = fr_sqr(zn);
   const Fr fac = fr_mul(fr_sub(zn, fr_one()), fr_inv_pow2(log2_n));
   const uint32_t hm = (uint32_t)0 - (uint32_t)(hit != 0xffffffffu);
-  Fr v = fr_select(hm, fr_load_be(f32 + 32ull * (hit & hm)), fr_mul(sum, fac));
-  fr_store_be(fr_select(bad, fr_zero(), v), out32);
+  return fr_select(hm, fr_load_be(f32 + 32ull * (hit & hm)), fr_mul(sum, fac));
+}
+// sum: the workgroup's plain sum; hit / bad: the lanes' combined (bad also where z itself was >= r) -> 32 bytes big-endian; returns the status (21 = NBLS_ST_NON_CANONICAL, else 0)
+NBLS_FR_HD int fr_eval_finish(const Fr& sum, uint32_t hit, uint32_t bad, const Fr& z, unsigned log2_n, const uint8_t* f32, uint8_t* out32) {
+  fr_store_be(fr_select(bad, fr_zero(), fr_eval_value(sum, hit, z, log2_n, f32)), out32);
   return (int)(bad & 21);
 }
 enum { FR_EVAL_LANES = 256 };   // lanes per polynomial: 16 terms each at N = 4096
+
+// ---- The quotient of an opening in evaluation form (compute_kzg_proof_impl of EIP-4844; kzg_quotient_kernel and nbls_sim_fr_quotient_roots): with y = p(z),
+//   q_j = (f_j - y) / (w_j - z)  where w_j != z,     q_m = sum_{j != m} (f_j - y) w_j / (z (z - w_j)) = -1 / z * sum_{j != m} q_j w_j  where z = w_m
+// (compute_quotient_eval_within_domain; z = w_m is a root of unity, so it is not zero).  The lanes are fr_eval_lane's, run with KEEP: after that walk the slots of `pre` hold
+// 1 / (z - w_j) in Montgomery form.  y and the elements are plain, so q_j = (y - f_j) * 1 / (z - w_j) is plain: it goes out as 32 bytes big-endian, the form the MSM reads.
+// fr_quot_lane: the lane's terms -> out_q32 (N x 32 bytes; all-zero where `bad`; zero at the term `hit`, which fr_quot_within fills); returns the lane's plain share of
+// sum_{j != hit} q_j w_j (zero when there is no hit: the products are then not formed -- hit is the workgroup's, the branch is uniform)
+NBLS_FR_HD void fr_store_q(const Fr& v, uint8_t* out32) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  uint4* o = (uint4*)out32;   // (16-byte aligned: a row of a staged or carved block)
+  o[0] = make_uint4(fr_bswap32(v.l[7]), fr_bswap32(v.l[6]), fr_bswap32(v.l[5]), fr_bswap32(v.l[4]));
+  o[1] = make_uint4(fr_bswap32(v.l[3]), fr_bswap32(v.l[2]), fr_bswap32(v.l[1]), fr_bswap32(v.l[0]));
+#else
+  fr_store_be(v, out32);
+#endif
+}
+NBLS_FR_HD Fr fr_quot_lane(const uint8_t* f32, const Fr* roots, const Fr& y, uint32_t hit, uint32_t bad, uint32_t N, uint32_t lane, uint32_t lanes, const uint32_t* pre, uint8_t* out_q32) {
+  const uint32_t terms = (N + lanes - 1) / lanes;
+  const Fr zero = fr_zero();
+  Fr acc = zero;
+  for (uint32_t k = 0; k < terms; k++) {
+    const uint32_t j = lane + k * lanes;
+    if (j >= N) break;   // (the lane's last term: nothing of the workgroup is left behind it)
+    Fr id;
+#pragma unroll
+    for (int i = 0; i < FR_NL; i++) id.l[i] = pre[(k * FR_NL + i) * lanes + lane];
+    const uint32_t out = bad | ((uint32_t)0 - (uint32_t)(j == hit));
+    const Fr q = fr_select(out, zero, fr_mul(fr_sub(y, fr_load_be(f32 + 32ull * j)), id));
+    fr_store_q(q, out_q32 + 32ull * j);
+    if (hit != 0xffffffffu) acc = fr_add(acc, fr_mul(q, roots[j]));
+  }
+  return acc;
+}
+// q_m from the workgroup's sum (plain) and z = w_m (Montgomery form): one inversion, on the lane that owns m
+NBLS_FR_HD Fr fr_quot_within(const Fr& sum, const Fr& z) { return fr_neg(fr_mul(sum, fr_inv(z))); }
 
 }  // namespace nbls

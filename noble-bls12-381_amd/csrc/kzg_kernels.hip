@@ -1,4 +1,5 @@
-// kzg_kernels.hip -- the scalar-field side of KZG verification (pipelines_kzg.cpp): polynomials in evaluation form evaluated at a point (nbls_fr_eval_roots, and y_i = p_i(z_i) of
+// kzg_kernels.hip -- the scalar-field side of KZG verification (pipelines_kzg.cpp) and proving (pipelines_kzg_prove.cpp: the quotient of an opening, the canonical check of
+// blobs that are only committed to, the closing kernel of the compressed results): polynomials in evaluation form evaluated at a point (nbls_fr_eval_roots, and y_i = p_i(z_i) of
 // nbls_kzg_verify_blobs), the table of roots of unity, and the small Fr kernels around the two MSMs of the combined check and the ladders of the per-item pass.  The arithmetic is
 // fr_exec.h's, written once and shared with the simulator (nbls_sim_fr_eval_roots); the curve arithmetic runs as step programs (decoder, MSM, ladders, Miller loops).
 #include <hip/hip_runtime.h>
@@ -46,6 +47,80 @@ __global__ void __launch_bounds__(EV) kzg_eval_kernel(u32 log2_n, const uint8_t*
     __syncthreads();
   }
   if (t == 0) status[p] = (int8_t)fr_eval_finish(part[0], sh_hit, sh_bad, z, log2_n, f32, out32 + 32 * p);
+}
+
+// The quotient of an opening (nbls_fr_quotient_roots, the proofs of pipelines_kzg_prove.cpp): kzg_eval_kernel's walk with the inverses 1 / (z - w_j) kept in the slots the
+// running products came from (no more LDS than the evaluation takes), the same tree for y, then a second walk over the lane's terms: q_j = (y - f_j) / (z - w_j) as 32 bytes
+// big-endian -- the batched MSM's scalar array -- and, where z is the root w_m (sh_hit: uniform over the workgroup), the products q_j w_j into a second tree over `part`; the
+// lane that owns m closes with one inversion, q_m = -1 / z * sum.  A non-canonical input leaves a zero y and a zero row.
+__global__ void __launch_bounds__(EV) kzg_quotient_kernel(u32 log2_n, const uint8_t* __restrict__ evals, const uint8_t* __restrict__ z32, const Fr* __restrict__ roots,
+                                                          uint8_t* __restrict__ out_y32, uint8_t* __restrict__ out_q32, int8_t* __restrict__ status) {
+  extern __shared__ u32 pre[];
+  __shared__ Fr part[EV];
+  __shared__ Fr sh_y;
+  __shared__ u32 sh_hit, sh_bad;
+  const u32 N = 1u << log2_n, t = threadIdx.x;
+  const u64 p = blockIdx.x;
+  const uint8_t* f32 = evals + ((p * 32) << log2_n);
+  uint8_t* q32 = out_q32 + ((p * 32) << log2_n);
+  const Fr zraw = fr_load_be(z32 + 32 * p), z = fr_mul(zraw, fr_r2());
+  if (t == 0) { sh_hit = 0xffffffffu; sh_bad = fr_ge_r_mask(zraw); }
+  __syncthreads();
+  const FrEvalPart me = fr_eval_lane_t<true>(f32, roots, z, N, t, EV, pre);
+  part[t] = me.sum;
+  if (me.hit != 0xffffffffu) sh_hit = me.hit;
+  if (me.bad) atomicOr(&sh_bad, 0xffffffffu);
+  __syncthreads();
+  for (u32 s = EV / 2; s > 0; s >>= 1) {
+    if (t < s) part[t] = fr_add(part[t], part[t + s]);
+    __syncthreads();
+  }
+  const u32 hit = sh_hit, bad = sh_bad;
+  if (t == 0) {
+    sh_y = fr_select(bad, fr_zero(), fr_eval_value(part[0], hit, z, log2_n, f32));
+    fr_store_be(sh_y, out_y32 + 32 * p);
+    status[p] = (int8_t)(bad & NBLS_ST_NON_CANONICAL);
+  }
+  __syncthreads();
+  const Fr y = sh_y;
+  const Fr share = fr_quot_lane(f32, roots, y, hit, bad, N, t, EV, pre, q32);
+  if (hit == 0xffffffffu) return;   // (uniform)
+  part[t] = share;
+  __syncthreads();
+  for (u32 s = EV / 2; s > 0; s >>= 1) {
+    if (t < s) part[t] = fr_add(part[t], part[t + s]);
+    __syncthreads();
+  }
+  if (t == hit % EV) fr_store_q(fr_select(bad, fr_zero(), fr_quot_within(part[0], z)), q32 + 32ull * hit);
+}
+
+// blobs that are only committed to (no quotient kernel reads them): status[i] = NBLS_ST_NON_CANONICAL where an element of blob i is >= r, and that blob's row is zeroed in
+// place, so that the MSM reads canonical scalars only.  One workgroup per blob
+__global__ void __launch_bounds__(256) kzg_canon_kernel(u32 log2_n, uint8_t* __restrict__ evals, int8_t* __restrict__ status) {
+  __shared__ u32 sh_bad;
+  const u32 N = 1u << log2_n, t = threadIdx.x;
+  uint8_t* f32 = evals + (((u64)blockIdx.x * 32) << log2_n);
+  if (t == 0) sh_bad = 0;
+  __syncthreads();
+  u32 bad = 0;
+  for (u32 j = t; j < N; j += 256) bad |= fr_ge_r_mask(fr_load_be(f32 + 32ull * j));
+  if (bad) atomicOr(&sh_bad, 0xffffffffu);
+  __syncthreads();
+  if (t == 0) status[blockIdx.x] = (int8_t)(sh_bad & NBLS_ST_NON_CANONICAL);
+  if (sh_bad) for (u32 j = t; j < 2 * N; j += 256) ((uint4*)f32)[j] = make_uint4(0u, 0u, 0u, 0u);
+}
+// the n compressed sums of a prover call, in place: status[i] = the first non-zero of st_a[i], st_b[i] (either array may be NULL); all-zero bytes where it is set, 0xc0 00..
+// where the sum is the zero point (zero[i] == 1)
+__global__ void kzg_prove_tail_kernel(u32 n, const int8_t* __restrict__ zero, const int8_t* __restrict__ st_a, const int8_t* __restrict__ st_b, uint8_t* __restrict__ out48,
+                                      int8_t* __restrict__ status) {
+  const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int8_t a = st_a ? st_a[i] : 0, b = st_b ? st_b[i] : 0, v = a ? a : b;
+  status[i] = v;
+  if (v || zero[i] == 1) {
+    uint4* o = (uint4*)(out48 + 48ull * i);
+    for (u32 w = 0; w < 3; w++) o[w] = make_uint4(w == 0 && !v ? 0xc0u : 0u, 0u, 0u, 0u);
+  }
 }
 
 __device__ inline void copy96(uint8_t* dst, const uint8_t* src) {
@@ -119,6 +194,22 @@ __global__ void kzg_item_status_kernel(u32 n, const int8_t* __restrict__ pre, co
 }
 
 inline unsigned blocks_for(u64 threads, unsigned per = 256) { return (unsigned)((threads + per - 1) / per); }
+// The running products of N = 4096 take more than the 64 KB a launch may ask for by default.  The limit is a per-device function attribute: set once on every device a launch of
+// `kernel` is made on (as nbls_vm_launch does); the common case, already set, takes no lock
+int lds_limit(const void* kernel, std::atomic<bool>* attr_set) {
+  static std::mutex attr_mu;
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
+  if (!attr_set[dev].load(std::memory_order_acquire)) {
+    std::lock_guard<std::mutex> g(attr_mu);
+    if (!attr_set[dev].load(std::memory_order_relaxed)) {
+      const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 16 * FR_NL * EV * 4);
+      if (e != hipSuccess) return (int)e;
+      attr_set[dev].store(true, std::memory_order_release);
+    }
+  }
+  return 0;
+}
 }  // namespace
 
 extern "C" {
@@ -131,21 +222,36 @@ int nbls_kzg_eval_launch(unsigned log2_n, unsigned n, const void* evals32, const
   if (!n) return 0;
   if (log2_n < 1 || log2_n > 12) return (int)hipErrorInvalidValue;
   const unsigned terms = ((1u << log2_n) + EV - 1) / EV, lds = terms * FR_NL * EV * 4;
-  // more than the 64 KB a launch may ask for by default.  The limit is a per-device function attribute: set once on every device a launch is made on (as nbls_vm_launch does);
-  // the common case, already set, takes no lock
   static std::atomic<bool> attr_set[64];
-  static std::mutex attr_mu;
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-  if (!attr_set[dev].load(std::memory_order_acquire)) {
-    std::lock_guard<std::mutex> g(attr_mu);
-    if (!attr_set[dev].load(std::memory_order_relaxed)) {
-      const hipError_t e = hipFuncSetAttribute((const void*)kzg_eval_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 16 * FR_NL * EV * 4);
-      if (e != hipSuccess) return (int)e;
-      attr_set[dev].store(true, std::memory_order_release);
-    }
-  }
+  const int e = lds_limit((const void*)kzg_eval_kernel, attr_set);
+  if (e) return e;
   hipLaunchKernelGGL(kzg_eval_kernel, dim3(n), dim3(EV), lds, (hipStream_t)stream, log2_n, (const uint8_t*)evals32, (const uint8_t*)z32, (const Fr*)roots, (uint8_t*)out32, (int8_t*)status);
+  return (int)hipGetLastError();
+}
+// the same n polynomials -> out_y32 (n x 32), the quotient rows out_q32 (n x 2^log2_n x 32 bytes, 16-byte aligned) and status (n bytes, not NULL)
+int nbls_kzg_quotient_launch(unsigned log2_n, unsigned n, const void* evals32, const void* z32, const void* roots, void* out_y32, void* out_q32, void* status, void* stream) {
+  if (!n) return 0;
+  if (log2_n < 1 || log2_n > 12 || ((uintptr_t)out_q32 & 15)) return (int)hipErrorInvalidValue;
+  const unsigned terms = ((1u << log2_n) + EV - 1) / EV, lds = terms * FR_NL * EV * 4;
+  static std::atomic<bool> attr_set[64];
+  const int e = lds_limit((const void*)kzg_quotient_kernel, attr_set);
+  if (e) return e;
+  hipLaunchKernelGGL(kzg_quotient_kernel, dim3(n), dim3(EV), lds, (hipStream_t)stream, log2_n, (const uint8_t*)evals32, (const uint8_t*)z32, (const Fr*)roots, (uint8_t*)out_y32,
+                     (uint8_t*)out_q32, (int8_t*)status);
+  return (int)hipGetLastError();
+}
+// evals32: n blobs of 2^log2_n elements, 16-byte aligned, zeroed in place where non-canonical
+int nbls_kzg_canon_launch(unsigned log2_n, unsigned n, void* evals32, void* status, void* stream) {
+  if (!n) return 0;
+  if (log2_n < 1 || log2_n > 12 || ((uintptr_t)evals32 & 15)) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(kzg_canon_kernel, dim3(n), dim3(256), 0, (hipStream_t)stream, log2_n, (uint8_t*)evals32, (int8_t*)status);
+  return (int)hipGetLastError();
+}
+int nbls_kzg_prove_tail_launch(unsigned n, const void* zero, const void* st_a, const void* st_b, void* out48, void* status, void* stream) {
+  if (!n) return 0;
+  if ((uintptr_t)out48 & 15) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(kzg_prove_tail_kernel, dim3(blocks_for(n)), dim3(256), 0, (hipStream_t)stream, n, (const int8_t*)zero, (const int8_t*)st_a, (const int8_t*)st_b, (uint8_t*)out48,
+                     (int8_t*)status);
   return (int)hipGetLastError();
 }
 int nbls_kzg_items_launch(unsigned n, const void* dst, const void* w32, const void* z32, const void* y32, const void* yst, const void* gen96, void* aff, void* s1, void* s2, void* t,

@@ -1,5 +1,5 @@
 // nbls_internal.h -- what the translation units of the runtime share (runtime.cpp / tuning.cpp / pipelines_pairing.cpp / pipelines_codec.cpp / pipelines_verify.cpp /
-// pipelines_multi_verify.cpp / pipelines_threshold.cpp / pipelines_poly.cpp / pipelines_msm_batch.cpp / pipelines_kzg.cpp; pool and multi-device handles: nbls_multi.cpp): the context, the map of its scratch slots (enum Slot: the one place that says which chain owns
+// pipelines_multi_verify.cpp / pipelines_threshold.cpp / pipelines_poly.cpp / pipelines_msm_batch.cpp / pipelines_kzg.cpp / pipelines_kzg_prove.cpp; pool and multi-device handles: nbls_multi.cpp): the context, the map of its scratch slots (enum Slot: the one place that says which chain owns
 // which slot, checked at compile time), the launch helpers, the staged block of the host-buffer pipelines (staging.h, included at the end) and the device-side pipelines the
 // exported entry points are built from.  Internal functions have hidden visibility (csrc/Makefile: -fvisibility=hidden).
 #pragma once
@@ -68,6 +68,9 @@ extern "C" int nbls_kzg_items_launch(unsigned n, const void* dst, const void* w3
 extern "C" int nbls_kzg_fix_zero_launch(unsigned n, const void* zero, const void* gen96, void* pts, void* stream);
 extern "C" int nbls_kzg_item_scalars_launch(unsigned n, const void* pre, const void* dst, const void* z32, const void* y32, void* zs, void* ny, void* stream);
 extern "C" int nbls_kzg_item_status_launch(unsigned n, const void* pre, const void* dst, const void* xzero, const void* one, void* status, void* stream);
+extern "C" int nbls_kzg_quotient_launch(unsigned log2_n, unsigned n, const void* evals32, const void* z32, const void* roots, void* out_y32, void* out_q32, void* status, void* stream);
+extern "C" int nbls_kzg_canon_launch(unsigned log2_n, unsigned n, void* evals32, void* status, void* stream);
+extern "C" int nbls_kzg_prove_tail_launch(unsigned n, const void* zero, const void* st_a, const void* st_b, void* out48, void* status, void* stream);
 // msmb_kernels.hip
 extern "C" int nbls_msmb_keys_launch(unsigned m, unsigned dims, unsigned nwin, unsigned c, unsigned i0, unsigned g0, unsigned ngroups, unsigned n_pts, const void* off,
                                      const void* scalars, void* keys, void* vals, void* stream);
@@ -128,9 +131,12 @@ enum Slot {
   // kzg_pipeline (pipelines_kzg.cpp): the decoded commitments and proofs (+ the generator), their statuses | weights, the scalars of the MSMs, the products r_i y_i, the
   // values y_i and statuses of the blob evaluation, the challenges | [tau]G2 and -G2, their two line tables, the two combined points, the three parts of B | what is read back | everything of the per-item pass
   SB_KZG_POINTS = 64, SB_KZG_SCALARS = 65, SB_KZG_PAIRS = 66, SB_KZG_OUT = 67, SB_KZG_ITEMS = 68,
+  // kzg_prove_pipeline and nbls_fr_quotient_roots (pipelines_kzg_prove.cpp): the quotient rows (the MSM's scalars), the challenges, the values y_i and the statuses of the two
+  // canonical checks | the affine sums and their zero flags, then what is read back (compressed points, values, statuses)
+  SB_KZGP_SCALARS = 69, SB_KZGP_OUT = 70,
   NSB
 };
-static_assert(NSB == 69, "sb[] indices do not shift");
+static_assert(NSB == 71, "sb[] indices do not shift");
 constexpr SlotMask slot_bit(int i) { return (SlotMask)1 << i; }
 template <typename... S> constexpr SlotMask slots(S... s) { return (slot_bit(s) | ...); }
 // one instance of dev_decompress: three arrays of field elements and the exponentiation table
@@ -158,6 +164,7 @@ constexpr SlotMask M_RLC_SIDE = DEC_SIGS.mask() | MSM_RLC.mask();               
 constexpr SlotMask M_THR_OWN = slots(SB_STAGED, SB_THR_SHARES, SB_THR_SCALARS, SB_THR_OUT) | SEG_THR.mask();   // combine_pipeline: what outlives the stages it calls
 constexpr SlotMask M_POLY_OWN = slots(SB_STAGED, SB_POLY_COEFS, SB_POLY_LABELS, SB_POLY_ACC, SB_POLY_STEP, SB_POLY_OUT);   // poly_pipeline: what outlives the decoder it calls
 constexpr SlotMask M_KZG_OWN = slots(SB_STAGED, SB_KZG_POINTS, SB_KZG_SCALARS, SB_KZG_PAIRS, SB_KZG_OUT, SB_KZG_ITEMS);   // kzg_pipeline: what outlives the decoder, the MSMs and the ladders it calls
+constexpr SlotMask M_KZGP_OWN = slots(SB_STAGED, SB_KZGP_SCALARS, SB_KZGP_OUT);   // kzg_prove_pipeline: what outlives the batched MSM it calls (msm_rows_dev, on M_MSMB_OWN)
 constexpr SlotMask M_MSMB_OWN = slots(SB_MSMB_CALL, SB_MSMB_SLAB);   // msm_batch_pipeline: what outlives the dev_msm calls of its big groups
 // what runs side by side
 static_assert(!(M_VB_MAIN & DEC_KEYS.mask()), "verifyBatch decodes its keys (side2, or the sub-batch's own stream) beside the hash chain");
@@ -173,6 +180,9 @@ static_assert(!(M_MSMB_OWN & (MSM_MAIN.mask() | M_POLY_OWN | M_THR_OWN | M_RLC_M
               "msm_batch_pipeline: its big groups run through dev_msm on the main slots between its slabs, which must regrow nothing the call still holds");
 static_assert(!(M_KZG_OWN & (DEC_MAIN.mask() | MSM_RLC.mask() | M_LADDER)), "kzg_pipeline: the decoder, the MSMs (on the slots of MSM_RLC: MSM_MAIN holds SB_STAGED) and the ladders of the per-item pass regrow their slots while the call holds its own");
 static_assert(!((M_KZG_OWN & ~slot_bit(SB_STAGED)) & (M_MSMB_OWN | M_POLY_OWN | M_THR_OWN | M_RLC_MAIN | M_RLC_SIDE | M_RLC_SIDE2 | M_VB_MAIN | MSM_MAIN.mask())), "kzg_pipeline keeps to slots of its own");
+static_assert(!(M_KZGP_OWN & (M_MSMB_OWN | DEC_MAIN.mask())), "kzg_prove_pipeline: the batched MSM sizes its two slots while the staged blobs and the quotient rows are held; nbls_kzg_setup_create decodes on the main slots");
+static_assert(!((M_KZGP_OWN & ~slot_bit(SB_STAGED)) & (M_KZG_OWN | M_POLY_OWN | M_THR_OWN | M_RLC_MAIN | M_RLC_SIDE | M_RLC_SIDE2 | M_VB_MAIN | M_LADDER | MSM_MAIN.mask() | MSM_RLC.mask())),
+              "kzg_prove_pipeline keeps to slots of its own");
 // ---- END scratch slots -------------------------------------------------------------------------------------------------------------------------------------
 #define EXPORT extern "C" __attribute__((visibility("default")))
 extern std::recursive_mutex g_null_mu;   // locked in place of a context's mutex when the caller passed no context (the call then fails with NBLS_EINVAL)
@@ -433,6 +443,26 @@ struct SegSums { const uint32_t* first; const int8_t* st; uint8_t* zero; };   //
 int segment_sums(nbls_ctx* ctx, bool g2, const SegSlots& sl, size_t count, size_t nseg, const uint32_t* d_off, const uint32_t* d_index, const uint8_t* src, const int8_t* st_src,
                  size_t maxseg, uint8_t* out, SegSums* o, hipStream_t s);
 unsigned scalars_bit_length(size_t n, const uint8_t* k32);
+// pipelines_msm_batch.cpp: the plan of one call (window width, slabs of whole groups, the carving of a slab's block) and the device core of nbls_g1_msm_rows that the KZG prover
+// feeds from device memory.  msm_rows_dev_plan sizes and takes SB_MSMB_CALL / SB_MSMB_SLAB: it comes with the caller's other need() calls, before anything is in flight.
+// msm_rows_dev: n_rows sums of n_pts points each; conv_pts = the output of P_G1_MSM_PREP (2 x 3 raw elements per point), d_scalars = n_rows * n_pts scalars of 32 bytes in
+// device memory, read as 256-bit values (the split path: they are never on the host for scalars_bit_length) -> affine sums (96 bytes each) and zero flags.  No group takes the
+// dev_msm route, whatever NBLS_TUNE_MSMB_BIG says: there are no affine points to give it
+struct MsmbPart { size_t g0, g1; bool big; int key_bits; };   // groups [g0, g1): one slab (and the bits of its keys), or one big group
+struct MsmbPlan {
+  bool g2 = false, split = false; unsigned nbits = 0, dims = 1, kbits = 0, c = 0;
+  size_t n_groups = 0, n_pts = 0, nwin = 0, J = 0, jtop = 0, maxM = 0, max_ngs = 0, sort_bytes = 0, scan_bytes = 0;
+  size_t s_cnt = 0, s_tmp = 0, s_P = 0, s_bk = 0, s_G = 0, s_Gh = 0, s_acc = 0, s_N = 0, s_NI = 0, slab_bytes = 0;
+  std::vector<MsmbPart> parts;
+  uint8_t *SL = nullptr, *Ks = nullptr;   // the slab's block; the split scalars
+};
+int msm_rows_dev_plan(nbls_ctx* ctx, size_t n_pts, size_t n_rows, MsmbPlan* pl);
+int msm_rows_dev(nbls_ctx* ctx, const MsmbPlan& pl, const uint8_t* conv_pts, const uint8_t* d_scalars, uint8_t* d_out96, uint8_t* d_zero, hipStream_t s);
+// pipelines_kzg.cpp: the table of roots of a context; the challenges of n blobs on host threads
+int kzg_roots(nbls_ctx* ctx, unsigned log2_n, hipStream_t s, const uint8_t** table);
+void blob_challenges(unsigned log2_n, size_t n, const uint8_t* blobs, const uint8_t* c48, uint8_t* z32);
+// a trusted setup's Lagrange basis in the form the batched MSM reads (nbls_kzg_setup_create): 2^log2_n points, each with its endomorphism image, raw projective
+struct nbls_kzg_setup { int device = 0; unsigned log2_n = 0; uint8_t* pts = nullptr; };
 int msm_host(nbls_ctx* ctx, bool g2, size_t n, const uint8_t* pts, const uint8_t* scalars32, uint8_t* out, int8_t* status);
 int dst_on_device(nbls_ctx* ctx, const uint8_t* dst, size_t* dst_len, hipStream_t s, uint8_t** dd);
 std::vector<size_t> verify_plan(nbls_ctx* ctx, size_t n);

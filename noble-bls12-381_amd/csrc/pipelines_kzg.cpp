@@ -45,7 +45,7 @@ static const uint8_t* neg_g2_wire() {
   return w;
 }
 
-static int kzg_roots(nbls_ctx* ctx, unsigned log2_n, hipStream_t s, const uint8_t** table) {
+int kzg_roots(nbls_ctx* ctx, unsigned log2_n, hipStream_t s, const uint8_t** table) {
   if (!ctx->kzg_roots[log2_n]) {
     uint8_t* t = nullptr;
     HIPCHK(hipMalloc(&t, (size_t)32 << log2_n));
@@ -81,7 +81,7 @@ static void blob_challenge(unsigned log2_n, const uint8_t* blob, const uint8_t* 
 }
 // the challenges of n blobs on up to eight host threads (2 N + 2 dependent SHA-256 blocks per blob: no work for a GPU lane); thread t takes the blobs t, t + threads, ..
 // A thread that cannot be started costs nothing but time: the calling thread does its share
-static void blob_challenges(unsigned log2_n, size_t n, const uint8_t* blobs, const uint8_t* c48, uint8_t* z32) {
+void blob_challenges(unsigned log2_n, size_t n, const uint8_t* blobs, const uint8_t* c48, uint8_t* z32) {
   const unsigned hw = std::thread::hardware_concurrency();
   const size_t nt = std::max<size_t>(1, std::min<size_t>({n, 8, hw ? hw : 1}));
   auto share = [=](size_t t) { for (size_t i = t; i < n; i += nt) blob_challenge(log2_n, blobs + ((i * 32) << log2_n), c48 + 48 * i, z32 + 32 * i); };

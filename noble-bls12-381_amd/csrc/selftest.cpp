@@ -1,7 +1,8 @@
 // selftest.cpp -- host-side self test of the wave VM's compiler and simulator for the sanitizer build (make debug -> nbls_selftest, built with
 // -fsanitize=address,undefined).  TEST INFRASTRUCTURE (not part of libnbls.so): compiles every step program, verifies each one statically
 // (verify_program), and runs the pairing of the two generators through the simulator -- Miller loop as one program and as LINES + ACC -- printing
-// the first coefficient of the Miller value, which tests/test_debug_build.py compares with the reference's (SURVEY 8(c) anchor).
+// the first coefficient of the Miller value, which tests/test_debug_build.py compares with the reference's (SURVEY 8(c) anchor).  Also the quotient walk of fr_exec.h
+// (fr_eval_lane_t<true> / fr_quot_lane: the host side of kzg_quotient_kernel) on heap blocks of exactly the call's sizes, off a root and on one.
 #include <cstdio>
 #include <cstring>
 #include <string>
@@ -13,6 +14,8 @@
 extern "C" int nbls_sim_run(int prog, unsigned n_items, uint8_t** ptrs, const uint64_t* strides);
 extern "C" int nbls_sim_extra_run_named(const char* name, int aot, unsigned n_items, uint8_t** ptrs, const uint64_t* strides);
 extern "C" void nbls_sim_set_aot(int on);
+extern "C" int nbls_sim_fr_eval_roots(unsigned log2_n, size_t n, const uint8_t* evals32, const uint8_t* z32, uint8_t* out32, int8_t* status);
+extern "C" int nbls_sim_fr_quotient_roots(unsigned log2_n, size_t n, const uint8_t* evals32, const uint8_t* z32, uint8_t* out_y32, uint8_t* out_q32, int8_t* status);
 using namespace nbls;
 
 static void be48(uint8_t* o, const u32* limbs) { u32 w[12]; limbs_to_words(w, limbs); for (int i = 0; i < 12; i++) { u32 v = w[11 - i]; o[4 * i] = v >> 24; o[4 * i + 1] = v >> 16; o[4 * i + 2] = v >> 8; o[4 * i + 3] = v; } }
@@ -59,6 +62,15 @@ int main() {
     }
     nbls_sim_set_aot(0);
   }
+  for (unsigned log2_n : {2u, 9u}) {   // below one term per lane, and two terms per lane; polynomial 0 at z = 5, polynomial 1 at z = 1 = w_0
+    const size_t N = (size_t)1 << log2_n;
+    std::vector<uint8_t> ev(2 * N * 32), z(2 * 32), y(2 * 32), y2(2 * 32), q(2 * N * 32); std::vector<int8_t> st(2);
+    for (size_t i = 0; i < ev.size(); i++) ev[i] = (i % 32) ? (uint8_t)(i * 37 + 11) : 0;   // (top byte 0: canonical)
+    z[31] = 5; z[63] = 1;
+    if (nbls_sim_fr_quotient_roots(log2_n, 2, ev.data(), z.data(), y.data(), q.data(), st.data()) || nbls_sim_fr_eval_roots(log2_n, 2, ev.data(), z.data(), y2.data(), nullptr)) return 2;
+    if (st[0] || st[1] || memcmp(y.data(), y2.data(), 64) || memcmp(y.data() + 32, ev.data() + N * 32, 32)) { printf("QUOTIENT: y differs from the evaluation\n"); bad++; }
+  }
+  printf("quotient walk ok\n");
   if (memcmp(out1, out2, 576)) { printf("MISMATCH between the fused and the split Miller loop\n"); bad++; }
   printf("miller c0.c0.c0 ");
   for (int i = 0; i < 48; i++) printf("%02x", out1[i]);

@@ -574,6 +574,39 @@ __attribute__((visibility("default"))) int nbls_sim_fr_eval_roots(unsigned log2_
   for (size_t p = 0; p < n; p++) sim_eval_poly(log2_n, evals32 + 32ull * N * p, z32 + 32ull * p, roots.data(), out32 + 32ull * p, status ? status + p : nullptr);
   return 0;
 }
+// nbls_fr_quotient_roots as kzg_quotient_kernel runs it: the lanes of the evaluation with the inverses kept, the tree, y, then the second walk of every lane, the second tree
+// where z is a root, and the closing inversion
+static void sim_quotient_poly(unsigned log2_n, const uint8_t* f32, const uint8_t* z32, const Fr* roots, uint8_t* y32, uint8_t* q32, int8_t* status) {
+  const u32 N = 1u << log2_n, W = FR_EVAL_LANES;
+  const Fr zraw = fr_load_be(z32), z = fr_mul(zraw, fr_r2());
+  std::vector<Fr> part(W);
+  std::vector<u32> pre((size_t)((N + W - 1) / W) * FR_NL * W);
+  u32 hit = 0xffffffffu, bad = fr_ge_r_mask(zraw);
+  for (u32 l = 0; l < W; l++) {
+    const FrEvalPart p = fr_eval_lane_t<true>(f32, roots, z, N, l, W, pre.data());
+    part[l] = p.sum; bad |= p.bad;
+    if (p.hit != 0xffffffffu) hit = p.hit;
+  }
+  for (u32 s = W / 2; s > 0; s >>= 1) for (u32 l = 0; l < s; l++) part[l] = fr_add(part[l], part[l + s]);
+  const Fr y = fr_select(bad, fr_zero(), fr_eval_value(part[0], hit, z, log2_n, f32));
+  fr_store_be(y, y32);
+  if (status) *status = (int8_t)(bad & 21);
+  for (u32 l = 0; l < W; l++) part[l] = fr_quot_lane(f32, roots, y, hit, bad, N, l, W, pre.data(), q32);
+  if (hit == 0xffffffffu) return;
+  for (u32 s = W / 2; s > 0; s >>= 1) for (u32 l = 0; l < s; l++) part[l] = fr_add(part[l], part[l + s]);
+  fr_store_q(fr_select(bad, fr_zero(), fr_quot_within(part[0], z)), q32 + 32ull * hit);
+}
+__attribute__((visibility("default"))) int nbls_sim_fr_quotient_roots(unsigned log2_n, size_t n, const uint8_t* evals32, const uint8_t* z32, uint8_t* out_y32, uint8_t* out_q32,
+                                                                      int8_t* status) {
+  if (log2_n < 1 || log2_n > 12 || (n && (!evals32 || !z32 || !out_y32 || !out_q32)) || (n << log2_n) > ((size_t)1 << 24)) return -1;
+  const u32 N = 1u << log2_n;
+  std::vector<Fr> roots(N);
+  const Fr omega = fr_omega(log2_n);
+  for (u32 j = 0; j < N; j++) roots[j] = fr_root_entry(omega, log2_n, j);
+  for (size_t p = 0; p < n; p++)
+    sim_quotient_poly(log2_n, evals32 + 32ull * N * p, z32 + 32ull * p, roots.data(), out_y32 + 32ull * p, out_q32 + 32ull * N * p, status ? status + p : nullptr);
+  return 0;
+}
 __attribute__((visibility("default"))) int nbls_sim_program_count() { return (int)P_COUNT; }
 __attribute__((visibility("default"))) void nbls_sim_stats() { for (int i = 0; i < P_COUNT; i++) print_stats(get_program((ProgId)i)); }
 }

@@ -84,6 +84,14 @@ def load_library():
     lib.nbls_fr_eval_roots.argtypes = [vp, C.c_uint, sz, vp, vp, vp, vp]
     lib.nbls_kzg_verify_proofs.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, C.POINTER(i32), vp]
     lib.nbls_kzg_verify_blobs.argtypes = [vp, C.c_uint, sz, vp, vp, vp, vp, vp, C.POINTER(i32), vp]
+    lib.nbls_kzg_setup_create.argtypes = [vp, C.c_uint, vp, vp, C.POINTER(vp)]
+    lib.nbls_kzg_setup_destroy.argtypes = [vp]
+    lib.nbls_kzg_setup_destroy.restype = None
+    lib.nbls_kzg_setup_log2n.argtypes = [vp, C.POINTER(C.c_uint)]
+    lib.nbls_fr_quotient_roots.argtypes = [vp, C.c_uint, sz, vp, vp, vp, vp, vp]
+    lib.nbls_kzg_commit_blobs.argtypes = [vp, vp, sz, vp, vp, vp]
+    lib.nbls_kzg_compute_proofs.argtypes = [vp, vp, sz, vp, vp, vp, vp, vp]
+    lib.nbls_kzg_compute_blob_proofs.argtypes = [vp, vp, sz, vp, vp, vp, vp, vp]
     lib.nbls_keyset_create.argtypes = [vp, sz, vp, vp, C.POINTER(vp)]
     lib.nbls_keyset_destroy.argtypes = [vp]
     lib.nbls_keyset_destroy.restype = None
@@ -175,6 +183,40 @@ class KeySet:
             self.close()
         except Exception:
             pass
+
+
+class KzgSetup:
+    """A trusted setup's Lagrange basis in device memory (nbls_kzg_setup_create; Engine.kzg_setup), decoded and split once.  Freed by close() or when the object goes away."""
+
+    def __init__(self, lib, handle):
+        self.lib = lib
+        self.h = handle
+
+    @property
+    def log2_n(self):
+        k = C.c_uint(0)
+        if self.h is None or self.lib.nbls_kzg_setup_log2n(self.h, C.byref(k)) != 0:
+            raise NblsError('KzgSetup: the setup is closed')
+        return k.value
+
+    def close(self):
+        if getattr(self, 'h', None):
+            self.lib.nbls_kzg_setup_destroy(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class KzgSetupError(NblsError):
+    """nbls_kzg_setup_create refused the points: .code is the call's return code, .status the decoder's status of every entry (bytes)"""
+
+    def __init__(self, msg, code, status):
+        NblsError.__init__(self, msg)
+        self.code, self.status = code, status
 
 
 class Engine:
@@ -551,6 +593,68 @@ class Engine:
         st = C.create_string_buffer(max(n, 1)) if per_item else None
         self._chk(self.lib.nbls_kzg_verify_blobs(self.h, log2_n, n, b''.join(blobs), b''.join(commitments48), b''.join(proofs48), bytes(tau_g2_96), seed, C.byref(ok), st))
         return bool(ok.value), (st.raw[:n] if per_item else None)
+
+    # ---- KZG, the prover's side (include/nbls.h: nbls_kzg_setup_*, nbls_fr_quotient_roots, nbls_kzg_commit_blobs, nbls_kzg_compute_proofs, nbls_kzg_compute_blob_proofs)
+    def kzg_setup(self, log2_n, lagrange48):
+        """lagrange48: the 2^log2_n compressed points [L_j(tau)]G1 of the setup in bit-reversed order (a list of 48-byte values or their concatenation) -> KzgSetup, usable from
+        every Engine on this device.  Raises KzgSetupError (with the per-entry statuses) when an entry does not decode or is the zero point"""
+        raw = bytes(lagrange48) if isinstance(lagrange48, (bytes, bytearray, memoryview)) else b''.join(bytes(x) for x in lagrange48)
+        if not 1 <= log2_n <= 12 or len(raw) != 48 << log2_n:
+            raise NblsError('kzg_setup: log2_n in 1 .. 12 and %d bytes of points, got %d' % (48 << min(max(log2_n, 0), 12), len(raw)))
+        st = C.create_string_buffer(1 << log2_n)
+        h = C.c_void_p()
+        r = self.lib.nbls_kzg_setup_create(self.h, log2_n, raw, st, C.byref(h))
+        if r != 0:
+            raise KzgSetupError('kzg_setup: %s (code %d)' % (self.lib.nbls_strerror(r).decode(), r), r, st.raw)
+        return KzgSetup(self.lib, h)
+
+    @staticmethod
+    def _kzg_blobs(name, setup, blobs):
+        if getattr(setup, 'h', None) is None:
+            raise NblsError('%s: the setup is closed' % name)
+        size = 32 << setup.log2_n
+        if not blobs or any(len(b) != size for b in blobs):
+            raise NblsError('%s: one blob or more, every blob has %d bytes' % (name, size))
+        return len(blobs), b''.join(bytes(b) for b in blobs)
+
+    def fr_quotient_roots(self, log2_n, polys, zs):
+        """the quotient of the opening of every polynomial at its point (arguments as fr_eval_roots) -> (list of 32-byte values y_i, list of the 2^log2_n 32-byte values q_ij per
+        polynomial, status list: 21 = an element or the point is >= r, y and the row are then all-zero)"""
+        n = len(zs)
+        ev = bytes(polys) if isinstance(polys, (bytes, bytearray, memoryview)) else b''.join(self._fr32(v) for f in polys for v in f)
+        if len(ev) != (32 * n) << log2_n:
+            raise NblsError('fr_quotient_roots: %d points need %d bytes of values, got %d' % (n, (32 * n) << log2_n, len(ev)))
+        y = C.create_string_buffer(max(32 * n, 1)); q = C.create_string_buffer(max(len(ev), 1)); st = C.create_string_buffer(max(n, 1))
+        self._chk(self.lib.nbls_fr_quotient_roots(self.h, log2_n, n, ev, b''.join(map(self._fr32, zs)), y, q, st))
+        yr, qr, row = y.raw, q.raw, 32 << log2_n
+        return [yr[32 * i:32 * i + 32] for i in range(n)], [[qr[row * i + 32 * j:row * i + 32 * j + 32] for j in range(1 << log2_n)] for i in range(n)], list(st.raw[:n])
+
+    def kzg_commit_blobs(self, setup, blobs):
+        """blob_to_kzg_commitment for n blobs (byte strings of 32 << setup.log2_n bytes) -> (list of 48-byte commitments, status bytes: 21 = an element >= r, the commitment is
+        then 48 zero bytes)"""
+        n, raw = self._kzg_blobs('kzg_commit_blobs', setup, blobs)
+        out = C.create_string_buffer(48 * n); st = C.create_string_buffer(n)
+        self._chk(self.lib.nbls_kzg_commit_blobs(self.h, setup.h, n, raw, out, st))
+        return [out.raw[48 * i:48 * i + 48] for i in range(n)], st.raw[:n]
+
+    def kzg_compute_proofs(self, setup, blobs, zs):
+        """compute_kzg_proof for n (blob, z) pairs -> (list of 48-byte proofs, list of 32-byte values y_i = p_i(z_i), status bytes)"""
+        n, raw = self._kzg_blobs('kzg_compute_proofs', setup, blobs)
+        if len(zs) != n:
+            raise NblsError('kzg_compute_proofs: %d blobs and %d points' % (n, len(zs)))
+        out = C.create_string_buffer(48 * n); y = C.create_string_buffer(32 * n); st = C.create_string_buffer(n)
+        self._chk(self.lib.nbls_kzg_compute_proofs(self.h, setup.h, n, raw, b''.join(map(self._fr32, zs)), out, y, st))
+        return [out.raw[48 * i:48 * i + 48] for i in range(n)], [y.raw[32 * i:32 * i + 32] for i in range(n)], st.raw[:n]
+
+    def kzg_compute_blob_proofs(self, setup, blobs, commitments48=None):
+        """compute_blob_kzg_proof for n blobs -> (list of 48-byte commitments, list of 48-byte proofs, status bytes).  commitments48: the blobs' commitments (only hashed into
+        the challenge, not decoded), or None: the call commits first and returns what it computed"""
+        n, raw = self._kzg_blobs('kzg_compute_blob_proofs', setup, blobs)
+        if commitments48 is not None and (len(commitments48) != n or any(len(c) != 48 for c in commitments48)):
+            raise NblsError('kzg_compute_blob_proofs: %d blobs need %d 48-byte commitments' % (n, n))
+        cs = C.create_string_buffer(48 * n); out = C.create_string_buffer(48 * n); st = C.create_string_buffer(n)
+        self._chk(self.lib.nbls_kzg_compute_blob_proofs(self.h, setup.h, n, raw, None if commitments48 is None else b''.join(bytes(c) for c in commitments48), cs, out, st))
+        return [cs.raw[48 * i:48 * i + 48] for i in range(n)], [out.raw[48 * i:48 * i + 48] for i in range(n)], st.raw[:n]
 
     def get_public_keys(self, keys):
         """getPublicKey for a batch of private keys -> list of 48-byte compressed keys; raises like the reference on a zero key"""

@@ -87,6 +87,15 @@ export declare class PointG1 {
   /** EIP-4844 verify_blob_kzg_proof_batch: blobs of 32 * 2^k bytes (k = 12 on mainnet); the challenge is hashed on the host, the polynomial evaluated on the device */
   static verifyBlobKzgProofBatch(blobs: Hex[], commitments: (PointG1 | Hex)[], proofs: (PointG1 | Hex)[], tauG2: PointG2 | Hex, opts?: KzgOptions): KzgResult;
   static verifyBlobKzgProofBatchAsync(blobs: Hex[], commitments: (PointG1 | Hex)[], proofs: (PointG1 | Hex)[], tauG2: PointG2 | Hex, opts?: KzgOptions): Promise<KzgResult>;
+  /** EIP-4844 blob_to_kzg_commitment / compute_kzg_proof / compute_blob_kzg_proof for many blobs; status: 0, or 21 (a non-canonical element: that blob's outputs are all-zero bytes) */
+  static readonly KzgSetup: typeof KzgSetup;
+  static blobToKzgCommitments(setup: KzgSetup, blobs: Hex[]): KzgCommitments;
+  static blobToKzgCommitmentsAsync(setup: KzgSetup, blobs: Hex[]): Promise<KzgCommitments>;
+  static computeKzgProofs(setup: KzgSetup, blobs: Hex[], zs: ShareId[]): KzgProofs;
+  static computeKzgProofsAsync(setup: KzgSetup, blobs: Hex[], zs: ShareId[]): Promise<KzgProofs>;
+  /** commitments given: only hashed into the challenge, not decoded; omitted: computed first and returned */
+  static computeBlobKzgProofs(setup: KzgSetup, blobs: Hex[], commitments?: (PointG1 | Hex)[]): KzgBlobProofs;
+  static computeBlobKzgProofsAsync(setup: KzgSetup, blobs: Hex[], commitments?: (PointG1 | Hex)[]): Promise<KzgBlobProofs>;
   isZero(): boolean; equals(rhs: PointG1): boolean; negate(): PointG1; add(rhs: PointG1): PointG1; subtract(rhs: PointG1): PointG1; double(): PointG1;
   multiply(scalar: bigint | number): PointG1; multiplyUnsafe(scalar: bigint | number): PointG1; multiplyPrecomputed(scalar: bigint | number): PointG1;
   assertValidity(): this; toAffine(): [Fp, Fp]; toRawBytes(isCompressed?: boolean): Uint8Array; toHex(isCompressed?: boolean): string;
@@ -136,6 +145,15 @@ export declare function verifyMultipleAggregateSignatures(sets: { publicKeys: (H
 export type ShareId = bigint | number | string | Uint8Array;
 /** KZG: seed = 32 bytes for reproducible weights (default: from the OS); perItem === false stops after the combined check (status null) */
 export interface KzgOptions { seed?: Hex; perItem?: boolean }
+/** A trusted setup's g1_lagrange (2^k points in bit-reversed order, 1 <= k <= 12) decoded once into device memory; close() frees it.  Reached as PointG1.KzgSetup */
+declare class KzgSetup {
+  constructor(points: (PointG1 | Hex)[]);
+  readonly log2n: number;
+  close(): void;
+}
+export interface KzgCommitments { commitments: Uint8Array[]; status: Uint8Array }
+export interface KzgProofs { proofs: Uint8Array[]; ys: Uint8Array[]; status: Uint8Array }
+export interface KzgBlobProofs { commitments: Uint8Array[]; proofs: Uint8Array[]; status: Uint8Array }
 export interface KzgResult { ok: boolean; status: Uint8Array | null }
 /** one group of combineSharesBatch: its shares are all points or all compressed bytes / hex */
 export type ShareGroup<P> = { shares: P[] | Hex[]; ids: ShareId[] } | [P[] | Hex[], ShareId[]];
@@ -154,6 +172,11 @@ export interface NativeThresholdCalls {
   kzgVerifyProofsAsync(commitments48: Uint8Array, z32: Uint8Array, y32: Uint8Array, proofs48: Uint8Array, tauG2: Uint8Array, seed32: Uint8Array | null, perItem: number): Promise<{ out: Uint8Array; status: Uint8Array }>;
   kzgVerifyBlobs(log2n: number, blobs: Uint8Array, commitments48: Uint8Array, proofs48: Uint8Array, tauG2: Uint8Array, seed32: Uint8Array | null, perItem: number): { out: Uint8Array; status: Uint8Array };
   kzgVerifyBlobsAsync(log2n: number, blobs: Uint8Array, commitments48: Uint8Array, proofs48: Uint8Array, tauG2: Uint8Array, seed32: Uint8Array | null, perItem: number): Promise<{ out: Uint8Array; status: Uint8Array }>;
+  /** nbls_kzg_setup_create / _destroy and the three prover calls (kind 0 commitments, 1 proofs at aux = z32, 2 blob proofs with aux = commitments48 or null); out = two arrays of n entries one behind the other */
+  kzgSetupCreate(log2n: number, lagrange48: Uint8Array): unknown;
+  kzgSetupDestroy(handle: unknown): void;
+  kzgProve(kind: number, handle: unknown, blobs: Uint8Array, aux: Uint8Array | null): { out: Uint8Array; status: Uint8Array };
+  kzgProveAsync(kind: number, handle: unknown, blobs: Uint8Array, aux: Uint8Array | null): Promise<{ out: Uint8Array; status: Uint8Array }>;
 }
 /** The two calls of the N-API addon (nbls_napi.node) that verifyMultipleSignatures / verifyMultipleAggregateSignatures take when at least two wire-format sets have equal messages:
  * msgs / offsets hold the distinct messages, set i signs message msgIndex[i] (nbls_verify_multiple_shared / nbls_verify_aggregates_shared; a type only, the facade does not export the addon) */

@@ -217,6 +217,44 @@ async function verifyBlobKzgProofBatchAsync(blobs, commitments, proofs, tauG2, o
   try { return kzgResult(await native.kzgVerifyBlobsAsync(a[0], a[1], a[2], a[3], a[4], a[5], a[6]), a[6]); } catch (e) { return kzgFail(e); }
 }
 
+// ---- KZG, the prover's side (nbls_kzg_setup_*, nbls_kzg_commit_blobs / _compute_proofs / _compute_blob_proofs): blob_to_kzg_commitment, compute_kzg_proof and
+// compute_blob_kzg_proof for many blobs against a setup kept on the device.  new PointG1.KzgSetup(points) (a static of PointG1, like the calls: the top-level exports stay as they are): the setup's g1_lagrange in bit-reversed order (2^k points, 1 <= k <= 12; 48
+// compressed bytes, hex, or PointG1 each), decoded once; close() frees it.  Blobs: bytes or hex of 32 * 2^k; z: bigint | number | hex | 32 bytes.  Results are arrays of
+// Uint8Array (48-byte compressed points, 32-byte values) and status = one byte per blob (0, or 21: a blob element or z is >= CURVE.r, that blob's outputs are then all-zero bytes)
+class KzgSetup {
+  constructor(points) {
+    const log2n = Math.round(Math.log2(points.length));
+    if (log2n < 1 || log2n > 12 || points.length !== 1 << log2n) throw new Error('Invalid setup: expected 2^k points, 1 <= k <= 12');
+    ensureInit();
+    this.log2n = log2n;
+    try { this.handle = native.kzgSetupCreate(log2n, kzgPack(points, 48, 'setup point', kzgG1)); } catch (e) {
+      if (e && e.nblsCode === -5) { const err = new Error('Invalid setup: a point does not decode, is outside the subgroup or is the zero point'); err.status = e.status; throw err; }
+      throw e;
+    }
+  }
+  close() { if (this.handle) native.kzgSetupDestroy(this.handle); this.handle = null; }
+}
+function kzgProveArgs(setup, blobs, aux, auxWidth, what, toBytes) {
+  if (!(setup instanceof KzgSetup) || !setup.handle) throw new Error('Expected an open KzgSetup');
+  if (!blobs.length) throw new Error('Expected non-empty array');
+  if (aux && aux.length !== blobs.length) throw new Error('Expected as many ' + what + 's as blobs');
+  return [setup.handle, kzgPack(blobs, 32 << setup.log2n, 'blob', ensureBytes), aux ? kzgPack(aux, auxWidth, what, toBytes) : null];
+}
+function kzgSplit(res, n, widths) {
+  const parts = []; let at = 0;
+  for (const w of widths) { const one = []; for (let i = 0; i < n; i++) one.push(res.out.slice(at + i * w, at + (i + 1) * w)); parts.push(one); at += n * w; }
+  return parts;
+}
+const kzgCommitResult = (res, n) => ({ commitments: kzgSplit(res, n, [48])[0], status: res.status });
+const kzgProofResult = (res, n) => { const p = kzgSplit(res, n, [48, 32]); return { proofs: p[0], ys: p[1], status: res.status }; };
+const kzgBlobProofResult = (res, n) => { const p = kzgSplit(res, n, [48, 48]); return { commitments: p[0], proofs: p[1], status: res.status }; };
+function blobToKzgCommitments(setup, blobs) { const a = kzgProveArgs(setup, blobs, null); return kzgCommitResult(native.kzgProve(0, a[0], a[1], null), blobs.length); }
+async function blobToKzgCommitmentsAsync(setup, blobs) { const a = kzgProveArgs(setup, blobs, null); return kzgCommitResult(await native.kzgProveAsync(0, a[0], a[1], null), blobs.length); }
+function computeKzgProofs(setup, blobs, zs) { const a = kzgProveArgs(setup, blobs, zs, 32, 'field element', shareIdBytes); return kzgProofResult(native.kzgProve(1, a[0], a[1], a[2]), blobs.length); }
+async function computeKzgProofsAsync(setup, blobs, zs) { const a = kzgProveArgs(setup, blobs, zs, 32, 'field element', shareIdBytes); return kzgProofResult(await native.kzgProveAsync(1, a[0], a[1], a[2]), blobs.length); }
+function computeBlobKzgProofs(setup, blobs, commitments) { const a = kzgProveArgs(setup, blobs, commitments || null, 48, 'commitment', kzgG1); return kzgBlobProofResult(native.kzgProve(2, a[0], a[1], a[2]), blobs.length); }
+async function computeBlobKzgProofsAsync(setup, blobs, commitments) { const a = kzgProveArgs(setup, blobs, commitments || null, 48, 'commitment', kzgG1); return kzgBlobProofResult(await native.kzgProveAsync(2, a[0], a[1], a[2]), blobs.length); }
+
 // Points are held as affine wire bytes (what the engine consumes) or as the zero point.  The reference's constructor form
 // new PointG1(x: Fp, y: Fp, z?: Fp) (index.ts:291) is accepted too: the projective triple is made affine on the host.
 class PointG1 {
@@ -339,6 +377,14 @@ class PointG1 {
   static verifyKzgProofBatchAsync(commitments, zs, ys, proofs, tauG2, opts) { return verifyKzgProofBatchAsync(commitments, zs, ys, proofs, tauG2, opts); }
   static verifyBlobKzgProofBatch(blobs, commitments, proofs, tauG2, opts) { return verifyBlobKzgProofBatch(blobs, commitments, proofs, tauG2, opts); }
   static verifyBlobKzgProofBatchAsync(blobs, commitments, proofs, tauG2, opts) { return verifyBlobKzgProofBatchAsync(blobs, commitments, proofs, tauG2, opts); }
+  // the prover's side against a KzgSetup (above): commitments, proofs at given points, blob proofs (commitments given, or computed first and returned)
+  static get KzgSetup() { return KzgSetup; }
+  static blobToKzgCommitments(setup, blobs) { return blobToKzgCommitments(setup, blobs); }
+  static blobToKzgCommitmentsAsync(setup, blobs) { return blobToKzgCommitmentsAsync(setup, blobs); }
+  static computeKzgProofs(setup, blobs, zs) { return computeKzgProofs(setup, blobs, zs); }
+  static computeKzgProofsAsync(setup, blobs, zs) { return computeKzgProofsAsync(setup, blobs, zs); }
+  static computeBlobKzgProofs(setup, blobs, commitments) { return computeBlobKzgProofs(setup, blobs, commitments); }
+  static computeBlobKzgProofsAsync(setup, blobs, commitments) { return computeBlobKzgProofsAsync(setup, blobs, commitments); }
   equals(rhs) { return this.zero === rhs.zero && (this.zero || bytesToHex(this.aff) === bytesToHex(rhs.aff)); }
   // reference index.ts:359-381
   toHex(isCompressed = false) {

@@ -2,7 +2,7 @@
  * nbls_napi.c -- thin N-API addon: exposes the C ABI of libnbls.so (include/nbls.h) to Node.  No arithmetic here.
  * libnbls.so is loaded with dlopen at module init so the addon builds with plain gcc (no HIP needed):
  *     gcc -shared -fPIC -I/usr/include/node -I../../include nbls_napi.c -o nbls_napi.node -ldl
- * Calls are synchronous (they block for the duration of the GPU work) except verifyBatchAsync (and signBatchAsync, verifyMultipleAsync, verifyAggregatesAsync, verifyMultipleSharedAsync, verifyAggregatesSharedAsync, frOpAsync, lagrangeAtZeroAsync, combineSharesAsync, polyEvalAsync, kzgVerifyProofsAsync, kzgVerifyBlobsAsync), which runs on a libuv worker thread
+ * Calls are synchronous (they block for the duration of the GPU work) except verifyBatchAsync (and signBatchAsync, verifyMultipleAsync, verifyAggregatesAsync, verifyMultipleSharedAsync, verifyAggregatesSharedAsync, frOpAsync, lagrangeAtZeroAsync, combineSharesAsync, polyEvalAsync, kzgVerifyProofsAsync, kzgVerifyBlobsAsync, kzgProveAsync), which runs on a libuv worker thread
  * (napi_create_async_work) and resolves a Promise: the facade's verifyBatch uses it for wire-format inputs (the calls that can take tens of milliseconds).  Typed arrays are passed by reference (napi_get_typedarray_info), no copies.
  */
 #include <node_api.h>
@@ -23,6 +23,7 @@ SYM(nbls_g2_prepare) SYM(nbls_pairing_prepared) SYM(nbls_verify_multiple) SYM(nb
 SYM(nbls_g1_from_hex_batch) SYM(nbls_g2_from_hex_batch) SYM(nbls_g2_from_signature_batch) SYM(nbls_g1_clear_cofactor_batch) SYM(nbls_g2_clear_cofactor_batch)
 SYM(nbls_fr_op_batch) SYM(nbls_lagrange_at_zero) SYM(nbls_g2_combine_shares) SYM(nbls_g1_combine_shares) SYM(nbls_g1_poly_eval) SYM(nbls_g2_poly_eval)
 SYM(nbls_kzg_verify_proofs) SYM(nbls_kzg_verify_blobs)
+SYM(nbls_kzg_setup_create) SYM(nbls_kzg_setup_destroy) SYM(nbls_kzg_setup_log2n) SYM(nbls_kzg_commit_blobs) SYM(nbls_kzg_compute_proofs) SYM(nbls_kzg_compute_blob_proofs)
 static nbls_ctx* ctx;
 static nbls_multi* multi;   /* several GPUs behind one handle (initMulti): ctx is then its first context; the batch calls shard over all of them */
 #define MULTI() (multi && p_nbls_multi_device_count(multi) > 1)
@@ -431,9 +432,10 @@ static napi_value SignBatchAsync(napi_env env, napi_callback_info info) {
  * The offsets must name identifiers and shares that are in the arrays (checked here); the library checks the rest. */
 typedef struct {
   napi_async_work work; napi_deferred deferred; napi_ref refs[9]; int nrefs;
-  int kind /* 0 frOp, 1 lagrangeAtZero, 2 combineShares, 3 polyEval, 4 kzgVerifyProofs, 5 kzgVerifyBlobs */, op, g2; const uint8_t *a, *b, *shares; const uint32_t *offs, *coffs; size_t n;
+  int kind /* 0 frOp, 1 lagrangeAtZero, 2 combineShares, 3 polyEval, 4 kzgVerifyProofs, 5 kzgVerifyBlobs, 6 .. 8 kzgProve */, op, g2; const uint8_t *a, *b, *shares; const uint32_t *offs, *coffs; size_t n;
   uint8_t* out; int8_t* st;
   const uint8_t *proofs, *tau, *seed; int per_item;   /* KZG: a = commitments, b = z (proofs) or the blobs, shares = y, op = log2_n; out = the verdict as one int */
+  const nbls_kzg_setup* su;   /* kzgProve: b = the blobs, a = the points z (7) or the given commitments (8; may be NULL), out = two arrays of n entries one behind the other */
   nbls_ctx* c; int rc;
 } thr_job;
 static void thr_execute(napi_env env, void* data) { thr_job* j = (thr_job*)data; (void)env;
@@ -441,6 +443,9 @@ static void thr_execute(napi_env env, void* data) { thr_job* j = (thr_job*)data;
         : j->kind == 1 ? p_nbls_lagrange_at_zero(j->c, j->n, j->offs, j->a, j->out, j->st)
         : j->kind == 4 ? p_nbls_kzg_verify_proofs(j->c, j->n, j->a, j->b, j->shares, j->proofs, j->tau, j->seed, (int*)j->out, j->per_item ? j->st : NULL)
         : j->kind == 5 ? p_nbls_kzg_verify_blobs(j->c, (unsigned)j->op, j->n, j->b, j->a, j->proofs, j->tau, j->seed, (int*)j->out, j->per_item ? j->st : NULL)
+        : j->kind == 6 ? p_nbls_kzg_commit_blobs(j->c, j->su, j->n, j->b, j->out, j->st)
+        : j->kind == 7 ? p_nbls_kzg_compute_proofs(j->c, j->su, j->n, j->b, j->a, j->out, j->out + 48 * j->n, j->st)
+        : j->kind == 8 ? p_nbls_kzg_compute_blob_proofs(j->c, j->su, j->n, j->b, j->a, j->out, j->out + 48 * j->n, j->st)
         : j->kind == 3 ? (j->g2 ? p_nbls_g2_poly_eval : p_nbls_g1_poly_eval)(j->c, j->n, j->coffs, j->shares, j->offs, j->a, j->out, j->st)
         : (j->g2 ? p_nbls_g2_combine_shares : p_nbls_g1_combine_shares)(j->c, j->n, j->offs, j->a, j->shares, j->out, j->st); }
 /* the Error of a failed call of this family: the message of throw_code, and the library's return code as the number `nblsCode` (what the facade reads: never the text) */
@@ -574,6 +579,55 @@ static napi_value kzg_blobs_call(napi_env env, napi_callback_info info, int asyn
 static napi_value KzgVerifyBlobs(napi_env env, napi_callback_info info) { return kzg_blobs_call(env, info, 0); }
 static napi_value KzgVerifyBlobsAsync(napi_env env, napi_callback_info info) { return kzg_blobs_call(env, info, 1); }
 
+/* The KZG prover (nbls_kzg_setup_*, nbls_kzg_commit_blobs / _compute_proofs / _compute_blob_proofs):
+ *   kzgSetupCreate(log2n, lagrange48) -> a handle (the setup's Lagrange basis on the device; freed by kzgSetupDestroy or with the handle); a refused setup throws with the
+ *                                        per-entry decoder statuses as the Error's `status`
+ *   kzgSetupDestroy(handle)              frees it now; the handle is dead afterwards.  Not while an asynchronous call uses it
+ *   kzgProve(kind, handle, blobs, aux)   kind 0: commitments (aux null) -> out = n x 48; 1: proofs at the points aux = z32 -> out = n x 48 proofs, then n x 32 values y;
+ *                                        2: blob proofs, aux = the commitments or null -> out = n x 48 commitments, then n x 48 proofs.  status = one byte per blob.  + Async */
+typedef struct { nbls_kzg_setup* s; } setup_box;
+static void setup_finalize(napi_env env, void* data, void* hint) { (void)env; (void)hint; setup_box* b = (setup_box*)data; if (b->s && p_nbls_kzg_setup_destroy) p_nbls_kzg_setup_destroy(b->s); free(b); }
+static napi_value KzgSetupCreate(napi_env env, napi_callback_info info) {
+  ARGS(2); NEED_CTX(); BYTES(1, pts, lp);
+  int32_t log2n; if (napi_get_value_int32(env, argv[0], &log2n) != napi_ok) { napi_throw_type_error(env, NULL, "expected a number for log2n"); return NULL; }
+  if (log2n < 1 || log2n > 12 || lp != (size_t)48 << log2n) { napi_throw_range_error(env, NULL, "log2n in 1 .. 12 and 48 << log2n bytes of compressed points"); return NULL; }
+  uint8_t* st; napi_value vs = new_u8(env, (size_t)1 << log2n, &st); ALLOCATED(vs);
+  setup_box* box = (setup_box*)calloc(1, sizeof *box); if (!box) { napi_throw_error(env, NULL, "out of memory"); return NULL; }
+  const int rc = p_nbls_kzg_setup_create(ctx, (unsigned)log2n, pts, (int8_t*)st, &box->s);
+  if (rc) { free(box); napi_value err = thr_error(env, rc); napi_set_named_property(env, err, "status", vs); napi_throw(env, err); return NULL; }
+  napi_value h;
+  if (napi_create_external(env, box, setup_finalize, NULL, &h) != napi_ok) { p_nbls_kzg_setup_destroy(box->s); free(box); napi_throw_error(env, NULL, "napi_create_external failed"); return NULL; }
+  return h;
+}
+static napi_value KzgSetupDestroy(napi_env env, napi_callback_info info) {
+  ARGS(1);
+  setup_box* box = NULL;
+  if (napi_get_value_external(env, argv[0], (void**)&box) != napi_ok || !box) { napi_throw_type_error(env, NULL, "expected a setup handle"); return NULL; }
+  if (box->s) { p_nbls_kzg_setup_destroy(box->s); box->s = NULL; }
+  return NULL;
+}
+static napi_value kzg_prove_call(napi_env env, napi_callback_info info, int async) {
+  ARGS(4); NEED_CTX(); BYTES(2, blobs, lb);
+  int32_t kind; if (napi_get_value_int32(env, argv[0], &kind) != napi_ok || kind < 0 || kind > 2) { napi_throw_type_error(env, NULL, "expected the kind 0, 1 or 2"); return NULL; }
+  setup_box* box = NULL;
+  if (napi_get_value_external(env, argv[1], (void**)&box) != napi_ok || !box || !box->s) { napi_throw_type_error(env, NULL, "expected a live setup handle"); return NULL; }
+  unsigned log2n = 0; p_nbls_kzg_setup_log2n(box->s, &log2n);
+  uint8_t* aux = NULL; size_t la = 0;
+  napi_valuetype t; napi_typeof(env, argv[3], &t);
+  if (t != napi_null && t != napi_undefined && !get_bytes(env, argv[3], &aux, &la)) { napi_throw_type_error(env, NULL, "expected Uint8Array or null"); return NULL; }
+  const size_t n = lb >> (5 + log2n);
+  if (!n || lb != (n * 32) << log2n || (kind == 0 && aux) || (kind == 1 && (!aux || la != n * 32)) || (kind == 2 && aux && la != n * 48)) {
+    napi_throw_range_error(env, NULL, "n blobs of 32 << log2n bytes; n points of 32 bytes (proofs) or n commitments of 48 bytes or null (blob proofs)"); return NULL; }
+  thr_job job; memset(&job, 0, sizeof job);
+  job.kind = 6 + kind; job.su = box->s; job.b = blobs; job.a = aux; job.n = n;
+  const size_t lo = kind == 0 ? n * 48 : kind == 1 ? n * 80 : n * 96;
+  napi_value vo = new_u8(env, lo, &job.out), vs = new_u8(env, n, (uint8_t**)&job.st); ALLOCATED(vo); ALLOCATED(vs);
+  memset(job.out, 0, lo); memset(job.st, 0, n);
+  return thr_run(env, &job, async, argv + 1, aux ? 3 : 2, vo, vs);   /* the handle stays referenced while the call runs */
+}
+static napi_value KzgProve(napi_env env, napi_callback_info info) { return kzg_prove_call(env, info, 0); }
+static napi_value KzgProveAsync(napi_env env, napi_callback_info info) { return kzg_prove_call(env, info, 1); }
+
 static napi_value ModuleInit(napi_env env, napi_value exports) {
   const char* path = getenv("NBLS_LIB");
   char buf[4096];
@@ -587,6 +641,7 @@ static napi_value ModuleInit(napi_env env, napi_value exports) {
   LOAD(nbls_init_multi) LOAD(nbls_destroy_multi) LOAD(nbls_multi_device_count) LOAD(nbls_multi_context) LOAD(nbls_multi_pairing_batch) LOAD(nbls_multi_miller_product) LOAD(nbls_multi_verify_batch) LOAD(nbls_g2_prepare) LOAD(nbls_pairing_prepared) LOAD(nbls_verify_multiple) LOAD(nbls_verify_aggregates) LOAD(nbls_verify_multiple_shared) LOAD(nbls_verify_aggregates_shared)
   LOAD(nbls_g1_from_hex_batch) LOAD(nbls_g2_from_hex_batch) LOAD(nbls_g2_from_signature_batch) LOAD(nbls_g1_clear_cofactor_batch) LOAD(nbls_g2_clear_cofactor_batch)
   LOAD(nbls_fr_op_batch) LOAD(nbls_lagrange_at_zero) LOAD(nbls_g2_combine_shares) LOAD(nbls_g1_combine_shares) LOAD(nbls_g1_poly_eval) LOAD(nbls_g2_poly_eval) LOAD(nbls_kzg_verify_proofs) LOAD(nbls_kzg_verify_blobs)
+  LOAD(nbls_kzg_setup_create) LOAD(nbls_kzg_setup_destroy) LOAD(nbls_kzg_setup_log2n) LOAD(nbls_kzg_commit_blobs) LOAD(nbls_kzg_compute_proofs) LOAD(nbls_kzg_compute_blob_proofs)
   {   /* the ABI the addon was written against (include/nbls.h NBLS_ABI_VERSION): an older or newer library is refused at load instead of misread at run time */
     int (*abi)(void) = (int (*)(void))dlsym(lib, "nbls_abi_version");
     if (!abi || abi() != NBLS_ABI_VERSION) { napi_throw_error(env, NULL, "libnbls.so: ABI version differs from the one this addon was built for (include/nbls.h NBLS_ABI_VERSION)"); return exports; }
@@ -606,7 +661,8 @@ static napi_value ModuleInit(napi_env env, napi_value exports) {
     {"combineSharesAsync", 0, CombineSharesAsync, 0, 0, 0, napi_enumerable, 0}, {"polyEval", 0, PolyEval, 0, 0, 0, napi_enumerable, 0},
     {"polyEvalAsync", 0, PolyEvalAsync, 0, 0, 0, napi_enumerable, 0}, {"kzgVerifyProofs", 0, KzgVerifyProofs, 0, 0, 0, napi_enumerable, 0},
     {"kzgVerifyProofsAsync", 0, KzgVerifyProofsAsync, 0, 0, 0, napi_enumerable, 0}, {"kzgVerifyBlobs", 0, KzgVerifyBlobs, 0, 0, 0, napi_enumerable, 0},
-    {"kzgVerifyBlobsAsync", 0, KzgVerifyBlobsAsync, 0, 0, 0, napi_enumerable, 0}};
+    {"kzgVerifyBlobsAsync", 0, KzgVerifyBlobsAsync, 0, 0, 0, napi_enumerable, 0}, {"kzgSetupCreate", 0, KzgSetupCreate, 0, 0, 0, napi_enumerable, 0},
+    {"kzgSetupDestroy", 0, KzgSetupDestroy, 0, 0, 0, napi_enumerable, 0}, {"kzgProve", 0, KzgProve, 0, 0, 0, napi_enumerable, 0}, {"kzgProveAsync", 0, KzgProveAsync, 0, 0, 0, napi_enumerable, 0}};
   napi_define_properties(env, exports, sizeof d / sizeof d[0], d);
   return exports;
 }
