@@ -1,4 +1,4 @@
-"""Helpers of the KZG tests (test_kzg_sim.py, test_kzg_abi.py, test_gpu_kzg.py): the scalar side in Python integers -- the roots of unity in bit-reversed order, the barycentric
+"""Helpers of the KZG tests (test_kzg_sim.py, test_kzg_abi.py, test_kzg_cases.py, test_gpu_kzg.py, test_gpu_kzg_adversarial.py): the scalar side in Python integers -- the roots of unity in bit-reversed order, the barycentric
 formula as the issue states it, Horner's rule, the blob challenge by hashlib -- and a test-only trusted setup: with the secret TAU known, commitments and proofs are single
 multiples of the generator, C = [p(tau)]G1 and pi = [(p(tau) - y) / (tau - z)]G1, taken from the oracle.  Nothing here calls the code under test."""
 import hashlib
@@ -69,6 +69,11 @@ def blob_bytes(f):
     return b''.join(b32(v) for v in f)
 
 
+def weight(seed, i):
+    """the weight of item i of a batched check as include/nbls.h states it: r_i = BE64(SHA-256(seed || BE64(i))[0..8]) | 2^63"""
+    return int.from_bytes(hashlib.sha256(seed + i.to_bytes(8, 'big')).digest()[:8], 'big') | 1 << 63
+
+
 def challenge(blob, commitment48, log2_n):
     """z = BE(SHA-256("FSBLOBVERIFY_V1_" || BE128(N) || blob || commitment)) mod r"""
     d = hashlib.sha256(b'FSBLOBVERIFY_V1_' + (1 << log2_n).to_bytes(16, 'big') + blob + commitment48).digest()
@@ -102,6 +107,17 @@ class Setup:
             y = eval_roots(f, z, log2_n)
         assert z != self.tau
         return y, self.g1((pt - y) * pow(self.tau - z, -1, R))
+
+    def tuple_for(self, s, z, y):
+        """-> (C, z, y, pi) with pi = [s]G1 and C = [y + s (tau - z)]G1: valid by construction, e(pi, [tau]G2) = e(C + [z]pi - [y]G1, G2) <=> s tau = c + z s - y.  No polynomial
+        is needed, so s, z and y can be chosen freely (s = 0: the zero proof; y = s (z - tau): the zero commitment)"""
+        return self.g1(y + s * (self.tau - z)), z, y, self.g1(s)
+
+    def tuples_pooled(self, n, rnd, pool=32):
+        """-> n valid tuples (C, z, y, pi) whose s and y come from a pool of non-zero values, z fresh: `pool` oracle multiplications for the proofs, one per commitment"""
+        ss = [rnd.randrange(1, R) for _ in range(pool)]
+        ys = [rnd.randrange(1, R) for _ in range(pool)]
+        return [self.tuple_for(rnd.choice(ss), rnd.randrange(1, R), rnd.choice(ys)) for _ in range(n)]
 
     def blob_case(self, f, log2_n):
         """-> (blob, commitment, proof, z, y) of verify_blob_kzg_proof"""
