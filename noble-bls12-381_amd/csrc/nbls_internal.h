@@ -16,6 +16,7 @@
 #include "pow_exec.h"
 #include "sha256.h"
 #include "curve.h"   // G1_FIXED_WIN and the table geometry of pt_mul_fixed_g1
+#include "bufs.h"    // BufArg / B(), BufList, ChainLink, bind_bufs
 #include <thread>
 
 extern "C" int nbls_vm_launch(const nbls::KernelArgs* ka, unsigned lds_bytes, void* stream);
@@ -225,9 +226,8 @@ struct nbls_ctx {
   // side stream for the one-element chains of verifyBatch (signature decompression: a 758-bit Fp2 exponentiation on a single
   // lane is ~4 ms of pure latency) so that they overlap the batch-wide kernels instead of serialising with them
   hipStream_t side = nullptr; hipEvent_t ev_fork = nullptr, ev_join = nullptr; uint8_t* side_scratch = nullptr;
-  // large pairing batches run as two halves on two streams (nbls_pairing_batch_dev): item offset applied to every per-item buffer of a launch, second stream, events
-  bool in_halves = false;   // the running pairing call is one of two halves on two streams: their launches fill each other's tails, so the final exponentiation's middle is NOT chained (run_chain)
-  size_t ioff = 0; hipStream_t half_stream = nullptr; hipEvent_t ev_half_fork = nullptr, ev_half_join = nullptr;
+  // large pairing batches run as two halves on two streams (nbls_pairing_batch_dev; each half is told its Window): second stream, events
+  hipStream_t half_stream = nullptr; hipEvent_t ev_half_fork = nullptr, ev_half_join = nullptr;
   // pairs from which a call runs as two halves on two streams.  16,384 since the end of round 6 (8192 before): on today's kernels one stream is faster up to 15,360 pairs
   // (10,240: 3.91 against 4.73 ms; 12,800 - 15,360: 5.05 - 5.24 against 5.67 - 5.9), the halves from 16,384 (6.1 against 6.45; profiles/round6_ab_halves.txt)
   size_t halves_min = env_long("NBLS_HALVES_MIN", 16384) > 0 ? (size_t)env_long("NBLS_HALVES_MIN", 16384) : (size_t)-1;   // NBLS_HALVES_MIN=0: never (profiles of kernels running alone)
@@ -293,9 +293,7 @@ struct nbls_ctx {
 
 // A chain: several programs executed back to back by ONE launch (aot.h): every wavefront runs them in order for its own items, the values between them pass
 // through the HBM scratch buffers the separate launches would use.  Falls back to one launch per program when some program is not on an ahead-of-time kernel,
-// when the programs do not share a kernel / the lanes per item, or in checked mode (whose per-launch buffer checks live in run()).
-typedef std::initializer_list<std::pair<int, std::pair<const void*, size_t>>> BufList;
-struct ChainLink { ProgId id; BufList bufs; };
+// when the programs do not share a kernel / the lanes per item, or in checked mode (whose per-launch buffer checks live in run()).  (ChainLink: bufs.h)
 // Calls on one context share its scratch buffers.  The mutex serialises the host side; on the device, work submitted to the
 // SAME stream is ordered anyway, and a call that names a different stream than its predecessor is made to wait for it.
 struct StreamOrder {
@@ -315,8 +313,15 @@ struct ForkGuard {
   bool armed = true; void* keys = nullptr; size_t key_bytes = 0;
   ~ForkGuard() { if (armed) { (void)hipDeviceSynchronize(); if (keys) (void)hipMemset(keys, 0, key_bytes); } }
 };
-typedef std::pair<int, std::pair<const void*, size_t>> BufArg;
-static inline BufArg B(int idx, const void* p, size_t stride) { return {idx, {p, stride}}; }
+// The part of a pairing call a function works on.  A call owns items [0, n) of the context's per-item scratch (F, N, NI, T[], L and the compressed-squaring scratch KS, KD,
+// Kflag, Klist); a function given a Window and a count uses items [first, first + count) of those arrays and nothing else of them, and every other pointer it is given -- the
+// caller's points and outputs, f_raw, in / out -- is bound as it stands: the caller has already moved it to the part's first item.  The default is the whole call.  Offsets, not
+// pointers: ensure_scratch / ensure_expc_scratch may still allocate after a Window was made.
+struct Window {
+  size_t first = 0;      // first item of the part
+  int half = 0;          // 0 or 1: which redo counter of the compressed-squaring form (Kcount[half]) the part uses
+  bool beside = false;   // another part of the same call runs beside this one on a second stream: their launches fill each other's tails, so the final exponentiation's middle is NOT chained
+};
 // ---- host-buffer wrappers ------------------------------------------------------------------------------------
 // The pipelines that pack all their inputs into ONE page-locked block, send it as one copy and read one block back do so through Staged (staging.h).  The per-array wrappers
 // use HostIO: staging buffers on the device for one host-buffer call.  Round 5: taken from a pool the context keeps (best fit among the free blocks of at most four times the size; a miss
@@ -379,13 +384,12 @@ void free_program(DevProgram& d);
 bool wide_applies(const nbls_ctx* ctx, const DevProgram& d, int id, size_t n);
 hipEvent_t timing_event(nbls_ctx* ctx);
 void aot_seg(AotSeg& g, const DevProgram& d, const IOBuf* bufs);
-int run_dev(nbls_ctx* ctx, const DevProgram& d, int id, size_t n, std::initializer_list<std::pair<int, std::pair<const void*, size_t>>> bufs, hipStream_t s, const uint32_t* n_dev,
-    const uint32_t* item_index);
-int run(nbls_ctx* ctx, ProgId id, size_t n, std::initializer_list<std::pair<int, std::pair<const void*, size_t>>> bufs, hipStream_t s, const uint32_t* n_dev = nullptr,
-    const uint32_t* item_index = nullptr);
-int run_inv(nbls_ctx* ctx, size_t n, hipStream_t s);
+void kernel_args(KernelArgs& ka, const nbls_ctx* ctx, const DevProgram& d, size_t n);   // everything of a launch that comes from the program; buffers: bind_bufs (bufs.h)
+int run_dev(nbls_ctx* ctx, const DevProgram& d, int id, size_t n, const BufList& bufs, hipStream_t s, const uint32_t* n_dev, const uint32_t* item_index);
+int run(nbls_ctx* ctx, ProgId id, size_t n, const BufList& bufs, hipStream_t s, const uint32_t* n_dev = nullptr, const uint32_t* item_index = nullptr);
+int run_inv(nbls_ctx* ctx, size_t n, const void* in, void* out, hipStream_t s);   // run_inv_buf, booked in the timing slot of the inversion kernel (P_COUNT)
 bool chains_enabled();
-int run_chain(nbls_ctx* ctx, size_t n, const ChainLink* links, size_t count, hipStream_t s);   // links: a named array (the buffer lists of a copied ChainLink dangle)
+int run_chain(nbls_ctx* ctx, size_t n, const ChainLink* links, size_t count, hipStream_t s);
 int ensure_scratch(nbls_ctx* ctx, size_t n);
 int ensure_expc_scratch(nbls_ctx* ctx);
 int ensure_io(nbls_ctx* ctx, size_t n);
@@ -403,10 +407,10 @@ int run_inv_buf(nbls_ctx* ctx, size_t n, const void* in, void* out, hipStream_t 
 ProgId ls_variant(nbls_ctx* ctx, ProgId id, size_t n);
 ProgId pt_ls2_variant(nbls_ctx* ctx, ProgId id, size_t n);
 int reduce_product(nbls_ctx* ctx, size_t n, uint8_t** result, hipStream_t s);
-int expx(nbls_ctx* ctx, size_t n, uint8_t* in, uint8_t* out, hipStream_t s);
-int final_exp_pipeline(nbls_ctx* ctx, size_t n, uint8_t* f_raw, void* d_out, hipStream_t s);
-int finish_single(nbls_ctx* ctx, uint8_t* f_raw, int final_exp, void* d_out, hipStream_t s);
-int pairing_core(nbls_ctx* ctx, size_t n, const void* d_g1, const void* d_g2, int with_final_exp, void* d_out, hipStream_t s, bool two_programs);
+int expx(nbls_ctx* ctx, const Window& w, size_t n, uint8_t* in, uint8_t* out, hipStream_t s);
+int final_exp_pipeline(nbls_ctx* ctx, const Window& w, size_t n, uint8_t* f_raw, void* d_out, hipStream_t s);
+int finish_single(nbls_ctx* ctx, const Window& w, uint8_t* f_raw, int final_exp, void* d_out, hipStream_t s);
+int pairing_core(nbls_ctx* ctx, const Window& w, size_t n, const void* d_g1, const void* d_g2, int with_final_exp, void* d_out, hipStream_t s, bool two_programs);
 int lines_acc(nbls_ctx* ctx, size_t c, const uint8_t* g1, const uint8_t* g2, uint8_t* L, size_t GR, uint8_t* acc_out, size_t h, hipStream_t s);
 int miller_values(nbls_ctx* ctx, size_t n, const void* d_g1, const void* d_g2, size_t* m_out, hipStream_t s);
 int acc_prepared(nbls_ctx* ctx, size_t n, const void* d_g1, const void* d_tables, size_t table_stride, hipStream_t s);

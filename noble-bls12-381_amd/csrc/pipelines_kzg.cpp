@@ -150,7 +150,7 @@ static int kzg_pipeline(nbls_ctx* ctx, const KzgIn& in, int* all_ok, int8_t* sta
     return r;
   LAUNCHCHK(nbls_kzg_fix_zero_launch(2, BK + 1, ctx->gen_g1, PT2, s));
   uint8_t* res = ctx->F;
-  if ((r = run(ctx, P_ACC_Q, 2, {B(0, PT2, 96), B(3, TB, LINE_BYTES), B(5, ctx->F, F12)}, s)) || (r = reduce_product(ctx, 2, &res, s)) || (r = finish_single(ctx, res, 1, RES, s))) return r;
+  if ((r = run(ctx, P_ACC_Q, 2, {B(0, PT2, 96), B(3, TB, LINE_BYTES), B(5, ctx->F, F12)}, s)) || (r = reduce_product(ctx, 2, &res, s)) || (r = finish_single(ctx, Window(), res, 1, RES, s))) return r;
   LAUNCHCHK(nbls_rlc_is_one_launch(1, RES, BK, s));
   if ((r = io.fetch(BK, back, &got))) return r;
   if (got[3] != 0) return NBLS_EDECODE;   // [tau]G2 does not decode, or is the zero point
@@ -188,7 +188,7 @@ static int kzg_pipeline(nbls_ctx* ctx, const KzgIn& in, int* all_ok, int8_t* sta
   // millerLoop(pi_i, [tau]G2) * millerLoop(X_i, -G2): the two shared tables (table_stride = 0), one batched final exponentiation, compared with one on the device
   if ((r = run(ctx, P_ACC_Q, n, {B(0, AFF + n * 96, 96), B(3, TB, 0), B(5, ctx->F, F12)}, s)) || (r = run(ctx, P_ACC_Q, n, {B(0, X, 96), B(3, TB + LINE_BYTES, 0), B(5, ctx->F + n * F12, F12)}, s)) ||
       (r = run(ctx, P_MUL2S, n, {B(3, ctx->F, F12), B(4, ctx->F + n * F12, F12), B(5, ctx->F, F12)}, s)) || (r = run(ctx, P_NORM_RAW, n, {B(3, ctx->F, F12), B(4, ctx->N, RAW)}, s)) ||
-      (r = final_exp_pipeline(ctx, n, ctx->F, E, s)))
+      (r = final_exp_pipeline(ctx, Window(), n, ctx->F, E, s)))
     return r;
   LAUNCHCHK(nbls_rlc_is_one_launch((unsigned)n, E, V, s));
   LAUNCHCHK(nbls_kzg_item_status_launch((unsigned)n, PRE, DST, XZ, V, FS, s));

@@ -166,7 +166,7 @@ int verify_multiple_pipeline(nbls_ctx* ctx, const MultiVerifyIn& in, int* all_ok
   HIPCHK(hipMemcpyAsync(RPK + nh * 96, ctx->neg_g1, 96, hipMemcpyDeviceToDevice, s));   // PointG1.BASE.negate()
   size_t m = 0;
   uint8_t* res = ctx->F;
-  if ((r = miller_values(ctx, nh + 1, RPK, H, &m, s)) || (r = reduce_product(ctx, m, &res, s)) || (r = finish_single(ctx, res, 1, O, s))) return r;
+  if ((r = miller_values(ctx, nh + 1, RPK, H, &m, s)) || (r = reduce_product(ctx, m, &res, s)) || (r = finish_single(ctx, Window(), res, 1, O, s))) return r;
   if ((r = io.fetch(O, back, &got))) return r;   // synchronised: both side streams were joined into s
   std::vector<uint8_t> rb(got, got + back);      // (the per-set pass reads back through the same block)
   uint32_t bad = 0, gzero = 0; memcpy(&bad, rb.data() + o_bad, 4);
@@ -188,7 +188,7 @@ int verify_multiple_pipeline(nbls_ctx* ctx, const MultiVerifyIn& in, int* all_ok
   uint8_t *G1x = X, *G2x = G1x + n * 192, *E = G2x + n * 384, *V = E + n * 576;
   LAUNCHCHK(mg ? nbls_grp_interleave_launch((unsigned)n, c + o_idx, PK, ctx->neg_g1, H, SG, G1x, G2x, s) : nbls_rlc_interleave_launch((unsigned)n, PK, ctx->neg_g1, H, SG, G1x, G2x, s));
   if ((r = run(ctx, P_MILLER_RAW2, n, {B(0, G1x, 192), B(1, G2x, 384), B(3, ctx->F, F12)}, s)) || (r = run(ctx, P_NORM_RAW, n, {B(3, ctx->F, F12), B(4, ctx->N, RAW)}, s)) ||
-      (r = final_exp_pipeline(ctx, n, ctx->F, E, s)))
+      (r = final_exp_pipeline(ctx, Window(), n, ctx->F, E, s)))
     return r;
   LAUNCHCHK(nbls_rlc_is_one_launch((unsigned)n, E, V, s));
   if ((r = read_back(ctx, s, V, n, &got))) return r;

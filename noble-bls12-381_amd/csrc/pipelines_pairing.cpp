@@ -25,26 +25,28 @@ int reduce_product(nbls_ctx* ctx, size_t n, uint8_t** result, hipStream_t s) {
 // compressed form that cannot multiply.  Kept because it is correct on every input and answers the question whether it pays; the
 // decompression divides by g2: an item with a vanishing g2 (the unit element, or a crafted
 // input) is flagged by DEC_B and recomputed by the plain program over an index list kept on the device, so the result is the reference's for every input.
-int expx(nbls_ctx* ctx, size_t n, uint8_t* in, uint8_t* out, hipStream_t s) {
+int expx(nbls_ctx* ctx, const Window& w, size_t n, uint8_t* in, uint8_t* out, hipStream_t s) {
   int r;
   if (n < ctx->expc_min) return run(ctx, ls_variant(ctx, P_EXPX, n), n, {B(3, in, F12), B(5, out, F12)}, s);
   const size_t KSB = (size_t)EXPC_SQ_ELEMS * RAW, KDB = (size_t)EXPC_DEC_ELEMS * RAW;
   if ((r = ensure_expc_scratch(ctx))) return r;
-  if ((r = run(ctx, P_EXPC_SQ, n, {B(3, in, F12), B(5, ctx->KS, KSB)}, s))) return r;
-  if ((r = run(ctx, P_EXPC_DEC_A, n, {B(3, ctx->KS, KSB), B(4, ctx->N, RAW), B(5, ctx->KD, KDB)}, s))) return r;
-  if ((r = run_inv(ctx, n, s))) return r;                 // N / NI are free once FE_EASY has run
-  if ((r = run(ctx, P_EXPC_DEC_B, n, {B(3, ctx->KS, KSB), B(4, ctx->NI, RAW), B(6, ctx->KD, KDB), B(5, out, F12), B(7, ctx->Kflag, 1)}, s))) return r;
-  uint32_t* count = ctx->Kcount + (ctx->ioff ? 1 : 0);    // the two halves of a split call run concurrently
-  uint32_t* list = ctx->Klist + ctx->ioff;
-  LAUNCHCHK(nbls_flag_compact_launch((unsigned)n, ctx->Kflag + ctx->ioff, list, count, s));
+  uint8_t *KS = ctx->KS + w.first * KSB, *KD = ctx->KD + w.first * KDB, *N = ctx->N + w.first * RAW, *NI = ctx->NI + w.first * RAW, *flag = ctx->Kflag + w.first;
+  if ((r = run(ctx, P_EXPC_SQ, n, {B(3, in, F12), B(5, KS, KSB)}, s))) return r;
+  if ((r = run(ctx, P_EXPC_DEC_A, n, {B(3, KS, KSB), B(4, N, RAW), B(5, KD, KDB)}, s))) return r;
+  if ((r = run_inv(ctx, n, N, NI, s))) return r;          // N / NI are free once FE_EASY has run
+  if ((r = run(ctx, P_EXPC_DEC_B, n, {B(3, KS, KSB), B(4, NI, RAW), B(6, KD, KDB), B(5, out, F12), B(7, flag, 1)}, s))) return r;
+  uint32_t* count = ctx->Kcount + w.half;                 // the two halves of a split call run concurrently
+  uint32_t* list = ctx->Klist + w.first;
+  LAUNCHCHK(nbls_flag_compact_launch((unsigned)n, flag, list, count, s));
   return run(ctx, P_EXPX, n, {B(3, in, F12), B(5, out, F12)}, s, count, list);   // workgroups beyond the listed items exit at once
 }
-// n raw Fp12 in `f_raw` (norms already in ctx->N) -> finalExponentiate -> wire bytes at d_out (math.ts:856-874)
-int final_exp_pipeline(nbls_ctx* ctx, size_t n, uint8_t* f_raw, void* d_out, hipStream_t s) {
+// n raw Fp12 in `f_raw`, their norms in the window's items of ctx->N -> finalExponentiate -> wire bytes at d_out (math.ts:856-874); scratch: the window's items of NI and T[]
+int final_exp_pipeline(nbls_ctx* ctx, const Window& w, size_t n, uint8_t* f_raw, void* d_out, hipStream_t s) {
   int r;
-  uint8_t** T = ctx->T;
-  if ((r = run_inv(ctx, n, s))) return r;
-  if ((r = run(ctx, P_FE_EASY, n, {B(3, f_raw, F12), B(4, ctx->NI, RAW), B(5, T[0], F12)}, s))) return r;
+  uint8_t *N = ctx->N + w.first * RAW, *NI = ctx->NI + w.first * RAW, *T[7];
+  for (int k = 0; k < 7; k++) T[k] = ctx->T[k] + w.first * F12;
+  if ((r = run_inv(ctx, n, N, NI, s))) return r;
+  if ((r = run(ctx, P_FE_EASY, n, {B(3, f_raw, F12), B(4, NI, RAW), B(5, T[0], F12)}, s))) return r;
   // the seven launches between the easy part and the final product (math.ts:862-867): t2 = t1^x, t3 = conj(t1^2) t2, t4 = t3^x, t5 = t4^x, t6' = t5^x, t6 = t6' t2^2, t7 = t6^x
   const ChainLink mid[7] = {{P_EXPX, {B(3, T[0], F12), B(5, T[1], F12)}},                          // t2
                             {P_FE_MID1, {B(3, T[0], F12), B(5, T[1], F12), B(6, T[2], F12)}},      // t3
@@ -53,20 +55,19 @@ int final_exp_pipeline(nbls_ctx* ctx, size_t n, uint8_t* f_raw, void* d_out, hip
                             {P_EXPX, {B(3, T[4], F12), B(5, T[6], F12)}},                          // t6' (parked in T7's buffer)
                             {P_FE_MID2, {B(3, T[6], F12), B(5, T[1], F12), B(6, T[5], F12)}},      // t6
                             {P_EXPX, {B(3, T[5], F12), B(5, T[6], F12)}}};                         // t7
-  if (n < ctx->expc_min && n < ctx->chain_max && !ctx->in_halves && ls_variant(ctx, P_EXPX, n) == P_EXPX && !wide_applies(ctx, ctx->prog[P_EXPX], (int)P_EXPX, n)) {
+  if (n < ctx->expc_min && n < ctx->chain_max && !w.beside && ls_variant(ctx, P_EXPX, n) == P_EXPX && !wide_applies(ctx, ctx->prog[P_EXPX], (int)P_EXPX, n)) {
     if ((r = run_chain(ctx, n, mid, 7, s))) return r;      // as one chain
   } else for (const ChainLink& l : mid) {                  // launch by launch; the exponentiations through expx(), which has forms of its own (rows of P_EXPX are {in, out})
-    const BufArg* b = l.bufs.begin();
-    if ((r = l.id == P_EXPX ? expx(ctx, n, (uint8_t*)b[0].second.first, (uint8_t*)b[1].second.first, s) : run(ctx, l.id, n, l.bufs, s))) return r;
+    if ((r = l.id == P_EXPX ? expx(ctx, w, n, (uint8_t*)l.bufs.a[0].ptr, (uint8_t*)l.bufs.a[1].ptr, s) : run(ctx, l.id, n, l.bufs, s))) return r;
   }
   return run(ctx, P_FE_FINAL, n, {B(0, T[0], F12), B(1, T[1], F12), B(2, T[2], F12), B(3, T[3], F12), B(4, T[4], F12), B(5, T[5], F12), B(6, T[6], F12), B(7, d_out, 576)}, s);
 }
 // one raw Fp12 -> final exponentiation (or plain encoding) -> wire bytes on device
-int finish_single(nbls_ctx* ctx, uint8_t* f_raw, int final_exp, void* d_out, hipStream_t s) {
+int finish_single(nbls_ctx* ctx, const Window& w, uint8_t* f_raw, int final_exp, void* d_out, hipStream_t s) {
   int r;
   if (!final_exp) return run(ctx, P_RAW_TO_BYTES, 1, {B(3, f_raw, F12), B(2, d_out, 576)}, s);
-  if ((r = run(ctx, P_NORM_RAW, 1, {B(3, f_raw, F12), B(4, ctx->N, RAW)}, s))) return r;
-  return final_exp_pipeline(ctx, 1, f_raw, d_out, s);
+  if ((r = run(ctx, P_NORM_RAW, 1, {B(3, f_raw, F12), B(4, ctx->N + w.first * RAW, RAW)}, s))) return r;
+  return final_exp_pipeline(ctx, w, 1, f_raw, d_out, s);
 }
 // the product of the m raw Fp12 values in ctx->F (m = 0: ONE) -> finish_single
 static int finish_product(nbls_ctx* ctx, size_t m, int final_exp, void* d_out, hipStream_t s) {
@@ -74,7 +75,7 @@ static int finish_product(nbls_ctx* ctx, size_t m, int final_exp, void* d_out, h
   uint8_t* res = ctx->F;
   if (m == 0) HIPCHK(hipMemcpyAsync(ctx->F, ctx->one12, F12, hipMemcpyDeviceToDevice, s));
   else if ((r = reduce_product(ctx, m, &res, s))) return r;
-  return finish_single(ctx, res, final_exp, d_out, s);
+  return finish_single(ctx, Window(), res, final_exp, d_out, s);
 }
 
 EXPORT int nbls_pairing_batch_dev(nbls_ctx* ctx, size_t n, const void* d_g1, const void* d_g2, int with_final_exp, void* d_out, void* stream) {
@@ -83,8 +84,8 @@ EXPORT int nbls_pairing_batch_dev(nbls_ctx* ctx, size_t n, const void* d_g1, con
   DEV_ENTER(ctx, stream);
   // A batch of ctx->halves_min pairs or more (16,384; 8192 until the end of round 6, nbls_internal.h) runs as two halves on two streams: every launch of a dependent chain ends in a
   // partly filled round of wavefronts (EXPX at 65,536 pairs: 4.65 rounds of 2,816 resident wavefronts), and the tail of one half is filled by the other (65,536 pairs: 27.4 -> 25.9 ms).
-  // Both halves use the caller's scratch through an item offset (ctx->ioff, applied by run() to every per-item buffer) and the two-program Miller loop (what counts with work in flight
-  // is the instruction count).
+  // The halves share the context's scratch: each is told its Window (nbls_internal.h) -- the second one starts at item h of every per-item array -- and is handed the caller's
+  // points and outputs from its own first item on.  Both take the two-program Miller loop (what counts with work in flight is the instruction count).
   // (measured in round 5, when the threshold was 8192: 8192 5.08 -> 4.69 ms, 16,384 8.53 -> 7.73, 24,576 11.96 -> 10.33, 32,768 14.96 -> 13.64, 65,536 27.5 -> 26.0.  The exception then
   // was a batch that fills the chip exactly three wavefronts deep in ONE round with the fused program, 12,288 pairs: 6.04 ms against 6.39; that window, 10,753 .. 12,288 pairs, lies
   // below today's threshold and has no case of its own any more)
@@ -100,18 +101,20 @@ EXPORT int nbls_pairing_batch_dev(nbls_ctx* ctx, size_t n, const void* d_g1, con
     if (h > 0 && h < n) {      // (a split that leaves one side empty -- rounding at a small n -- falls through to the single-stream path)
       HIPCHK(hipEventRecord(ctx->ev_half_fork, s)); HIPCHK(hipStreamWaitEvent(ctx->half_stream, ctx->ev_half_fork, 0));
       ForkGuard fork_guard;
-      ctx->in_halves = true;     // (round 4 compared each HALF with chain_max: calls of 8192..16383 pairs ran their halves chained, the configuration measured as slower)
-      r = pairing_core(ctx, h, d_g1, d_g2, with_final_exp, d_out, s, true);
-      if (!r) { ctx->ioff = h; r = pairing_core(ctx, n - h, d_g1, d_g2, with_final_exp, d_out, ctx->half_stream, true); ctx->ioff = 0; }
-      ctx->in_halves = false;
+      // beside: neither half chains the middle of its final exponentiation (round 4 compared each HALF with chain_max: calls of 8192..16383 pairs ran their halves chained, the
+      // configuration measured as slower)
+      Window first, second; first.beside = second.beside = true; second.first = h; second.half = 1;
+      r = pairing_core(ctx, first, h, d_g1, d_g2, with_final_exp, d_out, s, true);
+      if (!r) r = pairing_core(ctx, second, n - h, (const uint8_t*)d_g1 + h * 96, (const uint8_t*)d_g2 + h * 192, with_final_exp, (uint8_t*)d_out + h * 576, ctx->half_stream, true);
       HIPCHK(hipEventRecord(ctx->ev_half_join, ctx->half_stream)); HIPCHK(hipStreamWaitEvent(s, ctx->ev_half_join, 0));
       if (!r) fork_guard.armed = false;      // joined into s; a failed half leaves work in flight on both streams: the guard waits for it
       return r;
     }
   }
-  return pairing_core(ctx, n, d_g1, d_g2, with_final_exp, d_out, s, false);
+  return pairing_core(ctx, Window(), n, d_g1, d_g2, with_final_exp, d_out, s, false);
 }
-int pairing_core(nbls_ctx* ctx, size_t n, const void* d_g1, const void* d_g2, int with_final_exp, void* d_out, hipStream_t s, bool two_programs) {
+// n pairs -> n pairings (or Miller values) at d_out; scratch: the window's items of ctx->L, F and N, then final_exp_pipeline's
+int pairing_core(nbls_ctx* ctx, const Window& w, size_t n, const void* d_g1, const void* d_g2, int with_final_exp, void* d_out, hipStream_t s, bool two_programs) {
   int r;
   // One program or two?  LINES + ACC execute ~12 % fewer instructions per pairing (no idle lanes in the Fp12 steps, 20 instead of 37 lane-ops
   // per bit in the point chain) but are two dependent chains of 307 + 173 steps where the fused program has 349: a launch that is only a few
@@ -123,8 +126,8 @@ int pairing_core(nbls_ctx* ctx, size_t n, const void* d_g1, const void* d_g2, in
   if (fused) {
     if (!with_final_exp) return run(ctx, ls_variant(ctx, P_MILLER_BYTES, n), n, {B(0, d_g1, 96), B(1, d_g2, 192), B(2, d_out, 576)}, s);
     if ((r = ensure_scratch(ctx, n))) return r;
-    if ((r = run(ctx, ls_variant(ctx, P_MILLER_FE, n), n, {B(0, d_g1, 96), B(1, d_g2, 192), B(3, ctx->F, F12), B(4, ctx->N, RAW)}, s))) return r;
-    return final_exp_pipeline(ctx, n, ctx->F, d_out, s);
+    if ((r = run(ctx, ls_variant(ctx, P_MILLER_FE, n), n, {B(0, d_g1, 96), B(1, d_g2, 192), B(3, ctx->F + w.first * F12, F12), B(4, ctx->N + w.first * RAW, RAW)}, s))) return r;
+    return final_exp_pipeline(ctx, w, n, ctx->F + w.first * F12, d_out, s);
   }
   // calcPairingPrecomputes + millerLoop (math.ts:1331-1388) as two programs: line tables through HBM (LINE_BYTES per pair)
   if ((r = ensure_lines(ctx, n))) return r;
@@ -134,18 +137,19 @@ int pairing_core(nbls_ctx* ctx, size_t n, const void* d_g1, const void* d_g2, in
   // the representatives.  NBLS_LINES_FE=0 forces LINES_PQ everywhere (A/B runs; programs.h lines_fe_enabled).  The launch is booked in LINES_PQ's timing slot: the same stage of the call.
   const bool lines_fe = with_final_exp && lines_fe_enabled();
   if (lines_fe && (r = upload_extra(ctx, XP_LINES_FE))) return r;
+  uint8_t *L = ctx->L + w.first * LINE_BYTES, *F = with_final_exp ? ctx->F + w.first * F12 : nullptr, *N = with_final_exp ? ctx->N + w.first * RAW : nullptr;
   for (size_t o = 0; o < n; o += LINES_CHUNK) {
     const size_t c = n - o < LINES_CHUNK ? n - o : LINES_CHUNK;
     const uint8_t *g1 = (const uint8_t*)d_g1 + o * 96, *g2 = (const uint8_t*)d_g2 + o * 192;
-    if (lines_fe) r = run_dev(ctx, ctx->extra[XP_LINES_FE], (int)P_LINES_PQ, c, {B(0, g1, 96), B(1, g2, 192), B(3, ctx->L, LINE_BYTES)}, s, nullptr, nullptr);
-    else r = run(ctx, P_LINES_PQ, c, {B(0, g1, 96), B(1, g2, 192), B(3, ctx->L, LINE_BYTES)}, s);
+    if (lines_fe) r = run_dev(ctx, ctx->extra[XP_LINES_FE], (int)P_LINES_PQ, c, {B(0, g1, 96), B(1, g2, 192), B(3, L, LINE_BYTES)}, s, nullptr, nullptr);
+    else r = run(ctx, P_LINES_PQ, c, {B(0, g1, 96), B(1, g2, 192), B(3, L, LINE_BYTES)}, s);
     if (r) return r;
-    if (!with_final_exp) r = run(ctx, P_ACC_BYTES, c, {B(3, ctx->L, LINE_BYTES), B(2, (uint8_t*)d_out + o * 576, 576)}, s);
-    else r = run(ctx, P_ACC_FE, c, {B(3, ctx->L, LINE_BYTES), B(5, ctx->F + o * F12, F12), B(4, ctx->N + o * RAW, RAW)}, s);
+    if (!with_final_exp) r = run(ctx, P_ACC_BYTES, c, {B(3, L, LINE_BYTES), B(2, (uint8_t*)d_out + o * 576, 576)}, s);
+    else r = run(ctx, P_ACC_FE, c, {B(3, L, LINE_BYTES), B(5, F + o * F12, F12), B(4, N + o * RAW, RAW)}, s);
     if (r) return r;
   }
   if (!with_final_exp) return NBLS_OK;
-  return final_exp_pipeline(ctx, n, ctx->F, d_out, s);
+  return final_exp_pipeline(ctx, w, n, F, d_out, s);
 }
 
 // Host-buffer staging shared by nbls_pairing_batch and nbls_miller_product: the points go up ONCE (the validity programs read the same device copies the Miller
@@ -272,14 +276,14 @@ int miller_values(nbls_ctx* ctx, size_t n, const void* d_g1, const void* d_g2, s
       // runs as two halves): one pair per item below acc2_min, two below acc4_min, four above; eight no longer pays at any size (profiles/round6_ab_acc_width.txt: 4098 pairs
       // 2.91 -> 2.13 ms, 8192 4.01 -> 2.77, 16,384 4.54 -> 3.79, 49,152 8.59 -> 7.85, 2^18 32.2 -> 30.9 ms)
       static const size_t acc2_min = (size_t)env_long("NBLS_ACC2_MIN", 6144), acc4_min = (size_t)env_long("NBLS_ACC4_MIN", 28672);
-      const size_t chunk = n < LINES_CHUNK ? n : LINES_CHUNK, part = (chunk >= ctx->halves_min && ctx->ioff == 0) ? chunk / 2 : chunk;
+      const size_t chunk = n < LINES_CHUNK ? n : LINES_CHUNK, part = chunk >= ctx->halves_min ? chunk / 2 : chunk;
       const size_t GR = n >= ctx->acc8_min ? 8 : part >= acc4_min ? 4 : part >= acc2_min ? 2 : 1;
       if ((r = ensure_lines(ctx, n + GR - 1))) return r;
       m = 0;
       for (size_t o = 0; o < n; o += LINES_CHUNK) {   // LINES_CHUNK is a multiple of eight: a chunk boundary never splits a group
         const size_t c = n - o < LINES_CHUNK ? n - o : LINES_CHUNK;
         // a large chunk runs as two halves (whole groups) on two streams, like nbls_pairing_batch_dev: the tail of LINES / ACC of one half under the other
-        const size_t h = (c >= ctx->halves_min && ctx->ioff == 0) ? ((c / 2 + GR - 1) & ~(GR - 1)) : c;
+        const size_t h = c >= ctx->halves_min ? ((c / 2 + GR - 1) & ~(GR - 1)) : c;
         if ((r = lines_acc(ctx, c, (const uint8_t*)d_g1 + o * 96, (const uint8_t*)d_g2 + o * 192, ctx->L, GR, ctx->F + m * F12, h, s))) return r;
         m += (c + GR - 1) / GR;
       }
@@ -327,7 +331,7 @@ EXPORT int nbls_final_exp_batch_dev(nbls_ctx* ctx, size_t n, const void* d_in, v
   int r;
   if ((r = ensure_scratch(ctx, n))) return r;
   if ((r = run(ctx, P_NORM_BYTES, n, {B(2, d_in, 576), B(3, ctx->F, F12), B(4, ctx->N, RAW)}, s))) return r;
-  return final_exp_pipeline(ctx, n, ctx->F, d_out, s);
+  return final_exp_pipeline(ctx, Window(), n, ctx->F, d_out, s);
 }
 
 EXPORT int nbls_final_exp_batch(nbls_ctx* ctx, size_t n, const uint8_t* in, uint8_t* out) {
@@ -373,7 +377,7 @@ EXPORT int nbls_tower_op_batch(nbls_ctx* ctx, int field, int op, int param, size
     return run_dev(ctx, dp, -1, n, {B(0, da, esz), B(1, db, bsz), B(2, dc, csz), B(3, dd, dsz), B(4, ctx->N, RAW), B(5, ctx->NI, RAW), B(7, dout, esz)}, s, nullptr, nullptr);
   };
   if ((r = launch(0))) return r;
-  if (op == 5 && ((r = run_inv(ctx, n, s)) || (r = launch(1)))) return r;   // NBLS_TOP_INV
+  if (op == 5 && ((r = run_inv(ctx, n, ctx->N, ctx->NI, s)) || (r = launch(1)))) return r;   // NBLS_TOP_INV
   HIPCHK(hipMemcpyAsync(out, dout, n * esz, hipMemcpyDeviceToHost, s)); HIPCHK(hipStreamSynchronize(s));
   return NBLS_OK;
 }
@@ -424,7 +428,7 @@ EXPORT int nbls_pairing_prepared_dev(nbls_ctx* ctx, size_t n, const void* d_g1, 
   int r = acc_prepared(ctx, n, d_g1, d_tables, table_stride, s); if (r) return r;
   if (!with_final_exp) return run(ctx, P_RAW_TO_BYTES, n, {B(3, ctx->F, F12), B(2, d_out, 576)}, s);
   if ((r = run(ctx, P_NORM_RAW, n, {B(3, ctx->F, F12), B(4, ctx->N, RAW)}, s))) return r;
-  return final_exp_pipeline(ctx, n, ctx->F, d_out, s);
+  return final_exp_pipeline(ctx, Window(), n, ctx->F, d_out, s);
 }
 EXPORT int nbls_miller_product_prepared_dev(nbls_ctx* ctx, size_t n, const void* d_g1, const void* d_tables, size_t table_stride, int final_exp, void* d_out, void* stream) {
   if (!ctx || !d_out || (n && (!d_g1 || !d_tables))) return NBLS_EINVAL;

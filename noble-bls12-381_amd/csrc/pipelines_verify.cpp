@@ -159,7 +159,7 @@ int verify_pipeline(nbls_ctx* ctx, size_t n, const VerifyIn& in, int final_exp, 
   }
   uint8_t* res = ctx->F;
   if ((r = reduce_product(ctx, m_off, &res, s))) return r;
-  if ((r = finish_single(ctx, res, final_exp, final_exp ? (void*)O : d_out, s))) return r;
+  if ((r = finish_single(ctx, Window(), res, final_exp, final_exp ? (void*)O : d_out, s))) return r;
   // the result and the statuses lie behind one another (O | ST | bad-offsets word): ONE copy into page-locked memory (round 6: two copies into pageable memory before)
   const size_t st_bytes = ((np + 3) & ~(size_t)3) + 4, back = 576 + st_bytes;
   const uint8_t* got;

@@ -67,25 +67,39 @@ hipEvent_t timing_event(nbls_ctx* ctx) {
   if (!ctx->ev_pool.empty()) { hipEvent_t e = ctx->ev_pool.back(); ctx->ev_pool.pop_back(); return e; }
   hipEvent_t e = nullptr; hipEventCreate(&e); return e;
 }
+// The timing bracket of one launch, when the context's timing is on: two events from the pool recorded on `s` around the scope, booked in timing slot `id` (a ProgId; P_COUNT: the
+// inversion kernel) or handed back to the pool when id < 0 (programs outside the registry).
+struct Timed {
+  nbls_ctx* ctx; int id; hipStream_t s; hipEvent_t e0 = nullptr, e1 = nullptr;
+  Timed(nbls_ctx* c, int slot, hipStream_t st) : ctx(c), id(slot), s(st) { if (ctx->timing) { e0 = timing_event(ctx); e1 = timing_event(ctx); hipEventRecord(e0, s); } }
+  ~Timed() {
+    if (!e0) return;
+    hipEventRecord(e1, s);
+    if (id >= 0) ctx->tev.push_back({id, {e0, e1}}); else { ctx->ev_pool.push_back(e0); ctx->ev_pool.push_back(e1); }
+  }
+};
 
 void aot_seg(AotSeg& g, const DevProgram& d, const IOBuf* bufs) {
   g.steps = d.aot_steps; g.descs = d.aot_descs; g.consts = d.consts;
   g.nsteps = (u32)d.p->steps.size(); g.nconst = d.p->nconst; g.inst_bytes = d.p->inst_bytes(); g.slot_bytes = d.p->slot_bytes; g.shared_consts = d.p->shared_consts ? 1u : 0u;
   for (int k = 0; k < MAX_BUFS; k++) g.bufs[k] = bufs[k];
 }
-int run(nbls_ctx* ctx, ProgId id, size_t n, std::initializer_list<std::pair<int, std::pair<const void*, size_t>>> bufs, hipStream_t s, const uint32_t* n_dev, const uint32_t* item_index) {
+void kernel_args(KernelArgs& ka, const nbls_ctx* ctx, const DevProgram& d, size_t n) {
+  memset(&ka, 0, sizeof ka);
+  ka.steps = d.steps; ka.descs = d.descs; ka.consts = d.consts; ka.qp_table = ctx->qp_table;
+  ka.nsteps = (u32)d.p->steps.size(); ka.nconst = d.p->nconst; ka.W = d.p->W; ka.G = d.p->G; ka.slot_bytes = d.p->slot_bytes; ka.inst_bytes = d.p->inst_bytes();
+  ka.shared_consts = d.p->shared_consts ? 1u : 0u; ka.lsplit = d.p->lsplit; ka.n_items = (u32)n;
+}
+int run(nbls_ctx* ctx, ProgId id, size_t n, const BufList& bufs, hipStream_t s, const uint32_t* n_dev, const uint32_t* item_index) {
   int r = upload(ctx, id); if (r) return r;
   return run_dev(ctx, ctx->prog[id], (int)id, n, bufs, s, n_dev, item_index);
 }
-// id: the timing slot of the launch (a ProgId), or -1 for programs outside the registry (single tower operations)
-int run_dev(nbls_ctx* ctx, const DevProgram& d, int id, size_t n, std::initializer_list<std::pair<int, std::pair<const void*, size_t>>> bufs, hipStream_t s, const uint32_t* n_dev,
-    const uint32_t* item_index) {
-  KernelArgs ka; memset(&ka, 0, sizeof ka);
+// id: the timing slot of the launch (a ProgId), or -1 for programs outside the registry (single tower operations).  The buffers are bound as they are given.
+int run_dev(nbls_ctx* ctx, const DevProgram& d, int id, size_t n, const BufList& bufs, hipStream_t s, const uint32_t* n_dev, const uint32_t* item_index) {
+  KernelArgs ka; kernel_args(ka, ctx, d, n);
   d.launches++;
-  ka.steps = d.steps; ka.descs = d.descs; ka.consts = d.consts; ka.qp_table = ctx->qp_table;
-  ka.nsteps = (u32)d.p->steps.size(); ka.nconst = d.p->nconst; ka.W = d.p->W; ka.G = d.p->G; ka.slot_bytes = d.p->slot_bytes; ka.inst_bytes = d.p->inst_bytes();
-  ka.shared_consts = d.p->shared_consts ? 1u : 0u; ka.lsplit = d.p->lsplit; ka.n_items = (u32)n; ka.n_items_dev = n_dev; ka.item_index = item_index;
-  for (auto& b : bufs) { ka.bufs[b.first].ptr = (uint8_t*)b.second.first + ctx->ioff * b.second.second; ka.bufs[b.first].stride = b.second.second; }   // ioff: the second half of a split call
+  ka.n_items_dev = n_dev; ka.item_index = item_index;
+  if (!bind_bufs(ka.bufs, bufs)) { if (checked_mode()) fprintf(stderr, "nbls (checked): %s: a buffer index outside [0, %d)\n", d.p->name.c_str(), MAX_BUFS); return NBLS_EINVAL; }
   if (checked_mode()) {
     for (int k = 0; k < MAX_BUFS; k++) {
       const u32 ext = d.p->buf_extent[k];
@@ -107,30 +121,30 @@ int run_dev(nbls_ctx* ctx, const DevProgram& d, int id, size_t n, std::initializ
       } else (void)hipGetLastError();
     }
   }
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (ctx->timing) { e0 = timing_event(ctx); e1 = timing_event(ctx); hipEventRecord(e0, s); }
   int e;
-  if (wide_applies(ctx, d, id, n)) e = nbls_vm_wide_launch(&ka, d.p->inst_base(0) + d.p->inst_bytes(), s);
-  else if (d.aot >= 0) {
-    AotArgs a; memset(&a, 0, sizeof a);
-    aot_seg(a.seg[0], d, ka.bufs);
-    a.nseg = 1; a.W = ka.W; a.G = ka.G; a.n_items = ka.n_items; a.qp_table = ka.qp_table; a.item_index = ka.item_index; a.n_items_dev = ka.n_items_dev;
-    e = nbls_aot_launch(d.aot, &a, d.aot_lds, s);
-  } else e = nbls_vm_launch(&ka, d.p->lds_bytes(), s);
-  if (ctx->timing) { hipEventRecord(e1, s); if (id >= 0) ctx->tev.push_back({id, {e0, e1}}); else { ctx->ev_pool.push_back(e0); ctx->ev_pool.push_back(e1); } }
+  {
+    Timed timed(ctx, id, s);
+    if (wide_applies(ctx, d, id, n)) e = nbls_vm_wide_launch(&ka, d.p->inst_base(0) + d.p->inst_bytes(), s);
+    else if (d.aot >= 0) {
+      AotArgs a; memset(&a, 0, sizeof a);
+      aot_seg(a.seg[0], d, ka.bufs);
+      a.nseg = 1; a.W = ka.W; a.G = ka.G; a.n_items = ka.n_items; a.qp_table = ka.qp_table; a.item_index = ka.item_index; a.n_items_dev = ka.n_items_dev;
+      e = nbls_aot_launch(d.aot, &a, d.aot_lds, s);
+    } else e = nbls_vm_launch(&ka, d.p->lds_bytes(), s);
+  }
   if (e) { ctx->last_hip = e; return NBLS_EHIP; }
   return NBLS_OK;
 }
 // Launches of at most ctx->inv_wide_max elements run the inversion with one limb per lane, four elements per wavefront (fp_inv_wide.h: the same binary GCD, ~25 k instead of ~48 k
 // wave-instructions on the critical path of every single call); above, one element per lane.  NBLS_INV_WIDE_MAX / NBLS_TUNE_INV_WIDE_MAX (0 = never).
-int run_inv(nbls_ctx* ctx, size_t n, hipStream_t s) {
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (ctx->timing) { e0 = timing_event(ctx); e1 = timing_event(ctx); hipEventRecord(e0, s); }
-  const uint8_t* in = ctx->N + ctx->ioff * RAW; uint8_t* out = ctx->NI + ctx->ioff * RAW;
-  int e = n <= ctx->inv_wide_max ? nbls_fp_inv_wide_launch((unsigned)n, in, out, s) : nbls_fp_inv_launch((unsigned)n, in, out, s);
-  if (ctx->timing) { hipEventRecord(e1, s); ctx->tev.push_back({(int)P_COUNT, {e0, e1}}); }
-  if (e) { ctx->last_hip = e; return NBLS_EHIP; }
+int run_inv_buf(nbls_ctx* ctx, size_t n, const void* in, void* out, hipStream_t s) {
+  LAUNCHCHK(n <= ctx->inv_wide_max ? nbls_fp_inv_wide_launch((unsigned)n, in, out, s) : nbls_fp_inv_launch((unsigned)n, in, out, s));
   return NBLS_OK;
+}
+// the inversion of the pairing path and of the tower operations: the same launch, booked (the codec, MSM and hash pipelines call run_inv_buf: theirs are not)
+int run_inv(nbls_ctx* ctx, size_t n, const void* in, void* out, hipStream_t s) {
+  Timed timed(ctx, (int)P_COUNT, s);
+  return run_inv_buf(ctx, n, in, out, s);
 }
 
 // ctx->chain_max: items up to which the middle of the final exponentiation runs as one chain (default 8192, NBLS_CHAIN_MAX / NBLS_TUNE_CHAIN_MAX): measured equal to seven
@@ -152,15 +166,13 @@ int run_chain(nbls_ctx* ctx, size_t n, const ChainLink* links, size_t count, hip
   if (!fuse) { for (const ChainLink* l = links; l < links + count; l++) if ((r = run(ctx, l->id, n, l->bufs, s))) return r; return NBLS_OK; }
   AotArgs a; memset(&a, 0, sizeof a);
   for (const ChainLink* l = links; l < links + count; l++) {
-    IOBuf bufs[MAX_BUFS]; memset(bufs, 0, sizeof bufs);
-    for (auto& b : l->bufs) { bufs[b.first].ptr = (uint8_t*)b.second.first + ctx->ioff * b.second.second; bufs[b.first].stride = b.second.second; }
+    IOBuf bufs[MAX_BUFS];
+    if (!bind_bufs(bufs, l->bufs)) return NBLS_EINVAL;
     aot_seg(a.seg[a.nseg++], ctx->prog[l->id], bufs);
   }
   a.W = W; a.G = G; a.n_items = (u32)n; a.qp_table = ctx->qp_table;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (ctx->timing) { e0 = timing_event(ctx); e1 = timing_event(ctx); hipEventRecord(e0, s); }
-  const int e = nbls_aot_launch(k, &a, lds, s);
-  if (ctx->timing) { hipEventRecord(e1, s); ctx->tev.push_back({(int)links->id, {e0, e1}}); }   // the whole chain is booked on its first program
+  int e;
+  { Timed timed(ctx, (int)links->id, s); e = nbls_aot_launch(k, &a, lds, s); }   // the whole chain is booked on its first program
   if (e) { ctx->last_hip = e; return NBLS_EHIP; }
   return NBLS_OK;
 }
@@ -279,11 +291,6 @@ int run_pow(nbls_ctx* ctx, int which, size_t n, const void* in, void* out, hipSt
   LAUNCHCHK(nbls_fp_pow_launch((unsigned)n, in, out, ctx->nib[which], ctx->nnib[which], scratch, which == 1 ? 8 : which == 2 ? 7 : 0, s));   // Fp2: a^((p^2+7)/16) = b^K a^8, a^((p^2-9)/16) = b^K a^7
   return NBLS_OK;
 }
-int run_inv_buf(nbls_ctx* ctx, size_t n, const void* in, void* out, hipStream_t s) {
-  LAUNCHCHK(n <= ctx->inv_wide_max ? nbls_fp_inv_wide_launch((unsigned)n, in, out, s) : nbls_fp_inv_launch((unsigned)n, in, out, s));
-  return NBLS_OK;
-}
-
 
 EXPORT int nbls_init(int device_id, nbls_ctx** out) {
   if (!out) return NBLS_EINVAL;

@@ -54,12 +54,9 @@ EXPORT int nbls_placement_probe(nbls_ctx* ctx, size_t n, uint64_t* out_blocks) {
   const DevProgram& d = ctx->prog[pid];
   const size_t blocks = (n + d.p->G - 1) / d.p->G;
   uint64_t* dbg = nullptr; HIPCHK(hipMalloc(&dbg, blocks * 40));
-  KernelArgs ka; memset(&ka, 0, sizeof ka);
-  ka.steps = d.steps; ka.descs = d.descs; ka.consts = d.consts; ka.qp_table = ctx->qp_table;
-  ka.nsteps = (u32)d.p->steps.size(); ka.nconst = d.p->nconst; ka.W = d.p->W; ka.G = d.p->G; ka.slot_bytes = d.p->slot_bytes; ka.inst_bytes = d.p->inst_bytes();
-  ka.shared_consts = d.p->shared_consts ? 1u : 0u; ka.lsplit = d.p->lsplit; ka.n_items = (u32)n;
-  ka.bufs[3].ptr = ctx->T[0]; ka.bufs[3].stride = F12; ka.bufs[5].ptr = ctx->T[1]; ka.bufs[5].stride = F12;
-  if (pid == P_MILLER_FE) { ka.bufs[0].ptr = ctx->io_g1; ka.bufs[0].stride = 96; ka.bufs[1].ptr = ctx->io_g2; ka.bufs[1].stride = 192; ka.bufs[4].ptr = ctx->N; ka.bufs[4].stride = RAW; }
+  KernelArgs ka; kernel_args(ka, ctx, d, n);
+  bind_bufs(ka.bufs, pid == P_MILLER_FE ? BufList{B(0, ctx->io_g1, 96), B(1, ctx->io_g2, 192), B(3, ctx->T[0], F12), B(4, ctx->N, RAW), B(5, ctx->T[1], F12)}
+                                        : BufList{B(3, ctx->T[0], F12), B(5, ctx->T[1], F12)});
   ka.hwid_out = dbg;
   HIPCHK(hipMemsetAsync(ctx->T[0], 0, n * F12, ctx->stream));
   int e = nbls_vm_launch(&ka, d.p->lds_bytes(), ctx->stream);

@@ -85,6 +85,18 @@ def test_sanitizer_staging():
         assert (eff, got) == (len(want), want), n
 
 
+@pytest.mark.skipif(subprocess.call(['sh', '-c', 'echo "int main(){}" | g++ -x c++ -fsanitize=address,undefined -o /dev/null - 2>/dev/null']) != 0, reason='no sanitizer runtime')
+def test_sanitizer_bufs():
+    """the buffer lists of the launch path (csrc/bufs.h, tests/c/bufs_test.cpp): chain links returned by value and copied bind the pointers and strides they were written with,
+    an index outside [0, 8) or a ninth entry is refused, entries the list does not name stay {nullptr, 0}"""
+    subprocess.check_call(['make', '-s', '-C', CSRC, '../bufs_test'])
+    env = dict(os.environ, ASAN_OPTIONS='detect_leaks=0')
+    out = subprocess.run([os.path.join(ROOT, 'noble-bls12-381_amd', 'bufs_test')], capture_output=True, text=True, timeout=60, env=env)
+    assert out.returncode == 0, out.stdout + out.stderr
+    assert 'failures 0' in out.stdout and 'links 3 buffers 8' in out.stdout, out.stdout
+    assert 'ERROR: AddressSanitizer' not in out.stderr and 'runtime error' not in out.stderr, out.stderr
+
+
 @pytest.mark.gpu
 def test_checked_engine_library(golden):
     """the golden pairings, a Miller product and a verifyBatch through the checked library in a fresh process (NBLS_LIBRARY selects it)"""

@@ -68,6 +68,41 @@ def test_validation_beside_the_loop_and_in_line(eng, oracle, golden):
         assert eng.miller_product(G1, G2, True, True)[0] == prod[0]      # the context is fine afterwards
 
 
+@pytest.mark.parametrize('n', [130, 1500])
+def test_validated_pairings_in_two_halves(eng, oracle, golden, n):
+    """a validated nbls_pairing_batch that runs as two halves on two streams (forced by NBLS_TUNE_HALVES_MIN = 64): 130 pairs with the validity programs on the side streams beside
+    both halves, 1500 with them in line before the fork.  An invalid G1 point in the first half, an invalid G2 point as the last item of the second, one of each at item 3:
+    statuses and zeroed slots as in the one-stream run and as the oracle's, every other item byte-equal to the unvalidated call."""
+    v1, v2 = golden['validity']['g1'], golden['validity']['g2']
+    bad1 = [hx(v['aff']) for v in v1 if STATUS[v['result']] != 0][:2]; bad2 = [hx(v['aff']) for v in v2 if STATUS[v['result']] != 0][:2]
+    ok1 = [hx(v['aff']) for v in v1 if STATUS[v['result']] == 0 and hx(v['aff']) != bytes(96)][:3]
+    ok2 = [hx(v['aff']) for v in v2 if STATUS[v['result']] == 0 and hx(v['aff']) != bytes(192)][:3]
+    assert bad1 and bad2 and ok1 and ok2
+    P = [ok1[i % len(ok1)] for i in range(n)]; Q = [ok2[(i // 3) % len(ok2)] for i in range(n)]
+    G1, G2 = b''.join(P), b''.join(Q)
+    touched = {n // 2, n - 1, 3}
+    assert n // 2 < (((n * 55) // 100 + 63) & ~63) < n      # n // 2 lies in the first half, n - 1 in the second
+    P[n // 2] = bad1[0]; Q[n - 1] = bad2[0]; P[3] = bad1[-1]; Q[3] = bad2[-1]
+    B1, B2 = b''.join(P), b''.join(Q)
+    try:
+        eng.set_halves_min(0)
+        one_out, one_st = eng.pairing_batch(B1, B2, True, True)
+        eng.set_halves_min(64)
+        out, st = eng.pairing_batch(B1, B2, True, True)
+        plain = eng.pairing_batch(G1, G2, True, False)[0]
+    finally:
+        eng.set_halves_min(16384)
+    assert st == one_st and out == one_out
+    for i in sorted(touched | {0}):
+        rst, ref = oracle.pairing(B1[96 * i:96 * i + 96], B2[192 * i:192 * i + 192], True, True)
+        assert st[i] == rst and (rst != 0) == (i in touched), (n, i)
+        assert out[576 * i:576 * i + 576] == (ref if rst == 0 else bytes(576)), (n, i)
+    assert {i for i in range(n) if st[i]} == touched
+    for i in range(n):
+        if i not in touched:
+            assert out[576 * i:576 * i + 576] == plain[576 * i:576 * i + 576], (n, i)
+
+
 def test_decompress(eng, oracle, golden, testdata):
     for g2 in (False, True):
         vs = golden['codec']['g2' if g2 else 'g1']

@@ -224,6 +224,38 @@ def test_two_halves_execution(oracle, golden):
     eng.set_halves_min(16384)
 
 
+def test_halves_launch_by_launch(oracle, golden):
+    """What a 5000-pair call launches, program by program, on one stream and as two halves (2752 + 2248 pairs: 55 % rounded up to 64).  Above SPLIT_MILLER_MIN both runs take
+    LINES + ACC; both halves lie above the two-lane range, so the plain EXPX runs.  One stream: the middle of the final exponentiation is one chain, booked on its first program
+    (the checked library keeps seven launches).  Two halves: every stage once per half and the middle launch by launch.  Same bytes either way, equal to the oracle's."""
+    pkg = importlib.import_module('noble-bls12-381_amd')
+    eng = pkg.Engine(0)
+    pairs = golden['pairs']
+    n = 5000
+    g1 = b''.join(hx(pairs[i % len(pairs)]['g1']) for i in range(n)); g2 = b''.join(hx(pairs[(7 * i + 3) % len(pairs)]['g2']) for i in range(n))
+    checked = bool(os.environ.get('NBLS_CHECKED')) or 'dbg' in os.environ.get('NBLS_LIBRARY', '')
+    one = {'lines_pq': 1, 'acc_fe': 1, 'fp_inv': 1, 'fe_easy': 1, 'expx': 1, 'fe_final': 1}
+    if checked:
+        one.update({'expx': 5, 'fe_mid1': 1, 'fe_mid2': 1})
+    two = {'lines_pq': 2, 'acc_fe': 2, 'fp_inv': 2, 'fe_easy': 2, 'expx': 10, 'fe_mid1': 2, 'fe_mid2': 2, 'fe_final': 2}
+    eng.set_chain_max(8192)
+    eng.timing_enable(True)
+    try:
+        eng.set_halves_min(0)
+        ref, _ = eng.pairing_batch(g1, g2, True, False)
+        counts_one = {k: int(v[1]) for k, v in eng.timing_read().items()}
+        eng.set_halves_min(64)
+        got, _ = eng.pairing_batch(g1, g2, True, False)
+        counts_two = {k: int(v[1]) for k, v in eng.timing_read().items()}     # reading clears the counts
+    finally:
+        eng.timing_enable(False)
+        eng.set_halves_min(16384)
+    assert counts_one == one, counts_one
+    assert counts_two == two, counts_two
+    assert got == ref
+    assert got == oracle.pairing_batch(g1, g2, True, False, threads=16)[0]
+
+
 def test_chained_and_separate_final_exponentiation(oracle, golden):
     """The middle of the final exponentiation (EXPX, FE_MID1, EXPX x 3, FE_MID2, EXPX; math.ts:862-867) is one chained launch below NBLS_TUNE_CHAIN_MAX items and seven launches
     otherwise (what PairingPipeline's contexts use): same bytes either way, equal to the oracle's; sizes above the lane-split ranges (1024 / 2048: those forms run unchained), with a partly filled last wavefront."""
