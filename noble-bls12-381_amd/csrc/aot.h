@@ -76,7 +76,7 @@
   X(6, g2pt_ls2, P_H2C_C1_LS2, P_H2C_C2_LS2, P_G2_MUL_SAC_LS2, P_COUNT)
 
 // Kernels of the programs outside ProgId (programs.h ExtraProg): X(part, kernel name, two ExtraProgs it serves; XP_COUNT = none).  The Horner steps of nbls_g*_poly_eval, each
-// kernel serving the short and the full form of its group; the doubling-and-add steps of the batched MSM (pipelines_msm_batch.cpp), one kernel per group; the line program of
+// kernel serving the short and the full form of its group; the doubling-and-add steps of the batched MSM (pipelines_msm.cpp), one kernel per group; the line program of
 // the pairings that end in a final exponentiation (pipelines_pairing.cpp pairing_core).
 #define NBLS_AOT_EXTRA_KERNELS(X)                \
   X(1, poly_g1, XP_POLY_G1_16, XP_POLY_G1_256)  \

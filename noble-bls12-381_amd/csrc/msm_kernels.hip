@@ -1,8 +1,12 @@
-// msm_kernels.hip -- data movement of the multi-scalar multiplication sum_i [k_i]P_i (bucket method).
-// The group arithmetic itself runs as wave-VM step programs (P_G*_ADD_AB, P_G*_ADD2, P_G*_HORNER, P_G*_SHIFTADD); the
-// kernels here only decide WHICH points meet: window digits of the scalars, a device radix sort of (window, digit) keys
-// (hipCUB), and gathers by index.  Points are raw projective elements of E = 192 (G1) or 384 (G2) bytes, moved as 16-byte
-// vectors, one vector per thread, consecutive threads on consecutive vectors of the same point (coalesced).
+// msm_kernels.hip -- data movement of the multi-scalar multiplication sum_i [k_i]P_i (bucket method), for one sum and for many
+// independent sums that share every launch (pipelines_msm.cpp: bucket_slices).  The group arithmetic itself runs as wave-VM step programs
+// (P_G*_ADD_AB, P_G*_ADD2, P_G*_HORNER, P_G*_SHIFTADD, XP_DBLADD_G*); the kernels here only decide WHICH points meet: window digits of the
+// scalars, a device radix sort of the keys (hipCUB), and gathers by index.  The window width c is a run-time argument, and every key carries
+// the sum it belongs to:
+//   key = (group * nwin + window) << c | digit
+// so a run of equal keys never crosses a group, and the key is at the same time the index of its bucket; the single sum is one group with c = 12.
+// Points are raw projective elements of E = 192 (G1) or 384 (G2) bytes, moved as 16-byte vectors, one vector per thread, consecutive threads
+// on consecutive vectors of the same point (coalesced).
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 #include <stdint.h>
@@ -11,23 +15,34 @@
 namespace {
 typedef uint32_t u32;
 typedef uint64_t u64;
-const int C = 12;   // window bits == MSM_WINDOW_BITS (programs.h)
 
-// keys[w * n + i] = w << C | digit_w(k_i), vals[w * n + i] = i; scalars are 32-byte big-endian integers
-__global__ void msm_keys_kernel(u32 n, u32 nwin, const uint8_t* __restrict__ scalars, u32* __restrict__ keys, u32* __restrict__ vals) {
-  const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const u32* k = (const u32*)(scalars + 32ull * i);
+// One thread per item e of a slab: scalar i = i0 + e / dims of the call, part d = e % dims of its split (dims = 1: unsplit; the split scalars lie dims * 32 bytes per scalar;
+// scalars are 32-byte big-endian integers).  The item's group is found in the call's offsets (off[0 .. ngroups], relative to the first scalar; empty groups own nothing), or
+// is i / n_pts in the rows form (n_pts > 0), where the point is i % n_pts and off is not read.  keys[w * m + e] = ((group - g0) * nwin + w) << c | digit_w,
+// vals[w * m + e] = point * dims + d (the index of the converted point).  The single sum: i0 = g0 = 0 and n_pts = its points, so group 0, key = w << c | digit_w, val = e.
+__global__ void msm_keys_kernel(u32 m, u32 dims, u32 nwin, u32 c, u32 i0, u32 g0, u32 ngroups, u32 n_pts, const u32* __restrict__ off, const uint8_t* __restrict__ scalars,
+                                u32* __restrict__ keys, u32* __restrict__ vals) {
+  const u32 e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= m) return;
+  const u32 i = i0 + e / dims, d = e % dims;
+  u32 g, pt;
+  if (n_pts) { g = i / n_pts; pt = i - g * n_pts; }
+  else {
+    u32 lo = g0, hi = ngroups;      // the last g with off[g] <= i: off[g0] <= i holds for every item of the slab, and off[g + 1] > i follows
+    while (hi - lo > 1) { const u32 mid = (lo + hi) >> 1; if (off[mid] <= i) lo = mid; else hi = mid; }
+    g = lo; pt = i;
+  }
+  const u32* k = (const u32*)(scalars + 32ull * ((u64)i * dims + d));
   u32 w[9];
 #pragma unroll
   for (int j = 0; j < 8; j++) w[j] = __builtin_bswap32(k[7 - j]);
   w[8] = 0;
+  const u32 base = (g - g0) * nwin, val = pt * dims + d, mask = (1u << c) - 1;
   for (u32 win = 0; win < nwin; win++) {
-    const u32 bit = C * win, word = bit >> 5, off = bit & 31;
+    const u32 bit = c * win, word = bit >> 5, o = bit & 31;
     const u64 v = (u64)w[word] | ((u64)w[word + 1] << 32);
-    const u32 digit = (u32)(v >> off) & ((1u << C) - 1);
-    keys[(u64)win * n + i] = (win << C) | digit;
-    vals[(u64)win * n + i] = i;
+    keys[(u64)win * m + e] = ((base + win) << c) | ((u32)(v >> o) & mask);
+    vals[(u64)win * m + e] = val;
   }
 }
 
@@ -120,23 +135,25 @@ __global__ void msm_heads_kernel(u64 m, u32 q, const u32* __restrict__ keys, con
   buckets[(u64)key * q + part] = P[t];
 }
 
-// sum_b b * B_b = sum_t 2^t * (sum of the buckets whose index has bit t set): G[(w * C + t) * 2^(C-1) + j] = the j-th such bucket
-__global__ void msm_bitsel_kernel(u64 count, u32 q, const uint4* __restrict__ buckets, uint4* __restrict__ G) {
+// sum_b b * B_b = sum_t 2^t * (sum of the buckets whose index has bit t set), for every (group, window) = bw: G[((bw * c + t) << (c - 1)) + j] = the j-th such bucket of bw
+__global__ void msm_bitsel_kernel(u64 count, u32 q, u32 c, const uint4* __restrict__ buckets, uint4* __restrict__ G) {
   const u64 t = (u64)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= count * q) return;
   const u64 e = t / q; const u32 part = (u32)(t - e * q);
-  const u32 j = (u32)(e & ((1u << (C - 1)) - 1)); const u32 grp = (u32)(e >> (C - 1));
-  const u32 w = grp / C, bit = grp % C;
+  const u32 j = (u32)(e & ((1u << (c - 1)) - 1)); const u64 grp = e >> (c - 1);
+  const u64 bw = grp / c; const u32 bit = (u32)(grp - bw * c);
   const u32 b = ((j >> bit) << (bit + 1)) | (1u << bit) | (j & ((1u << bit) - 1));
-  G[t] = buckets[((u64)w * (1u << C) + b) * q + part];
+  G[t] = buckets[((bw << c) + b) * q + part];
 }
 
 inline unsigned blocks_for(u64 threads) { return (unsigned)((threads + 255) / 256); }
 }  // namespace
 
 extern "C" {
-int nbls_msm_keys_launch(unsigned n, unsigned nwin, const void* scalars, void* keys, void* vals, void* stream) {
-  hipLaunchKernelGGL(msm_keys_kernel, dim3(blocks_for(n)), dim3(256), 0, (hipStream_t)stream, n, nwin, (const uint8_t*)scalars, (u32*)keys, (u32*)vals);
+int nbls_msm_keys_launch(unsigned m, unsigned dims, unsigned nwin, unsigned c, unsigned i0, unsigned g0, unsigned ngroups, unsigned n_pts, const void* off, const void* scalars,
+                         void* keys, void* vals, void* stream) {
+  hipLaunchKernelGGL(msm_keys_kernel, dim3(blocks_for(m)), dim3(256), 0, (hipStream_t)stream, m, dims, nwin, c, i0, g0, ngroups, n_pts, (const u32*)off, (const uint8_t*)scalars,
+                     (u32*)keys, (u32*)vals);
   return (int)hipGetLastError();
 }
 int nbls_msm_decompose_launch(unsigned n, unsigned dims, const void* scalars, void* out, void* stream) {
@@ -181,10 +198,11 @@ int nbls_msm_heads_launch(size_t m, unsigned elem_bytes, const void* keys, const
   hipLaunchKernelGGL(msm_heads_kernel, dim3(blocks_for((u64)m * q)), dim3(256), 0, (hipStream_t)stream, (u64)m, q, (const u32*)keys, (const uint4*)P, (uint4*)buckets);
   return (int)hipGetLastError();
 }
-int nbls_msm_bitsel_launch(unsigned nwin, unsigned elem_bytes, const void* buckets, void* G, void* stream) {
+// nbw = groups * nwin
+int nbls_msm_bitsel_launch(size_t nbw, unsigned c, unsigned elem_bytes, const void* buckets, void* G, void* stream) {
   const u32 q = elem_bytes / 16;
-  const u64 count = (u64)nwin * C << (C - 1);
-  hipLaunchKernelGGL(msm_bitsel_kernel, dim3(blocks_for(count * q)), dim3(256), 0, (hipStream_t)stream, count, q, (const uint4*)buckets, (uint4*)G);
+  const u64 count = ((u64)nbw * c) << (c - 1);
+  hipLaunchKernelGGL(msm_bitsel_kernel, dim3(blocks_for(count * q)), dim3(256), 0, (hipStream_t)stream, count, q, c, (const uint4*)buckets, (uint4*)G);
   return (int)hipGetLastError();
 }
 }

@@ -1,5 +1,5 @@
 // nbls_internal.h -- what the translation units of the runtime share (runtime.cpp / tuning.cpp / pipelines_pairing.cpp / pipelines_codec.cpp / pipelines_verify.cpp /
-// pipelines_multi_verify.cpp / pipelines_threshold.cpp / pipelines_poly.cpp / pipelines_msm_batch.cpp / pipelines_kzg.cpp / pipelines_kzg_prove.cpp; pool and multi-device handles: nbls_multi.cpp): the context, the map of its scratch slots (enum Slot: the one place that says which chain owns
+// pipelines_multi_verify.cpp / pipelines_threshold.cpp / pipelines_poly.cpp / pipelines_msm.cpp / pipelines_kzg.cpp / pipelines_kzg_prove.cpp; pool and multi-device handles: nbls_multi.cpp): the context, the map of its scratch slots (enum Slot: the one place that says which chain owns
 // which slot, checked at compile time), the launch helpers, the staged block of the host-buffer pipelines (staging.h, included at the end) and the device-side pipelines the
 // exported entry points are built from.  Internal functions have hidden visibility (csrc/Makefile: -fvisibility=hidden).
 #pragma once
@@ -51,7 +51,9 @@ extern "C" int nbls_poly_group_launch(unsigned n, unsigned ngroups, const void* 
 extern "C" int nbls_poly_coef_launch(size_t items, unsigned elem_bytes, unsigned j, const void* group_of, const void* coff, const void* ident, const void* pts, void* dst, void* stream);
 extern "C" int nbls_poly_status_launch(unsigned n, unsigned out_bytes, const void* group_of, const void* first_bad, const void* st, const void* zero, void* out, void* status,
                                        void* stream);
-extern "C" int nbls_msm_keys_launch(unsigned n, unsigned nwin, const void* scalars, void* keys, void* vals, void* stream);
+// msm_kernels.hip
+extern "C" int nbls_msm_keys_launch(unsigned m, unsigned dims, unsigned nwin, unsigned c, unsigned i0, unsigned g0, unsigned ngroups, unsigned n_pts, const void* off,
+                                    const void* scalars, void* keys, void* vals, void* stream);
 extern "C" int nbls_msm_decompose_launch(unsigned n, unsigned dims, const void* scalars, void* out, void* stream);
 extern "C" int nbls_msm_sac_launch(unsigned n, const void* scalars, void* out, void* stream);
 extern "C" int nbls_msm_sort_launch(void* temp, size_t* temp_bytes, const void* keys_in, void* keys_out, const void* vals_in, void* vals_out, size_t m, int key_bits, void* stream);
@@ -60,7 +62,7 @@ extern "C" int nbls_msm_rank_launch(void* temp, size_t* temp_bytes, size_t m, co
 extern "C" int nbls_msm_pairs_launch(size_t m, unsigned d, const void* keys, const void* pos, void* list, void* count_u32, void* stream);
 extern "C" int nbls_msm_fill_launch(size_t count, unsigned elem_bytes, const void* ident, void* dst, void* stream);
 extern "C" int nbls_msm_heads_launch(size_t m, unsigned elem_bytes, const void* keys, const void* P, void* buckets, void* stream);
-extern "C" int nbls_msm_bitsel_launch(unsigned nwin, unsigned elem_bytes, const void* buckets, void* G, void* stream);
+extern "C" int nbls_msm_bitsel_launch(size_t nbw, unsigned c, unsigned elem_bytes, const void* buckets, void* G, void* stream);
 // kzg_kernels.hip
 extern "C" int nbls_kzg_roots_launch(unsigned log2_n, void* table, void* stream);
 extern "C" int nbls_kzg_eval_launch(unsigned log2_n, unsigned n, const void* evals32, const void* z32, const void* roots, void* out32, void* status, void* stream);
@@ -72,10 +74,6 @@ extern "C" int nbls_kzg_item_status_launch(unsigned n, const void* pre, const vo
 extern "C" int nbls_kzg_quotient_launch(unsigned log2_n, unsigned n, const void* evals32, const void* z32, const void* roots, void* out_y32, void* out_q32, void* status, void* stream);
 extern "C" int nbls_kzg_canon_launch(unsigned log2_n, unsigned n, void* evals32, void* status, void* stream);
 extern "C" int nbls_kzg_prove_tail_launch(unsigned n, const void* zero, const void* st_a, const void* st_b, void* out48, void* status, void* stream);
-// msmb_kernels.hip
-extern "C" int nbls_msmb_keys_launch(unsigned m, unsigned dims, unsigned nwin, unsigned c, unsigned i0, unsigned g0, unsigned ngroups, unsigned n_pts, const void* off,
-                                     const void* scalars, void* keys, void* vals, void* stream);
-extern "C" int nbls_msmb_bitsel_launch(size_t nbw, unsigned c, unsigned elem_bytes, const void* buckets, void* G, void* stream);
 extern "C" int nbls_fp_pow_launch(unsigned n, const void* in, void* out, const void* ops, int nops, void* scratch, int is_fp2, void* stream);
 extern "C" int nbls_pow_wide_launch(unsigned n, const void* in, void* out, const void* ops, int nops, int is_fp2, void* stream);
 
@@ -126,7 +124,7 @@ enum Slot {
   // poly_pipeline (pipelines_poly.cpp): the decoded coefficients, their statuses and raw projective forms | groups, ranks, first bad positions, the group of every identifier |
   // one slab: accumulators, norms, inverses, affine points, zero flags | one slab: the step's coefficient of every item | the compressed results and statuses (what is read back)
   SB_POLY_COEFS = 57, SB_POLY_LABELS = 58, SB_POLY_ACC = 59, SB_POLY_STEP = 60, SB_POLY_OUT = 61,
-  // msm_batch_pipeline (pipelines_msm_batch.cpp), both sized once per call before its first launch: the staged input, the converted points, the split scalars and what is read
+  // msm_batch_pipeline (pipelines_msm.cpp), both sized once per call before its first launch: the staged input, the converted points, the split scalars and what is read
   // back | one slab: keys, sorted points, buckets, bit-slices, accumulators.  (Two slots, carved by the pipeline.)
   SB_MSMB_CALL = 62, SB_MSMB_SLAB = 63,
   // kzg_pipeline (pipelines_kzg.cpp): the decoded commitments and proofs (+ the generator), their statuses | weights, the scalars of the MSMs, the products r_i y_i, the
@@ -210,7 +208,7 @@ struct nbls_ctx {
   DevProgram extra[XP_COUNT];   // the programs outside ProgId (programs.h ExtraProg), uploaded on first use with their ahead-of-time kernels
   size_t poly_slab = 0;         // nbls_set_tuning(NBLS_TUNE_POLY_SLAB): identifiers per slab of nbls_g*_poly_eval; 0 = the default (pipelines_poly.cpp)
   // nbls_set_tuning(NBLS_TUNE_MSMB_WINDOW / _BIG / _SLAB): the batched MSM's window width, the points from which a group runs through dev_msm, the entries of a slab; 0 = automatic /
-  // the defaults (pipelines_msm_batch.cpp)
+  // the defaults (pipelines_msm.cpp)
   size_t msmb_window = 0, msmb_big = 0, msmb_slab = 0;
   // scratch (device)
   uint8_t *F = nullptr, *N = nullptr, *NI = nullptr, *io_g1 = nullptr, *io_g2 = nullptr, *io_f12 = nullptr, *one12 = nullptr;
@@ -447,7 +445,7 @@ struct SegSums { const uint32_t* first; const int8_t* st; uint8_t* zero; };   //
 int segment_sums(nbls_ctx* ctx, bool g2, const SegSlots& sl, size_t count, size_t nseg, const uint32_t* d_off, const uint32_t* d_index, const uint8_t* src, const int8_t* st_src,
                  size_t maxseg, uint8_t* out, SegSums* o, hipStream_t s);
 unsigned scalars_bit_length(size_t n, const uint8_t* k32);
-// pipelines_msm_batch.cpp: the plan of one call (window width, slabs of whole groups, the carving of a slab's block) and the device core of nbls_g1_msm_rows that the KZG prover
+// pipelines_msm.cpp, the batched sums: the plan of one call (window width, slabs of whole groups, the carving of a slab's block) and the device core of nbls_g1_msm_rows that the KZG prover
 // feeds from device memory.  msm_rows_dev_plan sizes and takes SB_MSMB_CALL / SB_MSMB_SLAB: it comes with the caller's other need() calls, before anything is in flight.
 // msm_rows_dev: n_rows sums of n_pts points each; conv_pts = the output of P_G1_MSM_PREP (2 x 3 raw elements per point), d_scalars = n_rows * n_pts scalars of 32 bytes in
 // device memory, read as 256-bit values (the split path: they are never on the host for scalars_bit_length) -> affine sums (96 bytes each) and zero flags.  No group takes the

@@ -1,4 +1,4 @@
-// pipelines_codec.cpp -- validity, decoders / encoders, hash-to-curve, point sums, scalar multiplication, MSM and sign (reference index.ts:207-327, 359-448, 481-690, 738-752, 771-788).
+// pipelines_codec.cpp -- validity, decoders / encoders, hash-to-curve, point sums, scalar multiplication and sign (reference index.ts:207-327, 359-448, 481-690, 738-752, 771-788).
 #include "nbls_internal.h"
 
 // ================================================================================================================
@@ -423,129 +423,6 @@ EXPORT int nbls_g1_mul_batch(nbls_ctx* ctx, size_t n, const uint8_t* g1_aff, con
     out96, status); }
 EXPORT int nbls_g2_mul_batch(nbls_ctx* ctx, size_t n, const uint8_t* g2_aff, const uint8_t* scalars32, uint8_t* out192, int8_t* status) { return mul_host(ctx, true, n, g2_aff, scalars32,
     out192, status); }
-// ---- multi-scalar multiplication sum_i [k_i]P_i (the reference only has the unweighted sums aggregatePublicKeys /
-// aggregateSignatures, index.ts:771-788).  Bucket method with 12-bit windows, every group operation a complete addition run as
-// a step program over whole arrays:
-//   1. keys (window, digit) for every (point, window); device radix sort of the n * nwin keys (hipCUB); the points follow.
-//   2. segmented sum over the sorted list as a balanced tree inside every run of equal keys: in the round with stride d the
-//      elements whose rank in their run is a multiple of 2d absorb the element d further on.  The pairs of a round are
-//      listed by a compaction kernel (their number stays on the device: the step program reads it there) and added in place,
-//      the step program addressing its operands through the list: n * nwin - (number of buckets hit) additions in total whatever the distribution of the digits;
-//      ceil(log2(longest run)) rounds -- the longest run is the one value read back.  The head of every run ends up as its bucket sum.
-//   3. sum_b b * B_b per window = sum_t 2^t * T_t with T_t = sum of the buckets whose index has bit t: 12 * 2^11 gathered
-//      points per window, a balanced tree of 11 rounds of pairwise additions (data independent).
-//   4. Horner over t inside every window (one item per window), then acc <- 2^12 * acc + S_w from the top window down.
-// Result: affine wire bytes + status (1 = the sum is the zero point).  nbits bounds the scalars (< 2^nbits), 0 = 256.  sl: the scratch slots of this instance.
-//
-// Step 2 on its own, for every caller that has segments to sum (dev_msm: runs of equal keys; segment_sums in pipelines_multi_verify.cpp: the keys of a set, the sets of a message):
-// `count` points P whose segment is keys[j] and whose place inside it is rank[j]; ceil(log2(maxrun)) rounds leave every segment's sum at its first point.  counters: one word per
-// round (the pairs of that round), list: count words.
-int segmented_sum(nbls_ctx* ctx, bool g2, size_t count, const uint32_t* keys, const uint32_t* rank, uint32_t* list, uint32_t* counters, uint8_t* P, size_t maxrun, hipStream_t s) {
-  const size_t p = g2 ? 6 * RAW : 3 * RAW; int r;
-  for (size_t d = 1; d < maxrun; d *= 2, counters++) {
-    const size_t bound = count / (d + 1) + 1;      // every pair owns d + 1 list positions of its own segment
-    LAUNCHCHK(nbls_msm_pairs_launch(count, (unsigned)d, keys, rank, list, counters, s));
-    // P[j] += P[j + d] for the listed j, in place: the step program addresses its buffers through the list (KernelArgs.item_index);
-    // a listed element is never the partner of another one (ranks are multiples of 2d), so no pair touches another pair's points
-    if ((r = run(ctx, g2 ? P_G2_ADD_AB : P_G1_ADD_AB, bound, {B(3, P, p), B(4, P + d * p, p), B(5, P, p)}, s, counters, list))) return r;
-  }
-  return NBLS_OK;
-}
-int dev_msm(nbls_ctx* ctx, bool g2, size_t n, const void* d_pts, const void* d_scalars, unsigned nbits, void* d_out, void* d_status, hipStream_t s, const MsmSlots& sl) {
-  const size_t a = g2 ? 192 : 96, p = g2 ? 6 * RAW : 3 * RAW;
-  const unsigned C = MSM_WINDOW_BITS;
-  uint8_t* ident = g2 ? ctx->ident_g2 : ctx->ident_g1;
-  if (nbits == 0 || nbits > 256) nbits = 256;
-  if (n > ((size_t)1 << 22)) return NBLS_EINVAL;
-  // Wide scalars are split with the curve endomorphisms (GLV / GLS): k = sum_i a_i |z|^i, [|z|^i]P is one cheap map of P.  G1:
-  // 2 points with 129-bit scalars, G2: 4 points with 65-bit scalars -- the same number of bucket additions, but 10 / 5 instead
-  // of 21 rounds of "12 doublings + 1 addition" on a single point at the end (latency-bound: 0.11 ms each).
-  const bool split = nbits > 192;
-  const unsigned dims = split ? (g2 ? 4 : 2) : 1;
-  const size_t n_in = n;
-  if (split) { n *= dims; nbits = g2 ? 65 : 129; }
-  const unsigned nwin = (nbits + C - 1) / C;
-  const size_t m = n * nwin, nb = (size_t)nwin << C, ng = ((size_t)nwin * C) << (C - 1);
-  uint8_t *Pj, *P, *A, *K, *tmp, *Bk, *G, *Gh, *N, *NI, *acc, *cnt, *Ks = nullptr; int r;
-  if (split && (r = need(ctx, sl[MsmSlots::SPLIT_SCALARS], (n + 1) * 32, &Ks))) return r;
-  size_t tmp_bytes = 0;
-  size_t scan_bytes = 0;
-  if (m) { LAUNCHCHK(nbls_msm_sort_launch(nullptr, &tmp_bytes, nullptr, nullptr, nullptr, nullptr, m, 17, s)); LAUNCHCHK(nbls_msm_rank_launch(nullptr, &scan_bytes, m, nullptr, nullptr, nullptr,
-      s)); tmp_bytes = std::max(tmp_bytes, scan_bytes); }
-  if ((r = need(ctx, sl[MsmSlots::POINTS], (n + 1) * p, &Pj)) || (r = need(ctx, sl[MsmSlots::SORTED], (m + 1) * p, &P)) || (r = need(ctx, sl[MsmSlots::WINDOW_SUMS], ((size_t)nwin + 1) * p, &A)) ||
-      (r = need(ctx, sl[MsmSlots::KEYS], (m + 1) * 24, &K)) || (r = need(ctx, sl[MsmSlots::NORM], RAW, &N)) || (r = need(ctx, sl[MsmSlots::NORM_INV], RAW, &NI)) ||
-      (r = need(ctx, sl[MsmSlots::TEMP], tmp_bytes + 16, &tmp)) || (r = need(ctx, sl[MsmSlots::BUCKETS], nb * p, &Bk)) || (r = need(ctx, sl[MsmSlots::SLICES], ng * p, &G)) ||
-      (r = need(ctx, sl[MsmSlots::SLICES_HALF], (ng / 2 + 2) * p, &Gh)) || (r = need(ctx, sl[MsmSlots::COUNTERS], 64 * 4, &cnt))) return r;
-  acc = Gh + ng / 2 * p;
-  uint32_t *kin = (uint32_t*)K, *vin = kin + m, *kout = vin + m, *vout = kout + m, *pos = vout + m, *list = pos + m;
-  uint32_t* counters = (uint32_t*)cnt;    // [0] longest run, [1 + round] pairs of that round
-  LAUNCHCHK(nbls_msm_fill_launch(nb, (unsigned)p, ident, Bk, s));
-  if (m) {
-    if (split) {
-      if ((r = run(ctx, g2 ? P_G2_MSM_PREP : P_G1_MSM_PREP, n_in, {B(g2 ? 1 : 0, d_pts, a), B(3, Pj, dims * p)}, s))) return r;
-      LAUNCHCHK(nbls_msm_decompose_launch((unsigned)n_in, dims, d_scalars, Ks, s));
-    } else if ((r = run(ctx, g2 ? P_G2_TO_PROJ : P_G1_TO_PROJ, n, {B(g2 ? 1 : 0, d_pts, a), B(3, Pj, p)}, s))) return r;
-    LAUNCHCHK(nbls_msm_keys_launch((unsigned)n, nwin, split ? Ks : (const uint8_t*)d_scalars, kin, vin, s));
-    LAUNCHCHK(nbls_msm_sort_launch(tmp, &tmp_bytes, kin, kout, vin, vout, m, 17, s));
-    LAUNCHCHK(nbls_msm_gather_launch(m, (unsigned)p, vout, Pj, P, s));
-    LAUNCHCHK(nbls_msm_rank_launch(tmp, &scan_bytes, m, kout, pos, counters, s));
-    uint32_t maxrun = 0;
-    HIPCHK(hipMemcpyAsync(&maxrun, counters, 4, hipMemcpyDeviceToHost, s)); HIPCHK(hipStreamSynchronize(s));
-    if ((r = segmented_sum(ctx, g2, m, kout, pos, list, counters + 1, P, maxrun, s))) return r;
-    LAUNCHCHK(nbls_msm_heads_launch(m, (unsigned)p, kout, P, Bk, s));
-  }
-  LAUNCHCHK(nbls_msm_bitsel_launch(nwin, (unsigned)p, Bk, G, s));
-  uint8_t *src = G, *dst = Gh;
-  for (size_t cnt = ng; cnt > (size_t)nwin * C; cnt /= 2) {
-    if ((r = run(ctx, g2 ? P_G2_ADD2 : P_G1_ADD2, cnt / 2, {B(3, src, 2 * p), B(5, dst, p)}, s))) return r;
-    std::swap(src, dst);
-  }
-  uint8_t* S = A;   // per-window sums
-  static const bool wide_combine = env_long("NBLS_MSM_WIDE", 1) != 0;
-  // Horner over the bit-slices t of every window (sum_t 2^t T_t, one sum per window), then over the windows (below).  G1 (round 6): both with one limb per lane, a wavefront per
-  // sum, the four products of a doubling level on its four rows (g1_wide.h: 0.74 -> 0.25 ms of a 65,536-point call); G2 and NBLS_MSM_WIDE=0: the step programs
-  if (!g2 && wide_combine) LAUNCHCHK(nbls_g1_wide_combine_launch(src, (int)C, 1, S, nwin, s));
-  else if ((r = run(ctx, g2 ? P_G2_HORNER : P_G1_HORNER, nwin, {B(3, src, C * p), B(5, S, p)}, s))) return r;
-  // acc <- 2^12 acc + S_w from the top window down: (nwin - 1) x (12 doublings + 1 addition) on ONE point
-  if (!g2 && wide_combine) LAUNCHCHK(nbls_g1_wide_combine_launch(S, (int)nwin, (int)C, acc, 1, s));
-  else {
-    HIPCHK(hipMemcpyAsync(acc, S + (size_t)(nwin - 1) * p, p, hipMemcpyDeviceToDevice, s));
-    for (int w = (int)nwin - 2; w >= 0; w--)
-      if ((r = run(ctx, g2 ? P_G2_SHIFTADD : P_G1_SHIFTADD, 1, {B(3, acc, p), B(4, S + (size_t)w * p, p), B(5, acc, p)}, s))) return r;
-  }
-  return to_affine(ctx, g2, 1, acc, N, NI, d_out, d_status, s);
-}
-unsigned scalars_bit_length(size_t n, const uint8_t* k32) {   // max over the batch
-  int lead = 32;   // leading zero bytes common to all scalars
-  for (size_t i = 0; i < n && lead; i++) { int z = 0; while (z < lead && k32[32 * i + z] == 0) z++; lead = z; }
-  if (lead == 32) return 1;
-  uint8_t top = 0; for (size_t i = 0; i < n; i++) top |= k32[32 * i + lead];
-  unsigned bits = 8 * (31 - lead); while (top) { bits++; top >>= 1; }
-  return bits;
-}
-int msm_host(nbls_ctx* ctx, bool g2, size_t n, const uint8_t* pts, const uint8_t* scalars32, uint8_t* out, int8_t* status) {
-  if (!ctx || !out || (n && (!pts || !scalars32))) return NBLS_EINVAL;
-  const size_t a = g2 ? 192 : 96;
-  LOCKED(ctx); HostIO io{ctx}; void *dp = io.alloc(n * a), *dk = io.alloc(n * 32), *o = io.alloc(a), *st = io.alloc(1); if (!dp || !dk || !o || !st) return NBLS_EHIP;
-  if (n) { HIPCHK(hipMemcpyAsync(dp, pts, n * a, hipMemcpyHostToDevice, s)); HIPCHK(hipMemcpyAsync(dk, scalars32, n * 32, hipMemcpyHostToDevice, s)); }
-  int r = dev_msm(ctx, g2, n, dp, dk, n ? scalars_bit_length(n, scalars32) : 1, o, st, s); if (r) return r;
-  int8_t z = 0; HIPCHK(hipMemcpyAsync(out, o, a, hipMemcpyDeviceToHost, s)); HIPCHK(hipMemcpyAsync(&z, st, 1, hipMemcpyDeviceToHost, s)); HIPCHK(hipStreamSynchronize(s));
-  // the zero point has no affine form: what P_G*_TO_AFFINE leaves there depends on the representative of 0 in Z (the one-limb-per-lane combine leaves p, and the binary GCD of
-  // the inversion does not map that to 0).  All-zero bytes, as every other call reports the zero point
-  if (z == 1) memset(out, 0, a);
-  if (status) *status = z;
-  return NBLS_OK;
-}
-EXPORT int nbls_g1_msm(nbls_ctx* ctx, size_t n, const uint8_t* pts96, const uint8_t* scalars32, uint8_t* out96, int8_t* status) { return msm_host(ctx, false, n, pts96, scalars32, out96, status); }
-EXPORT int nbls_g2_msm(nbls_ctx* ctx, size_t n, const uint8_t* pts192, const uint8_t* scalars32, uint8_t* out192, int8_t* status) { return msm_host(ctx, true, n, pts192, scalars32, out192, status); }
-// device-resident variant: points (affine wire bytes), scalars (32 B big-endian, all < 2^nbits; nbits = 0 means 256), one affine result + int8 status
-// in device memory; enqueued on `stream` (NULL = the context's stream) except for one 4-byte read-back in the middle
-EXPORT int nbls_msm_dev(nbls_ctx* ctx, int g2, size_t n, const void* d_pts, const void* d_scalars32, unsigned nbits, void* d_out, void* d_status, void* stream) {
-  if (!ctx || !d_out || !d_status || (n && (!d_pts || !d_scalars32))) return NBLS_EINVAL;
-  DEV_ENTER(ctx, stream);
-  return dev_msm(ctx, g2 != 0, n, d_pts, d_scalars32, nbits, d_out, d_status, s);
-}
-
 // sign(message_i, key_i) (index.ts:744-752): hashToCurve -> multiply by the key -> affine signature point (the caller
 // compresses, PointG2.toSignature index.ts:586-602).  status: 0 ok, 5 key is 0 mod r.
 EXPORT int nbls_sign_batch(nbls_ctx* ctx, size_t n, const uint8_t* msgs, const uint32_t* offsets, const uint8_t* dst, size_t dst_len, const uint8_t* keys32, uint8_t* out192, int8_t* status) {

@@ -6,7 +6,7 @@
 //   H2D copy -> commitments: kzg_canon_kernel (a non-canonical blob is flagged and zeroed in place), the blob elements ARE the MSM's scalars
 //            -> proofs: the challenges (blob proofs: hashed on host threads behind the copy, a second small copy) -> kzg_quotient_kernel: y_i, the canonical check, and the
 //               quotient rows as 32-byte big-endian scalars
-//            -> msm_rows_dev (pipelines_msm_batch.cpp): the scalars split along the endomorphism, the slabs of the batched MSM against the setup's converted points, to-affine
+//            -> msm_rows_dev (pipelines_msm.cpp): the scalars split along the endomorphism, the slabs of the batched MSM against the setup's converted points, to-affine
 //            -> P_G1_COMPRESS -> kzg_prove_tail_kernel: statuses, 0xc0 00.. for a zero sum, all-zero bytes for a refused item -> D2H copy
 // nbls_kzg_compute_blob_proofs without commitments runs the first chain on the staged blobs, reads the 48 n bytes back (the one synchronisation the challenge needs), hashes,
 // and goes on with the second.  Scratch slots: SB_STAGED and SB_KZGP_* (nbls_internal.h, M_KZGP_OWN); the MSM on SB_MSMB_*.

@@ -35,7 +35,7 @@ enum ProgId {
   P_G1_CLEAR,           // projective point (3) -> clearCofactor -> projective point (6), Z (7)                            (index.ts:401-405)
   P_ENC2_A, P_ENC2_B,   // G2 encodeToCurve: 128 uniform bytes (0) -> u (3), SWU exponentiation input (4) ; u (3), power (5) -> projective point on E2 (6)
   P_G1_MUL, P_G2_MUL,            // [k]P for per-item 256-bit scalars: point (buf 0 / 1), scalar 32 B (buf 2) -> projective (3), norm of Z (4)   (getPublicKey / sign, index.ts:738-752)
-  // multi-scalar multiplication (bucket method, 12-bit windows; pipelines_codec.cpp dev_msm): points are raw projective (3 / 6 field elements)
+  // multi-scalar multiplication (bucket method, 12-bit windows; pipelines_msm.cpp dev_msm): points are raw projective (3 / 6 field elements)
   P_G1_ADD_AB, P_G2_ADD_AB,       // A[i] (buf 3) + B[i] (buf 4) -> buf 5 (may alias buf 3)
   P_G1_HORNER, P_G2_HORNER,       // T[0..11] of one window (buf 3) -> sum_t 2^t T[t] (buf 5)
   P_G1_SHIFTADD, P_G2_SHIFTADD,   // 2^12 * acc (buf 3) + S (buf 4) -> buf 5
@@ -108,7 +108,7 @@ const Program* get_tower_program(int field, int op, int param, int part);
 // kernels of their own (aot.h NBLS_AOT_EXTRA_KERNELS).  One Horner step of a commitment polynomial in the exponent (pipelines_poly.cpp): accumulator (buf 3: raw projective, in
 // place), identifier x (buf 2: 32 bytes big-endian, any value), the step's coefficient (buf 4: raw projective) -> acc = [x]acc + A.  The _16 forms read the low 16 bits of the
 // identifier (16 doublings instead of 256); the accumulator lies in the order-r subgroup, so the _256 forms take any 256-bit value as P_G1_MUL does.
-// The doubling-and-add steps of the batched MSM's combination (pipelines_msm_batch.cpp): accumulator (buf 3: raw projective, in place), bit-slice sum T (buf 4: raw projective)
+// The doubling-and-add steps of the batched MSM's combination (pipelines_msm.cpp): accumulator (buf 3: raw projective, in place), bit-slice sum T (buf 4: raw projective)
 // -> acc = 2 acc + T, complete formulas throughout (identity accumulators, identity slices, T = -2 acc and T = 2 acc are ordinary inputs).
 // The line program of the calls that END IN THE FINAL EXPONENTIATION (pipelines_pairing.cpp pairing_core, two-program form): G1 (buf 0), G2 (buf 1) -> lines (buf 3) in the
 // layout of P_LINES_PQ, every line the reference's times a non-zero Fp2 factor and R any projective representative (programs.cpp trace_lines_fe).  A factor in a proper subfield

@@ -105,7 +105,7 @@ def test_msm_large_linear(eng, oracle):
     assert s == 0 and o == _ref(oracle, [b64[i % 64] for i in range(n2)], kk, g2=True)
 
 
-# ---- every scalar-width path of dev_msm (csrc/pipelines_codec.cpp) and the edges of the bucket kernels (csrc/msm_kernels.hip) --------------------------------------------
+# ---- every scalar-width path of dev_msm (csrc/pipelines_msm.cpp) and the edges of the bucket kernels (csrc/msm_kernels.hip) --------------------------------------------
 # dev_msm takes nbits from the caller (msm_host: the longest scalar's bit length): up to 192 bits it runs unsplit with ceil(nbits / 12) windows (1 .. 16), above it splits
 # along the endomorphisms into 129-bit (G1, 11 windows) or 65-bit (G2, 6 windows) digits.  References: the oracle and Python integers only.
 P_MOD = 0x1a0111ea397fe69a4b1ba7b6434bacd764774b84f38512bf6730d2a0f6b0f6241eabfffeb153ffffb9feffffffffaaab

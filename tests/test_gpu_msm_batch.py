@@ -1,4 +1,4 @@
-"""GPU parity tests of the batched multi-scalar multiplication (nbls_g*_msm_batch / nbls_g*_msm_rows, csrc/pipelines_msm_batch.cpp) against the CPU oracle.  Every call is checked
+"""GPU parity tests of the batched multi-scalar multiplication (nbls_g*_msm_batch / nbls_g*_msm_rows, csrc/pipelines_msm.cpp) against the CPU oracle.  Every call is checked
 twice: against the oracle (its own sum of scalar multiples for small groups, the a_i G bookkeeping of test_gpu_msm.py -- one oracle multiplication per group -- for larger
 ones), and byte for byte against eng.msm on every group alone."""
 import ctypes as C

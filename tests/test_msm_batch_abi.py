@@ -30,7 +30,7 @@ def test_symbols_exported(lib):
     exported = {ln.split()[-1] for ln in out.splitlines() if ln.strip()}
     for nm in NAMES:
         assert nm in exported and hasattr(lib, nm), nm
-    for nm in ('nbls_msmb_keys_launch', 'nbls_msmb_bitsel_launch'):          # the kernels' launch wrappers stay internal
+    for nm in ('nbls_msm_keys_launch', 'nbls_msm_bitsel_launch'):            # the kernels' launch wrappers stay internal
         assert nm not in exported, nm
     assert lib.nbls_abi_version() == 5
     assert lib.nbls_program_count() == len(vmsim_py.PROGS) + 1          # the numbered registry did not grow

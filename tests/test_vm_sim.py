@@ -311,7 +311,7 @@ def test_sign_aligned_ladder_for_subgroup_points(sim, oracle, prog='G2_MUL_SAC')
 
 
 def test_msm_pipeline(sim, oracle):
-    """the bucket-method multi-scalar multiplication (dev_msm in csrc/pipelines_codec.cpp: sort by window digit, segmented sums,
+    """the bucket-method multi-scalar multiplication (dev_msm in csrc/pipelines_msm.cpp: sort by window digit, segmented sums,
     bit-sliced bucket weighting, Horner over the windows) with its step programs on the simulator, against the oracle's
     sum of scalar multiples; scalars with repeated digits (long runs in one bucket), zero digits and zero scalars"""
     import random

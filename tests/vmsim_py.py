@@ -282,7 +282,7 @@ def point_mul_sac(lib, pts192, scalars32, prog='G2_MUL_SAC'):
 
 
 def msm(lib, pts, scalars32, nbits, g2=False):
-    """dev_msm() of csrc/pipelines_codec.cpp on the simulator; the data-movement kernels of msm_kernels.hip (window digits, sort,
+    """dev_msm() of csrc/pipelines_msm.cpp on the simulator; the data-movement kernels of msm_kernels.hip (window digits, sort,
     gathers) are restated in Python, every group operation runs as a step program"""
     WB = 12
     sz, psz = (192, 6 * RAW) if g2 else (96, 3 * RAW)
