@@ -9,6 +9,7 @@
 //   its per-item exponent and selects.  Nothing here is an interface for secrets all the same: no value is wiped.
 #pragma once
 #include <stdint.h>
+#include "group_search.h"
 #if defined(__HIPCC__)
 #define NBLS_FR_HD __host__ __device__ inline
 #else
@@ -178,14 +179,7 @@ NBLS_FR_HD void fr_lagrange_fold(FrLagrange& s, const Fr& xj, uint32_t mine, uin
   s.den = fr_mul(s.den, fr_select(mine & ~self, fr_sub(xj, s.xk), one));
 }
 // the group of share k: off[g] <= k < off[g + 1] over ngroups + 1 strictly increasing offsets
-NBLS_FR_HD uint32_t fr_group_of(const uint32_t* off, uint32_t ngroups, uint32_t k) {
-  uint32_t lo = 0, hi = ngroups;
-  while (hi - lo > 1) {
-    const uint32_t mid = (lo + hi) >> 1;
-    if (off[mid] <= k) lo = mid; else hi = mid;
-  }
-  return lo;
-}
+NBLS_FR_HD uint32_t fr_group_of(const uint32_t* off, uint32_t ngroups, uint32_t k) { return group_search(off, 0, ngroups, k); }
 // one staged tile: identifiers t .. t + cnt - 1 of the call, for the lane of share k whose group is [gb, ge)
 NBLS_FR_HD void fr_lagrange_tile(FrLagrange& s, const Fr* tile, uint32_t t, uint32_t cnt, uint32_t gb, uint32_t ge, uint32_t k) {
   for (uint32_t c = 0; c < cnt; c++) {

@@ -5,6 +5,8 @@
 #include <stdint.h>
 #include "fr_exec.h"
 #include "nbls.h"   // NBLS_ST_BAD_IDS
+#include "kernel_parts.h"
+#include "launchers.h"
 
 namespace {
 typedef uint32_t u32;
@@ -68,7 +70,7 @@ __global__ void fr_lagrange_out_kernel(u32 n, const Fr* __restrict__ lambda, con
 }
 
 // status[g] = NBLS_ST_BAD_IDS for a flagged group, else the decoder status of the group's first share that did
-// not decode, else 1 when the combination is the zero point, else 0; the group's `e` output bytes (16-byte vectors) become 0xc0 00.. for status 1 and all-zero for a status >= 2
+// not decode, else 1 when the combination is the zero point, else 0; the group's `e` output bytes are closed by the status (kernel_parts.h close_compressed)
 __global__ void fr_combine_status_kernel(u32 ngroups, u32 e, const u32* __restrict__ bad_group, const u32* __restrict__ first_bad, const int8_t* __restrict__ st,
                                          const int8_t* __restrict__ zero, uint8_t* __restrict__ out, int8_t* __restrict__ status) {
   const u32 g = blockIdx.x * blockDim.x + threadIdx.x;
@@ -76,10 +78,7 @@ __global__ void fr_combine_status_kernel(u32 ngroups, u32 e, const u32* __restri
   int8_t v = NBLS_ST_BAD_IDS;
   if (!bad_group[g]) { const u32 f = first_bad[g]; v = f != 0xffffffffu ? st[f] : zero[g]; }
   status[g] = v;
-  if (v) {
-    uint4* o = (uint4*)(out + (u64)g * e);
-    for (u32 q = 0; q < e / 16; q++) o[q] = make_uint4(q == 0 && v == 1 ? 0xc0u : 0u, 0u, 0u, 0u);
-  }
+  close_compressed(out + (u64)g * e, e, v);
 }
 
 // status[g] = NBLS_ST_BAD_IDS for a flagged group, else 0 (nbls_lagrange_at_zero)
@@ -88,36 +87,27 @@ __global__ void fr_group_status_kernel(u32 ngroups, const u32* __restrict__ bad_
   if (g < ngroups) status[g] = bad_group[g] ? NBLS_ST_BAD_IDS : 0;
 }
 
-inline unsigned blocks_for(u64 threads, unsigned per = 256) { return (unsigned)((threads + per - 1) / per); }
 }  // namespace
 
 extern "C" {
-int nbls_fr_op_launch(unsigned n, int op, const void* a32, const void* b32, void* out32, void* status, void* stream) {
-  if (!n) return 0;
-  hipLaunchKernelGGL(fr_op_kernel, dim3(blocks_for(n, 64)), dim3(64), 0, (hipStream_t)stream, n, op, (const uint8_t*)a32, (const uint8_t*)b32, (uint8_t*)out32, (int8_t*)status);
-  return (int)hipGetLastError();
+int nbls_fr_op_launch(unsigned n, int op, const void* a32, const void* b32, void* out32, void* status, hipStream_t stream) {
+  return launch_1d(fr_op_kernel, n, 64, 0, stream, n, op, a32, b32, out32, status);
 }
 // ids32: n identifiers (wire bytes) in ngroups contiguous groups -> out32: n canonical coefficients; X, L: n Montgomery elements each; group_of: n words; bad_group: ngroups words
-int nbls_fr_lagrange_launch(unsigned n, unsigned ngroups, const void* off, const void* ids32, void* X, void* L, void* group_of, void* bad_group, void* out32, void* stream) {
+int nbls_fr_lagrange_launch(unsigned n, unsigned ngroups, const uint32_t* off, const void* ids32, void* X, void* L, uint32_t* group_of, uint32_t* bad_group, void* out32,
+                            hipStream_t stream) {
   if (!n || !ngroups) return 0;
-  hipStream_t s = (hipStream_t)stream;
-  const hipError_t e = hipMemsetAsync(bad_group, 0, (size_t)ngroups * 4, s);
-  if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(fr_to_mont_kernel, dim3(blocks_for(n)), dim3(256), 0, s, n, (const uint8_t*)ids32, (Fr*)X);
-  hipLaunchKernelGGL(fr_lagrange_kernel, dim3(blocks_for(n, LAG_BLOCK)), dim3(LAG_BLOCK), 0, s, n, ngroups, (const u32*)off, (const Fr*)X, (Fr*)L, (u32*)group_of, (u32*)bad_group);
-  hipLaunchKernelGGL(fr_lagrange_out_kernel, dim3(blocks_for(n)), dim3(256), 0, s, n, (const Fr*)L, (const u32*)group_of, (const u32*)bad_group, (uint8_t*)out32);
-  return (int)hipGetLastError();
+  int e = (int)hipMemsetAsync(bad_group, 0, (size_t)ngroups * 4, stream);
+  if (!e) e = launch_1d(fr_to_mont_kernel, n, 256, 0, stream, n, ids32, X);
+  if (!e) e = launch_1d(fr_lagrange_kernel, n, LAG_BLOCK, 0, stream, n, ngroups, off, X, L, group_of, bad_group);
+  if (!e) e = launch_1d(fr_lagrange_out_kernel, n, 256, 0, stream, n, L, group_of, bad_group, out32);
+  return e;
 }
-int nbls_fr_combine_status_launch(unsigned ngroups, unsigned out_bytes, const void* bad_group, const void* first_bad, const void* st, const void* zero, void* out, void* status,
-                                  void* stream) {
-  if (!ngroups) return 0;
-  hipLaunchKernelGGL(fr_combine_status_kernel, dim3(blocks_for(ngroups)), dim3(256), 0, (hipStream_t)stream, ngroups, out_bytes, (const u32*)bad_group, (const u32*)first_bad,
-                     (const int8_t*)st, (const int8_t*)zero, (uint8_t*)out, (int8_t*)status);
-  return (int)hipGetLastError();
+int nbls_fr_combine_status_launch(unsigned ngroups, unsigned out_bytes, const uint32_t* bad_group, const uint32_t* first_bad, const int8_t* st, const void* zero, void* out,
+                                  void* status, hipStream_t stream) {
+  return launch_1d(fr_combine_status_kernel, ngroups, 256, 0, stream, ngroups, out_bytes, bad_group, first_bad, st, zero, out, status);
 }
-int nbls_fr_group_status_launch(unsigned ngroups, const void* bad_group, void* status, void* stream) {
-  if (!ngroups) return 0;
-  hipLaunchKernelGGL(fr_group_status_kernel, dim3(blocks_for(ngroups)), dim3(256), 0, (hipStream_t)stream, ngroups, (const u32*)bad_group, (int8_t*)status);
-  return (int)hipGetLastError();
+int nbls_fr_group_status_launch(unsigned ngroups, const uint32_t* bad_group, void* status, hipStream_t stream) {
+  return launch_1d(fr_group_status_kernel, ngroups, 256, 0, stream, ngroups, bad_group, status);
 }
 }

@@ -8,6 +8,8 @@
 #include <mutex>
 #include "fr_exec.h"
 #include "nbls.h"   // NBLS_ST_NON_CANONICAL, NBLS_ST_NOT_VERIFIED
+#include "kernel_parts.h"
+#include "launchers.h"
 
 namespace {
 typedef uint32_t u32;
@@ -117,10 +119,7 @@ __global__ void kzg_prove_tail_kernel(u32 n, const int8_t* __restrict__ zero, co
   if (i >= n) return;
   const int8_t a = st_a ? st_a[i] : 0, b = st_b ? st_b[i] : 0, v = a ? a : b;
   status[i] = v;
-  if (v || zero[i] == 1) {
-    uint4* o = (uint4*)(out48 + 48ull * i);
-    for (u32 w = 0; w < 3; w++) o[w] = make_uint4(w == 0 && !v ? 0xc0u : 0u, 0u, 0u, 0u);
-  }
+  close_compressed(out48 + 48ull * i, 48, v ? v : zero[i] == 1);   // (st_a, st_b hold 0 or NBLS_ST_NON_CANONICAL)
 }
 
 __device__ inline void copy96(uint8_t* dst, const uint8_t* src) {
@@ -167,11 +166,6 @@ __global__ void __launch_bounds__(256) kzg_sum_kernel(u32 n, const Fr* __restric
   }
   if (threadIdx.x == 0) fr_store_be(fr_neg(part[0]), out32);
 }
-// pts[i] = the generator where zero[i] == 1: a zero point cannot go into a Miller loop; the verdict is taken from the flag, not from that factor
-__global__ void kzg_fix_zero_kernel(u32 n, const int8_t* __restrict__ zero, const uint8_t* __restrict__ gen96, uint8_t* __restrict__ pts) {
-  const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n && zero[i] == 1) copy96(pts + 96ull * i, gen96);
-}
 // the per-item pass: zs[i] = z_i (zero where the item is out or its proof is the zero point), ny[i] = -y_i mod r (zero where the item is out)
 __global__ void kzg_item_scalars_kernel(u32 n, const int8_t* __restrict__ pre, const int8_t* __restrict__ dst, const uint8_t* __restrict__ z32, const uint8_t* __restrict__ y32,
                                         uint8_t* __restrict__ zs, uint8_t* __restrict__ ny) {
@@ -193,7 +187,6 @@ __global__ void kzg_item_status_kernel(u32 n, const int8_t* __restrict__ pre, co
   status[i] = pre[i] ? pre[i] : ok ? 0 : NBLS_ST_NOT_VERIFIED;
 }
 
-inline unsigned blocks_for(u64 threads, unsigned per = 256) { return (unsigned)((threads + per - 1) / per); }
 // The running products of N = 4096 take more than the 64 KB a launch may ask for by default.  The limit is a per-device function attribute: set once on every device a launch of
 // `kernel` is made on (as nbls_vm_launch does); the common case, already set, takes no lock
 int lds_limit(const void* kernel, std::atomic<bool>* attr_set) {
@@ -213,71 +206,46 @@ int lds_limit(const void* kernel, std::atomic<bool>* attr_set) {
 }  // namespace
 
 extern "C" {
-int nbls_kzg_roots_launch(unsigned log2_n, void* table, void* stream) {
-  hipLaunchKernelGGL(kzg_roots_kernel, dim3(blocks_for((u64)1 << log2_n, 64)), dim3(64), 0, (hipStream_t)stream, log2_n, (Fr*)table);
-  return (int)hipGetLastError();
-}
+int nbls_kzg_roots_launch(unsigned log2_n, void* table, hipStream_t stream) { return launch_1d(kzg_roots_kernel, (u64)1 << log2_n, 64, 0, stream, log2_n, table); }
 // n polynomials of 2^log2_n elements each (1 <= log2_n <= 12) at their points z -> out32 (n x 32 bytes) and status (n bytes, not NULL)
-int nbls_kzg_eval_launch(unsigned log2_n, unsigned n, const void* evals32, const void* z32, const void* roots, void* out32, void* status, void* stream) {
+int nbls_kzg_eval_launch(unsigned log2_n, unsigned n, const void* evals32, const void* z32, const void* roots, void* out32, void* status, hipStream_t stream) {
   if (!n) return 0;
   if (log2_n < 1 || log2_n > 12) return (int)hipErrorInvalidValue;
   const unsigned terms = ((1u << log2_n) + EV - 1) / EV, lds = terms * FR_NL * EV * 4;
   static std::atomic<bool> attr_set[64];
   const int e = lds_limit((const void*)kzg_eval_kernel, attr_set);
-  if (e) return e;
-  hipLaunchKernelGGL(kzg_eval_kernel, dim3(n), dim3(EV), lds, (hipStream_t)stream, log2_n, (const uint8_t*)evals32, (const uint8_t*)z32, (const Fr*)roots, (uint8_t*)out32, (int8_t*)status);
-  return (int)hipGetLastError();
+  return e ? e : launch_1d(kzg_eval_kernel, (u64)n * EV, EV, lds, stream, log2_n, evals32, z32, roots, out32, status);
 }
 // the same n polynomials -> out_y32 (n x 32), the quotient rows out_q32 (n x 2^log2_n x 32 bytes, 16-byte aligned) and status (n bytes, not NULL)
-int nbls_kzg_quotient_launch(unsigned log2_n, unsigned n, const void* evals32, const void* z32, const void* roots, void* out_y32, void* out_q32, void* status, void* stream) {
+int nbls_kzg_quotient_launch(unsigned log2_n, unsigned n, const void* evals32, const void* z32, const void* roots, void* out_y32, void* out_q32, void* status,
+                             hipStream_t stream) {
   if (!n) return 0;
   if (log2_n < 1 || log2_n > 12 || ((uintptr_t)out_q32 & 15)) return (int)hipErrorInvalidValue;
   const unsigned terms = ((1u << log2_n) + EV - 1) / EV, lds = terms * FR_NL * EV * 4;
   static std::atomic<bool> attr_set[64];
   const int e = lds_limit((const void*)kzg_quotient_kernel, attr_set);
-  if (e) return e;
-  hipLaunchKernelGGL(kzg_quotient_kernel, dim3(n), dim3(EV), lds, (hipStream_t)stream, log2_n, (const uint8_t*)evals32, (const uint8_t*)z32, (const Fr*)roots, (uint8_t*)out_y32,
-                     (uint8_t*)out_q32, (int8_t*)status);
-  return (int)hipGetLastError();
+  return e ? e : launch_1d(kzg_quotient_kernel, (u64)n * EV, EV, lds, stream, log2_n, evals32, z32, roots, out_y32, out_q32, status);
 }
 // evals32: n blobs of 2^log2_n elements, 16-byte aligned, zeroed in place where non-canonical
-int nbls_kzg_canon_launch(unsigned log2_n, unsigned n, void* evals32, void* status, void* stream) {
+int nbls_kzg_canon_launch(unsigned log2_n, unsigned n, void* evals32, void* status, hipStream_t stream) {
   if (!n) return 0;
   if (log2_n < 1 || log2_n > 12 || ((uintptr_t)evals32 & 15)) return (int)hipErrorInvalidValue;
-  hipLaunchKernelGGL(kzg_canon_kernel, dim3(n), dim3(256), 0, (hipStream_t)stream, log2_n, (uint8_t*)evals32, (int8_t*)status);
-  return (int)hipGetLastError();
+  return launch_1d(kzg_canon_kernel, (u64)n * 256, 256, 0, stream, log2_n, evals32, status);
 }
-int nbls_kzg_prove_tail_launch(unsigned n, const void* zero, const void* st_a, const void* st_b, void* out48, void* status, void* stream) {
-  if (!n) return 0;
-  if ((uintptr_t)out48 & 15) return (int)hipErrorInvalidValue;
-  hipLaunchKernelGGL(kzg_prove_tail_kernel, dim3(blocks_for(n)), dim3(256), 0, (hipStream_t)stream, n, (const int8_t*)zero, (const int8_t*)st_a, (const int8_t*)st_b, (uint8_t*)out48,
-                     (int8_t*)status);
-  return (int)hipGetLastError();
+int nbls_kzg_prove_tail_launch(unsigned n, const void* zero, const void* st_a, const void* st_b, void* out48, void* status, hipStream_t stream) {
+  if (n && ((uintptr_t)out48 & 15)) return (int)hipErrorInvalidValue;
+  return launch_1d(kzg_prove_tail_kernel, n, 256, 0, stream, n, zero, st_a, st_b, out48, status);
 }
-int nbls_kzg_items_launch(unsigned n, const void* dst, const void* w32, const void* z32, const void* y32, const void* yst, const void* gen96, void* aff, void* s1, void* s2, void* t,
-                          void* pre, void* stream) {
+int nbls_kzg_items_launch(unsigned n, const void* dst, const void* w32, const void* z32, const void* y32, const void* yst, const void* gen96, void* aff, void* s1, void* s2,
+                          void* t, void* pre, hipStream_t stream) {
   if (!n) return 0;
-  hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(kzg_items_kernel, dim3(blocks_for(n, 64)), dim3(64), 0, s, n, (const int8_t*)dst, (const uint8_t*)w32, (const uint8_t*)z32, (const uint8_t*)y32, (const int8_t*)yst,
-                     (const uint8_t*)gen96, (uint8_t*)aff, (uint8_t*)s1, (uint8_t*)s2, (Fr*)t, (int8_t*)pre);
-  hipLaunchKernelGGL(kzg_sum_kernel, dim3(1), dim3(256), 0, s, n, (const Fr*)t, (uint8_t*)s2 + 64ull * n);
-  return (int)hipGetLastError();
+  const int e = launch_1d(kzg_items_kernel, n, 64, 0, stream, n, dst, w32, z32, y32, yst, gen96, aff, s1, s2, t, pre);
+  return e ? e : launch_1d(kzg_sum_kernel, 256, 256, 0, stream, n, t, (uint8_t*)s2 + 64ull * n);
 }
-int nbls_kzg_fix_zero_launch(unsigned n, const void* zero, const void* gen96, void* pts, void* stream) {
-  if (!n) return 0;
-  hipLaunchKernelGGL(kzg_fix_zero_kernel, dim3(blocks_for(n)), dim3(256), 0, (hipStream_t)stream, n, (const int8_t*)zero, (const uint8_t*)gen96, (uint8_t*)pts);
-  return (int)hipGetLastError();
+int nbls_kzg_item_scalars_launch(unsigned n, const void* pre, const void* dst, const void* z32, const void* y32, void* zs, void* ny, hipStream_t stream) {
+  return launch_1d(kzg_item_scalars_kernel, n, 64, 0, stream, n, pre, dst, z32, y32, zs, ny);
 }
-int nbls_kzg_item_scalars_launch(unsigned n, const void* pre, const void* dst, const void* z32, const void* y32, void* zs, void* ny, void* stream) {
-  if (!n) return 0;
-  hipLaunchKernelGGL(kzg_item_scalars_kernel, dim3(blocks_for(n, 64)), dim3(64), 0, (hipStream_t)stream, n, (const int8_t*)pre, (const int8_t*)dst, (const uint8_t*)z32,
-                     (const uint8_t*)y32, (uint8_t*)zs, (uint8_t*)ny);
-  return (int)hipGetLastError();
-}
-int nbls_kzg_item_status_launch(unsigned n, const void* pre, const void* dst, const void* xzero, const void* one, void* status, void* stream) {
-  if (!n) return 0;
-  hipLaunchKernelGGL(kzg_item_status_kernel, dim3(blocks_for(n)), dim3(256), 0, (hipStream_t)stream, n, (const int8_t*)pre, (const int8_t*)dst, (const int8_t*)xzero, (const uint8_t*)one,
-                     (int8_t*)status);
-  return (int)hipGetLastError();
+int nbls_kzg_item_status_launch(unsigned n, const void* pre, const void* dst, const void* xzero, const void* one, void* status, hipStream_t stream) {
+  return launch_1d(kzg_item_status_kernel, n, 256, 0, stream, n, pre, dst, xzero, one, status);
 }
 }

@@ -11,10 +11,14 @@
 #include <hipcub/hipcub.hpp>
 #include <stdint.h>
 #include "scalar_split.h"
+#include "group_search.h"
+#include "kernel_parts.h"
+#include "launchers.h"
 
 namespace {
 typedef uint32_t u32;
 typedef uint64_t u64;
+using namespace nbls;
 
 // One thread per item e of a slab: scalar i = i0 + e / dims of the call, part d = e % dims of its split (dims = 1: unsplit; the split scalars lie dims * 32 bytes per scalar;
 // scalars are 32-byte big-endian integers).  The item's group is found in the call's offsets (off[0 .. ngroups], relative to the first scalar; empty groups own nothing), or
@@ -27,11 +31,7 @@ __global__ void msm_keys_kernel(u32 m, u32 dims, u32 nwin, u32 c, u32 i0, u32 g0
   const u32 i = i0 + e / dims, d = e % dims;
   u32 g, pt;
   if (n_pts) { g = i / n_pts; pt = i - g * n_pts; }
-  else {
-    u32 lo = g0, hi = ngroups;      // the last g with off[g] <= i: off[g0] <= i holds for every item of the slab, and off[g + 1] > i follows
-    while (hi - lo > 1) { const u32 mid = (lo + hi) >> 1; if (off[mid] <= i) lo = mid; else hi = mid; }
-    g = lo; pt = i;
-  }
+  else { g = group_search(off, g0, ngroups, i); pt = i; }   // off[g0] <= i holds for every item of the slab
   const u32* k = (const u32*)(scalars + 32ull * ((u64)i * dims + d));
   u32 w[9];
 #pragma unroll
@@ -62,8 +62,8 @@ __global__ void msm_sac_kernel(u32 n, const uint8_t* __restrict__ scalars, uint8
 __global__ void msm_gather_kernel(u64 m, u32 q, const u32* __restrict__ idx, const uint4* __restrict__ src, uint4* __restrict__ dst) {
   const u64 t = (u64)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= m * q) return;
-  const u64 e = t / q; const u32 part = (u32)(t - e * q);
-  dst[t] = src[(u64)idx[e] * q + part];
+  const VecPart v = vec_split(t, q);
+  dst[t] = src[(u64)idx[v.elem] * q + v.part];
 }
 
 // rank of every element inside its run of equal keys: starts[j] = j at the head of a run, else 0; an inclusive max-scan (hipCUB)
@@ -122,87 +122,78 @@ __global__ void __launch_bounds__(1024) msm_pairs_kernel(u64 m, u32 d, const u32
 __global__ void msm_fill_kernel(u64 count, u32 q, const uint4* __restrict__ ident, uint4* __restrict__ dst) {
   const u64 t = (u64)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= count * q) return;
-  dst[t] = ident[t % q];
+  dst[t] = ident[vec_split(t, q).part];
 }
 
 // buckets[key] = P[j] for the head j of every run
 __global__ void msm_heads_kernel(u64 m, u32 q, const u32* __restrict__ keys, const uint4* __restrict__ P, uint4* __restrict__ buckets) {
   const u64 t = (u64)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= m * q) return;
-  const u64 e = t / q; const u32 part = (u32)(t - e * q);
-  const u32 key = keys[e];
-  if (e > 0 && keys[e - 1] == key) return;
-  buckets[(u64)key * q + part] = P[t];
+  const VecPart v = vec_split(t, q);
+  const u32 key = keys[v.elem];
+  if (v.elem > 0 && keys[v.elem - 1] == key) return;
+  buckets[(u64)key * q + v.part] = P[t];
 }
 
 // sum_b b * B_b = sum_t 2^t * (sum of the buckets whose index has bit t set), for every (group, window) = bw: G[((bw * c + t) << (c - 1)) + j] = the j-th such bucket of bw
 __global__ void msm_bitsel_kernel(u64 count, u32 q, u32 c, const uint4* __restrict__ buckets, uint4* __restrict__ G) {
   const u64 t = (u64)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= count * q) return;
-  const u64 e = t / q; const u32 part = (u32)(t - e * q);
-  const u32 j = (u32)(e & ((1u << (c - 1)) - 1)); const u64 grp = e >> (c - 1);
+  const VecPart v = vec_split(t, q);
+  const u32 j = (u32)(v.elem & ((1u << (c - 1)) - 1)); const u64 grp = v.elem >> (c - 1);
   const u64 bw = grp / c; const u32 bit = (u32)(grp - bw * c);
   const u32 b = ((j >> bit) << (bit + 1)) | (1u << bit) | (j & ((1u << bit) - 1));
-  G[t] = buckets[((bw << c) + b) * q + part];
+  G[t] = buckets[((bw << c) + b) * q + v.part];
 }
 
-inline unsigned blocks_for(u64 threads) { return (unsigned)((threads + 255) / 256); }
 }  // namespace
 
 extern "C" {
-int nbls_msm_keys_launch(unsigned m, unsigned dims, unsigned nwin, unsigned c, unsigned i0, unsigned g0, unsigned ngroups, unsigned n_pts, const void* off, const void* scalars,
-                         void* keys, void* vals, void* stream) {
-  hipLaunchKernelGGL(msm_keys_kernel, dim3(blocks_for(m)), dim3(256), 0, (hipStream_t)stream, m, dims, nwin, c, i0, g0, ngroups, n_pts, (const u32*)off, (const uint8_t*)scalars,
-                     (u32*)keys, (u32*)vals);
-  return (int)hipGetLastError();
+int nbls_msm_keys_launch(unsigned m, unsigned dims, unsigned nwin, unsigned c, unsigned i0, unsigned g0, unsigned ngroups, unsigned n_pts, const uint32_t* off,
+                         const void* scalars, uint32_t* keys, uint32_t* vals, hipStream_t stream) {
+  return launch_1d(msm_keys_kernel, m, 256, 0, stream, m, dims, nwin, c, i0, g0, ngroups, n_pts, off, scalars, keys, vals);
 }
-int nbls_msm_decompose_launch(unsigned n, unsigned dims, const void* scalars, void* out, void* stream) {
-  hipLaunchKernelGGL(msm_decompose_kernel, dim3(blocks_for(n)), dim3(256), 0, (hipStream_t)stream, n, dims, (const uint8_t*)scalars, (uint8_t*)out);
-  return (int)hipGetLastError();
+int nbls_msm_decompose_launch(unsigned n, unsigned dims, const void* scalars, void* out, hipStream_t stream) {
+  return launch_1d(msm_decompose_kernel, n, 256, 0, stream, n, dims, scalars, out);
 }
-int nbls_msm_sac_launch(unsigned n, const void* scalars, void* out, void* stream) {
-  hipLaunchKernelGGL(msm_sac_kernel, dim3(blocks_for(n)), dim3(256), 0, (hipStream_t)stream, n, (const uint8_t*)scalars, (uint8_t*)out);
-  return (int)hipGetLastError();
-}
+int nbls_msm_sac_launch(unsigned n, const void* scalars, void* out, hipStream_t stream) { return launch_1d(msm_sac_kernel, n, 256, 0, stream, n, scalars, out); }
 // temp == NULL: returns the scratch size in *temp_bytes
-int nbls_msm_sort_launch(void* temp, size_t* temp_bytes, const void* keys_in, void* keys_out, const void* vals_in, void* vals_out, size_t m, int key_bits, void* stream) {
-  return (int)hipcub::DeviceRadixSort::SortPairs(temp, *temp_bytes, (const u32*)keys_in, (u32*)keys_out, (const u32*)vals_in, (u32*)vals_out, (int)m, 0, key_bits, (hipStream_t)stream);
+int nbls_msm_sort_launch(void* temp, size_t* temp_bytes, const uint32_t* keys_in, uint32_t* keys_out, const uint32_t* vals_in, uint32_t* vals_out, size_t m, int key_bits,
+                         hipStream_t stream) {
+  return (int)hipcub::DeviceRadixSort::SortPairs(temp, *temp_bytes, keys_in, keys_out, vals_in, vals_out, (int)m, 0, key_bits, stream);
 }
-int nbls_msm_gather_launch(size_t m, unsigned elem_bytes, const void* idx, const void* src, void* dst, void* stream) {
+int nbls_msm_gather_launch(size_t m, unsigned elem_bytes, const uint32_t* idx, const void* src, void* dst, hipStream_t stream) {
   const u32 q = elem_bytes / 16;
-  hipLaunchKernelGGL(msm_gather_kernel, dim3(blocks_for((u64)m * q)), dim3(256), 0, (hipStream_t)stream, (u64)m, q, (const u32*)idx, (const uint4*)src, (uint4*)dst);
-  return (int)hipGetLastError();
+  return launch_1d(msm_gather_kernel, (u64)m * q, 256, 0, stream, m, q, idx, src, dst);
 }
 // temp == NULL: returns the scan's scratch size in *temp_bytes
-int nbls_msm_rank_launch(void* temp, size_t* temp_bytes, size_t m, const void* keys, void* pos, void* maxrun_u32, void* stream) {
-  if (!temp) return (int)hipcub::DeviceScan::InclusiveScan(nullptr, *temp_bytes, (const u32*)pos, (u32*)pos, hipcub::Max(), (int)m, (hipStream_t)stream);
-  hipMemsetAsync(maxrun_u32, 0, 4, (hipStream_t)stream);
-  hipLaunchKernelGGL(msm_heads_flag_kernel, dim3(blocks_for(m)), dim3(256), 0, (hipStream_t)stream, (u64)m, (const u32*)keys, (u32*)pos);
-  int e = (int)hipcub::DeviceScan::InclusiveScan(temp, *temp_bytes, (const u32*)pos, (u32*)pos, hipcub::Max(), (int)m, (hipStream_t)stream);
-  if (e) return e;
-  hipLaunchKernelGGL(msm_rank_kernel, dim3(blocks_for(m)), dim3(256), 0, (hipStream_t)stream, (u64)m, (const u32*)keys, (u32*)pos, (u32*)maxrun_u32);
-  return (int)hipGetLastError();
+int nbls_msm_rank_launch(void* temp, size_t* temp_bytes, size_t m, const uint32_t* keys, uint32_t* pos, uint32_t* maxrun, hipStream_t stream) {
+  if (!temp) return (int)hipcub::DeviceScan::InclusiveScan(nullptr, *temp_bytes, pos, pos, hipcub::Max(), (int)m, stream);
+  if (!m) return 0;
+  int e = (int)hipMemsetAsync(maxrun, 0, 4, stream);
+  if (!e) e = launch_1d(msm_heads_flag_kernel, m, 256, 0, stream, m, keys, pos);
+  if (!e) e = (int)hipcub::DeviceScan::InclusiveScan(temp, *temp_bytes, pos, pos, hipcub::Max(), (int)m, stream);
+  if (!e) e = launch_1d(msm_rank_kernel, m, 256, 0, stream, m, keys, pos, maxrun);
+  return e;
 }
-int nbls_msm_pairs_launch(size_t m, unsigned d, const void* keys, const void* pos, void* list, void* count_u32, void* stream) {
-  hipMemsetAsync(count_u32, 0, 4, (hipStream_t)stream);
-  hipLaunchKernelGGL(msm_pairs_kernel, dim3((unsigned)((m + 4095) / 4096)), dim3(1024), 0, (hipStream_t)stream, (u64)m, d, (const u32*)keys, (const u32*)pos, (u32*)list, (u32*)count_u32);
-  return (int)hipGetLastError();
+// 4096 elements per workgroup of 1024 threads
+int nbls_msm_pairs_launch(size_t m, unsigned d, const uint32_t* keys, const uint32_t* pos, uint32_t* list, uint32_t* count, hipStream_t stream) {
+  if (!m) return 0;
+  const hipError_t e = hipMemsetAsync(count, 0, 4, stream);
+  return e != hipSuccess ? (int)e : launch_1d(msm_pairs_kernel, ((u64)m + 3) / 4, 1024, 0, stream, m, d, keys, pos, list, count);
 }
-int nbls_msm_fill_launch(size_t count, unsigned elem_bytes, const void* ident, void* dst, void* stream) {
+int nbls_msm_fill_launch(size_t count, unsigned elem_bytes, const void* ident, void* dst, hipStream_t stream) {
   const u32 q = elem_bytes / 16;
-  hipLaunchKernelGGL(msm_fill_kernel, dim3(blocks_for((u64)count * q)), dim3(256), 0, (hipStream_t)stream, (u64)count, q, (const uint4*)ident, (uint4*)dst);
-  return (int)hipGetLastError();
+  return launch_1d(msm_fill_kernel, (u64)count * q, 256, 0, stream, count, q, ident, dst);
 }
-int nbls_msm_heads_launch(size_t m, unsigned elem_bytes, const void* keys, const void* P, void* buckets, void* stream) {
+int nbls_msm_heads_launch(size_t m, unsigned elem_bytes, const uint32_t* keys, const void* P, void* buckets, hipStream_t stream) {
   const u32 q = elem_bytes / 16;
-  hipLaunchKernelGGL(msm_heads_kernel, dim3(blocks_for((u64)m * q)), dim3(256), 0, (hipStream_t)stream, (u64)m, q, (const u32*)keys, (const uint4*)P, (uint4*)buckets);
-  return (int)hipGetLastError();
+  return launch_1d(msm_heads_kernel, (u64)m * q, 256, 0, stream, m, q, keys, P, buckets);
 }
 // nbw = groups * nwin
-int nbls_msm_bitsel_launch(size_t nbw, unsigned c, unsigned elem_bytes, const void* buckets, void* G, void* stream) {
+int nbls_msm_bitsel_launch(size_t nbw, unsigned c, unsigned elem_bytes, const void* buckets, void* G, hipStream_t stream) {
   const u32 q = elem_bytes / 16;
   const u64 count = ((u64)nbw * c) << (c - 1);
-  hipLaunchKernelGGL(msm_bitsel_kernel, dim3(blocks_for(count * q)), dim3(256), 0, (hipStream_t)stream, count, q, c, (const uint4*)buckets, (uint4*)G);
-  return (int)hipGetLastError();
+  return launch_1d(msm_bitsel_kernel, count * q, 256, 0, stream, count, q, c, buckets, G);
 }
 }

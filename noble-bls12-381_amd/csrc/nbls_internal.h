@@ -19,63 +19,11 @@
 #include "bufs.h"    // BufArg / B(), BufList, ChainLink, bind_bufs
 #include <thread>
 
-extern "C" int nbls_vm_launch(const nbls::KernelArgs* ka, unsigned lds_bytes, void* stream);
-extern "C" int nbls_vm_wide_launch(const nbls::KernelArgs* ka, unsigned lds_bytes, void* stream);
-extern "C" int nbls_fp_inv_wide_launch(unsigned n, const void* in, void* out, void* stream);   // fp_inv_wide.h: four elements per wavefront, one limb per lane
-// g1_wide.h: `sums` times sum_w 2^(shift w) S_w over nwin points, one wavefront each
-extern "C" int nbls_g1_wide_combine_launch(const void* S, int nwin, int shift, void* out, unsigned sums, void* stream);
+#include "launchers.h"   // every nbls_*_launch of the kernel files, declared once for both sides
 #include "wide_exec.h"   // wide_step_supported
 #include "aot.h"
 #include <map>
 #include <tuple>
-extern "C" int nbls_fp_inv_launch(unsigned n, const void* in, void* out, void* stream);
-extern "C" int nbls_flag_compact_launch(unsigned n, const void* flags, void* list, void* count, void* stream);
-extern "C" int nbls_xmd_launch(unsigned n, const void* msgs, const void* offsets, const void* dst, unsigned dst_len, void* out, unsigned len_in_bytes, void* bad_flag, void* stream);
-extern "C" int nbls_rlc_weights_launch(unsigned n, const void* seed32, void* out, void* stream);   // rlc_kernels.hip
-extern "C" int nbls_rlc_interleave_launch(unsigned n, const void* pk96, const void* neg_g1, const void* h192, const void* sig192, void* g1x, void* g2x, void* stream);
-extern "C" int nbls_rlc_is_one_launch(unsigned n, const void* f576, void* ok, void* stream);
-extern "C" int nbls_agg_keys_launch(unsigned nkeys, unsigned n, const void* koff, const void* index, const void* st_src, void* set_id, void* rank, void* st, void* first_bad,
-                                    void* stream);   // agg_kernels.hip
-extern "C" int nbls_agg_points_launch(size_t nkeys, unsigned elem_bytes, const void* index, const void* st, const void* ident, const void* src, void* dst, void* stream);
-extern "C" int nbls_agg_status_launch(unsigned n, const void* first_bad, const void* st, const void* zero, void* out, void* stream);
-extern "C" int nbls_grp_zero_launch(unsigned m, const void* zero, const void* fixed96, void* rpk96, void* flag_u32, void* stream);   // grp_kernels.hip
-extern "C" int nbls_grp_interleave_launch(unsigned n, const void* msg_index, const void* pk96, const void* neg_g1, const void* h192, const void* sig192, void* g1x, void* g2x,
-                                          void* stream);
-extern "C" int nbls_fr_op_launch(unsigned n, int op, const void* a32, const void* b32, void* out32, void* status, void* stream);   // fr_kernels.hip
-extern "C" int nbls_fr_lagrange_launch(unsigned n, unsigned ngroups, const void* off, const void* ids32, void* X, void* L, void* group_of, void* bad_group, void* out32, void* stream);
-extern "C" int nbls_fr_combine_status_launch(unsigned ngroups, unsigned out_bytes, const void* bad_group, const void* first_bad, const void* st, const void* zero, void* out,
-                                             void* status, void* stream);
-extern "C" int nbls_fr_group_status_launch(unsigned ngroups, const void* bad_group, void* status, void* stream);
-// poly_kernels.hip
-extern "C" int nbls_poly_group_launch(unsigned n, unsigned ngroups, const void* off, void* group_of, void* stream);
-extern "C" int nbls_poly_coef_launch(size_t items, unsigned elem_bytes, unsigned j, const void* group_of, const void* coff, const void* ident, const void* pts, void* dst, void* stream);
-extern "C" int nbls_poly_status_launch(unsigned n, unsigned out_bytes, const void* group_of, const void* first_bad, const void* st, const void* zero, void* out, void* status,
-                                       void* stream);
-// msm_kernels.hip
-extern "C" int nbls_msm_keys_launch(unsigned m, unsigned dims, unsigned nwin, unsigned c, unsigned i0, unsigned g0, unsigned ngroups, unsigned n_pts, const void* off,
-                                    const void* scalars, void* keys, void* vals, void* stream);
-extern "C" int nbls_msm_decompose_launch(unsigned n, unsigned dims, const void* scalars, void* out, void* stream);
-extern "C" int nbls_msm_sac_launch(unsigned n, const void* scalars, void* out, void* stream);
-extern "C" int nbls_msm_sort_launch(void* temp, size_t* temp_bytes, const void* keys_in, void* keys_out, const void* vals_in, void* vals_out, size_t m, int key_bits, void* stream);
-extern "C" int nbls_msm_gather_launch(size_t m, unsigned elem_bytes, const void* idx, const void* src, void* dst, void* stream);
-extern "C" int nbls_msm_rank_launch(void* temp, size_t* temp_bytes, size_t m, const void* keys, void* pos, void* maxrun_u32, void* stream);
-extern "C" int nbls_msm_pairs_launch(size_t m, unsigned d, const void* keys, const void* pos, void* list, void* count_u32, void* stream);
-extern "C" int nbls_msm_fill_launch(size_t count, unsigned elem_bytes, const void* ident, void* dst, void* stream);
-extern "C" int nbls_msm_heads_launch(size_t m, unsigned elem_bytes, const void* keys, const void* P, void* buckets, void* stream);
-extern "C" int nbls_msm_bitsel_launch(size_t nbw, unsigned c, unsigned elem_bytes, const void* buckets, void* G, void* stream);
-// kzg_kernels.hip
-extern "C" int nbls_kzg_roots_launch(unsigned log2_n, void* table, void* stream);
-extern "C" int nbls_kzg_eval_launch(unsigned log2_n, unsigned n, const void* evals32, const void* z32, const void* roots, void* out32, void* status, void* stream);
-extern "C" int nbls_kzg_items_launch(unsigned n, const void* dst, const void* w32, const void* z32, const void* y32, const void* yst, const void* gen96, void* aff, void* s1, void* s2,
-                                     void* t, void* pre, void* stream);
-extern "C" int nbls_kzg_fix_zero_launch(unsigned n, const void* zero, const void* gen96, void* pts, void* stream);
-extern "C" int nbls_kzg_item_scalars_launch(unsigned n, const void* pre, const void* dst, const void* z32, const void* y32, void* zs, void* ny, void* stream);
-extern "C" int nbls_kzg_item_status_launch(unsigned n, const void* pre, const void* dst, const void* xzero, const void* one, void* status, void* stream);
-extern "C" int nbls_kzg_quotient_launch(unsigned log2_n, unsigned n, const void* evals32, const void* z32, const void* roots, void* out_y32, void* out_q32, void* status, void* stream);
-extern "C" int nbls_kzg_canon_launch(unsigned log2_n, unsigned n, void* evals32, void* status, void* stream);
-extern "C" int nbls_kzg_prove_tail_launch(unsigned n, const void* zero, const void* st_a, const void* st_b, void* out48, void* status, void* stream);
-extern "C" int nbls_fp_pow_launch(unsigned n, const void* in, void* out, const void* ops, int nops, void* scratch, int is_fp2, void* stream);
-extern "C" int nbls_pow_wide_launch(unsigned n, const void* in, void* out, const void* ops, int nops, int is_fp2, void* stream);
 
 using namespace nbls;
 static_assert(P_COUNT <= NBLS_N_PROGRAMS, "nbls_timing_read's arrays (NBLS_N_PROGRAMS + 1 entries) must cover every step program");

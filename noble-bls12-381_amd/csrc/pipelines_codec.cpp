@@ -483,7 +483,7 @@ EXPORT int nbls_sign_batch_dev(nbls_ctx* ctx, size_t n, const void* d_msgs, cons
   if ((r = need(ctx, SB_UNIFORM, n * 256 + 16, &du))) return r;
   uint32_t* d_bad = (uint32_t*)(du + n * 256);
   HIPCHK(hipMemsetAsync(d_bad, 0, 4, s));
-  LAUNCHCHK(nbls_xmd_launch((unsigned)n, (const uint8_t*)d_msgs, (const uint8_t*)d_offsets, dd, (unsigned)dst_len, du, 256, d_bad, s));
+  LAUNCHCHK(nbls_xmd_launch((unsigned)n, d_msgs, d_offsets, dd, (unsigned)dst_len, du, 256, d_bad, s));
   if ((r = sign_points(ctx, n, du, h, d_keys32, d_out192, d_status, s))) return r;
   uint32_t bad = 0; HIPCHK(hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, s)); HIPCHK(hipStreamSynchronize(s));
   return bad ? NBLS_EINVAL : NBLS_OK;     // offsets[i + 1] < offsets[i] somewhere

@@ -148,7 +148,7 @@ static int kzg_pipeline(nbls_ctx* ctx, const KzgIn& in, int* all_ok, int8_t* sta
   if ((r = run(ctx, P_G1_ADD_AB, 1, {B(3, BJ, p), B(4, BJ + p, p), B(5, BJ, p)}, s)) || (r = run(ctx, P_G1_ADD_AB, 1, {B(3, BJ, p), B(4, BJ + 2 * p, p), B(5, BJ, p)}, s)) ||
       (r = to_affine(ctx, false, 1, BJ, BN, BN + RAW, PT2 + 96, BK + 2, s)))
     return r;
-  LAUNCHCHK(nbls_kzg_fix_zero_launch(2, BK + 1, ctx->gen_g1, PT2, s));
+  LAUNCHCHK(nbls_agg_fix_zero_launch(2, BK + 1, ctx->gen_g1, PT2, nullptr, s));
   uint8_t* res = ctx->F;
   if ((r = run(ctx, P_ACC_Q, 2, {B(0, PT2, 96), B(3, TB, LINE_BYTES), B(5, ctx->F, F12)}, s)) || (r = reduce_product(ctx, 2, &res, s)) || (r = finish_single(ctx, Window(), res, 1, RES, s))) return r;
   LAUNCHCHK(nbls_rlc_is_one_launch(1, RES, BK, s));
@@ -184,7 +184,7 @@ static int kzg_pipeline(nbls_ctx* ctx, const KzgIn& in, int* all_ok, int8_t* sta
   if ((r = run(ctx, P_G1_ADD_AB, n, {B(3, PJ, p), B(4, PJ + n * p, p), B(5, PJ, p)}, s)) || (r = run(ctx, P_G1_ADD_AB, n, {B(3, PJ, p), B(4, PJ + 2 * n * p, p), B(5, PJ, p)}, s)) ||
       (r = to_affine(ctx, false, n, PJ, N, NI, X, XZ, s)))
     return r;
-  LAUNCHCHK(nbls_kzg_fix_zero_launch((unsigned)n, XZ, ctx->gen_g1, X, s));
+  LAUNCHCHK(nbls_agg_fix_zero_launch((unsigned)n, XZ, ctx->gen_g1, X, nullptr, s));
   // millerLoop(pi_i, [tau]G2) * millerLoop(X_i, -G2): the two shared tables (table_stride = 0), one batched final exponentiation, compared with one on the device
   if ((r = run(ctx, P_ACC_Q, n, {B(0, AFF + n * 96, 96), B(3, TB, 0), B(5, ctx->F, F12)}, s)) || (r = run(ctx, P_ACC_Q, n, {B(0, X, 96), B(3, TB + LINE_BYTES, 0), B(5, ctx->F + n * F12, F12)}, s)) ||
       (r = run(ctx, P_MUL2S, n, {B(3, ctx->F, F12), B(4, ctx->F + n * F12, F12), B(5, ctx->F, F12)}, s)) || (r = run(ctx, P_NORM_RAW, n, {B(3, ctx->F, F12), B(4, ctx->N, RAW)}, s)) ||

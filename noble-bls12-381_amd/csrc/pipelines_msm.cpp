@@ -53,7 +53,7 @@ static int msm_prepare(nbls_ctx* ctx, bool g2, unsigned dims, size_t npoints, co
   return NBLS_OK;
 }
 // Steps 1 to 3: from the bucket fill to the last halving round, for nbw = groups x windows of c bits and M = keys.m * keys.nwin entries.  The caller sizes every buffer.
-struct MsmKeys { unsigned m, dims, nwin, i0, g0, ngroups, n_pts; const void *off, *scalars; };   // the arguments of the keys launch (msm_kernels.hip msm_keys_kernel) but c
+struct MsmKeys { unsigned m, dims, nwin, i0, g0, ngroups, n_pts; const uint32_t* off; const void* scalars; };   // the arguments of the keys launch (msm_kernels.hip msm_keys_kernel) but c
 struct BucketBufs {
   uint32_t *words, *counters;   // 6 M words: keys, values, both sorted, ranks, pair list; 64 counters: [0] longest run, [1 + round] pairs of that round
   uint8_t* tmp; size_t sort_bytes, scan_bytes;   // scratch of the sort and the scan, one after the other in the same bytes, and what each is told it has

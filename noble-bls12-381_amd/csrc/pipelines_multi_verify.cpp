@@ -82,12 +82,12 @@ static int aggregate_keys(nbls_ctx* ctx, size_t n, const AggKeys& agg, const uin
 // Shared messages: the weighted key of every message group, sum_{i : msg_index[i] = g} [r_i]pk_i, from the ladder's projective outputs Pj (n x 3 RAW, set order) -> RPK (affine
 // wire bytes, m x 96).  d_order: the sets sorted by group, d_goff: m + 1 group offsets into it (every group non-empty: checked on the host), STK: the key status of every set (a
 // set whose status is not 0 adds the identity; such a call never counts the combined check).  A group that sums to the zero point cannot go into a Miller loop: *d_gzero = 1 and
-// -G1 stands in for it (grp_zero_kernel); the caller reads the word back with the statuses and does not count the combined check.
+// -G1 stands in for it (agg_fix_zero_kernel); the caller reads the word back with the statuses and does not count the combined check.
 static int group_keys(nbls_ctx* ctx, size_t n, size_t m, size_t maxgroup, const uint32_t* d_order, const uint32_t* d_goff, const int8_t* STK, const uint8_t* Pj, uint8_t* RPK,
                       uint32_t* d_gzero, hipStream_t s) {
   SegSums o;
   const int r = segment_sums(ctx, false, SEG_GRP, n, m, d_goff, d_order, Pj, STK, maxgroup, RPK, &o, s); if (r) return r;
-  LAUNCHCHK(nbls_grp_zero_launch((unsigned)m, o.zero, ctx->neg_g1, RPK, d_gzero, s));
+  LAUNCHCHK(nbls_agg_fix_zero_launch((unsigned)m, o.zero, ctx->neg_g1, RPK, d_gzero, s));
   return NBLS_OK;
 }
 
@@ -186,7 +186,7 @@ int verify_multiple_pipeline(nbls_ctx* ctx, const MultiVerifyIn& in, int* all_ok
   uint8_t *X;
   if ((r = need(ctx, SB_RLC_PER_SET, n * (192 + 384 + 576) + n, &X))) return r;
   uint8_t *G1x = X, *G2x = G1x + n * 192, *E = G2x + n * 384, *V = E + n * 576;
-  LAUNCHCHK(mg ? nbls_grp_interleave_launch((unsigned)n, c + o_idx, PK, ctx->neg_g1, H, SG, G1x, G2x, s) : nbls_rlc_interleave_launch((unsigned)n, PK, ctx->neg_g1, H, SG, G1x, G2x, s));
+  LAUNCHCHK(nbls_rlc_interleave_launch((unsigned)n, mg ? (const uint32_t*)(c + o_idx) : nullptr, PK, ctx->neg_g1, H, SG, G1x, G2x, s));
   if ((r = run(ctx, P_MILLER_RAW2, n, {B(0, G1x, 192), B(1, G2x, 384), B(3, ctx->F, F12)}, s)) || (r = run(ctx, P_NORM_RAW, n, {B(3, ctx->F, F12), B(4, ctx->N, RAW)}, s)) ||
       (r = final_exp_pipeline(ctx, Window(), n, ctx->F, E, s)))
     return r;

@@ -6,6 +6,8 @@
 #include "fp_inv.h"
 #include "pow_exec.h"
 #include "pow_wide.h"
+#include "kernel_parts.h"
+#include "launchers.h"
 
 namespace nbls {
 
@@ -157,17 +159,14 @@ extern "C" __global__ void __launch_bounds__(64) nbls_pow_wide_kernel(unsigned n
 
 }  // namespace nbls
 
-extern "C" int nbls_pow_wide_launch(unsigned n, const void* in, void* out, const void* ops, int nops, int is_fp2, void* stream) {
-  if (n == 0) return 0;
+extern "C" int nbls_pow_wide_launch(unsigned n, const void* in, void* out, const uint8_t* ops, int nops, int is_fp2, hipStream_t stream) {   // one wavefront per element
   static const nbls::WideConsts consts = nbls::wide_consts();
-  hipLaunchKernelGGL(nbls::nbls_pow_wide_kernel, dim3(n), dim3(64), 0, (hipStream_t)stream, n, (const nbls::u32*)in, (nbls::u32*)out, (const unsigned char*)ops, nops, is_fp2, consts);
-  return (int)hipGetLastError();
+  return nbls::launch_1d(nbls::nbls_pow_wide_kernel, 64ull * n, 64, 0, stream, n, in, out, ops, nops, is_fp2, consts);
 }
-extern "C" int nbls_fp_pow_launch(unsigned n, const void* in, void* out, const void* ops, int nops, void* scratch, int is_fp2, void* stream) {   // ops: pow_exec.h op list (device memory); is_fp2: 0 Fp, 7 / 8: Fp2 with that tail (nbls_fp2_pow_kernel); scratch: POW_TAB raw elements per lane
-  if (n == 0) return 0;
-  if (is_fp2) hipLaunchKernelGGL(nbls::nbls_fp2_pow_kernel, dim3((2 * n + 63) / 64), dim3(64), 0, (hipStream_t)stream, n, (const nbls::u32*)in, (nbls::u32*)out, (const unsigned char*)ops, nops, (nbls::u32*)scratch, is_fp2);
-  else hipLaunchKernelGGL(nbls::nbls_fp_pow_kernel, dim3((n + 63) / 64), dim3(64), 0, (hipStream_t)stream, n, (const nbls::u32*)in, (nbls::u32*)out, (const unsigned char*)ops, nops, (nbls::u32*)scratch);
-  return (int)hipGetLastError();
+// ops: pow_exec.h op list (device memory); is_fp2: 0 Fp, 7 / 8: Fp2 with that tail (nbls_fp2_pow_kernel, two lanes per element); scratch: POW_TAB raw elements per lane
+extern "C" int nbls_fp_pow_launch(unsigned n, const void* in, void* out, const uint8_t* ops, int nops, void* scratch, int is_fp2, hipStream_t stream) {
+  if (is_fp2) return nbls::launch_1d(nbls::nbls_fp2_pow_kernel, 2ull * n, 64, 0, stream, n, in, out, ops, nops, scratch, is_fp2);
+  return nbls::launch_1d(nbls::nbls_fp_pow_kernel, n, 64, 0, stream, n, in, out, ops, nops, scratch);
 }
 
 // list[k] = index of the k-th item whose int8 flag is set, *count = their number (order irrelevant): the items of a compressed cyclotomic exponentiation that
@@ -178,15 +177,10 @@ __global__ void nbls_flag_compact_kernel(unsigned n, const signed char* __restri
   if (i < n && flags[i]) list[atomicAdd(count, 1u)] = i;
 }
 }
-extern "C" int nbls_flag_compact_launch(unsigned n, const void* flags, void* list, void* count, void* stream) {
+extern "C" int nbls_flag_compact_launch(unsigned n, const void* flags, uint32_t* list, uint32_t* count, hipStream_t stream) {
   if (n == 0) return 0;
-  if (hipMemsetAsync(count, 0, 4, (hipStream_t)stream) != hipSuccess) return (int)hipGetLastError();
-  hipLaunchKernelGGL(nbls::nbls_flag_compact_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, n, (const signed char*)flags, (nbls::u32*)list, (nbls::u32*)count);
-  return (int)hipGetLastError();
+  const hipError_t e = hipMemsetAsync(count, 0, 4, stream);
+  return e != hipSuccess ? (int)e : nbls::launch_1d(nbls::nbls_flag_compact_kernel, n, 256, 0, stream, n, flags, list, count);
 }
 
-extern "C" int nbls_fp_inv_launch(unsigned n, const void* in, void* out, void* stream) {
-  if (n == 0) return 0;
-  hipLaunchKernelGGL(nbls::nbls_fp_inv_kernel, dim3((n + 63) / 64), dim3(64), 0, (hipStream_t)stream, n, (const nbls::u32*)in, (nbls::u32*)out);
-  return (int)hipGetLastError();
-}
+extern "C" int nbls_fp_inv_launch(unsigned n, const void* in, void* out, hipStream_t stream) { return nbls::launch_1d(nbls::nbls_fp_inv_kernel, n, 64, 0, stream, n, in, out); }

@@ -12,6 +12,7 @@
 #include <atomic>
 #include <mutex>
 #include "vm_exec.h"
+#include "launchers.h"
 
 namespace nbls {
 
@@ -143,7 +144,7 @@ extern "C" __global__ void __launch_bounds__(64) nbls_vm_kernel_ls4(KernelArgs k
 }  // namespace nbls
 
 // host-side launcher (C linkage, used by runtime.cpp)
-extern "C" int nbls_vm_launch(const nbls::KernelArgs* ka, unsigned lds_bytes, void* stream) {
+extern "C" int nbls_vm_launch(const nbls::KernelArgs* ka, unsigned lds_bytes, hipStream_t stream) {
   using namespace nbls;
   if (ka->n_items == 0) return 0;
   unsigned blocks = (ka->n_items + ka->G - 1) / ka->G;
@@ -170,16 +171,16 @@ extern "C" int nbls_vm_launch(const nbls::KernelArgs* ka, unsigned lds_bytes, vo
   if (lds_bytes < lds_floor) lds_bytes = lds_floor;
   if (ka->lsplit == 4) {
     if (ka->shared_consts) return -1;   // lane-split programs are compiled with replicated constants only
-    hipLaunchKernelGGL(nbls_vm_kernel_ls4, dim3(blocks), dim3(64), lds_bytes, (hipStream_t)stream, *ka);
+    hipLaunchKernelGGL(nbls_vm_kernel_ls4, dim3(blocks), dim3(64), lds_bytes, stream, *ka);
   } else {
     static const int fair_mode = (int)env_long("NBLS_FAIR", -1);   // 0 never, 1 always, unset: launches of 2..4 wavefronts per SIMD
     const bool fair = fair_mode >= 0 ? fair_mode != 0 : (blocks > 1024 && blocks <= 4096);
     if (ka->shared_consts) {
-      if (fair) hipLaunchKernelGGL(nbls_vm_kernel_fair_sc, dim3(blocks), dim3(64), lds_bytes, (hipStream_t)stream, *ka);
-      else hipLaunchKernelGGL(nbls_vm_kernel_sc, dim3(blocks), dim3(64), lds_bytes, (hipStream_t)stream, *ka);
+      if (fair) hipLaunchKernelGGL(nbls_vm_kernel_fair_sc, dim3(blocks), dim3(64), lds_bytes, stream, *ka);
+      else hipLaunchKernelGGL(nbls_vm_kernel_sc, dim3(blocks), dim3(64), lds_bytes, stream, *ka);
     } else {
-      if (fair) hipLaunchKernelGGL(nbls_vm_kernel_fair, dim3(blocks), dim3(64), lds_bytes, (hipStream_t)stream, *ka);
-      else hipLaunchKernelGGL(nbls_vm_kernel, dim3(blocks), dim3(64), lds_bytes, (hipStream_t)stream, *ka);
+      if (fair) hipLaunchKernelGGL(nbls_vm_kernel_fair, dim3(blocks), dim3(64), lds_bytes, stream, *ka);
+      else hipLaunchKernelGGL(nbls_vm_kernel, dim3(blocks), dim3(64), lds_bytes, stream, *ka);
     }
   }
   return (int)hipGetLastError();

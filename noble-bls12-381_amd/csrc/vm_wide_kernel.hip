@@ -5,6 +5,8 @@
 #include "wide_exec.h"
 #include "g1_wide.h"
 #include "fp_inv_wide.h"
+#include "kernel_parts.h"
+#include "launchers.h"
 
 namespace nbls {
 
@@ -211,22 +213,17 @@ extern "C" __global__ void __launch_bounds__(64) nbls_fp_inv_wide_kernel(unsigne
 }
 }  // namespace nbls
 
-extern "C" int nbls_vm_wide_launch(const nbls::KernelArgs* ka, unsigned lds_bytes, void* stream) {
+extern "C" int nbls_vm_wide_launch(const nbls::KernelArgs* ka, unsigned lds_bytes, hipStream_t stream) {   // one workgroup per item
   using namespace nbls;
   if (ka->n_items == 0) return 0;
   if (ka->lsplit != 1 || ka->W > 16 || lds_bytes > 64 * 1024) return -1;
-  const unsigned waves = (ka->W + 3) / 4;
-  hipLaunchKernelGGL(nbls_vm_kernel_wide, dim3(ka->n_items), dim3(64 * waves), lds_bytes, (hipStream_t)stream, *ka);
-  return (int)hipGetLastError();
+  const unsigned block = 64 * ((ka->W + 3) / 4);
+  return launch_1d(nbls_vm_kernel_wide, (uint64_t)ka->n_items * block, block, lds_bytes, stream, *ka);
 }
-extern "C" int nbls_g1_wide_combine_launch(const void* S, int nwin, int shift, void* out, unsigned sums, void* stream) {
+extern "C" int nbls_g1_wide_combine_launch(const void* S, int nwin, int shift, void* out, unsigned sums, hipStream_t stream) {   // one wavefront per sum
   if (nwin < 1) return -1;
-  if (sums == 0) return 0;
-  hipLaunchKernelGGL(nbls::nbls_g1_wide_combine_kernel, dim3(sums), dim3(64), 0, (hipStream_t)stream, (const nbls::u32*)S, nwin, shift, (nbls::u32*)out);
-  return (int)hipGetLastError();
+  return nbls::launch_1d(nbls::nbls_g1_wide_combine_kernel, 64ull * sums, 64, 0, stream, S, nwin, shift, out);
 }
-extern "C" int nbls_fp_inv_wide_launch(unsigned n, const void* in, void* out, void* stream) {
-  if (n == 0) return 0;
-  hipLaunchKernelGGL(nbls::nbls_fp_inv_wide_kernel, dim3((n + 3) / 4), dim3(64), 0, (hipStream_t)stream, n, (const nbls::u32*)in, (nbls::u32*)out);
-  return (int)hipGetLastError();
+extern "C" int nbls_fp_inv_wide_launch(unsigned n, const void* in, void* out, hipStream_t stream) {   // sixteen lanes per element
+  return nbls::launch_1d(nbls::nbls_fp_inv_wide_kernel, 16ull * n, 64, 0, stream, n, in, out);
 }

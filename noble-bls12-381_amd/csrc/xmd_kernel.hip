@@ -4,6 +4,8 @@
 // verifyBatch / sign call needs no host pre-pass over the messages.  Bytes are fed one at a time into a block buffer in LDS (DevSha below).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "kernel_parts.h"
+#include "launchers.h"
 
 namespace nbls {
 typedef uint32_t u32;
@@ -145,8 +147,8 @@ extern "C" __global__ void __launch_bounds__(64) nbls_xmd_kernel(unsigned n, con
 }
 }  // namespace nbls
 
-extern "C" int nbls_xmd_launch(unsigned n, const void* msgs, const void* offsets, const void* dst, unsigned dst_len, void* out, unsigned len_in_bytes, void* bad_flag, void* stream) {   // bad_flag: NULL, or a device word that is set when an offset pair is not monotonic
-  if (n == 0) return 0;
-  hipLaunchKernelGGL(nbls::nbls_xmd_kernel, dim3((n + 63) / 64), dim3(64), 0, (hipStream_t)stream, n, (const uint8_t*)msgs, (const nbls::u32*)offsets, (const uint8_t*)dst, dst_len, (uint8_t*)out, len_in_bytes, (nbls::u32*)bad_flag);
-  return (int)hipGetLastError();
+// bad_flag: NULL, or a device word that is set when an offset pair is not monotonic
+extern "C" int nbls_xmd_launch(unsigned n, const void* msgs, const void* offsets, const void* dst, unsigned dst_len, void* out, unsigned len_in_bytes, uint32_t* bad_flag,
+                               hipStream_t stream) {
+  return nbls::launch_1d(nbls::nbls_xmd_kernel, n, 64, 0, stream, n, msgs, offsets, dst, dst_len, out, len_in_bytes, bad_flag);
 }

@@ -27,6 +27,9 @@ def test_library_exports_every_declared_symbol():
     # and nothing of the test-only oracle / simulator leaks into the product library
     out = subprocess.check_output(['nm', '-D', '--defined-only', os.path.join(ROOT, 'noble-bls12-381_amd', 'libnbls.so')]).decode()
     assert 'oracle_' not in out and 'nbls_sim_' not in out
+    # the kernels' launch wrappers (csrc/launchers.h) stay internal, whatever they are called
+    launchers = [line.split()[-1] for line in out.splitlines() if line.split() and line.split()[-1].endswith('_launch')]
+    assert not launchers, launchers
 
 
 def test_no_cpu_fallback():

@@ -3,10 +3,10 @@ known multiple of G1 from the oracle: a tuple is pi = [s]G1, C = [c]G1 with the 
 are known too (kzg_cases.weight).  `model` restates the combined check in those integers; every case first asserts that its input reaches the branch it was built for, then
 asserts the call's full (all_ok, status) answer, stated beforehand.  Nothing expected comes from the code under test.
 
-  A  sizes 257 and 600 (verifier), 300 blobs (prover): the second trip of kzg_sum_kernel's loop `i += 256`; the second block of kzg_fix_zero_kernel, kzg_item_status_kernel and
+  A  sizes 257 and 600 (verifier), 300 blobs (prover): the second trip of kzg_sum_kernel's loop `i += 256`; the second block of agg_fix_zero_kernel (a replaced point at index 256: six threads a point), kzg_item_status_kernel and
      kzg_prove_tail_kernel (a zero proof, a zero product and a status past index 256); the per-item pass -- P_ACC_Q with table_stride = 0, final_exp_pipeline, rlc_is_one --
      on more than 65 items
-  B  the zero flags BST[0..2] of the three partial sums of B and the flags of A and B, one row per combination: agg_points_kernel's identity and kzg_fix_zero_kernel's
+  B  the zero flags BST[0..2] of the three partial sums of B and the flags of A and B, one row per combination: agg_points_kernel's identity and agg_fix_zero_kernel's
      generator in the combined check, both arms of kzg_item_status_kernel (pz ? xz : !xz && one) with xz = 1 under a non-zero proof (row 6) and xz = 0 under a zero one (row 8)
   C  the weights: an error that cancels in the plain sums is caught under every seed; an error built to cancel under the documented r_i is accepted with that seed -- which
      pins r_i and that one r_i multiplies C_i, z_i pi_i and y_i -- and caught with any other seed and with the seed of the OS

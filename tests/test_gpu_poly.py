@@ -139,8 +139,9 @@ def test_bad_coefficients_leave_the_neighbours_alone(eng, sides, golden, g2):
     vec = golden['codec']['g2' if g2 else 'g1']
     sub = [hx(v['hex']) for v in vec if 'subgroup' in v['result']][0]
     noroot = [hx(v['hex']) for v in vec if v['result'] == ('Failed to find a square root' if g2 else 'Invalid compressed G1 point')][0]
-    shapes = [(3, 4), (5, 3), (2, 9), (7, 5), (4, 2), (9, 17), (3, 3)]
+    shapes = [(3, 4), (5, 3), (2, 9), (7, 5), (4, 2), (9, 17), (3, 3), (2, 2)]
     polys = [[rnd.randrange(1, R) for _ in range(t)] for t, _ in shapes]
+    polys[7] = [0, 0]                  # the zero polynomial: status 1 and 0xc0 00.. beside the statuses >= 2 and their all-zero bytes, in one call
     idsets = [[rnd.getrandbits(256) for _ in range(m)] for _, m in shapes]
     groups = [(side.points(c), i) for c, i in zip(polys, idsets)]
     bad = [(list(c), i) for c, i in groups]
@@ -156,7 +157,8 @@ def test_bad_coefficients_leave_the_neighbours_alone(eng, sides, golden, g2):
         if g in want:
             assert st[g] == [want[g]] * m and got[g] == [bytes(side.e)] * m, g
         else:
-            assert st[g] == [0] * m == cst[k] and got[g] == clean[k] == side.expected(polys[g], idsets[g])[0], g
+            pts, wst = side.expected(polys[g], idsets[g])
+            assert wst == ([1] if g == 7 else [0]) * m and st[g] == wst == cst[k] and got[g] == clean[k] == pts, g
             k += 1
     # the other order in one group
     bad[5][0][4], bad[5][0][7] = sub, noroot

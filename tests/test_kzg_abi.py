@@ -31,7 +31,7 @@ def test_symbols_exported(lib):
     for nm in NAMES:
         assert nm in exported, nm
         assert hasattr(lib, nm)
-    for nm in ('nbls_kzg_roots_launch', 'nbls_kzg_eval_launch', 'nbls_kzg_items_launch', 'nbls_kzg_fix_zero_launch', 'nbls_kzg_item_scalars_launch', 'nbls_kzg_item_status_launch'):
+    for nm in ('nbls_kzg_roots_launch', 'nbls_kzg_eval_launch', 'nbls_kzg_items_launch', 'nbls_agg_fix_zero_launch', 'nbls_kzg_item_scalars_launch', 'nbls_kzg_item_status_launch'):
         assert nm not in exported, nm          # the kernels' launch wrappers stay internal
     assert not any('nbls_sim_' in nm for nm in exported)
     assert lib.nbls_abi_version() == 5
