@@ -421,6 +421,49 @@ int nbls_kzg_compute_proofs(nbls_ctx* ctx, const nbls_kzg_setup* setup, size_t n
 int nbls_kzg_compute_blob_proofs(nbls_ctx* ctx, const nbls_kzg_setup* setup, size_t n, const uint8_t* blobs, const uint8_t* commitments48 /* or NULL */,
                                  uint8_t* out_commitments48 /* required when commitments48 == NULL */, uint8_t* out_proofs48, int8_t* status /* n, may be NULL */);
 
+/* PeerDAS (EIP-7594, polynomial-commitments-sampling.md: compute_cells, compute_cells_and_kzg_proofs) and the transform it rests on.  Conventions as above: N = 2^log2_n,
+ * omega_N = 7^((r - 1) / N), w_j = omega_N^rev(j), elements 32 bytes big-endian and CANONICAL, blobs = the values on w_j in bit-reversed order.  NOT an interface for secrets.
+ *
+ * nbls_fr_ntt: the transform between the two forms of n polynomials.  Polynomial i has the coefficients c_0 .. c_(N-1) in natural order, lowest first; its values are
+ *   v_j = p_i(s_i w_j)   in the bit-reversed order of nbls_fr_eval_roots,   s_i = shift32[i], or 1 when shift32 == NULL.
+ * NBLS_NTT_TO_COEFFS maps values to coefficients, NBLS_NTT_TO_EVALS coefficients to values.  status[i] (may be NULL): 0; NBLS_ST_NON_CANONICAL when an element or the shift
+ * is >= r; 5 when the shift is 0 mod r; in both cases row i is all-zero and the neighbours are not disturbed.  One copy in, one kernel (a workgroup per polynomial, the whole
+ * polynomial in LDS: a decimation network that takes natural order to bit-reversed order and back, so that no permutation pass exists), one copy out; the tables of the roots
+ * and of their inverses are built on first use of a size and kept with the context.  NBLS_EINVAL before any device work for log2_n outside 1 .. 12, an unknown direction, a
+ * NULL context, missing buffers with n > 0, more than 2^24 elements in the call; n = 0 is NBLS_OK. */
+#define NBLS_NTT_TO_COEFFS 0
+#define NBLS_NTT_TO_EVALS 1
+int nbls_fr_ntt(nbls_ctx* ctx, unsigned log2_n /* 1 .. 12 */, int dir, size_t n, const uint8_t* in32 /* n << log2_n */, const uint8_t* shift32 /* n, or NULL */,
+                uint8_t* out32 /* n << log2_n */, int8_t* status /* n, may be NULL */);
+/* compute_cells for n blobs with c = 2^log2_cell elements per cell (0 <= log2_cell <= log2_n; mainnet: log2_n = 12, log2_cell = 6, 128 cells of 64 elements).  With g = omega_2N
+ * and p the blob's polynomial, the extension in bit-reversed order over 2 N is  ext[i] = blob[i],  ext[N + i] = p(g w_i);  cell k is ext[c k .. c k + c), its points are
+ * h_k omega_c^rev(j) with h_k = g^rev(k) over log2_n + 1 - log2_cell bits (coset_for_cell).  out_cells holds, per blob, the 2 N elements in cell order: the blob's own bytes,
+ * then the coset values.  One chain per blob in ONE kernel: the canonical check, to coefficients, times g^i / N, to values; nothing crosses the host in between.
+ * status[i] (may be NULL): 0, or NBLS_ST_NON_CANONICAL for a blob with an element >= r: ALL its cells are then all-zero bytes, the neighbours are not disturbed.
+ * NBLS_EINVAL before any device work for log2_n outside 1 .. 12, log2_cell > log2_n, a NULL context, missing buffers with n > 0, more than 2^24 elements in the call; n = 0 is
+ * NBLS_OK.  The formulas are the EIP's; the consensus-spec test vectors have not been run against this call. */
+int nbls_kzg_compute_cells(nbls_ctx* ctx, unsigned log2_n, unsigned log2_cell, size_t n, const uint8_t* blobs /* n * (32 << log2_n) */,
+                           uint8_t* out_cells /* n * (64 << log2_n) */, int8_t* status /* n, may be NULL */);
+/* nbls_kzg_monomial: the setup's g1_monomial in device memory, decoded ONCE: monomial48 holds the 2^log2_n compressed points [tau^i]G1, i = 0 .. N - 1, in NATURAL order.
+ * Decoding, the subgroup check, status[], NBLS_EDECODE for an entry that does not decode or is the zero point (*out = NULL), lifetime and the device rule are those of
+ * nbls_kzg_setup_create; the points are kept in the batched MSM's converted form.  A handle type of its own: the Lagrange setup is not accepted in its place. */
+typedef struct nbls_kzg_monomial nbls_kzg_monomial;
+int  nbls_kzg_monomial_create(nbls_ctx* ctx, unsigned log2_n, const uint8_t* monomial48 /* 2^log2_n compressed G1 points */, int8_t* status /* 2^log2_n, may be NULL */,
+                              nbls_kzg_monomial** out);
+void nbls_kzg_monomial_destroy(nbls_kzg_monomial* m);
+int  nbls_kzg_monomial_log2n(const nbls_kzg_monomial* m, unsigned* log2_n);
+/* compute_cells_and_kzg_proofs: the cells of nbls_kzg_compute_cells and, for every cell k, the proof  sum_i [q_i] [tau^i]G1  of the floor quotient q of p by the cell's
+ * vanishing polynomial X^c - s_k (s_k = h_k^c) in coefficient form:  q_i = 0 for i >= N - c,  q_i = p_(i + c) + s_k q_(i + c)  downwards.  The coefficients stay on the device
+ * after the transform; a kernel writes the 2 N / c quotient rows of every blob as big-endian scalars straight into the batched MSM's scalar array (one lane per chain of the
+ * recurrence), the rows form of the batched MSM runs against the converted basis, then to-affine, compression and the closing kernel of the prover calls.  No FK20: 2 N / c sums
+ * of N points per blob.  The batched MSM takes 2^22 scalars and 2^20 rows a pass, so the call works through the blobs in chunks of whole blobs (8 mainnet blobs; fewer with
+ * NBLS_TUNE_CELLS_CHUNK) on one stream; the bytes do not depend on the chunks.  out_proofs48: n * (2 N / c) compressed points, blob by blob, cell by cell; ZERO POINTS ARE VALID
+ * (0xc0 00.., status 0: a polynomial of degree < c).  status[i] (may be NULL): 0, or NBLS_ST_NON_CANONICAL: that blob's cells are all-zero and its proofs 48 zero bytes each.
+ * Returns NBLS_OK whatever the blobs hold; NBLS_EINVAL before any device work for a missing pointer, n = 0, log2_cell > log2_n, a basis created on another device, more than
+ * 2^24 elements in the call, or one blob alone above the bounds of a pass: (2 N / c) * N > 2^22. */
+int nbls_kzg_compute_cells_and_proofs(nbls_ctx* ctx, const nbls_kzg_monomial* monomial, unsigned log2_cell, size_t n, const uint8_t* blobs, uint8_t* out_cells,
+                                      uint8_t* out_proofs48 /* n * (2 N / c) * 48 */, int8_t* status /* n, may be NULL */);
+
 /* One rank's share of a verifyBatch spread over several GPUs (one process per GPU): the Miller product of this rank's n
  * (key, message) pairs, times millerLoop(-G, S) on the ONE rank that passes the signature (d_sig96 = NULL elsewhere), WITHOUT the
  * final exponentiation, as 576 wire bytes in device memory.  Ranks all-gather their partials and finish with
@@ -450,7 +493,7 @@ const char* nbls_config_describe(void);   /* "NBLS_X=value(env|default) ...": ev
    nbls_verify_aggregates_indexed_shared, scratch slots 48 .. 50 (additions only, same version); then nbls_fr_op_batch, nbls_lagrange_at_zero, nbls_g2_combine_shares,
    nbls_g1_combine_shares, NBLS_FROP_*, NBLS_ST_BAD_IDS, scratch slots 51 .. 56 (additions only, same version); then nbls_field_kernel_raw (addition only, same version); then nbls_g1_poly_eval,
    nbls_g2_poly_eval, nbls_extra_program_kernel, NBLS_TUNE_POLY_SLAB, scratch slots 57 .. 61 (additions only, same version); then nbls_g1_msm_batch, nbls_g2_msm_batch,
-   nbls_g1_msm_rows, nbls_g2_msm_rows, NBLS_TUNE_MSMB_WINDOW / _BIG / _SLAB, the names "dbladd_g1" / "dbladd_g2" of nbls_extra_program_kernel, scratch slots 62 .. 63 (additions only, same version); then nbls_map_uniform_batch (addition only, same version); then nbls_fr_eval_roots, nbls_kzg_verify_proofs, nbls_kzg_verify_blobs, NBLS_ST_NON_CANONICAL, scratch slots 64 .. 68 (additions only, same version); then nbls_kzg_setup_create / _destroy / _log2n, nbls_fr_quotient_roots, nbls_kzg_commit_blobs, nbls_kzg_compute_proofs, nbls_kzg_compute_blob_proofs, scratch slots 69 .. 70 (additions only, same version); with the MSM calls ONE CHANGE TO EXISTING CALLS, same version: nbls_g1_msm / nbls_g2_msm write all-zero output bytes when the status is 1 (the sum is the
+   nbls_g1_msm_rows, nbls_g2_msm_rows, NBLS_TUNE_MSMB_WINDOW / _BIG / _SLAB, the names "dbladd_g1" / "dbladd_g2" of nbls_extra_program_kernel, scratch slots 62 .. 63 (additions only, same version); then nbls_map_uniform_batch (addition only, same version); then nbls_fr_eval_roots, nbls_kzg_verify_proofs, nbls_kzg_verify_blobs, NBLS_ST_NON_CANONICAL, scratch slots 64 .. 68 (additions only, same version); then nbls_kzg_setup_create / _destroy / _log2n, nbls_fr_quotient_roots, nbls_kzg_commit_blobs, nbls_kzg_compute_proofs, nbls_kzg_compute_blob_proofs, scratch slots 69 .. 70 (additions only, same version); then nbls_fr_ntt, NBLS_NTT_*, nbls_kzg_compute_cells, nbls_kzg_monomial_create / _destroy / _log2n, nbls_kzg_compute_cells_and_proofs, NBLS_TUNE_CELLS_CHUNK, scratch slots 71 .. 73 (additions only, same version); with the MSM calls ONE CHANGE TO EXISTING CALLS, same version: nbls_g1_msm / nbls_g2_msm write all-zero output bytes when the status is 1 (the sum is the
    zero point).  The bytes were unspecified there before (what the affine conversion made of a Z that is 0 mod p: in G1 a zero x and an arbitrary y); the status, and every output with status 0, are unchanged.
    nbls_msm_dev, which leaves its result on the device, is not changed.
    4 (round 6): nbls_hw_queues, NBLS_TUNE_WIDE_MAX, NBLS_TUNE_H2C_NORM_MIN, NBLS_TUNE_INV_WIDE_MAX, NBLS_TUNE_LS_MAX / _LS2_MAX (additions only); the library sets GPU_MAX_HW_QUEUES = 22 at load when the variable is unset (see nbls_pool_init below).
@@ -532,6 +575,7 @@ int nbls_field_kernel_raw(nbls_ctx* ctx, int kind, int form, size_t n, const uin
 #define NBLS_TUNE_MSMB_WINDOW 16      /* window width of nbls_g*_msm_batch / _rows: 4, 6, 8, 10 or 12 bits; 0 (default) = chosen per call: the width that minimises points * windows + windows * c * 2^(c - 1) for the mean group */
 #define NBLS_TUNE_MSMB_BIG 17         /* points (as given) above which a group of nbls_g*_msm_batch / _rows runs through the pipeline of nbls_g*_msm on the same stream (default 16384; 0 = the default) */
 #define NBLS_TUNE_MSMB_SLAB 18        /* budget of one slab of groups: sum over its groups of (points after the split) * windows + windows * c * 2^(c - 1), the sorted entries and gathered bucket points that are in scratch at a time; a group that exceeds it alone is a slab of its own (default 2^23; 0 = the default) */
+#define NBLS_TUNE_CELLS_CHUNK 20      /* (19 stays unassigned: tests/test_msm_batch_abi.py pins it as the first unknown key behind the batched MSM's) blobs that nbls_kzg_compute_cells_and_proofs hands to the batched MSM in one pass; 0 (default) = as many whole blobs as its bounds of 2^22 scalars and 2^20 rows take (8 mainnet blobs); a larger value than that changes nothing.  The bytes do not depend on it: it lets a test cross chunk borders with small blobs */
 int nbls_set_tuning(nbls_ctx* ctx, int key, long long value);
 int nbls_program_count(void);                 /* number of step programs; timing slot nbls_program_count() = the inversion kernel */
 const char* nbls_program_name(int prog);

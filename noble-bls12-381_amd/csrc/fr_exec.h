@@ -328,4 +328,120 @@ NBLS_FR_HD Fr fr_quot_lane(const uint8_t* f32, const Fr* roots, const Fr& y, uin
 // q_m from the workgroup's sum (plain) and z = w_m (Montgomery form): one inversion, on the lane that owns m
 NBLS_FR_HD Fr fr_quot_within(const Fr& sum, const Fr& z) { return fr_neg(fr_mul(sum, fr_inv(z))); }
 
+// ---- The transform between the two forms of a polynomial of N = 2^k coefficients, k = 1 .. 12 (kzg_ntt_kernel and nbls_sim_fr_ntt; the cells of EIP-7594 are built on it):
+//   coefficients c_0 .. c_{N-1}, natural order   <->   values v_j = p(s w_j) in the bit-reversed order of the table above, for a shift s != 0 (1: the roots themselves).
+// A workgroup of `lanes` lanes owns one polynomial, resident in shared memory as `a`, 8 N words laid out [limb][index]: a wavefront that walks consecutive indices reads
+// consecutive banks.  The network needs no permutation pass: X^(2 len) - zeta^2 splits into X^len - zeta and X^len + zeta, so block b of a stage with half-length len reduces
+//   lo' = lo + zeta hi,   hi' = lo - zeta hi,   zeta = table[2 b]
+// (the entry of omega^rev(2 b): the same for every butterfly of the block), from len = N / 2 down to 1 -- natural order in, bit-reversed out.  The way back undoes the stages in
+// reverse order, lo = lo' + hi', hi = (lo' - hi') / zeta with the table of the inverse roots (fr_inv_root_index), and leaves every coefficient times N.  The block of
+// the stage with len = N / 2 has zeta = 1: its product is not formed (the stage's, not the operand's, property).  Elements stay plain throughout (plain x Montgomery is plain);
+// the tables, the shift's powers and 1 / N are in Montgomery form.  A stage is fr_ntt_stage on every lane, then a barrier; lane t owns the butterflies t, t + lanes, ..
+// Lanes per polynomial: 512 = eight wavefronts, two on every SIMD of the compute unit the polynomial occupies (at N = 4096 its LDS admits one workgroup), four butterflies per
+// lane and stage at N = 4096.  The kernel needs 152 VGPRs: a workgroup of 1024 lanes is held to 128 and spills (measured: 64 bytes of private memory per lane)
+#ifndef NBLS_NTT_LOG2_LANES
+#define NBLS_NTT_LOG2_LANES 9
+#endif
+enum { FR_NTT_LOG2_LANES = NBLS_NTT_LOG2_LANES, FR_NTT_LANES = 1 << FR_NTT_LOG2_LANES };
+// the table of the inverse roots is a permutation of the table of roots: (1 / omega)^rev(j) = omega^(N - rev(j)) = entry rev(N - rev(j) mod N)
+NBLS_FR_HD uint32_t fr_inv_root_index(unsigned log2_n, uint32_t j) { return fr_bitrev(((1u << log2_n) - fr_bitrev(j, log2_n)) & ((1u << log2_n) - 1), log2_n); }
+enum FrNttMode { FR_NTT_TO_COEFFS = 0, FR_NTT_TO_EVALS = 1, FR_NTT_CELLS = 2 };   // (2: compute_cells' chain -- to coefficients, times g^i / N, to values on the coset)
+NBLS_FR_HD Fr fr_load_q(const uint8_t* in32) {   // fr_store_q's way back
+#if defined(__HIP_DEVICE_COMPILE__)
+  const uint4 hi = ((const uint4*)in32)[0], lo = ((const uint4*)in32)[1];   // (16-byte aligned: a row of a staged or carved block)
+  return Fr{{fr_bswap32(lo.w), fr_bswap32(lo.z), fr_bswap32(lo.y), fr_bswap32(lo.x), fr_bswap32(hi.w), fr_bswap32(hi.z), fr_bswap32(hi.y), fr_bswap32(hi.x)}};
+#else
+  return fr_load_be(in32);
+#endif
+}
+NBLS_FR_HD Fr fr_ntt_get(const uint32_t* a, uint32_t N, uint32_t i) {
+  Fr v;
+#pragma unroll
+  for (int l = 0; l < FR_NL; l++) v.l[l] = a[l * N + i];
+  return v;
+}
+NBLS_FR_HD void fr_ntt_put(uint32_t* a, uint32_t N, uint32_t i, const Fr& v) {
+#pragma unroll
+  for (int l = 0; l < FR_NL; l++) a[l * N + i] = v.l[l];
+}
+// x^e for an index e of at most `bits` bits: all of them are walked
+NBLS_FR_HD Fr fr_pow_index(const Fr& x, uint32_t e, unsigned bits) {
+  Fr acc = fr_one();
+  for (int b = (int)bits - 1; b >= 0; b--) {
+    acc = fr_sqr(acc);
+    acc = fr_select((uint32_t)0 - ((e >> b) & 1), fr_mul(acc, x), acc);
+  }
+  return acc;
+}
+// the lane's elements t, t + lanes, .. of a polynomial into `a`; returns all ones when one of them is >= r
+NBLS_FR_HD uint32_t fr_ntt_load(const uint8_t* in32, uint32_t N, uint32_t lane, uint32_t lanes, uint32_t* a) {
+  uint32_t bad = 0;
+  for (uint32_t i = lane; i < N; i += lanes) {
+    const Fr v = fr_load_q(in32 + 32ull * i);
+    bad |= fr_ge_r_mask(v);
+    fr_ntt_put(a, N, i, v);
+  }
+  return bad;
+}
+// the shift of a polynomial, read by one lane: -> s (Montgomery form; 1 / s where `invert`: the one inversion of the way back), *bad = all ones when it is >= r, *zero when
+// it is 0 mod r (which is then also what the inversion returns: nobody uses it)
+NBLS_FR_HD Fr fr_ntt_shift(const uint8_t* shift32, bool invert, uint32_t* bad, uint32_t* zero) {
+  const Fr raw = fr_load_be(shift32), s = fr_mul(raw, fr_r2());
+  *bad = fr_ge_r_mask(raw); *zero = fr_is_zero_mask(s);
+  return invert ? fr_inv(s) : s;
+}
+// the lane's elements of `a` times f (NULL: 1) and, element i, times s^i (NULL: s = 1): the lane starts at s^lane and steps by s^lanes.  coef_out (may be NULL): the
+// elements after the factor f and before the powers, as 32 bytes big-endian -- the coefficients that the cell proofs read
+NBLS_FR_HD void fr_ntt_scale(uint32_t* a, uint32_t N, uint32_t lane, uint32_t lanes, unsigned log2_lanes, const Fr* f, const Fr* s, uint8_t* coef_out) {
+  Fr pw = fr_one(), step = pw;
+  if (s) {
+    pw = fr_pow_index(*s, lane, log2_lanes);
+    step = *s;
+    for (unsigned b = 0; b < log2_lanes; b++) step = fr_sqr(step);
+  }
+  for (uint32_t i = lane; i < N; i += lanes) {
+    Fr v = fr_ntt_get(a, N, i);
+    if (f) v = fr_mul(v, *f);
+    if (coef_out) fr_store_q(v, coef_out + 32ull * i);
+    if (s) { v = fr_mul(v, pw); pw = fr_mul(pw, step); }
+    fr_ntt_put(a, N, i, v);
+  }
+}
+// one stage for one lane: half-length 2^log2_len; table = the roots (towards the values) or the inverse roots (`inverse`: towards the coefficients)
+NBLS_FR_HD void fr_ntt_stage(uint32_t* a, unsigned log2_n, unsigned log2_len, bool inverse, const Fr* table, uint32_t lane, uint32_t lanes) {
+  const uint32_t N = 1u << log2_n, len = 1u << log2_len;
+  const bool unit = log2_len + 1 == log2_n;   // the one block of the stage has zeta = 1
+  for (uint32_t b = lane; b < N / 2; b += lanes) {
+    const uint32_t blk = b >> log2_len, lo = (blk << (log2_len + 1)) | (b & (len - 1)), hi = lo + len;
+    const Fr u = fr_ntt_get(a, N, lo), v = fr_ntt_get(a, N, hi);
+    if (inverse) {
+      const Fr d = fr_sub(u, v);
+      fr_ntt_put(a, N, lo, fr_add(u, v));
+      fr_ntt_put(a, N, hi, unit ? d : fr_mul(d, table[2 * blk]));
+    } else {
+      const Fr t = unit ? v : fr_mul(v, table[2 * blk]);
+      fr_ntt_put(a, N, lo, fr_add(u, t));
+      fr_ntt_put(a, N, hi, fr_sub(u, t));
+    }
+  }
+}
+// the lane's elements of `a` as 32 bytes big-endian each
+NBLS_FR_HD void fr_ntt_store(const uint32_t* a, uint32_t N, uint32_t lane, uint32_t lanes, uint8_t* out32) {
+  for (uint32_t i = lane; i < N; i += lanes) fr_store_q(fr_ntt_get(a, N, i), out32 + 32ull * i);
+}
+
+// ---- The quotient rows of the cell proofs (compute_cells_and_kzg_proofs of EIP-7594; kzg_cell_rows_kernel and nbls_sim_kzg_cell_rows).  Cell k of a polynomial p of N
+// coefficients holds its values on the coset h_k <omega_c>, whose vanishing polynomial is X^c - s_k, s_k = h_k^c = entry k of the table of the 2 N / c roots of unity.  The
+// proof's quotient is the floor quotient of p by it in coefficient form:  q_i = 0 for i >= N - c,  q_i = p_(i + c) + s_k q_(i + c)  downwards -- c independent chains of N / c
+// steps.  A lane walks chain j of one row (i = j mod c) and writes it as big-endian scalars, the form the MSM reads; coefficients plain, s in Montgomery form
+NBLS_FR_HD void fr_cell_chain(const uint8_t* coef32, unsigned log2_n, unsigned log2_cell, uint32_t j, const Fr& s, uint8_t* row32) {
+  const uint32_t N = 1u << log2_n, c = 1u << log2_cell;
+  Fr q = fr_zero();
+  for (uint32_t i = N - c + j;; i -= c) {
+    fr_store_q(q, row32 + 32ull * i);
+    if (i < c) break;
+    q = fr_add(fr_load_q(coef32 + 32ull * i), fr_mul(q, s));   // q_(i - c)
+  }
+}
+
 }  // namespace nbls

@@ -96,6 +96,78 @@ __global__ void __launch_bounds__(EV) kzg_quotient_kernel(u32 log2_n, const uint
   if (t == hit % EV) fr_store_q(fr_select(bad, fr_zero(), fr_quot_within(part[0], z)), q32 + 32ull * hit);
 }
 
+// ---- The transform (nbls_fr_ntt), the cells of EIP-7594 (nbls_kzg_compute_cells) and the quotient rows of their proofs (pipelines_kzg_cells.cpp); fr_exec.h has the network.
+constexpr int NT = FR_NTT_LANES;
+// the table of the inverse roots, (1 / omega)^rev(j): what the stages towards the coefficients divide by.  A permutation of the table of roots, made once per context and log2_n
+__global__ void kzg_inv_roots_kernel(u32 log2_n, const Fr* __restrict__ roots, Fr* __restrict__ table) {
+  const u32 j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j < (1u << log2_n)) table[j] = roots[fr_inv_root_index(log2_n, j)];
+}
+// One workgroup per polynomial, the whole polynomial in dynamic LDS (32 N bytes: 128 KB at N = 4096), one barrier per stage.  mode (FrNttMode):
+//   TO_COEFFS  values in -> the stages with the inverse roots -> times 1 / N and (1 / s)^i -> coefficients out
+//   TO_EVALS   coefficients in, times s^i -> the stages with the roots -> values out
+//   CELLS      a blob in (shift32 = g = omega_2N for every blob: shift_stride = 0) -> its bytes to the first half of the output row -> coefficients (to coef32 as well, where
+//              given) -> times g^i -> values on the coset to the second half
+// in32 / out32 / coef32 are 16-byte aligned; out_stride = the bytes of an output row.  A polynomial with an element or a shift >= r (status NBLS_ST_NON_CANONICAL), or with a
+// shift that is 0 mod r (status 5), leaves all-zero rows; the branch is the workgroup's.  One lane inverts the shift on the way to the coefficients; the others wait
+__global__ void __launch_bounds__(NT) kzg_ntt_kernel(u32 log2_n, u32 mode, const uint8_t* __restrict__ in32, const uint8_t* __restrict__ shift32, u32 shift_stride,
+                                                     const Fr* __restrict__ roots, const Fr* __restrict__ iroots, uint8_t* __restrict__ out32, u64 out_stride,
+                                                     uint8_t* __restrict__ coef32, int8_t* __restrict__ status) {
+  extern __shared__ u32 a[];
+  __shared__ Fr sh_s;
+  __shared__ u32 sh_bad, sh_zero;
+  const u32 N = 1u << log2_n, t = threadIdx.x;
+  const u64 p = blockIdx.x;
+  const uint8_t* f32 = in32 + ((p * 32) << log2_n);
+  uint8_t* o32 = out32 + p * out_stride;
+  uint8_t* c32 = coef32 ? coef32 + ((p * 32) << log2_n) : nullptr;
+  if (t == 0) {
+    u32 bad = 0, zero = 0;
+    if (shift32) sh_s = fr_ntt_shift(shift32 + (u64)shift_stride * p, mode == FR_NTT_TO_COEFFS, &bad, &zero);
+    sh_bad = bad; sh_zero = zero;
+  }
+  __syncthreads();
+  if (fr_ntt_load(f32, N, t, NT, a)) atomicOr(&sh_bad, 0xffffffffu);
+  __syncthreads();
+  const int st = sh_bad ? NBLS_ST_NON_CANONICAL : sh_zero ? 5 : 0;
+  if (t == 0 && status) status[p] = (int8_t)st;
+  if (st) {
+    for (u64 j = t; j < out_stride / 16; j += NT) ((uint4*)o32)[j] = make_uint4(0u, 0u, 0u, 0u);
+    if (c32) for (u32 j = t; j < 2 * N; j += NT) ((uint4*)c32)[j] = make_uint4(0u, 0u, 0u, 0u);
+    return;
+  }
+  const Fr s = shift32 ? sh_s : fr_one(), ninv = fr_inv_pow2(log2_n);
+  if (mode == FR_NTT_TO_EVALS) {
+    if (shift32) fr_ntt_scale(a, N, t, NT, FR_NTT_LOG2_LANES, nullptr, &s, nullptr);
+    __syncthreads();
+  } else {
+    for (u32 ll = 0; ll < log2_n; ll++) { fr_ntt_stage(a, log2_n, ll, true, iroots, t, NT); __syncthreads(); }
+    if (mode == FR_NTT_TO_COEFFS) {   // (the lane scales and stores its own elements: no barrier between the two)
+      fr_ntt_scale(a, N, t, NT, FR_NTT_LOG2_LANES, &ninv, shift32 ? &s : nullptr, nullptr);
+      fr_ntt_store(a, N, t, NT, o32);
+      return;
+    }
+    for (u32 j = t; j < 2 * N; j += NT) ((uint4*)o32)[j] = ((const uint4*)f32)[j];
+    fr_ntt_scale(a, N, t, NT, FR_NTT_LOG2_LANES, &ninv, &s, c32);
+    __syncthreads();
+    o32 += (u64)32 << log2_n;
+  }
+  for (u32 ll = log2_n; ll-- > 0;) { fr_ntt_stage(a, log2_n, ll, false, roots, t, NT); __syncthreads(); }
+  fr_ntt_store(a, N, t, NT, o32);
+}
+// The quotient rows of n blobs' cell proofs, one lane per chain (fr_exec.h fr_cell_chain): lane (blob, k, j), j fastest, so that a wavefront reads and writes consecutive
+// elements.  coef32: n x N coefficients (all-zero for a refused blob: its rows come out zero); sroots: the table of the 2 N / c roots (s_k = entry k); out_q32: n x (2 N / c)
+// rows of N scalars; row_st[row] = the status of the row's blob, for the closing kernel
+__global__ void __launch_bounds__(256) kzg_cell_rows_kernel(u32 log2_n, u32 log2_cell, u32 n, const uint8_t* __restrict__ coef32, const Fr* __restrict__ sroots,
+                                                            const int8_t* __restrict__ blob_st, uint8_t* __restrict__ out_q32, int8_t* __restrict__ row_st) {
+  const u64 gid = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+  if (gid >= ((u64)n << (log2_n + 1))) return;
+  const u32 blob = (u32)(gid >> (log2_n + 1)), within = (u32)gid & ((2u << log2_n) - 1), k = within >> log2_cell, j = within & ((1u << log2_cell) - 1);
+  const u64 row = ((u64)blob << (log2_n + 1 - log2_cell)) + k;
+  fr_cell_chain(coef32 + (((u64)blob * 32) << log2_n), log2_n, log2_cell, j, sroots[k], out_q32 + ((row * 32) << log2_n));
+  if (j == 0) row_st[row] = blob_st[blob];
+}
+
 // blobs that are only committed to (no quotient kernel reads them): status[i] = NBLS_ST_NON_CANONICAL where an element of blob i is >= r, and that blob's row is zeroed in
 // place, so that the MSM reads canonical scalars only.  One workgroup per blob
 __global__ void __launch_bounds__(256) kzg_canon_kernel(u32 log2_n, uint8_t* __restrict__ evals, int8_t* __restrict__ status) {
@@ -225,6 +297,27 @@ int nbls_kzg_quotient_launch(unsigned log2_n, unsigned n, const void* evals32, c
   static std::atomic<bool> attr_set[64];
   const int e = lds_limit((const void*)kzg_quotient_kernel, attr_set);
   return e ? e : launch_1d(kzg_quotient_kernel, (u64)n * EV, EV, lds, stream, log2_n, evals32, z32, roots, out_y32, out_q32, status);
+}
+int nbls_kzg_inv_roots_launch(unsigned log2_n, const void* roots, void* table, hipStream_t stream) {
+  return launch_1d(kzg_inv_roots_kernel, (u64)1 << log2_n, 64, 0, stream, log2_n, roots, table);
+}
+// n polynomials of 2^log2_n elements through kzg_ntt_kernel (mode: FrNttMode; the arrays as the kernel states them; shift32, coef32 and status may be NULL)
+int nbls_kzg_ntt_launch(unsigned log2_n, unsigned mode, unsigned n, const void* in32, const void* shift32, unsigned shift_stride, const void* roots, const void* iroots,
+                        void* out32, void* coef32, void* status, hipStream_t stream) {
+  if (!n) return 0;
+  if (log2_n < 1 || log2_n > 12 || mode > FR_NTT_CELLS || (mode == FR_NTT_CELLS && !shift32) || (((uintptr_t)in32 | (uintptr_t)out32 | (uintptr_t)coef32) & 15))
+    return (int)hipErrorInvalidValue;
+  static std::atomic<bool> attr_set[64];
+  const int e = lds_limit((const void*)kzg_ntt_kernel, attr_set);
+  const u64 out_stride = (u64)(mode == FR_NTT_CELLS ? 64 : 32) << log2_n;
+  return e ? e : launch_1d(kzg_ntt_kernel, (u64)n * NT, NT, 32u << log2_n, stream, log2_n, mode, in32, shift32, shift_stride, roots, iroots, out32, out_stride, coef32, status);
+}
+// the quotient rows of n blobs (n << (log2_n + 1) lanes; the table of 2^(log2_n + 1 - log2_cell) roots has at most 2^12 entries)
+int nbls_kzg_cell_rows_launch(unsigned log2_n, unsigned log2_cell, unsigned n, const void* coef32, const void* sroots, const void* blob_st, void* out_q32, void* row_st,
+                              hipStream_t stream) {
+  if (!n) return 0;
+  if (log2_n < 1 || log2_n > 12 || log2_cell > log2_n || log2_n + 1 - log2_cell > 12 || (((uintptr_t)coef32 | (uintptr_t)out_q32) & 15)) return (int)hipErrorInvalidValue;
+  return launch_1d(kzg_cell_rows_kernel, (u64)n << (log2_n + 1), 256, 0, stream, log2_n, log2_cell, n, coef32, sroots, blob_st, out_q32, row_st);
 }
 // evals32: n blobs of 2^log2_n elements, 16-byte aligned, zeroed in place where non-canonical
 int nbls_kzg_canon_launch(unsigned log2_n, unsigned n, void* evals32, void* status, hipStream_t stream) {

@@ -73,4 +73,9 @@ int nbls_kzg_quotient_launch(unsigned log2_n, unsigned n, const void* evals32, c
                              hipStream_t stream);
 int nbls_kzg_canon_launch(unsigned log2_n, unsigned n, void* evals32, void* status, hipStream_t stream);
 int nbls_kzg_prove_tail_launch(unsigned n, const void* zero, const void* st_a, const void* st_b, void* out48, void* status, hipStream_t stream);
+int nbls_kzg_inv_roots_launch(unsigned log2_n, const void* roots, void* table, hipStream_t stream);
+int nbls_kzg_ntt_launch(unsigned log2_n, unsigned mode, unsigned n, const void* in32, const void* shift32, unsigned shift_stride, const void* roots, const void* iroots,
+                        void* out32, void* coef32, void* status, hipStream_t stream);
+int nbls_kzg_cell_rows_launch(unsigned log2_n, unsigned log2_cell, unsigned n, const void* coef32, const void* sroots, const void* blob_st, void* out_q32, void* row_st,
+                              hipStream_t stream);
 }

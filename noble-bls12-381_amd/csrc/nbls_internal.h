@@ -1,5 +1,5 @@
 // nbls_internal.h -- what the translation units of the runtime share (runtime.cpp / tuning.cpp / pipelines_pairing.cpp / pipelines_codec.cpp / pipelines_verify.cpp /
-// pipelines_multi_verify.cpp / pipelines_threshold.cpp / pipelines_poly.cpp / pipelines_msm.cpp / pipelines_kzg.cpp / pipelines_kzg_prove.cpp; pool and multi-device handles: nbls_multi.cpp): the context, the map of its scratch slots (enum Slot: the one place that says which chain owns
+// pipelines_multi_verify.cpp / pipelines_threshold.cpp / pipelines_poly.cpp / pipelines_msm.cpp / pipelines_kzg.cpp / pipelines_kzg_prove.cpp / pipelines_kzg_cells.cpp; pool and multi-device handles: nbls_multi.cpp): the context, the map of its scratch slots (enum Slot: the one place that says which chain owns
 // which slot, checked at compile time), the launch helpers, the staged block of the host-buffer pipelines (staging.h, included at the end) and the device-side pipelines the
 // exported entry points are built from.  Internal functions have hidden visibility (csrc/Makefile: -fvisibility=hidden).
 #pragma once
@@ -81,9 +81,12 @@ enum Slot {
   // kzg_prove_pipeline and nbls_fr_quotient_roots (pipelines_kzg_prove.cpp): the quotient rows (the MSM's scalars), the challenges, the values y_i and the statuses of the two
   // canonical checks | the affine sums and their zero flags, then what is read back (compressed points, values, statuses)
   SB_KZGP_SCALARS = 69, SB_KZGP_OUT = 70,
+  // cells_pipeline and nbls_fr_ntt (pipelines_kzg_cells.cpp): the coefficients of every blob and the blobs' statuses | one chunk's quotient rows (the MSM's scalars) and the
+  // rows' statuses | what is read back (transformed rows or cells, compressed proofs, statuses), then one chunk's affine sums, zero flags and closing statuses
+  SB_KZGC_COEFS = 71, SB_KZGC_ROWS = 72, SB_KZGC_OUT = 73,
   NSB
 };
-static_assert(NSB == 71, "sb[] indices do not shift");
+static_assert(NSB == 74, "sb[] indices do not shift");
 constexpr SlotMask slot_bit(int i) { return (SlotMask)1 << i; }
 template <typename... S> constexpr SlotMask slots(S... s) { return (slot_bit(s) | ...); }
 // one instance of dev_decompress: three arrays of field elements and the exponentiation table
@@ -112,6 +115,7 @@ constexpr SlotMask M_THR_OWN = slots(SB_STAGED, SB_THR_SHARES, SB_THR_SCALARS, S
 constexpr SlotMask M_POLY_OWN = slots(SB_STAGED, SB_POLY_COEFS, SB_POLY_LABELS, SB_POLY_ACC, SB_POLY_STEP, SB_POLY_OUT);   // poly_pipeline: what outlives the decoder it calls
 constexpr SlotMask M_KZG_OWN = slots(SB_STAGED, SB_KZG_POINTS, SB_KZG_SCALARS, SB_KZG_PAIRS, SB_KZG_OUT, SB_KZG_ITEMS);   // kzg_pipeline: what outlives the decoder, the MSMs and the ladders it calls
 constexpr SlotMask M_KZGP_OWN = slots(SB_STAGED, SB_KZGP_SCALARS, SB_KZGP_OUT);   // kzg_prove_pipeline: what outlives the batched MSM it calls (msm_rows_dev, on M_MSMB_OWN)
+constexpr SlotMask M_KZGC_OWN = slots(SB_STAGED, SB_KZGC_COEFS, SB_KZGC_ROWS, SB_KZGC_OUT);   // cells_pipeline: what outlives the batched MSM of every chunk
 constexpr SlotMask M_MSMB_OWN = slots(SB_MSMB_CALL, SB_MSMB_SLAB);   // msm_batch_pipeline: what outlives the dev_msm calls of its big groups
 // what runs side by side
 static_assert(!(M_VB_MAIN & DEC_KEYS.mask()), "verifyBatch decodes its keys (side2, or the sub-batch's own stream) beside the hash chain");
@@ -130,6 +134,9 @@ static_assert(!((M_KZG_OWN & ~slot_bit(SB_STAGED)) & (M_MSMB_OWN | M_POLY_OWN | 
 static_assert(!(M_KZGP_OWN & (M_MSMB_OWN | DEC_MAIN.mask())), "kzg_prove_pipeline: the batched MSM sizes its two slots while the staged blobs and the quotient rows are held; nbls_kzg_setup_create decodes on the main slots");
 static_assert(!((M_KZGP_OWN & ~slot_bit(SB_STAGED)) & (M_KZG_OWN | M_POLY_OWN | M_THR_OWN | M_RLC_MAIN | M_RLC_SIDE | M_RLC_SIDE2 | M_VB_MAIN | M_LADDER | MSM_MAIN.mask() | MSM_RLC.mask())),
               "kzg_prove_pipeline keeps to slots of its own");
+static_assert(!(M_KZGC_OWN & (M_MSMB_OWN | DEC_MAIN.mask())), "cells_pipeline: the batched MSM runs chunk after chunk while the staged blobs, the coefficients and the results are held; nbls_kzg_monomial_create decodes on the main slots");
+static_assert(!((M_KZGC_OWN & ~slot_bit(SB_STAGED)) & (M_KZGP_OWN | M_KZG_OWN | M_POLY_OWN | M_THR_OWN | M_RLC_MAIN | M_RLC_SIDE | M_RLC_SIDE2 | M_VB_MAIN | M_LADDER | MSM_MAIN.mask() | MSM_RLC.mask())),
+              "cells_pipeline keeps to slots of its own");
 // ---- END scratch slots -------------------------------------------------------------------------------------------------------------------------------------
 #define EXPORT extern "C" __attribute__((visibility("default")))
 extern std::recursive_mutex g_null_mu;   // locked in place of a context's mutex when the caller passed no context (the call then fails with NBLS_EINVAL)
@@ -158,6 +165,7 @@ struct nbls_ctx {
   // nbls_set_tuning(NBLS_TUNE_MSMB_WINDOW / _BIG / _SLAB): the batched MSM's window width, the points from which a group runs through dev_msm, the entries of a slab; 0 = automatic /
   // the defaults (pipelines_msm.cpp)
   size_t msmb_window = 0, msmb_big = 0, msmb_slab = 0;
+  size_t cells_chunk = 0;       // nbls_set_tuning(NBLS_TUNE_CELLS_CHUNK): blobs per pass of nbls_kzg_compute_cells_and_proofs; 0 = as many as the batched MSM takes (pipelines_kzg_cells.cpp)
   // scratch (device)
   uint8_t *F = nullptr, *N = nullptr, *NI = nullptr, *io_g1 = nullptr, *io_g2 = nullptr, *io_f12 = nullptr, *one12 = nullptr;
   uint8_t* T[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // t1..t7 of the final exponentiation, raw Fp12
@@ -218,6 +226,7 @@ struct nbls_ctx {
   size_t chain_max = (size_t)env_long("NBLS_CHAIN_MAX", 8192);                  // nbls_set_tuning(NBLS_TUNE_CHAIN_MAX); see run_chain
   u32* qp_table = nullptr;      // multiples of p for the weak reduction (vm_exec.h weak_reduce), device copy
   uint8_t* kzg_roots[13] = {nullptr};   // kzg_kernels.hip: the 2^k roots of unity in bit-reversed order, Montgomery form (32 bytes each), built on first use of log2_n = k, freed with the context
+  uint8_t* kzg_inv_roots[13] = {nullptr};   // the same for 1 / omega: what nbls_fr_ntt's stages towards the coefficients divide by
   uint8_t* unit_lines = nullptr;   // a line table whose 68 lines are all 1 (c0 = 1, c1 = c2 = 0): the neutral partner of an odd last pair
   uint8_t* partial = nullptr;   // 576 bytes: the Fp12 partial of the *_partial entry points (multi-GPU reductions)
   uint8_t* L = nullptr; size_t cap_L = 0;   // line tables of the Miller loop (LINE_BYTES each), at most LINES_CHUNK of them
@@ -410,9 +419,16 @@ int msm_rows_dev_plan(nbls_ctx* ctx, size_t n_pts, size_t n_rows, MsmbPlan* pl);
 int msm_rows_dev(nbls_ctx* ctx, const MsmbPlan& pl, const uint8_t* conv_pts, const uint8_t* d_scalars, uint8_t* d_out96, uint8_t* d_zero, hipStream_t s);
 // pipelines_kzg.cpp: the table of roots of a context; the challenges of n blobs on host threads
 int kzg_roots(nbls_ctx* ctx, unsigned log2_n, hipStream_t s, const uint8_t** table);
+int kzg_inv_roots(nbls_ctx* ctx, unsigned log2_n, hipStream_t s, const uint8_t** table);
 void blob_challenges(unsigned log2_n, size_t n, const uint8_t* blobs, const uint8_t* c48, uint8_t* z32);
 // a trusted setup's Lagrange basis in the form the batched MSM reads (nbls_kzg_setup_create): 2^log2_n points, each with its endomorphism image, raw projective
 struct nbls_kzg_setup { int device = 0; unsigned log2_n = 0; uint8_t* pts = nullptr; };
+// the monomial basis [tau^i]G1 in the same form (nbls_kzg_monomial_create): a handle type of its own, so that neither basis is taken for the other
+struct nbls_kzg_monomial { int device = 0; unsigned log2_n = 0; uint8_t* pts = nullptr; };
+// pipelines_kzg_prove.cpp, what the two create calls share: 2^log2_n compressed points decoded, subgroup-checked and converted into a device block of the context's device
+// (*pts, the caller frees it); NBLS_EDECODE (and no block) where an entry does not decode or is the zero point; status (may be NULL) as the create calls state it
+int kzg_basis_create(nbls_ctx* ctx, unsigned log2_n, const uint8_t* points48, int8_t* status, uint8_t** pts);
+void kzg_basis_free(int device, uint8_t* pts);
 int msm_host(nbls_ctx* ctx, bool g2, size_t n, const uint8_t* pts, const uint8_t* scalars32, uint8_t* out, int8_t* status);
 int dst_on_device(nbls_ctx* ctx, const uint8_t* dst, size_t* dst_len, hipStream_t s, uint8_t** dd);
 std::vector<size_t> verify_plan(nbls_ctx* ctx, size_t n);

@@ -56,6 +56,19 @@ int kzg_roots(nbls_ctx* ctx, unsigned log2_n, hipStream_t s, const uint8_t** tab
   *table = ctx->kzg_roots[log2_n];
   return NBLS_OK;
 }
+// the inverse roots, a permutation of the table above (made behind it on the same stream)
+int kzg_inv_roots(nbls_ctx* ctx, unsigned log2_n, hipStream_t s, const uint8_t** table) {
+  if (!ctx->kzg_inv_roots[log2_n]) {
+    const uint8_t* roots; uint8_t* t = nullptr;
+    const int r = kzg_roots(ctx, log2_n, s, &roots); if (r) return r;
+    HIPCHK(hipMalloc(&t, (size_t)32 << log2_n));
+    const int e = nbls_kzg_inv_roots_launch(log2_n, roots, t, s);
+    if (e) { hipFree(t); ctx->last_hip = e; return NBLS_EHIP; }
+    ctx->kzg_inv_roots[log2_n] = t;
+  }
+  *table = ctx->kzg_inv_roots[log2_n];
+  return NBLS_OK;
+}
 
 EXPORT int nbls_fr_eval_roots(nbls_ctx* ctx, unsigned log2_n, size_t n, const uint8_t* evals32, const uint8_t* z32, uint8_t* out32, int8_t* status) {
   WHOLE_CALL(ctx);

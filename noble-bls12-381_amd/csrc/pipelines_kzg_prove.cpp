@@ -19,24 +19,17 @@ static const size_t KZGP_MAX_SCALARS = (size_t)1 << 22;   // the batched MSM's b
 
 static size_t carve(size_t* off, size_t bytes) { const size_t o = *off; *off = o + ((bytes + 63) & ~(size_t)63); return o; }
 
-EXPORT int nbls_kzg_setup_create(nbls_ctx* ctx, unsigned log2_n, const uint8_t* lagrange48, int8_t* status, nbls_kzg_setup** out) {
-  WHOLE_CALL(ctx);
-  if (out) *out = nullptr;
-  if (!ctx || log2_n < 1 || log2_n > 12 || !lagrange48 || !out) return NBLS_EINVAL;
+int kzg_basis_create(nbls_ctx* ctx, unsigned log2_n, const uint8_t* points48, int8_t* status, uint8_t** pts) {
   const size_t n = (size_t)1 << log2_n, p = 3 * RAW;
   std::vector<int8_t> st(n);
   LOCKED(ctx);
   HostIO io{ctx};
   void *d = io.alloc(n * 48), *a = io.alloc(n * 96), *dst = io.alloc(n);
   if (!d || !a || !dst) return NBLS_EHIP;
-  nbls_kzg_setup* su = new (std::nothrow) nbls_kzg_setup;
-  if (!su) return NBLS_EHIP;
-  su->device = ctx->device; su->log2_n = log2_n;
   uint8_t* mem = nullptr;
-  if (hipMalloc(&mem, n * 2 * p) != hipSuccess) { ctx->last_hip = (int)hipGetLastError(); delete su; return NBLS_EHIP; }
-  su->pts = mem;
+  if (hipMalloc(&mem, n * 2 * p) != hipSuccess) { ctx->last_hip = (int)hipGetLastError(); return NBLS_EHIP; }
   int r = NBLS_OK;
-  hipError_t e = hipMemcpyAsync(d, lagrange48, n * 48, hipMemcpyHostToDevice, s);
+  hipError_t e = hipMemcpyAsync(d, points48, n * 48, hipMemcpyHostToDevice, s);
   // (an entry that does not decode goes through the conversion as whatever bytes the decoder left: the table is then discarded)
   if (e == hipSuccess && !(r = dev_decompress(ctx, false, n, d, a, dst, s)) && !(r = run(ctx, P_G1_MSM_PREP, n, {B(0, a, 96), B(3, mem, 2 * p)}, s))) {
     e = hipMemcpyAsync(st.data(), dst, n, hipMemcpyDeviceToHost, s);
@@ -47,16 +40,31 @@ EXPORT int nbls_kzg_setup_create(nbls_ctx* ctx, unsigned log2_n, const uint8_t* 
     if (status) memcpy(status, st.data(), n);
     for (size_t j = 0; j < n; j++) if (st[j]) r = NBLS_EDECODE;   // 1: a zero point, which no real setup contains
   }
-  if (r) { (void)hipStreamSynchronize(s); hipFree(mem); delete su; return r; }
+  if (r) { (void)hipStreamSynchronize(s); hipFree(mem); return r; }
+  *pts = mem;
+  return NBLS_OK;
+}
+void kzg_basis_free(int device, uint8_t* pts) {
+  int cur = 0;
+  const bool restore = hipGetDevice(&cur) == hipSuccess;
+  if (hipSetDevice(device) == hipSuccess) (void)hipFree(pts);
+  if (restore) (void)hipSetDevice(cur);
+}
+EXPORT int nbls_kzg_setup_create(nbls_ctx* ctx, unsigned log2_n, const uint8_t* lagrange48, int8_t* status, nbls_kzg_setup** out) {
+  WHOLE_CALL(ctx);
+  if (out) *out = nullptr;
+  if (!ctx || log2_n < 1 || log2_n > 12 || !lagrange48 || !out) return NBLS_EINVAL;
+  nbls_kzg_setup* su = new (std::nothrow) nbls_kzg_setup;
+  if (!su) return NBLS_EHIP;
+  su->device = ctx->device; su->log2_n = log2_n;
+  const int r = kzg_basis_create(ctx, log2_n, lagrange48, status, &su->pts);
+  if (r) { delete su; return r; }
   *out = su;
   return NBLS_OK;
 }
 EXPORT void nbls_kzg_setup_destroy(nbls_kzg_setup* su) {
   if (!su) return;
-  int cur = 0;
-  const bool restore = hipGetDevice(&cur) == hipSuccess;
-  if (hipSetDevice(su->device) == hipSuccess) (void)hipFree(su->pts);
-  if (restore) (void)hipSetDevice(cur);
+  kzg_basis_free(su->device, su->pts);
   delete su;
 }
 EXPORT int nbls_kzg_setup_log2n(const nbls_kzg_setup* su, unsigned* log2_n) {

@@ -2,7 +2,8 @@
 // -fsanitize=address,undefined).  TEST INFRASTRUCTURE (not part of libnbls.so): compiles every step program, verifies each one statically
 // (verify_program), and runs the pairing of the two generators through the simulator -- Miller loop as one program and as LINES + ACC -- printing
 // the first coefficient of the Miller value, which tests/test_debug_build.py compares with the reference's (SURVEY 8(c) anchor).  Also the quotient walk of fr_exec.h
-// (fr_eval_lane_t<true> / fr_quot_lane: the host side of kzg_quotient_kernel) on heap blocks of exactly the call's sizes, off a root and on one.
+// (fr_eval_lane_t<true> / fr_quot_lane: the host side of kzg_quotient_kernel) on heap blocks of exactly the call's sizes, off a root and on one, and the transform, the cells
+// and the quotient rows of the cell proofs (fr_ntt_* / fr_cell_chain: the host side of kzg_ntt_kernel and kzg_cell_rows_kernel) likewise.
 #include <cstdio>
 #include <cstring>
 #include <string>
@@ -16,6 +17,9 @@ extern "C" int nbls_sim_extra_run_named(const char* name, int aot, unsigned n_it
 extern "C" void nbls_sim_set_aot(int on);
 extern "C" int nbls_sim_fr_eval_roots(unsigned log2_n, size_t n, const uint8_t* evals32, const uint8_t* z32, uint8_t* out32, int8_t* status);
 extern "C" int nbls_sim_fr_quotient_roots(unsigned log2_n, size_t n, const uint8_t* evals32, const uint8_t* z32, uint8_t* out_y32, uint8_t* out_q32, int8_t* status);
+extern "C" int nbls_sim_fr_ntt(unsigned log2_n, int dir, size_t n, const uint8_t* in32, const uint8_t* shift32, uint8_t* out32, int8_t* status);
+extern "C" int nbls_sim_kzg_cells(unsigned log2_n, size_t n, const uint8_t* blobs, uint8_t* out_cells, uint8_t* coef32, int8_t* status);
+extern "C" int nbls_sim_kzg_cell_rows(unsigned log2_n, unsigned log2_cell, size_t n, const uint8_t* coef32, uint8_t* out_q32);
 using namespace nbls;
 
 static void be48(uint8_t* o, const u32* limbs) { u32 w[12]; limbs_to_words(w, limbs); for (int i = 0; i < 12; i++) { u32 v = w[11 - i]; o[4 * i] = v >> 24; o[4 * i + 1] = v >> 16; o[4 * i + 2] = v >> 8; o[4 * i + 3] = v; } }
@@ -71,6 +75,21 @@ int main() {
     if (st[0] || st[1] || memcmp(y.data(), y2.data(), 64) || memcmp(y.data() + 32, ev.data() + N * 32, 32)) { printf("QUOTIENT: y differs from the evaluation\n"); bad++; }
   }
   printf("quotient walk ok\n");
+  for (unsigned log2_n : {1u, 5u, 10u}) {   // below one element per lane, and two: the transform there and back with a shift, the cells, the quotient rows of one-element and of whole-blob cells
+    const size_t N = (size_t)1 << log2_n;
+    std::vector<uint8_t> ev(2 * N * 32), sh(2 * 32), co(2 * N * 32), back(2 * N * 32), cells(2 * 2 * N * 32), co2(2 * N * 32); std::vector<int8_t> st(2);
+    for (size_t i = 0; i < ev.size(); i++) ev[i] = (i % 32) ? (uint8_t)(i * 29 + 5) : 0;
+    sh[31] = 3; sh[63] = 7;
+    if (nbls_sim_fr_ntt(log2_n, 0, 2, ev.data(), sh.data(), co.data(), st.data()) || nbls_sim_fr_ntt(log2_n, 1, 2, co.data(), sh.data(), back.data(), nullptr)) return 2;
+    if (st[0] || st[1] || back != ev) { printf("NTT: the round trip differs\n"); bad++; }
+    if (nbls_sim_kzg_cells(log2_n, 2, ev.data(), cells.data(), co2.data(), st.data()) || nbls_sim_fr_ntt(log2_n, 0, 2, ev.data(), nullptr, co.data(), nullptr)) return 2;
+    if (st[0] || st[1] || co2 != co || memcmp(cells.data(), ev.data(), N * 32) || memcmp(cells.data() + 2 * N * 32, ev.data() + N * 32, N * 32)) { printf("CELLS: coefficients or blob bytes differ\n"); bad++; }
+    for (unsigned log2_cell : {0u, log2_n}) {
+      std::vector<uint8_t> q((size_t)2 * ((2 * N) >> log2_cell) * N * 32);
+      if (nbls_sim_kzg_cell_rows(log2_n, log2_cell, 2, co.data(), q.data())) return 2;
+    }
+  }
+  printf("transform and cell rows ok\n");
   if (memcmp(out1, out2, 576)) { printf("MISMATCH between the fused and the split Miller loop\n"); bad++; }
   printf("miller c0.c0.c0 ");
   for (int i = 0; i < 48; i++) printf("%02x", out1[i]);

@@ -144,6 +144,7 @@ EXPORT int nbls_set_tuning(nbls_ctx* ctx, int key, long long value) {
     case NBLS_TUNE_MSMB_WINDOW: if (value != 0 && value != 4 && value != 6 && value != 8 && value != 10 && value != 12) return NBLS_EINVAL; ctx->msmb_window = (size_t)value; return NBLS_OK;
     case NBLS_TUNE_MSMB_BIG: if (value < 0) return NBLS_EINVAL; ctx->msmb_big = (size_t)value; return NBLS_OK;
     case NBLS_TUNE_MSMB_SLAB: if (value < 0) return NBLS_EINVAL; ctx->msmb_slab = (size_t)value; return NBLS_OK;
+    case NBLS_TUNE_CELLS_CHUNK: if (value < 0) return NBLS_EINVAL; ctx->cells_chunk = (size_t)value; return NBLS_OK;
     default: return NBLS_EINVAL;
   }
 }

@@ -607,6 +607,86 @@ __attribute__((visibility("default"))) int nbls_sim_fr_quotient_roots(unsigned l
     sim_quotient_poly(log2_n, evals32 + 32ull * N * p, z32 + 32ull * p, roots.data(), out_y32 + 32ull * p, out_q32 + 32ull * N * p, status ? status + p : nullptr);
   return 0;
 }
+// One polynomial as kzg_ntt_kernel runs it: FR_NTT_LANES lanes, every phase between two barriers lane after lane, the same butterflies per lane and stage.  `a` has exactly
+// the kernel's dynamic LDS; out32 / coef32 exactly the rows the workgroup writes.  mode: FrNttMode (cells: shift32 = g, out32 = the 2 N elements of the blob's cells)
+static int sim_ntt_poly(unsigned log2_n, unsigned mode, const uint8_t* f32, const uint8_t* shift32, const Fr* roots, const Fr* iroots, uint8_t* out32, uint8_t* coef32) {
+  const u32 N = 1u << log2_n, W = FR_NTT_LANES;
+  std::vector<u32> a((size_t)FR_NL * N);
+  u32 bad = 0, zero = 0;
+  Fr s = fr_one();
+  if (shift32) s = fr_ntt_shift(shift32, mode == FR_NTT_TO_COEFFS, &bad, &zero);
+  for (u32 l = 0; l < W; l++) bad |= fr_ntt_load(f32, N, l, W, a.data());
+  const int st = bad ? 21 : zero ? 5 : 0;
+  if (st) {
+    memset(out32, 0, (size_t)(mode == FR_NTT_CELLS ? 64 : 32) << log2_n);
+    if (coef32) memset(coef32, 0, (size_t)32 << log2_n);
+    return st;
+  }
+  const Fr ninv = fr_inv_pow2(log2_n);
+  if (mode == FR_NTT_TO_EVALS) {
+    if (shift32) for (u32 l = 0; l < W; l++) fr_ntt_scale(a.data(), N, l, W, FR_NTT_LOG2_LANES, nullptr, &s, nullptr);
+  } else {
+    for (u32 ll = 0; ll < log2_n; ll++) for (u32 l = 0; l < W; l++) fr_ntt_stage(a.data(), log2_n, ll, true, iroots, l, W);
+    if (mode == FR_NTT_TO_COEFFS) {
+      for (u32 l = 0; l < W; l++) { fr_ntt_scale(a.data(), N, l, W, FR_NTT_LOG2_LANES, &ninv, shift32 ? &s : nullptr, nullptr); fr_ntt_store(a.data(), N, l, W, out32); }
+      return 0;
+    }
+    memcpy(out32, f32, (size_t)32 << log2_n);
+    for (u32 l = 0; l < W; l++) fr_ntt_scale(a.data(), N, l, W, FR_NTT_LOG2_LANES, &ninv, &s, coef32);
+    out32 += (size_t)32 << log2_n;
+  }
+  for (u32 ll = log2_n; ll-- > 0;) for (u32 l = 0; l < W; l++) fr_ntt_stage(a.data(), log2_n, ll, false, roots, l, W);
+  for (u32 l = 0; l < W; l++) fr_ntt_store(a.data(), N, l, W, out32);
+  return 0;
+}
+static void sim_ntt_tables(unsigned log2_n, std::vector<Fr>& roots, std::vector<Fr>& iroots) {
+  const u32 N = 1u << log2_n;
+  roots.resize(N); iroots.resize(N);
+  const Fr omega = fr_omega(log2_n);
+  for (u32 j = 0; j < N; j++) roots[j] = fr_root_entry(omega, log2_n, j);
+  for (u32 j = 0; j < N; j++) iroots[j] = roots[fr_inv_root_index(log2_n, j)];
+}
+// nbls_fr_ntt as kzg_kernels.hip runs it.  Returns -1 (NBLS_EINVAL) under the rules of the device call that need no context
+__attribute__((visibility("default"))) int nbls_sim_fr_ntt(unsigned log2_n, int dir, size_t n, const uint8_t* in32, const uint8_t* shift32, uint8_t* out32, int8_t* status) {
+  if (log2_n < 1 || log2_n > 12 || (dir != 0 && dir != 1) || (n && (!in32 || !out32)) || (n << log2_n) > ((size_t)1 << 24)) return -1;
+  std::vector<Fr> roots, iroots;
+  sim_ntt_tables(log2_n, roots, iroots);
+  for (size_t p = 0; p < n; p++) {
+    const int st = sim_ntt_poly(log2_n, dir == 0 ? FR_NTT_TO_COEFFS : FR_NTT_TO_EVALS, in32 + ((32 * p) << log2_n), shift32 ? shift32 + 32 * p : nullptr, roots.data(), iroots.data(),
+                                out32 + ((32 * p) << log2_n), nullptr);
+    if (status) status[p] = (int8_t)st;
+  }
+  return 0;
+}
+// nbls_kzg_compute_cells as the kernel's cells mode runs it; coef32 (may be NULL): the n x N coefficients the proofs read
+__attribute__((visibility("default"))) int nbls_sim_kzg_cells(unsigned log2_n, size_t n, const uint8_t* blobs, uint8_t* out_cells, uint8_t* coef32, int8_t* status) {
+  if (log2_n < 1 || log2_n > 12 || (n && (!blobs || !out_cells)) || (n << log2_n) > ((size_t)1 << 24)) return -1;
+  std::vector<Fr> roots, iroots;
+  sim_ntt_tables(log2_n, roots, iroots);
+  uint8_t g32[32];
+  fr_to_bytes(fr_omega(log2_n + 1), g32);
+  for (size_t p = 0; p < n; p++) {
+    const int st = sim_ntt_poly(log2_n, FR_NTT_CELLS, blobs + ((32 * p) << log2_n), g32, roots.data(), iroots.data(), out_cells + ((64 * p) << log2_n),
+                                coef32 ? coef32 + ((32 * p) << log2_n) : nullptr);
+    if (status) status[p] = (int8_t)st;
+  }
+  return 0;
+}
+// the quotient rows of n blobs' cell proofs as kzg_cell_rows_kernel writes them: lane (blob, k, j) walks chain j of row k.  coef32: n x N coefficients; out_q32: n x
+// (2 N / c) rows of N scalars.  -1 where the device call refuses the sizes (the table of the 2 N / c roots has at most 2^12 entries)
+__attribute__((visibility("default"))) int nbls_sim_kzg_cell_rows(unsigned log2_n, unsigned log2_cell, size_t n, const uint8_t* coef32, uint8_t* out_q32) {
+  if (log2_n < 1 || log2_n > 12 || log2_cell > log2_n || log2_n + 1 - log2_cell > 12 || (n && (!coef32 || !out_q32))) return -1;
+  const unsigned lm = log2_n + 1 - log2_cell;
+  std::vector<Fr> sroots((size_t)1 << lm);
+  const Fr omega = fr_omega(lm);
+  for (u32 k = 0; k < (1u << lm); k++) sroots[k] = fr_root_entry(omega, lm, k);
+  for (uint64_t gid = 0; gid < ((uint64_t)n << (log2_n + 1)); gid++) {
+    const u32 blob = (u32)(gid >> (log2_n + 1)), within = (u32)gid & ((2u << log2_n) - 1), k = within >> log2_cell, j = within & ((1u << log2_cell) - 1);
+    const uint64_t row = ((uint64_t)blob << lm) + k;
+    fr_cell_chain(coef32 + (((uint64_t)blob * 32) << log2_n), log2_n, log2_cell, j, sroots[k], out_q32 + ((row * 32) << log2_n));
+  }
+  return 0;
+}
 __attribute__((visibility("default"))) int nbls_sim_program_count() { return (int)P_COUNT; }
 __attribute__((visibility("default"))) void nbls_sim_stats() { for (int i = 0; i < P_COUNT; i++) print_stats(get_program((ProgId)i)); }
 }

@@ -92,6 +92,13 @@ def load_library():
     lib.nbls_kzg_commit_blobs.argtypes = [vp, vp, sz, vp, vp, vp]
     lib.nbls_kzg_compute_proofs.argtypes = [vp, vp, sz, vp, vp, vp, vp, vp]
     lib.nbls_kzg_compute_blob_proofs.argtypes = [vp, vp, sz, vp, vp, vp, vp, vp]
+    lib.nbls_fr_ntt.argtypes = [vp, C.c_uint, C.c_int, sz, vp, vp, vp, vp]
+    lib.nbls_kzg_compute_cells.argtypes = [vp, C.c_uint, C.c_uint, sz, vp, vp, vp]
+    lib.nbls_kzg_monomial_create.argtypes = [vp, C.c_uint, vp, vp, C.POINTER(vp)]
+    lib.nbls_kzg_monomial_destroy.argtypes = [vp]
+    lib.nbls_kzg_monomial_destroy.restype = None
+    lib.nbls_kzg_monomial_log2n.argtypes = [vp, C.POINTER(C.c_uint)]
+    lib.nbls_kzg_compute_cells_and_proofs.argtypes = [vp, vp, C.c_uint, sz, vp, vp, vp, vp]
     lib.nbls_keyset_create.argtypes = [vp, sz, vp, vp, C.POINTER(vp)]
     lib.nbls_keyset_destroy.argtypes = [vp]
     lib.nbls_keyset_destroy.restype = None
@@ -202,6 +209,33 @@ class KzgSetup:
     def close(self):
         if getattr(self, 'h', None):
             self.lib.nbls_kzg_setup_destroy(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class KzgMonomialSetup:
+    """A trusted setup's monomial basis [tau^i]G1 in device memory (nbls_kzg_monomial_create; Engine.kzg_monomial_setup), decoded and split once.  Freed by close() or when the
+    object goes away."""
+
+    def __init__(self, lib, handle):
+        self.lib = lib
+        self.h = handle
+
+    @property
+    def log2_n(self):
+        k = C.c_uint(0)
+        if self.h is None or self.lib.nbls_kzg_monomial_log2n(self.h, C.byref(k)) != 0:
+            raise NblsError('KzgMonomialSetup: the setup is closed')
+        return k.value
+
+    def close(self):
+        if getattr(self, 'h', None):
+            self.lib.nbls_kzg_monomial_destroy(self.h)
         self.h = None
 
     def __del__(self):
@@ -656,6 +690,63 @@ class Engine:
         self._chk(self.lib.nbls_kzg_compute_blob_proofs(self.h, setup.h, n, raw, None if commitments48 is None else b''.join(bytes(c) for c in commitments48), cs, out, st))
         return [cs.raw[48 * i:48 * i + 48] for i in range(n)], [out.raw[48 * i:48 * i + 48] for i in range(n)], st.raw[:n]
 
+    # ---- PeerDAS (include/nbls.h: nbls_fr_ntt, nbls_kzg_compute_cells, nbls_kzg_monomial_*, nbls_kzg_compute_cells_and_proofs)
+    def fr_ntt(self, log2_n, polys, to_evals, shifts=None):
+        """the transform of n polynomials of 2^log2_n elements each (lists of ints or 32-byte values, or their concatenated bytes): to_evals False: values on the roots in
+        bit-reversed order -> coefficients in natural order; True: the way back.  shifts: None, or one shift s per polynomial (the values are then those on s * w_j)
+        -> (list of the 2^log2_n 32-byte elements per polynomial, status list: 21 = an element or the shift is >= r, 5 = the shift is 0 mod r; the row is then all-zero)"""
+        raw = bytes(polys) if isinstance(polys, (bytes, bytearray, memoryview)) else b''.join(self._fr32(v) for f in polys for v in f)
+        row = 32 << log2_n
+        if not 1 <= log2_n <= 12 or len(raw) % row or (shifts is not None and len(shifts) * row != len(raw)):
+            raise NblsError('fr_ntt: log2_n in 1 .. 12, polynomials of %d bytes each and one shift per polynomial or None' % row)
+        n = len(raw) // row
+        out = C.create_string_buffer(max(len(raw), 1)); st = C.create_string_buffer(max(n, 1))
+        self._chk(self.lib.nbls_fr_ntt(self.h, log2_n, 1 if to_evals else 0, n, raw, None if shifts is None else b''.join(map(self._fr32, shifts)), out, st))
+        o = out.raw
+        return [[o[row * i + 32 * j:row * i + 32 * j + 32] for j in range(1 << log2_n)] for i in range(n)], list(st.raw[:n])
+
+    def kzg_monomial_setup(self, log2_n, monomial48):
+        """monomial48: the 2^log2_n compressed points [tau^i]G1 of the setup in natural order (a list of 48-byte values or their concatenation) -> KzgMonomialSetup, usable
+        from every Engine on this device.  Raises KzgSetupError (with the per-entry statuses) when an entry does not decode or is the zero point"""
+        raw = bytes(monomial48) if isinstance(monomial48, (bytes, bytearray, memoryview)) else b''.join(bytes(x) for x in monomial48)
+        if not 1 <= log2_n <= 12 or len(raw) != 48 << log2_n:
+            raise NblsError('kzg_monomial_setup: log2_n in 1 .. 12 and %d bytes of points, got %d' % (48 << min(max(log2_n, 0), 12), len(raw)))
+        st = C.create_string_buffer(1 << log2_n)
+        h = C.c_void_p()
+        r = self.lib.nbls_kzg_monomial_create(self.h, log2_n, raw, st, C.byref(h))
+        if r != 0:
+            raise KzgSetupError('kzg_monomial_setup: %s (code %d)' % (self.lib.nbls_strerror(r).decode(), r), r, st.raw)
+        return KzgMonomialSetup(self.lib, h)
+
+    @staticmethod
+    def _cells_of(raw, n, log2_n, log2_cell):
+        cell, per = 32 << log2_cell, 2 << (log2_n - log2_cell)
+        return [[raw[cell * (per * i + k):cell * (per * i + k + 1)] for k in range(per)] for i in range(n)]
+
+    def kzg_compute_cells(self, log2_n, log2_cell, blobs):
+        """compute_cells for n blobs (byte strings of 32 << log2_n bytes) with 2^log2_cell elements per cell -> (per blob the list of its 2^(log2_n + 1 - log2_cell) cells, bytes
+        each; status bytes: 21 = an element >= r, the blob's cells are then all-zero)"""
+        size = 32 << log2_n if 1 <= log2_n <= 12 else -1
+        if not 0 <= log2_cell <= log2_n or any(len(b) != size for b in blobs):
+            raise NblsError('kzg_compute_cells: log2_n in 1 .. 12, log2_cell in 0 .. log2_n, every blob has %d bytes' % size)
+        n = len(blobs)
+        out = C.create_string_buffer(max(2 * size * n, 1)); st = C.create_string_buffer(max(n, 1))
+        self._chk(self.lib.nbls_kzg_compute_cells(self.h, log2_n, log2_cell, n, b''.join(bytes(b) for b in blobs), out, st))
+        return self._cells_of(out.raw, n, log2_n, log2_cell), st.raw[:n]
+
+    def kzg_compute_cells_and_proofs(self, setup, log2_cell, blobs):
+        """compute_cells_and_kzg_proofs for n blobs against a KzgMonomialSetup -> (cells as kzg_compute_cells, per blob the list of its cells' 48-byte proofs, status bytes:
+        21 = an element >= r, the blob's cells are then all-zero and its proofs 48 zero bytes each)"""
+        n, raw = self._kzg_blobs('kzg_compute_cells_and_proofs', setup, blobs)
+        log2_n = setup.log2_n
+        if not 0 <= log2_cell <= log2_n:
+            raise NblsError('kzg_compute_cells_and_proofs: log2_cell in 0 .. %d' % log2_n)
+        per = 2 << (log2_n - log2_cell)
+        out = C.create_string_buffer(2 * len(raw)); pf = C.create_string_buffer(48 * per * n); st = C.create_string_buffer(n)
+        self._chk(self.lib.nbls_kzg_compute_cells_and_proofs(self.h, setup.h, log2_cell, n, raw, out, pf, st))
+        p = pf.raw
+        return self._cells_of(out.raw, n, log2_n, log2_cell), [[p[48 * (per * i + k):48 * (per * i + k + 1)] for k in range(per)] for i in range(n)], st.raw[:n]
+
     def get_public_keys(self, keys):
         """getPublicKey for a batch of private keys -> list of 48-byte compressed keys; raises like the reference on a zero key"""
         aff, st = self.point_mul_batch(keys)
@@ -894,6 +985,10 @@ class Engine:
         for key, v in ((16, window), (17, big), (18, slab)):
             if v is not None:
                 self._chk(self.lib.nbls_set_tuning(self.h, key, int(v)))
+
+    def set_cells_chunk(self, blobs):
+        """blobs that kzg_compute_cells_and_proofs hands to the batched MSM in one pass (NBLS_TUNE_CELLS_CHUNK = 20; 0: as many as its bounds take)"""
+        self._chk(self.lib.nbls_set_tuning(self.h, 20, int(blobs)))
 
     def set_verify_pipeline(self, chunks=None, last_pct=None, pipe_min=None):
         """verifyBatch as a software pipeline (NBLS_TUNE_VERIFY_CHUNKS / _LAST_PCT / _PIPE_MIN): number of chunks (0 / 1: one), size of the last chunk in

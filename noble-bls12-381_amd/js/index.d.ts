@@ -96,6 +96,15 @@ export declare class PointG1 {
   /** commitments given: only hashed into the challenge, not decoded; omitted: computed first and returned */
   static computeBlobKzgProofs(setup: KzgSetup, blobs: Hex[], commitments?: (PointG1 | Hex)[]): KzgBlobProofs;
   static computeBlobKzgProofsAsync(setup: KzgSetup, blobs: Hex[], commitments?: (PointG1 | Hex)[]): Promise<KzgBlobProofs>;
+  /** PeerDAS (EIP-7594).  frNtt: n polynomials of 2^log2n elements; toEvals false: values on the roots (bit-reversed order) -> coefficients (natural order), true: the way back;
+   *  shifts: one per polynomial (the values are those on shift * root), or omitted.  computeCells: 2^log2cell elements per cell (mainnet: log2n 12, log2cell 6) */
+  static readonly KzgMonomialSetup: typeof KzgMonomialSetup;
+  static frNtt(log2n: number, rows: Hex[], toEvals: boolean, shifts?: ShareId[]): FrNttRows;
+  static frNttAsync(log2n: number, rows: Hex[], toEvals: boolean, shifts?: ShareId[]): Promise<FrNttRows>;
+  static computeCells(log2n: number, log2cell: number, blobs: Hex[]): KzgCells;
+  static computeCellsAsync(log2n: number, log2cell: number, blobs: Hex[]): Promise<KzgCells>;
+  static computeCellsAndKzgProofs(setup: KzgMonomialSetup, log2cell: number, blobs: Hex[]): KzgCellsAndProofs;
+  static computeCellsAndKzgProofsAsync(setup: KzgMonomialSetup, log2cell: number, blobs: Hex[]): Promise<KzgCellsAndProofs>;
   isZero(): boolean; equals(rhs: PointG1): boolean; negate(): PointG1; add(rhs: PointG1): PointG1; subtract(rhs: PointG1): PointG1; double(): PointG1;
   multiply(scalar: bigint | number): PointG1; multiplyUnsafe(scalar: bigint | number): PointG1; multiplyPrecomputed(scalar: bigint | number): PointG1;
   assertValidity(): this; toAffine(): [Fp, Fp]; toRawBytes(isCompressed?: boolean): Uint8Array; toHex(isCompressed?: boolean): string;
@@ -151,6 +160,17 @@ declare class KzgSetup {
   readonly log2n: number;
   close(): void;
 }
+/** A trusted setup's g1_monomial (2^k points [tau^i]G1 in natural order, 1 <= k <= 12) decoded once into device memory; close() frees it.  Reached as PointG1.KzgMonomialSetup */
+declare class KzgMonomialSetup {
+  constructor(points: (PointG1 | Hex)[]);
+  readonly log2n: number;
+  close(): void;
+}
+/** status: one byte per polynomial (0; 21 an element or the shift is >= CURVE.r; 5 the shift is 0: the row is then all-zero) */
+export interface FrNttRows { rows: Uint8Array[]; status: Uint8Array }
+/** cells[blob][k]: the 32 << log2cell bytes of cell k; proofs[blob][k]: its 48-byte proof; status: one byte per blob (21: an element >= CURVE.r, cells all-zero, proofs 48 zero bytes) */
+export interface KzgCells { cells: Uint8Array[][]; status: Uint8Array }
+export interface KzgCellsAndProofs { cells: Uint8Array[][]; proofs: Uint8Array[][]; status: Uint8Array }
 export interface KzgCommitments { commitments: Uint8Array[]; status: Uint8Array }
 export interface KzgProofs { proofs: Uint8Array[]; ys: Uint8Array[]; status: Uint8Array }
 export interface KzgBlobProofs { commitments: Uint8Array[]; proofs: Uint8Array[]; status: Uint8Array }

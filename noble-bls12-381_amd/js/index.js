@@ -255,6 +255,71 @@ async function computeKzgProofsAsync(setup, blobs, zs) { const a = kzgProveArgs(
 function computeBlobKzgProofs(setup, blobs, commitments) { const a = kzgProveArgs(setup, blobs, commitments || null, 48, 'commitment', kzgG1); return kzgBlobProofResult(native.kzgProve(2, a[0], a[1], a[2]), blobs.length); }
 async function computeBlobKzgProofsAsync(setup, blobs, commitments) { const a = kzgProveArgs(setup, blobs, commitments || null, 48, 'commitment', kzgG1); return kzgBlobProofResult(await native.kzgProveAsync(2, a[0], a[1], a[2]), blobs.length); }
 
+// ---- PeerDAS (nbls_fr_ntt, nbls_kzg_compute_cells, nbls_kzg_monomial_*, nbls_kzg_compute_cells_and_proofs; EIP-7594): the transform between the coefficients of a polynomial
+// and its values on the roots of unity, compute_cells and compute_cells_and_kzg_proofs for many blobs.  Statics of PointG1 like the prover's calls.  new PointG1.KzgMonomialSetup(points):
+// the setup's g1_monomial in natural order (2^k points, 1 <= k <= 12), decoded once; close() frees it.  Rows and blobs: bytes or hex of 32 * 2^k.  Results are arrays of Uint8Array
+// and status = one byte per polynomial or blob (0; 21: an element or the shift is >= CURVE.r; 5: the shift is 0 -- the outputs of that item are then all-zero bytes)
+class KzgMonomialSetup {
+  constructor(points) {
+    const log2n = Math.round(Math.log2(points.length));
+    if (log2n < 1 || log2n > 12 || points.length !== 1 << log2n) throw new Error('Invalid setup: expected 2^k points, 1 <= k <= 12');
+    ensureInit();
+    this.log2n = log2n;
+    try { this.handle = native.kzgMonomialCreate(log2n, kzgPack(points, 48, 'setup point', kzgG1)); } catch (e) {
+      if (e && e.nblsCode === -5) { const err = new Error('Invalid setup: a point does not decode, is outside the subgroup or is the zero point'); err.status = e.status; throw err; }
+      throw e;
+    }
+  }
+  close() { if (this.handle) native.kzgMonomialDestroy(this.handle); this.handle = null; }
+}
+function frNttArgs(log2n, rows, toEvals, shifts) {
+  if (!Number.isInteger(log2n) || log2n < 1 || log2n > 12) throw new Error('Expected log2n in 1 .. 12');
+  if (!rows.length) throw new Error('Expected non-empty array');
+  if (shifts && shifts.length !== rows.length) throw new Error('Expected as many shifts as polynomials');
+  ensureInit();
+  return [log2n, toEvals ? 1 : 0, kzgPack(rows, 32 << log2n, 'polynomial', ensureBytes), shifts ? kzgPack(shifts, 32, 'field element', shareIdBytes) : null];
+}
+const frNttResult = (res, n, log2n) => ({ rows: kzgSplit(res, n, [32 << log2n])[0], status: res.status });
+function frNtt(log2n, rows, toEvals, shifts) { const a = frNttArgs(log2n, rows, toEvals, shifts); return frNttResult(native.frNtt(a[0], a[1], a[2], a[3]), rows.length, log2n); }
+async function frNttAsync(log2n, rows, toEvals, shifts) { const a = frNttArgs(log2n, rows, toEvals, shifts); return frNttResult(await native.frNttAsync(a[0], a[1], a[2], a[3]), rows.length, log2n); }
+function kzgCellArgs(log2n, log2cell, blobs) {
+  if (!Number.isInteger(log2cell) || log2cell < 0 || log2cell > log2n) throw new Error('Expected log2cell in 0 .. log2n');
+  if (!blobs.length) throw new Error('Expected non-empty array');
+  return kzgPack(blobs, 32 << log2n, 'blob', ensureBytes);
+}
+// res.out = per blob its 2 N elements in cell order (, then the proofs) -> cells[blob][k], proofs[blob][k]
+function kzgCellsResult(res, n, log2n, log2cell, withProofs) {
+  const per = 2 << (log2n - log2cell), cell = 32 << log2cell, cells = [], proofs = [], at = n * per * cell;
+  for (let i = 0; i < n; i++) {
+    const cs = [], ps = [];
+    for (let k = 0; k < per; k++) {
+      cs.push(res.out.slice((i * per + k) * cell, (i * per + k + 1) * cell));
+      if (withProofs) ps.push(res.out.slice(at + (i * per + k) * 48, at + (i * per + k + 1) * 48));
+    }
+    cells.push(cs); proofs.push(ps);
+  }
+  return withProofs ? { cells, proofs, status: res.status } : { cells, status: res.status };
+}
+function computeCells(log2n, log2cell, blobs) {
+  if (!Number.isInteger(log2n) || log2n < 1 || log2n > 12) throw new Error('Expected log2n in 1 .. 12');
+  const b = kzgCellArgs(log2n, log2cell, blobs); ensureInit();
+  return kzgCellsResult(native.kzgComputeCells(log2n, log2cell, b), blobs.length, log2n, log2cell, false);
+}
+async function computeCellsAsync(log2n, log2cell, blobs) {
+  if (!Number.isInteger(log2n) || log2n < 1 || log2n > 12) throw new Error('Expected log2n in 1 .. 12');
+  const b = kzgCellArgs(log2n, log2cell, blobs); ensureInit();
+  return kzgCellsResult(await native.kzgComputeCellsAsync(log2n, log2cell, b), blobs.length, log2n, log2cell, false);
+}
+function kzgMonomialOpen(setup) { if (!(setup instanceof KzgMonomialSetup) || !setup.handle) throw new Error('Expected an open KzgMonomialSetup'); }
+function computeCellsAndKzgProofs(setup, log2cell, blobs) {
+  kzgMonomialOpen(setup); const b = kzgCellArgs(setup.log2n, log2cell, blobs);
+  return kzgCellsResult(native.kzgCellsAndProofs(setup.handle, log2cell, b), blobs.length, setup.log2n, log2cell, true);
+}
+async function computeCellsAndKzgProofsAsync(setup, log2cell, blobs) {
+  kzgMonomialOpen(setup); const b = kzgCellArgs(setup.log2n, log2cell, blobs);
+  return kzgCellsResult(await native.kzgCellsAndProofsAsync(setup.handle, log2cell, b), blobs.length, setup.log2n, log2cell, true);
+}
+
 // Points are held as affine wire bytes (what the engine consumes) or as the zero point.  The reference's constructor form
 // new PointG1(x: Fp, y: Fp, z?: Fp) (index.ts:291) is accepted too: the projective triple is made affine on the host.
 class PointG1 {
@@ -385,6 +450,14 @@ class PointG1 {
   static computeKzgProofsAsync(setup, blobs, zs) { return computeKzgProofsAsync(setup, blobs, zs); }
   static computeBlobKzgProofs(setup, blobs, commitments) { return computeBlobKzgProofs(setup, blobs, commitments); }
   static computeBlobKzgProofsAsync(setup, blobs, commitments) { return computeBlobKzgProofsAsync(setup, blobs, commitments); }
+  // PeerDAS (above): the transform over Fr, the cells of blobs, and cells with their proofs against a KzgMonomialSetup
+  static get KzgMonomialSetup() { return KzgMonomialSetup; }
+  static frNtt(log2n, rows, toEvals, shifts) { return frNtt(log2n, rows, toEvals, shifts); }
+  static frNttAsync(log2n, rows, toEvals, shifts) { return frNttAsync(log2n, rows, toEvals, shifts); }
+  static computeCells(log2n, log2cell, blobs) { return computeCells(log2n, log2cell, blobs); }
+  static computeCellsAsync(log2n, log2cell, blobs) { return computeCellsAsync(log2n, log2cell, blobs); }
+  static computeCellsAndKzgProofs(setup, log2cell, blobs) { return computeCellsAndKzgProofs(setup, log2cell, blobs); }
+  static computeCellsAndKzgProofsAsync(setup, log2cell, blobs) { return computeCellsAndKzgProofsAsync(setup, log2cell, blobs); }
   equals(rhs) { return this.zero === rhs.zero && (this.zero || bytesToHex(this.aff) === bytesToHex(rhs.aff)); }
   // reference index.ts:359-381
   toHex(isCompressed = false) {

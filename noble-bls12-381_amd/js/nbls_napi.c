@@ -2,7 +2,7 @@
  * nbls_napi.c -- thin N-API addon: exposes the C ABI of libnbls.so (include/nbls.h) to Node.  No arithmetic here.
  * libnbls.so is loaded with dlopen at module init so the addon builds with plain gcc (no HIP needed):
  *     gcc -shared -fPIC -I/usr/include/node -I../../include nbls_napi.c -o nbls_napi.node -ldl
- * Calls are synchronous (they block for the duration of the GPU work) except verifyBatchAsync (and signBatchAsync, verifyMultipleAsync, verifyAggregatesAsync, verifyMultipleSharedAsync, verifyAggregatesSharedAsync, frOpAsync, lagrangeAtZeroAsync, combineSharesAsync, polyEvalAsync, kzgVerifyProofsAsync, kzgVerifyBlobsAsync, kzgProveAsync), which runs on a libuv worker thread
+ * Calls are synchronous (they block for the duration of the GPU work) except verifyBatchAsync (and signBatchAsync, verifyMultipleAsync, verifyAggregatesAsync, verifyMultipleSharedAsync, verifyAggregatesSharedAsync, frOpAsync, lagrangeAtZeroAsync, combineSharesAsync, polyEvalAsync, kzgVerifyProofsAsync, kzgVerifyBlobsAsync, kzgProveAsync, frNttAsync, kzgComputeCellsAsync, kzgCellsAndProofsAsync), which runs on a libuv worker thread
  * (napi_create_async_work) and resolves a Promise: the facade's verifyBatch uses it for wire-format inputs (the calls that can take tens of milliseconds).  Typed arrays are passed by reference (napi_get_typedarray_info), no copies.
  */
 #include <node_api.h>
@@ -24,6 +24,7 @@ SYM(nbls_g1_from_hex_batch) SYM(nbls_g2_from_hex_batch) SYM(nbls_g2_from_signatu
 SYM(nbls_fr_op_batch) SYM(nbls_lagrange_at_zero) SYM(nbls_g2_combine_shares) SYM(nbls_g1_combine_shares) SYM(nbls_g1_poly_eval) SYM(nbls_g2_poly_eval)
 SYM(nbls_kzg_verify_proofs) SYM(nbls_kzg_verify_blobs)
 SYM(nbls_kzg_setup_create) SYM(nbls_kzg_setup_destroy) SYM(nbls_kzg_setup_log2n) SYM(nbls_kzg_commit_blobs) SYM(nbls_kzg_compute_proofs) SYM(nbls_kzg_compute_blob_proofs)
+SYM(nbls_fr_ntt) SYM(nbls_kzg_compute_cells) SYM(nbls_kzg_monomial_create) SYM(nbls_kzg_monomial_destroy) SYM(nbls_kzg_monomial_log2n) SYM(nbls_kzg_compute_cells_and_proofs)
 static nbls_ctx* ctx;
 static nbls_multi* multi;   /* several GPUs behind one handle (initMulti): ctx is then its first context; the batch calls shard over all of them */
 #define MULTI() (multi && p_nbls_multi_device_count(multi) > 1)
@@ -432,10 +433,11 @@ static napi_value SignBatchAsync(napi_env env, napi_callback_info info) {
  * The offsets must name identifiers and shares that are in the arrays (checked here); the library checks the rest. */
 typedef struct {
   napi_async_work work; napi_deferred deferred; napi_ref refs[9]; int nrefs;
-  int kind /* 0 frOp, 1 lagrangeAtZero, 2 combineShares, 3 polyEval, 4 kzgVerifyProofs, 5 kzgVerifyBlobs, 6 .. 8 kzgProve */, op, g2; const uint8_t *a, *b, *shares; const uint32_t *offs, *coffs; size_t n;
+  int kind /* 0 frOp, 1 lagrangeAtZero, 2 combineShares, 3 polyEval, 4 kzgVerifyProofs, 5 kzgVerifyBlobs, 6 .. 8 kzgProve, 9 frNtt, 10 kzgComputeCells, 11 kzgCellsAndProofs */, op, g2; const uint8_t *a, *b, *shares; const uint32_t *offs, *coffs; size_t n;
   uint8_t* out; int8_t* st;
   const uint8_t *proofs, *tau, *seed; int per_item;   /* KZG: a = commitments, b = z (proofs) or the blobs, shares = y, op = log2_n; out = the verdict as one int */
   const nbls_kzg_setup* su;   /* kzgProve: b = the blobs, a = the points z (7) or the given commitments (8; may be NULL), out = two arrays of n entries one behind the other */
+  const nbls_kzg_monomial* mo; size_t proofs_at;   /* PeerDAS: op = log2_n, g2 = the direction (9) or log2_cell (10, 11), b = the rows or the blobs, a = the shifts (9; may be NULL); 11: out = the cells, then at proofs_at the proofs */
   nbls_ctx* c; int rc;
 } thr_job;
 static void thr_execute(napi_env env, void* data) { thr_job* j = (thr_job*)data; (void)env;
@@ -446,6 +448,9 @@ static void thr_execute(napi_env env, void* data) { thr_job* j = (thr_job*)data;
         : j->kind == 6 ? p_nbls_kzg_commit_blobs(j->c, j->su, j->n, j->b, j->out, j->st)
         : j->kind == 7 ? p_nbls_kzg_compute_proofs(j->c, j->su, j->n, j->b, j->a, j->out, j->out + 48 * j->n, j->st)
         : j->kind == 8 ? p_nbls_kzg_compute_blob_proofs(j->c, j->su, j->n, j->b, j->a, j->out, j->out + 48 * j->n, j->st)
+        : j->kind == 9 ? p_nbls_fr_ntt(j->c, (unsigned)j->op, j->g2, j->n, j->b, j->a, j->out, j->st)
+        : j->kind == 10 ? p_nbls_kzg_compute_cells(j->c, (unsigned)j->op, (unsigned)j->g2, j->n, j->b, j->out, j->st)
+        : j->kind == 11 ? p_nbls_kzg_compute_cells_and_proofs(j->c, j->mo, (unsigned)j->g2, j->n, j->b, j->out, j->out + j->proofs_at, j->st)
         : j->kind == 3 ? (j->g2 ? p_nbls_g2_poly_eval : p_nbls_g1_poly_eval)(j->c, j->n, j->coffs, j->shares, j->offs, j->a, j->out, j->st)
         : (j->g2 ? p_nbls_g2_combine_shares : p_nbls_g1_combine_shares)(j->c, j->n, j->offs, j->a, j->shares, j->out, j->st); }
 /* the Error of a failed call of this family: the message of throw_code, and the library's return code as the number `nblsCode` (what the facade reads: never the text) */
@@ -628,6 +633,81 @@ static napi_value kzg_prove_call(napi_env env, napi_callback_info info, int asyn
 static napi_value KzgProve(napi_env env, napi_callback_info info) { return kzg_prove_call(env, info, 0); }
 static napi_value KzgProveAsync(napi_env env, napi_callback_info info) { return kzg_prove_call(env, info, 1); }
 
+/* PeerDAS (nbls_fr_ntt, nbls_kzg_compute_cells, nbls_kzg_monomial_*, nbls_kzg_compute_cells_and_proofs), synchronous and *Async -> {out, status}:
+ *   frNtt(log2n, dir, rows, shifts32 | null)          dir 0: values -> coefficients, 1: the way back; out = the transformed rows, status per polynomial
+ *   kzgComputeCells(log2n, log2cell, blobs)            out = per blob its 2 N elements in cell order, status per blob
+ *   kzgMonomialCreate(log2n, monomial48) -> a handle   (the setup's monomial basis on the device; kzgMonomialDestroy(handle) or the handle's end frees it); a refused basis
+ *                                                      throws with the per-entry decoder statuses as the Error's `status`
+ *   kzgCellsAndProofs(handle, log2cell, blobs)         out = the cells of every blob, then n * (2 N / c) proofs of 48 bytes; status per blob */
+static napi_value fr_ntt_call(napi_env env, napi_callback_info info, int async) {
+  ARGS(4); NEED_CTX(); BYTES(2, rows, lr);
+  int32_t log2n, dir;
+  if (napi_get_value_int32(env, argv[0], &log2n) != napi_ok || napi_get_value_int32(env, argv[1], &dir) != napi_ok) { napi_throw_type_error(env, NULL, "expected numbers for log2n and the direction"); return NULL; }
+  uint8_t* sh = NULL; size_t ls = 0;
+  napi_valuetype t; napi_typeof(env, argv[3], &t);
+  if (t != napi_null && t != napi_undefined && !get_bytes(env, argv[3], &sh, &ls)) { napi_throw_type_error(env, NULL, "expected Uint8Array or null"); return NULL; }
+  if (log2n < 1 || log2n > 12 || (dir != 0 && dir != 1) || lr % ((size_t)32 << log2n) || (sh && ls != (lr >> log2n))) {
+    napi_throw_range_error(env, NULL, "log2n in 1 .. 12, direction 0 or 1, rows of 32 << log2n bytes, one shift of 32 bytes per row or null"); return NULL; }
+  thr_job job; memset(&job, 0, sizeof job);
+  job.kind = 9; job.op = log2n; job.g2 = dir; job.b = rows; job.a = sh; job.n = lr >> (5 + log2n);
+  napi_value vo = new_u8(env, lr ? lr : 1, &job.out), vs = new_u8(env, job.n ? job.n : 1, (uint8_t**)&job.st); ALLOCATED(vo); ALLOCATED(vs);
+  memset(job.st, 0, job.n ? job.n : 1);
+  return thr_run(env, &job, async, argv + 2, sh ? 2 : 1, vo, vs);
+}
+static napi_value FrNtt(napi_env env, napi_callback_info info) { return fr_ntt_call(env, info, 0); }
+static napi_value FrNttAsync(napi_env env, napi_callback_info info) { return fr_ntt_call(env, info, 1); }
+static napi_value kzg_cells_call(napi_env env, napi_callback_info info, int async) {
+  ARGS(3); NEED_CTX(); BYTES(2, blobs, lb);
+  int32_t log2n, log2c;
+  if (napi_get_value_int32(env, argv[0], &log2n) != napi_ok || napi_get_value_int32(env, argv[1], &log2c) != napi_ok) { napi_throw_type_error(env, NULL, "expected numbers for log2n and log2cell"); return NULL; }
+  if (log2n < 1 || log2n > 12 || log2c < 0 || log2c > log2n || !lb || lb % ((size_t)32 << log2n)) { napi_throw_range_error(env, NULL, "log2n in 1 .. 12, log2cell in 0 .. log2n, blobs of 32 << log2n bytes"); return NULL; }
+  thr_job job; memset(&job, 0, sizeof job);
+  job.kind = 10; job.op = log2n; job.g2 = log2c; job.b = blobs; job.n = lb >> (5 + log2n);
+  napi_value vo = new_u8(env, 2 * lb, &job.out), vs = new_u8(env, job.n, (uint8_t**)&job.st); ALLOCATED(vo); ALLOCATED(vs);
+  memset(job.st, 0, job.n);
+  return thr_run(env, &job, async, argv + 2, 1, vo, vs);
+}
+static napi_value KzgComputeCells(napi_env env, napi_callback_info info) { return kzg_cells_call(env, info, 0); }
+static napi_value KzgComputeCellsAsync(napi_env env, napi_callback_info info) { return kzg_cells_call(env, info, 1); }
+typedef struct { nbls_kzg_monomial* m; } monomial_box;
+static void monomial_finalize(napi_env env, void* data, void* hint) { (void)env; (void)hint; monomial_box* b = (monomial_box*)data; if (b->m && p_nbls_kzg_monomial_destroy) p_nbls_kzg_monomial_destroy(b->m); free(b); }
+static napi_value KzgMonomialCreate(napi_env env, napi_callback_info info) {
+  ARGS(2); NEED_CTX(); BYTES(1, pts, lp);
+  int32_t log2n; if (napi_get_value_int32(env, argv[0], &log2n) != napi_ok) { napi_throw_type_error(env, NULL, "expected a number for log2n"); return NULL; }
+  if (log2n < 1 || log2n > 12 || lp != (size_t)48 << log2n) { napi_throw_range_error(env, NULL, "log2n in 1 .. 12 and 48 << log2n bytes of compressed points"); return NULL; }
+  uint8_t* st; napi_value vs = new_u8(env, (size_t)1 << log2n, &st); ALLOCATED(vs);
+  monomial_box* box = (monomial_box*)calloc(1, sizeof *box); if (!box) { napi_throw_error(env, NULL, "out of memory"); return NULL; }
+  const int rc = p_nbls_kzg_monomial_create(ctx, (unsigned)log2n, pts, (int8_t*)st, &box->m);
+  if (rc) { free(box); napi_value err = thr_error(env, rc); napi_set_named_property(env, err, "status", vs); napi_throw(env, err); return NULL; }
+  napi_value h;
+  if (napi_create_external(env, box, monomial_finalize, NULL, &h) != napi_ok) { p_nbls_kzg_monomial_destroy(box->m); free(box); napi_throw_error(env, NULL, "napi_create_external failed"); return NULL; }
+  return h;
+}
+static napi_value KzgMonomialDestroy(napi_env env, napi_callback_info info) {
+  ARGS(1);
+  monomial_box* box = NULL;
+  if (napi_get_value_external(env, argv[0], (void**)&box) != napi_ok || !box) { napi_throw_type_error(env, NULL, "expected a monomial setup handle"); return NULL; }
+  if (box->m) { p_nbls_kzg_monomial_destroy(box->m); box->m = NULL; }
+  return NULL;
+}
+static napi_value kzg_cells_proofs_call(napi_env env, napi_callback_info info, int async) {
+  ARGS(3); NEED_CTX(); BYTES(2, blobs, lb);
+  monomial_box* box = NULL;
+  if (napi_get_value_external(env, argv[0], (void**)&box) != napi_ok || !box || !box->m) { napi_throw_type_error(env, NULL, "expected a live monomial setup handle"); return NULL; }
+  unsigned log2n = 0; p_nbls_kzg_monomial_log2n(box->m, &log2n);
+  int32_t log2c; if (napi_get_value_int32(env, argv[1], &log2c) != napi_ok) { napi_throw_type_error(env, NULL, "expected a number for log2cell"); return NULL; }
+  const size_t n = lb >> (5 + log2n);
+  if (log2c < 0 || (unsigned)log2c > log2n || !n || lb != (n * 32) << log2n) { napi_throw_range_error(env, NULL, "log2cell in 0 .. log2n and n blobs of 32 << log2n bytes"); return NULL; }
+  thr_job job; memset(&job, 0, sizeof job);
+  job.kind = 11; job.mo = box->m; job.g2 = log2c; job.b = blobs; job.n = n; job.proofs_at = 2 * lb;
+  const size_t lo = 2 * lb + n * ((size_t)2 << (log2n - log2c)) * 48;
+  napi_value vo = new_u8(env, lo, &job.out), vs = new_u8(env, n, (uint8_t**)&job.st); ALLOCATED(vo); ALLOCATED(vs);
+  memset(job.out, 0, lo); memset(job.st, 0, n);
+  return thr_run(env, &job, async, argv, 3, vo, vs);   /* the handle stays referenced while the call runs */
+}
+static napi_value KzgCellsAndProofs(napi_env env, napi_callback_info info) { return kzg_cells_proofs_call(env, info, 0); }
+static napi_value KzgCellsAndProofsAsync(napi_env env, napi_callback_info info) { return kzg_cells_proofs_call(env, info, 1); }
+
 static napi_value ModuleInit(napi_env env, napi_value exports) {
   const char* path = getenv("NBLS_LIB");
   char buf[4096];
@@ -642,6 +722,7 @@ static napi_value ModuleInit(napi_env env, napi_value exports) {
   LOAD(nbls_g1_from_hex_batch) LOAD(nbls_g2_from_hex_batch) LOAD(nbls_g2_from_signature_batch) LOAD(nbls_g1_clear_cofactor_batch) LOAD(nbls_g2_clear_cofactor_batch)
   LOAD(nbls_fr_op_batch) LOAD(nbls_lagrange_at_zero) LOAD(nbls_g2_combine_shares) LOAD(nbls_g1_combine_shares) LOAD(nbls_g1_poly_eval) LOAD(nbls_g2_poly_eval) LOAD(nbls_kzg_verify_proofs) LOAD(nbls_kzg_verify_blobs)
   LOAD(nbls_kzg_setup_create) LOAD(nbls_kzg_setup_destroy) LOAD(nbls_kzg_setup_log2n) LOAD(nbls_kzg_commit_blobs) LOAD(nbls_kzg_compute_proofs) LOAD(nbls_kzg_compute_blob_proofs)
+  LOAD(nbls_fr_ntt) LOAD(nbls_kzg_compute_cells) LOAD(nbls_kzg_monomial_create) LOAD(nbls_kzg_monomial_destroy) LOAD(nbls_kzg_monomial_log2n) LOAD(nbls_kzg_compute_cells_and_proofs)
   {   /* the ABI the addon was written against (include/nbls.h NBLS_ABI_VERSION): an older or newer library is refused at load instead of misread at run time */
     int (*abi)(void) = (int (*)(void))dlsym(lib, "nbls_abi_version");
     if (!abi || abi() != NBLS_ABI_VERSION) { napi_throw_error(env, NULL, "libnbls.so: ABI version differs from the one this addon was built for (include/nbls.h NBLS_ABI_VERSION)"); return exports; }
@@ -662,7 +743,11 @@ static napi_value ModuleInit(napi_env env, napi_value exports) {
     {"polyEvalAsync", 0, PolyEvalAsync, 0, 0, 0, napi_enumerable, 0}, {"kzgVerifyProofs", 0, KzgVerifyProofs, 0, 0, 0, napi_enumerable, 0},
     {"kzgVerifyProofsAsync", 0, KzgVerifyProofsAsync, 0, 0, 0, napi_enumerable, 0}, {"kzgVerifyBlobs", 0, KzgVerifyBlobs, 0, 0, 0, napi_enumerable, 0},
     {"kzgVerifyBlobsAsync", 0, KzgVerifyBlobsAsync, 0, 0, 0, napi_enumerable, 0}, {"kzgSetupCreate", 0, KzgSetupCreate, 0, 0, 0, napi_enumerable, 0},
-    {"kzgSetupDestroy", 0, KzgSetupDestroy, 0, 0, 0, napi_enumerable, 0}, {"kzgProve", 0, KzgProve, 0, 0, 0, napi_enumerable, 0}, {"kzgProveAsync", 0, KzgProveAsync, 0, 0, 0, napi_enumerable, 0}};
+    {"kzgSetupDestroy", 0, KzgSetupDestroy, 0, 0, 0, napi_enumerable, 0}, {"kzgProve", 0, KzgProve, 0, 0, 0, napi_enumerable, 0}, {"kzgProveAsync", 0, KzgProveAsync, 0, 0, 0, napi_enumerable, 0},
+    {"frNtt", 0, FrNtt, 0, 0, 0, napi_enumerable, 0}, {"frNttAsync", 0, FrNttAsync, 0, 0, 0, napi_enumerable, 0}, {"kzgComputeCells", 0, KzgComputeCells, 0, 0, 0, napi_enumerable, 0},
+    {"kzgComputeCellsAsync", 0, KzgComputeCellsAsync, 0, 0, 0, napi_enumerable, 0}, {"kzgMonomialCreate", 0, KzgMonomialCreate, 0, 0, 0, napi_enumerable, 0},
+    {"kzgMonomialDestroy", 0, KzgMonomialDestroy, 0, 0, 0, napi_enumerable, 0}, {"kzgCellsAndProofs", 0, KzgCellsAndProofs, 0, 0, 0, napi_enumerable, 0},
+    {"kzgCellsAndProofsAsync", 0, KzgCellsAndProofsAsync, 0, 0, 0, napi_enumerable, 0}};
   napi_define_properties(env, exports, sizeof d / sizeof d[0], d);
   return exports;
 }
