@@ -463,6 +463,36 @@ int  nbls_kzg_monomial_log2n(const nbls_kzg_monomial* m, unsigned* log2_n);
  * 2^24 elements in the call, or one blob alone above the bounds of a pass: (2 N / c) * N > 2^22. */
 int nbls_kzg_compute_cells_and_proofs(nbls_ctx* ctx, const nbls_kzg_monomial* monomial, unsigned log2_cell, size_t n, const uint8_t* blobs, uint8_t* out_cells,
                                       uint8_t* out_proofs48 /* n * (2 N / c) * 48 */, int8_t* status /* n, may be NULL */);
+/* verify_cell_kzg_proof_batch: n_cells cells, each with its proof, against commitments given ONCE each and named by index (the specification deduplicates them the same way;
+ * a commitment no cell names is decoded and otherwise ignored; cells may repeat).  N comes from the handle, c = 2^log2_cell; cell k of the call is cell number cell_index[k]
+ * (< 2 N / c) of the blob committed to by commitments48[commitment_index[k]]: c elements, byte for byte one cell of nbls_kzg_compute_cells' output, on the coset h <omega_c>,
+ * h = g^rev(cell_index[k]), s = h^c.  With I, of degree < c, interpolating the cell, it holds exactly when
+ *   e(pi, [tau^c]G2) = e(C - [I(tau)]G1 + [s]pi, G2);
+ * the cells are checked together by a random linear combination with the weights r_k of nbls_verify_multiple, indexed by the cell's position k in the call (same seed rule: NULL
+ * = 32 bytes from getrandom(2) on every call, never a fixed seed):
+ *   e(sum_k [r_k]pi_k, [tau^c]G2) * e(sum_k [r_k]C_k - sum_(i<c) [S_i][tau^i]G1 + sum_k [r_k s_k]pi_k, -G2) = 1,   S_i = sum_k r_k (coefficient i of I_k) mod r.
+ * This is the specification's verify_cell_kzg_proof_batch_impl with SECRET WEIGHTS in place of its Fiat-Shamir powers, as nbls_kzg_verify_proofs.  A kernel with c lanes per
+ * cell interpolates every cell in registers (a coset inverse transform of size c), weighs and sums: the n_cells * c coefficients never reach memory on the accepting path.  The
+ * sum over [tau^i]G1 uses the handle's first c converted points; a Lagrange nbls_kzg_setup is not accepted in the handle's place.  log2_cell <= 6 IS A DELIBERATE LIMIT: the
+ * EIP's cell has 64 elements and one wavefront holds one cell (nbls_kzg_compute_cells has larger cells only as test sizes).
+ * Commitments and proofs: 48 bytes compressed, PointG1.fromHex's rules, subgroup check included, every commitment decoded once.  tau_c_g2_96: [tau^c]G2 = the setup's
+ * g2_monomial[c], 96 bytes compressed, PointG2.fromSignature's rules.  Cell elements must be canonical.  ZERO POINTS ARE VALID: 0xc0 00.. is the zero polynomial's commitment
+ * and the proof of any cell of a polynomial of degree < c; a zero point takes part as the identity and status 1 is never reported; either or both combined points may be the
+ * zero point (both: accepted; exactly one: rejected).
+ * status[k] (may be NULL), in this order: the named commitment's decoder status if >= 2; else 10 + the proof decoder's status if >= 2; else NBLS_ST_NON_CANONICAL when an
+ * element of the cell is >= r; else 0, or NBLS_ST_NOT_VERIFIED.  *all_ok = 1 exactly when every status is 0.  A cell with one of the first three statuses has weight zero
+ * everywhere, and the combined check never accepts while there is one; a neighbour is never disturbed.  Where the combined check does not accept, a per-cell pass judges every
+ * cell with the single-cell equation (the two prepared tables shared by all cells, one batched final exponentiation; a zero proof holds exactly when the G1 point on the right
+ * is the zero point); with status == NULL the call stops after the combined check instead and answers *all_ok = 0 (fast reject).
+ * Returns NBLS_OK whatever the cells hold; NBLS_EDECODE when tau_c_g2_96 does not decode or is the zero point; NBLS_EINVAL before any device work for a missing pointer,
+ * n_cells = 0 or n_commitments = 0, a handle created on another device, log2_cell > 6 or > log2_n, log2_n + 1 - log2_cell > 12 (more cells per blob than the largest table of
+ * roots has entries), a cell_index >= 2 N / c, a commitment_index >= n_commitments, n_cells > 2^20 or n_cells << log2_cell > 2^22 (one pass of the batched MSM, which the
+ * per-cell pass needs), n_commitments > 2^22.  *all_ok and status are NOT written when the call returns an error, NBLS_EDECODE included.  NOT an interface for secrets.  The
+ * consensus-spec test vectors have not been run. */
+int nbls_kzg_verify_cells(nbls_ctx* ctx, const nbls_kzg_monomial* monomial, unsigned log2_cell, size_t n_commitments, const uint8_t* commitments48, size_t n_cells,
+                          const uint32_t* commitment_index /* n_cells */, const uint32_t* cell_index /* n_cells */, const uint8_t* cells /* n_cells * (32 << log2_cell) */,
+                          const uint8_t* proofs48 /* n_cells */, const uint8_t* tau_c_g2_96, const uint8_t* seed32 /* NULL: from the OS */, int* all_ok,
+                          int8_t* status /* n_cells, may be NULL */);
 
 /* One rank's share of a verifyBatch spread over several GPUs (one process per GPU): the Miller product of this rank's n
  * (key, message) pairs, times millerLoop(-G, S) on the ONE rank that passes the signature (d_sig96 = NULL elsewhere), WITHOUT the
@@ -493,7 +523,7 @@ const char* nbls_config_describe(void);   /* "NBLS_X=value(env|default) ...": ev
    nbls_verify_aggregates_indexed_shared, scratch slots 48 .. 50 (additions only, same version); then nbls_fr_op_batch, nbls_lagrange_at_zero, nbls_g2_combine_shares,
    nbls_g1_combine_shares, NBLS_FROP_*, NBLS_ST_BAD_IDS, scratch slots 51 .. 56 (additions only, same version); then nbls_field_kernel_raw (addition only, same version); then nbls_g1_poly_eval,
    nbls_g2_poly_eval, nbls_extra_program_kernel, NBLS_TUNE_POLY_SLAB, scratch slots 57 .. 61 (additions only, same version); then nbls_g1_msm_batch, nbls_g2_msm_batch,
-   nbls_g1_msm_rows, nbls_g2_msm_rows, NBLS_TUNE_MSMB_WINDOW / _BIG / _SLAB, the names "dbladd_g1" / "dbladd_g2" of nbls_extra_program_kernel, scratch slots 62 .. 63 (additions only, same version); then nbls_map_uniform_batch (addition only, same version); then nbls_fr_eval_roots, nbls_kzg_verify_proofs, nbls_kzg_verify_blobs, NBLS_ST_NON_CANONICAL, scratch slots 64 .. 68 (additions only, same version); then nbls_kzg_setup_create / _destroy / _log2n, nbls_fr_quotient_roots, nbls_kzg_commit_blobs, nbls_kzg_compute_proofs, nbls_kzg_compute_blob_proofs, scratch slots 69 .. 70 (additions only, same version); then nbls_fr_ntt, NBLS_NTT_*, nbls_kzg_compute_cells, nbls_kzg_monomial_create / _destroy / _log2n, nbls_kzg_compute_cells_and_proofs, NBLS_TUNE_CELLS_CHUNK, scratch slots 71 .. 73 (additions only, same version); with the MSM calls ONE CHANGE TO EXISTING CALLS, same version: nbls_g1_msm / nbls_g2_msm write all-zero output bytes when the status is 1 (the sum is the
+   nbls_g1_msm_rows, nbls_g2_msm_rows, NBLS_TUNE_MSMB_WINDOW / _BIG / _SLAB, the names "dbladd_g1" / "dbladd_g2" of nbls_extra_program_kernel, scratch slots 62 .. 63 (additions only, same version); then nbls_map_uniform_batch (addition only, same version); then nbls_fr_eval_roots, nbls_kzg_verify_proofs, nbls_kzg_verify_blobs, NBLS_ST_NON_CANONICAL, scratch slots 64 .. 68 (additions only, same version); then nbls_kzg_setup_create / _destroy / _log2n, nbls_fr_quotient_roots, nbls_kzg_commit_blobs, nbls_kzg_compute_proofs, nbls_kzg_compute_blob_proofs, scratch slots 69 .. 70 (additions only, same version); then nbls_fr_ntt, NBLS_NTT_*, nbls_kzg_compute_cells, nbls_kzg_monomial_create / _destroy / _log2n, nbls_kzg_compute_cells_and_proofs, NBLS_TUNE_CELLS_CHUNK, scratch slots 71 .. 73 (additions only, same version); then nbls_kzg_verify_cells, scratch slots 74 .. 78 (addition only, same version); with the MSM calls ONE CHANGE TO EXISTING CALLS, same version: nbls_g1_msm / nbls_g2_msm write all-zero output bytes when the status is 1 (the sum is the
    zero point).  The bytes were unspecified there before (what the affine conversion made of a Z that is 0 mod p: in G1 a zero x and an arbitrary y); the status, and every output with status 0, are unchanged.
    nbls_msm_dev, which leaves its result on the device, is not changed.
    4 (round 6): nbls_hw_queues, NBLS_TUNE_WIDE_MAX, NBLS_TUNE_H2C_NORM_MIN, NBLS_TUNE_INV_WIDE_MAX, NBLS_TUNE_LS_MAX / _LS2_MAX (additions only); the library sets GPU_MAX_HW_QUEUES = 22 at load when the variable is unset (see nbls_pool_init below).

@@ -444,4 +444,37 @@ NBLS_FR_HD void fr_cell_chain(const uint8_t* coef32, unsigned log2_n, unsigned l
   }
 }
 
+// ---- The interpolation of cells (verify_cell_kzg_proof_batch of EIP-7594; kzg_cell_interp_kernel and nbls_sim_kzg_cell_interp).  Cell k holds the values of p on the coset
+// h_k <omega_c> in bit-reversed order, h_k = g^rev(k), g = omega_2N; its interpolation polynomial has the coefficients
+//   a_(k,i) = h_k^(-i) / c * (the way back of the network above, size c, on the cell's values)_i.
+// c = 2^log2_cell <= 64 lanes own one cell: lane i holds element i between the stages and coefficient i after them, so a cell never leaves the registers of one wavefront.  A
+// stage pairs lane i with lane i ^ len (the caller brings the partner's value: a cross-lane read on the device, an array on the simulator): the lane whose bit `len` is clear
+// keeps lo + hi, the other (lo - hi) / zeta with the table of the inverse roots of size c -- fr_ntt_stage's butterfly with both halves computed on every lane and one
+// selected.  Elements stay plain, the tables and factors are in Montgomery form.
+NBLS_FR_HD Fr fr_cell_stage(const Fr& mine, const Fr& theirs, uint32_t i, unsigned log2_len, unsigned log2_cell, const Fr* iroots) {
+  const uint32_t up = (uint32_t)0 - ((i >> log2_len) & 1);   // this lane holds the butterfly's upper element
+  const Fr u = fr_select(up, theirs, mine), v = fr_select(up, mine, theirs);
+  const Fr d = fr_sub(u, v);
+  const Fr dz = log2_len + 1 == log2_cell ? d : fr_mul(d, iroots[2 * (i >> (log2_len + 1))]);   // (the one block of the last stage has zeta = 1)
+  return fr_select(up, dz, fr_add(u, v));
+}
+// what coefficient i is multiplied by after the stages: (1 / h_k)^i / c, from the table's entry 1 / h_k (log2_cell bits of the index: no inversion, no long exponent)
+NBLS_FR_HD Fr fr_cell_factor(const Fr& hinv, uint32_t i, unsigned log2_cell) { return fr_mul(fr_pow_index(hinv, i, log2_cell), fr_inv_pow2(log2_cell)); }
+// entry k of the table of the M = 2^log2_m inverse shifts of (log2_n, log2_cell), log2_m = log2_n + 1 - log2_cell:  1 / h_k = g^(2 N - rev(k)), an exponent of 14 bits at most
+NBLS_FR_HD Fr fr_cell_ishift_entry(const Fr& g, unsigned log2_n, unsigned log2_m, uint32_t k) { return fr_pow_index(g, (2u << log2_n) - fr_bitrev(k, log2_m), 14); }
+// The lanes of a launch: workgroups of FR_CELL_LANES lanes, lane groups of c lanes side by side, group q of the launch on the cells q, q + groups, ..  The rows mode gives every
+// cell a group of its own; the sum mode lets a group walk FR_CELL_WALK cells (fewer workgroups, hence fewer partial rows, while the device stays filled at the sizes that matter)
+enum { FR_CELL_LANES = 256, FR_CELL_WALK = 4, FR_CELL_MAX_WG = 1024 };
+NBLS_FR_HD uint32_t fr_cell_workgroups(uint32_t n_cells, unsigned log2_cell, bool sum) {
+  const uint64_t per_wg = (uint64_t)(FR_CELL_LANES >> log2_cell) * (sum ? FR_CELL_WALK : 1), wg = (n_cells + per_wg - 1) / per_wg;
+  return (uint32_t)(sum && wg > FR_CELL_MAX_WG ? FR_CELL_MAX_WG : wg);
+}
+// One cell on one lane, after the cross-lane part (bad: all ones when an element of the cell is >= r; v: the lane's value after the stages, of the cell's elements with a
+// refused cell's replaced by zero): -> the lane's coefficient a_(k,i), zero for a cell that is out (pre != 0, refused, or past the end: `out` all ones)
+NBLS_FR_HD Fr fr_cell_coeff(const Fr& v, const Fr& hinv, uint32_t i, unsigned log2_cell, uint32_t out) {
+  return fr_select(out, fr_zero(), fr_mul(v, fr_cell_factor(hinv, i, log2_cell)));
+}
+// the cell's status: what came in (a decoder's refusal), else NBLS_ST_NON_CANONICAL for an element >= r, else 0
+NBLS_FR_HD int fr_cell_status(int pre, uint32_t bad) { return pre ? pre : (int)(bad & 21); }
+
 }  // namespace nbls

@@ -2,6 +2,7 @@
 // blobs that are only committed to, the closing kernel of the compressed results): polynomials in evaluation form evaluated at a point (nbls_fr_eval_roots, and y_i = p_i(z_i) of
 // nbls_kzg_verify_blobs), the table of roots of unity, and the small Fr kernels around the two MSMs of the combined check and the ladders of the per-item pass.  The arithmetic is
 // fr_exec.h's, written once and shared with the simulator (nbls_sim_fr_eval_roots); the curve arithmetic runs as step programs (decoder, MSM, ladders, Miller loops).
+// Further down: the transform and the cells of EIP-7594 (pipelines_kzg_cells.cpp) and the interpolation of cells for their verifier (pipelines_kzg_verify_cells.cpp).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <atomic>
@@ -248,15 +249,113 @@ __global__ void kzg_item_scalars_kernel(u32 n, const int8_t* __restrict__ pre, c
   fr_store_be(fr_select(use_p, fr_load_be(z32 + 32ull * i), zero), zs + 32ull * i);
   fr_store_be(fr_neg(fr_select(live, fr_load_be(y32 + 32ull * i), zero)), ny + 32ull * i);
 }
-// status[i] of the per-item pass.  x = C_i + [z_i]pi_i - [y_i]G1: with a zero proof the tuple holds exactly when x is the zero point; with a non-zero proof a zero x fails
+// status[i] of the per-item pass (pst: the decoder statuses of the n proofs).  x = C_i + [z_i]pi_i - [y_i]G1 (the cells: C - [I_k(tau)]G1 + [s_k]pi_k): with a zero proof the tuple holds exactly when x is the zero point; with a non-zero proof a zero x fails
 // (e(pi, [tau]G2) is not one) and otherwise the pairing product decides (one[i]: the final exponentiation is Fp12.ONE)
-__global__ void kzg_item_status_kernel(u32 n, const int8_t* __restrict__ pre, const int8_t* __restrict__ dst, const int8_t* __restrict__ xzero, const uint8_t* __restrict__ one,
+__global__ void kzg_item_status_kernel(u32 n, const int8_t* __restrict__ pre, const int8_t* __restrict__ pst, const int8_t* __restrict__ xzero, const uint8_t* __restrict__ one,
                                        int8_t* __restrict__ status) {
   const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const bool pz = dst[n + i] == 1, xz = xzero[i] == 1;
+  const bool pz = pst[i] == 1, xz = xzero[i] == 1;
   const bool ok = pz ? xz : (!xz && one[i] != 0);
   status[i] = pre[i] ? pre[i] : ok ? 0 : NBLS_ST_NOT_VERIFIED;
+}
+
+// ---- The cells of EIP-7594 on the verifier's side (pipelines_kzg_verify_cells.cpp); fr_exec.h has the arithmetic.
+constexpr int CL = FR_CELL_LANES;
+// the table of the M = 2^log2_m inverse shifts 1 / h_k of (log2_n, log2_cell), Montgomery form: built once per context and pair, as the tables of roots are
+__global__ void kzg_cell_ishifts_kernel(u32 log2_n, u32 log2_m, Fr* __restrict__ table) {
+  const u32 k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k < (1u << log2_m)) table[k] = fr_cell_ishift_entry(fr_omega(log2_n + 1), log2_n, log2_m, k);
+}
+// lane (t ^ mask)'s value: the c <= 64 lanes of a cell lie inside one wavefront, so a stage's exchange is a cross-lane read -- no LDS, and no barrier between the stages
+__device__ inline Fr fr_lane_xor(const Fr& v, u32 mask) {
+  Fr o;
+#pragma unroll
+  for (int l = 0; l < FR_NL; l++) o.l[l] = (u32)__shfl_xor((int)v.l[l], (int)mask);
+  return o;
+}
+// the workgroup's lanes hold one value per (lane group, column): the column sums to part[0 .. c), a tree of modular additions; every wavefront meets every barrier
+__device__ inline void cell_column_tree(Fr* part, u32 t, u32 c, const Fr& mine) {
+  part[t] = mine;
+  for (u32 s = CL / 2; s >= c && s > 0; s >>= 1) {
+    __syncthreads();
+    if (t < s) part[t] = fr_add(part[t], part[t + s]);
+  }
+}
+// The interpolation polynomials of n_cells cells of c = 2^log2_cell <= 64 elements each, c lanes per cell (fr_exec.h fr_cell_*): a wavefront holds 64 / c cells side by side, a
+// workgroup four wavefronts.  Lane group q of the launch takes the cells q, q + groups, .. -- the same number of rounds on every lane, a round past the end on the last cell
+// with nothing kept -- and in every round: the elements in (32 bytes big-endian, 16-byte aligned), the canonical check over the group, the log2_cell stages towards the
+// coefficients, times (1 / h_k)^i / c with 1 / h_k = ishifts[cell_index[k]].  pre (may be NULL): a cell with pre[k] != 0 is out; so is one with an element >= r.  A cell that
+// is out has all-zero coefficients.  st_out (may be NULL): pre[k], else NBLS_ST_NON_CANONICAL, else 0.
+//   sum == 0 (rows): -a_(k,i) as 32 bytes big-endian to rows32[k * c + i], the rows of msm_rows_dev
+//   sum != 0:        the lane adds w_k a_(k,i) over its rounds (w32: the weights, 32 bytes big-endian, < r) in registers; the workgroup's groups meet in an LDS tree and
+//                    leave ONE row of c elements, partial[blockIdx.x * c + i], plain limbs -- kzg_cell_sum_kernel adds the rows.  No coefficient goes to memory
+template <bool sum>   // (two kernels, so that a trace tells the modes apart)
+__global__ void __launch_bounds__(CL) kzg_cell_interp_kernel(u32 log2_cell, u32 n_cells, const uint8_t* __restrict__ cells, const u32* __restrict__ cell_index,
+                                                             const int8_t* __restrict__ pre, const uint8_t* __restrict__ w32, const Fr* __restrict__ iroots,
+                                                             const Fr* __restrict__ ishifts, uint8_t* __restrict__ rows32, Fr* __restrict__ partial, int8_t* __restrict__ st_out) {
+  __shared__ Fr part[CL];
+  const u32 t = threadIdx.x, c = 1u << log2_cell, i = t & (c - 1);
+  const u32 groups = (gridDim.x * CL) >> log2_cell, q = (blockIdx.x * CL + t) >> log2_cell, rounds = (n_cells + groups - 1) / groups;
+  Fr acc = fr_zero();
+  for (u32 w = 0; w < rounds; w++) {
+    const u64 k = (u64)q + (u64)w * groups;
+    const bool valid = k < n_cells;
+    const u32 kk = valid ? (u32)k : n_cells - 1;
+    Fr v = fr_load_q(cells + (((u64)kk << log2_cell) + i) * 32);
+    u32 bad = fr_ge_r_mask(v);
+    for (u32 m = 1; m < c; m <<= 1) bad |= (u32)__shfl_xor((int)bad, (int)m);
+    const int p = pre ? pre[kk] : 0;
+    const u32 out = bad | ((u32)0 - (u32)(p != 0)) | ((u32)0 - (u32)!valid);
+    v = fr_select(bad, fr_zero(), v);
+    for (u32 ll = 0; ll < log2_cell; ll++) v = fr_cell_stage(v, fr_lane_xor(v, 1u << ll), i, ll, log2_cell, iroots);
+    const Fr a = fr_cell_coeff(v, ishifts[cell_index[kk]], i, log2_cell, out);
+    if (sum) acc = fr_add(acc, fr_mul(a, fr_mul(fr_load_q(w32 + 32ull * kk), fr_r2())));
+    else if (valid) fr_store_q(fr_neg(a), rows32 + (((u64)kk << log2_cell) + i) * 32);
+    if (st_out && valid && i == 0) st_out[kk] = (int8_t)fr_cell_status(p, bad);
+  }
+  if (!sum) return;   // (uniform)
+  cell_column_tree(part, t, c, acc);
+  if (t < c) partial[(u64)blockIdx.x * c + t] = part[t];   // (the lane's own last sum)
+}
+// out32[i] = -(sum over the n_parts partial rows of column i) mod r as 32 bytes big-endian, i < c: one workgroup, lane group g on the rows g, g + groups, ..
+__global__ void __launch_bounds__(CL) kzg_cell_sum_kernel(u32 log2_cell, u32 n_parts, const Fr* __restrict__ partial, uint8_t* __restrict__ out32) {
+  __shared__ Fr part[CL];
+  const u32 t = threadIdx.x, c = 1u << log2_cell, i = t & (c - 1);
+  Fr acc = fr_zero();
+  for (u32 p = t >> log2_cell; p < n_parts; p += CL >> log2_cell) acc = fr_add(acc, partial[(u64)p * c + i]);
+  cell_column_tree(part, t, c, acc);
+  if (t < c) fr_store_q(fr_neg(part[t]), out32 + 32ull * t);
+}
+// pre0[k]: what the two decoders say about cell k before its elements are looked at -- the named commitment's status if >= 2, else 10 + the proof's if >= 2, else 0
+__global__ void kzg_cell_pre_kernel(u32 n, const int8_t* __restrict__ dstc, const int8_t* __restrict__ dstp, const u32* __restrict__ ci, int8_t* __restrict__ pre0) {
+  const u32 k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= n) return;
+  const int sc = dstc[ci[k]], sp = dstp[k];
+  pre0[k] = (int8_t)(sc >= 2 ? sc : sp >= 2 ? 10 + sp : 0);
+}
+// kzg_items_kernel's part for cells, one cell per lane.  dstc / affc: the decoder's statuses and points of the commitments, named by ci[k]; dstp / affp: of the n proofs; pre:
+// the cells' statuses before any pairing (kzg_cell_interp_kernel's st_out); sroots: the table of the M roots, s_k = entry cell_index[k].  A cell with pre != 0 gets zero
+// scalars everywhere; a zero point takes part as the identity: zero scalars for that point alone.  The commitment of every cell is gathered into gath (its status into gst),
+// and every point that a zero scalar stands for is the generator, so that the MSMs read points of the curve only.
+//   s1[k] = r_k (the 64-bit MSM over the proofs);  s2[k] = r_k (over the gathered commitments);  s3[k] = r_k s_k mod r (the 256-bit MSM over the proofs);
+//   zs[k] = s_k (the ladder of the per-cell pass; zero where the cell is out or its proof is the zero point)
+__global__ void kzg_cell_items_kernel(u32 n, const int8_t* __restrict__ dstc, const int8_t* __restrict__ dstp, const u32* __restrict__ ci, const u32* __restrict__ cell_index,
+                                      const int8_t* __restrict__ pre, const uint8_t* __restrict__ w32, const Fr* __restrict__ sroots, const uint8_t* __restrict__ gen96,
+                                      const uint8_t* __restrict__ affc, uint8_t* __restrict__ affp, uint8_t* __restrict__ gath, int8_t* __restrict__ gst,
+                                      uint8_t* __restrict__ s1, uint8_t* __restrict__ s2, uint8_t* __restrict__ s3, uint8_t* __restrict__ zs) {
+  const u32 k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= n) return;
+  const int sc = dstc[ci[k]], sp = dstp[k];
+  const u32 live = (u32)0 - (u32)(pre[k] == 0), use_c = live & ((u32)0 - (u32)(sc == 0)), use_p = live & ((u32)0 - (u32)(sp == 0));
+  const Fr zero = fr_zero(), r = fr_load_be(w32 + 32ull * k), sk = sroots[cell_index[k]];
+  fr_store_be(fr_select(use_p, r, zero), s1 + 32ull * k);
+  fr_store_be(fr_select(use_c, r, zero), s2 + 32ull * k);
+  fr_store_be(fr_select(use_p, fr_mul(r, sk), zero), s3 + 32ull * k);
+  fr_store_be(fr_select(use_p, fr_from_mont(sk), zero), zs + 32ull * k);
+  gst[k] = (int8_t)sc;
+  copy96(gath + 96ull * k, use_c ? affc + 96ull * ci[k] : gen96);
+  if (!use_p) copy96(affp + 96ull * k, gen96);
 }
 
 // The running products of N = 4096 take more than the 64 KB a launch may ask for by default.  The limit is a per-device function attribute: set once on every device a launch of
@@ -335,10 +434,35 @@ int nbls_kzg_items_launch(unsigned n, const void* dst, const void* w32, const vo
   const int e = launch_1d(kzg_items_kernel, n, 64, 0, stream, n, dst, w32, z32, y32, yst, gen96, aff, s1, s2, t, pre);
   return e ? e : launch_1d(kzg_sum_kernel, 256, 256, 0, stream, n, t, (uint8_t*)s2 + 64ull * n);
 }
+// the table of the 2^log2_m inverse shifts of (log2_n, log2_cell = log2_n + 1 - log2_m)
+int nbls_kzg_cell_ishifts_launch(unsigned log2_n, unsigned log2_m, void* table, hipStream_t stream) {
+  if (log2_n < 1 || log2_n > 12 || log2_m < 1 || log2_m > log2_n + 1) return (int)hipErrorInvalidValue;
+  return launch_1d(kzg_cell_ishifts_kernel, (u64)1 << log2_m, 64, 0, stream, log2_n, log2_m, table);
+}
+// n_cells cells through kzg_cell_interp_kernel (the arrays as the kernel states them; cells, w32, rows32 and out32 16-byte aligned).  sum == 0: the rows to rows32.  Else the
+// -S_i to out32 (c x 32 bytes) by way of `partial`, which holds fr_cell_workgroups(n_cells, log2_cell, true) rows of c elements
+int nbls_kzg_cell_interp_launch(unsigned log2_cell, unsigned n_cells, int sum, const void* cells, const uint32_t* cell_index, const void* pre, const void* w32, const void* iroots,
+                                const void* ishifts, void* rows32, void* partial, void* out32, void* st_out, hipStream_t stream) {
+  if (!n_cells) return 0;
+  if (log2_cell > 6 || (((uintptr_t)cells | (uintptr_t)w32 | (uintptr_t)rows32 | (uintptr_t)out32 | (uintptr_t)partial) & 15) || (sum ? !w32 || !partial || !out32 : !rows32) ||
+      (log2_cell && !iroots))
+    return (int)hipErrorInvalidValue;
+  const unsigned wg = fr_cell_workgroups(n_cells, log2_cell, sum != 0);
+  const int e = launch_1d(sum ? kzg_cell_interp_kernel<true> : kzg_cell_interp_kernel<false>, (u64)wg * CL, CL, 0, stream, log2_cell, n_cells, cells, cell_index, pre, w32, iroots,
+                          ishifts, rows32, partial, st_out);
+  return e || !sum ? e : launch_1d(kzg_cell_sum_kernel, CL, CL, 0, stream, log2_cell, wg, partial, out32);
+}
+int nbls_kzg_cell_pre_launch(unsigned n, const void* dstc, const void* dstp, const uint32_t* ci, void* pre0, hipStream_t stream) {
+  return launch_1d(kzg_cell_pre_kernel, n, 256, 0, stream, n, dstc, dstp, ci, pre0);
+}
+int nbls_kzg_cell_items_launch(unsigned n, const void* dstc, const void* dstp, const uint32_t* ci, const uint32_t* cell_index, const void* pre, const void* w32, const void* sroots,
+                               const void* gen96, const void* affc, void* affp, void* gath, void* gst, void* s1, void* s2, void* s3, void* zs, hipStream_t stream) {
+  return launch_1d(kzg_cell_items_kernel, n, 64, 0, stream, n, dstc, dstp, ci, cell_index, pre, w32, sroots, gen96, affc, affp, gath, gst, s1, s2, s3, zs);
+}
 int nbls_kzg_item_scalars_launch(unsigned n, const void* pre, const void* dst, const void* z32, const void* y32, void* zs, void* ny, hipStream_t stream) {
   return launch_1d(kzg_item_scalars_kernel, n, 64, 0, stream, n, pre, dst, z32, y32, zs, ny);
 }
-int nbls_kzg_item_status_launch(unsigned n, const void* pre, const void* dst, const void* xzero, const void* one, void* status, hipStream_t stream) {
-  return launch_1d(kzg_item_status_kernel, n, 256, 0, stream, n, pre, dst, xzero, one, status);
+int nbls_kzg_item_status_launch(unsigned n, const void* pre, const void* pst, const void* xzero, const void* one, void* status, hipStream_t stream) {
+  return launch_1d(kzg_item_status_kernel, n, 256, 0, stream, n, pre, pst, xzero, one, status);
 }
 }

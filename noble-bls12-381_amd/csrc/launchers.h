@@ -68,7 +68,7 @@ int nbls_kzg_eval_launch(unsigned log2_n, unsigned n, const void* evals32, const
 int nbls_kzg_items_launch(unsigned n, const void* dst, const void* w32, const void* z32, const void* y32, const void* yst, const void* gen96, void* aff, void* s1, void* s2,
                           void* t, void* pre, hipStream_t stream);
 int nbls_kzg_item_scalars_launch(unsigned n, const void* pre, const void* dst, const void* z32, const void* y32, void* zs, void* ny, hipStream_t stream);
-int nbls_kzg_item_status_launch(unsigned n, const void* pre, const void* dst, const void* xzero, const void* one, void* status, hipStream_t stream);
+int nbls_kzg_item_status_launch(unsigned n, const void* pre, const void* pst, const void* xzero, const void* one, void* status, hipStream_t stream);
 int nbls_kzg_quotient_launch(unsigned log2_n, unsigned n, const void* evals32, const void* z32, const void* roots, void* out_y32, void* out_q32, void* status,
                              hipStream_t stream);
 int nbls_kzg_canon_launch(unsigned log2_n, unsigned n, void* evals32, void* status, hipStream_t stream);
@@ -78,4 +78,10 @@ int nbls_kzg_ntt_launch(unsigned log2_n, unsigned mode, unsigned n, const void* 
                         void* out32, void* coef32, void* status, hipStream_t stream);
 int nbls_kzg_cell_rows_launch(unsigned log2_n, unsigned log2_cell, unsigned n, const void* coef32, const void* sroots, const void* blob_st, void* out_q32, void* row_st,
                               hipStream_t stream);
+int nbls_kzg_cell_ishifts_launch(unsigned log2_n, unsigned log2_m, void* table, hipStream_t stream);
+int nbls_kzg_cell_interp_launch(unsigned log2_cell, unsigned n_cells, int sum, const void* cells, const uint32_t* cell_index, const void* pre, const void* w32, const void* iroots,
+                                const void* ishifts, void* rows32, void* partial, void* out32, void* st_out, hipStream_t stream);
+int nbls_kzg_cell_pre_launch(unsigned n, const void* dstc, const void* dstp, const uint32_t* ci, void* pre0, hipStream_t stream);
+int nbls_kzg_cell_items_launch(unsigned n, const void* dstc, const void* dstp, const uint32_t* ci, const uint32_t* cell_index, const void* pre, const void* w32, const void* sroots,
+                               const void* gen96, const void* affc, void* affp, void* gath, void* gst, void* s1, void* s2, void* s3, void* zs, hipStream_t stream);
 }

@@ -1,5 +1,5 @@
 // nbls_internal.h -- what the translation units of the runtime share (runtime.cpp / tuning.cpp / pipelines_pairing.cpp / pipelines_codec.cpp / pipelines_verify.cpp /
-// pipelines_multi_verify.cpp / pipelines_threshold.cpp / pipelines_poly.cpp / pipelines_msm.cpp / pipelines_kzg.cpp / pipelines_kzg_prove.cpp / pipelines_kzg_cells.cpp; pool and multi-device handles: nbls_multi.cpp): the context, the map of its scratch slots (enum Slot: the one place that says which chain owns
+// pipelines_multi_verify.cpp / pipelines_threshold.cpp / pipelines_poly.cpp / pipelines_msm.cpp / pipelines_kzg.cpp / pipelines_kzg_prove.cpp / pipelines_kzg_cells.cpp / pipelines_kzg_verify_cells.cpp; pool and multi-device handles: nbls_multi.cpp): the context, the map of its scratch slots (enum Slot: the one place that says which chain owns
 // which slot, checked at compile time), the launch helpers, the staged block of the host-buffer pipelines (staging.h, included at the end) and the device-side pipelines the
 // exported entry points are built from.  Internal functions have hidden visibility (csrc/Makefile: -fvisibility=hidden).
 #pragma once
@@ -84,9 +84,13 @@ enum Slot {
   // cells_pipeline and nbls_fr_ntt (pipelines_kzg_cells.cpp): the coefficients of every blob and the blobs' statuses | one chunk's quotient rows (the MSM's scalars) and the
   // rows' statuses | what is read back (transformed rows or cells, compressed proofs, statuses), then one chunk's affine sums, zero flags and closing statuses
   SB_KZGC_COEFS = 71, SB_KZGC_ROWS = 72, SB_KZGC_OUT = 73,
+  // verify_cells_pipeline (pipelines_kzg_verify_cells.cpp): the decoded commitments and proofs, the gathered commitments, their statuses | weights, the scalars of the MSMs,
+  // the partial rows and the row of the -S_i, the statuses before the elements are looked at | [tau^c]G2 and -G2, their two line tables, the two combined points, the three
+  // parts of B | what is read back | everything of the per-cell pass (the rows of the batched MSM in front)
+  SB_KZGV_POINTS = 74, SB_KZGV_SCALARS = 75, SB_KZGV_PAIRS = 76, SB_KZGV_OUT = 77, SB_KZGV_ITEMS = 78,
   NSB
 };
-static_assert(NSB == 74, "sb[] indices do not shift");
+static_assert(NSB == 79, "sb[] indices do not shift");
 constexpr SlotMask slot_bit(int i) { return (SlotMask)1 << i; }
 template <typename... S> constexpr SlotMask slots(S... s) { return (slot_bit(s) | ...); }
 // one instance of dev_decompress: three arrays of field elements and the exponentiation table
@@ -116,6 +120,7 @@ constexpr SlotMask M_POLY_OWN = slots(SB_STAGED, SB_POLY_COEFS, SB_POLY_LABELS, 
 constexpr SlotMask M_KZG_OWN = slots(SB_STAGED, SB_KZG_POINTS, SB_KZG_SCALARS, SB_KZG_PAIRS, SB_KZG_OUT, SB_KZG_ITEMS);   // kzg_pipeline: what outlives the decoder, the MSMs and the ladders it calls
 constexpr SlotMask M_KZGP_OWN = slots(SB_STAGED, SB_KZGP_SCALARS, SB_KZGP_OUT);   // kzg_prove_pipeline: what outlives the batched MSM it calls (msm_rows_dev, on M_MSMB_OWN)
 constexpr SlotMask M_KZGC_OWN = slots(SB_STAGED, SB_KZGC_COEFS, SB_KZGC_ROWS, SB_KZGC_OUT);   // cells_pipeline: what outlives the batched MSM of every chunk
+constexpr SlotMask M_KZGV_OWN = slots(SB_STAGED, SB_KZGV_POINTS, SB_KZGV_SCALARS, SB_KZGV_PAIRS, SB_KZGV_OUT, SB_KZGV_ITEMS);   // verify_cells_pipeline: what outlives the decoder, the MSMs, the batched MSM and the ladder it calls
 constexpr SlotMask M_MSMB_OWN = slots(SB_MSMB_CALL, SB_MSMB_SLAB);   // msm_batch_pipeline: what outlives the dev_msm calls of its big groups
 // what runs side by side
 static_assert(!(M_VB_MAIN & DEC_KEYS.mask()), "verifyBatch decodes its keys (side2, or the sub-batch's own stream) beside the hash chain");
@@ -137,6 +142,10 @@ static_assert(!((M_KZGP_OWN & ~slot_bit(SB_STAGED)) & (M_KZG_OWN | M_POLY_OWN | 
 static_assert(!(M_KZGC_OWN & (M_MSMB_OWN | DEC_MAIN.mask())), "cells_pipeline: the batched MSM runs chunk after chunk while the staged blobs, the coefficients and the results are held; nbls_kzg_monomial_create decodes on the main slots");
 static_assert(!((M_KZGC_OWN & ~slot_bit(SB_STAGED)) & (M_KZGP_OWN | M_KZG_OWN | M_POLY_OWN | M_THR_OWN | M_RLC_MAIN | M_RLC_SIDE | M_RLC_SIDE2 | M_VB_MAIN | M_LADDER | MSM_MAIN.mask() | MSM_RLC.mask())),
               "cells_pipeline keeps to slots of its own");
+static_assert(!(M_KZGV_OWN & (DEC_MAIN.mask() | MSM_RLC.mask() | M_LADDER | M_MSMB_OWN)),
+              "verify_cells_pipeline: the decoder, the MSMs (on the slots of MSM_RLC: MSM_MAIN holds SB_STAGED), the batched MSM and the ladder of the per-cell pass regrow their slots while the call holds the staged block and its own");
+static_assert(!((M_KZGV_OWN & ~slot_bit(SB_STAGED)) & (M_KZGC_OWN | M_KZGP_OWN | M_KZG_OWN | M_POLY_OWN | M_THR_OWN | M_RLC_MAIN | M_RLC_SIDE | M_RLC_SIDE2 | M_VB_MAIN | MSM_MAIN.mask())),
+              "verify_cells_pipeline keeps to slots of its own");
 // ---- END scratch slots -------------------------------------------------------------------------------------------------------------------------------------
 #define EXPORT extern "C" __attribute__((visibility("default")))
 extern std::recursive_mutex g_null_mu;   // locked in place of a context's mutex when the caller passed no context (the call then fails with NBLS_EINVAL)
@@ -227,6 +236,7 @@ struct nbls_ctx {
   u32* qp_table = nullptr;      // multiples of p for the weak reduction (vm_exec.h weak_reduce), device copy
   uint8_t* kzg_roots[13] = {nullptr};   // kzg_kernels.hip: the 2^k roots of unity in bit-reversed order, Montgomery form (32 bytes each), built on first use of log2_n = k, freed with the context
   uint8_t* kzg_inv_roots[13] = {nullptr};   // the same for 1 / omega: what nbls_fr_ntt's stages towards the coefficients divide by
+  uint8_t* kzg_cell_ishifts[13][7] = {{nullptr}};   // [log2_n][log2_cell]: the 2 N / c inverse shifts 1 / h_k of the cells that nbls_kzg_verify_cells interpolates, built on first use
   uint8_t* unit_lines = nullptr;   // a line table whose 68 lines are all 1 (c0 = 1, c1 = c2 = 0): the neutral partner of an odd last pair
   uint8_t* partial = nullptr;   // 576 bytes: the Fp12 partial of the *_partial entry points (multi-GPU reductions)
   uint8_t* L = nullptr; size_t cap_L = 0;   // line tables of the Miller loop (LINE_BYTES each), at most LINES_CHUNK of them
@@ -421,6 +431,14 @@ int msm_rows_dev(nbls_ctx* ctx, const MsmbPlan& pl, const uint8_t* conv_pts, con
 int kzg_roots(nbls_ctx* ctx, unsigned log2_n, hipStream_t s, const uint8_t** table);
 int kzg_inv_roots(nbls_ctx* ctx, unsigned log2_n, hipStream_t s, const uint8_t** table);
 void blob_challenges(unsigned log2_n, size_t n, const uint8_t* blobs, const uint8_t* c48, uint8_t* z32);
+// pipelines_kzg.cpp, what kzg_pipeline and verify_cells_pipeline (pipelines_kzg_verify_cells.cpp) share: -G2 in affine wire bytes; the combined check from the three parts of
+// B to its verdict; the per-item pass from the three summands of every X_i to the statuses (the buffers as offsets into one carved block)
+const uint8_t* neg_g2_wire();
+struct KzgCombined { uint8_t *B3, *BST, *BJ, *BN, *PT2, *TB, *RES, *BK; };
+int kzg_combined_tail(nbls_ctx* ctx, const KzgCombined& k, hipStream_t s);
+struct KzgItemTail { size_t p3, st3, proj, n, ni, x, e, v, xz, fs; };
+size_t kzg_item_tail_carve(size_t n, size_t* off, KzgItemTail* t);
+int kzg_item_tail(nbls_ctx* ctx, size_t n, const KzgItemTail& t, uint8_t* block, const uint8_t* proofs96, const uint8_t* tables, const uint8_t* pre, const uint8_t* proof_st, hipStream_t s);
 // a trusted setup's Lagrange basis in the form the batched MSM reads (nbls_kzg_setup_create): 2^log2_n points, each with its endomorphism image, raw projective
 struct nbls_kzg_setup { int device = 0; unsigned log2_n = 0; uint8_t* pts = nullptr; };
 // the monomial basis [tau^i]G1 in the same form (nbls_kzg_monomial_create): a handle type of its own, so that neither basis is taken for the other

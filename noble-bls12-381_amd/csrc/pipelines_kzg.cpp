@@ -22,7 +22,7 @@ static const size_t KZG_MAX_ELEMS = (size_t)1 << 24;
 static const size_t KZG_MAX_ITEMS = (size_t)1 << 22;   // dev_msm's bound: every sum of the chain has n points
 
 // -G2 in affine wire bytes (x.c0 || x.c1 || p - y.c0 || p - y.c1), from the generator's standard coordinates
-static const uint8_t* neg_g2_wire() {
+const uint8_t* neg_g2_wire() {
   static uint8_t w[192];
   static const bool once = [] {
     static const char* hex[5] = {
@@ -112,6 +112,54 @@ struct KzgIn { size_t n; unsigned log2_n; const uint8_t *blobs, *c48, *z32, *y32
 
 static size_t carve(size_t* off, size_t bytes) { const size_t o = *off; *off = o + ((bytes + 63) & ~(size_t)63); return o; }
 
+// From the three parts of B (affine points with a status each, 1 = the zero point) to the verdict of the combined check, shared with verify_cells_pipeline: raw projective,
+// the identity where the status says so, two complete additions, affine again with B's own zero flag (BK[2]; A and its flag BK[1] are in place), the generator for a zero A or
+// B, two Miller loops against the two tables, product, final exponentiation, BK[0] = the result is one
+int kzg_combined_tail(nbls_ctx* ctx, const KzgCombined& k, hipStream_t s) {
+  const size_t p = 3 * RAW; int r;
+  if ((r = run(ctx, P_G1_TO_PROJ, 3, {B(0, k.B3, 96), B(3, k.BJ, p)}, s))) return r;
+  LAUNCHCHK(nbls_agg_points_launch(3, (unsigned)p, nullptr, k.BST, ctx->ident_g1, k.BJ, k.BJ, s));
+  if ((r = run(ctx, P_G1_ADD_AB, 1, {B(3, k.BJ, p), B(4, k.BJ + p, p), B(5, k.BJ, p)}, s)) || (r = run(ctx, P_G1_ADD_AB, 1, {B(3, k.BJ, p), B(4, k.BJ + 2 * p, p), B(5, k.BJ, p)}, s)) ||
+      (r = to_affine(ctx, false, 1, k.BJ, k.BN, k.BN + RAW, k.PT2 + 96, k.BK + 2, s)))
+    return r;
+  LAUNCHCHK(nbls_agg_fix_zero_launch(2, k.BK + 1, ctx->gen_g1, k.PT2, nullptr, s));
+  uint8_t* res = ctx->F;
+  if ((r = run(ctx, P_ACC_Q, 2, {B(0, k.PT2, 96), B(3, k.TB, LINE_BYTES), B(5, ctx->F, F12)}, s)) || (r = reduce_product(ctx, 2, &res, s)) || (r = finish_single(ctx, Window(), res, 1, k.RES, s))) return r;
+  LAUNCHCHK(nbls_rlc_is_one_launch(1, k.RES, k.BK, s));
+  return NBLS_OK;
+}
+// The per-item tail, shared likewise.  kzg_item_tail_carve: its buffers as offsets from the block's own start (*off: the caller's carving, moved past the block; returns where
+// the block starts).  kzg_item_tail: block = that start; the caller has written the three summands of every X_i to p3 (3 n affine points, summand after summand) and their
+// statuses to st3 (non-zero: the identity) -> X_i by two complete additions, millerLoop(pi_i, table 0) * millerLoop(X_i, table 1) with table_stride = 0, one batched final
+// exponentiation, compared with one on the device, kzg_item_status_kernel's rule -> the n statuses at fs.  The caller has run ensure_scratch(ctx, 2 n)
+size_t kzg_item_tail_carve(size_t n, size_t* off, KzgItemTail* t) {
+  const size_t p = 3 * RAW, start = *off;
+  size_t o = 0;
+  t->p3 = carve(&o, 3 * n * 96); t->st3 = carve(&o, 3 * n); t->proj = carve(&o, 3 * n * p); t->n = carve(&o, n * RAW); t->ni = carve(&o, n * RAW); t->x = carve(&o, n * 96);
+  t->e = carve(&o, n * 576); t->v = carve(&o, n); t->xz = carve(&o, n); t->fs = carve(&o, n);
+  *off = start + o;
+  return start;
+}
+int kzg_item_tail(nbls_ctx* ctx, size_t n, const KzgItemTail& t, uint8_t* block, const uint8_t* proofs96, const uint8_t* tables, const uint8_t* pre, const uint8_t* proof_st, hipStream_t s) {
+  const size_t p = 3 * RAW; int r;
+  uint8_t *P3 = block + t.p3, *ST3 = block + t.st3, *PJ = block + t.proj, *N = block + t.n, *NI = block + t.ni, *X = block + t.x, *E = block + t.e, *V = block + t.v, *XZ = block + t.xz,
+          *FS = block + t.fs;
+  // the summands as raw projective points, the identity where the status says so (a zero commitment, a zero product, an item that is out), then two complete additions
+  if ((r = run(ctx, P_G1_TO_PROJ, 3 * n, {B(0, P3, 96), B(3, PJ, p)}, s))) return r;
+  LAUNCHCHK(nbls_agg_points_launch(3 * n, (unsigned)p, nullptr, ST3, ctx->ident_g1, PJ, PJ, s));
+  if ((r = run(ctx, P_G1_ADD_AB, n, {B(3, PJ, p), B(4, PJ + n * p, p), B(5, PJ, p)}, s)) || (r = run(ctx, P_G1_ADD_AB, n, {B(3, PJ, p), B(4, PJ + 2 * n * p, p), B(5, PJ, p)}, s)) ||
+      (r = to_affine(ctx, false, n, PJ, N, NI, X, XZ, s)))
+    return r;
+  LAUNCHCHK(nbls_agg_fix_zero_launch((unsigned)n, XZ, ctx->gen_g1, X, nullptr, s));
+  if ((r = run(ctx, P_ACC_Q, n, {B(0, proofs96, 96), B(3, tables, 0), B(5, ctx->F, F12)}, s)) || (r = run(ctx, P_ACC_Q, n, {B(0, X, 96), B(3, tables + LINE_BYTES, 0), B(5, ctx->F + n * F12, F12)}, s)) ||
+      (r = run(ctx, P_MUL2S, n, {B(3, ctx->F, F12), B(4, ctx->F + n * F12, F12), B(5, ctx->F, F12)}, s)) || (r = run(ctx, P_NORM_RAW, n, {B(3, ctx->F, F12), B(4, ctx->N, RAW)}, s)) ||
+      (r = final_exp_pipeline(ctx, Window(), n, ctx->F, E, s)))
+    return r;
+  LAUNCHCHK(nbls_rlc_is_one_launch((unsigned)n, E, V, s));
+  LAUNCHCHK(nbls_kzg_item_status_launch((unsigned)n, pre, proof_st, XZ, V, FS, s));
+  return NBLS_OK;
+}
+
 static int kzg_pipeline(nbls_ctx* ctx, const KzgIn& in, int* all_ok, int8_t* status) {
   const size_t n = in.n, p = 3 * RAW;
   std::vector<uint8_t> zhost;   // (declared in front of the staged block: it outlives the wait of that block's destructor)
@@ -155,16 +203,8 @@ static int kzg_pipeline(nbls_ctx* ctx, const KzgIn& in, int* all_ok, int8_t* sta
   // B = sum_i [r_i]C_i | sum_i [r_i z_i]pi_i | [-sum_i r_i y_i]G1: affine points with a status each (1 = the zero point) -> raw projective, the identity where the status says so,
   // two complete additions, affine again with B's own zero flag
   if ((r = dev_msm(ctx, false, n, AFF, S2, 64, B3, BST, s, MSM_RLC)) || (r = dev_msm(ctx, false, n, AFF + n * 96, S2 + n * 32, 256, B3 + 96, BST + 1, s, MSM_RLC)) ||
-      (r = dev_point_mul(ctx, false, 1, ctx->gen_g1, 0, S2 + 2 * n * 32, B3 + 192, BST + 2, s)) || (r = run(ctx, P_G1_TO_PROJ, 3, {B(0, B3, 96), B(3, BJ, p)}, s)))
+      (r = dev_point_mul(ctx, false, 1, ctx->gen_g1, 0, S2 + 2 * n * 32, B3 + 192, BST + 2, s)) || (r = kzg_combined_tail(ctx, {B3, BST, BJ, BN, PT2, TB, RES, BK}, s)))
     return r;
-  LAUNCHCHK(nbls_agg_points_launch(3, (unsigned)p, nullptr, BST, ctx->ident_g1, BJ, BJ, s));
-  if ((r = run(ctx, P_G1_ADD_AB, 1, {B(3, BJ, p), B(4, BJ + p, p), B(5, BJ, p)}, s)) || (r = run(ctx, P_G1_ADD_AB, 1, {B(3, BJ, p), B(4, BJ + 2 * p, p), B(5, BJ, p)}, s)) ||
-      (r = to_affine(ctx, false, 1, BJ, BN, BN + RAW, PT2 + 96, BK + 2, s)))
-    return r;
-  LAUNCHCHK(nbls_agg_fix_zero_launch(2, BK + 1, ctx->gen_g1, PT2, nullptr, s));
-  uint8_t* res = ctx->F;
-  if ((r = run(ctx, P_ACC_Q, 2, {B(0, PT2, 96), B(3, TB, LINE_BYTES), B(5, ctx->F, F12)}, s)) || (r = reduce_product(ctx, 2, &res, s)) || (r = finish_single(ctx, Window(), res, 1, RES, s))) return r;
-  LAUNCHCHK(nbls_rlc_is_one_launch(1, RES, BK, s));
   if ((r = io.fetch(BK, back, &got))) return r;
   if (got[3] != 0) return NBLS_EDECODE;   // [tau]G2 does not decode, or is the zero point
   const bool one = got[0] != 0, za = got[1] == 1, zb = got[2] == 1;
@@ -179,32 +219,19 @@ static int kzg_pipeline(nbls_ctx* ctx, const KzgIn& in, int* all_ok, int8_t* sta
   if (!status) return NBLS_OK;   // fast reject: no per-item work
   // ---- the per-item pass
   size_t sz_it = 0;
-  const size_t b_zs = carve(&sz_it, n * 32), b_ny = carve(&sz_it, n * 32), b_p3 = carve(&sz_it, 3 * n * 96), b_st3 = carve(&sz_it, 3 * n), b_proj = carve(&sz_it, 3 * n * p),
-               b_n = carve(&sz_it, n * RAW), b_ni = carve(&sz_it, n * RAW), b_x = carve(&sz_it, n * 96), b_e = carve(&sz_it, n * 576), b_v = carve(&sz_it, n), b_xz = carve(&sz_it, n),
-               b_fs = carve(&sz_it, n);
+  KzgItemTail t;
+  const size_t b_zs = carve(&sz_it, n * 32), b_ny = carve(&sz_it, n * 32), b_t = kzg_item_tail_carve(n, &sz_it, &t);
   uint8_t* IT;
   if ((r = need(ctx, SB_KZG_ITEMS, sz_it, &IT)) || (r = ensure_scratch(ctx, 2 * n))) return r;
-  uint8_t *ZS = IT + b_zs, *NY = IT + b_ny, *P3 = IT + b_p3, *ST3 = IT + b_st3, *PJ = IT + b_proj, *N = IT + b_n, *NI = IT + b_ni, *X = IT + b_x, *E = IT + b_e, *V = IT + b_v,
-          *XZ = IT + b_xz, *FS = IT + b_fs;
+  uint8_t *ZS = IT + b_zs, *NY = IT + b_ny, *P3 = IT + b_t + t.p3, *ST3 = IT + b_t + t.st3, *FS = IT + b_t + t.fs;
   ForkGuard guard;   // nothing is forked here: the guard is used for its wait alone.  fetch() has disarmed the staged block, and an error return below must not leave this chain running on slots the next call regrows
   LAUNCHCHK(nbls_kzg_item_scalars_launch((unsigned)n, PRE, DST, d_z, d_y, ZS, NY, s));
   HIPCHK(hipMemcpyAsync(P3, AFF, n * 96, hipMemcpyDeviceToDevice, s));
   HIPCHK(hipMemcpyAsync(ST3, DST, n, hipMemcpyDeviceToDevice, s));
-  if ((r = dev_point_mul(ctx, false, n, AFF + n * 96, 96, ZS, P3 + n * 96, ST3 + n, s)) || (r = dev_point_mul(ctx, false, n, ctx->gen_g1, 0, NY, P3 + 2 * n * 96, ST3 + 2 * n, s))) return r;
-  // C_i | [z_i]pi_i | [-y_i]G1 as raw projective points, the identity where the status says so (a zero commitment, a zero product, an item that is out), then two complete additions
-  if ((r = run(ctx, P_G1_TO_PROJ, 3 * n, {B(0, P3, 96), B(3, PJ, p)}, s))) return r;
-  LAUNCHCHK(nbls_agg_points_launch(3 * n, (unsigned)p, nullptr, ST3, ctx->ident_g1, PJ, PJ, s));
-  if ((r = run(ctx, P_G1_ADD_AB, n, {B(3, PJ, p), B(4, PJ + n * p, p), B(5, PJ, p)}, s)) || (r = run(ctx, P_G1_ADD_AB, n, {B(3, PJ, p), B(4, PJ + 2 * n * p, p), B(5, PJ, p)}, s)) ||
-      (r = to_affine(ctx, false, n, PJ, N, NI, X, XZ, s)))
+  // C_i | [z_i]pi_i | [-y_i]G1: the three summands of X_i
+  if ((r = dev_point_mul(ctx, false, n, AFF + n * 96, 96, ZS, P3 + n * 96, ST3 + n, s)) || (r = dev_point_mul(ctx, false, n, ctx->gen_g1, 0, NY, P3 + 2 * n * 96, ST3 + 2 * n, s)) ||
+      (r = kzg_item_tail(ctx, n, t, IT + b_t, AFF + n * 96, TB, PRE, DST + n, s)))
     return r;
-  LAUNCHCHK(nbls_agg_fix_zero_launch((unsigned)n, XZ, ctx->gen_g1, X, nullptr, s));
-  // millerLoop(pi_i, [tau]G2) * millerLoop(X_i, -G2): the two shared tables (table_stride = 0), one batched final exponentiation, compared with one on the device
-  if ((r = run(ctx, P_ACC_Q, n, {B(0, AFF + n * 96, 96), B(3, TB, 0), B(5, ctx->F, F12)}, s)) || (r = run(ctx, P_ACC_Q, n, {B(0, X, 96), B(3, TB + LINE_BYTES, 0), B(5, ctx->F + n * F12, F12)}, s)) ||
-      (r = run(ctx, P_MUL2S, n, {B(3, ctx->F, F12), B(4, ctx->F + n * F12, F12), B(5, ctx->F, F12)}, s)) || (r = run(ctx, P_NORM_RAW, n, {B(3, ctx->F, F12), B(4, ctx->N, RAW)}, s)) ||
-      (r = final_exp_pipeline(ctx, Window(), n, ctx->F, E, s)))
-    return r;
-  LAUNCHCHK(nbls_rlc_is_one_launch((unsigned)n, E, V, s));
-  LAUNCHCHK(nbls_kzg_item_status_launch((unsigned)n, PRE, DST, XZ, V, FS, s));
   if ((r = read_back(ctx, s, FS, n, &got))) return r;
   guard.armed = false;
   memcpy(status, got, n);

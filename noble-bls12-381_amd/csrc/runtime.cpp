@@ -360,6 +360,7 @@ EXPORT void nbls_destroy(nbls_ctx* ctx) {
   for (uint8_t* p : ctx->T) if (p) hipFree(p);
   for (uint8_t* p : ctx->kzg_roots) if (p) hipFree(p);
   for (uint8_t* p : ctx->kzg_inv_roots) if (p) hipFree(p);
+  for (auto& row : ctx->kzg_cell_ishifts) for (uint8_t* p : row) if (p) hipFree(p);
   for (uint8_t* p : ctx->sb) if (p) hipFree(p);
   for (auto& b : ctx->io_pool) if (b.p) hipFree(b.p);
   for (uint8_t* p : ctx->nib) if (p) hipFree(p);

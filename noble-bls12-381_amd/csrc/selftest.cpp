@@ -20,6 +20,8 @@ extern "C" int nbls_sim_fr_quotient_roots(unsigned log2_n, size_t n, const uint8
 extern "C" int nbls_sim_fr_ntt(unsigned log2_n, int dir, size_t n, const uint8_t* in32, const uint8_t* shift32, uint8_t* out32, int8_t* status);
 extern "C" int nbls_sim_kzg_cells(unsigned log2_n, size_t n, const uint8_t* blobs, uint8_t* out_cells, uint8_t* coef32, int8_t* status);
 extern "C" int nbls_sim_kzg_cell_rows(unsigned log2_n, unsigned log2_cell, size_t n, const uint8_t* coef32, uint8_t* out_q32);
+extern "C" int nbls_sim_kzg_cell_interp(unsigned log2_n, unsigned log2_cell, size_t n_cells, int sum, unsigned n_wg, const uint8_t* cells, const uint32_t* cell_index,
+                                        const int8_t* pre, const uint8_t* w32, uint8_t* out, int8_t* st_out);
 using namespace nbls;
 
 static void be48(uint8_t* o, const u32* limbs) { u32 w[12]; limbs_to_words(w, limbs); for (int i = 0; i < 12; i++) { u32 v = w[11 - i]; o[4 * i] = v >> 24; o[4 * i + 1] = v >> 16; o[4 * i + 2] = v >> 8; o[4 * i + 3] = v; } }
@@ -88,8 +90,20 @@ int main() {
       std::vector<uint8_t> q((size_t)2 * ((2 * N) >> log2_cell) * N * 32);
       if (nbls_sim_kzg_cell_rows(log2_n, log2_cell, 2, co.data(), q.data())) return 2;
     }
+    // the verifier's interpolation of whole-blob cells (c = N <= 64): three cells, the rows mode against the sum mode of each cell alone with weight one, over two workgroups
+    if (log2_n <= 6) {
+      const uint32_t idx[3] = {0, 1, 0};
+      std::vector<uint8_t> rows(3 * N * 32), sum(N * 32), one(32); std::vector<int8_t> cst(3, 1);
+      one[31] = 1;
+      if (nbls_sim_kzg_cell_interp(log2_n, log2_n, 3, 0, 0, cells.data(), idx, nullptr, nullptr, rows.data(), cst.data())) return 2;
+      if (cst[0] || cst[1] || cst[2]) { printf("CELL INTERP: a status is set\n"); bad++; }
+      for (size_t k = 0; k < 3; k++) {
+        if (nbls_sim_kzg_cell_interp(log2_n, log2_n, 1, 1, 2, cells.data() + k * N * 32, idx + k, nullptr, one.data(), sum.data(), nullptr)) return 2;
+        if (memcmp(sum.data(), rows.data() + k * N * 32, N * 32)) { printf("CELL INTERP: the sum of one cell differs from its row\n"); bad++; }
+      }
+    }
   }
-  printf("transform and cell rows ok\n");
+  printf("transform, cell rows and cell interpolation ok\n");
   if (memcmp(out1, out2, 576)) { printf("MISMATCH between the fused and the split Miller loop\n"); bad++; }
   printf("miller c0.c0.c0 ");
   for (int i = 0; i < 48; i++) printf("%02x", out1[i]);

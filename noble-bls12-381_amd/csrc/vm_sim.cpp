@@ -687,6 +687,65 @@ __attribute__((visibility("default"))) int nbls_sim_kzg_cell_rows(unsigned log2_
   }
   return 0;
 }
+// The interpolation of n_cells cells as kzg_cell_interp_kernel runs it (and kzg_cell_sum_kernel behind it in the sum mode): workgroups of FR_CELL_LANES lanes, lane groups of c
+// lanes, every phase of a round on all lanes of a workgroup before the next, a stage's partner value read from the lane i ^ len of the same group, the column trees of the
+// workgroup and of the closing kernel in the kernel's order.  n_wg: the workgroups of the launch (0: as many as the launcher takes).  sum == 0: out = the n_cells rows of
+// c scalars -a_(k,i); else the c scalars -S_i.  pre, w32 (rows mode) and st_out may be NULL.  -1 where the device call refuses the sizes or an index
+__attribute__((visibility("default"))) int nbls_sim_kzg_cell_interp(unsigned log2_n, unsigned log2_cell, size_t n_cells, int sum, unsigned n_wg, const uint8_t* cells,
+                                                                    const uint32_t* cell_index, const int8_t* pre, const uint8_t* w32, uint8_t* out, int8_t* st_out) {
+  if (log2_n < 1 || log2_n > 12 || log2_cell > 6 || log2_cell > log2_n || log2_n + 1 - log2_cell > 12 || !n_cells || n_cells > ((size_t)1 << 20) || !cells || !cell_index || !out ||
+      (sum && !w32))
+    return -1;
+  const unsigned lm = log2_n + 1 - log2_cell;
+  const u32 c = 1u << log2_cell, W = FR_CELL_LANES, n = (u32)n_cells;
+  for (size_t k = 0; k < n_cells; k++) if (cell_index[k] >> lm) return -1;
+  std::vector<Fr> roots, iroots, ishifts((size_t)1 << lm);
+  if (log2_cell) sim_ntt_tables(log2_cell, roots, iroots);
+  const Fr g = fr_omega(log2_n + 1);
+  for (u32 k = 0; k < (1u << lm); k++) ishifts[k] = fr_cell_ishift_entry(g, log2_n, lm, k);
+  const u32 wgs = n_wg ? n_wg : fr_cell_workgroups(n, log2_cell, sum != 0), groups = (wgs * W) >> log2_cell, rounds = (n + groups - 1) / groups;
+  auto tree = [&](std::vector<Fr>& part) {
+    for (u32 s = W / 2; s >= c && s > 0; s >>= 1) for (u32 t = 0; t < s; t++) part[t] = fr_add(part[t], part[t + s]);
+  };
+  std::vector<Fr> partial((size_t)wgs * c), v(W), nv(W), acc(W), part(W);
+  std::vector<u32> bad(W);
+  for (u32 b = 0; b < wgs; b++) {
+    for (u32 t = 0; t < W; t++) acc[t] = fr_zero();
+    for (u32 w = 0; w < rounds; w++) {
+      auto cell_of = [&](u32 t, bool* valid) { const uint64_t k = (uint64_t)((b * W + t) >> log2_cell) + (uint64_t)w * groups; *valid = k < n; return *valid ? (u32)k : n - 1; };
+      bool valid;
+      for (u32 t = 0; t < W; t++) { v[t] = fr_load_q(cells + (((uint64_t)cell_of(t, &valid) << log2_cell) + (t & (c - 1))) * 32); bad[t] = fr_ge_r_mask(v[t]); }
+      for (u32 m = 1; m < c; m <<= 1) { std::vector<u32> o(bad); for (u32 t = 0; t < W; t++) bad[t] = o[t] | o[t ^ m]; }
+      for (u32 t = 0; t < W; t++) v[t] = fr_select(bad[t], fr_zero(), v[t]);
+      for (u32 ll = 0; ll < log2_cell; ll++) {
+        for (u32 t = 0; t < W; t++) nv[t] = fr_cell_stage(v[t], v[t ^ (1u << ll)], t & (c - 1), ll, log2_cell, iroots.data());
+        v.swap(nv);
+      }
+      for (u32 t = 0; t < W; t++) {
+        const u32 i = t & (c - 1), kk = cell_of(t, &valid);
+        const int p = pre ? pre[kk] : 0;
+        const u32 outm = bad[t] | ((u32)0 - (u32)(p != 0)) | ((u32)0 - (u32)!valid);
+        const Fr a = fr_cell_coeff(v[t], ishifts[cell_index[kk]], i, log2_cell, outm);
+        if (sum) acc[t] = fr_add(acc[t], fr_mul(a, fr_mul(fr_load_q(w32 + 32ull * kk), fr_r2())));
+        else if (valid) fr_store_q(fr_neg(a), out + (((uint64_t)kk << log2_cell) + i) * 32);
+        if (st_out && valid && i == 0) st_out[kk] = (int8_t)fr_cell_status(p, bad[t]);
+      }
+    }
+    if (!sum) continue;
+    part = acc;
+    tree(part);
+    for (u32 t = 0; t < c; t++) partial[(size_t)b * c + t] = part[t];
+  }
+  if (!sum) return 0;
+  for (u32 t = 0; t < W; t++) {
+    Fr a = fr_zero();
+    for (u32 p = t >> log2_cell; p < wgs; p += W >> log2_cell) a = fr_add(a, partial[(size_t)p * c + (t & (c - 1))]);
+    part[t] = a;
+  }
+  tree(part);
+  for (u32 t = 0; t < c; t++) fr_store_q(fr_neg(part[t]), out + 32ull * t);
+  return 0;
+}
 __attribute__((visibility("default"))) int nbls_sim_program_count() { return (int)P_COUNT; }
 __attribute__((visibility("default"))) void nbls_sim_stats() { for (int i = 0; i < P_COUNT; i++) print_stats(get_program((ProgId)i)); }
 }

@@ -99,6 +99,7 @@ def load_library():
     lib.nbls_kzg_monomial_destroy.restype = None
     lib.nbls_kzg_monomial_log2n.argtypes = [vp, C.POINTER(C.c_uint)]
     lib.nbls_kzg_compute_cells_and_proofs.argtypes = [vp, vp, C.c_uint, sz, vp, vp, vp, vp]
+    lib.nbls_kzg_verify_cells.argtypes = [vp, vp, C.c_uint, sz, vp, sz, vp, vp, vp, vp, vp, vp, C.POINTER(i32), vp]
     lib.nbls_keyset_create.argtypes = [vp, sz, vp, vp, C.POINTER(vp)]
     lib.nbls_keyset_destroy.argtypes = [vp]
     lib.nbls_keyset_destroy.restype = None
@@ -746,6 +747,26 @@ class Engine:
         self._chk(self.lib.nbls_kzg_compute_cells_and_proofs(self.h, setup.h, log2_cell, n, raw, out, pf, st))
         p = pf.raw
         return self._cells_of(out.raw, n, log2_n, log2_cell), [[p[48 * (per * i + k):48 * (per * i + k + 1)] for k in range(per)] for i in range(n)], st.raw[:n]
+
+    def kzg_verify_cells(self, monomial, log2_cell, commitments48, commitment_index, cell_index, cells, proofs48, tau_c_g2_96, seed=None, per_item=True):
+        """verify_cell_kzg_proof_batch against a KzgMonomialSetup: cell k of the call is cell number cell_index[k] of the blob with commitment commitments48[commitment_index[k]]
+        (every commitment once; cells may repeat); cells: byte strings of 32 << log2_cell bytes (log2_cell <= 6), as kzg_compute_cells returns them; tau_c_g2_96: the setup's
+        compressed [tau^c]G2 -> (all_ok, status bytes or None).  statuses: 0 ok, 9 not verified, 3 / 4 the commitment does not decode, 13 / 14 the proof, 21 an element is >= r;
+        seed: 32 bytes, None = from the OS; per_item=False: the combined check alone (fast reject)"""
+        if getattr(monomial, 'h', None) is None:
+            raise NblsError('kzg_verify_cells: the setup is closed')
+        n, size = len(cells), 32 << log2_cell if 0 <= log2_cell <= 6 else -1
+        if not n or not commitments48 or len(commitment_index) != n or len(cell_index) != n or len(proofs48) != n or any(len(x) != size for x in cells) or \
+           any(len(x) != 48 for x in commitments48) or any(len(x) != 48 for x in proofs48) or len(tau_c_g2_96) != 96 or (seed is not None and len(seed) != 32) or \
+           any(not 0 <= int(i) < 1 << 32 for i in commitment_index) or any(not 0 <= int(i) < 1 << 32 for i in cell_index):
+            raise NblsError('kzg_verify_cells: one cell or more of %d bytes each (log2_cell in 0 .. 6), with an index into the 48-byte commitments, a cell index and a 48-byte proof '
+                            'each, 96 bytes of [tau^c]G2 and a seed of 32 bytes or None' % size)
+        ok = C.c_int(0)
+        st = C.create_string_buffer(n) if per_item else None
+        u32s = C.c_uint32 * n
+        self._chk(self.lib.nbls_kzg_verify_cells(self.h, monomial.h, log2_cell, len(commitments48), b''.join(bytes(x) for x in commitments48), n, u32s(*commitment_index), u32s(*cell_index),
+                                                 b''.join(bytes(x) for x in cells), b''.join(bytes(x) for x in proofs48), bytes(tau_c_g2_96), seed, C.byref(ok), st))
+        return bool(ok.value), (st.raw[:n] if per_item else None)
 
     def get_public_keys(self, keys):
         """getPublicKey for a batch of private keys -> list of 48-byte compressed keys; raises like the reference on a zero key"""

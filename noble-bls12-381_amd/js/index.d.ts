@@ -105,6 +105,12 @@ export declare class PointG1 {
   static computeCellsAsync(log2n: number, log2cell: number, blobs: Hex[]): Promise<KzgCells>;
   static computeCellsAndKzgProofs(setup: KzgMonomialSetup, log2cell: number, blobs: Hex[]): KzgCellsAndProofs;
   static computeCellsAndKzgProofsAsync(setup: KzgMonomialSetup, log2cell: number, blobs: Hex[]): Promise<KzgCellsAndProofs>;
+  /** EIP-7594 verify_cell_kzg_proof_batch: cell k is cell number cellIndices[k] of the blob with commitment commitments[commitmentIndices[k]] (every commitment once; cells of
+   *  32 << log2cell bytes, log2cell <= 6) against the setup's [tau^c]G2; status as verifyKzgProofBatch, 21 = an element of the cell is non-canonical */
+  static verifyCellKzgProofBatch(setup: KzgMonomialSetup, log2cell: number, commitments: (PointG1 | Hex)[], commitmentIndices: number[], cellIndices: number[], cells: Hex[],
+    proofs: (PointG1 | Hex)[], tauCG2: PointG2 | Hex, opts?: KzgOptions): KzgResult;
+  static verifyCellKzgProofBatchAsync(setup: KzgMonomialSetup, log2cell: number, commitments: (PointG1 | Hex)[], commitmentIndices: number[], cellIndices: number[], cells: Hex[],
+    proofs: (PointG1 | Hex)[], tauCG2: PointG2 | Hex, opts?: KzgOptions): Promise<KzgResult>;
   isZero(): boolean; equals(rhs: PointG1): boolean; negate(): PointG1; add(rhs: PointG1): PointG1; subtract(rhs: PointG1): PointG1; double(): PointG1;
   multiply(scalar: bigint | number): PointG1; multiplyUnsafe(scalar: bigint | number): PointG1; multiplyPrecomputed(scalar: bigint | number): PointG1;
   assertValidity(): this; toAffine(): [Fp, Fp]; toRawBytes(isCompressed?: boolean): Uint8Array; toHex(isCompressed?: boolean): string;

@@ -319,6 +319,30 @@ async function computeCellsAndKzgProofsAsync(setup, log2cell, blobs) {
   kzgMonomialOpen(setup); const b = kzgCellArgs(setup.log2n, log2cell, blobs);
   return kzgCellsResult(await native.kzgCellsAndProofsAsync(setup.handle, log2cell, b), blobs.length, setup.log2n, log2cell, true);
 }
+// verify_cell_kzg_proof_batch (nbls_kzg_verify_cells): cell k of the call is cell number cellIndices[k] of the blob committed to by commitments[commitmentIndices[k]] -- every
+// commitment once, cells may repeat --, with its proof; tauCG2: the setup's [tau^c]G2 (g2_monomial[c]; 96 compressed bytes, hex, or a PointG2), c = 2^log2cell <= 64 elements per
+// cell.  -> { ok, status } as verifyKzgProofBatch (status per cell: 21 = an element of the cell is >= CURVE.r); opts.seed, opts.perItem likewise
+function kzgVerifyCellsArgs(setup, log2cell, commitments, commitmentIndices, cellIndices, cells, proofs, tauCG2, opts) {
+  kzgMonomialOpen(setup);
+  if (!Number.isInteger(log2cell) || log2cell < 0 || log2cell > 6 || log2cell > setup.log2n) throw new Error('Expected log2cell in 0 .. min(6, log2n)');
+  const n = cells.length;
+  if (!n || !commitments.length) throw new Error('Expected non-empty array');
+  if (commitmentIndices.length !== n || cellIndices.length !== n || proofs.length !== n) throw new Error('Expected as many commitment indices, cell indices and proofs as cells');
+  const index = (v, bound, what) => { if (!Number.isInteger(v) || v < 0 || v >= bound) throw new Error('Invalid ' + what + ': expected an integer in 0 .. ' + (bound - 1)); return v; };
+  const ci = Uint32Array.from(commitmentIndices, (v) => index(v, commitments.length, 'commitment index'));
+  const ki = Uint32Array.from(cellIndices, (v) => index(v, 2 << (setup.log2n - log2cell), 'cell index'));
+  const perItem = !(opts && opts.perItem === false);
+  return [setup.handle, log2cell, kzgPack(commitments, 48, 'commitment', kzgG1), ci, ki, kzgPack(cells, 32 << log2cell, 'cell', ensureBytes), kzgPack(proofs, 48, 'proof', kzgG1),
+    kzgTau(tauCG2), kzgSeed(opts), perItem ? 1 : 0];
+}
+function verifyCellKzgProofBatch(setup, log2cell, commitments, commitmentIndices, cellIndices, cells, proofs, tauCG2, opts) {
+  const a = kzgVerifyCellsArgs(setup, log2cell, commitments, commitmentIndices, cellIndices, cells, proofs, tauCG2, opts);
+  try { return kzgResult(native.kzgVerifyCells(...a), a[9]); } catch (e) { return kzgFail(e); }
+}
+async function verifyCellKzgProofBatchAsync(setup, log2cell, commitments, commitmentIndices, cellIndices, cells, proofs, tauCG2, opts) {
+  const a = kzgVerifyCellsArgs(setup, log2cell, commitments, commitmentIndices, cellIndices, cells, proofs, tauCG2, opts);
+  try { return kzgResult(await native.kzgVerifyCellsAsync(...a), a[9]); } catch (e) { return kzgFail(e); }
+}
 
 // Points are held as affine wire bytes (what the engine consumes) or as the zero point.  The reference's constructor form
 // new PointG1(x: Fp, y: Fp, z?: Fp) (index.ts:291) is accepted too: the projective triple is made affine on the host.
@@ -458,6 +482,12 @@ class PointG1 {
   static computeCellsAsync(log2n, log2cell, blobs) { return computeCellsAsync(log2n, log2cell, blobs); }
   static computeCellsAndKzgProofs(setup, log2cell, blobs) { return computeCellsAndKzgProofs(setup, log2cell, blobs); }
   static computeCellsAndKzgProofsAsync(setup, log2cell, blobs) { return computeCellsAndKzgProofsAsync(setup, log2cell, blobs); }
+  static verifyCellKzgProofBatch(setup, log2cell, commitments, commitmentIndices, cellIndices, cells, proofs, tauCG2, opts) {
+    return verifyCellKzgProofBatch(setup, log2cell, commitments, commitmentIndices, cellIndices, cells, proofs, tauCG2, opts);
+  }
+  static verifyCellKzgProofBatchAsync(setup, log2cell, commitments, commitmentIndices, cellIndices, cells, proofs, tauCG2, opts) {
+    return verifyCellKzgProofBatchAsync(setup, log2cell, commitments, commitmentIndices, cellIndices, cells, proofs, tauCG2, opts);
+  }
   equals(rhs) { return this.zero === rhs.zero && (this.zero || bytesToHex(this.aff) === bytesToHex(rhs.aff)); }
   // reference index.ts:359-381
   toHex(isCompressed = false) {

@@ -2,7 +2,7 @@
  * nbls_napi.c -- thin N-API addon: exposes the C ABI of libnbls.so (include/nbls.h) to Node.  No arithmetic here.
  * libnbls.so is loaded with dlopen at module init so the addon builds with plain gcc (no HIP needed):
  *     gcc -shared -fPIC -I/usr/include/node -I../../include nbls_napi.c -o nbls_napi.node -ldl
- * Calls are synchronous (they block for the duration of the GPU work) except verifyBatchAsync (and signBatchAsync, verifyMultipleAsync, verifyAggregatesAsync, verifyMultipleSharedAsync, verifyAggregatesSharedAsync, frOpAsync, lagrangeAtZeroAsync, combineSharesAsync, polyEvalAsync, kzgVerifyProofsAsync, kzgVerifyBlobsAsync, kzgProveAsync, frNttAsync, kzgComputeCellsAsync, kzgCellsAndProofsAsync), which runs on a libuv worker thread
+ * Calls are synchronous (they block for the duration of the GPU work) except verifyBatchAsync (and signBatchAsync, verifyMultipleAsync, verifyAggregatesAsync, verifyMultipleSharedAsync, verifyAggregatesSharedAsync, frOpAsync, lagrangeAtZeroAsync, combineSharesAsync, polyEvalAsync, kzgVerifyProofsAsync, kzgVerifyBlobsAsync, kzgProveAsync, frNttAsync, kzgComputeCellsAsync, kzgCellsAndProofsAsync, kzgVerifyCellsAsync), which runs on a libuv worker thread
  * (napi_create_async_work) and resolves a Promise: the facade's verifyBatch uses it for wire-format inputs (the calls that can take tens of milliseconds).  Typed arrays are passed by reference (napi_get_typedarray_info), no copies.
  */
 #include <node_api.h>
@@ -24,7 +24,7 @@ SYM(nbls_g1_from_hex_batch) SYM(nbls_g2_from_hex_batch) SYM(nbls_g2_from_signatu
 SYM(nbls_fr_op_batch) SYM(nbls_lagrange_at_zero) SYM(nbls_g2_combine_shares) SYM(nbls_g1_combine_shares) SYM(nbls_g1_poly_eval) SYM(nbls_g2_poly_eval)
 SYM(nbls_kzg_verify_proofs) SYM(nbls_kzg_verify_blobs)
 SYM(nbls_kzg_setup_create) SYM(nbls_kzg_setup_destroy) SYM(nbls_kzg_setup_log2n) SYM(nbls_kzg_commit_blobs) SYM(nbls_kzg_compute_proofs) SYM(nbls_kzg_compute_blob_proofs)
-SYM(nbls_fr_ntt) SYM(nbls_kzg_compute_cells) SYM(nbls_kzg_monomial_create) SYM(nbls_kzg_monomial_destroy) SYM(nbls_kzg_monomial_log2n) SYM(nbls_kzg_compute_cells_and_proofs)
+SYM(nbls_fr_ntt) SYM(nbls_kzg_compute_cells) SYM(nbls_kzg_monomial_create) SYM(nbls_kzg_monomial_destroy) SYM(nbls_kzg_monomial_log2n) SYM(nbls_kzg_compute_cells_and_proofs) SYM(nbls_kzg_verify_cells)
 static nbls_ctx* ctx;
 static nbls_multi* multi;   /* several GPUs behind one handle (initMulti): ctx is then its first context; the batch calls shard over all of them */
 #define MULTI() (multi && p_nbls_multi_device_count(multi) > 1)
@@ -432,12 +432,12 @@ static napi_value SignBatchAsync(napi_env env, napi_callback_info info) {
  *                                                      identifiers of their groups; out = one compressed point per identifier, status per identifier
  * The offsets must name identifiers and shares that are in the arrays (checked here); the library checks the rest. */
 typedef struct {
-  napi_async_work work; napi_deferred deferred; napi_ref refs[9]; int nrefs;
-  int kind /* 0 frOp, 1 lagrangeAtZero, 2 combineShares, 3 polyEval, 4 kzgVerifyProofs, 5 kzgVerifyBlobs, 6 .. 8 kzgProve, 9 frNtt, 10 kzgComputeCells, 11 kzgCellsAndProofs */, op, g2; const uint8_t *a, *b, *shares; const uint32_t *offs, *coffs; size_t n;
+  napi_async_work work; napi_deferred deferred; napi_ref refs[12]; int nrefs;
+  int kind /* 0 frOp, 1 lagrangeAtZero, 2 combineShares, 3 polyEval, 4 kzgVerifyProofs, 5 kzgVerifyBlobs, 6 .. 8 kzgProve, 9 frNtt, 10 kzgComputeCells, 11 kzgCellsAndProofs, 12 kzgVerifyCells */, op, g2; const uint8_t *a, *b, *shares; const uint32_t *offs, *coffs; size_t n;
   uint8_t* out; int8_t* st;
   const uint8_t *proofs, *tau, *seed; int per_item;   /* KZG: a = commitments, b = z (proofs) or the blobs, shares = y, op = log2_n; out = the verdict as one int */
   const nbls_kzg_setup* su;   /* kzgProve: b = the blobs, a = the points z (7) or the given commitments (8; may be NULL), out = two arrays of n entries one behind the other */
-  const nbls_kzg_monomial* mo; size_t proofs_at;   /* PeerDAS: op = log2_n, g2 = the direction (9) or log2_cell (10, 11), b = the rows or the blobs, a = the shifts (9; may be NULL); 11: out = the cells, then at proofs_at the proofs */
+  const nbls_kzg_monomial* mo; size_t proofs_at;   /* PeerDAS: op = log2_n, g2 = the direction (9) or log2_cell (10, 11), b = the rows or the blobs, a = the shifts (9; may be NULL); 11: out = the cells, then at proofs_at the proofs; 12: a = the commitments (proofs_at of them), offs / coffs = the commitment and cell indices, b = the cells, proofs / tau / seed / per_item as the other verifiers */
   nbls_ctx* c; int rc;
 } thr_job;
 static void thr_execute(napi_env env, void* data) { thr_job* j = (thr_job*)data; (void)env;
@@ -451,6 +451,7 @@ static void thr_execute(napi_env env, void* data) { thr_job* j = (thr_job*)data;
         : j->kind == 9 ? p_nbls_fr_ntt(j->c, (unsigned)j->op, j->g2, j->n, j->b, j->a, j->out, j->st)
         : j->kind == 10 ? p_nbls_kzg_compute_cells(j->c, (unsigned)j->op, (unsigned)j->g2, j->n, j->b, j->out, j->st)
         : j->kind == 11 ? p_nbls_kzg_compute_cells_and_proofs(j->c, j->mo, (unsigned)j->g2, j->n, j->b, j->out, j->out + j->proofs_at, j->st)
+        : j->kind == 12 ? p_nbls_kzg_verify_cells(j->c, j->mo, (unsigned)j->g2, j->proofs_at, j->a, j->n, j->offs, j->coffs, j->b, j->proofs, j->tau, j->seed, (int*)j->out, j->per_item ? j->st : NULL)
         : j->kind == 3 ? (j->g2 ? p_nbls_g2_poly_eval : p_nbls_g1_poly_eval)(j->c, j->n, j->coffs, j->shares, j->offs, j->a, j->out, j->st)
         : (j->g2 ? p_nbls_g2_combine_shares : p_nbls_g1_combine_shares)(j->c, j->n, j->offs, j->a, j->shares, j->out, j->st); }
 /* the Error of a failed call of this family: the message of throw_code, and the library's return code as the number `nblsCode` (what the facade reads: never the text) */
@@ -638,7 +639,10 @@ static napi_value KzgProveAsync(napi_env env, napi_callback_info info) { return 
  *   kzgComputeCells(log2n, log2cell, blobs)            out = per blob its 2 N elements in cell order, status per blob
  *   kzgMonomialCreate(log2n, monomial48) -> a handle   (the setup's monomial basis on the device; kzgMonomialDestroy(handle) or the handle's end frees it); a refused basis
  *                                                      throws with the per-entry decoder statuses as the Error's `status`
- *   kzgCellsAndProofs(handle, log2cell, blobs)         out = the cells of every blob, then n * (2 N / c) proofs of 48 bytes; status per blob */
+ *   kzgCellsAndProofs(handle, log2cell, blobs)         out = the cells of every blob, then n * (2 N / c) proofs of 48 bytes; status per blob
+ *   kzgVerifyCells(handle, log2cell, commitments48, commitmentIndex, cellIndex, cells, proofs48, tauCG2, seed32 | null, perItem)
+ *                                                      nbls_kzg_verify_cells: the two index arrays are Uint32Arrays of one entry per cell; out = the verdict (4 bytes, a native
+ *                                                      int), status per cell, as kzgVerifyProofs */
 static napi_value fr_ntt_call(napi_env env, napi_callback_info info, int async) {
   ARGS(4); NEED_CTX(); BYTES(2, rows, lr);
   int32_t log2n, dir;
@@ -708,6 +712,27 @@ static napi_value kzg_cells_proofs_call(napi_env env, napi_callback_info info, i
 static napi_value KzgCellsAndProofs(napi_env env, napi_callback_info info) { return kzg_cells_proofs_call(env, info, 0); }
 static napi_value KzgCellsAndProofsAsync(napi_env env, napi_callback_info info) { return kzg_cells_proofs_call(env, info, 1); }
 
+static napi_value kzg_verify_cells_call(napi_env env, napi_callback_info info, int async) {
+  ARGS(10); NEED_CTX(); BYTES(2, cs, lc); BYTES(3, ci, lci); BYTES(4, ki, lki); BYTES(5, cells, lb); BYTES(6, ps, lp); BYTES(7, tau, lt);
+  monomial_box* box = NULL;
+  if (napi_get_value_external(env, argv[0], (void**)&box) != napi_ok || !box || !box->m) { napi_throw_type_error(env, NULL, "expected a live monomial setup handle"); return NULL; }
+  int32_t log2c, per;
+  if (napi_get_value_int32(env, argv[1], &log2c) != napi_ok || napi_get_value_int32(env, argv[9], &per) != napi_ok) { napi_throw_type_error(env, NULL, "expected numbers for log2cell and perItem"); return NULL; }
+  const uint8_t* seed; if (!kzg_seed(env, argv[8], &seed)) return NULL;
+  const size_t n = lp / 48, nc = lc / 48;
+  if (log2c < 0 || log2c > 6 || !n || !nc || lp != n * 48 || lc != nc * 48 || lci != n * 4 || lki != n * 4 || ((uintptr_t)ci | (uintptr_t)ki) % 4 || lb != (n * 32) << log2c || lt != 96) {
+    napi_throw_range_error(env, NULL, "log2cell in 0 .. 6, commitments of 48 bytes, per cell two 32-bit indices, 32 << log2cell bytes and a proof of 48 bytes, 96 bytes of [tau^c]G2"); return NULL; }
+  thr_job job; memset(&job, 0, sizeof job);
+  job.kind = 12; job.mo = box->m; job.g2 = log2c; job.a = cs; job.proofs_at = nc; job.offs = (const uint32_t*)ci; job.coffs = (const uint32_t*)ki; job.b = cells; job.proofs = ps; job.tau = tau;
+  job.seed = seed; job.per_item = per != 0; job.n = n;
+  napi_value vo = new_u8(env, 4, &job.out), vs = new_u8(env, n, (uint8_t**)&job.st); ALLOCATED(vo); ALLOCATED(vs);
+  memset(job.out, 0, 4); memset(job.st, 0, n);
+  if (!seed) argv[8] = argv[7];   /* (no seed array to keep alive: a second reference to [tau^c]G2 in its place) */
+  return thr_run(env, &job, async, argv, 9, vo, vs);   /* the handle and every array stay referenced while the call runs */
+}
+static napi_value KzgVerifyCells(napi_env env, napi_callback_info info) { return kzg_verify_cells_call(env, info, 0); }
+static napi_value KzgVerifyCellsAsync(napi_env env, napi_callback_info info) { return kzg_verify_cells_call(env, info, 1); }
+
 static napi_value ModuleInit(napi_env env, napi_value exports) {
   const char* path = getenv("NBLS_LIB");
   char buf[4096];
@@ -722,7 +747,7 @@ static napi_value ModuleInit(napi_env env, napi_value exports) {
   LOAD(nbls_g1_from_hex_batch) LOAD(nbls_g2_from_hex_batch) LOAD(nbls_g2_from_signature_batch) LOAD(nbls_g1_clear_cofactor_batch) LOAD(nbls_g2_clear_cofactor_batch)
   LOAD(nbls_fr_op_batch) LOAD(nbls_lagrange_at_zero) LOAD(nbls_g2_combine_shares) LOAD(nbls_g1_combine_shares) LOAD(nbls_g1_poly_eval) LOAD(nbls_g2_poly_eval) LOAD(nbls_kzg_verify_proofs) LOAD(nbls_kzg_verify_blobs)
   LOAD(nbls_kzg_setup_create) LOAD(nbls_kzg_setup_destroy) LOAD(nbls_kzg_setup_log2n) LOAD(nbls_kzg_commit_blobs) LOAD(nbls_kzg_compute_proofs) LOAD(nbls_kzg_compute_blob_proofs)
-  LOAD(nbls_fr_ntt) LOAD(nbls_kzg_compute_cells) LOAD(nbls_kzg_monomial_create) LOAD(nbls_kzg_monomial_destroy) LOAD(nbls_kzg_monomial_log2n) LOAD(nbls_kzg_compute_cells_and_proofs)
+  LOAD(nbls_fr_ntt) LOAD(nbls_kzg_compute_cells) LOAD(nbls_kzg_monomial_create) LOAD(nbls_kzg_monomial_destroy) LOAD(nbls_kzg_monomial_log2n) LOAD(nbls_kzg_compute_cells_and_proofs) LOAD(nbls_kzg_verify_cells)
   {   /* the ABI the addon was written against (include/nbls.h NBLS_ABI_VERSION): an older or newer library is refused at load instead of misread at run time */
     int (*abi)(void) = (int (*)(void))dlsym(lib, "nbls_abi_version");
     if (!abi || abi() != NBLS_ABI_VERSION) { napi_throw_error(env, NULL, "libnbls.so: ABI version differs from the one this addon was built for (include/nbls.h NBLS_ABI_VERSION)"); return exports; }
@@ -747,7 +772,8 @@ static napi_value ModuleInit(napi_env env, napi_value exports) {
     {"frNtt", 0, FrNtt, 0, 0, 0, napi_enumerable, 0}, {"frNttAsync", 0, FrNttAsync, 0, 0, 0, napi_enumerable, 0}, {"kzgComputeCells", 0, KzgComputeCells, 0, 0, 0, napi_enumerable, 0},
     {"kzgComputeCellsAsync", 0, KzgComputeCellsAsync, 0, 0, 0, napi_enumerable, 0}, {"kzgMonomialCreate", 0, KzgMonomialCreate, 0, 0, 0, napi_enumerable, 0},
     {"kzgMonomialDestroy", 0, KzgMonomialDestroy, 0, 0, 0, napi_enumerable, 0}, {"kzgCellsAndProofs", 0, KzgCellsAndProofs, 0, 0, 0, napi_enumerable, 0},
-    {"kzgCellsAndProofsAsync", 0, KzgCellsAndProofsAsync, 0, 0, 0, napi_enumerable, 0}};
+    {"kzgCellsAndProofsAsync", 0, KzgCellsAndProofsAsync, 0, 0, 0, napi_enumerable, 0}, {"kzgVerifyCells", 0, KzgVerifyCells, 0, 0, 0, napi_enumerable, 0},
+    {"kzgVerifyCellsAsync", 0, KzgVerifyCellsAsync, 0, 0, 0, napi_enumerable, 0}};
   napi_define_properties(env, exports, sizeof d / sizeof d[0], d);
   return exports;
 }
