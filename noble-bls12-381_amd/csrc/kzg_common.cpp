@@ -1,0 +1,231 @@
+// kzg_common.cpp -- what the four KZG chains share (nbls_internal.h, the KZG section): -G2 and the blob challenges, the context's device tables, the two basis handles, the
+// prover's closing stage, and the verifiers' frame (KzgFrame) around the combined check and the per-item pass, which kzg_pipeline and verify_cells_pipeline both run.
+#include "nbls_internal.h"
+#include "fr_exec.h"
+#include <algorithm>
+
+// -G2 in affine wire bytes (x.c0 || x.c1 || p - y.c0 || p - y.c1), from the generator's standard coordinates
+const uint8_t* neg_g2_wire() {
+  static uint8_t w[192];
+  static const bool once = [] {
+    static const char* hex[5] = {
+        "024aa2b2f08f0a91260805272dc51051c6e47ad4fa403b02b4510b647ae3d1770bac0326a805bbefd48056c8c121bdb8",
+        "13e02b6052719f607dacd3a088274f65596bd0d09920b61ab5da61bbdc7f5049334cf11213945d57e5ac7d055d042b7e",
+        "0ce5d527727d6e118cc9cdc6da2e351aadfd9baa8cbdd3a76d429a695160d12c923ac9cc3baca289e193548608b82801",
+        "0606c4a02ea734cc32acd2b02bc28b99cb3e287e85a763af267492ab572e99ab3f370d275cec1da1aaa9075ff05f79be",
+        "1a0111ea397fe69a4b1ba7b6434bacd764774b84f38512bf6730d2a0f6b0f6241eabfffeb153ffffb9feffffffffaaab"};
+    uint8_t v[5][48];
+    auto nib = [](char c) { return (uint8_t)(c <= '9' ? c - '0' : c - 'a' + 10); };
+    for (int k = 0; k < 5; k++) for (int i = 0; i < 48; i++) v[k][i] = (uint8_t)(nib(hex[k][2 * i]) << 4 | nib(hex[k][2 * i + 1]));
+    memcpy(w, v[0], 48); memcpy(w + 48, v[1], 48);
+    for (int k = 2; k < 4; k++) {
+      int bw = 0;
+      for (int i = 47; i >= 0; i--) { const int d = (int)v[4][i] - (int)v[k][i] - bw; w[48 * k + i] = (uint8_t)d; bw = d < 0; }
+    }
+    return true;
+  }();
+  (void)once;
+  return w;
+}
+
+// z = BE(SHA-256("FSBLOBVERIFY_V1_" || BE128(N) || blob || commitment)) mod r, canonical bytes
+static void blob_challenge(unsigned log2_n, const uint8_t* blob, const uint8_t* commitment48, uint8_t* z32) {
+  uint8_t head[32] = {'F', 'S', 'B', 'L', 'O', 'B', 'V', 'E', 'R', 'I', 'F', 'Y', '_', 'V', '1', '_'}, digest[32];
+  const uint32_t N = 1u << log2_n;
+  head[30] = (uint8_t)(N >> 8); head[31] = (uint8_t)N;
+  Sha256 h;
+  h.update(head, 32); h.update(blob, (size_t)32 << log2_n); h.update(commitment48, 48); h.final(digest);
+  fr_to_bytes(fr_from_bytes(digest), z32);
+}
+// the challenges of n blobs on up to eight host threads (2 N + 2 dependent SHA-256 blocks per blob: no work for a GPU lane); thread t takes the blobs t, t + threads, ..
+// A thread that cannot be started costs nothing but time: the calling thread does its share
+void blob_challenges(unsigned log2_n, size_t n, const uint8_t* blobs, const uint8_t* c48, uint8_t* z32) {
+  const unsigned hw = std::thread::hardware_concurrency();
+  const size_t nt = std::max<size_t>(1, std::min<size_t>({n, 8, hw ? hw : 1}));
+  auto share = [=](size_t t) { for (size_t i = t; i < n; i += nt) blob_challenge(log2_n, blobs + ((i * 32) << log2_n), c48 + 48 * i, z32 + 32 * i); };
+  std::vector<std::thread> th;
+  std::vector<size_t> mine{0};
+  for (size_t t = 1; t < nt; t++) {
+    try { th.emplace_back(share, t); } catch (...) { mine.push_back(t); }
+  }
+  for (size_t t : mine) share(t);
+  for (std::thread& x : th) x.join();
+}
+
+int kzg_table(nbls_ctx* ctx, KzgTable kind, unsigned log2_n, unsigned log2_cell, hipStream_t s, const uint8_t** table) {
+  const bool cells = kind == KZG_CELL_ISHIFTS;
+  uint8_t*& slot = ctx->kzg_tables[cells ? 26 + 7 * log2_n + log2_cell : 13 * kind + log2_n];
+  if (!slot) {
+    const unsigned lm = cells ? log2_n + 1 - log2_cell : log2_n;   // the table has 2^lm entries
+    const uint8_t* roots = nullptr; uint8_t* t = nullptr; int r;
+    if (kind == KZG_INV_ROOTS && (r = kzg_table(ctx, KZG_ROOTS, log2_n, 0, s, &roots))) return r;
+    HIPCHK(hipMalloc(&t, (size_t)32 << lm));
+    const int e = cells ? nbls_kzg_cell_ishifts_launch(log2_n, lm, t, s) : roots ? nbls_kzg_inv_roots_launch(log2_n, roots, t, s) : nbls_kzg_roots_launch(log2_n, t, s);
+    if (e) { hipFree(t); ctx->last_hip = e; return NBLS_EHIP; }
+    slot = t;
+  }
+  *table = slot;
+  return NBLS_OK;
+}
+
+// ---- the basis handles.  What the two create calls share: 2^log2_n compressed points decoded, subgroup-checked and converted into a device block of the context's device
+// (*pts, the caller frees it); NBLS_EDECODE (and no block) where an entry does not decode or is the zero point; status (may be NULL) as the create calls state it
+static int kzg_basis_decode(nbls_ctx* ctx, unsigned log2_n, const uint8_t* points48, int8_t* status, uint8_t** pts) {
+  const size_t n = (size_t)1 << log2_n, p = 3 * RAW;
+  std::vector<int8_t> st(n);
+  LOCKED(ctx);
+  HostIO io{ctx};
+  void *d = io.alloc(n * 48), *a = io.alloc(n * 96), *dst = io.alloc(n);
+  if (!d || !a || !dst) return NBLS_EHIP;
+  uint8_t* mem = nullptr;
+  if (hipMalloc(&mem, n * 2 * p) != hipSuccess) { ctx->last_hip = (int)hipGetLastError(); return NBLS_EHIP; }
+  int r = NBLS_OK;
+  hipError_t e = hipMemcpyAsync(d, points48, n * 48, hipMemcpyHostToDevice, s);
+  // (an entry that does not decode goes through the conversion as whatever bytes the decoder left: the table is then discarded)
+  if (e == hipSuccess && !(r = dev_decompress(ctx, false, n, d, a, dst, s)) && !(r = run(ctx, P_G1_MSM_PREP, n, {B(0, a, 96), B(3, mem, 2 * p)}, s))) {
+    e = hipMemcpyAsync(st.data(), dst, n, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+  }
+  if (e != hipSuccess) { ctx->last_hip = (int)e; r = NBLS_EHIP; }
+  if (!r) {
+    if (status) memcpy(status, st.data(), n);
+    for (size_t j = 0; j < n; j++) if (st[j]) r = NBLS_EDECODE;   // 1: a zero point, which no real setup contains
+  }
+  if (r) { (void)hipStreamSynchronize(s); hipFree(mem); return r; }
+  *pts = mem;
+  return NBLS_OK;
+}
+// H: the public handle type, which adds nothing to KzgBasis but its name
+template <class H> static int kzg_basis_create(nbls_ctx* ctx, unsigned log2_n, const uint8_t* points48, int8_t* status, H** out) {
+  WHOLE_CALL(ctx);
+  if (out) *out = nullptr;
+  if (!ctx || log2_n < 1 || log2_n > 12 || !points48 || !out) return NBLS_EINVAL;
+  H* h = new (std::nothrow) H;
+  if (!h) return NBLS_EHIP;
+  h->device = ctx->device; h->log2_n = log2_n;
+  const int r = kzg_basis_decode(ctx, log2_n, points48, status, &h->pts);
+  if (r) { delete h; return r; }
+  *out = h;
+  return NBLS_OK;
+}
+template <class H> static void kzg_basis_destroy(H* h) {
+  if (!h) return;
+  int cur = 0;
+  const bool restore = hipGetDevice(&cur) == hipSuccess;
+  if (hipSetDevice(h->device) == hipSuccess) (void)hipFree(h->pts);
+  if (restore) (void)hipSetDevice(cur);
+  delete h;
+}
+static int kzg_basis_log2n(const KzgBasis* h, unsigned* log2_n) {
+  if (!h || !log2_n) return NBLS_EINVAL;
+  *log2_n = h->log2_n;
+  return NBLS_OK;
+}
+EXPORT int nbls_kzg_setup_create(nbls_ctx* ctx, unsigned log2_n, const uint8_t* lagrange48, int8_t* status, nbls_kzg_setup** out) { return kzg_basis_create(ctx, log2_n, lagrange48, status, out); }
+EXPORT void nbls_kzg_setup_destroy(nbls_kzg_setup* su) { kzg_basis_destroy(su); }
+EXPORT int nbls_kzg_setup_log2n(const nbls_kzg_setup* su, unsigned* log2_n) { return kzg_basis_log2n(su, log2_n); }
+EXPORT int nbls_kzg_monomial_create(nbls_ctx* ctx, unsigned log2_n, const uint8_t* monomial48, int8_t* status, nbls_kzg_monomial** out) { return kzg_basis_create(ctx, log2_n, monomial48, status, out); }
+EXPORT void nbls_kzg_monomial_destroy(nbls_kzg_monomial* m) { kzg_basis_destroy(m); }
+EXPORT int nbls_kzg_monomial_log2n(const nbls_kzg_monomial* m, unsigned* log2_n) { return kzg_basis_log2n(m, log2_n); }
+
+int kzg_proof_tail(nbls_ctx* ctx, const MsmbPlan& pl, const uint8_t* basis_pts, const uint8_t* rows, uint8_t* aff96, uint8_t* zero, const uint8_t* st_a, const uint8_t* st_b,
+                   uint8_t* out48, uint8_t* status, hipStream_t s) {
+  const size_t n = pl.n_groups; int r;
+  if ((r = msm_rows_dev(ctx, pl, basis_pts, rows, aff96, zero, s)) || (r = run(ctx, P_G1_COMPRESS, n, {B(0, aff96, 96), B(2, out48, 48)}, s))) return r;
+  LAUNCHCHK(nbls_kzg_prove_tail_launch((unsigned)n, zero, st_a, st_b, out48, status, s));
+  return NBLS_OK;
+}
+
+// ---- the verifiers' frame
+// From the three parts of B (affine points with a status each, 1 = the zero point) to the verdict of the combined check: raw projective, the identity where the status says so,
+// two complete additions, affine again with B's own zero flag (A and its flag are in place), the generator for a zero A or B, two Miller loops against the two tables, product,
+// final exponentiation, the header's first byte = the result is one
+static int kzg_combined_tail(nbls_ctx* ctx, const KzgFrame& f, hipStream_t s) {
+  const size_t p = 3 * RAW; int r;
+  uint8_t *BJ = f.PR + f.a.bj, *BN = f.PR + f.a.bn, *RES = f.PR + f.a.res;
+  if ((r = run(ctx, P_G1_TO_PROJ, 3, {B(0, f.B3, 96), B(3, BJ, p)}, s))) return r;
+  LAUNCHCHK(nbls_agg_points_launch(3, (unsigned)p, nullptr, f.BST, ctx->ident_g1, BJ, BJ, s));
+  if ((r = run(ctx, P_G1_ADD_AB, 1, {B(3, BJ, p), B(4, BJ + p, p), B(5, BJ, p)}, s)) || (r = run(ctx, P_G1_ADD_AB, 1, {B(3, BJ, p), B(4, BJ + 2 * p, p), B(5, BJ, p)}, s)) ||
+      (r = to_affine(ctx, false, 1, BJ, BN, BN + RAW, f.PT2 + 96, kzg_hdr_b_zero(f.BK), s)))
+    return r;
+  LAUNCHCHK(nbls_agg_fix_zero_launch(2, f.A_ZERO, ctx->gen_g1, f.PT2, nullptr, s));
+  uint8_t* res = ctx->F;
+  if ((r = run(ctx, P_ACC_Q, 2, {B(0, f.PT2, 96), B(3, f.TB, LINE_BYTES), B(5, ctx->F, F12)}, s)) || (r = reduce_product(ctx, 2, &res, s)) || (r = finish_single(ctx, Window(), res, 1, RES, s))) return r;
+  LAUNCHCHK(nbls_rlc_is_one_launch(1, RES, kzg_hdr_one(f.BK), s));
+  return NBLS_OK;
+}
+// The per-item tail.  block = the start kzg_item_tail_carve returned; the caller has written the three summands of every X_i to p3 (3 n affine points, summand after summand)
+// and their statuses to st3 (non-zero: the identity) -> X_i by two complete additions, millerLoop(pi_i, table 0) * millerLoop(X_i, table 1) with table_stride = 0, one batched
+// final exponentiation, compared with one on the device, kzg_item_status_kernel's rule -> the n statuses at fs.  The caller has run ensure_scratch(ctx, 2 n)
+static int kzg_item_tail(nbls_ctx* ctx, size_t n, const KzgItemTail& t, uint8_t* block, const uint8_t* proofs96, const uint8_t* tables, const uint8_t* pre, const uint8_t* proof_st, hipStream_t s) {
+  const size_t p = 3 * RAW; int r;
+  uint8_t *P3 = block + t.p3, *ST3 = block + t.st3, *PJ = block + t.proj, *N = block + t.n, *NI = block + t.ni, *X = block + t.x, *E = block + t.e, *V = block + t.v, *XZ = block + t.xz,
+          *FS = block + t.fs;
+  // the summands as raw projective points, the identity where the status says so (a zero commitment, a zero product, an item that is out), then two complete additions
+  if ((r = run(ctx, P_G1_TO_PROJ, 3 * n, {B(0, P3, 96), B(3, PJ, p)}, s))) return r;
+  LAUNCHCHK(nbls_agg_points_launch(3 * n, (unsigned)p, nullptr, ST3, ctx->ident_g1, PJ, PJ, s));
+  if ((r = run(ctx, P_G1_ADD_AB, n, {B(3, PJ, p), B(4, PJ + n * p, p), B(5, PJ, p)}, s)) || (r = run(ctx, P_G1_ADD_AB, n, {B(3, PJ, p), B(4, PJ + 2 * n * p, p), B(5, PJ, p)}, s)) ||
+      (r = to_affine(ctx, false, n, PJ, N, NI, X, XZ, s)))
+    return r;
+  LAUNCHCHK(nbls_agg_fix_zero_launch((unsigned)n, XZ, ctx->gen_g1, X, nullptr, s));
+  if ((r = run(ctx, P_ACC_Q, n, {B(0, proofs96, 96), B(3, tables, 0), B(5, ctx->F, F12)}, s)) || (r = run(ctx, P_ACC_Q, n, {B(0, X, 96), B(3, tables + LINE_BYTES, 0), B(5, ctx->F + n * F12, F12)}, s)) ||
+      (r = run(ctx, P_MUL2S, n, {B(3, ctx->F, F12), B(4, ctx->F + n * F12, F12), B(5, ctx->F, F12)}, s)) || (r = run(ctx, P_NORM_RAW, n, {B(3, ctx->F, F12), B(4, ctx->N, RAW)}, s)) ||
+      (r = final_exp_pipeline(ctx, Window(), n, ctx->F, E, s)))
+    return r;
+  LAUNCHCHK(nbls_rlc_is_one_launch((unsigned)n, E, V, s));
+  LAUNCHCHK(nbls_kzg_item_status_launch((unsigned)n, pre, proof_st, XZ, V, FS, s));
+  return NBLS_OK;
+}
+
+int kzg_seed(const uint8_t* seed32, uint8_t* seed) {
+  if (!seed32) return os_seed(seed);
+  memcpy(seed, seed32, 32);
+  return NBLS_OK;
+}
+KzgFrame::KzgFrame(nbls_ctx* c, Staged& st, hipStream_t stream, size_t items, Slot pairs, Slot out, Slot per_item)
+    : ctx(c), io(st), s(stream), n(items), sb_pairs(pairs), sb_out(out), sb_items(per_item), a(kzg_pairs_carve()) {}
+void KzgFrame::stage(const uint8_t* tau96, const uint8_t* seed) { o_tau = io.bytes(tau96, 96); o_ng2 = io.bytes(neg_g2_wire(), 192); o_seed = io.bytes(seed, 32); }
+int KzgFrame::take() {
+  int r;
+  if ((r = need(ctx, sb_pairs, a.bytes, &PR)) || (r = need(ctx, sb_out, kzg_back_bytes(n), &BK)) || (r = ensure_scratch(ctx, 2))) return r;
+  TB = PR + a.tb; PT2 = PR + a.pt2; B3 = PR + a.b3; BST = PR + a.bst; A_ZERO = kzg_hdr_a_zero(BK); PRE = kzg_hdr_pre(BK);
+  return NBLS_OK;
+}
+int KzgFrame::open(uint8_t* c, uint8_t* W) {
+  uint8_t* G2P = PR + a.g2; int r;
+  HIPCHK(hipMemsetAsync(BK, 0, KZG_HDR_BYTES, s));
+  // the G2 point by PointG2.fromSignature's rules (its status is judged after the read-back: nothing is decided on the host before), then the two line tables
+  if ((r = dev_decompress(ctx, true, 1, c + o_tau, G2P, kzg_hdr_g2_status(BK), s))) return r;
+  HIPCHK(hipMemcpyAsync(G2P + 192, c + o_ng2, 192, hipMemcpyDeviceToDevice, s));
+  if ((r = run(ctx, P_LINES_Q, 2, {B(1, G2P, 192), B(3, TB, LINE_BYTES)}, s))) return r;
+  LAUNCHCHK(nbls_rlc_weights_launch((unsigned)n, c + o_seed, W, s));
+  return NBLS_OK;
+}
+int KzgFrame::decide(int* all_ok, int8_t* status, bool* more) {
+  const uint8_t* got; int r;
+  if ((r = kzg_combined_tail(ctx, *this, s)) || (r = io.fetch(BK, kzg_back_bytes(n), &got))) return r;
+  const KzgVerdict v = kzg_verdict(got, n);
+  if (v == KZG_BAD_G2) return NBLS_EDECODE;
+  *all_ok = v == KZG_ACCEPT;
+  if (v == KZG_ACCEPT && status) memset(status, 0, n);
+  *more = v == KZG_REJECT && status;   // (no statuses asked for: the fast reject, no per-item work)
+  return NBLS_OK;
+}
+int KzgFrame::items_begin(size_t front, uint8_t** FRONT, MsmbPlan* rows_plan, size_t row_pts) {
+  size_t sz = 0; uint8_t* IT; int r;
+  const size_t b_front = carve(&sz, front), b_t = kzg_item_tail_carve(n, &sz, &t);
+  if ((r = need(ctx, sb_items, sz, &IT)) || (r = ensure_scratch(ctx, 2 * n)) || (rows_plan && (r = msm_rows_dev_plan(ctx, row_pts, n, rows_plan)))) return r;
+  *FRONT = IT + b_front; TAIL = IT + b_t; P3 = TAIL + t.p3; ST3 = TAIL + t.st3;
+  // nothing is forked here: the guard is used for its wait alone.  fetch() has disarmed the staged block, and an error return from here on must not leave this chain running on
+  // slots the next call regrows
+  guard.armed = true;
+  return NBLS_OK;
+}
+int KzgFrame::items_close(const uint8_t* proofs96, const uint8_t* proof_st, int* all_ok, int8_t* status) {
+  const uint8_t* got; int r;
+  if ((r = kzg_item_tail(ctx, n, t, TAIL, proofs96, TB, PRE, proof_st, s)) || (r = read_back(ctx, s, TAIL + t.fs, n, &got))) return r;
+  guard.armed = false;
+  memcpy(status, got, n);
+  *all_ok = std::all_of(got, got + n, [](uint8_t st) { return st == 0; });
+  return NBLS_OK;
+}

@@ -25,31 +25,40 @@ __global__ void kzg_roots_kernel(u32 log2_n, Fr* __restrict__ table) {
   if (j < (1u << log2_n)) table[j] = fr_root_entry(fr_omega(log2_n), log2_n, j);
 }
 
+// the 256 values of part[] (one per lane of the workgroup) to part[0]: an LDS tree of modular additions; ends behind a barrier
+__device__ inline void fr_part_tree(Fr* part, u32 t) {
+  for (u32 s = EV / 2; s > 0; s >>= 1) {
+    if (t < s) part[t] = fr_add(part[t], part[t + s]);
+    __syncthreads();
+  }
+}
 // One workgroup per polynomial, lane t on the terms t, t + 256, .. (ceil(N / 256) of them: the loop bounds are the workgroup's), ONE fixed-chain inversion per lane.  N < 256
 // leaves lanes idle under fr_eval_lane's mask.  Dynamic LDS: the running products of the batch inversion, 8 KB per term of a lane (128 KB at N = 4096), [term][limb][lane] so that
 // a wavefront's 64 words fall on 64 banks.  The 256 partial sums meet in an LDS tree (8 KB) of modular additions; at most one lane of the workgroup meets a vanishing denominator
 // (the roots are distinct) and leaves its index in LDS.
+// The walk both kernels open with (keep: fr_eval_lane_t's) -> z in Montgomery form; behind a barrier part[0] = the sum, *sh_hit = the root z is (or all ones), *sh_bad = an element or z >= r
+template <bool keep> __device__ inline Fr kzg_eval_walk(u32 log2_n, const uint8_t* f32, const uint8_t* z32, const Fr* roots, u32* pre, Fr* part, u32* sh_hit, u32* sh_bad) {
+  const u32 N = 1u << log2_n, t = threadIdx.x;
+  const Fr zraw = fr_load_be(z32), z = fr_mul(zraw, fr_r2());
+  if (t == 0) { *sh_hit = 0xffffffffu; *sh_bad = fr_ge_r_mask(zraw); }
+  __syncthreads();
+  const FrEvalPart me = fr_eval_lane_t<keep>(f32, roots, z, N, t, EV, pre);
+  part[t] = me.sum;
+  if (me.hit != 0xffffffffu) *sh_hit = me.hit;
+  if (me.bad) atomicOr(sh_bad, 0xffffffffu);
+  __syncthreads();
+  fr_part_tree(part, t);
+  return z;
+}
 __global__ void __launch_bounds__(EV) kzg_eval_kernel(u32 log2_n, const uint8_t* __restrict__ evals, const uint8_t* __restrict__ z32, const Fr* __restrict__ roots,
                                                       uint8_t* __restrict__ out32, int8_t* __restrict__ status) {
   extern __shared__ u32 pre[];
   __shared__ Fr part[EV];
   __shared__ u32 sh_hit, sh_bad;
-  const u32 N = 1u << log2_n, t = threadIdx.x;
   const u64 p = blockIdx.x;
   const uint8_t* f32 = evals + ((p * 32) << log2_n);
-  const Fr zraw = fr_load_be(z32 + 32 * p), z = fr_mul(zraw, fr_r2());
-  if (t == 0) { sh_hit = 0xffffffffu; sh_bad = fr_ge_r_mask(zraw); }
-  __syncthreads();
-  const FrEvalPart me = fr_eval_lane(f32, roots, z, N, t, EV, pre);
-  part[t] = me.sum;
-  if (me.hit != 0xffffffffu) sh_hit = me.hit;
-  if (me.bad) atomicOr(&sh_bad, 0xffffffffu);
-  __syncthreads();
-  for (u32 s = EV / 2; s > 0; s >>= 1) {
-    if (t < s) part[t] = fr_add(part[t], part[t + s]);
-    __syncthreads();
-  }
-  if (t == 0) status[p] = (int8_t)fr_eval_finish(part[0], sh_hit, sh_bad, z, log2_n, f32, out32 + 32 * p);
+  const Fr z = kzg_eval_walk<false>(log2_n, f32, z32 + 32 * p, roots, pre, part, &sh_hit, &sh_bad);
+  if (threadIdx.x == 0) status[p] = (int8_t)fr_eval_finish(part[0], sh_hit, sh_bad, z, log2_n, f32, out32 + 32 * p);
 }
 
 // The quotient of an opening (nbls_fr_quotient_roots, the proofs of pipelines_kzg_prove.cpp): kzg_eval_kernel's walk with the inverses 1 / (z - w_j) kept in the slots the
@@ -66,18 +75,7 @@ __global__ void __launch_bounds__(EV) kzg_quotient_kernel(u32 log2_n, const uint
   const u64 p = blockIdx.x;
   const uint8_t* f32 = evals + ((p * 32) << log2_n);
   uint8_t* q32 = out_q32 + ((p * 32) << log2_n);
-  const Fr zraw = fr_load_be(z32 + 32 * p), z = fr_mul(zraw, fr_r2());
-  if (t == 0) { sh_hit = 0xffffffffu; sh_bad = fr_ge_r_mask(zraw); }
-  __syncthreads();
-  const FrEvalPart me = fr_eval_lane_t<true>(f32, roots, z, N, t, EV, pre);
-  part[t] = me.sum;
-  if (me.hit != 0xffffffffu) sh_hit = me.hit;
-  if (me.bad) atomicOr(&sh_bad, 0xffffffffu);
-  __syncthreads();
-  for (u32 s = EV / 2; s > 0; s >>= 1) {
-    if (t < s) part[t] = fr_add(part[t], part[t + s]);
-    __syncthreads();
-  }
+  const Fr z = kzg_eval_walk<true>(log2_n, f32, z32 + 32 * p, roots, pre, part, &sh_hit, &sh_bad);
   const u32 hit = sh_hit, bad = sh_bad;
   if (t == 0) {
     sh_y = fr_select(bad, fr_zero(), fr_eval_value(part[0], hit, z, log2_n, f32));
@@ -90,10 +88,7 @@ __global__ void __launch_bounds__(EV) kzg_quotient_kernel(u32 log2_n, const uint
   if (hit == 0xffffffffu) return;   // (uniform)
   part[t] = share;
   __syncthreads();
-  for (u32 s = EV / 2; s > 0; s >>= 1) {
-    if (t < s) part[t] = fr_add(part[t], part[t + s]);
-    __syncthreads();
-  }
+  fr_part_tree(part, t);
   if (t == hit % EV) fr_store_q(fr_select(bad, fr_zero(), fr_quot_within(part[0], z)), q32 + 32ull * hit);
 }
 
@@ -195,6 +190,8 @@ __global__ void kzg_prove_tail_kernel(u32 n, const int8_t* __restrict__ zero, co
   close_compressed(out48 + 48ull * i, 48, v ? v : zero[i] == 1);   // (st_a, st_b hold 0 or NBLS_ST_NON_CANONICAL)
 }
 
+// the status of an item before its scalars are looked at, from the two decoders: the commitment's if >= 2, else 10 + the proof's if >= 2, else `rest`
+__device__ inline int kzg_pre_status(int sc, int sp, int rest) { return sc >= 2 ? sc : sp >= 2 ? 10 + sp : rest; }
 __device__ inline void copy96(uint8_t* dst, const uint8_t* src) {
   const uint4* s = (const uint4*)src; uint4* d = (uint4*)dst;
 #pragma unroll
@@ -215,7 +212,7 @@ __global__ void kzg_items_kernel(u32 n, const int8_t* __restrict__ dst, const ui
   const int sc = dst[i], sp = dst[n + i];
   const Fr zr = fr_load_be(z32 + 32ull * i), yr = fr_load_be(y32 + 32ull * i);
   const bool nc = (fr_ge_r_mask(zr) | fr_ge_r_mask(yr)) != 0 || (yst && yst[i] != 0);
-  const int st = sc >= 2 ? sc : sp >= 2 ? 10 + sp : nc ? NBLS_ST_NON_CANONICAL : 0;
+  const int st = kzg_pre_status(sc, sp, nc ? NBLS_ST_NON_CANONICAL : 0);
   pre[i] = (int8_t)st;
   const u32 live = (u32)0 - (u32)(st == 0), use_c = live & ((u32)0 - (u32)(sc == 0)), use_p = live & ((u32)0 - (u32)(sp == 0));
   const Fr zero = fr_zero(), r = fr_load_be(w32 + 32ull * i), rm = fr_mul(r, fr_r2());
@@ -227,16 +224,13 @@ __global__ void kzg_items_kernel(u32 n, const int8_t* __restrict__ dst, const ui
   if (!use_p) copy96(aff + 96ull * (n + i), gen96);
 }
 // out32 = -(sum_i t[i]) mod r as 32 bytes big-endian: one workgroup, the lanes striding over the items, an LDS tree of modular additions
-__global__ void __launch_bounds__(256) kzg_sum_kernel(u32 n, const Fr* __restrict__ t, uint8_t* __restrict__ out32) {
-  __shared__ Fr part[256];
+__global__ void __launch_bounds__(EV) kzg_sum_kernel(u32 n, const Fr* __restrict__ t, uint8_t* __restrict__ out32) {
+  __shared__ Fr part[EV];
   Fr acc = fr_zero();
-  for (u32 i = threadIdx.x; i < n; i += 256) acc = fr_add(acc, t[i]);
+  for (u32 i = threadIdx.x; i < n; i += EV) acc = fr_add(acc, t[i]);
   part[threadIdx.x] = acc;
   __syncthreads();
-  for (u32 s = 128; s > 0; s >>= 1) {
-    if (threadIdx.x < s) part[threadIdx.x] = fr_add(part[threadIdx.x], part[threadIdx.x + s]);
-    __syncthreads();
-  }
+  fr_part_tree(part, threadIdx.x);
   if (threadIdx.x == 0) fr_store_be(fr_neg(part[0]), out32);
 }
 // the per-item pass: zs[i] = z_i (zero where the item is out or its proof is the zero point), ny[i] = -y_i mod r (zero where the item is out)
@@ -332,7 +326,7 @@ __global__ void kzg_cell_pre_kernel(u32 n, const int8_t* __restrict__ dstc, cons
   const u32 k = blockIdx.x * blockDim.x + threadIdx.x;
   if (k >= n) return;
   const int sc = dstc[ci[k]], sp = dstp[k];
-  pre0[k] = (int8_t)(sc >= 2 ? sc : sp >= 2 ? 10 + sp : 0);
+  pre0[k] = (int8_t)kzg_pre_status(sc, sp, 0);
 }
 // kzg_items_kernel's part for cells, one cell per lane.  dstc / affc: the decoder's statuses and points of the commitments, named by ci[k]; dstp / affp: of the n proofs; pre:
 // the cells' statuses before any pairing (kzg_cell_interp_kernel's st_out); sroots: the table of the M roots, s_k = entry cell_index[k].  A cell with pre != 0 gets zero
@@ -359,17 +353,20 @@ __global__ void kzg_cell_items_kernel(u32 n, const int8_t* __restrict__ dstc, co
 }
 
 // The running products of N = 4096 take more than the 64 KB a launch may ask for by default.  The limit is a per-device function attribute: set once on every device a launch of
-// `kernel` is made on (as nbls_vm_launch does); the common case, already set, takes no lock
-int lds_limit(const void* kernel, std::atomic<bool>* attr_set) {
+// `kernel` is made on (as nbls_vm_launch does); the common case, already set, takes no lock.  The flags of the three kernels that ask for it live here
+enum LdsKernel { LDS_EVAL, LDS_QUOTIENT, LDS_NTT, LDS_KERNELS };
+int lds_limit(LdsKernel which, const void* kernel) {
+  static std::atomic<bool> attr_set[LDS_KERNELS][64];
   static std::mutex attr_mu;
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-  if (!attr_set[dev].load(std::memory_order_acquire)) {
+  std::atomic<bool>& set = attr_set[which][dev];
+  if (!set.load(std::memory_order_acquire)) {
     std::lock_guard<std::mutex> g(attr_mu);
-    if (!attr_set[dev].load(std::memory_order_relaxed)) {
+    if (!set.load(std::memory_order_relaxed)) {
       const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 16 * FR_NL * EV * 4);
       if (e != hipSuccess) return (int)e;
-      attr_set[dev].store(true, std::memory_order_release);
+      set.store(true, std::memory_order_release);
     }
   }
   return 0;
@@ -383,8 +380,7 @@ int nbls_kzg_eval_launch(unsigned log2_n, unsigned n, const void* evals32, const
   if (!n) return 0;
   if (log2_n < 1 || log2_n > 12) return (int)hipErrorInvalidValue;
   const unsigned terms = ((1u << log2_n) + EV - 1) / EV, lds = terms * FR_NL * EV * 4;
-  static std::atomic<bool> attr_set[64];
-  const int e = lds_limit((const void*)kzg_eval_kernel, attr_set);
+  const int e = lds_limit(LDS_EVAL, (const void*)kzg_eval_kernel);
   return e ? e : launch_1d(kzg_eval_kernel, (u64)n * EV, EV, lds, stream, log2_n, evals32, z32, roots, out32, status);
 }
 // the same n polynomials -> out_y32 (n x 32), the quotient rows out_q32 (n x 2^log2_n x 32 bytes, 16-byte aligned) and status (n bytes, not NULL)
@@ -393,8 +389,7 @@ int nbls_kzg_quotient_launch(unsigned log2_n, unsigned n, const void* evals32, c
   if (!n) return 0;
   if (log2_n < 1 || log2_n > 12 || ((uintptr_t)out_q32 & 15)) return (int)hipErrorInvalidValue;
   const unsigned terms = ((1u << log2_n) + EV - 1) / EV, lds = terms * FR_NL * EV * 4;
-  static std::atomic<bool> attr_set[64];
-  const int e = lds_limit((const void*)kzg_quotient_kernel, attr_set);
+  const int e = lds_limit(LDS_QUOTIENT, (const void*)kzg_quotient_kernel);
   return e ? e : launch_1d(kzg_quotient_kernel, (u64)n * EV, EV, lds, stream, log2_n, evals32, z32, roots, out_y32, out_q32, status);
 }
 int nbls_kzg_inv_roots_launch(unsigned log2_n, const void* roots, void* table, hipStream_t stream) {
@@ -406,8 +401,7 @@ int nbls_kzg_ntt_launch(unsigned log2_n, unsigned mode, unsigned n, const void* 
   if (!n) return 0;
   if (log2_n < 1 || log2_n > 12 || mode > FR_NTT_CELLS || (mode == FR_NTT_CELLS && !shift32) || (((uintptr_t)in32 | (uintptr_t)out32 | (uintptr_t)coef32) & 15))
     return (int)hipErrorInvalidValue;
-  static std::atomic<bool> attr_set[64];
-  const int e = lds_limit((const void*)kzg_ntt_kernel, attr_set);
+  const int e = lds_limit(LDS_NTT, (const void*)kzg_ntt_kernel);
   const u64 out_stride = (u64)(mode == FR_NTT_CELLS ? 64 : 32) << log2_n;
   return e ? e : launch_1d(kzg_ntt_kernel, (u64)n * NT, NT, 32u << log2_n, stream, log2_n, mode, in32, shift32, shift_stride, roots, iroots, out32, out_stride, coef32, status);
 }
@@ -432,7 +426,7 @@ int nbls_kzg_items_launch(unsigned n, const void* dst, const void* w32, const vo
                           void* t, void* pre, hipStream_t stream) {
   if (!n) return 0;
   const int e = launch_1d(kzg_items_kernel, n, 64, 0, stream, n, dst, w32, z32, y32, yst, gen96, aff, s1, s2, t, pre);
-  return e ? e : launch_1d(kzg_sum_kernel, 256, 256, 0, stream, n, t, (uint8_t*)s2 + 64ull * n);
+  return e ? e : launch_1d(kzg_sum_kernel, EV, EV, 0, stream, n, t, (uint8_t*)s2 + 64ull * n);
 }
 // the table of the 2^log2_m inverse shifts of (log2_n, log2_cell = log2_n + 1 - log2_m)
 int nbls_kzg_cell_ishifts_launch(unsigned log2_n, unsigned log2_m, void* table, hipStream_t stream) {

@@ -1,7 +1,7 @@
-// nbls_internal.h -- what the translation units of the runtime share (runtime.cpp / tuning.cpp / pipelines_pairing.cpp / pipelines_codec.cpp / pipelines_verify.cpp /
-// pipelines_multi_verify.cpp / pipelines_threshold.cpp / pipelines_poly.cpp / pipelines_msm.cpp / pipelines_kzg.cpp / pipelines_kzg_prove.cpp / pipelines_kzg_cells.cpp / pipelines_kzg_verify_cells.cpp; pool and multi-device handles: nbls_multi.cpp): the context, the map of its scratch slots (enum Slot: the one place that says which chain owns
-// which slot, checked at compile time), the launch helpers, the staged block of the host-buffer pipelines (staging.h, included at the end) and the device-side pipelines the
-// exported entry points are built from.  Internal functions have hidden visibility (csrc/Makefile: -fvisibility=hidden).
+// nbls_internal.h -- what the translation units of the runtime share (runtime.cpp / tuning.cpp / pipelines_pairing.cpp / pipelines_codec.cpp / pipelines_verify.cpp / pipelines_multi_verify.cpp / pipelines_threshold.cpp /
+// pipelines_poly.cpp / pipelines_msm.cpp / kzg_common.cpp / pipelines_kzg.cpp / pipelines_kzg_prove.cpp / pipelines_kzg_cells.cpp / pipelines_kzg_verify_cells.cpp; pool and multi-device handles: nbls_multi.cpp): the context, the
+// map of its scratch slots (enum Slot: the one place that says which chain owns which slot, checked at compile time), the launch helpers, the staged block of the host-buffer pipelines (staging.h, included at the end) and the
+// device-side pipelines the exported entry points are built from.  Internal functions have hidden visibility (csrc/Makefile: -fvisibility=hidden).
 #pragma once
 #include <hip/hip_runtime.h>
 #include "config.h"
@@ -17,6 +17,7 @@
 #include "sha256.h"
 #include "curve.h"   // G1_FIXED_WIN and the table geometry of pt_mul_fixed_g1
 #include "bufs.h"    // BufArg / B(), BufList, ChainLink, bind_bufs
+#include "kzg_frame.h"   // the block formats of the KZG verifiers
 #include <thread>
 
 #include "launchers.h"   // every nbls_*_launch of the kernel files, declared once for both sides
@@ -234,9 +235,9 @@ struct nbls_ctx {
   size_t ls_max = ::ls_max(), ls2_max = ::ls2_max();
   size_t chain_max = (size_t)env_long("NBLS_CHAIN_MAX", 8192);                  // nbls_set_tuning(NBLS_TUNE_CHAIN_MAX); see run_chain
   u32* qp_table = nullptr;      // multiples of p for the weak reduction (vm_exec.h weak_reduce), device copy
-  uint8_t* kzg_roots[13] = {nullptr};   // kzg_kernels.hip: the 2^k roots of unity in bit-reversed order, Montgomery form (32 bytes each), built on first use of log2_n = k, freed with the context
-  uint8_t* kzg_inv_roots[13] = {nullptr};   // the same for 1 / omega: what nbls_fr_ntt's stages towards the coefficients divide by
-  uint8_t* kzg_cell_ishifts[13][7] = {{nullptr}};   // [log2_n][log2_cell]: the 2 N / c inverse shifts 1 / h_k of the cells that nbls_kzg_verify_cells interpolates, built on first use
+  // kzg_table (kzg_common.cpp): the device tables of kzg_kernels.hip, Montgomery form, 32 bytes an entry, built on first use and freed with the context.  [k]: the 2^k roots of unity in bit-reversed order;
+  // [13 + k]: the same for 1 / omega, what nbls_fr_ntt's stages towards the coefficients divide by; [26 + 7 log2_n + log2_cell]: the 2 N / c inverse shifts 1 / h_k of the cells that nbls_kzg_verify_cells interpolates
+  uint8_t* kzg_tables[26 + 13 * 7] = {nullptr};
   uint8_t* unit_lines = nullptr;   // a line table whose 68 lines are all 1 (c0 = 1, c1 = c2 = 0): the neutral partner of an odd last pair
   uint8_t* partial = nullptr;   // 576 bytes: the Fp12 partial of the *_partial entry points (multi-GPU reductions)
   uint8_t* L = nullptr; size_t cap_L = 0;   // line tables of the Miller loop (LINE_BYTES each), at most LINES_CHUNK of them
@@ -417,6 +418,7 @@ unsigned scalars_bit_length(size_t n, const uint8_t* k32);
 // msm_rows_dev: n_rows sums of n_pts points each; conv_pts = the output of P_G1_MSM_PREP (2 x 3 raw elements per point), d_scalars = n_rows * n_pts scalars of 32 bytes in
 // device memory, read as 256-bit values (the split path: they are never on the host for scalars_bit_length) -> affine sums (96 bytes each) and zero flags.  No group takes the
 // dev_msm route, whatever NBLS_TUNE_MSMB_BIG says: there are no affine points to give it
+static const size_t MSMB_MAX_ITEMS = (size_t)1 << 22, MSMB_MAX_GROUPS = (size_t)1 << 20;   // one pass of the batched MSM: scalars, rows (groups)
 struct MsmbPart { size_t g0, g1; bool big; int key_bits; };   // groups [g0, g1): one slab (and the bits of its keys), or one big group
 struct MsmbPlan {
   bool g2 = false, split = false; unsigned nbits = 0, dims = 1, kbits = 0, c = 0;
@@ -427,26 +429,45 @@ struct MsmbPlan {
 };
 int msm_rows_dev_plan(nbls_ctx* ctx, size_t n_pts, size_t n_rows, MsmbPlan* pl);
 int msm_rows_dev(nbls_ctx* ctx, const MsmbPlan& pl, const uint8_t* conv_pts, const uint8_t* d_scalars, uint8_t* d_out96, uint8_t* d_zero, hipStream_t s);
-// pipelines_kzg.cpp: the table of roots of a context; the challenges of n blobs on host threads
-int kzg_roots(nbls_ctx* ctx, unsigned log2_n, hipStream_t s, const uint8_t** table);
-int kzg_inv_roots(nbls_ctx* ctx, unsigned log2_n, hipStream_t s, const uint8_t** table);
-void blob_challenges(unsigned log2_n, size_t n, const uint8_t* blobs, const uint8_t* c48, uint8_t* z32);
-// pipelines_kzg.cpp, what kzg_pipeline and verify_cells_pipeline (pipelines_kzg_verify_cells.cpp) share: -G2 in affine wire bytes; the combined check from the three parts of
-// B to its verdict; the per-item pass from the three summands of every X_i to the statuses (the buffers as offsets into one carved block)
+// ---- KZG (kzg_common.cpp): what pipelines_kzg.cpp, pipelines_kzg_prove.cpp, pipelines_kzg_cells.cpp and pipelines_kzg_verify_cells.cpp share
+static const size_t KZG_MAX_ELEMS = (size_t)1 << 24;   // field elements per call of the Fr entry points and of the calls that take whole blobs
+// -G2 in affine wire bytes; the challenges of n blobs on host threads
 const uint8_t* neg_g2_wire();
-struct KzgCombined { uint8_t *B3, *BST, *BJ, *BN, *PT2, *TB, *RES, *BK; };
-int kzg_combined_tail(nbls_ctx* ctx, const KzgCombined& k, hipStream_t s);
-struct KzgItemTail { size_t p3, st3, proj, n, ni, x, e, v, xz, fs; };
-size_t kzg_item_tail_carve(size_t n, size_t* off, KzgItemTail* t);
-int kzg_item_tail(nbls_ctx* ctx, size_t n, const KzgItemTail& t, uint8_t* block, const uint8_t* proofs96, const uint8_t* tables, const uint8_t* pre, const uint8_t* proof_st, hipStream_t s);
-// a trusted setup's Lagrange basis in the form the batched MSM reads (nbls_kzg_setup_create): 2^log2_n points, each with its endomorphism image, raw projective
-struct nbls_kzg_setup { int device = 0; unsigned log2_n = 0; uint8_t* pts = nullptr; };
-// the monomial basis [tau^i]G1 in the same form (nbls_kzg_monomial_create): a handle type of its own, so that neither basis is taken for the other
-struct nbls_kzg_monomial { int device = 0; unsigned log2_n = 0; uint8_t* pts = nullptr; };
-// pipelines_kzg_prove.cpp, what the two create calls share: 2^log2_n compressed points decoded, subgroup-checked and converted into a device block of the context's device
-// (*pts, the caller frees it); NBLS_EDECODE (and no block) where an entry does not decode or is the zero point; status (may be NULL) as the create calls state it
-int kzg_basis_create(nbls_ctx* ctx, unsigned log2_n, const uint8_t* points48, int8_t* status, uint8_t** pts);
-void kzg_basis_free(int device, uint8_t* pts);
+void blob_challenges(unsigned log2_n, size_t n, const uint8_t* blobs, const uint8_t* c48, uint8_t* z32);
+// a context's device table, made on first use: the roots of 2^log2_n, the inverse roots (a permutation of the roots, made behind them on the same stream), or the inverse shifts
+// of (log2_n, log2_cell); log2_cell is read for the last alone
+enum KzgTable { KZG_ROOTS = 0, KZG_INV_ROOTS = 1, KZG_CELL_ISHIFTS = 2 };
+int kzg_table(nbls_ctx* ctx, KzgTable kind, unsigned log2_n, unsigned log2_cell, hipStream_t s, const uint8_t** table);
+// a basis of 2^log2_n points in the form the batched MSM reads (each point with its endomorphism image, raw projective).  The two public handles are types of their own, so
+// that neither basis is taken for the other: nbls_kzg_setup holds a trusted setup's Lagrange basis, nbls_kzg_monomial the monomial basis [tau^i]G1
+struct KzgBasis { int device = 0; unsigned log2_n = 0; uint8_t* pts = nullptr; };
+struct nbls_kzg_setup : KzgBasis {};
+struct nbls_kzg_monomial : KzgBasis {};
+// the prover's closing stage: pl.n_groups rows of scalars against the basis -> affine sums (aff96, zero) -> compressed to out48 -> closed by kzg_prove_tail_kernel with the
+// statuses st_a, st_b (either may be NULL)
+int kzg_proof_tail(nbls_ctx* ctx, const MsmbPlan& pl, const uint8_t* basis_pts, const uint8_t* rows, uint8_t* aff96, uint8_t* zero, const uint8_t* st_a, const uint8_t* st_b,
+                   uint8_t* out48, uint8_t* status, hipStream_t s);
+// The frame of a verifier's call: the seed, the three staged parts [tau^c]G2 | -G2 | seed, the pairs block and the read-back block (kzg_frame.h has their formats), the opening
+// launches, the combined check with its verdict and the per-item pass around the summands.  The caller keeps its staged inputs, its points and scalars blocks, its item
+// kernels, the four sums that fill PT2 / A_ZERO, B3 and BST, and the three summands of every X_i (P3, ST3).  A call: kzg_seed (in front of DEV_ENTER) -> stage (among the caller's
+// io.bytes) -> take (among its need() calls, in front of io.send) -> open (first launches; W: n weights) -> the caller's items and sums -> decide (*more: the statuses need the
+// per-item pass) -> items_begin -> the caller's summands -> items_close
+int kzg_seed(const uint8_t* seed32, uint8_t* seed);   // the caller's seed, or one from the OS
+struct Staged;
+struct KzgFrame {
+  nbls_ctx* ctx; Staged& io; hipStream_t s; size_t n; Slot sb_pairs, sb_out, sb_items;
+  size_t o_tau = 0, o_ng2 = 0, o_seed = 0; KzgPairs a; KzgItemTail t;
+  uint8_t *PR = nullptr, *BK = nullptr, *TB = nullptr, *PT2 = nullptr, *A_ZERO = nullptr, *B3 = nullptr, *BST = nullptr, *PRE = nullptr, *TAIL = nullptr, *P3 = nullptr, *ST3 = nullptr;
+  ForkGuard guard{false};   // armed by items_begin
+  KzgFrame(nbls_ctx* c, Staged& st, hipStream_t stream, size_t items, Slot pairs, Slot out, Slot per_item);
+  void stage(const uint8_t* tau96, const uint8_t* seed);
+  int take();
+  int open(uint8_t* staged, uint8_t* W);
+  int decide(int* all_ok, int8_t* status, bool* more);   // (*more is written on success alone)
+  // front: the caller's own bytes in front of the tail's block (*FRONT); rows_plan (may be NULL): the plan of a batched MSM of n rows of row_pts points, taken behind the block
+  int items_begin(size_t front, uint8_t** FRONT, MsmbPlan* rows_plan = nullptr, size_t row_pts = 0);
+  int items_close(const uint8_t* proofs96, const uint8_t* proof_st, int* all_ok, int8_t* status);
+};
 int msm_host(nbls_ctx* ctx, bool g2, size_t n, const uint8_t* pts, const uint8_t* scalars32, uint8_t* out, int8_t* status);
 int dst_on_device(nbls_ctx* ctx, const uint8_t* dst, size_t* dst_len, hipStream_t s, uint8_t** dd);
 std::vector<size_t> verify_plan(nbls_ctx* ctx, size_t n);

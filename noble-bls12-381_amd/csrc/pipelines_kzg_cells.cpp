@@ -7,7 +7,8 @@
 // One chain on the context's stream:
 //   H2D copy -> kzg_ntt_kernel in its cells mode: the canonical check, the blob's bytes, the coefficients (kept in device memory for the proofs), the coset values
 //            -> proofs, chunk after chunk of whole blobs (the batched MSM takes 2^22 scalars and 2^20 rows a pass: 8 mainnet blobs): kzg_cell_rows_kernel writes the 2 N / c
-//               quotient rows of every blob as big-endian scalars -> msm_rows_dev against the converted basis -> P_G1_COMPRESS -> kzg_prove_tail_kernel
+//               quotient rows of every blob as big-endian scalars -> kzg_proof_tail (kzg_common.cpp): msm_rows_dev against the converted basis -> P_G1_COMPRESS ->
+//               kzg_prove_tail_kernel.  The handle nbls_kzg_monomial and the tables of roots are kzg_common.cpp's as well
 //            -> D2H copy: cells | proofs | statuses
 // Scratch slots: SB_STAGED and SB_KZGC_* (nbls_internal.h, M_KZGC_OWN); the MSM on SB_MSMB_*.
 #include "nbls_internal.h"
@@ -16,48 +17,20 @@
 #include "fr_exec.h"
 #include <algorithm>
 
-static const size_t KZGC_MAX_ELEMS = (size_t)1 << 24;     // elements per call, as nbls_fr_eval_roots
-static const size_t KZGC_MAX_SCALARS = (size_t)1 << 22, KZGC_MAX_ROWS = (size_t)1 << 20;   // the batched MSM's bounds per pass
-
-static size_t carve(size_t* off, size_t bytes) { const size_t o = *off; *off = o + ((bytes + 63) & ~(size_t)63); return o; }
-
 EXPORT int nbls_fr_ntt(nbls_ctx* ctx, unsigned log2_n, int dir, size_t n, const uint8_t* in32, const uint8_t* shift32, uint8_t* out32, int8_t* status) {
   WHOLE_CALL(ctx);
-  if (!ctx || log2_n < 1 || log2_n > 12 || (dir != NBLS_NTT_TO_COEFFS && dir != NBLS_NTT_TO_EVALS) || (n && (!in32 || !out32)) || n > (KZGC_MAX_ELEMS >> log2_n)) return NBLS_EINVAL;
+  if (!ctx || log2_n < 1 || log2_n > 12 || (dir != NBLS_NTT_TO_COEFFS && dir != NBLS_NTT_TO_EVALS) || (n && (!in32 || !out32)) || n > (KZG_MAX_ELEMS >> log2_n)) return NBLS_EINVAL;
   if (!n) return NBLS_OK;
   DEV_ENTER(ctx, nullptr);
   Staged io(ctx, s);
   const size_t qb = (n * 32) << log2_n, o_in = io.bytes(in32, qb), o_sh = io.bytes(shift32, shift32 ? n * 32 : 0), back = qb + n;
   uint8_t *c, *O; const uint8_t *roots, *iroots; int r;
-  if ((r = need(ctx, SB_STAGED, io.in_bytes, &c)) || (r = need(ctx, SB_KZGC_OUT, back, &O)) || (r = kzg_roots(ctx, log2_n, s, &roots)) || (r = kzg_inv_roots(ctx, log2_n, s, &iroots)) ||
+  if ((r = need(ctx, SB_STAGED, io.in_bytes, &c)) || (r = need(ctx, SB_KZGC_OUT, back, &O)) || (r = kzg_table(ctx, KZG_ROOTS, log2_n, 0, s, &roots)) || (r = kzg_table(ctx, KZG_INV_ROOTS, log2_n, 0, s, &iroots)) ||
       (r = io.send(c, back)))
     return r;
   LAUNCHCHK(nbls_kzg_ntt_launch(log2_n, dir == NBLS_NTT_TO_COEFFS ? FR_NTT_TO_COEFFS : FR_NTT_TO_EVALS, (unsigned)n, c + o_in, shift32 ? c + o_sh : nullptr, 32, roots, iroots, O, nullptr,
                                 O + qb, s));
   return io.fetch_to(O, out32, qb, status, n);
-}
-
-EXPORT int nbls_kzg_monomial_create(nbls_ctx* ctx, unsigned log2_n, const uint8_t* monomial48, int8_t* status, nbls_kzg_monomial** out) {
-  WHOLE_CALL(ctx);
-  if (out) *out = nullptr;
-  if (!ctx || log2_n < 1 || log2_n > 12 || !monomial48 || !out) return NBLS_EINVAL;
-  nbls_kzg_monomial* m = new (std::nothrow) nbls_kzg_monomial;
-  if (!m) return NBLS_EHIP;
-  m->device = ctx->device; m->log2_n = log2_n;
-  const int r = kzg_basis_create(ctx, log2_n, monomial48, status, &m->pts);
-  if (r) { delete m; return r; }
-  *out = m;
-  return NBLS_OK;
-}
-EXPORT void nbls_kzg_monomial_destroy(nbls_kzg_monomial* m) {
-  if (!m) return;
-  kzg_basis_free(m->device, m->pts);
-  delete m;
-}
-EXPORT int nbls_kzg_monomial_log2n(const nbls_kzg_monomial* m, unsigned* log2_n) {
-  if (!m || !log2_n) return NBLS_EINVAL;
-  *log2_n = m->log2_n;
-  return NBLS_OK;
 }
 
 // mono == NULL: nbls_kzg_compute_cells (out_proofs unused)
@@ -73,7 +46,7 @@ static int cells_pipeline(nbls_ctx* ctx, const CellsIn& in, int8_t* status) {
   Staged io(ctx, s);
   const size_t o_blob = io.bytes(in.blobs, qb), o_g = io.bytes(g32, 32);
   // blobs per pass: as many whole blobs as the batched MSM takes, or fewer where the tuning key says so
-  size_t per = proofs ? std::min({n, (KZGC_MAX_SCALARS >> L) / M, KZGC_MAX_ROWS / M}) : n;
+  size_t per = proofs ? std::min({n, (MSMB_MAX_ITEMS >> L) / M, MSMB_MAX_GROUPS / M}) : n;
   if (proofs && ctx->cells_chunk && ctx->cells_chunk < per) per = ctx->cells_chunk;
   const size_t tail = n % per;
   // what is read back: the cells | the compressed proofs | the blobs' statuses; behind it one pass's affine sums, zero flags and closing statuses
@@ -85,17 +58,16 @@ static int cells_pipeline(nbls_ctx* ctx, const CellsIn& in, int8_t* status) {
   uint8_t *c, *OUT, *COEF = nullptr, *ROWS = nullptr; const uint8_t *roots, *iroots, *sroots = nullptr, *got; int r;
   if ((r = need(ctx, SB_STAGED, io.in_bytes, &c)) || (r = need(ctx, SB_KZGC_OUT, sz_out, &OUT)) || (proofs && (r = need(ctx, SB_KZGC_COEFS, qb, &COEF))) ||
       (proofs && (r = need(ctx, SB_KZGC_ROWS, sz_rows, &ROWS))) || (proofs && (r = msm_rows_dev_plan(ctx, N, per * M, &pl_full))) ||
-      (proofs && tail && (r = msm_rows_dev_plan(ctx, N, tail * M, &pl_tail))) || (r = kzg_roots(ctx, L, s, &roots)) || (r = kzg_inv_roots(ctx, L, s, &iroots)) ||
-      (proofs && (r = kzg_roots(ctx, L + 1 - lc, s, &sroots))) || (r = io.send(c, back)))
+      (proofs && tail && (r = msm_rows_dev_plan(ctx, N, tail * M, &pl_tail))) || (r = kzg_table(ctx, KZG_ROOTS, L, 0, s, &roots)) || (r = kzg_table(ctx, KZG_INV_ROOTS, L, 0, s, &iroots)) ||
+      (proofs && (r = kzg_table(ctx, KZG_ROOTS, L + 1 - lc, 0, s, &sroots))) || (r = io.send(c, back)))
     return r;
   uint8_t *BK = OUT + a_bk, *AFF = OUT + a_aff, *ZF = OUT + a_zf, *CST = OUT + a_cst, *Q = ROWS + a_q, *RST = ROWS + a_rst;
   LAUNCHCHK(nbls_kzg_ntt_launch(L, FR_NTT_CELLS, (unsigned)n, c + o_blob, c + o_g, 0, roots, iroots, BK, COEF, BK + b_st, s));
   for (size_t b0 = 0; proofs && b0 < n; b0 += per) {
-    const size_t nb = std::min(per, n - b0), rows = nb * M;
+    const size_t nb = std::min(per, n - b0);
     uint8_t* P = BK + b_pf + b0 * M * 48;
     LAUNCHCHK(nbls_kzg_cell_rows_launch(L, lc, (unsigned)nb, COEF + b0 * N * 32, sroots, BK + b_st + b0, Q, RST, s));
-    if ((r = msm_rows_dev(ctx, nb == per ? pl_full : pl_tail, in.mono->pts, Q, AFF, ZF, s)) || (r = run(ctx, P_G1_COMPRESS, rows, {B(0, AFF, 96), B(2, P, 48)}, s))) return r;
-    LAUNCHCHK(nbls_kzg_prove_tail_launch((unsigned)rows, ZF, RST, nullptr, P, CST, s));
+    if ((r = kzg_proof_tail(ctx, nb == per ? pl_full : pl_tail, in.mono->pts, Q, AFF, ZF, RST, nullptr, P, CST, s))) return r;
   }
   if ((r = io.fetch(BK, back, &got))) return r;
   memcpy(in.out_cells, got, 2 * qb);
@@ -106,7 +78,7 @@ static int cells_pipeline(nbls_ctx* ctx, const CellsIn& in, int8_t* status) {
 
 EXPORT int nbls_kzg_compute_cells(nbls_ctx* ctx, unsigned log2_n, unsigned log2_cell, size_t n, const uint8_t* blobs, uint8_t* out_cells, int8_t* status) {
   WHOLE_CALL(ctx);
-  if (!ctx || log2_n < 1 || log2_n > 12 || log2_cell > log2_n || (n && (!blobs || !out_cells)) || n > (KZGC_MAX_ELEMS >> log2_n)) return NBLS_EINVAL;
+  if (!ctx || log2_n < 1 || log2_n > 12 || log2_cell > log2_n || (n && (!blobs || !out_cells)) || n > (KZG_MAX_ELEMS >> log2_n)) return NBLS_EINVAL;
   if (!n) return NBLS_OK;
   return cells_pipeline(ctx, {log2_n, log2_cell, n, blobs, nullptr, out_cells, nullptr}, status);
 }
@@ -117,6 +89,6 @@ EXPORT int nbls_kzg_compute_cells_and_proofs(nbls_ctx* ctx, const nbls_kzg_monom
   if (!ctx || !monomial || !blobs || !out_cells || !out_proofs48 || !n || monomial->device != ctx->device || log2_cell > monomial->log2_n) return NBLS_EINVAL;
   const unsigned L = monomial->log2_n;
   // one blob alone must fit a pass of the batched MSM: (2 N / c) rows of N scalars
-  if (((size_t)2 << (2 * L - log2_cell)) > KZGC_MAX_SCALARS || n > (KZGC_MAX_ELEMS >> L)) return NBLS_EINVAL;
+  if (((size_t)2 << (2 * L - log2_cell)) > MSMB_MAX_ITEMS || n > (KZG_MAX_ELEMS >> L)) return NBLS_EINVAL;
   return cells_pipeline(ctx, {L, log2_cell, n, blobs, monomial, out_cells, out_proofs48}, status);
 }

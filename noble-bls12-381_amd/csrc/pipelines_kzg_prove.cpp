@@ -1,88 +1,29 @@
 // pipelines_kzg_prove.cpp -- the prover's side of KZG on BLS12-381 (EIP-4844: blob_to_kzg_commitment, compute_kzg_proof, compute_blob_kzg_proof), the quotient of an opening in
-// evaluation form (nbls_fr_quotient_roots) and the device-resident setup they run against (nbls_kzg_setup: the Lagrange basis decoded, checked and split ONCE).  With the
-// basis points L_j = [L_j(tau)]G1 in bit-reversed order,
+// evaluation form (nbls_fr_quotient_roots), against the device-resident setup (nbls_kzg_setup: the Lagrange basis decoded, checked and split ONCE by kzg_common.cpp, which
+// has the handle).  With the basis points L_j = [L_j(tau)]G1 in bit-reversed order,
 //   C_i = sum_j [f_ij] L_j,      pi_i = sum_j [q_ij] L_j,   q_ij = (f_ij - y_i) / (w_j - z_i)   (and compute_quotient_eval_within_domain's sum where z_i is a root).
 // One chain on the context's stream:
 //   H2D copy -> commitments: kzg_canon_kernel (a non-canonical blob is flagged and zeroed in place), the blob elements ARE the MSM's scalars
 //            -> proofs: the challenges (blob proofs: hashed on host threads behind the copy, a second small copy) -> kzg_quotient_kernel: y_i, the canonical check, and the
 //               quotient rows as 32-byte big-endian scalars
-//            -> msm_rows_dev (pipelines_msm.cpp): the scalars split along the endomorphism, the slabs of the batched MSM against the setup's converted points, to-affine
-//            -> P_G1_COMPRESS -> kzg_prove_tail_kernel: statuses, 0xc0 00.. for a zero sum, all-zero bytes for a refused item -> D2H copy
+//            -> kzg_proof_tail (kzg_common.cpp; the commit leg and the proof leg close with it): msm_rows_dev (pipelines_msm.cpp), the scalars split along the
+//               endomorphism, the slabs of the batched MSM against the setup's converted points, to-affine -> P_G1_COMPRESS -> kzg_prove_tail_kernel: statuses, 0xc0 00.. for a zero sum, all-zero bytes for a refused item -> D2H copy
 // nbls_kzg_compute_blob_proofs without commitments runs the first chain on the staged blobs, reads the 48 n bytes back (the one synchronisation the challenge needs), hashes,
 // and goes on with the second.  Scratch slots: SB_STAGED and SB_KZGP_* (nbls_internal.h, M_KZGP_OWN); the MSM on SB_MSMB_*.
 #include "nbls_internal.h"
 #include "fr_exec.h"
 #include <algorithm>
 
-static const size_t KZGP_MAX_ELEMS = (size_t)1 << 24;     // nbls_fr_quotient_roots: the bound of nbls_fr_eval_roots
-static const size_t KZGP_MAX_SCALARS = (size_t)1 << 22;   // the batched MSM's bound on scalars per call
-
-static size_t carve(size_t* off, size_t bytes) { const size_t o = *off; *off = o + ((bytes + 63) & ~(size_t)63); return o; }
-
-int kzg_basis_create(nbls_ctx* ctx, unsigned log2_n, const uint8_t* points48, int8_t* status, uint8_t** pts) {
-  const size_t n = (size_t)1 << log2_n, p = 3 * RAW;
-  std::vector<int8_t> st(n);
-  LOCKED(ctx);
-  HostIO io{ctx};
-  void *d = io.alloc(n * 48), *a = io.alloc(n * 96), *dst = io.alloc(n);
-  if (!d || !a || !dst) return NBLS_EHIP;
-  uint8_t* mem = nullptr;
-  if (hipMalloc(&mem, n * 2 * p) != hipSuccess) { ctx->last_hip = (int)hipGetLastError(); return NBLS_EHIP; }
-  int r = NBLS_OK;
-  hipError_t e = hipMemcpyAsync(d, points48, n * 48, hipMemcpyHostToDevice, s);
-  // (an entry that does not decode goes through the conversion as whatever bytes the decoder left: the table is then discarded)
-  if (e == hipSuccess && !(r = dev_decompress(ctx, false, n, d, a, dst, s)) && !(r = run(ctx, P_G1_MSM_PREP, n, {B(0, a, 96), B(3, mem, 2 * p)}, s))) {
-    e = hipMemcpyAsync(st.data(), dst, n, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-  }
-  if (e != hipSuccess) { ctx->last_hip = (int)e; r = NBLS_EHIP; }
-  if (!r) {
-    if (status) memcpy(status, st.data(), n);
-    for (size_t j = 0; j < n; j++) if (st[j]) r = NBLS_EDECODE;   // 1: a zero point, which no real setup contains
-  }
-  if (r) { (void)hipStreamSynchronize(s); hipFree(mem); return r; }
-  *pts = mem;
-  return NBLS_OK;
-}
-void kzg_basis_free(int device, uint8_t* pts) {
-  int cur = 0;
-  const bool restore = hipGetDevice(&cur) == hipSuccess;
-  if (hipSetDevice(device) == hipSuccess) (void)hipFree(pts);
-  if (restore) (void)hipSetDevice(cur);
-}
-EXPORT int nbls_kzg_setup_create(nbls_ctx* ctx, unsigned log2_n, const uint8_t* lagrange48, int8_t* status, nbls_kzg_setup** out) {
-  WHOLE_CALL(ctx);
-  if (out) *out = nullptr;
-  if (!ctx || log2_n < 1 || log2_n > 12 || !lagrange48 || !out) return NBLS_EINVAL;
-  nbls_kzg_setup* su = new (std::nothrow) nbls_kzg_setup;
-  if (!su) return NBLS_EHIP;
-  su->device = ctx->device; su->log2_n = log2_n;
-  const int r = kzg_basis_create(ctx, log2_n, lagrange48, status, &su->pts);
-  if (r) { delete su; return r; }
-  *out = su;
-  return NBLS_OK;
-}
-EXPORT void nbls_kzg_setup_destroy(nbls_kzg_setup* su) {
-  if (!su) return;
-  kzg_basis_free(su->device, su->pts);
-  delete su;
-}
-EXPORT int nbls_kzg_setup_log2n(const nbls_kzg_setup* su, unsigned* log2_n) {
-  if (!su || !log2_n) return NBLS_EINVAL;
-  *log2_n = su->log2_n;
-  return NBLS_OK;
-}
-
 EXPORT int nbls_fr_quotient_roots(nbls_ctx* ctx, unsigned log2_n, size_t n, const uint8_t* evals32, const uint8_t* z32, uint8_t* out_y32, uint8_t* out_q32, int8_t* status) {
   WHOLE_CALL(ctx);
-  if (!ctx || log2_n < 1 || log2_n > 12 || (n && (!evals32 || !z32 || !out_y32 || !out_q32)) || n > (KZGP_MAX_ELEMS >> log2_n)) return NBLS_EINVAL;
+  if (!ctx || log2_n < 1 || log2_n > 12 || (n && (!evals32 || !z32 || !out_y32 || !out_q32)) || n > (KZG_MAX_ELEMS >> log2_n)) return NBLS_EINVAL;
   if (!n) return NBLS_OK;
   DEV_ENTER(ctx, nullptr);
   Staged io(ctx, s);
   // what is read back: the values | the quotient rows | the statuses
   const size_t qb = (n * 32) << log2_n, o_ev = io.bytes(evals32, qb), o_z = io.bytes(z32, n * 32), back = n * 32 + qb + n;
   uint8_t *c, *O; const uint8_t *roots, *got; int r;
-  if ((r = need(ctx, SB_STAGED, io.in_bytes, &c)) || (r = need(ctx, SB_KZGP_SCALARS, back, &O)) || (r = kzg_roots(ctx, log2_n, s, &roots)) || (r = io.send(c, back))) return r;
+  if ((r = need(ctx, SB_STAGED, io.in_bytes, &c)) || (r = need(ctx, SB_KZGP_SCALARS, back, &O)) || (r = kzg_table(ctx, KZG_ROOTS, log2_n, 0, s, &roots)) || (r = io.send(c, back))) return r;
   LAUNCHCHK(nbls_kzg_quotient_launch(log2_n, (unsigned)n, c + o_ev, c + o_z, roots, O, O + n * 32, O + n * 32 + qb, s));
   if ((r = io.fetch(O, back, &got))) return r;
   memcpy(out_y32, got, n * 32); memcpy(out_q32, got + n * 32, qb);
@@ -110,14 +51,13 @@ static int kzg_prove_pipeline(nbls_ctx* ctx, const nbls_kzg_setup* su, const Pro
   MsmbPlan pl;
   uint8_t *c, *SC, *OUT; const uint8_t *roots = nullptr, *got; int r;
   if ((r = need(ctx, SB_STAGED, io.in_bytes, &c)) || (r = need(ctx, SB_KZGP_SCALARS, sz_sc, &SC)) || (r = need(ctx, SB_KZGP_OUT, sz_out, &OUT)) ||
-      (r = msm_rows_dev_plan(ctx, npts, n, &pl)) || (quot && (r = kzg_roots(ctx, log2_n, s, &roots))) || (r = io.send(c, std::max(back, n * 48))))
+      (r = msm_rows_dev_plan(ctx, npts, n, &pl)) || (quot && (r = kzg_table(ctx, KZG_ROOTS, log2_n, 0, s, &roots))) || (r = io.send(c, std::max(back, n * 48))))
     return r;
   uint8_t *Q = SC + a_q, *Z = SC + a_z, *QST = SC + a_qst, *CST = SC + a_cst, *AFF = OUT + a_aff, *ZF = OUT + a_zf, *BK = OUT + a_bk;
   const uint8_t* c48 = in.c48;
   if (commit) {
     LAUNCHCHK(nbls_kzg_canon_launch(log2_n, (unsigned)n, c + o_blob, CST, s));
-    if ((r = msm_rows_dev(ctx, pl, su->pts, c + o_blob, AFF, ZF, s)) || (r = run(ctx, P_G1_COMPRESS, n, {B(0, AFF, 96), B(2, BK, 48)}, s))) return r;
-    LAUNCHCHK(nbls_kzg_prove_tail_launch((unsigned)n, ZF, CST, nullptr, BK, BK + b_st, s));
+    if ((r = kzg_proof_tail(ctx, pl, su->pts, c + o_blob, AFF, ZF, CST, nullptr, BK, BK + b_st, s))) return r;
     if (quot) {   // the challenges need the commitments on the host
       if ((r = read_back(ctx, s, BK, n * 48, &got))) return r;
       memcpy(in.out_c48, got, n * 48);
@@ -133,8 +73,7 @@ static int kzg_prove_pipeline(nbls_ctx* ctx, const nbls_kzg_setup* su, const Pro
       d_z = Z;
     }
     LAUNCHCHK(nbls_kzg_quotient_launch(log2_n, (unsigned)n, c + o_blob, d_z, roots, in.mode == 1 ? BK + b_y : SC + a_y, Q, QST, s));
-    if ((r = msm_rows_dev(ctx, pl, su->pts, Q, AFF, ZF, s)) || (r = run(ctx, P_G1_COMPRESS, n, {B(0, AFF, 96), B(2, BK, 48)}, s))) return r;
-    LAUNCHCHK(nbls_kzg_prove_tail_launch((unsigned)n, ZF, commit ? CST : nullptr, QST, BK, BK + b_st, s));
+    if ((r = kzg_proof_tail(ctx, pl, su->pts, Q, AFF, ZF, commit ? CST : nullptr, QST, BK, BK + b_st, s))) return r;
   }
   if ((r = io.fetch(BK, back, &got))) return r;
   memcpy(in.out_p48, got, n * 48);
@@ -144,7 +83,7 @@ static int kzg_prove_pipeline(nbls_ctx* ctx, const nbls_kzg_setup* su, const Pro
 }
 
 static bool prove_args_ok(const nbls_ctx* ctx, const nbls_kzg_setup* su, size_t n, const uint8_t* blobs) {
-  return ctx && su && blobs && n && su->device == ctx->device && n <= (KZGP_MAX_SCALARS >> su->log2_n);
+  return ctx && su && blobs && n && su->device == ctx->device && n <= (MSMB_MAX_ITEMS >> su->log2_n);   // one pass of the batched MSM
 }
 EXPORT int nbls_kzg_commit_blobs(nbls_ctx* ctx, const nbls_kzg_setup* setup, size_t n, const uint8_t* blobs, uint8_t* out_commitments48, int8_t* status) {
   WHOLE_CALL(ctx);

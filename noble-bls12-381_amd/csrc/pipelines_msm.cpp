@@ -167,7 +167,6 @@ EXPORT int nbls_msm_dev(nbls_ctx* ctx, int g2, size_t n, const void* d_pts, cons
 }
 
 // ---- many sums in one call ------------------------------------------------------------------------------------------------------------------------------------------------
-static const size_t MSMB_MAX_ITEMS = (size_t)1 << 22, MSMB_MAX_GROUPS = (size_t)1 << 20;
 static const size_t MSMB_BIG_DEFAULT = 16384;              // points of a group, as given, above which it runs alone through dev_msm
 static const size_t MSMB_SLAB_DEFAULT = (size_t)1 << 23;   // sorted entries + gathered bucket points of a slab: 1.6 GB of raw G1 points, 3.2 GB in G2
 static const unsigned MSMB_WIDTHS[] = {4, 6, 8, 10, 12};

@@ -358,9 +358,7 @@ EXPORT void nbls_destroy(nbls_ctx* ctx) {
   for (uint8_t* p : {ctx->F, ctx->N, ctx->NI, ctx->io_g1, ctx->io_g2, ctx->io_f12, ctx->one12, ctx->gen_g1, ctx->g1_fixed, ctx->side_scratch, ctx->L, ctx->partial, ctx->unit_lines, ctx->KS,
       ctx->KD, ctx->Kflag, (uint8_t*)ctx->Klist, (uint8_t*)ctx->Kcount}) if (p) hipFree(p);
   for (uint8_t* p : ctx->T) if (p) hipFree(p);
-  for (uint8_t* p : ctx->kzg_roots) if (p) hipFree(p);
-  for (uint8_t* p : ctx->kzg_inv_roots) if (p) hipFree(p);
-  for (auto& row : ctx->kzg_cell_ishifts) for (uint8_t* p : row) if (p) hipFree(p);
+  for (uint8_t* p : ctx->kzg_tables) if (p) hipFree(p);
   for (uint8_t* p : ctx->sb) if (p) hipFree(p);
   for (auto& b : ctx->io_pool) if (b.p) hipFree(b.p);
   for (uint8_t* p : ctx->nib) if (p) hipFree(p);

@@ -300,3 +300,52 @@ def test_the_seed(eng, mono, tau_c, world):
         assert verify(eng, mono, tau_c, shape, call, seed=None) == (True, bytes(6))
         assert verify(eng, mono, tau_c, shape, bad, seed=None) == (False, bytes(want))
         assert verify(eng, mono, tau_c, shape, bad, seed=None, per_item=False) == (False, None)
+
+
+def test_both_verifiers_and_the_shared_tables_on_one_context(pkg, mono, tau_c, world, setup):
+    """the two verifiers alternate on a context of its own, each through its per-item pass (the shared tail on SB_KZG_* and on SB_KZGV_*), between calls that use the tables the
+    other made: the inverse roots of size 8 are made by nbls_kzg_verify_cells at (8,3) and read by nbls_fr_ntt(3), or the other way round on a second context"""
+    from kzg_cells_cases import to_coeffs
+    ints = lambda row: [int.from_bytes(v, 'big') for v in row]
+    c83 = some_cells(world(8, 3), (8, 3), 37, random.Random(8200 + 37))
+    c83.cells[18] = bumped(c83.cells[18], 0)
+    c21 = some_cells(world(2, 1), (2, 1), 3, random.Random(8200 + 3))
+    nine, rnd = Call(world(6, 0)), random.Random(8600)          # cells of one element are openings: the tuples of test_one_element_cells_against_the_opening_verifier
+    for j in range(9):
+        nine.add(j % 2, rnd.randrange(cells_per_blob(6, 0)))
+    cs, ci, ki, cells, proofs = nine.args()
+    tuples = [[cs[i] for i in ci], [cell_shift(k, 6, 0) for k in ki], [int.from_bytes(v, 'big') for v in cells], proofs]
+    tuples[2][4] = (tuples[2][4] + 1) % R
+    polys = [[rnd.randrange(R) for _ in range(8)] for _ in range(2)]
+    blob = world(8, 3)[0]
+
+    def calls(eng):
+        def ntt():
+            coef, st = eng.fr_ntt(3, polys, False)
+            back, st2 = eng.fr_ntt(3, [ints(v) for v in coef], True)
+            return [ints(v) for v in coef], st, [ints(v) for v in back], st2
+        return {1: lambda: verify(eng, mono, tau_c, (8, 3), c83),
+                2: ntt,
+                3: lambda: eng.kzg_verify_proofs(*tuples, setup.tau_g2(), SEED),
+                4: lambda: verify(eng, mono, tau_c, (2, 1), c21),
+                5: lambda: eng.kzg_compute_cells_and_proofs(mono(8), 3, [blob_bytes(blob.f)]),
+                6: lambda: eng.kzg_verify_proofs(*[v[:2] for v in tuples], setup.tau_g2(), SEED),
+                7: lambda: verify(eng, mono, tau_c, (8, 3), c83)}
+    st83 = bytes(NOT_VERIFIED if j == 18 else 0 for j in range(37))
+    want = {1: (False, st83),
+            2: ([to_coeffs(f, 3) for f in polys], [0, 0], polys, [0, 0]),
+            3: (False, bytes(NOT_VERIFIED if j == 4 else 0 for j in range(9))),
+            4: (True, bytes(3)),
+            5: ([[blob.cell(k) for k in range(64)]], [[blob.proof(k) for k in range(64)]], bytes(1)),
+            6: (True, bytes(2)),
+            7: (False, st83)}
+    runs = []
+    for order in ([1, 2, 3, 4, 5, 6, 7], [2, 1, 3, 4, 5, 6, 7]):
+        eng = pkg.Engine(0)          # every table and every slot of this context is made here
+        got = {}
+        for k in order:
+            got[k] = calls(eng)[k]()
+            assert got[k] == want[k], (order, k)
+        eng.close()
+        runs.append(got)
+    assert runs[0] == runs[1]

@@ -36,7 +36,8 @@ def test_symbols_exported(lib):
     for nm in NAMES:
         assert nm in exported, nm
         assert hasattr(lib, nm)
-    for nm in ('nbls_kzg_ntt_launch', 'nbls_kzg_cell_rows_launch', 'nbls_kzg_inv_roots_launch', 'kzg_inv_roots', 'kzg_basis_create', 'kzg_basis_free', 'cells_pipeline'):
+    for nm in ('nbls_kzg_ntt_launch', 'nbls_kzg_cell_rows_launch', 'nbls_kzg_inv_roots_launch', 'kzg_table', 'kzg_basis_create', 'kzg_basis_decode', 'kzg_basis_destroy', 'kzg_basis_log2n',
+               'kzg_proof_tail', 'cells_pipeline'):
         assert not any(nm in e for e in exported), nm          # the kernels' launch wrappers and the internal cores stay internal
     assert lib.nbls_abi_version() == 5
 

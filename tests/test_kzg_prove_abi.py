@@ -37,7 +37,7 @@ def test_symbols_exported(lib):
     for nm in NAMES:
         assert nm in exported, nm
         assert hasattr(lib, nm)
-    for nm in ('nbls_kzg_quotient_launch', 'nbls_kzg_canon_launch', 'nbls_kzg_prove_tail_launch', 'msm_rows_dev', 'msm_rows_dev_plan', 'blob_challenges', 'kzg_roots'):
+    for nm in ('nbls_kzg_quotient_launch', 'nbls_kzg_canon_launch', 'nbls_kzg_prove_tail_launch', 'msm_rows_dev', 'msm_rows_dev_plan', 'blob_challenges', 'kzg_table', 'kzg_proof_tail'):
         assert not any(nm in e for e in exported), nm          # the kernels' launch wrappers and the internal cores stay internal
     assert not any('nbls_sim_' in nm for nm in exported)
     assert lib.nbls_abi_version() == 5

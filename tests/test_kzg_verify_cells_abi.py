@@ -28,8 +28,8 @@ def test_symbol_exported(lib):
     out = subprocess.check_output(['nm', '-D', '--defined-only', os.path.join(PKG, 'libnbls.so')]).decode()
     exported = {ln.split()[-1] for ln in out.splitlines() if ln.strip()}
     assert 'nbls_kzg_verify_cells' in exported and hasattr(lib, 'nbls_kzg_verify_cells')
-    for nm in ('nbls_kzg_cell_interp_launch', 'nbls_kzg_cell_ishifts_launch', 'nbls_kzg_cell_pre_launch', 'nbls_kzg_cell_items_launch', 'verify_cells_pipeline', 'cell_ishifts',
-               'kzg_item_tail', 'kzg_combined_tail', 'neg_g2_wire'):
+    for nm in ('nbls_kzg_cell_interp_launch', 'nbls_kzg_cell_ishifts_launch', 'nbls_kzg_cell_pre_launch', 'nbls_kzg_cell_items_launch', 'verify_cells_pipeline', 'kzg_table',
+               'kzg_item_tail', 'kzg_combined_tail', 'neg_g2_wire', 'KzgFrame', 'kzg_seed', 'kzg_verdict', 'kzg_pairs_carve', 'carve'):
         assert not any(nm in e for e in exported), nm          # the kernels' launch wrappers and the internal cores stay internal
     assert lib.nbls_abi_version() == 5
 
