@@ -493,6 +493,33 @@ int nbls_kzg_verify_cells(nbls_ctx* ctx, const nbls_kzg_monomial* monomial, unsi
                           const uint32_t* commitment_index /* n_cells */, const uint32_t* cell_index /* n_cells */, const uint8_t* cells /* n_cells * (32 << log2_cell) */,
                           const uint8_t* proofs48 /* n_cells */, const uint8_t* tau_c_g2_96, const uint8_t* seed32 /* NULL: from the OS */, int* all_ok,
                           int8_t* status /* n_cells, may be NULL */);
+/* recover_cells_and_kzg_proofs: every cell of n blobs (and, in the second form, every cell proof) from at least half of each blob's cells.  Blob i owns the entries
+ * cell_offsets[i] .. cell_offsets[i + 1] of cell_index and of cells (non-decreasing offsets, the first 0); entry e is cell number cell_index[e] of that blob, c = 2^log2_cell
+ * elements, byte for byte one cell of nbls_kzg_compute_cells' output.  The indices of a blob may come in ANY ORDER (a caller who wants the stricter rule of some libraries,
+ * ascending order, checks it itself).  out_cells is laid out exactly as nbls_kzg_compute_cells lays it out (the blob first, then the coset values), out_proofs48 exactly as
+ * nbls_kzg_compute_cells_and_proofs; for a blob with status 0 both are byte for byte what those two calls return for the recovered blob.  ZERO POINTS ARE VALID, as there:
+ * 0xc0 00.. with status 0.
+ * The route never transforms at size 2 N (a row of 2 N elements does not fit the LDS of a compute unit): the vanishing polynomial Z of the missing cells is constant on
+ * every cell, so a blob takes M = 2 N / c values of it and M / 2 inversions, and six transforms of size N: E Z on H and on gH to the two halves A + B and A - B of
+ * P Z = A + x^N B, their combination A + 7^N B to the values on the coset 7 H, divided block by block, back to the coefficients of P, and from those the cells (fr_exec.h).
+ * The index sets are checked on the host before the copy; everything else happens on the device between one copy in and one copy out, in two launches whatever n is, then
+ * the proofs exactly as nbls_kzg_compute_cells_and_proofs makes them from the coefficients (chunks of whole blobs, NBLS_TUNE_CELLS_CHUNK; the bytes do not depend on them).
+ * After the coefficients are found the call compares the recomputed cells with EVERY given cell: with more than half of the cells an input can contradict itself, and is then
+ * refused, not answered with route-dependent bytes.  (With exactly half, every canonical input is consistent: N points always interpolate.)
+ * status[i] (may be NULL), the first that applies: NBLS_ST_BAD_CELLS; NBLS_ST_NON_CANONICAL: a given element is >= r; NBLS_ST_INCONSISTENT; 0.  Any non-zero status leaves
+ * that blob's cells all-zero and its proofs 48 zero bytes each; a neighbour is never disturbed.  Returns NBLS_OK whatever the blobs hold; NBLS_EINVAL before any device work
+ * for a missing pointer (cell_index and cells may be NULL only when no cell is given at all: every blob is then NBLS_ST_BAD_CELLS), decreasing offsets or a first offset
+ * other than 0, log2_n outside 1 .. 12, log2_cell > log2_n, log2_n + 1 - log2_cell > 12 (the table of the 2 N / c roots), more than 2^24 elements of blobs in the call;
+ * the proofs form also for n = 0 (the cells form answers NBLS_OK, as nbls_kzg_compute_cells), a basis created on another device, or one blob alone above a pass of the
+ * batched MSM: (2 N / c) * N > 2^22.  NOT an interface for secrets.  The consensus-spec test vectors have not been run. */
+#define NBLS_ST_BAD_CELLS 22      /* recovery: fewer than half of the blob's cells given, a cell index >= 2 N / c, or a cell given twice */
+#define NBLS_ST_INCONSISTENT 23   /* recovery: no polynomial of degree < N has all the given cells */
+int nbls_kzg_recover_cells(nbls_ctx* ctx, unsigned log2_n, unsigned log2_cell, size_t n /* blobs */, const uint32_t* cell_offsets /* n + 1 */,
+                           const uint32_t* cell_index /* cell_offsets[n] entries */, const uint8_t* cells /* cell_offsets[n] * (32 << log2_cell) */,
+                           uint8_t* out_cells /* n * (64 << log2_n) */, int8_t* status /* n, may be NULL */);
+int nbls_kzg_recover_cells_and_proofs(nbls_ctx* ctx, const nbls_kzg_monomial* monomial, unsigned log2_cell, size_t n, const uint32_t* cell_offsets,
+                                      const uint32_t* cell_index, const uint8_t* cells, uint8_t* out_cells, uint8_t* out_proofs48 /* n * (2 N / c) * 48 */,
+                                      int8_t* status /* n, may be NULL */);
 
 /* One rank's share of a verifyBatch spread over several GPUs (one process per GPU): the Miller product of this rank's n
  * (key, message) pairs, times millerLoop(-G, S) on the ONE rank that passes the signature (d_sig96 = NULL elsewhere), WITHOUT the
@@ -523,7 +550,7 @@ const char* nbls_config_describe(void);   /* "NBLS_X=value(env|default) ...": ev
    nbls_verify_aggregates_indexed_shared, scratch slots 48 .. 50 (additions only, same version); then nbls_fr_op_batch, nbls_lagrange_at_zero, nbls_g2_combine_shares,
    nbls_g1_combine_shares, NBLS_FROP_*, NBLS_ST_BAD_IDS, scratch slots 51 .. 56 (additions only, same version); then nbls_field_kernel_raw (addition only, same version); then nbls_g1_poly_eval,
    nbls_g2_poly_eval, nbls_extra_program_kernel, NBLS_TUNE_POLY_SLAB, scratch slots 57 .. 61 (additions only, same version); then nbls_g1_msm_batch, nbls_g2_msm_batch,
-   nbls_g1_msm_rows, nbls_g2_msm_rows, NBLS_TUNE_MSMB_WINDOW / _BIG / _SLAB, the names "dbladd_g1" / "dbladd_g2" of nbls_extra_program_kernel, scratch slots 62 .. 63 (additions only, same version); then nbls_map_uniform_batch (addition only, same version); then nbls_fr_eval_roots, nbls_kzg_verify_proofs, nbls_kzg_verify_blobs, NBLS_ST_NON_CANONICAL, scratch slots 64 .. 68 (additions only, same version); then nbls_kzg_setup_create / _destroy / _log2n, nbls_fr_quotient_roots, nbls_kzg_commit_blobs, nbls_kzg_compute_proofs, nbls_kzg_compute_blob_proofs, scratch slots 69 .. 70 (additions only, same version); then nbls_fr_ntt, NBLS_NTT_*, nbls_kzg_compute_cells, nbls_kzg_monomial_create / _destroy / _log2n, nbls_kzg_compute_cells_and_proofs, NBLS_TUNE_CELLS_CHUNK, scratch slots 71 .. 73 (additions only, same version); then nbls_kzg_verify_cells, scratch slots 74 .. 78 (addition only, same version); with the MSM calls ONE CHANGE TO EXISTING CALLS, same version: nbls_g1_msm / nbls_g2_msm write all-zero output bytes when the status is 1 (the sum is the
+   nbls_g1_msm_rows, nbls_g2_msm_rows, NBLS_TUNE_MSMB_WINDOW / _BIG / _SLAB, the names "dbladd_g1" / "dbladd_g2" of nbls_extra_program_kernel, scratch slots 62 .. 63 (additions only, same version); then nbls_map_uniform_batch (addition only, same version); then nbls_fr_eval_roots, nbls_kzg_verify_proofs, nbls_kzg_verify_blobs, NBLS_ST_NON_CANONICAL, scratch slots 64 .. 68 (additions only, same version); then nbls_kzg_setup_create / _destroy / _log2n, nbls_fr_quotient_roots, nbls_kzg_commit_blobs, nbls_kzg_compute_proofs, nbls_kzg_compute_blob_proofs, scratch slots 69 .. 70 (additions only, same version); then nbls_fr_ntt, NBLS_NTT_*, nbls_kzg_compute_cells, nbls_kzg_monomial_create / _destroy / _log2n, nbls_kzg_compute_cells_and_proofs, NBLS_TUNE_CELLS_CHUNK, scratch slots 71 .. 73 (additions only, same version); then nbls_kzg_verify_cells, scratch slots 74 .. 78 (addition only, same version); then nbls_kzg_recover_cells, nbls_kzg_recover_cells_and_proofs, NBLS_ST_BAD_CELLS, NBLS_ST_INCONSISTENT, scratch slot 79 (additions only, same version); with the MSM calls ONE CHANGE TO EXISTING CALLS, same version: nbls_g1_msm / nbls_g2_msm write all-zero output bytes when the status is 1 (the sum is the
    zero point).  The bytes were unspecified there before (what the affine conversion made of a Z that is 0 mod p: in G1 a zero x and an arbitrary y); the status, and every output with status 0, are unchanged.
    nbls_msm_dev, which leaves its result on the device, is not changed.
    4 (round 6): nbls_hw_queues, NBLS_TUNE_WIDE_MAX, NBLS_TUNE_H2C_NORM_MIN, NBLS_TUNE_INV_WIDE_MAX, NBLS_TUNE_LS_MAX / _LS2_MAX (additions only); the library sets GPU_MAX_HW_QUEUES = 22 at load when the variable is unset (see nbls_pool_init below).

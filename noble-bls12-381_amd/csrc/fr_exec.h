@@ -477,4 +477,101 @@ NBLS_FR_HD Fr fr_cell_coeff(const Fr& v, const Fr& hinv, uint32_t i, unsigned lo
 // the cell's status: what came in (a decoder's refusal), else NBLS_ST_NON_CANONICAL for an element >= r, else 0
 NBLS_FR_HD int fr_cell_status(int pre, uint32_t bad) { return pre ? pre : (int)(bad & 21); }
 
+// ---- The recovery of a blob from at least half of its cells (recover_cells_and_kzg_proofs of EIP-7594; kzg_recover_z_kernel, kzg_recover_kernel and nbls_sim_kzg_recover).
+// With M = 2 N / c cells, Z(x) = Zs(x^c), Zs(y) = prod over the missing k of (y - s_k), vanishes exactly on the missing cells and is CONSTANT on every cell: Zs(s_k) on cell k
+// of H u gH, Zs(7^c s_j) on block j < M / 2 of the coset 7 H (the c elements c j .. c j + c of its bit-reversed order).  Nobody needs Z's coefficients: a blob takes the M
+// values Zs(s_k) and the M / 2 inverses 1 / Zs(7^c s_j) -- never zero: 7 generates the multiplicative group, so 7^c s_j is no M-th root of unity.  The route, in transforms
+// of size N only (a row of 2 N elements does not fit the compute unit's LDS), with E the given values and zero where a cell is missing:
+//   (P Z)(x) = A(x) + x^N B(x), deg A, B < N (exact: deg P Z < N + (M / 2) c = 2 N);   S = A + B = to coefficients of (E Z on H);   D = A - B = the same of (E Z on gH), shift g;
+//   T = A + 7^N B = S (1 + 7^N) / 2 + D (1 - 7^N) / 2;   (P Z on 7 H) = to values of T, shift 7;   block j times 1 / Zs(7^c s_j);   P = to coefficients, shift 7.
+// P has degree < N, so its N values on 7 H determine it.  Then the cells are P's values on H and on gH, and every given cell is compared with them: with more than half of the
+// cells the input can contradict itself, the division is then not exact, and the blob is refused (NBLS_ST_INCONSISTENT) instead of answered route-dependently.
+// The index set is checked before anything is weighted (fr_recover_slots, on the host): at least M / 2 entries, every index < M, none twice.  Its result is the blob's slot
+// map: slot[k] = the entry (of the staged cells) that holds cell k, or FR_RECOVER_NONE.  Elements stay plain, the Z values, tables and constants are in Montgomery form.
+enum : uint32_t { FR_RECOVER_NONE = 0xffffffffu };
+struct FrRecoverConsts { Fr g, ginv, seven, seveninv, kp, km, c7; };   // omega_2N, 1 / g, 7, 1 / 7, (1 + 7^N) / 2, (1 - 7^N) / 2, 7^c: the same for every blob of a call, made once on the host
+NBLS_FR_HD FrRecoverConsts fr_recover_consts(unsigned log2_n, unsigned log2_cell) {
+  FrRecoverConsts k;
+  Fr seven = fr_zero(); seven.l[0] = 7;
+  k.seven = fr_mul(seven, fr_r2());
+  k.g = fr_omega(log2_n + 1);
+  k.ginv = fr_inv(k.g); k.seveninv = fr_inv(k.seven);
+  Fr p = k.seven;
+  for (unsigned i = 0; i < log2_n; i++) p = fr_sqr(p);
+  const Fr half = fr_inv_pow2(1);
+  k.kp = fr_mul(fr_add(fr_one(), p), half); k.km = fr_mul(fr_sub(fr_one(), p), half);
+  k.c7 = k.seven;
+  for (unsigned i = 0; i < log2_cell; i++) k.c7 = fr_sqr(k.c7);
+  return k;
+}
+// the slot map of one blob from its `count` indices, whose entries are first, first + 1, ..: returns 0, or 22 (NBLS_ST_BAD_CELLS) with an all-empty map
+NBLS_FR_HD int fr_recover_slots(const uint32_t* idx, uint32_t first, uint64_t count, unsigned log2_m, uint32_t* slot) {
+  const uint32_t M = 1u << log2_m;
+  for (uint32_t k = 0; k < M; k++) slot[k] = FR_RECOVER_NONE;
+  bool ok = count >= M / 2 && count <= M;
+  for (uint64_t e = 0; ok && e < count; e++) {
+    const uint32_t k = idx[e];
+    if (k >= M || slot[k] != FR_RECOVER_NONE) ok = false; else slot[k] = first + (uint32_t)e;
+  }
+  if (ok) return 0;
+  for (uint32_t k = 0; k < M; k++) slot[k] = FR_RECOVER_NONE;
+  return 22;
+}
+// Z value v of a blob, one lane each: v < M: Zs(s_v) (zero where cell v is missing itself);  M <= v < 3 M / 2: 1 / Zs(7^c s_(v - M)), ONE inversion per block of c elements.
+// sroots: the table of the M roots; the walk over k is the same on every lane
+NBLS_FR_HD Fr fr_recover_z(const Fr* sroots, const uint32_t* slot, unsigned log2_m, uint32_t v, const Fr& c7) {
+  const uint32_t M = 1u << log2_m;
+  const bool block = v >= M;
+  const Fr y = block ? fr_mul(c7, sroots[v - M]) : sroots[v];
+  Fr acc = fr_one();
+  for (uint32_t k = 0; k < M; k++) if (slot[k] == FR_RECOVER_NONE) acc = fr_mul(acc, fr_sub(y, sroots[k]));
+  return block ? fr_inv(acc) : acc;
+}
+// the lane's elements t, t + lanes, .. of half `half` of the extension (0: on H, 1: on gH), each times its cell's Zs(s_k), zero where the cell is missing, into `a` (NULL:
+// the canonical check alone); returns all ones when a given element is >= r.  cells: the staged entries of c elements each
+NBLS_FR_HD uint32_t fr_recover_load(const uint8_t* cells, const uint32_t* slot, const Fr* zv, unsigned log2_n, unsigned log2_cell, uint32_t half, uint32_t lane, uint32_t lanes,
+                                    uint32_t* a) {
+  const uint32_t N = 1u << log2_n, c = 1u << log2_cell;
+  uint32_t bad = 0;
+  for (uint32_t i = lane; i < N; i += lanes) {
+    const uint32_t x = half * N + i, k = x >> log2_cell, e = slot[k];
+    Fr v = fr_zero();
+    if (e != FR_RECOVER_NONE) {
+      v = fr_load_q(cells + (((uint64_t)e << log2_cell) + (x & (c - 1))) * 32);
+      bad |= fr_ge_r_mask(v);
+      if (a) v = fr_mul(v, zv[k]);
+    }
+    if (a) fr_ntt_put(a, N, i, v);
+  }
+  return bad;
+}
+// the lane's elements: a = D in, S from s32 (32 bytes big-endian each) -> T_i 7^i = (S_i kp + D_i km) 7^i, ready for the stages towards the values on 7 H
+NBLS_FR_HD void fr_recover_combine(uint32_t* a, const uint8_t* s32, uint32_t N, uint32_t lane, uint32_t lanes, unsigned log2_lanes, const FrRecoverConsts& k) {
+  Fr pw = fr_pow_index(k.seven, lane, log2_lanes), step = k.seven;
+  for (unsigned b = 0; b < log2_lanes; b++) step = fr_sqr(step);
+  for (uint32_t i = lane; i < N; i += lanes) {
+    const Fr t = fr_add(fr_mul(fr_load_q(s32 + 32ull * i), k.kp), fr_mul(fr_ntt_get(a, N, i), k.km));
+    fr_ntt_put(a, N, i, fr_mul(t, pw));
+    pw = fr_mul(pw, step);
+  }
+}
+// the lane's elements of the values on 7 H, each times its block's inverse zinv[i / c]
+NBLS_FR_HD void fr_recover_divide(uint32_t* a, const Fr* zinv, uint32_t N, unsigned log2_cell, uint32_t lane, uint32_t lanes) {
+  for (uint32_t i = lane; i < N; i += lanes) fr_ntt_put(a, N, i, fr_mul(fr_ntt_get(a, N, i), zinv[i >> log2_cell]));
+}
+// the lane's elements of `a` = the recomputed half `half` against the given cells: all ones when one differs
+NBLS_FR_HD uint32_t fr_recover_compare(const uint32_t* a, const uint8_t* cells, const uint32_t* slot, unsigned log2_n, unsigned log2_cell, uint32_t half, uint32_t lane,
+                                       uint32_t lanes) {
+  const uint32_t N = 1u << log2_n, c = 1u << log2_cell;
+  uint32_t diff = 0;
+  for (uint32_t i = lane; i < N; i += lanes) {
+    const uint32_t x = half * N + i, e = slot[x >> log2_cell];
+    if (e == FR_RECOVER_NONE) continue;
+    const Fr v = fr_load_q(cells + (((uint64_t)e << log2_cell) + (x & (c - 1))) * 32), w = fr_ntt_get(a, N, i);
+#pragma unroll
+    for (int l = 0; l < FR_NL; l++) diff |= v.l[l] ^ w.l[l];
+  }
+  return diff ? 0xffffffffu : 0u;
+}
+
 }  // namespace nbls

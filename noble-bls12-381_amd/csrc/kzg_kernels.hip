@@ -2,7 +2,8 @@
 // blobs that are only committed to, the closing kernel of the compressed results): polynomials in evaluation form evaluated at a point (nbls_fr_eval_roots, and y_i = p_i(z_i) of
 // nbls_kzg_verify_blobs), the table of roots of unity, and the small Fr kernels around the two MSMs of the combined check and the ladders of the per-item pass.  The arithmetic is
 // fr_exec.h's, written once and shared with the simulator (nbls_sim_fr_eval_roots); the curve arithmetic runs as step programs (decoder, MSM, ladders, Miller loops).
-// Further down: the transform and the cells of EIP-7594 (pipelines_kzg_cells.cpp) and the interpolation of cells for their verifier (pipelines_kzg_verify_cells.cpp).
+// Further down: the transform and the cells of EIP-7594, their recovery from half of the cells (pipelines_kzg_cells.cpp) and the interpolation of cells for their verifier
+// (pipelines_kzg_verify_cells.cpp).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <atomic>
@@ -162,6 +163,83 @@ __global__ void __launch_bounds__(256) kzg_cell_rows_kernel(u32 log2_n, u32 log2
   const u64 row = ((u64)blob << (log2_n + 1 - log2_cell)) + k;
   fr_cell_chain(coef32 + (((u64)blob * 32) << log2_n), log2_n, log2_cell, j, sroots[k], out_q32 + ((row * 32) << log2_n));
   if (j == 0) row_st[row] = blob_st[blob];
+}
+
+// ---- The recovery of blobs from at least half of their cells (nbls_kzg_recover_cells, pipelines_kzg_cells.cpp); fr_exec.h has the route and the arithmetic.
+// The Z values of n blobs, one lane per (blob, value): value v < M = 2^log2_m is Zs(s_v), value M + j the inverse 1 / Zs(7^c s_j) of block j -- M / 2 inversions a blob, none
+// per element.  slot: n x M (the host's slot maps); pre[blob] != 0: the index set was refused, nothing is written; zv: n x 3 M / 2 values, Montgomery form
+__global__ void __launch_bounds__(256) kzg_recover_z_kernel(u32 log2_m, u32 n, const u32* __restrict__ slot, const int8_t* __restrict__ pre, const Fr* __restrict__ sroots,
+                                                            const FrRecoverConsts* __restrict__ kc, Fr* __restrict__ zv) {
+  const u64 gid = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+  const u32 per = 3u << (log2_m - 1);
+  if (gid >= (u64)n * per) return;
+  const u32 blob = (u32)(gid / per), v = (u32)(gid % per);
+  if (pre[blob]) return;
+  zv[gid] = fr_recover_z(sroots, slot + ((u64)blob << log2_m), log2_m, v, kc->c7);
+}
+// One workgroup per blob, one polynomial in dynamic LDS at a time (32 N bytes), kzg_ntt_kernel's lanes, stages and barriers; six transforms of size N:
+//   the canonical check of every given element -> E Z on H -> S (kept in the blob's row of coef32) -> E Z on gH -> D -> T 7^i -> the values on 7 H -> block j times
+//   1 / Zs(7^c s_j) -> the coefficients of P (to coef32: what the proofs read) -> the values on H, compared and written to the first half of the output row -> the
+//   coefficients again, times g^i -> the values on gH, compared and written to the second half.
+// A lane scales, combines, stores and reloads its OWN elements t, t + 512, .. only: no barrier between such steps, one behind every stage.  Status: pre[blob]
+// (NBLS_ST_BAD_CELLS), else NBLS_ST_NON_CANONICAL, else NBLS_ST_INCONSISTENT where a recomputed element differs from a given one, else 0; a refused blob leaves an all-zero row
+// and all-zero coefficients, and the branch is the workgroup's.  cells / out32 / coef32 are 16-byte aligned; coef32 is read back by the lanes that wrote it (no __restrict__)
+__global__ void __launch_bounds__(NT) kzg_recover_kernel(u32 log2_n, u32 log2_cell, const uint8_t* __restrict__ cells, const u32* __restrict__ slot_all,
+                                                         const int8_t* __restrict__ pre, const Fr* __restrict__ zv_all, const FrRecoverConsts* __restrict__ kc,
+                                                         const Fr* __restrict__ roots, const Fr* __restrict__ iroots, uint8_t* __restrict__ out32, uint8_t* coef32,
+                                                         int8_t* __restrict__ status) {
+  extern __shared__ u32 a[];
+  __shared__ u32 sh_bad, sh_diff;
+  const u32 N = 1u << log2_n, t = threadIdx.x, log2_m = log2_n + 1 - log2_cell, M = 1u << log2_m;
+  const u64 p = blockIdx.x;
+  const u32* slot = slot_all + (p << log2_m);
+  const Fr* zv = zv_all + p * (3u << (log2_m - 1));
+  uint8_t* o32 = out32 + ((p * 64) << log2_n);
+  uint8_t* c32 = coef32 + ((p * 32) << log2_n);
+  if (t == 0) { sh_bad = 0; sh_diff = 0; }
+  __syncthreads();
+  int st = pre[p];
+  if (!st) {
+    const u32 bad = fr_recover_load(cells, slot, zv, log2_n, log2_cell, 0, t, NT, a) | fr_recover_load(cells, slot, zv, log2_n, log2_cell, 1, t, NT, nullptr);
+    if (bad) atomicOr(&sh_bad, 0xffffffffu);
+  }
+  __syncthreads();
+  if (!st && sh_bad) st = NBLS_ST_NON_CANONICAL;
+  if (!st) {
+    const Fr ninv = fr_inv_pow2(log2_n);
+    for (u32 ll = 0; ll < log2_n; ll++) { fr_ntt_stage(a, log2_n, ll, true, iroots, t, NT); __syncthreads(); }
+    fr_ntt_scale(a, N, t, NT, FR_NTT_LOG2_LANES, &ninv, nullptr, c32);   // S
+    fr_recover_load(cells, slot, zv, log2_n, log2_cell, 1, t, NT, a);
+    __syncthreads();
+    for (u32 ll = 0; ll < log2_n; ll++) { fr_ntt_stage(a, log2_n, ll, true, iroots, t, NT); __syncthreads(); }
+    fr_ntt_scale(a, N, t, NT, FR_NTT_LOG2_LANES, &ninv, &kc->ginv, nullptr);   // D
+    fr_recover_combine(a, c32, N, t, NT, FR_NTT_LOG2_LANES, *kc);
+    __syncthreads();
+    for (u32 ll = log2_n; ll-- > 0;) { fr_ntt_stage(a, log2_n, ll, false, roots, t, NT); __syncthreads(); }
+    fr_recover_divide(a, zv + M, N, log2_cell, t, NT);
+    __syncthreads();
+    for (u32 ll = 0; ll < log2_n; ll++) { fr_ntt_stage(a, log2_n, ll, true, iroots, t, NT); __syncthreads(); }
+    fr_ntt_scale(a, N, t, NT, FR_NTT_LOG2_LANES, &ninv, &kc->seveninv, nullptr);   // P
+    fr_ntt_store(a, N, t, NT, c32);
+    __syncthreads();
+    for (u32 ll = log2_n; ll-- > 0;) { fr_ntt_stage(a, log2_n, ll, false, roots, t, NT); __syncthreads(); }
+    u32 diff = fr_recover_compare(a, cells, slot, log2_n, log2_cell, 0, t, NT);
+    fr_ntt_store(a, N, t, NT, o32);
+    fr_ntt_load(c32, N, t, NT, a);
+    fr_ntt_scale(a, N, t, NT, FR_NTT_LOG2_LANES, nullptr, &kc->g, nullptr);
+    __syncthreads();
+    for (u32 ll = log2_n; ll-- > 0;) { fr_ntt_stage(a, log2_n, ll, false, roots, t, NT); __syncthreads(); }
+    diff |= fr_recover_compare(a, cells, slot, log2_n, log2_cell, 1, t, NT);
+    fr_ntt_store(a, N, t, NT, o32 + ((u64)32 << log2_n));
+    if (diff) atomicOr(&sh_diff, 0xffffffffu);
+    __syncthreads();
+    if (sh_diff) st = NBLS_ST_INCONSISTENT;
+  }
+  if (t == 0) status[p] = (int8_t)st;
+  if (st) {   // (behind a barrier in every case: the zeros follow the row's earlier stores)
+    for (u32 j = t; j < 4 * N; j += NT) ((uint4*)o32)[j] = make_uint4(0u, 0u, 0u, 0u);
+    for (u32 j = t; j < 2 * N; j += NT) ((uint4*)c32)[j] = make_uint4(0u, 0u, 0u, 0u);
+  }
 }
 
 // blobs that are only committed to (no quotient kernel reads them): status[i] = NBLS_ST_NON_CANONICAL where an element of blob i is >= r, and that blob's row is zeroed in
@@ -353,8 +431,8 @@ __global__ void kzg_cell_items_kernel(u32 n, const int8_t* __restrict__ dstc, co
 }
 
 // The running products of N = 4096 take more than the 64 KB a launch may ask for by default.  The limit is a per-device function attribute: set once on every device a launch of
-// `kernel` is made on (as nbls_vm_launch does); the common case, already set, takes no lock.  The flags of the three kernels that ask for it live here
-enum LdsKernel { LDS_EVAL, LDS_QUOTIENT, LDS_NTT, LDS_KERNELS };
+// `kernel` is made on (as nbls_vm_launch does); the common case, already set, takes no lock.  The flags of the four kernels that ask for it live here
+enum LdsKernel { LDS_EVAL, LDS_QUOTIENT, LDS_NTT, LDS_RECOVER, LDS_KERNELS };
 int lds_limit(LdsKernel which, const void* kernel) {
   static std::atomic<bool> attr_set[LDS_KERNELS][64];
   static std::mutex attr_mu;
@@ -411,6 +489,18 @@ int nbls_kzg_cell_rows_launch(unsigned log2_n, unsigned log2_cell, unsigned n, c
   if (!n) return 0;
   if (log2_n < 1 || log2_n > 12 || log2_cell > log2_n || log2_n + 1 - log2_cell > 12 || (((uintptr_t)coef32 | (uintptr_t)out_q32) & 15)) return (int)hipErrorInvalidValue;
   return launch_1d(kzg_cell_rows_kernel, (u64)n << (log2_n + 1), 256, 0, stream, log2_n, log2_cell, n, coef32, sroots, blob_st, out_q32, row_st);
+}
+// n blobs through kzg_recover_z_kernel and kzg_recover_kernel (the arrays as the kernels state them; slot: n << log2_m words, log2_m = log2_n + 1 - log2_cell <= 12; zv: room for
+// 3 n << (log2_m - 1) elements; out32: n rows of 2 N elements; coef32: n rows of N, never NULL; status: n bytes, never NULL).  Two launches, whatever n is
+int nbls_kzg_recover_launch(unsigned log2_n, unsigned log2_cell, unsigned n, const void* cells, const uint32_t* slot, const void* pre, const void* sroots, const void* consts,
+                            const void* roots, const void* iroots, void* zv, void* out32, void* coef32, void* status, hipStream_t stream) {
+  if (!n) return 0;
+  if (log2_n < 1 || log2_n > 12 || log2_cell > log2_n || log2_n + 1 - log2_cell > 12 || !coef32 || !status || (((uintptr_t)cells | (uintptr_t)out32 | (uintptr_t)coef32) & 15))
+    return (int)hipErrorInvalidValue;
+  const unsigned log2_m = log2_n + 1 - log2_cell;
+  int e = lds_limit(LDS_RECOVER, (const void*)kzg_recover_kernel);
+  if (!e) e = launch_1d(kzg_recover_z_kernel, (u64)n * (3u << (log2_m - 1)), 256, 0, stream, log2_m, n, slot, pre, sroots, consts, zv);
+  return e ? e : launch_1d(kzg_recover_kernel, (u64)n * NT, NT, 32u << log2_n, stream, log2_n, log2_cell, cells, slot, pre, zv, consts, roots, iroots, out32, coef32, status);
 }
 // evals32: n blobs of 2^log2_n elements, 16-byte aligned, zeroed in place where non-canonical
 int nbls_kzg_canon_launch(unsigned log2_n, unsigned n, void* evals32, void* status, hipStream_t stream) {

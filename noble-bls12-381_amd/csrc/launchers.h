@@ -79,6 +79,8 @@ int nbls_kzg_ntt_launch(unsigned log2_n, unsigned mode, unsigned n, const void* 
 int nbls_kzg_cell_rows_launch(unsigned log2_n, unsigned log2_cell, unsigned n, const void* coef32, const void* sroots, const void* blob_st, void* out_q32, void* row_st,
                               hipStream_t stream);
 int nbls_kzg_cell_ishifts_launch(unsigned log2_n, unsigned log2_m, void* table, hipStream_t stream);
+int nbls_kzg_recover_launch(unsigned log2_n, unsigned log2_cell, unsigned n, const void* cells, const uint32_t* slot, const void* pre, const void* sroots, const void* consts,
+                            const void* roots, const void* iroots, void* zv, void* out32, void* coef32, void* status, hipStream_t stream);
 int nbls_kzg_cell_interp_launch(unsigned log2_cell, unsigned n_cells, int sum, const void* cells, const uint32_t* cell_index, const void* pre, const void* w32, const void* iroots,
                                 const void* ishifts, void* rows32, void* partial, void* out32, void* st_out, hipStream_t stream);
 int nbls_kzg_cell_pre_launch(unsigned n, const void* dstc, const void* dstp, const uint32_t* ci, void* pre0, hipStream_t stream);

@@ -89,9 +89,12 @@ enum Slot {
   // the partial rows and the row of the -S_i, the statuses before the elements are looked at | [tau^c]G2 and -G2, their two line tables, the two combined points, the three
   // parts of B | what is read back | everything of the per-cell pass (the rows of the batched MSM in front)
   SB_KZGV_POINTS = 74, SB_KZGV_SCALARS = 75, SB_KZGV_PAIRS = 76, SB_KZGV_OUT = 77, SB_KZGV_ITEMS = 78,
+  // cells_pipeline's recovery front end (nbls_kzg_recover_cells*, pipelines_kzg_cells.cpp): per blob the 2 N / c values of the missing cells' vanishing polynomial and the
+  // N / c inverses of its values on the coset of 7; the rest of the call is on cells_pipeline's slots (SB_KZGC_COEFS holds a half's coefficients, then the blob's)
+  SB_KZGR_Z = 79,
   NSB
 };
-static_assert(NSB == 79, "sb[] indices do not shift");
+static_assert(NSB == 80, "sb[] indices do not shift");
 constexpr SlotMask slot_bit(int i) { return (SlotMask)1 << i; }
 template <typename... S> constexpr SlotMask slots(S... s) { return (slot_bit(s) | ...); }
 // one instance of dev_decompress: three arrays of field elements and the exponentiation table
@@ -121,6 +124,7 @@ constexpr SlotMask M_POLY_OWN = slots(SB_STAGED, SB_POLY_COEFS, SB_POLY_LABELS, 
 constexpr SlotMask M_KZG_OWN = slots(SB_STAGED, SB_KZG_POINTS, SB_KZG_SCALARS, SB_KZG_PAIRS, SB_KZG_OUT, SB_KZG_ITEMS);   // kzg_pipeline: what outlives the decoder, the MSMs and the ladders it calls
 constexpr SlotMask M_KZGP_OWN = slots(SB_STAGED, SB_KZGP_SCALARS, SB_KZGP_OUT);   // kzg_prove_pipeline: what outlives the batched MSM it calls (msm_rows_dev, on M_MSMB_OWN)
 constexpr SlotMask M_KZGC_OWN = slots(SB_STAGED, SB_KZGC_COEFS, SB_KZGC_ROWS, SB_KZGC_OUT);   // cells_pipeline: what outlives the batched MSM of every chunk
+constexpr SlotMask M_KZGR_OWN = M_KZGC_OWN | slots(SB_KZGR_Z);   // cells_pipeline behind the recovery front end: the Z values are read before the first chunk's MSM and not again
 constexpr SlotMask M_KZGV_OWN = slots(SB_STAGED, SB_KZGV_POINTS, SB_KZGV_SCALARS, SB_KZGV_PAIRS, SB_KZGV_OUT, SB_KZGV_ITEMS);   // verify_cells_pipeline: what outlives the decoder, the MSMs, the batched MSM and the ladder it calls
 constexpr SlotMask M_MSMB_OWN = slots(SB_MSMB_CALL, SB_MSMB_SLAB);   // msm_batch_pipeline: what outlives the dev_msm calls of its big groups
 // what runs side by side
@@ -143,6 +147,9 @@ static_assert(!((M_KZGP_OWN & ~slot_bit(SB_STAGED)) & (M_KZG_OWN | M_POLY_OWN | 
 static_assert(!(M_KZGC_OWN & (M_MSMB_OWN | DEC_MAIN.mask())), "cells_pipeline: the batched MSM runs chunk after chunk while the staged blobs, the coefficients and the results are held; nbls_kzg_monomial_create decodes on the main slots");
 static_assert(!((M_KZGC_OWN & ~slot_bit(SB_STAGED)) & (M_KZGP_OWN | M_KZG_OWN | M_POLY_OWN | M_THR_OWN | M_RLC_MAIN | M_RLC_SIDE | M_RLC_SIDE2 | M_VB_MAIN | M_LADDER | MSM_MAIN.mask() | MSM_RLC.mask())),
               "cells_pipeline keeps to slots of its own");
+static_assert(!(M_KZGR_OWN & (M_MSMB_OWN | DEC_MAIN.mask())), "the recovery front end of cells_pipeline: as cells_pipeline, whose chunks it runs");
+static_assert(!(slot_bit(SB_KZGR_Z) & (M_KZGC_OWN | M_KZGV_OWN | M_KZGP_OWN | M_KZG_OWN | M_POLY_OWN | M_THR_OWN | M_RLC_MAIN | M_RLC_SIDE | M_RLC_SIDE2 | M_VB_MAIN | M_LADDER | MSM_MAIN.mask() | MSM_RLC.mask())),
+              "the recovery front end keeps to a slot of its own");
 static_assert(!(M_KZGV_OWN & (DEC_MAIN.mask() | MSM_RLC.mask() | M_LADDER | M_MSMB_OWN)),
               "verify_cells_pipeline: the decoder, the MSMs (on the slots of MSM_RLC: MSM_MAIN holds SB_STAGED), the batched MSM and the ladder of the per-cell pass regrow their slots while the call holds the staged block and its own");
 static_assert(!((M_KZGV_OWN & ~slot_bit(SB_STAGED)) & (M_KZGC_OWN | M_KZGP_OWN | M_KZG_OWN | M_POLY_OWN | M_THR_OWN | M_RLC_MAIN | M_RLC_SIDE | M_RLC_SIDE2 | M_VB_MAIN | MSM_MAIN.mask())),

@@ -10,12 +10,15 @@
 //               quotient rows of every blob as big-endian scalars -> kzg_proof_tail (kzg_common.cpp): msm_rows_dev against the converted basis -> P_G1_COMPRESS ->
 //               kzg_prove_tail_kernel.  The handle nbls_kzg_monomial and the tables of roots are kzg_common.cpp's as well
 //            -> D2H copy: cells | proofs | statuses
-// Scratch slots: SB_STAGED and SB_KZGC_* (nbls_internal.h, M_KZGC_OWN); the MSM on SB_MSMB_*.
+// nbls_kzg_recover_cells / _and_proofs (recover_cells_and_kzg_proofs) are the same chain behind another front end: from at least half of every blob's cells to the same
+// coefficients buffer, by size-N transforms only (fr_exec.h has the route), then the same proofs loop.
+// Scratch slots: SB_STAGED and SB_KZGC_* (nbls_internal.h, M_KZGC_OWN), the recovery's Z values on SB_KZGR_Z (M_KZGR_OWN); the MSM on SB_MSMB_*.
 #include "nbls_internal.h"
 // (fr_omega runs on the host here: its exponent's shift asks for an unrolling that the host pass declines, which is all the warning says)
 #pragma clang diagnostic ignored "-Wpass-failed"
 #include "fr_exec.h"
 #include <algorithm>
+#include <vector>
 
 EXPORT int nbls_fr_ntt(nbls_ctx* ctx, unsigned log2_n, int dir, size_t n, const uint8_t* in32, const uint8_t* shift32, uint8_t* out32, int8_t* status) {
   WHOLE_CALL(ctx);
@@ -33,18 +36,40 @@ EXPORT int nbls_fr_ntt(nbls_ctx* ctx, unsigned log2_n, int dir, size_t n, const 
   return io.fetch_to(O, out32, qb, status, n);
 }
 
-// mono == NULL: nbls_kzg_compute_cells (out_proofs unused)
-struct CellsIn { unsigned log2_n, log2_cell; size_t n; const uint8_t* blobs; const nbls_kzg_monomial* mono; uint8_t *out_cells, *out_proofs; };
+// mono == NULL: nbls_kzg_compute_cells (out_proofs unused).  rec != NULL: the recovery front end -- the blobs come from subsets of their cells (blobs unused)
+struct RecoverIn { const uint32_t *offsets, *index; const uint8_t* cells; };
+struct CellsIn { unsigned log2_n, log2_cell; size_t n; const uint8_t* blobs; const nbls_kzg_monomial* mono; uint8_t *out_cells, *out_proofs; const RecoverIn* rec; };
 
+// Two front ends to one coefficients buffer, one proofs loop behind them.  From whole blobs: kzg_ntt_kernel's cells mode.  From cells (rec): the index sets are checked here,
+// on the host, before the copy -- a refused blob (NBLS_ST_BAD_CELLS) sends an empty slot map and none of its cells --, then kzg_recover_z_kernel and kzg_recover_kernel leave the
+// same three things the cells mode leaves: the 2 N elements of every blob, its coefficients, its status.  The Z values live on SB_KZGR_Z (M_KZGR_OWN)
 static int cells_pipeline(nbls_ctx* ctx, const CellsIn& in, int8_t* status) {
-  const unsigned L = in.log2_n, lc = in.log2_cell;
+  const unsigned L = in.log2_n, lc = in.log2_cell, lm = L + 1 - lc;
   const size_t n = in.n, N = (size_t)1 << L, M = (2 * N) >> lc, qb = n * N * 32;   // M: the cells, and the quotient rows, of one blob
   const bool proofs = in.mono != nullptr;
+  const RecoverIn* rec = in.rec;
   uint8_t g32[32];
   fr_to_bytes(fr_omega(L + 1), g32);   // g = omega_2N, the shift of the coset
   DEV_ENTER(ctx, nullptr);
   Staged io(ctx, s);
-  const size_t o_blob = io.bytes(in.blobs, qb), o_g = io.bytes(g32, 32);
+  size_t o_blob = 0, o_g = 0, o_cells = 0, o_slot = 0, o_pre = 0, o_k = 0;
+  std::vector<uint32_t> slot; std::vector<int8_t> pre; FrRecoverConsts kc;
+  if (rec) {
+    const size_t cb = (size_t)32 << lc;
+    slot.resize(n * M); pre.resize(n);
+    kc = fr_recover_consts(L, lc);
+    uint32_t at = 0;   // (entries staged so far: at most n M, the cells of 2^24 elements of blobs)
+    for (size_t i = 0; i < n; i++) {
+      const size_t first = rec->offsets[i], cnt = rec->offsets[i + 1] - first;
+      if ((pre[i] = (int8_t)fr_recover_slots(rec->index ? rec->index + first : nullptr, at, cnt, lm, &slot[i * M]))) continue;
+      const size_t o = io.bytes(rec->cells + first * cb, cnt * cb);   // (whole cells: the parts follow one another without a gap)
+      if (!at) o_cells = o;
+      at += (uint32_t)cnt;
+    }
+    o_slot = io.bytes(slot.data(), slot.size() * 4); o_pre = io.bytes(pre.data(), n); o_k = io.bytes(&kc, sizeof kc);
+  } else {
+    o_blob = io.bytes(in.blobs, qb); o_g = io.bytes(g32, 32);
+  }
   // blobs per pass: as many whole blobs as the batched MSM takes, or fewer where the tuning key says so
   size_t per = proofs ? std::min({n, (MSMB_MAX_ITEMS >> L) / M, MSMB_MAX_GROUPS / M}) : n;
   if (proofs && ctx->cells_chunk && ctx->cells_chunk < per) per = ctx->cells_chunk;
@@ -55,14 +80,16 @@ static int cells_pipeline(nbls_ctx* ctx, const CellsIn& in, int8_t* status) {
   const size_t a_bk = carve(&sz_out, back), a_aff = carve(&sz_out, proofs ? per * M * 96 : 0), a_zf = carve(&sz_out, proofs ? per * M : 0), a_cst = carve(&sz_out, proofs ? per * M : 0);
   const size_t a_q = carve(&sz_rows, proofs ? per * M * N * 32 : 0), a_rst = carve(&sz_rows, proofs ? per * M : 0);
   MsmbPlan pl_full, pl_tail;   // (the larger plan first: the smaller then finds both of the MSM's slots large enough and takes the same pointers)
-  uint8_t *c, *OUT, *COEF = nullptr, *ROWS = nullptr; const uint8_t *roots, *iroots, *sroots = nullptr, *got; int r;
-  if ((r = need(ctx, SB_STAGED, io.in_bytes, &c)) || (r = need(ctx, SB_KZGC_OUT, sz_out, &OUT)) || (proofs && (r = need(ctx, SB_KZGC_COEFS, qb, &COEF))) ||
+  uint8_t *c, *OUT, *COEF = nullptr, *ROWS = nullptr, *ZV = nullptr; const uint8_t *roots, *iroots, *sroots = nullptr, *got; int r;
+  if ((r = need(ctx, SB_STAGED, io.in_bytes, &c)) || (r = need(ctx, SB_KZGC_OUT, sz_out, &OUT)) || ((proofs || rec) && (r = need(ctx, SB_KZGC_COEFS, qb, &COEF))) ||
+      (rec && (r = need(ctx, SB_KZGR_Z, n * (M + M / 2) * sizeof(Fr), &ZV))) ||
       (proofs && (r = need(ctx, SB_KZGC_ROWS, sz_rows, &ROWS))) || (proofs && (r = msm_rows_dev_plan(ctx, N, per * M, &pl_full))) ||
       (proofs && tail && (r = msm_rows_dev_plan(ctx, N, tail * M, &pl_tail))) || (r = kzg_table(ctx, KZG_ROOTS, L, 0, s, &roots)) || (r = kzg_table(ctx, KZG_INV_ROOTS, L, 0, s, &iroots)) ||
-      (proofs && (r = kzg_table(ctx, KZG_ROOTS, L + 1 - lc, 0, s, &sroots))) || (r = io.send(c, back)))
+      ((proofs || rec) && (r = kzg_table(ctx, KZG_ROOTS, lm, 0, s, &sroots))) || (r = io.send(c, back)))
     return r;
   uint8_t *BK = OUT + a_bk, *AFF = OUT + a_aff, *ZF = OUT + a_zf, *CST = OUT + a_cst, *Q = ROWS + a_q, *RST = ROWS + a_rst;
-  LAUNCHCHK(nbls_kzg_ntt_launch(L, FR_NTT_CELLS, (unsigned)n, c + o_blob, c + o_g, 0, roots, iroots, BK, COEF, BK + b_st, s));
+  if (rec) LAUNCHCHK(nbls_kzg_recover_launch(L, lc, (unsigned)n, c + o_cells, (const uint32_t*)(c + o_slot), c + o_pre, sroots, c + o_k, roots, iroots, ZV, BK, COEF, BK + b_st, s));
+  else LAUNCHCHK(nbls_kzg_ntt_launch(L, FR_NTT_CELLS, (unsigned)n, c + o_blob, c + o_g, 0, roots, iroots, BK, COEF, BK + b_st, s));
   for (size_t b0 = 0; proofs && b0 < n; b0 += per) {
     const size_t nb = std::min(per, n - b0);
     uint8_t* P = BK + b_pf + b0 * M * 48;
@@ -80,7 +107,7 @@ EXPORT int nbls_kzg_compute_cells(nbls_ctx* ctx, unsigned log2_n, unsigned log2_
   WHOLE_CALL(ctx);
   if (!ctx || log2_n < 1 || log2_n > 12 || log2_cell > log2_n || (n && (!blobs || !out_cells)) || n > (KZG_MAX_ELEMS >> log2_n)) return NBLS_EINVAL;
   if (!n) return NBLS_OK;
-  return cells_pipeline(ctx, {log2_n, log2_cell, n, blobs, nullptr, out_cells, nullptr}, status);
+  return cells_pipeline(ctx, {log2_n, log2_cell, n, blobs, nullptr, out_cells, nullptr, nullptr}, status);
 }
 
 EXPORT int nbls_kzg_compute_cells_and_proofs(nbls_ctx* ctx, const nbls_kzg_monomial* monomial, unsigned log2_cell, size_t n, const uint8_t* blobs, uint8_t* out_cells,
@@ -90,5 +117,32 @@ EXPORT int nbls_kzg_compute_cells_and_proofs(nbls_ctx* ctx, const nbls_kzg_monom
   const unsigned L = monomial->log2_n;
   // one blob alone must fit a pass of the batched MSM: (2 N / c) rows of N scalars
   if (((size_t)2 << (2 * L - log2_cell)) > MSMB_MAX_ITEMS || n > (KZG_MAX_ELEMS >> L)) return NBLS_EINVAL;
-  return cells_pipeline(ctx, {L, log2_cell, n, blobs, monomial, out_cells, out_proofs48}, status);
+  return cells_pipeline(ctx, {L, log2_cell, n, blobs, monomial, out_cells, out_proofs48, nullptr}, status);
+}
+
+// what both recovery calls refuse before any device work (the header's list)
+static bool recover_args_ok(unsigned log2_n, unsigned log2_cell, size_t n, const uint32_t* off, const uint32_t* index, const uint8_t* cells, const uint8_t* out_cells) {
+  if (log2_n < 1 || log2_n > 12 || log2_cell > log2_n || log2_n + 1 - log2_cell > 12 || !off || !out_cells || off[0] != 0 || n > (KZG_MAX_ELEMS >> log2_n)) return false;
+  for (size_t i = 0; i < n; i++) if (off[i + 1] < off[i]) return false;
+  return !off[n] || (index && cells);
+}
+EXPORT int nbls_kzg_recover_cells(nbls_ctx* ctx, unsigned log2_n, unsigned log2_cell, size_t n, const uint32_t* cell_offsets, const uint32_t* cell_index, const uint8_t* cells,
+                                  uint8_t* out_cells, int8_t* status) {
+  WHOLE_CALL(ctx);
+  if (!ctx || log2_n < 1 || log2_n > 12 || log2_cell > log2_n || log2_n + 1 - log2_cell > 12) return NBLS_EINVAL;
+  if (!n) return NBLS_OK;
+  if (!recover_args_ok(log2_n, log2_cell, n, cell_offsets, cell_index, cells, out_cells)) return NBLS_EINVAL;
+  const RecoverIn rec{cell_offsets, cell_index, cells};
+  return cells_pipeline(ctx, {log2_n, log2_cell, n, nullptr, nullptr, out_cells, nullptr, &rec}, status);
+}
+
+EXPORT int nbls_kzg_recover_cells_and_proofs(nbls_ctx* ctx, const nbls_kzg_monomial* monomial, unsigned log2_cell, size_t n, const uint32_t* cell_offsets,
+                                             const uint32_t* cell_index, const uint8_t* cells, uint8_t* out_cells, uint8_t* out_proofs48, int8_t* status) {
+  WHOLE_CALL(ctx);
+  if (!ctx || !monomial || !out_proofs48 || !n || monomial->device != ctx->device) return NBLS_EINVAL;
+  const unsigned L = monomial->log2_n;
+  // one blob alone must fit a pass of the batched MSM: (2 N / c) rows of N scalars
+  if (!recover_args_ok(L, log2_cell, n, cell_offsets, cell_index, cells, out_cells) || ((size_t)2 << (2 * L - log2_cell)) > MSMB_MAX_ITEMS) return NBLS_EINVAL;
+  const RecoverIn rec{cell_offsets, cell_index, cells};
+  return cells_pipeline(ctx, {L, log2_cell, n, nullptr, monomial, out_cells, out_proofs48, &rec}, status);
 }

@@ -22,6 +22,8 @@ extern "C" int nbls_sim_kzg_cells(unsigned log2_n, size_t n, const uint8_t* blob
 extern "C" int nbls_sim_kzg_cell_rows(unsigned log2_n, unsigned log2_cell, size_t n, const uint8_t* coef32, uint8_t* out_q32);
 extern "C" int nbls_sim_kzg_cell_interp(unsigned log2_n, unsigned log2_cell, size_t n_cells, int sum, unsigned n_wg, const uint8_t* cells, const uint32_t* cell_index,
                                         const int8_t* pre, const uint8_t* w32, uint8_t* out, int8_t* st_out);
+extern "C" int nbls_sim_kzg_recover(unsigned log2_n, unsigned log2_cell, size_t n, const uint32_t* cell_offsets, const uint32_t* cell_index, const uint8_t* cells,
+                                    uint8_t* out_cells, uint8_t* coef32, int8_t* status);
 using namespace nbls;
 
 static void be48(uint8_t* o, const u32* limbs) { u32 w[12]; limbs_to_words(w, limbs); for (int i = 0; i < 12; i++) { u32 v = w[11 - i]; o[4 * i] = v >> 24; o[4 * i + 1] = v >> 16; o[4 * i + 2] = v >> 8; o[4 * i + 3] = v; } }
@@ -102,8 +104,23 @@ int main() {
         if (memcmp(sum.data(), rows.data() + k * N * 32, N * 32)) { printf("CELL INTERP: the sum of one cell differs from its row\n"); bad++; }
       }
     }
+    // the recovery: blob 0 from the odd cells in descending order, a refused blob (one cell short) behind it, blob 1 from all of its cells; one-element and whole-blob cells
+    for (unsigned log2_cell : {0u, log2_n}) {
+      const size_t M = (2 * N) >> log2_cell, cb = (size_t)32 << log2_cell;
+      std::vector<uint32_t> off{0}, idx; std::vector<uint8_t> given, rec(3 * 2 * N * 32), rco(3 * N * 32); std::vector<int8_t> rst(3);
+      auto give = [&](size_t blob, uint32_t k) { idx.push_back(k); given.insert(given.end(), cells.begin() + blob * 2 * N * 32 + k * cb, cells.begin() + blob * 2 * N * 32 + (k + 1) * cb); };
+      for (size_t k = M; k-- > 0;) if (k & 1) give(0, (uint32_t)k);
+      off.push_back((uint32_t)idx.size());
+      for (size_t k = 0; k + 1 < M / 2; k++) give(0, (uint32_t)k);
+      off.push_back((uint32_t)idx.size());
+      for (size_t k = 0; k < M; k++) give(1, (uint32_t)k);
+      off.push_back((uint32_t)idx.size());
+      if (nbls_sim_kzg_recover(log2_n, log2_cell, 3, off.data(), idx.data(), given.data(), rec.data(), rco.data(), rst.data())) return 2;
+      if (rst[0] || rst[1] != 22 || rst[2] || memcmp(rec.data(), cells.data(), 2 * N * 32) || memcmp(rec.data() + 4 * N * 32, cells.data() + 2 * N * 32, 2 * N * 32) ||
+          memcmp(rco.data(), co.data(), N * 32) || memcmp(rco.data() + 2 * N * 32, co.data() + N * 32, N * 32)) { printf("RECOVER: cells, coefficients or statuses differ\n"); bad++; }
+    }
   }
-  printf("transform, cell rows and cell interpolation ok\n");
+  printf("transform, cell rows, cell interpolation and recovery ok\n");
   if (memcmp(out1, out2, 576)) { printf("MISMATCH between the fused and the split Miller loop\n"); bad++; }
   printf("miller c0.c0.c0 ");
   for (int i = 0; i < 48; i++) printf("%02x", out1[i]);

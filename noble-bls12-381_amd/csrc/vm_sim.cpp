@@ -746,6 +746,72 @@ __attribute__((visibility("default"))) int nbls_sim_kzg_cell_interp(unsigned log
   for (u32 t = 0; t < c; t++) fr_store_q(fr_neg(part[t]), out + 32ull * t);
   return 0;
 }
+// nbls_kzg_recover_cells as kzg_recover_z_kernel and kzg_recover_kernel run it: the host's slot maps (fr_recover_slots), one lane per Z value, then per blob FR_NTT_LANES lanes,
+// every phase between two barriers lane after lane, `a` exactly the kernel's dynamic LDS, the half's coefficients S parked in the blob's coefficient row as on the device.
+// coef32 (may be NULL): the n x N coefficients the proofs read.  Returns -1 (NBLS_EINVAL) under the rules of the device call that need no context
+__attribute__((visibility("default"))) int nbls_sim_kzg_recover(unsigned log2_n, unsigned log2_cell, size_t n, const uint32_t* cell_offsets, const uint32_t* cell_index,
+                                                                const uint8_t* cells, uint8_t* out_cells, uint8_t* coef32, int8_t* status) {
+  if (log2_n < 1 || log2_n > 12 || log2_cell > log2_n || log2_n + 1 - log2_cell > 12) return -1;
+  if (!n) return 0;
+  if (!cell_offsets || !out_cells || cell_offsets[0] != 0 || (n << log2_n) > ((size_t)1 << 24)) return -1;
+  for (size_t i = 0; i < n; i++) if (cell_offsets[i + 1] < cell_offsets[i]) return -1;
+  if (cell_offsets[n] && (!cell_index || !cells)) return -1;
+  const unsigned lm = log2_n + 1 - log2_cell;
+  const u32 N = 1u << log2_n, M = 1u << lm, W = FR_NTT_LANES, per = M + M / 2;
+  std::vector<Fr> roots, iroots, sroots(M), zv(per);
+  sim_ntt_tables(log2_n, roots, iroots);
+  const Fr om = fr_omega(lm);
+  for (u32 k = 0; k < M; k++) sroots[k] = fr_root_entry(om, lm, k);
+  const FrRecoverConsts kc = fr_recover_consts(log2_n, log2_cell);
+  const Fr ninv = fr_inv_pow2(log2_n);
+  std::vector<u32> slot(M), a((size_t)FR_NL * N);
+  std::vector<uint8_t> own((size_t)32 * N);
+  auto stages = [&](bool inverse) {
+    if (inverse) { for (u32 ll = 0; ll < log2_n; ll++) for (u32 l = 0; l < W; l++) fr_ntt_stage(a.data(), log2_n, ll, true, iroots.data(), l, W); }
+    else for (u32 ll = log2_n; ll-- > 0;) for (u32 l = 0; l < W; l++) fr_ntt_stage(a.data(), log2_n, ll, false, roots.data(), l, W);
+  };
+  for (size_t p = 0; p < n; p++) {
+    uint8_t *o32 = out_cells + ((64 * p) << log2_n), *c32 = coef32 ? coef32 + ((32 * p) << log2_n) : own.data();
+    const u32 first = cell_offsets[p];
+    int st = fr_recover_slots(cell_index ? cell_index + first : nullptr, first, cell_offsets[p + 1] - first, lm, slot.data());
+    u32 bad = 0, diff = 0;
+    if (!st) {
+      for (u32 v = 0; v < per; v++) zv[v] = fr_recover_z(sroots.data(), slot.data(), lm, v, kc.c7);
+      for (u32 l = 0; l < W; l++)
+        bad |= fr_recover_load(cells, slot.data(), zv.data(), log2_n, log2_cell, 0, l, W, a.data()) | fr_recover_load(cells, slot.data(), zv.data(), log2_n, log2_cell, 1, l, W, nullptr);
+      if (bad) st = 21;
+    }
+    if (!st) {
+      stages(true);
+      for (u32 l = 0; l < W; l++) {
+        fr_ntt_scale(a.data(), N, l, W, FR_NTT_LOG2_LANES, &ninv, nullptr, c32);
+        fr_recover_load(cells, slot.data(), zv.data(), log2_n, log2_cell, 1, l, W, a.data());
+      }
+      stages(true);
+      for (u32 l = 0; l < W; l++) {
+        fr_ntt_scale(a.data(), N, l, W, FR_NTT_LOG2_LANES, &ninv, &kc.ginv, nullptr);
+        fr_recover_combine(a.data(), c32, N, l, W, FR_NTT_LOG2_LANES, kc);
+      }
+      stages(false);
+      for (u32 l = 0; l < W; l++) fr_recover_divide(a.data(), zv.data() + M, N, log2_cell, l, W);
+      stages(true);
+      for (u32 l = 0; l < W; l++) { fr_ntt_scale(a.data(), N, l, W, FR_NTT_LOG2_LANES, &ninv, &kc.seveninv, nullptr); fr_ntt_store(a.data(), N, l, W, c32); }
+      stages(false);
+      for (u32 l = 0; l < W; l++) {
+        diff |= fr_recover_compare(a.data(), cells, slot.data(), log2_n, log2_cell, 0, l, W);
+        fr_ntt_store(a.data(), N, l, W, o32);
+        fr_ntt_load(c32, N, l, W, a.data());
+        fr_ntt_scale(a.data(), N, l, W, FR_NTT_LOG2_LANES, nullptr, &kc.g, nullptr);
+      }
+      stages(false);
+      for (u32 l = 0; l < W; l++) { diff |= fr_recover_compare(a.data(), cells, slot.data(), log2_n, log2_cell, 1, l, W); fr_ntt_store(a.data(), N, l, W, o32 + ((size_t)32 << log2_n)); }
+      if (diff) st = 23;
+    }
+    if (status) status[p] = (int8_t)st;
+    if (st) { memset(o32, 0, (size_t)64 << log2_n); if (coef32) memset(c32, 0, (size_t)32 << log2_n); }
+  }
+  return 0;
+}
 __attribute__((visibility("default"))) int nbls_sim_program_count() { return (int)P_COUNT; }
 __attribute__((visibility("default"))) void nbls_sim_stats() { for (int i = 0; i < P_COUNT; i++) print_stats(get_program((ProgId)i)); }
 }

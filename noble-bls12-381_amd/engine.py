@@ -100,6 +100,8 @@ def load_library():
     lib.nbls_kzg_monomial_log2n.argtypes = [vp, C.POINTER(C.c_uint)]
     lib.nbls_kzg_compute_cells_and_proofs.argtypes = [vp, vp, C.c_uint, sz, vp, vp, vp, vp]
     lib.nbls_kzg_verify_cells.argtypes = [vp, vp, C.c_uint, sz, vp, sz, vp, vp, vp, vp, vp, vp, C.POINTER(i32), vp]
+    lib.nbls_kzg_recover_cells.argtypes = [vp, C.c_uint, C.c_uint, sz, vp, vp, vp, vp, vp]
+    lib.nbls_kzg_recover_cells_and_proofs.argtypes = [vp, vp, C.c_uint, sz, vp, vp, vp, vp, vp, vp]
     lib.nbls_keyset_create.argtypes = [vp, sz, vp, vp, C.POINTER(vp)]
     lib.nbls_keyset_destroy.argtypes = [vp]
     lib.nbls_keyset_destroy.restype = None
@@ -745,6 +747,42 @@ class Engine:
         per = 2 << (log2_n - log2_cell)
         out = C.create_string_buffer(2 * len(raw)); pf = C.create_string_buffer(48 * per * n); st = C.create_string_buffer(n)
         self._chk(self.lib.nbls_kzg_compute_cells_and_proofs(self.h, setup.h, log2_cell, n, raw, out, pf, st))
+        p = pf.raw
+        return self._cells_of(out.raw, n, log2_n, log2_cell), [[p[48 * (per * i + k):48 * (per * i + k + 1)] for k in range(per)] for i in range(n)], st.raw[:n]
+
+    def _recover_args(self, name, log2_n, log2_cell, cell_indices, cells):
+        size = 32 << log2_cell if 0 <= log2_cell <= log2_n else -1
+        if not 1 <= log2_n <= 12 or size < 0 or len(cell_indices) != len(cells) or any(len(i) != len(c) for i, c in zip(cell_indices, cells)) or \
+           any(not 0 <= int(k) < 1 << 32 for i in cell_indices for k in i) or any(len(x) != size for c in cells for x in c) or sum(len(i) for i in cell_indices) >= 1 << 32:
+            raise NblsError('%s: log2_n in 1 .. 12, log2_cell in 0 .. log2_n, per blob a list of cell indices and as many cells of %d bytes each' % (name, size))
+        off = [0]
+        for i in cell_indices:
+            off.append(off[-1] + len(i))
+        flat = [int(k) for i in cell_indices for k in i]
+        return (C.c_uint32 * len(off))(*off), (C.c_uint32 * len(flat))(*flat) if flat else None, b''.join(bytes(x) for c in cells for x in c) if flat else None
+
+    def kzg_recover_cells(self, log2_n, log2_cell, cell_indices, cells):
+        """recover_cells for n blobs from at least half of each blob's cells: cell_indices[i] lists the cell numbers given for blob i (any order), cells[i] those cells (byte
+        strings of 32 << log2_cell bytes, as kzg_compute_cells returns them) -> (per blob the list of ALL its cells, as kzg_compute_cells; status bytes: 22 = fewer than half of
+        the cells, an index out of range or twice, 21 = an element >= r, 23 = the given cells contradict one another; the blob's cells are then all-zero)"""
+        off, idx, raw = self._recover_args('kzg_recover_cells', log2_n, log2_cell, cell_indices, cells)
+        n = len(cells)
+        out = C.create_string_buffer(max((64 << log2_n) * n, 1)); st = C.create_string_buffer(max(n, 1))
+        self._chk(self.lib.nbls_kzg_recover_cells(self.h, log2_n, log2_cell, n, off, idx, raw, out, st))
+        return self._cells_of(out.raw, n, log2_n, log2_cell), st.raw[:n]
+
+    def kzg_recover_cells_and_proofs(self, monomial, log2_cell, cell_indices, cells):
+        """recover_cells_and_kzg_proofs against a KzgMonomialSetup: the arguments of kzg_recover_cells -> (cells, proofs, status bytes) as kzg_compute_cells_and_proofs returns
+        them for the recovered blobs; a refused blob (statuses as kzg_recover_cells) has all-zero cells and 48 zero bytes for every proof"""
+        if getattr(monomial, 'h', None) is None:
+            raise NblsError('kzg_recover_cells_and_proofs: the setup is closed')
+        log2_n, n = monomial.log2_n, len(cells)
+        off, idx, raw = self._recover_args('kzg_recover_cells_and_proofs', log2_n, log2_cell, cell_indices, cells)
+        if not n:
+            raise NblsError('kzg_recover_cells_and_proofs: one blob or more')
+        per = 2 << (log2_n - log2_cell)
+        out = C.create_string_buffer((64 << log2_n) * n); pf = C.create_string_buffer(48 * per * n); st = C.create_string_buffer(n)
+        self._chk(self.lib.nbls_kzg_recover_cells_and_proofs(self.h, monomial.h, log2_cell, n, off, idx, raw, out, pf, st))
         p = pf.raw
         return self._cells_of(out.raw, n, log2_n, log2_cell), [[p[48 * (per * i + k):48 * (per * i + k + 1)] for k in range(per)] for i in range(n)], st.raw[:n]
 

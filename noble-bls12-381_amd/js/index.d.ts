@@ -105,6 +105,13 @@ export declare class PointG1 {
   static computeCellsAsync(log2n: number, log2cell: number, blobs: Hex[]): Promise<KzgCells>;
   static computeCellsAndKzgProofs(setup: KzgMonomialSetup, log2cell: number, blobs: Hex[]): KzgCellsAndProofs;
   static computeCellsAndKzgProofsAsync(setup: KzgMonomialSetup, log2cell: number, blobs: Hex[]): Promise<KzgCellsAndProofs>;
+  /** recover_cells_and_kzg_proofs (EIP-7594): cellIndices[i] = the numbers of the cells given for blob i (any order, at least half of them), cells[i] = those cells.  Results as
+   *  computeCells / computeCellsAndKzgProofs return them for the recovered blobs; status per blob: 22 = fewer than half of the cells, an index out of range or twice,
+   *  21 = an element >= CURVE.r, 23 = the given cells contradict one another (the blob's outputs are then all-zero bytes) */
+  static recoverCells(log2n: number, log2cell: number, cellIndices: number[][], cells: Hex[][]): KzgCells;
+  static recoverCellsAsync(log2n: number, log2cell: number, cellIndices: number[][], cells: Hex[][]): Promise<KzgCells>;
+  static recoverCellsAndKzgProofs(setup: KzgMonomialSetup, log2cell: number, cellIndices: number[][], cells: Hex[][]): KzgCellsAndProofs;
+  static recoverCellsAndKzgProofsAsync(setup: KzgMonomialSetup, log2cell: number, cellIndices: number[][], cells: Hex[][]): Promise<KzgCellsAndProofs>;
   /** EIP-7594 verify_cell_kzg_proof_batch: cell k is cell number cellIndices[k] of the blob with commitment commitments[commitmentIndices[k]] (every commitment once; cells of
    *  32 << log2cell bytes, log2cell <= 6) against the setup's [tau^c]G2; status as verifyKzgProofBatch, 21 = an element of the cell is non-canonical */
   static verifyCellKzgProofBatch(setup: KzgMonomialSetup, log2cell: number, commitments: (PointG1 | Hex)[], commitmentIndices: number[], cellIndices: number[], cells: Hex[],

@@ -319,6 +319,40 @@ async function computeCellsAndKzgProofsAsync(setup, log2cell, blobs) {
   kzgMonomialOpen(setup); const b = kzgCellArgs(setup.log2n, log2cell, blobs);
   return kzgCellsResult(await native.kzgCellsAndProofsAsync(setup.handle, log2cell, b), blobs.length, setup.log2n, log2cell, true);
 }
+// recover_cells_and_kzg_proofs (nbls_kzg_recover_cells / _and_proofs): cellIndices[i] lists the numbers of the cells given for blob i, in any order, cells[i] those cells (bytes
+// or hex of 32 << log2cell each, as computeCells returns them); at least half of a blob's cells.  -> { cells, status } / { cells, proofs, status } as computeCells /
+// computeCellsAndKzgProofs return them for the recovered blobs; status per blob: 22 = fewer than half of the cells, an index out of range or twice; 21 = an element is >= CURVE.r;
+// 23 = the given cells contradict one another -- the blob's cells are then all-zero bytes and its proofs 48 zero bytes each
+function kzgRecoverArgs(log2n, log2cell, cellIndices, cells) {
+  if (!Number.isInteger(log2n) || log2n < 1 || log2n > 12) throw new Error('Expected log2n in 1 .. 12');
+  if (!Number.isInteger(log2cell) || log2cell < 0 || log2cell > log2n) throw new Error('Expected log2cell in 0 .. log2n');
+  if (!Array.isArray(cellIndices) || !Array.isArray(cells) || !cells.length) throw new Error('Expected non-empty array');
+  if (cellIndices.length !== cells.length) throw new Error('Expected as many lists of cell indices as lists of cells');
+  const offs = new Uint32Array(cells.length + 1), flat = [], all = [];
+  cells.forEach((cs, i) => {
+    if (!Array.isArray(cs) || !Array.isArray(cellIndices[i]) || cs.length !== cellIndices[i].length) throw new Error('Expected as many cell indices as cells for every blob');
+    for (const v of cellIndices[i]) { if (!Number.isInteger(v) || v < 0 || v > 0xffffffff) throw new Error('Invalid cell index: expected a 32-bit unsigned integer'); flat.push(v); }
+    for (const c of cs) all.push(c);
+    offs[i + 1] = flat.length;
+  });
+  return [offs, Uint32Array.from(flat), all.length ? kzgPack(all, 32 << log2cell, 'cell', ensureBytes) : new Uint8Array(0)];
+}
+function recoverCells(log2n, log2cell, cellIndices, cells) {
+  const a = kzgRecoverArgs(log2n, log2cell, cellIndices, cells); ensureInit();
+  return kzgCellsResult(native.kzgRecoverCells(log2n, log2cell, a[0], a[1], a[2]), cells.length, log2n, log2cell, false);
+}
+async function recoverCellsAsync(log2n, log2cell, cellIndices, cells) {
+  const a = kzgRecoverArgs(log2n, log2cell, cellIndices, cells); ensureInit();
+  return kzgCellsResult(await native.kzgRecoverCellsAsync(log2n, log2cell, a[0], a[1], a[2]), cells.length, log2n, log2cell, false);
+}
+function recoverCellsAndKzgProofs(setup, log2cell, cellIndices, cells) {
+  kzgMonomialOpen(setup); const a = kzgRecoverArgs(setup.log2n, log2cell, cellIndices, cells);
+  return kzgCellsResult(native.kzgRecoverCellsAndProofs(setup.handle, log2cell, a[0], a[1], a[2]), cells.length, setup.log2n, log2cell, true);
+}
+async function recoverCellsAndKzgProofsAsync(setup, log2cell, cellIndices, cells) {
+  kzgMonomialOpen(setup); const a = kzgRecoverArgs(setup.log2n, log2cell, cellIndices, cells);
+  return kzgCellsResult(await native.kzgRecoverCellsAndProofsAsync(setup.handle, log2cell, a[0], a[1], a[2]), cells.length, setup.log2n, log2cell, true);
+}
 // verify_cell_kzg_proof_batch (nbls_kzg_verify_cells): cell k of the call is cell number cellIndices[k] of the blob committed to by commitments[commitmentIndices[k]] -- every
 // commitment once, cells may repeat --, with its proof; tauCG2: the setup's [tau^c]G2 (g2_monomial[c]; 96 compressed bytes, hex, or a PointG2), c = 2^log2cell <= 64 elements per
 // cell.  -> { ok, status } as verifyKzgProofBatch (status per cell: 21 = an element of the cell is >= CURVE.r); opts.seed, opts.perItem likewise
@@ -482,6 +516,10 @@ class PointG1 {
   static computeCellsAsync(log2n, log2cell, blobs) { return computeCellsAsync(log2n, log2cell, blobs); }
   static computeCellsAndKzgProofs(setup, log2cell, blobs) { return computeCellsAndKzgProofs(setup, log2cell, blobs); }
   static computeCellsAndKzgProofsAsync(setup, log2cell, blobs) { return computeCellsAndKzgProofsAsync(setup, log2cell, blobs); }
+  static recoverCells(log2n, log2cell, cellIndices, cells) { return recoverCells(log2n, log2cell, cellIndices, cells); }
+  static recoverCellsAsync(log2n, log2cell, cellIndices, cells) { return recoverCellsAsync(log2n, log2cell, cellIndices, cells); }
+  static recoverCellsAndKzgProofs(setup, log2cell, cellIndices, cells) { return recoverCellsAndKzgProofs(setup, log2cell, cellIndices, cells); }
+  static recoverCellsAndKzgProofsAsync(setup, log2cell, cellIndices, cells) { return recoverCellsAndKzgProofsAsync(setup, log2cell, cellIndices, cells); }
   static verifyCellKzgProofBatch(setup, log2cell, commitments, commitmentIndices, cellIndices, cells, proofs, tauCG2, opts) {
     return verifyCellKzgProofBatch(setup, log2cell, commitments, commitmentIndices, cellIndices, cells, proofs, tauCG2, opts);
   }

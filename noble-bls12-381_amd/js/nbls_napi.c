@@ -25,6 +25,7 @@ SYM(nbls_fr_op_batch) SYM(nbls_lagrange_at_zero) SYM(nbls_g2_combine_shares) SYM
 SYM(nbls_kzg_verify_proofs) SYM(nbls_kzg_verify_blobs)
 SYM(nbls_kzg_setup_create) SYM(nbls_kzg_setup_destroy) SYM(nbls_kzg_setup_log2n) SYM(nbls_kzg_commit_blobs) SYM(nbls_kzg_compute_proofs) SYM(nbls_kzg_compute_blob_proofs)
 SYM(nbls_fr_ntt) SYM(nbls_kzg_compute_cells) SYM(nbls_kzg_monomial_create) SYM(nbls_kzg_monomial_destroy) SYM(nbls_kzg_monomial_log2n) SYM(nbls_kzg_compute_cells_and_proofs) SYM(nbls_kzg_verify_cells)
+SYM(nbls_kzg_recover_cells) SYM(nbls_kzg_recover_cells_and_proofs)
 static nbls_ctx* ctx;
 static nbls_multi* multi;   /* several GPUs behind one handle (initMulti): ctx is then its first context; the batch calls shard over all of them */
 #define MULTI() (multi && p_nbls_multi_device_count(multi) > 1)
@@ -433,11 +434,11 @@ static napi_value SignBatchAsync(napi_env env, napi_callback_info info) {
  * The offsets must name identifiers and shares that are in the arrays (checked here); the library checks the rest. */
 typedef struct {
   napi_async_work work; napi_deferred deferred; napi_ref refs[12]; int nrefs;
-  int kind /* 0 frOp, 1 lagrangeAtZero, 2 combineShares, 3 polyEval, 4 kzgVerifyProofs, 5 kzgVerifyBlobs, 6 .. 8 kzgProve, 9 frNtt, 10 kzgComputeCells, 11 kzgCellsAndProofs, 12 kzgVerifyCells */, op, g2; const uint8_t *a, *b, *shares; const uint32_t *offs, *coffs; size_t n;
+  int kind /* 0 frOp, 1 lagrangeAtZero, 2 combineShares, 3 polyEval, 4 kzgVerifyProofs, 5 kzgVerifyBlobs, 6 .. 8 kzgProve, 9 frNtt, 10 kzgComputeCells, 11 kzgCellsAndProofs, 12 kzgVerifyCells, 13 kzgRecoverCells, 14 kzgRecoverCellsAndProofs */, op, g2; const uint8_t *a, *b, *shares; const uint32_t *offs, *coffs; size_t n;
   uint8_t* out; int8_t* st;
   const uint8_t *proofs, *tau, *seed; int per_item;   /* KZG: a = commitments, b = z (proofs) or the blobs, shares = y, op = log2_n; out = the verdict as one int */
   const nbls_kzg_setup* su;   /* kzgProve: b = the blobs, a = the points z (7) or the given commitments (8; may be NULL), out = two arrays of n entries one behind the other */
-  const nbls_kzg_monomial* mo; size_t proofs_at;   /* PeerDAS: op = log2_n, g2 = the direction (9) or log2_cell (10, 11), b = the rows or the blobs, a = the shifts (9; may be NULL); 11: out = the cells, then at proofs_at the proofs; 12: a = the commitments (proofs_at of them), offs / coffs = the commitment and cell indices, b = the cells, proofs / tau / seed / per_item as the other verifiers */
+  const nbls_kzg_monomial* mo; size_t proofs_at;   /* PeerDAS: op = log2_n, g2 = the direction (9) or log2_cell (10, 11), b = the rows or the blobs, a = the shifts (9; may be NULL); 11: out = the cells, then at proofs_at the proofs; 12: a = the commitments (proofs_at of them), offs / coffs = the commitment and cell indices, b = the cells, proofs / tau / seed / per_item as the other verifiers; 13, 14: offs / coffs = the cell offsets (n + 1) and the cell indices, b = the given cells, out as 10 / 11 */
   nbls_ctx* c; int rc;
 } thr_job;
 static void thr_execute(napi_env env, void* data) { thr_job* j = (thr_job*)data; (void)env;
@@ -452,6 +453,8 @@ static void thr_execute(napi_env env, void* data) { thr_job* j = (thr_job*)data;
         : j->kind == 10 ? p_nbls_kzg_compute_cells(j->c, (unsigned)j->op, (unsigned)j->g2, j->n, j->b, j->out, j->st)
         : j->kind == 11 ? p_nbls_kzg_compute_cells_and_proofs(j->c, j->mo, (unsigned)j->g2, j->n, j->b, j->out, j->out + j->proofs_at, j->st)
         : j->kind == 12 ? p_nbls_kzg_verify_cells(j->c, j->mo, (unsigned)j->g2, j->proofs_at, j->a, j->n, j->offs, j->coffs, j->b, j->proofs, j->tau, j->seed, (int*)j->out, j->per_item ? j->st : NULL)
+        : j->kind == 13 ? p_nbls_kzg_recover_cells(j->c, (unsigned)j->op, (unsigned)j->g2, j->n, j->offs, j->coffs, j->b, j->out, j->st)
+        : j->kind == 14 ? p_nbls_kzg_recover_cells_and_proofs(j->c, j->mo, (unsigned)j->g2, j->n, j->offs, j->coffs, j->b, j->out, j->out + j->proofs_at, j->st)
         : j->kind == 3 ? (j->g2 ? p_nbls_g2_poly_eval : p_nbls_g1_poly_eval)(j->c, j->n, j->coffs, j->shares, j->offs, j->a, j->out, j->st)
         : (j->g2 ? p_nbls_g2_combine_shares : p_nbls_g1_combine_shares)(j->c, j->n, j->offs, j->a, j->shares, j->out, j->st); }
 /* the Error of a failed call of this family: the message of throw_code, and the library's return code as the number `nblsCode` (what the facade reads: never the text) */
@@ -642,7 +645,12 @@ static napi_value KzgProveAsync(napi_env env, napi_callback_info info) { return 
  *   kzgCellsAndProofs(handle, log2cell, blobs)         out = the cells of every blob, then n * (2 N / c) proofs of 48 bytes; status per blob
  *   kzgVerifyCells(handle, log2cell, commitments48, commitmentIndex, cellIndex, cells, proofs48, tauCG2, seed32 | null, perItem)
  *                                                      nbls_kzg_verify_cells: the two index arrays are Uint32Arrays of one entry per cell; out = the verdict (4 bytes, a native
- *                                                      int), status per cell, as kzgVerifyProofs */
+ *                                                      int), status per cell, as kzgVerifyProofs
+ *   kzgRecoverCells(log2n, log2cell, cellOffsets, cellIndex, cells)
+ *   kzgRecoverCellsAndProofs(handle, log2cell, cellOffsets, cellIndex, cells)
+ *                                                      nbls_kzg_recover_cells / _and_proofs: cellOffsets = Uint32Array of blobs + 1 entries, cellIndex = Uint32Array of one
+ *                                                      entry per given cell (checked here: the offsets start at 0, do not decrease and name cells that are in the arrays); out
+ *                                                      and status as kzgComputeCells / kzgCellsAndProofs */
 static napi_value fr_ntt_call(napi_env env, napi_callback_info info, int async) {
   ARGS(4); NEED_CTX(); BYTES(2, rows, lr);
   int32_t log2n, dir;
@@ -733,6 +741,33 @@ static napi_value kzg_verify_cells_call(napi_env env, napi_callback_info info, i
 static napi_value KzgVerifyCells(napi_env env, napi_callback_info info) { return kzg_verify_cells_call(env, info, 0); }
 static napi_value KzgVerifyCellsAsync(napi_env env, napi_callback_info info) { return kzg_verify_cells_call(env, info, 1); }
 
+/* proofs == 0: (log2n, log2cell, offsets, index, cells); else (handle, log2cell, offsets, index, cells) */
+static napi_value kzg_recover_call(napi_env env, napi_callback_info info, int proofs, int async) {
+  ARGS(5); NEED_CTX(); BYTES(2, offs, lo); BYTES(3, idx, li); BYTES(4, cells, lb);
+  monomial_box* box = NULL; int32_t l2n = 0, log2c;
+  if (proofs) {
+    if (napi_get_value_external(env, argv[0], (void**)&box) != napi_ok || !box || !box->m) { napi_throw_type_error(env, NULL, "expected a live monomial setup handle"); return NULL; }
+    unsigned v = 0; p_nbls_kzg_monomial_log2n(box->m, &v); l2n = (int32_t)v;
+  } else if (napi_get_value_int32(env, argv[0], &l2n) != napi_ok) { napi_throw_type_error(env, NULL, "expected a number for log2n"); return NULL; }
+  if (napi_get_value_int32(env, argv[1], &log2c) != napi_ok) { napi_throw_type_error(env, NULL, "expected a number for log2cell"); return NULL; }
+  size_t n = 0;
+  int ok = l2n >= 1 && l2n <= 12 && log2c >= 0 && log2c <= l2n && !(((uintptr_t)offs | (uintptr_t)idx) % 4) && li % 4 == 0 && thr_offsets_ok(offs, lo, li / 4, &n) && n > 0 &&
+           ((const uint32_t*)offs)[0] == 0 && ((const uint32_t*)offs)[n] == li / 4 && lb == (li / 4 * 32) << log2c;
+  for (size_t i = 0; ok && i < n; i++) ok = ((const uint32_t*)offs)[i] <= ((const uint32_t*)offs)[i + 1];
+  if (!ok) { napi_throw_range_error(env, NULL, "log2n in 1 .. 12, log2cell in 0 .. log2n, blobs + 1 non-decreasing 32-bit offsets from 0, one 32-bit index and 32 << log2cell bytes per given cell"); return NULL; }
+  thr_job job; memset(&job, 0, sizeof job);
+  job.kind = proofs ? 14 : 13; job.op = l2n; job.mo = box ? box->m : NULL; job.g2 = log2c; job.offs = (const uint32_t*)offs; job.coffs = (const uint32_t*)idx; job.b = cells; job.n = n;
+  job.proofs_at = (n * 64) << l2n;
+  const size_t lout = job.proofs_at + (proofs ? n * ((size_t)2 << (l2n - log2c)) * 48 : 0);
+  napi_value vo = new_u8(env, lout, &job.out), vs = new_u8(env, n, (uint8_t**)&job.st); ALLOCATED(vo); ALLOCATED(vs);
+  memset(job.out, 0, lout); memset(job.st, 0, n);
+  return thr_run(env, &job, async, argv, 5, vo, vs);   /* the handle and every array stay referenced while the call runs */
+}
+static napi_value KzgRecoverCells(napi_env env, napi_callback_info info) { return kzg_recover_call(env, info, 0, 0); }
+static napi_value KzgRecoverCellsAsync(napi_env env, napi_callback_info info) { return kzg_recover_call(env, info, 0, 1); }
+static napi_value KzgRecoverCellsAndProofs(napi_env env, napi_callback_info info) { return kzg_recover_call(env, info, 1, 0); }
+static napi_value KzgRecoverCellsAndProofsAsync(napi_env env, napi_callback_info info) { return kzg_recover_call(env, info, 1, 1); }
+
 static napi_value ModuleInit(napi_env env, napi_value exports) {
   const char* path = getenv("NBLS_LIB");
   char buf[4096];
@@ -748,6 +783,7 @@ static napi_value ModuleInit(napi_env env, napi_value exports) {
   LOAD(nbls_fr_op_batch) LOAD(nbls_lagrange_at_zero) LOAD(nbls_g2_combine_shares) LOAD(nbls_g1_combine_shares) LOAD(nbls_g1_poly_eval) LOAD(nbls_g2_poly_eval) LOAD(nbls_kzg_verify_proofs) LOAD(nbls_kzg_verify_blobs)
   LOAD(nbls_kzg_setup_create) LOAD(nbls_kzg_setup_destroy) LOAD(nbls_kzg_setup_log2n) LOAD(nbls_kzg_commit_blobs) LOAD(nbls_kzg_compute_proofs) LOAD(nbls_kzg_compute_blob_proofs)
   LOAD(nbls_fr_ntt) LOAD(nbls_kzg_compute_cells) LOAD(nbls_kzg_monomial_create) LOAD(nbls_kzg_monomial_destroy) LOAD(nbls_kzg_monomial_log2n) LOAD(nbls_kzg_compute_cells_and_proofs) LOAD(nbls_kzg_verify_cells)
+  LOAD(nbls_kzg_recover_cells) LOAD(nbls_kzg_recover_cells_and_proofs)
   {   /* the ABI the addon was written against (include/nbls.h NBLS_ABI_VERSION): an older or newer library is refused at load instead of misread at run time */
     int (*abi)(void) = (int (*)(void))dlsym(lib, "nbls_abi_version");
     if (!abi || abi() != NBLS_ABI_VERSION) { napi_throw_error(env, NULL, "libnbls.so: ABI version differs from the one this addon was built for (include/nbls.h NBLS_ABI_VERSION)"); return exports; }
@@ -773,7 +809,9 @@ static napi_value ModuleInit(napi_env env, napi_value exports) {
     {"kzgComputeCellsAsync", 0, KzgComputeCellsAsync, 0, 0, 0, napi_enumerable, 0}, {"kzgMonomialCreate", 0, KzgMonomialCreate, 0, 0, 0, napi_enumerable, 0},
     {"kzgMonomialDestroy", 0, KzgMonomialDestroy, 0, 0, 0, napi_enumerable, 0}, {"kzgCellsAndProofs", 0, KzgCellsAndProofs, 0, 0, 0, napi_enumerable, 0},
     {"kzgCellsAndProofsAsync", 0, KzgCellsAndProofsAsync, 0, 0, 0, napi_enumerable, 0}, {"kzgVerifyCells", 0, KzgVerifyCells, 0, 0, 0, napi_enumerable, 0},
-    {"kzgVerifyCellsAsync", 0, KzgVerifyCellsAsync, 0, 0, 0, napi_enumerable, 0}};
+    {"kzgVerifyCellsAsync", 0, KzgVerifyCellsAsync, 0, 0, 0, napi_enumerable, 0}, {"kzgRecoverCells", 0, KzgRecoverCells, 0, 0, 0, napi_enumerable, 0},
+    {"kzgRecoverCellsAsync", 0, KzgRecoverCellsAsync, 0, 0, 0, napi_enumerable, 0}, {"kzgRecoverCellsAndProofs", 0, KzgRecoverCellsAndProofs, 0, 0, 0, napi_enumerable, 0},
+    {"kzgRecoverCellsAndProofsAsync", 0, KzgRecoverCellsAndProofsAsync, 0, 0, 0, napi_enumerable, 0}};
   napi_define_properties(env, exports, sizeof d / sizeof d[0], d);
   return exports;
 }
