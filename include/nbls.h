@@ -455,7 +455,7 @@ int  nbls_kzg_monomial_log2n(const nbls_kzg_monomial* m, unsigned* log2_n);
 /* compute_cells_and_kzg_proofs: the cells of nbls_kzg_compute_cells and, for every cell k, the proof  sum_i [q_i] [tau^i]G1  of the floor quotient q of p by the cell's
  * vanishing polynomial X^c - s_k (s_k = h_k^c) in coefficient form:  q_i = 0 for i >= N - c,  q_i = p_(i + c) + s_k q_(i + c)  downwards.  The coefficients stay on the device
  * after the transform; a kernel writes the 2 N / c quotient rows of every blob as big-endian scalars straight into the batched MSM's scalar array (one lane per chain of the
- * recurrence), the rows form of the batched MSM runs against the converted basis, then to-affine, compression and the closing kernel of the prover calls.  No FK20: 2 N / c sums
+ * recurrence), the rows form of the batched MSM runs against the converted basis, then to-affine, compression and the closing kernel of the prover calls.  No FK20 (see nbls_kzg_compute_cells_and_proofs_fk20): 2 N / c sums
  * of N points per blob.  The batched MSM takes 2^22 scalars and 2^20 rows a pass, so the call works through the blobs in chunks of whole blobs (8 mainnet blobs; fewer with
  * NBLS_TUNE_CELLS_CHUNK) on one stream; the bytes do not depend on the chunks.  out_proofs48: n * (2 N / c) compressed points, blob by blob, cell by cell; ZERO POINTS ARE VALID
  * (0xc0 00.., status 0: a polynomial of degree < c).  status[i] (may be NULL): 0, or NBLS_ST_NON_CANONICAL: that blob's cells are all-zero and its proofs 48 zero bytes each.
@@ -520,6 +520,28 @@ int nbls_kzg_recover_cells(nbls_ctx* ctx, unsigned log2_n, unsigned log2_cell, s
 int nbls_kzg_recover_cells_and_proofs(nbls_ctx* ctx, const nbls_kzg_monomial* monomial, unsigned log2_cell, size_t n, const uint32_t* cell_offsets,
                                       const uint32_t* cell_index, const uint8_t* cells, uint8_t* out_cells, uint8_t* out_proofs48 /* n * (2 N / c) * 48 */,
                                       int8_t* status /* n, may be NULL */);
+/* FK20 (Feist-Khovratovich): all 2 N / c cell proofs of a blob together, from two small passes of the batched MSM.  THE CONTRACT: for every input the two *_fk20 calls return
+ * byte for byte what nbls_kzg_compute_cells_and_proofs and nbls_kzg_recover_cells_and_proofs return -- cells, proofs, statuses, return codes: NBLS_ST_NON_CANONICAL (cells
+ * all-zero, proofs 48 zero bytes), NBLS_ST_BAD_CELLS, NBLS_ST_INCONSISTENT, zero points as 0xc0 00.. with status 0, status == NULL -- and make the same refusals, with the
+ * handle in the monomial's place and log2_cell taken from the handle.  With n' = N / c, M = 2 n', w_i = omega_M^rev(i) (the order of the Fr network's output):
+ *   proof_k = sum_(u <= n' - 2) [s_k^u] h_u,  h_u = sum_(j < c) sum_t [p_(j + c (t + u + 1))] [tau^(j + c t)]G1 = IDFT_M(y^)_(n' - 1 + u),
+ *   y^_i = sum_(j < c) [a^[j][i]] X^[j][i],  a^[j] = DFT_M of stripe j of the coefficients, X^[j] = DFT_M of stripe j of the basis reversed (both zero-padded: no wrap-around);
+ *   proof_k = sum_i [B[k][i]] y^_i with the fixed matrix B[k][i] = 1 / M sum_u s_k^u w_i^(-(n' - 1 + u)).
+ * No butterfly network over G1: pass A is M groups of c terms per blob (2 N scalars: 2^22 a pass), pass B M groups of M terms per blob (M^2 scalars a blob), 2^20 groups a
+ * pass either way: 256 mainnet blobs a chunk, fewer with NBLS_TUNE_CELLS_CHUNK (the same key; the bytes do not depend on it).  The sums of pass A stay projective between the
+ * passes (the identity is an ordinary point there).
+ * The handle holds the c M points X^ (converted as the batched MSM reads them, index i c + j) and B (split), about 4 MB at the mainnet size; created on the device from the
+ * monomial handle by ONE batched MSM of c M groups of n' - 1 terms and two kernels.  Lifetime and device rules: nbls_kzg_setup_create's.  nbls_kzg_fk20_create returns
+ * NBLS_EINVAL before any device work, with *out = NULL (as on every failure), for a missing pointer, a basis on another device, log2_cell > log2_n, log2_n + 1 - log2_cell > 12,
+ * or (2 N / c) * N > 2^22 (the size of the creation MSM, and the bound of the other form).  n' = 1 (every proof the zero point) and n' = 2 are legal. */
+typedef struct nbls_kzg_fk20 nbls_kzg_fk20;
+int  nbls_kzg_fk20_create(nbls_ctx* ctx, const nbls_kzg_monomial* monomial, unsigned log2_cell, nbls_kzg_fk20** out);
+void nbls_kzg_fk20_destroy(nbls_kzg_fk20* fk);
+int  nbls_kzg_fk20_params(const nbls_kzg_fk20* fk, unsigned* log2_n, unsigned* log2_cell);
+int  nbls_kzg_compute_cells_and_proofs_fk20(nbls_ctx* ctx, const nbls_kzg_fk20* fk, size_t n, const uint8_t* blobs, uint8_t* out_cells,
+                                            uint8_t* out_proofs48 /* n * (2 N / c) * 48 */, int8_t* status /* n, may be NULL */);
+int  nbls_kzg_recover_cells_and_proofs_fk20(nbls_ctx* ctx, const nbls_kzg_fk20* fk, size_t n, const uint32_t* cell_offsets, const uint32_t* cell_index, const uint8_t* cells,
+                                            uint8_t* out_cells, uint8_t* out_proofs48 /* n * (2 N / c) * 48 */, int8_t* status /* n, may be NULL */);
 
 /* One rank's share of a verifyBatch spread over several GPUs (one process per GPU): the Miller product of this rank's n
  * (key, message) pairs, times millerLoop(-G, S) on the ONE rank that passes the signature (d_sig96 = NULL elsewhere), WITHOUT the
@@ -553,6 +575,7 @@ const char* nbls_config_describe(void);   /* "NBLS_X=value(env|default) ...": ev
    nbls_g1_msm_rows, nbls_g2_msm_rows, NBLS_TUNE_MSMB_WINDOW / _BIG / _SLAB, the names "dbladd_g1" / "dbladd_g2" of nbls_extra_program_kernel, scratch slots 62 .. 63 (additions only, same version); then nbls_map_uniform_batch (addition only, same version); then nbls_fr_eval_roots, nbls_kzg_verify_proofs, nbls_kzg_verify_blobs, NBLS_ST_NON_CANONICAL, scratch slots 64 .. 68 (additions only, same version); then nbls_kzg_setup_create / _destroy / _log2n, nbls_fr_quotient_roots, nbls_kzg_commit_blobs, nbls_kzg_compute_proofs, nbls_kzg_compute_blob_proofs, scratch slots 69 .. 70 (additions only, same version); then nbls_fr_ntt, NBLS_NTT_*, nbls_kzg_compute_cells, nbls_kzg_monomial_create / _destroy / _log2n, nbls_kzg_compute_cells_and_proofs, NBLS_TUNE_CELLS_CHUNK, scratch slots 71 .. 73 (additions only, same version); then nbls_kzg_verify_cells, scratch slots 74 .. 78 (addition only, same version); then nbls_kzg_recover_cells, nbls_kzg_recover_cells_and_proofs, NBLS_ST_BAD_CELLS, NBLS_ST_INCONSISTENT, scratch slot 79 (additions only, same version); with the MSM calls ONE CHANGE TO EXISTING CALLS, same version: nbls_g1_msm / nbls_g2_msm write all-zero output bytes when the status is 1 (the sum is the
    zero point).  The bytes were unspecified there before (what the affine conversion made of a Z that is 0 mod p: in G1 a zero x and an arbitrary y); the status, and every output with status 0, are unchanged.
    nbls_msm_dev, which leaves its result on the device, is not changed.
+   Then nbls_kzg_fk20_create / _destroy / _params, nbls_kzg_compute_cells_and_proofs_fk20, nbls_kzg_recover_cells_and_proofs_fk20, the name "endo_g1" of nbls_extra_program_kernel, scratch slots 80 .. 81 (additions only, same version).
    4 (round 6): nbls_hw_queues, NBLS_TUNE_WIDE_MAX, NBLS_TUNE_H2C_NORM_MIN, NBLS_TUNE_INV_WIDE_MAX, NBLS_TUNE_LS_MAX / _LS2_MAX (additions only); the library sets GPU_MAX_HW_QUEUES = 22 at load when the variable is unset (see nbls_pool_init below).
    3 (round 5): nbls_program_kernel, nbls_pool_*, nbls_sign_batch_dev, NBLS_TUNE_VERIFY_* / _SAC_MAX / _PT_LS2_MAX (additions only); nbls_verify_batch_partial_dev writes d_out_fp12 even when it reports a zero point or a decode error
    (contents then meaningless); 2: *_partial take *d_partial as OUT only, *_partial_into added, nbls_tower_op_batch, nbls_verify_batch_msgs_dev.  The bindings check it at load. */

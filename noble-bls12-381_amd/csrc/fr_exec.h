@@ -444,6 +444,73 @@ NBLS_FR_HD void fr_cell_chain(const uint8_t* coef32, unsigned log2_n, unsigned l
   }
 }
 
+// ---- All cell proofs of a blob together (FK20, Feist-Khovratovich; kzg_fk20_*_kernel and nbls_sim_kzg_fk20_*).  N coefficients p_i, c per cell, n' = N / c, M = 2 n' cells,
+// w_i = omega_M^rev(i) = entry i of the table of the M roots (the order of every array below: position i stands for the exponent v = rev(i), which is what the network
+// above leaves from natural input, so no permutation pass exists):
+//   a^[j][i] = sum_{t < n'} p_(j + c t) w_i^t                              the per-blob scalars: the size-M transform of stripe j of the coefficients, zero-padded
+//   X^[j][i] = sum_{t <= n' - 2} [w_i^t] [tau^(j + c (n' - 2 - t))]G1      the handle's fixed points
+//   y^_i = sum_{j < c} [a^[j][i]] X^[j][i]                                 pass A;   h_u = IDFT_M(y^)_(n' - 1 + u), u <= n' - 2 (the cyclic convolution does not wrap)
+//   proof_k = sum_u [s_k^u] h_u = sum_i [B[k][i]] y^_i,  B[k][i] = 1 / M * sum_{u <= n' - 2} s_k^u w_i^(-(n' - 1 + u))      pass B
+// The scalars kernel: a workgroup of FR_FK_LANES lanes holds `stripes` transforms side by side in shared memory, stripe `sub` of the workgroup at a[(limb M + index) stripes +
+// sub] -- thread t = lane * stripes + sub, so consecutive threads touch consecutive words of LDS and consecutive stripes j of the output.  M / 2 < FR_FK_LANES: one butterfly
+// per lane and stage, 2 FR_FK_LANES / M stripes a workgroup; from M / 2 = FR_FK_LANES on one stripe a workgroup, M / (2 FR_FK_LANES) butterflies per lane.  Elements stay plain
+enum { FR_FK_LANES = 256 };
+struct FrFkLane { uint32_t sub, lane, lanes, stripes, blob, j, live; };   // live = 0: a stripe past the call's last (it loads zeros, meets every barrier and stores nothing)
+NBLS_FR_HD FrFkLane fr_fk_lane(unsigned log2_m, unsigned log2_cell, uint32_t n_blobs, uint32_t wg, uint32_t t) {
+  const uint32_t half = 1u << (log2_m - 1), lanes = half < FR_FK_LANES ? half : (uint32_t)FR_FK_LANES, stripes = FR_FK_LANES / lanes;
+  const uint32_t sub = t % stripes;
+  const uint64_t S = (uint64_t)wg * stripes + sub;
+  const uint32_t live = S < ((uint64_t)n_blobs << log2_cell) ? 1u : 0u;
+  return FrFkLane{sub, t / stripes, lanes, stripes, (uint32_t)(S >> log2_cell), (uint32_t)S & ((1u << log2_cell) - 1), live};
+}
+NBLS_FR_HD uint32_t fr_fk_workgroups(unsigned log2_m, unsigned log2_cell, uint32_t n_blobs) {
+  const uint32_t half = 1u << (log2_m - 1), stripes = half < FR_FK_LANES ? FR_FK_LANES / half : 1u;
+  return (uint32_t)((((uint64_t)n_blobs << log2_cell) + stripes - 1) / stripes);
+}
+NBLS_FR_HD uint32_t fr_fk_lds_words(unsigned log2_m) { const uint32_t M = 1u << log2_m; return FR_NL * (M < 2 * FR_FK_LANES ? 2 * FR_FK_LANES : M); }
+// the lane's elements of its stripe: index t < n' is p_(j + c t), the upper half zero.  coef32: the call's n x N coefficients
+NBLS_FR_HD void fr_fk_load(const uint8_t* coef32, unsigned log2_n, unsigned log2_cell, unsigned log2_m, const FrFkLane& L, uint32_t* a) {
+  const uint32_t M = 1u << log2_m, W = M * L.stripes;
+  const uint8_t* p = coef32 + (((uint64_t)L.blob * 32) << log2_n);
+  for (uint32_t i = L.lane; i < M; i += L.lanes) {
+    const Fr v = L.live && i < M / 2 ? fr_load_q(p + 32ull * (L.j + ((uint64_t)i << log2_cell))) : fr_zero();
+    fr_ntt_put(a + L.sub, W, i * L.stripes, v);
+  }
+}
+// fr_ntt_stage towards the values, on the lane's stripe
+NBLS_FR_HD void fr_fk_stage(uint32_t* a, unsigned log2_m, unsigned log2_len, const Fr* sroots, const FrFkLane& L) {
+  const uint32_t M = 1u << log2_m, W = M * L.stripes, len = 1u << log2_len;
+  const bool unit = log2_len + 1 == log2_m;
+  for (uint32_t b = L.lane; b < M / 2; b += L.lanes) {
+    const uint32_t blk = b >> log2_len, lo = (blk << (log2_len + 1)) | (b & (len - 1)), hi = lo + len;
+    const Fr u = fr_ntt_get(a + L.sub, W, lo * L.stripes), v = fr_ntt_get(a + L.sub, W, hi * L.stripes);
+    const Fr t = unit ? v : fr_mul(v, sroots[2 * blk]);
+    fr_ntt_put(a + L.sub, W, lo * L.stripes, fr_add(u, t));
+    fr_ntt_put(a + L.sub, W, hi * L.stripes, fr_sub(u, t));
+  }
+}
+// the lane's elements as big-endian scalars into pass A's array: out32[((blob M + i) c + j) * 32]
+NBLS_FR_HD void fr_fk_store(const uint32_t* a, unsigned log2_cell, unsigned log2_m, const FrFkLane& L, uint8_t* out32) {
+  const uint32_t M = 1u << log2_m, W = M * L.stripes;
+  if (!L.live) return;
+  for (uint32_t i = L.lane; i < M; i += L.lanes)
+    fr_store_q(fr_ntt_get(a + L.sub, W, i * L.stripes), out32 + 32ull * (((((uint64_t)L.blob << log2_m) + i) << log2_cell) + L.j));
+}
+// scalar idx of the handle's one MSM: group (i, j) = idx / (n' - 1), term e = idx % (n' - 1) -> w_i^e, plain (the points are gathered to match: tau^(j + c (n' - 2 - e)))
+NBLS_FR_HD Fr fr_fk_power(const Fr* sroots, unsigned log2_cell, unsigned log2_m, uint32_t idx) {
+  const uint32_t terms = (1u << (log2_m - 1)) - 1, g = idx / terms, e = idx - g * terms;
+  return fr_from_mont(fr_pow_index(sroots[g >> log2_cell], e, 12));
+}
+// B[k][i], plain.  With r = s_k / w_i:  sum_{u < n'} r^u = prod_{b < log2 n'} (1 + r^(2^b)), less the term r^(n' - 1) = r^n' / r;  w_i^(-(n' - 1)) = w_i^(-n') w_i.
+// isroots: the table of the inverse roots, entry i = 1 / w_i.  n' = 1: the sum is empty and the entry zero
+NBLS_FR_HD Fr fr_fk_matrix_entry(const Fr* sroots, const Fr* isroots, unsigned log2_m, uint32_t k, uint32_t i) {
+  const Fr one = fr_one(), w = sroots[i], wi = isroots[i], r = fr_mul(sroots[k], wi), ri = fr_mul(isroots[k], w);
+  Fr prod = one, rp = r, wp = wi;
+  for (unsigned b = 0; b + 1 < log2_m; b++) { prod = fr_mul(prod, fr_add(one, rp)); rp = fr_sqr(rp); wp = fr_sqr(wp); }
+  const Fr sum = fr_sub(prod, fr_mul(rp, ri));
+  return fr_from_mont(fr_mul(fr_mul(sum, fr_mul(wp, w)), fr_inv_pow2(log2_m)));
+}
+
 // ---- The interpolation of cells (verify_cell_kzg_proof_batch of EIP-7594; kzg_cell_interp_kernel and nbls_sim_kzg_cell_interp).  Cell k holds the values of p on the coset
 // h_k <omega_c> in bit-reversed order, h_k = g^rev(k), g = omega_2N; its interpolation polynomial has the coefficients
 //   a_(k,i) = h_k^(-i) / c * (the way back of the network above, size c, on the cell's values)_i.

@@ -1,4 +1,4 @@
-// kzg_common.cpp -- what the four KZG chains share (nbls_internal.h, the KZG section): -G2 and the blob challenges, the context's device tables, the two basis handles, the
+// kzg_common.cpp -- what the four KZG chains share (nbls_internal.h, the KZG section): -G2 and the blob challenges, the context's device tables, the two basis handles and the handle of the FK20 cell proofs, the
 // prover's closing stage, and the verifiers' frame (KzgFrame) around the combined check and the per-item pass, which kzg_pipeline and verify_cells_pipeline both run.
 #include "nbls_internal.h"
 #include "fr_exec.h"
@@ -130,9 +130,70 @@ EXPORT int nbls_kzg_monomial_log2n(const nbls_kzg_monomial* m, unsigned* log2_n)
 
 int kzg_proof_tail(nbls_ctx* ctx, const MsmbPlan& pl, const uint8_t* basis_pts, const uint8_t* rows, uint8_t* aff96, uint8_t* zero, const uint8_t* st_a, const uint8_t* st_b,
                    uint8_t* out48, uint8_t* status, hipStream_t s) {
-  const size_t n = pl.n_groups; int r;
-  if ((r = msm_rows_dev(ctx, pl, basis_pts, rows, aff96, zero, s)) || (r = run(ctx, P_G1_COMPRESS, n, {B(0, aff96, 96), B(2, out48, 48)}, s))) return r;
+  int r;
+  if ((r = msm_rows_dev(ctx, pl, basis_pts, rows, aff96, zero, s))) return r;
+  return kzg_proof_close(ctx, pl.n_groups, aff96, zero, st_a, st_b, out48, status, s);
+}
+int kzg_proof_close(nbls_ctx* ctx, size_t n, const uint8_t* aff96, const uint8_t* zero, const uint8_t* st_a, const uint8_t* st_b, uint8_t* out48, uint8_t* status, hipStream_t s) {
+  int r;
+  if ((r = run(ctx, P_G1_COMPRESS, n, {B(0, aff96, 96), B(2, out48, 48)}, s))) return r;
   LAUNCHCHK(nbls_kzg_prove_tail_launch((unsigned)n, zero, st_a, st_b, out48, status, s));
+  return NBLS_OK;
+}
+
+// ---- the handle of the FK20 cell proofs (include/nbls.h has the contract, fr_exec.h the identities).  On the device throughout: the monomial basis gathered into the order of
+// the one MSM's terms, the powers of the roots as its scalars, c M groups of n' - 1 terms in one pass, its sums kept projective with their endomorphism images; the matrix B
+// from a kernel, split once.  The temporaries are the call's (HostIO); the MSM runs on the batched MSM's two slots
+static int fk20_build(nbls_ctx* ctx, const nbls_kzg_monomial* mono, nbls_kzg_fk20* h) {
+  const unsigned L = h->log2_n, lc = h->log2_cell, lm = L + 1 - lc;
+  const size_t c = (size_t)1 << lc, M = (size_t)1 << lm, terms = M / 2 - 1, p = 3 * RAW, groups = c * M;
+  LOCKED(ctx);
+  HostIO io{ctx};
+  // gathered point q = j (n' - 1) + e is tau^(j + c (n' - 2 - e)): the scalar index modulo c (n' - 1) then names its point
+  std::vector<uint32_t> idx(c * terms);
+  for (size_t j = 0; j < c; j++) for (size_t e = 0; e < terms; e++) idx[j * terms + e] = (uint32_t)(j + c * (terms - 1 - e));
+  void *d_idx = io.alloc(idx.size() * 4), *Q = io.alloc(idx.size() * 2 * p), *K = io.alloc(groups * terms * 32), *Bm = io.alloc(M * M * 32);
+  if (!d_idx || !Q || !K || !Bm) return NBLS_EHIP;
+  const uint8_t *sroots, *isroots; MsmbPlan pl; int r;
+  HIPCHK(hipMalloc(&h->xhat, groups * 2 * p));
+  HIPCHK(hipMalloc(&h->bsplit, M * M * 64));
+  HIPCHK(hipMemcpyAsync(d_idx, idx.data(), idx.size() * 4, hipMemcpyHostToDevice, s));
+  if ((r = kzg_table(ctx, KZG_ROOTS, lm, 0, s, &sroots)) || (r = kzg_table(ctx, KZG_INV_ROOTS, lm, 0, s, &isroots)) || (r = msm_map_dev_plan(ctx, terms, c * terms, 0, 0, groups, &pl)))
+    return r;
+  LAUNCHCHK(nbls_msm_gather_launch(idx.size(), (unsigned)(2 * p), (const uint32_t*)d_idx, mono->pts, Q, s));
+  LAUNCHCHK(nbls_kzg_fk20_powers_launch(L, lc, sroots, K, s));
+  LAUNCHCHK(nbls_kzg_fk20_matrix_launch(lm, sroots, isroots, Bm, s));
+  if ((r = msm_split_scalars(ctx, M * M, (const uint8_t*)Bm, h->bsplit, s)) || (r = msm_map_dev(ctx, pl, (const uint8_t*)Q, (const uint8_t*)K, nullptr, nullptr, nullptr, h->xhat, s)))
+    return r;
+  HIPCHK(hipStreamSynchronize(s));   // (idx is read by the copy until here; an error return waits in ~HostIO)
+  return NBLS_OK;
+}
+EXPORT int nbls_kzg_fk20_create(nbls_ctx* ctx, const nbls_kzg_monomial* mono, unsigned log2_cell, nbls_kzg_fk20** out) {
+  WHOLE_CALL(ctx);
+  if (out) *out = nullptr;
+  if (!ctx || !mono || !out || mono->device != ctx->device || log2_cell > mono->log2_n) return NBLS_EINVAL;
+  const unsigned L = mono->log2_n;
+  // the M groups of M terms of one blob's second pass fit a pass of the batched MSM wherever the handle's own MSM does: (2 N / c) N scalars
+  if (L + 1 - log2_cell > 12 || ((size_t)2 << (2 * L - log2_cell)) > MSMB_MAX_ITEMS) return NBLS_EINVAL;
+  nbls_kzg_fk20* h = new (std::nothrow) nbls_kzg_fk20;
+  if (!h) return NBLS_EHIP;
+  h->device = ctx->device; h->log2_n = L; h->log2_cell = log2_cell;
+  const int r = log2_cell == L ? NBLS_OK : fk20_build(ctx, mono, h);   // n' = 1: no sum has a term, every proof is the zero point
+  if (r) { nbls_kzg_fk20_destroy(h); return r; }
+  *out = h;
+  return NBLS_OK;
+}
+EXPORT void nbls_kzg_fk20_destroy(nbls_kzg_fk20* h) {
+  if (!h) return;
+  int cur = 0;
+  const bool restore = hipGetDevice(&cur) == hipSuccess;
+  if (hipSetDevice(h->device) == hipSuccess) { (void)hipFree(h->xhat); (void)hipFree(h->bsplit); }
+  if (restore) (void)hipSetDevice(cur);
+  delete h;
+}
+EXPORT int nbls_kzg_fk20_params(const nbls_kzg_fk20* h, unsigned* log2_n, unsigned* log2_cell) {
+  if (!h || !log2_n || !log2_cell) return NBLS_EINVAL;
+  *log2_n = h->log2_n; *log2_cell = h->log2_cell;
   return NBLS_OK;
 }
 

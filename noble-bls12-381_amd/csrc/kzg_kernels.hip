@@ -165,6 +165,36 @@ __global__ void __launch_bounds__(256) kzg_cell_rows_kernel(u32 log2_n, u32 log2
   if (j == 0) row_st[row] = blob_st[blob];
 }
 
+// ---- All cell proofs of a blob together (FK20: nbls_kzg_fk20_create and the two *_fk20 calls, pipelines_kzg_cells.cpp); fr_exec.h has the identities and the arithmetic.
+// The per-blob scalars of pass A: the size-M transform of every zero-padded stripe of the coefficients, FR_FK_LANES lanes a workgroup, its stripes side by side in dynamic LDS
+// (16 KB up to M = 512, 32 M bytes above), one barrier per stage.  coef32: n x N coefficients (all-zero for a refused blob: zero scalars); out32: n x M x c scalars, [blob][i][j]
+__global__ void __launch_bounds__(FR_FK_LANES) kzg_fk20_scalars_kernel(u32 log2_n, u32 log2_cell, u32 n, const uint8_t* __restrict__ coef32, const Fr* __restrict__ sroots,
+                                                                       uint8_t* __restrict__ out32) {
+  extern __shared__ u32 a[];
+  const u32 lm = log2_n + 1 - log2_cell;
+  const FrFkLane L = fr_fk_lane(lm, log2_cell, n, blockIdx.x, threadIdx.x);
+  fr_fk_load(coef32, log2_n, log2_cell, lm, L, a);
+  __syncthreads();
+  for (u32 ll = lm; ll-- > 0;) { fr_fk_stage(a, lm, ll, sroots, L); __syncthreads(); }
+  fr_fk_store(a, log2_cell, lm, L, out32);
+}
+// row_st[blob * M + k] = blob_st[blob]: what the closing kernel reads per proof
+__global__ void kzg_fk20_row_status_kernel(u32 log2_m, u32 n, const int8_t* __restrict__ blob_st, int8_t* __restrict__ row_st) {
+  const u64 gid = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+  if (gid < ((u64)n << log2_m)) row_st[gid] = blob_st[gid >> log2_m];
+}
+// the scalars of the handle's one MSM, one lane each: c M groups of n' - 1 powers of w_i
+__global__ void kzg_fk20_powers_kernel(u32 log2_cell, u32 log2_m, u32 count, const Fr* __restrict__ sroots, uint8_t* __restrict__ out32) {
+  const u32 idx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx < count) fr_store_q(fr_fk_power(sroots, log2_cell, log2_m, idx), out32 + 32ull * idx);
+}
+// the projection matrix B, one lane per entry: out32[(k M + i) * 32]
+__global__ void kzg_fk20_matrix_kernel(u32 log2_m, const Fr* __restrict__ sroots, const Fr* __restrict__ isroots, uint8_t* __restrict__ out32) {
+  const u32 idx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >> (2 * log2_m)) return;
+  fr_store_q(fr_fk_matrix_entry(sroots, isroots, log2_m, idx >> log2_m, idx & ((1u << log2_m) - 1)), out32 + 32ull * idx);
+}
+
 // ---- The recovery of blobs from at least half of their cells (nbls_kzg_recover_cells, pipelines_kzg_cells.cpp); fr_exec.h has the route and the arithmetic.
 // The Z values of n blobs, one lane per (blob, value): value v < M = 2^log2_m is Zs(s_v), value M + j the inverse 1 / Zs(7^c s_j) of block j -- M / 2 inversions a blob, none
 // per element.  slot: n x M (the host's slot maps); pre[blob] != 0: the index set was refused, nothing is written; zv: n x 3 M / 2 values, Montgomery form
@@ -517,6 +547,29 @@ int nbls_kzg_items_launch(unsigned n, const void* dst, const void* w32, const vo
   if (!n) return 0;
   const int e = launch_1d(kzg_items_kernel, n, 64, 0, stream, n, dst, w32, z32, y32, yst, gen96, aff, s1, s2, t, pre);
   return e ? e : launch_1d(kzg_sum_kernel, EV, EV, 0, stream, n, t, (uint8_t*)s2 + 64ull * n);
+}
+// the scalars of pass A for n blobs (log2_m = log2_n + 1 - log2_cell <= 11: at most 64 KB of LDS; coef32 and out32 16-byte aligned)
+int nbls_kzg_fk20_scalars_launch(unsigned log2_n, unsigned log2_cell, unsigned n, const void* coef32, const void* sroots, void* out32, hipStream_t stream) {
+  if (!n) return 0;
+  if (log2_n < 1 || log2_n > 12 || log2_cell > log2_n || log2_n + 1 - log2_cell > 11 || (((uintptr_t)coef32 | (uintptr_t)out32) & 15)) return (int)hipErrorInvalidValue;
+  const unsigned lm = log2_n + 1 - log2_cell;
+  return launch_1d(kzg_fk20_scalars_kernel, (u64)fr_fk_workgroups(lm, log2_cell, n) * FR_FK_LANES, FR_FK_LANES, fr_fk_lds_words(lm) * 4, stream, log2_n, log2_cell, n, coef32, sroots,
+                   out32);
+}
+int nbls_kzg_fk20_row_status_launch(unsigned log2_m, unsigned n, const void* blob_st, void* row_st, hipStream_t stream) {
+  return launch_1d(kzg_fk20_row_status_kernel, (u64)n << log2_m, 256, 0, stream, log2_m, n, blob_st, row_st);
+}
+// the c M (n' - 1) scalars of the handle's MSM (none for n' = 1)
+int nbls_kzg_fk20_powers_launch(unsigned log2_n, unsigned log2_cell, const void* sroots, void* out32, hipStream_t stream) {
+  if (log2_n < 1 || log2_n > 12 || log2_cell > log2_n || log2_n + 1 - log2_cell > 11 || ((uintptr_t)out32 & 15)) return (int)hipErrorInvalidValue;
+  const unsigned lm = log2_n + 1 - log2_cell;
+  const u64 count = ((u64)1 << (log2_cell + lm)) * ((1u << (lm - 1)) - 1);
+  if (count >> 32) return (int)hipErrorInvalidValue;
+  return launch_1d(kzg_fk20_powers_kernel, count, 256, 0, stream, log2_cell, lm, (u32)count, sroots, out32);
+}
+int nbls_kzg_fk20_matrix_launch(unsigned log2_m, const void* sroots, const void* isroots, void* out32, hipStream_t stream) {
+  if (log2_m < 1 || log2_m > 11 || ((uintptr_t)out32 & 15)) return (int)hipErrorInvalidValue;
+  return launch_1d(kzg_fk20_matrix_kernel, (u64)1 << (2 * log2_m), 256, 0, stream, log2_m, sroots, isroots, out32);
 }
 // the table of the 2^log2_m inverse shifts of (log2_n, log2_cell = log2_n + 1 - log2_m)
 int nbls_kzg_cell_ishifts_launch(unsigned log2_n, unsigned log2_m, void* table, hipStream_t stream) {

@@ -52,6 +52,8 @@ int nbls_poly_status_launch(unsigned n, unsigned out_bytes, const uint32_t* grou
 // msm_kernels.hip
 int nbls_msm_keys_launch(unsigned m, unsigned dims, unsigned nwin, unsigned c, unsigned i0, unsigned g0, unsigned ngroups, unsigned n_pts, const uint32_t* off,
                          const void* scalars, uint32_t* keys, uint32_t* vals, hipStream_t stream);
+int nbls_msm_keys_map_launch(unsigned m, unsigned dims, unsigned nwin, unsigned c, unsigned i0, unsigned g0, unsigned ngroups, unsigned n_pts, unsigned glen, unsigned pt_block,
+                             unsigned k_mod, const void* scalars, uint32_t* keys, uint32_t* vals, hipStream_t stream);
 int nbls_msm_decompose_launch(unsigned n, unsigned dims, const void* scalars, void* out, hipStream_t stream);
 int nbls_msm_sac_launch(unsigned n, const void* scalars, void* out, hipStream_t stream);
 int nbls_msm_sort_launch(void* temp, size_t* temp_bytes, const uint32_t* keys_in, uint32_t* keys_out, const uint32_t* vals_in, uint32_t* vals_out, size_t m, int key_bits,
@@ -78,6 +80,10 @@ int nbls_kzg_ntt_launch(unsigned log2_n, unsigned mode, unsigned n, const void* 
                         void* out32, void* coef32, void* status, hipStream_t stream);
 int nbls_kzg_cell_rows_launch(unsigned log2_n, unsigned log2_cell, unsigned n, const void* coef32, const void* sroots, const void* blob_st, void* out_q32, void* row_st,
                               hipStream_t stream);
+int nbls_kzg_fk20_scalars_launch(unsigned log2_n, unsigned log2_cell, unsigned n, const void* coef32, const void* sroots, void* out32, hipStream_t stream);
+int nbls_kzg_fk20_row_status_launch(unsigned log2_m, unsigned n, const void* blob_st, void* row_st, hipStream_t stream);
+int nbls_kzg_fk20_powers_launch(unsigned log2_n, unsigned log2_cell, const void* sroots, void* out32, hipStream_t stream);
+int nbls_kzg_fk20_matrix_launch(unsigned log2_m, const void* sroots, const void* isroots, void* out32, hipStream_t stream);
 int nbls_kzg_cell_ishifts_launch(unsigned log2_n, unsigned log2_m, void* table, hipStream_t stream);
 int nbls_kzg_recover_launch(unsigned log2_n, unsigned log2_cell, unsigned n, const void* cells, const uint32_t* slot, const void* pre, const void* sroots, const void* consts,
                             const void* roots, const void* iroots, void* zv, void* out32, void* coef32, void* status, hipStream_t stream);

@@ -24,15 +24,18 @@ using namespace nbls;
 // scalars are 32-byte big-endian integers).  The item's group is found in the call's offsets (off[0 .. ngroups], relative to the first scalar; empty groups own nothing), or
 // is i / n_pts in the rows form (n_pts > 0), where the point is i % n_pts and off is not read.  keys[w * m + e] = ((group - g0) * nwin + w) << c | digit_w,
 // vals[w * m + e] = point * dims + d (the index of the converted point).  The single sum: i0 = g0 = 0 and n_pts = its points, so group 0, key = w << c | digit_w, val = e.
-__global__ void msm_keys_kernel(u32 m, u32 dims, u32 nwin, u32 c, u32 i0, u32 g0, u32 ngroups, u32 n_pts, const u32* __restrict__ off, const uint8_t* __restrict__ scalars,
-                                u32* __restrict__ keys, u32* __restrict__ vals) {
+// The rows form is the case glen = n_pts, pt_block = k_mod = 0 of a wider map (the two passes of the FK20 cell proofs, pipelines_kzg_cells.cpp): the group is i / glen, the
+// point i % n_pts, moved on by n_pts for every pt_block scalars (pt_block > 0: block b of the scalars meets points b n_pts ..), and the scalar read is i % k_mod (k_mod > 0: one
+// array of k_mod scalars serves every block)
+__global__ void msm_keys_kernel(u32 m, u32 dims, u32 nwin, u32 c, u32 i0, u32 g0, u32 ngroups, u32 n_pts, u32 glen, u32 pt_block, u32 k_mod, const u32* __restrict__ off,
+                                const uint8_t* __restrict__ scalars, u32* __restrict__ keys, u32* __restrict__ vals) {
   const u32 e = blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= m) return;
   const u32 i = i0 + e / dims, d = e % dims;
   u32 g, pt;
-  if (n_pts) { g = i / n_pts; pt = i - g * n_pts; }
+  if (n_pts) { g = i / glen; pt = i % n_pts + (pt_block ? (i / pt_block) * n_pts : 0u); }
   else { g = group_search(off, g0, ngroups, i); pt = i; }   // off[g0] <= i holds for every item of the slab
-  const u32* k = (const u32*)(scalars + 32ull * ((u64)i * dims + d));
+  const u32* k = (const u32*)(scalars + 32ull * ((u64)(k_mod ? i % k_mod : i) * dims + d));
   u32 w[9];
 #pragma unroll
   for (int j = 0; j < 8; j++) w[j] = __builtin_bswap32(k[7 - j]);
@@ -151,7 +154,13 @@ __global__ void msm_bitsel_kernel(u64 count, u32 q, u32 c, const uint4* __restri
 extern "C" {
 int nbls_msm_keys_launch(unsigned m, unsigned dims, unsigned nwin, unsigned c, unsigned i0, unsigned g0, unsigned ngroups, unsigned n_pts, const uint32_t* off,
                          const void* scalars, uint32_t* keys, uint32_t* vals, hipStream_t stream) {
-  return launch_1d(msm_keys_kernel, m, 256, 0, stream, m, dims, nwin, c, i0, g0, ngroups, n_pts, off, scalars, keys, vals);
+  return launch_1d(msm_keys_kernel, m, 256, 0, stream, m, dims, nwin, c, i0, g0, ngroups, n_pts, n_pts, 0u, 0u, off, scalars, keys, vals);
+}
+// the wider map of the rows form (msm_keys_kernel): n_pts, glen > 0
+int nbls_msm_keys_map_launch(unsigned m, unsigned dims, unsigned nwin, unsigned c, unsigned i0, unsigned g0, unsigned ngroups, unsigned n_pts, unsigned glen, unsigned pt_block,
+                             unsigned k_mod, const void* scalars, uint32_t* keys, uint32_t* vals, hipStream_t stream) {
+  if (!n_pts || !glen) return (int)hipErrorInvalidValue;
+  return launch_1d(msm_keys_kernel, m, 256, 0, stream, m, dims, nwin, c, i0, g0, ngroups, n_pts, glen, pt_block, k_mod, (const uint32_t*)nullptr, scalars, keys, vals);
 }
 int nbls_msm_decompose_launch(unsigned n, unsigned dims, const void* scalars, void* out, hipStream_t stream) {
   return launch_1d(msm_decompose_kernel, n, 256, 0, stream, n, dims, scalars, out);

@@ -9,6 +9,7 @@
 #include <cstring>
 #include <mutex>
 #include <vector>
+#include <initializer_list>
 #include "nbls.h"
 #include "programs.h"
 #include "consts_gen.h"
@@ -92,9 +93,12 @@ enum Slot {
   // cells_pipeline's recovery front end (nbls_kzg_recover_cells*, pipelines_kzg_cells.cpp): per blob the 2 N / c values of the missing cells' vanishing polynomial and the
   // N / c inverses of its values on the coset of 7; the rest of the call is on cells_pipeline's slots (SB_KZGC_COEFS holds a half's coefficients, then the blob's)
   SB_KZGR_Z = 79,
+  // cells_pipeline's FK20 proofs loop (nbls_kzg_*_cells_and_proofs_fk20, pipelines_kzg_cells.cpp): one chunk's scalars of pass A and the rows' statuses | one chunk's sums of
+  // pass A in the converted projective form, the points of pass B.  They stand where the quotient rows (SB_KZGC_ROWS) stand in the other form
+  SB_KZGF_SCALARS = 80, SB_KZGF_POINTS = 81,
   NSB
 };
-static_assert(NSB == 80, "sb[] indices do not shift");
+static_assert(NSB == 82, "sb[] indices do not shift");
 constexpr SlotMask slot_bit(int i) { return (SlotMask)1 << i; }
 template <typename... S> constexpr SlotMask slots(S... s) { return (slot_bit(s) | ...); }
 // one instance of dev_decompress: three arrays of field elements and the exponentiation table
@@ -125,6 +129,7 @@ constexpr SlotMask M_KZG_OWN = slots(SB_STAGED, SB_KZG_POINTS, SB_KZG_SCALARS, S
 constexpr SlotMask M_KZGP_OWN = slots(SB_STAGED, SB_KZGP_SCALARS, SB_KZGP_OUT);   // kzg_prove_pipeline: what outlives the batched MSM it calls (msm_rows_dev, on M_MSMB_OWN)
 constexpr SlotMask M_KZGC_OWN = slots(SB_STAGED, SB_KZGC_COEFS, SB_KZGC_ROWS, SB_KZGC_OUT);   // cells_pipeline: what outlives the batched MSM of every chunk
 constexpr SlotMask M_KZGR_OWN = M_KZGC_OWN | slots(SB_KZGR_Z);   // cells_pipeline behind the recovery front end: the Z values are read before the first chunk's MSM and not again
+constexpr SlotMask M_KZGF_OWN = (M_KZGR_OWN & ~slot_bit(SB_KZGC_ROWS)) | slots(SB_KZGF_SCALARS, SB_KZGF_POINTS);   // cells_pipeline with the FK20 proofs loop, behind either front end: what outlives the two MSM passes of every chunk
 constexpr SlotMask M_KZGV_OWN = slots(SB_STAGED, SB_KZGV_POINTS, SB_KZGV_SCALARS, SB_KZGV_PAIRS, SB_KZGV_OUT, SB_KZGV_ITEMS);   // verify_cells_pipeline: what outlives the decoder, the MSMs, the batched MSM and the ladder it calls
 constexpr SlotMask M_MSMB_OWN = slots(SB_MSMB_CALL, SB_MSMB_SLAB);   // msm_batch_pipeline: what outlives the dev_msm calls of its big groups
 // what runs side by side
@@ -150,6 +155,9 @@ static_assert(!((M_KZGC_OWN & ~slot_bit(SB_STAGED)) & (M_KZGP_OWN | M_KZG_OWN | 
 static_assert(!(M_KZGR_OWN & (M_MSMB_OWN | DEC_MAIN.mask())), "the recovery front end of cells_pipeline: as cells_pipeline, whose chunks it runs");
 static_assert(!(slot_bit(SB_KZGR_Z) & (M_KZGC_OWN | M_KZGV_OWN | M_KZGP_OWN | M_KZG_OWN | M_POLY_OWN | M_THR_OWN | M_RLC_MAIN | M_RLC_SIDE | M_RLC_SIDE2 | M_VB_MAIN | M_LADDER | MSM_MAIN.mask() | MSM_RLC.mask())),
               "the recovery front end keeps to a slot of its own");
+static_assert(!(M_KZGF_OWN & (M_MSMB_OWN | DEC_MAIN.mask())), "the FK20 proofs loop: both passes run on the batched MSM's two slots, chunk after chunk, while the scalars of pass A and the points of pass B are held");
+static_assert(!(slots(SB_KZGF_SCALARS, SB_KZGF_POINTS) & (M_KZGR_OWN | M_KZGV_OWN | M_KZGP_OWN | M_KZG_OWN | M_POLY_OWN | M_THR_OWN | M_RLC_MAIN | M_RLC_SIDE | M_RLC_SIDE2 | M_VB_MAIN | M_LADDER | MSM_MAIN.mask() | MSM_RLC.mask())),
+              "the FK20 proofs loop keeps to slots of its own");
 static_assert(!(M_KZGV_OWN & (DEC_MAIN.mask() | MSM_RLC.mask() | M_LADDER | M_MSMB_OWN)),
               "verify_cells_pipeline: the decoder, the MSMs (on the slots of MSM_RLC: MSM_MAIN holds SB_STAGED), the batched MSM and the ladder of the per-cell pass regrow their slots while the call holds the staged block and its own");
 static_assert(!((M_KZGV_OWN & ~slot_bit(SB_STAGED)) & (M_KZGC_OWN | M_KZGP_OWN | M_KZG_OWN | M_POLY_OWN | M_THR_OWN | M_RLC_MAIN | M_RLC_SIDE | M_RLC_SIDE2 | M_VB_MAIN | MSM_MAIN.mask())),
@@ -429,6 +437,7 @@ static const size_t MSMB_MAX_ITEMS = (size_t)1 << 22, MSMB_MAX_GROUPS = (size_t)
 struct MsmbPart { size_t g0, g1; bool big; int key_bits; };   // groups [g0, g1): one slab (and the bits of its keys), or one big group
 struct MsmbPlan {
   bool g2 = false, split = false; unsigned nbits = 0, dims = 1, kbits = 0, c = 0;
+  size_t glen = 0, pt_block = 0, k_mod = 0;   // the wider map of the rows form (msm_map_dev_plan); glen = 0: the rows form itself, or offsets
   size_t n_groups = 0, n_pts = 0, nwin = 0, J = 0, jtop = 0, maxM = 0, max_ngs = 0, sort_bytes = 0, scan_bytes = 0;
   size_t s_cnt = 0, s_tmp = 0, s_P = 0, s_bk = 0, s_G = 0, s_Gh = 0, s_acc = 0, s_N = 0, s_NI = 0, slab_bytes = 0;
   std::vector<MsmbPart> parts;
@@ -436,6 +445,11 @@ struct MsmbPlan {
 };
 int msm_rows_dev_plan(nbls_ctx* ctx, size_t n_pts, size_t n_rows, MsmbPlan* pl);
 int msm_rows_dev(nbls_ctx* ctx, const MsmbPlan& pl, const uint8_t* conv_pts, const uint8_t* d_scalars, uint8_t* d_out96, uint8_t* d_zero, hipStream_t s);
+// the rows form with the group length, the point period and the scalars' period apart (pipelines_msm.cpp has the map): the passes of the FK20 cell proofs
+int msm_map_dev_plan(nbls_ctx* ctx, size_t glen, size_t period, size_t pt_block, size_t k_mod, size_t n_groups, MsmbPlan* pl);
+void msm_map_plans_settle(nbls_ctx* ctx, std::initializer_list<MsmbPlan*> plans);
+int msm_map_dev(nbls_ctx* ctx, const MsmbPlan& pl, const uint8_t* conv_pts, const uint8_t* d_scalars, const uint8_t* split, uint8_t* d_out96, uint8_t* d_zero, uint8_t* conv, hipStream_t s);
+int msm_split_scalars(nbls_ctx* ctx, size_t n, const uint8_t* d_scalars, uint8_t* split, hipStream_t s);
 // ---- KZG (kzg_common.cpp): what pipelines_kzg.cpp, pipelines_kzg_prove.cpp, pipelines_kzg_cells.cpp and pipelines_kzg_verify_cells.cpp share
 static const size_t KZG_MAX_ELEMS = (size_t)1 << 24;   // field elements per call of the Fr entry points and of the calls that take whole blobs
 // -G2 in affine wire bytes; the challenges of n blobs on host threads
@@ -450,10 +464,15 @@ int kzg_table(nbls_ctx* ctx, KzgTable kind, unsigned log2_n, unsigned log2_cell,
 struct KzgBasis { int device = 0; unsigned log2_n = 0; uint8_t* pts = nullptr; };
 struct nbls_kzg_setup : KzgBasis {};
 struct nbls_kzg_monomial : KzgBasis {};
+// the handle of the FK20 cell proofs (fr_exec.h has the identities): xhat = the c M fixed points X^[j][i] at index i c + j, in the converted form the batched MSM reads;
+// bsplit = the M x M projection matrix B, row after row, split as msm_split_scalars leaves it (2 x 32 bytes an entry).  Both NULL where n' = N / c = 1: every proof is the zero point
+struct nbls_kzg_fk20 { int device = 0; unsigned log2_n = 0, log2_cell = 0; uint8_t *xhat = nullptr, *bsplit = nullptr; };
 // the prover's closing stage: pl.n_groups rows of scalars against the basis -> affine sums (aff96, zero) -> compressed to out48 -> closed by kzg_prove_tail_kernel with the
 // statuses st_a, st_b (either may be NULL)
 int kzg_proof_tail(nbls_ctx* ctx, const MsmbPlan& pl, const uint8_t* basis_pts, const uint8_t* rows, uint8_t* aff96, uint8_t* zero, const uint8_t* st_a, const uint8_t* st_b,
                    uint8_t* out48, uint8_t* status, hipStream_t s);
+// what follows the sums in kzg_proof_tail, for a caller whose n affine sums and zero flags come from elsewhere (the second pass of the FK20 cell proofs)
+int kzg_proof_close(nbls_ctx* ctx, size_t n, const uint8_t* aff96, const uint8_t* zero, const uint8_t* st_a, const uint8_t* st_b, uint8_t* out48, uint8_t* status, hipStream_t s);
 // The frame of a verifier's call: the seed, the three staged parts [tau^c]G2 | -G2 | seed, the pairs block and the read-back block (kzg_frame.h has their formats), the opening
 // launches, the combined check with its verdict and the per-item pass around the summands.  The caller keeps its staged inputs, its points and scalars blocks, its item
 // kernels, the four sums that fill PT2 / A_ZERO, B3 and BST, and the three summands of every X_i (P3, ST3).  A call: kzg_seed (in front of DEV_ENTER) -> stage (among the caller's

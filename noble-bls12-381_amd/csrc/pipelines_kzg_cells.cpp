@@ -12,7 +12,11 @@
 //            -> D2H copy: cells | proofs | statuses
 // nbls_kzg_recover_cells / _and_proofs (recover_cells_and_kzg_proofs) are the same chain behind another front end: from at least half of every blob's cells to the same
 // coefficients buffer, by size-N transforms only (fr_exec.h has the route), then the same proofs loop.
-// Scratch slots: SB_STAGED and SB_KZGC_* (nbls_internal.h, M_KZGC_OWN), the recovery's Z values on SB_KZGR_Z (M_KZGR_OWN); the MSM on SB_MSMB_*.
+// The *_fk20 calls are the same chain again with another proofs loop (FK20; fr_exec.h has the identities, the handle nbls_kzg_fk20 is kzg_common.cpp's): per chunk of whole
+// blobs (256 mainnet blobs) kzg_fk20_scalars_kernel writes the transforms of the coefficients' stripes as pass A's scalars -> msm_map_dev against the handle's points: M
+// groups of c terms a blob, the sums left projective with their endomorphism images -> msm_map_dev with those sums as points and the handle's matrix as scalars: M groups of
+// M terms a blob -> kzg_proof_close.  n' = N / c = 1: no pass, every proof of an accepted blob is the zero point.
+// Scratch slots: SB_STAGED and SB_KZGC_* (nbls_internal.h, M_KZGC_OWN), the recovery's Z values on SB_KZGR_Z (M_KZGR_OWN), the FK20 loop's on SB_KZGF_* (M_KZGF_OWN); the MSM on SB_MSMB_*.
 #include "nbls_internal.h"
 // (fr_omega runs on the host here: its exponent's shift asks for an unrolling that the host pass declines, which is all the warning says)
 #pragma clang diagnostic ignored "-Wpass-failed"
@@ -36,9 +40,9 @@ EXPORT int nbls_fr_ntt(nbls_ctx* ctx, unsigned log2_n, int dir, size_t n, const 
   return io.fetch_to(O, out32, qb, status, n);
 }
 
-// mono == NULL: nbls_kzg_compute_cells (out_proofs unused).  rec != NULL: the recovery front end -- the blobs come from subsets of their cells (blobs unused)
+// mono == NULL and fk == NULL: nbls_kzg_compute_cells (out_proofs unused).  fk != NULL: the FK20 proofs loop.  rec != NULL: the recovery front end -- the blobs come from subsets of their cells (blobs unused)
 struct RecoverIn { const uint32_t *offsets, *index; const uint8_t* cells; };
-struct CellsIn { unsigned log2_n, log2_cell; size_t n; const uint8_t* blobs; const nbls_kzg_monomial* mono; uint8_t *out_cells, *out_proofs; const RecoverIn* rec; };
+struct CellsIn { unsigned log2_n, log2_cell; size_t n; const uint8_t* blobs; const nbls_kzg_monomial* mono; uint8_t *out_cells, *out_proofs; const RecoverIn* rec; const nbls_kzg_fk20* fk = nullptr; };
 
 // Two front ends to one coefficients buffer, one proofs loop behind them.  From whole blobs: kzg_ntt_kernel's cells mode.  From cells (rec): the index sets are checked here,
 // on the host, before the copy -- a refused blob (NBLS_ST_BAD_CELLS) sends an empty slot map and none of its cells --, then kzg_recover_z_kernel and kzg_recover_kernel leave the
@@ -46,7 +50,8 @@ struct CellsIn { unsigned log2_n, log2_cell; size_t n; const uint8_t* blobs; con
 static int cells_pipeline(nbls_ctx* ctx, const CellsIn& in, int8_t* status) {
   const unsigned L = in.log2_n, lc = in.log2_cell, lm = L + 1 - lc;
   const size_t n = in.n, N = (size_t)1 << L, M = (2 * N) >> lc, qb = n * N * 32;   // M: the cells, and the quotient rows, of one blob
-  const bool proofs = in.mono != nullptr;
+  const nbls_kzg_fk20* fk = in.fk;
+  const bool proofs = in.mono != nullptr || fk, passes = fk && M > 2;   // (M = 2: n' = 1)
   const RecoverIn* rec = in.rec;
   uint8_t g32[32];
   fr_to_bytes(fr_omega(L + 1), g32);   // g = omega_2N, the shift of the coset
@@ -71,28 +76,52 @@ static int cells_pipeline(nbls_ctx* ctx, const CellsIn& in, int8_t* status) {
     o_blob = io.bytes(in.blobs, qb); o_g = io.bytes(g32, 32);
   }
   // blobs per pass: as many whole blobs as the batched MSM takes, or fewer where the tuning key says so
-  size_t per = proofs ? std::min({n, (MSMB_MAX_ITEMS >> L) / M, MSMB_MAX_GROUPS / M}) : n;
+  // (the FK20 loop: 2 N scalars a blob in pass A, M^2 in pass B, M groups in both)
+  size_t per = fk ? std::min({n, MSMB_MAX_ITEMS / (2 * N), MSMB_MAX_ITEMS / (M * M), MSMB_MAX_GROUPS / M}) : proofs ? std::min({n, (MSMB_MAX_ITEMS >> L) / M, MSMB_MAX_GROUPS / M}) : n;
   if (proofs && ctx->cells_chunk && ctx->cells_chunk < per) per = ctx->cells_chunk;
   const size_t tail = n % per;
   // what is read back: the cells | the compressed proofs | the blobs' statuses; behind it one pass's affine sums, zero flags and closing statuses
   const size_t b_pf = 2 * qb, b_st = b_pf + (proofs ? n * M * 48 : 0), back = b_st + n;
   size_t sz_out = 0, sz_rows = 0;
   const size_t a_bk = carve(&sz_out, back), a_aff = carve(&sz_out, proofs ? per * M * 96 : 0), a_zf = carve(&sz_out, proofs ? per * M : 0), a_cst = carve(&sz_out, proofs ? per * M : 0);
-  const size_t a_q = carve(&sz_rows, proofs ? per * M * N * 32 : 0), a_rst = carve(&sz_rows, proofs ? per * M : 0);
-  MsmbPlan pl_full, pl_tail;   // (the larger plan first: the smaller then finds both of the MSM's slots large enough and takes the same pointers)
+  const size_t a_q = carve(&sz_rows, !proofs ? 0 : fk ? per * 2 * N * 32 : per * M * N * 32), a_rst = carve(&sz_rows, proofs ? per * M : 0);
+  const size_t sz_yh = passes ? per * M * 6 * RAW : 0, cs = (size_t)1 << lc;
+  // the plans of a pass of `blobs` blobs: the rows (a), or pass A (a) and pass B (b).  (The larger pass first: the smaller then finds both of the MSM's slots large enough)
+  MsmbPlan pl_full, pl_tail, plb_full, plb_tail;
+  auto plans = [&](size_t blobs, MsmbPlan* a, MsmbPlan* b) -> int {
+    if (!fk) return msm_rows_dev_plan(ctx, N, blobs * M, a);
+    if (!passes) return NBLS_OK;
+    const int e = msm_map_dev_plan(ctx, cs, cs * M, 0, 0, blobs * M, a);
+    return e ? e : msm_map_dev_plan(ctx, M, M, M * M, M * M, blobs * M, b);
+  };
+  uint8_t* YH = nullptr;
   uint8_t *c, *OUT, *COEF = nullptr, *ROWS = nullptr, *ZV = nullptr; const uint8_t *roots, *iroots, *sroots = nullptr, *got; int r;
   if ((r = need(ctx, SB_STAGED, io.in_bytes, &c)) || (r = need(ctx, SB_KZGC_OUT, sz_out, &OUT)) || ((proofs || rec) && (r = need(ctx, SB_KZGC_COEFS, qb, &COEF))) ||
       (rec && (r = need(ctx, SB_KZGR_Z, n * (M + M / 2) * sizeof(Fr), &ZV))) ||
-      (proofs && (r = need(ctx, SB_KZGC_ROWS, sz_rows, &ROWS))) || (proofs && (r = msm_rows_dev_plan(ctx, N, per * M, &pl_full))) ||
-      (proofs && tail && (r = msm_rows_dev_plan(ctx, N, tail * M, &pl_tail))) || (r = kzg_table(ctx, KZG_ROOTS, L, 0, s, &roots)) || (r = kzg_table(ctx, KZG_INV_ROOTS, L, 0, s, &iroots)) ||
+      (proofs && (r = need(ctx, fk ? SB_KZGF_SCALARS : SB_KZGC_ROWS, sz_rows, &ROWS))) || (passes && (r = need(ctx, SB_KZGF_POINTS, sz_yh, &YH))) ||
+      (proofs && (r = plans(per, &pl_full, &plb_full))) || (proofs && tail && (r = plans(tail, &pl_tail, &plb_tail))) || (r = kzg_table(ctx, KZG_ROOTS, L, 0, s, &roots)) || (r = kzg_table(ctx, KZG_INV_ROOTS, L, 0, s, &iroots)) ||
       ((proofs || rec) && (r = kzg_table(ctx, KZG_ROOTS, lm, 0, s, &sroots))) || (r = io.send(c, back)))
     return r;
+  if (passes) msm_map_plans_settle(ctx, {&pl_full, &plb_full, &pl_tail, &plb_tail});   // (four plans on the MSM's two slots: the last need() decided where they are)
   uint8_t *BK = OUT + a_bk, *AFF = OUT + a_aff, *ZF = OUT + a_zf, *CST = OUT + a_cst, *Q = ROWS + a_q, *RST = ROWS + a_rst;
   if (rec) LAUNCHCHK(nbls_kzg_recover_launch(L, lc, (unsigned)n, c + o_cells, (const uint32_t*)(c + o_slot), c + o_pre, sroots, c + o_k, roots, iroots, ZV, BK, COEF, BK + b_st, s));
   else LAUNCHCHK(nbls_kzg_ntt_launch(L, FR_NTT_CELLS, (unsigned)n, c + o_blob, c + o_g, 0, roots, iroots, BK, COEF, BK + b_st, s));
   for (size_t b0 = 0; proofs && b0 < n; b0 += per) {
     const size_t nb = std::min(per, n - b0);
     uint8_t* P = BK + b_pf + b0 * M * 48;
+    if (fk) {
+      LAUNCHCHK(nbls_kzg_fk20_row_status_launch(lm, (unsigned)nb, BK + b_st + b0, RST, s));
+      if (passes) {
+        LAUNCHCHK(nbls_kzg_fk20_scalars_launch(L, lc, (unsigned)nb, COEF + b0 * N * 32, sroots, Q, s));
+        if ((r = msm_map_dev(ctx, nb == per ? pl_full : pl_tail, fk->xhat, Q, nullptr, nullptr, nullptr, YH, s)) ||
+            (r = msm_map_dev(ctx, nb == per ? plb_full : plb_tail, YH, nullptr, fk->bsplit, AFF, ZF, nullptr, s)))
+          return r;
+      } else {   // every sum is empty: the zero point, whatever the blob holds
+        HIPCHK(hipMemsetAsync(AFF, 0, nb * M * 96, s)); HIPCHK(hipMemsetAsync(ZF, 1, nb * M, s));
+      }
+      if ((r = kzg_proof_close(ctx, nb * M, AFF, ZF, RST, nullptr, P, CST, s))) return r;
+      continue;
+    }
     LAUNCHCHK(nbls_kzg_cell_rows_launch(L, lc, (unsigned)nb, COEF + b0 * N * 32, sroots, BK + b_st + b0, Q, RST, s));
     if ((r = kzg_proof_tail(ctx, nb == per ? pl_full : pl_tail, in.mono->pts, Q, AFF, ZF, RST, nullptr, P, CST, s))) return r;
   }
@@ -108,6 +137,12 @@ EXPORT int nbls_kzg_compute_cells(nbls_ctx* ctx, unsigned log2_n, unsigned log2_
   if (!ctx || log2_n < 1 || log2_n > 12 || log2_cell > log2_n || (n && (!blobs || !out_cells)) || n > (KZG_MAX_ELEMS >> log2_n)) return NBLS_EINVAL;
   if (!n) return NBLS_OK;
   return cells_pipeline(ctx, {log2_n, log2_cell, n, blobs, nullptr, out_cells, nullptr, nullptr}, status);
+}
+
+EXPORT int nbls_kzg_compute_cells_and_proofs_fk20(nbls_ctx* ctx, const nbls_kzg_fk20* fk, size_t n, const uint8_t* blobs, uint8_t* out_cells, uint8_t* out_proofs48, int8_t* status) {
+  WHOLE_CALL(ctx);
+  if (!ctx || !fk || !blobs || !out_cells || !out_proofs48 || !n || fk->device != ctx->device || n > (KZG_MAX_ELEMS >> fk->log2_n)) return NBLS_EINVAL;
+  return cells_pipeline(ctx, {fk->log2_n, fk->log2_cell, n, blobs, nullptr, out_cells, out_proofs48, nullptr, fk}, status);
 }
 
 EXPORT int nbls_kzg_compute_cells_and_proofs(nbls_ctx* ctx, const nbls_kzg_monomial* monomial, unsigned log2_cell, size_t n, const uint8_t* blobs, uint8_t* out_cells,
@@ -145,4 +180,13 @@ EXPORT int nbls_kzg_recover_cells_and_proofs(nbls_ctx* ctx, const nbls_kzg_monom
   if (!recover_args_ok(L, log2_cell, n, cell_offsets, cell_index, cells, out_cells) || ((size_t)2 << (2 * L - log2_cell)) > MSMB_MAX_ITEMS) return NBLS_EINVAL;
   const RecoverIn rec{cell_offsets, cell_index, cells};
   return cells_pipeline(ctx, {L, log2_cell, n, nullptr, monomial, out_cells, out_proofs48, &rec}, status);
+}
+
+EXPORT int nbls_kzg_recover_cells_and_proofs_fk20(nbls_ctx* ctx, const nbls_kzg_fk20* fk, size_t n, const uint32_t* cell_offsets, const uint32_t* cell_index, const uint8_t* cells,
+                                                  uint8_t* out_cells, uint8_t* out_proofs48, int8_t* status) {
+  WHOLE_CALL(ctx);
+  if (!ctx || !fk || !out_proofs48 || !n || fk->device != ctx->device) return NBLS_EINVAL;
+  if (!recover_args_ok(fk->log2_n, fk->log2_cell, n, cell_offsets, cell_index, cells, out_cells)) return NBLS_EINVAL;   // (the handle exists: one blob fits a pass)
+  const RecoverIn rec{cell_offsets, cell_index, cells};
+  return cells_pipeline(ctx, {fk->log2_n, fk->log2_cell, n, nullptr, nullptr, out_cells, out_proofs48, &rec, fk}, status);
 }

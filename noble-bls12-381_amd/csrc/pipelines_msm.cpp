@@ -53,7 +53,7 @@ static int msm_prepare(nbls_ctx* ctx, bool g2, unsigned dims, size_t npoints, co
   return NBLS_OK;
 }
 // Steps 1 to 3: from the bucket fill to the last halving round, for nbw = groups x windows of c bits and M = keys.m * keys.nwin entries.  The caller sizes every buffer.
-struct MsmKeys { unsigned m, dims, nwin, i0, g0, ngroups, n_pts; const uint32_t* off; const void* scalars; };   // the arguments of the keys launch (msm_kernels.hip msm_keys_kernel) but c
+struct MsmKeys { unsigned m, dims, nwin, i0, g0, ngroups, n_pts; const uint32_t* off; const void* scalars; unsigned glen = 0, pt_block = 0, k_mod = 0; };   // the arguments of the keys launch (msm_kernels.hip msm_keys_kernel) but c; glen > 0: the wider map of the rows form
 struct BucketBufs {
   uint32_t *words, *counters;   // 6 M words: keys, values, both sorted, ranks, pair list; 64 counters: [0] longest run, [1 + round] pairs of that round
   uint8_t* tmp; size_t sort_bytes, scan_bytes;   // scratch of the sort and the scan, one after the other in the same bytes, and what each is told it has
@@ -67,7 +67,8 @@ static int bucket_slices(nbls_ctx* ctx, bool g2, size_t M, size_t nbw, unsigned 
   LAUNCHCHK(nbls_msm_fill_launch(nb, (unsigned)p, g2 ? ctx->ident_g2 : ctx->ident_g1, b.Bk, s));
   if (M) {
     uint32_t *kin = b.words, *vin = kin + M, *kout = vin + M, *vout = kout + M, *pos = vout + M, *list = pos + M;
-    LAUNCHCHK(nbls_msm_keys_launch(k.m, k.dims, k.nwin, c, k.i0, k.g0, k.ngroups, k.n_pts, k.off, k.scalars, kin, vin, s));
+    if (k.glen) LAUNCHCHK(nbls_msm_keys_map_launch(k.m, k.dims, k.nwin, c, k.i0, k.g0, k.ngroups, k.n_pts, k.glen, k.pt_block, k.k_mod, k.scalars, kin, vin, s));
+    else LAUNCHCHK(nbls_msm_keys_launch(k.m, k.dims, k.nwin, c, k.i0, k.g0, k.ngroups, k.n_pts, k.off, k.scalars, kin, vin, s));
     size_t sb = b.sort_bytes, cb = b.scan_bytes;
     LAUNCHCHK(nbls_msm_sort_launch(b.tmp, &sb, kin, kout, vin, vout, M, key_bits, s));
     LAUNCHCHK(nbls_msm_gather_launch(M, (unsigned)p, vout, Pj, b.P, s));
@@ -234,9 +235,10 @@ static int msmb_plan(nbls_ctx* ctx, bool g2, size_t n_groups, const uint32_t* of
 
 // The device core: every part of the plan on stream s.  Pj: the converted points (dims * p bytes each); d_k: the scalars as given (read when the call is not split, and by
 // dev_msm for a big group); pl.Ks: the split scalars; d_pts: the affine points as given (only a big group reads them); d_off: the offsets on the device (unused in the rows
-// form) -> O: one affine sum per group, OST: its zero flag
+// form) -> O: one affine sum per group, OST: its zero flag; or, conv != NULL (G1 only), every sum as it stands in projective coordinates with its endomorphism image
+// (XP_ENDO_G1: 2 x 3 raw elements, the form the split path reads) and nothing to O / OST: the sums are the points of a second pass and the identity may be among them
 static int msmb_run(nbls_ctx* ctx, const MsmbPlan& pl, const uint32_t* off, const uint8_t* Pj, const uint8_t* d_k, const uint8_t* d_pts, const uint32_t* d_off, uint8_t* O, uint8_t* OST,
-                    hipStream_t s) {
+                    hipStream_t s, uint8_t* conv = nullptr) {
   const bool g2 = pl.g2;
   const size_t a = g2 ? 192 : 96, p = g2 ? 6 * RAW : 3 * RAW, n_groups = pl.n_groups, n_pts = pl.n_pts, nwin = pl.nwin, J = pl.J, jtop = pl.jtop;
   const unsigned dims = pl.dims, c = pl.c;
@@ -254,13 +256,15 @@ static int msmb_run(nbls_ctx* ctx, const MsmbPlan& pl, const uint32_t* off, cons
     LAUNCHCHK(nbls_msm_fill_launch(ngs, (unsigned)p, g2 ? ctx->ident_g2 : ctx->ident_g1, acc, s));
     if (M) {   // (a slab without entries: every sum is the identity the accumulators hold)
       size_t maxg = 0; for (size_t g = pt.g0; g < pt.g1; g++) maxg = std::max(maxg, (size_t)(off[g + 1] - off[g]) * dims);   // a run lies inside one window of one group
-      const MsmKeys keys{(unsigned)m, dims, (unsigned)nwin, (unsigned)i0, (unsigned)g0, (unsigned)n_groups, (unsigned)n_pts, d_off, pl.split ? pl.Ks : d_k};
+      const MsmKeys keys{(unsigned)m, dims, (unsigned)nwin, (unsigned)i0, (unsigned)g0, (unsigned)n_groups, (unsigned)n_pts, d_off, pl.split ? pl.Ks : d_k, (unsigned)pl.glen,
+                         (unsigned)pl.pt_block, (unsigned)pl.k_mod};
       if ((r = bucket_slices(ctx, g2, M, ngs * nwin, c, pt.key_bits, keys, Pj, bufs, maxg > MSMB_NO_READBACK ? 0 : maxg, &T, s))) return r;
       // T[g * J + j], the slice of bit position j of group g
       for (size_t j = jtop; j-- > 0;)
         if ((r = run_dev(ctx, step, -1, ngs, {B(3, acc, p), B(4, T + j * p, J * p)}, s, nullptr, nullptr))) return r;
     }
-    if ((r = to_affine(ctx, g2, ngs, acc, Nm, NI, O + g0 * a, OST + g0, s))) return r;
+    if (conv) { if ((r = run_dev(ctx, ctx->extra[XP_ENDO_G1], -1, ngs, {B(3, acc, p), B(5, conv + g0 * 2 * p, 2 * p)}, s, nullptr, nullptr))) return r; }
+    else if ((r = to_affine(ctx, g2, ngs, acc, Nm, NI, O + g0 * a, OST + g0, s))) return r;
   }
   return NBLS_OK;
 }
@@ -310,6 +314,36 @@ int msm_rows_dev(nbls_ctx* ctx, const MsmbPlan& pl, const uint8_t* conv_pts, con
   if ((r = msm_prepare(ctx, false, pl.dims, 0, nullptr, nullptr, pl.n_groups * pl.n_pts, d_scalars, pl.Ks, s))) return r;   // (the points came converted)
   return msmb_run(ctx, pl, off.data(), conv_pts, d_scalars, nullptr, nullptr, d_out96, d_zero, s);
 }
+
+// The wider map of the rows form in G1 (msm_keys_kernel; the two passes of the FK20 cell proofs and the one MSM of their handle): n_groups sums of glen scalars each, scalar i
+// against point i % period + (i / pt_block) * period (pt_block = 0: i % period), read at i % k_mod of an array the caller has split already (k_mod > 0: no split here, and
+// SB_MSMB_CALL is not taken), else at i of d_scalars.  Several plans of one call share the two slots: msm_map_plans_settle gives every plan the slots' final pointers
+int msm_map_dev_plan(nbls_ctx* ctx, size_t glen, size_t period, size_t pt_block, size_t k_mod, size_t n_groups, MsmbPlan* pl) {
+  if (!glen || !period || !n_groups || n_groups > MSMB_MAX_GROUPS || n_groups * glen > MSMB_MAX_ITEMS) return NBLS_EINVAL;
+  std::vector<uint32_t> off(n_groups + 1);
+  for (size_t g = 0; g <= n_groups; g++) off[g] = (uint32_t)(g * glen);
+  int r;
+  if ((r = msmb_plan(ctx, false, n_groups, off.data(), period, 256, false, pl))) return r;
+  pl->glen = glen; pl->pt_block = pt_block; pl->k_mod = k_mod;
+  if ((!k_mod && (r = need(ctx, SB_MSMB_CALL, al((n_groups * glen + 1) * 32 * pl->dims), &pl->Ks))) || (r = need(ctx, SB_MSMB_SLAB, pl->slab_bytes, &pl->SL)) ||
+      (r = upload_extra(ctx, XP_DBLADD_G1)) || (r = upload_extra(ctx, XP_ENDO_G1)))
+    return r;
+  return NBLS_OK;
+}
+void msm_map_plans_settle(nbls_ctx* ctx, std::initializer_list<MsmbPlan*> plans) {
+  for (MsmbPlan* pl : plans) if (pl->n_groups) { pl->SL = ctx->sb[SB_MSMB_SLAB]; if (!pl->k_mod) pl->Ks = ctx->sb[SB_MSMB_CALL]; }
+}
+// split (k_mod > 0): the caller's split scalars.  conv != NULL: the sums in the converted projective form (msmb_run), else affine sums and zero flags
+int msm_map_dev(nbls_ctx* ctx, const MsmbPlan& pl, const uint8_t* conv_pts, const uint8_t* d_scalars, const uint8_t* split, uint8_t* d_out96, uint8_t* d_zero, uint8_t* conv, hipStream_t s) {
+  std::vector<uint32_t> off(pl.n_groups + 1); int r;
+  for (size_t g = 0; g <= pl.n_groups; g++) off[g] = (uint32_t)(g * pl.glen);
+  MsmbPlan run_pl = pl;
+  if (pl.k_mod) run_pl.Ks = const_cast<uint8_t*>(split);
+  else if ((r = msm_prepare(ctx, false, pl.dims, 0, nullptr, nullptr, pl.n_groups * pl.glen, d_scalars, pl.Ks, s))) return r;
+  return msmb_run(ctx, run_pl, off.data(), conv_pts, d_scalars, nullptr, nullptr, d_out96, d_zero, s, conv);
+}
+// a caller's scalars into the split form the wider map reads with k_mod (the handle's matrix, split once)
+int msm_split_scalars(nbls_ctx* ctx, size_t n, const uint8_t* d_scalars, uint8_t* split, hipStream_t s) { return msm_prepare(ctx, false, 2, 0, nullptr, nullptr, n, d_scalars, split, s); }
 
 static int msm_batch_host(nbls_ctx* ctx, bool g2, size_t n_groups, const uint32_t* group_offsets, size_t n_pts, const uint8_t* pts, const uint8_t* scalars, uint8_t* out, int8_t* status) {
   WHOLE_CALL(ctx);

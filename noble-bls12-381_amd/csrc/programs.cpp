@@ -970,6 +970,12 @@ static Program build_extra(ExtraProg id) {
     outputw(r.x, 3, 0); outputw(r.y, 3, 48); outputw(r.z, 3, 96);
     return B.compile("dbladd_g1", 4);
   }
+  if (id == XP_ENDO_G1) {
+    SFp x = inputw(3, 0), y = inputw(3, 48), z = inputw(3, 96);
+    outputw(x, 5, 0); outputw(y, 5, 48); outputw(z, 5, 96);
+    outputw(mul(x, fp_const(NBLS_BETA)), 5, 144); outputw(-y, 5, 192); outputw(z, 5, 240);
+    return B.compile("endo_g1", 4);
+  }
   if (id == XP_DBLADD_G2) {
     auto ld = [&](int buf) { return Pt<SFp2>{{inputw(buf, 0), inputw(buf, 48)}, {inputw(buf, 96), inputw(buf, 144)}, {inputw(buf, 192), inputw(buf, 240)}}; };
     Pt<SFp2> r = pt_add(pt_dbl(ld(3)), ld(4));

@@ -114,7 +114,9 @@ const Program* get_tower_program(int field, int op, int param, int part);
 // layout of P_LINES_PQ, every line the reference's times a non-zero Fp2 factor and R any projective representative (programs.cpp trace_lines_fe).  A factor in a proper subfield
 // of Fp12 is sent to ONE by the easy part of the final exponentiation, so pairing(P, Q) is the reference's element; pairing(P, Q, false), prepared lines and the Miller products
 // keep P_LINES_PQ, whose bytes are pinned.
-enum ExtraProg { XP_POLY_G1_16 = 0, XP_POLY_G1_256, XP_POLY_G2_16, XP_POLY_G2_256, XP_DBLADD_G1, XP_DBLADD_G2, XP_LINES_FE, XP_COUNT };
+// The conversion between the two passes of the FK20 cell proofs (pipelines_kzg_cells.cpp): a raw projective G1 point (buf 3) -> the point and its image (beta X, -Y, Z), the
+// form P_G1_MSM_PREP leaves, without leaving projective coordinates (buf 5): the identity stays the identity.  No ahead-of-time kernel: one short launch on the interpreter.
+enum ExtraProg { XP_POLY_G1_16 = 0, XP_POLY_G1_256, XP_POLY_G2_16, XP_POLY_G2_256, XP_DBLADD_G1, XP_DBLADD_G2, XP_LINES_FE, XP_ENDO_G1, XP_COUNT };
 // The simulator's index-taking entry points (nbls_sim_extra_count / _name / _verify / _run) stop in front of this one: the suite pins their count at the four Horner steps.
 // Every later program is reached by name (nbls_sim_extra_verify_named / _run_named), as nbls_extra_program_kernel reaches it in the engine.
 static const int XP_NUMBERED = XP_DBLADD_G1;

@@ -687,6 +687,31 @@ __attribute__((visibility("default"))) int nbls_sim_kzg_cell_rows(unsigned log2_
   }
   return 0;
 }
+// The per-blob scalars of the FK20 cell proofs as kzg_fk20_scalars_kernel writes them: workgroups of FR_FK_LANES lanes, every phase (the load, each stage, the store) on all
+// lanes of a workgroup before the next.  coef32: n x N coefficients; out32: n x M x c scalars, [blob][i][j].  -1 where the launcher refuses the sizes
+__attribute__((visibility("default"))) int nbls_sim_kzg_fk20_scalars(unsigned log2_n, unsigned log2_cell, size_t n, const uint8_t* coef32, uint8_t* out32) {
+  if (log2_n < 1 || log2_n > 12 || log2_cell > log2_n || log2_n + 1 - log2_cell > 11 || (n && (!coef32 || !out32)) || (n << log2_n) > ((size_t)1 << 24)) return -1;
+  const unsigned lm = log2_n + 1 - log2_cell;
+  std::vector<Fr> sroots((size_t)1 << lm);
+  const Fr omega = fr_omega(lm);
+  for (u32 k = 0; k < (1u << lm); k++) sroots[k] = fr_root_entry(omega, lm, k);
+  std::vector<u32> a(fr_fk_lds_words(lm));
+  const u32 wgs = fr_fk_workgroups(lm, log2_cell, (u32)n), W = FR_FK_LANES;
+  for (u32 wg = 0; wg < wgs; wg++) {
+    for (u32 t = 0; t < W; t++) fr_fk_load(coef32, log2_n, log2_cell, lm, fr_fk_lane(lm, log2_cell, (u32)n, wg, t), a.data());
+    for (u32 ll = lm; ll-- > 0;) for (u32 t = 0; t < W; t++) fr_fk_stage(a.data(), lm, ll, sroots.data(), fr_fk_lane(lm, log2_cell, (u32)n, wg, t));
+    for (u32 t = 0; t < W; t++) fr_fk_store(a.data(), log2_cell, lm, fr_fk_lane(lm, log2_cell, (u32)n, wg, t), out32);
+  }
+  return 0;
+}
+// the projection matrix B of the FK20 cell proofs as kzg_fk20_matrix_kernel writes it: out32[(k M + i) * 32], M = 2^log2_m
+__attribute__((visibility("default"))) int nbls_sim_kzg_fk20_matrix(unsigned log2_m, uint8_t* out32) {
+  if (log2_m < 1 || log2_m > 11 || !out32) return -1;
+  std::vector<Fr> roots, iroots;
+  sim_ntt_tables(log2_m, roots, iroots);
+  for (u32 idx = 0; !(idx >> (2 * log2_m)); idx++) fr_store_q(fr_fk_matrix_entry(roots.data(), iroots.data(), log2_m, idx >> log2_m, idx & ((1u << log2_m) - 1)), out32 + 32ull * idx);
+  return 0;
+}
 // The interpolation of n_cells cells as kzg_cell_interp_kernel runs it (and kzg_cell_sum_kernel behind it in the sum mode): workgroups of FR_CELL_LANES lanes, lane groups of c
 // lanes, every phase of a round on all lanes of a workgroup before the next, a stage's partner value read from the lane i ^ len of the same group, the column trees of the
 // workgroup and of the closing kernel in the kernel's order.  n_wg: the workgroups of the launch (0: as many as the launcher takes).  sum == 0: out = the n_cells rows of

@@ -102,6 +102,12 @@ def load_library():
     lib.nbls_kzg_verify_cells.argtypes = [vp, vp, C.c_uint, sz, vp, sz, vp, vp, vp, vp, vp, vp, C.POINTER(i32), vp]
     lib.nbls_kzg_recover_cells.argtypes = [vp, C.c_uint, C.c_uint, sz, vp, vp, vp, vp, vp]
     lib.nbls_kzg_recover_cells_and_proofs.argtypes = [vp, vp, C.c_uint, sz, vp, vp, vp, vp, vp, vp]
+    lib.nbls_kzg_fk20_create.argtypes = [vp, vp, C.c_uint, C.POINTER(vp)]
+    lib.nbls_kzg_fk20_destroy.argtypes = [vp]
+    lib.nbls_kzg_fk20_destroy.restype = None
+    lib.nbls_kzg_fk20_params.argtypes = [vp, C.POINTER(C.c_uint), C.POINTER(C.c_uint)]
+    lib.nbls_kzg_compute_cells_and_proofs_fk20.argtypes = [vp, vp, sz, vp, vp, vp, vp]
+    lib.nbls_kzg_recover_cells_and_proofs_fk20.argtypes = [vp, vp, sz, vp, vp, vp, vp, vp, vp]
     lib.nbls_keyset_create.argtypes = [vp, sz, vp, vp, C.POINTER(vp)]
     lib.nbls_keyset_destroy.argtypes = [vp]
     lib.nbls_keyset_destroy.restype = None
@@ -212,6 +218,40 @@ class KzgSetup:
     def close(self):
         if getattr(self, 'h', None):
             self.lib.nbls_kzg_setup_destroy(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class KzgFk20Setup:
+    """The fixed part of the FK20 cell proofs for one (log2_n, log2_cell) in device memory (nbls_kzg_fk20_create; Engine.kzg_fk20_setup): the transformed stripes of the
+    monomial basis and the projection matrix.  Usable from every Engine on its device.  Freed by close() or when the object goes away."""
+
+    def __init__(self, lib, handle):
+        self.lib = lib
+        self.h = handle
+
+    def _params(self):
+        a, b = C.c_uint(0), C.c_uint(0)
+        if self.h is None or self.lib.nbls_kzg_fk20_params(self.h, C.byref(a), C.byref(b)) != 0:
+            raise NblsError('KzgFk20Setup: the setup is closed')
+        return a.value, b.value
+
+    @property
+    def log2_n(self):
+        return self._params()[0]
+
+    @property
+    def log2_cell(self):
+        return self._params()[1]
+
+    def close(self):
+        if getattr(self, 'h', None):
+            self.lib.nbls_kzg_fk20_destroy(self.h)
         self.h = None
 
     def __del__(self):
@@ -747,6 +787,40 @@ class Engine:
         per = 2 << (log2_n - log2_cell)
         out = C.create_string_buffer(2 * len(raw)); pf = C.create_string_buffer(48 * per * n); st = C.create_string_buffer(n)
         self._chk(self.lib.nbls_kzg_compute_cells_and_proofs(self.h, setup.h, log2_cell, n, raw, out, pf, st))
+        p = pf.raw
+        return self._cells_of(out.raw, n, log2_n, log2_cell), [[p[48 * (per * i + k):48 * (per * i + k + 1)] for k in range(per)] for i in range(n)], st.raw[:n]
+
+    def kzg_fk20_setup(self, monomial, log2_cell):
+        """the FK20 handle of a KzgMonomialSetup for cells of 2^log2_cell elements (made on the device: one batched MSM) -> KzgFk20Setup"""
+        if getattr(monomial, 'h', None) is None:
+            raise NblsError('kzg_fk20_setup: the setup is closed')
+        if not 0 <= log2_cell <= monomial.log2_n:
+            raise NblsError('kzg_fk20_setup: log2_cell in 0 .. %d' % monomial.log2_n)
+        h = C.c_void_p()
+        self._chk(self.lib.nbls_kzg_fk20_create(self.h, monomial.h, log2_cell, C.byref(h)))
+        return KzgFk20Setup(self.lib, h)
+
+    def kzg_compute_cells_and_proofs_fk20(self, fk, blobs):
+        """kzg_compute_cells_and_proofs by FK20 against a KzgFk20Setup (which names log2_cell): the same return value, byte for byte"""
+        n, raw = self._kzg_blobs('kzg_compute_cells_and_proofs_fk20', fk, blobs)
+        log2_n, log2_cell = fk.log2_n, fk.log2_cell
+        per = 2 << (log2_n - log2_cell)
+        out = C.create_string_buffer(2 * len(raw)); pf = C.create_string_buffer(48 * per * n); st = C.create_string_buffer(n)
+        self._chk(self.lib.nbls_kzg_compute_cells_and_proofs_fk20(self.h, fk.h, n, raw, out, pf, st))
+        p = pf.raw
+        return self._cells_of(out.raw, n, log2_n, log2_cell), [[p[48 * (per * i + k):48 * (per * i + k + 1)] for k in range(per)] for i in range(n)], st.raw[:n]
+
+    def kzg_recover_cells_and_proofs_fk20(self, fk, cell_indices, cells):
+        """kzg_recover_cells_and_proofs by FK20 against a KzgFk20Setup: the same return value, byte for byte"""
+        if getattr(fk, 'h', None) is None:
+            raise NblsError('kzg_recover_cells_and_proofs_fk20: the setup is closed')
+        log2_n, log2_cell, n = fk.log2_n, fk.log2_cell, len(cells)
+        off, idx, raw = self._recover_args('kzg_recover_cells_and_proofs_fk20', log2_n, log2_cell, cell_indices, cells)
+        if not n:
+            raise NblsError('kzg_recover_cells_and_proofs_fk20: one blob or more')
+        per = 2 << (log2_n - log2_cell)
+        out = C.create_string_buffer((64 << log2_n) * n); pf = C.create_string_buffer(48 * per * n); st = C.create_string_buffer(n)
+        self._chk(self.lib.nbls_kzg_recover_cells_and_proofs_fk20(self.h, fk.h, n, off, idx, raw, out, pf, st))
         p = pf.raw
         return self._cells_of(out.raw, n, log2_n, log2_cell), [[p[48 * (per * i + k):48 * (per * i + k + 1)] for k in range(per)] for i in range(n)], st.raw[:n]
 
