@@ -543,6 +543,51 @@ int  nbls_kzg_compute_cells_and_proofs_fk20(nbls_ctx* ctx, const nbls_kzg_fk20* 
 int  nbls_kzg_recover_cells_and_proofs_fk20(nbls_ctx* ctx, const nbls_kzg_fk20* fk, size_t n, const uint32_t* cell_offsets, const uint32_t* cell_index, const uint8_t* cells,
                                             uint8_t* out_cells, uint8_t* out_proofs48 /* n * (2 N / c) * 48 */, int8_t* status /* n, may be NULL */);
 
+/* ---- Groth16 over BLS12-381: n proofs against one verifying key in one call (the shape of Zcash Sapling and Filecoin batches).  The key holds alpha in G1, beta, gamma, delta
+ * in G2 and IC_0 .. IC_m in G1, m = the number of public inputs.  Proof i = (A_i, B_i, C_i) with inputs x_i1 .. x_im holds when, with L_i = IC_0 + sum_j [x_ij]IC_j,
+ *   e(A_i, B_i) * e(L_i, -gamma) * e(C_i, -delta) * e(alpha, -beta) = 1.
+ * n proofs are checked together with the secret weights r_i of nbls_verify_multiple (r_i = BE64(SHA-256(seed || BE64(i))[0..8]) | 2^63; the same seed rule: NULL = 32 bytes
+ * from the OS on every call, never a fixed seed):
+ *   prod_i e([r_i]A_i, B_i) * e(sum_j [S_j]IC_j, -gamma) * e(sum_i [r_i]C_i, -delta) * e([S_0]alpha, -beta) = 1,   S_0 = sum_i r_i,  S_j = sum_i r_i x_ij mod r:
+ * n + 3 Miller loops and ONE final exponentiation where the per-proof equation takes 4 n and n.  The signs sit on the fixed G2 points: no point is negated on the device.
+ * ENCODINGS: G1 points are 48 bytes compressed by PointG1.fromHex's rules, G2 points 96 bytes compressed by PointG2.fromSignature's rules, both with the subgroup check, as
+ * everywhere in this header; a proof is A || B || C, 192 bytes (bellman's Proof::write); inputs are 32 bytes big-endian and must be canonical, as in the KZG calls.  Parsing
+ * bellman's uncompressed verifying-key file (VerifyingKey::write) into these points stays with the caller.
+ *   nbls_groth16_vk_create       decodes the key once and keeps, in memory of ctx's device: alpha affine; the prepared line tables of -beta, -gamma, -delta; the IC points affine
+ *                                and in the batched MSM's converted form.  status[] (m + 5, may be NULL), in the order alpha, beta, gamma, delta, IC_0 .. IC_m: the decoder's
+ *                                status.  An entry that does not decode, or is the zero point (status 1), makes the call return NBLS_EDECODE with *out = NULL; the statuses are
+ *                                written in both cases, as nbls_kzg_setup_create does.  Lifetime and device rules: nbls_kzg_setup_create's (any context on the same device may
+ *                                use the handle, also after its creator is destroyed).  NBLS_EINVAL for a missing pointer, m = 0 or m > 2^16.
+ *   nbls_groth16_verify          status[i] (n, may be NULL), the first that applies: A's decoder status if >= 1 (1 = the zero point, which bellman's reader refuses too; 3; 4);
+ *                                10 + B's decoder status if >= 1; NBLS_ST_G16_C + C's decoder status if >= 1; NBLS_ST_NON_CANONICAL for an input >= r; else 0 or
+ *                                NBLS_ST_NOT_VERIFIED.  *all_ok = 1 exactly when every status is 0.  A proof with one of the first four statuses has weight zero everywhere,
+ *                                the combined check never accepts while there is one, and a neighbour is never disturbed.  The combined check does not count either when one of
+ *                                its three combined G1 points is the zero point (nbls_verify_multiple's rule for a zero weighted signature sum).  Where it does not accept:
+ *                                with status == NULL the call stops and answers *all_ok = 0 (fast reject); else a per-proof pass judges every proof with the single-proof
+ *                                equation -- L_i from the rows form of the batched MSM against the handle's converted points plus IC_0 (a zero L_i is a factor of one),
+ *                                Miller loops against the three shared tables, one batched final exponentiation -- in chunks of whole proofs under the batched MSM's bounds
+ *                                of 2^22 scalars and 2^20 rows (NBLS_TUNE_G16_CHUNK: fewer; the bytes do not depend on the chunks).  Returns NBLS_OK whatever the proofs hold;
+ *                                NBLS_EINVAL before any device work for a missing pointer, n = 0, n > 2^20, n * m > 2^24, a key on another device.  *all_ok and status are
+ *                                NOT written on an error return.  One chain on the context's stream; nothing is decided on the host before the one read-back of verdict,
+ *                                zero flags and statuses.
+ *   nbls_groth16_prepare_inputs  out48[i] = compress(L_i); status[i] (n, may be NULL): 0; 1 when L_i is the zero point (bytes 0xc0 00..); NBLS_ST_NON_CANONICAL (48 zero bytes).
+ *                                The same chunks, bounds and refusals.
+ *   nbls_groth16_input_sums      the folding kernel on caller-chosen weights (it exists for tests, as nbls_map_uniform_batch exposes the maps): out32[0] = sum w_i,
+ *                                out32[j] = sum w_i x_ij mod r, over the rows with pre[i] == 0 and all inputs canonical; status[i] = pre[i], else NBLS_ST_NON_CANONICAL, else 0.
+ *                                NBLS_EINVAL for a weight >= 2^64, n or m = 0, n * m > 2^24, a missing pointer.
+ * NOT an interface for secrets: proofs, inputs and keys are public, and nothing is wiped. */
+#define NBLS_ST_G16_C 30          /* nbls_groth16_verify: NBLS_ST_G16_C + the decoder's status of C */
+typedef struct nbls_groth16_vk nbls_groth16_vk;
+int  nbls_groth16_vk_create(nbls_ctx* ctx, size_t m, const uint8_t* alpha_g1_48, const uint8_t* beta_g2_96, const uint8_t* gamma_g2_96, const uint8_t* delta_g2_96,
+                            const uint8_t* ic48 /* m + 1 */, int8_t* status /* m + 5, may be NULL */, nbls_groth16_vk** out);
+void nbls_groth16_vk_destroy(nbls_groth16_vk* vk);
+int  nbls_groth16_vk_inputs(const nbls_groth16_vk* vk, size_t* m);
+int  nbls_groth16_verify(nbls_ctx* ctx, const nbls_groth16_vk* vk, size_t n, const uint8_t* proofs192, const uint8_t* inputs32 /* n * m */, const uint8_t* seed32 /* NULL: from the OS */,
+                         int* all_ok, int8_t* status /* n, may be NULL */);
+int  nbls_groth16_prepare_inputs(nbls_ctx* ctx, const nbls_groth16_vk* vk, size_t n, const uint8_t* inputs32, uint8_t* out48 /* n */, int8_t* status /* n, may be NULL */);
+int  nbls_groth16_input_sums(nbls_ctx* ctx, size_t n, size_t m, const uint8_t* inputs32, const uint8_t* weights32 /* n, each < 2^64 */, const int8_t* pre /* n, may be NULL */,
+                             uint8_t* out32 /* m + 1 */, int8_t* status /* n, may be NULL */);
+
 /* One rank's share of a verifyBatch spread over several GPUs (one process per GPU): the Miller product of this rank's n
  * (key, message) pairs, times millerLoop(-G, S) on the ONE rank that passes the signature (d_sig96 = NULL elsewhere), WITHOUT the
  * final exponentiation, as 576 wire bytes in device memory.  Ranks all-gather their partials and finish with
@@ -575,7 +620,8 @@ const char* nbls_config_describe(void);   /* "NBLS_X=value(env|default) ...": ev
    nbls_g1_msm_rows, nbls_g2_msm_rows, NBLS_TUNE_MSMB_WINDOW / _BIG / _SLAB, the names "dbladd_g1" / "dbladd_g2" of nbls_extra_program_kernel, scratch slots 62 .. 63 (additions only, same version); then nbls_map_uniform_batch (addition only, same version); then nbls_fr_eval_roots, nbls_kzg_verify_proofs, nbls_kzg_verify_blobs, NBLS_ST_NON_CANONICAL, scratch slots 64 .. 68 (additions only, same version); then nbls_kzg_setup_create / _destroy / _log2n, nbls_fr_quotient_roots, nbls_kzg_commit_blobs, nbls_kzg_compute_proofs, nbls_kzg_compute_blob_proofs, scratch slots 69 .. 70 (additions only, same version); then nbls_fr_ntt, NBLS_NTT_*, nbls_kzg_compute_cells, nbls_kzg_monomial_create / _destroy / _log2n, nbls_kzg_compute_cells_and_proofs, NBLS_TUNE_CELLS_CHUNK, scratch slots 71 .. 73 (additions only, same version); then nbls_kzg_verify_cells, scratch slots 74 .. 78 (addition only, same version); then nbls_kzg_recover_cells, nbls_kzg_recover_cells_and_proofs, NBLS_ST_BAD_CELLS, NBLS_ST_INCONSISTENT, scratch slot 79 (additions only, same version); with the MSM calls ONE CHANGE TO EXISTING CALLS, same version: nbls_g1_msm / nbls_g2_msm write all-zero output bytes when the status is 1 (the sum is the
    zero point).  The bytes were unspecified there before (what the affine conversion made of a Z that is 0 mod p: in G1 a zero x and an arbitrary y); the status, and every output with status 0, are unchanged.
    nbls_msm_dev, which leaves its result on the device, is not changed.
-   Then nbls_kzg_fk20_create / _destroy / _params, nbls_kzg_compute_cells_and_proofs_fk20, nbls_kzg_recover_cells_and_proofs_fk20, the name "endo_g1" of nbls_extra_program_kernel, scratch slots 80 .. 81 (additions only, same version).
+   Then nbls_kzg_fk20_create / _destroy / _params, nbls_kzg_compute_cells_and_proofs_fk20, nbls_kzg_recover_cells_and_proofs_fk20, the name "endo_g1" of nbls_extra_program_kernel, scratch slots 80 .. 81 (additions only, same version). Then nbls_groth16_vk_create / _destroy / _inputs,
+   nbls_groth16_verify, nbls_groth16_prepare_inputs, nbls_groth16_input_sums, NBLS_ST_G16_C, NBLS_TUNE_G16_CHUNK, scratch slots 82 .. 86 (additions only, same version).
    4 (round 6): nbls_hw_queues, NBLS_TUNE_WIDE_MAX, NBLS_TUNE_H2C_NORM_MIN, NBLS_TUNE_INV_WIDE_MAX, NBLS_TUNE_LS_MAX / _LS2_MAX (additions only); the library sets GPU_MAX_HW_QUEUES = 22 at load when the variable is unset (see nbls_pool_init below).
    3 (round 5): nbls_program_kernel, nbls_pool_*, nbls_sign_batch_dev, NBLS_TUNE_VERIFY_* / _SAC_MAX / _PT_LS2_MAX (additions only); nbls_verify_batch_partial_dev writes d_out_fp12 even when it reports a zero point or a decode error
    (contents then meaningless); 2: *_partial take *d_partial as OUT only, *_partial_into added, nbls_tower_op_batch, nbls_verify_batch_msgs_dev.  The bindings check it at load. */
@@ -656,6 +702,7 @@ int nbls_field_kernel_raw(nbls_ctx* ctx, int kind, int form, size_t n, const uin
 #define NBLS_TUNE_MSMB_BIG 17         /* points (as given) above which a group of nbls_g*_msm_batch / _rows runs through the pipeline of nbls_g*_msm on the same stream (default 16384; 0 = the default) */
 #define NBLS_TUNE_MSMB_SLAB 18        /* budget of one slab of groups: sum over its groups of (points after the split) * windows + windows * c * 2^(c - 1), the sorted entries and gathered bucket points that are in scratch at a time; a group that exceeds it alone is a slab of its own (default 2^23; 0 = the default) */
 #define NBLS_TUNE_CELLS_CHUNK 20      /* (19 stays unassigned: tests/test_msm_batch_abi.py pins it as the first unknown key behind the batched MSM's) blobs that nbls_kzg_compute_cells_and_proofs hands to the batched MSM in one pass; 0 (default) = as many whole blobs as its bounds of 2^22 scalars and 2^20 rows take (8 mainnet blobs); a larger value than that changes nothing.  The bytes do not depend on it: it lets a test cross chunk borders with small blobs */
+#define NBLS_TUNE_G16_CHUNK 22        /* (21 stays unassigned: tests/test_kzg_fk20_abi.py pins it as the first unknown key behind NBLS_TUNE_CELLS_CHUNK) proofs that the per-proof pass of nbls_groth16_verify and nbls_groth16_prepare_inputs hand to the batched MSM in one pass; 0 (default) = as many whole proofs as its bounds of 2^22 scalars and 2^20 rows take; a larger value than that changes nothing.  The bytes do not depend on it: it lets a test cross chunk borders with few proofs */
 int nbls_set_tuning(nbls_ctx* ctx, int key, long long value);
 int nbls_program_count(void);                 /* number of step programs; timing slot nbls_program_count() = the inversion kernel */
 const char* nbls_program_name(int prog);

@@ -641,4 +641,69 @@ NBLS_FR_HD uint32_t fr_recover_compare(const uint32_t* a, const uint8_t* cells, 
   return diff ? 0xffffffffu : 0u;
 }
 
+// ---- The weighted sums of Groth16 public inputs (g16_input_sums_kernel, g16_sum_kernel and nbls_sim_g16_input_sums).  n proofs with m inputs each, the matrix row-major by
+// proof (row i = the m inputs of proof i, 32 bytes big-endian each, 16-byte aligned), one weight w_i < 2^64 per row:
+//   S_0 = sum_i w_i,   S_j = sum_i w_i x_(i,j),  j = 1 .. m,   over the rows that are in: pre[i] == 0 and every element of the row < r.
+// The m + 1 columns of the result are walked by lanes: column 0 reads nothing (its element is 1), column c >= 1 reads element c - 1 of the row, so a wavefront's 64 lanes load
+// 64 consecutive elements.  A workgroup of G16_LANES lanes is G16_GROUPS wavefronts on ONE tile of G16_TILE columns and on the rows q, q + groups, .. of its G16_GROUPS
+// row groups (q = the workgroup's number among those of its tile * G16_GROUPS + wavefront; groups = G16_GROUPS * the launch's workgroups per tile: G16_ROWS_WG rows a workgroup until G16_MAX_WG of them
+// are reached, more rows each from there on, so that the partial rows stay few).  Sixteen wavefronts a workgroup, four rows each: a row's loads wait for memory once per row,
+// and with four wavefronts of sixteen rows the kernel took 28 us at 8192 x 16 and 88 us at 8192 x 328, the latency of sixteen dependent rounds.
+// A row is in or out as a whole, so the wavefront looks at ALL its elements before it adds one: with m + 1 <= G16_TILE -- one tile -- every element is loaded once and checked
+// where it is used; with more tiles the wavefront walks the row's other tiles for the check alone (the tiles of a row run side by side and meet in the cache; the check is eight
+// subtractions an element against ~40 multiply-adds for the product).  Tile 0 writes the row's status.
+// The products are NOT reduced one by one: w x < 2^64 * 2^256 = 2^320 is added into an accumulator of G16_ACC_NL limbs, 16 multiply-adds a row where a Montgomery product
+// takes 136 (and the weight stays the two plain words it came as: there is no Montgomery form to bring it to), and a lane reduces ONCE, after its last row (g16_reduce).  The
+// bound on the rows per reduction stands next to the accumulator's width below.  Fr addition is exact, so neither the split into workgroups nor the tree's order changes a byte.
+enum { G16_TILE = 64, G16_GROUPS = 16, G16_LANES = G16_TILE * G16_GROUPS, G16_ROWS_WG = 64, G16_MAX_WG = 1024, G16_ACC_NL = 11 };
+static const uint64_t G16_MAX_ELEMS = (uint64_t)1 << 24;   // n * m of one call; a lane adds at most one product per row of the call, and n <= n * m
+struct G16Acc { uint32_t l[G16_ACC_NL]; };
+static_assert(G16_MAX_ELEMS <= ((uint64_t)1 << (32 * G16_ACC_NL - 320)), "rows per reduction: 2^32 products below 2^320 stay below 2^352, the accumulator's eleven limbs");
+NBLS_FR_HD uint32_t g16_tiles(uint32_t m) { return m / G16_TILE + 1; }   // ceil((m + 1) / G16_TILE)
+NBLS_FR_HD uint32_t g16_workgroups(uint32_t n) { const uint32_t w = (n + G16_ROWS_WG - 1) / G16_ROWS_WG; return w > G16_MAX_WG ? (uint32_t)G16_MAX_WG : w; }
+NBLS_FR_HD G16Acc g16_acc_zero() { G16Acc a; for (int i = 0; i < G16_ACC_NL; i++) a.l[i] = 0; return a; }
+// acc += x * (whi 2^32 + wlo): two rows of operand scanning, the carry walked to the accumulator's top
+NBLS_FR_HD void g16_mac(G16Acc& acc, const Fr& x, uint32_t wlo, uint32_t whi) {
+#pragma unroll
+  for (int k = 0; k < 2; k++) {
+    const uint32_t w = k ? whi : wlo;
+    uint64_t c = 0;
+#pragma unroll
+    for (int j = 0; j < FR_NL; j++) { c += (uint64_t)x.l[j] * w + acc.l[j + k]; acc.l[j + k] = (uint32_t)c; c >>= 32; }
+#pragma unroll
+    for (int j = FR_NL + k; j < G16_ACC_NL; j++) { c += acc.l[j]; acc.l[j] = (uint32_t)c; c >>= 32; }
+  }
+}
+// the accumulator mod r, plain: lo + hi 2^256 with lo = the low eight limbs (lo R^2 / R = lo R, then out of Montgomery form) and hi < 2^96 (hi R^2 / R = hi 2^256)
+NBLS_FR_HD Fr g16_reduce(const G16Acc& acc) {
+  Fr lo, hi = fr_zero();
+#pragma unroll
+  for (int i = 0; i < FR_NL; i++) lo.l[i] = acc.l[i];
+#pragma unroll
+  for (int i = FR_NL; i < G16_ACC_NL; i++) hi.l[i - FR_NL] = acc.l[i];
+  return fr_add(fr_from_mont(fr_mul(lo, fr_r2())), fr_mul(hi, fr_r2()));
+}
+// One row on one lane: the lane's own element -- column tile * G16_TILE + lane of the result: 1 for column 0, zero past column m -- and in *bad all ones when an element of
+// the row that this lane looked at is >= r (the wavefront ORs the lanes).  Lanes past the row's end read nothing
+NBLS_FR_HD Fr g16_row_lane(const uint8_t* row32, uint32_t m, uint32_t tiles, uint32_t tile, uint32_t lane, uint32_t* bad) {
+  Fr x = fr_zero(); uint32_t b = 0;
+  for (uint32_t tt = 0; tt < tiles; tt++) {
+    const uint32_t c = tt * G16_TILE + lane;
+    if (c < 1 || c > m) continue;
+    const Fr v = fr_load_q(row32 + 32ull * (c - 1));
+    b |= fr_ge_r_mask(v);
+    if (tt == tile) x = v;
+  }
+  if (tile == 0 && lane == 0) x.l[0] = 1;
+  *bad = b;
+  return x;
+}
+// the row's product into the lane's accumulator: the weight's two words (w32: 32 bytes big-endian, < 2^64) under the row's mask (all ones: the row is out)
+NBLS_FR_HD void g16_row_add(G16Acc& acc, const Fr& x, const uint8_t* w32, uint32_t out) {
+  const Fr w = fr_load_q(w32);
+  g16_mac(acc, x, w.l[0] & ~out, w.l[1] & ~out);
+}
+// the row's status: what came in, else NBLS_ST_NON_CANONICAL for an element >= r, else 0
+NBLS_FR_HD int g16_row_status(int pre, uint32_t bad) { return pre ? pre : (int)(bad & 21); }
+
 }  // namespace nbls

@@ -92,4 +92,12 @@ int nbls_kzg_cell_interp_launch(unsigned log2_cell, unsigned n_cells, int sum, c
 int nbls_kzg_cell_pre_launch(unsigned n, const void* dstc, const void* dstp, const uint32_t* ci, void* pre0, hipStream_t stream);
 int nbls_kzg_cell_items_launch(unsigned n, const void* dstc, const void* dstp, const uint32_t* ci, const uint32_t* cell_index, const void* pre, const void* w32, const void* sroots,
                                const void* gen96, const void* affc, void* affp, void* gath, void* gst, void* s1, void* s2, void* s3, void* zs, hipStream_t stream);
+// groth16_kernels.hip
+int nbls_g16_input_sums_launch(unsigned n, unsigned m, const void* inputs32, const void* w32, const void* pre, void* partial, void* out32, void* st_out, hipStream_t stream);
+int nbls_g16_split_launch(unsigned n, const void* proofs192, void* ac48, void* b96, hipStream_t stream);
+int nbls_g16_pre_launch(unsigned n, const void* sta, const void* stb, const void* stc, void* pre0, hipStream_t stream);
+int nbls_g16_items_launch(unsigned n, const void* pre, const void* w32, const void* gen96, const void* g2_192, void* a96, void* c96, void* b192, void* s1, hipStream_t stream);
+int nbls_g16_rows_launch(unsigned n, unsigned m, const void* pre, void* rows32, hipStream_t stream);
+int nbls_g16_status_launch(unsigned n, const void* pre, const void* one, void* status, hipStream_t stream);
+int nbls_g16_prepare_tail_launch(unsigned n, const void* zero, const void* pre, void* out48, void* status, hipStream_t stream);
 }

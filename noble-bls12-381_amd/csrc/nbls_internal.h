@@ -1,5 +1,5 @@
 // nbls_internal.h -- what the translation units of the runtime share (runtime.cpp / tuning.cpp / pipelines_pairing.cpp / pipelines_codec.cpp / pipelines_verify.cpp / pipelines_multi_verify.cpp / pipelines_threshold.cpp /
-// pipelines_poly.cpp / pipelines_msm.cpp / kzg_common.cpp / pipelines_kzg.cpp / pipelines_kzg_prove.cpp / pipelines_kzg_cells.cpp / pipelines_kzg_verify_cells.cpp; pool and multi-device handles: nbls_multi.cpp): the context, the
+// pipelines_poly.cpp / pipelines_msm.cpp / kzg_common.cpp / pipelines_kzg.cpp / pipelines_kzg_prove.cpp / pipelines_kzg_cells.cpp / pipelines_kzg_verify_cells.cpp / pipelines_groth16.cpp; pool and multi-device handles: nbls_multi.cpp): the context, the
 // map of its scratch slots (enum Slot: the one place that says which chain owns which slot, checked at compile time), the launch helpers, the staged block of the host-buffer pipelines (staging.h, included at the end) and the
 // device-side pipelines the exported entry points are built from.  Internal functions have hidden visibility (csrc/Makefile: -fvisibility=hidden).
 #pragma once
@@ -96,9 +96,13 @@ enum Slot {
   // cells_pipeline's FK20 proofs loop (nbls_kzg_*_cells_and_proofs_fk20, pipelines_kzg_cells.cpp): one chunk's scalars of pass A and the rows' statuses | one chunk's sums of
   // pass A in the converted projective form, the points of pass B.  They stand where the quotient rows (SB_KZGC_ROWS) stand in the other form
   SB_KZGF_SCALARS = 80, SB_KZGF_POINTS = 81,
+  // groth16_pipeline, nbls_groth16_prepare_inputs and nbls_groth16_input_sums (pipelines_groth16.cpp): the proofs' points split, decoded and weighted, their statuses | weights,
+  // the scalars of the MSM over the C_i, the partial rows and the m + 1 sums | the three combined points, the product's final exponentiation | what is read back | everything
+  // of one chunk of the per-proof pass (L_i, the final exponentiations, the verdicts)
+  SB_G16_POINTS = 82, SB_G16_SCALARS = 83, SB_G16_PAIRS = 84, SB_G16_OUT = 85, SB_G16_ITEMS = 86,
   NSB
 };
-static_assert(NSB == 82, "sb[] indices do not shift");
+static_assert(NSB == 87, "sb[] indices do not shift");
 constexpr SlotMask slot_bit(int i) { return (SlotMask)1 << i; }
 template <typename... S> constexpr SlotMask slots(S... s) { return (slot_bit(s) | ...); }
 // one instance of dev_decompress: three arrays of field elements and the exponentiation table
@@ -162,6 +166,11 @@ static_assert(!(M_KZGV_OWN & (DEC_MAIN.mask() | MSM_RLC.mask() | M_LADDER | M_MS
               "verify_cells_pipeline: the decoder, the MSMs (on the slots of MSM_RLC: MSM_MAIN holds SB_STAGED), the batched MSM and the ladder of the per-cell pass regrow their slots while the call holds the staged block and its own");
 static_assert(!((M_KZGV_OWN & ~slot_bit(SB_STAGED)) & (M_KZGC_OWN | M_KZGP_OWN | M_KZG_OWN | M_POLY_OWN | M_THR_OWN | M_RLC_MAIN | M_RLC_SIDE | M_RLC_SIDE2 | M_VB_MAIN | MSM_MAIN.mask())),
               "verify_cells_pipeline keeps to slots of its own");
+constexpr SlotMask M_G16_OWN = slots(SB_STAGED, SB_G16_POINTS, SB_G16_SCALARS, SB_G16_PAIRS, SB_G16_OUT, SB_G16_ITEMS);   // groth16_pipeline: what outlives the decoders, the ladders, the MSMs and the batched MSM it calls
+static_assert(!(M_G16_OWN & (DEC_MAIN.mask() | MSM_RLC.mask() | M_LADDER | M_MSMB_OWN)),
+              "groth16_pipeline: the decoders, the MSMs (on the slots of MSM_RLC: MSM_MAIN holds SB_STAGED), the ladder and the batched MSM of the per-proof pass regrow their slots while the call holds the staged block and its own");
+static_assert(!((M_G16_OWN & ~slot_bit(SB_STAGED)) & (M_KZGV_OWN | M_KZGF_OWN | M_KZGR_OWN | M_KZGC_OWN | M_KZGP_OWN | M_KZG_OWN | M_POLY_OWN | M_THR_OWN | M_RLC_MAIN | M_RLC_SIDE | M_RLC_SIDE2 | M_VB_MAIN | MSM_MAIN.mask())),
+              "groth16_pipeline keeps to slots of its own");
 // ---- END scratch slots -------------------------------------------------------------------------------------------------------------------------------------
 #define EXPORT extern "C" __attribute__((visibility("default")))
 extern std::recursive_mutex g_null_mu;   // locked in place of a context's mutex when the caller passed no context (the call then fails with NBLS_EINVAL)
@@ -191,6 +200,7 @@ struct nbls_ctx {
   // the defaults (pipelines_msm.cpp)
   size_t msmb_window = 0, msmb_big = 0, msmb_slab = 0;
   size_t cells_chunk = 0;       // nbls_set_tuning(NBLS_TUNE_CELLS_CHUNK): blobs per pass of nbls_kzg_compute_cells_and_proofs; 0 = as many as the batched MSM takes (pipelines_kzg_cells.cpp)
+  size_t g16_chunk = 0;         // nbls_set_tuning(NBLS_TUNE_G16_CHUNK): proofs per pass of the per-proof pass of nbls_groth16_verify and of nbls_groth16_prepare_inputs; 0 = as many as the batched MSM takes (pipelines_groth16.cpp)
   // scratch (device)
   uint8_t *F = nullptr, *N = nullptr, *NI = nullptr, *io_g1 = nullptr, *io_g2 = nullptr, *io_f12 = nullptr, *one12 = nullptr;
   uint8_t* T[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // t1..t7 of the final exponentiation, raw Fp12
@@ -494,6 +504,9 @@ struct KzgFrame {
   int items_begin(size_t front, uint8_t** FRONT, MsmbPlan* rows_plan = nullptr, size_t row_pts = 0);
   int items_close(const uint8_t* proofs96, const uint8_t* proof_st, int* all_ok, int8_t* status);
 };
+// the verifying key of nbls_groth16_* (pipelines_groth16.cpp): one device block.  alpha96: alpha affine; g2neg: -beta, -gamma, -delta affine (3 x 192 wire bytes); tables: their
+// three line tables; ic96: the m + 1 points IC_j affine; ic_conv: the same in the form the batched MSM reads (P_G1_MSM_PREP: 2 x 3 raw elements a point); ic0_proj: IC_0 raw projective
+struct nbls_groth16_vk { int device = 0; size_t m = 0; uint8_t *mem = nullptr, *alpha96 = nullptr, *g2neg = nullptr, *tables = nullptr, *ic96 = nullptr, *ic_conv = nullptr, *ic0_proj = nullptr; };
 int msm_host(nbls_ctx* ctx, bool g2, size_t n, const uint8_t* pts, const uint8_t* scalars32, uint8_t* out, int8_t* status);
 int dst_on_device(nbls_ctx* ctx, const uint8_t* dst, size_t* dst_len, hipStream_t s, uint8_t** dd);
 std::vector<size_t> verify_plan(nbls_ctx* ctx, size_t n);

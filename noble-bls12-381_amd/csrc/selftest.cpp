@@ -24,6 +24,7 @@ extern "C" int nbls_sim_kzg_cell_interp(unsigned log2_n, unsigned log2_cell, siz
                                         const int8_t* pre, const uint8_t* w32, uint8_t* out, int8_t* st_out);
 extern "C" int nbls_sim_kzg_recover(unsigned log2_n, unsigned log2_cell, size_t n, const uint32_t* cell_offsets, const uint32_t* cell_index, const uint8_t* cells,
                                     uint8_t* out_cells, uint8_t* coef32, int8_t* status);
+extern "C" int nbls_sim_g16_input_sums(size_t n, size_t m, unsigned n_wg, const uint8_t* inputs32, const uint8_t* weights32, const int8_t* pre, uint8_t* out32, int8_t* status);
 using namespace nbls;
 
 static void be48(uint8_t* o, const u32* limbs) { u32 w[12]; limbs_to_words(w, limbs); for (int i = 0; i < 12; i++) { u32 v = w[11 - i]; o[4 * i] = v >> 24; o[4 * i + 1] = v >> 16; o[4 * i + 2] = v >> 8; o[4 * i + 3] = v; } }
@@ -121,6 +122,17 @@ int main() {
     }
   }
   printf("transform, cell rows, cell interpolation and recovery ok\n");
+  // the weighted input sums of Groth16 in buffers of exactly the call's sizes: one tile and its last lane (m = 63), two tiles with one element in the second (m = 64), three
+  // (m = 129); rows below, at and above a workgroup's 64; weight one, so that column 0 is the number of rows that are in; row 1 out beforehand
+  for (size_t m : {(size_t)1, (size_t)63, (size_t)64, (size_t)129}) for (size_t n : {(size_t)2, (size_t)64, (size_t)65}) {
+    std::vector<uint8_t> x(n * m * 32), w(n * 32), out((m + 1) * 32); std::vector<int8_t> pre(n), st(n, 1);
+    for (size_t i = 0; i < x.size(); i++) x[i] = (i % 32) ? (uint8_t)(i * 41 + 3) : 0;   // (top byte 0: canonical)
+    for (size_t i = 0; i < n; i++) w[32 * i + 31] = 1;
+    pre[1] = 13;
+    if (nbls_sim_g16_input_sums(n, m, 0, x.data(), w.data(), pre.data(), out.data(), st.data()) || nbls_sim_g16_input_sums(n, m, 3, x.data(), w.data(), nullptr, out.data(), nullptr)) return 2;
+    if (out[31] != n || st[0] || st[1] != 13) { printf("G16 SUMS: the count of rows or a status differs\n"); bad++; }
+  }
+  printf("groth16 input sums ok\n");
   if (memcmp(out1, out2, 576)) { printf("MISMATCH between the fused and the split Miller loop\n"); bad++; }
   printf("miller c0.c0.c0 ");
   for (int i = 0; i < 48; i++) printf("%02x", out1[i]);

@@ -145,6 +145,7 @@ EXPORT int nbls_set_tuning(nbls_ctx* ctx, int key, long long value) {
     case NBLS_TUNE_MSMB_BIG: if (value < 0) return NBLS_EINVAL; ctx->msmb_big = (size_t)value; return NBLS_OK;
     case NBLS_TUNE_MSMB_SLAB: if (value < 0) return NBLS_EINVAL; ctx->msmb_slab = (size_t)value; return NBLS_OK;
     case NBLS_TUNE_CELLS_CHUNK: if (value < 0) return NBLS_EINVAL; ctx->cells_chunk = (size_t)value; return NBLS_OK;
+    case NBLS_TUNE_G16_CHUNK: if (value < 0) return NBLS_EINVAL; ctx->g16_chunk = (size_t)value; return NBLS_OK;
     default: return NBLS_EINVAL;
   }
 }

@@ -837,6 +837,43 @@ __attribute__((visibility("default"))) int nbls_sim_kzg_recover(unsigned log2_n,
   }
   return 0;
 }
+// nbls_groth16_input_sums as g16_input_sums_kernel and g16_sum_kernel run it: per tile of columns and workgroup of rows the G16_GROUPS wavefronts row after row -- every lane's
+// look at the row, the wavefront's OR of the lanes' canonical checks, the masked product into the lane's accumulator --, ONE reduction per lane, the column tree in the
+// kernel's order, the partial rows, the closing kernel's walk and tree.  n_wg: the workgroups per tile (0: as many as the launcher takes).  pre and status may be NULL.
+// Returns -1 under the rules of the device call that need no context (a weight >= 2^64 among them)
+__attribute__((visibility("default"))) int nbls_sim_g16_input_sums(size_t n, size_t m, unsigned n_wg, const uint8_t* inputs32, const uint8_t* weights32, const int8_t* pre,
+                                                                   uint8_t* out32, int8_t* status) {
+  if (!n || !m || !inputs32 || !weights32 || !out32 || n > G16_MAX_ELEMS || m > G16_MAX_ELEMS || n * m > G16_MAX_ELEMS) return -1;
+  for (size_t i = 0; i < n; i++) for (int k = 0; k < 24; k++) if (weights32[32 * i + k]) return -1;
+  const u32 M = (u32)m, tiles = g16_tiles(M), wgs = n_wg ? n_wg : g16_workgroups((u32)n), groups = wgs * G16_GROUPS, W = G16_LANES, T = G16_TILE;
+  std::vector<Fr> partial((size_t)wgs * (m + 1)), part(W), x(T);
+  std::vector<G16Acc> acc(W);
+  auto tree = [&]() { for (u32 s = W / 2; s >= T; s >>= 1) for (u32 t = 0; t < s; t++) part[t] = fr_add(part[t], part[t + s]); };
+  for (u32 tile = 0; tile < tiles; tile++) for (u32 b = 0; b < wgs; b++) {
+    for (u32 t = 0; t < W; t++) acc[t] = g16_acc_zero();
+    for (u32 g = 0; g < G16_GROUPS; g++) for (uint64_t i = b * G16_GROUPS + g; i < n; i += groups) {
+      u32 bad = 0;
+      for (u32 lane = 0; lane < T; lane++) { u32 bl; x[lane] = g16_row_lane(inputs32 + i * m * 32, M, tiles, tile, lane, &bl); bad |= bl; }
+      const int p = pre ? pre[i] : 0;
+      for (u32 lane = 0; lane < T; lane++) g16_row_add(acc[g * T + lane], x[lane], weights32 + 32 * i, bad | ((u32)0 - (u32)(p != 0)));
+      if (status && tile == 0) status[i] = (int8_t)g16_row_status(p, bad);
+    }
+    for (u32 t = 0; t < W; t++) part[t] = g16_reduce(acc[t]);
+    tree();
+    for (u32 t = 0; t < T; t++) if (tile * T + t <= M) partial[(size_t)b * (m + 1) + tile * T + t] = part[t];
+  }
+  for (u32 tile = 0; tile < tiles; tile++) {
+    for (u32 t = 0; t < W; t++) {
+      const u32 c = tile * T + (t & (T - 1));
+      Fr a = fr_zero();
+      if (c <= M) for (u32 p = t / T; p < wgs; p += G16_GROUPS) a = fr_add(a, partial[(size_t)p * (m + 1) + c]);
+      part[t] = a;
+    }
+    tree();
+    for (u32 t = 0; t < T; t++) if (tile * T + t <= M) fr_store_q(part[t], out32 + 32ull * (tile * T + t));
+  }
+  return 0;
+}
 __attribute__((visibility("default"))) int nbls_sim_program_count() { return (int)P_COUNT; }
 __attribute__((visibility("default"))) void nbls_sim_stats() { for (int i = 0; i < P_COUNT; i++) print_stats(get_program((ProgId)i)); }
 }

@@ -108,6 +108,13 @@ def load_library():
     lib.nbls_kzg_fk20_params.argtypes = [vp, C.POINTER(C.c_uint), C.POINTER(C.c_uint)]
     lib.nbls_kzg_compute_cells_and_proofs_fk20.argtypes = [vp, vp, sz, vp, vp, vp, vp]
     lib.nbls_kzg_recover_cells_and_proofs_fk20.argtypes = [vp, vp, sz, vp, vp, vp, vp, vp, vp]
+    lib.nbls_groth16_vk_create.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, C.POINTER(vp)]
+    lib.nbls_groth16_vk_destroy.argtypes = [vp]
+    lib.nbls_groth16_vk_destroy.restype = None
+    lib.nbls_groth16_vk_inputs.argtypes = [vp, C.POINTER(sz)]
+    lib.nbls_groth16_verify.argtypes = [vp, vp, sz, vp, vp, vp, C.POINTER(i32), vp]
+    lib.nbls_groth16_prepare_inputs.argtypes = [vp, vp, sz, vp, vp, vp]
+    lib.nbls_groth16_input_sums.argtypes = [vp, sz, sz, vp, vp, vp, vp, vp]
     lib.nbls_keyset_create.argtypes = [vp, sz, vp, vp, C.POINTER(vp)]
     lib.nbls_keyset_destroy.argtypes = [vp]
     lib.nbls_keyset_destroy.restype = None
@@ -279,6 +286,33 @@ class KzgMonomialSetup:
     def close(self):
         if getattr(self, 'h', None):
             self.lib.nbls_kzg_monomial_destroy(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Groth16Vk:
+    """A Groth16 verifying key in device memory (nbls_groth16_vk_create; Engine.groth16_vk): alpha, the line tables of -beta, -gamma, -delta and the IC points, decoded and
+    converted once.  Usable from every Engine on its device.  Freed by close() or when the object goes away."""
+
+    def __init__(self, lib, handle):
+        self.lib = lib
+        self.h = handle
+
+    @property
+    def inputs(self):
+        m = C.c_size_t(0)
+        if self.h is None or self.lib.nbls_groth16_vk_inputs(self.h, C.byref(m)) != 0:
+            raise NblsError('Groth16Vk: the key is closed')
+        return m.value
+
+    def close(self):
+        if getattr(self, 'h', None):
+            self.lib.nbls_groth16_vk_destroy(self.h)
         self.h = None
 
     def __del__(self):
@@ -670,6 +704,66 @@ class Engine:
         st = C.create_string_buffer(max(n, 1)) if per_item else None
         self._chk(self.lib.nbls_kzg_verify_blobs(self.h, log2_n, n, b''.join(blobs), b''.join(commitments48), b''.join(proofs48), bytes(tau_g2_96), seed, C.byref(ok), st))
         return bool(ok.value), (st.raw[:n] if per_item else None)
+
+    # ---- Groth16 (include/nbls.h: nbls_groth16_*)
+    def groth16_vk(self, alpha_g1_48, beta_g2_96, gamma_g2_96, delta_g2_96, ic48):
+        """the verifying key's compressed points (ic48: the m + 1 points IC_0 .. IC_m, a list of 48-byte values or their concatenation) -> Groth16Vk, usable from every Engine
+        on this device.  Raises KzgSetupError (with the statuses of alpha, beta, gamma, delta, IC_0 .. IC_m) when an entry does not decode or is the zero point"""
+        raw = bytes(ic48) if isinstance(ic48, (bytes, bytearray, memoryview)) else b''.join(bytes(x) for x in ic48)
+        m = len(raw) // 48 - 1
+        if len(raw) % 48 or not 1 <= m <= 1 << 16 or len(alpha_g1_48) != 48 or any(len(x) != 96 for x in (beta_g2_96, gamma_g2_96, delta_g2_96)):
+            raise NblsError('groth16_vk: 48 bytes of alpha, 96 bytes each of beta, gamma, delta and the 2 .. 2^16 + 1 points IC_j of 48 bytes each')
+        st = C.create_string_buffer(m + 5)
+        h = C.c_void_p()
+        r = self.lib.nbls_groth16_vk_create(self.h, m, bytes(alpha_g1_48), bytes(beta_g2_96), bytes(gamma_g2_96), bytes(delta_g2_96), raw, st, C.byref(h))
+        if r != 0:
+            raise KzgSetupError('groth16_vk: %s (code %d)' % (self.lib.nbls_strerror(r).decode(), r), r, st.raw)
+        return Groth16Vk(self.lib, h)
+
+    def _g16_inputs(self, name, m, inputs):
+        """inputs: one row of m field elements (ints or 32-byte values) per proof -> (n, the packed matrix)"""
+        if not inputs or any(len(row) != m for row in inputs):
+            raise NblsError('%s: one row or more, every row has %d inputs' % (name, m))
+        return len(inputs), b''.join(self._fr32(x) for row in inputs for x in row)
+
+    def groth16_verify(self, vk, proofs192, inputs, seed=None, per_item=True):
+        """n proofs (192 bytes each: A || B || C compressed) with their rows of public inputs against one key -> (all_ok, status bytes or None).  statuses: 0 ok, 9 not
+        verified, 1 / 3 / 4 A is the zero point / does not decode, 11 / 13 / 14 B, 31 / 33 / 34 C, 21 an input is >= r; seed: 32 bytes, None = from the OS; per_item=False:
+        the combined check alone (fast reject)"""
+        if getattr(vk, 'h', None) is None:
+            raise NblsError('groth16_verify: the key is closed')
+        n, mat = self._g16_inputs('groth16_verify', vk.inputs, inputs)
+        if len(proofs192) != n or any(len(p) != 192 for p in proofs192) or (seed is not None and len(seed) != 32):
+            raise NblsError('groth16_verify: %d rows of inputs need %d proofs of 192 bytes and a seed of 32 bytes or None' % (n, n))
+        ok = C.c_int(0)
+        st = C.create_string_buffer(n) if per_item else None
+        self._chk(self.lib.nbls_groth16_verify(self.h, vk.h, n, b''.join(bytes(p) for p in proofs192), mat, seed, C.byref(ok), st))
+        return bool(ok.value), (st.raw[:n] if per_item else None)
+
+    def groth16_prepare_inputs(self, vk, inputs):
+        """L_i = IC_0 + sum_j [x_ij]IC_j of every row -> (list of 48-byte compressed points, status list: 0, 1 = the zero point (0xc0 00..), 21 = an input is >= r (48 zero
+        bytes))"""
+        if getattr(vk, 'h', None) is None:
+            raise NblsError('groth16_prepare_inputs: the key is closed')
+        n, mat = self._g16_inputs('groth16_prepare_inputs', vk.inputs, inputs)
+        out, st = C.create_string_buffer(48 * n), C.create_string_buffer(n)
+        self._chk(self.lib.nbls_groth16_prepare_inputs(self.h, vk.h, n, mat, out, st))
+        raw = out.raw
+        return [raw[48 * i:48 * i + 48] for i in range(n)], list(st.raw[:n])
+
+    def groth16_input_sums(self, inputs, weights, pre=None):
+        """the folding kernel on caller-chosen weights (< 2^64): rows of m inputs each -> (the m + 1 sums sum w_i, sum w_i x_ij mod r as ints, status list) over the rows with
+        pre[i] == 0 and all inputs canonical"""
+        m = len(inputs[0]) if inputs else 0
+        if not m:
+            raise NblsError('groth16_input_sums: one row or more of one input or more')
+        n, mat = self._g16_inputs('groth16_input_sums', m, inputs)
+        if len(weights) != n or (pre is not None and len(pre) != n):
+            raise NblsError('groth16_input_sums: %d rows need %d weights' % (n, n))
+        out, st = C.create_string_buffer(32 * (m + 1)), C.create_string_buffer(n)
+        self._chk(self.lib.nbls_groth16_input_sums(self.h, n, m, mat, b''.join(self._fr32(w) for w in weights), None if pre is None else bytes(bytearray(int(p) & 0xff for p in pre)), out, st))
+        raw = out.raw
+        return [int.from_bytes(raw[32 * j:32 * j + 32], 'big') for j in range(m + 1)], list(st.raw[:n])
 
     # ---- KZG, the prover's side (include/nbls.h: nbls_kzg_setup_*, nbls_fr_quotient_roots, nbls_kzg_commit_blobs, nbls_kzg_compute_proofs, nbls_kzg_compute_blob_proofs)
     def kzg_setup(self, log2_n, lagrange48):
@@ -1122,6 +1216,10 @@ class Engine:
     def set_cells_chunk(self, blobs):
         """blobs that kzg_compute_cells_and_proofs hands to the batched MSM in one pass (NBLS_TUNE_CELLS_CHUNK = 20; 0: as many as its bounds take)"""
         self._chk(self.lib.nbls_set_tuning(self.h, 20, int(blobs)))
+
+    def set_groth16_chunk(self, proofs):
+        """proofs that the per-proof pass of groth16_verify and groth16_prepare_inputs hand to the batched MSM in one pass (NBLS_TUNE_G16_CHUNK = 22; 0: as many as its bounds take)"""
+        self._chk(self.lib.nbls_set_tuning(self.h, 22, int(proofs)))
 
     def set_verify_pipeline(self, chunks=None, last_pct=None, pipe_min=None):
         """verifyBatch as a software pipeline (NBLS_TUNE_VERIFY_CHUNKS / _LAST_PCT / _PIPE_MIN): number of chunks (0 / 1: one), size of the last chunk in

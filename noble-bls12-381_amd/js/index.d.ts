@@ -118,6 +118,12 @@ export declare class PointG1 {
     proofs: (PointG1 | Hex)[], tauCG2: PointG2 | Hex, opts?: KzgOptions): KzgResult;
   static verifyCellKzgProofBatchAsync(setup: KzgMonomialSetup, log2cell: number, commitments: (PointG1 | Hex)[], commitmentIndices: number[], cellIndices: number[], cells: Hex[],
     proofs: (PointG1 | Hex)[], tauCG2: PointG2 | Hex, opts?: KzgOptions): Promise<KzgResult>;
+  /** Groth16 over BLS12-381: n proofs (192 bytes each, A || B || C compressed; an array of bytes / hex or ONE packed Uint8Array) with their rows of public inputs (an array of
+   *  rows, or ONE packed Uint8Array of 32 bytes per input) against one key, by a random linear combination; status per proof: 0, 9 not verified, 1 / 3 / 4 A, 11 / 13 / 14 B,
+   *  31 / 33 / 34 C (the zero point / does not decode), 21 a non-canonical input */
+  static readonly Groth16Vk: typeof Groth16Vk;
+  static verifyGroth16Batch(vk: Groth16Vk, proofs: Hex[] | Uint8Array, inputs: ShareId[][] | Uint8Array, opts?: KzgOptions): KzgResult;
+  static verifyGroth16BatchAsync(vk: Groth16Vk, proofs: Hex[] | Uint8Array, inputs: ShareId[][] | Uint8Array, opts?: KzgOptions): Promise<KzgResult>;
   isZero(): boolean; equals(rhs: PointG1): boolean; negate(): PointG1; add(rhs: PointG1): PointG1; subtract(rhs: PointG1): PointG1; double(): PointG1;
   multiply(scalar: bigint | number): PointG1; multiplyUnsafe(scalar: bigint | number): PointG1; multiplyPrecomputed(scalar: bigint | number): PointG1;
   assertValidity(): this; toAffine(): [Fp, Fp]; toRawBytes(isCompressed?: boolean): Uint8Array; toHex(isCompressed?: boolean): string;
@@ -177,6 +183,13 @@ declare class KzgSetup {
 declare class KzgMonomialSetup {
   constructor(points: (PointG1 | Hex)[]);
   readonly log2n: number;
+  close(): void;
+}
+/** A Groth16 verifying key decoded once into device memory (alpha and the m + 1 points ic in G1, beta, gamma, delta in G2, all compressed); close() frees it.  Parsing
+ *  bellman's uncompressed key file stays with the caller.  Reached as PointG1.Groth16Vk */
+declare class Groth16Vk {
+  constructor(key: { alpha: PointG1 | Hex; beta: PointG2 | Hex; gamma: PointG2 | Hex; delta: PointG2 | Hex; ic: (PointG1 | Hex)[] });
+  readonly inputs: number;
   close(): void;
 }
 /** status: one byte per polynomial (0; 21 an element or the shift is >= CURVE.r; 5 the shift is 0: the row is then all-zero) */

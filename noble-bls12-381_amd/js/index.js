@@ -378,6 +378,49 @@ async function verifyCellKzgProofBatchAsync(setup, log2cell, commitments, commit
   try { return kzgResult(await native.kzgVerifyCellsAsync(...a), a[9]); } catch (e) { return kzgFail(e); }
 }
 
+// ---- Groth16 (nbls_groth16_vk_*, nbls_groth16_verify; not in the reference): n proofs against one verifying key, checked together by a random linear combination.
+// new PointG1.Groth16Vk({alpha, beta, gamma, delta, ic}): alpha and the m + 1 points ic: 48 compressed bytes, hex or PointG1; beta, gamma, delta: 96 compressed bytes, hex or
+// PointG2; decoded once, close() frees it.  Parsing bellman's uncompressed key file stays with the caller.  verifyGroth16Batch(vk, proofs, inputs, {seed, perItem}): proofs =
+// an array of 192-byte proofs (A || B || C compressed: bytes or hex) or ONE packed Uint8Array of n * 192 bytes; inputs = an array of rows of m field elements (bigint | number |
+// hex | 32 bytes, canonical) or ONE packed Uint8Array of n * m * 32 bytes.  -> { ok, status } as verifyKzgProofBatch: status per proof 0 ok, 9 not verified, 1 / 3 / 4 A is the
+// zero point / does not decode, 11 / 13 / 14 B, 31 / 33 / 34 C, 21 a non-canonical input
+const g16G2 = (p, what) => { const b = p instanceof PointG2 ? p.toSignature() : ensureBytes(p); if (b.length !== 96) throw new Error('Invalid ' + what + ': expected 96 compressed bytes'); return b; };
+class Groth16Vk {
+  constructor(key) {
+    if (!key || !key.ic || key.ic.length < 2 || key.ic.length > 65537) throw new Error('Invalid key: expected alpha, beta, gamma, delta and 2 .. 65537 points ic');
+    ensureInit();
+    this.inputs = key.ic.length - 1;
+    const alpha = kzgG1(key.alpha);
+    if (alpha.length !== 48) throw new Error('Invalid alpha: expected 48 compressed bytes');
+    try { this.handle = native.groth16VkCreate(alpha, g16G2(key.beta, 'beta'), g16G2(key.gamma, 'gamma'), g16G2(key.delta, 'delta'), kzgPack(key.ic, 48, 'key point', kzgG1)); } catch (e) {
+      if (e && e.nblsCode === -5) { const err = new Error('Invalid key: a point does not decode, is outside the subgroup or is the zero point'); err.status = e.status; throw err; }
+      throw e;
+    }
+  }
+  close() { if (this.handle) native.groth16VkDestroy(this.handle); this.handle = null; }
+}
+function groth16Args(vk, proofs, inputs, opts) {
+  if (!(vk instanceof Groth16Vk) || !vk.handle) throw new Error('Expected an open Groth16Vk');
+  const packed = (v) => v instanceof Uint8Array;
+  const ps = packed(proofs) ? proofs : kzgPack(proofs, 192, 'proof', ensureBytes);
+  const n = ps.length / 192;
+  if (!n || !Number.isInteger(n)) throw new Error('Expected one proof or more of 192 bytes each');
+  let xs = inputs;
+  if (!packed(inputs)) {
+    if (inputs.length !== n) throw new Error('Expected as many rows of inputs as proofs');
+    xs = new Uint8Array(n * vk.inputs * 32);
+    for (let i = 0; i < n; i++) {
+      if (inputs[i].length !== vk.inputs) throw new Error('Invalid inputs: expected ' + vk.inputs + ' per proof');
+      xs.set(kzgPack(inputs[i], 32, 'field element', shareIdBytes), i * vk.inputs * 32);
+    }
+  }
+  if (xs.length !== n * vk.inputs * 32) throw new Error('Invalid inputs: expected ' + vk.inputs + ' per proof, 32 bytes each');
+  const perItem = !(opts && opts.perItem === false);
+  return [vk.handle, ps, xs, kzgSeed(opts), perItem ? 1 : 0];
+}
+function verifyGroth16Batch(vk, proofs, inputs, opts) { const a = groth16Args(vk, proofs, inputs, opts); return kzgResult(native.groth16Verify(...a), a[4]); }
+async function verifyGroth16BatchAsync(vk, proofs, inputs, opts) { const a = groth16Args(vk, proofs, inputs, opts); return kzgResult(await native.groth16VerifyAsync(...a), a[4]); }
+
 // Points are held as affine wire bytes (what the engine consumes) or as the zero point.  The reference's constructor form
 // new PointG1(x: Fp, y: Fp, z?: Fp) (index.ts:291) is accepted too: the projective triple is made affine on the host.
 class PointG1 {
@@ -526,6 +569,10 @@ class PointG1 {
   static verifyCellKzgProofBatchAsync(setup, log2cell, commitments, commitmentIndices, cellIndices, cells, proofs, tauCG2, opts) {
     return verifyCellKzgProofBatchAsync(setup, log2cell, commitments, commitmentIndices, cellIndices, cells, proofs, tauCG2, opts);
   }
+  // Groth16 (above): a verifying key on the device and the batched check of proofs against it
+  static get Groth16Vk() { return Groth16Vk; }
+  static verifyGroth16Batch(vk, proofs, inputs, opts) { return verifyGroth16Batch(vk, proofs, inputs, opts); }
+  static verifyGroth16BatchAsync(vk, proofs, inputs, opts) { return verifyGroth16BatchAsync(vk, proofs, inputs, opts); }
   equals(rhs) { return this.zero === rhs.zero && (this.zero || bytesToHex(this.aff) === bytesToHex(rhs.aff)); }
   // reference index.ts:359-381
   toHex(isCompressed = false) {

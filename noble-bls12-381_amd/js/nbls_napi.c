@@ -2,7 +2,7 @@
  * nbls_napi.c -- thin N-API addon: exposes the C ABI of libnbls.so (include/nbls.h) to Node.  No arithmetic here.
  * libnbls.so is loaded with dlopen at module init so the addon builds with plain gcc (no HIP needed):
  *     gcc -shared -fPIC -I/usr/include/node -I../../include nbls_napi.c -o nbls_napi.node -ldl
- * Calls are synchronous (they block for the duration of the GPU work) except verifyBatchAsync (and signBatchAsync, verifyMultipleAsync, verifyAggregatesAsync, verifyMultipleSharedAsync, verifyAggregatesSharedAsync, frOpAsync, lagrangeAtZeroAsync, combineSharesAsync, polyEvalAsync, kzgVerifyProofsAsync, kzgVerifyBlobsAsync, kzgProveAsync, frNttAsync, kzgComputeCellsAsync, kzgCellsAndProofsAsync, kzgVerifyCellsAsync), which runs on a libuv worker thread
+ * Calls are synchronous (they block for the duration of the GPU work) except verifyBatchAsync (and signBatchAsync, verifyMultipleAsync, verifyAggregatesAsync, verifyMultipleSharedAsync, verifyAggregatesSharedAsync, frOpAsync, lagrangeAtZeroAsync, combineSharesAsync, polyEvalAsync, kzgVerifyProofsAsync, kzgVerifyBlobsAsync, kzgProveAsync, frNttAsync, kzgComputeCellsAsync, kzgCellsAndProofsAsync, kzgVerifyCellsAsync, groth16VerifyAsync), which runs on a libuv worker thread
  * (napi_create_async_work) and resolves a Promise: the facade's verifyBatch uses it for wire-format inputs (the calls that can take tens of milliseconds).  Typed arrays are passed by reference (napi_get_typedarray_info), no copies.
  */
 #include <node_api.h>
@@ -26,6 +26,7 @@ SYM(nbls_kzg_verify_proofs) SYM(nbls_kzg_verify_blobs)
 SYM(nbls_kzg_setup_create) SYM(nbls_kzg_setup_destroy) SYM(nbls_kzg_setup_log2n) SYM(nbls_kzg_commit_blobs) SYM(nbls_kzg_compute_proofs) SYM(nbls_kzg_compute_blob_proofs)
 SYM(nbls_fr_ntt) SYM(nbls_kzg_compute_cells) SYM(nbls_kzg_monomial_create) SYM(nbls_kzg_monomial_destroy) SYM(nbls_kzg_monomial_log2n) SYM(nbls_kzg_compute_cells_and_proofs) SYM(nbls_kzg_verify_cells)
 SYM(nbls_kzg_recover_cells) SYM(nbls_kzg_recover_cells_and_proofs)
+SYM(nbls_groth16_vk_create) SYM(nbls_groth16_vk_destroy) SYM(nbls_groth16_vk_inputs) SYM(nbls_groth16_verify)
 static nbls_ctx* ctx;
 static nbls_multi* multi;   /* several GPUs behind one handle (initMulti): ctx is then its first context; the batch calls shard over all of them */
 #define MULTI() (multi && p_nbls_multi_device_count(multi) > 1)
@@ -434,11 +435,12 @@ static napi_value SignBatchAsync(napi_env env, napi_callback_info info) {
  * The offsets must name identifiers and shares that are in the arrays (checked here); the library checks the rest. */
 typedef struct {
   napi_async_work work; napi_deferred deferred; napi_ref refs[12]; int nrefs;
-  int kind /* 0 frOp, 1 lagrangeAtZero, 2 combineShares, 3 polyEval, 4 kzgVerifyProofs, 5 kzgVerifyBlobs, 6 .. 8 kzgProve, 9 frNtt, 10 kzgComputeCells, 11 kzgCellsAndProofs, 12 kzgVerifyCells, 13 kzgRecoverCells, 14 kzgRecoverCellsAndProofs */, op, g2; const uint8_t *a, *b, *shares; const uint32_t *offs, *coffs; size_t n;
+  int kind /* 0 frOp, 1 lagrangeAtZero, 2 combineShares, 3 polyEval, 4 kzgVerifyProofs, 5 kzgVerifyBlobs, 6 .. 8 kzgProve, 9 frNtt, 10 kzgComputeCells, 11 kzgCellsAndProofs, 12 kzgVerifyCells, 13 kzgRecoverCells, 14 kzgRecoverCellsAndProofs, 15 groth16Verify */, op, g2; const uint8_t *a, *b, *shares; const uint32_t *offs, *coffs; size_t n;
   uint8_t* out; int8_t* st;
   const uint8_t *proofs, *tau, *seed; int per_item;   /* KZG: a = commitments, b = z (proofs) or the blobs, shares = y, op = log2_n; out = the verdict as one int */
   const nbls_kzg_setup* su;   /* kzgProve: b = the blobs, a = the points z (7) or the given commitments (8; may be NULL), out = two arrays of n entries one behind the other */
   const nbls_kzg_monomial* mo; size_t proofs_at;   /* PeerDAS: op = log2_n, g2 = the direction (9) or log2_cell (10, 11), b = the rows or the blobs, a = the shifts (9; may be NULL); 11: out = the cells, then at proofs_at the proofs; 12: a = the commitments (proofs_at of them), offs / coffs = the commitment and cell indices, b = the cells, proofs / tau / seed / per_item as the other verifiers; 13, 14: offs / coffs = the cell offsets (n + 1) and the cell indices, b = the given cells, out as 10 / 11 */
+  const nbls_groth16_vk* vk;   /* groth16Verify: proofs = the n proofs of 192 bytes, b = the n rows of inputs, seed / per_item as the KZG verifiers; out = the verdict as one int */
   nbls_ctx* c; int rc;
 } thr_job;
 static void thr_execute(napi_env env, void* data) { thr_job* j = (thr_job*)data; (void)env;
@@ -455,6 +457,7 @@ static void thr_execute(napi_env env, void* data) { thr_job* j = (thr_job*)data;
         : j->kind == 12 ? p_nbls_kzg_verify_cells(j->c, j->mo, (unsigned)j->g2, j->proofs_at, j->a, j->n, j->offs, j->coffs, j->b, j->proofs, j->tau, j->seed, (int*)j->out, j->per_item ? j->st : NULL)
         : j->kind == 13 ? p_nbls_kzg_recover_cells(j->c, (unsigned)j->op, (unsigned)j->g2, j->n, j->offs, j->coffs, j->b, j->out, j->st)
         : j->kind == 14 ? p_nbls_kzg_recover_cells_and_proofs(j->c, j->mo, (unsigned)j->g2, j->n, j->offs, j->coffs, j->b, j->out, j->out + j->proofs_at, j->st)
+        : j->kind == 15 ? p_nbls_groth16_verify(j->c, j->vk, j->n, j->proofs, j->b, j->seed, (int*)j->out, j->per_item ? j->st : NULL)
         : j->kind == 3 ? (j->g2 ? p_nbls_g2_poly_eval : p_nbls_g1_poly_eval)(j->c, j->n, j->coffs, j->shares, j->offs, j->a, j->out, j->st)
         : (j->g2 ? p_nbls_g2_combine_shares : p_nbls_g1_combine_shares)(j->c, j->n, j->offs, j->a, j->shares, j->out, j->st); }
 /* the Error of a failed call of this family: the message of throw_code, and the library's return code as the number `nblsCode` (what the facade reads: never the text) */
@@ -768,6 +771,53 @@ static napi_value KzgRecoverCellsAsync(napi_env env, napi_callback_info info) { 
 static napi_value KzgRecoverCellsAndProofs(napi_env env, napi_callback_info info) { return kzg_recover_call(env, info, 1, 0); }
 static napi_value KzgRecoverCellsAndProofsAsync(napi_env env, napi_callback_info info) { return kzg_recover_call(env, info, 1, 1); }
 
+/* Groth16 (nbls_groth16_vk_*, nbls_groth16_verify):
+ *   groth16VkCreate(alpha48, beta96, gamma96, delta96, ic48) -> a handle (the key on the device; freed by groth16VkDestroy or with the handle); a refused key throws with the
+ *                                                          library's code as `nblsCode` and the m + 5 statuses (alpha, beta, gamma, delta, IC_0 ..) as `status`
+ *   groth16VkDestroy(handle)                               frees it now; the handle is dead afterwards.  Not while an asynchronous call uses it
+ *   groth16Verify(handle, proofs192, inputs32, seed32 | null, perItem), groth16VerifyAsync -> {out, status} as kzgVerifyProofs: out = the verdict (4 bytes, a native int),
+ *                                                          status = one byte per proof */
+typedef struct { nbls_groth16_vk* k; } g16_box;
+static void g16_finalize(napi_env env, void* data, void* hint) { (void)env; (void)hint; g16_box* b = (g16_box*)data; if (b->k && p_nbls_groth16_vk_destroy) p_nbls_groth16_vk_destroy(b->k); free(b); }
+static napi_value Groth16VkCreate(napi_env env, napi_callback_info info) {
+  ARGS(5); NEED_CTX(); BYTES(0, alpha, la); BYTES(1, beta, lb); BYTES(2, gamma, lg); BYTES(3, delta, ld); BYTES(4, ic, li);
+  if (la != 48 || lb != 96 || lg != 96 || ld != 96 || li % 48 || li < 96 || li / 48 - 1 > 65536) {
+    napi_throw_range_error(env, NULL, "48 bytes of alpha, 96 bytes each of beta, gamma, delta, and m + 1 points IC_j of 48 bytes, 1 <= m <= 65536"); return NULL; }
+  const size_t m = li / 48 - 1;
+  uint8_t* st; napi_value vs = new_u8(env, m + 5, &st); ALLOCATED(vs);
+  g16_box* box = (g16_box*)calloc(1, sizeof *box); if (!box) { napi_throw_error(env, NULL, "out of memory"); return NULL; }
+  const int rc = p_nbls_groth16_vk_create(ctx, m, alpha, beta, gamma, delta, ic, (int8_t*)st, &box->k);
+  if (rc) { free(box); napi_value err = thr_error(env, rc); napi_set_named_property(env, err, "status", vs); napi_throw(env, err); return NULL; }
+  napi_value h;
+  if (napi_create_external(env, box, g16_finalize, NULL, &h) != napi_ok) { p_nbls_groth16_vk_destroy(box->k); free(box); napi_throw_error(env, NULL, "napi_create_external failed"); return NULL; }
+  return h;
+}
+static napi_value Groth16VkDestroy(napi_env env, napi_callback_info info) {
+  ARGS(1);
+  g16_box* box = NULL;
+  if (napi_get_value_external(env, argv[0], (void**)&box) != napi_ok || !box) { napi_throw_type_error(env, NULL, "expected a Groth16 key handle"); return NULL; }
+  if (box->k) { p_nbls_groth16_vk_destroy(box->k); box->k = NULL; }
+  return NULL;
+}
+static napi_value groth16_verify_call(napi_env env, napi_callback_info info, int async) {
+  ARGS(5); NEED_CTX(); BYTES(1, ps, lp); BYTES(2, xs, lx);
+  g16_box* box = NULL;
+  if (napi_get_value_external(env, argv[0], (void**)&box) != napi_ok || !box || !box->k) { napi_throw_type_error(env, NULL, "expected a live Groth16 key handle"); return NULL; }
+  int32_t per; if (napi_get_value_int32(env, argv[4], &per) != napi_ok) { napi_throw_type_error(env, NULL, "expected a number for perItem"); return NULL; }
+  const uint8_t* seed; if (!kzg_seed(env, argv[3], &seed)) return NULL;
+  size_t m = 0; p_nbls_groth16_vk_inputs(box->k, &m);
+  const size_t n = lp / 192;
+  if (!n || lp != n * 192 || lx != n * m * 32) { napi_throw_range_error(env, NULL, "n proofs of 192 bytes and n rows of m inputs of 32 bytes"); return NULL; }
+  thr_job job; memset(&job, 0, sizeof job);
+  job.kind = 15; job.vk = box->k; job.proofs = ps; job.b = xs; job.seed = seed; job.per_item = per != 0; job.n = n;
+  napi_value vo = new_u8(env, 4, &job.out), vs = new_u8(env, n, (uint8_t**)&job.st); ALLOCATED(vo); ALLOCATED(vs);
+  memset(job.out, 0, 4); memset(job.st, 0, n);
+  if (!seed) argv[3] = argv[2];   /* (no seed array to keep alive: a second reference to the inputs in its place) */
+  return thr_run(env, &job, async, argv, 4, vo, vs);   /* the handle and every array stay referenced while the call runs */
+}
+static napi_value Groth16Verify(napi_env env, napi_callback_info info) { return groth16_verify_call(env, info, 0); }
+static napi_value Groth16VerifyAsync(napi_env env, napi_callback_info info) { return groth16_verify_call(env, info, 1); }
+
 static napi_value ModuleInit(napi_env env, napi_value exports) {
   const char* path = getenv("NBLS_LIB");
   char buf[4096];
@@ -784,6 +834,7 @@ static napi_value ModuleInit(napi_env env, napi_value exports) {
   LOAD(nbls_kzg_setup_create) LOAD(nbls_kzg_setup_destroy) LOAD(nbls_kzg_setup_log2n) LOAD(nbls_kzg_commit_blobs) LOAD(nbls_kzg_compute_proofs) LOAD(nbls_kzg_compute_blob_proofs)
   LOAD(nbls_fr_ntt) LOAD(nbls_kzg_compute_cells) LOAD(nbls_kzg_monomial_create) LOAD(nbls_kzg_monomial_destroy) LOAD(nbls_kzg_monomial_log2n) LOAD(nbls_kzg_compute_cells_and_proofs) LOAD(nbls_kzg_verify_cells)
   LOAD(nbls_kzg_recover_cells) LOAD(nbls_kzg_recover_cells_and_proofs)
+  LOAD(nbls_groth16_vk_create) LOAD(nbls_groth16_vk_destroy) LOAD(nbls_groth16_vk_inputs) LOAD(nbls_groth16_verify)
   {   /* the ABI the addon was written against (include/nbls.h NBLS_ABI_VERSION): an older or newer library is refused at load instead of misread at run time */
     int (*abi)(void) = (int (*)(void))dlsym(lib, "nbls_abi_version");
     if (!abi || abi() != NBLS_ABI_VERSION) { napi_throw_error(env, NULL, "libnbls.so: ABI version differs from the one this addon was built for (include/nbls.h NBLS_ABI_VERSION)"); return exports; }
@@ -811,7 +862,9 @@ static napi_value ModuleInit(napi_env env, napi_value exports) {
     {"kzgCellsAndProofsAsync", 0, KzgCellsAndProofsAsync, 0, 0, 0, napi_enumerable, 0}, {"kzgVerifyCells", 0, KzgVerifyCells, 0, 0, 0, napi_enumerable, 0},
     {"kzgVerifyCellsAsync", 0, KzgVerifyCellsAsync, 0, 0, 0, napi_enumerable, 0}, {"kzgRecoverCells", 0, KzgRecoverCells, 0, 0, 0, napi_enumerable, 0},
     {"kzgRecoverCellsAsync", 0, KzgRecoverCellsAsync, 0, 0, 0, napi_enumerable, 0}, {"kzgRecoverCellsAndProofs", 0, KzgRecoverCellsAndProofs, 0, 0, 0, napi_enumerable, 0},
-    {"kzgRecoverCellsAndProofsAsync", 0, KzgRecoverCellsAndProofsAsync, 0, 0, 0, napi_enumerable, 0}};
+    {"kzgRecoverCellsAndProofsAsync", 0, KzgRecoverCellsAndProofsAsync, 0, 0, 0, napi_enumerable, 0}, {"groth16VkCreate", 0, Groth16VkCreate, 0, 0, 0, napi_enumerable, 0},
+    {"groth16VkDestroy", 0, Groth16VkDestroy, 0, 0, 0, napi_enumerable, 0}, {"groth16Verify", 0, Groth16Verify, 0, 0, 0, napi_enumerable, 0},
+    {"groth16VerifyAsync", 0, Groth16VerifyAsync, 0, 0, 0, napi_enumerable, 0}};
   napi_define_properties(env, exports, sizeof d / sizeof d[0], d);
   return exports;
 }
