@@ -1,27 +1,23 @@
-// kzg_common.cpp -- what the four KZG chains share (nbls_internal.h, the KZG section): -G2 and the blob challenges, the context's device tables, the two basis handles and the handle of the FK20 cell proofs, the
-// prover's closing stage, and the verifiers' frame (KzgFrame) around the combined check and the per-item pass, which kzg_pipeline and verify_cells_pipeline both run.
+// kzg_common.cpp -- what the four KZG chains share (nbls_internal.h, the KZG section): -G2 and the blob challenges, the context's device tables, the two basis handles and the
+// handle of the FK20 cell proofs, the prover's closing stage, and the KZG verifiers' frame (KzgFrame) around the combined check and the per-item pass, which kzg_pipeline and
+// verify_cells_pipeline both run.  It also owns the device helpers of every weighted verifier -- sum3_affine, combined_tail, items_is_one, statuses_back -- which KzgFrame,
+// groth16_pipeline and verify_multiple_pipeline's per-set pass run; the header those write into and the verdicts are verifier_frame.h's.
 #include "nbls_internal.h"
 #include "fr_exec.h"
 #include <algorithm>
 
-// -G2 in affine wire bytes (x.c0 || x.c1 || p - y.c0 || p - y.c1), from the generator's standard coordinates
+// -G2 in affine wire bytes: g2_wire_negate of the generator's standard coordinates x.c0, x.c1, y.c0, y.c1
 const uint8_t* neg_g2_wire() {
   static uint8_t w[192];
   static const bool once = [] {
-    static const char* hex[5] = {
-        "024aa2b2f08f0a91260805272dc51051c6e47ad4fa403b02b4510b647ae3d1770bac0326a805bbefd48056c8c121bdb8",
-        "13e02b6052719f607dacd3a088274f65596bd0d09920b61ab5da61bbdc7f5049334cf11213945d57e5ac7d055d042b7e",
-        "0ce5d527727d6e118cc9cdc6da2e351aadfd9baa8cbdd3a76d429a695160d12c923ac9cc3baca289e193548608b82801",
-        "0606c4a02ea734cc32acd2b02bc28b99cb3e287e85a763af267492ab572e99ab3f370d275cec1da1aaa9075ff05f79be",
-        "1a0111ea397fe69a4b1ba7b6434bacd764774b84f38512bf6730d2a0f6b0f6241eabfffeb153ffffb9feffffffffaaab"};
-    uint8_t v[5][48];
+    static const char* hex = "024aa2b2f08f0a91260805272dc51051c6e47ad4fa403b02b4510b647ae3d1770bac0326a805bbefd48056c8c121bdb8"
+                             "13e02b6052719f607dacd3a088274f65596bd0d09920b61ab5da61bbdc7f5049334cf11213945d57e5ac7d055d042b7e"
+                             "0ce5d527727d6e118cc9cdc6da2e351aadfd9baa8cbdd3a76d429a695160d12c923ac9cc3baca289e193548608b82801"
+                             "0606c4a02ea734cc32acd2b02bc28b99cb3e287e85a763af267492ab572e99ab3f370d275cec1da1aaa9075ff05f79be";
+    uint8_t g[192];
     auto nib = [](char c) { return (uint8_t)(c <= '9' ? c - '0' : c - 'a' + 10); };
-    for (int k = 0; k < 5; k++) for (int i = 0; i < 48; i++) v[k][i] = (uint8_t)(nib(hex[k][2 * i]) << 4 | nib(hex[k][2 * i + 1]));
-    memcpy(w, v[0], 48); memcpy(w + 48, v[1], 48);
-    for (int k = 2; k < 4; k++) {
-      int bw = 0;
-      for (int i = 47; i >= 0; i--) { const int d = (int)v[4][i] - (int)v[k][i] - bw; w[48 * k + i] = (uint8_t)d; bw = d < 0; }
-    }
+    for (int i = 0; i < 192; i++) g[i] = (uint8_t)(nib(hex[2 * i]) << 4 | nib(hex[2 * i + 1]));
+    g2_wire_negate(g, w);
     return true;
   }();
   (void)once;
@@ -96,25 +92,16 @@ static int kzg_basis_decode(nbls_ctx* ctx, unsigned log2_n, const uint8_t* point
   return NBLS_OK;
 }
 // H: the public handle type, which adds nothing to KzgBasis but its name
+template <class H> static void kzg_basis_destroy(H* h) {
+  if (!h) return;
+  handle_free(h->device, {h->pts});
+  delete h;
+}
 template <class H> static int kzg_basis_create(nbls_ctx* ctx, unsigned log2_n, const uint8_t* points48, int8_t* status, H** out) {
   WHOLE_CALL(ctx);
   if (out) *out = nullptr;
   if (!ctx || log2_n < 1 || log2_n > 12 || !points48 || !out) return NBLS_EINVAL;
-  H* h = new (std::nothrow) H;
-  if (!h) return NBLS_EHIP;
-  h->device = ctx->device; h->log2_n = log2_n;
-  const int r = kzg_basis_decode(ctx, log2_n, points48, status, &h->pts);
-  if (r) { delete h; return r; }
-  *out = h;
-  return NBLS_OK;
-}
-template <class H> static void kzg_basis_destroy(H* h) {
-  if (!h) return;
-  int cur = 0;
-  const bool restore = hipGetDevice(&cur) == hipSuccess;
-  if (hipSetDevice(h->device) == hipSuccess) (void)hipFree(h->pts);
-  if (restore) (void)hipSetDevice(cur);
-  delete h;
+  return handle_create(ctx, out, kzg_basis_destroy<H>, [&](H* h) { h->log2_n = log2_n; return kzg_basis_decode(ctx, log2_n, points48, status, &h->pts); });
 }
 static int kzg_basis_log2n(const KzgBasis* h, unsigned* log2_n) {
   if (!h || !log2_n) return NBLS_EINVAL;
@@ -175,20 +162,14 @@ EXPORT int nbls_kzg_fk20_create(nbls_ctx* ctx, const nbls_kzg_monomial* mono, un
   const unsigned L = mono->log2_n;
   // the M groups of M terms of one blob's second pass fit a pass of the batched MSM wherever the handle's own MSM does: (2 N / c) N scalars
   if (L + 1 - log2_cell > 12 || ((size_t)2 << (2 * L - log2_cell)) > MSMB_MAX_ITEMS) return NBLS_EINVAL;
-  nbls_kzg_fk20* h = new (std::nothrow) nbls_kzg_fk20;
-  if (!h) return NBLS_EHIP;
-  h->device = ctx->device; h->log2_n = L; h->log2_cell = log2_cell;
-  const int r = log2_cell == L ? NBLS_OK : fk20_build(ctx, mono, h);   // n' = 1: no sum has a term, every proof is the zero point
-  if (r) { nbls_kzg_fk20_destroy(h); return r; }
-  *out = h;
-  return NBLS_OK;
+  return handle_create(ctx, out, nbls_kzg_fk20_destroy, [&](nbls_kzg_fk20* h) {
+    h->log2_n = L; h->log2_cell = log2_cell;
+    return log2_cell == L ? NBLS_OK : fk20_build(ctx, mono, h);   // n' = 1: no sum has a term, every proof is the zero point
+  });
 }
 EXPORT void nbls_kzg_fk20_destroy(nbls_kzg_fk20* h) {
   if (!h) return;
-  int cur = 0;
-  const bool restore = hipGetDevice(&cur) == hipSuccess;
-  if (hipSetDevice(h->device) == hipSuccess) { (void)hipFree(h->xhat); (void)hipFree(h->bsplit); }
-  if (restore) (void)hipSetDevice(cur);
+  handle_free(h->device, {h->xhat, h->bsplit});
   delete h;
 }
 EXPORT int nbls_kzg_fk20_params(const nbls_kzg_fk20* h, unsigned* log2_n, unsigned* log2_cell) {
@@ -197,64 +178,68 @@ EXPORT int nbls_kzg_fk20_params(const nbls_kzg_fk20* h, unsigned* log2_n, unsign
   return NBLS_OK;
 }
 
-// ---- the verifiers' frame
-// From the three parts of B (affine points with a status each, 1 = the zero point) to the verdict of the combined check: raw projective, the identity where the status says so,
-// two complete additions, affine again with B's own zero flag (A and its flag are in place), the generator for a zero A or B, two Miller loops against the two tables, product,
-// final exponentiation, the header's first byte = the result is one
-static int kzg_combined_tail(nbls_ctx* ctx, const KzgFrame& f, hipStream_t s) {
+// ---- the device helpers of the weighted verifiers (nbls_internal.h states what each does)
+int sum3_affine(nbls_ctx* ctx, size_t n, const uint8_t* p3, const uint8_t* st3, uint8_t* pj, uint8_t* nn, uint8_t* ni, uint8_t* out96, uint8_t* zero, hipStream_t s) {
   const size_t p = 3 * RAW; int r;
-  uint8_t *BJ = f.PR + f.a.bj, *BN = f.PR + f.a.bn, *RES = f.PR + f.a.res;
-  if ((r = run(ctx, P_G1_TO_PROJ, 3, {B(0, f.B3, 96), B(3, BJ, p)}, s))) return r;
-  LAUNCHCHK(nbls_agg_points_launch(3, (unsigned)p, nullptr, f.BST, ctx->ident_g1, BJ, BJ, s));
-  if ((r = run(ctx, P_G1_ADD_AB, 1, {B(3, BJ, p), B(4, BJ + p, p), B(5, BJ, p)}, s)) || (r = run(ctx, P_G1_ADD_AB, 1, {B(3, BJ, p), B(4, BJ + 2 * p, p), B(5, BJ, p)}, s)) ||
-      (r = to_affine(ctx, false, 1, BJ, BN, BN + RAW, f.PT2 + 96, kzg_hdr_b_zero(f.BK), s)))
-    return r;
-  LAUNCHCHK(nbls_agg_fix_zero_launch(2, f.A_ZERO, ctx->gen_g1, f.PT2, nullptr, s));
+  if ((r = run(ctx, P_G1_TO_PROJ, 3 * n, {B(0, p3, 96), B(3, pj, p)}, s))) return r;
+  LAUNCHCHK(nbls_agg_points_launch(3 * n, (unsigned)p, nullptr, st3, ctx->ident_g1, pj, pj, s));
+  if ((r = run(ctx, P_G1_ADD_AB, n, {B(3, pj, p), B(4, pj + n * p, p), B(5, pj, p)}, s)) || (r = run(ctx, P_G1_ADD_AB, n, {B(3, pj, p), B(4, pj + 2 * n * p, p), B(5, pj, p)}, s))) return r;
+  return to_affine(ctx, false, n, pj, nn, ni, out96, zero, s);
+}
+int combined_tail(nbls_ctx* ctx, size_t k, size_t mm, uint8_t* pts96, uint8_t* zero, const uint8_t* tables, uint8_t* res576, uint8_t* one, hipStream_t s) {
+  int r;
+  LAUNCHCHK(nbls_agg_fix_zero_launch((unsigned)k, zero, ctx->gen_g1, pts96, nullptr, s));
   uint8_t* res = ctx->F;
-  if ((r = run(ctx, P_ACC_Q, 2, {B(0, f.PT2, 96), B(3, f.TB, LINE_BYTES), B(5, ctx->F, F12)}, s)) || (r = reduce_product(ctx, 2, &res, s)) || (r = finish_single(ctx, Window(), res, 1, RES, s))) return r;
-  LAUNCHCHK(nbls_rlc_is_one_launch(1, RES, kzg_hdr_one(f.BK), s));
+  if ((r = run(ctx, P_ACC_Q, k, {B(0, pts96, 96), B(3, tables, LINE_BYTES), B(5, ctx->F + mm * F12, F12)}, s)) || (r = reduce_product(ctx, mm + k, &res, s)) ||
+      (r = finish_single(ctx, Window(), res, 1, res576, s)))
+    return r;
+  LAUNCHCHK(nbls_rlc_is_one_launch(1, res576, one, s));
   return NBLS_OK;
 }
-// The per-item tail.  block = the start kzg_item_tail_carve returned; the caller has written the three summands of every X_i to p3 (3 n affine points, summand after summand)
-// and their statuses to st3 (non-zero: the identity) -> X_i by two complete additions, millerLoop(pi_i, table 0) * millerLoop(X_i, table 1) with table_stride = 0, one batched
-// final exponentiation, compared with one on the device, kzg_item_status_kernel's rule -> the n statuses at fs.  The caller has run ensure_scratch(ctx, 2 n)
-static int kzg_item_tail(nbls_ctx* ctx, size_t n, const KzgItemTail& t, uint8_t* block, const uint8_t* proofs96, const uint8_t* tables, const uint8_t* pre, const uint8_t* proof_st, hipStream_t s) {
-  const size_t p = 3 * RAW; int r;
-  uint8_t *P3 = block + t.p3, *ST3 = block + t.st3, *PJ = block + t.proj, *N = block + t.n, *NI = block + t.ni, *X = block + t.x, *E = block + t.e, *V = block + t.v, *XZ = block + t.xz,
-          *FS = block + t.fs;
-  // the summands as raw projective points, the identity where the status says so (a zero commitment, a zero product, an item that is out), then two complete additions
-  if ((r = run(ctx, P_G1_TO_PROJ, 3 * n, {B(0, P3, 96), B(3, PJ, p)}, s))) return r;
-  LAUNCHCHK(nbls_agg_points_launch(3 * n, (unsigned)p, nullptr, ST3, ctx->ident_g1, PJ, PJ, s));
-  if ((r = run(ctx, P_G1_ADD_AB, n, {B(3, PJ, p), B(4, PJ + n * p, p), B(5, PJ, p)}, s)) || (r = run(ctx, P_G1_ADD_AB, n, {B(3, PJ, p), B(4, PJ + 2 * n * p, p), B(5, PJ, p)}, s)) ||
-      (r = to_affine(ctx, false, n, PJ, N, NI, X, XZ, s)))
-    return r;
-  LAUNCHCHK(nbls_agg_fix_zero_launch((unsigned)n, XZ, ctx->gen_g1, X, nullptr, s));
-  if ((r = run(ctx, P_ACC_Q, n, {B(0, proofs96, 96), B(3, tables, 0), B(5, ctx->F, F12)}, s)) || (r = run(ctx, P_ACC_Q, n, {B(0, X, 96), B(3, tables + LINE_BYTES, 0), B(5, ctx->F + n * F12, F12)}, s)) ||
-      (r = run(ctx, P_MUL2S, n, {B(3, ctx->F, F12), B(4, ctx->F + n * F12, F12), B(5, ctx->F, F12)}, s)) || (r = run(ctx, P_NORM_RAW, n, {B(3, ctx->F, F12), B(4, ctx->N, RAW)}, s)) ||
-      (r = final_exp_pipeline(ctx, Window(), n, ctx->F, E, s)))
-    return r;
-  LAUNCHCHK(nbls_rlc_is_one_launch((unsigned)n, E, V, s));
-  LAUNCHCHK(nbls_kzg_item_status_launch((unsigned)n, pre, proof_st, XZ, V, FS, s));
+int items_is_one(nbls_ctx* ctx, size_t cnt, uint8_t* e576, uint8_t* v, hipStream_t s) {
+  int r;
+  if ((r = run(ctx, P_NORM_RAW, cnt, {B(3, ctx->F, F12), B(4, ctx->N, RAW)}, s)) || (r = final_exp_pipeline(ctx, Window(), cnt, ctx->F, e576, s))) return r;
+  LAUNCHCHK(nbls_rlc_is_one_launch((unsigned)cnt, e576, v, s));
+  return NBLS_OK;
+}
+int statuses_back(nbls_ctx* ctx, hipStream_t s, const uint8_t* fs, size_t n, ForkGuard& guard, int* all_ok, int8_t* status) {
+  const uint8_t* got;
+  const int r = read_back(ctx, s, fs, n, &got); if (r) return r;
+  guard.armed = false;
+  memcpy(status, got, n);
+  *all_ok = std::all_of(got, got + n, [](uint8_t st) { return st == 0; });
   return NBLS_OK;
 }
 
-int kzg_seed(const uint8_t* seed32, uint8_t* seed) {
-  if (!seed32) return os_seed(seed);
-  memcpy(seed, seed32, 32);
+// ---- the KZG verifiers' frame
+// The per-item tail.  block = the start kzg_item_tail_carve returned; the caller has written the three summands of every X_i to p3 (3 n affine points, summand after summand)
+// and their statuses to st3 (non-zero: the identity: a zero commitment, a zero product, an item that is out) -> X_i = their sum, millerLoop(pi_i, table 0) *
+// millerLoop(X_i, table 1) with table_stride = 0, one batched final exponentiation, compared with one on the device, kzg_item_status_kernel's rule -> the n statuses at fs.
+// The caller has run ensure_scratch(ctx, 2 n)
+static int kzg_item_tail(nbls_ctx* ctx, size_t n, const KzgItemTail& t, uint8_t* block, const uint8_t* proofs96, const uint8_t* tables, const uint8_t* pre, const uint8_t* proof_st, hipStream_t s) {
+  int r;
+  uint8_t *X = block + t.x, *V = block + t.v, *XZ = block + t.xz;
+  if ((r = sum3_affine(ctx, n, block + t.p3, block + t.st3, block + t.proj, block + t.n, block + t.ni, X, XZ, s))) return r;
+  LAUNCHCHK(nbls_agg_fix_zero_launch((unsigned)n, XZ, ctx->gen_g1, X, nullptr, s));
+  if ((r = run(ctx, P_ACC_Q, n, {B(0, proofs96, 96), B(3, tables, 0), B(5, ctx->F, F12)}, s)) || (r = run(ctx, P_ACC_Q, n, {B(0, X, 96), B(3, tables + LINE_BYTES, 0), B(5, ctx->F + n * F12, F12)}, s)) ||
+      (r = run(ctx, P_MUL2S, n, {B(3, ctx->F, F12), B(4, ctx->F + n * F12, F12), B(5, ctx->F, F12)}, s)) || (r = items_is_one(ctx, n, block + t.e, V, s)))
+    return r;
+  LAUNCHCHK(nbls_kzg_item_status_launch((unsigned)n, pre, proof_st, XZ, V, block + t.fs, s));
   return NBLS_OK;
 }
+
 KzgFrame::KzgFrame(nbls_ctx* c, Staged& st, hipStream_t stream, size_t items, Slot pairs, Slot out, Slot per_item)
     : ctx(c), io(st), s(stream), n(items), sb_pairs(pairs), sb_out(out), sb_items(per_item), a(kzg_pairs_carve()) {}
 void KzgFrame::stage(const uint8_t* tau96, const uint8_t* seed) { o_tau = io.bytes(tau96, 96); o_ng2 = io.bytes(neg_g2_wire(), 192); o_seed = io.bytes(seed, 32); }
 int KzgFrame::take() {
   int r;
-  if ((r = need(ctx, sb_pairs, a.bytes, &PR)) || (r = need(ctx, sb_out, kzg_back_bytes(n), &BK)) || (r = ensure_scratch(ctx, 2))) return r;
-  TB = PR + a.tb; PT2 = PR + a.pt2; B3 = PR + a.b3; BST = PR + a.bst; A_ZERO = kzg_hdr_a_zero(BK); PRE = kzg_hdr_pre(BK);
+  if ((r = need(ctx, sb_pairs, a.bytes, &PR)) || (r = need(ctx, sb_out, back_bytes(n), &BK)) || (r = ensure_scratch(ctx, 2))) return r;
+  TB = PR + a.tb; PT2 = PR + a.pt2; B3 = PR + a.b3; BST = PR + a.bst; A_ZERO = kzg_hdr_a_zero(BK); PRE = hdr_pre(BK);
   return NBLS_OK;
 }
 int KzgFrame::open(uint8_t* c, uint8_t* W) {
   uint8_t* G2P = PR + a.g2; int r;
-  HIPCHK(hipMemsetAsync(BK, 0, KZG_HDR_BYTES, s));
+  HIPCHK(hipMemsetAsync(BK, 0, HDR_BYTES, s));
   // the G2 point by PointG2.fromSignature's rules (its status is judged after the read-back: nothing is decided on the host before), then the two line tables
   if ((r = dev_decompress(ctx, true, 1, c + o_tau, G2P, kzg_hdr_g2_status(BK), s))) return r;
   HIPCHK(hipMemcpyAsync(G2P + 192, c + o_ng2, 192, hipMemcpyDeviceToDevice, s));
@@ -262,14 +247,16 @@ int KzgFrame::open(uint8_t* c, uint8_t* W) {
   LAUNCHCHK(nbls_rlc_weights_launch((unsigned)n, c + o_seed, W, s));
   return NBLS_OK;
 }
+// B = the sum of its three parts with B's own zero flag (A and its flag are in place), then the combined check of the two points against the two tables
 int KzgFrame::decide(int* all_ok, int8_t* status, bool* more) {
   const uint8_t* got; int r;
-  if ((r = kzg_combined_tail(ctx, *this, s)) || (r = io.fetch(BK, kzg_back_bytes(n), &got))) return r;
+  uint8_t* BN = PR + a.bn;
+  if ((r = sum3_affine(ctx, 1, B3, BST, PR + a.bj, BN, BN + RAW, PT2 + 96, kzg_hdr_b_zero(BK), s)) || (r = combined_tail(ctx, 2, 0, PT2, A_ZERO, TB, PR + a.res, hdr_one(BK), s)) ||
+      (r = io.fetch(BK, back_bytes(n), &got)))
+    return r;
   const KzgVerdict v = kzg_verdict(got, n);
   if (v == KZG_BAD_G2) return NBLS_EDECODE;
-  *all_ok = v == KZG_ACCEPT;
-  if (v == KZG_ACCEPT && status) memset(status, 0, n);
-  *more = v == KZG_REJECT && status;   // (no statuses asked for: the fast reject, no per-item work)
+  combined_result(v == KZG_ACCEPT, n, all_ok, status, more);
   return NBLS_OK;
 }
 int KzgFrame::items_begin(size_t front, uint8_t** FRONT, MsmbPlan* rows_plan, size_t row_pts) {
@@ -277,16 +264,10 @@ int KzgFrame::items_begin(size_t front, uint8_t** FRONT, MsmbPlan* rows_plan, si
   const size_t b_front = carve(&sz, front), b_t = kzg_item_tail_carve(n, &sz, &t);
   if ((r = need(ctx, sb_items, sz, &IT)) || (r = ensure_scratch(ctx, 2 * n)) || (rows_plan && (r = msm_rows_dev_plan(ctx, row_pts, n, rows_plan)))) return r;
   *FRONT = IT + b_front; TAIL = IT + b_t; P3 = TAIL + t.p3; ST3 = TAIL + t.st3;
-  // nothing is forked here: the guard is used for its wait alone.  fetch() has disarmed the staged block, and an error return from here on must not leave this chain running on
-  // slots the next call regrows
-  guard.armed = true;
+  guard.armed = true;   // (until statuses_back)
   return NBLS_OK;
 }
 int KzgFrame::items_close(const uint8_t* proofs96, const uint8_t* proof_st, int* all_ok, int8_t* status) {
-  const uint8_t* got; int r;
-  if ((r = kzg_item_tail(ctx, n, t, TAIL, proofs96, TB, PRE, proof_st, s)) || (r = read_back(ctx, s, TAIL + t.fs, n, &got))) return r;
-  guard.armed = false;
-  memcpy(status, got, n);
-  *all_ok = std::all_of(got, got + n, [](uint8_t st) { return st == 0; });
-  return NBLS_OK;
+  const int r = kzg_item_tail(ctx, n, t, TAIL, proofs96, TB, PRE, proof_st, s); if (r) return r;
+  return statuses_back(ctx, s, TAIL + t.fs, n, guard, all_ok, status);
 }

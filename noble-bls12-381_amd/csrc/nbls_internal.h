@@ -10,6 +10,7 @@
 #include <mutex>
 #include <vector>
 #include <initializer_list>
+#include <new>
 #include "nbls.h"
 #include "programs.h"
 #include "consts_gen.h"
@@ -18,7 +19,7 @@
 #include "sha256.h"
 #include "curve.h"   // G1_FIXED_WIN and the table geometry of pt_mul_fixed_g1
 #include "bufs.h"    // BufArg / B(), BufList, ChainLink, bind_bufs
-#include "kzg_frame.h"   // the block formats of the KZG verifiers
+#include "verifier_frame.h"   // the block formats of the weighted verifiers
 #include <thread>
 
 #include "launchers.h"   // every nbls_*_launch of the kernel files, declared once for both sides
@@ -460,9 +461,28 @@ int msm_map_dev_plan(nbls_ctx* ctx, size_t glen, size_t period, size_t pt_block,
 void msm_map_plans_settle(nbls_ctx* ctx, std::initializer_list<MsmbPlan*> plans);
 int msm_map_dev(nbls_ctx* ctx, const MsmbPlan& pl, const uint8_t* conv_pts, const uint8_t* d_scalars, const uint8_t* split, uint8_t* d_out96, uint8_t* d_zero, uint8_t* conv, hipStream_t s);
 int msm_split_scalars(nbls_ctx* ctx, size_t n, const uint8_t* d_scalars, uint8_t* split, hipStream_t s);
-// ---- KZG (kzg_common.cpp): what pipelines_kzg.cpp, pipelines_kzg_prove.cpp, pipelines_kzg_cells.cpp and pipelines_kzg_verify_cells.cpp share
+// ---- device handles (nbls_keyset, the KZG bases, nbls_kzg_fk20, nbls_groth16_vk): device memory of the device they were created on, usable from every context of that device.
+// handle_free: a handle's device blocks freed on the handle's device, the caller's device restored.  handle_create: the frame of a create call behind its argument check -- the
+// handle allocated, `device` set, build(h) run; where that fails the handle goes through its destroy function and *out stays NULL
+static inline void handle_free(int device, std::initializer_list<void*> blocks) {
+  int cur = 0;
+  const bool restore = hipGetDevice(&cur) == hipSuccess;
+  if (hipSetDevice(device) == hipSuccess) for (void* b : blocks) (void)hipFree(b);
+  if (restore) (void)hipSetDevice(cur);
+}
+template <class H, class Build> static int handle_create(nbls_ctx* ctx, H** out, void (*destroy)(H*), Build build) {
+  H* h = new (std::nothrow) H;
+  if (!h) return NBLS_EHIP;
+  h->device = ctx->device;
+  const int r = build(h);
+  if (r) { destroy(h); return r; }
+  *out = h;
+  return NBLS_OK;
+}
+// ---- KZG and the weighted verifiers (kzg_common.cpp): what pipelines_kzg.cpp, pipelines_kzg_prove.cpp, pipelines_kzg_cells.cpp and pipelines_kzg_verify_cells.cpp share, and
+// the device helpers that pipelines_groth16.cpp and pipelines_multi_verify.cpp run as well
 static const size_t KZG_MAX_ELEMS = (size_t)1 << 24;   // field elements per call of the Fr entry points and of the calls that take whole blobs
-// -G2 in affine wire bytes; the challenges of n blobs on host threads
+// -G2 in affine wire bytes (g2_wire_negate of the generator); the challenges of n blobs on host threads
 const uint8_t* neg_g2_wire();
 void blob_challenges(unsigned log2_n, size_t n, const uint8_t* blobs, const uint8_t* c48, uint8_t* z32);
 // a context's device table, made on first use: the roots of 2^log2_n, the inverse roots (a permutation of the roots, made behind them on the same stream), or the inverse shifts
@@ -483,18 +503,30 @@ int kzg_proof_tail(nbls_ctx* ctx, const MsmbPlan& pl, const uint8_t* basis_pts, 
                    uint8_t* out48, uint8_t* status, hipStream_t s);
 // what follows the sums in kzg_proof_tail, for a caller whose n affine sums and zero flags come from elsewhere (the second pass of the FK20 cell proofs)
 int kzg_proof_close(nbls_ctx* ctx, size_t n, const uint8_t* aff96, const uint8_t* zero, const uint8_t* st_a, const uint8_t* st_b, uint8_t* out48, uint8_t* status, hipStream_t s);
-// The frame of a verifier's call: the seed, the three staged parts [tau^c]G2 | -G2 | seed, the pairs block and the read-back block (kzg_frame.h has their formats), the opening
+// The device helpers of the weighted verifiers (verifier_frame.h has the header they write into).  Each is one fixed run of launches on `s`:
+// sum3_affine: n sums of three affine parts (p3: 3 n points, part after part; st3: a status each, non-zero = the identity) -> raw projective (pj: 3 n points), the identity
+//   where the status says so, two complete additions, affine again (out96) with a zero flag each; nn, ni: n norms and inverses
+// combined_tail: the k combined points at pts96 with their zero flags (the generator for a zero point) against k line tables -> their Miller values behind the mm the caller has
+//   left in ctx->F, product, final exponentiation (res576), *one = the result is one
+// items_is_one: the cnt raw Fp12 values in ctx->F -> norms, one batched final exponentiation (e576: cnt x 576), v[i] = value i is one
+// statuses_back: closes a per-item pass -- reads back the n final statuses at fs, disarms the pass's guard, copies them to the caller and sets *all_ok.  About that guard:
+//   nothing is forked in a per-item pass, it is used for its wait alone.  fetch() has disarmed the staged block, and an error return between arming it and this call must not
+//   leave the chain running on slots the next call regrows
+int sum3_affine(nbls_ctx* ctx, size_t n, const uint8_t* p3, const uint8_t* st3, uint8_t* pj, uint8_t* nn, uint8_t* ni, uint8_t* out96, uint8_t* zero, hipStream_t s);
+int combined_tail(nbls_ctx* ctx, size_t k, size_t mm, uint8_t* pts96, uint8_t* zero, const uint8_t* tables, uint8_t* res576, uint8_t* one, hipStream_t s);
+int items_is_one(nbls_ctx* ctx, size_t cnt, uint8_t* e576, uint8_t* v, hipStream_t s);
+int statuses_back(nbls_ctx* ctx, hipStream_t s, const uint8_t* fs, size_t n, ForkGuard& guard, int* all_ok, int8_t* status);
+// The frame of a KZG verifier's call: the three staged parts [tau^c]G2 | -G2 | seed, the pairs block and the read-back block (verifier_frame.h has their formats), the opening
 // launches, the combined check with its verdict and the per-item pass around the summands.  The caller keeps its staged inputs, its points and scalars blocks, its item
-// kernels, the four sums that fill PT2 / A_ZERO, B3 and BST, and the three summands of every X_i (P3, ST3).  A call: kzg_seed (in front of DEV_ENTER) -> stage (among the caller's
+// kernels, the four sums that fill PT2 / A_ZERO, B3 and BST, and the three summands of every X_i (P3, ST3).  A call: rlc_seed (in front of DEV_ENTER) -> stage (among the caller's
 // io.bytes) -> take (among its need() calls, in front of io.send) -> open (first launches; W: n weights) -> the caller's items and sums -> decide (*more: the statuses need the
 // per-item pass) -> items_begin -> the caller's summands -> items_close
-int kzg_seed(const uint8_t* seed32, uint8_t* seed);   // the caller's seed, or one from the OS
 struct Staged;
 struct KzgFrame {
   nbls_ctx* ctx; Staged& io; hipStream_t s; size_t n; Slot sb_pairs, sb_out, sb_items;
   size_t o_tau = 0, o_ng2 = 0, o_seed = 0; KzgPairs a; KzgItemTail t;
   uint8_t *PR = nullptr, *BK = nullptr, *TB = nullptr, *PT2 = nullptr, *A_ZERO = nullptr, *B3 = nullptr, *BST = nullptr, *PRE = nullptr, *TAIL = nullptr, *P3 = nullptr, *ST3 = nullptr;
-  ForkGuard guard{false};   // armed by items_begin
+  ForkGuard guard{false};   // armed by items_begin, disarmed by statuses_back
   KzgFrame(nbls_ctx* c, Staged& st, hipStream_t stream, size_t items, Slot pairs, Slot out, Slot per_item);
   void stage(const uint8_t* tau96, const uint8_t* seed);
   int take();
@@ -532,6 +564,7 @@ struct MultiVerifyIn {
 };
 int verify_multiple_pipeline(nbls_ctx* ctx, const MultiVerifyIn& in, int* all_ok, int8_t* status);
 int os_seed(uint8_t* seed32);
+int rlc_seed(const uint8_t* seed32, uint8_t* seed);   // the seed of a call's secret weights: the caller's, or one from the OS
 int verify_batch_partial_core(nbls_ctx* ctx, size_t n, const uint8_t* sig96 /* or NULL */, const uint8_t* msgs, const uint32_t* offsets, const uint8_t* pk48,
                                      const uint8_t* dst, size_t dst_len, void* d_dst, void** d_partial, int* zero_flag, int8_t* pk_status);
 #define NBLS_STAGING_CALL   // Staged / read_back use the context and the declarations above

@@ -15,35 +15,19 @@
 // bounds: L_i = msm_rows_dev against the handle's converted points (the rows are the staged inputs themselves) plus IC_0 by one complete addition -- a zero L_i is a factor of
 // one --, millerLoop(A_i, B_i), two Miller loops against the shared tables with table_stride = 0, the one value of millerLoop(alpha, table of -beta), one batched final
 // exponentiation, rlc_is_one.  nbls_groth16_prepare_inputs is the L_i of that pass, compressed.
+// This file owns the chain up to the three combined points and the chunk loop's Miller values.  The seed, the read-back header with its verdict (verifier_frame.h), the
+// combined check's tail, the close of a chunk and the read-back of the final statuses are the weighted verifiers' shared helpers (kzg_common.cpp); KzgFrame itself is not
+// used: there is no tau point and no line table to build per call.
 // Scratch slots: SB_STAGED and SB_G16_* (nbls_internal.h, M_G16_OWN); the decoders and the ladder run on the main slots, the MSMs on MSM_RLC's, the batched MSM on SB_MSMB_*.
 #include "nbls_internal.h"
 #include "fr_exec.h"
 #include <algorithm>
 
 static const size_t G16_MAX_PROOFS = MSMB_MAX_GROUPS, G16_MAX_INPUTS = (size_t)1 << 16;
-// what is read back: the product is one | [S_0]alpha is the zero point | sum [S_j]IC_j is | sum [r_i]C_i is | (12 unused) | the n statuses before any pairing
-static const size_t G16_HDR_BYTES = 16;
-
-// -Q for a decoded G2 point in affine wire bytes (x.c0 || x.c1 || y.c0 || y.c1, 48 bytes big-endian each): y -> p - y, a zero coordinate stays zero
-static void g2_wire_negate(const uint8_t* in192, uint8_t* out192) {
-  static const uint8_t P[48] = {0x1a, 0x01, 0x11, 0xea, 0x39, 0x7f, 0xe6, 0x9a, 0x4b, 0x1b, 0xa7, 0xb6, 0x43, 0x4b, 0xac, 0xd7, 0x64, 0x77, 0x4b, 0x84, 0xf3, 0x85, 0x12, 0xbf,
-                                0x67, 0x30, 0xd2, 0xa0, 0xf6, 0xb0, 0xf6, 0x24, 0x1e, 0xab, 0xff, 0xfe, 0xb1, 0x53, 0xff, 0xff, 0xb9, 0xfe, 0xff, 0xff, 0xff, 0xff, 0xaa, 0xab};
-  memcpy(out192, in192, 96);
-  for (int k = 2; k < 4; k++) {
-    const uint8_t* y = in192 + 48 * k; uint8_t* o = out192 + 48 * k;
-    bool zero = true;
-    for (int i = 0; i < 48; i++) zero = zero && y[i] == 0;
-    int bw = 0;
-    for (int i = 47; i >= 0; i--) { const int d = (int)P[i] - (int)y[i] - bw; o[i] = zero ? 0 : (uint8_t)d; bw = d < 0; }
-  }
-}
 
 EXPORT void nbls_groth16_vk_destroy(nbls_groth16_vk* vk) {
   if (!vk) return;
-  int cur = 0;
-  const bool restore = hipGetDevice(&cur) == hipSuccess;
-  if (hipSetDevice(vk->device) == hipSuccess) (void)hipFree(vk->mem);
-  if (restore) (void)hipSetDevice(cur);
+  handle_free(vk->device, {vk->mem});
   delete vk;
 }
 EXPORT int nbls_groth16_vk_inputs(const nbls_groth16_vk* vk, size_t* m) {
@@ -95,14 +79,8 @@ EXPORT int nbls_groth16_vk_create(nbls_ctx* ctx, size_t m, const uint8_t* alpha_
   WHOLE_CALL(ctx);
   if (out) *out = nullptr;
   if (!ctx || !m || m > G16_MAX_INPUTS || !alpha_g1_48 || !beta_g2_96 || !gamma_g2_96 || !delta_g2_96 || !ic48 || !out) return NBLS_EINVAL;
-  nbls_groth16_vk* vk = new (std::nothrow) nbls_groth16_vk;
-  if (!vk) return NBLS_EHIP;
-  vk->device = ctx->device; vk->m = m;
   const uint8_t* const g2[3] = {beta_g2_96, gamma_g2_96, delta_g2_96};
-  const int r = g16_vk_build(ctx, vk, alpha_g1_48, g2, ic48, status);
-  if (r) { nbls_groth16_vk_destroy(vk); return r; }
-  *out = vk;
-  return NBLS_OK;
+  return handle_create(ctx, out, nbls_groth16_vk_destroy, [&](nbls_groth16_vk* vk) { vk->m = m; return g16_vk_build(ctx, vk, alpha_g1_48, g2, ic48, status); });
 }
 
 EXPORT int nbls_groth16_input_sums(nbls_ctx* ctx, size_t n, size_t m, const uint8_t* inputs32, const uint8_t* weights32, const int8_t* pre, uint8_t* out32, int8_t* status) {
@@ -179,9 +157,9 @@ struct G16In { const nbls_groth16_vk* vk; size_t n; const uint8_t *proofs, *inpu
 
 static int groth16_pipeline(nbls_ctx* ctx, const G16In& in, int* all_ok, int8_t* status) {
   const nbls_groth16_vk* vk = in.vk;
-  const size_t n = in.n, m = vk->m, p = 3 * RAW, sums = (m + 1) * 32, back = G16_HDR_BYTES + n;
-  uint8_t seed[32]; int r;
-  if ((r = kzg_seed(in.seed32, seed))) return r;
+  const size_t n = in.n, m = vk->m, p = 3 * RAW, sums = (m + 1) * 32, back = back_bytes(n);
+  uint8_t seed[32]; int r; bool more;
+  if ((r = rlc_seed(in.seed32, seed))) return r;
   DEV_ENTER(ctx, nullptr);
   Staged io(ctx, s);
   // the staged block: proofs | inputs | seed
@@ -196,8 +174,8 @@ static int groth16_pipeline(nbls_ctx* ctx, const G16In& in, int* all_ok, int8_t*
       (r = need(ctx, SB_G16_OUT, back, &BK)) || (r = ensure_scratch(ctx, n + 3)) || (r = io.send(c, back)))
     return r;
   uint8_t *AC = PTS + a_ac, *BC = PTS + a_bc, *A = PTS + a_aff, *C = A + n * 96, *B2 = PTS + a_b, *DST = PTS + a_dst, *PJ = PTS + a_pj, *NN = PTS + a_nn, *NI = PTS + a_ni, *RA = PTS + a_ra, *RST = PTS + a_rst;
-  uint8_t *W = SC + a_w, *S1 = SC + a_s1, *S = SC + a_S, *PRE0 = SC + a_pre0, *PT3 = PR + a_pt3, *RES = PR + a_res, *PRE = BK + G16_HDR_BYTES, *ROWS = c + o_in;
-  HIPCHK(hipMemsetAsync(BK, 0, G16_HDR_BYTES, s));
+  uint8_t *W = SC + a_w, *S1 = SC + a_s1, *S = SC + a_S, *PRE0 = SC + a_pre0, *PT3 = PR + a_pt3, *RES = PR + a_res, *PRE = hdr_pre(BK), *ROWS = c + o_in;
+  HIPCHK(hipMemsetAsync(BK, 0, HDR_BYTES, s));
   LAUNCHCHK(nbls_g16_split_launch((unsigned)n, c + o_pf, AC, BC, s));
   LAUNCHCHK(nbls_rlc_weights_launch((unsigned)n, c + o_seed, W, s));
   // PointG1.fromHex of A_0 .. A_(n-1), C_0 .. C_(n-1); PointG2.fromSignature of the B_i
@@ -208,25 +186,13 @@ static int groth16_pipeline(nbls_ctx* ctx, const G16In& in, int* all_ok, int8_t*
   // [r_i]A_i, affine (never the zero point: A_i is a point of the subgroup other than zero, 2^63 <= r_i < 2^64)
   if ((r = run(ctx, P_G1_MUL64, n, {B(0, A, 96), B(2, W, 32), B(3, PJ, p), B(4, NN, RAW)}, s)) || (r = to_affine(ctx, false, n, PJ, NN, NI, RA, RST, s, false))) return r;
   // [S_0]alpha | sum_j [S_j]IC_j | sum_i [r_i]C_i: the partners of -beta, -gamma, -delta, each with its zero flag in the header
-  if ((r = dev_msm(ctx, false, n, C, S1, 64, PT3 + 192, BK + 3, s, MSM_RLC)) || (r = dev_msm(ctx, false, m + 1, vk->ic96, S, 256, PT3 + 96, BK + 2, s, MSM_RLC)) ||
-      (r = dev_point_mul(ctx, false, 1, vk->alpha96, 0, S, PT3, BK + 1, s)))
+  if ((r = dev_msm(ctx, false, n, C, S1, 64, PT3 + 192, g16_hdr_c_zero(BK), s, MSM_RLC)) || (r = dev_msm(ctx, false, m + 1, vk->ic96, S, 256, PT3 + 96, g16_hdr_ic_zero(BK), s, MSM_RLC)) ||
+      (r = dev_point_mul(ctx, false, 1, vk->alpha96, 0, S, PT3, g16_hdr_alpha_zero(BK), s)))
     return r;
-  LAUNCHCHK(nbls_agg_fix_zero_launch(3, BK + 1, ctx->gen_g1, PT3, nullptr, s));
   size_t mm = 0;
-  uint8_t* res = ctx->F;
-  if ((r = miller_values(ctx, n, RA, B2, &mm, s)) || (r = run(ctx, P_ACC_Q, 3, {B(0, PT3, 96), B(3, vk->tables, LINE_BYTES), B(5, ctx->F + mm * F12, F12)}, s)) ||
-      (r = reduce_product(ctx, mm + 3, &res, s)) || (r = finish_single(ctx, Window(), res, 1, RES, s)))
-    return r;
-  LAUNCHCHK(nbls_rlc_is_one_launch(1, RES, BK, s));
-  if ((r = io.fetch(BK, back, &got))) return r;
-  const bool clean = std::all_of(got + G16_HDR_BYTES, got + back, [](uint8_t st) { return st == 0; });
-  if (clean && got[0] != 0 && got[1] != 1 && got[2] != 1 && got[3] != 1) {
-    *all_ok = 1;
-    if (status) memset(status, 0, n);
-    return NBLS_OK;
-  }
-  *all_ok = 0;
-  if (!status) return NBLS_OK;   // the fast reject: no per-proof work
+  if ((r = miller_values(ctx, n, RA, B2, &mm, s)) || (r = combined_tail(ctx, 3, mm, PT3, hdr_flags(BK), vk->tables, RES, hdr_one(BK), s)) || (r = io.fetch(BK, back, &got))) return r;
+  combined_result(g16_verdict(got, n), n, all_ok, status, &more);
+  if (!more) return NBLS_OK;
   // ---- the per-proof pass, chunk after chunk.  F: millerLoop(A_i, B_i) | the loops of L_i | of C_i, cnt each; behind the largest chunk's the one value of millerLoop(alpha, -beta)
   const size_t per = g16_chunk(ctx, n, m), tail = n % per;
   size_t sz_it = 0;
@@ -235,9 +201,7 @@ static int groth16_pipeline(nbls_ctx* ctx, const G16In& in, int* all_ok, int8_t*
   MsmbPlan pl_full, pl_tail; uint8_t* IT;
   if ((r = need(ctx, SB_G16_ITEMS, sz_it, &IT)) || (r = ensure_scratch(ctx, 3 * per + 1)) || (r = msm_rows_dev_plan(ctx, m, per, &pl_full)) || (tail && (r = msm_rows_dev_plan(ctx, m, tail, &pl_tail))))
     return r;
-  // nothing is forked here: the guard is used for its wait alone.  fetch() has disarmed the staged block, and an error return from here on must not leave this chain running on
-  // slots the next call regrows
-  ForkGuard guard; guard.armed = true;
+  ForkGuard guard;   // (armed until statuses_back)
   uint8_t *L = IT + a.l, *LZ = IT + a.lz, *E = IT + a_e, *V = IT + a_v, *FS = IT + a_fs, *FAB = ctx->F + 3 * per * F12;
   LAUNCHCHK(nbls_g16_rows_launch((unsigned)n, (unsigned)m, PRE, ROWS, s));
   if ((r = run(ctx, P_ACC_Q, 1, {B(0, vk->alpha96, 96), B(3, vk->tables, LINE_BYTES), B(5, FAB, F12)}, s))) return r;
@@ -252,17 +216,11 @@ static int groth16_pipeline(nbls_ctx* ctx, const G16In& in, int* all_ok, int8_t*
       return r;
     LAUNCHCHK(nbls_agg_points_launch(cnt, (unsigned)F12, nullptr, LZ, ctx->one12, F1, F1, s));   // a zero L_i: the factor one
     if ((r = run(ctx, P_MUL2S, cnt, {B(3, F0, F12), B(4, F1, F12), B(5, F0, F12)}, s)) || (r = run(ctx, P_MUL2S, cnt, {B(3, F0, F12), B(4, F2, F12), B(5, F0, F12)}, s)) ||
-        (r = run(ctx, P_MUL2S, cnt, {B(3, F0, F12), B(4, FAB, 0), B(5, F0, F12)}, s)) || (r = run(ctx, P_NORM_RAW, cnt, {B(3, F0, F12), B(4, ctx->N, RAW)}, s)) ||
-        (r = final_exp_pipeline(ctx, Window(), cnt, F0, E, s)))
+        (r = run(ctx, P_MUL2S, cnt, {B(3, F0, F12), B(4, FAB, 0), B(5, F0, F12)}, s)) || (r = items_is_one(ctx, cnt, E, V, s)))
       return r;
-    LAUNCHCHK(nbls_rlc_is_one_launch((unsigned)cnt, E, V, s));
     LAUNCHCHK(nbls_g16_status_launch((unsigned)cnt, PRE + b0, V, FS + b0, s));
   }
-  if ((r = read_back(ctx, s, FS, n, &got))) return r;
-  guard.armed = false;
-  memcpy(status, got, n);
-  *all_ok = std::all_of(got, got + n, [](uint8_t st) { return st == 0; });
-  return NBLS_OK;
+  return statuses_back(ctx, s, FS, n, guard, all_ok, status);
 }
 
 EXPORT int nbls_groth16_verify(nbls_ctx* ctx, const nbls_groth16_vk* vk, size_t n, const uint8_t* proofs192, const uint8_t* inputs32, const uint8_t* seed32, int* all_ok, int8_t* status) {

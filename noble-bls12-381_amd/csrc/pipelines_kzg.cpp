@@ -13,8 +13,8 @@
 // point the generator stands in for it in the Miller loop while the flag decides: e(O, Q) = 1, so A = B = O accepts, exactly one of them zero rejects (e(P, Q) != 1 for P != O in
 // the subgroup).  Where the combined check does not accept and the caller asked for statuses, the per-item pass judges every tuple: X_i = C_i + [z_i]pi_i - [y_i]G1 by two
 // ladders and two complete additions, millerLoop(pi_i, table of [tau]G2) * millerLoop(X_i, table of -G2) with table_stride = 0, one batched final exponentiation, rlc_is_one.
-// The seed, the staged [tau]G2 | -G2 | seed, the pairs block, the opening launches, the read-back with its verdict and the close of the per-item pass are KzgFrame's
-// (kzg_common.cpp), shared with the cell verifier; the rest of the chain is this file's.
+// The staged [tau]G2 | -G2 | seed, the pairs block, the opening launches, the read-back with its verdict and the close of the per-item pass are KzgFrame's (kzg_common.cpp),
+// shared with the cell verifier; the seed and the device helpers KzgFrame runs are shared with every weighted verifier; the rest of the chain is this file's.
 // Scratch slots: SB_STAGED and SB_KZG_* (nbls_internal.h, M_KZG_OWN); the decoder and the ladders run on the main slots, the MSMs on MSM_RLC's (MSM_MAIN holds SB_STAGED).
 #include "nbls_internal.h"
 #include "fr_exec.h"
@@ -42,7 +42,7 @@ static int kzg_pipeline(nbls_ctx* ctx, const KzgIn& in, int* all_ok, int8_t* sta
   const size_t n = in.n;
   std::vector<uint8_t> zhost;   // (declared in front of the staged block: it outlives the wait of that block's destructor)
   uint8_t seed[32]; int r; bool more;
-  if ((r = kzg_seed(in.seed32, seed))) return r;
+  if ((r = rlc_seed(in.seed32, seed))) return r;
   DEV_ENTER(ctx, nullptr);
   Staged io(ctx, s);
   KzgFrame fr(ctx, io, s, n, SB_KZG_PAIRS, SB_KZG_OUT, SB_KZG_ITEMS);
@@ -56,7 +56,7 @@ static int kzg_pipeline(nbls_ctx* ctx, const KzgIn& in, int* all_ok, int8_t* sta
   const size_t a_w = carve(&sz_sc, n * 32), a_s1 = carve(&sz_sc, n * 32), a_s2 = carve(&sz_sc, (2 * n + 1) * 32), a_t = carve(&sz_sc, n * 32), a_y = carve(&sz_sc, n * 32), a_yst = carve(&sz_sc, n), a_z = carve(&sz_sc, n * 32);
   uint8_t *c, *PTS, *SC, *IT; const uint8_t* roots = nullptr;
   if ((r = need(ctx, SB_STAGED, io.in_bytes, &c)) || (r = need(ctx, SB_KZG_POINTS, sz_pt, &PTS)) || (r = need(ctx, SB_KZG_SCALARS, sz_sc, &SC)) || (r = fr.take()) ||
-      (in.blobs && (r = kzg_table(ctx, KZG_ROOTS, in.log2_n, 0, s, &roots))) || (r = io.send(c, kzg_back_bytes(n))))
+      (in.blobs && (r = kzg_table(ctx, KZG_ROOTS, in.log2_n, 0, s, &roots))) || (r = io.send(c, back_bytes(n))))
     return r;
   uint8_t *AFF = PTS + a_aff, *DST = PTS + a_dst, *W = SC + a_w, *S1 = SC + a_s1, *S2 = SC + a_s2, *T = SC + a_t, *Y = SC + a_y, *YST = SC + a_yst;
   const uint8_t *d_z = in.blobs ? SC + a_z : c + o_z, *d_y = in.blobs ? Y : c + o_y;

@@ -12,7 +12,7 @@
 //            -> kzg_cell_items_kernel: the scalars, the commitment of every cell gathered
 //            -> A: the 64-bit MSM over the proofs; B: a 64-bit MSM over the gathered commitments + a 256-bit MSM over the proofs + msm_rows_dev with ONE row of c scalars against
 //               the handle's first c points, joined by two complete additions -> two Miller loops -> product -> final exponentiation -> compared with one (KzgFrame::decide)
-//            -> D2H copy; acceptance by the frame's rule, which kzg_pipeline shares (kzg_frame.h: A = B = O accepts, exactly one of them zero rejects)
+//            -> D2H copy; acceptance by the frame's rule, which kzg_pipeline shares (verifier_frame.h: A = B = O accepts, exactly one of them zero rejects)
 // Where the combined check does not accept and the caller asked for statuses, the per-cell pass judges every cell with the equation above: the kernel's rows mode writes
 // -a_(k,.) into the rows of msm_rows_dev (n rows of c points), one ladder for [s_k]pi_k, the gathered C, and the frame's per-item tail (KzgFrame::items_close).
 // Scratch slots: SB_STAGED and SB_KZGV_* (nbls_internal.h, M_KZGV_OWN); the decoder and the ladder run on the main slots, the MSMs on MSM_RLC's, the batched MSM on SB_MSMB_*.
@@ -30,7 +30,7 @@ static int verify_cells_pipeline(nbls_ctx* ctx, const VerifyCellsIn& in, int* al
   const unsigned L = in.mono->log2_n, lc = in.log2_cell, lm = L + 1 - lc;
   const size_t n = in.n, nc = in.n_commitments, cc = (size_t)1 << lc;
   uint8_t seed[32]; int r; bool more;
-  if ((r = kzg_seed(in.seed32, seed))) return r;
+  if ((r = rlc_seed(in.seed32, seed))) return r;
   DEV_ENTER(ctx, nullptr);
   Staged io(ctx, s);
   KzgFrame fr(ctx, io, s, n, SB_KZGV_PAIRS, SB_KZGV_OUT, SB_KZGV_ITEMS);
@@ -47,7 +47,7 @@ static int verify_cells_pipeline(nbls_ctx* ctx, const VerifyCellsIn& in, int* al
   uint8_t *c, *PTS, *SC, *ROWS; const uint8_t *sroots, *iroots = nullptr, *ishifts;
   if ((r = need(ctx, SB_STAGED, io.in_bytes, &c)) || (r = need(ctx, SB_KZGV_POINTS, sz_pt, &PTS)) || (r = need(ctx, SB_KZGV_SCALARS, sz_sc, &SC)) || (r = fr.take()) ||
       (r = msm_rows_dev_plan(ctx, cc, 1, &pl_one)) || (r = kzg_table(ctx, KZG_ROOTS, lm, 0, s, &sroots)) || (lc && (r = kzg_table(ctx, KZG_INV_ROOTS, lc, 0, s, &iroots))) ||
-      (r = kzg_table(ctx, KZG_CELL_ISHIFTS, L, lc, s, &ishifts)) || (r = io.send(c, kzg_back_bytes(n))))
+      (r = kzg_table(ctx, KZG_CELL_ISHIFTS, L, lc, s, &ishifts)) || (r = io.send(c, back_bytes(n))))
     return r;
   uint8_t *AFF = PTS + a_aff, *PF = AFF + nc * 96, *GATH = PTS + a_gath, *DST = PTS + a_dst, *GST = PTS + a_gst;
   uint8_t *W = SC + a_w, *S1 = SC + a_s1, *S2 = SC + a_s2, *S3 = SC + a_s3, *ZS = SC + a_zs, *PART = SC + a_part, *SROW = SC + a_srow, *PRE0 = SC + a_pre0;

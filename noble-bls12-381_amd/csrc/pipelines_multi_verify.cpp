@@ -22,13 +22,18 @@
 #include <new>
 #include <sys/random.h>
 
-int os_seed(uint8_t* seed) {   // 32 bytes from getrandom(2): the seed of the secret weights when the caller passes none (also pipelines_kzg.cpp)
+int os_seed(uint8_t* seed) {   // 32 bytes from getrandom(2): the seed of the secret weights when the caller passes none
   size_t got = 0;
   while (got < 32) {
     const ssize_t k = getrandom(seed + got, 32 - got, 0);
     if (k < 0) { if (errno == EINTR) continue; return NBLS_ENOSUP; }   // never a fixed seed instead
     got += (size_t)k;
   }
+  return NBLS_OK;
+}
+int rlc_seed(const uint8_t* seed32, uint8_t* seed) {   // every weighted verifier's first step (this file, pipelines_kzg*.cpp, pipelines_groth16.cpp)
+  if (!seed32) return os_seed(seed);
+  memcpy(seed, seed32, 32);
   return NBLS_OK;
 }
 
@@ -97,8 +102,7 @@ static int group_keys(nbls_ctx* ctx, size_t n, size_t m, size_t maxgroup, const 
 int verify_multiple_pipeline(nbls_ctx* ctx, const MultiVerifyIn& in, int* all_ok, int8_t* status) {
   const size_t n = in.n; const uint32_t* offsets = in.offsets; const AggKeys* agg = in.agg; const MsgGroups* mg = in.mg;
   uint8_t seed[32];
-  if (in.seed32) memcpy(seed, in.seed32, 32);
-  else { const int e = os_seed(seed); if (e) return e; }
+  const int e = rlc_seed(in.seed32, seed); if (e) return e;
   const size_t nh = mg ? mg->n_msgs : n;
   for (size_t i = 0; i < nh; i++) if (offsets[i + 1] < offsets[i]) return NBLS_EINVAL;
   // shared messages: one pass over the index validates it and counts every group, a second one sorts the sets by group (counting sort, stable): goff[nh + 1] | order[n]
@@ -187,11 +191,7 @@ int verify_multiple_pipeline(nbls_ctx* ctx, const MultiVerifyIn& in, int* all_ok
   if ((r = need(ctx, SB_RLC_PER_SET, n * (192 + 384 + 576) + n, &X))) return r;
   uint8_t *G1x = X, *G2x = G1x + n * 192, *E = G2x + n * 384, *V = E + n * 576;
   LAUNCHCHK(nbls_rlc_interleave_launch((unsigned)n, mg ? (const uint32_t*)(c + o_idx) : nullptr, PK, ctx->neg_g1, H, SG, G1x, G2x, s));
-  if ((r = run(ctx, P_MILLER_RAW2, n, {B(0, G1x, 192), B(1, G2x, 384), B(3, ctx->F, F12)}, s)) || (r = run(ctx, P_NORM_RAW, n, {B(3, ctx->F, F12), B(4, ctx->N, RAW)}, s)) ||
-      (r = final_exp_pipeline(ctx, Window(), n, ctx->F, E, s)))
-    return r;
-  LAUNCHCHK(nbls_rlc_is_one_launch((unsigned)n, E, V, s));
-  if ((r = read_back(ctx, s, V, n, &got))) return r;
+  if ((r = run(ctx, P_MILLER_RAW2, n, {B(0, G1x, 192), B(1, G2x, 384), B(3, ctx->F, F12)}, s)) || (r = items_is_one(ctx, n, E, V, s)) || (r = read_back(ctx, s, V, n, &got))) return r;
   int all = 1;
   for (size_t i = 0; i < n; i++) {
     // the reference's order (oracle_verify): the key decodes, the message hashes, the signature decodes, the pairing throws on a zero point ("No pairings at point of Infinity")
@@ -262,20 +262,15 @@ EXPORT int nbls_verify_aggregates_indexed_shared(nbls_ctx* ctx, const nbls_keyse
 // The key table: PointG1.fromHex (index.ts:298-327) of every key once, kept as raw projective points with the identity in place of zero keys and keys that did not decode, and the
 // decoder's status of every key (which nbls_verify_aggregates_indexed reports for a set that names the key).  Owns its device memory: usable from any context on the same device,
 // and after the creating context is destroyed.
-EXPORT int nbls_keyset_create(nbls_ctx* ctx, size_t n, const uint8_t* pks48, int8_t* status, nbls_keyset** out) {
-  WHOLE_CALL(ctx);
-  if (!ctx || !n || !pks48 || !out || n > AGG_MAX_KEYS) return NBLS_EINVAL;
-  *out = nullptr;
+static int keyset_build(nbls_ctx* ctx, nbls_keyset* ks, const uint8_t* pks48, int8_t* status) {
+  const size_t n = ks->n;
   LOCKED(ctx);
   HostIO io{ctx};
   void *d = io.alloc(n * 48), *a = io.alloc(n * 96);
   if (!d || !a) return NBLS_EHIP;
-  nbls_keyset* ks = new (std::nothrow) nbls_keyset;
-  if (!ks) return NBLS_EHIP;
-  ks->device = ctx->device; ks->n = n;
   uint8_t* mem = nullptr;
-  if (hipMalloc(&mem, n * 3 * RAW + n) != hipSuccess) { ctx->last_hip = (int)hipGetLastError(); delete ks; return NBLS_EHIP; }
-  ks->pts = mem; ks->st = (int8_t*)(mem + n * 3 * RAW);
+  if (hipMalloc(&mem, n * 3 * RAW + n) != hipSuccess) { ctx->last_hip = (int)hipGetLastError(); return NBLS_EHIP; }
+  ks->pts = mem; ks->st = (int8_t*)(mem + n * 3 * RAW);   // (freed by the caller's nbls_keyset_destroy on every error return)
   int r = NBLS_OK;
   hipError_t e = hipMemcpyAsync(d, pks48, n * 48, hipMemcpyHostToDevice, s);
   if (e == hipSuccess && !(r = dev_decompress(ctx, false, n, d, a, ks->st, s)) && !(r = run(ctx, P_G1_TO_PROJ, n, {B(0, a, 96), B(3, ks->pts, 3 * RAW)}, s))) {
@@ -285,16 +280,18 @@ EXPORT int nbls_keyset_create(nbls_ctx* ctx, size_t n, const uint8_t* pks48, int
     if (!r && e == hipSuccess) e = hipStreamSynchronize(s);
   }
   if (e != hipSuccess) { ctx->last_hip = (int)e; r = NBLS_EHIP; }
-  if (r) { (void)hipStreamSynchronize(s); hipFree(mem); delete ks; return r; }
-  *out = ks;
-  return NBLS_OK;
+  if (r) (void)hipStreamSynchronize(s);
+  return r;
+}
+EXPORT int nbls_keyset_create(nbls_ctx* ctx, size_t n, const uint8_t* pks48, int8_t* status, nbls_keyset** out) {
+  WHOLE_CALL(ctx);
+  if (!ctx || !n || !pks48 || !out || n > AGG_MAX_KEYS) return NBLS_EINVAL;
+  *out = nullptr;
+  return handle_create(ctx, out, nbls_keyset_destroy, [&](nbls_keyset* ks) { ks->n = n; return keyset_build(ctx, ks, pks48, status); });
 }
 EXPORT void nbls_keyset_destroy(nbls_keyset* ks) {
   if (!ks) return;
-  int cur = 0;
-  const bool restore = hipGetDevice(&cur) == hipSuccess;
-  if (hipSetDevice(ks->device) == hipSuccess) (void)hipFree(ks->pts);
-  if (restore) (void)hipSetDevice(cur);
+  handle_free(ks->device, {ks->pts});
   delete ks;
 }
 EXPORT int nbls_keyset_size(const nbls_keyset* ks, size_t* n) {

@@ -183,143 +183,82 @@ def group_messages(msgs):
     return distinct, index
 
 
-class KeySet:
-    """A table of decoded keys in device memory (nbls_keyset_create; Engine.create_keyset).  Freed by close() or when the object goes away."""
+class _DeviceHandle:
+    """What the five handle classes below share: the library, the handle, close() / __del__ through the subclass's destroy function, and the read through one of its getters.
+    _destroy: the name of the destroy function; _thing: what the closed-handle message calls the object"""
+    _destroy = _thing = None
 
     def __init__(self, lib, handle):
         self.lib = lib
         self.h = handle
+
+    def _get(self, getter, *ctypes_out):
+        out = [t(0) for t in ctypes_out]
+        if self.h is None or getattr(self.lib, getter)(self.h, *[C.byref(o) for o in out]) != 0:
+            raise NblsError('%s: the %s is closed' % (type(self).__name__, self._thing))
+        return [o.value for o in out]
+
+    def close(self):
+        if getattr(self, 'h', None):
+            getattr(self.lib, self._destroy)(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class KeySet(_DeviceHandle):
+    """A table of decoded keys in device memory (nbls_keyset_create; Engine.create_keyset).  Freed by close() or when the object goes away."""
+    _destroy, _thing = 'nbls_keyset_destroy', 'table'
 
     def __len__(self):
-        n = C.c_size_t(0)
-        if self.h is None or self.lib.nbls_keyset_size(self.h, C.byref(n)) != 0:
-            raise NblsError('KeySet: the table is closed')
-        return n.value
-
-    def close(self):
-        if getattr(self, 'h', None):
-            self.lib.nbls_keyset_destroy(self.h)
-        self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return self._get('nbls_keyset_size', C.c_size_t)[0]
 
 
-class KzgSetup:
+class KzgSetup(_DeviceHandle):
     """A trusted setup's Lagrange basis in device memory (nbls_kzg_setup_create; Engine.kzg_setup), decoded and split once.  Freed by close() or when the object goes away."""
-
-    def __init__(self, lib, handle):
-        self.lib = lib
-        self.h = handle
+    _destroy, _thing = 'nbls_kzg_setup_destroy', 'setup'
 
     @property
     def log2_n(self):
-        k = C.c_uint(0)
-        if self.h is None or self.lib.nbls_kzg_setup_log2n(self.h, C.byref(k)) != 0:
-            raise NblsError('KzgSetup: the setup is closed')
-        return k.value
-
-    def close(self):
-        if getattr(self, 'h', None):
-            self.lib.nbls_kzg_setup_destroy(self.h)
-        self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return self._get('nbls_kzg_setup_log2n', C.c_uint)[0]
 
 
-class KzgFk20Setup:
+class KzgFk20Setup(_DeviceHandle):
     """The fixed part of the FK20 cell proofs for one (log2_n, log2_cell) in device memory (nbls_kzg_fk20_create; Engine.kzg_fk20_setup): the transformed stripes of the
     monomial basis and the projection matrix.  Usable from every Engine on its device.  Freed by close() or when the object goes away."""
-
-    def __init__(self, lib, handle):
-        self.lib = lib
-        self.h = handle
-
-    def _params(self):
-        a, b = C.c_uint(0), C.c_uint(0)
-        if self.h is None or self.lib.nbls_kzg_fk20_params(self.h, C.byref(a), C.byref(b)) != 0:
-            raise NblsError('KzgFk20Setup: the setup is closed')
-        return a.value, b.value
+    _destroy, _thing = 'nbls_kzg_fk20_destroy', 'setup'
 
     @property
     def log2_n(self):
-        return self._params()[0]
+        return self._get('nbls_kzg_fk20_params', C.c_uint, C.c_uint)[0]
 
     @property
     def log2_cell(self):
-        return self._params()[1]
-
-    def close(self):
-        if getattr(self, 'h', None):
-            self.lib.nbls_kzg_fk20_destroy(self.h)
-        self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return self._get('nbls_kzg_fk20_params', C.c_uint, C.c_uint)[1]
 
 
-class KzgMonomialSetup:
+class KzgMonomialSetup(_DeviceHandle):
     """A trusted setup's monomial basis [tau^i]G1 in device memory (nbls_kzg_monomial_create; Engine.kzg_monomial_setup), decoded and split once.  Freed by close() or when the
     object goes away."""
-
-    def __init__(self, lib, handle):
-        self.lib = lib
-        self.h = handle
+    _destroy, _thing = 'nbls_kzg_monomial_destroy', 'setup'
 
     @property
     def log2_n(self):
-        k = C.c_uint(0)
-        if self.h is None or self.lib.nbls_kzg_monomial_log2n(self.h, C.byref(k)) != 0:
-            raise NblsError('KzgMonomialSetup: the setup is closed')
-        return k.value
-
-    def close(self):
-        if getattr(self, 'h', None):
-            self.lib.nbls_kzg_monomial_destroy(self.h)
-        self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return self._get('nbls_kzg_monomial_log2n', C.c_uint)[0]
 
 
-class Groth16Vk:
+class Groth16Vk(_DeviceHandle):
     """A Groth16 verifying key in device memory (nbls_groth16_vk_create; Engine.groth16_vk): alpha, the line tables of -beta, -gamma, -delta and the IC points, decoded and
     converted once.  Usable from every Engine on its device.  Freed by close() or when the object goes away."""
-
-    def __init__(self, lib, handle):
-        self.lib = lib
-        self.h = handle
+    _destroy, _thing = 'nbls_groth16_vk_destroy', 'key'
 
     @property
     def inputs(self):
-        m = C.c_size_t(0)
-        if self.h is None or self.lib.nbls_groth16_vk_inputs(self.h, C.byref(m)) != 0:
-            raise NblsError('Groth16Vk: the key is closed')
-        return m.value
-
-    def close(self):
-        if getattr(self, 'h', None):
-            self.lib.nbls_groth16_vk_destroy(self.h)
-        self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return self._get('nbls_groth16_vk_inputs', C.c_size_t)[0]
 
 
 class KzgSetupError(NblsError):

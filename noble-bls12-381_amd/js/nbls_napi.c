@@ -597,33 +597,55 @@ static napi_value KzgVerifyBlobsAsync(napi_env env, napi_callback_info info) { r
  *   kzgSetupDestroy(handle)              frees it now; the handle is dead afterwards.  Not while an asynchronous call uses it
  *   kzgProve(kind, handle, blobs, aux)   kind 0: commitments (aux null) -> out = n x 48; 1: proofs at the points aux = z32 -> out = n x 48 proofs, then n x 32 values y;
  *                                        2: blob proofs, aux = the commitments or null -> out = n x 48 commitments, then n x 48 proofs.  status = one byte per blob.  + Async */
-typedef struct { nbls_kzg_setup* s; } setup_box;
-static void setup_finalize(napi_env env, void* data, void* hint) { (void)env; (void)hint; setup_box* b = (setup_box*)data; if (b->s && p_nbls_kzg_setup_destroy) p_nbls_kzg_setup_destroy(b->s); free(b); }
+/* The device handles (a Lagrange setup, a monomial setup, a Groth16 key) travel as one kind of external: a box that knows which destroy function its handle takes.  h == NULL:
+ * destroyed already.  box_wrap is the tail of the three create calls: a refused create throws the library's error with the statuses as `status`; else the handle is wrapped,
+ * or destroyed where it cannot be */
+typedef enum { BOX_SETUP, BOX_MONOMIAL, BOX_G16_VK } box_kind;
+typedef struct { void* h; box_kind kind; } handle_box;
+static void box_destroy(handle_box* b) {
+  if (!b->h) return;
+  if (b->kind == BOX_SETUP) { if (p_nbls_kzg_setup_destroy) p_nbls_kzg_setup_destroy((nbls_kzg_setup*)b->h); }
+  else if (b->kind == BOX_MONOMIAL) { if (p_nbls_kzg_monomial_destroy) p_nbls_kzg_monomial_destroy((nbls_kzg_monomial*)b->h); }
+  else if (p_nbls_groth16_vk_destroy) p_nbls_groth16_vk_destroy((nbls_groth16_vk*)b->h);
+  b->h = NULL;
+}
+static void box_finalize(napi_env env, void* data, void* hint) { (void)env; (void)hint; box_destroy((handle_box*)data); free(data); }
+static handle_box* box_new(napi_env env, box_kind kind) {
+  handle_box* box = (handle_box*)calloc(1, sizeof *box);
+  if (!box) napi_throw_error(env, NULL, "out of memory"); else box->kind = kind;
+  return box;
+}
+static napi_value box_wrap(napi_env env, handle_box* box, int rc, napi_value vs) {
+  if (rc) { free(box); napi_value err = thr_error(env, rc); napi_set_named_property(env, err, "status", vs); napi_throw(env, err); return NULL; }
+  napi_value h;
+  if (napi_create_external(env, box, box_finalize, NULL, &h) != napi_ok) { box_destroy(box); free(box); napi_throw_error(env, NULL, "napi_create_external failed"); return NULL; }
+  return h;
+}
+static napi_value box_destroy_call(napi_env env, napi_callback_info info, const char* expected) {
+  ARGS(1);
+  handle_box* box = NULL;
+  if (napi_get_value_external(env, argv[0], (void**)&box) != napi_ok || !box) { napi_throw_type_error(env, NULL, expected); return NULL; }
+  box_destroy(box);
+  return NULL;
+}
 static napi_value KzgSetupCreate(napi_env env, napi_callback_info info) {
   ARGS(2); NEED_CTX(); BYTES(1, pts, lp);
   int32_t log2n; if (napi_get_value_int32(env, argv[0], &log2n) != napi_ok) { napi_throw_type_error(env, NULL, "expected a number for log2n"); return NULL; }
   if (log2n < 1 || log2n > 12 || lp != (size_t)48 << log2n) { napi_throw_range_error(env, NULL, "log2n in 1 .. 12 and 48 << log2n bytes of compressed points"); return NULL; }
   uint8_t* st; napi_value vs = new_u8(env, (size_t)1 << log2n, &st); ALLOCATED(vs);
-  setup_box* box = (setup_box*)calloc(1, sizeof *box); if (!box) { napi_throw_error(env, NULL, "out of memory"); return NULL; }
-  const int rc = p_nbls_kzg_setup_create(ctx, (unsigned)log2n, pts, (int8_t*)st, &box->s);
-  if (rc) { free(box); napi_value err = thr_error(env, rc); napi_set_named_property(env, err, "status", vs); napi_throw(env, err); return NULL; }
-  napi_value h;
-  if (napi_create_external(env, box, setup_finalize, NULL, &h) != napi_ok) { p_nbls_kzg_setup_destroy(box->s); free(box); napi_throw_error(env, NULL, "napi_create_external failed"); return NULL; }
-  return h;
+  handle_box* box = box_new(env, BOX_SETUP); if (!box) return NULL;
+  nbls_kzg_setup* su = NULL;
+  const int rc = p_nbls_kzg_setup_create(ctx, (unsigned)log2n, pts, (int8_t*)st, &su);
+  box->h = su;
+  return box_wrap(env, box, rc, vs);
 }
-static napi_value KzgSetupDestroy(napi_env env, napi_callback_info info) {
-  ARGS(1);
-  setup_box* box = NULL;
-  if (napi_get_value_external(env, argv[0], (void**)&box) != napi_ok || !box) { napi_throw_type_error(env, NULL, "expected a setup handle"); return NULL; }
-  if (box->s) { p_nbls_kzg_setup_destroy(box->s); box->s = NULL; }
-  return NULL;
-}
+static napi_value KzgSetupDestroy(napi_env env, napi_callback_info info) { return box_destroy_call(env, info, "expected a setup handle"); }
 static napi_value kzg_prove_call(napi_env env, napi_callback_info info, int async) {
   ARGS(4); NEED_CTX(); BYTES(2, blobs, lb);
   int32_t kind; if (napi_get_value_int32(env, argv[0], &kind) != napi_ok || kind < 0 || kind > 2) { napi_throw_type_error(env, NULL, "expected the kind 0, 1 or 2"); return NULL; }
-  setup_box* box = NULL;
-  if (napi_get_value_external(env, argv[1], (void**)&box) != napi_ok || !box || !box->s) { napi_throw_type_error(env, NULL, "expected a live setup handle"); return NULL; }
-  unsigned log2n = 0; p_nbls_kzg_setup_log2n(box->s, &log2n);
+  handle_box* box = NULL;
+  if (napi_get_value_external(env, argv[1], (void**)&box) != napi_ok || !box || !box->h) { napi_throw_type_error(env, NULL, "expected a live setup handle"); return NULL; }
+  unsigned log2n = 0; p_nbls_kzg_setup_log2n((nbls_kzg_setup*)box->h, &log2n);
   uint8_t* aux = NULL; size_t la = 0;
   napi_valuetype t; napi_typeof(env, argv[3], &t);
   if (t != napi_null && t != napi_undefined && !get_bytes(env, argv[3], &aux, &la)) { napi_throw_type_error(env, NULL, "expected Uint8Array or null"); return NULL; }
@@ -631,7 +653,7 @@ static napi_value kzg_prove_call(napi_env env, napi_callback_info info, int asyn
   if (!n || lb != (n * 32) << log2n || (kind == 0 && aux) || (kind == 1 && (!aux || la != n * 32)) || (kind == 2 && aux && la != n * 48)) {
     napi_throw_range_error(env, NULL, "n blobs of 32 << log2n bytes; n points of 32 bytes (proofs) or n commitments of 48 bytes or null (blob proofs)"); return NULL; }
   thr_job job; memset(&job, 0, sizeof job);
-  job.kind = 6 + kind; job.su = box->s; job.b = blobs; job.a = aux; job.n = n;
+  job.kind = 6 + kind; job.su = (nbls_kzg_setup*)box->h; job.b = blobs; job.a = aux; job.n = n;
   const size_t lo = kind == 0 ? n * 48 : kind == 1 ? n * 80 : n * 96;
   napi_value vo = new_u8(env, lo, &job.out), vs = new_u8(env, n, (uint8_t**)&job.st); ALLOCATED(vo); ALLOCATED(vs);
   memset(job.out, 0, lo); memset(job.st, 0, n);
@@ -684,37 +706,28 @@ static napi_value kzg_cells_call(napi_env env, napi_callback_info info, int asyn
 }
 static napi_value KzgComputeCells(napi_env env, napi_callback_info info) { return kzg_cells_call(env, info, 0); }
 static napi_value KzgComputeCellsAsync(napi_env env, napi_callback_info info) { return kzg_cells_call(env, info, 1); }
-typedef struct { nbls_kzg_monomial* m; } monomial_box;
-static void monomial_finalize(napi_env env, void* data, void* hint) { (void)env; (void)hint; monomial_box* b = (monomial_box*)data; if (b->m && p_nbls_kzg_monomial_destroy) p_nbls_kzg_monomial_destroy(b->m); free(b); }
 static napi_value KzgMonomialCreate(napi_env env, napi_callback_info info) {
   ARGS(2); NEED_CTX(); BYTES(1, pts, lp);
   int32_t log2n; if (napi_get_value_int32(env, argv[0], &log2n) != napi_ok) { napi_throw_type_error(env, NULL, "expected a number for log2n"); return NULL; }
   if (log2n < 1 || log2n > 12 || lp != (size_t)48 << log2n) { napi_throw_range_error(env, NULL, "log2n in 1 .. 12 and 48 << log2n bytes of compressed points"); return NULL; }
   uint8_t* st; napi_value vs = new_u8(env, (size_t)1 << log2n, &st); ALLOCATED(vs);
-  monomial_box* box = (monomial_box*)calloc(1, sizeof *box); if (!box) { napi_throw_error(env, NULL, "out of memory"); return NULL; }
-  const int rc = p_nbls_kzg_monomial_create(ctx, (unsigned)log2n, pts, (int8_t*)st, &box->m);
-  if (rc) { free(box); napi_value err = thr_error(env, rc); napi_set_named_property(env, err, "status", vs); napi_throw(env, err); return NULL; }
-  napi_value h;
-  if (napi_create_external(env, box, monomial_finalize, NULL, &h) != napi_ok) { p_nbls_kzg_monomial_destroy(box->m); free(box); napi_throw_error(env, NULL, "napi_create_external failed"); return NULL; }
-  return h;
+  handle_box* box = box_new(env, BOX_MONOMIAL); if (!box) return NULL;
+  nbls_kzg_monomial* mo = NULL;
+  const int rc = p_nbls_kzg_monomial_create(ctx, (unsigned)log2n, pts, (int8_t*)st, &mo);
+  box->h = mo;
+  return box_wrap(env, box, rc, vs);
 }
-static napi_value KzgMonomialDestroy(napi_env env, napi_callback_info info) {
-  ARGS(1);
-  monomial_box* box = NULL;
-  if (napi_get_value_external(env, argv[0], (void**)&box) != napi_ok || !box) { napi_throw_type_error(env, NULL, "expected a monomial setup handle"); return NULL; }
-  if (box->m) { p_nbls_kzg_monomial_destroy(box->m); box->m = NULL; }
-  return NULL;
-}
+static napi_value KzgMonomialDestroy(napi_env env, napi_callback_info info) { return box_destroy_call(env, info, "expected a monomial setup handle"); }
 static napi_value kzg_cells_proofs_call(napi_env env, napi_callback_info info, int async) {
   ARGS(3); NEED_CTX(); BYTES(2, blobs, lb);
-  monomial_box* box = NULL;
-  if (napi_get_value_external(env, argv[0], (void**)&box) != napi_ok || !box || !box->m) { napi_throw_type_error(env, NULL, "expected a live monomial setup handle"); return NULL; }
-  unsigned log2n = 0; p_nbls_kzg_monomial_log2n(box->m, &log2n);
+  handle_box* box = NULL;
+  if (napi_get_value_external(env, argv[0], (void**)&box) != napi_ok || !box || !box->h) { napi_throw_type_error(env, NULL, "expected a live monomial setup handle"); return NULL; }
+  unsigned log2n = 0; p_nbls_kzg_monomial_log2n((nbls_kzg_monomial*)box->h, &log2n);
   int32_t log2c; if (napi_get_value_int32(env, argv[1], &log2c) != napi_ok) { napi_throw_type_error(env, NULL, "expected a number for log2cell"); return NULL; }
   const size_t n = lb >> (5 + log2n);
   if (log2c < 0 || (unsigned)log2c > log2n || !n || lb != (n * 32) << log2n) { napi_throw_range_error(env, NULL, "log2cell in 0 .. log2n and n blobs of 32 << log2n bytes"); return NULL; }
   thr_job job; memset(&job, 0, sizeof job);
-  job.kind = 11; job.mo = box->m; job.g2 = log2c; job.b = blobs; job.n = n; job.proofs_at = 2 * lb;
+  job.kind = 11; job.mo = (nbls_kzg_monomial*)box->h; job.g2 = log2c; job.b = blobs; job.n = n; job.proofs_at = 2 * lb;
   const size_t lo = 2 * lb + n * ((size_t)2 << (log2n - log2c)) * 48;
   napi_value vo = new_u8(env, lo, &job.out), vs = new_u8(env, n, (uint8_t**)&job.st); ALLOCATED(vo); ALLOCATED(vs);
   memset(job.out, 0, lo); memset(job.st, 0, n);
@@ -725,8 +738,8 @@ static napi_value KzgCellsAndProofsAsync(napi_env env, napi_callback_info info) 
 
 static napi_value kzg_verify_cells_call(napi_env env, napi_callback_info info, int async) {
   ARGS(10); NEED_CTX(); BYTES(2, cs, lc); BYTES(3, ci, lci); BYTES(4, ki, lki); BYTES(5, cells, lb); BYTES(6, ps, lp); BYTES(7, tau, lt);
-  monomial_box* box = NULL;
-  if (napi_get_value_external(env, argv[0], (void**)&box) != napi_ok || !box || !box->m) { napi_throw_type_error(env, NULL, "expected a live monomial setup handle"); return NULL; }
+  handle_box* box = NULL;
+  if (napi_get_value_external(env, argv[0], (void**)&box) != napi_ok || !box || !box->h) { napi_throw_type_error(env, NULL, "expected a live monomial setup handle"); return NULL; }
   int32_t log2c, per;
   if (napi_get_value_int32(env, argv[1], &log2c) != napi_ok || napi_get_value_int32(env, argv[9], &per) != napi_ok) { napi_throw_type_error(env, NULL, "expected numbers for log2cell and perItem"); return NULL; }
   const uint8_t* seed; if (!kzg_seed(env, argv[8], &seed)) return NULL;
@@ -734,7 +747,7 @@ static napi_value kzg_verify_cells_call(napi_env env, napi_callback_info info, i
   if (log2c < 0 || log2c > 6 || !n || !nc || lp != n * 48 || lc != nc * 48 || lci != n * 4 || lki != n * 4 || ((uintptr_t)ci | (uintptr_t)ki) % 4 || lb != (n * 32) << log2c || lt != 96) {
     napi_throw_range_error(env, NULL, "log2cell in 0 .. 6, commitments of 48 bytes, per cell two 32-bit indices, 32 << log2cell bytes and a proof of 48 bytes, 96 bytes of [tau^c]G2"); return NULL; }
   thr_job job; memset(&job, 0, sizeof job);
-  job.kind = 12; job.mo = box->m; job.g2 = log2c; job.a = cs; job.proofs_at = nc; job.offs = (const uint32_t*)ci; job.coffs = (const uint32_t*)ki; job.b = cells; job.proofs = ps; job.tau = tau;
+  job.kind = 12; job.mo = (nbls_kzg_monomial*)box->h; job.g2 = log2c; job.a = cs; job.proofs_at = nc; job.offs = (const uint32_t*)ci; job.coffs = (const uint32_t*)ki; job.b = cells; job.proofs = ps; job.tau = tau;
   job.seed = seed; job.per_item = per != 0; job.n = n;
   napi_value vo = new_u8(env, 4, &job.out), vs = new_u8(env, n, (uint8_t**)&job.st); ALLOCATED(vo); ALLOCATED(vs);
   memset(job.out, 0, 4); memset(job.st, 0, n);
@@ -747,10 +760,10 @@ static napi_value KzgVerifyCellsAsync(napi_env env, napi_callback_info info) { r
 /* proofs == 0: (log2n, log2cell, offsets, index, cells); else (handle, log2cell, offsets, index, cells) */
 static napi_value kzg_recover_call(napi_env env, napi_callback_info info, int proofs, int async) {
   ARGS(5); NEED_CTX(); BYTES(2, offs, lo); BYTES(3, idx, li); BYTES(4, cells, lb);
-  monomial_box* box = NULL; int32_t l2n = 0, log2c;
+  handle_box* box = NULL; int32_t l2n = 0, log2c;
   if (proofs) {
-    if (napi_get_value_external(env, argv[0], (void**)&box) != napi_ok || !box || !box->m) { napi_throw_type_error(env, NULL, "expected a live monomial setup handle"); return NULL; }
-    unsigned v = 0; p_nbls_kzg_monomial_log2n(box->m, &v); l2n = (int32_t)v;
+    if (napi_get_value_external(env, argv[0], (void**)&box) != napi_ok || !box || !box->h) { napi_throw_type_error(env, NULL, "expected a live monomial setup handle"); return NULL; }
+    unsigned v = 0; p_nbls_kzg_monomial_log2n((nbls_kzg_monomial*)box->h, &v); l2n = (int32_t)v;
   } else if (napi_get_value_int32(env, argv[0], &l2n) != napi_ok) { napi_throw_type_error(env, NULL, "expected a number for log2n"); return NULL; }
   if (napi_get_value_int32(env, argv[1], &log2c) != napi_ok) { napi_throw_type_error(env, NULL, "expected a number for log2cell"); return NULL; }
   size_t n = 0;
@@ -759,7 +772,7 @@ static napi_value kzg_recover_call(napi_env env, napi_callback_info info, int pr
   for (size_t i = 0; ok && i < n; i++) ok = ((const uint32_t*)offs)[i] <= ((const uint32_t*)offs)[i + 1];
   if (!ok) { napi_throw_range_error(env, NULL, "log2n in 1 .. 12, log2cell in 0 .. log2n, blobs + 1 non-decreasing 32-bit offsets from 0, one 32-bit index and 32 << log2cell bytes per given cell"); return NULL; }
   thr_job job; memset(&job, 0, sizeof job);
-  job.kind = proofs ? 14 : 13; job.op = l2n; job.mo = box ? box->m : NULL; job.g2 = log2c; job.offs = (const uint32_t*)offs; job.coffs = (const uint32_t*)idx; job.b = cells; job.n = n;
+  job.kind = proofs ? 14 : 13; job.op = l2n; job.mo = box ? (nbls_kzg_monomial*)box->h : NULL; job.g2 = log2c; job.offs = (const uint32_t*)offs; job.coffs = (const uint32_t*)idx; job.b = cells; job.n = n;
   job.proofs_at = (n * 64) << l2n;
   const size_t lout = job.proofs_at + (proofs ? n * ((size_t)2 << (l2n - log2c)) * 48 : 0);
   napi_value vo = new_u8(env, lout, &job.out), vs = new_u8(env, n, (uint8_t**)&job.st); ALLOCATED(vo); ALLOCATED(vs);
@@ -777,39 +790,30 @@ static napi_value KzgRecoverCellsAndProofsAsync(napi_env env, napi_callback_info
  *   groth16VkDestroy(handle)                               frees it now; the handle is dead afterwards.  Not while an asynchronous call uses it
  *   groth16Verify(handle, proofs192, inputs32, seed32 | null, perItem), groth16VerifyAsync -> {out, status} as kzgVerifyProofs: out = the verdict (4 bytes, a native int),
  *                                                          status = one byte per proof */
-typedef struct { nbls_groth16_vk* k; } g16_box;
-static void g16_finalize(napi_env env, void* data, void* hint) { (void)env; (void)hint; g16_box* b = (g16_box*)data; if (b->k && p_nbls_groth16_vk_destroy) p_nbls_groth16_vk_destroy(b->k); free(b); }
 static napi_value Groth16VkCreate(napi_env env, napi_callback_info info) {
   ARGS(5); NEED_CTX(); BYTES(0, alpha, la); BYTES(1, beta, lb); BYTES(2, gamma, lg); BYTES(3, delta, ld); BYTES(4, ic, li);
   if (la != 48 || lb != 96 || lg != 96 || ld != 96 || li % 48 || li < 96 || li / 48 - 1 > 65536) {
     napi_throw_range_error(env, NULL, "48 bytes of alpha, 96 bytes each of beta, gamma, delta, and m + 1 points IC_j of 48 bytes, 1 <= m <= 65536"); return NULL; }
   const size_t m = li / 48 - 1;
   uint8_t* st; napi_value vs = new_u8(env, m + 5, &st); ALLOCATED(vs);
-  g16_box* box = (g16_box*)calloc(1, sizeof *box); if (!box) { napi_throw_error(env, NULL, "out of memory"); return NULL; }
-  const int rc = p_nbls_groth16_vk_create(ctx, m, alpha, beta, gamma, delta, ic, (int8_t*)st, &box->k);
-  if (rc) { free(box); napi_value err = thr_error(env, rc); napi_set_named_property(env, err, "status", vs); napi_throw(env, err); return NULL; }
-  napi_value h;
-  if (napi_create_external(env, box, g16_finalize, NULL, &h) != napi_ok) { p_nbls_groth16_vk_destroy(box->k); free(box); napi_throw_error(env, NULL, "napi_create_external failed"); return NULL; }
-  return h;
+  handle_box* box = box_new(env, BOX_G16_VK); if (!box) return NULL;
+  nbls_groth16_vk* vk = NULL;
+  const int rc = p_nbls_groth16_vk_create(ctx, m, alpha, beta, gamma, delta, ic, (int8_t*)st, &vk);
+  box->h = vk;
+  return box_wrap(env, box, rc, vs);
 }
-static napi_value Groth16VkDestroy(napi_env env, napi_callback_info info) {
-  ARGS(1);
-  g16_box* box = NULL;
-  if (napi_get_value_external(env, argv[0], (void**)&box) != napi_ok || !box) { napi_throw_type_error(env, NULL, "expected a Groth16 key handle"); return NULL; }
-  if (box->k) { p_nbls_groth16_vk_destroy(box->k); box->k = NULL; }
-  return NULL;
-}
+static napi_value Groth16VkDestroy(napi_env env, napi_callback_info info) { return box_destroy_call(env, info, "expected a Groth16 key handle"); }
 static napi_value groth16_verify_call(napi_env env, napi_callback_info info, int async) {
   ARGS(5); NEED_CTX(); BYTES(1, ps, lp); BYTES(2, xs, lx);
-  g16_box* box = NULL;
-  if (napi_get_value_external(env, argv[0], (void**)&box) != napi_ok || !box || !box->k) { napi_throw_type_error(env, NULL, "expected a live Groth16 key handle"); return NULL; }
+  handle_box* box = NULL;
+  if (napi_get_value_external(env, argv[0], (void**)&box) != napi_ok || !box || !box->h) { napi_throw_type_error(env, NULL, "expected a live Groth16 key handle"); return NULL; }
   int32_t per; if (napi_get_value_int32(env, argv[4], &per) != napi_ok) { napi_throw_type_error(env, NULL, "expected a number for perItem"); return NULL; }
   const uint8_t* seed; if (!kzg_seed(env, argv[3], &seed)) return NULL;
-  size_t m = 0; p_nbls_groth16_vk_inputs(box->k, &m);
+  size_t m = 0; p_nbls_groth16_vk_inputs((nbls_groth16_vk*)box->h, &m);
   const size_t n = lp / 192;
   if (!n || lp != n * 192 || lx != n * m * 32) { napi_throw_range_error(env, NULL, "n proofs of 192 bytes and n rows of m inputs of 32 bytes"); return NULL; }
   thr_job job; memset(&job, 0, sizeof job);
-  job.kind = 15; job.vk = box->k; job.proofs = ps; job.b = xs; job.seed = seed; job.per_item = per != 0; job.n = n;
+  job.kind = 15; job.vk = (nbls_groth16_vk*)box->h; job.proofs = ps; job.b = xs; job.seed = seed; job.per_item = per != 0; job.n = n;
   napi_value vo = new_u8(env, 4, &job.out), vs = new_u8(env, n, (uint8_t**)&job.st); ALLOCATED(vo); ALLOCATED(vs);
   memset(job.out, 0, 4); memset(job.st, 0, n);
   if (!seed) argv[3] = argv[2];   /* (no seed array to keep alive: a second reference to the inputs in its place) */

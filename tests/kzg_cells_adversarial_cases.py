@@ -93,7 +93,7 @@ class Forge:
 
     def model(self, items, seed):
         """the combined check in integers, r_j = weight(seed, j) by position -> ([sum r cm is zero, sum r s q is zero, every S_i is zero: the three parts of B are the zero
-        point], A = sum r q is zero, B is zero, the check accepts).  B = sum r cm - sum_i S_i tau^i + sum r s q, and kzg_frame.h's rule -- A = B = O accepts, exactly one of them
+        point], A = sum r q is zero, B is zero, the check accepts).  B = sum r cm - sum_i S_i tau^i + sum r s q, and verifier_frame.h's rule -- A = B = O accepts, exactly one of them
         zero rejects, else the pairings decide tau^c A = B -- is `tau^c A = B` in the integers"""
         r = [weight(seed, j) for j in range(len(items))]
         s1 = sum(rj * t.cm for rj, t in zip(r, items)) % R

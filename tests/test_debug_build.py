@@ -99,11 +99,12 @@ def test_sanitizer_bufs():
 
 @pytest.mark.skipif(subprocess.call(['sh', '-c', 'echo "int main(){}" | g++ -x c++ -fsanitize=address,undefined -o /dev/null - 2>/dev/null']) != 0, reason='no sanitizer runtime')
 def test_sanitizer_kzg_frame():
-    """the block formats of the KZG verifiers (csrc/kzg_frame.h, tests/c/kzg_frame_test.cpp): the pairs block and the per-item tail at n = 1, 3, 257 carved into aligned,
-    disjoint parts whose totals are the formulas written out there, and the verdict of the combined check over every header and clean / unclean statuses"""
-    subprocess.check_call(['make', '-s', '-C', CSRC, '../kzg_frame_test'])
+    """the block formats of the weighted verifiers (csrc/verifier_frame.h, tests/c/verifier_frame_test.cpp): the pairs block and the per-item tail at n = 1, 3, 257 carved into
+    aligned, disjoint parts whose totals are the formulas written out there, the verdicts of the KZG and Groth16 combined checks over every header and clean / unclean statuses,
+    and the negation of a G2 point in wire bytes"""
+    subprocess.check_call(['make', '-s', '-C', CSRC, '../verifier_frame_test'])
     env = dict(os.environ, ASAN_OPTIONS='detect_leaks=0')
-    out = subprocess.run([os.path.join(ROOT, 'noble-bls12-381_amd', 'kzg_frame_test')], capture_output=True, text=True, timeout=60, env=env)
+    out = subprocess.run([os.path.join(ROOT, 'noble-bls12-381_amd', 'verifier_frame_test')], capture_output=True, text=True, timeout=60, env=env)
     assert out.returncode == 0, out.stdout + out.stderr
     assert 'failures 0' in out.stdout, out.stdout
     assert 'ERROR: AddressSanitizer' not in out.stderr and 'runtime error' not in out.stderr, out.stderr
