@@ -3,8 +3,7 @@
 // the sums and the per-proof pass.  The curve arithmetic runs as step programs (decoders, ladders, MSMs, Miller loops).  Every store is a plain C++ vector or byte store.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include "fr_exec.h"
-#include "nbls.h"   // NBLS_ST_G16_C, NBLS_ST_NOT_VERIFIED
+#include "fr_workgroup.h"   // fr_exec.h, nbls.h; the tree and the closing sum
 #include "kernel_parts.h"
 #include "launchers.h"
 
@@ -15,15 +14,6 @@ using namespace nbls;
 
 constexpr int GL = G16_LANES;
 
-// the workgroup's lanes hold one value per (row group, column): the column sums to part[0 .. G16_TILE), a tree of modular additions; every wavefront meets every barrier, and
-// a lane below G16_TILE reads its own last sum
-__device__ inline void g16_column_tree(Fr* part, u32 t, const Fr& mine) {
-  part[t] = mine;
-  for (u32 s = GL / 2; s >= G16_TILE; s >>= 1) {
-    __syncthreads();
-    if (t < s) part[t] = fr_add(part[t], part[t + s]);
-  }
-}
 // fr_exec.h has the walk.  inputs: n rows of m elements; w32: n weights; pre (may be NULL): a row with pre[i] != 0 is out; partial: one row of m + 1 plain-limb elements per
 // workgroup of rows (wgs of them); st_out (may be NULL): the rows' statuses, written by tile 0.
 // Grid: one dimension, ceil(wgs / 8) * 8 * tiles workgroups, dealt so that the `tiles` workgroups of one set of rows are 8 apart: workgroups b and b + 8 run on the same XCD,
@@ -44,18 +34,16 @@ __global__ void __launch_bounds__(GL) g16_input_sums_kernel(u32 n, u32 m, u32 wg
     g16_row_add(acc, x, w32 + 32ull * i, bad | ((u32)0 - (u32)(p != 0)));
     if (st_out && tile == 0 && lane == 0) st_out[i] = (int8_t)g16_row_status(p, bad);
   }
-  g16_column_tree(part, t, g16_reduce(acc));
+  const FrWorkgroup<GL> lanes;
+  lanes.phase([&](u32 l) { part[l] = g16_reduce(acc); });
+  fr_tree(lanes, part, G16_TILE);   // (every wavefront meets every barrier)
   const u32 c = tile * G16_TILE + t;
   if (t < G16_TILE && c <= m) partial[(u64)wg * (m + 1) + c] = part[t];
 }
 // out32[c] = the sum over the n_parts partial rows of column c as 32 bytes big-endian, c <= m: one workgroup per tile, row group g on the rows g, g + G16_GROUPS, ..
 __global__ void __launch_bounds__(GL) g16_sum_kernel(u32 m, u32 n_parts, const Fr* __restrict__ partial, uint8_t* __restrict__ out32) {
   __shared__ Fr part[GL];
-  const u32 t = threadIdx.x, c = blockIdx.x * G16_TILE + (t & (G16_TILE - 1));
-  Fr acc = fr_zero();
-  if (c <= m) for (u32 p = t / G16_TILE; p < n_parts; p += G16_GROUPS) acc = fr_add(acc, partial[(u64)p * (m + 1) + c]);
-  g16_column_tree(part, t, acc);
-  if (t < G16_TILE && c <= m) fr_store_q(part[t], out32 + 32ull * c);
+  g16_sum_body(FrWorkgroup<GL>(), m, blockIdx.x, n_parts, partial, out32, part);
 }
 
 // a proof is A || B || C (192 bytes = twelve 16-byte vectors): A to ac48[i], C to ac48[n + i] -- one array for one decoder call -- and B to b96[i]; one vector per thread

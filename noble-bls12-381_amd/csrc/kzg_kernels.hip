@@ -1,15 +1,15 @@
 // kzg_kernels.hip -- the scalar-field side of KZG verification (pipelines_kzg.cpp) and proving (pipelines_kzg_prove.cpp: the quotient of an opening, the canonical check of
 // blobs that are only committed to, the closing kernel of the compressed results): polynomials in evaluation form evaluated at a point (nbls_fr_eval_roots, and y_i = p_i(z_i) of
 // nbls_kzg_verify_blobs), the table of roots of unity, and the small Fr kernels around the two MSMs of the combined check and the ladders of the per-item pass.  The arithmetic is
-// fr_exec.h's, written once and shared with the simulator (nbls_sim_fr_eval_roots); the curve arithmetic runs as step programs (decoder, MSM, ladders, Miller loops).
+// fr_exec.h's and the workgroups' choreography fr_workgroup.h's, both written once and shared with the simulator (vm_sim.cpp); the curve arithmetic runs as step programs
+// (decoder, MSM, ladders, Miller loops).
 // Further down: the transform and the cells of EIP-7594, their recovery from half of the cells (pipelines_kzg_cells.cpp) and the interpolation of cells for their verifier
 // (pipelines_kzg_verify_cells.cpp).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <atomic>
 #include <mutex>
-#include "fr_exec.h"
-#include "nbls.h"   // NBLS_ST_NON_CANONICAL, NBLS_ST_NOT_VERIFIED
+#include "fr_workgroup.h"   // fr_exec.h, nbls.h; the workgroup bodies of the kernels below
 #include "kernel_parts.h"
 #include "launchers.h"
 
@@ -26,71 +26,29 @@ __global__ void kzg_roots_kernel(u32 log2_n, Fr* __restrict__ table) {
   if (j < (1u << log2_n)) table[j] = fr_root_entry(fr_omega(log2_n), log2_n, j);
 }
 
-// the 256 values of part[] (one per lane of the workgroup) to part[0]: an LDS tree of modular additions; ends behind a barrier
-__device__ inline void fr_part_tree(Fr* part, u32 t) {
-  for (u32 s = EV / 2; s > 0; s >>= 1) {
-    if (t < s) part[t] = fr_add(part[t], part[t + s]);
-    __syncthreads();
-  }
-}
 // One workgroup per polynomial, lane t on the terms t, t + 256, .. (ceil(N / 256) of them: the loop bounds are the workgroup's), ONE fixed-chain inversion per lane.  N < 256
 // leaves lanes idle under fr_eval_lane's mask.  Dynamic LDS: the running products of the batch inversion, 8 KB per term of a lane (128 KB at N = 4096), [term][limb][lane] so that
 // a wavefront's 64 words fall on 64 banks.  The 256 partial sums meet in an LDS tree (8 KB) of modular additions; at most one lane of the workgroup meets a vanishing denominator
-// (the roots are distinct) and leaves its index in LDS.
-// The walk both kernels open with (keep: fr_eval_lane_t's) -> z in Montgomery form; behind a barrier part[0] = the sum, *sh_hit = the root z is (or all ones), *sh_bad = an element or z >= r
-template <bool keep> __device__ inline Fr kzg_eval_walk(u32 log2_n, const uint8_t* f32, const uint8_t* z32, const Fr* roots, u32* pre, Fr* part, u32* sh_hit, u32* sh_bad) {
-  const u32 N = 1u << log2_n, t = threadIdx.x;
-  const Fr zraw = fr_load_be(z32), z = fr_mul(zraw, fr_r2());
-  if (t == 0) { *sh_hit = 0xffffffffu; *sh_bad = fr_ge_r_mask(zraw); }
-  __syncthreads();
-  const FrEvalPart me = fr_eval_lane_t<keep>(f32, roots, z, N, t, EV, pre);
-  part[t] = me.sum;
-  if (me.hit != 0xffffffffu) *sh_hit = me.hit;
-  if (me.bad) atomicOr(sh_bad, 0xffffffffu);
-  __syncthreads();
-  fr_part_tree(part, t);
-  return z;
-}
+// (the roots are distinct) and leaves its index in LDS.  The bodies: fr_workgroup.h kzg_eval_body, kzg_quotient_body
 __global__ void __launch_bounds__(EV) kzg_eval_kernel(u32 log2_n, const uint8_t* __restrict__ evals, const uint8_t* __restrict__ z32, const Fr* __restrict__ roots,
                                                       uint8_t* __restrict__ out32, int8_t* __restrict__ status) {
   extern __shared__ u32 pre[];
   __shared__ Fr part[EV];
   __shared__ u32 sh_hit, sh_bad;
   const u64 p = blockIdx.x;
-  const uint8_t* f32 = evals + ((p * 32) << log2_n);
-  const Fr z = kzg_eval_walk<false>(log2_n, f32, z32 + 32 * p, roots, pre, part, &sh_hit, &sh_bad);
-  if (threadIdx.x == 0) status[p] = (int8_t)fr_eval_finish(part[0], sh_hit, sh_bad, z, log2_n, f32, out32 + 32 * p);
+  kzg_eval_body(FrWorkgroup<EV>(), log2_n, evals + ((p * 32) << log2_n), z32 + 32 * p, roots, out32 + 32 * p, status + p, pre, part, &sh_hit, &sh_bad);
 }
-
-// The quotient of an opening (nbls_fr_quotient_roots, the proofs of pipelines_kzg_prove.cpp): kzg_eval_kernel's walk with the inverses 1 / (z - w_j) kept in the slots the
-// running products came from (no more LDS than the evaluation takes), the same tree for y, then a second walk over the lane's terms: q_j = (y - f_j) / (z - w_j) as 32 bytes
-// big-endian -- the batched MSM's scalar array -- and, where z is the root w_m (sh_hit: uniform over the workgroup), the products q_j w_j into a second tree over `part`; the
-// lane that owns m closes with one inversion, q_m = -1 / z * sum.  A non-canonical input leaves a zero y and a zero row.
+// The quotient of an opening (nbls_fr_quotient_roots, the proofs of pipelines_kzg_prove.cpp): no more LDS than the evaluation takes; q_j = (y - f_j) / (z - w_j) as 32 bytes
+// big-endian -- the batched MSM's scalar array
 __global__ void __launch_bounds__(EV) kzg_quotient_kernel(u32 log2_n, const uint8_t* __restrict__ evals, const uint8_t* __restrict__ z32, const Fr* __restrict__ roots,
                                                           uint8_t* __restrict__ out_y32, uint8_t* __restrict__ out_q32, int8_t* __restrict__ status) {
   extern __shared__ u32 pre[];
   __shared__ Fr part[EV];
   __shared__ Fr sh_y;
   __shared__ u32 sh_hit, sh_bad;
-  const u32 N = 1u << log2_n, t = threadIdx.x;
   const u64 p = blockIdx.x;
-  const uint8_t* f32 = evals + ((p * 32) << log2_n);
-  uint8_t* q32 = out_q32 + ((p * 32) << log2_n);
-  const Fr z = kzg_eval_walk<true>(log2_n, f32, z32 + 32 * p, roots, pre, part, &sh_hit, &sh_bad);
-  const u32 hit = sh_hit, bad = sh_bad;
-  if (t == 0) {
-    sh_y = fr_select(bad, fr_zero(), fr_eval_value(part[0], hit, z, log2_n, f32));
-    fr_store_be(sh_y, out_y32 + 32 * p);
-    status[p] = (int8_t)(bad & NBLS_ST_NON_CANONICAL);
-  }
-  __syncthreads();
-  const Fr y = sh_y;
-  const Fr share = fr_quot_lane(f32, roots, y, hit, bad, N, t, EV, pre, q32);
-  if (hit == 0xffffffffu) return;   // (uniform)
-  part[t] = share;
-  __syncthreads();
-  fr_part_tree(part, t);
-  if (t == hit % EV) fr_store_q(fr_select(bad, fr_zero(), fr_quot_within(part[0], z)), q32 + 32ull * hit);
+  kzg_quotient_body(FrWorkgroup<EV>(), log2_n, evals + ((p * 32) << log2_n), z32 + 32 * p, roots, out_y32 + 32 * p, out_q32 + ((p * 32) << log2_n), status + p, pre, part, &sh_y,
+                    &sh_hit, &sh_bad);
 }
 
 // ---- The transform (nbls_fr_ntt), the cells of EIP-7594 (nbls_kzg_compute_cells) and the quotient rows of their proofs (pipelines_kzg_cells.cpp); fr_exec.h has the network.
@@ -100,57 +58,17 @@ __global__ void kzg_inv_roots_kernel(u32 log2_n, const Fr* __restrict__ roots, F
   const u32 j = blockIdx.x * blockDim.x + threadIdx.x;
   if (j < (1u << log2_n)) table[j] = roots[fr_inv_root_index(log2_n, j)];
 }
-// One workgroup per polynomial, the whole polynomial in dynamic LDS (32 N bytes: 128 KB at N = 4096), one barrier per stage.  mode (FrNttMode):
-//   TO_COEFFS  values in -> the stages with the inverse roots -> times 1 / N and (1 / s)^i -> coefficients out
-//   TO_EVALS   coefficients in, times s^i -> the stages with the roots -> values out
-//   CELLS      a blob in (shift32 = g = omega_2N for every blob: shift_stride = 0) -> its bytes to the first half of the output row -> coefficients (to coef32 as well, where
-//              given) -> times g^i -> values on the coset to the second half
-// in32 / out32 / coef32 are 16-byte aligned; out_stride = the bytes of an output row.  A polynomial with an element or a shift >= r (status NBLS_ST_NON_CANONICAL), or with a
-// shift that is 0 mod r (status 5), leaves all-zero rows; the branch is the workgroup's.  One lane inverts the shift on the way to the coefficients; the others wait
+// One workgroup per polynomial, the whole polynomial in dynamic LDS (32 N bytes: 128 KB at N = 4096), one barrier per stage; fr_workgroup.h kzg_ntt_body has the modes and the
+// refusals.  shift32 = g for every blob of the cells mode: shift_stride = 0.  in32 / out32 / coef32 are 16-byte aligned; out_stride = the bytes of an output row
 __global__ void __launch_bounds__(NT) kzg_ntt_kernel(u32 log2_n, u32 mode, const uint8_t* __restrict__ in32, const uint8_t* __restrict__ shift32, u32 shift_stride,
                                                      const Fr* __restrict__ roots, const Fr* __restrict__ iroots, uint8_t* __restrict__ out32, u64 out_stride,
                                                      uint8_t* __restrict__ coef32, int8_t* __restrict__ status) {
   extern __shared__ u32 a[];
   __shared__ Fr sh_s;
   __shared__ u32 sh_bad, sh_zero;
-  const u32 N = 1u << log2_n, t = threadIdx.x;
   const u64 p = blockIdx.x;
-  const uint8_t* f32 = in32 + ((p * 32) << log2_n);
-  uint8_t* o32 = out32 + p * out_stride;
-  uint8_t* c32 = coef32 ? coef32 + ((p * 32) << log2_n) : nullptr;
-  if (t == 0) {
-    u32 bad = 0, zero = 0;
-    if (shift32) sh_s = fr_ntt_shift(shift32 + (u64)shift_stride * p, mode == FR_NTT_TO_COEFFS, &bad, &zero);
-    sh_bad = bad; sh_zero = zero;
-  }
-  __syncthreads();
-  if (fr_ntt_load(f32, N, t, NT, a)) atomicOr(&sh_bad, 0xffffffffu);
-  __syncthreads();
-  const int st = sh_bad ? NBLS_ST_NON_CANONICAL : sh_zero ? 5 : 0;
-  if (t == 0 && status) status[p] = (int8_t)st;
-  if (st) {
-    for (u64 j = t; j < out_stride / 16; j += NT) ((uint4*)o32)[j] = make_uint4(0u, 0u, 0u, 0u);
-    if (c32) for (u32 j = t; j < 2 * N; j += NT) ((uint4*)c32)[j] = make_uint4(0u, 0u, 0u, 0u);
-    return;
-  }
-  const Fr s = shift32 ? sh_s : fr_one(), ninv = fr_inv_pow2(log2_n);
-  if (mode == FR_NTT_TO_EVALS) {
-    if (shift32) fr_ntt_scale(a, N, t, NT, FR_NTT_LOG2_LANES, nullptr, &s, nullptr);
-    __syncthreads();
-  } else {
-    for (u32 ll = 0; ll < log2_n; ll++) { fr_ntt_stage(a, log2_n, ll, true, iroots, t, NT); __syncthreads(); }
-    if (mode == FR_NTT_TO_COEFFS) {   // (the lane scales and stores its own elements: no barrier between the two)
-      fr_ntt_scale(a, N, t, NT, FR_NTT_LOG2_LANES, &ninv, shift32 ? &s : nullptr, nullptr);
-      fr_ntt_store(a, N, t, NT, o32);
-      return;
-    }
-    for (u32 j = t; j < 2 * N; j += NT) ((uint4*)o32)[j] = ((const uint4*)f32)[j];
-    fr_ntt_scale(a, N, t, NT, FR_NTT_LOG2_LANES, &ninv, &s, c32);
-    __syncthreads();
-    o32 += (u64)32 << log2_n;
-  }
-  for (u32 ll = log2_n; ll-- > 0;) { fr_ntt_stage(a, log2_n, ll, false, roots, t, NT); __syncthreads(); }
-  fr_ntt_store(a, N, t, NT, o32);
+  kzg_ntt_body(FrWorkgroup<NT>(), log2_n, mode, in32 + ((p * 32) << log2_n), shift32 ? shift32 + (u64)shift_stride * p : nullptr, roots, iroots, out32 + p * out_stride, out_stride,
+               coef32 ? coef32 + ((p * 32) << log2_n) : nullptr, status ? status + p : nullptr, a, &sh_s, &sh_bad, &sh_zero);
 }
 // The quotient rows of n blobs' cell proofs, one lane per chain (fr_exec.h fr_cell_chain): lane (blob, k, j), j fastest, so that a wavefront reads and writes consecutive
 // elements.  coef32: n x N coefficients (all-zero for a refused blob: its rows come out zero); sroots: the table of the 2 N / c roots (s_k = entry k); out_q32: n x (2 N / c)
@@ -171,12 +89,7 @@ __global__ void __launch_bounds__(256) kzg_cell_rows_kernel(u32 log2_n, u32 log2
 __global__ void __launch_bounds__(FR_FK_LANES) kzg_fk20_scalars_kernel(u32 log2_n, u32 log2_cell, u32 n, const uint8_t* __restrict__ coef32, const Fr* __restrict__ sroots,
                                                                        uint8_t* __restrict__ out32) {
   extern __shared__ u32 a[];
-  const u32 lm = log2_n + 1 - log2_cell;
-  const FrFkLane L = fr_fk_lane(lm, log2_cell, n, blockIdx.x, threadIdx.x);
-  fr_fk_load(coef32, log2_n, log2_cell, lm, L, a);
-  __syncthreads();
-  for (u32 ll = lm; ll-- > 0;) { fr_fk_stage(a, lm, ll, sroots, L); __syncthreads(); }
-  fr_fk_store(a, log2_cell, lm, L, out32);
+  kzg_fk20_scalars_body(FrWorkgroup<FR_FK_LANES>(), log2_n, log2_cell, n, blockIdx.x, coef32, sroots, out32, a);
 }
 // row_st[blob * M + k] = blob_st[blob]: what the closing kernel reads per proof
 __global__ void kzg_fk20_row_status_kernel(u32 log2_m, u32 n, const int8_t* __restrict__ blob_st, int8_t* __restrict__ row_st) {
@@ -207,85 +120,25 @@ __global__ void __launch_bounds__(256) kzg_recover_z_kernel(u32 log2_m, u32 n, c
   if (pre[blob]) return;
   zv[gid] = fr_recover_z(sroots, slot + ((u64)blob << log2_m), log2_m, v, kc->c7);
 }
-// One workgroup per blob, one polynomial in dynamic LDS at a time (32 N bytes), kzg_ntt_kernel's lanes, stages and barriers; six transforms of size N:
-//   the canonical check of every given element -> E Z on H -> S (kept in the blob's row of coef32) -> E Z on gH -> D -> T 7^i -> the values on 7 H -> block j times
-//   1 / Zs(7^c s_j) -> the coefficients of P (to coef32: what the proofs read) -> the values on H, compared and written to the first half of the output row -> the
-//   coefficients again, times g^i -> the values on gH, compared and written to the second half.
-// A lane scales, combines, stores and reloads its OWN elements t, t + 512, .. only: no barrier between such steps, one behind every stage.  Status: pre[blob]
-// (NBLS_ST_BAD_CELLS), else NBLS_ST_NON_CANONICAL, else NBLS_ST_INCONSISTENT where a recomputed element differs from a given one, else 0; a refused blob leaves an all-zero row
-// and all-zero coefficients, and the branch is the workgroup's.  cells / out32 / coef32 are 16-byte aligned; coef32 is read back by the lanes that wrote it (no __restrict__)
+// One workgroup per blob, one polynomial in dynamic LDS at a time (32 N bytes), kzg_ntt_kernel's lanes, stages and barriers; fr_workgroup.h kzg_recover_body has the six
+// transforms and the statuses.  cells / out32 / coef32 are 16-byte aligned; coef32 is read back by the lanes that wrote it (no __restrict__)
 __global__ void __launch_bounds__(NT) kzg_recover_kernel(u32 log2_n, u32 log2_cell, const uint8_t* __restrict__ cells, const u32* __restrict__ slot_all,
                                                          const int8_t* __restrict__ pre, const Fr* __restrict__ zv_all, const FrRecoverConsts* __restrict__ kc,
                                                          const Fr* __restrict__ roots, const Fr* __restrict__ iroots, uint8_t* __restrict__ out32, uint8_t* coef32,
                                                          int8_t* __restrict__ status) {
   extern __shared__ u32 a[];
   __shared__ u32 sh_bad, sh_diff;
-  const u32 N = 1u << log2_n, t = threadIdx.x, log2_m = log2_n + 1 - log2_cell, M = 1u << log2_m;
+  const u32 log2_m = log2_n + 1 - log2_cell;
   const u64 p = blockIdx.x;
-  const u32* slot = slot_all + (p << log2_m);
-  const Fr* zv = zv_all + p * (3u << (log2_m - 1));
-  uint8_t* o32 = out32 + ((p * 64) << log2_n);
-  uint8_t* c32 = coef32 + ((p * 32) << log2_n);
-  if (t == 0) { sh_bad = 0; sh_diff = 0; }
-  __syncthreads();
-  int st = pre[p];
-  if (!st) {
-    const u32 bad = fr_recover_load(cells, slot, zv, log2_n, log2_cell, 0, t, NT, a) | fr_recover_load(cells, slot, zv, log2_n, log2_cell, 1, t, NT, nullptr);
-    if (bad) atomicOr(&sh_bad, 0xffffffffu);
-  }
-  __syncthreads();
-  if (!st && sh_bad) st = NBLS_ST_NON_CANONICAL;
-  if (!st) {
-    const Fr ninv = fr_inv_pow2(log2_n);
-    for (u32 ll = 0; ll < log2_n; ll++) { fr_ntt_stage(a, log2_n, ll, true, iroots, t, NT); __syncthreads(); }
-    fr_ntt_scale(a, N, t, NT, FR_NTT_LOG2_LANES, &ninv, nullptr, c32);   // S
-    fr_recover_load(cells, slot, zv, log2_n, log2_cell, 1, t, NT, a);
-    __syncthreads();
-    for (u32 ll = 0; ll < log2_n; ll++) { fr_ntt_stage(a, log2_n, ll, true, iroots, t, NT); __syncthreads(); }
-    fr_ntt_scale(a, N, t, NT, FR_NTT_LOG2_LANES, &ninv, &kc->ginv, nullptr);   // D
-    fr_recover_combine(a, c32, N, t, NT, FR_NTT_LOG2_LANES, *kc);
-    __syncthreads();
-    for (u32 ll = log2_n; ll-- > 0;) { fr_ntt_stage(a, log2_n, ll, false, roots, t, NT); __syncthreads(); }
-    fr_recover_divide(a, zv + M, N, log2_cell, t, NT);
-    __syncthreads();
-    for (u32 ll = 0; ll < log2_n; ll++) { fr_ntt_stage(a, log2_n, ll, true, iroots, t, NT); __syncthreads(); }
-    fr_ntt_scale(a, N, t, NT, FR_NTT_LOG2_LANES, &ninv, &kc->seveninv, nullptr);   // P
-    fr_ntt_store(a, N, t, NT, c32);
-    __syncthreads();
-    for (u32 ll = log2_n; ll-- > 0;) { fr_ntt_stage(a, log2_n, ll, false, roots, t, NT); __syncthreads(); }
-    u32 diff = fr_recover_compare(a, cells, slot, log2_n, log2_cell, 0, t, NT);
-    fr_ntt_store(a, N, t, NT, o32);
-    fr_ntt_load(c32, N, t, NT, a);
-    fr_ntt_scale(a, N, t, NT, FR_NTT_LOG2_LANES, nullptr, &kc->g, nullptr);
-    __syncthreads();
-    for (u32 ll = log2_n; ll-- > 0;) { fr_ntt_stage(a, log2_n, ll, false, roots, t, NT); __syncthreads(); }
-    diff |= fr_recover_compare(a, cells, slot, log2_n, log2_cell, 1, t, NT);
-    fr_ntt_store(a, N, t, NT, o32 + ((u64)32 << log2_n));
-    if (diff) atomicOr(&sh_diff, 0xffffffffu);
-    __syncthreads();
-    if (sh_diff) st = NBLS_ST_INCONSISTENT;
-  }
-  if (t == 0) status[p] = (int8_t)st;
-  if (st) {   // (behind a barrier in every case: the zeros follow the row's earlier stores)
-    for (u32 j = t; j < 4 * N; j += NT) ((uint4*)o32)[j] = make_uint4(0u, 0u, 0u, 0u);
-    for (u32 j = t; j < 2 * N; j += NT) ((uint4*)c32)[j] = make_uint4(0u, 0u, 0u, 0u);
-  }
+  kzg_recover_body(FrWorkgroup<NT>(), log2_n, log2_cell, cells, slot_all + (p << log2_m), pre[p], zv_all + p * (3u << (log2_m - 1)), *kc, roots, iroots,
+                   out32 + ((p * 64) << log2_n), coef32 + ((p * 32) << log2_n), status + p, a, &sh_bad, &sh_diff);
 }
 
 // blobs that are only committed to (no quotient kernel reads them): status[i] = NBLS_ST_NON_CANONICAL where an element of blob i is >= r, and that blob's row is zeroed in
 // place, so that the MSM reads canonical scalars only.  One workgroup per blob
 __global__ void __launch_bounds__(256) kzg_canon_kernel(u32 log2_n, uint8_t* __restrict__ evals, int8_t* __restrict__ status) {
   __shared__ u32 sh_bad;
-  const u32 N = 1u << log2_n, t = threadIdx.x;
-  uint8_t* f32 = evals + (((u64)blockIdx.x * 32) << log2_n);
-  if (t == 0) sh_bad = 0;
-  __syncthreads();
-  u32 bad = 0;
-  for (u32 j = t; j < N; j += 256) bad |= fr_ge_r_mask(fr_load_be(f32 + 32ull * j));
-  if (bad) atomicOr(&sh_bad, 0xffffffffu);
-  __syncthreads();
-  if (t == 0) status[blockIdx.x] = (int8_t)(sh_bad & NBLS_ST_NON_CANONICAL);
-  if (sh_bad) for (u32 j = t; j < 2 * N; j += 256) ((uint4*)f32)[j] = make_uint4(0u, 0u, 0u, 0u);
+  kzg_canon_body(FrWorkgroup<256>(), log2_n, evals + (((u64)blockIdx.x * 32) << log2_n), status + blockIdx.x, &sh_bad);
 }
 // the n compressed sums of a prover call, in place: status[i] = the first non-zero of st_a[i], st_b[i] (either array may be NULL); all-zero bytes where it is set, 0xc0 00..
 // where the sum is the zero point (zero[i] == 1)
@@ -334,12 +187,7 @@ __global__ void kzg_items_kernel(u32 n, const int8_t* __restrict__ dst, const ui
 // out32 = -(sum_i t[i]) mod r as 32 bytes big-endian: one workgroup, the lanes striding over the items, an LDS tree of modular additions
 __global__ void __launch_bounds__(EV) kzg_sum_kernel(u32 n, const Fr* __restrict__ t, uint8_t* __restrict__ out32) {
   __shared__ Fr part[EV];
-  Fr acc = fr_zero();
-  for (u32 i = threadIdx.x; i < n; i += EV) acc = fr_add(acc, t[i]);
-  part[threadIdx.x] = acc;
-  __syncthreads();
-  fr_part_tree(part, threadIdx.x);
-  if (threadIdx.x == 0) fr_store_be(fr_neg(part[0]), out32);
+  kzg_sum_body(FrWorkgroup<EV>(), n, t, out32, part);
 }
 // the per-item pass: zs[i] = z_i (zero where the item is out or its proof is the zero point), ny[i] = -y_i mod r (zero where the item is out)
 __global__ void kzg_item_scalars_kernel(u32 n, const int8_t* __restrict__ pre, const int8_t* __restrict__ dst, const uint8_t* __restrict__ z32, const uint8_t* __restrict__ y32,
@@ -376,14 +224,6 @@ __device__ inline Fr fr_lane_xor(const Fr& v, u32 mask) {
   for (int l = 0; l < FR_NL; l++) o.l[l] = (u32)__shfl_xor((int)v.l[l], (int)mask);
   return o;
 }
-// the workgroup's lanes hold one value per (lane group, column): the column sums to part[0 .. c), a tree of modular additions; every wavefront meets every barrier
-__device__ inline void cell_column_tree(Fr* part, u32 t, u32 c, const Fr& mine) {
-  part[t] = mine;
-  for (u32 s = CL / 2; s >= c && s > 0; s >>= 1) {
-    __syncthreads();
-    if (t < s) part[t] = fr_add(part[t], part[t + s]);
-  }
-}
 // The interpolation polynomials of n_cells cells of c = 2^log2_cell <= 64 elements each, c lanes per cell (fr_exec.h fr_cell_*): a wavefront holds 64 / c cells side by side, a
 // workgroup four wavefronts.  Lane group q of the launch takes the cells q, q + groups, .. -- the same number of rounds on every lane, a round past the end on the last cell
 // with nothing kept -- and in every round: the elements in (32 bytes big-endian, 16-byte aligned), the canonical check over the group, the log2_cell stages towards the
@@ -417,17 +257,15 @@ __global__ void __launch_bounds__(CL) kzg_cell_interp_kernel(u32 log2_cell, u32 
     if (st_out && valid && i == 0) st_out[kk] = (int8_t)fr_cell_status(p, bad);
   }
   if (!sum) return;   // (uniform)
-  cell_column_tree(part, t, c, acc);
-  if (t < c) partial[(u64)blockIdx.x * c + t] = part[t];   // (the lane's own last sum)
+  const FrWorkgroup<CL> lanes;
+  lanes.phase([&](u32 l) { part[l] = acc; });
+  fr_tree(lanes, part, c);   // (every wavefront meets every barrier)
+  if (t < c) partial[(u64)blockIdx.x * c + t] = part[t];
 }
 // out32[i] = -(sum over the n_parts partial rows of column i) mod r as 32 bytes big-endian, i < c: one workgroup, lane group g on the rows g, g + groups, ..
 __global__ void __launch_bounds__(CL) kzg_cell_sum_kernel(u32 log2_cell, u32 n_parts, const Fr* __restrict__ partial, uint8_t* __restrict__ out32) {
   __shared__ Fr part[CL];
-  const u32 t = threadIdx.x, c = 1u << log2_cell, i = t & (c - 1);
-  Fr acc = fr_zero();
-  for (u32 p = t >> log2_cell; p < n_parts; p += CL >> log2_cell) acc = fr_add(acc, partial[(u64)p * c + i]);
-  cell_column_tree(part, t, c, acc);
-  if (t < c) fr_store_q(fr_neg(part[t]), out32 + 32ull * t);
+  kzg_cell_sum_body(FrWorkgroup<CL>(), log2_cell, n_parts, partial, out32, part);
 }
 // pre0[k]: what the two decoders say about cell k before its elements are looked at -- the named commitment's status if >= 2, else 10 + the proof's if >= 2, else 0
 __global__ void kzg_cell_pre_kernel(u32 n, const int8_t* __restrict__ dstc, const int8_t* __restrict__ dstp, const u32* __restrict__ ci, int8_t* __restrict__ pre0) {

@@ -12,7 +12,7 @@
 #include "pow_exec.h"
 #include "pow_wide.h"
 #include "rlc_weights.h"
-#include "fr_exec.h"
+#include "fr_workgroup.h"
 #include "wide_exec.h"
 #include "g1_wide.h"
 #include "fp_inv_wide.h"
@@ -288,6 +288,39 @@ static void sim_g1_wide_combine(const u32* S, int nwin, int shift, u32* out) {
   }
 }
 static int g_sim_wide = 0;
+// fr_workgroup.h on the host
+static bool g_lanes_down = false;
+template <uint32_t LANES> static FrWorkgroup<LANES> sim_wg() { return FrWorkgroup<LANES>{g_lanes_down}; }
+// the table of roots as kzg_roots_kernel builds it, and kzg_inv_roots_kernel's permutation of it
+static std::vector<Fr> sim_roots(unsigned log2_n) {
+  std::vector<Fr> t((size_t)1 << log2_n);
+  const Fr omega = fr_omega(log2_n);
+  for (u32 j = 0; j < t.size(); j++) t[j] = fr_root_entry(omega, log2_n, j);
+  return t;
+}
+static std::vector<Fr> sim_inv_roots(unsigned log2_n, const std::vector<Fr>& roots) {
+  std::vector<Fr> t(roots.size());
+  for (u32 j = 0; j < t.size(); j++) t[j] = roots[fr_inv_root_index(log2_n, j)];
+  return t;
+}
+// n polynomials through kzg_ntt_kernel's body, one workgroup each (the arrays as nbls_kzg_ntt_launch takes them)
+static void sim_ntt(unsigned log2_n, unsigned mode, size_t n, const uint8_t* in32, const uint8_t* shift32, size_t shift_stride, uint8_t* out32, uint8_t* coef32, int8_t* status) {
+  const std::vector<Fr> roots = sim_roots(log2_n), iroots = sim_inv_roots(log2_n, roots);
+  const size_t row = (size_t)32 << log2_n, out_stride = mode == FR_NTT_CELLS ? 2 * row : row;
+  std::vector<u32> a(row / 4);
+  Fr s = fr_one(); u32 bad = 0, zero = 0;
+  for (size_t p = 0; p < n; p++)
+    kzg_ntt_body(sim_wg<FR_NTT_LANES>(), log2_n, mode, in32 + row * p, shift32 ? shift32 + shift_stride * p : nullptr, roots.data(), iroots.data(), out32 + out_stride * p, out_stride,
+                 coef32 ? coef32 + row * p : nullptr, status ? status + p : nullptr, a.data(), &s, &bad, &zero);
+}
+// slot placement of a program's translated form (aot_layout.h): out = {has a valid table row, LDS read cycles per wavefront as compiled, with the placement, without any conflict}
+static int sim_layout_info(const Program& p, unsigned long* out4) {
+  const AotLayout* l = aot_layout_for(p);
+  const AotLdsCost c0 = aot_layout_cost(p, AotLayout());
+  const AotLdsCost c1 = l ? aot_layout_cost(p, *l) : c0;
+  out4[0] = l ? 1 : 0; out4[1] = c0.cycles; out4[2] = c1.cycles; out4[3] = c0.floor;
+  return 0;
+}
 extern "C" {
 // the one-limb-per-lane form for the programs it implements (others run as usual): 0 off, 1 on; nbls_sim_wide_violations: device assumptions violated since the last call (0 on a correct build)
 __attribute__((visibility("default"))) void nbls_sim_set_wide(int on) { g_sim_wide = on; }
@@ -349,12 +382,7 @@ __attribute__((visibility("default"))) int nbls_sim_lines_fe_enabled(void) { ret
 // nbls_sim_layout_info for one of these
 __attribute__((visibility("default"))) int nbls_sim_extra_layout_info_named(const char* name, unsigned long* out4) {
   const int xp = sim_extra_by_name(name); if (xp < 0) return -1;
-  const Program& p = get_extra_program((ExtraProg)xp);
-  const AotLayout* l = aot_layout_for(p);
-  const AotLdsCost c0 = aot_layout_cost(p, AotLayout());
-  const AotLdsCost c1 = l ? aot_layout_cost(p, *l) : c0;
-  out4[0] = l ? 1 : 0; out4[1] = c0.cycles; out4[2] = c1.cycles; out4[3] = c0.floor;
-  return 0;
+  return sim_layout_info(get_extra_program((ExtraProg)xp), out4);
 }
 // out = in^-1 on raw elements (16 words each): the same fp_mont_inverse routine the inversion kernel runs per lane
 // the same inverse with one limb per lane (fp_inv_wide.h), one element after the other
@@ -424,15 +452,18 @@ struct Fp2Host {
   void tab_put(int j, const V& a) { tab[j] = a; }
   void tab_get(V& r, unsigned j) { r = tab[j]; }
 };
+// the op list of exponent `which` as the pow kernels walk it: the Fp2 exponents through their shared part ((p - 3) / 4 - 2) / 4 (pow_exec.h fp2_pow_seq has the split)
+static std::vector<unsigned char> sim_pow_ops(int which) {
+  if (which == 0) return pow_make_ops(NBLS_EXP_P_PLUS_1_DIV_4, NBLS_P_PLUS_1_DIV_4_BITS);
+  if (which != 1 && which != 2) return pow_make_ops(NBLS_EXP_P_MINUS_3_DIV_4, NBLS_P_MINUS_3_DIV_4_BITS);
+  uint64_t K[6]; for (int j = 0; j < 6; j++) K[j] = NBLS_EXP_P_MINUS_3_DIV_4[j];
+  K[0] -= 2;
+  for (int j = 0; j < 6; j++) K[j] = (K[j] >> 2) | (j < 5 ? K[j + 1] << 62 : 0);
+  return pow_make_ops(K, 377);
+}
 // out = in^e through the kernels' chains; which: 0 = (p+1)/4 on Fp, 1 = (p^2+7)/16 on Fp2, 2 = (p^2-9)/16 on Fp2, 3 = (p-3)/4 on Fp (raw elements of 16 words)
 __attribute__((visibility("default"))) void nbls_sim_fp_pow(unsigned n, const u32* in, u32* out, int which) {
-  std::vector<unsigned char> ops;
-  if (which == 1 || which == 2) {
-    uint64_t K[6]; for (int j = 0; j < 6; j++) K[j] = NBLS_EXP_P_MINUS_3_DIV_4[j];
-    K[0] -= 2;
-    for (int j = 0; j < 6; j++) K[j] = (K[j] >> 2) | (j < 5 ? K[j + 1] << 62 : 0);
-    ops = pow_make_ops(K, 377);
-  } else ops = which == 0 ? pow_make_ops(NBLS_EXP_P_PLUS_1_DIV_4, NBLS_P_PLUS_1_DIV_4_BITS) : pow_make_ops(NBLS_EXP_P_MINUS_3_DIV_4, NBLS_P_MINUS_3_DIV_4_BITS);
+  const std::vector<unsigned char> ops = sim_pow_ops(which);
   const int nops = (int)(ops.size() / 2);
   for (unsigned k = 0; k < n; k++) {
     if (which == 0 || which == 3) { FpHost o; o.in = in + 16 * k; o.out = out + 16 * k; fp_pow_seq(o, ops.data(), nops); }
@@ -441,13 +472,7 @@ __attribute__((visibility("default"))) void nbls_sim_fp_pow(unsigned n, const u3
 }
 // out = in^e through the one-limb-per-lane chains (which as nbls_sim_fp_pow); returns the number of violated device assumptions (0 on a correct build)
 __attribute__((visibility("default"))) unsigned long nbls_sim_fp_pow_wide(unsigned n, const u32* in, u32* out, int which) {
-  std::vector<unsigned char> ops;
-  if (which == 1 || which == 2) {
-    uint64_t K[6]; for (int j = 0; j < 6; j++) K[j] = NBLS_EXP_P_MINUS_3_DIV_4[j];
-    K[0] -= 2;
-    for (int j = 0; j < 6; j++) K[j] = (K[j] >> 2) | (j < 5 ? K[j + 1] << 62 : 0);
-    ops = pow_make_ops(K, 377);
-  } else ops = which == 0 ? pow_make_ops(NBLS_EXP_P_PLUS_1_DIV_4, NBLS_P_PLUS_1_DIV_4_BITS) : pow_make_ops(NBLS_EXP_P_MINUS_3_DIV_4, NBLS_P_MINUS_3_DIV_4_BITS);
+  const std::vector<unsigned char> ops = sim_pow_ops(which);
   const int nops = (int)(ops.size() / 2);
   const WideConsts consts = wide_consts();
   g_wide_violations = 0;
@@ -459,13 +484,7 @@ __attribute__((visibility("default"))) unsigned long nbls_sim_fp_pow_wide(unsign
 }
 // op list statistics of an exponent (tests): squarings, multiplications
 __attribute__((visibility("default"))) void nbls_sim_pow_ops(int which, unsigned* out2) {
-  std::vector<unsigned char> ops;
-  if (which == 1 || which == 2) {
-    uint64_t K[6]; for (int j = 0; j < 6; j++) K[j] = NBLS_EXP_P_MINUS_3_DIV_4[j];
-    K[0] -= 2;
-    for (int j = 0; j < 6; j++) K[j] = (K[j] >> 2) | (j < 5 ? K[j + 1] << 62 : 0);
-    ops = pow_make_ops(K, 377);
-  } else ops = which == 0 ? pow_make_ops(NBLS_EXP_P_PLUS_1_DIV_4, NBLS_P_PLUS_1_DIV_4_BITS) : pow_make_ops(NBLS_EXP_P_MINUS_3_DIV_4, NBLS_P_MINUS_3_DIV_4_BITS);
+  const std::vector<unsigned char> ops = sim_pow_ops(which);
   out2[0] = out2[1] = 0;
   for (size_t k = 0; k < ops.size() / 2; k++) { out2[0] += ops[2 * k]; if (k && ops[2 * k + 1] != 0xff) out2[1]++; }
 }
@@ -491,15 +510,10 @@ __attribute__((visibility("default"))) int nbls_sim_verify_damaged(int prog, uns
   if (msg && cap) snprintf(msg, cap, "%s", e.c_str());
   return e.empty() ? 0 : 1;
 }
-// slot placement of a program's translated form (aot_layout.h): out = {has a valid table row, LDS read cycles per wavefront as compiled, with the placement, without any conflict}
+// sim_layout_info of a numbered program
 __attribute__((visibility("default"))) int nbls_sim_layout_info(int prog, unsigned long* out4) {
   if (prog < 0 || prog >= P_COUNT) return -1;
-  const Program& p = get_program((ProgId)prog);
-  const AotLayout* l = aot_layout_for(p);
-  const AotLdsCost c0 = aot_layout_cost(p, AotLayout());
-  const AotLdsCost c1 = l ? aot_layout_cost(p, *l) : c0;
-  out4[0] = l ? 1 : 0; out4[1] = c0.cycles; out4[2] = c1.cycles; out4[3] = c0.floor;
-  return 0;
+  return sim_layout_info(get_program((ProgId)prog), out4);
 }
 // the scalar side of the endomorphism splits as the device runs it (scalar_split.h): dims = 2 / 4: base-|z| digits; dims = 0: the sign-aligned recoding (4 x 32 bytes per scalar)
 // the weights of nbls_verify_multiple as rlc_kernels.hip derives them (rlc_weights.h): r_i for the set index i, 32 bytes big-endian
@@ -548,128 +562,61 @@ __attribute__((visibility("default"))) void nbls_sim_fr_lagrange(unsigned n, uns
   for (unsigned k = 0; k < n; k++) fr_store_be(fr_select((u32)0 - (u32)(bad_group[group_of[k]] != 0), fr_zero(), fr_from_mont(lambda[k])), out32 + 32ull * k);
   for (unsigned j = 0; j < ngroups; j++) status[j] = bad_group[j] ? 20 : 0;
 }
-// nbls_fr_eval_roots as kzg_kernels.hip runs it: the table of roots (kzg_roots_kernel), then per polynomial the FR_EVAL_LANES lanes of kzg_eval_kernel with the same terms per
-// lane, the tree of additions in the workgroup's order, and the closing step.  Returns -1 (NBLS_EINVAL) under the rules of the device call that need no context
-static void sim_eval_poly(unsigned log2_n, const uint8_t* f32, const uint8_t* z32, const Fr* roots, uint8_t* out32, int8_t* status) {
-  const u32 N = 1u << log2_n, W = FR_EVAL_LANES;
-  const Fr zraw = fr_load_be(z32), z = fr_mul(zraw, fr_r2());
-  std::vector<Fr> part(W);
-  std::vector<u32> pre((size_t)((N + W - 1) / W) * FR_NL * W);
-  u32 hit = 0xffffffffu, bad = fr_ge_r_mask(zraw);
-  for (u32 l = 0; l < W; l++) {
-    const FrEvalPart p = fr_eval_lane(f32, roots, z, N, l, W, pre.data());
-    part[l] = p.sum; bad |= p.bad;
-    if (p.hit != 0xffffffffu) hit = p.hit;
-  }
-  for (u32 s = W / 2; s > 0; s >>= 1) for (u32 l = 0; l < s; l++) part[l] = fr_add(part[l], part[l + s]);
-  const int st = fr_eval_finish(part[0], hit, bad, z, log2_n, f32, out32);
-  if (status) *status = (int8_t)st;
-}
+// ---- The workgroup kernels of kzg_kernels.hip and groth16_kernels.hip: their bodies are fr_workgroup.h's, the text the device compiles, on the host's workgroup view -- a
+// phase is every lane of the workgroup in turn, from lane 0 up or (nbls_sim_set_lane_order) from the top down.  An entry point is the argument rules of the device call that
+// need no context (-1 = NBLS_EINVAL), the tables, the kernel's shared memory as arrays of exactly its size, a loop over the workgroups and the body's call.
+__attribute__((visibility("default"))) void nbls_sim_set_lane_order(int descending) { g_lanes_down = descending != 0; }
 __attribute__((visibility("default"))) int nbls_sim_fr_eval_roots(unsigned log2_n, size_t n, const uint8_t* evals32, const uint8_t* z32, uint8_t* out32, int8_t* status) {
   if (log2_n < 1 || log2_n > 12 || (n && (!evals32 || !z32 || !out32)) || (n << log2_n) > ((size_t)1 << 24)) return -1;
-  const u32 N = 1u << log2_n;
-  std::vector<Fr> roots(N);
-  const Fr omega = fr_omega(log2_n);
-  for (u32 j = 0; j < N; j++) roots[j] = fr_root_entry(omega, log2_n, j);
-  for (size_t p = 0; p < n; p++) sim_eval_poly(log2_n, evals32 + 32ull * N * p, z32 + 32ull * p, roots.data(), out32 + 32ull * p, status ? status + p : nullptr);
-  return 0;
-}
-// nbls_fr_quotient_roots as kzg_quotient_kernel runs it: the lanes of the evaluation with the inverses kept, the tree, y, then the second walk of every lane, the second tree
-// where z is a root, and the closing inversion
-static void sim_quotient_poly(unsigned log2_n, const uint8_t* f32, const uint8_t* z32, const Fr* roots, uint8_t* y32, uint8_t* q32, int8_t* status) {
   const u32 N = 1u << log2_n, W = FR_EVAL_LANES;
-  const Fr zraw = fr_load_be(z32), z = fr_mul(zraw, fr_r2());
+  const std::vector<Fr> roots = sim_roots(log2_n);
   std::vector<Fr> part(W);
   std::vector<u32> pre((size_t)((N + W - 1) / W) * FR_NL * W);
-  u32 hit = 0xffffffffu, bad = fr_ge_r_mask(zraw);
-  for (u32 l = 0; l < W; l++) {
-    const FrEvalPart p = fr_eval_lane_t<true>(f32, roots, z, N, l, W, pre.data());
-    part[l] = p.sum; bad |= p.bad;
-    if (p.hit != 0xffffffffu) hit = p.hit;
-  }
-  for (u32 s = W / 2; s > 0; s >>= 1) for (u32 l = 0; l < s; l++) part[l] = fr_add(part[l], part[l + s]);
-  const Fr y = fr_select(bad, fr_zero(), fr_eval_value(part[0], hit, z, log2_n, f32));
-  fr_store_be(y, y32);
-  if (status) *status = (int8_t)(bad & 21);
-  for (u32 l = 0; l < W; l++) part[l] = fr_quot_lane(f32, roots, y, hit, bad, N, l, W, pre.data(), q32);
-  if (hit == 0xffffffffu) return;
-  for (u32 s = W / 2; s > 0; s >>= 1) for (u32 l = 0; l < s; l++) part[l] = fr_add(part[l], part[l + s]);
-  fr_store_q(fr_select(bad, fr_zero(), fr_quot_within(part[0], z)), q32 + 32ull * hit);
+  u32 hit = 0, bad = 0; int8_t st;
+  for (size_t p = 0; p < n; p++)
+    kzg_eval_body(sim_wg<FR_EVAL_LANES>(), log2_n, evals32 + 32ull * N * p, z32 + 32ull * p, roots.data(), out32 + 32ull * p, status ? status + p : &st, pre.data(), part.data(), &hit, &bad);
+  return 0;
 }
 __attribute__((visibility("default"))) int nbls_sim_fr_quotient_roots(unsigned log2_n, size_t n, const uint8_t* evals32, const uint8_t* z32, uint8_t* out_y32, uint8_t* out_q32,
                                                                       int8_t* status) {
   if (log2_n < 1 || log2_n > 12 || (n && (!evals32 || !z32 || !out_y32 || !out_q32)) || (n << log2_n) > ((size_t)1 << 24)) return -1;
-  const u32 N = 1u << log2_n;
-  std::vector<Fr> roots(N);
-  const Fr omega = fr_omega(log2_n);
-  for (u32 j = 0; j < N; j++) roots[j] = fr_root_entry(omega, log2_n, j);
+  const u32 N = 1u << log2_n, W = FR_EVAL_LANES;
+  const std::vector<Fr> roots = sim_roots(log2_n);
+  std::vector<Fr> part(W);
+  std::vector<u32> pre((size_t)((N + W - 1) / W) * FR_NL * W);
+  Fr y = fr_zero(); u32 hit = 0, bad = 0; int8_t st;
   for (size_t p = 0; p < n; p++)
-    sim_quotient_poly(log2_n, evals32 + 32ull * N * p, z32 + 32ull * p, roots.data(), out_y32 + 32ull * p, out_q32 + 32ull * N * p, status ? status + p : nullptr);
+    kzg_quotient_body(sim_wg<FR_EVAL_LANES>(), log2_n, evals32 + 32ull * N * p, z32 + 32ull * p, roots.data(), out_y32 + 32ull * p, out_q32 + 32ull * N * p, status ? status + p : &st,
+                      pre.data(), part.data(), &y, &hit, &bad);
   return 0;
 }
-// One polynomial as kzg_ntt_kernel runs it: FR_NTT_LANES lanes, every phase between two barriers lane after lane, the same butterflies per lane and stage.  `a` has exactly
-// the kernel's dynamic LDS; out32 / coef32 exactly the rows the workgroup writes.  mode: FrNttMode (cells: shift32 = g, out32 = the 2 N elements of the blob's cells)
-static int sim_ntt_poly(unsigned log2_n, unsigned mode, const uint8_t* f32, const uint8_t* shift32, const Fr* roots, const Fr* iroots, uint8_t* out32, uint8_t* coef32) {
-  const u32 N = 1u << log2_n, W = FR_NTT_LANES;
-  std::vector<u32> a((size_t)FR_NL * N);
-  u32 bad = 0, zero = 0;
-  Fr s = fr_one();
-  if (shift32) s = fr_ntt_shift(shift32, mode == FR_NTT_TO_COEFFS, &bad, &zero);
-  for (u32 l = 0; l < W; l++) bad |= fr_ntt_load(f32, N, l, W, a.data());
-  const int st = bad ? 21 : zero ? 5 : 0;
-  if (st) {
-    memset(out32, 0, (size_t)(mode == FR_NTT_CELLS ? 64 : 32) << log2_n);
-    if (coef32) memset(coef32, 0, (size_t)32 << log2_n);
-    return st;
-  }
-  const Fr ninv = fr_inv_pow2(log2_n);
-  if (mode == FR_NTT_TO_EVALS) {
-    if (shift32) for (u32 l = 0; l < W; l++) fr_ntt_scale(a.data(), N, l, W, FR_NTT_LOG2_LANES, nullptr, &s, nullptr);
-  } else {
-    for (u32 ll = 0; ll < log2_n; ll++) for (u32 l = 0; l < W; l++) fr_ntt_stage(a.data(), log2_n, ll, true, iroots, l, W);
-    if (mode == FR_NTT_TO_COEFFS) {
-      for (u32 l = 0; l < W; l++) { fr_ntt_scale(a.data(), N, l, W, FR_NTT_LOG2_LANES, &ninv, shift32 ? &s : nullptr, nullptr); fr_ntt_store(a.data(), N, l, W, out32); }
-      return 0;
-    }
-    memcpy(out32, f32, (size_t)32 << log2_n);
-    for (u32 l = 0; l < W; l++) fr_ntt_scale(a.data(), N, l, W, FR_NTT_LOG2_LANES, &ninv, &s, coef32);
-    out32 += (size_t)32 << log2_n;
-  }
-  for (u32 ll = log2_n; ll-- > 0;) for (u32 l = 0; l < W; l++) fr_ntt_stage(a.data(), log2_n, ll, false, roots, l, W);
-  for (u32 l = 0; l < W; l++) fr_ntt_store(a.data(), N, l, W, out32);
-  return 0;
-}
-static void sim_ntt_tables(unsigned log2_n, std::vector<Fr>& roots, std::vector<Fr>& iroots) {
-  const u32 N = 1u << log2_n;
-  roots.resize(N); iroots.resize(N);
-  const Fr omega = fr_omega(log2_n);
-  for (u32 j = 0; j < N; j++) roots[j] = fr_root_entry(omega, log2_n, j);
-  for (u32 j = 0; j < N; j++) iroots[j] = roots[fr_inv_root_index(log2_n, j)];
-}
-// nbls_fr_ntt as kzg_kernels.hip runs it.  Returns -1 (NBLS_EINVAL) under the rules of the device call that need no context
+// nbls_fr_ntt (dir 0: to coefficients, 1: to values; a shift per polynomial or none)
 __attribute__((visibility("default"))) int nbls_sim_fr_ntt(unsigned log2_n, int dir, size_t n, const uint8_t* in32, const uint8_t* shift32, uint8_t* out32, int8_t* status) {
   if (log2_n < 1 || log2_n > 12 || (dir != 0 && dir != 1) || (n && (!in32 || !out32)) || (n << log2_n) > ((size_t)1 << 24)) return -1;
-  std::vector<Fr> roots, iroots;
-  sim_ntt_tables(log2_n, roots, iroots);
-  for (size_t p = 0; p < n; p++) {
-    const int st = sim_ntt_poly(log2_n, dir == 0 ? FR_NTT_TO_COEFFS : FR_NTT_TO_EVALS, in32 + ((32 * p) << log2_n), shift32 ? shift32 + 32 * p : nullptr, roots.data(), iroots.data(),
-                                out32 + ((32 * p) << log2_n), nullptr);
-    if (status) status[p] = (int8_t)st;
-  }
+  sim_ntt(log2_n, dir == 0 ? FR_NTT_TO_COEFFS : FR_NTT_TO_EVALS, n, in32, shift32, 32, out32, nullptr, status);
   return 0;
 }
-// nbls_kzg_compute_cells as the kernel's cells mode runs it; coef32 (may be NULL): the n x N coefficients the proofs read
+// nbls_kzg_compute_cells: the cells mode with the shift g for every blob; coef32 (may be NULL): the n x N coefficients the proofs read
 __attribute__((visibility("default"))) int nbls_sim_kzg_cells(unsigned log2_n, size_t n, const uint8_t* blobs, uint8_t* out_cells, uint8_t* coef32, int8_t* status) {
   if (log2_n < 1 || log2_n > 12 || (n && (!blobs || !out_cells)) || (n << log2_n) > ((size_t)1 << 24)) return -1;
-  std::vector<Fr> roots, iroots;
-  sim_ntt_tables(log2_n, roots, iroots);
   uint8_t g32[32];
   fr_to_bytes(fr_omega(log2_n + 1), g32);
-  for (size_t p = 0; p < n; p++) {
-    const int st = sim_ntt_poly(log2_n, FR_NTT_CELLS, blobs + ((32 * p) << log2_n), g32, roots.data(), iroots.data(), out_cells + ((64 * p) << log2_n),
-                                coef32 ? coef32 + ((32 * p) << log2_n) : nullptr);
-    if (status) status[p] = (int8_t)st;
-  }
+  sim_ntt(log2_n, FR_NTT_CELLS, n, blobs, g32, 0, out_cells, coef32, status);
+  return 0;
+}
+// kzg_canon_kernel: evals32 = n blobs, zeroed in place where an element is >= r; status: n bytes
+__attribute__((visibility("default"))) int nbls_sim_kzg_canon(unsigned log2_n, size_t n, uint8_t* evals32, int8_t* status) {
+  if (log2_n < 1 || log2_n > 12 || (n && (!evals32 || !status))) return -1;
+  u32 bad = 0;
+  for (size_t p = 0; p < n; p++) kzg_canon_body(sim_wg<256>(), log2_n, evals32 + ((32 * p) << log2_n), status + p, &bad);
+  return 0;
+}
+// kzg_sum_kernel: out32 = -(the sum of the n elements of v32, 32 bytes big-endian each) mod r
+__attribute__((visibility("default"))) int nbls_sim_kzg_sum(size_t n, const uint8_t* v32, uint8_t* out32) {
+  if ((n && !v32) || !out32 || n > ((size_t)1 << 24)) return -1;
+  std::vector<Fr> v(n), part(FR_EVAL_LANES);
+  for (size_t i = 0; i < n; i++) v[i] = fr_load_be(v32 + 32 * i);
+  kzg_sum_body(sim_wg<FR_EVAL_LANES>(), (u32)n, v.data(), out32, part.data());
   return 0;
 }
 // the quotient rows of n blobs' cell proofs as kzg_cell_rows_kernel writes them: lane (blob, k, j) walks chain j of row k.  coef32: n x N coefficients; out_q32: n x
@@ -677,9 +624,7 @@ __attribute__((visibility("default"))) int nbls_sim_kzg_cells(unsigned log2_n, s
 __attribute__((visibility("default"))) int nbls_sim_kzg_cell_rows(unsigned log2_n, unsigned log2_cell, size_t n, const uint8_t* coef32, uint8_t* out_q32) {
   if (log2_n < 1 || log2_n > 12 || log2_cell > log2_n || log2_n + 1 - log2_cell > 12 || (n && (!coef32 || !out_q32))) return -1;
   const unsigned lm = log2_n + 1 - log2_cell;
-  std::vector<Fr> sroots((size_t)1 << lm);
-  const Fr omega = fr_omega(lm);
-  for (u32 k = 0; k < (1u << lm); k++) sroots[k] = fr_root_entry(omega, lm, k);
+  const std::vector<Fr> sroots = sim_roots(lm);
   for (uint64_t gid = 0; gid < ((uint64_t)n << (log2_n + 1)); gid++) {
     const u32 blob = (u32)(gid >> (log2_n + 1)), within = (u32)gid & ((2u << log2_n) - 1), k = within >> log2_cell, j = within & ((1u << log2_cell) - 1);
     const uint64_t row = ((uint64_t)blob << lm) + k;
@@ -687,34 +632,25 @@ __attribute__((visibility("default"))) int nbls_sim_kzg_cell_rows(unsigned log2_
   }
   return 0;
 }
-// The per-blob scalars of the FK20 cell proofs as kzg_fk20_scalars_kernel writes them: workgroups of FR_FK_LANES lanes, every phase (the load, each stage, the store) on all
-// lanes of a workgroup before the next.  coef32: n x N coefficients; out32: n x M x c scalars, [blob][i][j].  -1 where the launcher refuses the sizes
+// The per-blob scalars of the FK20 cell proofs (kzg_fk20_scalars_kernel).  coef32: n x N coefficients; out32: n x M x c scalars, [blob][i][j]
 __attribute__((visibility("default"))) int nbls_sim_kzg_fk20_scalars(unsigned log2_n, unsigned log2_cell, size_t n, const uint8_t* coef32, uint8_t* out32) {
   if (log2_n < 1 || log2_n > 12 || log2_cell > log2_n || log2_n + 1 - log2_cell > 11 || (n && (!coef32 || !out32)) || (n << log2_n) > ((size_t)1 << 24)) return -1;
   const unsigned lm = log2_n + 1 - log2_cell;
-  std::vector<Fr> sroots((size_t)1 << lm);
-  const Fr omega = fr_omega(lm);
-  for (u32 k = 0; k < (1u << lm); k++) sroots[k] = fr_root_entry(omega, lm, k);
+  const std::vector<Fr> sroots = sim_roots(lm);
   std::vector<u32> a(fr_fk_lds_words(lm));
-  const u32 wgs = fr_fk_workgroups(lm, log2_cell, (u32)n), W = FR_FK_LANES;
-  for (u32 wg = 0; wg < wgs; wg++) {
-    for (u32 t = 0; t < W; t++) fr_fk_load(coef32, log2_n, log2_cell, lm, fr_fk_lane(lm, log2_cell, (u32)n, wg, t), a.data());
-    for (u32 ll = lm; ll-- > 0;) for (u32 t = 0; t < W; t++) fr_fk_stage(a.data(), lm, ll, sroots.data(), fr_fk_lane(lm, log2_cell, (u32)n, wg, t));
-    for (u32 t = 0; t < W; t++) fr_fk_store(a.data(), log2_cell, lm, fr_fk_lane(lm, log2_cell, (u32)n, wg, t), out32);
-  }
+  for (u32 b = 0; b < fr_fk_workgroups(lm, log2_cell, (u32)n); b++) kzg_fk20_scalars_body(sim_wg<FR_FK_LANES>(), log2_n, log2_cell, (u32)n, b, coef32, sroots.data(), out32, a.data());
   return 0;
 }
 // the projection matrix B of the FK20 cell proofs as kzg_fk20_matrix_kernel writes it: out32[(k M + i) * 32], M = 2^log2_m
 __attribute__((visibility("default"))) int nbls_sim_kzg_fk20_matrix(unsigned log2_m, uint8_t* out32) {
   if (log2_m < 1 || log2_m > 11 || !out32) return -1;
-  std::vector<Fr> roots, iroots;
-  sim_ntt_tables(log2_m, roots, iroots);
+  const std::vector<Fr> roots = sim_roots(log2_m), iroots = sim_inv_roots(log2_m, roots);
   for (u32 idx = 0; !(idx >> (2 * log2_m)); idx++) fr_store_q(fr_fk_matrix_entry(roots.data(), iroots.data(), log2_m, idx >> log2_m, idx & ((1u << log2_m) - 1)), out32 + 32ull * idx);
   return 0;
 }
-// The interpolation of n_cells cells as kzg_cell_interp_kernel runs it (and kzg_cell_sum_kernel behind it in the sum mode): workgroups of FR_CELL_LANES lanes, lane groups of c
-// lanes, every phase of a round on all lanes of a workgroup before the next, a stage's partner value read from the lane i ^ len of the same group, the column trees of the
-// workgroup and of the closing kernel in the kernel's order.  n_wg: the workgroups of the launch (0: as many as the launcher takes).  sum == 0: out = the n_cells rows of
+// The interpolation of n_cells cells as kzg_cell_interp_kernel runs it -- a re-enactment kept by hand: the kernel's lanes exchange registers, which the workgroup view does not
+// model -- and kzg_cell_sum_kernel's body behind it in the sum mode: workgroups of FR_CELL_LANES lanes, lane groups of c lanes, every phase of a round on all lanes of a
+// workgroup before the next, a stage's partner value read from the lane i ^ len of the same group, then fr_workgroup.h's tree.  n_wg: the workgroups of the launch (0: as many as the launcher takes).  sum == 0: out = the n_cells rows of
 // c scalars -a_(k,i); else the c scalars -S_i.  pre, w32 (rows mode) and st_out may be NULL.  -1 where the device call refuses the sizes or an index
 __attribute__((visibility("default"))) int nbls_sim_kzg_cell_interp(unsigned log2_n, unsigned log2_cell, size_t n_cells, int sum, unsigned n_wg, const uint8_t* cells,
                                                                     const uint32_t* cell_index, const int8_t* pre, const uint8_t* w32, uint8_t* out, int8_t* st_out) {
@@ -724,14 +660,11 @@ __attribute__((visibility("default"))) int nbls_sim_kzg_cell_interp(unsigned log
   const unsigned lm = log2_n + 1 - log2_cell;
   const u32 c = 1u << log2_cell, W = FR_CELL_LANES, n = (u32)n_cells;
   for (size_t k = 0; k < n_cells; k++) if (cell_index[k] >> lm) return -1;
-  std::vector<Fr> roots, iroots, ishifts((size_t)1 << lm);
-  if (log2_cell) sim_ntt_tables(log2_cell, roots, iroots);
+  std::vector<Fr> iroots, ishifts((size_t)1 << lm);
+  if (log2_cell) iroots = sim_inv_roots(log2_cell, sim_roots(log2_cell));
   const Fr g = fr_omega(log2_n + 1);
   for (u32 k = 0; k < (1u << lm); k++) ishifts[k] = fr_cell_ishift_entry(g, log2_n, lm, k);
   const u32 wgs = n_wg ? n_wg : fr_cell_workgroups(n, log2_cell, sum != 0), groups = (wgs * W) >> log2_cell, rounds = (n + groups - 1) / groups;
-  auto tree = [&](std::vector<Fr>& part) {
-    for (u32 s = W / 2; s >= c && s > 0; s >>= 1) for (u32 t = 0; t < s; t++) part[t] = fr_add(part[t], part[t + s]);
-  };
   std::vector<Fr> partial((size_t)wgs * c), v(W), nv(W), acc(W), part(W);
   std::vector<u32> bad(W);
   for (u32 b = 0; b < wgs; b++) {
@@ -758,22 +691,14 @@ __attribute__((visibility("default"))) int nbls_sim_kzg_cell_interp(unsigned log
     }
     if (!sum) continue;
     part = acc;
-    tree(part);
+    fr_tree(sim_wg<FR_CELL_LANES>(), part.data(), c);
     for (u32 t = 0; t < c; t++) partial[(size_t)b * c + t] = part[t];
   }
-  if (!sum) return 0;
-  for (u32 t = 0; t < W; t++) {
-    Fr a = fr_zero();
-    for (u32 p = t >> log2_cell; p < wgs; p += W >> log2_cell) a = fr_add(a, partial[(size_t)p * c + (t & (c - 1))]);
-    part[t] = a;
-  }
-  tree(part);
-  for (u32 t = 0; t < c; t++) fr_store_q(fr_neg(part[t]), out + 32ull * t);
+  if (sum) kzg_cell_sum_body(sim_wg<FR_CELL_LANES>(), log2_cell, wgs, partial.data(), out, part.data());
   return 0;
 }
-// nbls_kzg_recover_cells as kzg_recover_z_kernel and kzg_recover_kernel run it: the host's slot maps (fr_recover_slots), one lane per Z value, then per blob FR_NTT_LANES lanes,
-// every phase between two barriers lane after lane, `a` exactly the kernel's dynamic LDS, the half's coefficients S parked in the blob's coefficient row as on the device.
-// coef32 (may be NULL): the n x N coefficients the proofs read.  Returns -1 (NBLS_EINVAL) under the rules of the device call that need no context
+// nbls_kzg_recover_cells: the host's slot maps (fr_recover_slots), one lane per Z value (kzg_recover_z_kernel), then kzg_recover_kernel's body per blob, the half's coefficients
+// S parked in the blob's coefficient row as on the device.  coef32 (may be NULL): the n x N coefficients the proofs read
 __attribute__((visibility("default"))) int nbls_sim_kzg_recover(unsigned log2_n, unsigned log2_cell, size_t n, const uint32_t* cell_offsets, const uint32_t* cell_index,
                                                                 const uint8_t* cells, uint8_t* out_cells, uint8_t* coef32, int8_t* status) {
   if (log2_n < 1 || log2_n > 12 || log2_cell > log2_n || log2_n + 1 - log2_cell > 12) return -1;
@@ -782,64 +707,25 @@ __attribute__((visibility("default"))) int nbls_sim_kzg_recover(unsigned log2_n,
   for (size_t i = 0; i < n; i++) if (cell_offsets[i + 1] < cell_offsets[i]) return -1;
   if (cell_offsets[n] && (!cell_index || !cells)) return -1;
   const unsigned lm = log2_n + 1 - log2_cell;
-  const u32 N = 1u << log2_n, M = 1u << lm, W = FR_NTT_LANES, per = M + M / 2;
-  std::vector<Fr> roots, iroots, sroots(M), zv(per);
-  sim_ntt_tables(log2_n, roots, iroots);
-  const Fr om = fr_omega(lm);
-  for (u32 k = 0; k < M; k++) sroots[k] = fr_root_entry(om, lm, k);
+  const u32 M = 1u << lm, per = M + M / 2;
+  const std::vector<Fr> roots = sim_roots(log2_n), iroots = sim_inv_roots(log2_n, roots), sroots = sim_roots(lm);
   const FrRecoverConsts kc = fr_recover_consts(log2_n, log2_cell);
-  const Fr ninv = fr_inv_pow2(log2_n);
-  std::vector<u32> slot(M), a((size_t)FR_NL * N);
-  std::vector<uint8_t> own((size_t)32 * N);
-  auto stages = [&](bool inverse) {
-    if (inverse) { for (u32 ll = 0; ll < log2_n; ll++) for (u32 l = 0; l < W; l++) fr_ntt_stage(a.data(), log2_n, ll, true, iroots.data(), l, W); }
-    else for (u32 ll = log2_n; ll-- > 0;) for (u32 l = 0; l < W; l++) fr_ntt_stage(a.data(), log2_n, ll, false, roots.data(), l, W);
-  };
+  std::vector<Fr> zv(per);
+  std::vector<u32> slot(M), a((size_t)FR_NL << log2_n);
+  std::vector<uint8_t> own((size_t)32 << log2_n);
+  u32 bad = 0, diff = 0; int8_t st;
   for (size_t p = 0; p < n; p++) {
-    uint8_t *o32 = out_cells + ((64 * p) << log2_n), *c32 = coef32 ? coef32 + ((32 * p) << log2_n) : own.data();
     const u32 first = cell_offsets[p];
-    int st = fr_recover_slots(cell_index ? cell_index + first : nullptr, first, cell_offsets[p + 1] - first, lm, slot.data());
-    u32 bad = 0, diff = 0;
-    if (!st) {
-      for (u32 v = 0; v < per; v++) zv[v] = fr_recover_z(sroots.data(), slot.data(), lm, v, kc.c7);
-      for (u32 l = 0; l < W; l++)
-        bad |= fr_recover_load(cells, slot.data(), zv.data(), log2_n, log2_cell, 0, l, W, a.data()) | fr_recover_load(cells, slot.data(), zv.data(), log2_n, log2_cell, 1, l, W, nullptr);
-      if (bad) st = 21;
-    }
-    if (!st) {
-      stages(true);
-      for (u32 l = 0; l < W; l++) {
-        fr_ntt_scale(a.data(), N, l, W, FR_NTT_LOG2_LANES, &ninv, nullptr, c32);
-        fr_recover_load(cells, slot.data(), zv.data(), log2_n, log2_cell, 1, l, W, a.data());
-      }
-      stages(true);
-      for (u32 l = 0; l < W; l++) {
-        fr_ntt_scale(a.data(), N, l, W, FR_NTT_LOG2_LANES, &ninv, &kc.ginv, nullptr);
-        fr_recover_combine(a.data(), c32, N, l, W, FR_NTT_LOG2_LANES, kc);
-      }
-      stages(false);
-      for (u32 l = 0; l < W; l++) fr_recover_divide(a.data(), zv.data() + M, N, log2_cell, l, W);
-      stages(true);
-      for (u32 l = 0; l < W; l++) { fr_ntt_scale(a.data(), N, l, W, FR_NTT_LOG2_LANES, &ninv, &kc.seveninv, nullptr); fr_ntt_store(a.data(), N, l, W, c32); }
-      stages(false);
-      for (u32 l = 0; l < W; l++) {
-        diff |= fr_recover_compare(a.data(), cells, slot.data(), log2_n, log2_cell, 0, l, W);
-        fr_ntt_store(a.data(), N, l, W, o32);
-        fr_ntt_load(c32, N, l, W, a.data());
-        fr_ntt_scale(a.data(), N, l, W, FR_NTT_LOG2_LANES, nullptr, &kc.g, nullptr);
-      }
-      stages(false);
-      for (u32 l = 0; l < W; l++) { diff |= fr_recover_compare(a.data(), cells, slot.data(), log2_n, log2_cell, 1, l, W); fr_ntt_store(a.data(), N, l, W, o32 + ((size_t)32 << log2_n)); }
-      if (diff) st = 23;
-    }
-    if (status) status[p] = (int8_t)st;
-    if (st) { memset(o32, 0, (size_t)64 << log2_n); if (coef32) memset(c32, 0, (size_t)32 << log2_n); }
+    const int pre = fr_recover_slots(cell_index ? cell_index + first : nullptr, first, cell_offsets[p + 1] - first, lm, slot.data());
+    if (!pre) for (u32 v = 0; v < per; v++) zv[v] = fr_recover_z(sroots.data(), slot.data(), lm, v, kc.c7);
+    kzg_recover_body(sim_wg<FR_NTT_LANES>(), log2_n, log2_cell, cells, slot.data(), pre, zv.data(), kc, roots.data(), iroots.data(), out_cells + ((64 * p) << log2_n),
+                     coef32 ? coef32 + ((32 * p) << log2_n) : own.data(), status ? status + p : &st, a.data(), &bad, &diff);
   }
   return 0;
 }
-// nbls_groth16_input_sums as g16_input_sums_kernel and g16_sum_kernel run it: per tile of columns and workgroup of rows the G16_GROUPS wavefronts row after row -- every lane's
-// look at the row, the wavefront's OR of the lanes' canonical checks, the masked product into the lane's accumulator --, ONE reduction per lane, the column tree in the
-// kernel's order, the partial rows, the closing kernel's walk and tree.  n_wg: the workgroups per tile (0: as many as the launcher takes).  pre and status may be NULL.
+// nbls_groth16_input_sums as g16_input_sums_kernel runs it -- a re-enactment kept by hand: the wavefront's OR is a cross-lane operation, which the workgroup view does not
+// model: per tile of columns and workgroup of rows the G16_GROUPS wavefronts row after row -- every lane's look at the row, the wavefront's OR of the lanes' canonical checks,
+// the masked product into the lane's accumulator --, ONE reduction per lane, fr_workgroup.h's tree, the partial rows; then g16_sum_kernel's body per tile.  n_wg: the workgroups per tile (0: as many as the launcher takes).  pre and status may be NULL.
 // Returns -1 under the rules of the device call that need no context (a weight >= 2^64 among them)
 __attribute__((visibility("default"))) int nbls_sim_g16_input_sums(size_t n, size_t m, unsigned n_wg, const uint8_t* inputs32, const uint8_t* weights32, const int8_t* pre,
                                                                    uint8_t* out32, int8_t* status) {
@@ -848,7 +734,6 @@ __attribute__((visibility("default"))) int nbls_sim_g16_input_sums(size_t n, siz
   const u32 M = (u32)m, tiles = g16_tiles(M), wgs = n_wg ? n_wg : g16_workgroups((u32)n), groups = wgs * G16_GROUPS, W = G16_LANES, T = G16_TILE;
   std::vector<Fr> partial((size_t)wgs * (m + 1)), part(W), x(T);
   std::vector<G16Acc> acc(W);
-  auto tree = [&]() { for (u32 s = W / 2; s >= T; s >>= 1) for (u32 t = 0; t < s; t++) part[t] = fr_add(part[t], part[t + s]); };
   for (u32 tile = 0; tile < tiles; tile++) for (u32 b = 0; b < wgs; b++) {
     for (u32 t = 0; t < W; t++) acc[t] = g16_acc_zero();
     for (u32 g = 0; g < G16_GROUPS; g++) for (uint64_t i = b * G16_GROUPS + g; i < n; i += groups) {
@@ -859,19 +744,10 @@ __attribute__((visibility("default"))) int nbls_sim_g16_input_sums(size_t n, siz
       if (status && tile == 0) status[i] = (int8_t)g16_row_status(p, bad);
     }
     for (u32 t = 0; t < W; t++) part[t] = g16_reduce(acc[t]);
-    tree();
+    fr_tree(sim_wg<G16_LANES>(), part.data(), T);
     for (u32 t = 0; t < T; t++) if (tile * T + t <= M) partial[(size_t)b * (m + 1) + tile * T + t] = part[t];
   }
-  for (u32 tile = 0; tile < tiles; tile++) {
-    for (u32 t = 0; t < W; t++) {
-      const u32 c = tile * T + (t & (T - 1));
-      Fr a = fr_zero();
-      if (c <= M) for (u32 p = t / T; p < wgs; p += G16_GROUPS) a = fr_add(a, partial[(size_t)p * (m + 1) + c]);
-      part[t] = a;
-    }
-    tree();
-    for (u32 t = 0; t < T; t++) if (tile * T + t <= M) fr_store_q(part[t], out32 + 32ull * (tile * T + t));
-  }
+  for (u32 tile = 0; tile < tiles; tile++) g16_sum_body(sim_wg<G16_LANES>(), M, tile, wgs, partial.data(), out32, part.data());
   return 0;
 }
 __attribute__((visibility("default"))) int nbls_sim_program_count() { return (int)P_COUNT; }
