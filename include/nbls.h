@@ -622,6 +622,7 @@ const char* nbls_config_describe(void);   /* "NBLS_X=value(env|default) ...": ev
    nbls_msm_dev, which leaves its result on the device, is not changed.
    Then nbls_kzg_fk20_create / _destroy / _params, nbls_kzg_compute_cells_and_proofs_fk20, nbls_kzg_recover_cells_and_proofs_fk20, the name "endo_g1" of nbls_extra_program_kernel, scratch slots 80 .. 81 (additions only, same version). Then nbls_groth16_vk_create / _destroy / _inputs,
    nbls_groth16_verify, nbls_groth16_prepare_inputs, nbls_groth16_input_sums, NBLS_ST_G16_C, NBLS_TUNE_G16_CHUNK, scratch slots 82 .. 86 (additions only, same version).
+   Then NBLS_TUNE_FE_TAIL_CHAIN, nbls_chain_launches and the name "fe_final12" of nbls_extra_program_kernel (additions only, same version).
    4 (round 6): nbls_hw_queues, NBLS_TUNE_WIDE_MAX, NBLS_TUNE_H2C_NORM_MIN, NBLS_TUNE_INV_WIDE_MAX, NBLS_TUNE_LS_MAX / _LS2_MAX (additions only); the library sets GPU_MAX_HW_QUEUES = 22 at load when the variable is unset (see nbls_pool_init below).
    3 (round 5): nbls_program_kernel, nbls_pool_*, nbls_sign_batch_dev, NBLS_TUNE_VERIFY_* / _SAC_MAX / _PT_LS2_MAX (additions only); nbls_verify_batch_partial_dev writes d_out_fp12 even when it reports a zero point or a decode error
    (contents then meaningless); 2: *_partial take *d_partial as OUT only, *_partial_into added, nbls_tower_op_batch, nbls_verify_batch_msgs_dev.  The bindings check it at load. */
@@ -703,6 +704,7 @@ int nbls_field_kernel_raw(nbls_ctx* ctx, int kind, int form, size_t n, const uin
 #define NBLS_TUNE_MSMB_SLAB 18        /* budget of one slab of groups: sum over its groups of (points after the split) * windows + windows * c * 2^(c - 1), the sorted entries and gathered bucket points that are in scratch at a time; a group that exceeds it alone is a slab of its own (default 2^23; 0 = the default) */
 #define NBLS_TUNE_CELLS_CHUNK 20      /* (19 stays unassigned: tests/test_msm_batch_abi.py pins it as the first unknown key behind the batched MSM's) blobs that nbls_kzg_compute_cells_and_proofs hands to the batched MSM in one pass; 0 (default) = as many whole blobs as its bounds of 2^22 scalars and 2^20 rows take (8 mainnet blobs); a larger value than that changes nothing.  The bytes do not depend on it: it lets a test cross chunk borders with small blobs */
 #define NBLS_TUNE_G16_CHUNK 22        /* (21 stays unassigned: tests/test_kzg_fk20_abi.py pins it as the first unknown key behind NBLS_TUNE_CELLS_CHUNK) proofs that the per-proof pass of nbls_groth16_verify and nbls_groth16_prepare_inputs hand to the batched MSM in one pass; 0 (default) = as many whole proofs as its bounds of 2^22 scalars and 2^20 rows take; a larger value than that changes nothing.  The bytes do not depend on it: it lets a test cross chunk borders with few proofs */
+#define NBLS_TUNE_FE_TAIL_CHAIN 24     /* (23 stays unassigned: tests/test_groth16_abi.py pins it as the first unknown key behind NBLS_TUNE_G16_CHUNK) a final exponentiation that runs launch by launch (a pool context, the halves of a large call) ends short programs inside the launch of the cyclotomic exponentiation before them, for the same items: bit 0 the final product (EXPX + FE_FINAL are one launch), bit 1 FE_MID1 and FE_MID2 likewise; 13 launches per pairing batch become 12 (1), 10 (3).  The bytes do not depend on it.  Default 0 (environment: NBLS_FE_TAIL_CHAIN); nbls_pool_init sets 3 on its contexts, whose streams may share hardware queues: there every launch boundary drains a queue */
 int nbls_set_tuning(nbls_ctx* ctx, int key, long long value);
 int nbls_program_count(void);                 /* number of step programs; timing slot nbls_program_count() = the inversion kernel */
 const char* nbls_program_name(int prog);
@@ -715,6 +717,9 @@ const char* nbls_program_kernel(nbls_ctx* ctx, int prog);
 const char* nbls_extra_program_kernel(nbls_ctx* ctx, const char* name);
 /* launches of such a program in this context so far, -1 for a name that is none (its launches are booked in the timing slot of the numbered program whose stage they serve) */
 long long nbls_extra_program_launches(nbls_ctx* ctx, const char* name);
+/* launches of this context so far that ran several step programs back to back as ONE launch (a chain: the middle of a final exponentiation, the forms of
+   NBLS_TUNE_FE_TAIL_CHAIN); where a chain falls back to one launch per program (checked mode, NBLS_CHAIN=0) it does not count.  -1 without a context. */
+long long nbls_chain_launches(nbls_ctx* ctx);
 /* private (scratch) memory per lane of ahead-of-time kernel k = 0, 1, ... as loaded, -1 past the last one: 0 for every kernel of this build */
 int nbls_aot_kernel_private_bytes(int k);
 int nbls_timing_enable(nbls_ctx* ctx, int on);

@@ -27,10 +27,11 @@
 // Ahead-of-time kernels: X(kernel name, up to four ProgIds it serves; P_COUNT = none).  A kernel's signature table is the union over its programs; programs that
 // share a kernel (and the lanes per item) can run as a CHAIN -- one launch that executes them back to back for the same items, values passing through the same
 // HBM scratch as between separate launches but without a grid-wide boundary: the seven launches EXPX, FE_MID1, EXPX x 3, FE_MID2, EXPX in the middle of a final
-// exponentiation (math.ts:862-867) are one.
+// exponentiation (math.ts:862-867) are one.  A program outside ProgId joins a row as extra_key(its ExtraProg) (programs.h): the final product in its chainable form
+// (XP_FE_FINAL12) is the fourth program of `expx`, so that the last exponentiation and the product are one launch (pipelines_pairing.cpp final_exp_pipeline).
 #define NBLS_AOT_PARTS 8   /* aot_kernel.hip is compiled once per part (Makefile): X's first argument is the part that holds the kernel's device code */
 #define NBLS_AOT_KERNELS(X)                                                  \
-  X(0, expx, P_EXPX, P_FE_MID1, P_FE_MID2, P_COUNT)                          \
+  X(0, expx, P_EXPX, P_FE_MID1, P_FE_MID2, extra_key(XP_FE_FINAL12))         \
   X(0, acc_fe, P_ACC_FE, P_ACC_RAW, P_ACC_BYTES, P_COUNT)                    \
   X(0, lines_pq, P_LINES_PQ, P_COUNT, P_COUNT, P_COUNT)                      \
   X(0, acc4_raw, P_ACC4_RAW, P_ACC8_RAW, P_ACC2_RAW, P_COUNT)                \

@@ -170,7 +170,11 @@ extern "C" int nbls_aot_launch(int k, const nbls::AotArgs* ka, unsigned lds_byte
     if (!attr_set[dev].load(std::memory_order_acquire)) {
       std::lock_guard<std::mutex> g(attr_mu);
       if (!attr_set[dev].load(std::memory_order_relaxed)) {
-        for (int i = 0; i < g_nkernels; i++) (void)hipFuncSetAttribute(g_kernels[i].fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        // a kernel that was refused the attribute would fail every launch above the default LDS limit with a less telling error: report it here, and try again at the next launch
+        for (int i = 0; i < g_nkernels; i++) {
+          const hipError_t e = hipFuncSetAttribute(g_kernels[i].fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+          if (e != hipSuccess) { (void)hipGetLastError(); return (int)e; }
+        }
         attr_set[dev].store(true, std::memory_order_release);
       }
     }

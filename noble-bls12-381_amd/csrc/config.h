@@ -8,4 +8,7 @@ namespace nbls {
 long env_long(const char* name, long dflt);   // integer value of the variable, or dflt when it is unset or empty
 bool env_set(const char* name);               // the variable is defined (whatever its value)
 std::string env_describe();                   // "NAME=value (env|default) ..." of every switch read so far, in order of first use
+// NBLS_FE_TAIL_CHAIN (include/nbls.h NBLS_TUNE_FE_TAIL_CHAIN) when the environment has it, else what the caller gives for its kind of context.  A switch keeps the default of
+// its first reader, so the single context's 0 (nbls_internal.h) and the pool's value (nbls_multi.cpp) go through this one reader
+inline unsigned fe_tail_chain_default(unsigned unset) { const long v = env_long("NBLS_FE_TAIL_CHAIN", -1); return v < 0 ? unset : (unsigned)v & 3u; }
 }  // namespace nbls

@@ -183,7 +183,7 @@ struct DevProgram {
   bool wide_ok = false;   // every step is one the one-limb-per-lane interpreter implements (wide_exec.h): launches of at most ctx->wide_max items run on nbls_vm_kernel_wide
   // ahead-of-time kernel of this program (aot.h) and the translated program, when every step's signature is in the kernel's table
   int aot = -1; AotStep* aot_steps = nullptr; u32* aot_descs = nullptr; u32 aot_lds = 0;
-  mutable unsigned long long launches = 0;   // launches of this program in this context (run_dev): nbls_extra_program_launches tells a test WHICH line program a call took
+  mutable unsigned long long launches = 0;   // launches of this program in this context (run_dev, run_chain): nbls_extra_program_launches tells a test WHICH line program a call took
 };
 
 size_t ls_max();      // defaults of the lane-split thresholds (NBLS_LS_MAX / NBLS_LS2_MAX), tuning.cpp
@@ -260,6 +260,10 @@ struct nbls_ctx {
   // shorter for ONE call, up to four times the instructions per item -- nbls_pool_init sets both to 0 on its contexts (twelve 1024-pairing calls in flight: 1.52 -> 1.95 M pairings/s)
   size_t ls_max = ::ls_max(), ls2_max = ::ls2_max();
   size_t chain_max = (size_t)env_long("NBLS_CHAIN_MAX", 8192);                  // nbls_set_tuning(NBLS_TUNE_CHAIN_MAX); see run_chain
+  // nbls_set_tuning(NBLS_TUNE_FE_TAIL_CHAIN): which short programs of a final exponentiation that runs launch by launch end inside the launch of the exponentiation before
+  // them (final_exp_pipeline: bit 0 the final product, bit 1 FE_MID1 / FE_MID2).  0 for a single context, whose chained middle is one launch already; nbls_pool_init sets it
+  unsigned fe_tail_chain = fe_tail_chain_default(0);
+  unsigned long long chain_launches = 0;   // launches that ran more than one program (run_chain's fused path), nbls_chain_launches: a test tells a chain from its fallback by it
   u32* qp_table = nullptr;      // multiples of p for the weak reduction (vm_exec.h weak_reduce), device copy
   // kzg_table (kzg_common.cpp): the device tables of kzg_kernels.hip, Montgomery form, 32 bytes an entry, built on first use and freed with the context.  [k]: the 2^k roots of unity in bit-reversed order;
   // [13 + k]: the same for 1 / omega, what nbls_fr_ntt's stages towards the coefficients divide by; [26 + 7 log2_n + log2_cell]: the 2 N / c inverse shifts 1 / h_k of the cells that nbls_kzg_verify_cells interpolates

@@ -55,12 +55,25 @@ int final_exp_pipeline(nbls_ctx* ctx, const Window& w, size_t n, uint8_t* f_raw,
                             {P_EXPX, {B(3, T[4], F12), B(5, T[6], F12)}},                          // t6' (parked in T7's buffer)
                             {P_FE_MID2, {B(3, T[6], F12), B(5, T[1], F12), B(6, T[5], F12)}},      // t6
                             {P_EXPX, {B(3, T[5], F12), B(5, T[6], F12)}}};                         // t7
-  if (n < ctx->expc_min && n < ctx->chain_max && !w.beside && ls_variant(ctx, P_EXPX, n) == P_EXPX && !wide_applies(ctx, ctx->prog[P_EXPX], (int)P_EXPX, n)) {
+  const BufList fin = {B(0, T[0], F12), B(1, T[1], F12), B(2, T[2], F12), B(3, T[3], F12), B(4, T[4], F12), B(5, T[5], F12), B(6, T[6], F12), B(7, d_out, 576)};
+  const bool plain_expx = n < ctx->expc_min && ls_variant(ctx, P_EXPX, n) == P_EXPX && !wide_applies(ctx, ctx->prog[P_EXPX], (int)P_EXPX, n);
+  if (plain_expx && n < ctx->chain_max && !w.beside) {
     if ((r = run_chain(ctx, n, mid, 7, s))) return r;      // as one chain
-  } else for (const ChainLink& l : mid) {                  // launch by launch; the exponentiations through expx(), which has forms of its own (rows of P_EXPX are {in, out})
-    if ((r = l.id == P_EXPX ? expx(ctx, w, n, (uint8_t*)l.bufs.a[0].ptr, (uint8_t*)l.bufs.a[1].ptr, s) : run(ctx, l.id, n, l.bufs, s))) return r;
+    return run(ctx, P_FE_FINAL, n, fin, s);
   }
-  return run(ctx, P_FE_FINAL, n, {B(0, T[0], F12), B(1, T[1], F12), B(2, T[2], F12), B(3, T[3], F12), B(4, T[4], F12), B(5, T[5], F12), B(6, T[6], F12), B(7, d_out, 576)}, s);
+  // Launch by launch; the exponentiations through expx(), which has forms of its own (rows of P_EXPX are {in, out}).  With calls in flight on streams that share a hardware
+  // queue, a queue runs one batch's launches back to back and fewer, no coarser launches are faster (+2 % on four queues with both bits, EXPERIMENTS.md): a context told
+  // so (ctx->fe_tail_chain, nbls_pool_init) ends a short program inside the launch of the exponentiation before it, for the same items.  Bit 0: t7 = t6^x and the final
+  // product (XP_FE_FINAL12: FE_FINAL on EXPX's kernel) are one launch; bit 1: FE_MID1 and FE_MID2 join the exponentiation that feeds them.  13 launches per batch become 12 or 10.
+  const unsigned tail = plain_expx ? ctx->fe_tail_chain : 0u;
+  for (int k = 0; k < 7; k++) {
+    const ChainLink& l = mid[k];
+    if (l.id != P_EXPX) { if ((r = run(ctx, l.id, n, l.bufs, s))) return r; continue; }
+    if (k == 6 && (tail & 1)) { const ChainLink last[2] = {l, {extra_key(XP_FE_FINAL12), fin}}; return run_chain(ctx, n, last, 2, s); }
+    if ((tail & 2) && k < 6 && mid[k + 1].id != P_EXPX) { if ((r = run_chain(ctx, n, mid + k, 2, s))) return r; k++; continue; }
+    if ((r = expx(ctx, w, n, (uint8_t*)l.bufs.a[0].ptr, (uint8_t*)l.bufs.a[1].ptr, s))) return r;
+  }
+  return run(ctx, P_FE_FINAL, n, fin, s);
 }
 // one raw Fp12 -> final exponentiation (or plain encoding) -> wire bytes on device
 int finish_single(nbls_ctx* ctx, const Window& w, uint8_t* f_raw, int final_exp, void* d_out, hipStream_t s) {

@@ -286,6 +286,7 @@ static const int MILLER_W = env_int("NBLS_MILLER_W", 16);
 // G2 programs stay at 8: at 4 lanes their LDS footprint (50 KB per wavefront) leaves less than one wavefront per SIMD.
 static const int G1_W = env_int("NBLS_G1_W", 4), G2_W = env_int("NBLS_G2_W", 8), G2MUL_W = env_int("NBLS_G2MUL_W", 8), G1MUL_W = env_int("NBLS_G1MUL_W", 4);
 static const int EXPX_W = env_int("NBLS_EXPX_W", 12);
+static const int FE_FINAL12_WINDOW = 50;   // scheduler look-ahead of XP_FE_FINAL12 (build_extra): 36 slots, 12,224 B; from 60 on 48 slots, 16,064 B; the same 59 steps either way
 // the two Miller programs: ten lane-ops per level of the point chain (6 items per wavefront); an Fp12 op has 12 lane-ops (5 items, no idle lane).
 // ACC_WINDOW keeps the line loads about one and a half iterations ahead of their use (they would otherwise all be hoisted to the front and pin 408 slots)
 static const int LINES_W = env_int("NBLS_LINES_W", 10), ACC_W = env_int("NBLS_ACC_W", 12), ACC_WINDOW = env_int("NBLS_ACC_WINDOW", 330);   // an Fp12 op has exactly 12 lane-ops: 5 items per wave, no idle lane (+5..9 % over 16 lanes once >= 2 waves share a SIMD)
@@ -963,6 +964,14 @@ static Program build_extra(ExtraProg id) {
     B.light_max = MAX_DOT_PRODUCTS; B.neg_cap = 7.0; B.store_batch = 6;   // as P_LINES_PQ: the ten lane-ops of a level in ONE step, 3 t0 and 3 u subtracted as they are
     trace_lines_fe(Px, Py, Qx, Qy, 3);
     return B.compile("lines_fe", LINES_W);
+  }
+  if (id == XP_FE_FINAL12) {
+    // P_FE_FINAL's chain of nine factors at twelve lanes, five items a wavefront: the item shape of P_EXPX, whose launch it ends (final_exp_pipeline).  A chain launch takes the
+    // largest LDS image of its segments, and EXPX's 30 slots leave twelve workgroups a CU: the window is the widest at which this program's image still does (P_FE_FINAL alone
+    // runs with 150 and 48 slots, ten a CU)
+    B.sched_window = env_int("NBLS_FE_FINAL12_WINDOW", FE_FINAL12_WINDOW);
+    output_fp12(trace_fe_final_chain([&](int i) { return inputw_fp12(i - 1, 0); }), 7, 0);
+    return B.compile("fe_final12", 12);
   }
   if (id == XP_DBLADD_G1) {
     auto ld = [&](int buf) { return Pt<SFp>{inputw(buf, 0), inputw(buf, 48), inputw(buf, 96)}; };

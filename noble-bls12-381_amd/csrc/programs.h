@@ -116,11 +116,20 @@ const Program* get_tower_program(int field, int op, int param, int part);
 // keep P_LINES_PQ, whose bytes are pinned.
 // The conversion between the two passes of the FK20 cell proofs (pipelines_kzg_cells.cpp): a raw projective G1 point (buf 3) -> the point and its image (beta X, -Y, Z), the
 // form P_G1_MSM_PREP leaves, without leaving projective coordinates (buf 5): the identity stays the identity.  No ahead-of-time kernel: one short launch on the interpreter.
-enum ExtraProg { XP_POLY_G1_16 = 0, XP_POLY_G1_256, XP_POLY_G2_16, XP_POLY_G2_256, XP_DBLADD_G1, XP_DBLADD_G2, XP_LINES_FE, XP_ENDO_G1, XP_COUNT };
+// The final product of the final exponentiation in the form a chain can hold (pipelines_pairing.cpp final_exp_pipeline): P_FE_FINAL's trace and buffers (t1..t7 in buf 0..6 ->
+// wire bytes in buf 7) under a name of its own, served by the kernel of P_EXPX, so that one launch runs t7 = t6^x and the product for the same items.  P_FE_FINAL keeps its
+// own kernel for the launches that stand alone.
+enum ExtraProg { XP_POLY_G1_16 = 0, XP_POLY_G1_256, XP_POLY_G2_16, XP_POLY_G2_256, XP_DBLADD_G1, XP_DBLADD_G2, XP_LINES_FE, XP_ENDO_G1, XP_FE_FINAL12, XP_COUNT };
+// An ExtraProg where a ProgId is asked for -- a row of NBLS_AOT_KERNELS (aot.h), a link of a chain (bufs.h ChainLink): P_COUNT + 1 + its number, the key nbls_aot_extra_index and
+// the simulator's kernel table look for.  program_by_key resolves either kind.
+static inline ProgId extra_key(ExtraProg e) { return (ProgId)((int)P_COUNT + 1 + (int)e); }
+static inline bool key_is_extra(ProgId id) { return (int)id > (int)P_COUNT; }
+static inline ExtraProg key_extra(ProgId id) { return (ExtraProg)((int)id - (int)P_COUNT - 1); }
 // The simulator's index-taking entry points (nbls_sim_extra_count / _name / _verify / _run) stop in front of this one: the suite pins their count at the four Horner steps.
 // Every later program is reached by name (nbls_sim_extra_verify_named / _run_named), as nbls_extra_program_kernel reaches it in the engine.
 static const int XP_NUMBERED = XP_DBLADD_G1;
 const Program& get_extra_program(ExtraProg id);
+static inline const Program& program_by_key(ProgId id) { return key_is_extra(id) ? get_extra_program(key_extra(id)) : get_program(id); }
 // Does a call that ends in the final exponentiation take its lines from XP_LINES_FE?  NBLS_LINES_FE=0: never (LINES_PQ everywhere, for A/B runs); read once per process.
 bool lines_fe_enabled();
 void print_stats(const Program& p);

@@ -157,23 +157,32 @@ int run_chain(nbls_ctx* ctx, size_t n, const ChainLink* links, size_t count, hip
   int r;
   bool fuse = chains_enabled() && !checked_mode() && count <= (size_t)AOT_MAX_SEGS;
   int k = -1; u32 W = 0, G = 0, lds = 0;
+  // a link names a ProgId or, as extra_key(e), a program outside it (programs.h)
+  auto dev = [&](const ChainLink* l) -> DevProgram& { return key_is_extra(l->id) ? ctx->extra[key_extra(l->id)] : ctx->prog[l->id]; };
   for (const ChainLink* l = links; l < links + count; l++) {
-    if ((r = upload(ctx, l->id))) return r;
-    const DevProgram& d = ctx->prog[l->id];
+    if ((r = key_is_extra(l->id) ? upload_extra(ctx, key_extra(l->id)) : upload(ctx, l->id))) return r;
+    const DevProgram& d = dev(l);
     if (d.aot < 0 || (k >= 0 && (d.aot != k || d.p->W != W || d.p->G != G))) fuse = false;
     k = d.aot; W = d.p->W; G = d.p->G; lds = std::max(lds, d.aot_lds);
   }
-  if (!fuse) { for (const ChainLink* l = links; l < links + count; l++) if ((r = run(ctx, l->id, n, l->bufs, s))) return r; return NBLS_OK; }
+  if (!fuse) {      // (a program outside ProgId has no timing slot of its own)
+    for (const ChainLink* l = links; l < links + count; l++)
+      if ((r = key_is_extra(l->id) ? run_dev(ctx, dev(l), -1, n, l->bufs, s, nullptr, nullptr) : run(ctx, l->id, n, l->bufs, s))) return r;
+    return NBLS_OK;
+  }
   AotArgs a; memset(&a, 0, sizeof a);
   for (const ChainLink* l = links; l < links + count; l++) {
     IOBuf bufs[MAX_BUFS];
     if (!bind_bufs(bufs, l->bufs)) return NBLS_EINVAL;
-    aot_seg(a.seg[a.nseg++], ctx->prog[l->id], bufs);
+    DevProgram& d = dev(l);
+    d.launches++;
+    aot_seg(a.seg[a.nseg++], d, bufs);
   }
   a.W = W; a.G = G; a.n_items = (u32)n; a.qp_table = ctx->qp_table;
   int e;
-  { Timed timed(ctx, (int)links->id, s); e = nbls_aot_launch(k, &a, lds, s); }   // the whole chain is booked on its first program
+  { Timed timed(ctx, key_is_extra(links->id) ? -1 : (int)links->id, s); e = nbls_aot_launch(k, &a, lds, s); }   // the whole chain is booked on its first program
   if (e) { ctx->last_hip = e; return NBLS_EHIP; }
+  ctx->chain_launches++;
   return NBLS_OK;
 }
 

@@ -146,6 +146,7 @@ EXPORT int nbls_set_tuning(nbls_ctx* ctx, int key, long long value) {
     case NBLS_TUNE_MSMB_SLAB: if (value < 0) return NBLS_EINVAL; ctx->msmb_slab = (size_t)value; return NBLS_OK;
     case NBLS_TUNE_CELLS_CHUNK: if (value < 0) return NBLS_EINVAL; ctx->cells_chunk = (size_t)value; return NBLS_OK;
     case NBLS_TUNE_G16_CHUNK: if (value < 0) return NBLS_EINVAL; ctx->g16_chunk = (size_t)value; return NBLS_OK;
+    case NBLS_TUNE_FE_TAIL_CHAIN: if (value < 0 || value > 3) return NBLS_EINVAL; ctx->fe_tail_chain = (unsigned)value; return NBLS_OK;
     default: return NBLS_EINVAL;
   }
 }
@@ -160,7 +161,7 @@ EXPORT const char* nbls_program_kernel(nbls_ctx* ctx, int prog) {
   return d.aot >= 0 ? nbls_aot_name(d.aot) : d.p->lsplit == 4 ? "nbls_vm_kernel_ls4" : d.p->lsplit == 1 ? "nbls_vm_kernel" : "none (two-lane programs have no interpreter form)";
 }
 // The same for a program outside the numbered registry, by its name ("poly_g1_16", "poly_g1_256", "poly_g2_16", "poly_g2_256": the Horner steps of nbls_g*_poly_eval;
-// "dbladd_g1", "dbladd_g2": the combination steps of nbls_g*_msm_batch / _rows; "lines_fe": the line program of the pairings that end in a final exponentiation); NULL for a name that is not one.  The query uploads the program.
+// "dbladd_g1", "dbladd_g2": the combination steps of nbls_g*_msm_batch / _rows; "lines_fe": the line program of the pairings that end in a final exponentiation; "fe_final12": the final product as the last segment of a chain); NULL for a name that is not one.  The query uploads the program.
 EXPORT const char* nbls_extra_program_kernel(nbls_ctx* ctx, const char* name) {
   if (!ctx || !name) return nullptr;
   std::lock_guard<std::recursive_mutex> g(ctx->mu);
@@ -182,6 +183,9 @@ EXPORT long long nbls_extra_program_launches(nbls_ctx* ctx, const char* name) {
 }
 // private (scratch) memory per lane of ahead-of-time kernel k as the loaded code object declares it, -1 past the last kernel: every kernel of aot_kernel.hip is built to need none
 // (a spill in a step body costs every step; tests/test_gpu_lines_fe.py asserts 0 on the device for every kernel)
+// launches of this context so far that ran several programs back to back (run_chain's fused path; its fallback -- checked mode, NBLS_CHAIN=0, programs that do not share a
+// kernel and an item shape -- launches the programs one by one and does not count): tells a test that a chain really was one launch
+EXPORT long long nbls_chain_launches(nbls_ctx* ctx) { if (!ctx) return -1; std::lock_guard<std::recursive_mutex> g(ctx->mu); return (long long)ctx->chain_launches; }
 EXPORT int nbls_aot_kernel_private_bytes(int k) { return nbls_aot_private_bytes(k); }
 EXPORT int nbls_program_count(void) { return (int)P_COUNT; }
 EXPORT const char* nbls_program_name(int prog) { return prog >= 0 && prog < P_COUNT ? get_program((ProgId)prog).name.c_str() : nullptr; }

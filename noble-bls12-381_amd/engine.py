@@ -1116,6 +1116,11 @@ class Engine:
         """items below which the middle of the final exponentiation is one chained launch (NBLS_TUNE_CHAIN_MAX; default 8192, 0: one launch per program)"""
         self._chk(self.lib.nbls_set_tuning(self.h, 4, n))
 
+    def set_fe_tail_chain(self, bits):
+        """which short programs of a final exponentiation that runs launch by launch end inside the exponentiation's launch before them (NBLS_TUNE_FE_TAIL_CHAIN): bit 0 the
+        final product, bit 1 FE_MID1 / FE_MID2; default 0, pool contexts are set by nbls_pool_init"""
+        self._chk(self.lib.nbls_set_tuning(self.h, 24, int(bits)))
+
     def set_sac_max(self, n):
         """keys up to which sign's ladder is the sign-aligned one-addition-per-bit form (NBLS_TUNE_SAC_MAX; default 6144, 0: the windowed psi-split ladder at every size)"""
         self._chk(self.lib.nbls_set_tuning(self.h, 8, n))
@@ -1196,6 +1201,12 @@ class Engine:
         self.lib.nbls_extra_program_launches.restype = C.c_longlong
         self.lib.nbls_extra_program_launches.argtypes = [C.c_void_p, C.c_char_p]
         return self.lib.nbls_extra_program_launches(self.h, name.encode())
+
+    def chain_launches(self):
+        """launches of this context so far that ran several programs as one launch (nbls_chain_launches; a chain's fallback of one launch per program does not count)"""
+        self.lib.nbls_chain_launches.restype = C.c_longlong
+        self.lib.nbls_chain_launches.argtypes = [C.c_void_p]
+        return self.lib.nbls_chain_launches(self.h)
 
     def kernel_bindings(self):
         """{program: kernel} over every step program"""
