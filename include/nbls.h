@@ -435,6 +435,25 @@ int nbls_kzg_compute_blob_proofs(nbls_ctx* ctx, const nbls_kzg_setup* setup, siz
 #define NBLS_NTT_TO_EVALS 1
 int nbls_fr_ntt(nbls_ctx* ctx, unsigned log2_n /* 1 .. 12 */, int dir, size_t n, const uint8_t* in32 /* n << log2_n */, const uint8_t* shift32 /* n, or NULL */,
                 uint8_t* out32 /* n << log2_n */, int8_t* status /* n, may be NULL */);
+/* nbls_fr_ntt_large / nbls_fr_ntt_dev: the same transform for N = 2^log2_n up to 2^24 elements a polynomial, with nbls_fr_ntt's contract word for word: coefficients in
+ * natural order, values p_i(s_i w_j) in bit-reversed order, canonical 32-byte big-endian elements, status 0 / NBLS_ST_NON_CANONICAL / 5 for a zero shift (non-canonical
+ * before zero), a refused row all-zero, its neighbours not disturbed.  With t the log size of the tails (12) and K = log2_n - t:
+ *   log2_n <= t    the kernel of nbls_fr_ntt, launched as nbls_fr_ntt launches it: the same bytes;
+ *   log2_n >  t    towards the values: the first K stages of the same network as launches over runs of at most P consecutive stages (a workgroup holds 2^q rows of 2^c
+ *                  contiguous elements in LDS and reads only the table of 2^K roots: T_N[j] = T_(2^K)[j] for j < 2^K, so no table of N roots exists), then one launch of
+ *                  2^K tails a polynomial: block B holds p mod (X^(2^t) - T_N[B]), whose values are those of the transform of size 2^t with the shift omega_N^rev_K(B).
+ *                  Towards the coefficients: the tails first, then the runs in reverse order, then 1 / N.  The first launch checks the canonical form and multiplies by
+ *                  s^i (the last by (1 / s)^i); a refused polynomial raises a flag word in scratch that the last launch turns into zeros and the status.
+ * t and P are NBLS_TUNE_NTT_TAIL_BITS / _PASS_BITS; the bytes never depend on them.  K <= 12 is required (NBLS_EINVAL otherwise: a tail size below log2_n - 12).
+ * NBLS_EINVAL before any device work for log2_n outside 1 .. 24, an unknown direction, a NULL context, missing buffers with n > 0, more than 2^24 elements in the call;
+ * n = 0 is NBLS_OK.
+ * nbls_fr_ntt_dev works on device memory and is asynchronous: ordered on `stream` (NULL: the context's) like the other _dev calls.  d_in32 and d_out32 are 16-byte
+ * aligned; d_out32 may equal d_in32 (every launch reads and writes the same disjoint set of elements per workgroup), any other overlap is NBLS_EINVAL.  d_shift32: n x 32
+ * bytes or NULL; d_status: n bytes or NULL.  At 2^24 elements a host-buffer call moves 1 GB over the bus: callers that keep their polynomials on the device want this form. */
+int nbls_fr_ntt_large(nbls_ctx* ctx, unsigned log2_n /* 1 .. 24 */, int dir, size_t n, const uint8_t* in32 /* n << log2_n */, const uint8_t* shift32 /* n, or NULL */,
+                      uint8_t* out32 /* n << log2_n */, int8_t* status /* n, may be NULL */);
+int nbls_fr_ntt_dev(nbls_ctx* ctx, unsigned log2_n /* 1 .. 24 */, int dir, size_t n, const void* d_in32, const void* d_shift32 /* or NULL */, void* d_out32,
+                    void* d_status /* n bytes, or NULL */, void* stream);
 /* compute_cells for n blobs with c = 2^log2_cell elements per cell (0 <= log2_cell <= log2_n; mainnet: log2_n = 12, log2_cell = 6, 128 cells of 64 elements).  With g = omega_2N
  * and p the blob's polynomial, the extension in bit-reversed order over 2 N is  ext[i] = blob[i],  ext[N + i] = p(g w_i);  cell k is ext[c k .. c k + c), its points are
  * h_k omega_c^rev(j) with h_k = g^rev(k) over log2_n + 1 - log2_cell bits (coset_for_cell).  out_cells holds, per blob, the 2 N elements in cell order: the blob's own bytes,
@@ -623,6 +642,7 @@ const char* nbls_config_describe(void);   /* "NBLS_X=value(env|default) ...": ev
    Then nbls_kzg_fk20_create / _destroy / _params, nbls_kzg_compute_cells_and_proofs_fk20, nbls_kzg_recover_cells_and_proofs_fk20, the name "endo_g1" of nbls_extra_program_kernel, scratch slots 80 .. 81 (additions only, same version). Then nbls_groth16_vk_create / _destroy / _inputs,
    nbls_groth16_verify, nbls_groth16_prepare_inputs, nbls_groth16_input_sums, NBLS_ST_G16_C, NBLS_TUNE_G16_CHUNK, scratch slots 82 .. 86 (additions only, same version).
    Then NBLS_TUNE_FE_TAIL_CHAIN, nbls_chain_launches and the name "fe_final12" of nbls_extra_program_kernel (additions only, same version).
+   Then nbls_fr_ntt_large, nbls_fr_ntt_dev, NBLS_TUNE_NTT_TAIL_BITS / _PASS_BITS, scratch slot 87 (additions only, same version).
    4 (round 6): nbls_hw_queues, NBLS_TUNE_WIDE_MAX, NBLS_TUNE_H2C_NORM_MIN, NBLS_TUNE_INV_WIDE_MAX, NBLS_TUNE_LS_MAX / _LS2_MAX (additions only); the library sets GPU_MAX_HW_QUEUES = 22 at load when the variable is unset (see nbls_pool_init below).
    3 (round 5): nbls_program_kernel, nbls_pool_*, nbls_sign_batch_dev, NBLS_TUNE_VERIFY_* / _SAC_MAX / _PT_LS2_MAX (additions only); nbls_verify_batch_partial_dev writes d_out_fp12 even when it reports a zero point or a decode error
    (contents then meaningless); 2: *_partial take *d_partial as OUT only, *_partial_into added, nbls_tower_op_batch, nbls_verify_batch_msgs_dev.  The bindings check it at load. */
@@ -705,6 +725,8 @@ int nbls_field_kernel_raw(nbls_ctx* ctx, int kind, int form, size_t n, const uin
 #define NBLS_TUNE_CELLS_CHUNK 20      /* (19 stays unassigned: tests/test_msm_batch_abi.py pins it as the first unknown key behind the batched MSM's) blobs that nbls_kzg_compute_cells_and_proofs hands to the batched MSM in one pass; 0 (default) = as many whole blobs as its bounds of 2^22 scalars and 2^20 rows take (8 mainnet blobs); a larger value than that changes nothing.  The bytes do not depend on it: it lets a test cross chunk borders with small blobs */
 #define NBLS_TUNE_G16_CHUNK 22        /* (21 stays unassigned: tests/test_kzg_fk20_abi.py pins it as the first unknown key behind NBLS_TUNE_CELLS_CHUNK) proofs that the per-proof pass of nbls_groth16_verify and nbls_groth16_prepare_inputs hand to the batched MSM in one pass; 0 (default) = as many whole proofs as its bounds of 2^22 scalars and 2^20 rows take; a larger value than that changes nothing.  The bytes do not depend on it: it lets a test cross chunk borders with few proofs */
 #define NBLS_TUNE_FE_TAIL_CHAIN 24     /* (23 stays unassigned: tests/test_groth16_abi.py pins it as the first unknown key behind NBLS_TUNE_G16_CHUNK) a final exponentiation that runs launch by launch (a pool context, the halves of a large call) ends short programs inside the launch of the cyclotomic exponentiation before them, for the same items: bit 0 the final product (EXPX + FE_FINAL are one launch), bit 1 FE_MID1 and FE_MID2 likewise; 13 launches per pairing batch become 12 (1), 10 (3).  The bytes do not depend on it.  Default 0 (environment: NBLS_FE_TAIL_CHAIN); nbls_pool_init sets 3 on its contexts, whose streams may share hardware queues: there every launch boundary drains a queue */
+#define NBLS_TUNE_NTT_TAIL_BITS 26    /* (25 stays unassigned: tests/test_fr_ntt_large_abi.py pins it as the first unknown key behind NBLS_TUNE_FE_TAIL_CHAIN) t, the log size of the tails of nbls_fr_ntt_large / nbls_fr_ntt_dev: 1 .. 12; 0 (default) = 12.  A transform of 2^log2_n elements with log2_n > t runs log2_n - t <= 12 global stages in front of (behind, on the way back) 2^(log2_n - t) transforms of size 2^t.  The bytes do not depend on it: it lets a test drive the split at sizes where Python integers are the oracle */
+#define NBLS_TUNE_NTT_PASS_BITS 27    /* P, the global stages one launch of the same calls runs at most: 1 .. 9 (nine stages of rows of 8 elements fill the LDS tile of 2^12 elements); 0 (default) = 8.  The log2_n - t global stages are cut into ceil((log2_n - t) / P) runs whose lengths differ by one at most.  The bytes do not depend on it (28 stays unassigned) */
 int nbls_set_tuning(nbls_ctx* ctx, int key, long long value);
 int nbls_program_count(void);                 /* number of step programs; timing slot nbls_program_count() = the inversion kernel */
 const char* nbls_program_name(int prog);

@@ -430,6 +430,93 @@ NBLS_FR_HD void fr_ntt_store(const uint32_t* a, uint32_t N, uint32_t lane, uint3
   for (uint32_t i = lane; i < N; i += lanes) fr_store_q(fr_ntt_get(a, N, i), out32 + 32ull * i);
 }
 
+// ---- Transforms of more elements than one workgroup holds: N = 2^L, L <= 24 (nbls_fr_ntt_large / nbls_fr_ntt_dev; kzg_ntt_pass_kernel, kzg_ntt_tail_kernel and
+// nbls_sim_fr_ntt_large).  With T_N[j] = omega_N^rev_L(j) the table above, t the tail's log size and K = L - t <= 12, the network above splits into
+//   K global stages j = 0 .. K - 1 (half-length N / 2^(j+1), block b with zeta = T_N[2 b], 2 b < 2^K: T_N[j] = T_(2^K)[j] for j < 2^K, so the table of 2^K roots serves
+//     and no table of N roots exists), cut into runs of at most P consecutive stages, one launch per run;
+//   2^K tails: after K stages block B (2^t contiguous elements) holds p mod (X^(2^t) - T_N[B]), and its values are those of that remainder on s_B w_j, w_j the table of
+//     2^t roots, s_B = omega_N^rev_K(B) (s_B^(2^t) = T_N[B]): the transform above on the block with the shift s_B.
+// A run j0 .. j0 + q - 1 is independent per (hi, lo) of index = hi 2^(L - j0) + row 2^(L - j0 - q) + lo: a network over the q bits of `row`, whose stage j0 + k has the
+// block number (hi << k) | (the top k bits of row).  A workgroup takes one hi and 2^c consecutive lo -- a tile of 2^q rows of 2^c contiguous elements, element i of the
+// tile at row i >> c, column i & (2^c - 1), in `a` laid out [limb][i] as above -- and runs the q stages as the stages of a transform of 2^(q + c) elements whose table
+// starts at entry 2 (hi << k).  c <= the log of the lanes: a lane's elements t, t + lanes, .. then share their column, and their indices step by a fixed amount.
+// The way back: the tails towards the coefficients with 1 / s_B, then the runs in reverse order with the inverse roots of size 2^K, then 1 / N in the run that has stage 0.
+struct FrNttRun { uint32_t log2_n, j0, q, c; };
+#if defined(__HIPCC__)
+#define NBLS_FR_RUN_HD __host__ __device__ __forceinline__   // (forced: a run or a factor passed by address to a function the compiler declines to inline costs the kernel a stack)
+#else
+#define NBLS_FR_RUN_HD inline
+#endif
+enum { FR_NTTL_MAX_LOG2 = 24, FR_NTTL_MAX_TAIL = 12, FR_NTTL_MAX_PASS = 9, FR_NTTL_MAX_TILE = 12 };   // (9 stages of rows of 8 elements fill the tile of 2^12)
+enum { FR_NTTL_DEFAULT_TAIL = 12, FR_NTTL_DEFAULT_PASS = 8 };   // t and P where the caller sets none (the sweep behind P: EXPERIMENTS.md)
+enum { FR_NTTL_BAD = 1, FR_NTTL_ZERO = 2 };   // the bits of a polynomial's flag word: an element or the shift is >= r | the shift is 0 mod r
+// the plan: K stages in ceil(K / P) runs whose lengths differ by one at most, the longer ones first; run i of them -> its first stage and its length
+NBLS_FR_HD uint32_t fr_nttl_runs(uint32_t K, uint32_t P) { return (K + P - 1) / P; }
+NBLS_FR_HD FrNttRun fr_nttl_run(uint32_t log2_n, uint32_t K, uint32_t P, uint32_t i) {
+  const uint32_t runs = fr_nttl_runs(K, P), base = K / runs, more = K % runs;
+  FrNttRun R;
+  R.log2_n = log2_n; R.j0 = i * base + (i < more ? i : more); R.q = base + (i < more ? 1u : 0u);
+  const uint32_t rest = log2_n - R.j0 - R.q, room = FR_NTTL_MAX_TILE - R.q;
+  R.c = rest < room ? rest : room;
+  if (R.c > FR_NTT_LOG2_LANES) R.c = FR_NTT_LOG2_LANES;
+  return R;
+}
+// element i of the tile (hi, lo0) -> its index in the polynomial
+NBLS_FR_RUN_HD uint32_t fr_run_index(const FrNttRun& R, uint32_t hi, uint32_t lo0, uint32_t i) {
+  return (hi << (R.log2_n - R.j0)) + ((i >> R.c) << (R.log2_n - R.j0 - R.q)) + lo0 + (i & ((1u << R.c) - 1));
+}
+// the lane's elements of the tile into `a`; returns all ones when one of them is >= r
+NBLS_FR_RUN_HD uint32_t fr_run_load(const FrNttRun& R, const uint8_t* in32, uint32_t hi, uint32_t lo0, uint32_t lane, uint32_t lanes, uint32_t* a) {
+  const uint32_t T = 1u << (R.q + R.c);
+  uint32_t bad = 0;
+  for (uint32_t i = lane; i < T; i += lanes) {
+    const Fr v = fr_load_q(in32 + 32ull * fr_run_index(R, hi, lo0, i));
+    bad |= fr_ge_r_mask(v);
+    fr_ntt_put(a, T, i, v);
+  }
+  return bad;
+}
+// the lane's elements of a tile of the run that has stage 0 (hi = 0) times f (NULL: 1) and, the element of index g in the polynomial, times s^g (NULL: s = 1): one power
+// per lane, then steps of s^((lanes >> c) 2^(L - q)), the distance of the lane's consecutive elements
+NBLS_FR_RUN_HD void fr_run_scale(uint32_t* a, const FrNttRun& R, uint32_t lo0, uint32_t lane, uint32_t lanes, unsigned log2_lanes, const Fr* f, const Fr* s) {
+  const uint32_t T = 1u << (R.q + R.c);
+  Fr pw = fr_one(), step = pw;
+  if (s) {
+    pw = fr_pow_index(*s, fr_run_index(R, 0, lo0, lane) & ((1u << R.log2_n) - 1), R.log2_n);
+    step = *s;
+    for (unsigned b = 0; b < log2_lanes - R.c + R.log2_n - R.q; b++) step = fr_sqr(step);
+  }
+  for (uint32_t i = lane; i < T; i += lanes) {
+    Fr v = fr_ntt_get(a, T, i);
+    if (f) v = fr_mul(v, *f);
+    if (s) { v = fr_mul(v, pw); pw = fr_mul(pw, step); }
+    fr_ntt_put(a, T, i, v);
+  }
+}
+// fr_ntt_stage on a tile of 2^log2_tile elements: half-length 2^log2_len; table = entry 2 (hi << k) of the roots (or of the inverse roots) of size 2^K on; unit: the stage
+// is stage 0 of the transform, whose one block has zeta = 1
+NBLS_FR_RUN_HD void fr_run_stage(uint32_t* a, unsigned log2_tile, unsigned log2_len, bool inverse, bool unit, const Fr* table, uint32_t lane, uint32_t lanes) {
+  const uint32_t T = 1u << log2_tile, len = 1u << log2_len;
+  for (uint32_t b = lane; b < T / 2; b += lanes) {
+    const uint32_t blk = b >> log2_len, lo = (blk << (log2_len + 1)) | (b & (len - 1)), hi = lo + len;
+    const Fr u = fr_ntt_get(a, T, lo), v = fr_ntt_get(a, T, hi);
+    if (inverse) {
+      const Fr d = fr_sub(u, v);
+      fr_ntt_put(a, T, lo, fr_add(u, v));
+      fr_ntt_put(a, T, hi, unit ? d : fr_mul(d, table[2 * blk]));
+    } else {
+      const Fr t = unit ? v : fr_mul(v, table[2 * blk]);
+      fr_ntt_put(a, T, lo, fr_add(u, t));
+      fr_ntt_put(a, T, hi, fr_sub(u, t));
+    }
+  }
+}
+// the lane's elements of the tile back to the polynomial (zero: as all-zero bytes)
+NBLS_FR_RUN_HD void fr_run_store(const FrNttRun& R, const uint32_t* a, bool zero, uint32_t hi, uint32_t lo0, uint32_t lane, uint32_t lanes, uint8_t* out32) {
+  const uint32_t T = 1u << (R.q + R.c);
+  for (uint32_t i = lane; i < T; i += lanes) fr_store_q(zero ? fr_zero() : fr_ntt_get(a, T, i), out32 + 32ull * fr_run_index(R, hi, lo0, i));
+}
+
 // ---- The quotient rows of the cell proofs (compute_cells_and_kzg_proofs of EIP-7594; kzg_cell_rows_kernel and nbls_sim_kzg_cell_rows).  Cell k of a polynomial p of N
 // coefficients holds its values on the coset h_k <omega_c>, whose vanishing polynomial is X^c - s_k, s_k = h_k^c = entry k of the table of the 2 N / c roots of unity.  The
 // proof's quotient is the floor quotient of p by it in coefficient form:  q_i = 0 for i >= N - c,  q_i = p_(i + c) + s_k q_(i + c)  downwards -- c independent chains of N / c

@@ -26,6 +26,7 @@ template <uint32_t LANES> struct FrWorkgroup {
   template <class F> __device__ __forceinline__ void phase(F f) const { f((uint32_t)threadIdx.x); __syncthreads(); }
   template <class F> __device__ __forceinline__ void last(F f) const { f((uint32_t)threadIdx.x); }
   __device__ void raise(uint32_t* flag) const { atomicOr(flag, 0xffffffffu); }
+  __device__ void raise(uint32_t* flag, uint32_t bits) const { atomicOr(flag, bits); }
 };
 #else
 #define NBLS_WG_FN inline
@@ -35,6 +36,7 @@ template <uint32_t LANES> struct FrWorkgroup {
   template <class F> void phase(F f) const { last(f); }
   template <class F> void last(F f) const { for (uint32_t i = 0; i < LANES; i++) f(descending ? LANES - 1 - i : i); }
   void raise(uint32_t* flag) const { *flag = 0xffffffffu; }
+  void raise(uint32_t* flag, uint32_t bits) const { *flag |= bits; }
 };
 #endif
 
@@ -210,6 +212,85 @@ NBLS_WG_FN void kzg_recover_body(WG wg, unsigned log2_n, unsigned log2_cell, con
     if (t == 0) *status = (int8_t)st;
     if (st) { fr_lane_zero16(o32, 4 * N, t, L); fr_lane_zero16(c32, 2 * N, t, L); }
   });
+}
+
+// ---- Transforms past one workgroup's LDS (kzg_ntt_pass_kernel, kzg_ntt_tail_kernel; nbls_sim_fr_ntt_large); fr_exec.h has the split.  A polynomial is seen by many
+// workgroups, so what refuses it lives in global memory: one flag word per polynomial (FR_NTTL_BAD | FR_NTTL_ZERO), cleared in front of the call's first launch and raised
+// atomically; no launch reads the word it may raise, and the launch that runs last turns a flagged row into zeros and writes the status (the workgroup `reader`, one per
+// polynomial, which is also the one that looks at the caller's shift).
+NBLS_WG_FN int fr_nttl_status(uint32_t flag) { return flag & FR_NTTL_BAD ? NBLS_ST_NON_CANONICAL : flag & FR_NTTL_ZERO ? FR_ST_ZERO_DIVISOR : 0; }
+// One run of global stages on the tile (hi, lo0) of one polynomial: f32 -> o32 (the polynomial's rows; equal, or disjoint), the tile in `a`, one barrier per stage.
+//   towards the values   the run with stage 0 checks the canonical form of what it reads and multiplies element g by s^g (shift32: the caller's, may be NULL)
+//   towards the coefficients (`inverse`, table = the inverse roots)   the run with stage 0 is the call's last launch: times 1 / N and (1 / s)^g (sinv: what the tail
+//                        launch left, Montgomery form; NULL: no shift), or zeros, and the status
+template <class WG>
+NBLS_WG_FN void kzg_ntt_pass_body(WG wg, const FrNttRun& R, bool inverse, uint32_t hi, uint32_t lo0, bool reader, const uint8_t* f32, uint8_t* o32, const uint8_t* shift32,
+                                  const Fr* sinv, const Fr* table, uint32_t* flag, int8_t* status, uint32_t* a) {
+  const uint32_t L = wg.lanes(), lt = R.q + R.c;
+  const bool first = R.j0 == 0;
+  auto stage = [&](uint32_t k) { wg.phase([&](uint32_t t) { fr_run_stage(a, lt, lt - 1 - k, inverse, R.j0 + k == 0, table + ((size_t)hi << (k + 1)), t, L); }); };
+  if (!inverse) {
+    const Fr s = first && shift32 ? fr_from_bytes(shift32) : fr_one();
+    wg.phase([&](uint32_t t) {
+      const uint32_t bad = fr_run_load(R, f32, hi, lo0, t, L, a);
+      if (!first) return;
+      if (bad) wg.raise(flag, FR_NTTL_BAD);
+      if (!shift32) return;
+      if (reader && t == 0) {
+        if (fr_ge_r_mask(fr_load_be(shift32))) wg.raise(flag, FR_NTTL_BAD);
+        if (fr_is_zero_mask(s)) wg.raise(flag, FR_NTTL_ZERO);
+      }
+      fr_run_scale(a, R, lo0, t, L, FR_NTT_LOG2_LANES, nullptr, &s);
+    });
+    for (uint32_t k = 0; k < R.q; k++) stage(k);
+    wg.last([&](uint32_t t) { fr_run_store(R, a, false, hi, lo0, t, L, o32); });
+    return;
+  }
+  wg.phase([&](uint32_t t) { fr_run_load(R, f32, hi, lo0, t, L, a); });
+  for (uint32_t k = R.q; k-- > 0;) stage(k);
+  if (!first) { wg.last([&](uint32_t t) { fr_run_store(R, a, false, hi, lo0, t, L, o32); }); return; }
+  const int st = fr_nttl_status(*flag);
+  const Fr ninv = fr_inv_pow2(R.log2_n), si = sinv ? *sinv : fr_one();
+  wg.last([&](uint32_t t) {
+    if (reader && t == 0 && status) *status = (int8_t)st;
+    if (!st) fr_run_scale(a, R, lo0, t, L, FR_NTT_LOG2_LANES, &ninv, sinv ? &si : nullptr);
+    fr_run_store(R, a, st != 0, hi, lo0, t, L, o32);
+  });
+}
+// One tail: block B of a polynomial (2^log2_t contiguous elements, f32 -> o32; B < 2^log2_k) through the stages of kzg_ntt_body with the shift s_B = w^rev(B), which one
+// lane computes (w = omega_N towards the values, 1 / omega_N towards the coefficients; Montgomery form).
+//   towards the values   the call's last launch: a flagged polynomial's blocks come out as zeros, and block 0 writes the status
+//   towards the coefficients (`inverse`)   the call's first: the canonical check; block 0 looks at the caller's shift (shift32, may be NULL) and leaves 1 / s in *sinv.
+//                        The factor 1 / 2^log2_t waits for the last run
+template <class WG>
+NBLS_WG_FN void kzg_ntt_tail_body(WG wg, unsigned log2_t, unsigned log2_k, bool inverse, uint32_t B, const Fr& w, const uint8_t* f32, uint8_t* o32, const uint8_t* shift32,
+                                  Fr* sinv, const Fr* roots, const Fr* iroots, uint32_t* flag, int8_t* status, uint32_t* a, Fr* sh_s) {
+  const uint32_t N = 1u << log2_t, L = wg.lanes();
+  wg.phase([&](uint32_t t) {
+    if (t != 0) return;
+    *sh_s = fr_pow_index(w, fr_bitrev(B, log2_k), FR_NTTL_MAX_TAIL);   // (the exponent has at most 12 bits: all of them are walked, as fr_root_entry does)
+    if (inverse && B == 0 && shift32) {
+      uint32_t bad = 0, zero = 0;
+      *sinv = fr_ntt_shift(shift32, true, &bad, &zero);
+      if (bad) wg.raise(flag, FR_NTTL_BAD);
+      if (zero) wg.raise(flag, FR_NTTL_ZERO);
+    }
+  });
+  const Fr s = *sh_s;
+  if (inverse) {
+    wg.phase([&](uint32_t t) { if (fr_ntt_load(f32, N, t, L, a)) wg.raise(flag, FR_NTTL_BAD); });
+    fr_ntt_stages(wg, a, log2_t, true, iroots);
+    wg.last([&](uint32_t t) { fr_ntt_scale(a, N, t, L, FR_NTT_LOG2_LANES, nullptr, &s, nullptr); fr_ntt_store(a, N, t, L, o32); });
+    return;
+  }
+  const int st = fr_nttl_status(*flag);
+  if (st) {
+    wg.last([&](uint32_t t) { if (B == 0 && t == 0 && status) *status = (int8_t)st; fr_lane_zero16(o32, 2 * N, t, L); });
+    return;
+  }
+  wg.phase([&](uint32_t t) { fr_ntt_load(f32, N, t, L, a); fr_ntt_scale(a, N, t, L, FR_NTT_LOG2_LANES, nullptr, &s, nullptr); });
+  fr_ntt_stages(wg, a, log2_t, false, roots);
+  wg.last([&](uint32_t t) { if (B == 0 && t == 0 && status) *status = 0; fr_ntt_store(a, N, t, L, o32); });
 }
 
 // ---- The per-blob scalars of FK20's pass A (kzg_fk20_scalars_kernel; nbls_sim_kzg_fk20_scalars): workgroup `block` of FR_FK_LANES lanes, its stripes side by side in `a`

@@ -70,6 +70,26 @@ __global__ void __launch_bounds__(NT) kzg_ntt_kernel(u32 log2_n, u32 mode, const
   kzg_ntt_body(FrWorkgroup<NT>(), log2_n, mode, in32 + ((p * 32) << log2_n), shift32 ? shift32 + (u64)shift_stride * p : nullptr, roots, iroots, out32 + p * out_stride, out_stride,
                coef32 ? coef32 + ((p * 32) << log2_n) : nullptr, status ? status + p : nullptr, a, &sh_s, &sh_bad, &sh_zero);
 }
+// Transforms of up to 2^24 elements (nbls_fr_ntt_large / nbls_fr_ntt_dev; fr_exec.h has the split, fr_workgroup.h kzg_ntt_pass_body and kzg_ntt_tail_body the bodies).
+// One run of global stages: workgroup = (polynomial, hi, tile of 2^c consecutive lo), its 2^(q + c) elements in dynamic LDS (at most 128 KB), one barrier per stage.  in32
+// and out32 are equal or disjoint (every workgroup reads and writes the same elements): no __restrict__.  shift32: n shifts, or NULL; sinv: n elements, or NULL
+__global__ void __launch_bounds__(NT) kzg_ntt_pass_kernel(FrNttRun R, u32 inverse, const uint8_t* in32, uint8_t* out32, const uint8_t* __restrict__ shift32,
+                                                          const Fr* __restrict__ sinv, const Fr* __restrict__ table, u32* flags, int8_t* __restrict__ status) {
+  extern __shared__ u32 a[];
+  const u32 lt = R.log2_n - R.j0 - R.q - R.c, w = blockIdx.x, within = w & ((1u << (lt + R.j0)) - 1);   // lt: the log of the tiles of one hi
+  const u64 p = w >> (lt + R.j0), row = (p * 32) << R.log2_n;
+  kzg_ntt_pass_body(FrWorkgroup<NT>(), R, inverse != 0, within >> lt, (within & ((1u << lt) - 1)) << R.c, within == 0, in32 + row, out32 + row, shift32 ? shift32 + 32 * p : nullptr,
+                    sinv ? sinv + p : nullptr, table, flags + p, status ? status + p : nullptr, a);
+}
+// The tails: workgroup = block B of 2^log2_t elements of a polynomial of 2^log2_k blocks, kzg_ntt_kernel's stages with the block's own shift
+__global__ void __launch_bounds__(NT) kzg_ntt_tail_kernel(u32 log2_t, u32 log2_k, u32 inverse, Fr w, const uint8_t* in32, uint8_t* out32, const uint8_t* __restrict__ shift32,
+                                                          Fr* sinv, const Fr* __restrict__ roots, const Fr* __restrict__ iroots, u32* flags, int8_t* __restrict__ status) {
+  extern __shared__ u32 a[];
+  __shared__ Fr sh_s;
+  const u64 blk = blockIdx.x, p = blk >> log2_k, off = (blk * 32) << log2_t;
+  kzg_ntt_tail_body(FrWorkgroup<NT>(), log2_t, log2_k, inverse != 0, (u32)blk & ((1u << log2_k) - 1), w, in32 + off, out32 + off, shift32 ? shift32 + 32 * p : nullptr, sinv + p, roots,
+                    iroots, flags + p, status ? status + p : nullptr, a, &sh_s);
+}
 // The quotient rows of n blobs' cell proofs, one lane per chain (fr_exec.h fr_cell_chain): lane (blob, k, j), j fastest, so that a wavefront reads and writes consecutive
 // elements.  coef32: n x N coefficients (all-zero for a refused blob: its rows come out zero); sroots: the table of the 2 N / c roots (s_k = entry k); out_q32: n x (2 N / c)
 // rows of N scalars; row_st[row] = the status of the row's blob, for the closing kernel
@@ -300,7 +320,7 @@ __global__ void kzg_cell_items_kernel(u32 n, const int8_t* __restrict__ dstc, co
 
 // The running products of N = 4096 take more than the 64 KB a launch may ask for by default.  The limit is a per-device function attribute: set once on every device a launch of
 // `kernel` is made on (as nbls_vm_launch does); the common case, already set, takes no lock.  The flags of the four kernels that ask for it live here
-enum LdsKernel { LDS_EVAL, LDS_QUOTIENT, LDS_NTT, LDS_RECOVER, LDS_KERNELS };
+enum LdsKernel { LDS_EVAL, LDS_QUOTIENT, LDS_NTT, LDS_RECOVER, LDS_NTT_PASS, LDS_NTT_TAIL, LDS_KERNELS };
 int lds_limit(LdsKernel which, const void* kernel) {
   static std::atomic<bool> attr_set[LDS_KERNELS][64];
   static std::mutex attr_mu;
@@ -350,6 +370,31 @@ int nbls_kzg_ntt_launch(unsigned log2_n, unsigned mode, unsigned n, const void* 
   const int e = lds_limit(LDS_NTT, (const void*)kzg_ntt_kernel);
   const u64 out_stride = (u64)(mode == FR_NTT_CELLS ? 64 : 32) << log2_n;
   return e ? e : launch_1d(kzg_ntt_kernel, (u64)n * NT, NT, 32u << log2_n, stream, log2_n, mode, in32, shift32, shift_stride, roots, iroots, out32, out_stride, coef32, status);
+}
+// run R of the global stages of n polynomials of 2^R.log2_n elements (R: fr_nttl_run's; table: the roots, or the inverse roots where `inverse`, of the size the global
+// stages have together; in32 == out32, or disjoint; shift32 / sinv / status may be NULL; flags: n words)
+int nbls_kzg_ntt_pass_launch(const nbls::FrNttRun* run, unsigned inverse, unsigned n, const void* in32, void* out32, const void* shift32, const void* sinv, const void* table,
+                             void* flags, void* status, hipStream_t stream) {
+  if (!n) return 0;
+  const FrNttRun R = *run;
+  if (R.log2_n < 2 || R.log2_n > FR_NTTL_MAX_LOG2 || !R.q || R.q > FR_NTTL_MAX_PASS || !R.c || R.c > FR_NTT_LOG2_LANES || R.q + R.c > FR_NTTL_MAX_TILE || R.j0 + R.q + R.c > R.log2_n ||
+      R.j0 + R.q > 12 || ((u64)n << R.log2_n) > ((u64)1 << FR_NTTL_MAX_LOG2) || !flags || (((uintptr_t)in32 | (uintptr_t)out32) & 15))
+    return (int)hipErrorInvalidValue;
+  const int e = lds_limit(LDS_NTT_PASS, (const void*)kzg_ntt_pass_kernel);
+  return e ? e : launch_1d(kzg_ntt_pass_kernel, ((u64)n << (R.log2_n - R.q - R.c)) * NT, NT, 32u << (R.q + R.c), stream, R, inverse, in32, out32, shift32, sinv, table, flags, status);
+}
+// the 2^log2_k tails of 2^log2_t elements of each of n polynomials (w32: omega_N, or its inverse where `inverse`, as 8 words in Montgomery form; roots / iroots: the
+// tables of size 2^log2_t; sinv: n elements; flags: n words; shift32 and status may be NULL)
+int nbls_kzg_ntt_tail_launch(unsigned log2_t, unsigned log2_k, unsigned inverse, unsigned n, const uint32_t* w32, const void* in32, void* out32, const void* shift32, void* sinv,
+                             const void* roots, const void* iroots, void* flags, void* status, hipStream_t stream) {
+  if (!n) return 0;
+  if (log2_t < 1 || log2_t > FR_NTTL_MAX_TAIL || log2_k < 1 || log2_k > 12 || ((u64)n << (log2_t + log2_k)) > ((u64)1 << FR_NTTL_MAX_LOG2) || !sinv || !flags ||
+      (((uintptr_t)in32 | (uintptr_t)out32) & 15))
+    return (int)hipErrorInvalidValue;
+  Fr w;
+  for (int i = 0; i < FR_NL; i++) w.l[i] = w32[i];
+  const int e = lds_limit(LDS_NTT_TAIL, (const void*)kzg_ntt_tail_kernel);
+  return e ? e : launch_1d(kzg_ntt_tail_kernel, ((u64)n << log2_k) * NT, NT, 32u << log2_t, stream, log2_t, log2_k, inverse, w, in32, out32, shift32, sinv, roots, iroots, flags, status);
 }
 // the quotient rows of n blobs (n << (log2_n + 1) lanes; the table of 2^(log2_n + 1 - log2_cell) roots has at most 2^12 entries)
 int nbls_kzg_cell_rows_launch(unsigned log2_n, unsigned log2_cell, unsigned n, const void* coef32, const void* sroots, const void* blob_st, void* out_q32, void* row_st,

@@ -9,7 +9,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
-namespace nbls { struct KernelArgs; }
+namespace nbls { struct KernelArgs; struct FrNttRun; }
 
 extern "C" {
 // vm_kernel.hip, vm_wide_kernel.hip
@@ -78,6 +78,10 @@ int nbls_kzg_prove_tail_launch(unsigned n, const void* zero, const void* st_a, c
 int nbls_kzg_inv_roots_launch(unsigned log2_n, const void* roots, void* table, hipStream_t stream);
 int nbls_kzg_ntt_launch(unsigned log2_n, unsigned mode, unsigned n, const void* in32, const void* shift32, unsigned shift_stride, const void* roots, const void* iroots,
                         void* out32, void* coef32, void* status, hipStream_t stream);
+int nbls_kzg_ntt_pass_launch(const nbls::FrNttRun* run, unsigned inverse, unsigned n, const void* in32, void* out32, const void* shift32, const void* sinv, const void* table,
+                             void* flags, void* status, hipStream_t stream);
+int nbls_kzg_ntt_tail_launch(unsigned log2_t, unsigned log2_k, unsigned inverse, unsigned n, const uint32_t* w32, const void* in32, void* out32, const void* shift32, void* sinv,
+                             const void* roots, const void* iroots, void* flags, void* status, hipStream_t stream);
 int nbls_kzg_cell_rows_launch(unsigned log2_n, unsigned log2_cell, unsigned n, const void* coef32, const void* sroots, const void* blob_st, void* out_q32, void* row_st,
                               hipStream_t stream);
 int nbls_kzg_fk20_scalars_launch(unsigned log2_n, unsigned log2_cell, unsigned n, const void* coef32, const void* sroots, void* out32, hipStream_t stream);

@@ -101,9 +101,12 @@ enum Slot {
   // the scalars of the MSM over the C_i, the partial rows and the m + 1 sums | the three combined points, the product's final exponentiation | what is read back | everything
   // of one chunk of the per-proof pass (L_i, the final exponentiations, the verdicts)
   SB_G16_POINTS = 82, SB_G16_SCALARS = 83, SB_G16_PAIRS = 84, SB_G16_OUT = 85, SB_G16_ITEMS = 86,
+  // fr_ntt_large_dev (nbls_fr_ntt_large, nbls_fr_ntt_dev; pipelines_kzg_cells.cpp): one flag word per polynomial, cleared on the stream in front of the call's first launch,
+  // then one element per polynomial: the inverse of the caller's shift on the way to the coefficients.  The host-buffer call stages on nbls_fr_ntt's slots (SB_STAGED, SB_KZGC_OUT)
+  SB_NTTL_FLAGS = 87,
   NSB
 };
-static_assert(NSB == 87, "sb[] indices do not shift");
+static_assert(NSB == 88, "sb[] indices do not shift");
 constexpr SlotMask slot_bit(int i) { return (SlotMask)1 << i; }
 template <typename... S> constexpr SlotMask slots(S... s) { return (slot_bit(s) | ...); }
 // one instance of dev_decompress: three arrays of field elements and the exponentiation table
@@ -172,6 +175,9 @@ static_assert(!(M_G16_OWN & (DEC_MAIN.mask() | MSM_RLC.mask() | M_LADDER | M_MSM
               "groth16_pipeline: the decoders, the MSMs (on the slots of MSM_RLC: MSM_MAIN holds SB_STAGED), the ladder and the batched MSM of the per-proof pass regrow their slots while the call holds the staged block and its own");
 static_assert(!((M_G16_OWN & ~slot_bit(SB_STAGED)) & (M_KZGV_OWN | M_KZGF_OWN | M_KZGR_OWN | M_KZGC_OWN | M_KZGP_OWN | M_KZG_OWN | M_POLY_OWN | M_THR_OWN | M_RLC_MAIN | M_RLC_SIDE | M_RLC_SIDE2 | M_VB_MAIN | MSM_MAIN.mask())),
               "groth16_pipeline keeps to slots of its own");
+constexpr SlotMask M_NTTL_OWN = slots(SB_STAGED, SB_KZGC_OUT, SB_NTTL_FLAGS);   // nbls_fr_ntt_large: nbls_fr_ntt's staging and the flags; nbls_fr_ntt_dev touches the flags only
+static_assert(!(slot_bit(SB_NTTL_FLAGS) & (M_G16_OWN | M_KZGV_OWN | M_KZGF_OWN | M_KZGR_OWN | M_KZGC_OWN | M_KZGP_OWN | M_KZG_OWN | M_POLY_OWN | M_THR_OWN | M_RLC_MAIN | M_RLC_SIDE | M_RLC_SIDE2 | M_VB_MAIN | M_LADDER | M_MSMB_OWN | MSM_MAIN.mask() | MSM_RLC.mask())),
+              "the large transform keeps its flags on a slot of its own: a device-resident call leaves them in flight behind it");
 // ---- END scratch slots -------------------------------------------------------------------------------------------------------------------------------------
 #define EXPORT extern "C" __attribute__((visibility("default")))
 extern std::recursive_mutex g_null_mu;   // locked in place of a context's mutex when the caller passed no context (the call then fails with NBLS_EINVAL)
@@ -201,6 +207,8 @@ struct nbls_ctx {
   // the defaults (pipelines_msm.cpp)
   size_t msmb_window = 0, msmb_big = 0, msmb_slab = 0;
   size_t cells_chunk = 0;       // nbls_set_tuning(NBLS_TUNE_CELLS_CHUNK): blobs per pass of nbls_kzg_compute_cells_and_proofs; 0 = as many as the batched MSM takes (pipelines_kzg_cells.cpp)
+  // nbls_set_tuning(NBLS_TUNE_NTT_TAIL_BITS / _PASS_BITS): the log size of the tails of nbls_fr_ntt_large / nbls_fr_ntt_dev and the global stages a launch runs at most; 0 = the defaults (pipelines_kzg_cells.cpp)
+  unsigned ntt_tail_bits = 0, ntt_pass_bits = 0;
   size_t g16_chunk = 0;         // nbls_set_tuning(NBLS_TUNE_G16_CHUNK): proofs per pass of the per-proof pass of nbls_groth16_verify and of nbls_groth16_prepare_inputs; 0 = as many as the batched MSM takes (pipelines_groth16.cpp)
   // scratch (device)
   uint8_t *F = nullptr, *N = nullptr, *NI = nullptr, *io_g1 = nullptr, *io_g2 = nullptr, *io_f12 = nullptr, *one12 = nullptr;

@@ -40,6 +40,72 @@ EXPORT int nbls_fr_ntt(nbls_ctx* ctx, unsigned log2_n, int dir, size_t n, const 
   return io.fetch_to(O, out32, qb, status, n);
 }
 
+// ---- Transforms of up to 2^24 elements a polynomial (fr_exec.h has the split into global stages and tails).  The plan of a call: t = the tails' log size, P = the stages
+// a launch runs at most, both the context's (NBLS_TUNE_NTT_TAIL_BITS / _PASS_BITS) or fr_exec.h's defaults
+static unsigned ntt_tail_bits(const nbls_ctx* ctx) { return ctx->ntt_tail_bits ? ctx->ntt_tail_bits : FR_NTTL_DEFAULT_TAIL; }
+// what both entry points refuse before any device work (the buffers are theirs to look at)
+static bool ntt_large_args(const nbls_ctx* ctx, unsigned log2_n, int dir, size_t n) {
+  return ctx && log2_n >= 1 && log2_n <= FR_NTTL_MAX_LOG2 && (dir == NBLS_NTT_TO_COEFFS || dir == NBLS_NTT_TO_EVALS) && n <= (KZG_MAX_ELEMS >> log2_n) &&
+         (log2_n <= ntt_tail_bits(ctx) || log2_n - ntt_tail_bits(ctx) <= 12);
+}
+// n polynomials on the device, in -> out (equal, or disjoint; 16-byte aligned), on s.  Up to the tails' size: kzg_ntt_kernel as nbls_fr_ntt launches it.  Above: the flags
+// cleared, then the runs and the tails in the direction's order -- the first launch reads `in`, every later one works in place on `out`
+static int fr_ntt_large_dev(nbls_ctx* ctx, unsigned L, int dir, size_t n, const uint8_t* in, const uint8_t* shift, uint8_t* out, int8_t* status, hipStream_t s) {
+  const unsigned t = ntt_tail_bits(ctx), P = ctx->ntt_pass_bits ? ctx->ntt_pass_bits : FR_NTTL_DEFAULT_PASS;
+  const bool inverse = dir == NBLS_NTT_TO_COEFFS;
+  const uint8_t *roots, *iroots, *table; int r;
+  if (L <= t) {
+    if ((r = kzg_table(ctx, KZG_ROOTS, L, 0, s, &roots)) || (r = kzg_table(ctx, KZG_INV_ROOTS, L, 0, s, &iroots))) return r;
+    LAUNCHCHK(nbls_kzg_ntt_launch(L, inverse ? FR_NTT_TO_COEFFS : FR_NTT_TO_EVALS, (unsigned)n, in, shift, 32, roots, iroots, out, nullptr, status, s));
+    return NBLS_OK;
+  }
+  const unsigned K = L - t, runs = fr_nttl_runs(K, P);
+  const size_t fb = (n * 4 + 31) & ~(size_t)31;
+  uint8_t* F;
+  if ((r = need(ctx, SB_NTTL_FLAGS, fb + n * 32, &F)) || (r = kzg_table(ctx, KZG_ROOTS, t, 0, s, &roots)) || (r = kzg_table(ctx, KZG_INV_ROOTS, t, 0, s, &iroots)) ||
+      (r = kzg_table(ctx, inverse ? KZG_INV_ROOTS : KZG_ROOTS, K, 0, s, &table)))
+    return r;
+  uint8_t* SINV = F + fb;
+  const Fr omega = fr_omega(L), w = inverse ? fr_inv(omega) : omega;
+  HIPCHK(hipMemsetAsync(F, 0, fb, s));
+  auto tails = [&](const uint8_t* src) { return nbls_kzg_ntt_tail_launch(t, K, inverse, (unsigned)n, w.l, src, out, shift, SINV, roots, iroots, F, status, s); };
+  auto run = [&](unsigned i, const uint8_t* src) {
+    const FrNttRun R = fr_nttl_run(L, K, P, i);
+    const bool first = R.j0 == 0;   // the run that has stage 0: the caller's shift on the way to the values, its inverse and the status on the way back
+    return nbls_kzg_ntt_pass_launch(&R, inverse, (unsigned)n, src, out, first && !inverse ? shift : nullptr, first && inverse && shift ? SINV : nullptr, table, F,
+                                    first && inverse ? status : nullptr, s);
+  };
+  if (inverse) {
+    LAUNCHCHK(tails(in));
+    for (unsigned i = runs; i-- > 0;) LAUNCHCHK(run(i, out));
+  } else {
+    for (unsigned i = 0; i < runs; i++) LAUNCHCHK(run(i, i ? out : in));
+    LAUNCHCHK(tails(out));
+  }
+  return NBLS_OK;
+}
+EXPORT int nbls_fr_ntt_large(nbls_ctx* ctx, unsigned log2_n, int dir, size_t n, const uint8_t* in32, const uint8_t* shift32, uint8_t* out32, int8_t* status) {
+  WHOLE_CALL(ctx);
+  if (!ntt_large_args(ctx, log2_n, dir, n) || (n && (!in32 || !out32))) return NBLS_EINVAL;
+  if (!n) return NBLS_OK;
+  DEV_ENTER(ctx, nullptr);
+  Staged io(ctx, s);
+  const size_t qb = (n * 32) << log2_n, o_in = io.bytes(in32, qb), o_sh = io.bytes(shift32, shift32 ? n * 32 : 0), back = qb + n;
+  uint8_t *c, *O; int r;
+  if ((r = need(ctx, SB_STAGED, io.in_bytes, &c)) || (r = need(ctx, SB_KZGC_OUT, back, &O)) || (r = io.send(c, back)) ||
+      (r = fr_ntt_large_dev(ctx, log2_n, dir, n, c + o_in, shift32 ? c + o_sh : nullptr, O, (int8_t*)(O + qb), s)))
+    return r;
+  return io.fetch_to(O, out32, qb, status, n);
+}
+EXPORT int nbls_fr_ntt_dev(nbls_ctx* ctx, unsigned log2_n, int dir, size_t n, const void* d_in32, const void* d_shift32, void* d_out32, void* d_status, void* stream) {
+  if (!ntt_large_args(ctx, log2_n, dir, n) || (n && (!d_in32 || !d_out32))) return NBLS_EINVAL;
+  if (!n) return NBLS_OK;
+  const uintptr_t a = (uintptr_t)d_in32, b = (uintptr_t)d_out32, qb = ((uintptr_t)n * 32) << log2_n;
+  if (((a | b) & 15) || (a != b && a < b + qb && b < a + qb)) return NBLS_EINVAL;
+  DEV_ENTER(ctx, stream);
+  return fr_ntt_large_dev(ctx, log2_n, dir, n, (const uint8_t*)d_in32, (const uint8_t*)d_shift32, (uint8_t*)d_out32, (int8_t*)d_status, s);
+}
+
 // mono == NULL and fk == NULL: nbls_kzg_compute_cells (out_proofs unused).  fk != NULL: the FK20 proofs loop.  rec != NULL: the recovery front end -- the blobs come from subsets of their cells (blobs unused)
 struct RecoverIn { const uint32_t *offsets, *index; const uint8_t* cells; };
 struct CellsIn { unsigned log2_n, log2_cell; size_t n; const uint8_t* blobs; const nbls_kzg_monomial* mono; uint8_t *out_cells, *out_proofs; const RecoverIn* rec; const nbls_kzg_fk20* fk = nullptr; };

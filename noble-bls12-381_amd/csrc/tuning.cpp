@@ -146,6 +146,8 @@ EXPORT int nbls_set_tuning(nbls_ctx* ctx, int key, long long value) {
     case NBLS_TUNE_MSMB_SLAB: if (value < 0) return NBLS_EINVAL; ctx->msmb_slab = (size_t)value; return NBLS_OK;
     case NBLS_TUNE_CELLS_CHUNK: if (value < 0) return NBLS_EINVAL; ctx->cells_chunk = (size_t)value; return NBLS_OK;
     case NBLS_TUNE_G16_CHUNK: if (value < 0) return NBLS_EINVAL; ctx->g16_chunk = (size_t)value; return NBLS_OK;
+    case NBLS_TUNE_NTT_TAIL_BITS: if (value < 0 || value > 12) return NBLS_EINVAL; ctx->ntt_tail_bits = (unsigned)value; return NBLS_OK;
+    case NBLS_TUNE_NTT_PASS_BITS: if (value < 0 || value > 9) return NBLS_EINVAL; ctx->ntt_pass_bits = (unsigned)value; return NBLS_OK;
     case NBLS_TUNE_FE_TAIL_CHAIN: if (value < 0 || value > 3) return NBLS_EINVAL; ctx->fe_tail_chain = (unsigned)value; return NBLS_OK;
     default: return NBLS_EINVAL;
   }

@@ -596,6 +596,47 @@ __attribute__((visibility("default"))) int nbls_sim_fr_ntt(unsigned log2_n, int 
   sim_ntt(log2_n, dir == 0 ? FR_NTT_TO_COEFFS : FR_NTT_TO_EVALS, n, in32, shift32, 32, out32, nullptr, status);
   return 0;
 }
+// nbls_fr_ntt_large / nbls_fr_ntt_dev with the plan given (tail_bits / pass_bits 0: the engine's defaults): the bodies of kzg_ntt_pass_kernel and
+// kzg_ntt_tail_kernel, launch after launch, one workgroup after another; out32 may equal in32
+__attribute__((visibility("default"))) int nbls_sim_fr_ntt_large(unsigned log2_n, int dir, size_t n, const uint8_t* in32, const uint8_t* shift32, uint8_t* out32, int8_t* status,
+                                                                 unsigned tail_bits, unsigned pass_bits) {
+  const unsigned t = tail_bits ? tail_bits : FR_NTTL_DEFAULT_TAIL, P = pass_bits ? pass_bits : FR_NTTL_DEFAULT_PASS;
+  if (log2_n < 1 || log2_n > FR_NTTL_MAX_LOG2 || (dir != 0 && dir != 1) || (n && (!in32 || !out32)) || (n << log2_n) > ((size_t)1 << 24) || n > ((size_t)1 << 24) ||
+      t > FR_NTTL_MAX_TAIL || P > FR_NTTL_MAX_PASS || (log2_n > t && log2_n - t > 12))
+    return -1;
+  if (!n) return 0;
+  const bool inverse = dir == 0;
+  if (log2_n <= t) { sim_ntt(log2_n, inverse ? FR_NTT_TO_COEFFS : FR_NTT_TO_EVALS, n, in32, shift32, 32, out32, nullptr, status); return 0; }
+  const unsigned K = log2_n - t, runs = fr_nttl_runs(K, P);
+  const std::vector<Fr> roots = sim_roots(t), iroots = sim_inv_roots(t, roots), groots = sim_roots(K), table = inverse ? sim_inv_roots(K, groots) : groots;
+  const Fr omega = fr_omega(log2_n), w = inverse ? fr_inv(omega) : omega;
+  const size_t row = (size_t)32 << log2_n;
+  std::vector<u32> flags(n, 0), a((size_t)8 << FR_NTTL_MAX_TILE);
+  std::vector<Fr> sinv(n, fr_zero());
+  Fr sh_s = fr_one();
+  auto tails = [&](const uint8_t* src) {
+    for (size_t blk = 0; blk < (n << K); blk++) {
+      const size_t p = blk >> K, off = (blk * 32) << t;
+      kzg_ntt_tail_body(sim_wg<FR_NTT_LANES>(), t, K, inverse, (u32)(blk & ((1u << K) - 1)), w, src + off, out32 + off, shift32 ? shift32 + 32 * p : nullptr, &sinv[p], roots.data(),
+                        iroots.data(), &flags[p], status ? status + p : nullptr, a.data(), &sh_s);
+    }
+  };
+  auto run = [&](unsigned i, const uint8_t* src) {
+    const FrNttRun R = fr_nttl_run(log2_n, K, P, i);
+    const unsigned lt = R.log2_n - R.j0 - R.q - R.c;
+    const bool first = R.j0 == 0;
+    for (size_t wgi = 0; wgi < (n << (lt + R.j0)); wgi++) {
+      const u32 within = (u32)(wgi & ((1u << (lt + R.j0)) - 1));
+      const size_t p = wgi >> (lt + R.j0);
+      kzg_ntt_pass_body(sim_wg<FR_NTT_LANES>(), R, inverse, within >> lt, (within & ((1u << lt) - 1)) << R.c, within == 0, src + row * p, out32 + row * p,
+                        first && !inverse && shift32 ? shift32 + 32 * p : nullptr, first && inverse && shift32 ? &sinv[p] : nullptr, table.data(), &flags[p],
+                        first && inverse && status ? status + p : nullptr, a.data());
+    }
+  };
+  if (inverse) { tails(in32); for (unsigned i = runs; i-- > 0;) run(i, out32); }
+  else { for (unsigned i = 0; i < runs; i++) run(i, i ? out32 : in32); tails(out32); }
+  return 0;
+}
 // nbls_kzg_compute_cells: the cells mode with the shift g for every blob; coef32 (may be NULL): the n x N coefficients the proofs read
 __attribute__((visibility("default"))) int nbls_sim_kzg_cells(unsigned log2_n, size_t n, const uint8_t* blobs, uint8_t* out_cells, uint8_t* coef32, int8_t* status) {
   if (log2_n < 1 || log2_n > 12 || (n && (!blobs || !out_cells)) || (n << log2_n) > ((size_t)1 << 24)) return -1;

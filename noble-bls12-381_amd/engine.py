@@ -93,6 +93,8 @@ def load_library():
     lib.nbls_kzg_compute_proofs.argtypes = [vp, vp, sz, vp, vp, vp, vp, vp]
     lib.nbls_kzg_compute_blob_proofs.argtypes = [vp, vp, sz, vp, vp, vp, vp, vp]
     lib.nbls_fr_ntt.argtypes = [vp, C.c_uint, C.c_int, sz, vp, vp, vp, vp]
+    lib.nbls_fr_ntt_large.argtypes = [vp, C.c_uint, C.c_int, sz, vp, vp, vp, vp]
+    lib.nbls_fr_ntt_dev.argtypes = [vp, C.c_uint, C.c_int, sz, vp, vp, vp, vp, vp]
     lib.nbls_kzg_compute_cells.argtypes = [vp, C.c_uint, C.c_uint, sz, vp, vp, vp]
     lib.nbls_kzg_monomial_create.argtypes = [vp, C.c_uint, vp, vp, C.POINTER(vp)]
     lib.nbls_kzg_monomial_destroy.argtypes = [vp]
@@ -780,6 +782,36 @@ class Engine:
         self._chk(self.lib.nbls_fr_ntt(self.h, log2_n, 1 if to_evals else 0, n, raw, None if shifts is None else b''.join(map(self._fr32, shifts)), out, st))
         o = out.raw
         return [[o[row * i + 32 * j:row * i + 32 * j + 32] for j in range(1 << log2_n)] for i in range(n)], list(st.raw[:n])
+
+    def fr_ntt_large(self, log2_n, polys, to_evals, shifts=None):
+        """fr_ntt for polynomials of up to 2^24 elements (nbls_fr_ntt_large: global stages in front of tails of 2^12 elements; the same bytes as fr_ntt where both apply).
+        polys and shifts as fr_ntt takes them.  Given bytes -> (bytes, status list); given lists -> (list of the 32-byte elements per polynomial, status list)"""
+        as_bytes = isinstance(polys, (bytes, bytearray, memoryview))
+        raw = bytes(polys) if as_bytes else b''.join(self._fr32(v) for f in polys for v in f)
+        row = 32 << log2_n
+        if not 1 <= log2_n <= 24 or len(raw) % row:
+            raise NblsError('fr_ntt_large: log2_n in 1 .. 24 and polynomials of %d bytes each' % row)
+        n = len(raw) // row
+        sh = None if shifts is None else bytes(shifts) if isinstance(shifts, (bytes, bytearray, memoryview)) else b''.join(map(self._fr32, shifts))
+        if sh is not None and len(sh) != 32 * n:
+            raise NblsError('fr_ntt_large: one shift per polynomial or None')
+        out = C.create_string_buffer(max(len(raw), 1)); st = C.create_string_buffer(max(n, 1))
+        self._chk(self.lib.nbls_fr_ntt_large(self.h, log2_n, 1 if to_evals else 0, n, raw, sh, out, st))
+        if as_bytes:
+            return out.raw[:len(raw)], list(st.raw[:n])
+        o = out.raw
+        return [[o[row * i + 32 * j:row * i + 32 * j + 32] for j in range(1 << log2_n)] for i in range(n)], list(st.raw[:n])
+
+    def fr_ntt_dev(self, log2_n, n, d_in, to_evals, d_out, d_shifts=None, d_status=None, stream=None):
+        """nbls_fr_ntt_dev on device addresses (ints, e.g. torch.Tensor.data_ptr()): n polynomials of 2^log2_n elements, d_in -> d_out (equal, or disjoint; 16-byte aligned),
+        d_shifts: n x 32 bytes or None, d_status: n bytes or None, stream: a hipStream_t as an int (None: the context's).  Asynchronous, ordered on the stream"""
+        self._chk(self.lib.nbls_fr_ntt_dev(self.h, log2_n, 1 if to_evals else 0, n, d_in, d_shifts, d_out, d_status, stream))
+
+    def set_ntt_plan(self, tail_bits=None, pass_bits=None):
+        """the plan of fr_ntt_large / fr_ntt_dev: the log size of the tails (NBLS_TUNE_NTT_TAIL_BITS = 26; 1 .. 12, 0: the default 12) and the global stages a launch runs at
+        most (NBLS_TUNE_NTT_PASS_BITS = 27; 1 .. 9, 0: the default).  The bytes do not depend on either"""
+        if tail_bits is not None: self._chk(self.lib.nbls_set_tuning(self.h, 26, int(tail_bits)))
+        if pass_bits is not None: self._chk(self.lib.nbls_set_tuning(self.h, 27, int(pass_bits)))
 
     def kzg_monomial_setup(self, log2_n, monomial48):
         """monomial48: the 2^log2_n compressed points [tau^i]G1 of the setup in natural order (a list of 48-byte values or their concatenation) -> KzgMonomialSetup, usable
