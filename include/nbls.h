@@ -642,6 +642,7 @@ const char* nbls_config_describe(void);   /* "NBLS_X=value(env|default) ...": ev
    Then nbls_kzg_fk20_create / _destroy / _params, nbls_kzg_compute_cells_and_proofs_fk20, nbls_kzg_recover_cells_and_proofs_fk20, the name "endo_g1" of nbls_extra_program_kernel, scratch slots 80 .. 81 (additions only, same version). Then nbls_groth16_vk_create / _destroy / _inputs,
    nbls_groth16_verify, nbls_groth16_prepare_inputs, nbls_groth16_input_sums, NBLS_ST_G16_C, NBLS_TUNE_G16_CHUNK, scratch slots 82 .. 86 (additions only, same version).
    Then NBLS_TUNE_FE_TAIL_CHAIN, nbls_chain_launches and the name "fe_final12" of nbls_extra_program_kernel (additions only, same version).
+   Then NBLS_TUNE_FE_HEAD_CHAIN, NBLS_TUNE_INV_PRIO and the name "fe_easy12" of nbls_extra_program_kernel (additions only, same version).
    Then nbls_fr_ntt_large, nbls_fr_ntt_dev, NBLS_TUNE_NTT_TAIL_BITS / _PASS_BITS, scratch slot 87 (additions only, same version).
    4 (round 6): nbls_hw_queues, NBLS_TUNE_WIDE_MAX, NBLS_TUNE_H2C_NORM_MIN, NBLS_TUNE_INV_WIDE_MAX, NBLS_TUNE_LS_MAX / _LS2_MAX (additions only); the library sets GPU_MAX_HW_QUEUES = 22 at load when the variable is unset (see nbls_pool_init below).
    3 (round 5): nbls_program_kernel, nbls_pool_*, nbls_sign_batch_dev, NBLS_TUNE_VERIFY_* / _SAC_MAX / _PT_LS2_MAX (additions only); nbls_verify_batch_partial_dev writes d_out_fp12 even when it reports a zero point or a decode error
@@ -724,9 +725,11 @@ int nbls_field_kernel_raw(nbls_ctx* ctx, int kind, int form, size_t n, const uin
 #define NBLS_TUNE_MSMB_SLAB 18        /* budget of one slab of groups: sum over its groups of (points after the split) * windows + windows * c * 2^(c - 1), the sorted entries and gathered bucket points that are in scratch at a time; a group that exceeds it alone is a slab of its own (default 2^23; 0 = the default) */
 #define NBLS_TUNE_CELLS_CHUNK 20      /* (19 stays unassigned: tests/test_msm_batch_abi.py pins it as the first unknown key behind the batched MSM's) blobs that nbls_kzg_compute_cells_and_proofs hands to the batched MSM in one pass; 0 (default) = as many whole blobs as its bounds of 2^22 scalars and 2^20 rows take (8 mainnet blobs); a larger value than that changes nothing.  The bytes do not depend on it: it lets a test cross chunk borders with small blobs */
 #define NBLS_TUNE_G16_CHUNK 22        /* (21 stays unassigned: tests/test_kzg_fk20_abi.py pins it as the first unknown key behind NBLS_TUNE_CELLS_CHUNK) proofs that the per-proof pass of nbls_groth16_verify and nbls_groth16_prepare_inputs hand to the batched MSM in one pass; 0 (default) = as many whole proofs as its bounds of 2^22 scalars and 2^20 rows take; a larger value than that changes nothing.  The bytes do not depend on it: it lets a test cross chunk borders with few proofs */
-#define NBLS_TUNE_FE_TAIL_CHAIN 24     /* (23 stays unassigned: tests/test_groth16_abi.py pins it as the first unknown key behind NBLS_TUNE_G16_CHUNK) a final exponentiation that runs launch by launch (a pool context, the halves of a large call) ends short programs inside the launch of the cyclotomic exponentiation before them, for the same items: bit 0 the final product (EXPX + FE_FINAL are one launch), bit 1 FE_MID1 and FE_MID2 likewise; 13 launches per pairing batch become 12 (1), 10 (3).  The bytes do not depend on it.  Default 0 (environment: NBLS_FE_TAIL_CHAIN); nbls_pool_init sets 3 on its contexts, whose streams may share hardware queues: there every launch boundary drains a queue */
+#define NBLS_TUNE_FE_TAIL_CHAIN 24     /* (23 stays unassigned: tests/test_groth16_abi.py pins it as the first unknown key behind NBLS_TUNE_G16_CHUNK) a final exponentiation that runs launch by launch (a pool context, the halves of a large call) ends short programs inside the launch of the cyclotomic exponentiation before them, for the same items: bit 0 the final product (EXPX + FE_FINAL are one launch), bit 1 FE_MID1 and FE_MID2 likewise; 12 launches per pairing batch become 11 (1), 9 (3).  The bytes do not depend on it.  Default 0 (environment: NBLS_FE_TAIL_CHAIN); nbls_pool_init sets 3 on its contexts, whose streams may share hardware queues: there every launch boundary drains a queue */
 #define NBLS_TUNE_NTT_TAIL_BITS 26    /* (25 stays unassigned: tests/test_fr_ntt_large_abi.py pins it as the first unknown key behind NBLS_TUNE_FE_TAIL_CHAIN) t, the log size of the tails of nbls_fr_ntt_large / nbls_fr_ntt_dev: 1 .. 12; 0 (default) = 12.  A transform of 2^log2_n elements with log2_n > t runs log2_n - t <= 12 global stages in front of (behind, on the way back) 2^(log2_n - t) transforms of size 2^t.  The bytes do not depend on it: it lets a test drive the split at sizes where Python integers are the oracle */
 #define NBLS_TUNE_NTT_PASS_BITS 27    /* P, the global stages one launch of the same calls runs at most: 1 .. 9 (nine stages of rows of 8 elements fill the LDS tile of 2^12 elements); 0 (default) = 8.  The log2_n - t global stages are cut into ceil((log2_n - t) / P) runs whose lengths differ by one at most.  The bytes do not depend on it (28 stays unassigned) */
+#define NBLS_TUNE_FE_HEAD_CHAIN 29     /* (25 and 28 stay unassigned: tests pin them as the first unknown keys of their time) 0 / 1: such a final exponentiation runs the easy part at the head of the first exponentiation's launch (FE_EASY + EXPX are one launch, and FE_MID1 with them under bit 1 of NBLS_TUNE_FE_TAIL_CHAIN) instead of as a launch of its own: 9 launches per pairing batch become 8.  The bytes do not depend on it.  Default 0 (environment: NBLS_FE_HEAD_CHAIN); nbls_pool_init sets 1 on its contexts */
+#define NBLS_TUNE_INV_PRIO 30          /* 0 .. 3: the issue priority of the wavefronts of the one-element-per-lane Fp inversion kernel (launches above NBLS_TUNE_INV_WIDE_MAX elements); a wavefront of higher priority wins the arbitration for VALU issue against those of other launches on its SIMD.  The bytes do not depend on it.  Default 0 (environment: NBLS_INV_PRIO); nbls_pool_init sets its contexts' (nbls_multi.cpp POOL_INV_PRIO) */
 int nbls_set_tuning(nbls_ctx* ctx, int key, long long value);
 int nbls_program_count(void);                 /* number of step programs; timing slot nbls_program_count() = the inversion kernel */
 const char* nbls_program_name(int prog);

@@ -24,57 +24,58 @@
 #include "vm.h"
 #include "programs.h"
 
-// Ahead-of-time kernels: X(kernel name, up to four ProgIds it serves; P_COUNT = none).  A kernel's signature table is the union over its programs; programs that
+// Ahead-of-time kernels: X(part, kernel name, up to five ProgIds it serves; P_COUNT = none).  A kernel's signature table is the union over its programs; programs that
 // share a kernel (and the lanes per item) can run as a CHAIN -- one launch that executes them back to back for the same items, values passing through the same
 // HBM scratch as between separate launches but without a grid-wide boundary: the seven launches EXPX, FE_MID1, EXPX x 3, FE_MID2, EXPX in the middle of a final
 // exponentiation (math.ts:862-867) are one.  A program outside ProgId joins a row as extra_key(its ExtraProg) (programs.h): the final product in its chainable form
-// (XP_FE_FINAL12) is the fourth program of `expx`, so that the last exponentiation and the product are one launch (pipelines_pairing.cpp final_exp_pipeline).
+// (XP_FE_FINAL12) is the fourth program of `expx`, so that the last exponentiation and the product are one launch, and the easy part in its chainable form (XP_FE_EASY12) the
+// fifth, so that the easy part and the first exponentiation are one (pipelines_pairing.cpp final_exp_pipeline).
 #define NBLS_AOT_PARTS 8   /* aot_kernel.hip is compiled once per part (Makefile): X's first argument is the part that holds the kernel's device code */
-#define NBLS_AOT_KERNELS(X)                                                  \
-  X(0, expx, P_EXPX, P_FE_MID1, P_FE_MID2, extra_key(XP_FE_FINAL12))         \
-  X(0, acc_fe, P_ACC_FE, P_ACC_RAW, P_ACC_BYTES, P_COUNT)                    \
-  X(0, lines_pq, P_LINES_PQ, P_COUNT, P_COUNT, P_COUNT)                      \
-  X(0, acc4_raw, P_ACC4_RAW, P_ACC8_RAW, P_ACC2_RAW, P_COUNT)                \
-  X(1, fe_easy, P_FE_EASY, P_COUNT, P_COUNT, P_COUNT)                        \
-  X(1, fe_final, P_FE_FINAL, P_COUNT, P_COUNT, P_COUNT)                      \
-  X(1, miller_fe, P_MILLER_FE, P_MILLER_RAW, P_MILLER_BYTES, P_COUNT)        \
-  X(1, mul2, P_MUL2, P_MUL2S, P_COUNT, P_COUNT)                             \
-  X(1, norm, P_NORM_RAW, P_NORM_BYTES, P_RAW_TO_BYTES, P_COUNT)              \
-  X(2, h2c_a, P_H2C_A, P_COUNT, P_COUNT, P_COUNT)                            \
-  X(2, h2c_b, P_H2C_B1, P_H2C_B2, P_COUNT, P_COUNT)                          \
-  X(2, h2c_c1, P_H2C_C1, P_H2C_C0, P_COUNT, P_COUNT)                         \
-  X(2, h2c_c2, P_H2C_C2, P_COUNT, P_COUNT, P_COUNT)                          \
-  X(2, g1_dec, P_G1_DEC_A, P_G1_DEC_B, P_COUNT, P_COUNT)                     \
-  X(2, g2_dec, P_G2_DEC_A, P_G2_DEC_B, P_COUNT, P_COUNT)                     \
-  X(2, g2_to_affine, P_G2_TO_AFFINE, P_G2_NORM, P_G2_TO_PROJ, P_G2_ADD2)     \
-  X(3, g2_mul, P_G2_MUL, P_G2_MUL_W3, P_G2_MUL_GLS, P_G2_MUL_SAC)         \
-  X(3, g1_mul, P_G1_MUL, P_G1_MUL_W3, P_G1_MUL_FIXED, P_G1_MUL64)               \
-  X(4, g1_validate, P_G1_VALIDATE, P_COUNT, P_COUNT, P_COUNT)                \
-  X(4, g2_validate, P_G2_VALIDATE, P_COUNT, P_COUNT, P_COUNT)                \
-  X(4, g1_sum, P_G1_TO_PROJ, P_G1_ADD2, P_G1_NORM, P_G1_TO_AFFINE)           \
-  X(5, g1_msm, P_G1_ADD_AB, P_G1_HORNER, P_G1_SHIFTADD, P_G1_MSM_PREP)       \
-  X(5, g2_msm, P_G2_ADD_AB, P_G2_HORNER, P_G2_SHIFTADD, P_G2_MSM_PREP)       \
-  X(6, lines_q, P_LINES_Q, P_ACC_Q, P_LINES_BYTES, P_LINES_FROM_BYTES)       \
-  X(6, miller_raw2, P_MILLER_RAW2, P_COUNT, P_COUNT, P_COUNT)                \
-  X(6, g2_dec192, P_G2_DEC_A192, P_G2_DEC_B192, P_G2_DEC_B_HEX, P_G2_SWAP)   \
-  X(6, from_raw, P_G1_FROM_RAW, P_G2_FROM_RAW, P_G1_COMPRESS, P_G2_COMPRESS) \
-  X(7, h2c1, P_H2C1_A, P_H2C1_B, P_ENC1_A, P_ENC1_B)                         \
-  X(7, g1_clear, P_G1_CLEAR, P_COUNT, P_COUNT, P_COUNT)                      \
-  X(7, enc2, P_ENC2_A, P_ENC2_B, P_COUNT, P_COUNT)                            \
-  X(4, h2c_n, P_H2C_NA, P_H2C_NM, P_H2C_NB, P_COUNT)
+#define NBLS_AOT_KERNELS(X)                                                             \
+  X(0, expx, P_EXPX, P_FE_MID1, P_FE_MID2, extra_key(XP_FE_FINAL12), extra_key(XP_FE_EASY12)) \
+  X(0, acc_fe, P_ACC_FE, P_ACC_RAW, P_ACC_BYTES, P_COUNT, P_COUNT)                      \
+  X(0, lines_pq, P_LINES_PQ, P_COUNT, P_COUNT, P_COUNT, P_COUNT)                        \
+  X(0, acc4_raw, P_ACC4_RAW, P_ACC8_RAW, P_ACC2_RAW, P_COUNT, P_COUNT)                  \
+  X(1, fe_easy, P_FE_EASY, P_COUNT, P_COUNT, P_COUNT, P_COUNT)                          \
+  X(1, fe_final, P_FE_FINAL, P_COUNT, P_COUNT, P_COUNT, P_COUNT)                        \
+  X(1, miller_fe, P_MILLER_FE, P_MILLER_RAW, P_MILLER_BYTES, P_COUNT, P_COUNT)          \
+  X(1, mul2, P_MUL2, P_MUL2S, P_COUNT, P_COUNT, P_COUNT)                                \
+  X(1, norm, P_NORM_RAW, P_NORM_BYTES, P_RAW_TO_BYTES, P_COUNT, P_COUNT)                \
+  X(2, h2c_a, P_H2C_A, P_COUNT, P_COUNT, P_COUNT, P_COUNT)                              \
+  X(2, h2c_b, P_H2C_B1, P_H2C_B2, P_COUNT, P_COUNT, P_COUNT)                            \
+  X(2, h2c_c1, P_H2C_C1, P_H2C_C0, P_COUNT, P_COUNT, P_COUNT)                           \
+  X(2, h2c_c2, P_H2C_C2, P_COUNT, P_COUNT, P_COUNT, P_COUNT)                            \
+  X(2, g1_dec, P_G1_DEC_A, P_G1_DEC_B, P_COUNT, P_COUNT, P_COUNT)                       \
+  X(2, g2_dec, P_G2_DEC_A, P_G2_DEC_B, P_COUNT, P_COUNT, P_COUNT)                       \
+  X(2, g2_to_affine, P_G2_TO_AFFINE, P_G2_NORM, P_G2_TO_PROJ, P_G2_ADD2, P_COUNT)       \
+  X(3, g2_mul, P_G2_MUL, P_G2_MUL_W3, P_G2_MUL_GLS, P_G2_MUL_SAC, P_COUNT)              \
+  X(3, g1_mul, P_G1_MUL, P_G1_MUL_W3, P_G1_MUL_FIXED, P_G1_MUL64, P_COUNT)              \
+  X(4, g1_validate, P_G1_VALIDATE, P_COUNT, P_COUNT, P_COUNT, P_COUNT)                  \
+  X(4, g2_validate, P_G2_VALIDATE, P_COUNT, P_COUNT, P_COUNT, P_COUNT)                  \
+  X(4, g1_sum, P_G1_TO_PROJ, P_G1_ADD2, P_G1_NORM, P_G1_TO_AFFINE, P_COUNT)             \
+  X(5, g1_msm, P_G1_ADD_AB, P_G1_HORNER, P_G1_SHIFTADD, P_G1_MSM_PREP, P_COUNT)         \
+  X(5, g2_msm, P_G2_ADD_AB, P_G2_HORNER, P_G2_SHIFTADD, P_G2_MSM_PREP, P_COUNT)         \
+  X(6, lines_q, P_LINES_Q, P_ACC_Q, P_LINES_BYTES, P_LINES_FROM_BYTES, P_COUNT)         \
+  X(6, miller_raw2, P_MILLER_RAW2, P_COUNT, P_COUNT, P_COUNT, P_COUNT)                  \
+  X(6, g2_dec192, P_G2_DEC_A192, P_G2_DEC_B192, P_G2_DEC_B_HEX, P_G2_SWAP, P_COUNT)     \
+  X(6, from_raw, P_G1_FROM_RAW, P_G2_FROM_RAW, P_G1_COMPRESS, P_G2_COMPRESS, P_COUNT)   \
+  X(7, h2c1, P_H2C1_A, P_H2C1_B, P_ENC1_A, P_ENC1_B, P_COUNT)                           \
+  X(7, g1_clear, P_G1_CLEAR, P_COUNT, P_COUNT, P_COUNT, P_COUNT)                        \
+  X(7, enc2, P_ENC2_A, P_ENC2_B, P_COUNT, P_COUNT, P_COUNT)                             \
+  X(4, h2c_n, P_H2C_NA, P_H2C_NM, P_H2C_NB, P_COUNT, P_COUNT)
 
 // Lane-split kernels (latency form for launches of at most one wavefront per SIMD): ONE item per wavefront, every K_DOT lane-op spread over four adjacent
 // lanes that each accumulate a share of its products; the 28 columns are summed across the four lanes (two DPP stages) before the one reduction on the first of them.
-#define NBLS_AOT_LS_KERNELS(X)                                                              \
-  X(7, expx_ls, P_EXPX_LS, P_COUNT, P_COUNT, P_COUNT)                                      \
-  X(3, miller_ls, P_MILLER_FE_LS, P_MILLER_RAW_LS, P_MILLER_BYTES_LS, P_COUNT)
+#define NBLS_AOT_LS_KERNELS(X)                                                          \
+  X(7, expx_ls, P_EXPX_LS, P_COUNT, P_COUNT, P_COUNT, P_COUNT)                          \
+  X(3, miller_ls, P_MILLER_FE_LS, P_MILLER_RAW_LS, P_MILLER_BYTES_LS, P_COUNT, P_COUNT)
 
 // Two-lane split (round 5): launches of 1025 .. 2048 items -- at most one wavefront per SIMD with TWO items per wavefront --, every K_DOT lane-op on two adjacent lanes, ONE DPP
 // stage.  Round 3 costed this form from the interpreter's numbers and left it; on the specialised kernels 2048 pairings take 1.9 instead of 2.17 ms (profiles/round5_ab_ls2.txt).
-#define NBLS_AOT_LS2_KERNELS(X)                                                             \
-  X(4, expx_ls2, P_EXPX_LS2, P_COUNT, P_COUNT, P_COUNT)                                    \
-  X(5, miller_ls2, P_MILLER_FE_LS2, P_MILLER_RAW_LS2, P_MILLER_BYTES_LS2, P_COUNT)                    \
-  X(6, g2pt_ls2, P_H2C_C1_LS2, P_H2C_C2_LS2, P_G2_MUL_SAC_LS2, P_COUNT)
+#define NBLS_AOT_LS2_KERNELS(X)                                                         \
+  X(4, expx_ls2, P_EXPX_LS2, P_COUNT, P_COUNT, P_COUNT, P_COUNT)                        \
+  X(5, miller_ls2, P_MILLER_FE_LS2, P_MILLER_RAW_LS2, P_MILLER_BYTES_LS2, P_COUNT, P_COUNT) \
+  X(6, g2pt_ls2, P_H2C_C1_LS2, P_H2C_C2_LS2, P_G2_MUL_SAC_LS2, P_COUNT, P_COUNT)
 
 // Kernels of the programs outside ProgId (programs.h ExtraProg): X(part, kernel name, two ExtraProgs it serves; XP_COUNT = none).  The Horner steps of nbls_g*_poly_eval, each
 // kernel serving the short and the full form of its group; the doubling-and-add steps of the batched MSM (pipelines_msm.cpp), one kernel per group; the line program of

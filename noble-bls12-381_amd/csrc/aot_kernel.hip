@@ -86,7 +86,7 @@ __device__ __forceinline__ void aot_body(const AotArgs& ka, Dispatch&& dispatch)
 #if !defined(NBLS_AOT_PART)
 #define NBLS_AOT_PART 0
 #endif
-#define AOT_DECL(PART, NAME, P0, P1, P2, P3) extern "C" __global__ void nbls_aot_##NAME(AotArgs ka);
+#define AOT_DECL(PART, NAME, P0, P1, P2, P3, P4) extern "C" __global__ void nbls_aot_##NAME(AotArgs ka);
 NBLS_AOT_KERNELS(AOT_DECL)
 NBLS_AOT_LS_KERNELS(AOT_DECL)
 NBLS_AOT_LS2_KERNELS(AOT_DECL)
@@ -110,17 +110,17 @@ NBLS_AOT_EXTRA_KERNELS(AOT_DECL_EXTRA)
 
 #if NBLS_AOT_PART == 0
 namespace nbls {
-#define AOT_TABLE(PART, NAME, P0, P1, P2, P3) static const AotSig sigs_##NAME[] = {AOT_SIGS_##NAME(AOT_ROW)};
+#define AOT_TABLE(PART, NAME, P0, P1, P2, P3, P4) static const AotSig sigs_##NAME[] = {AOT_SIGS_##NAME(AOT_ROW)};
 NBLS_AOT_KERNELS(AOT_TABLE)
 NBLS_AOT_LS_KERNELS(AOT_TABLE)
 NBLS_AOT_LS2_KERNELS(AOT_TABLE)
 #define AOT_TABLE_EXTRA(PART, NAME, E0, E1) static const AotSig sigs_##NAME[] = {AOT_SIGS_##NAME(AOT_ROW)};
 NBLS_AOT_EXTRA_KERNELS(AOT_TABLE_EXTRA)
-struct AotKernel { int prog_id[4]; const void* fn; const AotSig* sigs; unsigned nsigs; const char* name; };
-#define AOT_ENTRY(PART, NAME, P0, P1, P2, P3) {{(int)P0, (int)P1, (int)P2, (int)P3}, (const void*)nbls_aot_##NAME, sigs_##NAME, (unsigned)(sizeof(sigs_##NAME) / sizeof(AotSig)), "nbls_aot_" #NAME},
+struct AotKernel { int prog_id[5]; const void* fn; const AotSig* sigs; unsigned nsigs; const char* name; };
+#define AOT_ENTRY(PART, NAME, P0, P1, P2, P3, P4) {{(int)P0, (int)P1, (int)P2, (int)P3, (int)P4}, (const void*)nbls_aot_##NAME, sigs_##NAME, (unsigned)(sizeof(sigs_##NAME) / sizeof(AotSig)), "nbls_aot_" #NAME},
 // a program outside ProgId (programs.h ExtraProg) is entered as P_COUNT + 1 + its number: nbls_aot_index never finds it, nbls_aot_extra_index does
 #define AOT_XP(E) ((int)E == (int)XP_COUNT ? (int)P_COUNT : (int)P_COUNT + 1 + (int)E)
-#define AOT_ENTRY_EXTRA(PART, NAME, E0, E1) {{AOT_XP(E0), AOT_XP(E1), (int)P_COUNT, (int)P_COUNT}, (const void*)nbls_aot_##NAME, sigs_##NAME, (unsigned)(sizeof(sigs_##NAME) / sizeof(AotSig)), "nbls_aot_" #NAME},
+#define AOT_ENTRY_EXTRA(PART, NAME, E0, E1) {{AOT_XP(E0), AOT_XP(E1), (int)P_COUNT, (int)P_COUNT, (int)P_COUNT}, (const void*)nbls_aot_##NAME, sigs_##NAME, (unsigned)(sizeof(sigs_##NAME) / sizeof(AotSig)), "nbls_aot_" #NAME},
 static const AotKernel g_kernels[] = {NBLS_AOT_KERNELS(AOT_ENTRY) NBLS_AOT_LS_KERNELS(AOT_ENTRY) NBLS_AOT_LS2_KERNELS(AOT_ENTRY) NBLS_AOT_EXTRA_KERNELS(AOT_ENTRY_EXTRA)};
 static const int g_nkernels = (int)(sizeof(g_kernels) / sizeof(g_kernels[0]));
 
@@ -128,12 +128,12 @@ static const int g_nkernels = (int)(sizeof(g_kernels) / sizeof(g_kernels[0]));
 
 extern "C" int nbls_aot_index(int prog_id) {
   if (prog_id < 0 || prog_id >= (int)nbls::P_COUNT) return -1;
-  for (int k = 0; k < nbls::g_nkernels; k++) for (int j = 0; j < 4; j++) if (nbls::g_kernels[k].prog_id[j] == prog_id) return k;
+  for (int k = 0; k < nbls::g_nkernels; k++) for (int j = 0; j < 5; j++) if (nbls::g_kernels[k].prog_id[j] == prog_id) return k;
   return -1;
 }
 extern "C" int nbls_aot_extra_index(int extra_prog) {
   if (extra_prog < 0 || extra_prog >= (int)nbls::XP_COUNT) return -1;
-  for (int k = 0; k < nbls::g_nkernels; k++) for (int j = 0; j < 4; j++) if (nbls::g_kernels[k].prog_id[j] == (int)nbls::P_COUNT + 1 + extra_prog) return k;
+  for (int k = 0; k < nbls::g_nkernels; k++) for (int j = 0; j < 5; j++) if (nbls::g_kernels[k].prog_id[j] == (int)nbls::P_COUNT + 1 + extra_prog) return k;
   return -1;
 }
 extern "C" int nbls_aot_private_bytes(int k) {

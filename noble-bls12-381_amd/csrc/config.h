@@ -11,4 +11,7 @@ std::string env_describe();                   // "NAME=value (env|default) ..." 
 // NBLS_FE_TAIL_CHAIN (include/nbls.h NBLS_TUNE_FE_TAIL_CHAIN) when the environment has it, else what the caller gives for its kind of context.  A switch keeps the default of
 // its first reader, so the single context's 0 (nbls_internal.h) and the pool's value (nbls_multi.cpp) go through this one reader
 inline unsigned fe_tail_chain_default(unsigned unset) { const long v = env_long("NBLS_FE_TAIL_CHAIN", -1); return v < 0 ? unset : (unsigned)v & 3u; }
+// NBLS_FE_HEAD_CHAIN (NBLS_TUNE_FE_HEAD_CHAIN) and NBLS_INV_PRIO (NBLS_TUNE_INV_PRIO) likewise: the single context's 0 and the pool's values through one reader each
+inline unsigned fe_head_chain_default(unsigned unset) { const long v = env_long("NBLS_FE_HEAD_CHAIN", -1); return v < 0 ? unset : (unsigned)v & 1u; }
+inline unsigned inv_prio_default(unsigned unset) { const long v = env_long("NBLS_INV_PRIO", -1); return v < 0 ? unset : (unsigned)v & 3u; }
 }  // namespace nbls

@@ -19,7 +19,7 @@ int nbls_fp_inv_wide_launch(unsigned n, const void* in, void* out, hipStream_t s
 // g1_wide.h: `sums` times sum_w 2^(shift w) S_w over nwin points, one wavefront each
 int nbls_g1_wide_combine_launch(const void* S, int nwin, int shift, void* out, unsigned sums, hipStream_t stream);
 // pow_kernels.hip
-int nbls_fp_inv_launch(unsigned n, const void* in, void* out, hipStream_t stream);
+int nbls_fp_inv_launch(unsigned n, const void* in, void* out, unsigned prio, hipStream_t stream);   // prio: issue priority of the launch's wavefronts, 0 .. 3
 int nbls_fp_pow_launch(unsigned n, const void* in, void* out, const uint8_t* ops, int nops, void* scratch, int is_fp2, hipStream_t stream);
 int nbls_pow_wide_launch(unsigned n, const void* in, void* out, const uint8_t* ops, int nops, int is_fp2, hipStream_t stream);
 int nbls_flag_compact_launch(unsigned n, const void* flags, uint32_t* list, uint32_t* count, hipStream_t stream);

@@ -271,6 +271,9 @@ struct nbls_ctx {
   // nbls_set_tuning(NBLS_TUNE_FE_TAIL_CHAIN): which short programs of a final exponentiation that runs launch by launch end inside the launch of the exponentiation before
   // them (final_exp_pipeline: bit 0 the final product, bit 1 FE_MID1 / FE_MID2).  0 for a single context, whose chained middle is one launch already; nbls_pool_init sets it
   unsigned fe_tail_chain = fe_tail_chain_default(0);
+  // nbls_set_tuning(NBLS_TUNE_FE_HEAD_CHAIN): such a final exponentiation runs the easy part at the head of the first exponentiation's launch (XP_FE_EASY12) instead of as a
+  // launch of P_FE_EASY; nbls_set_tuning(NBLS_TUNE_INV_PRIO): issue priority 0 .. 3 of the wavefronts of nbls_fp_inv_kernel (run_inv_buf).  0 for a single context; nbls_pool_init sets them
+  unsigned fe_head_chain = fe_head_chain_default(0), inv_prio = inv_prio_default(0);
   unsigned long long chain_launches = 0;   // launches that ran more than one program (run_chain's fused path), nbls_chain_launches: a test tells a chain from its fallback by it
   u32* qp_table = nullptr;      // multiples of p for the weak reduction (vm_exec.h weak_reduce), device copy
   // kzg_table (kzg_common.cpp): the device tables of kzg_kernels.hip, Montgomery form, 32 bytes an entry, built on first use and freed with the context.  [k]: the 2^k roots of unity in bit-reversed order;

@@ -243,8 +243,8 @@ EXPORT int nbls_multi_verify_batch(nbls_multi* m, size_t n, const uint8_t* sig96
 // batches keeps several calls in flight on contexts of their own.  Round 4 had this only as a Python helper (noble-bls12-381_amd/pipeline.py) and in the JS facade; the pool is
 // the same thing behind the C ABI: `depth` contexts, each with its own stream and scratch, tuned for overlapping calls (the two-program Miller loop at every size, the
 // final exponentiation launch by launch, not as a chained middle: what counts with other calls' wavefronts on the SIMDs is the instruction count and fine launches -- a batch
-// is LINES_FE, ACC_FE, the inversion, FE_EASY, then EXPX + FE_MID1, EXPX, EXPX, EXPX + FE_MID2 and EXPX + the final product, each pair ONE launch: 10 launches;
-// POOL_FE_TAIL_CHAIN below), fed round-robin.
+// is LINES_FE, ACC_FE, the inversion, then FE_EASY + EXPX + FE_MID1, EXPX, EXPX, EXPX + FE_MID2 and EXPX + the final product, each sum ONE launch: 8 launches, three of
+// them chains; POOL_FE_TAIL_CHAIN and POOL_FE_HEAD_CHAIN below), fed round-robin.
 // nbls_pool_pairing_batch_dev enqueues and returns; results are complete after nbls_pool_synchronize (or a synchronisation of the device by the caller).
 //
 // Hardware queues (round 6).  The HIP runtime maps a process's streams onto GPU_MAX_HW_QUEUES hardware queues (default 4), read ONCE when the runtime initialises; with fewer
@@ -259,6 +259,11 @@ EXPORT int nbls_multi_verify_batch(nbls_multi* m, size_t n, const uint8_t* sig96
 // are +2 % there (2.56 -> 2.62 M pairings/s; the final product alone, one boundary, is within the spread), and with a queue per stream the form costs
 // nothing (3.09 -> 3.10 M).  Chaining the long exponentiations themselves loses 3 % on four queues: coarse launches.  EXPERIMENTS.md, profiles/fe_tail_chain_ab.json.
 static const unsigned POOL_FE_TAIL_CHAIN = 3;
+// The two short launches left after that, the easy part and the inversion, carry 3 % of a batch's instructions and held their queue for 8 % of its time: each starts as the
+// youngest wavefront on its SIMD and gets the issue slots the other queues' long-running wavefronts leave.  The easy part runs at the head of the first exponentiation's
+// launch (NBLS_TUNE_FE_HEAD_CHAIN; NBLS_FE_HEAD_CHAIN overrides); the inversion stays a launch -- folded into a step kernel every wavefront would execute the whole binary
+// GCD for its five items -- and its wavefronts take a raised issue priority (NBLS_TUNE_INV_PRIO; NBLS_INV_PRIO overrides).  EXPERIMENTS.md, profiles/fe_head_chain_ab.json.
+static const unsigned POOL_FE_HEAD_CHAIN = 1, POOL_INV_PRIO = 1;
 static int g_queues_set_by_library = 0;
 __attribute__((constructor)) static void nbls_on_load() {
   if (getenv("NBLS_KEEP_HW_QUEUES")) return;
@@ -295,6 +300,8 @@ EXPORT int nbls_pool_init(int device_id, int depth, nbls_pool** out) {
       if (nbls::env_long("NBLS_PIPELINE_CHAIN", 0) != 1) nbls_set_tuning(c, NBLS_TUNE_CHAIN_MAX, 0);
       nbls_set_tuning(c, NBLS_TUNE_LS_MAX, 0); nbls_set_tuning(c, NBLS_TUNE_LS2_MAX, 0);      // the lane-split forms too: with calls side by side the plain programs carry more (1024-pair calls: 1.52 -> 1.95 M pairings/s)
       nbls_set_tuning(c, NBLS_TUNE_FE_TAIL_CHAIN, nbls::fe_tail_chain_default(POOL_FE_TAIL_CHAIN));
+      nbls_set_tuning(c, NBLS_TUNE_FE_HEAD_CHAIN, nbls::fe_head_chain_default(POOL_FE_HEAD_CHAIN));
+      nbls_set_tuning(c, NBLS_TUNE_INV_PRIO, nbls::inv_prio_default(POOL_INV_PRIO));
       nbls_set_tuning(c, NBLS_TUNE_INV_WIDE_MAX, 256);      // contexts kept busy side by side: instructions count, not one call's latency (nbls_internal.h inv_wide_max)
     }
   }

@@ -46,7 +46,7 @@ int final_exp_pipeline(nbls_ctx* ctx, const Window& w, size_t n, uint8_t* f_raw,
   uint8_t *N = ctx->N + w.first * RAW, *NI = ctx->NI + w.first * RAW, *T[7];
   for (int k = 0; k < 7; k++) T[k] = ctx->T[k] + w.first * F12;
   if ((r = run_inv(ctx, n, N, NI, s))) return r;
-  if ((r = run(ctx, P_FE_EASY, n, {B(3, f_raw, F12), B(4, NI, RAW), B(5, T[0], F12)}, s))) return r;
+  const BufList easy = {B(3, f_raw, F12), B(4, NI, RAW), B(5, T[0], F12)};      // t1; launched below, by itself or at the head of the first exponentiation
   // the seven launches between the easy part and the final product (math.ts:862-867): t2 = t1^x, t3 = conj(t1^2) t2, t4 = t3^x, t5 = t4^x, t6' = t5^x, t6 = t6' t2^2, t7 = t6^x
   const ChainLink mid[7] = {{P_EXPX, {B(3, T[0], F12), B(5, T[1], F12)}},                          // t2
                             {P_FE_MID1, {B(3, T[0], F12), B(5, T[1], F12), B(6, T[2], F12)}},      // t3
@@ -58,16 +58,33 @@ int final_exp_pipeline(nbls_ctx* ctx, const Window& w, size_t n, uint8_t* f_raw,
   const BufList fin = {B(0, T[0], F12), B(1, T[1], F12), B(2, T[2], F12), B(3, T[3], F12), B(4, T[4], F12), B(5, T[5], F12), B(6, T[6], F12), B(7, d_out, 576)};
   const bool plain_expx = n < ctx->expc_min && ls_variant(ctx, P_EXPX, n) == P_EXPX && !wide_applies(ctx, ctx->prog[P_EXPX], (int)P_EXPX, n);
   if (plain_expx && n < ctx->chain_max && !w.beside) {
+    if ((r = run(ctx, P_FE_EASY, n, easy, s))) return r;
     if ((r = run_chain(ctx, n, mid, 7, s))) return r;      // as one chain
     return run(ctx, P_FE_FINAL, n, fin, s);
   }
   // Launch by launch; the exponentiations through expx(), which has forms of its own (rows of P_EXPX are {in, out}).  With calls in flight on streams that share a hardware
   // queue, a queue runs one batch's launches back to back and fewer, no coarser launches are faster (+2 % on four queues with both bits, EXPERIMENTS.md): a context told
   // so (ctx->fe_tail_chain, nbls_pool_init) ends a short program inside the launch of the exponentiation before it, for the same items.  Bit 0: t7 = t6^x and the final
-  // product (XP_FE_FINAL12: FE_FINAL on EXPX's kernel) are one launch; bit 1: FE_MID1 and FE_MID2 join the exponentiation that feeds them.  13 launches per batch become 12 or 10.
+  // product (XP_FE_FINAL12: FE_FINAL on EXPX's kernel) are one launch; bit 1: FE_MID1 and FE_MID2 join the exponentiation that feeds them.
+  // 12 launches per batch (two of the Miller loop, the inversion, the easy part, these seven, the final product) become 11 or 9.
+  // ctx->fe_head_chain: the easy part (XP_FE_EASY12: FE_EASY on EXPX's kernel) runs at the head of the first exponentiation's launch, on wavefronts that then go on into
+  // t2 = t1^x -- a short launch of its own starts as the youngest wavefront on every SIMD and holds its queue while it gets the issue slots the others leave.  One launch
+  // fewer: 8 a batch with both tail bits.  A table that does not bind the program to EXPX's kernel (a stale build) keeps the launch of P_FE_EASY.
   const unsigned tail = plain_expx ? ctx->fe_tail_chain : 0u;
+  bool head = plain_expx && ctx->fe_head_chain;
+  if (head) {
+    if ((r = upload_extra(ctx, XP_FE_EASY12)) || (r = upload(ctx, P_EXPX))) return r;
+    head = ctx->extra[XP_FE_EASY12].aot >= 0 && ctx->extra[XP_FE_EASY12].aot == ctx->prog[P_EXPX].aot;
+  }
+  if (!head && (r = run(ctx, P_FE_EASY, n, easy, s))) return r;
   for (int k = 0; k < 7; k++) {
     const ChainLink& l = mid[k];
+    if (k == 0 && head) {      // {easy part, EXPX(t1 -> t2)} and, with tail bit 1, FE_MID1 behind them
+      const ChainLink first[3] = {{extra_key(XP_FE_EASY12), easy}, mid[0], mid[1]};
+      const int links = (tail & 2) ? 3 : 2;
+      if ((r = run_chain(ctx, n, first, links, s))) return r;
+      k = links - 2; continue;
+    }
     if (l.id != P_EXPX) { if ((r = run(ctx, l.id, n, l.bufs, s))) return r; continue; }
     if (k == 6 && (tail & 1)) { const ChainLink last[2] = {l, {extra_key(XP_FE_FINAL12), fin}}; return run_chain(ctx, n, last, 2, s); }
     if ((tail & 2) && k < 6 && mid[k + 1].id != P_EXPX) { if ((r = run_chain(ctx, n, mid + k, 2, s))) return r; k++; continue; }

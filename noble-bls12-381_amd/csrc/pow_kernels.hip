@@ -14,7 +14,16 @@ namespace nbls {
 // Fixed-exponent powers (pow_exec.h): one element per lane (Fp) or per pair of lanes (Fp2), sliding windows over a table of odd powers kept in global scratch.
 // Fp:  Fp.pow / Fp.sqrt's a^((p+1)/4) (math.ts:251-264).   Fp2: Fp2.pow for Fp2.sqrt and sqrt_div_fp2 (math.ts:463-465, 493, 1200).
 // Elements are raw scratch elements (16 words: 14 limbs + padding), Montgomery form.
-extern "C" __global__ void __launch_bounds__(64) nbls_fp_inv_kernel(unsigned n, const u32* __restrict__ in, u32* __restrict__ out) {
+// prio (a kernel argument: the same for every wavefront) is the issue priority the wavefront takes for its whole life.  VALU issue is arbitrated by priority, then by age, and a
+// freshly launched wavefront is the youngest on its SIMD: beside other contexts' long-running step kernels it gets the slots they leave, while its own stream has nothing
+// else to run (nbls_multi.cpp POOL_INV_PRIO).  The instruction takes an immediate, hence the switch; it ignores EXEC, so it stands in front of the bounds check.
+extern "C" __global__ void __launch_bounds__(64) nbls_fp_inv_kernel(unsigned n, const u32* __restrict__ in, u32* __restrict__ out, unsigned prio) {
+  switch (prio) {
+    case 1: __builtin_amdgcn_s_setprio(1); break;
+    case 2: __builtin_amdgcn_s_setprio(2); break;
+    case 3: __builtin_amdgcn_s_setprio(3); break;
+    default: break;
+  }
   unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   u32 x[NL], y[NL];
@@ -183,4 +192,4 @@ extern "C" int nbls_flag_compact_launch(unsigned n, const void* flags, uint32_t*
   return e != hipSuccess ? (int)e : nbls::launch_1d(nbls::nbls_flag_compact_kernel, n, 256, 0, stream, n, flags, list, count);
 }
 
-extern "C" int nbls_fp_inv_launch(unsigned n, const void* in, void* out, hipStream_t stream) { return nbls::launch_1d(nbls::nbls_fp_inv_kernel, n, 64, 0, stream, n, in, out); }
+extern "C" int nbls_fp_inv_launch(unsigned n, const void* in, void* out, unsigned prio, hipStream_t stream) { return nbls::launch_1d(nbls::nbls_fp_inv_kernel, n, 64, 0, stream, n, in, out, prio); }

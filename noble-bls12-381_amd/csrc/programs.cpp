@@ -286,6 +286,7 @@ static const int MILLER_W = env_int("NBLS_MILLER_W", 16);
 // G2 programs stay at 8: at 4 lanes their LDS footprint (50 KB per wavefront) leaves less than one wavefront per SIMD.
 static const int G1_W = env_int("NBLS_G1_W", 4), G2_W = env_int("NBLS_G2_W", 8), G2MUL_W = env_int("NBLS_G2MUL_W", 8), G1MUL_W = env_int("NBLS_G1MUL_W", 4);
 static const int EXPX_W = env_int("NBLS_EXPX_W", 12);
+static const int FE_EASY12_WINDOW = 80, FE_EASY12_MAXDOT = 6;    // scheduler look-ahead and product cap of XP_FE_EASY12 (build_extra): 36 slots, 12,096 B at 50 and 80 (24 steps at 80, 25 at 50), 40 slots from 120 on; the cap of 6 adds seven signatures to the kernel, 8 eight (two of them of eight rounds)
 static const int FE_FINAL12_WINDOW = 50;   // scheduler look-ahead of XP_FE_FINAL12 (build_extra): 36 slots, 12,224 B; from 60 on 48 slots, 16,064 B; the same 59 steps either way
 // the two Miller programs: ten lane-ops per level of the point chain (6 items per wavefront); an Fp12 op has 12 lane-ops (5 items, no idle lane).
 // ACC_WINDOW keeps the line loads about one and a half iterations ahead of their use (they would otherwise all be hoisted to the front and pin 408 slots)
@@ -295,7 +296,7 @@ static const int LINES_W = env_int("NBLS_LINES_W", 10), ACC_W = env_int("NBLS_AC
 // (the interpreter pays three instructions per operand for it) and frees the replicated copies' LDS: FE_MID1 13,440 -> 11,904 B, which keeps twelve
 // workgroups per CU for the chained final exponentiation
 static bool aot_listed(ProgId id) {
-#define AOT_HAS(PART, NAME, P0, P1, P2, P3) if (id == P0 || id == P1 || id == P2 || id == P3) return true;
+#define AOT_HAS(PART, NAME, P0, P1, P2, P3, P4) if (id == P0 || id == P1 || id == P2 || id == P3 || id == P4) return true;
   NBLS_AOT_KERNELS(AOT_HAS)
 #undef AOT_HAS
   return false;
@@ -972,6 +973,18 @@ static Program build_extra(ExtraProg id) {
     B.sched_window = env_int("NBLS_FE_FINAL12_WINDOW", FE_FINAL12_WINDOW);
     output_fp12(trace_fe_final_chain([&](int i) { return inputw_fp12(i - 1, 0); }), 7, 0);
     return B.compile("fe_final12", 12);
+  }
+  if (id == XP_FE_EASY12) {
+    // P_FE_EASY's trace at twelve lanes, five items a wavefront, for the head of the first EXPX launch (final_exp_pipeline).  The same condition on the LDS image as
+    // XP_FE_FINAL12: no more than its 36 slots, so that every EXPX launch keeps twelve workgroups a CU
+    B.sched_window = env_int("NBLS_FE_EASY12_WINDOW", FE_EASY12_WINDOW);
+    B.max_dot = env_int("NBLS_FE_EASY12_MAXDOT", FE_EASY12_MAXDOT);
+    SFp12 f = inputw_fp12(3, 0);
+    SFp ninv = inputw(4, 0);
+    InvChain c = inv_chain(f);
+    SFp12 finv = mat(inv_finish(f, c, ninv));
+    outputw_fp12(trace_fe_easy(f, finv), 5, 0);
+    return B.compile("fe_easy12", 12);
   }
   if (id == XP_DBLADD_G1) {
     auto ld = [&](int buf) { return Pt<SFp>{inputw(buf, 0), inputw(buf, 48), inputw(buf, 96)}; };

@@ -119,7 +119,9 @@ const Program* get_tower_program(int field, int op, int param, int part);
 // The final product of the final exponentiation in the form a chain can hold (pipelines_pairing.cpp final_exp_pipeline): P_FE_FINAL's trace and buffers (t1..t7 in buf 0..6 ->
 // wire bytes in buf 7) under a name of its own, served by the kernel of P_EXPX, so that one launch runs t7 = t6^x and the product for the same items.  P_FE_FINAL keeps its
 // own kernel for the launches that stand alone.
-enum ExtraProg { XP_POLY_G1_16 = 0, XP_POLY_G1_256, XP_POLY_G2_16, XP_POLY_G2_256, XP_DBLADD_G1, XP_DBLADD_G2, XP_LINES_FE, XP_ENDO_G1, XP_FE_FINAL12, XP_COUNT };
+// The easy part likewise, at the head of the first exponentiation's launch: P_FE_EASY's trace and buffers (raw f in buf 3, the inverse norm in buf 4 -> t1 in buf 5) at the
+// twelve lanes per item of P_EXPX, served by its kernel, so that one launch runs the easy part and t2 = t1^x for the same items.  P_FE_EASY keeps its own kernel.
+enum ExtraProg { XP_POLY_G1_16 = 0, XP_POLY_G1_256, XP_POLY_G2_16, XP_POLY_G2_256, XP_DBLADD_G1, XP_DBLADD_G2, XP_LINES_FE, XP_ENDO_G1, XP_FE_FINAL12, XP_FE_EASY12, XP_COUNT };
 // An ExtraProg where a ProgId is asked for -- a row of NBLS_AOT_KERNELS (aot.h), a link of a chain (bufs.h ChainLink): P_COUNT + 1 + its number, the key nbls_aot_extra_index and
 // the simulator's kernel table look for.  program_by_key resolves either kind.
 static inline ProgId extra_key(ExtraProg e) { return (ProgId)((int)P_COUNT + 1 + (int)e); }

@@ -136,9 +136,10 @@ int run_dev(nbls_ctx* ctx, const DevProgram& d, int id, size_t n, const BufList&
   return NBLS_OK;
 }
 // Launches of at most ctx->inv_wide_max elements run the inversion with one limb per lane, four elements per wavefront (fp_inv_wide.h: the same binary GCD, ~25 k instead of ~48 k
-// wave-instructions on the critical path of every single call); above, one element per lane.  NBLS_INV_WIDE_MAX / NBLS_TUNE_INV_WIDE_MAX (0 = never).
+// wave-instructions on the critical path of every single call); above, one element per lane, its wavefronts at the issue priority the context asks for (ctx->inv_prio,
+// NBLS_TUNE_INV_PRIO; the wide kernel always runs at 0).  NBLS_INV_WIDE_MAX / NBLS_TUNE_INV_WIDE_MAX (0 = never).
 int run_inv_buf(nbls_ctx* ctx, size_t n, const void* in, void* out, hipStream_t s) {
-  LAUNCHCHK(n <= ctx->inv_wide_max ? nbls_fp_inv_wide_launch((unsigned)n, in, out, s) : nbls_fp_inv_launch((unsigned)n, in, out, s));
+  LAUNCHCHK(n <= ctx->inv_wide_max ? nbls_fp_inv_wide_launch((unsigned)n, in, out, s) : nbls_fp_inv_launch((unsigned)n, in, out, ctx->inv_prio, s));
   return NBLS_OK;
 }
 // the inversion of the pairing path and of the tower operations: the same launch, booked (the codec, MSM and hash pipelines call run_inv_buf: theirs are not)
@@ -179,8 +180,11 @@ int run_chain(nbls_ctx* ctx, size_t n, const ChainLink* links, size_t count, hip
     aot_seg(a.seg[a.nseg++], d, bufs);
   }
   a.W = W; a.G = G; a.n_items = (u32)n; a.qp_table = ctx->qp_table;
+  // the whole chain is booked on its first numbered program: one outside ProgId (the easy part at the head of EXPX's launch) has no timing slot
+  int slot = -1;
+  for (const ChainLink* l = links; l < links + count && slot < 0; l++) if (!key_is_extra(l->id)) slot = (int)l->id;
   int e;
-  { Timed timed(ctx, key_is_extra(links->id) ? -1 : (int)links->id, s); e = nbls_aot_launch(k, &a, lds, s); }   // the whole chain is booked on its first program
+  { Timed timed(ctx, slot, s); e = nbls_aot_launch(k, &a, lds, s); }
   if (e) { ctx->last_hip = e; return NBLS_EHIP; }
   ctx->chain_launches++;
   return NBLS_OK;

@@ -78,7 +78,7 @@ EXPORT int nbls_field_kernel_raw(nbls_ctx* ctx, int kind, int form, size_t n, co
   int r;
   if (kind == 4) {
     if (form == 0) { if ((r = run_inv_buf(ctx, n, d, o, s))) return r; }
-    else LAUNCHCHK(form == 2 ? nbls_fp_inv_wide_launch((unsigned)n, d, o, s) : nbls_fp_inv_launch((unsigned)n, d, o, s));
+    else LAUNCHCHK(form == 2 ? nbls_fp_inv_wide_launch((unsigned)n, d, o, s) : nbls_fp_inv_launch((unsigned)n, d, o, 0, s));
   } else if (form == 0) { if ((r = run_pow(ctx, kind, n, d, o, s))) return r; }
   else {
     const int tail = kind == 1 ? 8 : kind == 2 ? 7 : 0;
@@ -149,6 +149,8 @@ EXPORT int nbls_set_tuning(nbls_ctx* ctx, int key, long long value) {
     case NBLS_TUNE_NTT_TAIL_BITS: if (value < 0 || value > 12) return NBLS_EINVAL; ctx->ntt_tail_bits = (unsigned)value; return NBLS_OK;
     case NBLS_TUNE_NTT_PASS_BITS: if (value < 0 || value > 9) return NBLS_EINVAL; ctx->ntt_pass_bits = (unsigned)value; return NBLS_OK;
     case NBLS_TUNE_FE_TAIL_CHAIN: if (value < 0 || value > 3) return NBLS_EINVAL; ctx->fe_tail_chain = (unsigned)value; return NBLS_OK;
+    case NBLS_TUNE_FE_HEAD_CHAIN: if (value < 0 || value > 1) return NBLS_EINVAL; ctx->fe_head_chain = (unsigned)value; return NBLS_OK;
+    case NBLS_TUNE_INV_PRIO: if (value < 0 || value > 3) return NBLS_EINVAL; ctx->inv_prio = (unsigned)value; return NBLS_OK;
     default: return NBLS_EINVAL;
   }
 }
@@ -163,7 +165,7 @@ EXPORT const char* nbls_program_kernel(nbls_ctx* ctx, int prog) {
   return d.aot >= 0 ? nbls_aot_name(d.aot) : d.p->lsplit == 4 ? "nbls_vm_kernel_ls4" : d.p->lsplit == 1 ? "nbls_vm_kernel" : "none (two-lane programs have no interpreter form)";
 }
 // The same for a program outside the numbered registry, by its name ("poly_g1_16", "poly_g1_256", "poly_g2_16", "poly_g2_256": the Horner steps of nbls_g*_poly_eval;
-// "dbladd_g1", "dbladd_g2": the combination steps of nbls_g*_msm_batch / _rows; "lines_fe": the line program of the pairings that end in a final exponentiation; "fe_final12": the final product as the last segment of a chain); NULL for a name that is not one.  The query uploads the program.
+// "dbladd_g1", "dbladd_g2": the combination steps of nbls_g*_msm_batch / _rows; "lines_fe": the line program of the pairings that end in a final exponentiation; "fe_final12": the final product as the last segment of a chain; "fe_easy12": the easy part as the first); NULL for a name that is not one.  The query uploads the program.
 EXPORT const char* nbls_extra_program_kernel(nbls_ctx* ctx, const char* name) {
   if (!ctx || !name) return nullptr;
   std::lock_guard<std::recursive_mutex> g(ctx->mu);

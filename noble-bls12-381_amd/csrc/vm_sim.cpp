@@ -78,14 +78,14 @@ struct HostDesc {
 struct Pend { u32 dst; u32 v[NL]; };
 #define SIM_CASE(ID, KIND, P0, FLAGS, T, SH0, SH1, CNT) \
   case ID: aot_step<KIND, P0, FLAGS, T, SH0, SH1>(d, lds, item, live, bufs, qp, [&](u32 dst, const u32* res) { Pend pd; pd.dst = dst; memcpy(pd.v, res, NL * 4); pend.push_back(pd); }); break;
-#define SIM_TABLE(PART, NAME, Q0, Q1, Q2, Q3)                                                                                                        \
+#define SIM_TABLE(PART, NAME, Q0, Q1, Q2, Q3, Q4)                                                                                                     \
   static const AotSig sim_sigs_##NAME[] = {AOT_SIGS_##NAME(SIM_ROW)};                                                                      \
   static void sim_step_##NAME(u32 sig, const HostDesc& d, char* lds, u32 item, bool live, const IOBuf* bufs, const u32* qp, std::vector<Pend>& pend) { \
     switch (sig) { AOT_SIGS_##NAME(SIM_CASE) default: abort(); }                                                                          \
   }
 #define SIM_ROW(ID, KIND, P0, FLAGS, T, SH0, SH1, CNT) {KIND, P0, FLAGS, T, SH0, SH1},
 NBLS_AOT_KERNELS(SIM_TABLE)
-#define SIM_TABLE_EXTRA(PART, NAME, E0, E1) SIM_TABLE(PART, NAME, E0, E1, E0, E1)
+#define SIM_TABLE_EXTRA(PART, NAME, E0, E1) SIM_TABLE(PART, NAME, E0, E1, E0, E1, E0)
 NBLS_AOT_EXTRA_KERNELS(SIM_TABLE_EXTRA)   // the kernels of the programs outside ProgId (programs.h ExtraProg)
 // lane-split kernels (aot.h NBLS_AOT_LS_KERNELS): the same bodies with LS = 4.  The device sums the columns of the four sub-lanes of a lane-op with two DPP stages
 // (lane i <- v[i] + v[i+1] + v[i+2] + v[i+3] inside rows of 16 lanes); here the lanes of a step are visited from 63 down to 0, every lane leaves its columns in
@@ -106,23 +106,23 @@ NBLS_AOT_LS_KERNELS(SIM_TABLE)
   case ID: aot_step<KIND, P0, FLAGS, T, SH0, SH1, 2>(d, lds, item, live, bufs, qp, [&](u32 dst, const u32* res) { Pend pd; pd.dst = dst; memcpy(pd.v, res, NL * 4); pend.push_back(pd); }); break;
 NBLS_AOT_LS2_KERNELS(SIM_TABLE)
 typedef void (*SimStepFn)(u32, const HostDesc&, char*, u32, bool, const IOBuf*, const u32*, std::vector<Pend>&);
-struct SimKernel { int prog_id[4]; SimStepFn fn; const AotSig* sigs; unsigned nsigs; unsigned ls; };   // ls: sub-lanes per lane-op (0: none)
-#define SIM_ENTRY(PART, NAME, Q0, Q1, Q2, Q3) {{(int)Q0, (int)Q1, (int)Q2, (int)Q3}, sim_step_##NAME, sim_sigs_##NAME, (unsigned)(sizeof(sim_sigs_##NAME) / sizeof(AotSig)), 0},
-#define SIM_ENTRY_LS(PART, NAME, Q0, Q1, Q2, Q3) {{(int)Q0, (int)Q1, (int)Q2, (int)Q3}, sim_step_##NAME, sim_sigs_##NAME, (unsigned)(sizeof(sim_sigs_##NAME) / sizeof(AotSig)), 4},
-#define SIM_ENTRY_LS2(PART, NAME, Q0, Q1, Q2, Q3) {{(int)Q0, (int)Q1, (int)Q2, (int)Q3}, sim_step_##NAME, sim_sigs_##NAME, (unsigned)(sizeof(sim_sigs_##NAME) / sizeof(AotSig)), 2},
+struct SimKernel { int prog_id[5]; SimStepFn fn; const AotSig* sigs; unsigned nsigs; unsigned ls; };   // ls: sub-lanes per lane-op (0: none)
+#define SIM_ENTRY(PART, NAME, Q0, Q1, Q2, Q3, Q4) {{(int)Q0, (int)Q1, (int)Q2, (int)Q3, (int)Q4}, sim_step_##NAME, sim_sigs_##NAME, (unsigned)(sizeof(sim_sigs_##NAME) / sizeof(AotSig)), 0},
+#define SIM_ENTRY_LS(PART, NAME, Q0, Q1, Q2, Q3, Q4) {{(int)Q0, (int)Q1, (int)Q2, (int)Q3, (int)Q4}, sim_step_##NAME, sim_sigs_##NAME, (unsigned)(sizeof(sim_sigs_##NAME) / sizeof(AotSig)), 4},
+#define SIM_ENTRY_LS2(PART, NAME, Q0, Q1, Q2, Q3, Q4) {{(int)Q0, (int)Q1, (int)Q2, (int)Q3, (int)Q4}, sim_step_##NAME, sim_sigs_##NAME, (unsigned)(sizeof(sim_sigs_##NAME) / sizeof(AotSig)), 2},
 // an ExtraProg is entered as P_COUNT + 1 + its number, as in aot_kernel.hip
 #define SIM_XP(E) ((int)E == (int)XP_COUNT ? (int)P_COUNT : (int)P_COUNT + 1 + (int)E)
-#define SIM_ENTRY_EXTRA(PART, NAME, E0, E1) {{SIM_XP(E0), SIM_XP(E1), (int)P_COUNT, (int)P_COUNT}, sim_step_##NAME, sim_sigs_##NAME, (unsigned)(sizeof(sim_sigs_##NAME) / sizeof(AotSig)), 0},
+#define SIM_ENTRY_EXTRA(PART, NAME, E0, E1) {{SIM_XP(E0), SIM_XP(E1), (int)P_COUNT, (int)P_COUNT, (int)P_COUNT}, sim_step_##NAME, sim_sigs_##NAME, (unsigned)(sizeof(sim_sigs_##NAME) / sizeof(AotSig)), 0},
 static const SimKernel g_sim_kernels[] = {NBLS_AOT_KERNELS(SIM_ENTRY) NBLS_AOT_LS_KERNELS(SIM_ENTRY_LS) NBLS_AOT_LS2_KERNELS(SIM_ENTRY_LS2) NBLS_AOT_EXTRA_KERNELS(SIM_ENTRY_EXTRA)};
 static int g_sim_aot = 0;
 // 0: ran; -2: the program has no ahead-of-time kernel; -3: its signatures are not in the kernel's table
-// key: a ProgId, or P_COUNT + 1 + an ExtraProg
-static int sim_run_aot_program(int key, const Program& p, unsigned n_items, const IOBuf* bufs) {
+// key: a ProgId, or P_COUNT + 1 + an ExtraProg; placed = false: the LDS slots as compiled, whatever row aot_layout.inc has for the program
+static int sim_run_aot_program(int key, const Program& p, unsigned n_items, const IOBuf* bufs, bool placed = true) {
   const SimKernel* K = nullptr;
-  if (key >= 0 && key != (int)P_COUNT) for (auto& k : g_sim_kernels) for (int j = 0; j < 4; j++) if (k.prog_id[j] == key) K = &k;
+  if (key >= 0 && key != (int)P_COUNT) for (auto& k : g_sim_kernels) for (int j = 0; j < 5; j++) if (k.prog_id[j] == key) K = &k;
   if (!K) return -2;
   AotProgram ap;
-  if (!aot_translate(p, ap).empty()) return -3;
+  if (!(placed ? aot_translate(p, ap) : aot_translate_with(p, ap, nullptr)).empty()) return -3;
   std::vector<unsigned> map(ap.sigs.size());
   for (size_t i = 0; i < ap.sigs.size(); i++) { unsigned id = 0; while (id < K->nsigs && !(K->sigs[id] == ap.sigs[i])) id++; if (id == K->nsigs) return -3; map[i] = id; }
   const u32* qp_table = qp_table_words();
@@ -330,7 +330,7 @@ __attribute__((visibility("default"))) unsigned long nbls_sim_wide_violations() 
 __attribute__((visibility("default"))) int nbls_sim_wide_supported(int prog) { if (prog < 0 || prog >= (int)P_COUNT) return 0; const Program& p = get_program((ProgId)prog); if (p.lsplit != 1 || p.W > 16) return 0; for (auto& st : p.steps) if (!wide_step_supported(st, p.descs.data())) return 0; return 1; }
 // translated programs (aot.h) instead of the interpreter's semantics for the programs that have an ahead-of-time kernel: 0 off, 1 on
 __attribute__((visibility("default"))) void nbls_sim_set_aot(int on) { g_sim_aot = on; }
-__attribute__((visibility("default"))) int nbls_sim_has_aot(int prog) { if (prog < 0 || prog >= (int)P_COUNT) return 0; for (auto& k : g_sim_kernels) for (int j = 0; j < 4; j++) if (k.prog_id[j] == prog) return 1; return 0; }
+__attribute__((visibility("default"))) int nbls_sim_has_aot(int prog) { if (prog < 0 || prog >= (int)P_COUNT) return 0; for (auto& k : g_sim_kernels) for (int j = 0; j < 5; j++) if (k.prog_id[j] == prog) return 1; return 0; }
 // bufs: 8 pointers + 8 strides
 __attribute__((visibility("default"))) int nbls_sim_run(int prog, unsigned n_items, uint8_t** ptrs, const uint64_t* strides) {
   if (prog < 0 || prog >= P_COUNT) return -1;
@@ -343,7 +343,7 @@ __attribute__((visibility("default"))) int nbls_sim_run(int prog, unsigned n_ite
 }
 // The programs outside ProgId (programs.h ExtraProg; nbls_sim_run refuses everything from P_COUNT on): count, name, the static verifier (0 = passed; the message goes to
 // stderr), and a run -- aot = 0: the interpreter's semantics; 1: the translated form on the step bodies of the program's ahead-of-time kernel (-2: it has none, -3: its
-// signatures are not in the kernel's table)
+// signatures are not in the kernel's table); 2: the same with the LDS slots as compiled, the form a program takes while aot_layout.inc has no current row for it
 __attribute__((visibility("default"))) int nbls_sim_extra_count(void) { return XP_NUMBERED; }
 __attribute__((visibility("default"))) const char* nbls_sim_extra_name(int xp) { return xp >= 0 && xp < XP_NUMBERED ? get_extra_program((ExtraProg)xp).name.c_str() : nullptr; }
 static int sim_extra_verify(int xp) {
@@ -355,7 +355,7 @@ static int sim_extra_run(int xp, int aot, unsigned n_items, uint8_t** ptrs, cons
   IOBuf b[MAX_BUFS];
   for (int i = 0; i < MAX_BUFS; i++) { b[i].ptr = ptrs[i]; b[i].stride = strides[i]; }
   const Program& p = get_extra_program((ExtraProg)xp);
-  if (aot) return sim_run_aot_program((int)P_COUNT + 1 + xp, p, n_items, b);
+  if (aot) return sim_run_aot_program((int)P_COUNT + 1 + xp, p, n_items, b, aot != 2);
   sim_run(p, n_items, b);
   return 0;
 }

@@ -1153,6 +1153,15 @@ class Engine:
         final product, bit 1 FE_MID1 / FE_MID2; default 0, pool contexts are set by nbls_pool_init"""
         self._chk(self.lib.nbls_set_tuning(self.h, 24, int(bits)))
 
+    def set_fe_head_chain(self, on):
+        """such a final exponentiation runs the easy part at the head of the first exponentiation's launch (NBLS_TUNE_FE_HEAD_CHAIN): 0 / 1; default 0, pool contexts are set by
+        nbls_pool_init"""
+        self._chk(self.lib.nbls_set_tuning(self.h, 29, int(on)))
+
+    def set_inv_prio(self, level):
+        """issue priority 0 .. 3 of the wavefronts of the one-element-per-lane Fp inversion kernel (NBLS_TUNE_INV_PRIO); default 0, pool contexts are set by nbls_pool_init"""
+        self._chk(self.lib.nbls_set_tuning(self.h, 30, int(level)))
+
     def set_sac_max(self, n):
         """keys up to which sign's ladder is the sign-aligned one-addition-per-bit form (NBLS_TUNE_SAC_MAX; default 6144, 0: the windowed psi-split ladder at every size)"""
         self._chk(self.lib.nbls_set_tuning(self.h, 8, n))

@@ -16,8 +16,8 @@ from .engine import Engine, NblsError, load_library
 
 class PairingPipeline:
     """Round 5: a thin view of the C ABI's pool (include/nbls.h nbls_pool_*: `depth` contexts, each with its own stream and scratch, tuned for overlapping calls --
-    the two-program Miller loop at every size, the final exponentiation launch by launch with its short programs inside the launch of the exponentiation before them -- and fed
-    round-robin); `engines` wraps the pool's contexts."""
+    the two-program Miller loop at every size, the final exponentiation launch by launch with its short programs inside the launches of the exponentiations next to them, eight launches a batch -- and
+    fed round-robin); `engines` wraps the pool's contexts."""
 
     def __init__(self, device_id=0, depth=12):
         assert depth >= 1
