@@ -607,6 +607,69 @@ int  nbls_groth16_prepare_inputs(nbls_ctx* ctx, const nbls_groth16_vk* vk, size_
 int  nbls_groth16_input_sums(nbls_ctx* ctx, size_t n, size_t m, const uint8_t* inputs32, const uint8_t* weights32 /* n, each < 2^64 */, const int8_t* pre /* n, may be NULL */,
                              uint8_t* out32 /* m + 1 */, int8_t* status /* n, may be NULL */);
 
+/* The Groth16 prover: from a witness to the 192 bytes nbls_groth16_verify reads, against a proving key kept on the device.  Conventions as above: N = 2^log2_n,
+ * omega = omega_N = 7^((r - 1) / N), Fr elements 32 bytes big-endian and CANONICAL, G1 points 48 bytes compressed (PointG1.fromHex), G2 points 96 bytes compressed
+ * (PointG2.fromSignature), both decoders with the subgroup check, a proof A || B || C; "values in bit-reversed order" is nbls_fr_ntt's order: position i holds the value at
+ * omega^rev(i).
+ * The statement: an R1CS instance of three sparse N-row matrices A, B, C over Fr with n_vars columns -- the first n_constraints <= N rows given in CSR form, the others
+ * empty, row j belonging to the domain point omega^j -- and the assignment z = (1, x_1 .. x_m, aux ..) with m = n_public inputs.  With a = A z, b = B z, c = C z, their
+ * interpolants a(X), b(X), c(X) and Z = X^N - 1, the quotient is h = (a b - c) / Z: N coefficients, the top one zero.  The proof for the blinding scalars (r, s):
+ *   A = alpha_g1 + sum_i [z_i] a_query_i + [r] delta_g1
+ *   B = beta_g2 + sum_i [z_i] b_g2_query_i + [s] delta_g2          (B1: the same in G1, with beta_g1 / b_g1_query / delta_g1)
+ *   C = sum_{i > m} [z_i] l_query_(i-m-1) + sum_{k < N-1} [h_k] h_query_k + [s] A + [r] B1 - [r s] delta_g1
+ * This is meant to be bellman's ProvingKey -- h_query_k = [tau^k Z(tau) / delta]G1, l_query = [(beta A_i + alpha B_i + C_i)(tau) / delta]G1, omega and the row <-> omega^j
+ * rule its EvaluationDomain's -- but NO bellman key or proof has been run against these calls: the compatibility is intended and untested; what is tested
+ * is that nbls_groth16_verify accepts the proofs, and their bytes against a key with a known trapdoor.
+ *   nbls_groth16_pk_create   decodes every point once and keeps in memory of its own on ctx's device: the three matrices with their coefficients in Montgomery limb form
+ *                            and the rows ordered by length; the points as the four contiguous affine arrays the sums read (a_query | alpha_g1 | delta_g1; b_g1_query |
+ *                            beta_g1 | delta_g1; b_g2_query | beta_g2 | delta_g2; l_query | h_query | [slot A] | [slot B1] | delta_g1); one mask byte per query point; and
+ *                            the whole workspace of a proof (z in limb form, the three N-element vectors, the three scalar arrays, flags, result points).  status (may be
+ *                            NULL): 5 + 3 n_vars + n_aux + N - 1 decoder statuses in the order of the descriptor's point fields, n_aux = n_vars - n_public - 1.  A ZERO POINT
+ *                            (0xc0 00..) IS VALID in the four per-variable queries (a variable no constraint of that matrix names): status 1, the point masked -- a fixed
+ *                            point of the subgroup stands in the array and its scalar is forced to zero.  A zero point among the five fixed points or in h_query, or any
+ *                            entry that does not decode: NBLS_EDECODE, *out = NULL, the statuses written all the same (as nbls_groth16_vk_create).  NBLS_EINVAL before any
+ *                            device work for a missing pointer, log2_n outside 1 .. 21, n_public = 0 or n_vars <= n_public, n_constraints > N, n_aux + N + 2 or n_vars + 2
+ *                            above 2^22 (the bound of nbls_msm_dev on one sum), more than 2^24 entries in one matrix, offsets that decrease or do not start at 0, a column
+ *                            >= n_vars, a non-canonical coefficient, b_g1_query[i] and b_g2_query[i] that disagree on being the zero point.  Lifetime and device rules are
+ *                            nbls_groth16_vk_create's; the handle carries a lock: two contexts never prove on it at once.
+ *   nbls_groth16_prove       n witnesses (1 .. 2^16), one chain each on the context's stream: one copy in -> the canonical check of z and (r, s), z to limb form, z_0 == 1 ->
+ *                            a, b, c by g16p_spmv_kernel (rows of at least NBLS_TUNE_G16P_ROW_WAVE entries summed by a wavefront, the others by a lane; all three matrices of
+ *                            a row in one place, so a_j b_j == c_j is checked there) -> the quotient as below (nbls_fr_ntt_dev, in place) -> the three scalar arrays with the
+ *                            masks applied -> four sums by the bucket MSM of nbls_msm_dev (A and B1 written straight into their slots of the fourth array) -> compression.
+ *                            One copy out of all proofs and statuses behind the last.  status[i] (may be NULL), the first that applies: NBLS_ST_NON_CANONICAL for an element
+ *                            of z_i, r_i or s_i >= r; NBLS_ST_G16_UNSATISFIED; 1 when A or B is the zero point (the verifier refuses such a proof anyway); 0.  A proof whose
+ *                            status is not 0 is 192 ZERO BYTES and never disturbs its neighbours; the call returns NBLS_OK whatever the witnesses hold.  rs32 == NULL: r_i and
+ *                            s_i are drawn uniformly below r from getrandom(2) (32 bytes masked to 255 bits, redrawn while >= r); NBLS_ENOSUP when the OS gives none, never a
+ *                            fixed value.  NBLS_EINVAL before any device work for a missing pointer, n = 0, n > 2^16, a key on another device.
+ *                            THE WITNESS AND (r, s) ARE SECRETS: before the call returns the handle's copies of z, h and the scalar arrays and the staged block are zeroed on
+ *                            the device and the page-locked host block is wiped (as nbls_sign_batch wipes its keys).  The bucket MSM's timing depends on the scalars, as
+ *                            bellman's multiexp does: this is the only sense in which the call is not constant time.
+ *   nbls_groth16_quotient    the quotient alone on caller-chosen vectors (it exists for tests, as nbls_groth16_input_sums exposes the folding kernel): n independent triples
+ *                            a, b, c of N values in bit-reversed order -> h, N coefficients in natural order.  Each vector to coefficients, to the values on the coset
+ *                            7 <omega> (any shift g with g^N != 1 gives the same h; 7 is bellman's), (a' b' - c') / (7^N - 1) per element, back to coefficients with the shift 7.
+ *                            status[i] (may be NULL): NBLS_ST_NON_CANONICAL for a triple with an element >= r (the output row is then all-zero); NBLS_ST_G16_UNSATISFIED when
+ *                            a_j b_j != c_j somewhere -- the output row is then what the same arithmetic gives, UNSPECIFIED bytes and no quotient of anything; 0.
+ *                            NBLS_EINVAL for log2_n outside 1 .. 22 (or more than 12 above NBLS_TUNE_NTT_TAIL_BITS), more than 2^24 elements in a row set (n << log2_n), a
+ *                            NULL context, missing buffers with n > 0; n = 0 is NBLS_OK.  Nothing here is wiped. */
+#define NBLS_ST_G16_UNSATISFIED 24     /* z_0 != 1, or a row j with (Az)_j (Bz)_j != (Cz)_j */
+typedef struct {
+  unsigned log2_n; size_t n_vars, n_public /* m */, n_constraints /* <= N */;
+  const uint32_t *a_rows, *a_cols; const uint8_t* a_vals32;      /* CSR: n_constraints + 1 offsets from 0, non-decreasing; columns < n_vars; canonical coefficients */
+  const uint32_t *b_rows, *b_cols; const uint8_t* b_vals32;
+  const uint32_t *c_rows, *c_cols; const uint8_t* c_vals32;
+  const uint8_t *alpha_g1_48, *beta_g1_48, *beta_g2_96, *delta_g1_48, *delta_g2_96;
+  const uint8_t *a_query48 /* n_vars */, *b_g1_query48 /* n_vars */, *b_g2_query96 /* n_vars */, *l_query48 /* n_vars - m - 1 */, *h_query48 /* N - 1 */;
+} nbls_groth16_pk_desc;
+typedef struct nbls_groth16_pk nbls_groth16_pk;
+int  nbls_groth16_pk_create(nbls_ctx* ctx, const nbls_groth16_pk_desc* desc, int8_t* status /* 5 + 3 n_vars + n_aux + N - 1, may be NULL */, nbls_groth16_pk** out);
+void nbls_groth16_pk_destroy(nbls_groth16_pk* pk);
+int  nbls_groth16_pk_params(const nbls_groth16_pk* pk, unsigned* log2_n, size_t* n_vars, size_t* n_public);
+int  nbls_groth16_pk_wiped(nbls_ctx* ctx, nbls_groth16_pk* pk, int* wiped);   /* for tests: *wiped = 1 when the handle's secret arrays (the staged witness and (r, s), z, a | b | c and h, the three scalar arrays) read back as zeros */
+int  nbls_groth16_prove(nbls_ctx* ctx, nbls_groth16_pk* pk, size_t n, const uint8_t* witness32 /* n * n_vars, z_0 = 1 first */,
+                        const uint8_t* rs32 /* n * 64: r_i || s_i; NULL: from the OS */, uint8_t* out_proofs192, int8_t* status /* n, may be NULL */);
+int  nbls_groth16_quotient(nbls_ctx* ctx, unsigned log2_n, size_t n, const uint8_t* a32, const uint8_t* b32, const uint8_t* c32 /* n << log2_n each, values in bit-reversed order */,
+                           uint8_t* out_h32 /* n << log2_n coefficients, natural order */, int8_t* status /* n, may be NULL */);
+
 /* One rank's share of a verifyBatch spread over several GPUs (one process per GPU): the Miller product of this rank's n
  * (key, message) pairs, times millerLoop(-G, S) on the ONE rank that passes the signature (d_sig96 = NULL elsewhere), WITHOUT the
  * final exponentiation, as 576 wire bytes in device memory.  Ranks all-gather their partials and finish with
@@ -644,6 +707,7 @@ const char* nbls_config_describe(void);   /* "NBLS_X=value(env|default) ...": ev
    Then NBLS_TUNE_FE_TAIL_CHAIN, nbls_chain_launches and the name "fe_final12" of nbls_extra_program_kernel (additions only, same version).
    Then NBLS_TUNE_FE_HEAD_CHAIN, NBLS_TUNE_INV_PRIO and the name "fe_easy12" of nbls_extra_program_kernel (additions only, same version).
    Then nbls_fr_ntt_large, nbls_fr_ntt_dev, NBLS_TUNE_NTT_TAIL_BITS / _PASS_BITS, scratch slot 87 (additions only, same version).
+   Then nbls_groth16_pk_create / _destroy / _params / _wiped, nbls_groth16_prove, nbls_groth16_quotient, NBLS_ST_G16_UNSATISFIED, NBLS_TUNE_G16P_ROW_WAVE, no scratch slot (additions only, same version).
    4 (round 6): nbls_hw_queues, NBLS_TUNE_WIDE_MAX, NBLS_TUNE_H2C_NORM_MIN, NBLS_TUNE_INV_WIDE_MAX, NBLS_TUNE_LS_MAX / _LS2_MAX (additions only); the library sets GPU_MAX_HW_QUEUES = 22 at load when the variable is unset (see nbls_pool_init below).
    3 (round 5): nbls_program_kernel, nbls_pool_*, nbls_sign_batch_dev, NBLS_TUNE_VERIFY_* / _SAC_MAX / _PT_LS2_MAX (additions only); nbls_verify_batch_partial_dev writes d_out_fp12 even when it reports a zero point or a decode error
    (contents then meaningless); 2: *_partial take *d_partial as OUT only, *_partial_into added, nbls_tower_op_batch, nbls_verify_batch_msgs_dev.  The bindings check it at load. */
@@ -730,6 +794,7 @@ int nbls_field_kernel_raw(nbls_ctx* ctx, int kind, int form, size_t n, const uin
 #define NBLS_TUNE_NTT_PASS_BITS 27    /* P, the global stages one launch of the same calls runs at most: 1 .. 9 (nine stages of rows of 8 elements fill the LDS tile of 2^12 elements); 0 (default) = 8.  The log2_n - t global stages are cut into ceil((log2_n - t) / P) runs whose lengths differ by one at most.  The bytes do not depend on it (28 stays unassigned) */
 #define NBLS_TUNE_FE_HEAD_CHAIN 29     /* (25 and 28 stay unassigned: tests pin them as the first unknown keys of their time) 0 / 1: such a final exponentiation runs the easy part at the head of the first exponentiation's launch (FE_EASY + EXPX are one launch, and FE_MID1 with them under bit 1 of NBLS_TUNE_FE_TAIL_CHAIN) instead of as a launch of its own: 9 launches per pairing batch become 8.  The bytes do not depend on it.  Default 0 (environment: NBLS_FE_HEAD_CHAIN); nbls_pool_init sets 1 on its contexts */
 #define NBLS_TUNE_INV_PRIO 30          /* 0 .. 3: the issue priority of the wavefronts of the one-element-per-lane Fp inversion kernel (launches above NBLS_TUNE_INV_WIDE_MAX elements); a wavefront of higher priority wins the arbitration for VALU issue against those of other launches on its SIMD.  The bytes do not depend on it.  Default 0 (environment: NBLS_INV_PRIO); nbls_pool_init sets its contexts' (nbls_multi.cpp POOL_INV_PRIO) */
+#define NBLS_TUNE_G16P_ROW_WAVE 31     /* matrix entries from which a row is summed by a whole wavefront instead of one lane; 0 = default.  The bytes do not depend on it */
 int nbls_set_tuning(nbls_ctx* ctx, int key, long long value);
 int nbls_program_count(void);                 /* number of step programs; timing slot nbls_program_count() = the inversion kernel */
 const char* nbls_program_name(int prog);

@@ -9,7 +9,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
-namespace nbls { struct KernelArgs; struct FrNttRun; }
+namespace nbls { struct KernelArgs; struct FrNttRun; struct G16pScalars; }
 
 extern "C" {
 // vm_kernel.hip, vm_wide_kernel.hip
@@ -104,4 +104,13 @@ int nbls_g16_items_launch(unsigned n, const void* pre, const void* w32, const vo
 int nbls_g16_rows_launch(unsigned n, unsigned m, const void* pre, void* rows32, hipStream_t stream);
 int nbls_g16_status_launch(unsigned n, const void* pre, const void* one, void* status, hipStream_t stream);
 int nbls_g16_prepare_tail_launch(unsigned n, const void* zero, const void* pre, void* out48, void* status, hipStream_t stream);
+// groth16_prove_kernels.hip
+int nbls_g16p_witness_launch(size_t n_vars, const void* w32, void* z, void* flags, hipStream_t stream);
+int nbls_g16p_spmv_launch(unsigned log2_n, unsigned n_wave, const uint32_t* order, const void* const mats[9], const void* z, void* v32, void* flags, hipStream_t stream);
+int nbls_g16p_quotient_launch(unsigned log2_n, size_t n, void* a32, const void* b32, const void* c32, const void* st3, const uint32_t* kinv, hipStream_t stream);
+int nbls_g16p_check_launch(unsigned log2_n, size_t n, const void* a32, const void* b32, const void* c32, void* violated, hipStream_t stream);
+int nbls_g16p_quot_status_launch(size_t n, const void* st3, const void* violated, void* status, hipStream_t stream);
+int nbls_g16p_scalars_launch(const nbls::G16pScalars* S, hipStream_t stream);
+int nbls_g16p_mask_launch(size_t n, unsigned elem_bytes, const void* st, const void* fixed, void* pts, void* mask, hipStream_t stream);
+int nbls_g16p_finish_launch(const void* flags, const void* zero3, void* out192, void* status, hipStream_t stream);
 }

@@ -1,5 +1,5 @@
 // nbls_internal.h -- what the translation units of the runtime share (runtime.cpp / tuning.cpp / pipelines_pairing.cpp / pipelines_codec.cpp / pipelines_verify.cpp / pipelines_multi_verify.cpp / pipelines_threshold.cpp /
-// pipelines_poly.cpp / pipelines_msm.cpp / kzg_common.cpp / pipelines_kzg.cpp / pipelines_kzg_prove.cpp / pipelines_kzg_cells.cpp / pipelines_kzg_verify_cells.cpp / pipelines_groth16.cpp; pool and multi-device handles: nbls_multi.cpp): the context, the
+// pipelines_poly.cpp / pipelines_msm.cpp / kzg_common.cpp / pipelines_kzg.cpp / pipelines_kzg_prove.cpp / pipelines_kzg_cells.cpp / pipelines_kzg_verify_cells.cpp / pipelines_groth16.cpp / pipelines_groth16_prove.cpp; pool and multi-device handles: nbls_multi.cpp): the context, the
 // map of its scratch slots (enum Slot: the one place that says which chain owns which slot, checked at compile time), the launch helpers, the staged block of the host-buffer pipelines (staging.h, included at the end) and the
 // device-side pipelines the exported entry points are built from.  Internal functions have hidden visibility (csrc/Makefile: -fvisibility=hidden).
 #pragma once
@@ -210,6 +210,7 @@ struct nbls_ctx {
   // nbls_set_tuning(NBLS_TUNE_NTT_TAIL_BITS / _PASS_BITS): the log size of the tails of nbls_fr_ntt_large / nbls_fr_ntt_dev and the global stages a launch runs at most; 0 = the defaults (pipelines_kzg_cells.cpp)
   unsigned ntt_tail_bits = 0, ntt_pass_bits = 0;
   size_t g16_chunk = 0;         // nbls_set_tuning(NBLS_TUNE_G16_CHUNK): proofs per pass of the per-proof pass of nbls_groth16_verify and of nbls_groth16_prepare_inputs; 0 = as many as the batched MSM takes (pipelines_groth16.cpp)
+  size_t g16p_row_wave = 0;     // nbls_set_tuning(NBLS_TUNE_G16P_ROW_WAVE): matrix entries from which nbls_groth16_prove sums a row by a whole wavefront; 0 = the default (g16p_exec.h)
   // scratch (device)
   uint8_t *F = nullptr, *N = nullptr, *NI = nullptr, *io_g1 = nullptr, *io_g2 = nullptr, *io_f12 = nullptr, *one12 = nullptr;
   uint8_t* T[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // t1..t7 of the final exponentiation, raw Fp12

@@ -151,6 +151,7 @@ EXPORT int nbls_set_tuning(nbls_ctx* ctx, int key, long long value) {
     case NBLS_TUNE_FE_TAIL_CHAIN: if (value < 0 || value > 3) return NBLS_EINVAL; ctx->fe_tail_chain = (unsigned)value; return NBLS_OK;
     case NBLS_TUNE_FE_HEAD_CHAIN: if (value < 0 || value > 1) return NBLS_EINVAL; ctx->fe_head_chain = (unsigned)value; return NBLS_OK;
     case NBLS_TUNE_INV_PRIO: if (value < 0 || value > 3) return NBLS_EINVAL; ctx->inv_prio = (unsigned)value; return NBLS_OK;
+    case NBLS_TUNE_G16P_ROW_WAVE: if (value < 0) return NBLS_EINVAL; ctx->g16p_row_wave = (size_t)value; return NBLS_OK;
     default: return NBLS_EINVAL;
   }
 }

@@ -13,6 +13,8 @@
 #include "pow_wide.h"
 #include "rlc_weights.h"
 #include "fr_workgroup.h"
+#include "g16p_exec.h"
+#include <algorithm>
 #include "wide_exec.h"
 #include "g1_wide.h"
 #include "fp_inv_wide.h"
@@ -789,6 +791,99 @@ __attribute__((visibility("default"))) int nbls_sim_g16_input_sums(size_t n, siz
     for (u32 t = 0; t < T; t++) if (tile * T + t <= M) partial[(size_t)b * (m + 1) + tile * T + t] = part[t];
   }
   for (u32 tile = 0; tile < tiles; tile++) g16_sum_body(sim_wg<G16_LANES>(), M, tile, wgs, partial.data(), out32, part.data());
+  return 0;
+}
+// ---- The Groth16 prover's kernels (groth16_prove_kernels.hip; the lane code is g16p_exec.h's, the text the device compiles).
+// g16p_witness_kernel and g16p_spmv_kernel on one witness.  mats: rows, cols, vals32 of A, of B, of C as nbls_groth16_pk_create takes them (n_constraints + 1 offsets,
+// canonical coefficients); w32: z | r | s; row_wave: the threshold (0: the default).  The launch is re-enacted wavefront by wavefront: the rows ordered by length as the key
+// orders them, the first n_wave a wavefront each -- 64 shares, then the six levels of the cross-lane sum as the shuffles pair the lanes --, the others a lane each, in the
+// simulator's lane order.  -> v32: a | b | c, values at rev(j); flags2: non-canonical, unsatisfied.  -1 under pk_create's rules on the matrices
+__attribute__((visibility("default"))) int nbls_sim_g16p_spmv(unsigned log2_n, size_t n_vars, size_t n_constraints, const void* const mats[9], const uint8_t* w32, unsigned row_wave,
+                                                              uint8_t* v32, uint8_t* flags2) {
+  if (log2_n < 1 || log2_n > 21 || !n_vars || !mats || !w32 || !v32 || !flags2 || n_constraints > ((size_t)1 << log2_n)) return -1;
+  const u32 N = 1u << log2_n, W = G16P_WAVE;
+  std::vector<u32> rows[3]; std::vector<Fr> vals[3]; G16pMatrix M[3];
+  for (int k = 0; k < 3; k++) {
+    const u32 *r = (const u32*)mats[3 * k], *c = (const u32*)mats[3 * k + 1]; const uint8_t* v = (const uint8_t*)mats[3 * k + 2];
+    if (!r || r[0] != 0) return -1;
+    for (size_t j = 0; j < n_constraints; j++) if (r[j + 1] < r[j]) return -1;
+    const u32 nnz = r[n_constraints];
+    if (nnz && (!c || !v)) return -1;
+    rows[k].assign((size_t)N + 1, nnz);
+    for (size_t j = 0; j <= n_constraints; j++) rows[k][j] = r[j];
+    vals[k].resize(nnz);
+    for (u32 e = 0; e < nnz; e++) {
+      if (c[e] >= n_vars || fr_ge_r_mask(fr_load_be(v + 32ull * e))) return -1;
+      vals[k][e] = fr_from_bytes(v + 32ull * e);
+    }
+    M[k] = G16pMatrix{rows[k].data(), c, vals[k].data()};
+  }
+  std::vector<u32> len(N), order(N);
+  for (u32 j = 0; j < N; j++) {
+    len[j] = 0;
+    for (int k = 0; k < 3; k++) if (rows[k][j + 1] - rows[k][j] > len[j]) len[j] = rows[k][j + 1] - rows[k][j];
+    order[j] = j;
+  }
+  std::stable_sort(order.begin(), order.end(), [&](u32 x, u32 y) { return len[x] > len[y]; });
+  const u32 T = row_wave ? row_wave : (u32)G16P_ROW_WAVE_DEFAULT;
+  u32 n_wave = 0;
+  while (n_wave < N && len[order[n_wave]] >= T) n_wave++;
+  uint8_t flags[G16P_FLAGS] = {0};
+  std::vector<Fr> z(n_vars);
+  for (uint64_t i = 0; i < n_vars + 2; i++) { const uint64_t e = g_lanes_down ? n_vars + 1 - i : i; g16p_witness_element(n_vars, e, w32, z.data(), flags); }
+  const uint64_t waves = (uint64_t)n_wave + ((uint64_t)N - n_wave + W - 1) / W;
+  for (uint64_t wave = 0; wave < waves; wave++) {
+    if (wave < n_wave) {
+      const u32 row = order[wave];
+      Fr p[3][G16P_WAVE], q[G16P_WAVE];
+      for (int k = 0; k < 3; k++) {
+        for (u32 l = 0; l < W; l++) { const u32 lane = g_lanes_down ? W - 1 - l : l; p[k][lane] = g16p_row_part(M[k], z.data(), row, lane, W); }
+        for (u32 m = 1; m < W; m <<= 1) { for (u32 l = 0; l < W; l++) q[l] = fr_add(p[k][l], p[k][l ^ m]); for (u32 l = 0; l < W; l++) p[k][l] = q[l]; }
+      }
+      g16p_row_store(log2_n, row, p[0][0], p[1][0], p[2][0], v32, flags);
+      continue;
+    }
+    for (u32 l = 0; l < W; l++) {
+      const u32 lane = g_lanes_down ? W - 1 - l : l;
+      const uint64_t k = (wave - n_wave) * W + lane + n_wave;
+      if (k >= N) continue;
+      const u32 row = order[k];
+      g16p_row_store(log2_n, row, g16p_row_part(M[0], z.data(), row, 0, 1), g16p_row_part(M[1], z.data(), row, 0, 1), g16p_row_part(M[2], z.data(), row, 0, 1), v32, flags);
+    }
+  }
+  flags2[0] = flags[G16P_F_NONCANON]; flags2[1] = flags[G16P_F_UNSAT];
+  return 0;
+}
+// nbls_groth16_quotient: g16p_check_kernel, the transforms of nbls_sim_fr_ntt_large with the plan given (tail_bits / pass_bits as there), g16p_quotient_kernel between
+// them, the closing statuses.  status may be NULL
+__attribute__((visibility("default"))) int nbls_sim_g16p_quotient(unsigned log2_n, size_t n, const uint8_t* a32, const uint8_t* b32, const uint8_t* c32, uint8_t* out_h32, int8_t* status,
+                                                                  unsigned tail_bits, unsigned pass_bits) {
+  const unsigned t = tail_bits ? tail_bits : FR_NTTL_DEFAULT_TAIL;
+  if (log2_n < 1 || log2_n > 22 || (log2_n > t && log2_n - t > 12) || (n << log2_n) > ((size_t)1 << 24) || n > ((size_t)1 << 24) || (n && (!a32 || !b32 || !c32 || !out_h32))) return -1;
+  if (!n) return 0;
+  const size_t elems = n << log2_n, qb = elems * 32;
+  std::vector<uint8_t> v[3] = {std::vector<uint8_t>(a32, a32 + qb), std::vector<uint8_t>(b32, b32 + qb), std::vector<uint8_t>(c32, c32 + qb)}, shift(n * 32, 0), violated(n, 0);
+  std::vector<int8_t> st3(3 * n, 0);
+  for (size_t i = 0; i < n; i++) shift[32 * i + 31] = 7;
+  for (size_t i = 0; i < elems; i++) g16p_check_element(log2_n, g_lanes_down ? elems - 1 - i : i, a32, b32, c32, violated.data());
+  for (int k = 0; k < 3; k++) if (nbls_sim_fr_ntt_large(log2_n, 0, n, v[k].data(), nullptr, v[k].data(), st3.data() + k * n, tail_bits, pass_bits)) return -1;
+  for (int k = 0; k < 3; k++) if (nbls_sim_fr_ntt_large(log2_n, 1, n, v[k].data(), shift.data(), v[k].data(), nullptr, tail_bits, pass_bits)) return -1;
+  const Fr kinv = g16p_quot_factor(log2_n);
+  for (size_t i = 0; i < elems; i++) g16p_quot_element(log2_n, n, g_lanes_down ? elems - 1 - i : i, v[0].data(), v[1].data(), v[2].data(), st3.data(), kinv);
+  if (nbls_sim_fr_ntt_large(log2_n, 0, n, v[0].data(), shift.data(), out_h32, nullptr, tail_bits, pass_bits)) return -1;
+  if (status) for (size_t i = 0; i < n; i++) status[i] = (int8_t)g16p_quot_status(n, i, st3.data(), violated.data());
+  return 0;
+}
+// g16p_scalars_kernel on one witness: w32 = z | r | s, h32 = the N coefficients of the quotient, one mask byte per query point, flags2 = non-canonical, unsatisfied
+// -> sa, sb (n_vars + 2 scalars each), sc (n_aux + N + 2)
+__attribute__((visibility("default"))) int nbls_sim_g16p_scalars(unsigned log2_n, size_t n_vars, size_t n_public, const uint8_t* w32, const uint8_t* h32, const uint8_t* mask_a,
+                                                                 const uint8_t* mask_b, const uint8_t* mask_l, const uint8_t* flags2, uint8_t* sa, uint8_t* sb, uint8_t* sc) {
+  if (log2_n < 1 || log2_n > 21 || !n_public || n_vars <= n_public || !w32 || !h32 || !mask_a || !mask_b || (n_vars - n_public - 1 && !mask_l) || !flags2 || !sa || !sb || !sc) return -1;
+  uint8_t flags[G16P_FLAGS] = {0};
+  flags[G16P_F_NONCANON] = flags2[0]; flags[G16P_F_UNSAT] = flags2[1];
+  const G16pScalars S{n_vars, n_public, (uint64_t)1 << log2_n, w32, h32, mask_a, mask_b, mask_l, flags, sa, sb, sc};
+  const uint64_t count = g16p_scalar_count(n_vars, n_public, S.N);
+  for (uint64_t i = 0; i < count; i++) g16p_scalar_element(S, g_lanes_down ? count - 1 - i : i);
   return 0;
 }
 __attribute__((visibility("default"))) int nbls_sim_program_count() { return (int)P_COUNT; }

@@ -25,6 +25,13 @@ def lib_path():
     return os.environ.get('NBLS_LIBRARY') or os.path.join(_HERE, 'libnbls.so')   # NBLS_LIBRARY: explicit path of the engine library
 
 
+class Groth16PkDesc(C.Structure):
+    """nbls_groth16_pk_desc (include/nbls.h): the R1CS matrices in CSR form and the proving key's compressed points"""
+    _fields_ = ([('log2_n', C.c_uint), ('n_vars', C.c_size_t), ('n_public', C.c_size_t), ('n_constraints', C.c_size_t)] +
+                [(m + f, C.c_void_p) for m in 'abc' for f in ('_rows', '_cols', '_vals32')] +
+                [(f, C.c_void_p) for f in ('alpha_g1_48', 'beta_g1_48', 'beta_g2_96', 'delta_g1_48', 'delta_g2_96', 'a_query48', 'b_g1_query48', 'b_g2_query96', 'l_query48', 'h_query48')])
+
+
 def load_library():
     p = lib_path()
     if not os.path.exists(p):
@@ -117,6 +124,13 @@ def load_library():
     lib.nbls_groth16_verify.argtypes = [vp, vp, sz, vp, vp, vp, C.POINTER(i32), vp]
     lib.nbls_groth16_prepare_inputs.argtypes = [vp, vp, sz, vp, vp, vp]
     lib.nbls_groth16_input_sums.argtypes = [vp, sz, sz, vp, vp, vp, vp, vp]
+    lib.nbls_groth16_pk_create.argtypes = [vp, C.POINTER(Groth16PkDesc), vp, C.POINTER(vp)]
+    lib.nbls_groth16_pk_destroy.argtypes = [vp]
+    lib.nbls_groth16_pk_destroy.restype = None
+    lib.nbls_groth16_pk_params.argtypes = [vp, C.POINTER(C.c_uint), C.POINTER(sz), C.POINTER(sz)]
+    lib.nbls_groth16_pk_wiped.argtypes = [vp, vp, C.POINTER(i32)]
+    lib.nbls_groth16_prove.argtypes = [vp, vp, sz, vp, vp, vp, vp]
+    lib.nbls_groth16_quotient.argtypes = [vp, C.c_uint, sz, vp, vp, vp, vp, vp]
     lib.nbls_keyset_create.argtypes = [vp, sz, vp, vp, C.POINTER(vp)]
     lib.nbls_keyset_destroy.argtypes = [vp]
     lib.nbls_keyset_destroy.restype = None
@@ -261,6 +275,27 @@ class Groth16Vk(_DeviceHandle):
     @property
     def inputs(self):
         return self._get('nbls_groth16_vk_inputs', C.c_size_t)[0]
+
+
+class Groth16Pk(_DeviceHandle):
+    """A Groth16 proving key in device memory (nbls_groth16_pk_create; Engine.groth16_pk): the R1CS matrices, the decoded query points as the arrays the sums read, and the
+    workspace of a proof.  Usable from every Engine on its device, one proof at a time.  Freed by close() or when the object goes away."""
+    _destroy, _thing = 'nbls_groth16_pk_destroy', 'key'
+
+    def _params(self):
+        return self._get('nbls_groth16_pk_params', C.c_uint, C.c_size_t, C.c_size_t)
+
+    @property
+    def log2_n(self):
+        return self._params()[0]
+
+    @property
+    def n_vars(self):
+        return self._params()[1]
+
+    @property
+    def n_public(self):
+        return self._params()[2]
 
 
 class KzgSetupError(NblsError):
@@ -705,6 +740,84 @@ class Engine:
         self._chk(self.lib.nbls_groth16_input_sums(self.h, n, m, mat, b''.join(self._fr32(w) for w in weights), None if pre is None else bytes(bytearray(int(p) & 0xff for p in pre)), out, st))
         raw = out.raw
         return [int.from_bytes(raw[32 * j:32 * j + 32], 'big') for j in range(m + 1)], list(st.raw[:n])
+
+    # ---- the Groth16 prover (include/nbls.h: nbls_groth16_pk_*, nbls_groth16_prove, nbls_groth16_quotient)
+    def groth16_pk(self, log2_n, n_vars, n_public, matrices, alpha_g1_48, beta_g1_48, beta_g2_96, delta_g1_48, delta_g2_96, a_query48, b_g1_query48, b_g2_query96, l_query48,
+                   h_query48):
+        """matrices: A, B, C, each a list of rows (at most 2^log2_n of them, the same number in all three), a row a list of (column, coefficient) with the coefficient an int
+        or 32 bytes; the queries: lists of compressed points or their concatenation (n_vars, n_vars, n_vars, n_vars - n_public - 1, 2^log2_n - 1 of them) -> Groth16Pk.
+        Raises KzgSetupError (with the statuses in the order alpha_g1, beta_g1, beta_g2, delta_g1, delta_g2, a_query, b_g1_query, b_g2_query, l_query, h_query) when an
+        entry does not decode or a zero point stands where none may"""
+        join = lambda x: bytes(x) if isinstance(x, (bytes, bytearray, memoryview)) else b''.join(bytes(p) for p in x)
+        pts = [bytes(alpha_g1_48), bytes(beta_g1_48), bytes(beta_g2_96), bytes(delta_g1_48), bytes(delta_g2_96), join(a_query48), join(b_g1_query48), join(b_g2_query96),
+               join(l_query48), join(h_query48)]
+        if not 1 <= log2_n <= 21 or len(matrices) != 3 or len({len(m) for m in matrices}) != 1 or len(matrices[0]) > 1 << log2_n or not 0 < n_public < n_vars:
+            raise NblsError('groth16_pk: log2_n in 1 .. 21, 0 < n_public < n_vars, three matrices of the same number of rows, at most 2^log2_n')
+        n_aux = n_vars - n_public - 1
+        if [len(p) for p in pts] != [48, 48, 96, 48, 96, 48 * n_vars, 48 * n_vars, 96 * n_vars, 48 * n_aux, 48 * ((1 << log2_n) - 1)]:
+            raise NblsError('groth16_pk: 48 / 96 bytes per fixed point, n_vars points in a_query, b_g1_query and b_g2_query, n_vars - n_public - 1 in l_query, 2^log2_n - 1 in h_query')
+        d = Groth16PkDesc(log2_n=log2_n, n_vars=n_vars, n_public=n_public, n_constraints=len(matrices[0]))
+        keep = []
+        for name, mat in zip('abc', matrices):
+            offs, cols, vals = [0], [], []
+            for row in mat:
+                for col, v in row:
+                    cols.append(int(col)); vals.append(self._fr32(v))
+                offs.append(len(cols))
+            if any(not 0 <= c < 1 << 32 for c in cols):
+                raise NblsError('groth16_pk: a column index outside 32 bits')
+            bufs = ((C.c_uint32 * len(offs))(*offs), (C.c_uint32 * max(len(cols), 1))(*cols), C.create_string_buffer(b''.join(vals), max(32 * len(vals), 1)))
+            keep.append(bufs)
+            for f, b in zip(('_rows', '_cols', '_vals32'), bufs):
+                setattr(d, name + f, C.cast(b, C.c_void_p))
+        for f, p in zip(('alpha_g1_48', 'beta_g1_48', 'beta_g2_96', 'delta_g1_48', 'delta_g2_96', 'a_query48', 'b_g1_query48', 'b_g2_query96', 'l_query48', 'h_query48'), pts):
+            b = C.create_string_buffer(p, max(len(p), 1))
+            keep.append(b)
+            setattr(d, f, C.cast(b, C.c_void_p))
+        st = C.create_string_buffer(5 + 3 * n_vars + n_aux + (1 << log2_n) - 1)
+        h = C.c_void_p()
+        r = self.lib.nbls_groth16_pk_create(self.h, C.byref(d), st, C.byref(h))
+        if r != 0:
+            raise KzgSetupError('groth16_pk: %s (code %d)' % (self.lib.nbls_strerror(r).decode(), r), r, st.raw)
+        pk = Groth16Pk(self.lib, h)
+        pk.status = st.raw          # 1 marks a masked (zero) query point
+        return pk
+
+    def groth16_prove(self, pk, witnesses, rs=None):
+        """one proof per witness z = (1, x_1 .. x_m, aux ..) (a list of n_vars ints or 32-byte values) -> (list of 192-byte proofs A || B || C, status list: 0; 21 an
+        element of z, r or s is >= r; 24 the witness does not satisfy the constraints or z_0 != 1; 1 A or B is the zero point -- the proof is then 192 zero bytes).
+        rs: one (r, s) per witness, or None: drawn from the OS.  The witness and (r, s) are wiped from the engine's buffers before the call returns"""
+        if getattr(pk, 'h', None) is None:
+            raise NblsError('groth16_prove: the key is closed')
+        nv, n = pk.n_vars, len(witnesses)
+        if not n or any(len(z) != nv for z in witnesses) or (rs is not None and (len(rs) != n or any(len(p) != 2 for p in rs))):
+            raise NblsError('groth16_prove: one witness or more of %d elements each, and one pair (r, s) per witness or None' % nv)
+        raw = b''.join(self._fr32(v) for z in witnesses for v in z)
+        out, st = C.create_string_buffer(192 * n), C.create_string_buffer(n)
+        self._chk(self.lib.nbls_groth16_prove(self.h, pk.h, n, raw, None if rs is None else b''.join(self._fr32(v) for p in rs for v in p), out, st))
+        o = out.raw
+        return [o[192 * i:192 * i + 192] for i in range(n)], list(st.raw[:n])
+
+    def groth16_pk_wiped(self, pk):
+        """for tests: True when the key's secret arrays (the staged witness and (r, s), z, the three vectors and h, the scalar arrays) read back as zeros"""
+        if getattr(pk, 'h', None) is None:
+            raise NblsError('groth16_pk_wiped: the key is closed')
+        w = C.c_int(0)
+        self._chk(self.lib.nbls_groth16_pk_wiped(self.h, pk.h, C.byref(w)))
+        return bool(w.value)
+
+    def groth16_quotient(self, log2_n, a, b, c):
+        """h = (a b - c) / (X^N - 1) for n triples of N = 2^log2_n values in bit-reversed order (lists of rows of ints or 32-byte values, or concatenated bytes) -> (list of
+        the N coefficients of every h as ints, status list: 21 = an element is >= r (the row is all-zero), 24 = a_j b_j != c_j somewhere (the row is unspecified))"""
+        raws = [bytes(v) if isinstance(v, (bytes, bytearray, memoryview)) else b''.join(self._fr32(x) for row in v for x in row) for v in (a, b, c)]
+        row = 32 << log2_n
+        if not 1 <= log2_n <= 22 or len(raws[0]) % row or len({len(x) for x in raws}) != 1:
+            raise NblsError('groth16_quotient: log2_n in 1 .. 22 and three arrays of the same number of rows of %d bytes' % row)
+        n = len(raws[0]) // row
+        out, st = C.create_string_buffer(max(len(raws[0]), 1)), C.create_string_buffer(max(n, 1))
+        self._chk(self.lib.nbls_groth16_quotient(self.h, log2_n, n, raws[0], raws[1], raws[2], out, st))
+        o = out.raw
+        return [[int.from_bytes(o[row * i + 32 * j:row * i + 32 * j + 32], 'big') for j in range(1 << log2_n)] for i in range(n)], list(st.raw[:n])
 
     # ---- KZG, the prover's side (include/nbls.h: nbls_kzg_setup_*, nbls_fr_quotient_roots, nbls_kzg_commit_blobs, nbls_kzg_compute_proofs, nbls_kzg_compute_blob_proofs)
     def kzg_setup(self, log2_n, lagrange48):
@@ -1205,6 +1318,10 @@ class Engine:
     def set_groth16_chunk(self, proofs):
         """proofs that the per-proof pass of groth16_verify and groth16_prepare_inputs hand to the batched MSM in one pass (NBLS_TUNE_G16_CHUNK = 22; 0: as many as its bounds take)"""
         self._chk(self.lib.nbls_set_tuning(self.h, 22, int(proofs)))
+
+    def set_groth16_row_wave(self, entries):
+        """matrix entries from which groth16_prove sums a row by a whole wavefront instead of one lane (NBLS_TUNE_G16P_ROW_WAVE = 31; 0: the default).  The bytes do not depend on it"""
+        self._chk(self.lib.nbls_set_tuning(self.h, 31, int(entries)))
 
     def set_verify_pipeline(self, chunks=None, last_pct=None, pipe_min=None):
         """verifyBatch as a software pipeline (NBLS_TUNE_VERIFY_CHUNKS / _LAST_PCT / _PIPE_MIN): number of chunks (0 / 1: one), size of the last chunk in

@@ -124,6 +124,11 @@ export declare class PointG1 {
   static readonly Groth16Vk: typeof Groth16Vk;
   static verifyGroth16Batch(vk: Groth16Vk, proofs: Hex[] | Uint8Array, inputs: ShareId[][] | Uint8Array, opts?: KzgOptions): KzgResult;
   static verifyGroth16BatchAsync(vk: Groth16Vk, proofs: Hex[] | Uint8Array, inputs: ShareId[][] | Uint8Array, opts?: KzgOptions): Promise<KzgResult>;
+  /** The Groth16 prover: one proof (192 bytes, A || B || C compressed) per witness z = [1, x_1 .. x_m, aux ..] against a proving key on the device; rs: [r, s] per witness, or
+   *  null: drawn from the OS.  status per proof: 0, 21 an element >= CURVE.r, 24 the witness does not satisfy the constraints, 1 A or B is the zero point (192 zero bytes then) */
+  static readonly Groth16Pk: typeof Groth16Pk;
+  static groth16ProvingKey(key: Groth16PkInit): Groth16Pk;
+  static groth16Prove(pk: Groth16Pk, witnesses: ShareId[][] | Uint8Array, rs?: [ShareId, ShareId][] | null): { proofs: Uint8Array[]; status: Uint8Array };
   isZero(): boolean; equals(rhs: PointG1): boolean; negate(): PointG1; add(rhs: PointG1): PointG1; subtract(rhs: PointG1): PointG1; double(): PointG1;
   multiply(scalar: bigint | number): PointG1; multiplyUnsafe(scalar: bigint | number): PointG1; multiplyPrecomputed(scalar: bigint | number): PointG1;
   assertValidity(): this; toAffine(): [Fp, Fp]; toRawBytes(isCompressed?: boolean): Uint8Array; toHex(isCompressed?: boolean): string;
@@ -190,6 +195,20 @@ declare class KzgMonomialSetup {
 declare class Groth16Vk {
   constructor(key: { alpha: PointG1 | Hex; beta: PointG2 | Hex; gamma: PointG2 | Hex; delta: PointG2 | Hex; ic: (PointG1 | Hex)[] });
   readonly inputs: number;
+  close(): void;
+}
+/** An R1CS instance and its Groth16 proving key: a matrix is an array of rows (at most 2^log2n, the same number in all three), a row an array of [column, coefficient];
+ *  the queries hold nVars, nVars, nVars, nVars - nPublic - 1 and 2^log2n - 1 compressed points; a zero point is valid in the four per-variable queries */
+export interface Groth16PkInit {
+  log2n: number; nVars: number; nPublic: number; matrices: [number, ShareId][][][];
+  alphaG1: PointG1 | Hex; betaG1: PointG1 | Hex; betaG2: PointG2 | Hex; deltaG1: PointG1 | Hex; deltaG2: PointG2 | Hex;
+  aQuery: (PointG1 | Hex)[]; bG1Query: (PointG1 | Hex)[]; bG2Query: (PointG2 | Hex)[]; lQuery: (PointG1 | Hex)[]; hQuery: (PointG1 | Hex)[];
+}
+/** A Groth16 proving key decoded once into device memory with the workspace of a proof; close() frees it.  Reading bellman's or snarkjs's key files stays with the caller.
+ *  Reached as PointG1.Groth16Pk / PointG1.groth16ProvingKey */
+declare class Groth16Pk {
+  constructor(key: Groth16PkInit);
+  readonly log2n: number; readonly nVars: number; readonly nPublic: number;
   close(): void;
 }
 /** status: one byte per polynomial (0; 21 an element or the shift is >= CURVE.r; 5 the shift is 0: the row is then all-zero) */

@@ -421,6 +421,65 @@ function groth16Args(vk, proofs, inputs, opts) {
 function verifyGroth16Batch(vk, proofs, inputs, opts) { const a = groth16Args(vk, proofs, inputs, opts); return kzgResult(native.groth16Verify(...a), a[4]); }
 async function verifyGroth16BatchAsync(vk, proofs, inputs, opts) { const a = groth16Args(vk, proofs, inputs, opts); return kzgResult(await native.groth16VerifyAsync(...a), a[4]); }
 
+// ---- The Groth16 prover (nbls_groth16_pk_*, nbls_groth16_prove; not in the reference).  groth16ProvingKey({log2n, nVars, nPublic, matrices: [A, B, C], alphaG1, betaG1,
+// betaG2, deltaG1, deltaG2, aQuery, bG1Query, bG2Query, lQuery, hQuery}): a matrix is an array of rows (the same number in all three, at most 2^log2n), a row an array of
+// [column, coefficient] with the coefficient a field element (bigint | number | hex | 32 bytes, canonical); G1 points 48 compressed bytes, hex or PointG1, G2 points 96
+// compressed bytes, hex or PointG2; a zero point (c0 00..) is valid in the four per-variable queries.  Decoded once, close() frees it; a refused key throws with the decoder's statuses as `status`.
+// groth16Prove(pk, witnesses, rs): witnesses = an array of assignments z = [1, x_1 .. x_m, aux ..] of nVars field elements each, or ONE packed Uint8Array; rs = an array of
+// [r, s] per witness, or null / undefined: drawn from the OS.  -> { proofs: n x 192 bytes (A || B || C compressed), status } -- status per proof 0 ok, 21 an element >= CURVE.r,
+// 24 the witness does not satisfy the constraints, 1 A or B is the zero point; a proof whose status is not 0 is 192 zero bytes.  The library wipes its own copies of the
+// witness and of (r, s); the arrays passed in are the caller's
+class Groth16Pk {
+  constructor(key) {
+    if (!key || !Array.isArray(key.matrices) || key.matrices.length !== 3) throw new Error('Invalid key: expected log2n, nVars, nPublic, three matrices and the key points');
+    const { log2n, nVars, nPublic } = key, rows = key.matrices[0].length;
+    if (!Number.isInteger(log2n) || log2n < 1 || log2n > 21 || !Number.isInteger(nVars) || !Number.isInteger(nPublic) || nPublic < 1 || nVars <= nPublic)
+      throw new Error('Invalid key: expected log2n in 1 .. 21 and 0 < nPublic < nVars');
+    if (key.matrices.some((m) => m.length !== rows) || rows > 2 ** log2n) throw new Error('Invalid key: expected three matrices of the same number of rows, at most 2^log2n');
+    ensureInit();
+    const args = [Uint32Array.of(log2n, nVars, nPublic, rows)];
+    for (const m of key.matrices) {
+      const offs = new Uint32Array(rows + 1), cols = [], vals = [];
+      m.forEach((row, j) => { for (const [c, v] of row) { cols.push(c); vals.push(v); } offs[j + 1] = cols.length; });
+      args.push(offs, Uint32Array.from(cols), kzgPack(vals, 32, 'coefficient', shareIdBytes));
+    }
+    const g1 = (p, what) => { const b = kzgG1(p); if (b.length !== 48) throw new Error('Invalid ' + what + ': expected 48 compressed bytes'); return b; };
+    args.push(g1(key.alphaG1, 'alphaG1'), g1(key.betaG1, 'betaG1'), g16G2(key.betaG2, 'betaG2'), g1(key.deltaG1, 'deltaG1'), g16G2(key.deltaG2, 'deltaG2'));
+    const query = (q, count, width, what, toBytes) => { if (!q || q.length !== count) throw new Error('Invalid ' + what + ': expected ' + count + ' points'); return kzgPack(q, width, what, toBytes); };
+    args.push(query(key.aQuery, nVars, 48, 'aQuery', kzgG1), query(key.bG1Query, nVars, 48, 'bG1Query', kzgG1), query(key.bG2Query, nVars, 96, 'bG2Query', (p) => g16G2(p, 'bG2Query')),
+      query(key.lQuery, nVars - nPublic - 1, 48, 'lQuery', kzgG1), query(key.hQuery, 2 ** log2n - 1, 48, 'hQuery', kzgG1));
+    this.log2n = log2n; this.nVars = nVars; this.nPublic = nPublic;
+    try { this.handle = native.groth16PkCreate(...args); } catch (e) {
+      if (e && e.nblsCode === -5) { const err = new Error('Invalid key: a point does not decode, is outside the subgroup or is a zero point where none may stand'); err.status = e.status; throw err; }
+      throw e;
+    }
+  }
+  close() { if (this.handle) native.groth16PkDestroy(this.handle); this.handle = null; }
+}
+function groth16ProvingKey(key) { return new Groth16Pk(key); }
+function groth16Prove(pk, witnesses, rs) {
+  if (!(pk instanceof Groth16Pk) || !pk.handle) throw new Error('Expected an open Groth16Pk');
+  let ws = witnesses;
+  if (!(witnesses instanceof Uint8Array)) {
+    if (!witnesses.length) throw new Error('Expected one witness or more');
+    ws = new Uint8Array(witnesses.length * pk.nVars * 32);
+    witnesses.forEach((z, i) => {
+      if (z.length !== pk.nVars) throw new Error('Invalid witness: expected ' + pk.nVars + ' field elements');
+      ws.set(kzgPack(z, 32, 'field element', shareIdBytes), i * pk.nVars * 32);
+    });
+  }
+  const n = ws.length / (pk.nVars * 32);
+  if (!n || !Number.isInteger(n)) throw new Error('Expected one witness or more of ' + pk.nVars + ' field elements of 32 bytes');
+  let pairs = null;
+  if (rs !== null && rs !== undefined) {
+    if (rs.length !== n) throw new Error('Expected one pair [r, s] per witness');
+    pairs = new Uint8Array(n * 64);
+    rs.forEach((p, i) => { if (p.length !== 2) throw new Error('Expected one pair [r, s] per witness'); pairs.set(kzgPack(p, 32, 'blinding scalar', shareIdBytes), i * 64); });
+  }
+  const res = native.groth16Prove(pk.handle, ws, pairs);
+  return { proofs: Array.from({ length: n }, (_, i) => res.out.subarray(192 * i, 192 * i + 192)), status: res.status };
+}
+
 // Points are held as affine wire bytes (what the engine consumes) or as the zero point.  The reference's constructor form
 // new PointG1(x: Fp, y: Fp, z?: Fp) (index.ts:291) is accepted too: the projective triple is made affine on the host.
 class PointG1 {
@@ -573,6 +632,10 @@ class PointG1 {
   static get Groth16Vk() { return Groth16Vk; }
   static verifyGroth16Batch(vk, proofs, inputs, opts) { return verifyGroth16Batch(vk, proofs, inputs, opts); }
   static verifyGroth16BatchAsync(vk, proofs, inputs, opts) { return verifyGroth16BatchAsync(vk, proofs, inputs, opts); }
+  // the Groth16 prover (above): a proving key on the device and proofs from witnesses
+  static get Groth16Pk() { return Groth16Pk; }
+  static groth16ProvingKey(key) { return groth16ProvingKey(key); }
+  static groth16Prove(pk, witnesses, rs) { return groth16Prove(pk, witnesses, rs); }
   equals(rhs) { return this.zero === rhs.zero && (this.zero || bytesToHex(this.aff) === bytesToHex(rhs.aff)); }
   // reference index.ts:359-381
   toHex(isCompressed = false) {

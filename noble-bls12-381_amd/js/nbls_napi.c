@@ -27,6 +27,7 @@ SYM(nbls_kzg_setup_create) SYM(nbls_kzg_setup_destroy) SYM(nbls_kzg_setup_log2n)
 SYM(nbls_fr_ntt) SYM(nbls_kzg_compute_cells) SYM(nbls_kzg_monomial_create) SYM(nbls_kzg_monomial_destroy) SYM(nbls_kzg_monomial_log2n) SYM(nbls_kzg_compute_cells_and_proofs) SYM(nbls_kzg_verify_cells)
 SYM(nbls_kzg_recover_cells) SYM(nbls_kzg_recover_cells_and_proofs)
 SYM(nbls_groth16_vk_create) SYM(nbls_groth16_vk_destroy) SYM(nbls_groth16_vk_inputs) SYM(nbls_groth16_verify)
+SYM(nbls_groth16_pk_create) SYM(nbls_groth16_pk_destroy) SYM(nbls_groth16_pk_params) SYM(nbls_groth16_prove)
 static nbls_ctx* ctx;
 static nbls_multi* multi;   /* several GPUs behind one handle (initMulti): ctx is then its first context; the batch calls shard over all of them */
 #define MULTI() (multi && p_nbls_multi_device_count(multi) > 1)
@@ -597,15 +598,16 @@ static napi_value KzgVerifyBlobsAsync(napi_env env, napi_callback_info info) { r
  *   kzgSetupDestroy(handle)              frees it now; the handle is dead afterwards.  Not while an asynchronous call uses it
  *   kzgProve(kind, handle, blobs, aux)   kind 0: commitments (aux null) -> out = n x 48; 1: proofs at the points aux = z32 -> out = n x 48 proofs, then n x 32 values y;
  *                                        2: blob proofs, aux = the commitments or null -> out = n x 48 commitments, then n x 48 proofs.  status = one byte per blob.  + Async */
-/* The device handles (a Lagrange setup, a monomial setup, a Groth16 key) travel as one kind of external: a box that knows which destroy function its handle takes.  h == NULL:
+/* The device handles (a Lagrange setup, a monomial setup, a Groth16 verifying key, a Groth16 proving key) travel as one kind of external: a box that knows which destroy function its handle takes.  h == NULL:
  * destroyed already.  box_wrap is the tail of the three create calls: a refused create throws the library's error with the statuses as `status`; else the handle is wrapped,
  * or destroyed where it cannot be */
-typedef enum { BOX_SETUP, BOX_MONOMIAL, BOX_G16_VK } box_kind;
+typedef enum { BOX_SETUP, BOX_MONOMIAL, BOX_G16_VK, BOX_G16_PK } box_kind;
 typedef struct { void* h; box_kind kind; } handle_box;
 static void box_destroy(handle_box* b) {
   if (!b->h) return;
   if (b->kind == BOX_SETUP) { if (p_nbls_kzg_setup_destroy) p_nbls_kzg_setup_destroy((nbls_kzg_setup*)b->h); }
   else if (b->kind == BOX_MONOMIAL) { if (p_nbls_kzg_monomial_destroy) p_nbls_kzg_monomial_destroy((nbls_kzg_monomial*)b->h); }
+  else if (b->kind == BOX_G16_PK) { if (p_nbls_groth16_pk_destroy) p_nbls_groth16_pk_destroy((nbls_groth16_pk*)b->h); }
   else if (p_nbls_groth16_vk_destroy) p_nbls_groth16_vk_destroy((nbls_groth16_vk*)b->h);
   b->h = NULL;
 }
@@ -822,6 +824,59 @@ static napi_value groth16_verify_call(napi_env env, napi_callback_info info, int
 static napi_value Groth16Verify(napi_env env, napi_callback_info info) { return groth16_verify_call(env, info, 0); }
 static napi_value Groth16VerifyAsync(napi_env env, napi_callback_info info) { return groth16_verify_call(env, info, 1); }
 
+/* The Groth16 prover (nbls_groth16_pk_*, nbls_groth16_prove), synchronous:
+ *   groth16PkCreate(dims, aRows, aCols, aVals, bRows, bCols, bVals, cRows, cCols, cVals, alphaG1, betaG1, betaG2, deltaG1, deltaG2, aQuery, bG1Query, bG2Query, lQuery, hQuery)
+ *       dims = Uint32Array [log2n, nVars, nPublic, nConstraints]; rows / cols: Uint32Array (CSR), vals: 32 bytes a coefficient; the points compressed -> a handle; a refused
+ *       key throws with the library's code as `nblsCode` and the statuses (the descriptor's order) as `status`
+ *   groth16PkDestroy(handle)
+ *   groth16Prove(handle, witness32, rs64 | null) -> {out: n x 192 bytes, status: n bytes}; the arrays are the caller's to wipe */
+static napi_value Groth16PkCreate(napi_env env, napi_callback_info info) {
+  ARGS(20); NEED_CTX(); BYTES(0, dims, ldims);
+  if (ldims != 16) { napi_throw_type_error(env, NULL, "expected a Uint32Array [log2n, nVars, nPublic, nConstraints]"); return NULL; }
+  const uint32_t* dm = (const uint32_t*)dims;
+  const size_t L = dm[0], nv = dm[1], m = dm[2], nc = dm[3];
+  if (L < 1 || L > 21 || !m || nv <= m || nc > ((size_t)1 << L)) { napi_throw_range_error(env, NULL, "log2n in 1 .. 21, 0 < nPublic < nVars, nConstraints <= 2^log2n"); return NULL; }
+  const size_t N = (size_t)1 << L, na = nv - m - 1;
+  uint8_t* p[19]; size_t len[19];
+  for (int i = 0; i < 19; i++) if (!get_bytes(env, argv[1 + i], &p[i], &len[i])) { napi_throw_type_error(env, NULL, "expected typed arrays"); return NULL; }
+  for (int k = 0; k < 3; k++) {   /* the offsets say how long the other two arrays must be; the library checks what they hold */
+    if (len[3 * k] != (nc + 1) * 4) { napi_throw_range_error(env, NULL, "a matrix needs nConstraints + 1 offsets"); return NULL; }
+    const size_t nnz = ((const uint32_t*)p[3 * k])[nc];
+    if (len[3 * k + 1] != nnz * 4 || len[3 * k + 2] != nnz * 32) { napi_throw_range_error(env, NULL, "a matrix needs as many columns and 32-byte coefficients as its last offset says"); return NULL; }
+  }
+  const size_t want[10] = {48, 48, 96, 48, 96, nv * 48, nv * 48, nv * 96, na * 48, (N - 1) * 48};
+  for (int i = 0; i < 10; i++) if (len[9 + i] != want[i]) { napi_throw_range_error(env, NULL, "48 / 96 bytes a point: nVars points a per-variable query, nVars - nPublic - 1 in lQuery, 2^log2n - 1 in hQuery"); return NULL; }
+  nbls_groth16_pk_desc d; memset(&d, 0, sizeof d);
+  d.log2_n = (unsigned)L; d.n_vars = nv; d.n_public = m; d.n_constraints = nc;
+  d.a_rows = (const uint32_t*)p[0]; d.a_cols = (const uint32_t*)p[1]; d.a_vals32 = p[2]; d.b_rows = (const uint32_t*)p[3]; d.b_cols = (const uint32_t*)p[4]; d.b_vals32 = p[5];
+  d.c_rows = (const uint32_t*)p[6]; d.c_cols = (const uint32_t*)p[7]; d.c_vals32 = p[8];
+  d.alpha_g1_48 = p[9]; d.beta_g1_48 = p[10]; d.beta_g2_96 = p[11]; d.delta_g1_48 = p[12]; d.delta_g2_96 = p[13];
+  d.a_query48 = p[14]; d.b_g1_query48 = p[15]; d.b_g2_query96 = p[16]; d.l_query48 = p[17]; d.h_query48 = p[18];
+  uint8_t* st; napi_value vs = new_u8(env, 5 + 3 * nv + na + N - 1, &st); ALLOCATED(vs);
+  handle_box* box = box_new(env, BOX_G16_PK); if (!box) return NULL;
+  nbls_groth16_pk* pk = NULL;
+  const int rc = p_nbls_groth16_pk_create(ctx, &d, (int8_t*)st, &pk);
+  box->h = pk;
+  return box_wrap(env, box, rc, vs);
+}
+static napi_value Groth16PkDestroy(napi_env env, napi_callback_info info) { return box_destroy_call(env, info, "expected a Groth16 proving key handle"); }
+static napi_value Groth16Prove(napi_env env, napi_callback_info info) {
+  ARGS(3); NEED_CTX(); BYTES(1, w, lw);
+  handle_box* box = NULL;
+  if (napi_get_value_external(env, argv[0], (void**)&box) != napi_ok || !box || !box->h || box->kind != BOX_G16_PK) { napi_throw_type_error(env, NULL, "expected a live Groth16 proving key handle"); return NULL; }
+  unsigned L = 0; size_t nv = 0, m = 0; p_nbls_groth16_pk_params((nbls_groth16_pk*)box->h, &L, &nv, &m);
+  const size_t n = nv ? lw / (nv * 32) : 0;
+  uint8_t* rs = NULL; size_t lrs = 0;
+  napi_valuetype t; napi_typeof(env, argv[2], &t);
+  if (t != napi_null && t != napi_undefined && !get_bytes(env, argv[2], &rs, &lrs)) { napi_throw_type_error(env, NULL, "expected Uint8Array or null for (r, s)"); return NULL; }
+  if (!n || n > 65536 || lw != n * nv * 32 || (rs && lrs != n * 64)) { napi_throw_range_error(env, NULL, "1 .. 65536 witnesses of nVars elements of 32 bytes, and 64 bytes of (r, s) a witness or null"); return NULL; }
+  uint8_t *out, *st; napi_value vo = new_u8(env, n * 192, &out), vs = new_u8(env, n, &st); ALLOCATED(vo); ALLOCATED(vs);
+  const int rc = p_nbls_groth16_prove(ctx, (nbls_groth16_pk*)box->h, n, w, rs, out, (int8_t*)st);
+  if (rc) { napi_throw(env, thr_error(env, rc)); return NULL; }
+  napi_value res; napi_create_object(env, &res); napi_set_named_property(env, res, "out", vo); napi_set_named_property(env, res, "status", vs);
+  return res;
+}
+
 static napi_value ModuleInit(napi_env env, napi_value exports) {
   const char* path = getenv("NBLS_LIB");
   char buf[4096];
@@ -839,6 +894,7 @@ static napi_value ModuleInit(napi_env env, napi_value exports) {
   LOAD(nbls_fr_ntt) LOAD(nbls_kzg_compute_cells) LOAD(nbls_kzg_monomial_create) LOAD(nbls_kzg_monomial_destroy) LOAD(nbls_kzg_monomial_log2n) LOAD(nbls_kzg_compute_cells_and_proofs) LOAD(nbls_kzg_verify_cells)
   LOAD(nbls_kzg_recover_cells) LOAD(nbls_kzg_recover_cells_and_proofs)
   LOAD(nbls_groth16_vk_create) LOAD(nbls_groth16_vk_destroy) LOAD(nbls_groth16_vk_inputs) LOAD(nbls_groth16_verify)
+  LOAD(nbls_groth16_pk_create) LOAD(nbls_groth16_pk_destroy) LOAD(nbls_groth16_pk_params) LOAD(nbls_groth16_prove)
   {   /* the ABI the addon was written against (include/nbls.h NBLS_ABI_VERSION): an older or newer library is refused at load instead of misread at run time */
     int (*abi)(void) = (int (*)(void))dlsym(lib, "nbls_abi_version");
     if (!abi || abi() != NBLS_ABI_VERSION) { napi_throw_error(env, NULL, "libnbls.so: ABI version differs from the one this addon was built for (include/nbls.h NBLS_ABI_VERSION)"); return exports; }
@@ -868,7 +924,8 @@ static napi_value ModuleInit(napi_env env, napi_value exports) {
     {"kzgRecoverCellsAsync", 0, KzgRecoverCellsAsync, 0, 0, 0, napi_enumerable, 0}, {"kzgRecoverCellsAndProofs", 0, KzgRecoverCellsAndProofs, 0, 0, 0, napi_enumerable, 0},
     {"kzgRecoverCellsAndProofsAsync", 0, KzgRecoverCellsAndProofsAsync, 0, 0, 0, napi_enumerable, 0}, {"groth16VkCreate", 0, Groth16VkCreate, 0, 0, 0, napi_enumerable, 0},
     {"groth16VkDestroy", 0, Groth16VkDestroy, 0, 0, 0, napi_enumerable, 0}, {"groth16Verify", 0, Groth16Verify, 0, 0, 0, napi_enumerable, 0},
-    {"groth16VerifyAsync", 0, Groth16VerifyAsync, 0, 0, 0, napi_enumerable, 0}};
+    {"groth16VerifyAsync", 0, Groth16VerifyAsync, 0, 0, 0, napi_enumerable, 0}, {"groth16PkCreate", 0, Groth16PkCreate, 0, 0, 0, napi_enumerable, 0},
+    {"groth16PkDestroy", 0, Groth16PkDestroy, 0, 0, 0, napi_enumerable, 0}, {"groth16Prove", 0, Groth16Prove, 0, 0, 0, napi_enumerable, 0}};
   napi_define_properties(env, exports, sizeof d / sizeof d[0], d);
   return exports;
 }
