@@ -708,6 +708,7 @@ const char* nbls_config_describe(void);   /* "NBLS_X=value(env|default) ...": ev
    Then NBLS_TUNE_FE_HEAD_CHAIN, NBLS_TUNE_INV_PRIO and the name "fe_easy12" of nbls_extra_program_kernel (additions only, same version).
    Then nbls_fr_ntt_large, nbls_fr_ntt_dev, NBLS_TUNE_NTT_TAIL_BITS / _PASS_BITS, scratch slot 87 (additions only, same version).
    Then nbls_groth16_pk_create / _destroy / _params / _wiped, nbls_groth16_prove, nbls_groth16_quotient, NBLS_ST_G16_UNSATISFIED, NBLS_TUNE_G16P_ROW_WAVE, no scratch slot (additions only, same version).
+   Then nbls_pool_init_ex, NBLS_POOL_SPREAD_PRIORITIES, nbls_pool_stream_priority (additions only, same version).
    4 (round 6): nbls_hw_queues, NBLS_TUNE_WIDE_MAX, NBLS_TUNE_H2C_NORM_MIN, NBLS_TUNE_INV_WIDE_MAX, NBLS_TUNE_LS_MAX / _LS2_MAX (additions only); the library sets GPU_MAX_HW_QUEUES = 22 at load when the variable is unset (see nbls_pool_init below).
    3 (round 5): nbls_program_kernel, nbls_pool_*, nbls_sign_batch_dev, NBLS_TUNE_VERIFY_* / _SAC_MAX / _PT_LS2_MAX (additions only); nbls_verify_batch_partial_dev writes d_out_fp12 even when it reports a zero point or a decode error
    (contents then meaningless); 2: *_partial take *d_partial as OUT only, *_partial_into added, nbls_tower_op_batch, nbls_verify_batch_msgs_dev.  The bindings check it at load. */
@@ -726,7 +727,18 @@ int nbls_context_device(nbls_ctx* ctx);
  * nbls_hw_queues: the value in the environment (0 = unset: the runtime's default of 4); *set_by_library (may be NULL) = 1 when the library put it there. */
 int nbls_hw_queues(int* set_by_library);
 typedef struct nbls_pool nbls_pool;
-int nbls_pool_init(int device_id, int depth /* 1 .. 64 */, nbls_pool** out);
+int nbls_pool_init(int device_id, int depth /* 1 .. 64 */, nbls_pool** out);      /* = nbls_pool_init_ex(device_id, depth, 0, out) */
+/* Stream priorities against a queue cap.  The runtime's limit of GPU_MAX_HW_QUEUES hardware queues holds PER STREAM PRIORITY, not per process: streams of another priority
+ * level get queues of their own.  A process that cannot raise the variable (HIP was initialised before the library was loaded, or the host fixes the value) asks for
+ * NBLS_POOL_SPREAD_PRIORITIES: when `depth` exceeds the queues in force, context i's stream is created at priority level i mod L of the L levels of
+ * hipDeviceGetStreamPriorityRange (level 0 = the default priority), so twelve contexts on three levels run on eleven hardware queues under a cap of four (the null stream holds one queue of the default level): 3.03 M pairings/s against 2.68 M,
+ * and 3.10 M with 22 queues.  The levels are not served alike: the high level's streams finish a saturated burst first.  With depth <= queues, or one
+ * level, every stream keeps the default priority (the flag is a no-op); with depth > L x queues the surplus streams share queues as before, and the warning says so.  The priority
+ * is the QUEUE's: all contexts run the same kernels, the bytes do not depend on it.  Environment: NBLS_POOL_SPREAD = 0 / 1 overrides the flag (A/B runs), NBLS_POOL_SPREAD_LEVELS caps L.
+ * nbls_pool_stream_priority: *priority = hipStreamGetPriority of context i's stream (0 = default, negative = higher). */
+#define NBLS_POOL_SPREAD_PRIORITIES 1u
+int nbls_pool_init_ex(int device_id, int depth /* 1 .. 64 */, unsigned flags, nbls_pool** out);
+int nbls_pool_stream_priority(nbls_pool* p, int i, int* priority);
 void nbls_pool_destroy(nbls_pool* p);
 int nbls_pool_depth(const nbls_pool* p);
 nbls_ctx* nbls_pool_context(nbls_pool* p, int i);

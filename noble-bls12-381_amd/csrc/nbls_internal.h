@@ -383,6 +383,8 @@ static inline hipStream_t call_stream(nbls_ctx* ctx, void* stream) { return stre
 
 // ---- internal functions (hidden visibility; defined in runtime.cpp, tuning.cpp and the pipelines_*.cpp files)
 struct VerifyIn;
+int nbls_init_prio(int device_id, int prio, nbls_ctx** out);   // nbls_init with ctx->stream created at stream priority `prio` (0 = the default: what nbls_init passes)
+int nbls_stream_priority(nbls_ctx* ctx, int* prio);            // hipStreamGetPriority of ctx->stream
 bool checked_mode();
 bool aot_enabled();
 int upload_program(nbls_ctx* ctx, DevProgram& d, const Program& p, const int k);

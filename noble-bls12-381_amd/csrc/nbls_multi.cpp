@@ -5,7 +5,7 @@
 //     are copied device-to-device (hipMemcpyPeer over xGMI) into the first device's gather buffer, which multiplies them and runs the one
 //     shared final exponentiation.  The exchange is 576 bytes per device -- pure latency -- so no collective library is involved.
 // nbls_pool_* (the end of this file): several contexts of ONE device fed round-robin -- the in-flight form of bench.py's headline, for C callers.
-// This layer uses only the public single-device ABI (include/nbls.h) plus HIP for the peer copies.
+// This layer uses only the public single-device ABI (include/nbls.h) plus HIP for the peer copies; the pool also creates its contexts through nbls_init_prio (runtime.cpp).
 #include <hip/hip_runtime.h>
 #include <condition_variable>
 #include <cstdio>
@@ -18,6 +18,7 @@
 #include <vector>
 #include "nbls.h"
 #include "config.h"
+#include "pool_levels.h"
 
 #define EXPORT extern "C" __attribute__((visibility("default")))
 
@@ -274,14 +275,36 @@ EXPORT int nbls_hw_queues(int* set_by_library) {
   const char* v = getenv("GPU_MAX_HW_QUEUES");
   return v && *v ? atoi(v) : 0;
 }
+// Stream priorities against a queue cap (NBLS_POOL_SPREAD_PRIORITIES).  The runtime's GPU_MAX_HW_QUEUES is a limit PER STREAM PRIORITY: every priority level has its own set of
+// up to that many hardware queues (the runtime's own log line counts them per level).  A process that cannot raise the variable -- the host sets 4 in front of every command --
+// still gets a queue per stream by creating its streams at several levels: with depth > queues, context i's stream takes level i mod L of the L levels the device reports
+// (pool_levels.h; level 0 = the default priority, then high, then low), twelve contexts = four streams a level.  Measured under a cap of four: eleven queues carry the pool's
+// kernels (the null stream holds one of the default level's four, so two default-level streams share), 2.68 -> 3.03 M pairings/s, 84 % of the way to the 3.10 M of 22 queues; the
+// levels are not served alike (of a 780 ms region the high level's streams idle the last 260-280 ms, the low level's the last 40-90, the sharing pair ends it).  Two levels
+// (default + high, eight queues) give 3.01 M.  With depth <= queues nothing
+// changes (the 22-queue regime and a C caller on the library's default keep default-priority streams), and plain nbls_pool_init never asks for it.
+// NBLS_POOL_SPREAD = 0 / 1 overrides the caller's flag, NBLS_POOL_SPREAD_LEVELS caps L (2 = default and high only): A/B switches.  EXPERIMENTS.md, profiles/pool_priorities_ab.json.
+int nbls_init_prio(int device_id, int prio, nbls_ctx** out);      // runtime.cpp (nbls_internal.h)
+int nbls_stream_priority(nbls_ctx* ctx, int* prio);
+static const int POOL_SPREAD_LEVELS = 3;
 struct nbls_pool { std::vector<nbls_ctx*> ctx; std::mutex mu; size_t next = 0; int device = 0; };
 EXPORT void nbls_pool_destroy(nbls_pool* p) { if (!p) return; for (nbls_ctx* c : p->ctx) nbls_destroy(c); delete p; }
-EXPORT int nbls_pool_init(int device_id, int depth, nbls_pool** out) {
-  if (!out || depth < 1 || depth > 64) return NBLS_EINVAL;
+EXPORT int nbls_pool_init(int device_id, int depth, nbls_pool** out) { return nbls_pool_init_ex(device_id, depth, 0, out); }
+EXPORT int nbls_pool_init_ex(int device_id, int depth, unsigned flags, nbls_pool** out) {
+  if (!out || depth < 1 || depth > 64 || (flags & ~NBLS_POOL_SPREAD_PRIORITIES)) return NBLS_EINVAL;
+  const int q = nbls_hw_queues(nullptr), eff = q > 0 ? q : 4;
+  std::vector<int> levels(1, 0);      // the stream priority of every level; one level of the default priority = no spreading
+  const long spread_env = nbls::env_long("NBLS_POOL_SPREAD", -1);
+  if ((spread_env < 0 ? (flags & NBLS_POOL_SPREAD_PRIORITIES) != 0 : spread_env != 0) && depth > eff) {
+    int least = 0, greatest = 0;
+    if (hipSetDevice(device_id) != hipSuccess) return NBLS_ENOGPU;
+    if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess) return NBLS_EHIP;
+    levels = nbls::pool_priority_levels(greatest, least, (int)nbls::env_long("NBLS_POOL_SPREAD_LEVELS", POOL_SPREAD_LEVELS));
+    if (levels.size() == 1) levels[0] = 0;      // one level: nothing to spread over, the streams are hipStreamCreate's
+  }
   {
-    const int q = nbls_hw_queues(nullptr), eff = q > 0 ? q : 4;
     static bool warned = false;
-    if (depth > eff && !warned) {
+    if (depth > eff * (int)levels.size() && !warned) {
       warned = true;
       fprintf(stderr, "nbls: pool of %d contexts on %d hardware queues (GPU_MAX_HW_QUEUES %s): streams will share queues and their kernels serialise; "
                       "set GPU_MAX_HW_QUEUES >= depth (<= 22) before the first HIP call of the process\n",
@@ -291,7 +314,7 @@ EXPORT int nbls_pool_init(int device_id, int depth, nbls_pool** out) {
   nbls_pool* p = new nbls_pool(); p->device = device_id;
   for (int i = 0; i < depth; i++) {
     nbls_ctx* c = nullptr;
-    const int r = nbls_init(device_id, &c);
+    const int r = nbls_init_prio(device_id, levels[(size_t)nbls::pool_priority_level(i, depth, eff, (int)levels.size())], &c);
     if (r) { nbls_pool_destroy(p); return r; }
     p->ctx.push_back(c);
     // NBLS_PIPELINE_CHAIN=1: A/B switch (tools/ab_pipeline.sh)
@@ -308,6 +331,7 @@ EXPORT int nbls_pool_init(int device_id, int depth, nbls_pool** out) {
   *out = p;
   return NBLS_OK;
 }
+EXPORT int nbls_pool_stream_priority(nbls_pool* p, int i, int* priority) { return p && i >= 0 && i < (int)p->ctx.size() ? nbls_stream_priority(p->ctx[i], priority) : NBLS_EINVAL; }
 EXPORT int nbls_pool_depth(const nbls_pool* p) { return p ? (int)p->ctx.size() : 0; }
 EXPORT nbls_ctx* nbls_pool_context(nbls_pool* p, int i) { return p && i >= 0 && i < (int)p->ctx.size() ? p->ctx[i] : nullptr; }
 // pairing(P_i, Q_i) for n device-resident pairs (index.ts:715-722) on the next context's own stream; returns at once.  *slot (optional) = index of the context used: a caller that

@@ -305,7 +305,15 @@ int run_pow(nbls_ctx* ctx, int which, size_t n, const void* in, void* out, hipSt
   return NBLS_OK;
 }
 
-EXPORT int nbls_init(int device_id, nbls_ctx** out) {
+EXPORT int nbls_init(int device_id, nbls_ctx** out) { return nbls_init_prio(device_id, 0, out); }
+int nbls_stream_priority(nbls_ctx* ctx, int* prio) {
+  if (!ctx || !prio) return NBLS_EINVAL;
+  if (hipStreamGetPriority(ctx->stream, prio) != hipSuccess) { ctx->last_hip = (int)hipGetLastError(); return NBLS_EHIP; }
+  return NBLS_OK;
+}
+// ctx->stream at stream priority `prio` (0 = the default priority: the stream hipStreamCreate made); the flags are hipStreamCreate's, so its ordering against the null stream is unchanged.
+// The side streams keep the default priority.  A pool that spreads its contexts over the priority levels creates them through this (nbls_multi.cpp).
+int nbls_init_prio(int device_id, int prio, nbls_ctx** out) {
   if (!out) return NBLS_EINVAL;
   int count = 0;
   if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return NBLS_ENOGPU;
@@ -313,7 +321,7 @@ EXPORT int nbls_init(int device_id, nbls_ctx** out) {
   nbls_ctx* ctx = new nbls_ctx();
   ctx->device = device_id;
   if (hipSetDevice(device_id) != hipSuccess) { delete ctx; return NBLS_ENOGPU; }
-  if (hipStreamCreate(&ctx->stream) != hipSuccess) { delete ctx; return NBLS_EHIP; }
+  if (hipStreamCreateWithPriority(&ctx->stream, hipStreamDefault, prio) != hipSuccess) { delete ctx; return NBLS_EHIP; }
   if (hipMalloc(&ctx->qp_table, (size_t)QP_TABLE_ENTRIES * RAW_WORDS * 4) != hipSuccess || hipMemcpy(ctx->qp_table, qp_table_words(), (size_t)QP_TABLE_ENTRIES * RAW_WORDS * 4,
       hipMemcpyHostToDevice) != hipSuccess) { delete ctx; return NBLS_EHIP; }
   {

@@ -19,13 +19,17 @@ class PairingPipeline:
     the two-program Miller loop at every size, the final exponentiation launch by launch with its short programs inside the launches of the exponentiations next to them, eight launches a batch -- and
     fed round-robin); `engines` wraps the pool's contexts."""
 
-    def __init__(self, device_id=0, depth=12):
+    POOL_SPREAD_PRIORITIES = 1      # include/nbls.h NBLS_POOL_SPREAD_PRIORITIES
+
+    def __init__(self, device_id=0, depth=12, spread_priorities=True):
+        """spread_priorities: when `depth` exceeds the hardware queues in force (GPU_MAX_HW_QUEUES is a limit per stream priority), the contexts' streams are created
+        round-robin over the device's stream priority levels, so each gets a queue of its own; a no-op with a queue per stream (nbls_pool_init_ex)"""
         assert depth >= 1
         self.lib = load_library()
         h = C.c_void_p()
-        r = self.lib.nbls_pool_init(device_id, depth, C.byref(h))
+        r = self.lib.nbls_pool_init_ex(device_id, depth, self.POOL_SPREAD_PRIORITIES if spread_priorities else 0, C.byref(h))
         if r != 0:
-            raise NblsError('nbls_pool_init failed: %s (code %d)' % (self.lib.nbls_strerror(r).decode(), r))
+            raise NblsError('nbls_pool_init_ex failed: %s (code %d)' % (self.lib.nbls_strerror(r).decode(), r))
         self.h = h
         self.depth = depth
         self.engines = [Engine(_handle=self.lib.nbls_pool_context(self.h, i)) for i in range(depth)]
@@ -42,6 +46,17 @@ class PairingPipeline:
             self.close()
         except Exception:
             pass
+
+    def stream_priorities(self):
+        """the HIP stream priority of every context's stream (0 = default, negative = higher): the placement nbls_pool_init_ex chose"""
+        out = []
+        for i in range(self.depth):
+            v = C.c_int()
+            r = self.lib.nbls_pool_stream_priority(self.h, i, C.byref(v))
+            if r != 0:
+                raise NblsError('nbls_pool_stream_priority: code %d' % r)
+            out.append(v.value)
+        return out
 
     @property
     def slot(self):
