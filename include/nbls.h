@@ -709,6 +709,7 @@ const char* nbls_config_describe(void);   /* "NBLS_X=value(env|default) ...": ev
    Then nbls_fr_ntt_large, nbls_fr_ntt_dev, NBLS_TUNE_NTT_TAIL_BITS / _PASS_BITS, scratch slot 87 (additions only, same version).
    Then nbls_groth16_pk_create / _destroy / _params / _wiped, nbls_groth16_prove, nbls_groth16_quotient, NBLS_ST_G16_UNSATISFIED, NBLS_TUNE_G16P_ROW_WAVE, no scratch slot (additions only, same version).
    Then nbls_pool_init_ex, NBLS_POOL_SPREAD_PRIORITIES, nbls_pool_stream_priority (additions only, same version).
+   Then NBLS_POOL_BALANCE, nbls_pool_outstanding (additions only, same version).
    4 (round 6): nbls_hw_queues, NBLS_TUNE_WIDE_MAX, NBLS_TUNE_H2C_NORM_MIN, NBLS_TUNE_INV_WIDE_MAX, NBLS_TUNE_LS_MAX / _LS2_MAX (additions only); the library sets GPU_MAX_HW_QUEUES = 22 at load when the variable is unset (see nbls_pool_init below).
    3 (round 5): nbls_program_kernel, nbls_pool_*, nbls_sign_batch_dev, NBLS_TUNE_VERIFY_* / _SAC_MAX / _PT_LS2_MAX (additions only); nbls_verify_batch_partial_dev writes d_out_fp12 even when it reports a zero point or a decode error
    (contents then meaningless); 2: *_partial take *d_partial as OUT only, *_partial_into added, nbls_tower_op_batch, nbls_verify_batch_msgs_dev.  The bindings check it at load. */
@@ -737,8 +738,20 @@ int nbls_pool_init(int device_id, int depth /* 1 .. 64 */, nbls_pool** out);    
  * is the QUEUE's: all contexts run the same kernels, the bytes do not depend on it.  Environment: NBLS_POOL_SPREAD = 0 / 1 overrides the flag (A/B runs), NBLS_POOL_SPREAD_LEVELS caps L.
  * nbls_pool_stream_priority: *priority = hipStreamGetPriority of context i's stream (0 = default, negative = higher). */
 #define NBLS_POOL_SPREAD_PRIORITIES 1u
+/* Who gets the next batch.  Round-robin gives every context the same number of batches whatever the rate its queue is served at (under a queue cap the priority levels are
+ * not served alike, above), so a burst ends on the slowest queue alone and a service builds backlog on the slow contexts while the fast ones idle.  With NBLS_POOL_BALANCE
+ * a context has at most K batches outstanding (default 2; environment NBLS_POOL_MAX_OUTSTANDING = 1 .. 8, anything else is NBLS_EINVAL at init) and a batch goes to the
+ * context with the fewest, ties round-robin behind the context used last -- a pool nobody waits on still visits its contexts in index order.  Completion is seen through
+ * one event per batch, recorded on the context's stream inside the library.  SUBMIT MAY NOW WAIT: with every context at K, nbls_pool_pairing_batch_dev -- and
+ * nbls_pool_next_slot, which makes the same choice in advance -- blocks (polling, 50 us between rounds, no device synchronisation) until a batch completes; a HIP error seen
+ * while waiting is returned as NBLS_EHIP (next_slot: -1) and nothing is submitted.  nbls_pool_next_slot latches its choice: called twice it returns the same slot, and the
+ * submit that follows uses it; a submit with no next_slot before it chooses for itself.  Pair the two calls from one thread at a time.  Without the flag nothing changes
+ * (strict round-robin, submit never waits); plain nbls_pool_init never sets it.  The bytes do not depend on it.  Environment: NBLS_POOL_BALANCE = 0 / 1 overrides the flag.
+ * nbls_pool_outstanding: *n = batches enqueued on context i whose completion has not been seen yet (0 .. K; always 0 without the flag). */
+#define NBLS_POOL_BALANCE 2u
 int nbls_pool_init_ex(int device_id, int depth /* 1 .. 64 */, unsigned flags, nbls_pool** out);
 int nbls_pool_stream_priority(nbls_pool* p, int i, int* priority);
+int nbls_pool_outstanding(nbls_pool* p, int i, int* n);
 void nbls_pool_destroy(nbls_pool* p);
 int nbls_pool_depth(const nbls_pool* p);
 nbls_ctx* nbls_pool_context(nbls_pool* p, int i);

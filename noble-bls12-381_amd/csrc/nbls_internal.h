@@ -385,6 +385,7 @@ static inline hipStream_t call_stream(nbls_ctx* ctx, void* stream) { return stre
 struct VerifyIn;
 int nbls_init_prio(int device_id, int prio, nbls_ctx** out);   // nbls_init with ctx->stream created at stream priority `prio` (0 = the default: what nbls_init passes)
 int nbls_stream_priority(nbls_ctx* ctx, int* prio);            // hipStreamGetPriority of ctx->stream
+int nbls_record_event(nbls_ctx* ctx, hipEvent_t ev);           // hipEventRecord(ev, ctx->stream): complete when everything enqueued on the context's stream so far is (the balanced pool's completion events; the stream itself stays inside the context)
 bool checked_mode();
 bool aot_enabled();
 int upload_program(nbls_ctx* ctx, DevProgram& d, const Program& p, const int k);

@@ -4,9 +4,10 @@
 //   * Miller product / verifyBatch: every device reduces its shard to ONE Fp12 partial (576 bytes, no final exponentiation), the partials
 //     are copied device-to-device (hipMemcpyPeer over xGMI) into the first device's gather buffer, which multiplies them and runs the one
 //     shared final exponentiation.  The exchange is 576 bytes per device -- pure latency -- so no collective library is involved.
-// nbls_pool_* (the end of this file): several contexts of ONE device fed round-robin -- the in-flight form of bench.py's headline, for C callers.
+// nbls_pool_* (the end of this file): several contexts of ONE device fed round-robin or, NBLS_POOL_BALANCE, by the batches each has outstanding -- the in-flight form of bench.py's headline, for C callers.
 // This layer uses only the public single-device ABI (include/nbls.h) plus HIP for the peer copies; the pool also creates its contexts through nbls_init_prio (runtime.cpp).
 #include <hip/hip_runtime.h>
+#include <chrono>
 #include <condition_variable>
 #include <cstdio>
 #include <cstdlib>
@@ -19,6 +20,7 @@
 #include "nbls.h"
 #include "config.h"
 #include "pool_levels.h"
+#include "pool_pick.h"
 
 #define EXPORT extern "C" __attribute__((visibility("default")))
 
@@ -284,14 +286,67 @@ EXPORT int nbls_hw_queues(int* set_by_library) {
 // (default + high, eight queues) give 3.01 M.  With depth <= queues nothing
 // changes (the 22-queue regime and a C caller on the library's default keep default-priority streams), and plain nbls_pool_init never asks for it.
 // NBLS_POOL_SPREAD = 0 / 1 overrides the caller's flag, NBLS_POOL_SPREAD_LEVELS caps L (2 = default and high only): A/B switches.  EXPERIMENTS.md, profiles/pool_priorities_ab.json.
+//
+// Who gets the next batch (NBLS_POOL_BALANCE).  Round-robin hands every context the same number of batches whatever the rate its queue is served at, and the host enqueues a
+// whole burst long before the second batch of any context completes: the streams on the high priority level run out of work a third of a region before the two streams
+// that share a queue do, and the region ends on one queue, one kernel at a time.  A balanced pool bounds the batches a context may have outstanding (K, default 2:
+// one running, one behind it, so the stream does not run dry while the host reacts within a batch's time; NBLS_POOL_MAX_OUTSTANDING = 1 .. 8) and gives a batch to the
+// context with the fewest, ties round-robin (pool_pick.h); with every context at K the submit WAITS until one retires.  Completion is seen through events: every context has
+// a ring of K events (no timing), one recorded on the context's stream behind each batch (nbls_record_event, runtime.cpp), retired oldest first when hipEventQuery reports
+// them complete.  The wait polls the oldest event of every context and sleeps 50 us between rounds with the pool's mutex released; a query that fails with anything but
+// "not ready" ends it (NBLS_EHIP).  nbls_pool_next_slot makes the choice -- wait included -- and latches it: the submit that follows uses the latched context, so the slot
+// announced is the slot used; one submitter at a time is assumed for that pairing of calls, as before.  Without the flag nothing changes: strict round-robin, no events,
+// submit never waits.  NBLS_POOL_BALANCE = 0 / 1 overrides the caller's flag (A/B switch).  EXPERIMENTS.md, profiles/pool_balance_ab.json.
 int nbls_init_prio(int device_id, int prio, nbls_ctx** out);      // runtime.cpp (nbls_internal.h)
 int nbls_stream_priority(nbls_ctx* ctx, int* prio);
-static const int POOL_SPREAD_LEVELS = 3;
-struct nbls_pool { std::vector<nbls_ctx*> ctx; std::mutex mu; size_t next = 0; int device = 0; };
-EXPORT void nbls_pool_destroy(nbls_pool* p) { if (!p) return; for (nbls_ctx* c : p->ctx) nbls_destroy(c); delete p; }
+int nbls_record_event(nbls_ctx* ctx, hipEvent_t ev);
+static const int POOL_SPREAD_LEVELS = 3, POOL_MAX_OUTSTANDING = 2;
+struct PoolRing { std::vector<hipEvent_t> ev; int head = 0; };      // the events of one context: ev[head] is the oldest outstanding one, outstanding[i] of them are recorded
+struct nbls_pool {
+  std::vector<nbls_ctx*> ctx; std::mutex mu; size_t next = 0; int device = 0;
+  // balanced pools only (all under `mu`)
+  bool balance = false; int K = 0;
+  std::vector<PoolRing> ring; std::vector<int> outstanding;
+  int last = -1, latched = -1;      // the context used last; the context nbls_pool_next_slot announced for the next submit (-1: none)
+};
+// retire, oldest first, the events that are complete; the counts are then what pool_pick sees
+static int pool_refresh(nbls_pool* p) {
+  for (size_t i = 0; i < p->ring.size(); i++) {
+    PoolRing& r = p->ring[i];
+    while (p->outstanding[i] > 0) {
+      const hipError_t e = hipEventQuery(r.ev[(size_t)r.head]);
+      if (e == hipErrorNotReady) { (void)hipGetLastError(); break; }
+      if (e != hipSuccess) return NBLS_EHIP;
+      r.head = (r.head + 1) % p->K; p->outstanding[i]--;
+    }
+  }
+  return NBLS_OK;
+}
+// the context of the next submit of a balanced pool: the latched one, or pool_pick's, waiting (mutex released) while every context is at K
+static int pool_choose(nbls_pool* p, std::unique_lock<std::mutex>& l, int* k) {
+  for (;;) {
+    if (p->latched >= 0) { *k = p->latched; return NBLS_OK; }
+    const int r = pool_refresh(p);
+    if (r) return r;
+    *k = nbls::pool_pick(p->outstanding.data(), (int)p->outstanding.size(), p->K, p->last);
+    if (*k >= 0) return NBLS_OK;
+    l.unlock();
+    std::this_thread::sleep_for(std::chrono::microseconds(50));
+    l.lock();
+  }
+}
+EXPORT void nbls_pool_destroy(nbls_pool* p) {
+  if (!p) return;
+  for (nbls_ctx* c : p->ctx) nbls_destroy(c);
+  for (PoolRing& r : p->ring) for (hipEvent_t e : r.ev) if (e) hipEventDestroy(e);
+  delete p;
+}
 EXPORT int nbls_pool_init(int device_id, int depth, nbls_pool** out) { return nbls_pool_init_ex(device_id, depth, 0, out); }
 EXPORT int nbls_pool_init_ex(int device_id, int depth, unsigned flags, nbls_pool** out) {
-  if (!out || depth < 1 || depth > 64 || (flags & ~NBLS_POOL_SPREAD_PRIORITIES)) return NBLS_EINVAL;
+  if (!out || depth < 1 || depth > 64 || (flags & ~(NBLS_POOL_SPREAD_PRIORITIES | NBLS_POOL_BALANCE))) return NBLS_EINVAL;
+  const long balance_env = nbls::env_long("NBLS_POOL_BALANCE", -1), max_out = nbls::env_long("NBLS_POOL_MAX_OUTSTANDING", POOL_MAX_OUTSTANDING);
+  if (max_out < 1 || max_out > 8) return NBLS_EINVAL;
+  const bool balance = balance_env < 0 ? (flags & NBLS_POOL_BALANCE) != 0 : balance_env != 0;
   const int q = nbls_hw_queues(nullptr), eff = q > 0 ? q : 4;
   std::vector<int> levels(1, 0);      // the stream priority of every level; one level of the default priority = no spreading
   const long spread_env = nbls::env_long("NBLS_POOL_SPREAD", -1);
@@ -328,20 +383,71 @@ EXPORT int nbls_pool_init_ex(int device_id, int depth, unsigned flags, nbls_pool
       nbls_set_tuning(c, NBLS_TUNE_INV_WIDE_MAX, 256);      // contexts kept busy side by side: instructions count, not one call's latency (nbls_internal.h inv_wide_max)
     }
   }
+  if (balance) {
+    p->balance = true; p->K = (int)max_out;
+    p->outstanding.assign((size_t)depth, 0); p->ring.resize((size_t)depth);
+    for (PoolRing& r : p->ring) {
+      r.ev.assign((size_t)p->K, nullptr);
+      for (hipEvent_t& e : r.ev) if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) { e = nullptr; (void)hipGetLastError(); nbls_pool_destroy(p); return NBLS_EHIP; }
+    }
+  }
   *out = p;
   return NBLS_OK;
 }
 EXPORT int nbls_pool_stream_priority(nbls_pool* p, int i, int* priority) { return p && i >= 0 && i < (int)p->ctx.size() ? nbls_stream_priority(p->ctx[i], priority) : NBLS_EINVAL; }
 EXPORT int nbls_pool_depth(const nbls_pool* p) { return p ? (int)p->ctx.size() : 0; }
 EXPORT nbls_ctx* nbls_pool_context(nbls_pool* p, int i) { return p && i >= 0 && i < (int)p->ctx.size() ? p->ctx[i] : nullptr; }
-// pairing(P_i, Q_i) for n device-resident pairs (index.ts:715-722) on the next context's own stream; returns at once.  *slot (optional) = index of the context used: a caller that
-// keeps calls in flight gives every slot its own output buffer (the pool does not order two calls that write the same memory).
+// pairing(P_i, Q_i) for n device-resident pairs (index.ts:715-722) on the next context's own stream; returns at once (a balanced pool: once a context is below its bound).
+// *slot (optional) = index of the context used: a caller that keeps calls in flight gives every slot its own output buffer (the pool does not order two calls that write the same memory).
 EXPORT int nbls_pool_pairing_batch_dev(nbls_pool* p, size_t n, const void* d_g1, const void* d_g2, int with_final_exp, void* d_out, int* slot) {
   if (!p || p->ctx.empty()) return NBLS_EINVAL;
+  if (p->balance) {
+    // choice, enqueue and event record under the mutex: the ring entry written is the one counted.  A failed wait, enqueue or record submits nothing more in this call;
+    // a batch enqueued without its event is not counted (its context merely looks less loaded than it is)
+    std::unique_lock<std::mutex> l(p->mu);
+    int k = -1;
+    int r = pool_choose(p, l, &k);
+    if (r) return r;
+    p->latched = -1; p->last = k;
+    if (slot) *slot = k;
+    r = nbls_pairing_batch_dev(p->ctx[(size_t)k], n, d_g1, d_g2, with_final_exp, d_out, nullptr);
+    if (r) return r;
+    PoolRing& ring = p->ring[(size_t)k];
+    r = nbls_record_event(p->ctx[(size_t)k], ring.ev[(size_t)((ring.head + p->outstanding[(size_t)k]) % p->K)]);
+    if (r) return r;
+    p->outstanding[(size_t)k]++;
+    return NBLS_OK;
+  }
   size_t k;
   { std::lock_guard<std::mutex> l(p->mu); k = p->next++ % p->ctx.size(); }
   if (slot) *slot = (int)k;
   return nbls_pairing_batch_dev(p->ctx[k], n, d_g1, d_g2, with_final_exp, d_out, nullptr);
 }
-EXPORT int nbls_pool_next_slot(nbls_pool* p) { if (!p || p->ctx.empty()) return -1; std::lock_guard<std::mutex> l(p->mu); return (int)(p->next % p->ctx.size()); }
-EXPORT int nbls_pool_synchronize(nbls_pool* p) { return p && !p->ctx.empty() ? nbls_device_synchronize(p->ctx[0]) : NBLS_EINVAL; }
+// the context the next submit will use.  Balanced pool: makes the choice now -- waiting like a submit when every context is at its bound -- and latches it, so a second call
+// returns the same slot and the submit that follows uses it; -1 when the wait ended on a HIP error (the submit will report it)
+EXPORT int nbls_pool_next_slot(nbls_pool* p) {
+  if (!p || p->ctx.empty()) return -1;
+  std::unique_lock<std::mutex> l(p->mu);
+  if (!p->balance) return (int)(p->next % p->ctx.size());
+  int k = -1;
+  if (pool_choose(p, l, &k)) return -1;
+  p->latched = k;
+  return k;
+}
+// batches enqueued on context i whose completion has not been seen yet (after a refresh); always 0 for a pool that does not balance
+EXPORT int nbls_pool_outstanding(nbls_pool* p, int i, int* n) {
+  if (!p || !n || i < 0 || i >= (int)p->ctx.size()) return NBLS_EINVAL;
+  if (!p->balance) { *n = 0; return NBLS_OK; }
+  std::lock_guard<std::mutex> l(p->mu);
+  const int r = pool_refresh(p);
+  if (r) return r;
+  *n = p->outstanding[(size_t)i];
+  return NBLS_OK;
+}
+EXPORT int nbls_pool_synchronize(nbls_pool* p) {
+  if (!p || p->ctx.empty()) return NBLS_EINVAL;
+  const int r = nbls_device_synchronize(p->ctx[0]);      // outside the mutex: other threads' submits and their waits go on meanwhile
+  if (r || !p->balance) return r;
+  std::lock_guard<std::mutex> l(p->mu);
+  return pool_refresh(p);      // everything recorded before the wait is complete now and retires; what another thread enqueued since stays counted
+}

@@ -311,6 +311,13 @@ int nbls_stream_priority(nbls_ctx* ctx, int* prio) {
   if (hipStreamGetPriority(ctx->stream, prio) != hipSuccess) { ctx->last_hip = (int)hipGetLastError(); return NBLS_EHIP; }
   return NBLS_OK;
 }
+int nbls_record_event(nbls_ctx* ctx, hipEvent_t ev) {
+  if (!ctx || !ev) return NBLS_EINVAL;
+  std::lock_guard<std::recursive_mutex> g_(ctx->mu);
+  HIPCHK(hipSetDevice(ctx->device));
+  HIPCHK(hipEventRecord(ev, ctx->stream));
+  return NBLS_OK;
+}
 // ctx->stream at stream priority `prio` (0 = the default priority: the stream hipStreamCreate made); the flags are hipStreamCreate's, so its ordering against the null stream is unchanged.
 // The side streams keep the default priority.  A pool that spreads its contexts over the priority levels creates them through this (nbls_multi.cpp).
 int nbls_init_prio(int device_id, int prio, nbls_ctx** out) {

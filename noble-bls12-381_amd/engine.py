@@ -167,6 +167,7 @@ def load_library():
     lib.nbls_pool_init.argtypes = [i32, i32, C.POINTER(vp)]
     lib.nbls_pool_init_ex.argtypes = [i32, i32, C.c_uint, C.POINTER(vp)]
     lib.nbls_pool_stream_priority.argtypes = [vp, i32, C.POINTER(i32)]
+    lib.nbls_pool_outstanding.argtypes = [vp, i32, C.POINTER(i32)]
     lib.nbls_pool_destroy.argtypes = [vp]
     lib.nbls_pool_depth.argtypes = [vp]
     lib.nbls_pool_context.restype = vp

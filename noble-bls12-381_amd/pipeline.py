@@ -1,4 +1,4 @@
-"""Batches in flight: D engine contexts on one GPU, each with its own HIP stream and scratch, fed round-robin (a thin wrapper over the C-ABI pool, nbls_pool_*).
+"""Batches in flight: D engine contexts on one GPU, each with its own HIP stream and scratch, each batch to the context with the fewest outstanding (a thin wrapper over the C-ABI pool, nbls_pool_*).
 
 A call of 4096 pairings fills the chip exactly one wavefront deep (1024 workgroups on 1024 SIMDs), and a lone wavefront reaches well under half of a SIMD's
 issue rate, so one batch at a time leaves most of the machine idle.  Consecutive batches are independent, so a service keeps several of
@@ -20,14 +20,17 @@ class PairingPipeline:
     fed round-robin); `engines` wraps the pool's contexts."""
 
     POOL_SPREAD_PRIORITIES = 1      # include/nbls.h NBLS_POOL_SPREAD_PRIORITIES
+    POOL_BALANCE = 2                # include/nbls.h NBLS_POOL_BALANCE
 
-    def __init__(self, device_id=0, depth=12, spread_priorities=True):
+    def __init__(self, device_id=0, depth=12, spread_priorities=True, balance=True):
         """spread_priorities: when `depth` exceeds the hardware queues in force (GPU_MAX_HW_QUEUES is a limit per stream priority), the contexts' streams are created
-        round-robin over the device's stream priority levels, so each gets a queue of its own; a no-op with a queue per stream (nbls_pool_init_ex)"""
+        round-robin over the device's stream priority levels, so each gets a queue of its own; a no-op with a queue per stream (nbls_pool_init_ex).
+        balance: a batch goes to the context with the fewest batches outstanding (at most two each; ties round-robin) instead of strictly round-robin, and `slot` / submit()
+        wait while every context is at that bound: contexts whose queues are served faster take more batches (NBLS_POOL_BALANCE)"""
         assert depth >= 1
         self.lib = load_library()
         h = C.c_void_p()
-        r = self.lib.nbls_pool_init_ex(device_id, depth, self.POOL_SPREAD_PRIORITIES if spread_priorities else 0, C.byref(h))
+        r = self.lib.nbls_pool_init_ex(device_id, depth, (self.POOL_SPREAD_PRIORITIES if spread_priorities else 0) | (self.POOL_BALANCE if balance else 0), C.byref(h))
         if r != 0:
             raise NblsError('nbls_pool_init_ex failed: %s (code %d)' % (self.lib.nbls_strerror(r).decode(), r))
         self.h = h
@@ -60,7 +63,8 @@ class PairingPipeline:
 
     @property
     def slot(self):
-        """index (0 .. depth-1) of the context the next submit() will use: callers keep one output buffer per slot"""
+        """index (0 .. depth-1) of the context the next submit() will use: callers keep one output buffer per slot (a balanced pool chooses -- and, with every context
+        at its bound, waits -- here, and the submit that follows uses that choice)"""
         return self.lib.nbls_pool_next_slot(self.h)
 
     def submit(self, n, d_g1, d_g2, d_out, with_final_exp=True):
